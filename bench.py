@@ -7,6 +7,8 @@ bench.py -- MC path-steps/s of the StochVolModels Monte Carlo hot path on MI355X
         --nproc-per-node N --master-addr 127.0.0.1 ... bench.py <same arguments>), one per visible GPU, RCCL backend
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W          (the driver's form: used as launched)
+    --dump-outputs DIR: after the timed steps, the prices and standard errors the last timed step returned are written to
+        DIR/prices.npy and DIR/stderrs.npy (float64, expiries x strikes); the same arguments give the same inputs.
 
 Workloads (BASELINE.json `configs`):
   c2  (default at --gpus 1; the configuration the headline metric is quoted on)  LogSV quadratic-drift MC,
@@ -121,7 +123,25 @@ def parse():
     ap.add_argument("--devices", default=None, help="--single-process: comma-separated device ids (default 0..N-1)")
     ap.add_argument("--no-secondary", action="store_true", help="N = 1: skip the `secondary` block (C1, C3, C5, f3)")
     ap.add_argument("--no-single-process-leg", action="store_true", help="N > 1: skip the single_process_route leg")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to DIR/prices.npy and DIR/stderrs.npy")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    if args.dump_outputs is not None:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
+    return args
+
+
+def dump_outputs(out_dir: str, prices, stderrs) -> None:
+    """--dump-outputs: the chain's prices and standard errors as the pricer returned them in the last timed step, float64,
+    one row per expiry (every workload has the same strikes count at each expiry).  The inputs are fixed by the arguments
+    (the timed steps' seeds are 20240602 + i), so two builds run with the same arguments can be compared output for output."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arrays in (("prices", prices), ("stderrs", stderrs)):
+        np.save(os.path.join(out_dir, name + ".npy"), np.stack([np.asarray(a, dtype=np.float64) for a in arrays]))
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -844,6 +864,8 @@ def single_process_main(args) -> int:
     for i in range(args.steps):
         prices, stderrs = step(i)
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs is not None:
+        dump_outputs(args.dump_outputs, prices, stderrs)
     info = get_multi_session(devices, n_total, len(wl["ttms"]), wl["n_strikes"], reduce=reduce).info()
     p777, _ = step(777)
     wd.disarm()
@@ -1044,6 +1066,8 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     final_barrier_ms = 1e3 * (time.perf_counter() - t_b)
+    if args.dump_outputs is not None and rank == 0:          # every rank holds the job's all-reduced prices
+        dump_outputs(args.dump_outputs, prices, stderrs)
     per_step_ms = 1e3 * np.diff(np.array([t0] + step_ends))
     kernel_ms = (eng.stop_kernel_timing() if eng._prof is not None else {}).get(kernel, [float("nan")])
     # the shader clock the LAST timed launch ran at, stamped inside the kernel (svmc_clock_probe_read)

@@ -796,6 +796,69 @@ def g_varswap():
     save("varswap", **out)
 
 
+# -- INTEGRATION.md route B: the reference's pricer objects with this package's Monte Carlo entry points rebound in ----------
+REBIND_TTMS, REBIND_FORWARDS, REBIND_DFS = np.array([0.08, 0.25]), np.array([1.0, 1.02]), np.array([0.995, 0.98])
+REBIND_STRIKES = (np.array([0.9, 1.0, 1.1]), np.array([0.85, 1.02, 1.2]))
+REBIND_TYPES = (np.array(["P", "C", "C"]), np.array(["IP", "IC", "C"]))
+REBIND_QVAR_STRIKES, REBIND_QVAR_TYPES = (np.array([0.1, 0.4]),) * 2, (np.array(["C", "P"]),) * 2
+
+
+def g_reference_rebind():
+    """What tests/test_reference_rebind.py holds this package to: the reference's LogSVPricer / HestonPricer objects, OptionChain,
+    parameter dataclasses and enums driving this package's module-level Monte Carlo entry points (rebound into the reference's
+    modules, the engine replaced by the CPU test double), and the reference's own fixed-randoms chain pricer on the randoms of its
+    own get_randoms_for_chain_valuation (the call its MC calibration objective makes, logsv_pricer.py:244-265)."""
+    import importlib
+
+    import stochvolmodels as ref
+    import stochvolmodels_amd as sv
+    import stochvolmodels_amd.pricers.heston_pricer as amd_heston
+    import stochvolmodels_amd.pricers.logsv_pricer as amd_logsv
+    sys.path.insert(0, os.path.dirname(HERE))
+    from fake_engine import FakeEngine
+    out = {}
+    # the reference's own fixed-randoms pricer, before anything is rebound
+    p = lp.LOGSV_BTC_PARAMS
+    W0s, W1s, dts = lp.get_randoms_for_chain_valuation(ttms=REBIND_TTMS, nb_path=400, nb_steps_per_year=100, seed=9)
+    pr, se = lp.logsv_mc_chain_pricer_fixed_randoms(
+        ttms=REBIND_TTMS, forwards=REBIND_FORWARDS, discfactors=REBIND_DFS, strikes_ttms=REBIND_STRIKES,
+        optiontypes_ttms=REBIND_TYPES, W0s=W0s, W1s=W1s, dts=dts, v0=p.sigma0, theta=p.theta, kappa1=p.kappa1,
+        kappa2=p.kappa2, beta=p.beta, volvol=p.volvol, vol_backbone_etas=p.get_vol_backbone_etas(ttms=REBIND_TTMS))
+    for i in range(len(REBIND_TTMS)):
+        out[f"fixed_W0_{i}"], out[f"fixed_W1_{i}"] = np.asarray(W0s[i]), np.asarray(W1s[i])
+        out[f"fixed_prices_{i}"], out[f"fixed_stderrs_{i}"] = np.asarray(pr[i]), np.asarray(se[i])
+    out["fixed_dts"] = np.array([float(d) for d in dts])
+    # the rebinding
+    engines = {}
+
+    def fake_get_engine(n_path, path_offset=0, device=None):
+        return engines.setdefault((n_path, path_offset), FakeEngine(n_path, path_offset))
+
+    amd_logsv.get_engine = amd_heston.get_engine = fake_get_engine
+    for name in ("logsv_mc_chain_pricer", "logsv_mc_chain_pricer_fixed_randoms", "simulate_logsv_x_vol_terminal"):
+        setattr(lp, name, getattr(amd_logsv, name))
+    hp.heston_mc_chain_pricer = amd_heston.heston_mc_chain_pricer
+    for vt_name, strikes, types, nb_steps in (("LOG_RETURN", REBIND_STRIKES, REBIND_TYPES, None),
+                                              ("Q_VAR", REBIND_QVAR_STRIKES, REBIND_QVAR_TYPES, 150)):
+        chain = ref.OptionChain(ttms=REBIND_TTMS, forwards=REBIND_FORWARDS, discfactors=REBIND_DFS, strikes_ttms=strikes,
+                                optiontypes_ttms=types, ids=np.array(["a", "b"]))
+        sv.set_seed(11)
+        pr, se = ref.LogSVPricer().model_mc_price_chain(option_chain=chain, params=lp.LOGSV_BTC_PARAMS, nb_path=777,
+                                                        nb_steps=nb_steps, variable_type=getattr(ref.VariableType, vt_name))
+        assert isinstance(pr, list) and len(pr) == 2 and pr[0].dtype == np.float64
+        for i in range(2):
+            out[f"logsv_{vt_name}_prices_{i}"], out[f"logsv_{vt_name}_stderrs_{i}"] = pr[i], se[i]
+    chain = ref.OptionChain(ttms=REBIND_TTMS, forwards=REBIND_FORWARDS, discfactors=REBIND_DFS, strikes_ttms=REBIND_STRIKES,
+                            optiontypes_ttms=REBIND_TYPES, ids=np.array(["a", "b"]))
+    sv.set_seed(3)
+    pr, se = ref.HestonPricer().model_mc_price_chain(option_chain=chain, params=hp.HestonParams(), nb_path=555)
+    for i in range(2):
+        out[f"heston_prices_{i}"], out[f"heston_stderrs_{i}"] = pr[i], se[i]
+    importlib.reload(lp)
+    importlib.reload(hp)
+    save("reference_rebind", **out)
+
+
 # -- f4 set-up: the kernel quadrature rule behind LogSvParams.approximate_kernel -------------------------
 def g_rough_kernel():
     from stochvolmodels.pricers.rough_logsv.rough_kernel import european_rule
@@ -837,3 +900,4 @@ if __name__ == "__main__":
     g_rough_kernel()
     g_varswap()
     g_calibration()
+    g_reference_rebind()

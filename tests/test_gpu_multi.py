@@ -247,10 +247,9 @@ def test_c_host_multi_example(sv, tmp_path):
     np.testing.assert_allclose(out3["heston_qe_prices"], out1["heston_qe_prices"], rtol=1e-12, atol=0)
 
 
-@pytest.mark.skipif("_device_count() < 2")
 def test_multi_session_over_rccl_on_distinct_devices(sv):
-    """with two or more GPUs in the box: the RCCL transport (ncclCommInitAll) against the host transport, bit for bit up to
-    the collective's own order of additions"""
+    """one shard on every GPU of the box (a one-rank communicator where there is one): the RCCL transport (ncclCommInitAll)
+    against the host transport, bit for bit up to the collective's own order of additions"""
     from stochvolmodels_amd.multi import MultiDeviceSession
     n_dev = _device_count()
     p = sv.LOGSV_BTC_PARAMS

@@ -614,6 +614,14 @@ def test_rccl_group_on_one_rank(oracle, tmp_path):
         np.testing.assert_array_equal(runs[0][key], runs[1][key], err_msg=key)
 
 
+def _device_count():
+    import ctypes as C
+    from stochvolmodels_amd import _lib
+    n = C.c_int(0)
+    _lib.check(_lib.load().svmc_device_count(C.byref(n)))
+    return n.value
+
+
 def _run_dist_workers(tmp_path, tag, world, port, extra_env, timeout=300):
     import os
     import subprocess
@@ -659,12 +667,14 @@ def test_rccl_through_the_c_abi_one_rank(oracle, tmp_path):
 
 @pytest.mark.parametrize("route", ["rccl", "torch"])
 def test_two_rccl_ranks_on_one_gpu(oracle, tmp_path, route):
-    """a REAL two-rank RCCL communicator, both ranks on this box's single GPU, through either route (libsvmc's C ABI /
-    torch.distributed "nccl").  RCCL may refuse two ranks on one device ("Duplicate GPU detected"): then there is
-    nothing to test on a 1-GPU box and the case is skipped; where it is allowed, both ranks must return the
-    single-process oracle result and the stream-ordered and host-synchronised runs must agree bit for bit."""
+    """a REAL two-rank RCCL communicator through either route (libsvmc's C ABI / torch.distributed "nccl"), rank r on device
+    r % devices.  With two devices or more both ranks must return the single-process oracle result and the stream-ordered and
+    host-synchronised runs must agree bit for bit.  With ONE device RCCL takes one rank per device: the run must then end
+    promptly on every rank with that refusal named -- libsvmc's own check ("RCCL needs one device per rank") on the C-ABI
+    route, RCCL's "invalid usage" (duplicate GPU) on the torch route -- not hang and not return numbers."""
     from test_dist_gloo import _expected
     exp = _expected(oracle)
+    shared = _device_count() < 2
     runs = []
     for k, strict in enumerate(("0", "1")):
         extra = dict(SVMC_DIST_STRICT_SYNC=strict)
@@ -672,11 +682,16 @@ def test_two_rccl_ranks_on_one_gpu(oracle, tmp_path, route):
                      else dict(SVMC_EXPECT_BACKEND="nccl"))
         ok, log, files = _run_dist_workers(tmp_path, f"{route}{strict}", 2, 29751 + 2 * k + (10 if route == "torch" else 0),
                                            extra, timeout=180)
-        if not ok:
+        if shared:
             low = log.lower()
-            if "duplicate gpu" in low or "invalid usage" in low or "[timeout]" in low or "nccl" in low or "rccl" in low:
-                pytest.skip("RCCL does not run two ranks on one device here: " + log.strip().splitlines()[-1][:200])
-            assert ok, log
+            assert not ok and "[timeout]" not in low, log[-3000:]
+            if route == "rccl":
+                assert "rccl needs one device per rank" in low, log[-3000:]
+            else:
+                assert "invalid usage" in low or "duplicate gpu" in low, log[-3000:]
+            assert not any(os.path.exists(f) for f in files), "a rank returned prices from a refused communicator"
+            return
+        assert ok, log
         got = [np.load(f) for f in files]
         for r in range(2):
             for key in got[r].files:
@@ -852,7 +867,8 @@ def test_c_host_rccl_example(sv, tmp_path):
                                        seed=seed)
     np.testing.assert_array_equal(np.concatenate(pr), one["heston_qe_prices"])
     np.testing.assert_array_equal(np.concatenate(sd), one["heston_qe_stderrs"])
-    # two ranks, one GPU
+    # two ranks, rank r on device r % devices.  On ONE device RCCL takes one rank per device: both ranks must then end
+    # promptly with RCCL's refusal (ncclCommInitRank: invalid usage) and print no result
     idf = str(tmp_path / "id2")
     procs = [subprocess.Popen([exe, "2", str(r), idf, str(n), str(seed)], stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                               text=True, env=env) for r in range(2)]
@@ -863,9 +879,13 @@ def test_c_host_rccl_example(sv, tmp_path):
         except subprocess.TimeoutExpired:
             for q in procs:
                 q.kill()
-            pytest.skip("two RCCL ranks on one device did not complete here")
-    if any(p.returncode != 0 for p in procs):
-        pytest.skip("RCCL does not run two ranks on one device here: " + outs[0][1].strip()[-200:] + outs[1][1].strip()[-200:])
+                q.communicate()
+            pytest.fail("two RCCL ranks did not finish within 120 s")
+    if _device_count() < 2:
+        for p, (out, err) in zip(procs, outs):
+            assert p.returncode != 0 and "invalid usage" in err and not any(ln.startswith("{") for ln in out.splitlines()), out + err
+        return
+    assert all(p.returncode == 0 for p in procs), outs
     two = [last_json(o[0]) for o in outs]
     for key in ("logsv_prices", "logsv_stderrs", "heston_qe_prices", "heston_qe_stderrs"):
         np.testing.assert_array_equal(two[0][key], two[1][key], err_msg=key)          # every rank: the job's result
@@ -2373,7 +2393,8 @@ def test_bench_line_two_ranks(tmp_path):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     run = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
-                          "--cpu-sample-paths", "4096"], capture_output=True, text=True, env=env, timeout=600, cwd=root)
+                          "--cpu-sample-paths", "4096", "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True,
+                         env=env, timeout=600, cwd=root)
     assert run.returncode == 0, run.stdout[-2000:] + run.stderr[-2000:]
     line = json.loads([ln for ln in run.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["steps"] == 4 and line["scaling"] == "weak" and line["dtype"] == "f64"
@@ -2391,6 +2412,15 @@ def test_bench_line_two_ranks(tmp_path):
     rr = line["rccl_route"]
     assert ("skipped" in rr) or (rr["value"] > 0 and line["rccl_ranks_seen"] == 2 and rr["prices_equal_torch_route"] is True)
     _check_self_proving_fields(line, 2)
+    _check_dumped_outputs(tmp_path / "out", line, 8)
+
+
+def _check_dumped_outputs(out_dir, line, expiries):
+    """--dump-outputs: the last timed step's prices and standard errors, float64, expiries x strikes, as the line quotes them"""
+    prices, stderrs = np.load(out_dir / "prices.npy"), np.load(out_dir / "stderrs.npy")
+    assert prices.dtype == stderrs.dtype == np.float64 and prices.shape == stderrs.shape == (expiries, 21)
+    assert list(prices[0, :3]) == line["prices_head"] and list(stderrs[0, :3]) == line["stderr_head"]
+    assert np.all(np.isfinite(prices)) and np.all(stderrs > 0)
 
 
 def _check_self_proving_fields(line, world):
@@ -2407,7 +2437,7 @@ def _check_self_proving_fields(line, world):
     assert 500.0 < r["clock_mhz_in_kernel"] <= 2500.0 and r["frac"] <= r["frac_at_sustained_clock"] < 1.05
 
 
-def test_bench_line_one_gpu():
+def test_bench_line_one_gpu(tmp_path):
     """the default single-GPU line (C2) at a few steps: the fused C driver's leg (bit-equal prices, interleaved with the Python
     route), the clock measured inside the kernel and the fraction against it, the counters only when they are this library's"""
     import json
@@ -2418,7 +2448,8 @@ def test_bench_line_one_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "SVMC_DIST_BACKEND")}
     env["SVMC_BENCH_PREWARM"] = "3"
     run = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "5", "--warmup", "2", "--cpu-sample-paths",
-                          "4096", "--no-streamed", "--no-extra-legs"], capture_output=True, text=True, env=env, timeout=600, cwd=root)
+                          "4096", "--no-streamed", "--no-extra-legs", "--dump-outputs", str(tmp_path / "out")], capture_output=True,
+                         text=True, env=env, timeout=600, cwd=root)
     assert run.returncode == 0, run.stdout[-2000:] + run.stderr[-2000:]
     line = json.loads([ln for ln in run.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["n_gpus"] == 1 and line["config"]["workload"].startswith("C2") and line["config"]["paths_total"] == 1 << 20
@@ -2430,30 +2461,25 @@ def test_bench_line_one_gpu():
     assert r["frac"] <= r["frac_at_sustained_clock"] < 1.0 and r["frac_at_sustained_clock"] <= r["frac_in_stream_at_sustained_clock"] < 1.1
     assert ("counters" in r) == (r["insts_per_wave_step_counters"] is not None)
     assert line["cpu_baseline"]["kind"] == "port" and "self_check_failed" not in line
+    assert line["steps"] == 5 and line["ms_per_step"] > 0
+    _check_dumped_outputs(tmp_path / "out", line, 1)
 
 
-def test_bench_line_eight_ranks_share_one_gpu():
-    """the rehearsal of the driver's 8-GPU run on the hardware there is: `python bench.py --gpus 8` starts its own eight
-    ranks (gloo: they share this GPU), 8-way shard_range, eight local ranks -> devices, eight torch.distributed.run
-    children; the line must carry the self-proving fields and the command must return 0"""
-    import json
-    import os
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, SVMC_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", SVMC_BENCH_PREWARM="2")
-    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
-        env.pop(k, None)
-    run = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--paths-per-gpu", "131072",
-                          "--steps", "3", "--warmup", "1", "--no-cpu-baseline"], capture_output=True, text=True, env=env,
-                         timeout=900, cwd=root)
-    assert run.returncode == 0, run.stdout[-2000:] + run.stderr[-3000:]
-    line = json.loads([ln for ln in run.stdout.splitlines() if ln.startswith("{")][-1])
-    assert line["n_gpus"] == 8 and line["config"]["paths_total"] == 8 * 131072 and line["config"]["parallelism"] == "path-sharded x8"
+def test_bench_line_three_ranks_share_one_gpu():
+    """the rehearsal of the driver's N-GPU run on the hardware there is: `python bench.py --gpus 3` starts its own three
+    ranks (gloo: they share this GPU), 3-way shard_range, three local ranks -> devices, three torch.distributed.run
+    children; the line must carry the self-proving fields and the command must return 0.  Three ranks, and no
+    single-process child: with this test process, bench.py's launcher and the torch.distributed.run agent that is six
+    processes with the GPU open, the most a shared machine allows (the eight-shard job runs in ONE process in
+    test_bench_single_process_mode and test_c4_eight_shards_of_full_size_on_one_device)"""
+    run, line = _run_bench(["--gpus", "3", "--paths-per-gpu", "131072", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
+                            "--no-single-process-leg"], dict(SVMC_DIST_BACKEND="gloo", SVMC_BENCH_PREWARM="2"))
+    assert run.returncode == 0 and line is not None, run.stdout[-2000:] + run.stderr[-3000:]
+    assert line["n_gpus"] == 3 and line["config"]["paths_total"] == 3 * 131072 and line["config"]["parallelism"] == "path-sharded x3"
     assert line["self_launched"] is True and line["backend"] == "gloo" and "skipped" in line["rccl_route"]
-    assert line["n1_share_value"] > 0 and line["c4_full_one_gpu"]["paths"] == 8 * 131072
-    _check_self_proving_fields(line, 8)
-    print("8 ranks on one GPU: sharded vs one-GPU job", line["sharded_vs_one_gpu_max_rel_dev"],
+    assert line["n1_share_value"] > 0 and line["c4_full_one_gpu"]["paths"] == 3 * 131072
+    _check_self_proving_fields(line, 3)
+    print("3 ranks on one GPU: sharded vs one-GPU job", line["sharded_vs_one_gpu_max_rel_dev"],
           "kernel ms over ranks", line["kernel_ms_over_ranks"])
 
 
@@ -2491,17 +2517,36 @@ def test_bench_refuses_more_ranks_than_gpus():
     assert run.returncode != 0 and "GPU(s) visible" in (run.stdout + run.stderr)
 
 
-def _run_bench(argv, env_extra, timeout=900):
+def _run_bench(argv, env_extra, timeout=900, torchrun_ranks=None):
+    """bench.py as its own command (it self-launches its ranks at --gpus N > 1), or with torchrun_ranks = N in the driver's
+    form: its N ranks started by `python -m torch.distributed.run` directly.  The command runs in a session of its own so that
+    a timeout ends its ranks too, not only the process this test started."""
     import json
     import os
+    import signal
+    import socket
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT",
                                                             "SVMC_DIST_BACKEND")}
     env.update(HSA_ENABLE_IPC_MODE_LEGACY="0", **env_extra)
-    run = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + argv, capture_output=True, text=True, env=env,
-                         timeout=timeout, cwd=root)
+    cmd = [sys.executable, os.path.join(root, "bench.py")] + argv
+    if torchrun_ranks is not None:
+        with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as sk:
+            sk.bind(("127.0.0.1", 0))
+            port = sk.getsockname()[1]
+        cmd[1:1] = ["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(torchrun_ranks), "--master-addr",
+                    "127.0.0.1", "--master-port", str(port)]
+    proc = subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env, cwd=root,
+                            start_new_session=True)
+    try:
+        out, err = proc.communicate(timeout=timeout)
+    except subprocess.TimeoutExpired:
+        os.killpg(proc.pid, signal.SIGKILL)
+        proc.communicate()
+        raise
+    run = subprocess.CompletedProcess(cmd, proc.returncode, out, err)
     lines = [ln for ln in run.stdout.splitlines() if ln.startswith("{")]
     return run, (json.loads(lines[-1]) if lines else None)
 
@@ -2511,10 +2556,13 @@ def test_bench_ladder_lands_on_gloo_with_a_number(fault):
     """first contact with a node whose RCCL does not come up must still produce a line: two ranks (sharing this GPU), the nccl
     rung failing in its probe children -- by an exception ("nccl_init") or by HANGING until the parent kills the child
     ("nccl_hang") -- the rccl rung failing on its own (two ranks on one device), the job running on the gloo rung: exit status 0,
-    a number, the rung and the reasons in the line, the self-proving fields intact, and the single-process route beside it"""
+    a number, the rung and the reasons in the line, the self-proving fields intact, and the single-process route beside it.
+    The ranks are started in the driver's form (torch.distributed.run, no bench.py launcher around them): while the rccl rung is
+    probed, this test process, the agent, the two ranks and their two probe children are the six processes with the GPU open
+    that a shared machine allows"""
     run, line = _run_bench(["--gpus", "2", "--paths-per-gpu", "65536", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"],
-                           dict(SVMC_BENCH_SHARE_DEVICES="1", SVMC_DIST_FORCE_PROBE="1", SVMC_BENCH_FAULT=fault, SVMC_BENCH_PREWARM="1",
-                                SVMC_BENCH_INIT_TIMEOUT="20" if fault == "nccl_hang" else "90"))
+                           dict(SVMC_DIST_FORCE_PROBE="1", SVMC_BENCH_FAULT=fault, SVMC_BENCH_PREWARM="1",
+                                SVMC_BENCH_INIT_TIMEOUT="20" if fault == "nccl_hang" else "90"), torchrun_ranks=2)
     assert run.returncode == 0 and line is not None, run.stdout[-1500:] + run.stderr[-3000:]
     assert line["n_gpus"] == 2 and line["value"] > 0 and line["comm"] == "TorchComm" and line["backend"] == "gloo"
     lad = line["comm_ladder"]

@@ -1,30 +1,22 @@
 """
-INTEGRATION.md, route B, exercised for real: the reference package (imported from /root/reference in the build
-container, NumPy mode through the identity-njit stand-ins) with its module-level Monte Carlo entry points rebound to
-this package's, driven through the REFERENCE's own LogSVPricer / HestonPricer objects, OptionChain, parameter
-dataclasses and enums.  The engine is the CPU test double (no GPU here), so what this pins is the host seam: foreign
-types in, reference-shaped results out.  Skipped where the reference checkout is absent (the GPU box).
+INTEGRATION.md, route B: the reference package with its module-level Monte Carlo entry points rebound to this package's,
+driven through the REFERENCE's own LogSVPricer / HestonPricer objects, OptionChain, parameter dataclasses and enums.
+What that route returned is recorded in tests/golden/reference_rebind.npz (tests/golden/make_golden.py g_reference_rebind,
+run against the unmodified reference with the engine replaced by the CPU test double); this package's own pricer objects,
+on the same double, must return it bit for bit.  The fixture also holds the reference's own fixed-randoms chain pricer on
+the randoms of its get_randoms_for_chain_valuation -- the call its MC calibration objective makes.
 """
-import os
-import sys
-
 import numpy as np
 import pytest
 
-REF = "/root/reference/src"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present")
+TTMS, FORWARDS, DFS = np.array([0.08, 0.25]), np.array([1.0, 1.02]), np.array([0.995, 0.98])
+STRIKES = (np.array([0.9, 1.0, 1.1]), np.array([0.85, 1.02, 1.2]))
+TYPES = (np.array(["P", "C", "C"]), np.array(["IP", "IC", "C"]))
+QVAR_STRIKES, QVAR_TYPES = (np.array([0.1, 0.4]),) * 2, (np.array(["C", "P"]),) * 2
 
 
 @pytest.fixture()
-def rebound(monkeypatch, oracle):
-    here = os.path.dirname(os.path.abspath(__file__))
-    for p in (os.path.join(here, "golden", "_shims"), REF, here):
-        if p not in sys.path:
-            monkeypatch.syspath_prepend(p)
-    import stochvolmodels as ref
-    import stochvolmodels.pricers.heston_pricer as ref_heston
-    import stochvolmodels.pricers.logsv_pricer as ref_logsv
-    import stochvolmodels.utils.mc_payoffs as ref_payoffs
+def sv(monkeypatch, oracle):
     import stochvolmodels_amd as sv
     import stochvolmodels_amd.pricers.heston_pricer as amd_heston
     import stochvolmodels_amd.pricers.logsv_pricer as amd_logsv
@@ -36,70 +28,49 @@ def rebound(monkeypatch, oracle):
 
     monkeypatch.setattr(amd_logsv, "get_engine", fake_get_engine)
     monkeypatch.setattr(amd_heston, "get_engine", fake_get_engine)
-    for name in ("logsv_mc_chain_pricer", "logsv_mc_chain_pricer_fixed_randoms", "simulate_logsv_x_vol_terminal"):
-        monkeypatch.setattr(ref_logsv, name, getattr(amd_logsv, name))
-    monkeypatch.setattr(ref_heston, "heston_mc_chain_pricer", amd_heston.heston_mc_chain_pricer)
-    return ref, sv, ref_logsv, ref_heston, ref_payoffs
+    return sv
 
 
-def _chains(ref, sv):
-    ttms, fw, df = np.array([0.08, 0.25]), np.array([1.0, 1.02]), np.array([0.995, 0.98])
-    kk = (np.array([0.9, 1.0, 1.1]), np.array([0.85, 1.02, 1.2]))
-    ty = (np.array(["P", "C", "C"]), np.array(["IP", "IC", "C"]))
-    mk = lambda mod: mod.OptionChain(ttms=ttms, forwards=fw, discfactors=df, strikes_ttms=kk, optiontypes_ttms=ty,   # noqa: E731
-                                     ids=np.array(["a", "b"]))
-    return mk(ref), mk(sv)
+def _chain(sv, strikes=STRIKES, types=TYPES):
+    return sv.OptionChain(ttms=TTMS, forwards=FORWARDS, discfactors=DFS, strikes_ttms=strikes, optiontypes_ttms=types,
+                          ids=np.array(["a", "b"]))
 
 
-def test_reference_pricer_objects_drive_the_rebound_path(rebound):
-    ref, sv, ref_logsv, ref_heston, _ = rebound
-    chain_ref, chain_amd = _chains(ref, sv)
-    # LogSV: the reference's pricer, params, chain and enum; the nb_steps default rule included
-    for vt_name in ("LOG_RETURN", "Q_VAR"):
-        kw = dict(nb_path=777, nb_steps=None if vt_name == "LOG_RETURN" else 150)
-        chains = (chain_ref, chain_amd)
-        if vt_name == "Q_VAR":
-            q = dict(strikes_ttms=(np.array([0.1, 0.4]),) * 2, optiontypes_ttms=(np.array(["C", "P"]),) * 2)
-            chains = tuple(m.OptionChain(ttms=c.ttms, forwards=c.forwards, discfactors=c.discfactors, ids=c.ids, **q)
-                           for m, c in ((ref, chain_ref), (sv, chain_amd)))
+def test_reference_pricer_objects_drive_the_rebound_path(sv, golden):
+    g = golden("reference_rebind")
+    # LogSV: the nb_steps default rule included
+    for vt_name, strikes, types, nb_steps in (("LOG_RETURN", STRIKES, TYPES, None), ("Q_VAR", QVAR_STRIKES, QVAR_TYPES, 150)):
         sv.set_seed(11)
-        a, ea = ref.LogSVPricer().model_mc_price_chain(option_chain=chains[0], params=ref_logsv.LOGSV_BTC_PARAMS,
-                                                       variable_type=getattr(ref.VariableType, vt_name), **kw)
-        sv.set_seed(11)
-        b, eb = sv.LogSVPricer().model_mc_price_chain(option_chain=chains[1], params=sv.LOGSV_BTC_PARAMS,
-                                                      variable_type=getattr(sv.VariableType, vt_name), **kw)
-        assert isinstance(a, list) and len(a) == 2 and a[0].dtype == np.float64
-        for x, y in zip(list(a) + list(ea), list(b) + list(eb)):
-            np.testing.assert_array_equal(x, y)
-    # Heston through the reference's HestonPricer
+        b, eb = sv.LogSVPricer().model_mc_price_chain(option_chain=_chain(sv, strikes, types), params=sv.LOGSV_BTC_PARAMS,
+                                                      nb_path=777, nb_steps=nb_steps, variable_type=getattr(sv.VariableType, vt_name))
+        assert isinstance(b, list) and len(b) == 2 and b[0].dtype == np.float64
+        for i in range(2):
+            np.testing.assert_array_equal(b[i], g[f"logsv_{vt_name}_prices_{i}"])
+            np.testing.assert_array_equal(eb[i], g[f"logsv_{vt_name}_stderrs_{i}"])
+    # Heston
     sv.set_seed(3)
-    a, _ = ref.HestonPricer().model_mc_price_chain(option_chain=chain_ref, params=ref_heston.HestonParams(), nb_path=555)
-    sv.set_seed(3)
-    b, _ = sv.HestonPricer().model_mc_price_chain(option_chain=chain_amd, params=sv.HestonParams(), nb_path=555)
-    for x, y in zip(a, b):
-        np.testing.assert_array_equal(x, y)
-    # the reference's error contract survives the rebinding
+    b, eb = sv.HestonPricer().model_mc_price_chain(option_chain=_chain(sv), params=sv.HestonParams(), nb_path=555)
+    for i in range(2):
+        np.testing.assert_array_equal(b[i], g[f"heston_prices_{i}"])
+        np.testing.assert_array_equal(eb[i], g[f"heston_stderrs_{i}"])
+    # the reference's error contract
     with pytest.raises(NotImplementedError):
-        ref.LogSVPricer().model_mc_price_chain(option_chain=chain_ref, params=ref_logsv.LOGSV_BTC_PARAMS, nb_path=64,
-                                               variable_type=ref.VariableType.SIGMA)
+        sv.LogSVPricer().model_mc_price_chain(option_chain=_chain(sv), params=sv.LOGSV_BTC_PARAMS, nb_path=64,
+                                              variable_type=sv.VariableType.SIGMA)
 
 
-def test_reference_fixed_randoms_objective_path(rebound, oracle):
+def test_reference_fixed_randoms_objective_path(sv, golden):
     """the call the reference's MC calibration objective makes (logsv_pricer.py:244-265): its own
-    get_randoms_for_chain_valuation output handed to the rebound fixed-randoms pricer, against the reference's own
+    get_randoms_for_chain_valuation output handed to this package's fixed-randoms pricer, against the reference's own
     pricer on the same randoms"""
-    ref, sv, ref_logsv, _, _ = rebound
-    import importlib
-    import stochvolmodels.pricers.logsv_pricer as fresh
-    chain_ref, _ = _chains(ref, sv)
-    p = ref_logsv.LOGSV_BTC_PARAMS
-    W0s, W1s, dts = fresh.get_randoms_for_chain_valuation(ttms=chain_ref.ttms, nb_path=400, nb_steps_per_year=100, seed=9)
-    kw = dict(ttms=chain_ref.ttms, forwards=chain_ref.forwards, discfactors=chain_ref.discfactors,
-              strikes_ttms=chain_ref.strikes_ttms, optiontypes_ttms=chain_ref.optiontypes_ttms, W0s=W0s, W1s=W1s, dts=dts,
-              v0=p.sigma0, theta=p.theta, kappa1=p.kappa1, kappa2=p.kappa2, beta=p.beta, volvol=p.volvol,
-              vol_backbone_etas=p.get_vol_backbone_etas(ttms=chain_ref.ttms))
-    got, got_e = ref_logsv.logsv_mc_chain_pricer_fixed_randoms(**kw)            # rebound -> this package
-    original = importlib.reload(importlib.import_module("stochvolmodels.pricers.logsv_pricer"))
-    want, want_e = original.logsv_mc_chain_pricer_fixed_randoms(**kw)           # the reference's own NumPy-mode code
-    for x, y in zip(list(got) + list(got_e), list(want) + list(want_e)):
-        np.testing.assert_allclose(x, y, rtol=1e-12, atol=1e-15)
+    from stochvolmodels_amd.pricers import logsv_pricer
+    g = golden("reference_rebind")
+    p = sv.LOGSV_BTC_PARAMS
+    got, got_e = logsv_pricer.logsv_mc_chain_pricer_fixed_randoms(
+        ttms=TTMS, forwards=FORWARDS, discfactors=DFS, strikes_ttms=STRIKES, optiontypes_ttms=TYPES,
+        W0s=[g["fixed_W0_0"], g["fixed_W0_1"]], W1s=[g["fixed_W1_0"], g["fixed_W1_1"]], dts=list(g["fixed_dts"]), v0=p.sigma0,
+        theta=p.theta, kappa1=p.kappa1, kappa2=p.kappa2, beta=p.beta, volvol=p.volvol,
+        vol_backbone_etas=p.get_vol_backbone_etas(ttms=TTMS))
+    for i in range(2):
+        np.testing.assert_allclose(got[i], g[f"fixed_prices_{i}"], rtol=1e-12, atol=1e-15)
+        np.testing.assert_allclose(got_e[i], g[f"fixed_stderrs_{i}"], rtol=1e-12, atol=1e-15)
