@@ -574,6 +574,33 @@ SVMC_API int svmc_mgf_vanilla_slice(const double *phi, const double *log_mgf, si
                                     const double *strikes_host, size_t n_strikes, double *capped,
                                     svmc_stream_t stream);
 
+/* ---- Hawkes jump-diffusion: pricers/hawkes_jd_pricer.py (F. Liu, N. Packham, A. Sepp 2025) ------------------------
+ * params_host: SVMC_HAWKESJD_PARAMS doubles in the order of HawkesJDParams' fields = {mu, sigma, shift_p, mean_p, shift_m,
+ * mean_m, lambda_p, theta_p, kappa_p, beta1_p, beta2_p, lambda_m, theta_m, kappa_m, beta1_m, beta2_m}; need sigma >= 0,
+ * 0 <= mean_p < 1, mean_m <= 0.  Random streams 6 and 7 (src header svmc_rng.h): indexed by (global path id, chain-global step).
+ *   svmc_hawkesjd_terminal_rng  simulate_hawkesjd_terminal (:715-779): nb_steps of dt on the state (x, lambda_p,
+ *                               lambda_m) in place; the first step has the chain-global index step_offset.
+ *   svmc_hawkesjd_chain_price   hawkesjd_mc_chain_pricer (:644-711) on a session: state (0, lambda_p, lambda_m) carried
+ *                               over the expiries, per slice int((T_i - T_(i-1)) nb_steps_per_year) + 1 steps (the
+ *                               reference hard-wires 1800 per year), payoffs as svmc_logsv_chain_price.  The session's
+ *                               state arrays hold (x, lambda_p, lambda_m) afterwards.  variable_type SVMC_LOG_RETURN only.
+ *                               With a communicator attached it issues the same two all-reduces.
+ *   svmc_hawkesjd_mgf_grid      compute_hawkes_a_mgf_grid (:518-546): per grid point the three Riccati ODEs of
+ *                               solve_ode_for_a (:582-640) over ttm from a[] ([n_grid][3] complex, in: the previous expiry's,
+ *                               out: this one's) with DOP853 at rtol / atol; log_mgf = a0 + a1 lambda_p + a2 lambda_m. */
+#define SVMC_HAWKESJD_PARAMS 16
+SVMC_API int svmc_hawkesjd_terminal_rng(double *x, double *lambda_p, double *lambda_m, size_t n_path, int nb_steps,
+                                        double dt, const double *params_host, uint64_t seed, uint32_t call_id,
+                                        uint64_t path_offset, uint32_t step_offset, svmc_stream_t stream);
+SVMC_API int svmc_hawkesjd_chain_price(svmc_session_t session, const double *ttms_host, const double *forwards_host,
+                                       const double *discfactors_host, int n_expiries, const double *strikes_host,
+                                       const int8_t *types_host, const size_t *strike_offsets_host,
+                                       const double *params_host, int nb_steps_per_year, int variable_type, uint64_t seed,
+                                       uint32_t call_id, double *prices_host, double *stderrs_host);
+SVMC_API int svmc_hawkesjd_mgf_grid(const double *phi, const double *psi, size_t n_grid, double ttm,
+                                    const double *params_host, double *a, double *log_mgf, double rtol, double atol,
+                                    svmc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

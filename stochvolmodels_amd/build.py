@@ -25,9 +25,11 @@ LIB = os.path.join(PKG, "libsvmc.so")
 # line stale when the library it loaded is not the one the histogram describes
 ISA_JSON = os.path.join(PKG, "libsvmc.isa.json")
 ISA_KERNELS = ("logsv_rng_kernel", "logsv_chain_rng_kernel", "heston_rng_kernelILi0", "heston_rng_kernelILi1", "heston_rng_kernelILi2",
-               "logsv_rng_lat_kernelILi4ELi4ELi256", "logsv_chain_rng_lat_kernelILi4ELi4ELi256")
-SOURCES = ("svmc_runtime.hip", "svmc_kernels.hip", "svmc_analytic.hip", "svmc_chain.hip", "svmc_comm.hip", "svmc_multi.hip")
-HEADERS = ("svmc_internal.h", "svmc_models.h", "svmc_rng.h", "svmc_math.h", "svmc_log_table.h", "svmc_icdf_table.h", "svmc_black.h", "svmc_ode.h", "svmc_dop853.h")
+               "logsv_rng_lat_kernelILi4ELi4ELi256", "logsv_chain_rng_lat_kernelILi4ELi4ELi256", "hawkesjd_chain_rng_kernel")
+SOURCES = ("svmc_runtime.hip", "svmc_kernels.hip", "svmc_analytic.hip", "svmc_chain.hip", "svmc_comm.hip", "svmc_multi.hip",
+           "svmc_hawkes.hip")
+HEADERS = ("svmc_internal.h", "svmc_models.h", "svmc_rng.h", "svmc_math.h", "svmc_log_table.h", "svmc_icdf_table.h", "svmc_black.h", "svmc_ode.h", "svmc_dop853.h",
+           "svmc_slice.h")
 ARCH = "gfx950"
 
 
@@ -88,14 +90,15 @@ def kernel_metadata(asm_dir: str) -> dict:
     return out
 
 
-def write_isa_json(asm_path: str) -> None:
-    """per-kernel instruction histogram of the time loops (tools/isa_histogram.py) + the library's hash"""
+def write_isa_json(asm_path: str, *more_asm: str) -> None:
+    """per-kernel instruction histogram of the time loops (tools/isa_histogram.py) + the library's hash; the kernels are looked
+    up in the assembly of every translation unit given"""
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     try:
         import isa_histogram
     finally:
         sys.path.pop(0)
-    text = open(asm_path).read()
+    text = "\n".join(open(p).read() for p in (asm_path,) + more_asm)
     kernels = {}
     for name in ISA_KERNELS:
         try:
@@ -122,7 +125,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
             print(res.stderr)
         asm = os.path.join(tmp, "svmc_kernels-hip-amdgcn-amd-amdhsa-gfx950.s")
         try:
-            write_isa_json(asm)
+            write_isa_json(asm, os.path.join(tmp, "svmc_hawkes-hip-amdgcn-amd-amdhsa-gfx950.s"))
         except Exception as exc:                             # the histogram is measurement metadata, never a build failure
             if verbose:
                 print("isa histogram skipped:", exc)

@@ -1007,6 +1007,38 @@ int svmc_heston_chain_price(svmc_session_t session, const double *ttms_host, con
     return reduce_and_finalize(s, c, variable_type, prices_host, stderrs_host, true);
 }
 
+int svmc_hawkesjd_chain_price(svmc_session_t session, const double *ttms_host, const double *forwards_host,
+                              const double *discfactors_host, int n_expiries, const double *strikes_host,
+                              const int8_t *types_host, const size_t *strike_offsets_host, const double *params_host,
+                              int nb_steps_per_year, int variable_type, uint64_t seed, uint32_t call_id, double *prices_host,
+                              double *stderrs_host)
+{
+    const char *fn = "svmc_hawkesjd_chain_price";
+    Session *s = reinterpret_cast<Session *>(session);
+    const ChainView c = {n_expiries, ttms_host, forwards_host, discfactors_host, strikes_host, types_host, strike_offsets_host};
+    if (int rc = check_chain(fn, s, c, variable_type, prices_host, stderrs_host)) return rc;
+    if (variable_type != SVMC_LOG_RETURN)      // the reference would price the log-return as a variance (:701-707)
+        return fail(SVMC_ERR_UNSUPPORTED_VARIABLE, "svmc_hawkesjd_chain_price: LOG_RETURN only");
+    SVMC_REQUIRE(params_host != nullptr, "svmc_hawkesjd_chain_price: null params");
+    SVMC_REQUIRE(nb_steps_per_year > 0, "svmc_hawkesjd_chain_price: nb_steps_per_year must be positive");
+    double t0 = 0.0;
+    std::vector<int> nbs(c.m);
+    std::vector<double> dts(c.m);
+    for (int i = 0; i < c.m; ++i) {                                                                       // :680-700
+        time_grid(c.ttms[i] - t0, nb_steps_per_year, nbs[i], dts[i]);
+        t0 = c.ttms[i];
+    }
+    // the session's vol / qvar slots hold lambda_p / lambda_m
+    const bool pending = c.m <= MAX_FUSED_SLICES;
+    stepping_begin(s);
+    if (int rc = hawkes_step_partials(params_host, s->x, s->vol, s->qvar, s->n_path, c.m, nbs.data(), dts.data(), c.forwards, seed,
+                                      call_id, s->path_offset, s->snap, pending ? nullptr : s->spot, pending ? s->spot_ws : s->ws,
+                                      pending ? s->spot_ws_bytes : s->ws_bytes, s->stream))
+        return rc;
+    stepping_end(s);
+    return reduce_and_finalize(s, c, variable_type, prices_host, stderrs_host, pending);
+}
+
 int svmc_session_state(svmc_session_t session, double *x_host, double *vol_host, double *qvar_host)
 {
     Session *s = reinterpret_cast<Session *>(session);

@@ -1,0 +1,424 @@
+// svmc_hawkes.hip -- the Hawkes jump-diffusion on gfx950 (pricers/hawkes_jd_pricer.py of the reference; F. Liu, N. Packham,
+// A. Sepp 2025): the Monte Carlo generator and the coefficient-ODE transform grid.
+//
+//   hawkesjd_chain_rng_kernel  one lane per path, the state (x, lambda_p, lambda_m) in fp64 registers, ALL expiries of a chain in
+//                              one launch: the step of simulate_hawkesjd_terminal (:715-779) in its order, the slice epilogue of
+//                              svmc_slice.h per expiry (snapshot + per-wave spot partials for the chain payoff tail)
+//   hawkesjd_rng_kernel        the same body for one slice on caller-owned state (simulate_hawkesjd_terminal)
+//   hawkes_mgf_grid_kernel     one lane per transform-grid point: the three complex Riccati ODEs of solve_ode_for_a (:582-640)
+//                              with the DOP853 pair of svmc_dop853.h and per-point step control; log E = a0 + a1 lp + a2 lm
+//
+// Randoms (svmc_rng.h, streams 6 and 7): step s of path p is ONE Philox call of stream 6 at counter index s (the chain-global
+// step): word 0 -> the N(0,1) of the diffusion (normal_icdf32), words 1 and 2 -> u_p, u_m = (r + 1/2) 2^-32, word 3 unused.
+// A side jumps iff lambda dt > -ln u (the reference's lambda > -log(u)/dt); -ln u >= 1 - u screens the test, so the fp64
+// logarithm runs only where 1 - u < lambda dt.  Only on a step where a side jumped is stream 7's call at the same index drawn:
+// E_p = -ln((r0 + 1/2) 2^-32), E_m = -ln((r1 + 1/2) 2^-32), J_P = shift_p + mean_p E_p, J_M = shift_m - (-mean_m) E_m.
+// The intensities follow the reference's Euler step with no floor: they may go negative exactly as there.
+#include "svmc_internal.h"
+
+#include <cmath>
+#include <string>
+
+#include "svmc_rng.h"
+#include "svmc_slice.h"
+#include "svmc_ode.h"
+#include "svmc_dop853.h"
+
+namespace svmc {
+
+namespace {
+
+constexpr int HAWKES_BLOCK = 512;          // a block stages the draw's table in LDS once for its eight waves
+constexpr int HAWKES_MAX_SLICES = MAX_FUSED_SLICES;
+constexpr uint32_t HAWKES_STREAM = 6u, HAWKES_JUMP_STREAM = 7u;
+
+// the per-path constants of the model (params order of include/svmc.h SVMC_HAWKESJD_PARAMS)
+struct HawkesModel {
+    double shift_p, mean_p, shift_m, neg_mean_m;
+    double theta_p, beta1_p, beta2_p, theta_m, beta1_m, beta2_m;
+};
+
+// the constants of one slice's step (:753-764)
+struct HawkesStep {
+    double dt, drift_dt, comp_p_dt, comp_m_dt, sigma_sqrt_dt, kappa_p_dt, kappa_m_dt;
+};
+
+struct HawkesChainSlices {
+    HawkesStep c[HAWKES_MAX_SLICES];
+    double forward[HAWKES_MAX_SLICES];
+    int nb_steps[HAWKES_MAX_SLICES];
+    int m;
+};
+
+enum { P_MU, P_SIGMA, P_SHIFT_P, P_MEAN_P, P_SHIFT_M, P_MEAN_M, P_LAMBDA_P, P_THETA_P, P_KAPPA_P, P_BETA1_P, P_BETA2_P,
+       P_LAMBDA_M, P_THETA_M, P_KAPPA_M, P_BETA1_M, P_BETA2_M };
+static_assert(P_BETA2_M + 1 == SVMC_HAWKESJD_PARAMS, "include/svmc.h and the parameter block must agree");
+
+HawkesModel make_hawkes_model(const double *p)
+{
+    return HawkesModel{p[P_SHIFT_P], p[P_MEAN_P], p[P_SHIFT_M], -p[P_MEAN_M], p[P_THETA_P], p[P_BETA1_P], p[P_BETA2_P],
+                       p[P_THETA_M], p[P_BETA1_M], p[P_BETA2_M]};
+}
+
+HawkesStep make_hawkes_step(double dt, const double *p)
+{
+    HawkesStep c;
+    c.dt = dt;
+    c.drift_dt = (p[P_MU] - 0.5 * p[P_SIGMA] * p[P_SIGMA]) * dt;                                     // :764
+    c.comp_p_dt = dt * (std::exp(p[P_SHIFT_P]) / (1.0 - p[P_MEAN_P]) - 1.0);                       // :761
+    c.comp_m_dt = dt * (std::exp(p[P_SHIFT_M]) / (1.0 - p[P_MEAN_M]) - 1.0);                       // :762
+    c.sigma_sqrt_dt = p[P_SIGMA] * std::sqrt(dt);
+    c.kappa_p_dt = p[P_KAPPA_P] * dt;
+    c.kappa_m_dt = p[P_KAPPA_M] * dt;
+    return c;
+}
+
+// one time step (:765-774) at the chain-global step index s (wave-uniform)
+__device__ __forceinline__ void hawkes_step(const HawkesModel &md, const HawkesStep &c, const PhiloxLane &lane,
+                                            const PhiloxLane &lane_j, uint32_t s, const RngTables &tab, double &x, double &lp,
+                                            double &lm)
+{
+    uint32_t r[4];
+    philox_draw(lane, s, r);
+    const double z = normal_icdf32<SVMC_ICDF_M, SVMC_ICDF_SEGMENTS, SVMC_ICDF_DEG, SVMC_ICDF_EDGE != 0, SVMC_ICDF_RAW != 0>(r[0], tab.icdf);
+    const double up = uniform_32(r[1]), um = uniform_32(r[2]);
+    const double hp = lp * c.dt, hm = lm * c.dt;
+    bool jp = (1.0 - up) < hp, jm = (1.0 - um) < hm;          // -ln u >= 1 - u: no jump without this (1 - u is exact)
+    if (jp) jp = neg_log(up) < hp;                             // :768, fp64
+    if (jm) jm = neg_log(um) < hm;                             // :769
+    double jump_p = 0.0, jump_m = 0.0;
+    if (jp || jm) {                                            // rare and divergent: the jump sizes of this step, stream 7
+        uint32_t e[4];
+        philox_draw(lane_j, s, e);
+        if (jp) jump_p = md.shift_p + md.mean_p * neg_log(uniform_32(e[0]));          // :757
+        if (jm) jump_m = md.shift_m - md.neg_mean_m * neg_log(uniform_32(e[1]));      // :758
+    }
+    // :766 with the intensities at the start of the step, then :770-774
+    const double diffusion = ((c.drift_dt - c.comp_p_dt * lp) - c.comp_m_dt * lm) + c.sigma_sqrt_dt * z;
+    x = ((x + diffusion) + jump_p) + jump_m;
+    const double load_p = md.beta1_p * jump_p + md.beta2_p * jump_m;
+    const double load_m = md.beta1_m * jump_p + md.beta2_m * jump_m;
+    lp = (lp + c.kappa_p_dt * (md.theta_p - lp)) + load_p;
+    lm = (lm + c.kappa_m_dt * (md.theta_m - lm)) + load_m;
+}
+
+// x_snap / partials null: a single slice on caller-owned state (no epilogue)
+__device__ __forceinline__ void hawkes_body(double *__restrict__ x, double *__restrict__ lam_p, double *__restrict__ lam_m, size_t n,
+                                            const HawkesChainSlices &cs, const HawkesModel &md, uint64_t seed, uint32_t c3,
+                                            uint64_t path_offset, uint32_t step_offset, double *__restrict__ x_snap,
+                                            double *__restrict__ partials, const StateInit &init)
+{
+    __shared__ RngTablesLds s_tab;
+    const RngTables tab = stage_rng_tables(s_tab);
+    const size_t p = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    const bool active = p < n;
+    double xv = 0.0, lp = 0.0, lm = 0.0;
+    if (active) {
+        if (init.uniform) {                                    // wave-uniform
+            xv = init.x0;
+            lp = init.vol0;
+            lm = init.qvar0;
+        } else {
+            xv = x[p];
+            lp = lam_p[p];
+            lm = lam_m[p];
+        }
+    }
+    const PhiloxLane lane = philox_prepare(seed, c3 | HAWKES_STREAM, path_offset + p);
+    const PhiloxLane lane_j = philox_prepare(seed, c3 | HAWKES_JUMP_STREAM, path_offset + p);
+    uint32_t step = step_offset;
+    for (int i = 0; i < cs.m; ++i) {
+        const uint32_t end = step + static_cast<uint32_t>(cs.nb_steps[i]);
+        if (active) {
+            const HawkesStep c = cs.c[i];
+            for (uint32_t s = step; s < end; ++s) hawkes_step(md, c, lane, lane_j, s, tab, xv, lp, lm);
+        }
+        step = end;
+        if (x_snap != nullptr) {
+            const size_t rows = (n + 63) >> 6;
+            const SliceOut so = {x_snap + static_cast<size_t>(i) * n, nullptr, partials + 2 * static_cast<size_t>(i) * rows,
+                                 cs.forward[i], rows};
+            slice_epilogue(so, p, active, xv, 0.0);
+        }
+    }
+    if (active) {
+        x[p] = xv;
+        lam_p[p] = lp;
+        lam_m[p] = lm;
+    }
+}
+
+__global__ __launch_bounds__(HAWKES_BLOCK) void hawkesjd_chain_rng_kernel(double *__restrict__ x, double *__restrict__ lam_p,
+                                                                         double *__restrict__ lam_m, size_t n, HawkesChainSlices cs,
+                                                                         HawkesModel md, uint64_t seed, uint32_t c3,
+                                                                         uint64_t path_offset, uint32_t step_offset,
+                                                                         double *__restrict__ x_snap, double *__restrict__ partials,
+                                                                         StateInit init)
+{
+    hawkes_body(x, lam_p, lam_m, n, cs, md, seed, c3, path_offset, step_offset, x_snap, partials, init);
+}
+
+__global__ __launch_bounds__(HAWKES_BLOCK) void hawkesjd_rng_kernel(double *__restrict__ x, double *__restrict__ lam_p,
+                                                                   double *__restrict__ lam_m, size_t n, HawkesChainSlices cs,
+                                                                   HawkesModel md, uint64_t seed, uint32_t c3, uint64_t path_offset,
+                                                                   uint32_t step_offset)
+{
+    hawkes_body(x, lam_p, lam_m, n, cs, md, seed, c3, path_offset, step_offset, nullptr, nullptr, StateInit());
+}
+
+int check_params(const char *fn, const double *p)
+{
+    SVMC_REQUIRE(p != nullptr, std::string(fn) + ": null params");
+    for (int i = 0; i < SVMC_HAWKESJD_PARAMS; ++i)
+        SVMC_REQUIRE(std::isfinite(p[i]), std::string(fn) + ": non-finite parameter");
+    SVMC_REQUIRE(p[P_SIGMA] >= 0.0, std::string(fn) + ": sigma must be non-negative");
+    SVMC_REQUIRE(p[P_MEAN_P] >= 0.0 && p[P_MEAN_P] < 1.0, std::string(fn) + ": need 0 <= mean_p < 1");
+    SVMC_REQUIRE(p[P_MEAN_M] <= 0.0, std::string(fn) + ": need mean_m <= 0");
+    return SVMC_OK;
+}
+
+int check_launch_h(const char *what)
+{
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(SVMC_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+    return SVMC_OK;
+}
+
+unsigned hawkes_grid(size_t n) { return static_cast<unsigned>((n + HAWKES_BLOCK - 1) / HAWKES_BLOCK); }
+
+// ---- the transform grid ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ cd hk_cexp(cd z)
+{
+    double s, c;
+    sincos(z.im, &s, &c);
+    const double e = exp(z.re);
+    return cd{e * c, e * s};
+}
+__device__ __forceinline__ cd hk_cdiv(cd a, cd b)
+{
+    const double d = b.re * b.re + b.im * b.im;
+    return cd{(a.re * b.re + a.im * b.im) / d, (a.im * b.re - a.re * b.im) / d};
+}
+
+struct HawkesOde {
+    double sigma2, kappa_p, kappa_m, kth_p, kth_m, comp_p, comp_m;
+    double shift_p, mean_p, shift_m, mean_m, beta1_p, beta2_p, beta1_m, beta2_m;
+};
+
+HawkesOde make_hawkes_ode(const double *p)
+{
+    HawkesOde o;
+    o.sigma2 = p[P_SIGMA] * p[P_SIGMA];
+    o.kappa_p = p[P_KAPPA_P];
+    o.kappa_m = p[P_KAPPA_M];
+    o.kth_p = p[P_KAPPA_P] * p[P_THETA_P];
+    o.kth_m = p[P_KAPPA_M] * p[P_THETA_M];
+    o.comp_p = std::exp(p[P_SHIFT_P]) / (1.0 - p[P_MEAN_P]) - 1.0;                                  // :69
+    o.comp_m = std::exp(p[P_SHIFT_M]) / (1.0 - p[P_MEAN_M]) - 1.0;                                  // :70
+    o.shift_p = p[P_SHIFT_P];
+    o.mean_p = p[P_MEAN_P];
+    o.shift_m = p[P_SHIFT_M];
+    o.mean_m = p[P_MEAN_M];
+    o.beta1_p = p[P_BETA1_P];
+    o.beta2_p = p[P_BETA2_P];
+    o.beta1_m = p[P_BETA1_M];
+    o.beta2_m = p[P_BETA2_M];
+    return o;
+}
+
+// func_rhs of solve_ode_for_a (:607-626); h0 = sigma^2 (phi (phi + 1) / 2 - psi) is the same for every evaluation
+__device__ __forceinline__ void hawkes_rhs(const HawkesOde &o, cd phi, cd h0, const cd (&a)[3], cd (&out)[3])
+{
+    const cd zp = (phi - o.beta1_p * a[1]) - o.beta1_m * a[2];
+    const cd zm = (phi - o.beta2_p * a[1]) - o.beta2_m * a[2];
+    const cd j_p = hk_cdiv(hk_cexp(-(o.shift_p * zp)), 1.0 + o.mean_p * zp) - 1.0;                  // e_p, :594-601
+    const cd j_m = hk_cdiv(hk_cexp(-(o.shift_m * zm)), 1.0 + o.mean_m * zm) - 1.0;                  // e_m, :603-605
+    out[0] = (o.kth_p * a[1] + o.kth_m * a[2]) + h0;
+    out[1] = (j_p - o.kappa_p * a[1]) + o.comp_p * phi;
+    out[2] = (j_m - o.kappa_m * a[2]) + o.comp_m * phi;
+}
+
+// DOP853 on the three components, the controller of svmc_analytic.hip's dop853 (SciPy's), error normed over n = 3
+__device__ void hawkes_dop853(const HawkesOde &o, cd phi, cd h0, double ttm, cd (&y)[3], double rtol, double atol)
+{
+    constexpr double STEP_FLOOR = 0x1.0p-46;
+    constexpr int MAX_TRIES = 1 << 15;
+    cd K1[3], K2[3] = {}, K3[3] = {}, K4[3] = {}, K5[3] = {}, K6[3] = {}, K7[3] = {}, K8[3] = {}, K9[3] = {}, K10[3] = {},
+       K11[3] = {}, K12[3] = {}, yt[3], yn[3], kn[3];
+    double t = 0.0, h = ttm / 8.0;
+    int tries = 0;
+    bool rejected = false;
+    hawkes_rhs(o, phi, h0, y, K1);
+#define SVMC_HK_STAGE(S, KS)                                                                                                 \
+    _Pragma("unroll") for (int i = 0; i < 3; ++i)                                                                            \
+    {                                                                                                                        \
+        const cd k1 = K1[i], k2 = K2[i], k3 = K3[i], k4 = K4[i], k5 = K5[i], k6 = K6[i], k7 = K7[i], k8 = K8[i], k9 = K9[i],  \
+                 k10 = K10[i], k11 = K11[i];                                                                                 \
+        (void)k2; (void)k3; (void)k4; (void)k5; (void)k6; (void)k7; (void)k8; (void)k9; (void)k10; (void)k11;               \
+        yt[i] = y[i] + h * (SVMC_D853_STAGE_##S);                                                                            \
+    }                                                                                                                        \
+    hawkes_rhs(o, phi, h0, yt, KS)
+    while (t < ttm && tries < MAX_TRIES) {
+        ++tries;
+        if (!(h >= STEP_FLOOR * ttm)) break;
+        if (t + h > ttm) h = ttm - t;
+        SVMC_HK_STAGE(2, K2);
+        SVMC_HK_STAGE(3, K3);
+        SVMC_HK_STAGE(4, K4);
+        SVMC_HK_STAGE(5, K5);
+        SVMC_HK_STAGE(6, K6);
+        SVMC_HK_STAGE(7, K7);
+        SVMC_HK_STAGE(8, K8);
+        SVMC_HK_STAGE(9, K9);
+        SVMC_HK_STAGE(10, K10);
+        SVMC_HK_STAGE(11, K11);
+        SVMC_HK_STAGE(12, K12);
+        double e5 = 0.0, e3 = 0.0;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            const cd k1 = K1[i], k6 = K6[i], k7 = K7[i], k8 = K8[i], k9 = K9[i], k10 = K10[i], k11 = K11[i], k12 = K12[i];
+            yn[i] = y[i] + h * (SVMC_D853_B);
+            const cd err5 = SVMC_D853_E5, err3 = SVMC_D853_E3;
+            const double m2 = fmax(y[i].re * y[i].re + y[i].im * y[i].im, yn[i].re * yn[i].re + yn[i].im * yn[i].im);
+            const double sc = atol + rtol * sqrt(m2);
+            const double inv = 1.0 / (sc * sc);
+            e5 += (err5.re * err5.re + err5.im * err5.im) * inv;
+            e3 += (err3.re * err3.re + err3.im * err3.im) * inv;
+        }
+        const double denom = e5 + 0.01 * e3;
+        const bool finite = denom < 0x1.0p+1000;               // false for inf and NaN: an overflowed trial step
+        const double err_sq = !finite ? __builtin_huge_val() : ((denom > 0.0) ? (h * h) * (e5 * e5) / (denom * 3.0) : 0.0);
+        const bool accept = err_sq < 1.0;
+        double fac = !finite ? 0.2 : ((err_sq > 0.0) ? 0.9 * pow(err_sq, -0.0625) : 10.0);
+        if (accept) {
+            hawkes_rhs(o, phi, h0, yn, kn);
+            t += h;
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                y[i] = yn[i];
+                K1[i] = kn[i];
+            }
+            fac = fmin(rejected ? 1.0 : 10.0, fac);
+            rejected = false;
+        } else {
+            fac = fmax(0.2, fmin(fac, 1.0));
+            rejected = true;
+        }
+        h *= fac;
+    }
+#undef SVMC_HK_STAGE
+    if (!(t >= ttm)) {                                         // given up: NaN, dropped by the inversion's nansum
+#pragma unroll
+        for (int i = 0; i < 3; ++i) y[i] = cd{__builtin_nan(""), __builtin_nan("")};
+    }
+}
+
+constexpr int HK_AB = 64;
+
+__global__ __launch_bounds__(HK_AB) void hawkes_mgf_grid_kernel(const cd *__restrict__ phi, const cd *__restrict__ psi, size_t n_grid,
+                                                               double ttm, HawkesOde o, double lambda_p, double lambda_m,
+                                                               cd *__restrict__ a, cd *__restrict__ log_mgf, double rtol, double atol)
+{
+    const size_t j = static_cast<size_t>(blockIdx.x) * HK_AB + threadIdx.x;
+    if (j >= n_grid) return;
+    const cd ph = phi[j];
+    const cd h0 = o.sigma2 * ((0.5 * ((ph + 1.0) * ph)) - psi[j]);                                 // :623
+    cd y[3] = {a[3 * j], a[3 * j + 1], a[3 * j + 2]};                                              // a_t0, chained across expiries
+    hawkes_dop853(o, ph, h0, ttm, y, rtol, atol);
+    a[3 * j] = y[0];
+    a[3 * j + 1] = y[1];
+    a[3 * j + 2] = y[2];
+    log_mgf[j] = (y[0] + lambda_p * y[1]) + lambda_m * y[2];                                       // :545
+}
+
+}  // namespace
+
+// the chain's stepping (svmc_chain.hip's svmc_hawkesjd_chain_price): every expiry in one launch per 16, the state starting at
+// (0, lambda_p, lambda_m); the per-wave spot partials of each expiry left in `workspace` unreduced (spot_sums null, at most 16
+// expiries) or reduced into spot_sums
+int hawkes_step_partials(const double *params_host, double *x, double *lam_p, double *lam_m, size_t n_path, int n_slices,
+                         const int *nb_steps_host, const double *dts_host, const double *forwards_host, uint64_t seed,
+                         uint32_t call_id, uint64_t path_offset, double *x_snapshots, double *spot_sums, void *workspace,
+                         size_t workspace_bytes, hipStream_t stream)
+{
+    const char *fn = "svmc_hawkesjd_chain_price";
+    if (int rc = check_params(fn, params_host)) return rc;
+    SVMC_REQUIRE(x && lam_p && lam_m && x_snapshots && workspace, std::string(fn) + ": null pointer");
+    SVMC_REQUIRE(nb_steps_host && dts_host && forwards_host && n_slices >= 1, std::string(fn) + ": null grids / no slices");
+    SVMC_REQUIRE(spot_sums != nullptr || n_slices <= HAWKES_MAX_SLICES, std::string(fn) + ": unreduced partials need one launch");
+    SVMC_REQUIRE(call_id < (1u << 24), std::string(fn) + ": call_id must fit 24 bits");
+    SVMC_REQUIRE(n_path > 0, std::string(fn) + ": n_path must be positive");
+    for (int i = 0; i < n_slices; ++i)
+        SVMC_REQUIRE(nb_steps_host[i] > 0 && dts_host[i] > 0.0, std::string(fn) + ": nb_steps and dt must be positive");
+    const HawkesModel md = make_hawkes_model(params_host);
+    const StateInit init = {1, 0.0, params_host[P_LAMBDA_P], params_host[P_LAMBDA_M]};             // :672-674
+    uint32_t step_offset = 0;
+    for (int i0 = 0; i0 < n_slices; i0 += HAWKES_MAX_SLICES) {
+        HawkesChainSlices cs;
+        cs.m = (n_slices - i0 < HAWKES_MAX_SLICES) ? (n_slices - i0) : HAWKES_MAX_SLICES;
+        if (workspace_bytes < static_cast<size_t>(wave_rows(n_path)) * 2 * cs.m * sizeof(double))
+            return fail(SVMC_ERR_WORKSPACE, std::string(fn) + ": workspace too small (svmc_slice_workspace_bytes)");
+        uint32_t steps = 0;
+        for (int i = 0; i < HAWKES_MAX_SLICES; ++i) {
+            const int j = (i < cs.m) ? i0 + i : i0;
+            cs.c[i] = make_hawkes_step(dts_host[j], params_host);
+            cs.forward[i] = forwards_host[j];
+            cs.nb_steps[i] = (i < cs.m) ? nb_steps_host[j] : 0;
+            steps += static_cast<uint32_t>(cs.nb_steps[i]);
+        }
+        hipLaunchKernelGGL(hawkesjd_chain_rng_kernel, dim3(hawkes_grid(n_path)), dim3(HAWKES_BLOCK), 0, stream, x, lam_p, lam_m, n_path,
+                           cs, md, seed, call_id << 8, path_offset, step_offset, x_snapshots + static_cast<size_t>(i0) * n_path,
+                           static_cast<double *>(workspace), (i0 == 0) ? init : StateInit());
+        if (int rc = check_launch_h(fn)) return rc;
+        if (spot_sums != nullptr)
+            if (int rc = reduce_spot_partials(workspace, n_path, 2 * cs.m, spot_sums + 2 * i0, stream)) return rc;
+        step_offset += steps;
+    }
+    return SVMC_OK;
+}
+
+}  // namespace svmc
+
+using namespace svmc;
+
+extern "C" {
+
+int svmc_hawkesjd_terminal_rng(double *x, double *lambda_p, double *lambda_m, size_t n_path, int nb_steps, double dt,
+                               const double *params_host, uint64_t seed, uint32_t call_id, uint64_t path_offset,
+                               uint32_t step_offset, svmc_stream_t stream)
+{
+    const char *fn = "svmc_hawkesjd_terminal_rng";
+    if (int rc = check_params(fn, params_host)) return rc;
+    SVMC_REQUIRE(x && lambda_p && lambda_m, std::string(fn) + ": null state array");
+    SVMC_REQUIRE(n_path > 0, std::string(fn) + ": n_path must be positive");
+    SVMC_REQUIRE(nb_steps >= 0 && dt > 0.0 && std::isfinite(dt), std::string(fn) + ": need nb_steps >= 0 and dt > 0");
+    SVMC_REQUIRE(call_id < (1u << 24), std::string(fn) + ": call_id must fit 24 bits");
+    if (nb_steps == 0) return SVMC_OK;
+    HawkesChainSlices cs;
+    cs.m = 1;
+    for (int i = 0; i < HAWKES_MAX_SLICES; ++i) {
+        cs.c[i] = make_hawkes_step(dt, params_host);
+        cs.forward[i] = 1.0;
+        cs.nb_steps[i] = (i == 0) ? nb_steps : 0;
+    }
+    hipLaunchKernelGGL(hawkesjd_rng_kernel, dim3(hawkes_grid(n_path)), dim3(HAWKES_BLOCK), 0, as_stream(stream), x, lambda_p, lambda_m,
+                       n_path, cs, make_hawkes_model(params_host), seed, call_id << 8, path_offset, step_offset);
+    return check_launch_h(fn);
+}
+
+int svmc_hawkesjd_mgf_grid(const double *phi, const double *psi, size_t n_grid, double ttm, const double *params_host, double *a,
+                           double *log_mgf, double rtol, double atol, svmc_stream_t stream)
+{
+    const char *fn = "svmc_hawkesjd_mgf_grid";
+    if (int rc = check_params(fn, params_host)) return rc;
+    SVMC_REQUIRE(phi && psi && a && log_mgf, std::string(fn) + ": null pointer");
+    SVMC_REQUIRE(ttm > 0.0 && rtol > 0.0 && atol > 0.0, std::string(fn) + ": ttm, rtol, atol must be positive");
+    if (n_grid == 0) return SVMC_OK;
+    hipLaunchKernelGGL(hawkes_mgf_grid_kernel, dim3(static_cast<unsigned>((n_grid + HK_AB - 1) / HK_AB)), dim3(HK_AB), 0,
+                       as_stream(stream), reinterpret_cast<const cd *>(phi), reinterpret_cast<const cd *>(psi), n_grid, ttm,
+                       make_hawkes_ode(params_host), params_host[P_LAMBDA_P], params_host[P_LAMBDA_M], reinterpret_cast<cd *>(a),
+                       reinterpret_cast<cd *>(log_mgf), rtol, atol);
+    return check_launch_h(fn);
+}
+
+}  // extern "C"

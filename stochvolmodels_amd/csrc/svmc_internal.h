@@ -76,6 +76,11 @@ int heston_step_partials(double var0, double *x, double *var, double *qvar, size
                          const double *dts_host, const double *forwards_host, double theta, double kappa, double rho, double volvol,
                          int scheme, uint64_t seed, uint32_t call_id, uint64_t path_offset, double *x_snapshots,
                          double *qvar_snapshots, void *workspace, size_t workspace_bytes, hipStream_t stream);
+// svmc_hawkes.hip: the Hawkes jump-diffusion chain's stepping from (0, lambda_p, lambda_m) (params: SVMC_HAWKESJD_PARAMS doubles)
+int hawkes_step_partials(const double *params_host, double *x, double *lam_p, double *lam_m, size_t n_path, int n_slices,
+                         const int *nb_steps_host, const double *dts_host, const double *forwards_host, uint64_t seed,
+                         uint32_t call_id, uint64_t path_offset, double *x_snapshots, double *spot_sums, void *workspace,
+                         size_t workspace_bytes, hipStream_t stream);
 bool spot_sums_in_payoff_kernel(size_t n_path);
 int reduce_spot_partials(const void *workspace, size_t n_path, int n_cols, double *spot_sums, hipStream_t stream);
 int chain_payoff_and_finish(const double *const *x_snapshots_host, const double *const *qvar_snapshots_host, size_t n_path,

@@ -15,6 +15,7 @@
 #include "svmc_black.h"
 #include "svmc_models.h"
 #include "svmc_rng.h"
+#include "svmc_slice.h"
 
 namespace svmc {
 
@@ -115,13 +116,6 @@ __global__ __launch_bounds__(BLOCK) void fill_uniforms_kernel(double *__restrict
 // Deterministic block reductions: wave shuffles in a fixed tree, one LDS exchange, ONE barrier for any number of
 // values (the first version paid two barriers per value: 96 per payoff block).
 // ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-
 // One halving level of the multi-value butterfly: lanes with (lane & MASK) set keep the upper half of v[0..2H),
 // the others the lower half, and add the partner lane's copy of the half they keep.
 template <int H, int MASK>
@@ -310,47 +304,6 @@ __device__ __forceinline__ void progress_priority(int stage)
     case 1: __builtin_amdgcn_s_setprio(2); break;
     case 2: __builtin_amdgcn_s_setprio(1); break;
     default: __builtin_amdgcn_s_setprio(0); break;
-    }
-}
-
-// Optional slice epilogue fused into the stepping kernels: the terminal x (and qvar) is also written to the
-// per-expiry snapshot the payoff pass reads, and [sum F*exp(x), count] (utils/mc_payoffs.py:61-62) goes out as one row PER
-// WAVE -- partials[column][wave], wave = global thread index / 64 -- which reduce_columns_kernel adds up in row order: one
-// launch and one pass over x less per expiry.  Rows per wave, not per block: the sum's order of additions is then the same
-// whatever block size a kernel runs (the one-slice generators run 512-thread blocks, the whole-chain kernel 1024, the
-// streamed ones 256, and their results must agree to the bit), and the epilogue needs no LDS and no barrier.
-struct SliceOut {
-    double *x_snap;     // nullable
-    double *q_snap;     // nullable
-    double *partials;   // nullable: this slice's two COLUMNS, [2][rows] -- column-major, so that the reduction reads them coalesced
-    double forward;
-    size_t rows = 0;    // column stride of `partials`: wave_rows(n) of the launch
-};
-
-
-// Start state of a generator launch: read from x / vol / qvar (uniform = 0), or the same three constants for every path --
-// what a chain pricing starts from (x0 = 0, sigma0 | v0, qvar0 = 0: pricers/logsv_pricer.py:823-826, heston_pricer.py:303-305).
-// The svmc_*_rng_from entry points use it: no fill launch (11 us + the write-back of its 24 bytes per path at the kernel
-// boundary) and no 24-byte read per path ahead of the stepping.
-struct StateInit {
-    int uniform = 0;
-    double x0 = 0.0, vol0 = 0.0, qvar0 = 0.0;
-};
-
-__device__ __forceinline__ void slice_epilogue(const SliceOut &so, size_t p, bool active, double xv, double q)
-{
-    if (active) {
-        if (so.x_snap != nullptr) so.x_snap[p] = xv;
-        if (so.q_snap != nullptr) so.q_snap[p] = q;
-    }
-    if (so.partials != nullptr) {
-        const double sp = so.forward * exp_full(xv);       // full-range exp: x = +-inf must give inf / 0   :61
-        const bool ok = active && (sp == sp);                                                   // nanmean :62
-        const double v0 = wave_sum(ok ? sp : 0.0), v1 = wave_sum(ok ? 1.0 : 0.0);
-        if ((threadIdx.x & 63u) == 0u && (p >> 6) < so.rows) {        // a launch's last block may hold waves past the last path
-            so.partials[p >> 6] = v0;
-            so.partials[so.rows + (p >> 6)] = v1;
-        }
     }
 }
 

@@ -533,6 +533,24 @@ class HipEngine:
             float(theta), float(kappa), float(rho), float(volvol), int(scheme), int(nb_steps_per_year), int(variable_type),
             int(seed), int(call_id), p, e), "heston_rng_kernel" if ch["m"] == 1 else "heston_chain_rng_kernel")
 
+    def price_hawkesjd_chain_fused(self, ch: dict, params: np.ndarray, nb_steps_per_year: int, variable_type: int, seed: int,
+                                   call_id: int):
+        """hawkesjd_mc_chain_pricer on one GPU as ONE svmc_hawkesjd_chain_price call on this engine's state (vol / qvar hold
+        lambda_p / lambda_m afterwards); params: the SVMC_HAWKESJD_PARAMS doubles of include/svmc.h"""
+        params = np.ascontiguousarray(params, dtype=np.float64)
+        return self._fused_call(ch, lambda sess, p, e: self.lib.svmc_hawkesjd_chain_price(
+            sess, ch["ttms"], ch["forwards"], ch["discfactors"], ch["m"], ch["strikes"], ch["codes"], ch["offsets"],
+            params.ctypes.data_as(C.POINTER(C.c_double)), int(nb_steps_per_year), int(variable_type), int(seed), int(call_id),
+            p, e), "hawkesjd_chain_rng_kernel")
+
+    def hawkesjd_rng(self, nb_steps: int, dt: float, params: np.ndarray, seed: int, call_id: int, step_offset: int = 0) -> None:
+        """simulate_hawkesjd_terminal on this engine's state (x, lambda_p, lambda_m) in place"""
+        params = np.ascontiguousarray(params, dtype=np.float64)
+        self._timed("hawkesjd_rng_kernel", lambda: _lib.check(self.lib.svmc_hawkesjd_terminal_rng(
+            self.x.ptr, self.vol.ptr, self.qvar.ptr, self.n_path, int(nb_steps), float(dt),
+            params.ctypes.data_as(C.POINTER(C.c_double)), int(seed), int(call_id), self.path_offset, int(step_offset),
+            self.stream)))
+
     # ---- state ----------------------------------------------------------------------------------
     def fill_state(self, x0: float, vol0: float, qvar0: float) -> None:
         _lib.check(self.lib.svmc_fill_state(self.x.ptr, self.vol.ptr, self.qvar.ptr, self.n_path,

@@ -1,0 +1,203 @@
+"""
+The Hawkes jump-diffusion on the GPU (csrc/svmc_hawkes.hip, stochvolmodels_amd.pricers.hawkes_jd_pricer): the on-device-RNG
+chain pricer against the reference run on the same stream (tests/golden/hawkes_mc*.npz, through the CPU twin), one slice against
+the twin, shard invariance, the C ABI against the Python route, the Fourier pricer against the reference's, the Monte Carlo
+against the Fourier pricer in distribution, and the C ABI's error codes.
+"""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import hawkes_twin as twin
+
+pytestmark = pytest.mark.gpu
+
+
+def _chain(f):
+    m = f["ttms"].size
+    return (f["ttms"], f["forwards"], f["discfactors"], [f[f"strikes_{i}"] for i in range(m)], [f[f"types_{i}"] for i in range(m)])
+
+
+def _kw(f):
+    return dict(zip(twin.PARAM_NAMES, (float(v) for v in f["params"])))
+
+
+@pytest.mark.parametrize("name", ["hawkes_mc", "hawkes_mc_excited"])
+def test_chain_pricer_reproduces_the_reference_on_the_stream(golden, name):
+    from stochvolmodels_amd.engine import get_engine
+    from stochvolmodels_amd.pricers import hawkes_jd_pricer as hp
+    f = golden(name)
+    ttms, fw, df, ks, ts = _chain(f)
+    n, seed = int(f["n_path"]), int(f["seed"])
+    pr, sd = hp.hawkesjd_mc_chain_pricer(ttms=ttms, forwards=fw, discfactors=df, strikes_ttms=ks, optiontypes_ttms=ts, nb_path=n,
+                                         seed=seed, **_kw(f))
+    np.testing.assert_allclose(np.concatenate(pr), f["prices"], rtol=1e-11, atol=1e-14)
+    np.testing.assert_allclose(np.concatenate(sd), f["stderrs"], rtol=1e-11, atol=1e-14)
+    # the state after each expiry: the chain cut after it (the stream is indexed by chain-global steps)
+    for i in range(ttms.size):
+        hp.hawkesjd_mc_chain_pricer(ttms=ttms[:i + 1], forwards=fw[:i + 1], discfactors=df[:i + 1], strikes_ttms=ks[:i + 1],
+                                    optiontypes_ttms=ts[:i + 1], nb_path=n, seed=seed, **_kw(f))
+        state = np.stack([a[:256] for a in get_engine(n).get_state()])
+        np.testing.assert_allclose(state, f["states"][i], rtol=1e-12, atol=1e-12)
+
+
+def test_single_slice_matches_the_twin():
+    from stochvolmodels_amd.pricers import hawkes_jd_pricer as hp
+    p = hp.HawkesJDParams()
+    n, seed = 1 << 14, 99
+    x, lp, lm = hp.HawkesJDPricer().simulate_terminal_values(params=p, ttm=0.25, nb_path=n, seed=seed)
+    kw = {k: getattr(p, k) for k in twin.PARAM_NAMES}
+    tx, tlp, tlm, nb = twin.simulate_terminal(0.25, np.zeros(n), p.lambda_p * np.ones(n), p.lambda_m * np.ones(n), kw, seed)
+    assert nb == 451
+    np.testing.assert_allclose(x, tx, rtol=1e-12, atol=1e-12)
+    np.testing.assert_allclose(lp, tlp, rtol=1e-12, atol=1e-12)
+    np.testing.assert_allclose(lm, tlm, rtol=1e-12, atol=1e-12)
+    # the reference's length-1 broadcast of the start state
+    kw.pop("lambda_p"), kw.pop("lambda_m")
+    x1, lp1, lm1 = hp.simulate_hawkesjd_terminal(ttm=0.25, x0=np.array([0.0]), lambda_p0=np.array([p.lambda_p]),
+                                                 lambda_m0=np.array([p.lambda_m]), nb_path=n, seed=seed, **kw)
+    assert np.array_equal(x1, x) and np.array_equal(lp1, lp) and np.array_equal(lm1, lm)
+
+
+def test_shard_invariance(golden):
+    from stochvolmodels_amd.engine import get_engine, marshalled_chain, option_type_codes
+    from stochvolmodels_amd.pricers import hawkes_jd_pricer as hp
+    f = golden("hawkes_mc")
+    ttms, fw, df, ks, ts = _chain(f)
+    ch = marshalled_chain(ttms, fw, df, ks, [option_type_codes(t) for t in ts])
+    block = hp.params_block(**_kw(f))
+    n = 1 << 16
+    one = get_engine(n)
+    one.price_hawkesjd_chain_fused(ch, block, 1800, 1, 4242, 3)
+    whole = one.get_state()
+    parts = []
+    for off in (0, n // 2):
+        eng = get_engine(n // 2, path_offset=off)
+        eng.price_hawkesjd_chain_fused(ch, block, 1800, 1, 4242, 3)
+        parts.append(eng.get_state())
+    for k in range(3):
+        assert np.array_equal(np.concatenate([parts[0][k], parts[1][k]]), whole[k])
+
+
+def test_c_abi_matches_the_python_route(golden):
+    from stochvolmodels_amd import _lib
+    from stochvolmodels_amd.engine import get_engine, option_type_codes
+    from stochvolmodels_amd.pricers import hawkes_jd_pricer as hp
+    L = _lib.load()
+    f = golden("hawkes_mc")
+    ttms, fw, df, ks, ts = _chain(f)
+    n, seed = 20000, 777
+    pr, sd = hp.hawkesjd_mc_chain_pricer(ttms=ttms, forwards=fw, discfactors=df, strikes_ttms=ks, optiontypes_ttms=ts, nb_path=n,
+                                         seed=seed, **_kw(f))
+    py_state = get_engine(n).get_state()
+    dp = C.POINTER(C.c_double)
+    strikes = np.concatenate(ks)
+    codes = np.concatenate([option_type_codes(t) for t in ts]).astype(np.int8)
+    offs = np.concatenate([[0], np.cumsum([k.size for k in ks])]).astype(np.uintp)
+    block = hp.params_block(**_kw(f))
+    prices, stderrs = np.empty(strikes.size), np.empty(strikes.size)
+    sess = C.c_void_p()
+    _lib.check(L.svmc_session_create(C.byref(sess), n, ttms.size, strikes.size))
+    try:
+        _lib.check(L.svmc_hawkesjd_chain_price(sess, ttms.ctypes.data_as(dp), fw.ctypes.data_as(dp), df.ctypes.data_as(dp), ttms.size,
+                                               strikes.ctypes.data_as(dp), codes.ctypes.data_as(C.POINTER(C.c_int8)),
+                                               offs.ctypes.data_as(C.POINTER(C.c_size_t)), block.ctypes.data_as(dp), 1800, 1, seed, 0,
+                                               prices.ctypes.data_as(dp), stderrs.ctypes.data_as(dp)))
+        st = [np.empty(n) for _ in range(3)]
+        _lib.check(L.svmc_session_state(sess, *[a.ctypes.data for a in st]))
+    finally:
+        L.svmc_session_destroy(sess)
+    assert np.array_equal(prices, np.concatenate(pr)) and np.array_equal(stderrs, np.concatenate(sd))
+    for a, b in zip(st, py_state):
+        assert np.array_equal(a, b)
+
+
+def test_analytic_matches_the_reference(golden):
+    from stochvolmodels_amd.pricers import hawkes_jd_pricer as hp
+    from stochvolmodels_amd.utils import mgf_pricer as mgfp
+    f = golden("hawkes_analytic")
+    ttms, fw, df, ks, ts = _chain(f)
+    p = hp.HawkesJDParams(**_kw(f))
+    pr = np.concatenate(hp.hawkesjd_chain_pricer(model_params=p, ttms=ttms, forwards=fw, discfactors=df, strikes_ttms=ks,
+                                                 optiontypes_ttms=ts))
+    scale = np.repeat(fw, [k.size for k in ks])
+    assert np.max(np.abs(pr - f["prices_tight"]) / np.maximum(np.abs(f["prices_tight"]), 1e-4 * scale)) <= 1e-8
+    assert np.max(np.abs(pr - f["prices_default"]) / np.maximum(np.abs(f["prices_default"]), 1e-4 * scale)) <= 2e-3
+    # the first expiry's coefficients and log-MGF on the transform grid; is_stiff_solver is answered by the same integrator
+    phi, psi, _ = mgfp.get_transform_var_grid(max_phi=hp.MAX_PHI, vol_scaler=hp.set_vol_scaler(p.sigma, np.min(ttms)))
+    np.testing.assert_array_equal(phi, f["phi"])
+    a1, lm1 = hp.compute_hawkes_a_mgf_grid(ttm=ttms[0], phi_grid=phi, psi_grid=psi, model_params=p, is_stiff_solver=True)
+    np.testing.assert_allclose(lm1, f["log_mgf1_tight"], rtol=1e-8, atol=1e-9)
+    np.testing.assert_allclose(a1, f["a1_tight"], rtol=1e-8, atol=1e-9)
+    # a_t0 chained: two halves of the first expiry are the whole
+    ah, _ = hp.compute_hawkes_a_mgf_grid(ttm=ttms[0] / 2, phi_grid=phi, model_params=p)
+    a2, lm2 = hp.compute_hawkes_a_mgf_grid(ttm=ttms[0] / 2, phi_grid=phi, model_params=p, a_t0=ah)
+    np.testing.assert_allclose(lm2, lm1, rtol=1e-8, atol=1e-9)
+    via = hp.HawkesJDPricer().price_chain(
+        __import__("stochvolmodels_amd").OptionChain(ttms=ttms, forwards=fw, discfactors=df, strikes_ttms=tuple(ks),
+                                                    optiontypes_ttms=tuple(ts), ids=None), p)
+    assert np.array_equal(np.concatenate(via), pr)
+
+
+def test_mc_agrees_with_analytic_in_distribution(golden):
+    """independent of any stream: 2^20 paths at 16x the reference's step count (its time-discretisation bias is first order in
+    dt and leans negative at 1800 per year); every option within 4 standard errors of the Fourier price"""
+    from stochvolmodels_amd.pricers import hawkes_jd_pricer as hp
+    f = golden("hawkes_analytic")
+    ttms, fw, df, ks, ts = _chain(f)
+    p = hp.HawkesJDParams(**_kw(f))
+    ref = np.concatenate(hp.hawkesjd_chain_pricer(model_params=p, ttms=ttms, forwards=fw, discfactors=df, strikes_ttms=ks,
+                                                  optiontypes_ttms=ts))
+    pr, sd = hp.HawkesJDPricer().model_mc_price_chain(
+        __import__("stochvolmodels_amd").OptionChain(ttms=ttms, forwards=fw, discfactors=df, strikes_ttms=tuple(ks),
+                                                    optiontypes_ttms=tuple(ts), ids=None),
+        p, nb_path=1 << 20, nb_steps_per_year=28800, seed=2025)
+    z = (np.concatenate(pr) - ref) / np.concatenate(sd)
+    print("z-scores at 28800 steps/yr, 2^20 paths:", np.round(z, 2).tolist())
+    assert z.size == 49 and np.all(np.abs(z) <= 4.0), z
+
+
+def test_error_codes():
+    from stochvolmodels_amd import _lib
+    from stochvolmodels_amd.pricers import hawkes_jd_pricer as hp
+    L = _lib.load()
+    dp = C.POINTER(C.c_double)
+    block = hp.params_block(**hp.HawkesJDParams().to_dict())
+    bp = block.ctypes.data_as(dp)
+    buf = C.c_void_p()
+    _lib.check(L.svmc_malloc(C.byref(buf), 3 * 8 * 64))
+    x, lp, lm = buf.value, buf.value + 8 * 64, buf.value + 16 * 64
+    try:
+        assert L.svmc_hawkesjd_terminal_rng(None, lp, lm, 64, 10, 0.001, bp, 1, 0, 0, 0, None) == _lib.ERR_INVALID_ARGUMENT
+        assert L.svmc_hawkesjd_terminal_rng(x, lp, lm, 64, 10, 0.001, None, 1, 0, 0, 0, None) == _lib.ERR_INVALID_ARGUMENT
+        assert L.svmc_hawkesjd_terminal_rng(x, lp, lm, 0, 10, 0.001, bp, 1, 0, 0, 0, None) == _lib.ERR_INVALID_ARGUMENT
+        assert L.svmc_hawkesjd_terminal_rng(x, lp, lm, 64, 10, 0.0, bp, 1, 0, 0, 0, None) == _lib.ERR_INVALID_ARGUMENT
+        bad = block.copy()
+        bad[3] = 1.5                                                            # mean_p >= 1
+        assert L.svmc_hawkesjd_terminal_rng(x, lp, lm, 64, 10, 0.001, bad.ctypes.data_as(dp), 1, 0, 0, 0, None) == \
+            _lib.ERR_INVALID_ARGUMENT
+        assert L.svmc_hawkesjd_mgf_grid(None, None, 4, 0.1, bp, None, None, 1e-10, 1e-12, None) == _lib.ERR_INVALID_ARGUMENT
+    finally:
+        L.svmc_free(buf)
+    one = np.array([0.1])
+    k = np.array([1.0])
+    codes = np.array([9], dtype=np.int8)
+    offs = np.array([0, 1], dtype=np.uintp)
+    out = np.empty(2)
+    sess = C.c_void_p()
+    _lib.check(L.svmc_session_create(C.byref(sess), 256, 1, 1))
+    try:
+        args = lambda types, vt, params=bp: L.svmc_hawkesjd_chain_price(  # noqa: E731
+            sess, one.ctypes.data_as(dp), one.ctypes.data_as(dp), one.ctypes.data_as(dp), 1, k.ctypes.data_as(dp),
+            types.ctypes.data_as(C.POINTER(C.c_int8)), offs.ctypes.data_as(C.POINTER(C.c_size_t)), params, 1800, vt, 1, 0,
+            out[:1].ctypes.data_as(dp), out[1:].ctypes.data_as(dp))
+        assert args(codes, 1) == _lib.ERR_UNKNOWN_PAYOFF
+        good = np.array([0], dtype=np.int8)
+        assert args(good, 2) == _lib.ERR_UNSUPPORTED_VARIABLE
+        assert args(good, 1, None) == _lib.ERR_INVALID_ARGUMENT
+        assert L.svmc_hawkesjd_chain_price(None, None, None, None, 1, None, None, None, bp, 1800, 1, 1, 0, None, None) == \
+            _lib.ERR_INVALID_ARGUMENT
+        assert args(good, 1) == _lib.OK
+    finally:
+        L.svmc_session_destroy(sess)
