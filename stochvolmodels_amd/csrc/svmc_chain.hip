@@ -123,13 +123,6 @@ static void session_release(Session *s)
     delete s;
 }
 
-// utils/funcs.py:44-47
-static void time_grid(double ttm, int spy, int &nb_steps, double &dt)
-{
-    nb_steps = static_cast<int>(ttm * static_cast<double>(spy)) + 1;
-    dt = (nb_steps == 1) ? ttm : ttm / static_cast<double>(nb_steps);
-}
-
 // intrinsic value at the forward for LOG_RETURN, zero otherwise (the shift of svmc_payoff_sums)
 static double payoff_shift(double strike, int type, double forward, int variable_type)
 {
@@ -145,6 +138,20 @@ struct ChainView {
     const int8_t *types;
     const size_t *offsets;   // [m + 1] into strikes/types
 };
+
+// the step grid of every expiry of a chain, each slice starting at the previous expiry (utils/funcs.py:44-47)
+static void expiry_grids(const ChainView &c, int nb_steps_per_year, std::vector<int> &nbs, std::vector<double> &dts)
+{
+    nbs.resize(c.m);
+    dts.resize(c.m);
+    double t0 = 0.0;
+    for (int i = 0; i < c.m; ++i) {
+        const double ttm = c.ttms[i] - t0;
+        nbs[i] = static_cast<int>(ttm * static_cast<double>(nb_steps_per_year)) + 1;
+        dts[i] = (nbs[i] == 1) ? ttm : ttm / static_cast<double>(nbs[i]);
+        t0 = c.ttms[i];
+    }
+}
 
 static int check_chain(const char *fn, const Session *s, const ChainView &c, int variable_type, const double *prices,
                        const double *stderrs)
@@ -474,31 +481,21 @@ int svmc_logsv_chain_price(svmc_session_t session, const double *ttms_host, cons
     SVMC_REQUIRE(nb_steps_per_year > 0, "svmc_logsv_chain_price: nb_steps_per_year must be positive");
     const size_t n = s->n_path;
     // the start state (0, v0, 0) of every path (:832-834) travels as three constants: no fill launch
-    double t0 = 0.0;
-    std::vector<int> nbs(c.m);
-    std::vector<double> dts(c.m);
-    for (int i = 0; i < c.m; ++i) {                                                                       // :840-865
-        time_grid(c.ttms[i] - t0, nb_steps_per_year, nbs[i], dts[i]);
-        t0 = c.ttms[i];
-    }
-    // the stepping launch (a single expiry: the plain slice kernel -- the same bits, and the one bench.py profiles); its per-wave
-    // spot partials stay in s->spot_ws, reduce_and_finalize decides who sums them
+    std::vector<int> nbs;
+    std::vector<double> dts;
+    expiry_grids(c, nb_steps_per_year, nbs, dts);                                                        // :840-865
+    // the stepping (a single expiry: the plain slice kernel -- the same bits, and the one bench.py profiles); with one launch its
+    // per-wave spot partials stay in s->spot_ws and reduce_and_finalize decides who sums them, with more each launch reduces its own
     double *qsnap = (variable_type == SVMC_Q_VAR) ? s->snap + static_cast<size_t>(c.m) * n : nullptr;
+    const bool pending = c.m <= MAX_FUSED_SLICES;
     stepping_begin(s);
-    if (c.m > MAX_FUSED_SLICES) {          // more expiries than one stepping launch takes: launch by launch, each reducing its own
-        if (int rc = svmc_logsv_chain_rng_from(0.0, v0, 0.0, s->x, s->vol, s->qvar, n, c.m, nbs.data(), dts.data(), vol_backbone_etas_host,
-                                               c.forwards, theta, kappa1, kappa2, beta, volvol, is_spot_measure, seed, call_id,
-                                               s->path_offset, 0, s->snap, qsnap, s->spot, s->ws, s->ws_bytes, s->stream))
-            return rc;
-        stepping_end(s);
-        return reduce_and_finalize(s, c, variable_type, prices_host, stderrs_host, false);
-    }
     if (int rc = logsv_step_partials(v0, s->x, s->vol, s->qvar, n, c.m, nbs.data(), dts.data(), vol_backbone_etas_host, c.forwards, theta,
                                      kappa1, kappa2, beta, volvol, is_spot_measure, seed, call_id, s->path_offset, s->snap, qsnap,
-                                     s->spot_ws, s->spot_ws_bytes, s->stream))
+                                     pending ? nullptr : s->spot, pending ? s->spot_ws : s->ws, pending ? s->spot_ws_bytes : s->ws_bytes,
+                                     s->stream))
         return rc;
     stepping_end(s);
-    return reduce_and_finalize(s, c, variable_type, prices_host, stderrs_host, true);
+    return reduce_and_finalize(s, c, variable_type, prices_host, stderrs_host, pending);
 }
 
 int svmc_logsv_chain_price_fixed(svmc_session_t session, const double *ttms_host, const double *forwards_host,
@@ -983,28 +980,18 @@ int svmc_heston_chain_price(svmc_session_t session, const double *ttms_host, con
     SVMC_REQUIRE(nb_steps_per_year > 0, "svmc_heston_chain_price: nb_steps_per_year must be positive");
     const size_t n = s->n_path;
     // the start state (0, v0, 0) of every path (:303-305) travels as three constants: no fill launch
-    double t0 = 0.0;
-    std::vector<int> nbs(c.m);
-    std::vector<double> dts(c.m);
-    for (int i = 0; i < c.m; ++i) {                                                                       // :308-329
-        time_grid(c.ttms[i] - t0, nb_steps_per_year, nbs[i], dts[i]);
-        t0 = c.ttms[i];
-    }
+    std::vector<int> nbs;
+    std::vector<double> dts;
+    expiry_grids(c, nb_steps_per_year, nbs, dts);                                                        // :308-329
     double *qsnap = (variable_type == SVMC_Q_VAR) ? s->snap + static_cast<size_t>(c.m) * n : nullptr;
+    const bool pending = c.m <= MAX_FUSED_SLICES;
     stepping_begin(s);
-    if (c.m > MAX_FUSED_SLICES) {
-        if (int rc = svmc_heston_chain_rng_from(0.0, v0, 0.0, s->x, s->vol, s->qvar, n, c.m, nbs.data(), dts.data(), c.forwards, theta, kappa,
-                                                rho, volvol, scheme, seed, call_id, s->path_offset, 0, s->snap, qsnap, s->spot, s->ws,
-                                                s->ws_bytes, s->stream))
-            return rc;
-        stepping_end(s);
-        return reduce_and_finalize(s, c, variable_type, prices_host, stderrs_host, false);
-    }
     if (int rc = heston_step_partials(v0, s->x, s->vol, s->qvar, n, c.m, nbs.data(), dts.data(), c.forwards, theta, kappa, rho, volvol, scheme,
-                                      seed, call_id, s->path_offset, s->snap, qsnap, s->spot_ws, s->spot_ws_bytes, s->stream))
+                                      seed, call_id, s->path_offset, s->snap, qsnap, pending ? nullptr : s->spot,
+                                      pending ? s->spot_ws : s->ws, pending ? s->spot_ws_bytes : s->ws_bytes, s->stream))
         return rc;
     stepping_end(s);
-    return reduce_and_finalize(s, c, variable_type, prices_host, stderrs_host, true);
+    return reduce_and_finalize(s, c, variable_type, prices_host, stderrs_host, pending);
 }
 
 int svmc_hawkesjd_chain_price(svmc_session_t session, const double *ttms_host, const double *forwards_host,
@@ -1021,13 +1008,9 @@ int svmc_hawkesjd_chain_price(svmc_session_t session, const double *ttms_host, c
         return fail(SVMC_ERR_UNSUPPORTED_VARIABLE, "svmc_hawkesjd_chain_price: LOG_RETURN only");
     SVMC_REQUIRE(params_host != nullptr, "svmc_hawkesjd_chain_price: null params");
     SVMC_REQUIRE(nb_steps_per_year > 0, "svmc_hawkesjd_chain_price: nb_steps_per_year must be positive");
-    double t0 = 0.0;
-    std::vector<int> nbs(c.m);
-    std::vector<double> dts(c.m);
-    for (int i = 0; i < c.m; ++i) {                                                                       // :680-700
-        time_grid(c.ttms[i] - t0, nb_steps_per_year, nbs[i], dts[i]);
-        t0 = c.ttms[i];
-    }
+    std::vector<int> nbs;
+    std::vector<double> dts;
+    expiry_grids(c, nb_steps_per_year, nbs, dts);                                                        // :680-700
     // the session's vol / qvar slots hold lambda_p / lambda_m
     const bool pending = c.m <= MAX_FUSED_SLICES;
     stepping_begin(s);

@@ -177,13 +177,6 @@ int check_params(const char *fn, const double *p)
     return SVMC_OK;
 }
 
-int check_launch_h(const char *what)
-{
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(SVMC_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
-    return SVMC_OK;
-}
-
 unsigned hawkes_grid(size_t n) { return static_cast<unsigned>((n + HAWKES_BLOCK - 1) / HAWKES_BLOCK); }
 
 // ---- the transform grid ------------------------------------------------------------------------------------------------
@@ -343,38 +336,18 @@ int hawkes_step_partials(const double *params_host, double *x, double *lam_p, do
 {
     const char *fn = "svmc_hawkesjd_chain_price";
     if (int rc = check_params(fn, params_host)) return rc;
-    SVMC_REQUIRE(x && lam_p && lam_m && x_snapshots && workspace, std::string(fn) + ": null pointer");
-    SVMC_REQUIRE(nb_steps_host && dts_host && forwards_host && n_slices >= 1, std::string(fn) + ": null grids / no slices");
-    SVMC_REQUIRE(spot_sums != nullptr || n_slices <= HAWKES_MAX_SLICES, std::string(fn) + ": unreduced partials need one launch");
-    SVMC_REQUIRE(call_id < (1u << 24), std::string(fn) + ": call_id must fit 24 bits");
-    SVMC_REQUIRE(n_path > 0, std::string(fn) + ": n_path must be positive");
-    for (int i = 0; i < n_slices; ++i)
-        SVMC_REQUIRE(nb_steps_host[i] > 0 && dts_host[i] > 0.0, std::string(fn) + ": nb_steps and dt must be positive");
     const HawkesModel md = make_hawkes_model(params_host);
     const StateInit init = {1, 0.0, params_host[P_LAMBDA_P], params_host[P_LAMBDA_M]};             // :672-674
-    uint32_t step_offset = 0;
-    for (int i0 = 0; i0 < n_slices; i0 += HAWKES_MAX_SLICES) {
-        HawkesChainSlices cs;
-        cs.m = (n_slices - i0 < HAWKES_MAX_SLICES) ? (n_slices - i0) : HAWKES_MAX_SLICES;
-        if (workspace_bytes < static_cast<size_t>(wave_rows(n_path)) * 2 * cs.m * sizeof(double))
-            return fail(SVMC_ERR_WORKSPACE, std::string(fn) + ": workspace too small (svmc_slice_workspace_bytes)");
-        uint32_t steps = 0;
-        for (int i = 0; i < HAWKES_MAX_SLICES; ++i) {
-            const int j = (i < cs.m) ? i0 + i : i0;
-            cs.c[i] = make_hawkes_step(dts_host[j], params_host);
-            cs.forward[i] = forwards_host[j];
-            cs.nb_steps[i] = (i < cs.m) ? nb_steps_host[j] : 0;
-            steps += static_cast<uint32_t>(cs.nb_steps[i]);
-        }
+    const auto fill = [&](HawkesChainSlices &cs, int i, int j) {
+        cs.c[i] = make_hawkes_step(dts_host[j], params_host);
+        cs.forward[i] = forwards_host[j];
+    };
+    const auto launch = [&](const HawkesChainSlices &cs, double *xs, double *, const StateInit &init_i, uint32_t step0) {
         hipLaunchKernelGGL(hawkesjd_chain_rng_kernel, dim3(hawkes_grid(n_path)), dim3(HAWKES_BLOCK), 0, stream, x, lam_p, lam_m, n_path,
-                           cs, md, seed, call_id << 8, path_offset, step_offset, x_snapshots + static_cast<size_t>(i0) * n_path,
-                           static_cast<double *>(workspace), (i0 == 0) ? init : StateInit());
-        if (int rc = check_launch_h(fn)) return rc;
-        if (spot_sums != nullptr)
-            if (int rc = reduce_spot_partials(workspace, n_path, 2 * cs.m, spot_sums + 2 * i0, stream)) return rc;
-        step_offset += steps;
-    }
-    return SVMC_OK;
+                           cs, md, seed, call_id << 8, path_offset, step0, xs, static_cast<double *>(workspace), init_i);
+    };
+    return step_chain<HawkesChainSlices>(fn, init, x, lam_p, lam_m, n_path, n_slices, nb_steps_host, dts_host, forwards_host, call_id,
+                                         0, x_snapshots, nullptr, spot_sums, workspace, workspace_bytes, stream, fill, launch);
 }
 
 }  // namespace svmc
@@ -403,7 +376,7 @@ int svmc_hawkesjd_terminal_rng(double *x, double *lambda_p, double *lambda_m, si
     }
     hipLaunchKernelGGL(hawkesjd_rng_kernel, dim3(hawkes_grid(n_path)), dim3(HAWKES_BLOCK), 0, as_stream(stream), x, lambda_p, lambda_m,
                        n_path, cs, make_hawkes_model(params_host), seed, call_id << 8, path_offset, step_offset);
-    return check_launch_h(fn);
+    return check_launch(fn);
 }
 
 int svmc_hawkesjd_mgf_grid(const double *phi, const double *psi, size_t n_grid, double ttm, const double *params_host, double *a,
@@ -418,7 +391,7 @@ int svmc_hawkesjd_mgf_grid(const double *phi, const double *psi, size_t n_grid, 
                        as_stream(stream), reinterpret_cast<const cd *>(phi), reinterpret_cast<const cd *>(psi), n_grid, ttm,
                        make_hawkes_ode(params_host), params_host[P_LAMBDA_P], params_host[P_LAMBDA_M], reinterpret_cast<cd *>(a),
                        reinterpret_cast<cd *>(log_mgf), rtol, atol);
-    return check_launch_h(fn);
+    return check_launch(fn);
 }
 
 }  // extern "C"

@@ -64,18 +64,19 @@ int payoff_sums_chain_sets(const double *const *x_snapshots_host, const double *
                            const size_t *strike_offsets_host, int variable_type, double *sums, void *workspace,
                            size_t workspace_bytes, hipStream_t stream, int n_sets, size_t x_set_stride, size_t q_set_stride,
                            size_t spot_set_stride);
-// ---- the one-device tail of an on-device-RNG chain (round 6): stepping WITHOUT the reduce of its per-wave spot partials, then the
-// payoff kernel (up to 2048 partial rows: every block sums its expiry's two columns itself) and chain_finish_kernel (a wave per
-// quote: column sums in reduce_columns_kernel's order, stored where the host reads them)
+// ---- the one-device tail of an on-device-RNG chain (round 6): stepping that leaves its per-wave spot partials in `workspace`
+// (spot_sums null, at most MAX_FUSED_SLICES expiries) or reduces them into spot_sums, then the payoff kernel (up to 2048 partial
+// rows: every block sums its expiry's two columns itself) and chain_finish_kernel (a wave per quote: column sums in
+// reduce_columns_kernel's order, stored where the host reads them)
 int logsv_step_partials(double sigma0, double *x, double *sigma, double *qvar, size_t n_path, int n_slices, const int *nb_steps_host,
                         const double *dts_host, const double *etas_host, const double *forwards_host, double theta, double kappa1,
                         double kappa2, double beta, double volvol, int is_spot_measure, uint64_t seed, uint32_t call_id,
-                        uint64_t path_offset, double *x_snapshots, double *qvar_snapshots, void *workspace, size_t workspace_bytes,
-                        hipStream_t stream);
+                        uint64_t path_offset, double *x_snapshots, double *qvar_snapshots, double *spot_sums, void *workspace,
+                        size_t workspace_bytes, hipStream_t stream);
 int heston_step_partials(double var0, double *x, double *var, double *qvar, size_t n_path, int n_slices, const int *nb_steps_host,
                          const double *dts_host, const double *forwards_host, double theta, double kappa, double rho, double volvol,
                          int scheme, uint64_t seed, uint32_t call_id, uint64_t path_offset, double *x_snapshots,
-                         double *qvar_snapshots, void *workspace, size_t workspace_bytes, hipStream_t stream);
+                         double *qvar_snapshots, double *spot_sums, void *workspace, size_t workspace_bytes, hipStream_t stream);
 // svmc_hawkes.hip: the Hawkes jump-diffusion chain's stepping from (0, lambda_p, lambda_m) (params: SVMC_HAWKESJD_PARAMS doubles)
 int hawkes_step_partials(const double *params_host, double *x, double *lam_p, double *lam_m, size_t n_path, int n_slices,
                          const int *nb_steps_host, const double *dts_host, const double *forwards_host, uint64_t seed,
@@ -83,6 +84,47 @@ int hawkes_step_partials(const double *params_host, double *x, double *lam_p, do
                          size_t workspace_bytes, hipStream_t stream);
 bool spot_sums_in_payoff_kernel(size_t n_path);
 int reduce_spot_partials(const void *workspace, size_t n_path, int n_cols, double *spot_sums, hipStream_t stream);
+int check_launch(const char *what);          // hipGetLastError -> SVMC_ERR_HIP "what: ..."
+
+// The chain stepping of every on-device-RNG generator (LogSV, Heston: svmc_kernels.hip; Hawkes: svmc_hawkes.hip): the argument
+// checks, launches of at most MAX_FUSED_SLICES expiries whose unused slice entries repeat a valid one, the step offset carried
+// from launch to launch, and the reduce of each launch's per-wave spot partials into spot_sums -- with spot_sums null (one launch
+// at most) they stay in `workspace`.  The model supplies fill(cs, i, j): entry i of its slices struct from expiry j (nb_steps and
+// m are set here), and launch(cs, x_snap, q_snap, init, step_offset): one batch from its snapshot rows (q_snap nullable).
+template <class Slices, class Init, class Fill, class Launch>
+int step_chain(const char *fn, const Init &init, const double *x, const double *v, const double *q, size_t n_path, int n_slices,
+               const int *nb_steps_host, const double *dts_host, const double *forwards_host, uint32_t call_id, uint32_t step_offset,
+               double *x_snapshots, double *qvar_snapshots, double *spot_sums, void *workspace, size_t workspace_bytes,
+               hipStream_t stream, Fill &&fill, Launch &&launch)
+{
+    SVMC_REQUIRE(x && v && q && x_snapshots && workspace, std::string(fn) + ": null pointer");
+    SVMC_REQUIRE(nb_steps_host && dts_host && forwards_host && n_slices >= 1, std::string(fn) + ": null grids / no slices");
+    SVMC_REQUIRE(spot_sums != nullptr || n_slices <= MAX_FUSED_SLICES, std::string(fn) + ": unreduced partials need one launch");
+    SVMC_REQUIRE(call_id < (1u << 24), std::string(fn) + ": call_id must fit 24 bits");
+    SVMC_REQUIRE(n_path > 0, std::string(fn) + ": n_path must be positive");
+    for (int i = 0; i < n_slices; ++i)
+        SVMC_REQUIRE(nb_steps_host[i] > 0 && dts_host[i] > 0.0, std::string(fn) + ": nb_steps and dt must be positive");
+    for (int i0 = 0; i0 < n_slices; i0 += MAX_FUSED_SLICES) {
+        Slices cs;
+        cs.m = (n_slices - i0 < MAX_FUSED_SLICES) ? (n_slices - i0) : MAX_FUSED_SLICES;
+        if (workspace_bytes < static_cast<size_t>(wave_rows(n_path)) * 2 * cs.m * sizeof(double))
+            return fail(SVMC_ERR_WORKSPACE, std::string(fn) + ": workspace too small (svmc_slice_workspace_bytes)");
+        uint32_t steps = 0;
+        for (int i = 0; i < MAX_FUSED_SLICES; ++i) {
+            const int j = (i < cs.m) ? i0 + i : i0;
+            cs.nb_steps[i] = (i < cs.m) ? nb_steps_host[j] : 0;
+            steps += static_cast<uint32_t>(cs.nb_steps[i]);
+            fill(cs, i, j);
+        }
+        const size_t row = static_cast<size_t>(i0) * n_path;
+        launch(cs, x_snapshots + row, qvar_snapshots ? qvar_snapshots + row : nullptr, (i0 == 0) ? init : Init(), step_offset);
+        if (int rc = check_launch(fn)) return rc;
+        if (spot_sums != nullptr)
+            if (int rc = reduce_spot_partials(workspace, n_path, 2 * cs.m, spot_sums + 2 * i0, stream)) return rc;
+        step_offset += steps;
+    }
+    return SVMC_OK;
+}
 int chain_payoff_and_finish(const double *const *x_snapshots_host, const double *const *qvar_snapshots_host, size_t n_path,
                             const double *forwards_host, const double *ttms_host, double *spot_sums, const double *spot_partials,
                             int n_expiries, const double *strikes_host, const int8_t *types_host, const double *shifts_host,

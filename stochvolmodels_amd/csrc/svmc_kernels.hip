@@ -492,7 +492,7 @@ struct ChainSlices {
     LogsvFast c[MAX_CHAIN_SLICES];
     double forward[MAX_CHAIN_SLICES];
     int nb_steps[MAX_CHAIN_SLICES];
-    int m, total_steps;
+    int m, total_steps = 0;
 };
 
 #ifndef SVMC_CHAIN_WAVES
@@ -2009,7 +2009,7 @@ static inline unsigned reduce_grid(size_t n)
     return static_cast<unsigned>(g < 1 ? 1 : (g > MAX_REDUCE_GRID ? MAX_REDUCE_GRID : g));
 }
 
-static int check_launch(const char *what)
+int check_launch(const char *what)
 {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(SVMC_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
@@ -2086,14 +2086,6 @@ static int logsv_rng_launch(const char *fn, double *x, double *sigma, double *qv
     return check_launch(fn);
 }
 
-// the [wave][2] spot partials of a fused slice kernel -> spot_sums[2]
-static int finish_slice_sums(const char *fn, unsigned block_rows, double *spot_sums, void *workspace, svmc_stream_t stream)
-{
-    hipLaunchKernelGGL(reduce_columns_kernel, dim3(2), dim3(BLOCK), 0, as_stream(stream),
-                       static_cast<const double *>(workspace), block_rows, size_t(1), static_cast<size_t>(block_rows), spot_sums);
-    return check_launch(fn);
-}
-
 // allow_null_spot (the two on-device-RNG slice launchers, for their internal callers only -- the public entry points reject a null
 // spot_sums first): with spot_sums == nullptr the launch leaves its per-wave partial columns in the workspace unreduced, and the
 // payoff kernel of svmc_chain.hip's one-device tail sums them itself
@@ -2133,7 +2125,7 @@ static int logsv_slice_rng_impl(const char *fn, const StateInit &init, double *x
                                   vol_backbone_eta, is_spot_measure, seed, call_id, path_offset, step_offset, so, stream, init))
         return rc;
     if (spot_sums == nullptr) return SVMC_OK;
-    return finish_slice_sums(fn, wave_rows(n_path), spot_sums, workspace, stream);
+    return reduce_spot_partials(workspace, n_path, 2, spot_sums, as_stream(stream));
 }
 
 extern "C" {
@@ -2173,45 +2165,24 @@ static int logsv_chain_rng_impl(const char *fn, const StateInit &init, double *x
                          double *qvar_snapshots, double *spot_sums, void *workspace, size_t workspace_bytes,
                          svmc_stream_t stream)
 {
-    SVMC_REQUIRE(x && sigma && qvar && x_snapshots && workspace, std::string(fn) + ": null pointer");
-    SVMC_REQUIRE(nb_steps_host && dts_host && forwards_host && n_slices >= 1, std::string(fn) + ": null grids / no slices");
-    SVMC_REQUIRE(spot_sums != nullptr || n_slices <= MAX_CHAIN_SLICES, std::string(fn) + ": unreduced partials need one launch");
-    SVMC_REQUIRE(call_id < (1u << 24), std::string(fn) + ": call_id must fit 24 bits");
-    SVMC_REQUIRE(n_path > 0, std::string(fn) + ": n_path must be positive");
-    for (int i = 0; i < n_slices; ++i)
-        SVMC_REQUIRE(nb_steps_host[i] > 0 && dts_host[i] > 0.0, std::string(fn) + ": nb_steps and dt must be positive");
-    const unsigned g = chain_grid(n_path);
-    for (int i0 = 0; i0 < n_slices; i0 += MAX_CHAIN_SLICES) {
-        ChainSlices cs;
-        cs.m = (n_slices - i0 < MAX_CHAIN_SLICES) ? (n_slices - i0) : MAX_CHAIN_SLICES;
-        if (workspace_bytes < static_cast<size_t>(wave_rows(n_path)) * 2 * cs.m * sizeof(double))
-            return fail(SVMC_ERR_WORKSPACE, std::string(fn) + ": workspace too small (svmc_slice_workspace_bytes)");
-        cs.total_steps = 0;
-        for (int i = 0; i < MAX_CHAIN_SLICES; ++i) {
-            const int j = (i < cs.m) ? i0 + i : i0;        // unused entries repeat a valid one
-            cs.c[i] = logsv_fast_in_log_units(make_logsv_fast(make_logsv_consts(
-                dts_host[j], theta, kappa1, kappa2, beta, volvol, etas_host ? etas_host[j] : 1.0, is_spot_measure)));
-            cs.forward[i] = forwards_host[j];
-            cs.nb_steps[i] = (i < cs.m) ? nb_steps_host[j] : 0;
-            cs.total_steps += cs.nb_steps[i];
-        }
-        double *xs = x_snapshots + static_cast<size_t>(i0) * n_path;
-        double *qs = qvar_snapshots ? qvar_snapshots + static_cast<size_t>(i0) * n_path : nullptr;
+    const auto fill = [&](ChainSlices &cs, int i, int j) {
+        cs.c[i] = logsv_fast_in_log_units(make_logsv_fast(make_logsv_consts(
+            dts_host[j], theta, kappa1, kappa2, beta, volvol, etas_host ? etas_host[j] : 1.0, is_spot_measure)));
+        cs.forward[i] = forwards_host[j];
+        cs.total_steps += cs.nb_steps[i];
+    };
+    const auto launch = [&](const ChainSlices &cs, double *xs, double *qs, const StateInit &init_i, uint32_t step0) {
+        double *const ws = static_cast<double *>(workspace);
         if (const LogsvLatVariant *v = logsv_lat_variant(n_path))
             hipLaunchKernelGGL(v->chain, dim3(lat_grid(n_path, v->block)), dim3(v->block), 0, as_stream(stream), x, sigma, qvar, n_path,
-                               cs, seed, make_c3(call_id), path_offset, step_offset, xs, qs, static_cast<double *>(workspace),
-                               (i0 == 0) ? init : StateInit(), armed_probe());
+                               cs, seed, make_c3(call_id), path_offset, step0, xs, qs, ws, init_i, armed_probe());
         else
-            hipLaunchKernelGGL(logsv_chain_rng_kernel, dim3(g), dim3(CHAIN_BLOCK), 0, as_stream(stream), x, sigma, qvar, n_path,
-                               cs, seed, make_c3(call_id), path_offset, step_offset, xs, qs, static_cast<double *>(workspace),
-                               (i0 == 0) ? init : StateInit(), armed_probe());
-        if (spot_sums != nullptr)
-            hipLaunchKernelGGL(reduce_columns_kernel, dim3(2 * cs.m), dim3(BLOCK), 0, as_stream(stream),
-                               static_cast<const double *>(workspace), wave_rows(n_path), size_t(1), static_cast<size_t>(wave_rows(n_path)), spot_sums + 2 * i0);
-        if (int rc = check_launch(fn)) return rc;
-        step_offset += static_cast<uint32_t>(cs.total_steps);
-    }
-    return SVMC_OK;
+            hipLaunchKernelGGL(logsv_chain_rng_kernel, dim3(chain_grid(n_path)), dim3(CHAIN_BLOCK), 0, as_stream(stream), x, sigma, qvar,
+                               n_path, cs, seed, make_c3(call_id), path_offset, step0, xs, qs, ws, init_i, armed_probe());
+    };
+    return step_chain<ChainSlices>(fn, init, x, sigma, qvar, n_path, n_slices, nb_steps_host, dts_host, forwards_host, call_id,
+                                   step_offset, x_snapshots, qvar_snapshots, spot_sums, workspace, workspace_bytes, as_stream(stream),
+                                   fill, launch);
 }
 
 extern "C" {
@@ -2283,7 +2254,7 @@ int svmc_logsv_slice_w(double *x, double *sigma, double *qvar, size_t n_path, in
     if (int rc = logsv_w_launch(fn, x, sigma, qvar, n_path, nb_steps, dt, theta, kappa1, kappa2, beta, volvol,
                                 vol_backbone_eta, is_spot_measure, W0, W1, ldw, so, stream))
         return rc;
-    return finish_slice_sums(fn, wave_rows(n_path), spot_sums, workspace, stream);
+    return reduce_spot_partials(workspace, n_path, 2, spot_sums, as_stream(stream));
 }
 
 }  // extern "C"
@@ -2312,7 +2283,7 @@ int logsv_slice_w_indirect(double *x, double *sigma, double *qvar, size_t n_path
     hipLaunchKernelGGL(logsv_w_indirect_kernel, dim3(grid_for(n_path)), dim3(BLOCK), 0, stream, x, sigma, qvar, n_path,
                        nb_steps, reinterpret_cast<const LogsvConsts *>(consts_dev), W0, W1, ldw, so);
     if (int rc = check_launch(fn)) return rc;
-    return finish_slice_sums(fn, wave_rows(n_path), spot_sums, workspace, reinterpret_cast<svmc_stream_t>(stream));
+    return reduce_spot_partials(workspace, n_path, 2, spot_sums, stream);
 }
 
 // every expiry of a chain on resident randoms in one launch + one column reduce (graph-replayed driver, svmc_chain.hip):
@@ -2620,13 +2591,20 @@ static const HestonLatVariant HESTON_LAT_VARIANTS[3][N_HESTON_LAT_VARIANTS] = {
     }};
 #undef SVMC_HESTON_LAT
 
-static const HestonLatVariant *heston_lat_variant(int scheme, size_t n_path)
+// the full-launch kernels, per kernel scheme id (0, 1 or HESTON_QE_QUAD)
+static const HestonLatVariant HESTON_FULL_KERNELS[3] = {
+    {heston_rng_kernel<SVMC_HESTON_EULER_FLOOR>, heston_chain_rng_kernel<SVMC_HESTON_EULER_FLOOR>, RNG_BLOCK},
+    {heston_rng_kernel<SVMC_HESTON_QE>, heston_chain_rng_kernel<SVMC_HESTON_QE>, RNG_BLOCK},
+    {heston_rng_kernel<HESTON_QE_QUAD>, heston_chain_rng_kernel<HESTON_QE_QUAD>, RNG_BLOCK}};
+
+// -> the kernels a launch of n_path paths of kernel scheme `scheme` runs: a few-waves form or the full-launch ones
+static const HestonLatVariant *heston_variant(int scheme, size_t n_path)
 {
-    const HestonLatVariant *row = HESTON_LAT_VARIANTS[scheme];       // kernel scheme id: 0, 1 or HESTON_QE_QUAD
+    const HestonLatVariant *row = HESTON_LAT_VARIANTS[scheme];
     const int forced = forced_gen_variant();
-    if (forced == -1) return nullptr;
+    if (forced == -1) return &HESTON_FULL_KERNELS[scheme];
     if (forced >= 0) return &row[forced < N_HESTON_LAT_VARIANTS ? forced : 0];
-    return few_waves_launch(n_path) ? &row[0] : nullptr;
+    return few_waves_launch(n_path) ? &row[0] : &HESTON_FULL_KERNELS[scheme];
 }
 
 static int heston_rng_launch(const char *fn, double *x, double *var, double *qvar, size_t n_path, int nb_steps, double dt,
@@ -2641,19 +2619,9 @@ static int heston_rng_launch(const char *fn, double *x, double *var, double *qva
     if (n_path == 0) return SVMC_OK;
     const HestonConsts c = make_heston_consts(dt, theta, kappa, rho, volvol);
     const QeConsts qc = make_qe_consts(dt, theta, kappa, rho, volvol);
-    const int ks = heston_kernel_scheme(scheme, qc);
-    if (const HestonLatVariant *v = heston_lat_variant(ks, n_path))
-        hipLaunchKernelGGL(v->slice, dim3(lat_grid(n_path, v->block)), dim3(v->block), 0, as_stream(stream), x, var, qvar, n_path, nb_steps,
-                           c, qc, seed, make_c3(call_id), path_offset, step_offset, so, init);
-    else if (ks == HESTON_QE_QUAD)
-        hipLaunchKernelGGL(heston_rng_kernel<HESTON_QE_QUAD>, dim3(rng_grid(n_path)), dim3(rng_block()), 0, as_stream(stream), x, var, qvar,
-                           n_path, nb_steps, c, qc, seed, make_c3(call_id), path_offset, step_offset, so, init);
-    else if (scheme == SVMC_HESTON_QE)
-        hipLaunchKernelGGL(heston_rng_kernel<SVMC_HESTON_QE>, dim3(rng_grid(n_path)), dim3(rng_block()), 0, as_stream(stream), x, var, qvar,
-                           n_path, nb_steps, c, qc, seed, make_c3(call_id), path_offset, step_offset, so, init);
-    else
-        hipLaunchKernelGGL(heston_rng_kernel<SVMC_HESTON_EULER_FLOOR>, dim3(rng_grid(n_path)), dim3(rng_block()), 0, as_stream(stream), x,
-                           var, qvar, n_path, nb_steps, c, qc, seed, make_c3(call_id), path_offset, step_offset, so, init);
+    const HestonLatVariant *v = heston_variant(heston_kernel_scheme(scheme, qc), n_path);
+    hipLaunchKernelGGL(v->slice, dim3(lat_grid(n_path, v->block)), dim3(v->block), 0, as_stream(stream), x, var, qvar, n_path, nb_steps, c,
+                       qc, seed, make_c3(call_id), path_offset, step_offset, so, init);
     return check_launch(fn);
 }
 
@@ -2682,7 +2650,7 @@ static int heston_slice_rng_impl(const char *fn, const StateInit &init, double *
                                    call_id, path_offset, step_offset, so, stream, init))
         return rc;
     if (spot_sums == nullptr) return SVMC_OK;
-    return finish_slice_sums(fn, wave_rows(n_path), spot_sums, workspace, stream);
+    return reduce_spot_partials(workspace, n_path, 2, spot_sums, as_stream(stream));
 }
 
 extern "C" {
@@ -2720,58 +2688,26 @@ static int heston_chain_rng_impl(const char *fn, const StateInit &init, double *
                           uint32_t step_offset, double *x_snapshots, double *qvar_snapshots, double *spot_sums,
                           void *workspace, size_t workspace_bytes, svmc_stream_t stream)
 {
-    SVMC_REQUIRE(x && var && qvar && x_snapshots && workspace, std::string(fn) + ": null pointer");
-    SVMC_REQUIRE(nb_steps_host && dts_host && forwards_host && n_slices >= 1, std::string(fn) + ": null grids / no slices");
-    SVMC_REQUIRE(spot_sums != nullptr || n_slices <= MAX_CHAIN_SLICES, std::string(fn) + ": unreduced partials need one launch");
     SVMC_REQUIRE(scheme == SVMC_HESTON_EULER_FLOOR || scheme == SVMC_HESTON_QE, std::string(fn) + ": unknown scheme");
-    SVMC_REQUIRE(call_id < (1u << 24), std::string(fn) + ": call_id must fit 24 bits");
-    SVMC_REQUIRE(n_path > 0, std::string(fn) + ": n_path must be positive");
-    for (int i = 0; i < n_slices; ++i)
-        SVMC_REQUIRE(nb_steps_host[i] > 0 && dts_host[i] > 0.0, std::string(fn) + ": nb_steps and dt must be positive");
-    const unsigned g = rng_grid(n_path);
-    for (int i0 = 0; i0 < n_slices; i0 += MAX_CHAIN_SLICES) {
-        HestonChainSlices cs;
-        cs.m = (n_slices - i0 < MAX_CHAIN_SLICES) ? (n_slices - i0) : MAX_CHAIN_SLICES;
-        if (workspace_bytes < static_cast<size_t>(wave_rows(n_path)) * 2 * cs.m * sizeof(double))
-            return fail(SVMC_ERR_WORKSPACE, std::string(fn) + ": workspace too small (svmc_slice_workspace_bytes)");
-        int steps = 0;
-        for (int i = 0; i < MAX_CHAIN_SLICES; ++i) {
-            const int j = (i < cs.m) ? i0 + i : i0;
-            cs.c[i] = make_heston_consts(dts_host[j], theta, kappa, rho, volvol);
-            cs.qc[i] = make_qe_consts(dts_host[j], theta, kappa, rho, volvol);
-            cs.forward[i] = forwards_host[j];
-            cs.nb_steps[i] = (i < cs.m) ? nb_steps_host[j] : 0;
-            steps += cs.nb_steps[i];
-        }
-        double *xs = x_snapshots + static_cast<size_t>(i0) * n_path;
-        double *qs = qvar_snapshots ? qvar_snapshots + static_cast<size_t>(i0) * n_path : nullptr;
-        const StateInit init_i = (i0 == 0) ? init : StateInit();
-        double *const ws = static_cast<double *>(workspace);
+    const auto fill = [&](HestonChainSlices &cs, int i, int j) {
+        cs.c[i] = make_heston_consts(dts_host[j], theta, kappa, rho, volvol);
+        cs.qc[i] = make_qe_consts(dts_host[j], theta, kappa, rho, volvol);
+        cs.forward[i] = forwards_host[j];
+    };
+    const auto launch = [&](const HestonChainSlices &cs, double *xs, double *qs, const StateInit &init_i, uint32_t step0) {
         int ks = scheme;
         if (scheme == SVMC_HESTON_QE) {                    // the specialised kernel only if EVERY slice of the launch allows it
             ks = HESTON_QE_QUAD;
             for (int i = 0; i < cs.m; ++i)
                 if (heston_kernel_scheme(scheme, cs.qc[i]) != HESTON_QE_QUAD) ks = scheme;
         }
-        if (const HestonLatVariant *v = heston_lat_variant(ks, n_path))
-            hipLaunchKernelGGL(v->chain, dim3(lat_grid(n_path, v->block)), dim3(v->block), 0, as_stream(stream), x, var, qvar, n_path, cs,
-                               seed, make_c3(call_id), path_offset, step_offset, xs, qs, ws, init_i);
-        else if (ks == HESTON_QE_QUAD)
-            hipLaunchKernelGGL(heston_chain_rng_kernel<HESTON_QE_QUAD>, dim3(g), dim3(rng_block()), 0, as_stream(stream), x, var, qvar,
-                               n_path, cs, seed, make_c3(call_id), path_offset, step_offset, xs, qs, ws, init_i);
-        else if (scheme == SVMC_HESTON_QE)
-            hipLaunchKernelGGL(heston_chain_rng_kernel<SVMC_HESTON_QE>, dim3(g), dim3(rng_block()), 0, as_stream(stream), x, var, qvar,
-                               n_path, cs, seed, make_c3(call_id), path_offset, step_offset, xs, qs, ws, init_i);
-        else
-            hipLaunchKernelGGL(heston_chain_rng_kernel<SVMC_HESTON_EULER_FLOOR>, dim3(g), dim3(rng_block()), 0, as_stream(stream), x, var,
-                               qvar, n_path, cs, seed, make_c3(call_id), path_offset, step_offset, xs, qs, ws, init_i);
-        if (spot_sums != nullptr)
-            hipLaunchKernelGGL(reduce_columns_kernel, dim3(2 * cs.m), dim3(BLOCK), 0, as_stream(stream),
-                               static_cast<const double *>(workspace), wave_rows(n_path), size_t(1), static_cast<size_t>(wave_rows(n_path)), spot_sums + 2 * i0);
-        if (int rc = check_launch(fn)) return rc;
-        step_offset += static_cast<uint32_t>(steps);
-    }
-    return SVMC_OK;
+        const HestonLatVariant *v = heston_variant(ks, n_path);
+        hipLaunchKernelGGL(v->chain, dim3(lat_grid(n_path, v->block)), dim3(v->block), 0, as_stream(stream), x, var, qvar, n_path, cs, seed,
+                           make_c3(call_id), path_offset, step0, xs, qs, static_cast<double *>(workspace), init_i);
+    };
+    return step_chain<HestonChainSlices>(fn, init, x, var, qvar, n_path, n_slices, nb_steps_host, dts_host, forwards_host, call_id,
+                                         step_offset, x_snapshots, qvar_snapshots, spot_sums, workspace, workspace_bytes,
+                                         as_stream(stream), fill, launch);
 }
 
 extern "C" {
@@ -2916,7 +2852,7 @@ int svmc_rough_logsv_slice(double *log_s, double *vol, double *qvar, size_t n_pa
                                     v0_host, theta, kappa1, kappa2, rho, volvol, Z0, Z1, ldw, seed, call_id,
                                     path_offset, step_offset, from_origin, so, stream))
         return rc;
-    return finish_slice_sums(fn, wave_rows(n_path), spot_sums, workspace, stream);
+    return reduce_spot_partials(workspace, n_path, 2, spot_sums, as_stream(stream));
 }
 
 int svmc_rough_logsv_chain(double *log_s, double *vol, double *qvar, size_t n_path, int n_expiries, const int *nb_steps_host,
@@ -3220,6 +3156,8 @@ int payoff_sums_chain_sets(const double *const *x_snapshots_host, const double *
 // sets 19 -> 31 us), and the implied vols inside the finish kernel (one lane of 52 waves on 13 CUs: 24.6 us against 5.0 + 12.2
 // for reduce + chain_implied_vols_kernel, whose one wave inverts 64 quotes side by side) -- profiles/r06_frozen_trace.txt.
 // The chain must fit one payoff launch (payoff_sets_fit).
+// a virtual thread sums four rows: no payoff launch may produce more partial rows than that
+static_assert(PAYOFF_BLOCKS <= 4u * BLOCK && MAX_REDUCE_GRID <= 4 * BLOCK, "chain_finish_kernel sums at most 4 x BLOCK rows");
 __global__ __launch_bounds__(BLOCK) void chain_finish_kernel(const double *__restrict__ partials, unsigned n_rows, int cols,
                                                              double *__restrict__ sums_out)
 {
@@ -3272,38 +3210,38 @@ int chain_payoff_and_finish(const double *const *x_snapshots_host, const double 
     return check_launch(fn);
 }
 
-// the stepping launch of a chain WITHOUT the reduce of its per-wave partial columns (they stay in `workspace`):
-// svmc_*_slice_rng_from / svmc_*_chain_rng_from with spot_sums = null, for svmc_chain.hip's one-device tail
+// the stepping of svmc_chain.hip's fused chains from the start state (0, sigma0 | var0, 0): svmc_*_chain_rng_from, or the slice
+// kernel for a single expiry; spot_sums null leaves the per-wave partial columns in `workspace` for the one-device tail
 int logsv_step_partials(double sigma0, double *x, double *sigma, double *qvar, size_t n_path, int n_slices, const int *nb_steps_host,
                         const double *dts_host, const double *etas_host, const double *forwards_host, double theta, double kappa1,
                         double kappa2, double beta, double volvol, int is_spot_measure, uint64_t seed, uint32_t call_id,
-                        uint64_t path_offset, double *x_snapshots, double *qvar_snapshots, void *workspace, size_t workspace_bytes,
-                        hipStream_t stream)
+                        uint64_t path_offset, double *x_snapshots, double *qvar_snapshots, double *spot_sums, void *workspace,
+                        size_t workspace_bytes, hipStream_t stream)
 {
     const StateInit init = {1, 0.0, sigma0, 0.0};
     const svmc_stream_t st = reinterpret_cast<svmc_stream_t>(stream);
     if (n_slices == 1)
         return logsv_slice_rng_impl("logsv_step_partials", init, x, sigma, qvar, n_path, nb_steps_host[0], dts_host[0], theta, kappa1,
                                     kappa2, beta, volvol, etas_host ? etas_host[0] : 1.0, is_spot_measure, seed, call_id, path_offset, 0,
-                                    forwards_host[0], x_snapshots, qvar_snapshots, nullptr, workspace, workspace_bytes, st);
+                                    forwards_host[0], x_snapshots, qvar_snapshots, spot_sums, workspace, workspace_bytes, st);
     return logsv_chain_rng_impl("logsv_step_partials", init, x, sigma, qvar, n_path, n_slices, nb_steps_host, dts_host, etas_host,
                                 forwards_host, theta, kappa1, kappa2, beta, volvol, is_spot_measure, seed, call_id, path_offset, 0,
-                                x_snapshots, qvar_snapshots, nullptr, workspace, workspace_bytes, st);
+                                x_snapshots, qvar_snapshots, spot_sums, workspace, workspace_bytes, st);
 }
 
 int heston_step_partials(double var0, double *x, double *var, double *qvar, size_t n_path, int n_slices, const int *nb_steps_host,
                          const double *dts_host, const double *forwards_host, double theta, double kappa, double rho, double volvol,
                          int scheme, uint64_t seed, uint32_t call_id, uint64_t path_offset, double *x_snapshots,
-                         double *qvar_snapshots, void *workspace, size_t workspace_bytes, hipStream_t stream)
+                         double *qvar_snapshots, double *spot_sums, void *workspace, size_t workspace_bytes, hipStream_t stream)
 {
     const StateInit init = {1, 0.0, var0, 0.0};
     const svmc_stream_t st = reinterpret_cast<svmc_stream_t>(stream);
     if (n_slices == 1)
         return heston_slice_rng_impl("heston_step_partials", init, x, var, qvar, n_path, nb_steps_host[0], dts_host[0], theta, kappa, rho,
                                      volvol, scheme, seed, call_id, path_offset, 0, forwards_host[0], x_snapshots, qvar_snapshots,
-                                     nullptr, workspace, workspace_bytes, st);
+                                     spot_sums, workspace, workspace_bytes, st);
     return heston_chain_rng_impl("heston_step_partials", init, x, var, qvar, n_path, n_slices, nb_steps_host, dts_host, forwards_host,
-                                 theta, kappa, rho, volvol, scheme, seed, call_id, path_offset, 0, x_snapshots, qvar_snapshots, nullptr,
+                                 theta, kappa, rho, volvol, scheme, seed, call_id, path_offset, 0, x_snapshots, qvar_snapshots, spot_sums,
                                  workspace, workspace_bytes, st);
 }
 

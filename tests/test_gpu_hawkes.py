@@ -80,6 +80,32 @@ def test_shard_invariance(golden):
         assert np.array_equal(np.concatenate([parts[0][k], parts[1][k]]), whole[k])
 
 
+def test_chain_of_more_than_16_expiries_matches_the_twin():
+    # 18 expiries: two stepping launches, each reducing its own spot partials, the second continuing the chain-global steps
+    from stochvolmodels_amd.engine import get_engine
+    from stochvolmodels_amd.pricers import hawkes_jd_pricer as hp
+    p = hp.HawkesJDParams()
+    kw = {k: getattr(p, k) for k in twin.PARAM_NAMES}
+    m, n, seed, spy = 18, 4096, 31, 360
+    ttms = 0.02 * np.arange(1, m + 1)
+    fw, df = np.exp(0.01 * ttms), np.exp(-0.02 * ttms)
+    ks = [f * np.array([0.9, 1.0, 1.1]) for f in fw]
+    ts = [np.array(["P", "C", "C"])] * m
+    pr, sd = hp.hawkesjd_mc_chain_pricer(ttms=ttms, forwards=fw, discfactors=df, strikes_ttms=ks, optiontypes_ttms=ts, nb_path=n,
+                                         seed=seed, nb_steps_per_year=spy, **kw)
+    tp, tsd, _ = twin.mc_chain(ttms, fw, df, ks, ts, kw, n, seed, nb_steps_per_year=spy)
+    np.testing.assert_allclose(np.concatenate(pr), np.concatenate(tp), rtol=1e-11, atol=1e-14)
+    np.testing.assert_allclose(np.concatenate(sd), np.concatenate(tsd), rtol=1e-11, atol=1e-14)
+    x, lp, lm = get_engine(n).get_state()
+    tx, tlp, tlm = np.zeros(n), p.lambda_p * np.ones(n), p.lambda_m * np.ones(n)
+    t0, step0 = 0.0, 0
+    for ttm in ttms:
+        tx, tlp, tlm, nb = twin.simulate_terminal(ttm - t0, tx, tlp, tlm, kw, seed, step0=step0, nb_steps_per_year=spy)
+        t0, step0 = ttm, step0 + nb
+    for a, b in ((x, tx), (lp, tlp), (lm, tlm)):
+        np.testing.assert_allclose(a, b, rtol=1e-12, atol=1e-12)
+
+
 def test_c_abi_matches_the_python_route(golden):
     from stochvolmodels_amd import _lib
     from stochvolmodels_amd.engine import get_engine, option_type_codes
