@@ -1,9 +1,10 @@
 """
-Build recipe of libsvmc.so (the only native artefact of the package): hipcc, gfx950 only, in-tree.
+Build recipe of libsvmc.so (the only native artefact of the package): hipcc, gfx950 only, in-tree.  It also builds the
+test-only device probe tests/native/libsvmc_device_probe.so with the same flags.
 
     python -m stochvolmodels_amd.build [--force]
 
-hipcc cross-compiles without a GPU; the resulting .so is git-ignored but travels with the tree.
+hipcc cross-compiles without a GPU; the resulting .so files are git-ignored but travel with the tree.
 """
 from __future__ import annotations
 
@@ -29,8 +30,12 @@ ISA_KERNELS = ("logsv_rng_kernel", "logsv_chain_rng_kernel", "heston_rng_kernelI
 SOURCES = ("svmc_runtime.hip", "svmc_kernels.hip", "svmc_analytic.hip", "svmc_chain.hip", "svmc_comm.hip", "svmc_multi.hip",
            "svmc_hawkes.hip")
 HEADERS = ("svmc_internal.h", "svmc_models.h", "svmc_rng.h", "svmc_math.h", "svmc_log_table.h", "svmc_icdf_table.h", "svmc_black.h", "svmc_ode.h", "svmc_dop853.h",
-           "svmc_slice.h")
+           "svmc_slice.h", "svmc_complex.h")
 ARCH = "gfx950"
+# the test-only device build of the math, complex and Black-76 helpers (tests/test_gpu_device_math.py): not part of the
+# package or its C ABI, built here so that it is compiled whenever the library is, with the library's flags
+PROBE_SRC = os.path.join(ROOT, "tests", "native", "device_math_probe.hip")
+PROBE_LIB = os.path.join(ROOT, "tests", "native", "libsvmc_device_probe.so")
 
 
 def hipcc() -> str:
@@ -56,6 +61,33 @@ def is_stale() -> bool:
     t = os.path.getmtime(LIB)
     deps = [os.path.join(CSRC, f) for f in SOURCES + HEADERS] + [os.path.join(INCLUDE, "svmc.h"), __file__]
     return any(os.path.getmtime(d) > t for d in deps)
+
+
+def probe_is_stale() -> bool:
+    if not os.path.exists(PROBE_LIB):
+        return True
+    t = os.path.getmtime(PROBE_LIB)
+    deps = [PROBE_SRC, os.path.join(INCLUDE, "svmc.h"), __file__] + [os.path.join(CSRC, f) for f in HEADERS]
+    return any(os.path.getmtime(d) > t for d in deps)
+
+
+def probe_command() -> list:
+    return [hipcc()] + flags() + [PROBE_SRC, "-o", PROBE_LIB]
+
+
+def build_device_probe(force: bool = False, verbose: bool = False) -> str:
+    """tests/native/libsvmc_device_probe.so, rebuilt when its source, a header of csrc/ or svmc.h is newer (about 2 s)"""
+    if not os.path.exists(PROBE_SRC) or (not force and not probe_is_stale()):
+        return PROBE_LIB
+    cmd = probe_command()
+    if verbose:
+        print(" ".join(cmd))
+    res = subprocess.run(cmd, capture_output=True, text=True, cwd=ROOT)
+    if res.returncode != 0:
+        raise RuntimeError("hipcc failed on the device probe:\n" + res.stdout + res.stderr)
+    if verbose and res.stderr:
+        print(res.stderr)
+    return PROBE_LIB
 
 
 def file_sha256(path: str) -> str:
@@ -111,6 +143,7 @@ def write_isa_json(asm_path: str, *more_asm: str) -> None:
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
+    build_device_probe(force, verbose)
     if not force and not is_stale() and os.path.exists(ISA_JSON):
         return LIB
     # --save-temps: the device assembly of this very compilation is kept for the histogram (temporaries in a scratch dir)

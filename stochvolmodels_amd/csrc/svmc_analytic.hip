@@ -17,6 +17,7 @@
 #include <cstdlib>
 
 #include "svmc_math.h"
+#include "svmc_complex.h"
 #include "svmc_ode.h"
 #include "svmc_dop853.h"
 
@@ -25,29 +26,6 @@
 #endif
 
 namespace svmc {
-
-__device__ __forceinline__ double cabs_(cd a) { return hypot(a.re, a.im); }
-__device__ __forceinline__ cd operator/(cd a, cd b)
-{
-    const double d = b.re * b.re + b.im * b.im;
-    return cd{(a.re * b.re + a.im * b.im) / d, (a.im * b.re - a.re * b.im) / d};
-}
-__device__ __forceinline__ cd cexp_(cd z)
-{
-    double s, c;
-    sincos(z.im, &s, &c);
-    const double e = exp(z.re);
-    return cd{e * c, e * s};
-}
-__device__ __forceinline__ cd csqrt_(cd z)   // principal branch
-{
-    const double r = cabs_(z);
-    if (r == 0.0) return cd{0.0, 0.0};
-    const double t = sqrt(0.5 * (r + fabs(z.re)));
-    if (z.re >= 0.0) return cd{t, z.im / (2.0 * t)};
-    return cd{fabs(z.im) / (2.0 * t), copysign(t, z.im)};
-}
-__device__ __forceinline__ cd clog_(cd z) { return cd{log(cabs_(z)), atan2(z.im, z.re)}; }
 
 // ---- one grid point per LANE: the form for LONG grids ----------------------------------------------------------------
 // The row form below wins on latency (a lone wave per SIMD, a third of the instructions per step) and loses on volume: it
@@ -483,7 +461,10 @@ __global__ __launch_bounds__(AB) void heston_mgf_grid_kernel(const cd *__restric
     if (j >= n_grid) return;
     const double volvol2 = volvol * volvol;
     const cd ph = phi[j], ps = psi[j];
-    const cd b1 = (rho * volvol) * ph + kappa;                                                   // :197
+    // kappa joins as the complex kappa + 0i, as NumPy adds a real to a complex: where ph is real, rho < 0 makes the product's
+    // imaginary part -0, and kept as -0 it would put zeta of a negative real discriminant (psi grid at p = 0 when
+    // kappa < volvol) on the lower side of csqrt_'s cut, conjugate to the principal value NumPy and mpmath take there
+    const cd b1 = (rho * volvol) * ph + C(kappa);                                                // :197
     const cd b0 = 0.5 * (ph * (ph + 1.0)) - ps;                                                 // :198
     const cd zeta = csqrt_(b1 * b1 - (2.0 * volvol2) * b0);                                     // :199
     const cd exp_zeta = cexp_(-(ttm * zeta));

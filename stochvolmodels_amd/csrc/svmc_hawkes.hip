@@ -21,6 +21,7 @@
 
 #include "svmc_rng.h"
 #include "svmc_slice.h"
+#include "svmc_complex.h"
 #include "svmc_ode.h"
 #include "svmc_dop853.h"
 
@@ -180,19 +181,6 @@ int check_params(const char *fn, const double *p)
 unsigned hawkes_grid(size_t n) { return static_cast<unsigned>((n + HAWKES_BLOCK - 1) / HAWKES_BLOCK); }
 
 // ---- the transform grid ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ cd hk_cexp(cd z)
-{
-    double s, c;
-    sincos(z.im, &s, &c);
-    const double e = exp(z.re);
-    return cd{e * c, e * s};
-}
-__device__ __forceinline__ cd hk_cdiv(cd a, cd b)
-{
-    const double d = b.re * b.re + b.im * b.im;
-    return cd{(a.re * b.re + a.im * b.im) / d, (a.im * b.re - a.re * b.im) / d};
-}
-
 struct HawkesOde {
     double sigma2, kappa_p, kappa_m, kth_p, kth_m, comp_p, comp_m;
     double shift_p, mean_p, shift_m, mean_m, beta1_p, beta2_p, beta1_m, beta2_m;
@@ -224,8 +212,8 @@ __device__ __forceinline__ void hawkes_rhs(const HawkesOde &o, cd phi, cd h0, co
 {
     const cd zp = (phi - o.beta1_p * a[1]) - o.beta1_m * a[2];
     const cd zm = (phi - o.beta2_p * a[1]) - o.beta2_m * a[2];
-    const cd j_p = hk_cdiv(hk_cexp(-(o.shift_p * zp)), 1.0 + o.mean_p * zp) - 1.0;                  // e_p, :594-601
-    const cd j_m = hk_cdiv(hk_cexp(-(o.shift_m * zm)), 1.0 + o.mean_m * zm) - 1.0;                  // e_m, :603-605
+    const cd j_p = cexp_(-(o.shift_p * zp)) / (1.0 + o.mean_p * zp) - 1.0;                  // e_p, :594-601
+    const cd j_m = cexp_(-(o.shift_m * zm)) / (1.0 + o.mean_m * zm) - 1.0;                  // e_m, :603-605
     out[0] = (o.kth_p * a[1] + o.kth_m * a[2]) + h0;
     out[1] = (j_p - o.kappa_p * a[1]) + o.comp_p * phi;
     out[2] = (j_m - o.kappa_m * a[2]) + o.comp_m * phi;

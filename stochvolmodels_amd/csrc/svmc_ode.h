@@ -9,23 +9,9 @@
 // one lane working through all five components, and the launch is latency-bound on exactly that count.
 // Host-compilable (tests/native/ode_probe.cpp checks the rows against the CPU twin's right-hand side).
 #pragma once
-#include "svmc_math.h"
+#include "svmc_complex.h"
 
 namespace svmc {
-
-struct cd {
-    double re, im;
-};
-SVMC_HD cd C(double re, double im = 0.0) { return cd{re, im}; }
-SVMC_HD cd operator+(cd a, cd b) { return cd{a.re + b.re, a.im + b.im}; }
-SVMC_HD cd operator-(cd a, cd b) { return cd{a.re - b.re, a.im - b.im}; }
-SVMC_HD cd operator-(cd a) { return cd{-a.re, -a.im}; }
-SVMC_HD cd operator*(cd a, cd b) { return cd{a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re}; }
-SVMC_HD cd operator*(double s, cd a) { return cd{s * a.re, s * a.im}; }
-SVMC_HD cd operator+(cd a, double s) { return cd{a.re + s, a.im}; }
-SVMC_HD cd operator+(double s, cd a) { return cd{a.re + s, a.im}; }
-SVMC_HD cd operator-(cd a, double s) { return cd{a.re - s, a.im}; }
-SVMC_HD cd operator-(double s, cd a) { return cd{s - a.re, -a.im}; }
 
 struct OdeConsts {
     double theta, theta2, vartheta2, qv, qv2, b, eta2, lamda, kappa2_p, kappa_p;
