@@ -587,7 +587,13 @@ SVMC_API int svmc_mgf_vanilla_slice(const double *phi, const double *log_mgf, si
  *                               With a communicator attached it issues the same two all-reduces.
  *   svmc_hawkesjd_mgf_grid      compute_hawkes_a_mgf_grid (:518-546): per grid point the three Riccati ODEs of
  *                               solve_ode_for_a (:582-640) over ttm from a[] ([n_grid][3] complex, in: the previous expiry's,
- *                               out: this one's) with DOP853 at rtol / atol; log_mgf = a0 + a1 lambda_p + a2 lambda_m. */
+ *                               out: this one's) with DOP853 at rtol / atol; log_mgf = a0 + a1 lambda_p + a2 lambda_m.
+ *   svmc_hawkesjd_mgf_grid_batch  the same for n_sets parameter sets side by side (the bumped vectors of a calibration's
+ *                               finite-difference gradient): phi, psi [n_sets][n_grid] complex (each set its own grid),
+ *                               params_host [n_sets][SVMC_HAWKESJD_PARAMS], a [n_sets][n_grid][3] complex, log_mgf
+ *                               [n_sets][n_grid] complex.  Every set is checked before anything is launched; an invalid one
+ *                               fails the whole call.  A grid point the integrator gives up on is NaN in its own set only.
+ *                               Results are bit-identical to n_sets single calls. */
 #define SVMC_HAWKESJD_PARAMS 16
 SVMC_API int svmc_hawkesjd_terminal_rng(double *x, double *lambda_p, double *lambda_m, size_t n_path, int nb_steps,
                                         double dt, const double *params_host, uint64_t seed, uint32_t call_id,
@@ -600,6 +606,9 @@ SVMC_API int svmc_hawkesjd_chain_price(svmc_session_t session, const double *ttm
 SVMC_API int svmc_hawkesjd_mgf_grid(const double *phi, const double *psi, size_t n_grid, double ttm,
                                     const double *params_host, double *a, double *log_mgf, double rtol, double atol,
                                     svmc_stream_t stream);
+SVMC_API int svmc_hawkesjd_mgf_grid_batch(const double *phi, const double *psi, size_t n_grid, int n_sets, double ttm,
+                                          const double *params_host, double *a, double *log_mgf, double rtol, double atol,
+                                          svmc_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -205,8 +205,9 @@ class AnalyticGrid(_Pooled):
 
 
 class AnalyticGridBatch(_Pooled):
-    """the transform grids of SEVERAL LogSV parameter sets resident on the device, advanced expiry by expiry in one
-    launch per expiry (svmc_logsv_mgf_grid_batch) and inverted in one launch per expiry (svmc_mgf_vanilla_slice_batch):
+    """the transform grids of SEVERAL LogSV or Hawkes parameter sets resident on the device, advanced expiry by expiry in one
+    launch per expiry (svmc_logsv_mgf_grid_batch, svmc_hawkesjd_mgf_grid_batch) and inverted in one launch per expiry
+    (svmc_mgf_vanilla_slice_batch):
     config C5's five sets, or the bumped parameter vectors of a finite-difference gradient, side by side.  Bit-identical
     to one AnalyticGrid per set."""
 
@@ -253,6 +254,16 @@ class AnalyticGridBatch(_Pooled):
                                                       int(expansion_order), self.a.ptr, self.log_mgf.ptr,
                                                       ODE_RTOL if rtol is None else float(rtol),
                                                       ODE_ATOL if atol is None else float(atol), None))
+
+    def hawkes_advance(self, ttm: float, params_rows: np.ndarray, rtol: Optional[float] = None,
+                       atol: Optional[float] = None) -> None:
+        """params_rows [n_sets][16]: the Hawkes jump-diffusion parameter blocks (include/svmc.h SVMC_HAWKESJD_PARAMS order)"""
+        rows = np.ascontiguousarray(params_rows, dtype=np.float64)
+        assert rows.shape == (self.n_sets, 16) and self.n_coef == 3
+        _lib.check(self.lib.svmc_hawkesjd_mgf_grid_batch(self.phi.ptr, self.psi.ptr, self.n, self.n_sets, float(ttm),
+                                                         rows.ctypes.data_as(C.POINTER(C.c_double)), self.a.ptr,
+                                                         self.log_mgf.ptr, ODE_RTOL if rtol is None else float(rtol),
+                                                         ODE_ATOL if atol is None else float(atol), None))
 
     def capped_sums(self, forward: float, strikes: np.ndarray) -> np.ndarray:
         """-> [n_sets][n_strikes]"""

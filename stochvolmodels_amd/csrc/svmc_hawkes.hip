@@ -5,8 +5,10 @@
 //                              one launch: the step of simulate_hawkesjd_terminal (:715-779) in its order, the slice epilogue of
 //                              svmc_slice.h per expiry (snapshot + per-wave spot partials for the chain payoff tail)
 //   hawkesjd_rng_kernel        the same body for one slice on caller-owned state (simulate_hawkesjd_terminal)
-//   hawkes_mgf_grid_kernel     one lane per transform-grid point: the three complex Riccati ODEs of solve_ode_for_a (:582-640)
-//                              with the DOP853 pair of svmc_dop853.h and per-point step control; log E = a0 + a1 lp + a2 lm
+//   hawkes_mgf_grid_batch_kernel  one lane per transform-grid point of up to 16 parameter sets per launch (blockIdx.y = set;
+//                              one set, or the base point and bumped vectors of a calibration's finite-difference gradient):
+//                              the three complex Riccati ODEs of solve_ode_for_a (:582-640) with the DOP853 pair of
+//                              svmc_dop853.h and per-point step control; log E = a0 + a1 lp + a2 lm
 //
 // Randoms (svmc_rng.h, streams 6 and 7): step s of path p is ONE Philox call of stream 6 at counter index s (the chain-global
 // step): word 0 -> the N(0,1) of the diffusion (normal_icdf32), words 1 and 2 -> u_p, u_m = (r + 1/2) 2^-32, word 3 unused.
@@ -295,13 +297,13 @@ __device__ void hawkes_dop853(const HawkesOde &o, cd phi, cd h0, double ttm, cd 
 }
 
 constexpr int HK_AB = 64;
+constexpr int HK_MAX_SETS = 16;        // parameter sets per batched launch (kernel-argument block: 16 x 136 B)
 
-__global__ __launch_bounds__(HK_AB) void hawkes_mgf_grid_kernel(const cd *__restrict__ phi, const cd *__restrict__ psi, size_t n_grid,
-                                                               double ttm, HawkesOde o, double lambda_p, double lambda_m,
-                                                               cd *__restrict__ a, cd *__restrict__ log_mgf, double rtol, double atol)
+// one transform-grid point: a_t0 in, a_t1 and log E = a0 + a1 lambda_p + a2 lambda_m (:545) out
+__device__ __forceinline__ void hawkes_grid_point(const cd *__restrict__ phi, const cd *__restrict__ psi, size_t j, double ttm,
+                                                  const HawkesOde &o, double lambda_p, double lambda_m, cd *__restrict__ a,
+                                                  cd *__restrict__ log_mgf, double rtol, double atol)
 {
-    const size_t j = static_cast<size_t>(blockIdx.x) * HK_AB + threadIdx.x;
-    if (j >= n_grid) return;
     const cd ph = phi[j];
     const cd h0 = o.sigma2 * ((0.5 * ((ph + 1.0) * ph)) - psi[j]);                                 // :623
     cd y[3] = {a[3 * j], a[3 * j + 1], a[3 * j + 2]};                                              // a_t0, chained across expiries
@@ -310,6 +312,31 @@ __global__ __launch_bounds__(HK_AB) void hawkes_mgf_grid_kernel(const cd *__rest
     a[3 * j + 1] = y[1];
     a[3 * j + 2] = y[2];
     log_mgf[j] = (y[0] + lambda_p * y[1]) + lambda_m * y[2];                                       // :545
+}
+
+// The parameter sets of one launch.  blockIdx.y picks the set, so a block's one wave belongs to one set and its constants
+// are read from the kernel arguments at a wave-uniform index (scalar loads).  Each set has its own transform grid (the grid
+// scale follows its sigma), coefficients and output.  svmc_hawkesjd_mgf_grid is this kernel at one set: a separate
+// single-set kernel built from the same lines was scheduled differently enough to differ in the last bit at 3 % of the
+// points, and the batch must equal one call per set bit for bit.
+struct HawkesOdeSet {
+    HawkesOde o;
+    double lambda_p, lambda_m;
+};
+struct HawkesOdeBatch {
+    HawkesOdeSet s[HK_MAX_SETS];
+};
+
+__global__ __launch_bounds__(HK_AB) void hawkes_mgf_grid_batch_kernel(const cd *__restrict__ phi, const cd *__restrict__ psi,
+                                                                     size_t n_grid, double ttm, HawkesOdeBatch sets,
+                                                                     cd *__restrict__ a, cd *__restrict__ log_mgf, double rtol,
+                                                                     double atol)
+{
+    const size_t j = static_cast<size_t>(blockIdx.x) * HK_AB + threadIdx.x;
+    if (j >= n_grid) return;
+    const HawkesOdeSet &set = sets.s[blockIdx.y];
+    const size_t off = static_cast<size_t>(blockIdx.y) * n_grid;       // this set's rows
+    hawkes_grid_point(phi + off, psi + off, j, ttm, set.o, set.lambda_p, set.lambda_m, a + 3 * off, log_mgf + off, rtol, atol);
 }
 
 }  // namespace
@@ -374,11 +401,35 @@ int svmc_hawkesjd_mgf_grid(const double *phi, const double *psi, size_t n_grid, 
     if (int rc = check_params(fn, params_host)) return rc;
     SVMC_REQUIRE(phi && psi && a && log_mgf, std::string(fn) + ": null pointer");
     SVMC_REQUIRE(ttm > 0.0 && rtol > 0.0 && atol > 0.0, std::string(fn) + ": ttm, rtol, atol must be positive");
+    return svmc_hawkesjd_mgf_grid_batch(phi, psi, n_grid, 1, ttm, params_host, a, log_mgf, rtol, atol, stream);
+}
+
+int svmc_hawkesjd_mgf_grid_batch(const double *phi, const double *psi, size_t n_grid, int n_sets, double ttm,
+                                 const double *params_host, double *a, double *log_mgf, double rtol, double atol,
+                                 svmc_stream_t stream)
+{
+    const char *fn = "svmc_hawkesjd_mgf_grid_batch";
+    SVMC_REQUIRE(phi && psi && a && log_mgf && params_host, std::string(fn) + ": null pointer");
+    SVMC_REQUIRE(n_sets >= 1, std::string(fn) + ": n_sets < 1");
+    SVMC_REQUIRE(ttm > 0.0 && rtol > 0.0 && atol > 0.0, std::string(fn) + ": ttm, rtol, atol must be positive");
+    for (int s = 0; s < n_sets; ++s)                           // every set before anything is launched
+        if (int rc = check_params((std::string(fn) + " set " + std::to_string(s)).c_str(),
+                                  params_host + static_cast<size_t>(SVMC_HAWKESJD_PARAMS) * s))
+            return rc;
     if (n_grid == 0) return SVMC_OK;
-    hipLaunchKernelGGL(hawkes_mgf_grid_kernel, dim3(static_cast<unsigned>((n_grid + HK_AB - 1) / HK_AB)), dim3(HK_AB), 0,
-                       as_stream(stream), reinterpret_cast<const cd *>(phi), reinterpret_cast<const cd *>(psi), n_grid, ttm,
-                       make_hawkes_ode(params_host), params_host[P_LAMBDA_P], params_host[P_LAMBDA_M], reinterpret_cast<cd *>(a),
-                       reinterpret_cast<cd *>(log_mgf), rtol, atol);
+    for (int s0 = 0; s0 < n_sets; s0 += HK_MAX_SETS) {
+        const int m = (n_sets - s0 < HK_MAX_SETS) ? (n_sets - s0) : HK_MAX_SETS;
+        HawkesOdeBatch sets;
+        for (int i = 0; i < HK_MAX_SETS; ++i) {                // unused slots repeat the first set: never read
+            const double *p = params_host + static_cast<size_t>(SVMC_HAWKESJD_PARAMS) * (s0 + (i < m ? i : 0));
+            sets.s[i] = HawkesOdeSet{make_hawkes_ode(p), p[P_LAMBDA_P], p[P_LAMBDA_M]};
+        }
+        const size_t off = static_cast<size_t>(s0) * n_grid;
+        hipLaunchKernelGGL(hawkes_mgf_grid_batch_kernel, dim3(static_cast<unsigned>((n_grid + HK_AB - 1) / HK_AB), static_cast<unsigned>(m)),
+                           dim3(HK_AB), 0, as_stream(stream), reinterpret_cast<const cd *>(phi) + off,
+                           reinterpret_cast<const cd *>(psi) + off, n_grid, ttm, sets, reinterpret_cast<cd *>(a) + 3 * off,
+                           reinterpret_cast<cd *>(log_mgf) + off, rtol, atol);
+    }
     return check_launch(fn);
 }
 

@@ -10,10 +10,14 @@ self- and cross-exciting Hawkes processes.  Two pricers:
   - Fourier (hawkesjd_chain_pricer, compute_hawkes_a_mgf_grid; :365-417, :518-640): the three complex Riccati ODEs
     integrated per transform-grid point on the device with DOP853 at rtol 1e-10 / atol 1e-12 (the reference calls SciPy at
     its default rtol 1e-3), inverted by the existing vanilla slice kernel.
+Calibration (HawkesJDPricer.calibrate_model_params_to_chain; :230-302): SLSQP on the vega-weighted squared vol error of 8
+parameters, each objective evaluation one Fourier chain pricing on the device.  The forward-difference gradient SLSQP needs at
+an iterate (the base point and 8 bumped vectors) is priced in one batch of launches per expiry (hawkesjd_chain_pricer_batch,
+csrc/svmc_hawkes.hip's hawkes_mgf_grid_batch_kernel), bit-identical to one pricing per vector.
 The reference's quirks are kept: `risk_premia_gamma` is accepted and unused by the Monte Carlo, `is_spot_measure` is ignored
 by it, and a variable_type other than LOG_RETURN raises (the reference would price the log-return as a variance).
-Out of scope: the risk-premia pricer (price_chain raises NotImplementedError when params.risk_premia_gamma is set) and the
-Hawkes calibration.
+Out of scope: the risk-premia pricer (price_chain raises NotImplementedError when params.risk_premia_gamma is set) and so
+calibrate_risk_premia_gamma_to_chain, which prices through it.
 """
 from __future__ import annotations
 
@@ -25,13 +29,14 @@ import numpy as np
 
 from .. import _lib
 from .. import dist as svdist
-from ..analytic import ODE_ATOL, ODE_RTOL, AnalyticGrid, vanilla_prices_from_capped
+from ..analytic import ODE_ATOL, ODE_RTOL, AnalyticGrid, AnalyticGridBatch, vanilla_prices_from_capped
 from ..data.option_chain import OptionChain
 from ..engine import get_engine, marshalled_chain, option_type_codes
 from ..mc_chain import variable_type_code
 from ..utils import mgf_pricer as mgfp
+from ..utils.calibration import ImpliedVolObjective, chain_calibration_weights
 from ..utils.config import VariableType
-from ..utils.funcs import next_rng_call, time_grid_steps, timer
+from ..utils.funcs import next_rng_call, time_grid_steps, timer, to_flat_np_array
 from .model_pricer import ModelParams, ModelPricer
 
 MAX_PHI = 500
@@ -139,6 +144,63 @@ class HawkesJDPricer(ModelPricer):
                                         optiontypes_ttms=option_chain.optiontypes_ttms, nb_path=nb_path,
                                         **params.to_dict(), **kwargs)
 
+    def price_chain_batch(self, option_chain: OptionChain, params_list: Sequence[HawkesJDParams], is_spot_measure: bool = True,
+                          **kwargs) -> List[List[np.ndarray]]:
+        """price_chain for several parameter sets in one batch of launches (hawkesjd_chain_pricer_batch)"""
+        if any(p.risk_premia_gamma is not None for p in params_list):
+            raise NotImplementedError("the risk-premia Hawkes pricer (hawkesjd_chain_pricer_with_risk_premia) is not implemented")
+        return hawkesjd_chain_pricer_batch(params_list=params_list, ttms=option_chain.ttms, forwards=option_chain.forwards,
+                                           discfactors=option_chain.discfactors, strikes_ttms=option_chain.strikes_ttms,
+                                           optiontypes_ttms=option_chain.optiontypes_ttms, is_spot_measure=is_spot_measure,
+                                           **kwargs)
+
+    def calibration_objective(self, option_chain: OptionChain, params0: HawkesJDParams, is_vega_weighted: bool = True,
+                              is_unit_ttm_vega: bool = False, **kwargs) -> ImpliedVolObjective:
+        """the objective of calibrate_model_params_to_chain as a callable of the optimizer's 8-vector (reference :280-285),
+        with its batched gradient unless batched_gradient=False; ode_rtol= / ode_atol= as there"""
+        _, market_vols_ttms = option_chain.get_chain_data_as_xy()
+        market_vols = to_flat_np_array(market_vols_ttms)
+        weights = chain_calibration_weights(option_chain, market_vols, is_vega_weighted, is_unit_ttm_vega)
+        tol = {k: kwargs[k] for k in ("ode_rtol", "ode_atol") if k in kwargs}
+
+        def model_vols(pars):
+            return self.compute_model_ivols_for_chain(option_chain=option_chain,
+                                                      params=unpack_calibration_vector(pars, params0), **tol)
+
+        def model_vols_batch(pars_list):
+            prices = self.price_chain_batch(option_chain=option_chain,
+                                            params_list=[unpack_calibration_vector(p, params0) for p in pars_list], **tol)
+            return [option_chain.compute_model_ivols_from_chain_data(model_prices=pr) for pr in prices]
+
+        batched = bool(kwargs.get("batched_gradient", True))
+        return ImpliedVolObjective(model_vols, market_vols, weights, model_vols_batch=model_vols_batch if batched else None,
+                                   bounds=CALIBRATION_BOUNDS)
+
+    @timer
+    def calibrate_model_params_to_chain(self, option_chain: OptionChain, params0: HawkesJDParams,
+                                        is_vega_weighted: bool = True, is_unit_ttm_vega: bool = False, **kwargs
+                                        ) -> HawkesJDParams:
+        """fit sigma, mean_p, mean_m, theta_p, theta_m, one kappa for both sides, beta_p (beta1_p = -beta2_p) and beta_m
+        (beta1_m = -beta2_m) to the chain's mid implied vols, with shift_p, shift_m, lambda_p, lambda_m from params0 and
+        mu = 0 (reference :230-302): SLSQP (ftol 1e-8) on the np.nansum of per-slice-normalised vega-weighted squared vol
+        errors, subject to jump1_cond + jump2_cond >= 0 (calibration_start_vector, CALIBRATION_BOUNDS,
+        unpack_calibration_vector, calibration_constraint).  As in the reference, the transform grid follows each
+        candidate's own sigma, and the optimizer's vector is returned whatever SLSQP's exit status.
+        `kwargs`: disp= (SLSQP printing, default True as in the reference); batched_gradient= (default True: SLSQP's
+        forward-difference gradient -- the same points it would evaluate itself -- from one hawkesjd_chain_pricer_batch per
+        iterate); ode_rtol= / ode_atol= (the coefficient ODEs' tolerances, default 1e-10 / 1e-12).
+        `self.last_calibration` keeps {"n_eval", "n_gradient_batches", "objective"} of the run."""
+        from scipy.optimize import minimize
+        objective = self.calibration_objective(option_chain, params0, is_vega_weighted, is_unit_ttm_vega, **kwargs)
+        batched = objective.model_vols_batch is not None
+        extra = dict(jac=objective.gradient) if batched else {}
+        res = minimize(objective, calibration_start_vector(params0), args=None, method="SLSQP",
+                       constraints={"type": "ineq", "fun": lambda pars: calibration_constraint(pars, params0)},
+                       bounds=CALIBRATION_BOUNDS, options={"disp": bool(kwargs.get("disp", True)), "ftol": 1e-8}, **extra)
+        self.last_calibration = dict(n_eval=objective.n_eval, n_gradient_batches=objective.n_batches,
+                                     objective=objective(res.x), success=bool(res.success), message=str(res.message))
+        return unpack_calibration_vector(res.x, params0)
+
     @timer
     def simulate_terminal_values(self, params: HawkesJDParams, ttm: float = 1.0, nb_path: int = 100000,
                                  is_spot_measure: bool = True, **kwargs) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
@@ -150,6 +212,35 @@ class HawkesJDPricer(ModelPricer):
                                           lambda_m0=lambda_m * np.ones(nb_path), nb_path=nb_path, **p,
                                           nb_steps_per_year=kwargs.get("nb_steps_per_year", NB_STEPS_PER_YEAR),
                                           seed=kwargs.get("seed"))
+
+
+# ---- the calibration's codec (reference :246-290): the optimizer's 8-vector <-> HawkesJDParams --------------------------------
+# (sigma, mean_p, mean_m, theta_p, theta_m, kappa, beta_p, beta_m)
+CALIBRATION_BOUNDS = ((0.10, 2.0), (0.01, 0.99), (-0.99, -0.01), (0.01, 100.0), (0.01, 100.0), (1.0, 100.0), (1.0, 100.0),
+                      (1.0, 100.0))
+
+
+def calibration_start_vector(params0: HawkesJDParams) -> np.ndarray:
+    """the start vector of the reference (:251-254), its beta_m0 = (beta2_p - beta2_m) / 2 included"""
+    return np.array([params0.sigma, params0.mean_p, params0.mean_m, params0.theta_p, params0.theta_m,
+                     0.5 * (params0.kappa_p + params0.kappa_m), 0.5 * (params0.beta1_p - params0.beta2_p),
+                     0.5 * (params0.beta2_p - params0.beta2_m)])
+
+
+def unpack_calibration_vector(pars: np.ndarray, params0: HawkesJDParams) -> HawkesJDParams:
+    """the optimizer's vector as model parameters (:258-278): mu = 0, one kappa for both sides, beta2_p = -beta_p,
+    beta2_m = -beta_m, shift_p / shift_m / lambda_p / lambda_m from params0"""
+    sigma, mean_p, mean_m, theta_p, theta_m, kappa, beta_p, beta_m = (pars[0], pars[1], pars[2], pars[3], pars[4], pars[5],
+                                                                      pars[6], pars[7])
+    return HawkesJDParams(mu=0.0, sigma=sigma, shift_p=params0.shift_p, mean_p=mean_p, shift_m=params0.shift_m, mean_m=mean_m,
+                          lambda_p=params0.lambda_p, theta_p=theta_p, kappa_p=kappa, beta1_p=beta_p, beta2_p=-beta_p,
+                          lambda_m=params0.lambda_m, theta_m=theta_m, kappa_m=kappa, beta1_m=beta_m, beta2_m=-beta_m)
+
+
+def calibration_constraint(pars: np.ndarray, params0: HawkesJDParams) -> float:
+    """the inequality constraint (>= 0) of the calibration: the sum of both intensities' stationarity margins (:287-290)"""
+    params = unpack_calibration_vector(pars, params0)
+    return params.jump1_cond + params.jump2_cond
 
 
 def set_vol_scaler(sigma0: float, ttm: float) -> float:
@@ -217,6 +308,47 @@ def hawkesjd_chain_pricer(model_params: HawkesJDParams, ttms: np.ndarray, forwar
                                                                               optiontypes_ttms))]
     finally:
         grid.release()
+
+
+def hawkesjd_chain_pricer_batch(params_list: Sequence[HawkesJDParams], ttms: np.ndarray, forwards: np.ndarray,
+                                discfactors: np.ndarray, strikes_ttms: Sequence[np.ndarray],
+                                optiontypes_ttms: Sequence[np.ndarray], is_spot_measure: bool = True,
+                                variable_type: VariableType = VariableType.LOG_RETURN, vol_scaler: float = None,
+                                ode_rtol: Optional[float] = None, ode_atol: Optional[float] = None) -> List[List[np.ndarray]]:
+    """hawkesjd_chain_pricer for SEVERAL parameter sets on one chain: [set][expiry] -> prices, bit-identical to one
+    hawkesjd_chain_pricer call per set.  Each set keeps its own transform grid (set_vol_scaler follows its sigma unless
+    vol_scaler is given); per expiry the sets advance in one launch and are inverted in one launch, and the chain's sums come
+    back in one download.  Not in the reference API: the batched form of a calibration's finite-difference gradient."""
+    if int(getattr(variable_type, "value", variable_type)) != LOG_RETURN:
+        raise NotImplementedError(f"variable_type={variable_type}")
+    ttms = np.asarray(ttms, dtype=np.float64)
+    n_sets = len(params_list)
+    if n_sets == 0:
+        return []
+    grids = [mgfp.get_transform_var_grid(variable_type=variable_type, max_phi=MAX_PHI,
+                                         vol_scaler=(set_vol_scaler(sigma0=p.sigma, ttm=np.min(ttms))
+                                                     if vol_scaler is None else vol_scaler)) for p in params_list]
+    rows = np.stack([_model_block(p) for p in params_list])
+    batch = AnalyticGridBatch.acquire([g[0] for g in grids], [g[1] for g in grids], 3)
+    try:
+        ks = [int(np.asarray(k).size) for k in strikes_ttms]
+        offs = np.concatenate([[0], np.cumsum([n_sets * k for k in ks])]).astype(int)
+        batch.reserve_results(int(offs[-1]))
+        ttm0 = 0.0
+        for i, (ttm, forward, strikes) in enumerate(zip(ttms, forwards, strikes_ttms)):
+            batch.hawkes_advance(float(ttm - ttm0), rows, ode_rtol, ode_atol)
+            batch.queue_capped_sums(float(forward), np.asarray(strikes, dtype=np.float64), int(offs[i]))
+            ttm0 = ttm
+        sums = batch.download_results(int(offs[-1]))
+        out = [[] for _ in params_list]
+        for i, (forward, discfactor, strikes, types) in enumerate(zip(forwards, discfactors, strikes_ttms, optiontypes_ttms)):
+            capped = sums[offs[i]:offs[i + 1]].reshape(n_sets, ks[i])
+            for s in range(n_sets):
+                out[s].append(vanilla_prices_from_capped(capped[s], float(forward), np.asarray(strikes), types,
+                                                         float(discfactor), is_spot_measure))
+        return out
+    finally:
+        batch.release()
 
 
 def hawkesjd_mc_chain_pricer(ttms: np.ndarray, forwards: np.ndarray, discfactors: np.ndarray,
