@@ -174,35 +174,36 @@ static int check_chain(const char *fn, const Session *s, const ChainView &c, int
     return SVMC_OK;
 }
 
-// phase 3 of mc_chain.py: per-strike sums of every slice, queued on the session's stream
-static int enqueue_payoff_sums(Session *s, const ChainView &c, int variable_type, std::vector<double> &shifts)
+static void payoff_shifts_of(const ChainView &c, int variable_type, std::vector<double> &shifts)
 {
-    const size_t n = s->n_path;
     shifts.resize(c.offsets[c.m]);
-    std::vector<const double *> xs(c.m), qs(c.m);
-    for (int i = 0; i < c.m; ++i) {
+    for (int i = 0; i < c.m; ++i)
         for (size_t k = c.offsets[i]; k < c.offsets[i + 1]; ++k)
             shifts[k] = payoff_shift(c.strikes[k], c.types[k], c.forwards[i], variable_type);
-        xs[i] = s->snap + static_cast<size_t>(i) * n;
-        qs[i] = s->snap + static_cast<size_t>(c.m + i) * n;
-    }
-    return svmc_payoff_sums_chain(xs.data(), variable_type == SVMC_Q_VAR ? qs.data() : nullptr, n, c.forwards, c.ttms,
-                                  s->spot, c.m, c.strikes, c.types, shifts.data(), c.offsets, variable_type, s->sums,
-                                  s->ws, s->ws_bytes, s->stream);
 }
 
-// the same for parameter set `set` of P (svmc_logsv_chain_price_fixed_sets): its snapshot rows, spot sums and output
-// block -- one launch pair per set with the single-set launch shape, hence the single-set bits
+// the snapshot rows of parameter set q of P: x of expiry i at row q m + i, qvar at row (P + q) m + i (rows of n_path doubles)
+struct SnapshotRows {
+    std::vector<const double *> x, qvar;
+};
+static SnapshotRows snapshot_rows(const Session *s, const ChainView &c, int q, int P)
+{
+    SnapshotRows r{std::vector<const double *>(c.m), std::vector<const double *>(c.m)};
+    for (int i = 0; i < c.m; ++i) {
+        r.x[i] = s->snap + static_cast<size_t>(q * c.m + i) * s->n_path;
+        r.qvar[i] = s->snap + static_cast<size_t>((P + q) * c.m + i) * s->n_path;
+    }
+    return r;
+}
+
+// phase 3 of mc_chain.py, per-strike sums of every slice queued on the session's stream, for parameter set `set` of P: its
+// snapshot rows, spot sums and output block -- one launch pair per set with the single-set launch shape, hence the single-set bits
 static int enqueue_payoff_sums_of_set(Session *s, const ChainView &c, int variable_type, const std::vector<double> &shifts,
                                       int set, int n_sets)
 {
-    const size_t n = s->n_path, K = c.offsets[c.m];
-    std::vector<const double *> xs(c.m), qs(c.m);
-    for (int i = 0; i < c.m; ++i) {
-        xs[i] = s->snap + static_cast<size_t>(set * c.m + i) * n;
-        qs[i] = s->snap + static_cast<size_t>((n_sets + set) * c.m + i) * n;
-    }
-    return svmc_payoff_sums_chain(xs.data(), variable_type == SVMC_Q_VAR ? qs.data() : nullptr, n, c.forwards, c.ttms,
+    const size_t K = c.offsets[c.m];
+    const SnapshotRows r = snapshot_rows(s, c, set, n_sets);
+    return svmc_payoff_sums_chain(r.x.data(), variable_type == SVMC_Q_VAR ? r.qvar.data() : nullptr, s->n_path, c.forwards, c.ttms,
                                   s->spot + 2 * static_cast<size_t>(set) * c.m, c.m, c.strikes, c.types, shifts.data(), c.offsets,
                                   variable_type, s->sums + 3 * K * static_cast<size_t>(set), s->ws, s->ws_bytes, s->stream);
 }
@@ -213,12 +214,8 @@ static int enqueue_payoff_sums_of_sets(Session *s, const ChainView &c, int varia
 {
     if (n_sets > 1 && payoff_sets_fit(s->n_path, c.m, c.offsets, c.types, n_sets, s->ws_bytes)) {
         const size_t n = s->n_path;
-        std::vector<const double *> xs(c.m), qs(c.m);
-        for (int i = 0; i < c.m; ++i) {
-            xs[i] = s->snap + static_cast<size_t>(i) * n;
-            qs[i] = s->snap + static_cast<size_t>(n_sets * c.m + i) * n;
-        }
-        return payoff_sums_chain_sets(xs.data(), variable_type == SVMC_Q_VAR ? qs.data() : nullptr, n, c.forwards, c.ttms, s->spot,
+        const SnapshotRows r = snapshot_rows(s, c, 0, n_sets);
+        return payoff_sums_chain_sets(r.x.data(), variable_type == SVMC_Q_VAR ? r.qvar.data() : nullptr, n, c.forwards, c.ttms, s->spot,
                                       c.m, c.strikes, c.types, shifts.data(), c.offsets, variable_type, s->sums, s->ws, s->ws_bytes,
                                       s->stream, n_sets, static_cast<size_t>(c.m) * n, static_cast<size_t>(c.m) * n,
                                       2 * static_cast<size_t>(c.m));
@@ -228,18 +225,45 @@ static int enqueue_payoff_sums_of_sets(Session *s, const ChainView &c, int varia
     return SVMC_OK;
 }
 
-// phase 4: host finalisation of the downloaded sums (utils/mc_payoffs.py:85-88); the standard error divides by the
-// path count of the WHOLE job
-static int finalize_prices(const Session *s, const ChainView &c, const double *sums, const std::vector<double> &shifts,
-                           double *prices, double *stderrs)
+// host side of the implied vols for the routes that do not replay a graph (multi-GPU, graphs off): the same solver
+static void implied_vols_on_host(const ChainView &c, int variable_type, const double *prices, double *ivols)
 {
-    const double n_all = static_cast<double>(s->sharded() ? s->n_total : s->n_path);
-    for (int i = 0; i < c.m; ++i) {
-        const size_t k0 = c.offsets[i], k = c.offsets[i + 1] - k0;
-        if (int rc = svmc_payoff_finalize(sums + 3 * k0, shifts.data() + k0, k, c.discfactors[i], n_all, prices + k0,
-                                          stderrs + k0))
-            return rc;
-    }
+    for (int i = 0; i < c.m; ++i)
+        for (size_t k = c.offsets[i]; k < c.offsets[i + 1]; ++k) {
+            // quotes on the log-return only: options on the realised variance have no Black vol on the forward; inverse
+            // options (IC / IP) as in chain_implied_vols_kernel: the vanilla inversion of price x forward
+            const bool call = c.types[k] == SVMC_CALL || c.types[k] == SVMC_INV_CALL;
+            const double px = c.types[k] >= SVMC_INV_CALL ? prices[k] * c.forwards[i] : prices[k];
+            ivols[k] = variable_type == SVMC_LOG_RETURN
+                           ? black_implied_vol(px, c.strikes[k], call, c.forwards[i], c.ttms[i], c.discfactors[i], IV_VOL_LO, IV_VOL_HI)
+                           : std::numeric_limits<double>::quiet_NaN();
+        }
+}
+
+// the path count of the WHOLE job, which the standard errors divide by
+static double paths_of_job(const Session *s)
+{
+    return static_cast<double>(s->sharded() ? s->n_total : s->n_path);
+}
+
+// phase 4 for P parameter sets, blocks of K = offsets[m] quotes: host finalisation of the downloaded sums
+// (utils/mc_payoffs.py:85-88), then, when asked for, the implied vols -- the graph's, or the host solver's where it has none
+static int finish_sets(const Session *s, const ChainView &c, const double *sums, const std::vector<double> &shifts, int P,
+                       int variable_type, double *prices, double *stderrs, double *ivols, const double *ivols_pinned)
+{
+    const size_t K = c.offsets[c.m];
+    const double n_all = paths_of_job(s);
+    for (int q = 0; q < P; ++q)
+        for (int i = 0; i < c.m; ++i) {
+            const size_t k0 = c.offsets[i], k = c.offsets[i + 1] - k0, b = K * q + k0;
+            if (int rc = svmc_payoff_finalize(sums + 3 * b, shifts.data() + k0, k, c.discfactors[i], n_all, prices + b, stderrs + b))
+                return rc;
+        }
+    if (ivols == nullptr) return SVMC_OK;
+    if (ivols_pinned != nullptr)
+        memcpy(ivols, ivols_pinned, K * P * sizeof(double));
+    else
+        for (int q = 0; q < P; ++q) implied_vols_on_host(c, variable_type, prices + K * q, ivols + K * q);
     return SVMC_OK;
 }
 
@@ -271,26 +295,14 @@ static bool one_device_tail(const Session *s, const ChainView &c)
            payoff_sets_fit(s->n_path, c.m, c.offsets, c.types, 1, s->ws_bytes);
 }
 
-static void payoff_shifts_of(const ChainView &c, int variable_type, std::vector<double> &shifts)
-{
-    shifts.resize(c.offsets[c.m]);
-    for (int i = 0; i < c.m; ++i)
-        for (size_t k = c.offsets[i]; k < c.offsets[i + 1]; ++k)
-            shifts[k] = payoff_shift(c.strikes[k], c.types[k], c.forwards[i], variable_type);
-}
-
 static int enqueue_one_device_tail(Session *s, const ChainView &c, int variable_type, const std::vector<double> &shifts, double *sums_out)
 {
     const size_t n = s->n_path;
-    std::vector<const double *> xs(c.m), qs(c.m);
-    for (int i = 0; i < c.m; ++i) {
-        xs[i] = s->snap + static_cast<size_t>(i) * n;
-        qs[i] = s->snap + static_cast<size_t>(c.m + i) * n;
-    }
+    const SnapshotRows r = snapshot_rows(s, c, 0, 1);
     const bool in_kernel = spot_sums_in_payoff_kernel(n);
     if (!in_kernel)
         if (int rc = reduce_spot_partials(s->spot_ws, n, 2 * c.m, s->spot, s->stream)) return rc;
-    return chain_payoff_and_finish(xs.data(), variable_type == SVMC_Q_VAR ? qs.data() : nullptr, n, c.forwards, c.ttms, s->spot,
+    return chain_payoff_and_finish(r.x.data(), variable_type == SVMC_Q_VAR ? r.qvar.data() : nullptr, n, c.forwards, c.ttms, s->spot,
                                    in_kernel ? s->spot_ws : nullptr, c.m, c.strikes, c.types, shifts.data(), c.offsets, variable_type,
                                    s->ws, s->ws_bytes, s->stream, sums_out);
 }
@@ -300,31 +312,140 @@ static int enqueue_one_device_tail(Session *s, const ChainView &c, int variable_
 static int reduce_and_finalize(Session *s, const ChainView &c, int variable_type, double *prices, double *stderrs,
                                bool partials_pending)
 {
-    if (partials_pending && one_device_tail(s, c)) {
-        std::vector<double> shifts;
-        payoff_shifts_of(c, variable_type, shifts);
-        if (int rc = enqueue_one_device_tail(s, c, variable_type, shifts, s->sums_pinned)) return rc;
-        SVMC_HIP_TRY(hipStreamSynchronize(s->stream));
-        stepping_read(s);
-        return finalize_prices(s, c, s->sums_pinned, shifts, prices, stderrs);
-    }
-    if (partials_pending)
-        if (int rc = reduce_spot_partials(s->spot_ws, s->n_path, 2 * c.m, s->spot, s->stream)) return rc;
-    if (int rc = all_reduce(s, s->spot, 2 * static_cast<size_t>(c.m))) return rc;
     std::vector<double> shifts;
-    if (int rc = enqueue_payoff_sums(s, c, variable_type, shifts)) return rc;
-    if (int rc = all_reduce(s, s->sums, 3 * c.offsets[c.m])) return rc;
-    SVMC_HIP_TRY(hipMemcpyAsync(s->sums_pinned, s->sums, 3 * c.offsets[c.m] * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    payoff_shifts_of(c, variable_type, shifts);
+    if (partials_pending && one_device_tail(s, c)) {
+        if (int rc = enqueue_one_device_tail(s, c, variable_type, shifts, s->sums_pinned)) return rc;
+    } else {
+        if (partials_pending)
+            if (int rc = reduce_spot_partials(s->spot_ws, s->n_path, 2 * c.m, s->spot, s->stream)) return rc;
+        if (int rc = all_reduce(s, s->spot, 2 * static_cast<size_t>(c.m))) return rc;
+        if (int rc = enqueue_payoff_sums_of_set(s, c, variable_type, shifts, 0, 1)) return rc;
+        if (int rc = all_reduce(s, s->sums, 3 * c.offsets[c.m])) return rc;
+        SVMC_HIP_TRY(hipMemcpyAsync(s->sums_pinned, s->sums, 3 * c.offsets[c.m] * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    }
     SVMC_HIP_TRY(hipStreamSynchronize(s->stream));
     stepping_read(s);
-    return finalize_prices(s, c, s->sums_pinned, shifts, prices, stderrs);
+    return finish_sets(s, c, s->sums_pinned, shifts, 1, variable_type, prices, stderrs, nullptr, nullptr);
 }
+
+// ---- the captured chains (FixedGraph): a key, the buffers it sizes, a graph captured from the driver's `enqueue`
 
 template <class T>
 static void key_append(std::vector<unsigned char> &key, const T *p, size_t count)
 {
     const unsigned char *b = reinterpret_cast<const unsigned char *>(p);
     key.insert(key.end(), b, b + count * sizeof(T));
+}
+
+// the part of a graph's key every driver shares: the chain, P and the results asked for (the discount factors only matter to the
+// implied vols); each driver appends what else shapes its launches
+static std::vector<unsigned char> chain_key(const ChainView &c, int P, int variable_type, int want_iv)
+{
+    std::vector<unsigned char> key;
+    key_append(key, &c.m, 1);
+    key_append(key, &P, 1);
+    key_append(key, &variable_type, 1);
+    key_append(key, &want_iv, 1);
+    key_append(key, c.ttms, c.m);
+    key_append(key, c.discfactors, want_iv ? c.m : 0);
+    key_append(key, c.forwards, c.m);
+    key_append(key, c.offsets, c.m + 1);
+    key_append(key, c.strikes, c.offsets[c.m]);
+    key_append(key, c.types, c.offsets[c.m]);
+    return key;
+}
+
+// the parameter block of P sets: [P] initial volatilities, then [m][P] model constants of WIDTH doubles -- for one set the
+// [v0][m constants] of the single-set kernels.  Set q is sets + row q = (v0, theta, kappa1, kappa2, beta, volvol), its vol-backbone
+// etas are at etas + row q (1 where etas is null).
+template <void (*TO_DOUBLES)(double, double, double, double, double, double, double, int, double *), int WIDTH>
+static void fill_params(double *block, const ChainView &c, int P, const double *sets, const double *etas, size_t row,
+                        const double *dts, int is_spot_measure)
+{
+    for (int q = 0; q < P; ++q) {
+        const double *pr = sets + row * q, *eta = etas ? etas + row * q : nullptr;
+        block[q] = pr[0];
+        for (int i = 0; i < c.m; ++i)
+            TO_DOUBLES(dts[i], pr[1], pr[2], pr[3], pr[4], pr[5], eta ? eta[i] : 1.0, is_spot_measure,
+                       block + P + (static_cast<size_t>(i) * P + q) * WIDTH);
+    }
+}
+
+// (re)allocates g for a new key: the pinned and device parameter blocks (fill_params, constants of params_width doubles), the
+// pinned sums of P sets and, with implied vols, the quote table of every set -- part of the key, so uploaded once, outside the graph
+static int graph_prepare(FixedGraph &g, const std::vector<unsigned char> &key, const ChainView &c, const std::vector<double> &shifts,
+                         int P, int params_width, bool want_iv)
+{
+    fixed_graph_release(g);
+    const size_t K = c.offsets[c.m], n_quotes = K * P;
+    g.params_doubles = static_cast<size_t>(P) * (1 + static_cast<size_t>(c.m) * params_width);
+    g.sums_doubles = 3 * n_quotes;
+    SVMC_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&g.params_host), g.params_doubles * sizeof(double), hipHostMallocDefault));
+    SVMC_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&g.sums_host), (g.sums_doubles ? g.sums_doubles : 1) * sizeof(double),
+                               hipHostMallocDefault));
+    SVMC_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&g.params_dev), g.params_doubles * sizeof(double)));
+    if (want_iv && n_quotes) {
+        std::vector<double> quotes(IV_QUOTE_DOUBLES_HOST * n_quotes);
+        for (int q = 0; q < P; ++q)
+            for (int i = 0; i < c.m; ++i)
+                for (size_t k = c.offsets[i]; k < c.offsets[i + 1]; ++k) {
+                    double *qd = quotes.data() + IV_QUOTE_DOUBLES_HOST * (K * q + k);
+                    qd[0] = c.strikes[k];
+                    qd[1] = static_cast<double>(c.types[k]);
+                    qd[2] = shifts[k];
+                    qd[3] = c.forwards[i];
+                    qd[4] = c.ttms[i];
+                    qd[5] = c.discfactors[i];
+                }
+        SVMC_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&g.quotes_dev), quotes.size() * sizeof(double)));
+        SVMC_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&g.ivols_dev), n_quotes * sizeof(double)));
+        SVMC_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&g.ivols_host), n_quotes * sizeof(double), hipHostMallocDefault));
+        SVMC_HIP_TRY(hipMemcpy(g.quotes_dev, quotes.data(), quotes.size() * sizeof(double), hipMemcpyHostToDevice));
+    }
+    g.key = key;
+    return SVMC_OK;
+}
+
+// captures enqueue() -- a driver's launches on the session's stream, one linear chain of nodes -- into g and instantiates it.
+// Capture mode is always left; g is released on any error.
+template <class Enqueue>
+static int graph_capture(Session *s, FixedGraph &g, const char *fn, Enqueue enqueue)
+{
+    int rc = SVMC_OK;
+    hipError_t e = hipStreamBeginCapture(s->stream, hipStreamCaptureModeRelaxed);
+    if (e == hipSuccess) {
+        rc = enqueue();
+        e = hipStreamEndCapture(s->stream, &g.graph);
+        if (rc == SVMC_OK && e == hipSuccess) e = hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0);
+    }
+    if (rc == SVMC_OK && e == hipSuccess) return SVMC_OK;
+    fixed_graph_release(g);
+    return rc != SVMC_OK ? rc : fail(SVMC_ERR_HIP, std::string(fn) + ": graph capture: " + hipGetErrorString(e));
+}
+
+// the last step of a captured chain, its results home: with implied vols the last kernel writes both the sums and the vols into
+// the pinned host buffers (two copy nodes fewer per replay); without, the sums' copy
+static int enqueue_results_home(Session *s, const FixedGraph &g)
+{
+    if (g.ivols_dev != nullptr)
+        return chain_implied_vols(s->sums, g.quotes_dev, g.sums_doubles / 3, paths_of_job(s), IV_VOL_LO, IV_VOL_HI, g.ivols_host,
+                                  g.sums_host, s->stream);
+    if (g.sums_doubles)
+        SVMC_HIP_TRY(hipMemcpyAsync(g.sums_host, s->sums, g.sums_doubles * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    return SVMC_OK;
+}
+
+// the key of a chain on fixed randoms (svmc_logsv_chain_price_fixed_iv, _fixed_sets)
+static std::vector<unsigned char> fixed_key(const ChainView &c, int P, int variable_type, int want_iv, size_t ldw,
+                                            const double *const *W0s, const double *const *W1s, const int *nb_steps)
+{
+    std::vector<unsigned char> key = chain_key(c, P, variable_type, want_iv);
+    key_append(key, &ldw, 1);
+    key_append(key, W0s, c.m);
+    key_append(key, W1s, c.m);
+    key_append(key, nb_steps, c.m);
+    return key;
 }
 
 }  // namespace svmc
@@ -512,21 +633,6 @@ int svmc_logsv_chain_price_fixed(svmc_session_t session, const double *ttms_host
                                            prices_host, stderrs_host, nullptr);
 }
 
-// host side of the implied vols for the routes that do not replay a graph (multi-GPU, graphs off): the same solver
-static void implied_vols_on_host(const ChainView &c, int variable_type, const double *prices, double *ivols)
-{
-    for (int i = 0; i < c.m; ++i)
-        for (size_t k = c.offsets[i]; k < c.offsets[i + 1]; ++k) {
-            // quotes on the log-return only: options on the realised variance have no Black vol on the forward; inverse
-            // options (IC / IP) as in chain_implied_vols_kernel: the vanilla inversion of price x forward
-            const bool call = c.types[k] == SVMC_CALL || c.types[k] == SVMC_INV_CALL;
-            const double px = c.types[k] >= SVMC_INV_CALL ? prices[k] * c.forwards[i] : prices[k];
-            ivols[k] = variable_type == SVMC_LOG_RETURN
-                           ? black_implied_vol(px, c.strikes[k], call, c.forwards[i], c.ttms[i], c.discfactors[i], IV_VOL_LO, IV_VOL_HI)
-                           : std::numeric_limits<double>::quiet_NaN();
-        }
-}
-
 int svmc_logsv_chain_price_fixed_iv(svmc_session_t session, const double *ttms_host, const double *forwards_host,
                                     const double *discfactors_host, const double *vol_backbone_etas_host, int n_expiries,
                                     const double *strikes_host, const int8_t *types_host, const size_t *strike_offsets_host,
@@ -543,106 +649,46 @@ int svmc_logsv_chain_price_fixed_iv(svmc_session_t session, const double *ttms_h
     const size_t n = s->n_path;
     if (s->use_graphs && !s->sharded()) {
         // ---- replay path: the launch structure is captured once per (chain, randoms) and replayed per parameter set
-        std::vector<unsigned char> key;
-        const int want_iv = (ivols_host != nullptr && variable_type == SVMC_LOG_RETURN) ? 1 : 0;
-        key_append(key, &c.m, 1);
-        key_append(key, &variable_type, 1);
-        key_append(key, &want_iv, 1);
-        key_append(key, &ldw, 1);
-        key_append(key, c.ttms, c.m);
-        key_append(key, c.discfactors, want_iv ? c.m : 0);
-        key_append(key, c.forwards, c.m);
-        key_append(key, c.offsets, c.m + 1);
-        key_append(key, c.strikes, c.offsets[c.m]);
-        key_append(key, c.types, c.offsets[c.m]);
-        key_append(key, W0s, c.m);
-        key_append(key, W1s, c.m);
-        key_append(key, nb_steps_host, c.m);
-        FixedGraph &g = s->fixed;
-        const size_t n_params = 1 + static_cast<size_t>(c.m) * LOGSV_CONSTS_DOUBLES, n_sums = 3 * c.offsets[c.m];
-        std::vector<double> shifts(c.offsets[c.m]);
-        for (int i = 0; i < c.m; ++i)
-            for (size_t k = c.offsets[i]; k < c.offsets[i + 1]; ++k)
-                shifts[k] = payoff_shift(c.strikes[k], c.types[k], c.forwards[i], variable_type);
-        if (g.exec == nullptr || g.key != key) {
-            fixed_graph_release(g);
-            g.params_doubles = n_params;
-            g.sums_doubles = n_sums;
-            SVMC_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&g.params_host), n_params * sizeof(double), hipHostMallocDefault));
-            SVMC_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&g.sums_host), (n_sums ? n_sums : 1) * sizeof(double), hipHostMallocDefault));
-            SVMC_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&g.params_dev), n_params * sizeof(double)));
-            const size_t n_quotes = c.offsets[c.m];
-            if (want_iv && n_quotes) {
-                // the quotes' constants are part of the key: uploaded once, outside the graph
-                std::vector<double> quotes(IV_QUOTE_DOUBLES_HOST * n_quotes);
-                for (int i = 0; i < c.m; ++i)
-                    for (size_t k = c.offsets[i]; k < c.offsets[i + 1]; ++k) {
-                        double *qd = quotes.data() + IV_QUOTE_DOUBLES_HOST * k;
-                        qd[0] = c.strikes[k];
-                        qd[1] = static_cast<double>(c.types[k]);
-                        qd[2] = shifts[k];
-                        qd[3] = c.forwards[i];
-                        qd[4] = c.ttms[i];
-                        qd[5] = c.discfactors[i];
-                    }
-                SVMC_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&g.quotes_dev), quotes.size() * sizeof(double)));
-                SVMC_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&g.ivols_dev), n_quotes * sizeof(double)));
-                SVMC_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&g.ivols_host), n_quotes * sizeof(double), hipHostMallocDefault));
-                SVMC_HIP_TRY(hipMemcpy(g.quotes_dev, quotes.data(), quotes.size() * sizeof(double), hipMemcpyHostToDevice));
-            }
-            SVMC_HIP_TRY(hipStreamBeginCapture(s->stream, hipStreamCaptureModeRelaxed));
-            int rc = SVMC_OK;
-            hipError_t e = hipMemcpyAsync(g.params_dev, g.params_host, n_params * sizeof(double), hipMemcpyHostToDevice, s->stream);
-            if (e == hipSuccess && c.m <= MAX_FUSED_SLICES) {
-                // the whole chain in one launch: state initialised in the kernel (:1128-1130), slice loop inside (:1136-1160)
-                double *qsnaps = (variable_type == SVMC_Q_VAR) ? s->snap + static_cast<size_t>(c.m) * n : nullptr;
-                rc = logsv_chain_w_indirect(s->x, s->vol, s->qvar, n, c.m, nb_steps_host, g.params_dev + 1, g.params_dev, W0s, W1s,
-                                            ldw, c.forwards, s->snap, qsnaps, s->spot, s->ws, s->ws_bytes, s->stream);
-            } else if (e == hipSuccess) {
-                rc = fill_state_indirect(s->x, s->vol, s->qvar, n, g.params_dev, s->stream);                       // :1128-1130
-            }
-            for (int i = 0; c.m > MAX_FUSED_SLICES && i < c.m && e == hipSuccess && rc == SVMC_OK; ++i) {           // :1136-1160
-                double *qsnap = (variable_type == SVMC_Q_VAR) ? s->snap + static_cast<size_t>(c.m + i) * n : nullptr;
-                rc = logsv_slice_w_indirect(s->x, s->vol, s->qvar, n, nb_steps_host[i],
-                                            g.params_dev + 1 + static_cast<size_t>(i) * LOGSV_CONSTS_DOUBLES, W0s[i], W1s[i],
-                                            ldw, c.forwards[i], s->snap + static_cast<size_t>(i) * n, qsnap, s->spot + 2 * i,
-                                            s->ws, s->ws_bytes, s->stream);
-            }
-            std::vector<double> unused;
-            if (e == hipSuccess && rc == SVMC_OK) rc = enqueue_payoff_sums(s, c, variable_type, unused);
-            // results home: with implied vols the last kernel writes both the sums and the vols into the pinned host buffers
-            // (two copy nodes fewer per replay); without, the sums' copy
-            if (e == hipSuccess && rc == SVMC_OK && g.ivols_dev != nullptr)
-                rc = chain_implied_vols(s->sums, g.quotes_dev, n_quotes, static_cast<double>(s->n_path), IV_VOL_LO, IV_VOL_HI,
-                                        g.ivols_host, g.sums_host, s->stream);
-            else if (e == hipSuccess && rc == SVMC_OK && n_sums)
-                e = hipMemcpyAsync(g.sums_host, s->sums, n_sums * sizeof(double), hipMemcpyDeviceToHost, s->stream);
-            const hipError_t e_end = hipStreamEndCapture(s->stream, &g.graph);      // always leave capture mode
-            if (rc != SVMC_OK) { fixed_graph_release(g); return rc; }
-            if (e != hipSuccess || e_end != hipSuccess) {
-                fixed_graph_release(g);
-                return fail(SVMC_ERR_HIP, std::string("svmc_logsv_chain_price_fixed: graph capture: ") +
-                                              hipGetErrorString(e != hipSuccess ? e : e_end));
-            }
-            SVMC_HIP_TRY(hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0));
-            g.key = key;
-        }
-        g.params_host[0] = v0;
-        for (int i = 0; i < c.m; ++i)
-            logsv_consts_to_doubles(dts_host[i], theta, kappa1, kappa2, beta, volvol,
-                                    vol_backbone_etas_host ? vol_backbone_etas_host[i] : 1.0, is_spot_measure,
-                                    g.params_host + 1 + static_cast<size_t>(i) * LOGSV_CONSTS_DOUBLES);
         for (int i = 0; i < c.m; ++i)
             SVMC_REQUIRE(dts_host[i] > 0.0 && nb_steps_host[i] > 0, "svmc_logsv_chain_price_fixed: dt and nb_steps must be positive");
+        const int want_iv = (ivols_host != nullptr && variable_type == SVMC_LOG_RETURN) ? 1 : 0;
+        const std::vector<unsigned char> key = fixed_key(c, 1, variable_type, want_iv, ldw, W0s, W1s, nb_steps_host);
+        FixedGraph &g = s->fixed;
+        std::vector<double> shifts;
+        payoff_shifts_of(c, variable_type, shifts);
+        auto enqueue = [&]() -> int {
+            SVMC_HIP_TRY(hipMemcpyAsync(g.params_dev, g.params_host, g.params_doubles * sizeof(double), hipMemcpyHostToDevice, s->stream));
+            if (c.m <= MAX_FUSED_SLICES) {
+                // the whole chain in one launch: state initialised in the kernel (:1128-1130), slice loop inside (:1136-1160)
+                double *qsnaps = (variable_type == SVMC_Q_VAR) ? s->snap + static_cast<size_t>(c.m) * n : nullptr;
+                if (int rc = logsv_chain_w_indirect(s->x, s->vol, s->qvar, n, c.m, nb_steps_host, g.params_dev + 1, g.params_dev, W0s,
+                                                    W1s, ldw, c.forwards, s->snap, qsnaps, s->spot, s->ws, s->ws_bytes, s->stream))
+                    return rc;
+            } else {
+                if (int rc = fill_state_indirect(s->x, s->vol, s->qvar, n, g.params_dev, s->stream)) return rc;      // :1128-1130
+                for (int i = 0; i < c.m; ++i) {                                                                        // :1136-1160
+                    double *qsnap = (variable_type == SVMC_Q_VAR) ? s->snap + static_cast<size_t>(c.m + i) * n : nullptr;
+                    if (int rc = logsv_slice_w_indirect(s->x, s->vol, s->qvar, n, nb_steps_host[i],
+                                                        g.params_dev + 1 + static_cast<size_t>(i) * LOGSV_CONSTS_DOUBLES, W0s[i], W1s[i],
+                                                        ldw, c.forwards[i], s->snap + static_cast<size_t>(i) * n, qsnap, s->spot + 2 * i,
+                                                        s->ws, s->ws_bytes, s->stream))
+                        return rc;
+                }
+            }
+            if (int rc = enqueue_payoff_sums_of_set(s, c, variable_type, shifts, 0, 1)) return rc;
+            return enqueue_results_home(s, g);
+        };
+        if (g.key != key)
+            if (int rc = graph_prepare(g, key, c, shifts, 1, LOGSV_CONSTS_DOUBLES, want_iv)) return rc;
+        if (g.exec == nullptr)
+            if (int rc = graph_capture(s, g, fn, enqueue)) return rc;
+        const double set[6] = {v0, theta, kappa1, kappa2, beta, volvol};
+        fill_params<logsv_consts_to_doubles, LOGSV_CONSTS_DOUBLES>(g.params_host, c, 1, set, vol_backbone_etas_host, 0, dts_host,
+                                                                   is_spot_measure);
         SVMC_HIP_TRY(hipGraphLaunch(g.exec, s->stream));
         SVMC_HIP_TRY(hipStreamSynchronize(s->stream));
         ++s->graph_launches;
-        if (int rc = finalize_prices(s, c, g.sums_host, shifts, prices_host, stderrs_host)) return rc;
-        if (ivols_host != nullptr) {
-            if (g.ivols_host != nullptr) memcpy(ivols_host, g.ivols_host, c.offsets[c.m] * sizeof(double));
-            else implied_vols_on_host(c, variable_type, prices_host, ivols_host);      // Q_VAR chains: NaN
-        }
-        return SVMC_OK;
+        return finish_sets(s, c, g.sums_host, shifts, 1, variable_type, prices_host, stderrs_host, ivols_host, g.ivols_host);
     }
     if (int rc = svmc_fill_state(s->x, s->vol, s->qvar, n, 0.0, v0, 0.0, s->stream)) return rc;           // :1128-1130
     for (int i = 0; i < c.m; ++i) {                                                                       // :1136-1160
@@ -695,104 +741,30 @@ int svmc_logsv_chain_price_fixed_sets(svmc_session_t session, const double *ttms
     const int P = n_sets;
     for (int i = 0; i < c.m; ++i)
         SVMC_REQUIRE(dts_host[i] > 0.0 && nb_steps_host[i] > 0, "svmc_logsv_chain_price_fixed_sets: dt and nb_steps must be positive");
-    std::vector<unsigned char> key;
     const int want_iv = (ivols_host != nullptr && variable_type == SVMC_LOG_RETURN) ? 1 : 0;
-    key_append(key, &c.m, 1);
-    key_append(key, &P, 1);
-    key_append(key, &variable_type, 1);
-    key_append(key, &want_iv, 1);
-    key_append(key, &ldw, 1);
-    key_append(key, c.ttms, c.m);
-    key_append(key, c.discfactors, want_iv ? c.m : 0);
-    key_append(key, c.forwards, c.m);
-    key_append(key, c.offsets, c.m + 1);
-    key_append(key, c.strikes, K);
-    key_append(key, c.types, K);
-    key_append(key, W0s, c.m);
-    key_append(key, W1s, c.m);
-    key_append(key, nb_steps_host, c.m);
+    const std::vector<unsigned char> key = fixed_key(c, P, variable_type, want_iv, ldw, W0s, W1s, nb_steps_host);
     FixedGraph &g = s->fixed_sets;
-    // parameter block: [P] initial volatilities, then [m][P] LogsvConsts
-    const size_t n_params = static_cast<size_t>(P) + static_cast<size_t>(c.m) * P * LOGSV_CONSTS_DOUBLES, n_sums = 3 * K * P;
-    std::vector<double> shifts(K);
-    for (int i = 0; i < c.m; ++i)
-        for (size_t k = c.offsets[i]; k < c.offsets[i + 1]; ++k)
-            shifts[k] = payoff_shift(c.strikes[k], c.types[k], c.forwards[i], variable_type);
-    if (g.exec == nullptr || g.key != key) {
-        fixed_graph_release(g);
-        g.params_doubles = n_params;
-        g.sums_doubles = n_sums;
-        SVMC_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&g.params_host), n_params * sizeof(double), hipHostMallocDefault));
-        SVMC_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&g.sums_host), (n_sums ? n_sums : 1) * sizeof(double), hipHostMallocDefault));
-        SVMC_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&g.params_dev), n_params * sizeof(double)));
-        const size_t n_quotes = K * P;
-        if (want_iv && n_quotes) {
-            std::vector<double> quotes(IV_QUOTE_DOUBLES_HOST * n_quotes);
-            for (int q = 0; q < P; ++q)
-                for (int i = 0; i < c.m; ++i)
-                    for (size_t k = c.offsets[i]; k < c.offsets[i + 1]; ++k) {
-                        double *qd = quotes.data() + IV_QUOTE_DOUBLES_HOST * (K * q + k);
-                        qd[0] = c.strikes[k];
-                        qd[1] = static_cast<double>(c.types[k]);
-                        qd[2] = shifts[k];
-                        qd[3] = c.forwards[i];
-                        qd[4] = c.ttms[i];
-                        qd[5] = c.discfactors[i];
-                    }
-            SVMC_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&g.quotes_dev), quotes.size() * sizeof(double)));
-            SVMC_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&g.ivols_dev), n_quotes * sizeof(double)));
-            SVMC_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&g.ivols_host), n_quotes * sizeof(double), hipHostMallocDefault));
-            SVMC_HIP_TRY(hipMemcpy(g.quotes_dev, quotes.data(), quotes.size() * sizeof(double), hipMemcpyHostToDevice));
-        }
-        SVMC_HIP_TRY(hipStreamBeginCapture(s->stream, hipStreamCaptureModeRelaxed));
-        int rc = SVMC_OK;
-        hipError_t e = hipMemcpyAsync(g.params_dev, g.params_host, n_params * sizeof(double), hipMemcpyHostToDevice, s->stream);
-        if (e == hipSuccess) {
-            double *qsnaps = (variable_type == SVMC_Q_VAR) ? s->snap + static_cast<size_t>(c.m) * P * n : nullptr;
-            rc = logsv_chain_w_sets(n, P, c.m, nb_steps_host, g.params_dev + P, g.params_dev, W0s, W1s, ldw, c.forwards, s->snap,
-                                    qsnaps, s->spot, s->ws, s->ws_bytes, s->stream);
-        }
-        if (e == hipSuccess && rc == SVMC_OK) rc = enqueue_payoff_sums_of_sets(s, c, variable_type, shifts, P);
-        if (e == hipSuccess && rc == SVMC_OK && g.ivols_dev != nullptr)       // (the last kernel writes the pinned host buffers)
-            rc = chain_implied_vols(s->sums, g.quotes_dev, n_quotes, static_cast<double>(s->n_path), IV_VOL_LO, IV_VOL_HI,
-                                    g.ivols_host, g.sums_host, s->stream);
-        else if (e == hipSuccess && rc == SVMC_OK && n_sums)
-            e = hipMemcpyAsync(g.sums_host, s->sums, n_sums * sizeof(double), hipMemcpyDeviceToHost, s->stream);
-        const hipError_t e_end = hipStreamEndCapture(s->stream, &g.graph);      // always leave capture mode
-        if (rc != SVMC_OK) { fixed_graph_release(g); return rc; }
-        if (e != hipSuccess || e_end != hipSuccess) {
-            fixed_graph_release(g);
-            return fail(SVMC_ERR_HIP, std::string(fn) + ": graph capture: " + hipGetErrorString(e != hipSuccess ? e : e_end));
-        }
-        SVMC_HIP_TRY(hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0));
-        g.key = key;
-    }
-    for (int q = 0; q < P; ++q) {
-        const double *pr = params_host + row * q;
-        g.params_host[q] = pr[0];
-        for (int i = 0; i < c.m; ++i)
-            logsv_consts_to_doubles(dts_host[i], pr[1], pr[2], pr[3], pr[4], pr[5], pr[6 + i], is_spot_measure,
-                                    g.params_host + P + (static_cast<size_t>(i) * P + q) * LOGSV_CONSTS_DOUBLES);
-    }
+    std::vector<double> shifts;
+    payoff_shifts_of(c, variable_type, shifts);
+    auto enqueue = [&]() -> int {
+        SVMC_HIP_TRY(hipMemcpyAsync(g.params_dev, g.params_host, g.params_doubles * sizeof(double), hipMemcpyHostToDevice, s->stream));
+        double *qsnaps = (variable_type == SVMC_Q_VAR) ? s->snap + static_cast<size_t>(c.m) * P * n : nullptr;
+        if (int rc = logsv_chain_w_sets(n, P, c.m, nb_steps_host, g.params_dev + P, g.params_dev, W0s, W1s, ldw, c.forwards, s->snap,
+                                        qsnaps, s->spot, s->ws, s->ws_bytes, s->stream))
+            return rc;
+        if (int rc = enqueue_payoff_sums_of_sets(s, c, variable_type, shifts, P)) return rc;
+        return enqueue_results_home(s, g);
+    };
+    if (g.key != key)
+        if (int rc = graph_prepare(g, key, c, shifts, P, LOGSV_CONSTS_DOUBLES, want_iv)) return rc;
+    if (g.exec == nullptr)
+        if (int rc = graph_capture(s, g, fn, enqueue)) return rc;
+    fill_params<logsv_consts_to_doubles, LOGSV_CONSTS_DOUBLES>(g.params_host, c, P, params_host, params_host + 6, row, dts_host,
+                                                               is_spot_measure);
     SVMC_HIP_TRY(hipGraphLaunch(g.exec, s->stream));
     SVMC_HIP_TRY(hipStreamSynchronize(s->stream));
     ++s->graph_launches;
-    const double n_all = static_cast<double>(s->n_path);
-    for (int q = 0; q < P; ++q)
-        for (int i = 0; i < c.m; ++i) {
-            const size_t k0 = c.offsets[i], k = c.offsets[i + 1] - k0;
-            if (int rc = svmc_payoff_finalize(g.sums_host + 3 * (K * q + k0), shifts.data() + k0, k, c.discfactors[i], n_all,
-                                              prices_host + K * q + k0, stderrs_host + K * q + k0))
-                return rc;
-        }
-    if (ivols_host != nullptr) {
-        if (g.ivols_host != nullptr) {
-            memcpy(ivols_host, g.ivols_host, K * P * sizeof(double));
-        } else {
-            for (int q = 0; q < P; ++q) implied_vols_on_host(c, variable_type, prices_host + K * q, ivols_host + K * q);
-        }
-    }
-    return SVMC_OK;
+    return finish_sets(s, c, g.sums_host, shifts, P, variable_type, prices_host, stderrs_host, ivols_host, g.ivols_host);
 }
 
 int svmc_logsv_chain_price_frozen_sets(svmc_session_t session, const double *ttms_host, const double *forwards_host,
@@ -834,36 +806,20 @@ int svmc_logsv_chain_price_frozen_sets(svmc_session_t session, const double *ttm
     const bool graph = s->use_graphs && !s->sharded();
     const int want_iv = (ivols_host != nullptr && variable_type == SVMC_LOG_RETURN) ? 1 : 0;
     // everything that shapes the launches; the model constants travel in the parameter block
-    std::vector<unsigned char> key;
+    std::vector<unsigned char> key = chain_key(c, P, variable_type, want_iv);
     const int sharded = s->sharded() ? 1 : 0;
-    key_append(key, &c.m, 1);
-    key_append(key, &P, 1);
-    key_append(key, &variable_type, 1);
-    key_append(key, &want_iv, 1);
     key_append(key, &sharded, 1);
     key_append(key, &seed, 1);
     key_append(key, &call_id, 1);
     key_append(key, &s->path_offset, 1);
-    key_append(key, c.ttms, c.m);
-    key_append(key, c.discfactors, want_iv ? c.m : 0);
-    key_append(key, c.forwards, c.m);
-    key_append(key, c.offsets, c.m + 1);
-    key_append(key, c.strikes, K);
-    key_append(key, c.types, K);
     key_append(key, nb_steps_host, c.m);
     FixedGraph &g = s->frozen[P];
-    // parameter block: [P] initial volatilities, then [m][P] LogsvFast (log units)
-    const size_t n_params = static_cast<size_t>(P) + static_cast<size_t>(c.m) * P * LOGSV_FAST_CONSTS_DOUBLES, n_sums = 3 * K * P;
-    const size_t n_quotes = K * P;
-    const double n_all = static_cast<double>(s->sharded() ? s->n_total : s->n_path);
-    std::vector<double> shifts(K);
-    for (int i = 0; i < c.m; ++i)
-        for (size_t k = c.offsets[i]; k < c.offsets[i + 1]; ++k)
-            shifts[k] = payoff_shift(c.strikes[k], c.types[k], c.forwards[i], variable_type);
+    std::vector<double> shifts;
+    payoff_shifts_of(c, variable_type, shifts);
     // the chain's launches, queued on the session's stream: captured into the graph, or issued as they are (a communicator
     // attached, graphs off) with the two all-reduces between them
     auto enqueue = [&]() -> int {
-        SVMC_HIP_TRY(hipMemcpyAsync(g.params_dev, g.params_host, n_params * sizeof(double), hipMemcpyHostToDevice, s->stream));
+        SVMC_HIP_TRY(hipMemcpyAsync(g.params_dev, g.params_host, g.params_doubles * sizeof(double), hipMemcpyHostToDevice, s->stream));
         double *qsnaps = (variable_type == SVMC_Q_VAR) ? s->snap + static_cast<size_t>(c.m) * P * n : nullptr;
         // (a captured launch never carries the thread's clock probe: the graph outlives the probe's buffer)
         if (int rc = logsv_chain_rng_sets(n, P, c.m, nb_steps_host, g.params_dev + P, g.params_dev, c.forwards, seed, call_id,
@@ -871,61 +827,15 @@ int svmc_logsv_chain_price_frozen_sets(svmc_session_t session, const double *ttm
             return rc;
         if (int rc = all_reduce(s, s->spot, 2 * static_cast<size_t>(c.m) * P)) return rc;
         if (int rc = enqueue_payoff_sums_of_sets(s, c, variable_type, shifts, P)) return rc;
-        if (int rc = all_reduce(s, s->sums, n_sums)) return rc;
-        if (g.ivols_dev != nullptr) {               // (the last kernel writes the pinned host buffers: no copy nodes)
-            if (int rc = chain_implied_vols(s->sums, g.quotes_dev, n_quotes, n_all, IV_VOL_LO, IV_VOL_HI, g.ivols_host, g.sums_host,
-                                            s->stream))
-                return rc;
-        } else if (n_sums) {
-            SVMC_HIP_TRY(hipMemcpyAsync(g.sums_host, s->sums, n_sums * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-        }
-        return SVMC_OK;
+        if (int rc = all_reduce(s, s->sums, g.sums_doubles)) return rc;
+        return enqueue_results_home(s, g);
     };
-    if (g.params_dev == nullptr || g.key != key) {
-        fixed_graph_release(g);
-        g.params_doubles = n_params;
-        g.sums_doubles = n_sums;
-        SVMC_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&g.params_host), n_params * sizeof(double), hipHostMallocDefault));
-        SVMC_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&g.sums_host), (n_sums ? n_sums : 1) * sizeof(double), hipHostMallocDefault));
-        SVMC_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&g.params_dev), n_params * sizeof(double)));
-        if (want_iv && n_quotes) {
-            std::vector<double> quotes(IV_QUOTE_DOUBLES_HOST * n_quotes);
-            for (int q = 0; q < P; ++q)
-                for (int i = 0; i < c.m; ++i)
-                    for (size_t k = c.offsets[i]; k < c.offsets[i + 1]; ++k) {
-                        double *qd = quotes.data() + IV_QUOTE_DOUBLES_HOST * (K * q + k);
-                        qd[0] = c.strikes[k];
-                        qd[1] = static_cast<double>(c.types[k]);
-                        qd[2] = shifts[k];
-                        qd[3] = c.forwards[i];
-                        qd[4] = c.ttms[i];
-                        qd[5] = c.discfactors[i];
-                    }
-            SVMC_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&g.quotes_dev), quotes.size() * sizeof(double)));
-            SVMC_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&g.ivols_dev), n_quotes * sizeof(double)));
-            SVMC_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&g.ivols_host), n_quotes * sizeof(double), hipHostMallocDefault));
-            SVMC_HIP_TRY(hipMemcpy(g.quotes_dev, quotes.data(), quotes.size() * sizeof(double), hipMemcpyHostToDevice));
-        }
-        g.key = key;
-    }
-    if (graph && g.exec == nullptr) {      // captured at the first replayed call of this shape (an un-replayed call may come first)
-        SVMC_HIP_TRY(hipStreamBeginCapture(s->stream, hipStreamCaptureModeRelaxed));
-        const int rc = enqueue();
-        const hipError_t e_end = hipStreamEndCapture(s->stream, &g.graph);      // always leave capture mode
-        if (rc != SVMC_OK) { fixed_graph_release(g); return rc; }
-        if (e_end != hipSuccess) {
-            fixed_graph_release(g);
-            return fail(SVMC_ERR_HIP, std::string(fn) + ": graph capture: " + hipGetErrorString(e_end));
-        }
-        SVMC_HIP_TRY(hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0));
-    }
-    for (int q = 0; q < P; ++q) {
-        const double *pr = params_host + row * q;
-        g.params_host[q] = pr[0];
-        for (int i = 0; i < c.m; ++i)
-            logsv_fast_to_doubles(dts_host[i], pr[1], pr[2], pr[3], pr[4], pr[5], pr[6 + i], is_spot_measure,
-                                  g.params_host + P + (static_cast<size_t>(i) * P + q) * LOGSV_FAST_CONSTS_DOUBLES);
-    }
+    if (g.key != key)
+        if (int rc = graph_prepare(g, key, c, shifts, P, LOGSV_FAST_CONSTS_DOUBLES, want_iv)) return rc;
+    if (graph && g.exec == nullptr)        // captured at the first replayed call of this shape (an un-replayed call may come first)
+        if (int rc = graph_capture(s, g, fn, enqueue)) return rc;
+    fill_params<logsv_fast_to_doubles, LOGSV_FAST_CONSTS_DOUBLES>(g.params_host, c, P, params_host, params_host + 6, row, dts_host,
+                                                                  is_spot_measure);
     if (graph) {
         SVMC_HIP_TRY(hipGraphLaunch(g.exec, s->stream));
         ++s->graph_launches;
@@ -933,21 +843,7 @@ int svmc_logsv_chain_price_frozen_sets(svmc_session_t session, const double *ttm
         return rc;
     }
     SVMC_HIP_TRY(hipStreamSynchronize(s->stream));
-    for (int q = 0; q < P; ++q)
-        for (int i = 0; i < c.m; ++i) {
-            const size_t k0 = c.offsets[i], k = c.offsets[i + 1] - k0;
-            if (int rc = svmc_payoff_finalize(g.sums_host + 3 * (K * q + k0), shifts.data() + k0, k, c.discfactors[i], n_all,
-                                              prices_host + K * q + k0, stderrs_host + K * q + k0))
-                return rc;
-        }
-    if (ivols_host != nullptr) {
-        if (g.ivols_host != nullptr) {
-            memcpy(ivols_host, g.ivols_host, K * P * sizeof(double));
-        } else {
-            for (int q = 0; q < P; ++q) implied_vols_on_host(c, variable_type, prices_host + K * q, ivols_host + K * q);
-        }
-    }
-    return SVMC_OK;
+    return finish_sets(s, c, g.sums_host, shifts, P, variable_type, prices_host, stderrs_host, ivols_host, g.ivols_host);
 }
 
 int svmc_session_use_graphs(svmc_session_t session, int enable)

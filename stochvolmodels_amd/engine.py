@@ -326,7 +326,9 @@ def marshalled_chain(ttms, forwards, discfactors, strikes: Sequence[np.ndarray],
     """a chain's arrays as the fused C drivers take them (private contiguous copies, their ctypes pointers, the strike offsets and
     the slices that cut a result row into expiries), kept per chain CONTENT: a pricer is called on the same chain over and over
     (a calibration, a scenario sweep), and building these arrays costs as much as the launches of a small chain"""
-    arrs = [np.asarray(ttms), np.asarray(forwards), np.asarray(discfactors)] + list(strikes) + list(codes)
+    strikes = [np.asarray(k, dtype=np.float64) for k in strikes]
+    codes = [np.asarray(c) for c in codes]
+    arrs = [np.asarray(ttms), np.asarray(forwards), np.asarray(discfactors)] + strikes + codes
     key = tuple((a.dtype.str, a.shape, a.tobytes()) for a in arrs)
     hit = _CHAIN_CACHE.get(key)
     if hit is not None:
@@ -977,14 +979,15 @@ class DeviceRandoms:
         one synchronisation, prices and stderrs back -- the inner loop of an MC calibration.  Same kernels in the
         same order as mc_chain.price_chain_on_engine, hence the same bits.  want_ivols: a third list, the Black-76
         implied vols of the prices, computed by the graph's last kernel (svmc_logsv_chain_price_fixed_iv)."""
+        self._check_expiries(strikes)
         if self.is_frozen:
             row = np.concatenate([[v0, theta, kappa1, kappa2, beta, volvol], np.asarray(etas, dtype=np.float64).ravel()])
             return self.price_logsv_chain_sets(ttms, forwards, discfactors, strikes, codes, row[None, :], is_spot_measure,
                                                variable_type, want_ivols=want_ivols, use_graph=use_graph)[0]
         lib = _lib.load()
         m = len(self)
-        offs = np.concatenate([[0], np.cumsum([len(k) for k in strikes])]).astype(np.uintp)
-        total = int(offs[-1])
+        ch = marshalled_chain(ttms, forwards, discfactors, strikes, codes)
+        total = ch["total"]
         if self._session is None or self._session_strikes < total:
             if self._session is not None:
                 _lib.check(lib.svmc_session_destroy(self._session))
@@ -993,58 +996,29 @@ class DeviceRandoms:
             self._session, self._session_strikes = sess, max(total, 1)
         _lib.check(lib.svmc_session_use_graphs(self._session, int(bool(use_graph))))
         dp = C.POINTER(C.c_double)
-        f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)      # noqa: E731
-        ttms, forwards, discfactors, etas = f64(ttms), f64(forwards), f64(discfactors), f64(etas)
-        k_all = f64(np.concatenate(strikes)) if total else np.zeros(1)
-        c_all = np.ascontiguousarray(np.concatenate(codes), dtype=np.int8) if total else np.zeros(1, dtype=np.int8)
+        etas = np.ascontiguousarray(etas, dtype=np.float64)
         w0 = (C.c_void_p * m)(*[b.ptr for b in self.w0])
         w1 = (C.c_void_p * m)(*[b.ptr for b in self.w1])
-        nbs = (C.c_int * m)(*self.nb_steps)
-        dts = f64(self.dts)
+        nbs, dts = self._step_grid
         prices, stderrs = np.empty(max(total, 1)), np.empty(max(total, 1))
         ivols = np.empty(max(total, 1)) if want_ivols else None
         _lib.check(lib.svmc_logsv_chain_price_fixed_iv(
-            self._session, ttms.ctypes.data_as(dp), forwards.ctypes.data_as(dp), discfactors.ctypes.data_as(dp),
-            etas.ctypes.data_as(dp), m, k_all.ctypes.data_as(dp), c_all.ctypes.data_as(C.POINTER(C.c_int8)),
-            offs.ctypes.data_as(C.POINTER(C.c_size_t)), float(v0), float(theta), float(kappa1), float(kappa2),
-            float(beta), float(volvol), int(bool(is_spot_measure)), int(variable_type), w0, w1, nbs,
-            dts.ctypes.data_as(dp), self.n_local, prices.ctypes.data_as(dp), stderrs.ctypes.data_as(dp),
-            ivols.ctypes.data_as(dp) if want_ivols else None))
-        split = lambda a: [a[offs[i]:offs[i + 1]].copy() for i in range(m)]      # noqa: E731
+            self._session, ch["ttms"], ch["forwards"], ch["discfactors"], etas.ctypes.data_as(dp), m, ch["strikes"], ch["codes"],
+            ch["offsets"], float(v0), float(theta), float(kappa1), float(kappa2), float(beta), float(volvol),
+            int(bool(is_spot_measure)), int(variable_type), w0, w1, nbs, dts, self.n_local, prices.ctypes.data_as(dp),
+            stderrs.ctypes.data_as(dp), ivols.ctypes.data_as(dp) if want_ivols else None))
+        split = lambda a: [a[sl].copy() for sl in ch["slices"]]      # noqa: E731
         return (split(prices), split(stderrs), split(ivols)) if want_ivols else (split(prices), split(stderrs))
 
+    def _check_expiries(self, strikes) -> None:
+        if len(strikes) != len(self):
+            raise ValueError(f"the chain has {len(strikes)} expiries, the randoms {len(self)}")
 
-    def _marshalled_chain(self, ttms, forwards, discfactors, strikes, codes):
-        """the chain's arrays as the C ABI takes them (contiguous copies, their ctypes pointers, the strike offsets and the
-        slices that cut a result row into expiries), kept per chain CONTENT: the objective of a calibration prices the same
-        chain hundreds of times and the marshalling was a quarter of an evaluation's wall time."""
-        arrs = [np.asarray(ttms), np.asarray(forwards), np.asarray(discfactors)] + list(strikes) + list(codes)
-        key = tuple((a.dtype.str, a.shape, a.tobytes()) for a in arrs)
-        cache = self.__dict__.setdefault("_chain_cache", {})
-        hit = cache.get(key)
-        if hit is not None:
-            return hit
-        m = len(self)
-        dp = C.POINTER(C.c_double)
-        f64 = lambda a: np.array(a, dtype=np.float64, order="C", copy=True).ravel()      # noqa: E731  (private copies)
-        offs = np.concatenate([[0], np.cumsum([len(k) for k in strikes])]).astype(np.uintp)
-        total = int(offs[-1])
-        t, f, d = f64(ttms), f64(forwards), f64(discfactors)
-        k_all = f64(np.concatenate(strikes)) if total else np.zeros(1)
-        c_all = np.array(np.concatenate(codes), dtype=np.int8) if total else np.zeros(1, dtype=np.int8)
-        dts = f64(self.dts)
-        hit = {
-            "keep": (t, f, d, k_all, c_all, offs, dts), "total": total, "offs": offs,
-            "slices": [slice(int(offs[i]), int(offs[i + 1])) for i in range(m)],
-            "ttms": t.ctypes.data_as(dp), "forwards": f.ctypes.data_as(dp), "discfactors": d.ctypes.data_as(dp),
-            "strikes": k_all.ctypes.data_as(dp), "codes": c_all.ctypes.data_as(C.POINTER(C.c_int8)),
-            "offsets": offs.ctypes.data_as(C.POINTER(C.c_size_t)), "nbs": (C.c_int * m)(*self.nb_steps),
-            "dts": dts.ctypes.data_as(dp),
-        }
-        if len(cache) >= 8:
-            cache.clear()
-        cache[key] = hit
-        return hit
+    @functools.cached_property
+    def _step_grid(self):
+        """the randoms' step grid as the C drivers take it: nb_steps as a C int array, dts as a double pointer (which keeps its
+        array alive)"""
+        return (C.c_int * len(self))(*self.nb_steps), np.array(self.dts, dtype=np.float64).ctypes.data_as(C.POINTER(C.c_double))
 
     def price_logsv_chain_sets(self, ttms, forwards, discfactors, strikes: Sequence[np.ndarray], codes: Sequence[np.ndarray],
                                params_rows: np.ndarray, is_spot_measure: bool, variable_type: int, want_ivols: bool = False,
@@ -1053,14 +1027,16 @@ class DeviceRandoms:
         replayed graph whose stepping launch reads the randoms once for all of them.  params_rows [n_sets][6 + m] =
         (v0, theta, kappa1, kappa2, beta, volvol, vol-backbone eta per expiry).  Returns per set what price_logsv_chain
         returns -- the same bits."""
+        self._check_expiries(strikes)
         lib = _lib.load()
         m = len(self)
         params_rows = np.ascontiguousarray(params_rows, dtype=np.float64)
         n_sets = params_rows.shape[0]
         if params_rows.ndim != 2 or params_rows.shape[1] != 6 + m or n_sets < 1:
             raise ValueError("params_rows must have shape [n_sets, 6 + n_expiries]")
-        ch = self._marshalled_chain(ttms, forwards, discfactors, strikes, codes)
-        offs, total = ch["offs"], ch["total"]
+        ch = marshalled_chain(ttms, forwards, discfactors, strikes, codes)
+        total = ch["total"]
+        nbs, dts = self._step_grid
         per_launch = min(n_sets, 8)
         need = (m * per_launch, max(total * per_launch, 1))
         if self.is_frozen:
@@ -1088,15 +1064,15 @@ class DeviceRandoms:
             seed, call_id = self.frozen_stream
             _lib.check(lib.svmc_logsv_chain_price_frozen_sets(
                 self._session_sets, ch["ttms"], ch["forwards"], ch["discfactors"], m, ch["strikes"], ch["codes"], ch["offsets"],
-                n_sets, params_rows.ctypes.data_as(dp), int(bool(is_spot_measure)), int(variable_type), ch["nbs"], ch["dts"],
+                n_sets, params_rows.ctypes.data_as(dp), int(bool(is_spot_measure)), int(variable_type), nbs, dts,
                 seed, call_id, ptr(0), ptr(1), ptr(2) if want_ivols else None))
         else:
             w0 = (C.c_void_p * m)(*[b.ptr for b in self.w0])
             w1 = (C.c_void_p * m)(*[b.ptr for b in self.w1])
             _lib.check(lib.svmc_logsv_chain_price_fixed_sets(
                 self._session_sets, ch["ttms"], ch["forwards"], ch["discfactors"], m, ch["strikes"], ch["codes"], ch["offsets"],
-                n_sets, params_rows.ctypes.data_as(dp), int(bool(is_spot_measure)), int(variable_type), w0, w1, ch["nbs"],
-                ch["dts"], self.n_local, ptr(0), ptr(1), ptr(2) if want_ivols else None))
+                n_sets, params_rows.ctypes.data_as(dp), int(bool(is_spot_measure)), int(variable_type), w0, w1, nbs,
+                dts, self.n_local, ptr(0), ptr(1), ptr(2) if want_ivols else None))
         return [tuple([part[q, sl] for sl in slices] for part in res) for q in range(n_sets)]
 
 
