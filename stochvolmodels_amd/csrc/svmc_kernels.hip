@@ -320,9 +320,6 @@ __global__ __launch_bounds__(RNG_BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8)
     const auto exp_of = [&](double v) { return exp2u_tab(v, s_exp); };     // L is carried in units of ln2/256
     const size_t p = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
     const bool active = p < n;
-#ifdef SVMC_TAIL_PROBE                                     // tools/r03/tail_probe.py: per-wave start / end stamps instead of the
-    const uint64_t probe_t0 = wall_clock64();              // qvar snapshot (100 MHz s_memrealtime)
-#endif
     double xv = 0.0, s = 1.0, q = 0.0;
     if (active) {
         if (init.uniform) {                                // wave-uniform
@@ -355,43 +352,28 @@ __global__ __launch_bounds__(RNG_BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8)
         qvar[p] = q;
     }
     clock_probe_stamp(probe, 1);
-#ifdef SVMC_TAIL_PROBE
-    if ((threadIdx.x & 63u) == 0u && so.q_snap != nullptr) {
-        so.q_snap[2 * (p >> 6)] = static_cast<double>(probe_t0);
-        so.q_snap[2 * (p >> 6) + 1] = static_cast<double>(wall_clock64());
-    }
-    so.q_snap = nullptr;
-#endif
     slice_epilogue(so, p, active, xv, q);
 }
 
 // logsv_rng_kernel for a launch of a few waves per SIMD (few_waves_launch(): up to seven; the reference's default 10^5 paths are
 // 1.5).  Statement for statement the kernel above -- the same bits -- but compiled for latency instead of residency: TB-thread
-// blocks (256 in the product: every CU gets work, and four blocks' tables fit a CU's LDS), the register budget of WAVES waves per
-// SIMD, and the time loop in form LOOP (svmc_rng.h):
-//   GEN_LOOP_PIPE   the product: the step in two halves around its exp-table read, the next pair's cubics, the next Philox call
-//                   and the issue of the pair after that between them -- a wave overlaps its own LDS round trips with its own
-//                   arithmetic, and the waves of a CU cannot fall into a common LDS phase
-//   GEN_LOOP_FEW    round 5's form (all eight reads of a call, then the cubics), GEN_LOOP_AHEAD / GEN_LOOP_PAIR: the alternatives
-//                   the round-6 sweep measured against it (LOGSV_LAT_VARIANTS below)
+// blocks (256: every CU gets work, and four blocks' tables fit a CU's LDS), the register budget of WAVES waves per SIMD, and the
+// time loop in form GEN_LOOP_PIPE (svmc_rng.h): the step in two halves around its exp-table read, the next pair's cubics, the
+// next Philox call and the issue of the pair after that between them -- a wave overlaps its own LDS round trips with its own
+// arithmetic, and the waves of a CU cannot fall into a common LDS phase.  The forms it was measured against:
+// profiles/r06_mid_waves_sweep.json.
 constexpr int FEW_BLOCK = 256;
-// the time loop of a LogSV generator in form LOOP: the pipelined form takes the step in its two halves
+// the time loop of a LogSV generator: the pipelined form, the step in its two halves
 template <int LOOP>
 __device__ __forceinline__ void logsv_gen_time_loop(const PhiloxLane &lane, uint32_t step0, int nb, const RngTables &tab, const LogsvFast &c,
                                                     double &xacc, double &L, double &s, double &acc, const double *exp_table)
 {
-    if constexpr (LOOP == GEN_LOOP_PIPE) {
-        LogsvStepInFlight h;
-        const Exp2uTailV k = exp2u_tail_consts();
-        rng_time_loop_pipelined(
-            lane, step0, nb, tab, [&](double z0, double z1) { logsv_step_acc_front(c, xacc, L, s, z0, z1, exp_table, h); },
-            [&]() { logsv_step_acc_mid(h, k); }, [&]() { logsv_step_acc_back(s, acc, h); });
-    } else {
-        double s2_unused = 0.0;
-        gen_time_loop<LOOP>(lane, step0, nb, tab, [&](double z0, double z1) {
-            logsv_step_acc(c, xacc, L, s, s2_unused, acc, z0, z1, [&](double v) { return exp2u_tab(v, exp_table); });
-        });
-    }
+    static_assert(LOOP == GEN_LOOP_PIPE, "the LogSV few-waves generators run the pipelined loop");
+    LogsvStepInFlight h;
+    const Exp2uTailV k = exp2u_tail_consts();
+    rng_time_loop_pipelined(
+        lane, step0, nb, tab, [&](double z0, double z1) { logsv_step_acc_front(c, xacc, L, s, z0, z1, exp_table, h); },
+        [&]() { logsv_step_acc_mid(h, k); }, [&]() { logsv_step_acc_back(s, acc, h); });
 }
 
 template <int LOOP, int WAVES, int TB>
@@ -434,16 +416,15 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
 //   up to lat_waves_per_simd() (7: 458752 paths on an MI355X, 256 CUs x 4 SIMDs)   the few-waves form: 256-thread blocks, the
 //                                                                                  pipelined time loop, a 128-register budget
 //   above                                                                          the full-launch kernels (eight waves per SIMD)
-// Round 6 (tools/r06/mid_waves_sweep.py -> profiles/r06_mid_waves_sweep.json; wall time of logsv_mc_chain_pricer, 4 x 13 chain x
-// 364 steps, pipelined form / round 5's batched form / full-launch kernels): 2^16 paths 0.125 / 0.140 / 0.211 ms, 10^5 0.151 /
+// Round 6 (profiles/r06_mid_waves_sweep.json; wall time of logsv_mc_chain_pricer, 4 x 13 chain x 364 steps, pipelined form /
+// round 5's batched form / full-launch kernels): 2^16 paths 0.125 / 0.140 / 0.211 ms, 10^5 0.151 /
 // 0.165 / 0.212, 2 x 10^5 0.221 / 0.264 / 0.219, 4 x 10^5 0.331 / 0.411 / 0.344, 2^19 0.371 / 0.459 / 0.362.  From two waves per
 // SIMD on EVERY form runs at 250-275 cycles per wave-step -- C2's rate: the loop is bound by VALU issue and the LDS pipe together,
 // not by latency -- and a launch takes as long as its fullest SIMD: 200 000 paths are 3.05 waves per SIMD on average but four on
 // the fullest, so they cost what 262 144 cost.  What the pipelined form buys is the latency-bound end (one or two waves per SIMD,
 // the reference's default 10^5 paths) and the block shape in between (256-thread blocks spread 6.1 waves per SIMD evenly where
 // 1024-thread blocks leave a third of the CUs with eight).
-// SVMC_FEW_WAVES_MAX_PATHS overrides the limit as a path count (0: the full-launch kernels always); SVMC_GEN_VARIANT = index into
-// LOGSV_LAT_VARIANTS / HESTON_LAT_VARIANTS (-1: full-launch) forces one compiled form for every launch (measurement only).
+// SVMC_FEW_WAVES_MAX_PATHS overrides the limit as a path count (0: the full-launch kernels always).
 static size_t device_simds()
 {
     // per device of the calling thread's current context; the attribute query costs microseconds, so it is cached per device
@@ -471,15 +452,6 @@ static bool few_waves_launch(size_t n_path)
     }();
     const size_t limit = env_max >= 0 ? static_cast<size_t>(env_max) : static_cast<size_t>(LAT_WAVES_PER_SIMD) * 64 * device_simds();
     return n_path <= limit;
-}
-
-static int forced_gen_variant()
-{
-    static const int forced = [] {
-        const char *e = getenv("SVMC_GEN_VARIANT");
-        return e ? atoi(e) : -2;
-    }();
-    return forced;
 }
 
 // All expiries of a chain in ONE stepping launch: the slice loop runs inside the kernel, each slice with its own
@@ -634,8 +606,7 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
     clock_probe_stamp(probe, 1);
 }
 
-// The compiled few-waves forms of the LogSV generators.  Entry 0 is the product form; the rest are the alternatives the round-6
-// sweep measured against it (tools/r06/mid_waves_sweep.py selects one for EVERY launch with SVMC_GEN_VARIANT = index).
+// The few-waves form of the LogSV generators.
 using LogsvSliceKernel = void (*)(double *, double *, double *, size_t, int, LogsvFast, uint64_t, uint32_t, uint64_t, uint32_t, SliceOut,
                                   StateInit, uint64_t *);
 using LogsvChainKernel = void (*)(double *, double *, double *, size_t, ChainSlices, uint64_t, uint32_t, uint64_t, uint32_t, double *,
@@ -645,23 +616,13 @@ struct LogsvLatVariant {
     LogsvChainKernel chain;
     int block;
 };
-#define SVMC_LOGSV_LAT(LOOP, WAVES, TB) {logsv_rng_lat_kernel<LOOP, WAVES, TB>, logsv_chain_rng_lat_kernel<LOOP, WAVES, TB>, TB}
-static const LogsvLatVariant LOGSV_LAT_VARIANTS[] = {
-    SVMC_LOGSV_LAT(GEN_LOOP_PIPE, 4, 256),     // 0: the product form
-    SVMC_LOGSV_LAT(GEN_LOOP_FEW, 2, 256),      // 1: round 5's few-waves form (all eight reads of a call, then the cubics)
-    SVMC_LOGSV_LAT(GEN_LOOP_AHEAD, 4, 256),    // 2: the next call's reads under this call's two steps
-    SVMC_LOGSV_LAT(GEN_LOOP_PAIR, 4, 256),     // 3: the next step's reads under this step
-};
-#undef SVMC_LOGSV_LAT
-constexpr int N_LOGSV_LAT_VARIANTS = static_cast<int>(sizeof(LOGSV_LAT_VARIANTS) / sizeof(LOGSV_LAT_VARIANTS[0]));
+static const LogsvLatVariant LOGSV_FEW_WAVES_KERNELS = {logsv_rng_lat_kernel<GEN_LOOP_PIPE, 4, FEW_BLOCK>,
+                                                        logsv_chain_rng_lat_kernel<GEN_LOOP_PIPE, 4, FEW_BLOCK>, FEW_BLOCK};
 
-// -> the entry of LOGSV_LAT_VARIANTS a launch of n_path paths runs, or null: the full-launch kernels
+// -> the few-waves kernels a launch of n_path paths runs, or null: the full-launch kernels
 static const LogsvLatVariant *logsv_lat_variant(size_t n_path)
 {
-    const int forced = forced_gen_variant();
-    if (forced == -1) return nullptr;
-    if (forced >= 0) return &LOGSV_LAT_VARIANTS[forced < N_LOGSV_LAT_VARIANTS ? forced : 0];
-    return few_waves_launch(n_path) ? &LOGSV_LAT_VARIANTS[0] : nullptr;
+    return few_waves_launch(n_path) ? &LOGSV_FEW_WAVES_KERNELS : nullptr;
 }
 
 static inline unsigned lat_grid(size_t n, int block = FEW_BLOCK) { return static_cast<unsigned>((n + block - 1) / block); }
@@ -910,16 +871,15 @@ constexpr int LOGSV_FAST_DOUBLES = static_cast<int>(sizeof(LogsvFast) / sizeof(d
 //   * the register allocator is told the launch runs two waves per SIMD (amdgpu_waves_per_eu(2, 2): 256 registers) --
 //     left at its default it schedules for eight, reuses a handful of registers for every LDS read and waits for each read
 //     before issuing the next (185 full lgkmcnt waits per trip at P = 8);
-//   * the step runs piece by piece across the P states (logsv_step_acc_sets), all P exp-table reads in flight together;
-//   * an interior Philox call turns all four of its words into normals before the first of its two steps (eight table reads
-//     in flight), the edge calls of a slice that starts or ends on an odd step take the one half they own -- which
-//     (path, step) sees which word is rng_time_loop's rule, unchanged;
+//   * the step runs piece by piece across the P states (logsv_step_acc_sets_front / _back), all P exp-table reads in flight
+//     together;
+//   * the time loop is the generators' pipelined one (rng_time_loop_pipelined): the step in two halves around its P exp-table
+//     reads, the next pair's cubics, the next Philox call and the issue of the pair after that between them -- which
+//     (path, step) sees which word is rng_time_loop's rule, unchanged.  One / seven sets: 0.150 / 0.401 ms per evaluation
+//     (profiles/r06_frozen_objective.jsonl); round 5's draw forms: profiles/r05_frozen_objective.jsonl;
 //   * the (slice, set) constants are plain loads from the block's LDS copy: loop-invariant, the compiler keeps them in
 //     registers across the time loop where the budget allows and re-reads them where it does not.
 // The launch shape (block size, one block per CU) was measured NOT to matter: the dispatcher spreads 391 blocks evenly.
-#ifndef SVMC_FROZEN_DRAW_DEFAULT
-#define SVMC_FROZEN_DRAW_DEFAULT(P) 4      // which form of the draw the P-set kernel compiles (see the comment in its time loop)
-#endif
 template <int P>
 __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void logsv_chain_rng_sets_kernel(size_t n, ChainRngSetsSlices cs, const LogsvFast *__restrict__ consts,
@@ -981,97 +941,19 @@ void logsv_chain_rng_sets_kernel(size_t n, ChainRngSetsSlices cs, const LogsvFas
             kb[s] = s_c[s].bs;
             ke[s] = s_c[s].es;
         }
-        const auto step = [&](double z0, double z1) { logsv_step_acc_sets<P>(k1, k2, k3, kb, ke, xacc, L, sg, acc, z0, z1, s_exp); };
-#ifdef SVMC_FROZEN_DRAW
-        constexpr int DRAW = SVMC_FROZEN_DRAW;
-#else
-        constexpr int DRAW = SVMC_FROZEN_DRAW_DEFAULT(P);
-#endif
-        if constexpr (DRAW == 4) {
-            // round 6: the generators' pipelined loop -- the step in two halves around its P exp-table reads, the next pair's
-            // cubics, the next Philox call and the issue of the pair after that between them (rng_time_loop_pipelined)
-            LogsvSetsInFlight<P> h;
-            if constexpr (P <= 6) {
-                // the tails in the middle region on coefficients in vector registers (seven sets have no registers left for them)
-                const Exp2uTailV tail_k = exp2u_tail_consts();
-                rng_time_loop_pipelined(
-                    lane, tg, nb, tab,
-                    [&](double z0, double z1) { logsv_step_acc_sets_front<P>(k1, k2, k3, kb, ke, xacc, L, sg, z0, z1, s_exp, h); },
-                    [&]() { logsv_step_acc_sets_mid<P>(h, tail_k); }, [&]() { logsv_step_acc_sets_back<P, true>(sg, acc, h); });
-            } else {
-                rng_time_loop_pipelined(
-                    lane, tg, nb, tab,
-                    [&](double z0, double z1) { logsv_step_acc_sets_front<P>(k1, k2, k3, kb, ke, xacc, L, sg, z0, z1, s_exp, h); },
-                    [&]() { logsv_step_acc_sets_back<P>(sg, acc, h); });
-            }
-        } else if (nb > 0) {
-            // rng_time_loop's rule -- call c serves the steps 2c (words 0, 1) and 2c + 1 (words 2, 3) -- as an odd-start half
-            // call, the full calls, an even-end half call
-            const uint32_t first = tg, last = tg + static_cast<uint32_t>(nb) - 1u;
-            uint32_t c = first >> 1, r[4];
-            double a0, a1, b0, b1;
-            if (first & 1u) {
-                philox_draw(lane, c, r);
-                normals_from_words(r[2], r[3], tab, b0, b1);
-                step(b0, b1);
-                ++c;
-            }
-            // How the draw's table reads are scheduled against the steps decides a launch of one or two waves per SIMD, where no
-            // other wave hides an LDS round trip (10^5 paths x 364 steps, wall time of an evaluation, one / seven sets):
-            //   0  word by word, as the full-occupancy generators do -- the compiler reads, waits, evaluates four times over:
-            //      0.180 / 0.427 ms;
-            //   1  all eight reads of a call in flight, then the cubics (draw_issue / draw_finish): 0.172 / 0.419;
-            //   3  call c + 1's words, indices and READS issued before call c's two steps, its cubics after them -- the draw's
-            //      round trip hides behind the steps (it does not depend on the state); the last trip draws a call nobody
-            //      uses rather than branch inside the trip (with the branch, form 2, the trip is 8 us slower than form 0):
-            //      0.175 / 0.410.
-            //   4  (round 6) the step itself in two halves around its exp-table reads with the draw's pieces between them:
-            //      see above.
-            // SVMC_FROZEN_DRAW forces one form (tools/ubench A/B builds); round 5 ran form 1 for one set, form 3 for several.
-            const uint32_t c_end = (last + 1u) >> 1;
-            if constexpr (DRAW == 0) {
-                for (; c < c_end; ++c) {
-                    philox_draw(lane, c, r);
-                    normals_from_words(r[0], r[1], tab, a0, a1);
-                    normals_from_words(r[2], r[3], tab, b0, b1);
-                    step(a0, a1);
-                    step(b0, b1);
-                }
-            } else if constexpr (DRAW == 1) {
-                for (; c < c_end; ++c) {
-                    DrawInFlight d;
-                    double z[4];
-                    philox_draw(lane, c, r);
-                    draw_issue(r, tab, d);
-                    draw_finish(d, z);
-                    step(z[0], z[1]);
-                    step(z[2], z[3]);
-                }
-            } else if (c < c_end) {
-                DrawInFlight d;
-                philox_draw(lane, c, r);
-                draw_issue(r, tab, d);
-                for (; c < c_end; ++c) {
-                    double z[4];
-                    draw_finish(d, z);
-                    if constexpr (DRAW == 2) {
-                        if (c + 1u < c_end) {
-                            philox_draw(lane, c + 1u, r);
-                            draw_issue(r, tab, d);
-                        }
-                    } else {
-                        philox_draw(lane, c + 1u, r);
-                        draw_issue(r, tab, d);
-                    }
-                    step(z[0], z[1]);
-                    step(z[2], z[3]);
-                }
-            }
-            if (!(last & 1u)) {
-                philox_draw(lane, last >> 1, r);
-                normals_from_words(r[0], r[1], tab, a0, a1);
-                step(a0, a1);
-            }
+        LogsvSetsInFlight<P> h;
+        if constexpr (P <= 6) {
+            // the tails in the middle region on coefficients in vector registers (seven sets have no registers left for them)
+            const Exp2uTailV tail_k = exp2u_tail_consts();
+            rng_time_loop_pipelined(
+                lane, tg, nb, tab,
+                [&](double z0, double z1) { logsv_step_acc_sets_front<P>(k1, k2, k3, kb, ke, xacc, L, sg, z0, z1, s_exp, h); },
+                [&]() { logsv_step_acc_sets_mid<P>(h, tail_k); }, [&]() { logsv_step_acc_sets_back<P, true>(sg, acc, h); });
+        } else {
+            rng_time_loop_pipelined(
+                lane, tg, nb, tab,
+                [&](double z0, double z1) { logsv_step_acc_sets_front<P>(k1, k2, k3, kb, ke, xacc, L, sg, z0, z1, s_exp, h); },
+                [&]() { logsv_step_acc_sets_back<P>(sg, acc, h); });
         }
         tg += static_cast<uint32_t>(nb);
 #pragma unroll
@@ -1125,6 +1007,8 @@ __global__ __launch_bounds__(BLOCK) void fill_state_indirect_kernel(double *__re
 //     Identical in exact arithmetic to :942; rounding differs at the 1e-16 level per step (the tests hold both instantiations
 //     against the reference's golden paths at 1e-12).
 //   * supplied brownians are loaded a group of four steps ahead.
+//   * round 6: the next call's reads ahead and four steps with their four stores back to back were measured and not kept
+//     (profiles/r06_vol_paths_ab.jsonl).
 struct VolPathConsts {
     double c1;      // kappa1 theta dt K          (K = 256 / ln2: L is carried in units of ln2 / 256)
     double c2;      // (adj - kappa2) dt K
@@ -1137,22 +1021,6 @@ struct VolPathConsts {
 #define SVMC_VOLPATHS_RNG_BLOCK 1024   // drawing instantiation: two blocks per CU share one copy each of the draw's table
 #endif
 constexpr int VOLPATHS_RNG_BLOCK = SVMC_VOLPATHS_RNG_BLOCK;
-#ifndef SVMC_VOLPATHS_VARIANT
-#define SVMC_VOLPATHS_VARIANT 0        // measurement builds only (tools/r06/ab_vol_paths.sh): 1 = next call's reads ahead, 2 = four steps, four stores
-#endif
-#ifndef SVMC_VOLPATHS_PROBE
-#define SVMC_VOLPATHS_PROBE 0          // measurement builds only (tools/ubench/ab_vol_paths.py): 1 = no stores (the store stays in
-#endif                                 // the code behind a test that never holds), 2 = every store lands on row 1 (L2-resident)
-
-__device__ __forceinline__ void vol_paths_store(double *ptr, double v)
-{
-#if SVMC_VOLPATHS_PROBE == 1
-    if (v == -1.2345e300) *ptr = v;
-#else
-    *ptr = v;
-#endif
-}
-
 template <bool RNG>
 __global__ __launch_bounds__(RNG ? VOLPATHS_RNG_BLOCK : BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8)))
 void logsv_vol_paths_kernel(double *__restrict__ sigma_t, size_t ld, size_t n, int nb_steps, double v0, VolPathConsts c,
@@ -1167,7 +1035,7 @@ void logsv_vol_paths_kernel(double *__restrict__ sigma_t, size_t ld, size_t n, i
     const size_t p = static_cast<size_t>(blockIdx.x) * TB + threadIdx.x;
     if (p < n) {
         double s = v0, L = c.L0;
-        vol_paths_store(sigma_t + p, s);                                                        // :937
+        sigma_t[p] = s;                                                                         // :937
         double *out = sigma_t + ld + p;                    // row t + 1 of this path
         const auto step = [&](double w) {                  // w: N(0,1) (RNG) or the scaled increment sqrt(dt) N(0,1)   :925
             const double y = rcp_1n(s);
@@ -1176,10 +1044,8 @@ void logsv_vol_paths_kernel(double *__restrict__ sigma_t, size_t ld, size_t n, i
             L = L + c.c3;
             L = fma(c.cz, w, L);
             s = exp2u_tab(L, s_exp);                                                            // :943
-            vol_paths_store(out, s);                                                            // :944
-#if SVMC_VOLPATHS_PROBE != 2
+            *out = s;                                                                           // :944
             out += ld;
-#endif
         };
         int t = 0;
         if (RNG) {
@@ -1188,47 +1054,6 @@ void logsv_vol_paths_kernel(double *__restrict__ sigma_t, size_t ld, size_t n, i
             const PhiloxLane pl = philox_prepare(seed, c3 | 2u, path_offset + p);
             uint32_t r[4];
             double a0, a1, b0, b1;
-#if SVMC_VOLPATHS_VARIANT == 1     // measurement: the NEXT call's table reads in flight under this call's four steps (the same bits)
-            if (t + 4 <= nb_steps) {
-                DrawInFlight d;
-                philox_draw(pl, 0u, r);
-                draw_issue(r, tab, d);
-                for (; t + 4 <= nb_steps; t += 4) {
-                    double z[4];
-                    draw_finish(d, z);
-                    philox_draw(pl, static_cast<uint32_t>((t >> 2) + 1), r);      // the last trip draws a call nobody uses
-                    draw_issue(r, tab, d);
-                    step(z[0]);
-                    step(z[1]);
-                    step(z[2]);
-                    step(z[3]);
-                }
-            }
-#elif SVMC_VOLPATHS_VARIANT == 2   // measurement: four steps into registers, then their four stores back to back (the same bits)
-            for (; t + 4 <= nb_steps; t += 4) {
-                philox_draw(pl, static_cast<uint32_t>(t >> 2), r);
-                normals_from_words(r[0], r[1], tab, a0, a1);
-                normals_from_words(r[2], r[3], tab, b0, b1);
-                double sv[4];
-                const double zz[4] = {a0, a1, b0, b1};
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const double y = rcp_1n(s);
-                    L = fma(c.c2, s, L);
-                    L = fma(c.c1, y, L);
-                    L = L + c.c3;
-                    L = fma(c.cz, zz[u], L);
-                    s = exp2u_tab(L, s_exp);
-                    sv[u] = s;
-                }
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    vol_paths_store(out, sv[u]);
-                    out += ld;
-                }
-            }
-#else
             for (; t + 4 <= nb_steps; t += 4) {
                 philox_draw(pl, static_cast<uint32_t>(t >> 2), r);
                 normals_from_words(r[0], r[1], tab, a0, a1);
@@ -1238,7 +1063,6 @@ void logsv_vol_paths_kernel(double *__restrict__ sigma_t, size_t ld, size_t n, i
                 step(b0);
                 step(b1);
             }
-#endif
             if (t < nb_steps) {                            // the last, partial call (wave-uniform)
                 philox_draw(pl, static_cast<uint32_t>(t >> 2), r);
                 normals_from_words(r[0], r[1], tab, a0, a1);
@@ -1550,9 +1374,6 @@ __global__ __launch_bounds__(RNG ? RNG_BLOCK : BLOCK) void rough_logsv_expiries_
 // ---------------------------------------------------------------------------------------------------
 // Heston generators (pricers/heston_pricer.py:334-381; QE is new)
 // ---------------------------------------------------------------------------------------------------
-#ifndef SVMC_HESTON_ATTR
-#define SVMC_HESTON_ATTR               // A/B hook (tools/ubench/build_variants.sh): e.g. __attribute__((amdgpu_waves_per_eu(8, 8)))
-#endif
 // LOOP: the form of the time loop (svmc_rng.h GenLoop): the full-launch kernels run GEN_LOOP_FULL, the few-waves ones GEN_LOOP_PAIR
 // kernel-template scheme ids: the C ABI's two (SVMC_HESTON_EULER_FLOOR = 0, SVMC_HESTON_QE = 1) and QE specialised at compile
 // time for parameter sets that never leave the quadratic branch and keep the martingale correction defined (QeConsts::quad_only
@@ -1630,7 +1451,7 @@ __device__ __forceinline__ void heston_rng_body(double *__restrict__ x, double *
 }
 
 template <int SCHEME>
-__global__ __launch_bounds__(RNG_BLOCK) SVMC_HESTON_ATTR void heston_rng_kernel(double *__restrict__ x, double *__restrict__ var,
+__global__ __launch_bounds__(RNG_BLOCK) void heston_rng_kernel(double *__restrict__ x, double *__restrict__ var,
                                                            double *__restrict__ qvar, size_t n, int nb_steps,
                                                            HestonConsts c, QeConsts qc, uint64_t seed,
                                                            uint32_t c3, uint64_t path_offset,
@@ -1733,7 +1554,7 @@ __device__ __forceinline__ void heston_chain_rng_body(double *__restrict__ x, do
 }
 
 template <int SCHEME>
-__global__ __launch_bounds__(RNG_BLOCK) SVMC_HESTON_ATTR void heston_chain_rng_kernel(double *__restrict__ x, double *__restrict__ var,
+__global__ __launch_bounds__(RNG_BLOCK) void heston_chain_rng_kernel(double *__restrict__ x, double *__restrict__ var,
                                                                  double *__restrict__ qvar, size_t n,
                                                                  HestonChainSlices cs, uint64_t seed, uint32_t c3,
                                                                  uint64_t path_offset, uint32_t step_offset,
@@ -2559,9 +2380,9 @@ int svmc_expanding_mean_squares(const double *a, size_t ld, size_t n_rows, size_
     return check_launch("svmc_expanding_mean_squares");
 }
 
-// the compiled few-waves forms of the Heston generators, per scheme (see LOGSV_LAT_VARIANTS: entry 0 the product form, the rest
-// measurement alternatives behind SVMC_GEN_VARIANT).  The Euler step has no LDS read of its own, so one pair ahead hides the
-// draw's round trip completely; QE (100 registers by itself) runs the same loop at the 128-register budget.
+// the few-waves forms of the Heston generators, per kernel scheme id (the forms they were measured against:
+// profiles/r06_mid_waves_sweep.json).  The Euler step has no LDS read of its own, so one pair ahead hides the draw's round trip
+// completely; QE (100 registers by itself) runs the same loop at the 128-register budget.
 using HestonSliceKernel = void (*)(double *, double *, double *, size_t, int, HestonConsts, QeConsts, uint64_t, uint32_t, uint64_t, uint32_t,
                                    SliceOut, StateInit);
 using HestonChainKernel = void (*)(double *, double *, double *, size_t, HestonChainSlices, uint64_t, uint32_t, uint64_t, uint32_t, double *,
@@ -2571,24 +2392,12 @@ struct HestonLatVariant {
     HestonChainKernel chain;
     int block;
 };
-#define SVMC_HESTON_LAT(S, LOOP, WAVES, TB) {heston_rng_lat_kernel<S, LOOP, WAVES, TB>, heston_chain_rng_lat_kernel<S, LOOP, WAVES, TB>, TB}
-constexpr int N_HESTON_LAT_VARIANTS = 3;
-static const HestonLatVariant HESTON_LAT_VARIANTS[3][N_HESTON_LAT_VARIANTS] = {
-    {   // Euler with the reference's floor
-        SVMC_HESTON_LAT(SVMC_HESTON_EULER_FLOOR, GEN_LOOP_PAIR, 4, 256),
-        SVMC_HESTON_LAT(SVMC_HESTON_EULER_FLOOR, GEN_LOOP_FEW, 2, 256),
-        SVMC_HESTON_LAT(SVMC_HESTON_EULER_FLOOR, GEN_LOOP_AHEAD, 4, 256),
-    },
-    {   // QE
-        SVMC_HESTON_LAT(SVMC_HESTON_QE, GEN_LOOP_PAIR, 3, 256),
-        SVMC_HESTON_LAT(SVMC_HESTON_QE, GEN_LOOP_FEW, 2, 256),
-        SVMC_HESTON_LAT(SVMC_HESTON_QE, GEN_LOOP_AHEAD, 3, 256),
-    },
-    {   // QE, quadratic branch only
-        SVMC_HESTON_LAT(HESTON_QE_QUAD, GEN_LOOP_PAIR, 4, 256),
-        SVMC_HESTON_LAT(HESTON_QE_QUAD, GEN_LOOP_FEW, 2, 256),
-        SVMC_HESTON_LAT(HESTON_QE_QUAD, GEN_LOOP_AHEAD, 3, 256),
-    }};
+#define SVMC_HESTON_LAT(S, WAVES) \
+    {heston_rng_lat_kernel<S, GEN_LOOP_PAIR, WAVES, FEW_BLOCK>, heston_chain_rng_lat_kernel<S, GEN_LOOP_PAIR, WAVES, FEW_BLOCK>, FEW_BLOCK}
+static const HestonLatVariant HESTON_FEW_WAVES_KERNELS[3] = {
+    SVMC_HESTON_LAT(SVMC_HESTON_EULER_FLOOR, 4),           // Euler with the reference's floor
+    SVMC_HESTON_LAT(SVMC_HESTON_QE, 3),                    // QE
+    SVMC_HESTON_LAT(HESTON_QE_QUAD, 4)};                   // QE, quadratic branch only
 #undef SVMC_HESTON_LAT
 
 // the full-launch kernels, per kernel scheme id (0, 1 or HESTON_QE_QUAD)
@@ -2600,11 +2409,7 @@ static const HestonLatVariant HESTON_FULL_KERNELS[3] = {
 // -> the kernels a launch of n_path paths of kernel scheme `scheme` runs: a few-waves form or the full-launch ones
 static const HestonLatVariant *heston_variant(int scheme, size_t n_path)
 {
-    const HestonLatVariant *row = HESTON_LAT_VARIANTS[scheme];
-    const int forced = forced_gen_variant();
-    if (forced == -1) return &HESTON_FULL_KERNELS[scheme];
-    if (forced >= 0) return &row[forced < N_HESTON_LAT_VARIANTS ? forced : 0];
-    return few_waves_launch(n_path) ? &row[0] : &HESTON_FULL_KERNELS[scheme];
+    return few_waves_launch(n_path) ? &HESTON_FEW_WAVES_KERNELS[scheme] : &HESTON_FULL_KERNELS[scheme];
 }
 
 static int heston_rng_launch(const char *fn, double *x, double *var, double *qvar, size_t n_path, int nb_steps, double dt,

@@ -27,6 +27,8 @@
 #include <stdint.h>
 #include <string.h>
 
+#include "svmc_icdf_table.h"          // the random stream's table: its lattice decides icdf_lattice_point below
+
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 #define SVMC_HD __host__ __device__ __forceinline__
@@ -281,12 +283,7 @@ SVMC_HD double exp2u_tab(double y, const double *tab)
     int ni;
     double r;
     exp2u_reduce(y, ni, r);
-#if defined(SVMC_PROBE) && (SVMC_PROBE & 1)          // measurement build: no exp-table read
-    const double t = 1.0;
-    (void)tab;
-#else
     const double t = tab[ni & 255];
-#endif
     return exp2u_scale(t, exp2u_tail(r), ni);
 }
 
@@ -397,7 +394,7 @@ struct alignas(16) IcdfPiece {
 // the lattice point of a word: the signed integer itself (stream version 4: magnitudes 0 .. 2^31, both ends map to z = 0, every
 // other magnitude occurs with both signs -- exactly symmetric with no add), or k + 1/2 (version 3's table: SVMC_ICDF_HALF_LATTICE)
 #ifndef SVMC_ICDF_HALF_LATTICE
-#define SVMC_ICDF_HALF_LATTICE 0
+#error "svmc_icdf_table.h must define SVMC_ICDF_HALF_LATTICE (tools/gen_icdf_table.py)"
 #endif
 SVMC_HD double icdf_lattice_point(uint32_t w)
 {
@@ -418,15 +415,8 @@ SVMC_HD double normal_icdf32(uint32_t w, const IcdfPiece *tab)
     const uint32_t hi = double_hi(t);
     const uint32_t off = (hi >> (16 - M)) & ((static_cast<uint32_t>(SEGMENTS) - 1u) << 4);
     const char *base = reinterpret_cast<const char *>(tab) + off;
-#if defined(SVMC_PROBE) && (SVMC_PROBE & 2)          // measurement build: no table reads in the draw
-    asm volatile("" : : "v"(off));                     // the offset is still computed: the VALU stream is the product's
-    const IcdfPiece e0 = IcdfPiece{1e-10, 1e-10};
-    const IcdfPiece e1 = IcdfPiece{1e-20, 1e-30};
-    (void)base;
-#else
     const IcdfPiece e0 = *reinterpret_cast<const IcdfPiece *>(base);
     const IcdfPiece e1 = *reinterpret_cast<const IcdfPiece *>(base + 16 * SEGMENTS);
-#endif
     double p;
     if (RAW) {
         // pieces {a0, a1}, {a2, a3}: the cubic in |t| ITSELF.  Re-expanding a segment's polynomial about 0 makes its terms

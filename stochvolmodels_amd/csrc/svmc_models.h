@@ -170,11 +170,7 @@ __device__ __forceinline__ void logsv_step_acc_front(const LogsvFast &f, double 
     L = fma(f.bs, z0, L);
     L = fma(f.es, z1, L);
     exp2u_reduce(L, h.ni, h.r);
-#if defined(SVMC_PROBE) && (SVMC_PROBE & 1)          // measurement build: no exp-table read on the step's chain
-    h.t = 1.0;
-#else
     h.t = exp_table[h.ni & 255];
-#endif
 }
 // the exponential's polynomial tail: needs the reduced argument only, so it runs in the loop's middle region, among the draw's
 // integer work, instead of as a dependent chain (with its hazard s_nop's) right before the table value is consumed
@@ -190,45 +186,10 @@ __device__ __forceinline__ void logsv_step_acc_back(double &sigma, double &acc, 
 }
 
 // logsv_step_acc for P independent states of one lane (P parameter sets on the same two normals), piece by piece ACROSS the
-// states: the reciprocals, the five updates of L, the exp's reduction, all P table reads, the tails, the scalings.  Per
-// state these are logsv_step_acc's operations in logsv_step_acc's order -- the same bits -- but the P dependent chains
-// (about twenty fp64 operations around an LDS round trip each) now overlap instead of running one after the other.
-template <int P>
-__device__ __forceinline__ void logsv_step_acc_sets(const double (&c1)[P], const double (&c2)[P], const double (&c3)[P],
-                                                    const double (&bs)[P], const double (&es)[P], double (&xacc)[P],
-                                                    double (&L)[P], double (&sigma)[P], double (&acc)[P], double z0, double z1,
-                                                    const double *exp_table)
-{
-    double y[P], r[P], t[P];
-    int ni[P];
-#pragma unroll
-    for (int s = 0; s < P; ++s) y[s] = rcp_1n(sigma[s]);
-#pragma unroll
-    for (int s = 0; s < P; ++s) xacc[s] = fma(sigma[s], z0, xacc[s]);
-#pragma unroll
-    for (int s = 0; s < P; ++s) {
-        double l = fma(c2[s], sigma[s], L[s]);
-        l = fma(c1[s], y[s], l);
-        l = l + c3[s];
-        l = fma(bs[s], z0, l);
-        L[s] = fma(es[s], z1, l);
-    }
-#pragma unroll
-    for (int s = 0; s < P; ++s) exp2u_reduce(L[s], ni[s], r[s]);
-#pragma unroll
-    for (int s = 0; s < P; ++s) t[s] = exp_table[ni[s] & 255];
-#pragma unroll
-    for (int s = 0; s < P; ++s) r[s] = exp2u_tail(r[s]);
-#pragma unroll
-    for (int s = 0; s < P; ++s) {
-        const double sn = exp2u_scale(t[s], r[s], ni[s]);
-        acc[s] = fma(sn, sn, acc[s]);
-        sigma[s] = sn;
-    }
-}
-
-// logsv_step_acc_sets in two halves around the P exp-table reads (rng_time_loop_pipelined): front = everything up to the ISSUE
-// of the reads, back = what consumes them.  Per state logsv_step_acc_sets' operations in its order: the same bits.
+// states and in two halves around the P exp-table reads (rng_time_loop_pipelined): front = the reciprocals, the five updates of
+// L, the exp's reduction and the ISSUE of all P table reads, back = what consumes them.  Per state these are logsv_step_acc's
+// operations with exp2u_tab as the exponential, in its order -- the same bits -- but the P dependent chains (about twenty fp64
+// operations around an LDS round trip each) overlap instead of running one after the other.
 template <int P>
 struct LogsvSetsInFlight {
     double r[P], t[P];

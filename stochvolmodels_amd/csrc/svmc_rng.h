@@ -29,14 +29,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#ifdef SVMC_ICDF_TABLE_HEADER          // A/B hook: another (M, degree) of tools/gen_icdf_table.py
-#include SVMC_ICDF_TABLE_HEADER
-#else
 #include "svmc_icdf_table.h"
-#endif
-#ifndef SVMC_ICDF_RAW
-#define SVMC_ICDF_RAW 0
-#endif
 #include "svmc_log_table.h"
 #include "svmc_math.h"
 
@@ -61,20 +54,10 @@ struct RngTables {
 };
 
 constexpr unsigned ICDF_PIECES = SVMC_ICDF_PIECES;
-// SVMC_ICDF_MIXED (measurement builds only, round 6, VERDICT r05 item 2: "one LDS read per normal"): the EDGE form of the table
-// with its two high-order coefficients kept as fp32 in LDS -- 24 bytes per normal (one ds_read_b128 + one ds_read_b64) instead of
-// 32 (two ds_read_b128); the cubic then runs a3 d + a2 in fp32 and the two low-order steps in fp64 (12 VALU instructions per
-// normal against the product's 8).  Another stream (other bits): never the product.  tools/r06/ab_icdf.sh builds and times it.
-#ifndef SVMC_ICDF_MIXED
-#define SVMC_ICDF_MIXED 0
-#endif
+// (a 24-byte mixed-precision form of the table, another stream, measured LDS -22 %, VALU +24 %, 10 % slower on C2:
+// profiles/r06_ab_icdf.jsonl)
 struct RngTablesLds {
-#if SVMC_ICDF_MIXED
-    IcdfPiece icdf[SVMC_ICDF_SEGMENTS];
-    float2 hi[SVMC_ICDF_SEGMENTS];
-#else
     IcdfPiece icdf[ICDF_PIECES * SVMC_ICDF_SEGMENTS];
-#endif
 };
 
 // the log table alone (the streamed Heston QE kernel: its martingale correction takes logs, it draws nothing)
@@ -87,16 +70,7 @@ __device__ __forceinline__ const LogTabEntry *stage_log_table(LogTabEntry (&lds)
 
 __device__ __forceinline__ void copy_icdf_table(RngTablesLds &lds)
 {
-#if SVMC_ICDF_MIXED
-    static_assert(SVMC_ICDF_EDGE && !SVMC_ICDF_RAW && SVMC_ICDF_DEG == 3, "the mixed-precision table is the edge form of a cubic");
-    for (unsigned i = threadIdx.x; i < SVMC_ICDF_SEGMENTS; i += blockDim.x) {
-        lds.icdf[i] = g_icdf_table[i];
-        const IcdfPiece h = g_icdf_table[SVMC_ICDF_SEGMENTS + i];
-        lds.hi[i] = make_float2(static_cast<float>(h.a), static_cast<float>(h.b));
-    }
-#else
     for (unsigned i = threadIdx.x; i < ICDF_PIECES * SVMC_ICDF_SEGMENTS; i += blockDim.x) lds.icdf[i] = g_icdf_table[i];
-#endif
 }
 
 __device__ __forceinline__ RngTables stage_rng_tables(RngTablesLds &lds)
@@ -143,12 +117,6 @@ __device__ __forceinline__ RngTables stage_tables(RngTablesLds &lds, double (&ld
     return RngTables{lds.icdf, nullptr};
 }
 
-#ifndef SVMC_TRIP_BARRIER
-#define SVMC_TRIP_BARRIER 0
-#endif
-#ifndef SVMC_PHILOX_FENCE
-#define SVMC_PHILOX_FENCE 0
-#endif
 #ifndef SVMC_PHILOX_ROUNDS
 #define SVMC_PHILOX_ROUNDS 7
 #endif
@@ -268,77 +236,11 @@ __device__ __forceinline__ double uniform_32(uint32_t k)
 }
 
 // The two normals of a time step from two words, each by inversion (svmc_math.h normal_icdf32)
-#if SVMC_ICDF_MIXED
-__device__ __forceinline__ double normal_icdf32_mixed(uint32_t w, const IcdfPiece *tab)
-{
-    const double t = icdf_lattice_point(w);
-    const uint32_t hi = double_hi(t);
-    const uint32_t off = (hi >> (16 - SVMC_ICDF_M)) & ((static_cast<uint32_t>(SVMC_ICDF_SEGMENTS) - 1u) << 4);
-    const char *base = reinterpret_cast<const char *>(tab);
-    const IcdfPiece e0 = *reinterpret_cast<const IcdfPiece *>(base + off);
-    const float2 e1 = *reinterpret_cast<const float2 *>(base + 16 * SVMC_ICDF_SEGMENTS + (off >> 1));
-    const double edge = bits_to_double(0u, hi & (0x7FFFFFFFu & ~((1u << (20 - SVMC_ICDF_M)) - 1u)));
-    const double d = fabs(t) - edge;
-    const float q = fmaf(e1.y, static_cast<float>(d), e1.x);
-    double p = fma(static_cast<double>(q), d, e0.b);
-    p = fma(p, d, e0.a);
-    return copysign(p, t);
-}
-#endif
-
 __device__ __forceinline__ void normals_from_words(uint32_t ra, uint32_t rb, const RngTables &t, double &w0, double &w1)
 {
-#if SVMC_ICDF_MIXED
-    w0 = normal_icdf32_mixed(ra, t.icdf);
-    w1 = normal_icdf32_mixed(rb, t.icdf);
-    return;
-#endif
     w0 = normal_icdf32<SVMC_ICDF_M, SVMC_ICDF_SEGMENTS, SVMC_ICDF_DEG, SVMC_ICDF_EDGE != 0, SVMC_ICDF_RAW != 0>(ra, t.icdf);
     w1 = normal_icdf32<SVMC_ICDF_M, SVMC_ICDF_SEGMENTS, SVMC_ICDF_DEG, SVMC_ICDF_EDGE != 0, SVMC_ICDF_RAW != 0>(rb, t.icdf);
 }
-
-// The four normals of one Philox call in two halves, for launches of one or two waves per SIMD where an LDS round trip is not
-// hidden by other waves: draw_issue() converts the words and puts all eight table reads in flight (nothing is scheduled
-// across its end), draw_finish() runs the four cubics.  normal_icdf32's operations on the same operands: the same bits.
-struct DrawInFlight {
-    double t[4];
-    IcdfPiece e0[4], e1[4];
-};
-#if SVMC_ICDF_MIXED          // (the measurement build times the full-launch kernels only: the split forms just have to compile)
-__device__ __forceinline__ void draw_issue(const uint32_t (&r)[4], const RngTables &tab, DrawInFlight &d)
-{
-    for (int k = 0; k < 4; ++k) d.t[k] = normal_icdf32_mixed(r[k], tab.icdf);
-}
-__device__ __forceinline__ void draw_finish(const DrawInFlight &d, double (&z)[4])
-{
-    for (int k = 0; k < 4; ++k) z[k] = d.t[k];
-}
-#else
-__device__ __forceinline__ void draw_issue(const uint32_t (&r)[4], const RngTables &tab, DrawInFlight &d)
-{
-    static_assert(SVMC_ICDF_RAW != 0, "the split draw is written for the raw form of the table");
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        d.t[k] = icdf_lattice_point(r[k]);
-        const uint32_t off = (double_hi(d.t[k]) >> (16 - SVMC_ICDF_M)) & ((static_cast<uint32_t>(SVMC_ICDF_SEGMENTS) - 1u) << 4);
-        const char *base = reinterpret_cast<const char *>(tab.icdf) + off;
-        d.e0[k] = *reinterpret_cast<const IcdfPiece *>(base);
-        d.e1[k] = *reinterpret_cast<const IcdfPiece *>(base + 16 * SVMC_ICDF_SEGMENTS);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-}
-__device__ __forceinline__ void draw_finish(const DrawInFlight &d, double (&z)[4])
-{
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const double a = fabs(d.t[k]);
-        double p = fma(d.e1[k].b, a, d.e1[k].a);
-        p = fma(p, a, d.e0[k].b);
-        p = fma(p, a, d.e0[k].a);
-        z[k] = copysign(p, d.t[k]);
-    }
-}
-#endif
 
 // The time loop of every on-device-RNG generator: time steps [0, nb) of a lane whose first step has the chain-global
 // index step0.  One Philox call serves the two steps 2c, 2c + 1, so the loop runs over CALLS and each half is guarded by
@@ -354,14 +256,8 @@ __device__ __forceinline__ void rng_time_loop(const PhiloxLane &lane, uint32_t s
     const uint32_t first = step0, last = step0 + static_cast<uint32_t>(nb) - 1u;
     for (uint32_t c = first >> 1; c <= (last >> 1); ++c) {
         tick(static_cast<int>(2u * c - first));
-#if SVMC_TRIP_BARRIER          // A/B hook (tools/r05/ab_pairing.sh): the waves of a block re-align every SVMC_TRIP_BARRIER-th trip
-        if ((c % SVMC_TRIP_BARRIER) == 0u) __builtin_amdgcn_s_barrier();
-#endif
         uint32_t r[4];
         philox_draw(lane, c, r);
-#if SVMC_PHILOX_FENCE          // A/B hook: nothing is scheduled across the end of the Philox rounds
-        __builtin_amdgcn_sched_barrier(0);
-#endif
         double z0, z1;
         if (2u * c >= first) {
             normals_from_words(r[0], r[1], tab, z0, z1);
@@ -381,74 +277,6 @@ __device__ __forceinline__ void rng_time_loop(const PhiloxLane &lane, uint32_t s
     rng_time_loop(lane, step0, nb, tab, step, [](int) {});
 }
 
-// rng_time_loop for launches of a few waves per SIMD (a calibration- or default-sized path set: 10^5 paths are 1.5 waves per
-// SIMD on this chip), where no other wave hides an LDS round trip: all eight table reads of a call are in flight before the
-// first cubic (draw_issue / draw_finish) instead of four read-wait-evaluate rounds.  The same words for the same (path,
-// step), the same operations on them: the same bits.  Costs 24 more live registers, which a full launch does not have.
-template <class Step>
-__device__ __forceinline__ void rng_time_loop_few_waves(const PhiloxLane &lane, uint32_t step0, int nb, const RngTables &tab,
-                                                        Step &&step)
-{
-    if (nb <= 0) return;
-    const uint32_t first = step0, last = step0 + static_cast<uint32_t>(nb) - 1u;
-    for (uint32_t c = first >> 1; c <= (last >> 1); ++c) {
-        uint32_t r[4];
-        philox_draw(lane, c, r);
-        DrawInFlight d;
-        double z[4];
-        draw_issue(r, tab, d);
-        draw_finish(d, z);
-        if (2u * c >= first) step(z[0], z[1]);
-        if (2u * c + 1u <= last) step(z[2], z[3]);
-    }
-}
-
-// rng_time_loop for launches of three to seven waves per SIMD (2^17 < paths < 2^20: the path counts the reference's own runs
-// use -- 10^5 by default, 4 x 10^5 in its paper).  There the batched draw of rng_time_loop_few_waves turns against itself: the
-// waves of a CU run the same code from the same start, so they all sit in the draw's LDS phase together (8 ds_read_b128 per
-// wave, ~100 LDS cycles each with the bank conflicts of random indices) and then all in the VALU phase together -- LDS time and
-// VALU time ADD (measured: 1250 cycles per step at three waves per SIMD, against 620 of issue and 670 of LDS).  Here every wave
-// overlaps the two BY ITSELF: the words, indices and table reads of call c + 1 are issued before the two steps of call c, its
-// cubics run after them (the draw does not depend on the state), so the LDS pipe works through a wave's reads while that
-// wave's own steps issue.  The last trip draws a call nobody uses rather than branching inside the trip (a branch splits the
-// scheduling region: logsv_chain_rng_sets_kernel measured it).  The edge halves of a slice that starts or ends on an odd step
-// are peeled.  Which (path, step) sees which word is rng_time_loop's rule, the operations on them are normal_icdf32's: the
-// same bits.  Costs ~40 live registers more than rng_time_loop (the eight table pieces in flight across two steps).
-template <class Step>
-__device__ __forceinline__ void rng_time_loop_ahead(const PhiloxLane &lane, uint32_t step0, int nb, const RngTables &tab,
-                                                    Step &&step)
-{
-    if (nb <= 0) return;
-    const uint32_t first = step0, last = step0 + static_cast<uint32_t>(nb) - 1u;
-    uint32_t c = first >> 1, r[4];
-    double a0, a1;
-    if (first & 1u) {
-        philox_draw(lane, c, r);
-        normals_from_words(r[2], r[3], tab, a0, a1);
-        step(a0, a1);
-        ++c;
-    }
-    const uint32_t c_end = (last + 1u) >> 1;               // the full calls are [c, c_end)
-    if (c < c_end) {
-        DrawInFlight d;
-        philox_draw(lane, c, r);
-        draw_issue(r, tab, d);
-        for (; c < c_end; ++c) {
-            double z[4];
-            draw_finish(d, z);
-            philox_draw(lane, c + 1u, r);
-            draw_issue(r, tab, d);
-            step(z[0], z[1]);
-            step(z[2], z[3]);
-        }
-    }
-    if (!(last & 1u)) {
-        philox_draw(lane, last >> 1, r);
-        normals_from_words(r[0], r[1], tab, a0, a1);
-        step(a0, a1);
-    }
-}
-
 // The draw of ONE time step's pair of normals in three pieces (prepare: word -> t and table offset; read: the four
 // ds_read_b128; finish: the two cubics), for the loops that keep one pair in flight under the step before it.  normal_icdf32's
 // operations on the same operands: the same bits.
@@ -456,18 +284,6 @@ struct PairInFlight {
     double t[2];
     IcdfPiece e0[2], e1[2];
 };
-#if SVMC_ICDF_MIXED
-__device__ __forceinline__ void pair_issue(uint32_t ra, uint32_t rb, const RngTables &tab, PairInFlight &d)
-{
-    d.t[0] = normal_icdf32_mixed(ra, tab.icdf);
-    d.t[1] = normal_icdf32_mixed(rb, tab.icdf);
-}
-__device__ __forceinline__ void pair_finish(const PairInFlight &d, double &z0, double &z1)
-{
-    z0 = d.t[0];
-    z1 = d.t[1];
-}
-#else
 __device__ __forceinline__ void pair_issue(uint32_t ra, uint32_t rb, const RngTables &tab, PairInFlight &d)
 {
     static_assert(SVMC_ICDF_RAW != 0, "the split draw is written for the raw form of the table");
@@ -477,15 +293,8 @@ __device__ __forceinline__ void pair_issue(uint32_t ra, uint32_t rb, const RngTa
         d.t[k] = icdf_lattice_point(w[k]);
         const uint32_t off = (double_hi(d.t[k]) >> (16 - SVMC_ICDF_M)) & ((static_cast<uint32_t>(SVMC_ICDF_SEGMENTS) - 1u) << 4);
         const char *base = reinterpret_cast<const char *>(tab.icdf) + off;
-#if defined(SVMC_PROBE) && (SVMC_PROBE & 2)          // measurement build: no table reads in the draw
-        asm volatile("" : : "v"(off));                 // the offset is still computed: the VALU stream is the product's
-        d.e0[k] = IcdfPiece{1e-10, 1e-10};
-        d.e1[k] = IcdfPiece{1e-20, 1e-30};
-        (void)base;
-#else
         d.e0[k] = *reinterpret_cast<const IcdfPiece *>(base);
         d.e1[k] = *reinterpret_cast<const IcdfPiece *>(base + 16 * SVMC_ICDF_SEGMENTS);
-#endif
     }
 }
 __device__ __forceinline__ void pair_finish(const PairInFlight &d, double &z0, double &z1)
@@ -502,15 +311,15 @@ __device__ __forceinline__ void pair_finish(const PairInFlight &d, double &z0, d
     z0 = z[0];
     z1 = z[1];
 }
-#endif
 
-// SVMC_PIPE_HOIST_KEYS (A/B hook, default 1): the few-waves loops below draw with the round keys hoisted out of the time loop
-#ifndef SVMC_PIPE_HOIST_KEYS
-#define SVMC_PIPE_HOIST_KEYS 1
-#endif
-// rng_time_loop with ONE PAIR ahead: the table reads of the next step's two normals are issued before this step runs and
-// their cubics evaluated after it -- half the registers of rng_time_loop_ahead (one pair in flight, not four normals), for
-// launches that still want five to seven waves per SIMD.  Same words, same operations: the same bits.
+// rng_time_loop with ONE PAIR ahead, for launches of a few waves per SIMD (up to seven; the reference's default 10^5 paths are
+// 1.5), where no other wave hides an LDS round trip: the table reads of the next step's two normals are issued before this step
+// runs and their cubics evaluated after it, so a wave overlaps its own draw with its own step.  Batching a call's eight reads
+// before its cubics instead puts the waves of a CU in a common LDS phase and then a common VALU phase -- LDS time and VALU time
+// add (1250 cycles per step at three waves per SIMD, against 620 of issue and 670 of LDS; the forms measured:
+// profiles/r06_mid_waves_sweep.json).  The last trip draws a call nobody uses rather than branching inside the trip (a branch
+// splits the scheduling region), and the round keys are hoisted out of the time loop (philox_draw<true>).  Same words, same
+// operations: the same bits.
 template <class Step>
 __device__ __forceinline__ void rng_time_loop_pair_ahead(const PhiloxLane &lane, uint32_t step0, int nb, const RngTables &tab,
                                                          Step &&step)
@@ -538,7 +347,7 @@ __device__ __forceinline__ void rng_time_loop_pair_ahead(const PhiloxLane &lane,
             __builtin_amdgcn_sched_barrier(0);
             step(z0, z1);
             pair_finish(d, z0, z1);
-            philox_draw<SVMC_PIPE_HOIST_KEYS != 0>(lane, c + 1u, r);   // the last trip draws a call nobody uses (no branch in the trip)
+            philox_draw<true>(lane, c + 1u, r);            // the last trip draws a call nobody uses (no branch in the trip)
             pair_issue(r[0], r[1], tab, d);
             __builtin_amdgcn_sched_barrier(0);
             step(z0, z1);
@@ -587,7 +396,7 @@ __device__ __forceinline__ void rng_time_loop_pipelined(const PhiloxLane &lane, 
             front(z0, z1);                                 // step 2c; its table read is now the youngest LDS operation
             __builtin_amdgcn_sched_barrier(0);
             pair_finish(d, z0, z1);                        // the normals of step 2c + 1
-            philox_draw<SVMC_PIPE_HOIST_KEYS != 0>(lane, c + 1u, r);   // the last trip draws a call nobody uses (no branch in the trip)
+            philox_draw<true>(lane, c + 1u, r);            // the last trip draws a call nobody uses (no branch in the trip)
             pair_issue(r[0], r[1], tab, d);                // ... of step 2c + 2: in flight under back() and the next front()
             mid();                                         // what of the step needs neither the table value nor another wave's time
             __builtin_amdgcn_sched_barrier(0);
@@ -617,14 +426,15 @@ __device__ __forceinline__ void rng_time_loop_pipelined(const PhiloxLane &lane, 
     rng_time_loop_pipelined(lane, step0, nb, tab, front, []() {}, back);
 }
 
-// the three forms of the generators' time loop, by launch size (generator_loop_for() in svmc_kernels.hip picks)
-enum GenLoop { GEN_LOOP_FULL = 0, GEN_LOOP_FEW = 1, GEN_LOOP_PAIR = 2, GEN_LOOP_AHEAD = 3, GEN_LOOP_PIPE = 4 };
+// the forms of the generators' time loop, by launch size (few_waves_launch() in svmc_kernels.hip picks): full launches run
+// rng_time_loop, the few-waves Heston generators rng_time_loop_pair_ahead, the few-waves LogSV ones rng_time_loop_pipelined.
+// The values are template arguments of the kernels, part of their symbol names: they stay as they are.
+enum GenLoop { GEN_LOOP_FULL = 0, GEN_LOOP_PAIR = 2, GEN_LOOP_PIPE = 4 };
 template <int LOOP, class Step>
 __device__ __forceinline__ void gen_time_loop(const PhiloxLane &lane, uint32_t step0, int nb, const RngTables &tab, Step &&step)
 {
-    if constexpr (LOOP == GEN_LOOP_FEW) rng_time_loop_few_waves(lane, step0, nb, tab, step);
-    else if constexpr (LOOP == GEN_LOOP_AHEAD) rng_time_loop_ahead(lane, step0, nb, tab, step);
-    else if constexpr (LOOP == GEN_LOOP_PAIR || LOOP == GEN_LOOP_PIPE) rng_time_loop_pair_ahead(lane, step0, nb, tab, step);
+    static_assert(LOOP == GEN_LOOP_FULL || LOOP == GEN_LOOP_PAIR, "the pipelined loop takes the step in halves");
+    if constexpr (LOOP == GEN_LOOP_PAIR) rng_time_loop_pair_ahead(lane, step0, nb, tab, step);
     else rng_time_loop(lane, step0, nb, tab, step);
 }
 
