@@ -593,7 +593,21 @@ SVMC_API int svmc_mgf_vanilla_slice(const double *phi, const double *log_mgf, si
  *                               params_host [n_sets][SVMC_HAWKESJD_PARAMS], a [n_sets][n_grid][3] complex, log_mgf
  *                               [n_sets][n_grid] complex.  Every set is checked before anything is launched; an invalid one
  *                               fails the whole call.  A grid point the integrator gives up on is NaN in its own set only.
- *                               Results are bit-identical to n_sets single calls. */
+ *                               Results are bit-identical to n_sets single calls.
+ *   svmc_hawkesjd_risk_forwards_batch  hawkesjd_forwards_under_risk_kernel (:487-515) for n_sets parameter sets, each with its
+ *                               own risk-premia gamma (gammas_host [n_sets]): per expiry the coefficient ODEs from zero over the
+ *                               whole [0, ttm] at the real points phi = -gamma and -gamma - 1 (psi = 0); normalizer =
+ *                               1 / exp(Re log E(-gamma)), gamma_forward = forward exp(Re log E(-gamma - 1)) normalizer.
+ *                               normalizers, gamma_forwards: device [n_ttms][n_sets] (expiry-major).  ttms must be positive.
+ *                               An ODE the integrator gives up on is NaN in its own set and expiry only.
+ *   svmc_mgf_gamma_slice_batch  slice_pricer_with_mgf_grid_with_gamma (utils/mgf_pricer.py:273-321) of one expiry for n_sets
+ *                               sets (phi, log_mgf [n_sets][n_grid] complex, each set its own grid): legacy Simpson weights,
+ *                               the real shortcut (dp/pi)/(p^2 + 1/4) where shortcut_host[s] != 0, else the complex weight
+ *                               -(dp/pi)/((phi + gamma + 1)(phi + gamma)); cap = nansum Re[w exp(-x phi + log E)], x =
+ *                               log(forward / K); type code 0 ('C') gamma_forward - normalizer K^(1+gamma) cap, 1 ('P')
+ *                               K - normalizer K^(1+gamma) cap, others SVMC_ERR_UNKNOWN_PAYOFF.  normalizers / gamma_forwards
+ *                               are svmc_hawkesjd_risk_forwards_batch's device output, read at row `expiry`; prices: device
+ *                               [n_sets][n_strikes], undiscounted. */
 #define SVMC_HAWKESJD_PARAMS 16
 SVMC_API int svmc_hawkesjd_terminal_rng(double *x, double *lambda_p, double *lambda_m, size_t n_path, int nb_steps,
                                         double dt, const double *params_host, uint64_t seed, uint32_t call_id,
@@ -609,6 +623,14 @@ SVMC_API int svmc_hawkesjd_mgf_grid(const double *phi, const double *psi, size_t
 SVMC_API int svmc_hawkesjd_mgf_grid_batch(const double *phi, const double *psi, size_t n_grid, int n_sets, double ttm,
                                           const double *params_host, double *a, double *log_mgf, double rtol, double atol,
                                           svmc_stream_t stream);
+SVMC_API int svmc_hawkesjd_risk_forwards_batch(const double *params_host, const double *gammas_host, int n_sets,
+                                               const double *ttms_host, const double *forwards_host, size_t n_ttms,
+                                               double *normalizers, double *gamma_forwards, double rtol, double atol,
+                                               svmc_stream_t stream);
+SVMC_API int svmc_mgf_gamma_slice_batch(const double *phi, const double *log_mgf, size_t n_grid, int n_sets,
+                                        const double *gammas_host, const int *shortcut_host, const double *normalizers,
+                                        const double *gamma_forwards, int expiry, double forward, const double *strikes_host,
+                                        const int *type_codes_host, size_t n_strikes, double *prices, svmc_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -7,7 +7,9 @@ Module layout and public names mirror the reference package (`stochvolmodels`) f
     stochvolmodels_amd.pricers.heston_pricer  HestonPricer, HestonParams, heston_mc_chain_pricer,
                                               simulate_heston_x_vol_terminal
     stochvolmodels_amd.pricers.hawkes_jd_pricer  HawkesJDPricer, HawkesJDParams, hawkesjd_mc_chain_pricer,
-                                              hawkesjd_chain_pricer(_batch), simulate_hawkesjd_terminal
+                                              hawkesjd_chain_pricer(_batch), simulate_hawkesjd_terminal,
+                                              hawkesjd_forwards_under_risk_kernel,
+                                              hawkesjd_chain_pricer_with_risk_premia(_batch)
     stochvolmodels_amd.utils.mc_payoffs       compute_mc_vars_payoff
     stochvolmodels_amd.utils.funcs            set_time_grid, set_seed, timer
     stochvolmodels_amd.utils.config           OptionType, VariableType

@@ -207,7 +207,7 @@ class AnalyticGrid(_Pooled):
 class AnalyticGridBatch(_Pooled):
     """the transform grids of SEVERAL LogSV or Hawkes parameter sets resident on the device, advanced expiry by expiry in one
     launch per expiry (svmc_logsv_mgf_grid_batch, svmc_hawkesjd_mgf_grid_batch) and inverted in one launch per expiry
-    (svmc_mgf_vanilla_slice_batch):
+    (svmc_mgf_vanilla_slice_batch, or svmc_mgf_gamma_slice_batch under the Hawkes risk-premia kernel):
     config C5's five sets, or the bumped parameter vectors of a finite-difference gradient, side by side.  Bit-identical
     to one AnalyticGrid per set."""
 
@@ -243,6 +243,8 @@ class AnalyticGridBatch(_Pooled):
         self.log_mgf = DeviceBuffer(2 * self.n_sets * self.n)
         _lib.check(self.lib.svmc_memset(self.a.ptr, 0, self.a.nbytes, None))
         self._capped: Optional[DeviceBuffer] = None
+        self._risk: Optional[DeviceBuffer] = None            # normalizers then gamma forwards, [n_ttms][n_sets] each
+        self._risk_ttms = 0
 
     def logsv_advance(self, ttm: float, params_rows: np.ndarray, is_spot_measure: bool, expansion_order: int,
                       rtol: Optional[float] = None, atol: Optional[float] = None) -> None:
@@ -264,6 +266,55 @@ class AnalyticGridBatch(_Pooled):
                                                          rows.ctypes.data_as(C.POINTER(C.c_double)), self.a.ptr,
                                                          self.log_mgf.ptr, ODE_RTOL if rtol is None else float(rtol),
                                                          ODE_ATOL if atol is None else float(atol), None))
+
+    def risk_forwards(self, params_rows: np.ndarray, gammas: np.ndarray, ttms: np.ndarray, forwards: np.ndarray,
+                      rtol: Optional[float] = None, atol: Optional[float] = None) -> None:
+        """queue the risk-premia normalizers and gamma forwards of every set and expiry (svmc_hawkesjd_risk_forwards_batch)
+        into the batch's device buffer, where queue_gamma_slice reads them; download_risk_results brings them back"""
+        rows = np.ascontiguousarray(params_rows, dtype=np.float64)
+        gammas = np.ascontiguousarray(gammas, dtype=np.float64)
+        ttms = np.ascontiguousarray(ttms, dtype=np.float64)
+        forwards = np.ascontiguousarray(forwards, dtype=np.float64)
+        assert rows.shape == (self.n_sets, 16) and gammas.shape == (self.n_sets,) and ttms.shape == forwards.shape
+        n = max(int(ttms.size), 1) * self.n_sets
+        if self._risk is None or self._risk.n < 2 * n:
+            if self._risk is not None:
+                self._risk.free()
+            self._risk = DeviceBuffer(2 * n)
+        self._risk_ttms = int(ttms.size)
+        pf = C.POINTER(C.c_double)
+        _lib.check(self.lib.svmc_hawkesjd_risk_forwards_batch(rows.ctypes.data_as(pf), gammas.ctypes.data_as(pf), self.n_sets,
+                                                              ttms.ctypes.data_as(pf), forwards.ctypes.data_as(pf), ttms.size,
+                                                              self._risk.ptr, self._risk.offset(n),
+                                                              ODE_RTOL if rtol is None else float(rtol),
+                                                              ODE_ATOL if atol is None else float(atol), None))
+
+    def queue_gamma_slice(self, gammas: np.ndarray, shortcut: np.ndarray, expiry: int, forward: float, strikes: np.ndarray,
+                          type_codes: np.ndarray, offset: int) -> None:
+        """the [n_sets][n_strikes] undiscounted risk-premia prices of expiry `expiry` from the current log-MGF, queued into
+        the result buffer at `offset` (svmc_mgf_gamma_slice_batch; type codes 0 'C', 1 'P')"""
+        strikes = np.ascontiguousarray(strikes, dtype=np.float64)
+        codes = np.ascontiguousarray(type_codes, dtype=np.int32)
+        gammas = np.ascontiguousarray(gammas, dtype=np.float64)
+        short = np.ascontiguousarray(shortcut, dtype=np.int32)
+        assert 0 <= expiry < self._risk_ttms and codes.shape == strikes.shape
+        n = self._risk_ttms * self.n_sets
+        pf, pi = C.POINTER(C.c_double), C.POINTER(C.c_int)
+        _lib.check(self.lib.svmc_mgf_gamma_slice_batch(self.phi.ptr, self.log_mgf.ptr, self.n, self.n_sets,
+                                                       gammas.ctypes.data_as(pf), short.ctypes.data_as(pi), self._risk.ptr,
+                                                       self._risk.offset(n), int(expiry), float(forward),
+                                                       strikes.ctypes.data_as(pf), codes.ctypes.data_as(pi), strikes.size,
+                                                       self._capped.offset(offset), None))
+
+    def download_risk_results(self, n_doubles: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(queued prices, normalizers [n_ttms][n_sets], gamma forwards [n_ttms][n_sets]) in one wait; last_given_up as in
+        download_results"""
+        n = self._risk_ttms * self.n_sets
+        risk = np.empty(2 * n)
+        if n:
+            _lib.check(self.lib.svmc_memcpy_d2h(risk.ctypes.data, self._risk.ptr, risk.nbytes, None))
+        out = self.download_results(n_doubles)
+        return out, risk[:n].reshape(self._risk_ttms, self.n_sets), risk[n:].reshape(self._risk_ttms, self.n_sets)
 
     def capped_sums(self, forward: float, strikes: np.ndarray) -> np.ndarray:
         """-> [n_sets][n_strikes]"""
@@ -303,9 +354,38 @@ class AnalyticGridBatch(_Pooled):
         return out
 
     def close(self) -> None:
-        for b in (self.phi, self.psi, self.a, self.log_mgf, self._capped):
+        for b in (self.phi, self.psi, self.a, self.log_mgf, self._capped, self._risk):
             if b is not None:
                 b.free()
+
+
+def gamma_slice_prices(phi: np.ndarray, log_mgf: np.ndarray, gamma: float, shortcut: bool, normalizer: float,
+                       gamma_forward: float, forward: float, strikes: np.ndarray, type_codes: np.ndarray) -> np.ndarray:
+    """one slice under the risk-premia kernel from a given log-MGF (svmc_mgf_gamma_slice_batch at one set): uploads the grid,
+    the log-MGF and the slice's normalizer / gamma forward, returns the undiscounted prices"""
+    lib = _lib.load()
+    phi = np.ascontiguousarray(phi, dtype=np.complex128)
+    log_mgf = np.ascontiguousarray(log_mgf, dtype=np.complex128)
+    strikes = np.ascontiguousarray(strikes, dtype=np.float64)
+    codes = np.ascontiguousarray(type_codes, dtype=np.int32)
+    nf = np.array([normalizer, gamma_forward], dtype=np.float64)
+    gammas, short = np.array([gamma], dtype=np.float64), np.array([int(bool(shortcut))], dtype=np.int32)
+    bufs = [DeviceBuffer(2 * phi.size), DeviceBuffer(2 * log_mgf.size), DeviceBuffer(2), DeviceBuffer(max(strikes.size, 1))]
+    try:
+        for buf, z in zip(bufs[:3], (phi, log_mgf, nf)):
+            _lib.check(lib.svmc_memcpy_h2d(buf.ptr, z.ctypes.data, z.nbytes, None))
+        pf, pi = C.POINTER(C.c_double), C.POINTER(C.c_int)
+        _lib.check(lib.svmc_mgf_gamma_slice_batch(bufs[0].ptr, bufs[1].ptr, phi.size, 1, gammas.ctypes.data_as(pf),
+                                                  short.ctypes.data_as(pi), bufs[2].ptr, bufs[2].offset(1), 0, float(forward),
+                                                  strikes.ctypes.data_as(pf), codes.ctypes.data_as(pi), strikes.size,
+                                                  bufs[3].ptr, None))
+        out = np.empty(strikes.size)
+        _lib.check(lib.svmc_memcpy_d2h(out.ctypes.data, bufs[3].ptr, out.nbytes, None))
+        _lib.check(lib.svmc_stream_synchronize(None))
+        return out
+    finally:
+        for b in bufs:
+            b.free()
 
 
 def vanilla_prices_from_capped(capped: np.ndarray, forward: float, strikes: np.ndarray, optiontypes: Sequence,

@@ -9,6 +9,10 @@
 //                              one set, or the base point and bumped vectors of a calibration's finite-difference gradient):
 //                              the three complex Riccati ODEs of solve_ode_for_a (:582-640) with the DOP853 pair of
 //                              svmc_dop853.h and per-point step control; log E = a0 + a1 lp + a2 lm
+//   hawkes_risk_forwards_kernel  the risk-premia kernel's normalizers and gamma forwards (:487-515): one lane pair per expiry,
+//                              one wave per set, each lane the same ODEs from zero over the whole ttm at a real phi
+//   mgf_gamma_slice_kernel     one block per (strike, set): the slice inversion under the risk-premia kernel
+//                              (utils/mgf_pricer.py:273-321), the price finished on the device from the forwards kernel's output
 //
 // Randoms (svmc_rng.h, streams 6 and 7): step s of path p is ONE Philox call of stream 6 at counter index s (the chain-global
 // step): word 0 -> the N(0,1) of the diffusion (normal_icdf32), words 1 and 2 -> u_p, u_m = (r + 1/2) 2^-32, word 3 unused.
@@ -339,6 +343,105 @@ __global__ __launch_bounds__(HK_AB) void hawkes_mgf_grid_batch_kernel(const cd *
     hawkes_grid_point(phi + off, psi + off, j, ttm, set.o, set.lambda_p, set.lambda_m, a + 3 * off, log_mgf + off, rtol, atol);
 }
 
+// ---- the risk-premia (Esscher-type) kernel: hawkesjd_forwards_under_risk_kernel (:487-515) and
+//      slice_pricer_with_mgf_grid_with_gamma (utils/mgf_pricer.py:273-321) ----------------------------------------------------
+constexpr int HK_RISK_MAX_TTMS = HK_AB / 2;    // expiries per forwards launch: one lane pair each, one wave per set
+
+struct HawkesRiskTtms {
+    double ttm[HK_RISK_MAX_TTMS], forward[HK_RISK_MAX_TTMS];
+    double gamma[HK_MAX_SETS];
+    int m;                                     // expiries in this launch
+};
+
+// One wave per set (blockIdx.y), one lane pair per expiry: lane 2e + k integrates the coefficient ODEs from zero over the WHOLE
+// [0, ttm_e] (no chaining across expiries, :497-507) at the real point phi = -gamma - k, psi = 0.  The even lane of the pair
+// forms normalizer = 1 / exp(Re log E(-gamma)) and gamma_forward = forward exp(Re log E(-gamma - 1)) normalizer (:508-511).
+// Latency-bound and tiny: the pair's two integrations diverge and are left to.  Outputs are [expiry][set] (ld = n_sets).
+__global__ __launch_bounds__(HK_AB) void hawkes_risk_forwards_kernel(HawkesOdeBatch sets, HawkesRiskTtms tt, int n_sets,
+                                                                     double *__restrict__ normalizers,
+                                                                     double *__restrict__ gamma_forwards, double rtol,
+                                                                     double atol)
+{
+    const int lane = threadIdx.x;
+    const int e = lane >> 1, k = lane & 1;
+    const HawkesOdeSet &set = sets.s[blockIdx.y];
+    const double gamma = tt.gamma[blockIdx.y];
+    double re = 0.0;
+    if (e < tt.m) {
+        const cd ph = C(-gamma - static_cast<double>(k));                     // phi_grid = [-gamma], phi_grid - 1.0
+        const cd h0 = set.o.sigma2 * (0.5 * ((ph + 1.0) * ph));              // :623 with psi = 0
+        cd y[3] = {C(0.0), C(0.0), C(0.0)};
+        hawkes_dop853(set.o, ph, h0, tt.ttm[e], y, rtol, atol);
+        re = ((y[0] + set.lambda_p * y[1]) + set.lambda_m * y[2]).re;        // :545
+    }
+    const double re1 = __shfl_xor(re, 1, 64);
+    if (e < tt.m && k == 0) {
+        const double normalizer = 1.0 / exp(re);
+        const size_t at = static_cast<size_t>(e) * n_sets + blockIdx.y;
+        normalizers[at] = normalizer;
+        gamma_forwards[at] = (tt.forward[e] * exp(re1)) * normalizer;
+    }
+}
+
+struct GammaSliceArgs {
+    double x[32];                              // log(forward / strike)
+    double strike[32];
+    int type[32];                              // 0 'C', 1 'P'
+    double gamma[HK_MAX_SETS];
+    int shortcut[HK_MAX_SETS];                 // 1: every |Re phi - (0.5 + gamma)| < 1e-10 (:296), decided on the host
+    int k;
+};
+
+// One block per (strike, set), as mgf_vanilla_slice_kernel: the legacy Simpson dp, then the payoff weight of :296-302 -- the real
+// shortcut (dp / pi) / (p^2 + 1/4) or the complex -(dp / pi) / ((phi + gamma + 1)(phi + gamma)) -- and
+// nansum Re[w exp(-x phi + log E)] (NaN terms dropped, inf kept).  Thread 0 finishes the price from this expiry's normalizer and
+// gamma forward (hawkes_risk_forwards_kernel's output, [expiry][set]): 'C' gamma_forward - normalizer K^(1 + gamma) cap,
+// 'P' K - normalizer K^(1 + gamma) cap (:313-317).
+__global__ __launch_bounds__(256) void mgf_gamma_slice_kernel(const cd *__restrict__ phi, const cd *__restrict__ log_mgf, int n_grid,
+                                                              GammaSliceArgs sa, const double *__restrict__ normalizers,
+                                                              const double *__restrict__ gamma_forwards, size_t nf_at,
+                                                              double *__restrict__ prices, int prices_ld)
+{
+    __shared__ double lds[4];
+    const double PI = 3.14159265358979323846;
+    const int s = blockIdx.y;
+    phi += static_cast<size_t>(s) * n_grid;
+    log_mgf += static_cast<size_t>(s) * n_grid;
+    const double x = sa.x[blockIdx.x];
+    const double gamma = sa.gamma[s];
+    const bool shortcut = sa.shortcut[s] != 0;
+    const double h = phi[1].im - phi[0].im;
+    double acc = 0.0;
+    for (int j = threadIdx.x; j < n_grid; j += 256) {
+        double w = 2.0;
+        if (j == 0 || j == n_grid - 1) w = 1.0;
+        if (j & 1) w = 4.0;
+        const cd ph = phi[j];
+        const double dp_pi = ((h / 3.0) * w) / PI;
+        cd pw;
+        if (shortcut) {
+            pw = C(dp_pi / (ph.im * ph.im + 0.25));
+        } else {
+            const cd pg = ph + gamma;
+            pw = C(-dp_pi) / ((pg + 1.0) * pg);
+        }
+        const cd e = cexp_(log_mgf[j] - x * ph);
+        const double term = pw.re * e.re - pw.im * e.im;
+        if (term == term) acc += term;                                                          // nansum
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double cap = ((lds[0] + lds[1]) + lds[2]) + lds[3];
+        const double strike = sa.strike[blockIdx.x];
+        const double nk = normalizers[nf_at + s] * pow(strike, 1.0 + gamma);
+        prices[static_cast<size_t>(s) * prices_ld + blockIdx.x] =
+            (sa.type[blockIdx.x] == 0 ? gamma_forwards[nf_at + s] : strike) - nk * cap;
+    }
+}
+
 }  // namespace
 
 // the chain's stepping (svmc_chain.hip's svmc_hawkesjd_chain_price): every expiry in one launch per 16, the state starting at
@@ -429,6 +532,94 @@ int svmc_hawkesjd_mgf_grid_batch(const double *phi, const double *psi, size_t n_
                            dim3(HK_AB), 0, as_stream(stream), reinterpret_cast<const cd *>(phi) + off,
                            reinterpret_cast<const cd *>(psi) + off, n_grid, ttm, sets, reinterpret_cast<cd *>(a) + 3 * off,
                            reinterpret_cast<cd *>(log_mgf) + off, rtol, atol);
+    }
+    return check_launch(fn);
+}
+
+int svmc_hawkesjd_risk_forwards_batch(const double *params_host, const double *gammas_host, int n_sets, const double *ttms_host,
+                                      const double *forwards_host, size_t n_ttms, double *normalizers, double *gamma_forwards,
+                                      double rtol, double atol, svmc_stream_t stream)
+{
+    const char *fn = "svmc_hawkesjd_risk_forwards_batch";
+    SVMC_REQUIRE(params_host && gammas_host && normalizers && gamma_forwards, std::string(fn) + ": null pointer");
+    SVMC_REQUIRE(n_ttms == 0 || (ttms_host && forwards_host), std::string(fn) + ": null ttms or forwards");
+    SVMC_REQUIRE(n_sets >= 1, std::string(fn) + ": n_sets < 1");
+    SVMC_REQUIRE(rtol > 0.0 && atol > 0.0, std::string(fn) + ": rtol, atol must be positive");
+    for (int s = 0; s < n_sets; ++s) {                         // every set and expiry before anything is launched
+        if (int rc = check_params((std::string(fn) + " set " + std::to_string(s)).c_str(),
+                                  params_host + static_cast<size_t>(SVMC_HAWKESJD_PARAMS) * s))
+            return rc;
+        SVMC_REQUIRE(std::isfinite(gammas_host[s]), std::string(fn) + ": non-finite gamma");
+    }
+    for (size_t e = 0; e < n_ttms; ++e) {
+        SVMC_REQUIRE(ttms_host[e] > 0.0 && std::isfinite(ttms_host[e]), std::string(fn) + ": ttm must be positive and finite");
+        SVMC_REQUIRE(std::isfinite(forwards_host[e]), std::string(fn) + ": non-finite forward");
+    }
+    for (int s0 = 0; s0 < n_sets; s0 += HK_MAX_SETS) {
+        const int m = (n_sets - s0 < HK_MAX_SETS) ? (n_sets - s0) : HK_MAX_SETS;
+        HawkesOdeBatch sets;
+        HawkesRiskTtms tt;
+        for (int i = 0; i < HK_MAX_SETS; ++i) {                // unused slots repeat the first set: never read
+            const int si = s0 + (i < m ? i : 0);
+            const double *p = params_host + static_cast<size_t>(SVMC_HAWKESJD_PARAMS) * si;
+            sets.s[i] = HawkesOdeSet{make_hawkes_ode(p), p[P_LAMBDA_P], p[P_LAMBDA_M]};
+            tt.gamma[i] = gammas_host[si];
+        }
+        for (size_t e0 = 0; e0 < n_ttms; e0 += HK_RISK_MAX_TTMS) {
+            tt.m = static_cast<int>((n_ttms - e0 < HK_RISK_MAX_TTMS) ? (n_ttms - e0) : HK_RISK_MAX_TTMS);
+            for (int e = 0; e < HK_RISK_MAX_TTMS; ++e) {
+                tt.ttm[e] = (e < tt.m) ? ttms_host[e0 + e] : 1.0;
+                tt.forward[e] = (e < tt.m) ? forwards_host[e0 + e] : 1.0;
+            }
+            const size_t at = e0 * static_cast<size_t>(n_sets) + static_cast<size_t>(s0);
+            hipLaunchKernelGGL(hawkes_risk_forwards_kernel, dim3(1, static_cast<unsigned>(m)), dim3(HK_AB), 0, as_stream(stream),
+                               sets, tt, n_sets, normalizers + at, gamma_forwards + at, rtol, atol);
+        }
+    }
+    return check_launch(fn);
+}
+
+int svmc_mgf_gamma_slice_batch(const double *phi, const double *log_mgf, size_t n_grid, int n_sets, const double *gammas_host,
+                               const int *shortcut_host, const double *normalizers, const double *gamma_forwards, int expiry,
+                               double forward, const double *strikes_host, const int *type_codes_host, size_t n_strikes,
+                               double *prices, svmc_stream_t stream)
+{
+    const char *fn = "svmc_mgf_gamma_slice_batch";
+    SVMC_REQUIRE(phi && log_mgf && gammas_host && shortcut_host && normalizers && gamma_forwards && prices,
+                 std::string(fn) + ": null pointer");
+    SVMC_REQUIRE(n_strikes == 0 || (strikes_host && type_codes_host), std::string(fn) + ": null strikes or types");
+    SVMC_REQUIRE(n_grid >= 3 && n_grid < (1u << 30), std::string(fn) + ": grid too short or too long");
+    SVMC_REQUIRE(n_sets >= 1 && n_sets <= 65535, std::string(fn) + ": n_sets out of range");
+    SVMC_REQUIRE(expiry >= 0, std::string(fn) + ": negative expiry");
+    SVMC_REQUIRE(forward > 0.0 && std::isfinite(forward), std::string(fn) + ": forward must be positive and finite");
+    for (int s = 0; s < n_sets; ++s)
+        SVMC_REQUIRE(std::isfinite(gammas_host[s]), std::string(fn) + ": non-finite gamma");
+    for (size_t k = 0; k < n_strikes; ++k) {
+        SVMC_REQUIRE(strikes_host[k] > 0.0 && std::isfinite(strikes_host[k]), std::string(fn) + ": strikes must be positive");
+        if (type_codes_host[k] != 0 && type_codes_host[k] != 1)   // :313-319: 'C' and 'P' only
+            return fail(SVMC_ERR_UNKNOWN_PAYOFF, std::string(fn) + ": option type must be 'C' (0) or 'P' (1)");
+    }
+    const size_t nf_at = static_cast<size_t>(expiry) * static_cast<size_t>(n_sets);
+    for (int s0 = 0; s0 < n_sets; s0 += HK_MAX_SETS) {
+        const int m = (n_sets - s0 < HK_MAX_SETS) ? (n_sets - s0) : HK_MAX_SETS;
+        for (size_t k0 = 0; k0 < n_strikes; k0 += 32) {
+            GammaSliceArgs sa;
+            sa.k = static_cast<int>((n_strikes - k0 < 32) ? (n_strikes - k0) : 32);
+            for (int k = 0; k < 32; ++k) {
+                sa.x[k] = (k < sa.k) ? log(forward / strikes_host[k0 + k]) : 0.0;                // :304
+                sa.strike[k] = (k < sa.k) ? strikes_host[k0 + k] : 1.0;
+                sa.type[k] = (k < sa.k) ? type_codes_host[k0 + k] : 0;
+            }
+            for (int i = 0; i < HK_MAX_SETS; ++i) {
+                sa.gamma[i] = gammas_host[s0 + (i < m ? i : 0)];
+                sa.shortcut[i] = shortcut_host[s0 + (i < m ? i : 0)] != 0;
+            }
+            const size_t off = static_cast<size_t>(s0) * n_grid;
+            hipLaunchKernelGGL(mgf_gamma_slice_kernel, dim3(sa.k, static_cast<unsigned>(m)), dim3(256), 0, as_stream(stream),
+                               reinterpret_cast<const cd *>(phi) + off, reinterpret_cast<const cd *>(log_mgf) + off,
+                               static_cast<int>(n_grid), sa, normalizers + s0, gamma_forwards + s0, nf_at,
+                               prices + static_cast<size_t>(s0) * n_strikes + k0, static_cast<int>(n_strikes));
+        }
     }
     return check_launch(fn);
 }

@@ -14,14 +14,24 @@ Calibration (HawkesJDPricer.calibrate_model_params_to_chain; :230-302): SLSQP on
 parameters, each objective evaluation one Fourier chain pricing on the device.  The forward-difference gradient SLSQP needs at
 an iterate (the base point and 8 bumped vectors) is priced in one batch of launches per expiry (hawkesjd_chain_pricer_batch,
 csrc/svmc_hawkes.hip's hawkes_mgf_grid_batch_kernel), bit-identical to one pricing per vector.
+Risk-premia (Esscher-type) kernel (hawkesjd_forwards_under_risk_kernel, hawkesjd_chain_pricer_with_risk_premia,
+HawkesJDPricer.calibrate_risk_premia_gamma_to_chain; :304-357, :420-515): the normalizers and gamma forwards of every expiry in
+one launch (hawkes_risk_forwards_kernel: the coefficient ODEs from zero over each whole ttm at phi = -gamma and -gamma - 1),
+the chained coefficient ODEs on the grid of real part -0.5 - gamma, and per expiry one inversion launch that finishes the
+prices on the device (mgf_gamma_slice_kernel); hawkesjd_chain_pricer_with_risk_premia_batch prices several (sigma, gamma) sets
+side by side for the calibration's gradient.
 The reference's quirks are kept: `risk_premia_gamma` is accepted and unused by the Monte Carlo, `is_spot_measure` is ignored
-by it, and a variable_type other than LOG_RETURN raises (the reference would price the log-return as a variance).
-Out of scope: the risk-premia pricer (price_chain raises NotImplementedError when params.risk_premia_gamma is set) and so
-calibrate_risk_premia_gamma_to_chain, which prices through it.
+by it, and a variable_type other than LOG_RETURN raises (the reference would price the log-return as a variance).  Under the
+risk-premia kernel: the forwards follow zip(ttms, forwards) (entries beyond the shorter stay 1.0), discfactors are ignored
+(the prices are undiscounted), and the calibration mutates and returns params0.
+Not switched (yet): price_chain, price_chain_batch and compute_chain_prices_with_vols still raise NotImplementedError when
+params.risk_premia_gamma is set, where the reference dispatches to the risk-premia pricer; the calibration calls that pricer
+directly.  Switching that dispatch changes existing behaviour and is a separate change.
 """
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 from dataclasses import asdict, dataclass
 from typing import Any, Dict, List, Optional, Sequence, Tuple
 
@@ -31,7 +41,7 @@ from .. import _lib
 from .. import dist as svdist
 from ..analytic import ODE_ATOL, ODE_RTOL, AnalyticGrid, AnalyticGridBatch, vanilla_prices_from_capped
 from ..data.option_chain import OptionChain
-from ..engine import get_engine, marshalled_chain, option_type_codes
+from ..engine import DeviceBuffer, get_engine, marshalled_chain, option_type_codes
 from ..mc_chain import variable_type_code
 from ..utils import mgf_pricer as mgfp
 from ..utils.calibration import ImpliedVolObjective, chain_calibration_weights
@@ -128,9 +138,12 @@ class HawkesJDPricer(ModelPricer):
 
     def price_chain(self, option_chain: OptionChain, params: HawkesJDParams, is_spot_measure: bool = True, **kwargs
                     ) -> List[np.ndarray]:
-        """analytic chain prices (reference :125-153)"""
+        """analytic chain prices (reference :125-153).  With params.risk_premia_gamma set this still raises rather than
+        dispatch to hawkesjd_chain_pricer_with_risk_premia as the reference does (a separate, behaviour-changing step): call
+        that pricer directly"""
         if params.risk_premia_gamma is not None:
-            raise NotImplementedError("the risk-premia Hawkes pricer (hawkesjd_chain_pricer_with_risk_premia) is not implemented")
+            raise NotImplementedError("price_chain does not dispatch to the risk-premia pricer: call "
+                                      "hawkesjd_chain_pricer_with_risk_premia(_batch) directly")
         return hawkesjd_chain_pricer(model_params=params, ttms=option_chain.ttms, forwards=option_chain.forwards,
                                      discfactors=option_chain.discfactors, strikes_ttms=option_chain.strikes_ttms,
                                      optiontypes_ttms=option_chain.optiontypes_ttms, is_spot_measure=is_spot_measure, **kwargs)
@@ -148,7 +161,8 @@ class HawkesJDPricer(ModelPricer):
                           **kwargs) -> List[List[np.ndarray]]:
         """price_chain for several parameter sets in one batch of launches (hawkesjd_chain_pricer_batch)"""
         if any(p.risk_premia_gamma is not None for p in params_list):
-            raise NotImplementedError("the risk-premia Hawkes pricer (hawkesjd_chain_pricer_with_risk_premia) is not implemented")
+            raise NotImplementedError("price_chain does not dispatch to the risk-premia pricer: call "
+                                      "hawkesjd_chain_pricer_with_risk_premia(_batch) directly")
         return hawkesjd_chain_pricer_batch(params_list=params_list, ttms=option_chain.ttms, forwards=option_chain.forwards,
                                            discfactors=option_chain.discfactors, strikes_ttms=option_chain.strikes_ttms,
                                            optiontypes_ttms=option_chain.optiontypes_ttms, is_spot_measure=is_spot_measure,
@@ -201,6 +215,81 @@ class HawkesJDPricer(ModelPricer):
                                      objective=objective(res.x), success=bool(res.success), message=str(res.message))
         return unpack_calibration_vector(res.x, params0)
 
+    def risk_premia_calibration_objective(self, option_chain: OptionChain, params0: HawkesJDParams,
+                                          is_vega_weighted: bool = True, is_unit_ttm_vega: bool = False,
+                                          print_iter: bool = True, **kwargs) -> ImpliedVolObjective:
+        """the objective of calibrate_risk_premia_gamma_to_chain as a callable of the optimizer's (sigma, gamma / 8)
+        (reference :336-342): every call unpacks into params0 IN PLACE, as there; with its batched gradient at SLSQP's step
+        0.025 unless batched_gradient=False; ode_rtol= / ode_atol= as in hawkesjd_chain_pricer"""
+        if params0.risk_premia_gamma is None:
+            raise ValueError("params0.risk_premia_gamma must be set: it is the start value of the fit")
+        _, market_vols_ttms = option_chain.get_chain_data_as_xy()
+        market_vols = to_flat_np_array(market_vols_ttms)
+        weights = risk_premia_calibration_weights(option_chain, market_vols, is_vega_weighted, is_unit_ttm_vega)
+        tol = {k: kwargs[k] for k in ("ode_rtol", "ode_atol") if k in kwargs}
+        chain = dict(ttms=option_chain.ttms, forwards=option_chain.forwards, discfactors=option_chain.discfactors,
+                     strikes_ttms=option_chain.strikes_ttms, optiontypes_ttms=option_chain.optiontypes_ttms,
+                     return_forwards=True, **tol)
+
+        def unpack(pars) -> HawkesJDParams:
+            params = unpack_risk_premia_vector(pars, params0)
+            if print_iter:
+                print(f"unpack_pars: sigma={pars[0]}, gamma={params.risk_premia_gamma}")
+            return params
+
+        def ivols(prices_ttms, gamma_forwards):             # inverted against the gamma forwards (:173-191)
+            # an expiry whose forward ODE the integrator gave up on (NaN) has NaN prices and NaN vols, dropped by the nansum
+            ok = np.isfinite(gamma_forwards) & (gamma_forwards > 0.0)
+            vols = option_chain.compute_model_ivols_from_chain_data(model_prices=prices_ttms,
+                                                                    forwards=np.where(ok, gamma_forwards, 1.0))
+            return [v if good else np.full_like(v, np.nan) for v, good in zip(vols, ok)]
+
+        def model_vols(pars):
+            prices, (_, gamma_forwards) = hawkesjd_chain_pricer_with_risk_premia(model_params=unpack(pars), **chain)
+            return ivols(prices, gamma_forwards)
+
+        def model_vols_batch(pars_list):
+            # each vector priced with its own copy of params0 as unpack leaves it; params0 ends at the last vector
+            params_list = [dataclasses.replace(unpack(pars)) for pars in pars_list]
+            prices, forwards = hawkesjd_chain_pricer_with_risk_premia_batch(params_list=params_list, **chain)
+            return [ivols(pr, gf) for pr, (_, gf) in zip(prices, forwards)]
+
+        batched = bool(kwargs.get("batched_gradient", True))
+        return ImpliedVolObjective(model_vols, market_vols, weights, model_vols_batch=model_vols_batch if batched else None,
+                                   bounds=RISK_PREMIA_BOUNDS, fd_step=RISK_PREMIA_FD_STEP)
+
+    @timer
+    def calibrate_risk_premia_gamma_to_chain(self, option_chain: OptionChain, params0: HawkesJDParams,
+                                             is_vega_weighted: bool = True, is_unit_ttm_vega: bool = False, maxiter: int = 100,
+                                             print_iter: bool = True, **kwargs) -> HawkesJDParams:
+        """fit sigma and risk_premia_gamma to the chain's mid implied vols with every other parameter from params0 (reference
+        :304-357): SLSQP on the optimizer vector (sigma, gamma / 8) in RISK_PREMIA_BOUNDS, options {'disp': True, 'ftol':
+        1e-16, 'maxiter': maxiter, 'eps': 0.025} and tol=1e-16, no constraint and no result check; the objective is
+        np.nansum(w (model - market)^2) with w = 10000 x the per-slice normalised vegas (or 10000 x ones), the model vols
+        inverted against the gamma forwards (risk_premia_calibration_objective).  Each evaluation is one
+        hawkesjd_chain_pricer_with_risk_premia on the device.  As in the reference, every unpack MUTATES params0 (sigma,
+        risk_premia_gamma), the fit is params0 itself, and print_iter prints one line per evaluated vector.
+        `kwargs`: disp= (SLSQP printing, default True); batched_gradient= (default True: SLSQP's forward-difference
+        gradient at its step 0.025 -- the same points it would evaluate -- from one
+        hawkesjd_chain_pricer_with_risk_premia_batch of the bumped vectors per iterate; False lets SLSQP difference itself);
+        ode_rtol= / ode_atol= (default 1e-10 / 1e-12).
+        `self.last_calibration` keeps {"n_eval", "n_gradient_batches", "objective", "success", "status", "message", "nit",
+        "nfev", "x"} of the run."""
+        from scipy.optimize import minimize
+        objective = self.risk_premia_calibration_objective(option_chain, params0, is_vega_weighted, is_unit_ttm_vega,
+                                                           print_iter, **kwargs)
+        extra = dict(jac=objective.gradient) if objective.model_vols_batch is not None else {}
+        options = {"disp": bool(kwargs.get("disp", True)), "ftol": 1e-16, "maxiter": maxiter, "eps": RISK_PREMIA_FD_STEP}
+        res = minimize(objective, risk_premia_start_vector(params0), args=None, method="SLSQP", bounds=RISK_PREMIA_BOUNDS,
+                       options=options, tol=1e-16, **extra)
+        self.last_calibration = dict(n_eval=objective.n_eval, n_gradient_batches=objective.n_batches, objective=float(res.fun),
+                                     success=bool(res.success), status=int(res.status), message=str(res.message),
+                                     nit=int(res.nit), nfev=int(res.nfev), x=np.array(res.x, dtype=float))
+        fit = unpack_risk_premia_vector(res.x, params0)
+        if print_iter:
+            print(f"unpack_pars: sigma={res.x[0]}, gamma={fit.risk_premia_gamma}")
+        return fit
+
     @timer
     def simulate_terminal_values(self, params: HawkesJDParams, ttm: float = 1.0, nb_path: int = 100000,
                                  is_spot_measure: bool = True, **kwargs) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
@@ -241,6 +330,29 @@ def calibration_constraint(pars: np.ndarray, params0: HawkesJDParams) -> float:
     """the inequality constraint (>= 0) of the calibration: the sum of both intensities' stationarity margins (:287-290)"""
     params = unpack_calibration_vector(pars, params0)
     return params.jump1_cond + params.jump2_cond
+
+
+# ---- the risk-premia calibration's codec (reference :320-335): the optimizer's (sigma, gamma / 8) <-> HawkesJDParams ---------
+RISK_PREMIA_GAMMA_SCALER = 8.0
+RISK_PREMIA_BOUNDS = ((0.01, 1.5), (-1.0, 1.0))
+RISK_PREMIA_FD_STEP = 0.025                   # SLSQP's `eps` in the reference's options
+
+
+def risk_premia_start_vector(params0: HawkesJDParams) -> np.ndarray:
+    return np.array([params0.sigma, params0.risk_premia_gamma / RISK_PREMIA_GAMMA_SCALER])
+
+
+def unpack_risk_premia_vector(pars: np.ndarray, params0: HawkesJDParams) -> HawkesJDParams:
+    """the reference's unpack_pars: sets params0.sigma and params0.risk_premia_gamma IN PLACE and returns params0"""
+    params0.sigma = pars[0]
+    params0.risk_premia_gamma = RISK_PREMIA_GAMMA_SCALER * pars[1]
+    return params0
+
+
+def risk_premia_calibration_weights(option_chain: OptionChain, market_vols: np.ndarray, is_vega_weighted: bool,
+                                    is_unit_ttm_vega: bool) -> np.ndarray:
+    """10000 x the per-slice normalised vegas, or 10000 x ones (:316-322)"""
+    return 10000.0 * chain_calibration_weights(option_chain, market_vols, is_vega_weighted, is_unit_ttm_vega)
 
 
 def set_vol_scaler(sigma0: float, ttm: float) -> float:
@@ -349,6 +461,132 @@ def hawkesjd_chain_pricer_batch(params_list: Sequence[HawkesJDParams], ttms: np.
         return out
     finally:
         batch.release()
+
+
+def _risk_ttms_forwards(ttms, forwards) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(ttms as float64, the first min(len(ttms), len(forwards)) ttms and forwards): the reference's zip"""
+    ttms = np.asarray(ttms, dtype=np.float64)
+    forwards = np.asarray(forwards, dtype=np.float64).ravel()
+    n = min(len(ttms), forwards.size)
+    return ttms, np.ascontiguousarray(ttms.ravel()[:n]), np.ascontiguousarray(forwards[:n])
+
+
+def hawkesjd_forwards_under_risk_kernel(model_params: HawkesJDParams, risk_premia_gamma: float, ttms: np.ndarray,
+                                        forwards: np.ndarray, is_stiff_solver: bool = False, ode_rtol: Optional[float] = None,
+                                        ode_atol: Optional[float] = None) -> Tuple[np.ndarray, np.ndarray]:
+    """(normalizers, gamma_forwards) of the risk-premia kernel (reference :487-515): per (ttm, forward) of zip(ttms, forwards)
+    the coefficient ODEs from zero over the whole [0, ttm] at phi = -gamma and -gamma - 1; normalizer = 1 / exp(Re log E(-gamma)),
+    gamma_forward = forward exp(Re log E(-gamma - 1)) normalizer.  Both have the shape of ttms and are pre-filled with ones, so
+    entries beyond the shorter of ttms and forwards stay 1.0 (the paper passes forwards=np.array([1.0]) with 12 ttms).  One
+    launch (svmc_hawkesjd_risk_forwards_batch); is_stiff_solver is answered by the same integrator, ode_rtol / ode_atol as in
+    hawkesjd_chain_pricer."""
+    ttms, t, f = _risk_ttms_forwards(ttms, forwards)
+    normalizers, gamma_forwards = np.ones_like(ttms), np.ones_like(ttms)
+    if t.size == 0:
+        return normalizers, gamma_forwards
+    lib = _lib.load()
+    rows = _model_block(model_params).reshape(1, -1)
+    gammas = np.array([float(risk_premia_gamma)])
+    buf = DeviceBuffer(2 * t.size)
+    try:
+        pf = C.POINTER(C.c_double)
+        _lib.check(lib.svmc_hawkesjd_risk_forwards_batch(rows.ctypes.data_as(pf), gammas.ctypes.data_as(pf), 1, t.ctypes.data_as(pf),
+                                                         f.ctypes.data_as(pf), t.size, buf.ptr, buf.offset(t.size),
+                                                         ODE_RTOL if ode_rtol is None else float(ode_rtol),
+                                                         ODE_ATOL if ode_atol is None else float(ode_atol), None))
+        out = np.empty(2 * t.size)
+        _lib.check(lib.svmc_memcpy_d2h(out.ctypes.data, buf.ptr, out.nbytes, None))
+        _lib.check(lib.svmc_stream_synchronize(None))
+    finally:
+        buf.free()
+    normalizers.ravel()[:t.size] = out[:t.size]
+    gamma_forwards.ravel()[:t.size] = out[t.size:]
+    return normalizers, gamma_forwards
+
+
+def hawkesjd_chain_pricer_with_risk_premia(model_params: HawkesJDParams, ttms: np.ndarray, forwards: np.ndarray,
+                                           discfactors: np.ndarray, strikes_ttms: Sequence[np.ndarray],
+                                           optiontypes_ttms: Sequence[np.ndarray], is_stiff_solver: bool = False,
+                                           is_spot_measure: bool = True, variable_type: VariableType = VariableType.LOG_RETURN,
+                                           vol_scaler: float = None, ode_rtol: Optional[float] = None,
+                                           ode_atol: Optional[float] = None, return_forwards: bool = False):
+    """chain prices under the risk-premia kernel of model_params.risk_premia_gamma (reference :420-484): the normalizers and
+    gamma forwards of hawkesjd_forwards_under_risk_kernel, the coefficient ODEs chained over the expiries on the transform grid
+    of real part -0.5 - gamma (the plain ODE: the reference's risk_premia_gamma= keyword is swallowed by **kwargs), each slice
+    by slice_pricer_with_mgf_grid_with_gamma.  discfactors are ignored (undiscounted prices, as in the reference); LOG_RETURN
+    only.  Extensions: ode_rtol / ode_atol, and return_forwards=True -> (prices, (normalizers, gamma_forwards)).  This is
+    hawkesjd_chain_pricer_with_risk_premia_batch at one set, so the two agree bit for bit."""
+    prices, fwds = hawkesjd_chain_pricer_with_risk_premia_batch(
+        params_list=[model_params], ttms=ttms, forwards=forwards, discfactors=discfactors, strikes_ttms=strikes_ttms,
+        optiontypes_ttms=optiontypes_ttms, is_stiff_solver=is_stiff_solver, is_spot_measure=is_spot_measure,
+        variable_type=variable_type, vol_scaler=vol_scaler, ode_rtol=ode_rtol, ode_atol=ode_atol, return_forwards=True)
+    return (prices[0], fwds[0]) if return_forwards else prices[0]
+
+
+def hawkesjd_chain_pricer_with_risk_premia_batch(params_list: Sequence[HawkesJDParams], ttms: np.ndarray, forwards: np.ndarray,
+                                                 discfactors: np.ndarray, strikes_ttms: Sequence[np.ndarray],
+                                                 optiontypes_ttms: Sequence[np.ndarray], is_stiff_solver: bool = False,
+                                                 is_spot_measure: bool = True,
+                                                 variable_type: VariableType = VariableType.LOG_RETURN,
+                                                 vol_scaler: float = None, ode_rtol: Optional[float] = None,
+                                                 ode_atol: Optional[float] = None, return_forwards: bool = False):
+    """hawkesjd_chain_pricer_with_risk_premia for SEVERAL parameter sets (each its own sigma and risk_premia_gamma, so its own
+    grid: real part -0.5 - gamma, scale from its sigma unless vol_scaler is given) on one chain: [set][expiry] -> prices, and
+    with return_forwards=True also [set] -> (normalizers, gamma_forwards).  One forwards launch, then per expiry one advance
+    launch and one inversion launch for all sets, then one download.  Everything the reference would reject is rejected on
+    the host before any device call.  Not in the reference API: the batched form of the risk-premia calibration's gradient."""
+    if int(getattr(variable_type, "value", variable_type)) != LOG_RETURN:
+        raise NotImplementedError(f"variable_type={variable_type}")
+    n_sets = len(params_list)
+    if n_sets == 0:
+        return ([], []) if return_forwards else []
+    for p in params_list:
+        if p.risk_premia_gamma is None:
+            raise ValueError("risk_premia_gamma must be set for the risk-premia pricer")
+    ttms, t_fwd, f_fwd = _risk_ttms_forwards(ttms, forwards)
+    n_exp = min(t_fwd.size, len(strikes_ttms), len(optiontypes_ttms))
+    strikes = [np.asarray(k, dtype=np.float64) for k in list(strikes_ttms)[:n_exp]]
+    codes = []
+    for k, types in zip(strikes, list(optiontypes_ttms)[:n_exp]):   # the slice pricer's ValueErrors, up front
+        if k.size and not is_spot_measure:
+            raise ValueError("not implemented")
+        codes.append(mgfp.gamma_type_codes(np.asarray(types).ravel()))
+        if codes[-1].size != k.size:
+            raise ValueError("strikes and optiontypes of a slice differ in length")
+    gammas = np.array([float(p.risk_premia_gamma) for p in params_list])
+    grids = [mgfp.get_transform_var_grid(variable_type=variable_type, max_phi=MAX_PHI,
+                                         vol_scaler=(set_vol_scaler(sigma0=p.sigma, ttm=np.min(ttms))
+                                                     if vol_scaler is None else vol_scaler), real_phi=-0.5 - g)
+             for p, g in zip(params_list, gammas)]
+    shortcut = np.array([mgfp.gamma_shortcut(g[0], gm) for g, gm in zip(grids, gammas)], dtype=np.int32)
+    rows = np.stack([_model_block(p) for p in params_list])
+    normalizers = [np.ones_like(ttms) for _ in params_list]
+    gamma_forwards = [np.ones_like(ttms) for _ in params_list]
+    out = [[] for _ in params_list]
+    if t_fwd.size == 0:
+        return (out, list(zip(normalizers, gamma_forwards))) if return_forwards else out
+    batch = AnalyticGridBatch.acquire([g[0] for g in grids], [g[1] for g in grids], 3)
+    try:
+        ks = [k.size for k in strikes]
+        offs = np.concatenate([[0], np.cumsum([n_sets * k for k in ks])]).astype(int)
+        batch.reserve_results(int(offs[-1]))
+        batch.risk_forwards(rows, gammas, t_fwd, f_fwd, ode_rtol, ode_atol)
+        ttm0 = 0.0
+        for i in range(n_exp):
+            batch.hawkes_advance(float(t_fwd[i] - ttm0), rows, ode_rtol, ode_atol)
+            batch.queue_gamma_slice(gammas, shortcut, i, float(f_fwd[i]), strikes[i].ravel(), codes[i], int(offs[i]))
+            ttm0 = t_fwd[i]
+        sums, norms, gfwds = batch.download_risk_results(int(offs[-1]))
+    finally:
+        batch.release()
+    for s in range(n_sets):
+        normalizers[s].ravel()[:t_fwd.size] = norms[:, s]
+        gamma_forwards[s].ravel()[:t_fwd.size] = gfwds[:, s]
+    for i in range(n_exp):
+        prices = sums[offs[i]:offs[i + 1]].reshape(n_sets, ks[i])
+        for s in range(n_sets):
+            out[s].append(prices[s].reshape(strikes[i].shape).copy())
+    return (out, list(zip(normalizers, gamma_forwards))) if return_forwards else out
 
 
 def hawkesjd_mc_chain_pricer(ttms: np.ndarray, forwards: np.ndarray, discfactors: np.ndarray,

@@ -70,14 +70,16 @@ class ImpliedVolObjective:
     `model_vols_batch(list of pars)` (optional) returns the vols of SEVERAL parameter vectors from one batch of launches;
     `gradient` then hands SLSQP the forward-difference gradient it would otherwise build itself from n + 1 separate
     objective calls -- the same evaluation points (scipy.optimize approx_derivative, '2-point', abs_step = sqrt(eps),
-    a step that would leave the box flipped), the same numbers, one launch batch per optimizer iterate."""
+    a step that would leave the box flipped), the same numbers, one launch batch per optimizer iterate.  `fd_step`: the
+    absolute step, for a caller that passes SLSQP its own `eps` (default sqrt(eps), SLSQP's default)."""
 
     FD_STEP = float(np.sqrt(np.finfo(float).eps))          # scipy's SLSQP default `eps`
 
     def __init__(self, model_vols: Callable[[np.ndarray], List[np.ndarray]], market_vols: np.ndarray,
                  weights: np.ndarray, model_vols_batch: Callable[[List[np.ndarray]], List[List[np.ndarray]]] = None,
-                 bounds: Sequence[Tuple[float, float]] = None):
+                 bounds: Sequence[Tuple[float, float]] = None, fd_step: float = None):
         self.model_vols = model_vols
+        self.fd_step = self.FD_STEP if fd_step is None else float(fd_step)     # SLSQP's `eps` of the caller's options
         self.model_vols_batch = model_vols_batch
         self.market_vols = np.asarray(market_vols, dtype=float)
         self.weights = np.asarray(weights, dtype=float)
@@ -101,7 +103,7 @@ class ImpliedVolObjective:
 
     def fd_steps(self, x0: np.ndarray) -> np.ndarray:
         """the signed absolute steps of the forward difference at x0 (approx_derivative's rule for a bounded box)"""
-        h = np.full(x0.shape, self.FD_STEP)
+        h = np.full(x0.shape, self.fd_step)
         if self.lower is None or np.all(np.isinf(self.lower) & np.isinf(self.upper)):
             return h
         lower_dist, upper_dist = x0 - self.lower, self.upper - x0

@@ -1,8 +1,9 @@
 """
 Transform grids, quadrature weights and the Fourier slice pricer (mirror of the reference's utils/mgf_pricer.py:
 get_phi_grid :11-34, get_psi_grid :37-47, get_theta_grid :50-58, get_transform_var_grid :61-94,
-compute_integration_weights :97-155, vanilla_slice_pricer_with_mgf_grid :174-221).  Grid construction is host
-NumPy; the strike sums of the slice pricer run in libsvmc's mgf_vanilla_slice_kernel.
+compute_integration_weights :97-155, vanilla_slice_pricer_with_mgf_grid :174-221, slice_pricer_with_mgf_grid_with_gamma
+:273-321).  Grid construction is host NumPy; the strike sums of the slice pricers run in libsvmc's mgf_vanilla_slice_kernel and
+mgf_gamma_slice_kernel.
 """
 from __future__ import annotations
 
@@ -10,7 +11,7 @@ from typing import Tuple
 
 import numpy as np
 
-from ..analytic import AnalyticGrid, vanilla_prices_from_capped
+from ..analytic import AnalyticGrid, gamma_slice_prices, vanilla_prices_from_capped
 from .config import VariableType
 
 
@@ -88,3 +89,42 @@ def vanilla_slice_pricer_with_mgf_grid(log_mgf_grid: np.ndarray, phi_grid: np.nd
     finally:
         grid.close()
     return vanilla_prices_from_capped(capped, forward, strikes, optiontypes, discfactor, is_spot_measure)
+
+
+def gamma_shortcut(phi_grid: np.ndarray, risk_premia_gamma: float) -> bool:
+    """the reference's branch of the risk-premia payoff weight (:296): the real shortcut where every
+    |Re phi - (0.5 + gamma)| < 1e-10 -- on the risk grid Re phi = -0.5 - gamma, i.e. only at gamma = -0.5"""
+    return bool(np.all(np.abs(np.real(phi_grid) - (0.5 + risk_premia_gamma)) < 1e-10))
+
+
+def gamma_type_codes(optiontypes) -> np.ndarray:
+    """'C' -> 0, 'P' -> 1; any other type raises as the reference does (:318-319)"""
+    codes = np.empty(len(optiontypes), dtype=np.int32)
+    for i, t in enumerate(optiontypes):
+        t = str(t)
+        if t not in ("C", "P"):
+            raise ValueError("not implemented")
+        codes[i] = 0 if t == "C" else 1
+    return codes
+
+
+def slice_pricer_with_mgf_grid_with_gamma(log_mgf_grid: np.ndarray, phi_grid: np.ndarray, risk_premia_gamma: float, ttm: float,
+                                          forward: float, normalizer: float, gamma_forward: float, strikes: np.ndarray,
+                                          optiontypes: np.ndarray, discfactor: float = 1.0, is_spot_measure: bool = True,
+                                          is_simpson: bool = True) -> np.ndarray:
+    """vanilla prices of one slice under the risk-premia kernel from log E on the phi grid (reference :273-321): legacy Simpson
+    weights, the payoff weight (dp / pi) / (p^2 + 1/4) where gamma_shortcut holds and -(dp / pi) / ((phi + gamma + 1)(phi +
+    gamma)) otherwise, cap = nansum Re[w exp(-x phi + log E)]; 'C' -> gamma_forward - normalizer K^(1+gamma) cap, 'P' -> K -
+    normalizer K^(1+gamma) cap.  As in the reference, the prices are undiscounted (discfactor and ttm are unused), and
+    is_spot_measure=False or a type other than 'C' / 'P' raises ValueError."""
+    if not is_simpson:
+        raise NotImplementedError("the GPU slice pricer covers the Simpson rule")
+    strikes = np.asarray(strikes, dtype=np.float64)
+    if strikes.size and not is_spot_measure:
+        raise ValueError("not implemented")
+    codes = gamma_type_codes(optiontypes)
+    phi_grid = np.asarray(phi_grid, dtype=np.complex128).ravel()
+    prices = gamma_slice_prices(phi_grid, np.asarray(log_mgf_grid, dtype=np.complex128).ravel(), float(risk_premia_gamma),
+                                gamma_shortcut(phi_grid, risk_premia_gamma), float(normalizer), float(gamma_forward),
+                                float(forward), strikes.ravel(), codes)
+    return prices.reshape(strikes.shape)
