@@ -442,6 +442,38 @@ SVMC_API int svmc_heston_chain_price(svmc_session_t session, const double *ttms_
                                      int nb_steps_per_year, int variable_type, uint64_t seed, uint32_t call_id,
                                      double *prices_host, double *stderrs_host);
 
+/* ---- many independent jobs of one chain in one call ---------------------------------------------------------------
+ * n_jobs jobs share the chain (ttms .. strike_offsets, n_expiries <= 16), the session's path count, the step grid and the
+ * variable type (LogSV also is_spot_measure, Heston the scheme); each has its own parameters and random stream.  Job j's
+ * prices and standard errors (row j of prices_host / stderrs_host [n_jobs][sum K_i]) are those of svmc_logsv_chain_price /
+ * svmc_heston_chain_price on the same session with job j's parameters, seeds_host[j] and call_ids_host[j], BIT FOR BIT: ONE
+ * stepping launch steps every job (blockIdx.y = job), one payoff launch and one finish launch serve them all.
+ *   params_host  LogSV:  [n_jobs][6 + n_expiries]  v0 theta kappa1 kappa2 beta volvol, then the expiries' vol-backbone etas
+ *                Heston: [n_jobs][5]               v0 theta kappa rho volvol
+ * Session: any single-GPU session whose max_expiries / max_strikes_total hold the chain (the sizes a single call of the chain
+ * needs); the driver grows a per-job workspace of its own inside the session on demand -- about (1 or 2 with Q_VAR) x
+ * n_jobs x n_expiries x n_path doubles of snapshots, kept until the session is destroyed -- and touches none of the
+ * buffers, state arrays or graphs of the other drivers: a later single call returns what it would have returned.
+ * At most SVMC_MANY_MAX_JOBS jobs per call (split longer lists).  Errors, all before anything is launched:
+ *   SVMC_ERR_INVALID_ARGUMENT  n_jobs < 1 or > SVMC_MANY_MAX_JOBS, a null pointer (session included), n_expiries outside
+ *                              [1, 16], a call id of 24 bits or more, an unknown scheme, a session with a communicator
+ *                              or reducer attached (no sharded batch);
+ *   SVMC_ERR_WORKSPACE         a session too small for the chain (n_expiries > max_expiries or sum K_i > max_strikes_total);
+ *   SVMC_ERR_HIP               the per-job workspace could not be allocated. */
+#define SVMC_MANY_MAX_JOBS 64
+SVMC_API int svmc_logsv_chain_price_many(svmc_session_t session, const double *ttms_host, const double *forwards_host,
+                                         const double *discfactors_host, int n_expiries, const double *strikes_host,
+                                         const int8_t *types_host, const size_t *strike_offsets_host, int n_jobs,
+                                         const double *params_host, const uint64_t *seeds_host, const uint32_t *call_ids_host,
+                                         int is_spot_measure, int nb_steps_per_year, int variable_type, double *prices_host,
+                                         double *stderrs_host);
+SVMC_API int svmc_heston_chain_price_many(svmc_session_t session, const double *ttms_host, const double *forwards_host,
+                                          const double *discfactors_host, int n_expiries, const double *strikes_host,
+                                          const int8_t *types_host, const size_t *strike_offsets_host, int n_jobs,
+                                          const double *params_host, const uint64_t *seeds_host, const uint32_t *call_ids_host,
+                                          int scheme, int nb_steps_per_year, int variable_type, double *prices_host,
+                                          double *stderrs_host);
+
 /* ---- multi-GPU below the host language: RCCL over xGMI ----------------------------------------------------------
  * One process (or thread) per GPU.  Paths are independent, so rank r holds the global path ids
  * [path_offset, path_offset + n_path) of a job of n_path_total paths in its own session; the counter-based randoms

@@ -2,9 +2,9 @@
 stochvolmodels_amd -- MI355X-native Monte Carlo engine for the StochVolModels hot path.
 
 Module layout and public names mirror the reference package (`stochvolmodels`) for the Monte Carlo path:
-    stochvolmodels_amd.pricers.logsv_pricer   LogSVPricer, logsv_mc_chain_pricer(_fixed_randoms),
+    stochvolmodels_amd.pricers.logsv_pricer   LogSVPricer, logsv_mc_chain_pricer(_fixed_randoms, _many),
                                               simulate_logsv_x_vol_terminal, get_randoms_for_chain_valuation
-    stochvolmodels_amd.pricers.heston_pricer  HestonPricer, HestonParams, heston_mc_chain_pricer,
+    stochvolmodels_amd.pricers.heston_pricer  HestonPricer, HestonParams, heston_mc_chain_pricer(_many),
                                               simulate_heston_x_vol_terminal
     stochvolmodels_amd.pricers.hawkes_jd_pricer  HawkesJDPricer, HawkesJDParams, hawkesjd_mc_chain_pricer,
                                               hawkesjd_chain_pricer(_batch), simulate_hawkesjd_terminal,
@@ -34,6 +34,7 @@ _EXPORTS = {
     "LogSvParams": "pricers.logsv.logsv_params",
     "LogSVPricer": "pricers.logsv_pricer", "LOGSV_BTC_PARAMS": "pricers.logsv_pricer",
     "logsv_mc_chain_pricer": "pricers.logsv_pricer",
+    "logsv_mc_chain_pricer_many": "pricers.logsv_pricer",
     "logsv_mc_chain_pricer_fixed_randoms": "pricers.logsv_pricer",
     "simulate_logsv_x_vol_terminal": "pricers.logsv_pricer",
     "simulate_vol_paths": "pricers.logsv_pricer",
@@ -56,6 +57,7 @@ _EXPORTS = {
     "heston_chain_pricer": "pricers.heston_pricer", "compute_heston_mgf_grid": "pricers.heston_pricer",
     "HestonPricer": "pricers.heston_pricer", "HestonParams": "pricers.heston_pricer",
     "BTC_HESTON_PARAMS": "pricers.heston_pricer", "heston_mc_chain_pricer": "pricers.heston_pricer",
+    "heston_mc_chain_pricer_many": "pricers.heston_pricer",
     "simulate_heston_x_vol_terminal": "pricers.heston_pricer",
     "compute_analytic_qvar": "pricers.logsv.vol_moments_ode",
     "compute_analytic_vol_moments": "pricers.logsv.vol_moments_ode",

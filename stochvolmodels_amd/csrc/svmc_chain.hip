@@ -35,6 +35,16 @@ struct FixedGraph {
     double *quotes_dev = nullptr, *ivols_dev = nullptr, *ivols_host = nullptr;
 };
 
+// the buffers of the many-job drivers (svmc_*_chain_price_many), grown on demand and apart from everything the other drivers use
+struct ManyBuffers {
+    double *snap = nullptr, *spot_ws = nullptr, *spot = nullptr, *sums = nullptr;     // device
+    void *ws = nullptr, *table_dev = nullptr;                                          // device
+    void *table_host = nullptr;                                                        // pinned
+    double *sums_pinned = nullptr;                                                     // pinned
+    size_t snap_bytes = 0, spot_ws_bytes = 0, spot_bytes = 0, sums_bytes = 0, ws_bytes = 0, table_bytes = 0, table_host_bytes = 0,
+           sums_pinned_bytes = 0;
+};
+
 struct Session {
     // multi-GPU (svmc_session_set_comm): this session holds the paths [path_offset, path_offset + n_path) of a job of
     // n_total paths spread over `world` ranks; `comm` is the ncclComm_t the two reductions of a chain go through
@@ -70,6 +80,7 @@ struct Session {
     bool time_stepping = false;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     float last_stepping_ms = -1.0f;
+    ManyBuffers many;
 };
 
 // events around a stepping call of a timed session (no-ops otherwise)
@@ -117,6 +128,12 @@ static void session_release(Session *s)
                     static_cast<void *>(s->spot_ws)})
         if (p != nullptr) (void)hipFree(p);
     if (s->sums_pinned != nullptr) (void)hipHostFree(s->sums_pinned);
+    ManyBuffers &mb = s->many;
+    for (void *p : {static_cast<void *>(mb.snap), static_cast<void *>(mb.spot_ws), static_cast<void *>(mb.spot),
+                    static_cast<void *>(mb.sums), mb.ws, mb.table_dev})
+        if (p != nullptr) (void)hipFree(p);
+    for (void *p : {mb.table_host, static_cast<void *>(mb.sums_pinned)})
+        if (p != nullptr) (void)hipHostFree(p);
     if (s->ev0 != nullptr) (void)hipEventDestroy(s->ev0);
     if (s->ev1 != nullptr) (void)hipEventDestroy(s->ev1);
     if (s->owns_stream && s->stream != nullptr) (void)hipStreamDestroy(s->stream);
@@ -916,6 +933,146 @@ int svmc_hawkesjd_chain_price(svmc_session_t session, const double *ttms_host, c
         return rc;
     stepping_end(s);
     return reduce_and_finalize(s, c, variable_type, prices_host, stderrs_host, pending);
+}
+
+}  // extern "C"
+
+// ---- many jobs of one chain (svmc_logsv_chain_price_many / svmc_heston_chain_price_many)
+
+// *p at least `need` bytes (its contents are not kept); every many-call ends synchronised, so nothing still reads the old buffer
+static hipError_t grow(void **p, size_t &cap, size_t need, bool pinned)
+{
+    if (*p != nullptr && need <= cap) return hipSuccess;
+    if (*p != nullptr) (void)(pinned ? hipHostFree(*p) : hipFree(*p));
+    *p = nullptr;
+    cap = 0;
+    const hipError_t e = pinned ? hipHostMalloc(p, need, hipHostMallocDefault) : hipMalloc(p, need);
+    if (e == hipSuccess) cap = need;
+    return e;
+}
+
+static int grow_many(const char *fn, ManyBuffers &mb, size_t n, size_t J, size_t m, size_t K, bool need_q)
+{
+    const size_t d = sizeof(double), sums = (3 * K * J > 0 ? 3 * K * J : 1) * d;
+    const struct {
+        void **p;
+        size_t *cap, need;
+        bool pinned;
+    } bufs[] = {
+        {reinterpret_cast<void **>(&mb.snap), &mb.snap_bytes, (need_q ? 2 : 1) * J * m * n * d, false},
+        {reinterpret_cast<void **>(&mb.spot_ws), &mb.spot_ws_bytes, static_cast<size_t>(wave_rows(n)) * 2 * m * J * d, false},
+        {reinterpret_cast<void **>(&mb.spot), &mb.spot_bytes, 2 * m * J * d, false},
+        {reinterpret_cast<void **>(&mb.sums), &mb.sums_bytes, sums, false},
+        {&mb.ws, &mb.ws_bytes, payoff_sets_workspace_bytes(n, K, static_cast<int>(J)), false},
+        {&mb.table_dev, &mb.table_bytes, many_table_bytes(static_cast<int>(J), static_cast<int>(m)), false},
+        {&mb.table_host, &mb.table_host_bytes, many_table_bytes(static_cast<int>(J), static_cast<int>(m)), true},
+        {reinterpret_cast<void **>(&mb.sums_pinned), &mb.sums_pinned_bytes, sums, true},
+    };
+    for (const auto &b : bufs)
+        if (hipError_t e = grow(b.p, *b.cap, b.need, b.pinned))
+            return fail(SVMC_ERR_HIP, std::string(fn) + ": per-job workspace: " + hipGetErrorString(e));
+    return SVMC_OK;
+}
+
+// The driver of both models: the checks (all before any device work), the per-job workspace, step(nbs, dts, qsnap) -- the model's
+// ONE stepping launch of every job into the ManyBuffers -- then the jobs' spot sums (one column reduce), ONE payoff launch and ONE
+// finish launch for all jobs (a payoff launch per job where the chain does not fit one), and the host finalisation per job.
+template <class Step>
+static int chain_price_many(const char *fn, svmc_session_t session, const ChainView &c, int n_jobs, const void *params,
+                            const uint64_t *seeds, const uint32_t *call_ids, int nb_steps_per_year, int variable_type, double *prices,
+                            double *stderrs, Step &&step)
+{
+    Session *s = reinterpret_cast<Session *>(session);
+    SVMC_REQUIRE(s != nullptr, std::string(fn) + ": null session");
+    SVMC_REQUIRE(n_jobs >= 1 && n_jobs <= SVMC_MANY_MAX_JOBS, std::string(fn) + ": n_jobs must be in [1, SVMC_MANY_MAX_JOBS]");
+    SVMC_REQUIRE(params && seeds && call_ids && c.ttms && c.forwards && c.discfactors && c.strikes && c.types && c.offsets && prices &&
+                     stderrs,
+                 std::string(fn) + ": null pointer");
+    SVMC_REQUIRE(c.m >= 1 && c.m <= MAX_FUSED_SLICES, std::string(fn) + ": 1 to 16 expiries");
+    if (c.m > s->max_expiries || c.offsets[c.m] > s->max_strikes)
+        return fail(SVMC_ERR_WORKSPACE, std::string(fn) + ": the chain exceeds the session (max_expiries / max_strikes_total)");
+    SVMC_REQUIRE(!s->sharded(), std::string(fn) + ": no sharded batch: detach the communicator / reducer");
+    SVMC_REQUIRE(nb_steps_per_year > 0, std::string(fn) + ": nb_steps_per_year must be positive");
+    for (int j = 0; j < n_jobs; ++j) SVMC_REQUIRE(call_ids[j] < (1u << 24), std::string(fn) + ": call_id must fit 24 bits");
+    if (int rc = check_chain(fn, s, c, variable_type, prices, stderrs)) return rc;
+    const size_t n = s->n_path, J = static_cast<size_t>(n_jobs), m = static_cast<size_t>(c.m), K = c.offsets[c.m];
+    const bool need_q = variable_type == SVMC_Q_VAR;
+    ManyBuffers &mb = s->many;
+    if (int rc = grow_many(fn, mb, n, J, m, K, need_q)) return rc;
+    std::vector<int> nbs;
+    std::vector<double> dts, shifts;
+    expiry_grids(c, nb_steps_per_year, nbs, dts);
+    payoff_shifts_of(c, variable_type, shifts);
+    double *qsnap = need_q ? mb.snap + J * m * n : nullptr;
+    stepping_begin(s);
+    if (int rc = step(nbs, dts, qsnap)) return rc;
+    if (int rc = reduce_spot_partials(mb.spot_ws, n, static_cast<int>(2 * m * J), mb.spot, s->stream)) return rc;
+    stepping_end(s);
+    std::vector<const double *> xs(m), qs(m);
+    for (size_t i = 0; i < m; ++i) {
+        xs[i] = mb.snap + i * n;
+        qs[i] = need_q ? qsnap + i * n : nullptr;
+    }
+    if (payoff_sets_fit(n, c.m, c.offsets, c.types, n_jobs, mb.ws_bytes)) {
+        if (int rc = chain_payoff_and_finish_sets(xs.data(), need_q ? qs.data() : nullptr, n, c.forwards, c.ttms, mb.spot, c.m, c.strikes,
+                                                  c.types, shifts.data(), c.offsets, variable_type, mb.ws, mb.ws_bytes, s->stream, n_jobs,
+                                                  m * n, m * n, 2 * m, mb.sums, mb.sums_pinned))
+            return rc;
+    } else {
+        // more strike groups than one payoff launch takes: a payoff pass per job, as the single call then runs it
+        for (size_t j = 0; j < J; ++j) {
+            std::vector<const double *> xj(m), qj(m);
+            for (size_t i = 0; i < m; ++i) {
+                xj[i] = xs[i] + j * m * n;
+                qj[i] = need_q ? qs[i] + j * m * n : nullptr;
+            }
+            if (int rc = svmc_payoff_sums_chain(xj.data(), need_q ? qj.data() : nullptr, n, c.forwards, c.ttms, mb.spot + 2 * m * j, c.m,
+                                                c.strikes, c.types, shifts.data(), c.offsets, variable_type, mb.sums + 3 * K * j, mb.ws,
+                                                mb.ws_bytes, reinterpret_cast<svmc_stream_t>(s->stream)))
+                return rc;
+        }
+        SVMC_HIP_TRY(hipMemcpyAsync(mb.sums_pinned, mb.sums, 3 * K * J * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    }
+    SVMC_HIP_TRY(hipStreamSynchronize(s->stream));
+    stepping_read(s);
+    return finish_sets(s, c, mb.sums_pinned, shifts, n_jobs, variable_type, prices, stderrs, nullptr, nullptr);
+}
+
+extern "C" {
+
+int svmc_logsv_chain_price_many(svmc_session_t session, const double *ttms_host, const double *forwards_host,
+                                const double *discfactors_host, int n_expiries, const double *strikes_host, const int8_t *types_host,
+                                const size_t *strike_offsets_host, int n_jobs, const double *params_host, const uint64_t *seeds_host,
+                                const uint32_t *call_ids_host, int is_spot_measure, int nb_steps_per_year, int variable_type,
+                                double *prices_host, double *stderrs_host)
+{
+    const ChainView c = {n_expiries, ttms_host, forwards_host, discfactors_host, strikes_host, types_host, strike_offsets_host};
+    Session *s = reinterpret_cast<Session *>(session);
+    return chain_price_many("svmc_logsv_chain_price_many", session, c, n_jobs, params_host, seeds_host, call_ids_host, nb_steps_per_year,
+                            variable_type, prices_host, stderrs_host,
+                            [&](const std::vector<int> &nbs, const std::vector<double> &dts, double *qsnap) {
+        ManyBuffers &mb = s->many;
+        return logsv_chain_rng_many(s->n_path, n_jobs, c.m, nbs.data(), dts.data(), c.forwards, params_host, is_spot_measure, seeds_host,
+                                    call_ids_host, s->path_offset, mb.table_host, mb.table_dev, mb.snap, qsnap, mb.spot_ws, s->stream);
+    });
+}
+
+int svmc_heston_chain_price_many(svmc_session_t session, const double *ttms_host, const double *forwards_host,
+                                 const double *discfactors_host, int n_expiries, const double *strikes_host, const int8_t *types_host,
+                                 const size_t *strike_offsets_host, int n_jobs, const double *params_host, const uint64_t *seeds_host,
+                                 const uint32_t *call_ids_host, int scheme, int nb_steps_per_year, int variable_type,
+                                 double *prices_host, double *stderrs_host)
+{
+    const ChainView c = {n_expiries, ttms_host, forwards_host, discfactors_host, strikes_host, types_host, strike_offsets_host};
+    Session *s = reinterpret_cast<Session *>(session);
+    SVMC_REQUIRE(scheme == SVMC_HESTON_EULER_FLOOR || scheme == SVMC_HESTON_QE, "svmc_heston_chain_price_many: unknown scheme");
+    return chain_price_many("svmc_heston_chain_price_many", session, c, n_jobs, params_host, seeds_host, call_ids_host,
+                            nb_steps_per_year, variable_type, prices_host, stderrs_host,
+                            [&](const std::vector<int> &nbs, const std::vector<double> &dts, double *qsnap) {
+        ManyBuffers &mb = s->many;
+        return heston_chain_rng_many(s->n_path, n_jobs, c.m, nbs.data(), dts.data(), c.forwards, params_host, scheme, seeds_host,
+                                     call_ids_host, s->path_offset, mb.table_host, mb.table_dev, mb.snap, qsnap, mb.spot_ws, s->stream);
+    });
 }
 
 int svmc_session_state(svmc_session_t session, double *x_host, double *vol_host, double *qvar_host)

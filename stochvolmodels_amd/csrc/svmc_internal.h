@@ -82,6 +82,26 @@ int hawkes_step_partials(const double *params_host, double *x, double *lam_p, do
                          const int *nb_steps_host, const double *dts_host, const double *forwards_host, uint64_t seed,
                          uint32_t call_id, uint64_t path_offset, double *x_snapshots, double *spot_sums, void *workspace,
                          size_t workspace_bytes, hipStream_t stream);
+// ---- many independent jobs of one chain in one stepping launch (svmc_*_chain_price_many): the launch uploads its job table
+// (many_table_bytes, from the pinned table_host into table_dev) and writes job j's snapshot rows j m + i ([J m][n], qvar rows the
+// same at qvar_snapshots) and per-wave spot partial column pairs 2 (j m + i) ([2 J m][wave_rows(n)]); params_host rows as in
+// svmc.h.  payoff_sets_workspace_bytes bounds the workspace chain_payoff_and_finish_sets needs for the jobs' payoff partials.
+size_t many_table_bytes(int n_jobs, int n_slices);
+int logsv_chain_rng_many(size_t n_path, int n_jobs, int n_slices, const int *nb_steps_host, const double *dts_host,
+                         const double *forwards_host, const double *params_host, int is_spot_measure, const uint64_t *seeds,
+                         const uint32_t *call_ids, uint64_t path_offset, void *table_host, void *table_dev, double *x_snapshots,
+                         double *qvar_snapshots, double *spot_partials, hipStream_t stream);
+int heston_chain_rng_many(size_t n_path, int n_jobs, int n_slices, const int *nb_steps_host, const double *dts_host,
+                          const double *forwards_host, const double *params_host, int scheme, const uint64_t *seeds,
+                          const uint32_t *call_ids, uint64_t path_offset, void *table_host, void *table_dev, double *x_snapshots,
+                          double *qvar_snapshots, double *spot_partials, hipStream_t stream);
+size_t payoff_sets_workspace_bytes(size_t n_path, size_t total_strikes, int n_sets);
+int chain_payoff_and_finish_sets(const double *const *x_snapshots_host, const double *const *qvar_snapshots_host, size_t n_path,
+                                 const double *forwards_host, const double *ttms_host, const double *spot_sums, int n_expiries,
+                                 const double *strikes_host, const int8_t *types_host, const double *shifts_host,
+                                 const size_t *strike_offsets_host, int variable_type, void *workspace, size_t workspace_bytes,
+                                 hipStream_t stream, int n_sets, size_t x_set_stride, size_t q_set_stride, size_t spot_set_stride,
+                                 double *sums_dev, double *sums_out);
 bool spot_sums_in_payoff_kernel(size_t n_path);
 int reduce_spot_partials(const void *workspace, size_t n_path, int n_cols, double *spot_sums, hipStream_t stream);
 int check_launch(const char *what);          // hipGetLastError -> SVMC_ERR_HIP "what: ..."

@@ -627,6 +627,134 @@ static const LogsvLatVariant *logsv_lat_variant(size_t n_path)
 
 static inline unsigned lat_grid(size_t n, int block = FEW_BLOCK) { return static_cast<unsigned>((n + block - 1) / block); }
 
+// ---- many independent jobs of one chain in ONE stepping launch (svmc_logsv_chain_price_many / svmc_heston_chain_price_many)
+// blockIdx.y = job, blockIdx.x = block of that job's n paths; path p of job j draws philox_prepare(seed_j, c3_j, path_offset + p)
+// and runs the statements of the one-job kernels above from the start state (0, vol0_j, 0), so job j's snapshots and per-wave
+// spot partials are those of a single call with (seed_j, call_id_j), bit for bit.  Outputs go to row j m + i (expiry i of job j)
+// in the set-major layout of logsv_chain_rng_sets_kernel: ONE payoff launch (blockIdx.z = job) and ONE finish launch serve
+// every job.  The terminal state is not written back (no job owns the session's state arrays).
+constexpr int MAX_MANY_JOBS = SVMC_MANY_MAX_JOBS;
+struct ManySlices {
+    double forward[MAX_CHAIN_SLICES];
+    int nb_steps[MAX_CHAIN_SLICES];
+    int m, total_steps = 0;
+};
+// the per-job device table, one upload per call: the (job, expiry) constants [J][m] (LogsvFast, or HestonConsts + QeConsts),
+// then per job the start vol (variance for Heston), the Philox key and the call id's counter word
+struct ManyJobs {
+    const void *consts;
+    const double *vol0;
+    const uint64_t *seed;
+    const uint32_t *c3;
+};
+
+// a job-uniform value read from the job table, word by word into scalar registers: the step takes its constants as scalar
+// operands (fma_k's "s" constraint), which a table load the compiler issued as a vector load would not satisfy
+template <class T>
+__device__ __forceinline__ T uniform_load(const T *p)
+{
+    static_assert(sizeof(T) % 4 == 0, "whole 32-bit words");
+    uint32_t w[sizeof(T) / 4];
+    memcpy(w, p, sizeof(T));
+#pragma unroll
+    for (int k = 0; k < static_cast<int>(sizeof(T) / 4); ++k) w[k] = __builtin_amdgcn_readfirstlane(w[k]);
+    T out;
+    memcpy(&out, w, sizeof(T));
+    return out;
+}
+
+__global__ __launch_bounds__(CHAIN_BLOCK) __attribute__((amdgpu_waves_per_eu(SVMC_CHAIN_WAVES), amdgpu_num_sgpr(SVMC_CHAIN_SGPRS))) void logsv_chain_rng_many_kernel(
+    size_t n, ManySlices cs, ManyJobs jobs, uint64_t path_offset, double *__restrict__ x_snap, double *__restrict__ q_snap,
+    double *__restrict__ partials, uint64_t *probe)
+{
+    // logsv_chain_rng_kernel's statements: x and qvar parked in LDS across the time loop, the lanes past the last path stepping
+    // on a dummy state
+    __shared__ RngTablesLds s_tab;
+    __shared__ double s_exp[256];
+    __shared__ double s_park[2 * CHAIN_BLOCK];
+    const RngTables tab = stage_tables(s_tab, s_exp);
+    clock_probe_stamp(probe, 0);
+    const auto exp_of = [&](double v) { return exp2u_tab(v, s_exp); };
+    const auto path_index = [&]() {
+        uint32_t t = threadIdx.x;
+        asm volatile("" : "+v"(t));
+        return static_cast<size_t>(blockIdx.x) * CHAIN_BLOCK + t;
+    };
+    const int job = blockIdx.y;
+    const LogsvFast *__restrict__ cj = static_cast<const LogsvFast *>(jobs.consts) + static_cast<size_t>(job) * cs.m;
+    const bool active = path_index() < n;
+    double s = uniform_load(jobs.vol0 + job);
+    s_park[threadIdx.x] = 0.0;
+    s_park[CHAIN_BLOCK + threadIdx.x] = 0.0;
+    const PhiloxLane lane = philox_prepare(uniform_load(jobs.seed + job), uniform_load(jobs.c3 + job), path_offset + path_index());
+    const int quarter = (cs.total_steps + 3) >> 2;
+    int stage = 0, next_stage_t = 0, tg = 0;
+    for (int i = 0; i < cs.m; ++i) {
+        const int nb = cs.nb_steps[i];
+        double xv = 0.0, q = 0.0;
+        {
+            const LogsvFast c = uniform_load(cj + i);
+            double L = log_state(s) * LOG_UNITS_PER_NAT;                                              // :1039
+            double s2 = square_rn(s), acc = 0.0, xacc = 0.0;
+            const double s2_start = s2;
+            rng_time_loop(
+                lane, static_cast<uint32_t>(tg), nb, tab,
+                [&](double z0, double z1) { logsv_step_acc(c, xacc, L, s, s2, acc, z0, z1, exp_of); },
+                [&](int t) {
+                    if (tg + t >= next_stage_t) {          // wave-uniform
+                        progress_priority(stage++);
+                        next_stage_t += quarter;
+                    }
+                });
+            xv = s_park[threadIdx.x];
+            q = s_park[CHAIN_BLOCK + threadIdx.x];
+            logsv_fold_acc(c, xv, q, xacc, acc, s2_start, square_rn(s));
+            s_park[threadIdx.x] = xv;
+            s_park[CHAIN_BLOCK + threadIdx.x] = q;
+        }
+        tg += nb;
+        const size_t row = static_cast<size_t>(job) * cs.m + i;
+        const SliceOut so = {x_snap + row * n, q_snap ? q_snap + row * n : nullptr, partials + 2 * row * ((n + 63) >> 6), cs.forward[i],
+                             (n + 63) >> 6};
+        slice_epilogue(so, path_index(), active, xv, q);
+    }
+    clock_probe_stamp(probe, 1);
+}
+
+// logsv_chain_rng_many_kernel for a launch of a few waves per SIMD in all (J x n paths): logsv_chain_rng_lat_kernel's statements
+template <int LOOP, int WAVES, int TB>
+__global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) void logsv_chain_rng_many_lat_kernel(
+    size_t n, ManySlices cs, ManyJobs jobs, uint64_t path_offset, double *__restrict__ x_snap, double *__restrict__ q_snap,
+    double *__restrict__ partials, uint64_t *probe)
+{
+    __shared__ RngTablesLds s_tab;
+    __shared__ double s_exp[256];
+    const RngTables tab = stage_tables(s_tab, s_exp);
+    clock_probe_stamp(probe, 0);
+    const int job = blockIdx.y;
+    const LogsvFast *__restrict__ cj = static_cast<const LogsvFast *>(jobs.consts) + static_cast<size_t>(job) * cs.m;
+    const size_t p = static_cast<size_t>(blockIdx.x) * TB + threadIdx.x;
+    const bool active = p < n;
+    double xv = 0.0, s = uniform_load(jobs.vol0 + job), q = 0.0;
+    const PhiloxLane lane = philox_prepare(uniform_load(jobs.seed + job), uniform_load(jobs.c3 + job), path_offset + p);
+    int tg = 0;
+    for (int i = 0; i < cs.m; ++i) {
+        const int nb = cs.nb_steps[i];
+        const LogsvFast c = uniform_load(cj + i);
+        double L = log_state(s) * LOG_UNITS_PER_NAT;                                                  // :1039
+        double acc = 0.0, xacc = 0.0;
+        const double s2_start = square_rn(s);
+        logsv_gen_time_loop<LOOP>(lane, static_cast<uint32_t>(tg), nb, tab, c, xacc, L, s, acc, s_exp);
+        logsv_fold_acc(c, xv, q, xacc, acc, s2_start, square_rn(s));
+        tg += nb;
+        const size_t row = static_cast<size_t>(job) * cs.m + i;
+        const SliceOut so = {x_snap + row * n, q_snap ? q_snap + row * n : nullptr, partials + 2 * row * ((n + 63) >> 6), cs.forward[i],
+                             (n + 63) >> 6};
+        slice_epilogue(so, p, active, xv, q);
+    }
+    clock_probe_stamp(probe, 1);
+}
+
 // Streamed-randoms time loop: HBM-bound (8 B per supplied random per path-step).  Software-pipelined by hand:
 // the NARR*U loads of the next U steps are issued before the current U steps are computed, so every wave keeps
 // NARR*U x 512 B in flight (hipcc does not unroll a loop that contains inline asm, and one load per array in
@@ -1479,6 +1607,40 @@ struct HestonChainSlices {
     int m;
 };
 
+// one slice of a many-job Heston path (heston_chain_rng_body's slice statements): nb steps from step `step` of the lane's stream,
+// then the slice's fold into (x, v, q)
+template <int SCHEME, int LOOP>
+__device__ __forceinline__ void heston_chain_slice(const PhiloxLane &lane, const PhiloxLane &lane_u, QeUniforms &uc, uint32_t step, int nb,
+                                                   const RngTables &tab, const HestonConsts c, const QeConsts qc, double &xv, double &v,
+                                                   double &q)
+{
+    const HestonEulerFast ef = make_heston_euler_fast(c);
+    double xacc = 0.0, vacc = 0.0;
+    if constexpr (SCHEME == HESTON_QE_QUAD) {
+        double vsum = 0.0, ksum = 0.0;
+        const double v_first = v;
+        const QeVec qv = make_qe_vec(qc);
+        heston_time_loop<LOOP>(lane, step, nb, tab, [&](double w0, double w1) {
+            heston_qe_step<true>(qc, qv, tab.log, xv, v, vsum, ksum, w0, w1, []() { return 0.0; });
+        });
+        heston_qe_fold(qc, xv, q, vsum, ksum, v_first, v);
+    } else if constexpr (SCHEME == SVMC_HESTON_QE) {
+        double vsum = 0.0, ksum = 0.0;
+        const double v_first = v;
+        uint32_t st = step;
+        const QeVec qv = make_qe_vec(qc);
+        heston_time_loop<LOOP>(lane, step, nb, tab, [&](double w0, double w1) {
+            heston_qe_step(qc, qv, tab.log, xv, v, vsum, ksum, w0, w1, [&]() { return qe_uniform(lane_u, st, uc); });
+            ++st;
+        });
+        heston_qe_fold(qc, xv, q, vsum, ksum, v_first, v);
+    } else {
+        v = heston_euler_guard_zero(v);
+        heston_time_loop<LOOP>(lane, step, nb, tab, [&](double w0, double w1) { heston_euler_step_acc(ef, xacc, v, vacc, w0, w1); });
+        heston_fold_acc(ef, xv, q, v, xacc, vacc);
+    }
+}
+
 template <int SCHEME, int LOOP>
 __device__ __forceinline__ void heston_chain_rng_body(double *__restrict__ x, double *__restrict__ var, double *__restrict__ qvar,
                                                       size_t n, const HestonChainSlices &cs, uint64_t seed, uint32_t c3,
@@ -1571,6 +1733,60 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
     double *__restrict__ partials, StateInit init)
 {
     heston_chain_rng_body<SCHEME, LOOP>(x, var, qvar, n, cs, seed, c3, path_offset, step_offset, x_snap, q_snap, partials, init);
+}
+
+// many jobs of one chain in one launch (see logsv_chain_rng_many_kernel): job blockIdx.y, heston_chain_rng_body's statements from
+// (0, v0_j, 0) on the stream (seed_j, c3_j), outputs at row j m + i; the job table's constants are HestonManyConsts [J][m]
+struct HestonManyConsts {
+    HestonConsts c;
+    QeConsts qc;
+};
+template <int SCHEME, int LOOP>
+__device__ __forceinline__ void heston_chain_rng_many_body(size_t n, const ManySlices &cs, const ManyJobs &jobs, uint64_t path_offset,
+                                                           double *__restrict__ x_snap, double *__restrict__ q_snap,
+                                                           double *__restrict__ partials)
+{
+    __shared__ RngTablesLds s_tab;
+    __shared__ LogTabEntry s_log[heston_is_qe(SCHEME) ? 512 : 1];
+    RngTables tab;
+    if constexpr (heston_is_qe(SCHEME)) tab = stage_rng_log_tables(s_tab, s_log);
+    else tab = stage_rng_tables(s_tab);
+    const int job = blockIdx.y;
+    const HestonManyConsts *__restrict__ cj = static_cast<const HestonManyConsts *>(jobs.consts) + static_cast<size_t>(job) * cs.m;
+    const size_t p = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    const bool active = p < n;
+    double xv = 0.0, v = uniform_load(jobs.vol0 + job), q = 0.0;
+    const uint64_t seed = uniform_load(jobs.seed + job);
+    const uint32_t c3 = uniform_load(jobs.c3 + job);
+    const PhiloxLane lane = philox_prepare(seed, heston_is_qe(SCHEME) ? (c3 | 4u) : c3, path_offset + p);
+    const PhiloxLane lane_u = philox_prepare(seed, c3 | 5u, path_offset + p);      // QE's uniforms (dead in the other schemes)
+    QeUniforms uc;
+    uint32_t step = 0;
+    for (int i = 0; i < cs.m; ++i) {
+        const int nb = cs.nb_steps[i];
+        if (active) heston_chain_slice<SCHEME, LOOP>(lane, lane_u, uc, step, nb, tab, cj[i].c, cj[i].qc, xv, v, q);
+        step += static_cast<uint32_t>(nb);
+        const size_t row = static_cast<size_t>(job) * cs.m + i;
+        const SliceOut so = {x_snap + row * n, q_snap ? q_snap + row * n : nullptr, partials + 2 * row * ((n + 63) >> 6), cs.forward[i],
+                             (n + 63) >> 6};
+        slice_epilogue(so, p, active, xv, q);
+    }
+}
+
+template <int SCHEME>
+__global__ __launch_bounds__(RNG_BLOCK) void heston_chain_rng_many_kernel(size_t n, ManySlices cs, ManyJobs jobs, uint64_t path_offset,
+                                                                      double *__restrict__ x_snap, double *__restrict__ q_snap,
+                                                                      double *__restrict__ partials)
+{
+    heston_chain_rng_many_body<SCHEME, GEN_LOOP_FULL>(n, cs, jobs, path_offset, x_snap, q_snap, partials);
+}
+
+template <int SCHEME, int LOOP, int WAVES, int TB>
+__global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) void heston_chain_rng_many_lat_kernel(
+    size_t n, ManySlices cs, ManyJobs jobs, uint64_t path_offset, double *__restrict__ x_snap, double *__restrict__ q_snap,
+    double *__restrict__ partials)
+{
+    heston_chain_rng_many_body<SCHEME, LOOP>(n, cs, jobs, path_offset, x_snap, q_snap, partials);
 }
 
 __global__ __launch_bounds__(BLOCK) void heston_w_kernel(double *__restrict__ x, double *__restrict__ var,
@@ -3063,6 +3279,175 @@ int reduce_spot_partials(const void *workspace, size_t n_path, int n_cols, doubl
                        static_cast<const double *>(workspace), wave_rows(n_path), size_t(1), static_cast<size_t>(wave_rows(n_path)),
                        spot_sums);
     return check_launch("reduce_spot_partials");
+}
+
+// ---- many jobs of one chain (svmc_chain.hip's svmc_*_chain_price_many)
+
+// the job table of n_jobs jobs of n_slices expiries: [J][m] constants, [J] start vols, [J] seeds, [J] counter words
+static size_t many_consts_bytes()
+{
+    return sizeof(HestonManyConsts) > sizeof(LogsvFast) ? sizeof(HestonManyConsts) : sizeof(LogsvFast);
+}
+size_t many_table_bytes(int n_jobs, int n_slices)
+{
+    const size_t J = static_cast<size_t>(n_jobs);
+    return J * static_cast<size_t>(n_slices) * many_consts_bytes() + J * (sizeof(double) + sizeof(uint64_t) + sizeof(uint32_t));
+}
+
+// fills the pinned table_host (the table's byte layout, constants of CONSTS each), queues its upload and returns the device view
+template <class Consts, class Fill>
+static ManyJobs many_table(int n_jobs, int n_slices, const uint64_t *seeds, const uint32_t *call_ids, void *table_host, void *table_dev,
+                           hipStream_t stream, Fill &&fill, hipError_t &err)
+{
+    const size_t J = static_cast<size_t>(n_jobs), nc = J * static_cast<size_t>(n_slices);
+    unsigned char *h = static_cast<unsigned char *>(table_host);
+    Consts *consts = reinterpret_cast<Consts *>(h);
+    double *vol0 = reinterpret_cast<double *>(h + nc * sizeof(Consts));
+    uint64_t *seed = reinterpret_cast<uint64_t *>(vol0 + J);
+    uint32_t *c3 = reinterpret_cast<uint32_t *>(seed + J);
+    for (int j = 0; j < n_jobs; ++j) {
+        vol0[j] = fill(j, consts + static_cast<size_t>(j) * n_slices);
+        seed[j] = seeds[j];
+        c3[j] = make_c3(call_ids[j]);
+    }
+    const size_t bytes = reinterpret_cast<unsigned char *>(c3 + J) - h;
+    err = hipMemcpyAsync(table_dev, table_host, bytes, hipMemcpyHostToDevice, stream);
+    const unsigned char *d = static_cast<const unsigned char *>(table_dev);
+    const size_t o_vol = nc * sizeof(Consts), o_seed = o_vol + J * sizeof(double), o_c3 = o_seed + J * sizeof(uint64_t);
+    return ManyJobs{d, reinterpret_cast<const double *>(d + o_vol), reinterpret_cast<const uint64_t *>(d + o_seed),
+                    reinterpret_cast<const uint32_t *>(d + o_c3)};
+}
+
+static ManySlices many_slices(int n_slices, const int *nb_steps_host, const double *forwards_host)
+{
+    ManySlices cs;
+    cs.m = n_slices;
+    for (int i = 0; i < MAX_CHAIN_SLICES; ++i) {
+        cs.forward[i] = forwards_host[i < n_slices ? i : 0];
+        cs.nb_steps[i] = i < n_slices ? nb_steps_host[i] : 0;
+        cs.total_steps += cs.nb_steps[i];
+    }
+    return cs;
+}
+
+static int check_many(const char *fn, size_t n_path, int n_jobs, int n_slices, const int *nb_steps_host, const double *dts_host,
+                      const uint32_t *call_ids)
+{
+    SVMC_REQUIRE(n_path > 0 && n_jobs >= 1 && n_jobs <= MAX_MANY_JOBS && n_slices >= 1 && n_slices <= MAX_CHAIN_SLICES,
+                 std::string(fn) + ": bad sizes");
+    for (int i = 0; i < n_slices; ++i)
+        SVMC_REQUIRE(nb_steps_host[i] > 0 && dts_host[i] > 0.0, std::string(fn) + ": nb_steps and dt must be positive");
+    for (int j = 0; j < n_jobs; ++j) SVMC_REQUIRE(call_ids[j] < (1u << 24), std::string(fn) + ": call_id must fit 24 bits");
+    return SVMC_OK;
+}
+
+int logsv_chain_rng_many(size_t n_path, int n_jobs, int n_slices, const int *nb_steps_host, const double *dts_host,
+                         const double *forwards_host, const double *params_host, int is_spot_measure, const uint64_t *seeds,
+                         const uint32_t *call_ids, uint64_t path_offset, void *table_host, void *table_dev, double *x_snapshots,
+                         double *qvar_snapshots, double *spot_partials, hipStream_t stream)
+{
+    const char *fn = "logsv_chain_rng_many";
+    if (int rc = check_many(fn, n_path, n_jobs, n_slices, nb_steps_host, dts_host, call_ids)) return rc;
+    const size_t row = 6 + static_cast<size_t>(n_slices);       // v0 theta kappa1 kappa2 beta volvol, etas
+    hipError_t e = hipSuccess;
+    const ManyJobs jobs = many_table<LogsvFast>(n_jobs, n_slices, seeds, call_ids, table_host, table_dev, stream,
+                                                [&](int j, LogsvFast *c) {
+        const double *p = params_host + row * static_cast<size_t>(j);
+        for (int i = 0; i < n_slices; ++i)
+            c[i] = logsv_fast_in_log_units(make_logsv_fast(make_logsv_consts(dts_host[i], p[1], p[2], p[3], p[4], p[5], p[6 + i],
+                                                                             is_spot_measure)));
+        return p[0];
+    }, e);
+    SVMC_HIP_TRY(e);
+    const ManySlices cs = many_slices(n_slices, nb_steps_host, forwards_host);
+    const unsigned J = static_cast<unsigned>(n_jobs);
+    // the form is chosen by the launch's TOTAL path count: J jobs of n paths put J n / 64 waves on the device
+    if (few_waves_launch(static_cast<size_t>(n_jobs) * n_path))
+        hipLaunchKernelGGL((logsv_chain_rng_many_lat_kernel<GEN_LOOP_PIPE, 4, FEW_BLOCK>), dim3(lat_grid(n_path), J), dim3(FEW_BLOCK), 0,
+                           stream, n_path, cs, jobs, path_offset, x_snapshots, qvar_snapshots, spot_partials, armed_probe());
+    else
+        hipLaunchKernelGGL(logsv_chain_rng_many_kernel, dim3(chain_grid(n_path), J), dim3(CHAIN_BLOCK), 0, stream, n_path, cs, jobs,
+                           path_offset, x_snapshots, qvar_snapshots, spot_partials, armed_probe());
+    return check_launch(fn);
+}
+
+using HestonManyKernel = void (*)(size_t, ManySlices, ManyJobs, uint64_t, double *, double *, double *);
+#define SVMC_HESTON_MANY_LAT(S, WAVES) heston_chain_rng_many_lat_kernel<S, GEN_LOOP_PAIR, WAVES, FEW_BLOCK>
+static const HestonManyKernel HESTON_MANY_FEW_WAVES_KERNELS[3] = {
+    SVMC_HESTON_MANY_LAT(SVMC_HESTON_EULER_FLOOR, 4), SVMC_HESTON_MANY_LAT(SVMC_HESTON_QE, 3), SVMC_HESTON_MANY_LAT(HESTON_QE_QUAD, 4)};
+#undef SVMC_HESTON_MANY_LAT
+static const HestonManyKernel HESTON_MANY_FULL_KERNELS[3] = {
+    heston_chain_rng_many_kernel<SVMC_HESTON_EULER_FLOOR>, heston_chain_rng_many_kernel<SVMC_HESTON_QE>,
+    heston_chain_rng_many_kernel<HESTON_QE_QUAD>};
+
+int heston_chain_rng_many(size_t n_path, int n_jobs, int n_slices, const int *nb_steps_host, const double *dts_host,
+                          const double *forwards_host, const double *params_host, int scheme, const uint64_t *seeds,
+                          const uint32_t *call_ids, uint64_t path_offset, void *table_host, void *table_dev, double *x_snapshots,
+                          double *qvar_snapshots, double *spot_partials, hipStream_t stream)
+{
+    const char *fn = "heston_chain_rng_many";
+    if (int rc = check_many(fn, n_path, n_jobs, n_slices, nb_steps_host, dts_host, call_ids)) return rc;
+    SVMC_REQUIRE(scheme == SVMC_HESTON_EULER_FLOOR || scheme == SVMC_HESTON_QE, std::string(fn) + ": unknown scheme");
+    // the QE specialisation only if EVERY (job, expiry) of the launch allows it (as heston_chain_rng_impl per launch)
+    bool quad = scheme == SVMC_HESTON_QE;
+    hipError_t e = hipSuccess;
+    const ManyJobs jobs = many_table<HestonManyConsts>(n_jobs, n_slices, seeds, call_ids, table_host, table_dev, stream,
+                                                       [&](int j, HestonManyConsts *c) {
+        const double *p = params_host + 5 * static_cast<size_t>(j);    // v0 theta kappa rho volvol
+        for (int i = 0; i < n_slices; ++i) {
+            c[i].c = make_heston_consts(dts_host[i], p[1], p[2], p[3], p[4]);
+            c[i].qc = make_qe_consts(dts_host[i], p[1], p[2], p[3], p[4]);
+            quad = quad && heston_kernel_scheme(scheme, c[i].qc) == HESTON_QE_QUAD;
+        }
+        return p[0];
+    }, e);
+    SVMC_HIP_TRY(e);
+    const ManySlices cs = many_slices(n_slices, nb_steps_host, forwards_host);
+    const int ks = quad ? HESTON_QE_QUAD : scheme;
+    const bool few = few_waves_launch(static_cast<size_t>(n_jobs) * n_path);
+    const HestonManyKernel k = few ? HESTON_MANY_FEW_WAVES_KERNELS[ks] : HESTON_MANY_FULL_KERNELS[ks];
+    const unsigned block = few ? FEW_BLOCK : RNG_BLOCK;
+    hipLaunchKernelGGL(k, dim3(lat_grid(n_path, block), static_cast<unsigned>(n_jobs)), dim3(block), 0, stream, n_path, cs, jobs,
+                       path_offset, x_snapshots, qvar_snapshots, spot_partials);
+    return check_launch(fn);
+}
+
+// an upper bound of the payoff workspace chain_payoff_and_finish_sets needs for n_sets sets of total_strikes quotes
+size_t payoff_sets_workspace_bytes(size_t n_path, size_t total_strikes, int n_sets)
+{
+    const size_t g = reduce_grid(n_path), a = g * 3 * PAYOFF_KT * PAYOFF_GROUPS, b = g * static_cast<size_t>(n_sets) * 3 * total_strikes;
+    return (a > b ? a : b) * sizeof(double);
+}
+
+// the tail of n_sets jobs whose spot sums are in spot_sums [set][m][2]: ONE payoff launch (blockIdx.z = set, the path blocks of a
+// one-set launch) and ONE chain_finish_kernel over the n_sets x cols quotes -- partials[path block][set][3 cols] are the columns
+// of one [rows][3 n_sets cols] matrix -- into sums_out [set][3 cols]; a launch with more path blocks than that kernel sums takes
+// the column reduce into sums_dev and a copy instead.  The chain must fit one payoff launch (payoff_sets_fit).
+int chain_payoff_and_finish_sets(const double *const *x_snapshots_host, const double *const *qvar_snapshots_host, size_t n_path,
+                                 const double *forwards_host, const double *ttms_host, const double *spot_sums, int n_expiries,
+                                 const double *strikes_host, const int8_t *types_host, const double *shifts_host,
+                                 const size_t *strike_offsets_host, int variable_type, void *workspace, size_t workspace_bytes,
+                                 hipStream_t stream, int n_sets, size_t x_set_stride, size_t q_set_stride, size_t spot_set_stride,
+                                 double *sums_dev, double *sums_out)
+{
+    const char *fn = "chain_payoff_and_finish_sets";
+    PayoffPartialsOut po;
+    if (int rc = payoff_sums_impl(fn, x_snapshots_host, qvar_snapshots_host, n_path, forwards_host, ttms_host, spot_sums, n_expiries,
+                                  strikes_host, types_host, shifts_host, strike_offsets_host, variable_type, nullptr, workspace,
+                                  workspace_bytes, reinterpret_cast<svmc_stream_t>(stream), n_sets,
+                                  PayoffSetStrides{x_set_stride, q_set_stride, spot_set_stride}, nullptr, 0, &po))
+        return rc;
+    if (po.cols == 0) return SVMC_OK;
+    const size_t cols = static_cast<size_t>(po.cols) * static_cast<size_t>(n_sets);
+    if (po.rows <= 4u * BLOCK) {
+        hipLaunchKernelGGL(chain_finish_kernel, dim3(static_cast<unsigned>((cols + BLOCK / 64 - 1) / (BLOCK / 64))), dim3(BLOCK), 0,
+                           stream, static_cast<const double *>(workspace), po.rows, static_cast<int>(cols), sums_out);
+    } else {
+        hipLaunchKernelGGL(reduce_columns_kernel, dim3(static_cast<unsigned>(3 * cols)), dim3(BLOCK), 0, stream,
+                           static_cast<const double *>(workspace), po.rows, 3 * cols, size_t(1), sums_dev);
+        SVMC_HIP_TRY(hipMemcpyAsync(sums_out, sums_dev, 3 * cols * sizeof(double), hipMemcpyDeviceToHost, stream));
+    }
+    return check_launch(fn);
 }
 
 }  // namespace svmc

@@ -356,6 +356,7 @@ def marshalled_chain(ttms, forwards, discfactors, strikes: Sequence[np.ndarray],
     return hit
 
 
+MANY_MAX_JOBS = 64             # jobs per svmc_*_chain_price_many call: SVMC_MANY_MAX_JOBS of include/svmc.h
 BULK_KEEP_FRACTION = 0.125     # of the device's memory: what an engine's cached bulk buffers may hold between calls (trim_bulk)
 
 
@@ -534,6 +535,27 @@ class HipEngine:
             sess, ch["ttms"], ch["forwards"], ch["discfactors"], ch["m"], ch["strikes"], ch["codes"], ch["offsets"], float(v0),
             float(theta), float(kappa), float(rho), float(volvol), int(scheme), int(nb_steps_per_year), int(variable_type),
             int(seed), int(call_id), p, e), "heston_rng_kernel" if ch["m"] == 1 else "heston_chain_rng_kernel")
+
+    def price_chain_many_fused(self, ch: dict, model: str, params: np.ndarray, seeds: Sequence[int], call_ids: Sequence[int],
+                               mode: int, nb_steps_per_year: int, variable_type: int):
+        """J jobs of one chain as ONE svmc_logsv_chain_price_many (model "logsv", mode = is_spot_measure, params [J][6 + m]) or
+        svmc_heston_chain_price_many ("heston", mode = scheme code, params [J][5]) call on this engine's session, J at most
+        MANY_MAX_JOBS: per job the (prices, stderrs) of the single fused call with its (seed, call id), cut into expiries"""
+        params = np.ascontiguousarray(params, dtype=np.float64)
+        n_jobs = params.shape[0]
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
+        ids = np.ascontiguousarray(call_ids, dtype=np.uint32)
+        if not (seeds.size == ids.size == n_jobs):
+            raise ValueError("one seed and one call id per job")
+        sess = self.fused_chain_session(ch["m"], ch["total"])
+        res = np.empty((2, n_jobs, max(ch["total"], 1)))
+        dp = C.POINTER(C.c_double)
+        fn = self.lib.svmc_logsv_chain_price_many if model == "logsv" else self.lib.svmc_heston_chain_price_many
+        _lib.check(fn(sess, ch["ttms"], ch["forwards"], ch["discfactors"], ch["m"], ch["strikes"], ch["codes"], ch["offsets"], n_jobs,
+                      params.ctypes.data_as(dp), seeds.ctypes.data_as(C.POINTER(C.c_uint64)),
+                      ids.ctypes.data_as(C.POINTER(C.c_uint32)), int(mode), int(nb_steps_per_year), int(variable_type),
+                      C.cast(res.ctypes.data, dp), C.cast(res.ctypes.data + res.strides[0], dp)))
+        return [([res[0, j, sl] for sl in ch["slices"]], [res[1, j, sl] for sl in ch["slices"]]) for j in range(n_jobs)]
 
     def price_hawkesjd_chain_fused(self, ch: dict, params: np.ndarray, nb_steps_per_year: int, variable_type: int, seed: int,
                                    call_id: int):

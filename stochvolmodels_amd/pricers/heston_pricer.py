@@ -17,14 +17,14 @@ import numpy as np
 
 from .. import dist as svdist
 from ..data.option_chain import OptionChain
-from ..engine import HESTON_EULER_FLOOR, HESTON_QE, get_engine, marshalled_chain, option_type_codes
+from ..engine import HESTON_EULER_FLOOR, HESTON_QE, MANY_MAX_JOBS, get_engine, marshalled_chain, option_type_codes
 from ..mc_chain import price_chain_on_engine, variable_type_code
 from ..utils.calibration import ImpliedVolObjective, chain_calibration_weights, minimize_slsqp
 from ..utils.config import VariableType
 from ..utils.funcs import next_rng_call, set_time_grid, time_grid_steps, timer
 from ..analytic import AnalyticGrid, qvar_prices_from_sums, vanilla_prices_from_capped
 from ..utils import mgf_pricer as mgfp
-from .logsv_pricer import _broadcast_state
+from .logsv_pricer import _broadcast_state, check_many_args, many_job_streams
 from .model_pricer import ModelParams, ModelPricer
 
 
@@ -76,6 +76,18 @@ class HestonPricer(ModelPricer):
                                       nb_steps_per_year=kwargs.get("nb_steps_per_year", 360),
                                       seed=kwargs.get("seed"), comm=kwargs.get("comm"), devices=kwargs.get("devices"),
                                       reduce=kwargs.get("reduce"))
+
+    def model_mc_price_chain_many(self, option_chain: OptionChain, params_list: Sequence[HestonParams], nb_path: int = 100000,
+                                  variable_type: VariableType = VariableType.LOG_RETURN, seeds: Optional[Sequence[int]] = None,
+                                  **kwargs) -> List[Tuple[List[np.ndarray], List[np.ndarray]]]:
+        """model_mc_price_chain for several parameter sets, each with its own stream (heston_mc_chain_pricer_many): job j
+        returns what model_mc_price_chain(option_chain, params_list[j], seed=seeds[j], ...) returns"""
+        return heston_mc_chain_pricer_many(params_list=params_list, ttms=option_chain.ttms, forwards=option_chain.forwards,
+                                           discfactors=option_chain.discfactors, strikes_ttms=option_chain.strikes_ttms,
+                                           optiontypes_ttms=option_chain.optiontypes_ttms, nb_path=nb_path,
+                                           variable_type=variable_type, scheme=kwargs.get("scheme", "euler"),
+                                           nb_steps_per_year=kwargs.get("nb_steps_per_year", 360), seeds=seeds,
+                                           comm=kwargs.get("comm"), devices=kwargs.get("devices"))
 
     @timer
     def calibrate_model_params_to_chain(self, option_chain: OptionChain, params0: HestonParams = None,
@@ -172,6 +184,42 @@ def heston_chain_pricer(v0: float, theta: float, kappa: float, volvol: float, rh
         return prices
     finally:
         grid.release()
+
+
+def heston_mc_chain_pricer_many(params_list: Sequence[HestonParams], ttms: np.ndarray, forwards: np.ndarray,
+                                discfactors: np.ndarray, strikes_ttms: Sequence[np.ndarray],
+                                optiontypes_ttms: Sequence[np.ndarray], nb_path: int = 100000,
+                                variable_type: VariableType = VariableType.LOG_RETURN, scheme="euler",
+                                nb_steps_per_year: int = 360, seeds: Optional[Sequence[int]] = None, comm=None, devices=None
+                                ) -> List[Tuple[List[np.ndarray], List[np.ndarray]]]:
+    """heston_mc_chain_pricer for several independent jobs of ONE chain, as logsv_mc_chain_pricer_many: job j has the
+    parameters params_list[j] and the stream seeds[j] (or the next call id, in list order, with seeds=None), and returns
+    what heston_mc_chain_pricer(..., seed=seeds[j]) returns, bit for bit.  On one GPU up to MANY_MAX_JOBS jobs per
+    svmc_heston_chain_price_many call; with comm.world > 1, devices= or more than 16 expiries a loop of single calls."""
+    params_list = check_many_args(params_list, seeds)
+    code = _scheme_code(scheme)
+    if not params_list:
+        return []
+    comm = comm or svdist.get_default_comm()
+    if devices is not None or comm.world > 1 or len(ttms) > 16 or not (FUSED_MC_CHAIN_DRIVER and WHOLE_CHAIN_STEPPING):
+        # a loop of single calls (a sharded batch is out of scope): each takes its own stream, unseeded ones in list order
+        return [heston_mc_chain_pricer(ttms=ttms, forwards=forwards, discfactors=discfactors, strikes_ttms=strikes_ttms,
+                                       optiontypes_ttms=optiontypes_ttms, v0=p.v0, theta=p.theta, kappa=p.kappa, rho=p.rho,
+                                       volvol=p.volvol, nb_path=nb_path, variable_type=variable_type, scheme=scheme,
+                                       nb_steps_per_year=nb_steps_per_year, seed=None if seeds is None else seeds[j],
+                                       comm=comm, devices=devices)
+                for j, p in enumerate(params_list)]
+    streams = many_job_streams(len(params_list), seeds)
+    rows = np.array([(p.v0, p.theta, p.kappa, p.rho, p.volvol) for p in params_list], dtype=np.float64)
+    ch = marshalled_chain(ttms, forwards, discfactors, strikes_ttms, [option_type_codes(t) for t in optiontypes_ttms])
+    eng = get_engine(nb_path)
+    out = []
+    for q0 in range(0, len(rows), MANY_MAX_JOBS):
+        part = streams[q0:q0 + MANY_MAX_JOBS]
+        out += eng.price_chain_many_fused(ch, "heston", rows[q0:q0 + MANY_MAX_JOBS], [s for s, _ in part], [c for _, c in part],
+                                          code, nb_steps_per_year, variable_type_code(variable_type))
+    return [([a.reshape(np.shape(k)) for a, k in zip(pr, strikes_ttms)], [a.reshape(np.shape(k)) for a, k in zip(se, strikes_ttms)])
+            for pr, se in out]
 
 
 def simulate_heston_x_vol_terminal(ttm: float, x0: np.ndarray, var0: np.ndarray, qvar0: np.ndarray, theta: float,

@@ -19,7 +19,7 @@ import pandas as pd
 
 from .. import dist as svdist
 from ..data.option_chain import OptionChain
-from ..engine import DeviceRandoms, get_engine, marshalled_chain, option_type_codes, payoff_finalize
+from ..engine import MANY_MAX_JOBS, DeviceRandoms, get_engine, marshalled_chain, option_type_codes, payoff_finalize
 from ..mc_chain import price_chain_on_engine, variable_type_code
 from ..utils.calibration import ImpliedVolObjective, chain_calibration_weights, minimize_slsqp
 from ..utils.config import VariableType
@@ -240,6 +240,22 @@ class LogSVPricer(ModelPricer):
                                      nb_steps_per_year=nb_steps or int(360 * np.max(option_chain.ttms)) + 1,
                                      seed=kwargs.get("seed"), comm=kwargs.get("comm"), devices=kwargs.get("devices"),
                                      reduce=kwargs.get("reduce"))
+
+    def model_mc_price_chain_many(self, option_chain: OptionChain, params_list: Sequence[LogSvParams],
+                                  is_spot_measure: bool = True, variable_type: VariableType = VariableType.LOG_RETURN,
+                                  nb_path: int = 100000, nb_steps: Optional[int] = None,
+                                  seeds: Optional[Sequence[int]] = None, **kwargs
+                                  ) -> List[Tuple[List[np.ndarray], List[np.ndarray]]]:
+        """model_mc_price_chain for several parameter sets, each with its own stream (logsv_mc_chain_pricer_many), on
+        model_mc_price_chain's step rule: job j returns what model_mc_price_chain(option_chain, params_list[j],
+        seed=seeds[j], ...) returns"""
+        return logsv_mc_chain_pricer_many(params_list=params_list, ttms=option_chain.ttms, forwards=option_chain.forwards,
+                                          discfactors=option_chain.discfactors, strikes_ttms=option_chain.strikes_ttms,
+                                          optiontypes_ttms=option_chain.optiontypes_ttms, is_spot_measure=is_spot_measure,
+                                          nb_path=nb_path,
+                                          nb_steps_per_year=nb_steps or int(360 * np.max(option_chain.ttms)) + 1,
+                                          variable_type=variable_type, seeds=seeds, comm=kwargs.get("comm"),
+                                          devices=kwargs.get("devices"))
 
     def set_vol_scaler(self, option_chain: OptionChain) -> float:
         """transform-grid scaler from the chain's first ATM vol, held fixed over a calibration (reference :429-438)"""
@@ -585,6 +601,63 @@ def logsv_mc_chain_pricer(ttms: np.ndarray, forwards: np.ndarray, discfactors: n
     return _logsv_mc_chain_on_grids(grids, rng_seed, call_id, comm, ttms, forwards, discfactors, strikes_ttms, optiontypes_ttms,
                                     v0, theta, kappa1, kappa2, beta, volvol, vol_backbone_etas, is_spot_measure, nb_path,
                                     variable_type)
+
+
+def many_job_streams(n_params: int, seeds: Optional[Sequence[int]]) -> List[Tuple[int, int]]:
+    """the (seed, call id) of each job of a many-job call: seeds given -> (seed_j, 0); seeds None -> the process seed and
+    n_params consecutive call ids, in list order -- what as many single calls would take"""
+    return [next_rng_call(None if seeds is None else seeds[j]) for j in range(n_params)]
+
+
+def check_many_args(params_list, seeds) -> list:
+    """the checks of a many-job call, made before any device work"""
+    params_list = list(params_list)
+    if seeds is not None and len(seeds) != len(params_list):
+        raise ValueError(f"seeds has {len(seeds)} entries for {len(params_list)} parameter sets")
+    return params_list
+
+
+def logsv_mc_chain_pricer_many(params_list: Sequence[LogSvParams], ttms: np.ndarray, forwards: np.ndarray,
+                               discfactors: np.ndarray, strikes_ttms: Sequence[np.ndarray],
+                               optiontypes_ttms: Sequence[np.ndarray], is_spot_measure: bool = True, nb_path: int = 100000,
+                               nb_steps_per_year: int = 360, variable_type: VariableType = VariableType.LOG_RETURN,
+                               seeds: Optional[Sequence[int]] = None, comm=None, devices=None
+                               ) -> List[Tuple[List[np.ndarray], List[np.ndarray]]]:
+    """logsv_mc_chain_pricer for several independent jobs of ONE chain: job j has the parameters params_list[j] (with their
+    vol-backbone etas) and its own random stream -- seeds[j] (call id 0), or with seeds=None the process seed and the next call
+    id, taken in list order.  Returns [(prices, stderrs)] per job, each BIT-EQUAL to logsv_mc_chain_pricer(..., seed=seeds[j])
+    (or to the j-th of as many consecutive unseeded calls).  On one GPU up to MANY_MAX_JOBS jobs are stepped by ONE launch
+    (svmc_logsv_chain_price_many; longer lists in several calls, in order); with comm.world > 1, devices=, or more than 16
+    expiries it is a loop of single calls -- the same numbers.  Not in the reference API."""
+    params_list = check_many_args(params_list, seeds)
+    if not params_list:
+        return []
+    comm = comm or svdist.get_default_comm()
+    m = len(ttms)
+    etas = [p.get_vol_backbone_etas(ttms=np.asarray(ttms, dtype=float)) for p in params_list]
+    if devices is not None or comm.world > 1 or m > 16 or not (FUSED_MC_CHAIN_DRIVER and WHOLE_CHAIN_STEPPING):
+        # a loop of single calls (a sharded batch is out of scope): each takes its own stream, unseeded ones in list order
+        return [logsv_mc_chain_pricer(ttms=ttms, forwards=forwards, discfactors=discfactors, strikes_ttms=strikes_ttms,
+                                      optiontypes_ttms=optiontypes_ttms, v0=p.sigma0, theta=p.theta, kappa1=p.kappa1,
+                                      kappa2=p.kappa2, beta=p.beta, volvol=p.volvol, vol_backbone_etas=e,
+                                      is_spot_measure=is_spot_measure, nb_path=nb_path, nb_steps_per_year=nb_steps_per_year,
+                                      variable_type=variable_type, seed=None if seeds is None else seeds[j], comm=comm,
+                                      devices=devices)
+                for j, (p, e) in enumerate(zip(params_list, etas))]
+    streams = many_job_streams(len(params_list), seeds)
+    rows = np.ones((len(params_list), 6 + m))
+    for row, p in zip(rows, params_list):
+        row[:6] = (p.sigma0, p.theta, p.kappa1, p.kappa2, p.beta, p.volvol)
+    rows[:, 6:] = np.reshape(etas, (len(params_list), m))
+    ch = marshalled_chain(ttms, forwards, discfactors, strikes_ttms, [option_type_codes(t) for t in optiontypes_ttms])
+    eng = get_engine(nb_path)
+    out = []
+    for q0 in range(0, len(rows), MANY_MAX_JOBS):
+        part = streams[q0:q0 + MANY_MAX_JOBS]
+        out += eng.price_chain_many_fused(ch, "logsv", rows[q0:q0 + MANY_MAX_JOBS], [s for s, _ in part], [c for _, c in part],
+                                          int(bool(is_spot_measure)), nb_steps_per_year, variable_type_code(variable_type))
+    return [([_shaped_like(a, k) for a, k in zip(pr, strikes_ttms)], [_shaped_like(a, k) for a, k in zip(se, strikes_ttms)])
+            for pr, se in out]
 
 
 def _logsv_mc_chain_on_grids(grids, rng_seed: int, call_id: int, comm, ttms, forwards, discfactors, strikes_ttms,
