@@ -31,7 +31,8 @@ namespace svmc {
 // The row form below wins on latency (a lone wave per SIMD, a third of the instructions per step) and loses on volume: it
 // spends 16 lanes per point.  The 40 000-point psi grid of the quadratic-variance transform fills the chip either way --
 // 625 waves one lane per point, 10 000 waves in rows -- and is then bound by total instruction issue, where a point costs
-// 1850 instructions per step here against 16 x 800 / 5 useful in rows.  svmc_logsv_mgf_grid_batch picks by grid length.
+// 1850 instructions per step here against 16 x 800 / 5 useful in rows.  svmc_logsv_mgf_grid_batch picks by grid length
+// (one set's, so that a batch of sets takes the form each set would take on its own).
 // A' = A^T M^(k) A + L^(k) A + H^(k): the non-zero entries of :146-182 written out
 __device__ __forceinline__ void ode_rhs(const OdeConsts &c, cd phi, cd psi, const cd (&A)[5], cd (&out)[5])
 {
@@ -580,9 +581,11 @@ int svmc_logsv_mgf_grid_batch(const double *phi, const double *psi, size_t n_gri
             sets.y0[i] = p[0] - p[1];
         }
         const size_t off = static_cast<size_t>(s0) * n_grid;
-        // rows while the launch stays within two waves per SIMD (8192 points at one set), lanes beyond: see above
+        // rows while ONE set's grid stays within two waves per SIMD (8192 points), lanes beyond: see above.  The form follows
+        // the grid length alone, never the number of sets sharing the launch: the two forms round differently (ode_rhs against
+        // the rows of ode_rhs_lane), and a set's coefficients must be the same bits in a batch of any size as in a call of its own
         static const size_t row_max = getenv("SVMC_MGF_ROW_MAX_POINTS") ? strtoull(getenv("SVMC_MGF_ROW_MAX_POINTS"), nullptr, 10) : 8192;
-        if (n_grid * static_cast<size_t>(m) <= row_max)
+        if (n_grid <= row_max)
             hipLaunchKernelGGL(logsv_mgf_grid_kernel,
                                dim3(static_cast<unsigned>((n_grid + ODE_POINTS_PER_BLOCK - 1) / ODE_POINTS_PER_BLOCK), static_cast<unsigned>(m)),
                                dim3(AB), 0, as_stream(stream), reinterpret_cast<const cd *>(phi) + off,
