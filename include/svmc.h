@@ -664,6 +664,34 @@ SVMC_API int svmc_mgf_gamma_slice_batch(const double *phi, const double *log_mgf
                                         const double *gamma_forwards, int expiry, double forward, const double *strikes_host,
                                         const int *type_codes_host, size_t n_strikes, double *prices, svmc_stream_t stream);
 
+/* ---- densities, digital options, histograms (src svmc_density.hip) ---------------------------------------
+ * The weights w are the legacy pricer weights of utils/mgf_pricer.py:157-171: Simpson 1,4,2,... with every odd index 4 (even-
+ * length grids included), or with is_simpson = 0 half the first step on the first point and p_j - p_(j-1) on the others.  NaN
+ * terms are dropped (nansum).  Batched like svmc_mgf_vanilla_slice_batch; a set of a batch is bit-equal to the set alone.
+ *   svmc_mgf_pdf_slice_batch      pdf_with_mgf_grid (utils/mgf_pricer.py:361-384) for n_sets sets: var_grid, log_mgf device
+ *                                 [n_sets][n_grid] complex (each set its own transform grid), space device [n_sets][n_space]
+ *                                 (each set its own space grid, n_space >= 2), shifts_host / scales_host [n_sets];
+ *                                 pdf[s][i] = (space[s][1] - space[s][0]) nansum_j Re[ (w_j / pi) exp(z u_j + log_mgf_j) ],
+ *                                 z = (space[s][i] - shift[s]) / scale[s]; pdf: device [n_sets][n_space].
+ *   svmc_mgf_digital_slice_batch  the strike sums of digital_slice_pricer_with_mgf_grid (:224-269): sums[s][k] = nansum_j
+ *                                 Re[ p_j exp(-ln(F/K_k) phi_j + log_mgf_j) ], p_j = -(w_j / pi) / phi_j with negative_contour
+ *                                 != 0 (every Re phi < 0: the sums are digital calls) and +(w_j / pi) / phi_j otherwise (puts);
+ *                                 the complement 1 - sum for the other type and the discount factor are host code.  forward and
+ *                                 strikes must be positive and finite.  sums: device [n_sets][n_strikes].
+ *   svmc_histogram_uniform        np.histogram(values / divisor, bins = n_bins, range = (edges[0], edges[n_bins])) as integer
+ *                                 counts: values outside the range and NaNs are dropped, the last bin owns its right edge, and
+ *                                 the index is corrected against edges (device, n_bins + 1 doubles: the host's linspace) as NumPy
+ *                                 corrects it, so the counts EQUAL NumPy's.  counts: device uint64 [n_bins], zeroed by the call;
+ *                                 1 <= n_bins <= 8192; divisor 1 leaves the values as they are. */
+SVMC_API int svmc_mgf_pdf_slice_batch(const double *var_grid, const double *log_mgf, size_t n_grid, int n_sets,
+                                      const double *space, size_t n_space, const double *shifts_host, const double *scales_host,
+                                      int is_simpson, double *pdf, svmc_stream_t stream);
+SVMC_API int svmc_mgf_digital_slice_batch(const double *phi, const double *log_mgf, size_t n_grid, int n_sets, double forward,
+                                          const double *strikes_host, size_t n_strikes, int negative_contour, int is_simpson,
+                                          double *sums, svmc_stream_t stream);
+SVMC_API int svmc_histogram_uniform(const double *values, size_t n, double divisor, const double *edges, int n_bins,
+                                    uint64_t *counts, svmc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -64,6 +64,10 @@ _EXPORTS = {
     "fit_model_vol_backbone_to_varswaps": "pricers.logsv.vol_moments_ode",
     "compute_var_swap_strike": "utils.var_swap_pricer",
     "HawkesJDParams": "pricers.hawkes_jd_pricer", "HawkesJDPricer": "pricers.hawkes_jd_pricer",
+    "logsv_pdfs": "pricers.logsv_pricer", "logsv_pdfs_batch": "pricers.logsv_pricer",
+    "get_init_conditions_a": "pricers.logsv.affine_expansion",
+    "pdf_with_mgf_grid": "utils.mgf_pricer", "digital_slice_pricer_with_mgf_grid": "utils.mgf_pricer",
+    "compute_histogram_data": "utils.funcs",
 }
 
 __all__ = sorted(_EXPORTS)

@@ -102,6 +102,7 @@ class AnalyticGrid(_Pooled):
         _lib.check(self.lib.svmc_memset(self.a.ptr, 0, self.a.nbytes, None))
         _lib.check(self.lib.svmc_memset(self.b.ptr, 0, self.b.nbytes, None))
         self._capped: Optional[DeviceBuffer] = None
+        self._var: Optional[DeviceBuffer] = None             # a transform variable other than phi / psi (pdf_sums)
 
     def _up(self, z: np.ndarray) -> DeviceBuffer:
         buf = DeviceBuffer(2 * z.size)
@@ -186,6 +187,48 @@ class AnalyticGrid(_Pooled):
         self.last_given_up = int(np.count_nonzero(np.isnan(lm.real) | np.isnan(lm.imag)))
         return out
 
+    def _var_ptr(self, var_grid: np.ndarray, resident: Optional[str]) -> int:
+        """the device copy of the transform variable an inversion runs over: the resident phi or psi buffer when the caller
+        names it, else `var_grid` uploaded into a buffer the grid keeps (the theta grid of the volatility)"""
+        if resident == "phi":
+            return self.phi.ptr
+        if resident == "psi":
+            return self.psi.ptr
+        if self._var is None or self._var.n < 2 * var_grid.size:
+            if self._var is not None:
+                self._var.free()
+            self._var = DeviceBuffer(2 * var_grid.size)
+        _lib.check(self.lib.svmc_memcpy_h2d(self._var.ptr, var_grid.ctypes.data, var_grid.nbytes, None))
+        return self._var.ptr
+
+    def pdf_sums(self, var_grid: np.ndarray, space_grid: np.ndarray, shift: float = 0.0, scale: float = 1.0,
+                 is_simpson: bool = True, resident: Optional[str] = None) -> np.ndarray:
+        """pdf_with_mgf_grid (reference utils/mgf_pricer.py:361-384) from the log-MGF resident on the device
+        (svmc_mgf_pdf_slice_batch at one set).  `var_grid` is the transform variable the density is inverted over;
+        resident="phi" / "psi" says it IS the grid's phi / psi buffer, otherwise it is uploaded (the theta grid of the
+        volatility).  The space grid and the masses go through the grid's pooled result buffer.  In the same wait the log-MGF
+        comes back and self.last_given_up is counted (download_results)."""
+        var_grid = np.ascontiguousarray(var_grid, dtype=np.complex128).ravel()
+        space = np.ascontiguousarray(space_grid, dtype=np.float64).ravel()
+        assert var_grid.size == self.n
+        k = space.size
+        self.reserve_results(2 * k)                                    # [space | masses]
+        var_ptr = self._var_ptr(var_grid, resident)
+        _lib.check(self.lib.svmc_memcpy_h2d(self._capped.ptr, space.ctypes.data, space.nbytes, None))
+        pf = C.POINTER(C.c_double)
+        sh, sc = np.array([float(shift)]), np.array([float(scale)])
+        _lib.check(self.lib.svmc_mgf_pdf_slice_batch(var_ptr, self.log_mgf.ptr, self.n, 1, self._capped.ptr, k,
+                                                     sh.ctypes.data_as(pf), sc.ctypes.data_as(pf), int(bool(is_simpson)),
+                                                     self._capped.offset(k), None))
+        out = np.empty(k)
+        lm = np.empty(self.n, dtype=np.complex128)
+        if k:
+            _lib.check(self.lib.svmc_memcpy_d2h(out.ctypes.data, self._capped.offset(k), out.nbytes, None))
+        _lib.check(self.lib.svmc_memcpy_d2h(lm.ctypes.data, self.log_mgf.ptr, lm.nbytes, None))
+        _lib.check(self.lib.svmc_stream_synchronize(None))
+        self.last_given_up = int(np.count_nonzero(np.isnan(lm.real) | np.isnan(lm.imag)))
+        return out
+
     def qvar_sums(self, ttm: float, strikes: np.ndarray) -> np.ndarray:
         strikes = np.ascontiguousarray(strikes, dtype=np.float64)
         k = strikes.size
@@ -199,7 +242,7 @@ class AnalyticGrid(_Pooled):
         return out
 
     def close(self) -> None:
-        for b in (self.phi, self.psi, self.a, self.b, self.log_mgf, self._capped):
+        for b in (self.phi, self.psi, self.a, self.b, self.log_mgf, self._capped, self._var):
             if b is not None:
                 b.free()
 
@@ -244,6 +287,7 @@ class AnalyticGridBatch(_Pooled):
         _lib.check(self.lib.svmc_memset(self.a.ptr, 0, self.a.nbytes, None))
         self._capped: Optional[DeviceBuffer] = None
         self._risk: Optional[DeviceBuffer] = None            # normalizers then gamma forwards, [n_ttms][n_sets] each
+        self._var: Optional[DeviceBuffer] = None             # a transform variable other than phi / psi (pdf_sums)
         self._risk_ttms = 0
 
     def logsv_advance(self, ttm: float, params_rows: np.ndarray, is_spot_measure: bool, expansion_order: int,
@@ -330,6 +374,38 @@ class AnalyticGridBatch(_Pooled):
         _lib.check(self.lib.svmc_stream_synchronize(None))
         return out
 
+    def set_a(self, a_t0: np.ndarray) -> None:
+        """A(0) of every set, [n_sets][n_grid][n_coef] (zeros after acquire(); -Theta in the 2nd slot for the volatility)"""
+        a_t0 = np.ascontiguousarray(a_t0, dtype=np.complex128)
+        assert a_t0.shape == (self.n_sets, self.n, self.n_coef)
+        _lib.check(self.lib.svmc_memcpy_h2d(self.a.ptr, a_t0.ctypes.data, a_t0.nbytes, None))
+        _lib.check(self.lib.svmc_stream_synchronize(None))
+
+    def pdf_sums(self, var_grids: Sequence[np.ndarray], space_grids: Sequence[np.ndarray], shifts: Sequence[float],
+                 scales: Sequence[float], is_simpson: bool = True, resident: Optional[str] = None) -> np.ndarray:
+        """AnalyticGrid.pdf_sums for every set in ONE launch -> [n_sets][n_space]; each set has its own transform grid, space
+        grid (of one common length), shift and scale.  self.last_given_up is counted per set in the same wait."""
+        var = np.ascontiguousarray(np.stack([np.asarray(v, dtype=np.complex128).ravel() for v in var_grids]))
+        space = np.ascontiguousarray(np.stack([np.asarray(s, dtype=np.float64).ravel() for s in space_grids]))
+        sh, sc = np.ascontiguousarray(shifts, dtype=np.float64), np.ascontiguousarray(scales, dtype=np.float64)
+        assert var.shape == (self.n_sets, self.n) and space.shape[0] == self.n_sets and sh.shape == sc.shape == (self.n_sets,)
+        k = space.size
+        self.reserve_results(2 * k)                                    # [spaces | masses]
+        var_ptr = AnalyticGrid._var_ptr(self, var, resident)
+        _lib.check(self.lib.svmc_memcpy_h2d(self._capped.ptr, space.ctypes.data, space.nbytes, None))
+        pf = C.POINTER(C.c_double)
+        _lib.check(self.lib.svmc_mgf_pdf_slice_batch(var_ptr, self.log_mgf.ptr, self.n, self.n_sets, self._capped.ptr,
+                                                     space.shape[1], sh.ctypes.data_as(pf), sc.ctypes.data_as(pf),
+                                                     int(bool(is_simpson)), self._capped.offset(k), None))
+        out = np.empty(space.shape)
+        lm = np.empty((self.n_sets, self.n), dtype=np.complex128)
+        if k:
+            _lib.check(self.lib.svmc_memcpy_d2h(out.ctypes.data, self._capped.offset(k), out.nbytes, None))
+        _lib.check(self.lib.svmc_memcpy_d2h(lm.ctypes.data, self.log_mgf.ptr, lm.nbytes, None))
+        _lib.check(self.lib.svmc_stream_synchronize(None))
+        self.last_given_up = np.count_nonzero(np.isnan(lm.real) | np.isnan(lm.imag), axis=1).astype(int)
+        return out
+
     def reserve_results(self, n_doubles: int) -> None:
         if self._capped is None or self._capped.n < n_doubles:
             if self._capped is not None:
@@ -354,7 +430,7 @@ class AnalyticGridBatch(_Pooled):
         return out
 
     def close(self) -> None:
-        for b in (self.phi, self.psi, self.a, self.log_mgf, self._capped, self._risk):
+        for b in (self.phi, self.psi, self.a, self.log_mgf, self._capped, self._risk, self._var):
             if b is not None:
                 b.free()
 
@@ -383,6 +459,111 @@ def gamma_slice_prices(phi: np.ndarray, log_mgf: np.ndarray, gamma: float, short
         _lib.check(lib.svmc_memcpy_d2h(out.ctypes.data, bufs[3].ptr, out.nbytes, None))
         _lib.check(lib.svmc_stream_synchronize(None))
         return out
+    finally:
+        for b in bufs:
+            b.free()
+
+
+def pdf_slices(var_grids: np.ndarray, log_mgfs: np.ndarray, space_grids: np.ndarray, shifts, scales,
+               is_simpson: bool = True) -> np.ndarray:
+    """pdf_with_mgf_grid for [n_sets] given log-MGFs in one launch (svmc_mgf_pdf_slice_batch): var_grids, log_mgfs
+    [n_sets][n_grid] complex, space_grids [n_sets][n_space], shifts / scales [n_sets] -> [n_sets][n_space].  Uploads its
+    inputs; the pricers keep the log-MGF on the device instead (AnalyticGrid.pdf_sums)."""
+    lib = _lib.load()
+    var = np.ascontiguousarray(var_grids, dtype=np.complex128)
+    lm = np.ascontiguousarray(log_mgfs, dtype=np.complex128)
+    space = np.ascontiguousarray(space_grids, dtype=np.float64)
+    sh, sc = np.ascontiguousarray(shifts, dtype=np.float64), np.ascontiguousarray(scales, dtype=np.float64)
+    if not (var.ndim == 2 and var.shape == lm.shape and space.ndim == 2 and space.shape[0] == var.shape[0]
+            and sh.shape == sc.shape == (var.shape[0],)):
+        raise ValueError("pdf_slices: var_grids / log_mgfs [n_sets][n_grid], space_grids [n_sets][n_space], shifts / scales [n_sets]")
+    bufs = [DeviceBuffer(2 * var.size), DeviceBuffer(2 * lm.size), DeviceBuffer(max(space.size, 1)), DeviceBuffer(max(space.size, 1))]
+    try:
+        for buf, z in zip(bufs[:3], (var, lm, space)):
+            _lib.check(lib.svmc_memcpy_h2d(buf.ptr, z.ctypes.data, z.nbytes, None))
+        pf = C.POINTER(C.c_double)
+        _lib.check(lib.svmc_mgf_pdf_slice_batch(bufs[0].ptr, bufs[1].ptr, var.shape[1], var.shape[0], bufs[2].ptr, space.shape[1],
+                                                sh.ctypes.data_as(pf), sc.ctypes.data_as(pf), int(bool(is_simpson)), bufs[3].ptr,
+                                                None))
+        out = np.empty(space.shape)
+        if out.size:
+            _lib.check(lib.svmc_memcpy_d2h(out.ctypes.data, bufs[3].ptr, out.nbytes, None))
+        _lib.check(lib.svmc_stream_synchronize(None))
+        return out
+    finally:
+        for b in bufs:
+            b.free()
+
+
+def digital_slice_sums(phis: np.ndarray, log_mgfs: np.ndarray, forward: float, strikes: np.ndarray, negative_contour: bool,
+                       is_simpson: bool = True) -> np.ndarray:
+    """the strike sums of digital_slice_pricer_with_mgf_grid for [n_sets] given log-MGFs in one launch
+    (svmc_mgf_digital_slice_batch) -> [n_sets][n_strikes]"""
+    lib = _lib.load()
+    phi = np.ascontiguousarray(phis, dtype=np.complex128)
+    lm = np.ascontiguousarray(log_mgfs, dtype=np.complex128)
+    strikes = np.ascontiguousarray(strikes, dtype=np.float64).ravel()
+    if not (phi.ndim == 2 and phi.shape == lm.shape):
+        raise ValueError("digital_slice_sums: phis / log_mgfs [n_sets][n_grid]")
+    bufs = [DeviceBuffer(2 * phi.size), DeviceBuffer(2 * lm.size), DeviceBuffer(max(strikes.size * phi.shape[0], 1))]
+    try:
+        for buf, z in zip(bufs[:2], (phi, lm)):
+            _lib.check(lib.svmc_memcpy_h2d(buf.ptr, z.ctypes.data, z.nbytes, None))
+        _lib.check(lib.svmc_mgf_digital_slice_batch(bufs[0].ptr, bufs[1].ptr, phi.shape[1], phi.shape[0], float(forward),
+                                                    strikes.ctypes.data_as(C.POINTER(C.c_double)), strikes.size,
+                                                    int(bool(negative_contour)), int(bool(is_simpson)), bufs[2].ptr, None))
+        out = np.empty((phi.shape[0], strikes.size))
+        if out.size:
+            _lib.check(lib.svmc_memcpy_d2h(out.ctypes.data, bufs[2].ptr, out.nbytes, None))
+        _lib.check(lib.svmc_stream_synchronize(None))
+        return out
+    finally:
+        for b in bufs:
+            b.free()
+
+
+def digital_prices_from_sums(sums: np.ndarray, optiontypes: Sequence, discfactor: float, is_all_calls: bool) -> np.ndarray:
+    """the payoff algebra of digital_slice_pricer_with_mgf_grid, reference utils/mgf_pricer.py:254-267"""
+    prices = np.zeros(len(sums))
+    for idx, (s, type_) in enumerate(zip(sums, optiontypes)):
+        type_ = str(type_)
+        if type_ == "C":
+            price = s if is_all_calls else 1.0 - s
+        elif type_ == "P":
+            price = 1.0 - s if is_all_calls else s
+        else:
+            raise ValueError("not implemented")
+        prices[idx] = discfactor * price
+    return prices
+
+
+def histogram_edges(lo: float, hi: float, n_bins: int) -> np.ndarray:
+    """the bin edges np.histogram(a, bins=n_bins, range=(lo, hi)) itself forms (its checks and its widening of lo == hi included)"""
+    return np.ascontiguousarray(np.histogram_bin_edges(np.empty(0), bins=int(n_bins), range=(float(lo), float(hi))),
+                                dtype=np.float64)
+
+
+def device_histograms(value_ptrs: Sequence[int], n: int, edges_list: Sequence[np.ndarray], divisors: Sequence[float],
+                      stream=None) -> list:
+    """np.histogram counts of several device vectors of `n` doubles (svmc_histogram_uniform), one launch per vector and ONE
+    download of all the counts: [int64 counts [len(edges) - 1]] per vector, equal to np.histogram(values / divisor,
+    bins=len(edges) - 1, range=(edges[0], edges[-1]))[0] of the downloaded values"""
+    lib = _lib.load()
+    edges_list = [np.ascontiguousarray(e, dtype=np.float64) for e in edges_list]
+    n_edges = [e.size for e in edges_list]
+    eoff = np.concatenate([[0], np.cumsum(n_edges)]).astype(int)
+    coff = np.concatenate([[0], np.cumsum([m - 1 for m in n_edges])]).astype(int)
+    all_edges = np.concatenate(edges_list)
+    bufs = [DeviceBuffer(all_edges.size), DeviceBuffer(max(int(coff[-1]), 1))]           # counts: uint64, 8 bytes each
+    try:
+        _lib.check(lib.svmc_memcpy_h2d(bufs[0].ptr, all_edges.ctypes.data, all_edges.nbytes, stream))
+        for i, (ptr, div) in enumerate(zip(value_ptrs, divisors)):
+            _lib.check(lib.svmc_histogram_uniform(ptr, int(n), float(div), bufs[0].offset(eoff[i]), n_edges[i] - 1,
+                                                  bufs[1].offset(coff[i]), stream))
+        counts = np.empty(int(coff[-1]), dtype=np.uint64)
+        _lib.check(lib.svmc_memcpy_d2h(counts.ctypes.data, bufs[1].ptr, counts.nbytes, stream))
+        _lib.check(lib.svmc_stream_synchronize(stream))
+        return [counts[coff[i]:coff[i + 1]].astype(np.int64) for i in range(len(edges_list))]
     finally:
         for b in bufs:
             b.free()

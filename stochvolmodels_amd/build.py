@@ -28,7 +28,7 @@ ISA_JSON = os.path.join(PKG, "libsvmc.isa.json")
 ISA_KERNELS = ("logsv_rng_kernel", "logsv_chain_rng_kernel", "heston_rng_kernelILi0", "heston_rng_kernelILi1", "heston_rng_kernelILi2",
                "logsv_rng_lat_kernelILi4ELi4ELi256", "logsv_chain_rng_lat_kernelILi4ELi4ELi256", "hawkesjd_chain_rng_kernel")
 SOURCES = ("svmc_runtime.hip", "svmc_kernels.hip", "svmc_analytic.hip", "svmc_chain.hip", "svmc_comm.hip", "svmc_multi.hip",
-           "svmc_hawkes.hip")
+           "svmc_hawkes.hip", "svmc_density.hip")
 HEADERS = ("svmc_internal.h", "svmc_models.h", "svmc_rng.h", "svmc_math.h", "svmc_log_table.h", "svmc_icdf_table.h", "svmc_black.h", "svmc_ode.h", "svmc_dop853.h",
            "svmc_slice.h", "svmc_complex.h")
 ARCH = "gfx950"

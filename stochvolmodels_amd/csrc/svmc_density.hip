@@ -1,0 +1,229 @@
+// svmc_density.hip -- model densities, digital options and histograms on gfx950: DESIGN.md row f6.
+//
+//   mgf_pdf_slice_kernel       one block per space point z_i = (space_i - shift) / scale: the bin mass
+//                              dx sum_j Re[ (w_j / pi) exp(z_i u_j + log E_j) ] over the transform grid u   (utils/mgf_pricer.py:361-384)
+//   mgf_digital_slice_kernel   one block per strike: sum_j Re[ p_j exp(-x_K phi_j + log E_j) ], p_j = -+(w_j / pi) / phi_j
+//                              (utils/mgf_pricer.py:224-269; the C / P complement and the discount factor are the host's)
+//   histogram_uniform_kernel   integer counts of a state vector on equal bins with np.histogram's semantics: per-block counts in
+//                              LDS, one 64-bit integer atomic per non-empty bin and block
+//
+// The weights w are the reference's LEGACY pricer weights (:157-171), as mgf_vanilla_slice_kernel forms them: Simpson 1,4,2,...
+// with every odd index 4 (an even-length grid keeps 4 on its last point), or for is_simpson = 0 half the first step on the
+// first point and the local step p_j - p_(j-1) on the others.
+//
+// Decomposition of the density kernel: a block per space point, 256 threads striding the grid.  The kernel is bound by the
+// fp64 exp and sincos of each term (a few hundred instructions against 32 bytes read), the transform and the log-MGF of the
+// longest grid (40 000 points) are 1.3 MB that every block re-reads from L2, and a figure's 200 space points are already 800
+// waves; a tile of space points per block would share loads that cost nothing and leave fewer, longer blocks.  The order of
+// the sum over j depends on the grid length alone -- thread t adds j = t, t + 256, ... in order, the 64 lanes of a wave meet in
+// one shuffle tree and the four waves are added in order -- so a set of a batch (blockIdx.y) is bit-equal to the set alone.
+#include "svmc_internal.h"
+
+#include <cmath>
+
+#include "svmc_math.h"
+#include "svmc_complex.h"
+#include "svmc_slice.h"
+
+namespace svmc {
+
+constexpr int DB = 256;                  // threads per block of the two slice kernels
+constexpr int MAX_PDF_SETS = 64;         // parameter sets per launch (kernel-argument block: 64 x 16 B)
+constexpr double PI = 3.14159265358979323846;
+
+// w_j of the legacy pricer weights, BEFORE the division by pi
+__device__ __forceinline__ double legacy_weight(const cd *__restrict__ u, int j, int n_grid, double h, int is_simpson)
+{
+    if (is_simpson) {
+        double w = 2.0;
+        if (j == 0 || j == n_grid - 1) w = 1.0;
+        if (j & 1) w = 4.0;
+        return (h / 3.0) * w;
+    }
+    return (j == 0) ? 0.5 * h : u[j].im - u[j - 1].im;
+}
+
+// the block's sum in its fixed order; thread 0 holds it
+__device__ __forceinline__ double block_sum(double s, double *lds)
+{
+    s = wave_sum(s);
+    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = s;
+    __syncthreads();
+    return ((lds[0] + lds[1]) + lds[2]) + lds[3];
+}
+
+struct PdfSets {
+    double shift[MAX_PDF_SETS];
+    double scale[MAX_PDF_SETS];
+};
+
+__global__ __launch_bounds__(DB) void mgf_pdf_slice_kernel(const cd *__restrict__ u, const cd *__restrict__ log_mgf, int n_grid,
+                                                           const double *__restrict__ space, int n_space, PdfSets ps,
+                                                           int is_simpson, double *__restrict__ pdf)
+{
+    __shared__ double lds[4];
+    const int set = blockIdx.y;                                       // the parameter set of a batched call
+    u += static_cast<size_t>(set) * n_grid;
+    log_mgf += static_cast<size_t>(set) * n_grid;
+    space += static_cast<size_t>(set) * n_space;
+    pdf += static_cast<size_t>(set) * n_space;
+    const double z = (space[blockIdx.x] - ps.shift[set]) / ps.scale[set];                       // :379
+    const double h = u[1].im - u[0].im;
+    double s = 0.0;
+    for (int j = threadIdx.x; j < n_grid; j += DB) {
+        const double w = legacy_weight(u, j, n_grid, h, is_simpson) / PI;                       // :375-377
+        const cd uj = u[j], lm = log_mgf[j];
+        const cd e = cexp_(cd{z * uj.re + lm.re, z * uj.im + lm.im});
+        const double term = w * e.re;
+        if (term == term) s += term;                                                            // nansum :381
+    }
+    const double total = block_sum(s, lds);
+    if (threadIdx.x == 0) pdf[blockIdx.x] = (space[1] - space[0]) * total;                      // :382-383
+}
+
+struct DigitalArgs {
+    double x[32];   // log(forward / strike)
+};
+
+__global__ __launch_bounds__(DB) void mgf_digital_slice_kernel(const cd *__restrict__ phi, const cd *__restrict__ log_mgf,
+                                                               int n_grid, DigitalArgs da, int negative_contour, int is_simpson,
+                                                               double *__restrict__ sums, int sums_ld)
+{
+    __shared__ double lds[4];
+    phi += static_cast<size_t>(blockIdx.y) * n_grid;                  // blockIdx.y: the parameter set of a batched call
+    log_mgf += static_cast<size_t>(blockIdx.y) * n_grid;
+    sums += static_cast<size_t>(blockIdx.y) * sums_ld;
+    const double x = da.x[blockIdx.x];
+    const double h = phi[1].im - phi[0].im;
+    double s = 0.0;
+    for (int j = threadIdx.x; j < n_grid; j += DB) {
+        const double a = legacy_weight(phi, j, n_grid, h, is_simpson) / PI;
+        const cd b = phi[j];
+        // (a + 0i) / b as NumPy divides (Smith's form: the larger component of b scales the other)
+        cd p;
+        if (fabs(b.re) >= fabs(b.im)) {
+            const double rat = b.im / b.re, scl = 1.0 / (b.re + b.im * rat);
+            p = cd{a * scl, -(a * rat) * scl};
+        } else {
+            const double rat = b.re / b.im, scl = 1.0 / (b.im + b.re * rat);
+            p = cd{(a * rat) * scl, -a * scl};
+        }
+        if (negative_contour) p = -p;                                                           // calls :244, puts :247
+        const cd e = cexp_(log_mgf[j] - x * b);
+        const double term = p.re * e.re - p.im * e.im;
+        if (term == term) s += term;                                                            // nansum :253
+    }
+    const double total = block_sum(s, lds);
+    if (threadIdx.x == 0) sums[blockIdx.x] = total;
+}
+
+// np.histogram(a, bins=n_bins, range=(lo, hi)) on equal bins, NumPy's own steps: values outside [lo, hi] and NaNs are dropped; the
+// index is trunc(((a - lo) / (hi - lo)) n_bins), n_bins folded into the last bin, then corrected against the edges (the
+// host's linspace(lo, hi, n_bins + 1)): one down where a < edge[i], one up where a >= edge[i + 1] except in the last bin, which
+// owns `hi`.  `divisor` divides the value first (ttm for the annualised quadratic variance, as the host's qvar / ttm; 1 is exact).
+// Counts are integers and integer addition commutes: the result does not depend on the order the atomics arrive in.
+constexpr int HIST_BLOCK = 256;
+constexpr int HIST_MAX_BINS = 8192;      // 32 KB of LDS counters
+constexpr int HIST_MAX_BLOCKS = 1024;
+
+__global__ __launch_bounds__(HIST_BLOCK) void histogram_uniform_kernel(const double *__restrict__ a, size_t n, double divisor,
+                                                                       const double *__restrict__ edges, int n_bins,
+                                                                       unsigned long long *__restrict__ counts)
+{
+    extern __shared__ unsigned int bins[];
+    for (int b = threadIdx.x; b < n_bins; b += HIST_BLOCK) bins[b] = 0u;
+    __syncthreads();
+    const double lo = edges[0], hi = edges[n_bins], width = hi - lo;
+    for (size_t p = static_cast<size_t>(blockIdx.x) * HIST_BLOCK + threadIdx.x; p < n;
+         p += static_cast<size_t>(gridDim.x) * HIST_BLOCK) {
+        const double v = a[p] / divisor;
+        if (!(v >= lo && v <= hi)) continue;                          // outside the range, or NaN
+        int i = static_cast<int>(((v - lo) / width) * n_bins);
+        i = (i >= n_bins) ? n_bins - 1 : (i < 0 ? 0 : i);             // n_bins -> the last bin; the clamp keeps every read below in bounds
+        if (i > 0 && v < edges[i]) --i;
+        if (i != n_bins - 1 && v >= edges[i + 1]) ++i;
+        atomicAdd(&bins[i], 1u);
+    }
+    __syncthreads();
+    for (int b = threadIdx.x; b < n_bins; b += HIST_BLOCK) {
+        const unsigned int c = bins[b];
+        if (c != 0u) atomicAdd(&counts[b], static_cast<unsigned long long>(c));
+    }
+}
+
+}  // namespace svmc
+
+using namespace svmc;
+
+extern "C" {
+
+int svmc_mgf_pdf_slice_batch(const double *var_grid, const double *log_mgf, size_t n_grid, int n_sets, const double *space,
+                             size_t n_space, const double *shifts_host, const double *scales_host, int is_simpson, double *pdf,
+                             svmc_stream_t stream)
+{
+    SVMC_REQUIRE(var_grid && log_mgf && pdf, "svmc_mgf_pdf_slice_batch: null pointer");
+    SVMC_REQUIRE(n_grid >= 3 && n_grid < (1u << 30), "svmc_mgf_pdf_slice_batch: grid too short or too long");
+    SVMC_REQUIRE(n_sets >= 1 && n_sets <= 65535, "svmc_mgf_pdf_slice_batch: n_sets out of range");
+    SVMC_REQUIRE(n_space == 0 || (space && shifts_host && scales_host), "svmc_mgf_pdf_slice_batch: null space grid, shifts or scales");
+    SVMC_REQUIRE(n_space == 0 || (n_space >= 2 && n_space < (1u << 30)), "svmc_mgf_pdf_slice_batch: a space grid needs two points (dx)");
+    if (n_space == 0) return SVMC_OK;
+    for (int s = 0; s < n_sets; ++s)
+        SVMC_REQUIRE(scales_host[s] != 0.0 && scales_host[s] == scales_host[s], "svmc_mgf_pdf_slice_batch: scale must be non-zero");
+    for (int s0 = 0; s0 < n_sets; s0 += MAX_PDF_SETS) {
+        const int m = (n_sets - s0 < MAX_PDF_SETS) ? (n_sets - s0) : MAX_PDF_SETS;
+        PdfSets ps;
+        for (int i = 0; i < MAX_PDF_SETS; ++i) {
+            ps.shift[i] = (i < m) ? shifts_host[s0 + i] : 0.0;
+            ps.scale[i] = (i < m) ? scales_host[s0 + i] : 1.0;
+        }
+        const size_t goff = static_cast<size_t>(s0) * n_grid, soff = static_cast<size_t>(s0) * n_space;
+        hipLaunchKernelGGL(mgf_pdf_slice_kernel, dim3(static_cast<unsigned>(n_space), static_cast<unsigned>(m)), dim3(DB), 0,
+                           as_stream(stream), reinterpret_cast<const cd *>(var_grid) + goff,
+                           reinterpret_cast<const cd *>(log_mgf) + goff, static_cast<int>(n_grid), space + soff,
+                           static_cast<int>(n_space), ps, is_simpson ? 1 : 0, pdf + soff);
+    }
+    return check_launch("svmc_mgf_pdf_slice_batch");
+}
+
+int svmc_mgf_digital_slice_batch(const double *phi, const double *log_mgf, size_t n_grid, int n_sets, double forward,
+                                 const double *strikes_host, size_t n_strikes, int negative_contour, int is_simpson,
+                                 double *sums, svmc_stream_t stream)
+{
+    SVMC_REQUIRE(phi && log_mgf && sums, "svmc_mgf_digital_slice_batch: null pointer");
+    SVMC_REQUIRE(n_grid >= 3 && n_grid < (1u << 30), "svmc_mgf_digital_slice_batch: grid too short or too long");
+    SVMC_REQUIRE(n_strikes == 0 || strikes_host, "svmc_mgf_digital_slice_batch: null strikes");
+    SVMC_REQUIRE(n_strikes < (1u << 30), "svmc_mgf_digital_slice_batch: too many strikes");
+    SVMC_REQUIRE(n_sets >= 1 && n_sets <= 65535, "svmc_mgf_digital_slice_batch: n_sets out of range");
+    SVMC_REQUIRE(forward > 0.0 && forward < HUGE_VAL, "svmc_mgf_digital_slice_batch: forward must be positive and finite");
+    for (size_t k = 0; k < n_strikes; ++k)           // log(forward / strike) of any other strike is NaN or inf: every term dropped, a silent 0
+        SVMC_REQUIRE(strikes_host[k] > 0.0 && strikes_host[k] < HUGE_VAL,
+                     "svmc_mgf_digital_slice_batch: strikes must be positive and finite");
+    for (size_t k0 = 0; k0 < n_strikes; k0 += 32) {
+        DigitalArgs da;
+        const int k_here = static_cast<int>((n_strikes - k0 < 32) ? (n_strikes - k0) : 32);
+        for (int k = 0; k < 32; ++k) da.x[k] = (k < k_here) ? log(forward / strikes_host[k0 + k]) : 0.0;      // :249
+        hipLaunchKernelGGL(mgf_digital_slice_kernel, dim3(k_here, static_cast<unsigned>(n_sets)), dim3(DB), 0,
+                           as_stream(stream), reinterpret_cast<const cd *>(phi), reinterpret_cast<const cd *>(log_mgf),
+                           static_cast<int>(n_grid), da, negative_contour ? 1 : 0, is_simpson ? 1 : 0, sums + k0,
+                           static_cast<int>(n_strikes));
+    }
+    return check_launch("svmc_mgf_digital_slice_batch");
+}
+
+int svmc_histogram_uniform(const double *values, size_t n, double divisor, const double *edges, int n_bins, uint64_t *counts,
+                           svmc_stream_t stream)
+{
+    SVMC_REQUIRE(edges && counts, "svmc_histogram_uniform: null pointer");
+    SVMC_REQUIRE(n == 0 || values, "svmc_histogram_uniform: null values");
+    SVMC_REQUIRE(n_bins >= 1 && n_bins <= HIST_MAX_BINS, "svmc_histogram_uniform: n_bins must be in 1 .. 8192");
+    SVMC_REQUIRE(divisor != 0.0 && divisor == divisor, "svmc_histogram_uniform: divisor must be non-zero");
+    SVMC_HIP_TRY(hipMemsetAsync(counts, 0, sizeof(uint64_t) * static_cast<size_t>(n_bins), as_stream(stream)));
+    if (n == 0) return SVMC_OK;
+    const size_t want = (n + HIST_BLOCK - 1) / HIST_BLOCK;
+    const unsigned blocks = static_cast<unsigned>(want < HIST_MAX_BLOCKS ? want : HIST_MAX_BLOCKS);
+    hipLaunchKernelGGL(histogram_uniform_kernel, dim3(blocks), dim3(HIST_BLOCK), sizeof(unsigned int) * static_cast<size_t>(n_bins),
+                       as_stream(stream), values, n, divisor, edges, n_bins, reinterpret_cast<unsigned long long *>(counts));
+    return check_launch("svmc_histogram_uniform");
+}
+
+}  // extern "C"

@@ -117,13 +117,27 @@ class HestonPricer(ModelPricer):
     def simulate_terminal_values(self, params: HestonParams, ttm: float = 1.0, nb_path: int = 100000,
                                  x0: float = 0.0, **kwargs) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """returns (x, VARIANCE, qvar) like the reference (:89-108); the x0 argument is ignored there too."""
+        return self._simulate_on_engine(params, ttm, nb_path, kwargs.get("scheme", "euler"), kwargs.get("seed")).get_state()
+
+    @staticmethod
+    def _simulate_on_engine(params: HestonParams, ttm: float, nb_path: int, scheme, seed):
+        """the terminal state of simulate_terminal_values left on the engine it returns (the state stays on the device)"""
         nb_steps, dt = time_grid_steps(ttm=ttm, nb_steps_per_year=360)
-        rng_seed, call_id = next_rng_call(kwargs.get("seed"))
+        rng_seed, call_id = next_rng_call(seed)
         eng = get_engine(nb_path)
         eng.fill_state(0.0, params.v0, 0.0)           # constant initial state written on the device (reference :98-107)
-        eng.heston_rng(nb_steps, dt, params.theta, params.kappa, params.rho, params.volvol,
-                       _scheme_code(kwargs.get("scheme", "euler")), rng_seed, call_id, 0)
-        return eng.get_state()
+        eng.heston_rng(nb_steps, dt, params.theta, params.kappa, params.rho, params.volvol, _scheme_code(scheme), rng_seed,
+                       call_id, 0)
+        return eng
+
+    def terminal_value_histograms(self, params: HestonParams, space_grids: dict, ttm: float = 1.0, nb_path: int = 100000,
+                                  **kwargs) -> dict:
+        """simulate_terminal_values followed by compute_histogram_data of x, qvar / ttm and the VARIANCE (keyed
+        VariableType.SIGMA: the second state vector) on the given space grids {VariableType: grid}, counted on the device --
+        LogSVPricer.terminal_value_histograms for this model.  seed= / scheme= as simulate_terminal_values."""
+        from .logsv_pricer import engine_state_histograms
+        eng = self._simulate_on_engine(params, ttm, nb_path, kwargs.get("scheme", "euler"), kwargs.get("seed"))
+        return engine_state_histograms(eng, space_grids, ttm)
 
 
 def compute_heston_mgf_grid(v0: float, theta: float, kappa: float, volvol: float, rho: float, ttm: float,

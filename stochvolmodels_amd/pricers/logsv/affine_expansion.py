@@ -1,6 +1,7 @@
 """
 Affine expansion of the LogSV MGF on the GPU (mirror of the numerical path of the reference's
-pricers/logsv/affine_expansion.py: ExpansionOrder :43-55, get_expansion_n :58-65, compute_logsv_a_mgf_grid :570-685).
+pricers/logsv/affine_expansion.py: ExpansionOrder :43-55, get_expansion_n :58-65, get_init_conditions_a :533-567,
+compute_logsv_a_mgf_grid :570-685).
 
 The coefficient ODEs A' = A^T M A + L A + H (Eq. 4.14; matrices of Eqs. 4.17 / 4.25) are integrated by
 libsvmc's logsv_mgf_grid_kernel, one 16-lane row per transform-grid point, with the Dormand-Prince 8(5,3) pair (DOP853) at
@@ -58,6 +59,22 @@ def _order_code(expansion_order) -> int:
     if code not in (1, 2):
         raise NotImplementedError
     return code
+
+
+def get_init_conditions_a(phi_grid: np.ndarray, psi_grid: np.ndarray, theta_grid: np.ndarray, n_terms: int,
+                          variable_type: VariableType = VariableType.LOG_RETURN) -> np.ndarray:
+    """A(0) of the coefficient ODEs over the transform grid, [n_grid][n_terms] complex (reference :533-567): zeros for the
+    log-return and the quadratic variance, (0, -Theta, 0, ...) for the volatility"""
+    if variable_type == VariableType.LOG_RETURN:
+        a_t0 = np.zeros((phi_grid.shape[0], n_terms), dtype=np.complex128)
+    elif variable_type == VariableType.Q_VAR:
+        a_t0 = np.zeros((psi_grid.shape[0], n_terms), dtype=np.complex128)
+    elif variable_type == VariableType.SIGMA:
+        a_t0 = np.zeros((theta_grid.shape[0], n_terms), dtype=np.complex128)
+        a_t0[:, 1] = -theta_grid
+    else:
+        raise NotImplementedError
+    return a_t0
 
 
 def compute_logsv_a_mgf_grid(ttm: float, phi_grid: np.ndarray, psi_grid: np.ndarray, theta_grid: np.ndarray,

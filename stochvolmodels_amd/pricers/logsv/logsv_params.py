@@ -1,8 +1,8 @@
 """
 LogSvParams: parameters of the log-normal SV model with quadratic drift, Eq. (3.12)
     dsigma = (kappa1 + kappa2 sigma)(theta - sigma) dt + beta sigma dW0 + volvol sigma dW1
-(the reference's pricers/logsv/logsv_params.py:34-161, plus the generator of the truncated volatility-moment
-system :269-323 that the variance-swap backbone fit of the calibration uses).
+(the reference's pricers/logsv/logsv_params.py:34-161, the space grids of the three state variables' densities :212-267, and
+the generator of the truncated volatility-moment system :269-323 that the variance-swap backbone fit of the calibration uses).
 """
 from __future__ import annotations
 
@@ -12,6 +12,7 @@ from typing import Any, Dict, Optional
 import numpy as np
 import pandas as pd
 
+from ...utils.config import VariableType
 from ..model_pricer import ModelParams
 
 
@@ -84,6 +85,37 @@ class LogSvParams(ModelParams):
     @property
     def gamma(self) -> float:
         return self.kappa1 / self.theta
+
+    def get_x_grid(self, ttm: float = 1.0, n_stdevs: float = 3.0, n: int = 200) -> np.ndarray:
+        """space grid of the log-return's density: n_stdevs + 1 standard deviations either side of the drift (reference :212-224)"""
+        sigma_t = np.sqrt(ttm * 0.5 * (np.square(self.sigma0) + np.square(self.theta)))
+        drift = - 0.5*sigma_t*sigma_t
+        stdev = (n_stdevs+1)*sigma_t
+        return np.linspace(-stdev+drift, stdev+drift, n)
+
+    def get_sigma_grid(self, ttm: float = 1.0, n_stdevs: float = 3.0, n: int = 200) -> np.ndarray:
+        """space grid on [0, .] of the volatility's density (reference :226-235)"""
+        sigma_t = np.sqrt(0.5*(np.square(self.sigma0) + np.square(self.theta)))
+        vvol = 0.5*np.sqrt(self.vartheta2*ttm)
+        return np.linspace(0.0, sigma_t+n_stdevs*vvol, n)
+
+    def get_qvar_grid(self, ttm: float = 1.0, n_stdevs: float = 3.0, n: int = 200) -> np.ndarray:
+        """space grid on [0, .] of the quadratic variance's density (reference :237-245)"""
+        sigma_t = np.sqrt(ttm * (np.square(self.sigma0) + np.square(self.theta)))
+        vvol = np.sqrt(self.vartheta2)*ttm
+        return np.linspace(0.0, sigma_t+n_stdevs*vvol, n)
+
+    def get_variable_space_grid(self, variable_type: VariableType = VariableType.LOG_RETURN, ttm: float = 1.0,
+                                n_stdevs: float = 3, n: int = 200) -> np.ndarray:
+        """the space grid of the state variable selected by variable_type (reference :247-267)"""
+        if variable_type == VariableType.LOG_RETURN:
+            return self.get_x_grid(ttm=ttm, n_stdevs=n_stdevs, n=n)
+        if variable_type == VariableType.SIGMA:
+            return self.get_sigma_grid(ttm=ttm, n_stdevs=n_stdevs, n=n)
+        elif variable_type == VariableType.Q_VAR:
+            return self.get_qvar_grid(ttm=ttm, n_stdevs=n_stdevs, n=n)
+        else:
+            raise NotImplementedError
 
     def get_vol_moments_lambda(self, n_terms: int = 4) -> np.ndarray:
         """generator of the truncated moment system of Y = sigma - theta (reference :269-323; Eq. (3.48)).

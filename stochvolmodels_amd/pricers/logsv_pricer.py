@@ -1,6 +1,6 @@
 """
 LogSV Monte Carlo on MI355X: drop-in for the MC part of the reference's pricers/logsv_pricer.py
-(model_mc_price_chain :368-427, simulate_terminal_values :589-611, logsv_mc_chain_pricer :806-867,
+(model_mc_price_chain :368-427, simulate_terminal_values :589-611, logsv_pdfs :613-635 / :742-803, logsv_mc_chain_pricer :806-867,
 simulate_logsv_x_vol_terminal :950-1047, get_randoms_for_chain_valuation :1051-1074,
 logsv_mc_chain_pricer_fixed_randoms :1100-1162).
 
@@ -23,10 +23,11 @@ from ..engine import MANY_MAX_JOBS, DeviceRandoms, get_engine, marshalled_chain,
 from ..mc_chain import price_chain_on_engine, variable_type_code
 from ..utils.calibration import ImpliedVolObjective, chain_calibration_weights, minimize_slsqp
 from ..utils.config import VariableType
-from ..utils.funcs import next_rng_call, set_time_grid, time_grid_steps, timer
-from ..analytic import AnalyticGrid, qvar_prices_from_sums, vanilla_prices_from_capped
+from ..utils.funcs import histogram_series, next_rng_call, set_time_grid, time_grid_steps, timer
+from ..analytic import (AnalyticGrid, device_histograms, histogram_edges, qvar_prices_from_sums,
+                        vanilla_prices_from_capped)
 from ..utils import mgf_pricer as mgfp
-from .logsv.affine_expansion import ExpansionOrder, _order_code, note_integrator_flags
+from .logsv.affine_expansion import ExpansionOrder, _order_code, get_init_conditions_a, note_integrator_flags
 from .logsv.logsv_params import LogSvParams
 from .logsv.vol_moments_ode import fit_model_vol_backbone_to_varswaps
 from .model_pricer import ModelPricer
@@ -401,13 +402,57 @@ class LogSVPricer(ModelPricer):
                                  ) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         # same as simulate_logsv_x_vol_terminal(x0=zeros, sigma0=sigma0*ones, qvar0=zeros, ...) (reference :600-610),
         # with the constant initial state written on the device instead of uploaded
+        return self._simulate_on_engine(params, ttm, nb_path, is_spot_measure, kwargs.get("seed")).get_state()
+
+    @staticmethod
+    def _simulate_on_engine(params: LogSvParams, ttm: float, nb_path: int, is_spot_measure: bool, seed):
+        """the terminal state of simulate_terminal_values left on the engine it returns (the state stays on the device)"""
         nb_steps, dt = time_grid_steps(ttm=ttm, nb_steps_per_year=360)
-        rng_seed, call_id = next_rng_call(kwargs.get("seed"))
+        rng_seed, call_id = next_rng_call(seed)
         eng = get_engine(nb_path)
         eng.fill_state(0.0, params.sigma0, 0.0)
         eng.logsv_rng(nb_steps, dt, params.theta, params.kappa1, params.kappa2, params.beta, params.volvol, 1.0,
                       is_spot_measure, rng_seed, call_id, 0)
-        return eng.get_state()
+        return eng
+
+    @timer
+    def logsv_pdfs(self, params: LogSvParams, ttm: float, space_grid: np.ndarray, is_stiff_solver: bool = False,
+                   is_analytic: bool = False, is_spot_measure: bool = True,
+                   expansion_order: ExpansionOrder = ExpansionOrder.SECOND,
+                   variable_type: VariableType = VariableType.LOG_RETURN, vol_scaler: float = None) -> np.ndarray:
+        """the model density of the log-return, the annualised quadratic variance or the volatility on `space_grid`, as bin
+        masses (reference :613-635; module-level logsv_pdfs)"""
+        return logsv_pdfs(params=params, ttm=ttm, space_grid=space_grid, is_stiff_solver=is_stiff_solver,
+                          is_analytic=is_analytic, is_spot_measure=is_spot_measure, expansion_order=expansion_order,
+                          variable_type=variable_type, vol_scaler=vol_scaler)
+
+    def terminal_value_histograms(self, params: LogSvParams, ttm: float = 1.0, nb_path: int = 100000,
+                                  is_spot_measure: bool = True, space_grids: Optional[dict] = None, n: int = 200,
+                                  n_stdevs: float = 3.0, **kwargs) -> dict:
+        """simulate_terminal_values followed by compute_histogram_data of x, qvar / ttm and sigma on their space grids, with
+        the counting done on the device: {VariableType: pd.Series}, each Series what utils.funcs.compute_histogram_data
+        returns for that variable (its first entry is x_grid[0] / nb_path, the reference's quirk) -- 3 x n_bins counts come
+        back instead of 3 x nb_path doubles.  space_grids: {VariableType: grid}; default params.get_variable_space_grid(
+        ttm=ttm, n=n, n_stdevs=n_stdevs) of the three variables.  seed= as simulate_terminal_values.  Not in the reference API."""
+        if space_grids is None:
+            space_grids = {vt: params.get_variable_space_grid(variable_type=vt, ttm=ttm, n=n, n_stdevs=n_stdevs)
+                           for vt in (VariableType.LOG_RETURN, VariableType.Q_VAR, VariableType.SIGMA)}
+        eng = self._simulate_on_engine(params, ttm, nb_path, is_spot_measure, kwargs.get("seed"))
+        return engine_state_histograms(eng, space_grids, ttm)
+
+
+def engine_state_histograms(eng, space_grids: dict, ttm: float) -> dict:
+    """compute_histogram_data of the engine's resident state on the given grids, counted on the device (svmc_histogram_uniform):
+    LOG_RETURN -> x, Q_VAR -> qvar / ttm, SIGMA -> the second state vector (the volatility; Heston's variance)"""
+    src = {1: (eng.x.ptr, 1.0), 2: (eng.qvar.ptr, float(ttm)), 3: (eng.vol.ptr, 1.0)}
+    keys = list(space_grids)
+    grids = [np.asarray(space_grids[k], dtype=np.float64) for k in keys]
+    codes = [int(getattr(k, "value", k)) for k in keys]
+    if any(c not in src for c in codes):
+        raise NotImplementedError
+    edges = [histogram_edges(g[0], g[-1], len(g) - 1) for g in grids]
+    counts = device_histograms([src[c][0] for c in codes], eng.n_path, edges, [src[c][1] for c in codes], eng.stream)
+    return {k: histogram_series(cnt, e, g[0], eng.n_path) for k, g, e, cnt in zip(keys, grids, edges, counts)}
 
 
 def set_vol_scaler(sigma0: float, ttm: float) -> float:
@@ -463,6 +508,98 @@ def logsv_chain_pricer(params: LogSvParams, ttms: np.ndarray, forwards: np.ndarr
         return prices
     finally:
         grid.release()
+
+
+def _pdf_setup(params: LogSvParams, ttm: float, is_spot_measure: bool, order: int, variable_type, vol_scaler):
+    """the grids, A(0) and the inversion's (transform grid, which resident buffer it is, shift, scale) of one logsv_pdfs case
+    (reference :756-795)"""
+    if variable_type not in (VariableType.LOG_RETURN, VariableType.Q_VAR, VariableType.SIGMA):
+        raise NotImplementedError
+    if vol_scaler is None:
+        vol_scaler = set_vol_scaler(sigma0=params.sigma0, ttm=ttm)
+    phi_grid, psi_grid, theta_grid = mgfp.get_transform_var_grid(variable_type=variable_type, is_spot_measure=is_spot_measure,
+                                                                 vol_scaler=vol_scaler)
+    a_t0 = get_init_conditions_a(phi_grid=phi_grid, psi_grid=psi_grid, theta_grid=theta_grid, n_terms=5 if order == 2 else 3,
+                                 variable_type=variable_type)
+    if variable_type == VariableType.LOG_RETURN:
+        var_grid, resident, shift, scale = phi_grid, "phi", 0.0, 1.0
+    elif variable_type == VariableType.Q_VAR:                 # scaled by ttm
+        var_grid, resident, shift, scale = psi_grid, "psi", 0.0, 1.0 / ttm
+    else:                                                     # SIGMA: the theta grid is not one of the ODE's two, it is uploaded
+        var_grid, resident, shift, scale = theta_grid, None, params.theta, 1.0
+    return phi_grid, psi_grid, a_t0, var_grid, resident, shift, scale
+
+
+def logsv_pdfs(params: LogSvParams, ttm: float, space_grid: np.ndarray, is_stiff_solver: bool = False,
+               is_analytic: bool = False, is_spot_measure: bool = True, expansion_order: ExpansionOrder = ExpansionOrder.SECOND,
+               variable_type: VariableType = VariableType.LOG_RETURN, vol_scaler: float = None, **kwargs) -> np.ndarray:
+    """model density of the log-return (1000-point phi grid), the annualised quadratic variance (40 000-point psi grid) or the
+    volatility (5000-point theta grid) at `space_grid`, as the bin masses dx * density (reference :742-803): one launch
+    integrating the coefficient ODEs from A(0) = get_init_conditions_a over ttm, one launch inverting over the space grid; the
+    log-MGF stays on the device between them.  is_stiff_solver / is_analytic are accepted and answered by the one device
+    integrator (warned once); grid points it gives up on are counted and warned about (LAST_ANALYTIC_GIVEN_UP).
+    ode_rtol= / ode_atol= as logsv_chain_pricer."""
+    note_integrator_flags(is_stiff_solver, is_analytic)
+    order = _order_code(expansion_order)
+    phi_grid, psi_grid, a_t0, var_grid, resident, shift, scale = _pdf_setup(params, ttm, is_spot_measure, order, variable_type,
+                                                                            vol_scaler)
+    grid = AnalyticGrid.acquire(phi_grid, psi_grid, 5 if order == 2 else 3)
+    try:
+        if np.any(a_t0):
+            grid.set_a(a_t0)
+        grid.logsv_advance(ttm, params.sigma0, params.theta, params.kappa1, params.kappa2, params.beta, params.volvol,
+                           is_spot_measure, order, 1.0, rtol=kwargs.get("ode_rtol"), atol=kwargs.get("ode_atol"))
+        pdf = grid.pdf_sums(var_grid, np.asarray(space_grid, dtype=np.float64), shift=shift, scale=scale, resident=resident)
+        _note_given_up(grid.last_given_up, grid.n)
+        return (pdf / scale).reshape(np.shape(space_grid))
+    finally:
+        grid.release()
+
+
+def logsv_pdfs_batch(params_list: Sequence[LogSvParams], ttm: float, space_grids: Sequence[np.ndarray],
+                     is_spot_measure: bool = True, expansion_orders=ExpansionOrder.SECOND,
+                     variable_type: VariableType = VariableType.LOG_RETURN, vol_scaler: float = None, **kwargs
+                     ) -> List[np.ndarray]:
+    """logsv_pdfs for several cases of ONE variable, maturity and measure: case i has the parameters params_list[i], the space
+    grid space_grids[i] (all of one length) and the expansion order expansion_orders[i] (one order for all when not a
+    sequence).  The cases of one expansion order share one ODE launch and one inversion launch (the coefficient arrays of the
+    two orders differ in width, so a list holding both orders takes two launches of each); every result is bit-equal to its
+    single logsv_pdfs call.  Not in the reference API: the batched form of the six calls behind one panel of its density figure."""
+    from ..analytic import AnalyticGridBatch
+    params_list = list(params_list)
+    if not isinstance(expansion_orders, (list, tuple)):
+        expansion_orders = [expansion_orders] * len(params_list)
+    if not (len(params_list) == len(space_grids) == len(expansion_orders)):
+        raise ValueError("logsv_pdfs_batch: params_list, space_grids and expansion_orders must have one length")
+    orders = [_order_code(o) for o in expansion_orders]
+    spaces = [np.asarray(g, dtype=np.float64) for g in space_grids]
+    if len({g.size for g in spaces}) > 1:
+        raise ValueError("logsv_pdfs_batch: the space grids must have one length")
+    out: List[Optional[np.ndarray]] = [None] * len(params_list)
+    given_up = np.zeros(len(params_list), dtype=int)
+    n_grid = 0
+    for order in sorted(set(orders)):
+        idx = [i for i, o in enumerate(orders) if o == order]
+        setups = [_pdf_setup(params_list[i], ttm, is_spot_measure, order, variable_type, vol_scaler) for i in idx]
+        batch = AnalyticGridBatch.acquire([s[0] for s in setups], [s[1] for s in setups], 5 if order == 2 else 3)
+        try:
+            a_t0 = np.stack([s[2] for s in setups])
+            if np.any(a_t0):
+                batch.set_a(a_t0)
+            rows = np.array([[p.sigma0, p.theta, p.kappa1, p.kappa2, p.beta, p.volvol, 1.0, 0.0]
+                             for p in (params_list[i] for i in idx)])
+            batch.logsv_advance(ttm, rows, is_spot_measure, order, rtol=kwargs.get("ode_rtol"), atol=kwargs.get("ode_atol"))
+            scales = [s[6] for s in setups]
+            pdf = batch.pdf_sums([s[3] for s in setups], [spaces[i].ravel() for i in idx], [s[5] for s in setups], scales,
+                                 resident=setups[0][4])
+            n_grid = batch.n
+            for k, i in enumerate(idx):
+                out[i] = (pdf[k] / scales[k]).reshape(spaces[i].shape)
+                given_up[i] = batch.last_given_up[k]
+        finally:
+            batch.release()
+    _note_given_up(given_up, n_grid)
+    return out
 
 
 def _broadcast_state(x0, vol0, qvar0, nb_path):

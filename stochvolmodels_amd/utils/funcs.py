@@ -1,7 +1,7 @@
 """
 Time grid, seeding and timing helpers of the Monte Carlo path
 (mirror of the reference's utils/funcs.py: set_time_grid :24-48, set_seed :51-60, timer :63-78,
-to_flat_np_array :19-21).
+to_flat_np_array :19-21, compute_histogram_data :81-96).
 """
 from __future__ import annotations
 
@@ -13,6 +13,7 @@ import time
 from typing import List, Optional, Tuple
 
 import numpy as np
+import pandas as pd
 
 
 def to_flat_np_array(input_list: List[np.ndarray]) -> np.ndarray:
@@ -85,6 +86,22 @@ def next_rng_call(seed: Optional[int] = None) -> Tuple[int, int]:
             warnings.warn("stochvolmodels_amd: 2^24 un-seeded generator calls under one seed -- the call counter wraps and "
                           "the next calls repeat earlier randoms; call set_seed() with a new value", RuntimeWarning)
         return _rng_seed, call
+
+
+def compute_histogram_data(data: np.ndarray, x_grid: np.ndarray, name: str = 'Histogram') -> pd.Series:
+    """frequencies of `data` on the len(x_grid) - 1 equal bins over [x_grid[0], x_grid[-1]], indexed by the bin edges
+    (reference utils/funcs.py:81-96).  As there, the FIRST entry is x_grid[0] / len(data), not a frequency: the reference
+    prepends x_grid[0] to the counts to make them as long as the edges, and that quirk is kept.  Host NumPy; the pricers'
+    terminal_value_histograms returns the same Series from counts taken on the device."""
+    hist_data, bin_edges = np.histogram(a=data, bins=len(x_grid) - 1, range=(x_grid[0], x_grid[-1]))
+    return histogram_series(hist_data, bin_edges, x_grid[0], len(data), name)
+
+
+def histogram_series(counts: np.ndarray, bin_edges: np.ndarray, first: float, n_data: int, name: str = 'Histogram') -> pd.Series:
+    """compute_histogram_data's Series from the integer counts (:93-95)"""
+    hist_data = np.append(np.array(first), counts)
+    hist_data = hist_data / n_data
+    return pd.Series(hist_data, index=bin_edges, name=name)
 
 
 def timer(func):

@@ -1,9 +1,10 @@
 """
 Transform grids, quadrature weights and the Fourier slice pricer (mirror of the reference's utils/mgf_pricer.py:
 get_phi_grid :11-34, get_psi_grid :37-47, get_theta_grid :50-58, get_transform_var_grid :61-94,
-compute_integration_weights :97-155, vanilla_slice_pricer_with_mgf_grid :174-221, slice_pricer_with_mgf_grid_with_gamma
-:273-321).  Grid construction is host NumPy; the strike sums of the slice pricers run in libsvmc's mgf_vanilla_slice_kernel and
-mgf_gamma_slice_kernel.
+compute_integration_weights :97-155, vanilla_slice_pricer_with_mgf_grid :174-221, digital_slice_pricer_with_mgf_grid :224-269,
+slice_pricer_with_mgf_grid_with_gamma :273-321, pdf_with_mgf_grid :361-384).  Grid construction is host NumPy; the sums of the
+slice pricers run in libsvmc's mgf_vanilla_slice_kernel, mgf_gamma_slice_kernel, mgf_digital_slice_kernel and
+mgf_pdf_slice_kernel.
 """
 from __future__ import annotations
 
@@ -11,7 +12,8 @@ from typing import Tuple
 
 import numpy as np
 
-from ..analytic import AnalyticGrid, gamma_slice_prices, vanilla_prices_from_capped
+from ..analytic import (AnalyticGrid, digital_prices_from_sums, digital_slice_sums, gamma_slice_prices, pdf_slices,
+                        vanilla_prices_from_capped)
 from .config import VariableType
 
 
@@ -128,3 +130,30 @@ def slice_pricer_with_mgf_grid_with_gamma(log_mgf_grid: np.ndarray, phi_grid: np
                                 gamma_shortcut(phi_grid, risk_premia_gamma), float(normalizer), float(gamma_forward),
                                 float(forward), strikes.ravel(), codes)
     return prices.reshape(strikes.shape)
+
+
+def digital_slice_pricer_with_mgf_grid(log_mgf_grid: np.ndarray, phi_grid: np.ndarray, forward: float, strikes: np.ndarray,
+                                       optiontypes: np.ndarray, discfactor: float = 1.0, is_simpson: bool = True) -> np.ndarray:
+    """digital option prices of one slice from log E on the phi grid (reference :224-269), any model's log-MGF: the payoff
+    weight is -(dp / pi) / phi where every Re phi < 0 (the sums are digital calls) and +(dp / pi) / phi otherwise (puts), the
+    other type is the complement 1 - sum, a type other than 'C' / 'P' raises ValueError."""
+    phi_grid = np.asarray(phi_grid, dtype=np.complex128).ravel()
+    strikes = np.asarray(strikes, dtype=np.float64)
+    for t in optiontypes:
+        if str(t) not in ("C", "P"):
+            raise ValueError("not implemented")
+    calls = bool(np.all(np.real(phi_grid) < 0.0))                                               # :242
+    sums = digital_slice_sums(phi_grid[None, :], np.asarray(log_mgf_grid, dtype=np.complex128).ravel()[None, :], float(forward),
+                              strikes.ravel(), calls, is_simpson)[0]
+    return digital_prices_from_sums(sums, list(np.asarray(optiontypes).ravel()), float(discfactor), calls).reshape(strikes.shape)
+
+
+def pdf_with_mgf_grid(log_mgf_grid: np.ndarray, transform_var_grid: np.ndarray, space_grid: np.ndarray, shift: float = 0.0,
+                      scale: float = 1.0, is_simpson: bool = True) -> np.ndarray:
+    """bin masses dx * density of the variable whose log-MGF is given on its transform grid, at z = (space_grid - shift) / scale
+    (reference :361-384; dx = space_grid[1] - space_grid[0]), any model's log-MGF"""
+    space = np.asarray(space_grid, dtype=np.float64)
+    out = pdf_slices(np.asarray(transform_var_grid, dtype=np.complex128).ravel()[None, :],
+                     np.asarray(log_mgf_grid, dtype=np.complex128).ravel()[None, :], space.ravel()[None, :], [float(shift)],
+                     [float(scale)], is_simpson)[0]
+    return out.reshape(space.shape)
