@@ -1,13 +1,17 @@
 """
-Host side of the analytic (Fourier) chain pricers: device buffers for the transform grid and thin callers of
-libsvmc's svmc_logsv_mgf_grid / svmc_heston_mgf_grid / svmc_mgf_vanilla_slice (csrc/svmc_analytic.hip).
+Host side of the analytic (Fourier) chain pricers: AnalyticGrid, the device buffers of n_sets >= 1 transform grids with thin
+callers of libsvmc's batch entry points (svmc_logsv_mgf_grid_batch, svmc_hawkesjd_mgf_grid_batch, svmc_mgf_vanilla_slice_batch,
+svmc_mgf_gamma_slice_batch, svmc_mgf_pdf_slice_batch; svmc_heston_mgf_grid and svmc_mgf_qvar_slice have no batch form) -- a
+single-set pricing is the batch at one set, as it is inside the library -- and chain_sums, the one loop over a chain's expiries
+that every analytic chain pricer runs (csrc/svmc_analytic.hip, svmc_hawkes.hip, svmc_density.hip).
 Complex arrays travel as numpy.complex128 <-> interleaved doubles.  GPU only, like the Monte Carlo path.
 """
 from __future__ import annotations
 
 import ctypes as C
 import threading
-from typing import Optional, Sequence, Tuple
+from itertools import accumulate
+from typing import Callable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -23,20 +27,50 @@ from .engine import DeviceBuffer, _current_device
 ODE_RTOL, ODE_ATOL = 1e-10, 1e-12
 
 
-# Grids are pooled per (thread, device, class, sizes): a chain pricing took a grid's five allocations, two uploads (each with its own
-# wait) and five frees -- 58 us per chain (tools/r04/analytic_grid_probe.py) of an 0.9-1.2 ms pricing, and the whole of it
-# again at every objective evaluation of an analytic calibration, whose transform grid never changes.  acquire() hands back
-# the pooled object with its ODE state zeroed (queued memsets) and re-uploads phi / psi only when their bytes changed;
+# Grids are pooled per (thread, device, n_sets, n_grid, n_coef): a chain pricing took a grid's five allocations, two uploads
+# (each with its own wait) and five frees -- 58 us per chain (tools/r04/analytic_grid_probe.py) of an 0.9-1.2 ms pricing, and the
+# whole of it again at every objective evaluation of an analytic calibration, whose transform grid never changes.  acquire()
+# hands back the pooled object with its ODE state zeroed (queued memsets) and re-uploads phi / psi only when their bytes changed;
 # release() returns it.  One pooled grid per key: a second acquire() before the release() builds a private one.
 _POOL = {}
 _POOL_LOCK = threading.Lock()
 MAX_POOLED_GRIDS = 8                        # resident pooled grids per process (a 1000-point, 5-coefficient grid is ~130 KB of HBM)
 
 
-class _Pooled:
+def _doubles(a) -> C.Array:
+    """a small host array (parameter rows, strikes) as a `const double *` argument: a private float64 copy handed over
+    through the buffer protocol -- the library reads it before the call returns.  These go out once or twice per expiry, and
+    ndarray.ctypes.data_as costs 4 us a time where the copy and from_buffer cost 2."""
+    a = np.array(a, dtype=np.float64, order="C")
+    return (C.c_double * a.size).from_buffer(a)
+
+
+class AnalyticGrid:
+    """the transform grids phi (and psi) of n_sets >= 1 parameter sets resident on the device, with the per-grid-point ODE state
+    of every set carried expiry to expiry: the sets advance in one launch per expiry (logsv_advance, hawkes_advance) and are
+    inverted in one launch per expiry (queue_capped_sums, or queue_gamma_slice under the Hawkes risk-premia kernel) -- one
+    chain, config C5's five sets, or the bumped parameter vectors of a finite-difference gradient side by side.
+    phi / psi: one 1-D grid (one set), or a sequence / 2-D stack of n_sets grids of one length.  Per-set host data always has
+    the leading set axis -- A [n_sets][n][n_coef], the log-MGF [n_sets][n], sums [n_sets][k], last_given_up [n_sets] -- and a
+    set's bits do not depend on its neighbours in the launch; single-set callers take element 0.  Heston's closed form and the
+    quadratic-variance inversion have no batch entry point: heston_advance and queue_qvar_sums need n_sets == 1."""
+
+    @staticmethod
+    def _shape(phi) -> Tuple[int, int]:
+        """(n_sets, n_grid) of the constructor's phi, without copying it"""
+        if len(phi) == 0 or np.ndim(phi[0]) == 0:
+            return 1, len(phi)
+        return len(phi), len(phi[0])
+
+    @staticmethod
+    def _stacked(z) -> np.ndarray:
+        """a private [n_sets][n_grid] copy: the pooled object compares the NEXT caller's grids with it -- a caller that reuses and
+        mutates its own array in place must not end up comparing the array with itself (and keeping a stale grid on the device)"""
+        return np.array(z, dtype=np.complex128, copy=True, order="C", ndmin=2)
+
     @classmethod
-    def acquire(cls, *args):
-        key = (threading.get_ident(), _current_device(), cls.__name__) + cls._pool_key(*args)
+    def acquire(cls, phi, psi, n_coef: int) -> "AnalyticGrid":
+        key = (threading.get_ident(), _current_device()) + cls._shape(phi) + (int(n_coef),)
         with _POOL_LOCK:
             obj = _POOL.pop(key, None)
             if len(_POOL) > 8:                                  # grids of threads that ended: free their HBM
@@ -46,9 +80,9 @@ class _Pooled:
             while len(_POOL) > MAX_POOLED_GRIDS:                # ... and the least recently released ones beyond the cap: a
                 _POOL.pop(next(iter(_POOL))).close()            # live thread that prices many grid shapes does not keep them all
         if obj is None:
-            obj = cls(*args)
+            obj = cls(phi, psi, n_coef)
         else:
-            obj._reset(*args)
+            obj._reset(phi, psi)
         obj._pool_slot = key
         return obj
 
@@ -60,49 +94,37 @@ class _Pooled:
                 return
         self.close()
 
-
-class AnalyticGrid(_Pooled):
-    """transform grid phi (and psi) resident on the device, with the per-grid-point ODE state carried slice to slice"""
-
-    @staticmethod
-    def _pool_key(phi, psi, n_coef):
-        return (int(np.asarray(phi).size), int(n_coef))
-
-    def _reset(self, phi, psi, n_coef) -> None:
-        # private copies: the pooled object compares the NEXT caller's grid with these -- a caller that reuses and mutates its
-        # own array in place must not end up comparing the array with itself (and keeping a stale grid on the device)
-        phi = np.array(phi, dtype=np.complex128, copy=True, order="C")
-        psi = np.array(psi, dtype=np.complex128, copy=True, order="C")
-        if not np.array_equal(phi, self.phi_host):
-            _lib.check(self.lib.svmc_memcpy_h2d(self.phi.ptr, phi.ctypes.data, phi.nbytes, None))
-            self.phi_host = phi
-        if not np.array_equal(psi, self.psi_host):
-            _lib.check(self.lib.svmc_memcpy_h2d(self.psi.ptr, psi.ctypes.data, psi.nbytes, None))
-            self.psi_host = psi
+    def _reset(self, phi, psi) -> None:
+        for buf, z, name in ((self.phi, self._stacked(phi), "phi_host"), (self.psi, self._stacked(psi), "psi_host")):
+            assert z.shape == (self.n_sets, self.n)
+            if not np.array_equal(z, getattr(self, name)):
+                _lib.check(self.lib.svmc_memcpy_h2d(buf.ptr, z.ctypes.data, z.nbytes, None))
+                setattr(self, name, z)
         _lib.check(self.lib.svmc_stream_synchronize(None))     # pageable sources: the copies must not outlive the arrays
         _lib.check(self.lib.svmc_memset(self.a.ptr, 0, self.a.nbytes, None))
-        _lib.check(self.lib.svmc_memset(self.b.ptr, 0, self.b.nbytes, None))
+        _lib.check(self.lib.svmc_memset(self.b.ptr, 0, self.b.nbytes, None))     # Heston's chained have_t0 start from zero
 
-    def __init__(self, phi: np.ndarray, psi: np.ndarray, n_coef: int):
+    def __init__(self, phi, psi, n_coef: int):
         self.lib = _lib.load()
         cnt = C.c_int()
         _lib.check(self.lib.svmc_device_count(C.byref(cnt)))
         if cnt.value < 1:
             raise _lib.SvmcError("no HIP device visible: the analytic pricers run on the GPU only")
-        self.n = int(phi.size)
+        self.phi_host, self.psi_host = self._stacked(phi), self._stacked(psi)
+        self.n_sets, self.n = self.phi_host.shape
         self.n_coef = int(n_coef)
-        self.phi_host = np.array(phi, dtype=np.complex128, copy=True, order="C")
-        self.phi = self._up(self.phi_host)
-        self.psi_host = np.array(psi, dtype=np.complex128, copy=True, order="C")
-        self.psi = self._up(self.psi_host)
-        self.last_given_up = 0
-        self.a = DeviceBuffer(2 * self.n * self.n_coef)
-        self.b = DeviceBuffer(2 * self.n)
-        self.log_mgf = DeviceBuffer(2 * self.n)
+        assert self.psi_host.shape == (self.n_sets, self.n)
+        self.phi, self.psi = self._up(self.phi_host), self._up(self.psi_host)
+        self.last_given_up = np.zeros(self.n_sets, dtype=int)
+        self.a = DeviceBuffer(2 * self.n_sets * self.n * self.n_coef)
+        self.b = DeviceBuffer(2 * self.n_sets * self.n)
+        self.log_mgf = DeviceBuffer(2 * self.n_sets * self.n)
         _lib.check(self.lib.svmc_memset(self.a.ptr, 0, self.a.nbytes, None))
         _lib.check(self.lib.svmc_memset(self.b.ptr, 0, self.b.nbytes, None))
-        self._capped: Optional[DeviceBuffer] = None
+        self._capped: Optional[DeviceBuffer] = None          # the queued results of a chain (reserve_results)
+        self._risk: Optional[DeviceBuffer] = None            # normalizers then gamma forwards, [n_ttms][n_sets] each
         self._var: Optional[DeviceBuffer] = None             # a transform variable other than phi / psi (pdf_sums)
+        self._risk_ttms = 0
 
     def _up(self, z: np.ndarray) -> DeviceBuffer:
         buf = DeviceBuffer(2 * z.size)
@@ -117,186 +139,24 @@ class AnalyticGrid(_Pooled):
         return out
 
     def set_a(self, a_t0: np.ndarray) -> None:
+        """A(0) of every set, [n_sets][n_grid][n_coef] (zeros after acquire(); -Theta in the 2nd slot for the volatility)"""
         a_t0 = np.ascontiguousarray(a_t0, dtype=np.complex128)
-        assert a_t0.shape == (self.n, self.n_coef)
+        assert a_t0.shape == (self.n_sets, self.n, self.n_coef)
         _lib.check(self.lib.svmc_memcpy_h2d(self.a.ptr, a_t0.ctypes.data, a_t0.nbytes, None))
         _lib.check(self.lib.svmc_stream_synchronize(None))
 
     def get_a(self) -> np.ndarray:
-        return self._down(self.a, (self.n, self.n_coef))
+        return self._down(self.a, (self.n_sets, self.n, self.n_coef))
 
     def get_log_mgf(self) -> np.ndarray:
-        return self._down(self.log_mgf, (self.n,))
-
-    def logsv_advance(self, ttm, sigma0, theta, kappa1, kappa2, beta, volvol, is_spot_measure, expansion_order,
-                      vol_backbone_eta, rtol: Optional[float] = None, atol: Optional[float] = None) -> None:
-        _lib.check(self.lib.svmc_logsv_mgf_grid(self.phi.ptr, self.psi.ptr, self.n, float(ttm), float(sigma0),
-                                                float(theta), float(kappa1), float(kappa2), float(beta), float(volvol),
-                                                int(bool(is_spot_measure)), int(expansion_order), float(vol_backbone_eta),
-                                                self.a.ptr, self.log_mgf.ptr, ODE_RTOL if rtol is None else float(rtol),
-                                                ODE_ATOL if atol is None else float(atol), None))
-
-    def heston_advance(self, ttm, v0, theta, kappa, volvol, rho, have_t0: bool) -> None:
-        _lib.check(self.lib.svmc_heston_mgf_grid(self.phi.ptr, self.psi.ptr, self.n, float(ttm), float(v0), float(theta),
-                                                 float(kappa), float(volvol), float(rho), self.a.ptr, self.b.ptr,
-                                                 int(bool(have_t0)), self.log_mgf.ptr, None))
-
-    def capped_sums(self, forward: float, strikes: np.ndarray, log_mgf_ptr: Optional[int] = None) -> np.ndarray:
-        strikes = np.ascontiguousarray(strikes, dtype=np.float64)
-        k = strikes.size
-        if self._capped is None or self._capped.n < k:
-            self._capped = DeviceBuffer(max(k, 32))
-        _lib.check(self.lib.svmc_mgf_vanilla_slice(self.phi.ptr, log_mgf_ptr or self.log_mgf.ptr, self.n, float(forward),
-                                                   strikes.ctypes.data_as(C.POINTER(C.c_double)), k, self._capped.ptr, None))
-        out = np.empty(k)
-        _lib.check(self.lib.svmc_memcpy_d2h(out.ctypes.data, self._capped.ptr, 8 * k, None))
-        _lib.check(self.lib.svmc_stream_synchronize(None))
-        return out
-
-    # -- the same two reductions QUEUED into slices of one result buffer, downloaded once per chain: a chain's expiries are
-    #    then launched back to back (advance, invert, advance, invert, ...) with no host round trip between them -- the wait
-    #    for each expiry's sums cost a wake-up, the interpreter and a launch latency per expiry with the GPU idle (~50 us each)
-    def reserve_results(self, n_doubles: int) -> None:
-        if self._capped is None or self._capped.n < n_doubles:
-            if self._capped is not None:
-                self._capped.free()
-            self._capped = DeviceBuffer(max(int(n_doubles), 32))
-
-    def queue_capped_sums(self, forward: float, strikes: np.ndarray, offset: int) -> None:
-        strikes = np.ascontiguousarray(strikes, dtype=np.float64)      # copied by the call (kernel arguments / pinned staging)
-        _lib.check(self.lib.svmc_mgf_vanilla_slice(self.phi.ptr, self.log_mgf.ptr, self.n, float(forward),
-                                                   strikes.ctypes.data_as(C.POINTER(C.c_double)), strikes.size,
-                                                   self._capped.offset(offset), None))
-
-    def queue_qvar_sums(self, ttm: float, strikes: np.ndarray, offset: int) -> None:
-        strikes = np.ascontiguousarray(strikes, dtype=np.float64)
-        _lib.check(self.lib.svmc_mgf_qvar_slice(self.psi.ptr, self.log_mgf.ptr, self.n, float(ttm),
-                                                strikes.ctypes.data_as(C.POINTER(C.c_double)), strikes.size,
-                                                self._capped.offset(offset), None))
-
-    def download_results(self, n_doubles: int) -> np.ndarray:
-        """the queued sums of the chain -- and, in the same wait, the last expiry's log-MGF: a grid point the ODE integrator
-        GAVE UP on (step floor / try cap of csrc/svmc_analytic.hip) is NaN there and stays NaN for every later expiry, and the
-        inversion drops it like the reference's nansum -- silently.  self.last_given_up counts them (0 for every sane set):
-        the chain pricers warn and a calibrator can penalise the evaluation."""
-        out = np.empty(int(n_doubles))
-        lm = np.empty(self.n, dtype=np.complex128)
-        _lib.check(self.lib.svmc_memcpy_d2h(out.ctypes.data, self._capped.ptr, 8 * int(n_doubles), None))
-        _lib.check(self.lib.svmc_memcpy_d2h(lm.ctypes.data, self.log_mgf.ptr, lm.nbytes, None))
-        _lib.check(self.lib.svmc_stream_synchronize(None))
-        self.last_given_up = int(np.count_nonzero(np.isnan(lm.real) | np.isnan(lm.imag)))
-        return out
-
-    def _var_ptr(self, var_grid: np.ndarray, resident: Optional[str]) -> int:
-        """the device copy of the transform variable an inversion runs over: the resident phi or psi buffer when the caller
-        names it, else `var_grid` uploaded into a buffer the grid keeps (the theta grid of the volatility)"""
-        if resident == "phi":
-            return self.phi.ptr
-        if resident == "psi":
-            return self.psi.ptr
-        if self._var is None or self._var.n < 2 * var_grid.size:
-            if self._var is not None:
-                self._var.free()
-            self._var = DeviceBuffer(2 * var_grid.size)
-        _lib.check(self.lib.svmc_memcpy_h2d(self._var.ptr, var_grid.ctypes.data, var_grid.nbytes, None))
-        return self._var.ptr
-
-    def pdf_sums(self, var_grid: np.ndarray, space_grid: np.ndarray, shift: float = 0.0, scale: float = 1.0,
-                 is_simpson: bool = True, resident: Optional[str] = None) -> np.ndarray:
-        """pdf_with_mgf_grid (reference utils/mgf_pricer.py:361-384) from the log-MGF resident on the device
-        (svmc_mgf_pdf_slice_batch at one set).  `var_grid` is the transform variable the density is inverted over;
-        resident="phi" / "psi" says it IS the grid's phi / psi buffer, otherwise it is uploaded (the theta grid of the
-        volatility).  The space grid and the masses go through the grid's pooled result buffer.  In the same wait the log-MGF
-        comes back and self.last_given_up is counted (download_results)."""
-        var_grid = np.ascontiguousarray(var_grid, dtype=np.complex128).ravel()
-        space = np.ascontiguousarray(space_grid, dtype=np.float64).ravel()
-        assert var_grid.size == self.n
-        k = space.size
-        self.reserve_results(2 * k)                                    # [space | masses]
-        var_ptr = self._var_ptr(var_grid, resident)
-        _lib.check(self.lib.svmc_memcpy_h2d(self._capped.ptr, space.ctypes.data, space.nbytes, None))
-        pf = C.POINTER(C.c_double)
-        sh, sc = np.array([float(shift)]), np.array([float(scale)])
-        _lib.check(self.lib.svmc_mgf_pdf_slice_batch(var_ptr, self.log_mgf.ptr, self.n, 1, self._capped.ptr, k,
-                                                     sh.ctypes.data_as(pf), sc.ctypes.data_as(pf), int(bool(is_simpson)),
-                                                     self._capped.offset(k), None))
-        out = np.empty(k)
-        lm = np.empty(self.n, dtype=np.complex128)
-        if k:
-            _lib.check(self.lib.svmc_memcpy_d2h(out.ctypes.data, self._capped.offset(k), out.nbytes, None))
-        _lib.check(self.lib.svmc_memcpy_d2h(lm.ctypes.data, self.log_mgf.ptr, lm.nbytes, None))
-        _lib.check(self.lib.svmc_stream_synchronize(None))
-        self.last_given_up = int(np.count_nonzero(np.isnan(lm.real) | np.isnan(lm.imag)))
-        return out
-
-    def qvar_sums(self, ttm: float, strikes: np.ndarray) -> np.ndarray:
-        strikes = np.ascontiguousarray(strikes, dtype=np.float64)
-        k = strikes.size
-        if self._capped is None or self._capped.n < k:
-            self._capped = DeviceBuffer(max(k, 32))
-        _lib.check(self.lib.svmc_mgf_qvar_slice(self.psi.ptr, self.log_mgf.ptr, self.n, float(ttm),
-                                                strikes.ctypes.data_as(C.POINTER(C.c_double)), k, self._capped.ptr, None))
-        out = np.empty(k)
-        _lib.check(self.lib.svmc_memcpy_d2h(out.ctypes.data, self._capped.ptr, 8 * k, None))
-        _lib.check(self.lib.svmc_stream_synchronize(None))
-        return out
-
-    def close(self) -> None:
-        for b in (self.phi, self.psi, self.a, self.b, self.log_mgf, self._capped, self._var):
-            if b is not None:
-                b.free()
-
-
-class AnalyticGridBatch(_Pooled):
-    """the transform grids of SEVERAL LogSV or Hawkes parameter sets resident on the device, advanced expiry by expiry in one
-    launch per expiry (svmc_logsv_mgf_grid_batch, svmc_hawkesjd_mgf_grid_batch) and inverted in one launch per expiry
-    (svmc_mgf_vanilla_slice_batch, or svmc_mgf_gamma_slice_batch under the Hawkes risk-premia kernel):
-    config C5's five sets, or the bumped parameter vectors of a finite-difference gradient, side by side.  Bit-identical
-    to one AnalyticGrid per set."""
-
-    @staticmethod
-    def _pool_key(phis, psis, n_coef):
-        return (len(phis), int(np.asarray(phis[0]).size), int(n_coef))
-
-    def _reset(self, phis, psis, n_coef) -> None:
-        phi = np.ascontiguousarray(np.stack([np.asarray(p, dtype=np.complex128) for p in phis]))
-        psi = np.ascontiguousarray(np.stack([np.asarray(p, dtype=np.complex128) for p in psis]))
-        for buf, z, name in ((self.phi, phi, "phi_host"), (self.psi, psi, "psi_host")):
-            if not np.array_equal(z, getattr(self, name)):
-                _lib.check(self.lib.svmc_memcpy_h2d(buf.ptr, z.ctypes.data, z.nbytes, None))
-                setattr(self, name, z)
-        _lib.check(self.lib.svmc_stream_synchronize(None))
-        _lib.check(self.lib.svmc_memset(self.a.ptr, 0, self.a.nbytes, None))
-
-    def __init__(self, phis: Sequence[np.ndarray], psis: Sequence[np.ndarray], n_coef: int):
-        self.lib = _lib.load()
-        self.n_sets = len(phis)
-        self.n = int(np.asarray(phis[0]).size)
-        self.n_coef = int(n_coef)
-        phi = np.ascontiguousarray(np.stack([np.asarray(p, dtype=np.complex128) for p in phis]))       # np.stack copies: private
-        psi = np.ascontiguousarray(np.stack([np.asarray(p, dtype=np.complex128) for p in psis]))
-        assert phi.shape == psi.shape == (self.n_sets, self.n)
-        self.last_given_up = np.zeros(self.n_sets, dtype=int)
-        self.phi_host, self.psi_host = phi, psi
-        self.phi, self.psi = DeviceBuffer(2 * phi.size), DeviceBuffer(2 * psi.size)
-        for buf, z in ((self.phi, phi), (self.psi, psi)):
-            _lib.check(self.lib.svmc_memcpy_h2d(buf.ptr, z.ctypes.data, z.nbytes, None))
-        _lib.check(self.lib.svmc_stream_synchronize(None))
-        self.a = DeviceBuffer(2 * self.n_sets * self.n * self.n_coef)
-        self.log_mgf = DeviceBuffer(2 * self.n_sets * self.n)
-        _lib.check(self.lib.svmc_memset(self.a.ptr, 0, self.a.nbytes, None))
-        self._capped: Optional[DeviceBuffer] = None
-        self._risk: Optional[DeviceBuffer] = None            # normalizers then gamma forwards, [n_ttms][n_sets] each
-        self._var: Optional[DeviceBuffer] = None             # a transform variable other than phi / psi (pdf_sums)
-        self._risk_ttms = 0
+        return self._down(self.log_mgf, (self.n_sets, self.n))
 
     def logsv_advance(self, ttm: float, params_rows: np.ndarray, is_spot_measure: bool, expansion_order: int,
                       rtol: Optional[float] = None, atol: Optional[float] = None) -> None:
         """params_rows [n_sets][8] = (sigma0, theta, kappa1, kappa2, beta, volvol, vol_backbone_eta, 0)"""
-        rows = np.ascontiguousarray(params_rows, dtype=np.float64)
-        assert rows.shape == (self.n_sets, 8)
+        assert np.shape(params_rows) == (self.n_sets, 8)
         _lib.check(self.lib.svmc_logsv_mgf_grid_batch(self.phi.ptr, self.psi.ptr, self.n, self.n_sets, float(ttm),
-                                                      rows.ctypes.data_as(C.POINTER(C.c_double)), int(bool(is_spot_measure)),
+                                                      _doubles(params_rows), int(bool(is_spot_measure)),
                                                       int(expansion_order), self.a.ptr, self.log_mgf.ptr,
                                                       ODE_RTOL if rtol is None else float(rtol),
                                                       ODE_ATOL if atol is None else float(atol), None))
@@ -304,17 +164,22 @@ class AnalyticGridBatch(_Pooled):
     def hawkes_advance(self, ttm: float, params_rows: np.ndarray, rtol: Optional[float] = None,
                        atol: Optional[float] = None) -> None:
         """params_rows [n_sets][16]: the Hawkes jump-diffusion parameter blocks (include/svmc.h SVMC_HAWKESJD_PARAMS order)"""
-        rows = np.ascontiguousarray(params_rows, dtype=np.float64)
-        assert rows.shape == (self.n_sets, 16) and self.n_coef == 3
+        assert np.shape(params_rows) == (self.n_sets, 16) and self.n_coef == 3
         _lib.check(self.lib.svmc_hawkesjd_mgf_grid_batch(self.phi.ptr, self.psi.ptr, self.n, self.n_sets, float(ttm),
-                                                         rows.ctypes.data_as(C.POINTER(C.c_double)), self.a.ptr,
+                                                         _doubles(params_rows), self.a.ptr,
                                                          self.log_mgf.ptr, ODE_RTOL if rtol is None else float(rtol),
                                                          ODE_ATOL if atol is None else float(atol), None))
+
+    def heston_advance(self, ttm, v0, theta, kappa, volvol, rho, have_t0: bool) -> None:
+        assert self.n_sets == 1, "svmc_heston_mgf_grid has no batch form"
+        _lib.check(self.lib.svmc_heston_mgf_grid(self.phi.ptr, self.psi.ptr, self.n, float(ttm), float(v0), float(theta),
+                                                 float(kappa), float(volvol), float(rho), self.a.ptr, self.b.ptr,
+                                                 int(bool(have_t0)), self.log_mgf.ptr, None))
 
     def risk_forwards(self, params_rows: np.ndarray, gammas: np.ndarray, ttms: np.ndarray, forwards: np.ndarray,
                       rtol: Optional[float] = None, atol: Optional[float] = None) -> None:
         """queue the risk-premia normalizers and gamma forwards of every set and expiry (svmc_hawkesjd_risk_forwards_batch)
-        into the batch's device buffer, where queue_gamma_slice reads them; download_risk_results brings them back"""
+        into the grid's device buffer, where queue_gamma_slice reads them; download_risk_results brings them back"""
         rows = np.ascontiguousarray(params_rows, dtype=np.float64)
         gammas = np.ascontiguousarray(gammas, dtype=np.float64)
         ttms = np.ascontiguousarray(ttms, dtype=np.float64)
@@ -333,6 +198,26 @@ class AnalyticGridBatch(_Pooled):
                                                               ODE_RTOL if rtol is None else float(rtol),
                                                               ODE_ATOL if atol is None else float(atol), None))
 
+    # -- the inversions are QUEUED into slices of one result buffer, downloaded once per chain: a chain's expiries are then
+    #    launched back to back (advance, invert, advance, invert, ...) with no host round trip between them -- the wait for each
+    #    expiry's sums cost a wake-up, the interpreter and a launch latency per expiry with the GPU idle (~50 us each)
+    def reserve_results(self, n_doubles: int) -> None:
+        if self._capped is None or self._capped.n < n_doubles:
+            if self._capped is not None:
+                self._capped.free()
+            self._capped = DeviceBuffer(max(int(n_doubles), 32))
+
+    def queue_capped_sums(self, forward: float, strikes: np.ndarray, offset: int, log_mgf_ptr: Optional[int] = None) -> None:
+        """the [n_sets][n_strikes] capped sums of one expiry from the current log-MGF, queued into the result buffer at `offset`"""
+        _lib.check(self.lib.svmc_mgf_vanilla_slice_batch(self.phi.ptr, log_mgf_ptr or self.log_mgf.ptr, self.n, self.n_sets,
+                                                         float(forward), _doubles(strikes), np.size(strikes),
+                                                         self._capped.offset(offset), None))
+
+    def queue_qvar_sums(self, ttm: float, strikes: np.ndarray, offset: int) -> None:
+        assert self.n_sets == 1, "svmc_mgf_qvar_slice has no batch form"
+        _lib.check(self.lib.svmc_mgf_qvar_slice(self.psi.ptr, self.log_mgf.ptr, self.n, float(ttm), _doubles(strikes),
+                                                np.size(strikes), self._capped.offset(offset), None))
+
     def queue_gamma_slice(self, gammas: np.ndarray, shortcut: np.ndarray, expiry: int, forward: float, strikes: np.ndarray,
                           type_codes: np.ndarray, offset: int) -> None:
         """the [n_sets][n_strikes] undiscounted risk-premia prices of expiry `expiry` from the current log-MGF, queued into
@@ -350,6 +235,24 @@ class AnalyticGridBatch(_Pooled):
                                                        strikes.ctypes.data_as(pf), codes.ctypes.data_as(pi), strikes.size,
                                                        self._capped.offset(offset), None))
 
+    def _download(self, offset: int, shape) -> np.ndarray:
+        """`shape` doubles of the result buffer from `offset` -- and, in the same wait, the log-MGF: a grid point the ODE
+        integrator GAVE UP on (step floor / try cap of csrc/svmc_analytic.hip) is NaN there and stays NaN for every later
+        expiry, and the inversion drops it like the reference's nansum -- silently.  self.last_given_up counts them per set
+        (0 for every sane set): the chain pricers warn and a calibrator can penalise the evaluation."""
+        out = np.empty(shape)
+        lm = np.empty((self.n_sets, self.n), dtype=np.complex128)
+        if out.size:
+            _lib.check(self.lib.svmc_memcpy_d2h(out.ctypes.data, self._capped.offset(offset), out.nbytes, None))
+        _lib.check(self.lib.svmc_memcpy_d2h(lm.ctypes.data, self.log_mgf.ptr, lm.nbytes, None))
+        _lib.check(self.lib.svmc_stream_synchronize(None))
+        self.last_given_up = np.isnan(lm).sum(axis=1)          # complex: NaN in either part
+        return out
+
+    def download_results(self, n_doubles: int) -> np.ndarray:
+        """the queued sums of the chain; sets self.last_given_up (_download)"""
+        return self._download(0, int(n_doubles))
+
     def download_risk_results(self, n_doubles: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """(queued prices, normalizers [n_ttms][n_sets], gamma forwards [n_ttms][n_sets]) in one wait; last_given_up as in
         download_results"""
@@ -360,79 +263,99 @@ class AnalyticGridBatch(_Pooled):
         out = self.download_results(n_doubles)
         return out, risk[:n].reshape(self._risk_ttms, self.n_sets), risk[n:].reshape(self._risk_ttms, self.n_sets)
 
-    def capped_sums(self, forward: float, strikes: np.ndarray) -> np.ndarray:
-        """-> [n_sets][n_strikes]"""
-        strikes = np.ascontiguousarray(strikes, dtype=np.float64)
-        k = strikes.size
-        if self._capped is None or self._capped.n < k * self.n_sets:
-            self._capped = DeviceBuffer(max(k * self.n_sets, 32))
-        _lib.check(self.lib.svmc_mgf_vanilla_slice_batch(self.phi.ptr, self.log_mgf.ptr, self.n, self.n_sets, float(forward),
-                                                         strikes.ctypes.data_as(C.POINTER(C.c_double)), k, self._capped.ptr,
-                                                         None))
+    def capped_sums(self, forward: float, strikes: np.ndarray, log_mgf_ptr: Optional[int] = None) -> np.ndarray:
+        """-> [n_sets][n_strikes], from the grid's log-MGF or from a caller's device copy of one (utils/mgf_pricer.py's slice
+        pricer); the grid's own log-MGF is not looked at, last_given_up stays"""
+        k = int(np.size(strikes))
+        self.reserve_results(self.n_sets * k)
+        self.queue_capped_sums(forward, strikes, 0, log_mgf_ptr=log_mgf_ptr)
         out = np.empty((self.n_sets, k))
         _lib.check(self.lib.svmc_memcpy_d2h(out.ctypes.data, self._capped.ptr, out.nbytes, None))
         _lib.check(self.lib.svmc_stream_synchronize(None))
         return out
 
-    def set_a(self, a_t0: np.ndarray) -> None:
-        """A(0) of every set, [n_sets][n_grid][n_coef] (zeros after acquire(); -Theta in the 2nd slot for the volatility)"""
-        a_t0 = np.ascontiguousarray(a_t0, dtype=np.complex128)
-        assert a_t0.shape == (self.n_sets, self.n, self.n_coef)
-        _lib.check(self.lib.svmc_memcpy_h2d(self.a.ptr, a_t0.ctypes.data, a_t0.nbytes, None))
-        _lib.check(self.lib.svmc_stream_synchronize(None))
+    def _var_ptr(self, var_grids: np.ndarray) -> int:
+        """`var_grids` uploaded into a buffer the grid keeps: a transform variable other than the resident phi / psi (the theta
+        grid of the volatility)"""
+        if self._var is None or self._var.n < 2 * var_grids.size:
+            if self._var is not None:
+                self._var.free()
+            self._var = DeviceBuffer(2 * var_grids.size)
+        _lib.check(self.lib.svmc_memcpy_h2d(self._var.ptr, var_grids.ctypes.data, var_grids.nbytes, None))
+        return self._var.ptr
 
     def pdf_sums(self, var_grids: Sequence[np.ndarray], space_grids: Sequence[np.ndarray], shifts: Sequence[float],
                  scales: Sequence[float], is_simpson: bool = True, resident: Optional[str] = None) -> np.ndarray:
-        """AnalyticGrid.pdf_sums for every set in ONE launch -> [n_sets][n_space]; each set has its own transform grid, space
-        grid (of one common length), shift and scale.  self.last_given_up is counted per set in the same wait."""
-        var = np.ascontiguousarray(np.stack([np.asarray(v, dtype=np.complex128).ravel() for v in var_grids]))
-        space = np.ascontiguousarray(np.stack([np.asarray(s, dtype=np.float64).ravel() for s in space_grids]))
-        sh, sc = np.ascontiguousarray(shifts, dtype=np.float64), np.ascontiguousarray(scales, dtype=np.float64)
-        assert var.shape == (self.n_sets, self.n) and space.shape[0] == self.n_sets and sh.shape == sc.shape == (self.n_sets,)
+        """pdf_with_mgf_grid (reference utils/mgf_pricer.py:361-384) of every set from the log-MGF resident on the device, in
+        ONE launch (svmc_mgf_pdf_slice_batch) -> [n_sets][n_space]; each set has its own transform grid (the variable the
+        density is inverted over), space grid (of one common length), shift and scale.  resident="phi" / "psi" says the
+        transform grids ARE the grid's phi / psi buffer, otherwise they are uploaded (the theta grid of the volatility).  The
+        space grids and the masses go through the pooled result buffer; self.last_given_up is counted in the same wait."""
+        space = np.array([np.ravel(s) for s in space_grids], dtype=np.float64, order="C")
+        assert space.shape[0] == self.n_sets and len(var_grids) == np.size(shifts) == np.size(scales) == self.n_sets
         k = space.size
         self.reserve_results(2 * k)                                    # [spaces | masses]
-        var_ptr = AnalyticGrid._var_ptr(self, var, resident)
+        if resident is None:
+            var = np.ascontiguousarray(np.stack([np.asarray(v, dtype=np.complex128).ravel() for v in var_grids]))
+            assert var.shape == (self.n_sets, self.n)
+        var_ptr = getattr(self, resident).ptr if resident in ("phi", "psi") else self._var_ptr(var)
         _lib.check(self.lib.svmc_memcpy_h2d(self._capped.ptr, space.ctypes.data, space.nbytes, None))
-        pf = C.POINTER(C.c_double)
         _lib.check(self.lib.svmc_mgf_pdf_slice_batch(var_ptr, self.log_mgf.ptr, self.n, self.n_sets, self._capped.ptr,
-                                                     space.shape[1], sh.ctypes.data_as(pf), sc.ctypes.data_as(pf),
+                                                     space.shape[1], _doubles(shifts), _doubles(scales),
                                                      int(bool(is_simpson)), self._capped.offset(k), None))
-        out = np.empty(space.shape)
-        lm = np.empty((self.n_sets, self.n), dtype=np.complex128)
-        if k:
-            _lib.check(self.lib.svmc_memcpy_d2h(out.ctypes.data, self._capped.offset(k), out.nbytes, None))
-        _lib.check(self.lib.svmc_memcpy_d2h(lm.ctypes.data, self.log_mgf.ptr, lm.nbytes, None))
-        _lib.check(self.lib.svmc_stream_synchronize(None))
-        self.last_given_up = np.count_nonzero(np.isnan(lm.real) | np.isnan(lm.imag), axis=1).astype(int)
-        return out
-
-    def reserve_results(self, n_doubles: int) -> None:
-        if self._capped is None or self._capped.n < n_doubles:
-            if self._capped is not None:
-                self._capped.free()
-            self._capped = DeviceBuffer(max(int(n_doubles), 32))
-
-    def queue_capped_sums(self, forward: float, strikes: np.ndarray, offset: int) -> None:
-        """the [n_sets][n_strikes] sums of one expiry, queued into the result buffer at `offset` (AnalyticGrid.queue_capped_sums)"""
-        strikes = np.ascontiguousarray(strikes, dtype=np.float64)
-        _lib.check(self.lib.svmc_mgf_vanilla_slice_batch(self.phi.ptr, self.log_mgf.ptr, self.n, self.n_sets, float(forward),
-                                                         strikes.ctypes.data_as(C.POINTER(C.c_double)), strikes.size,
-                                                         self._capped.offset(offset), None))
-
-    def download_results(self, n_doubles: int) -> np.ndarray:
-        """as AnalyticGrid.download_results; self.last_given_up is an array, one count per parameter set"""
-        out = np.empty(int(n_doubles))
-        lm = np.empty((self.n_sets, self.n), dtype=np.complex128)
-        _lib.check(self.lib.svmc_memcpy_d2h(out.ctypes.data, self._capped.ptr, 8 * int(n_doubles), None))
-        _lib.check(self.lib.svmc_memcpy_d2h(lm.ctypes.data, self.log_mgf.ptr, lm.nbytes, None))
-        _lib.check(self.lib.svmc_stream_synchronize(None))
-        self.last_given_up = np.count_nonzero(np.isnan(lm.real) | np.isnan(lm.imag), axis=1).astype(int)
-        return out
+        return self._download(k, space.shape)
 
     def close(self) -> None:
-        for b in (self.phi, self.psi, self.a, self.log_mgf, self._capped, self._risk, self._var):
+        for b in (self.phi, self.psi, self.a, self.b, self.log_mgf, self._capped, self._risk, self._var):
             if b is not None:
                 b.free()
+
+
+def chain_sums(grid: AnalyticGrid, ttms, forwards, strikes_ttms, advance: Callable[[int, float], None],
+               inversion: str = "vanilla", gamma: Optional[tuple] = None):
+    """the loop every analytic chain pricer runs on a grid of n_sets: reserve the chain's results, then per expiry
+    advance(i, ttm_i - ttm_(i-1)) -- the caller's launch moving every set's ODE state on to expiry i -- and the queued
+    inversion, then ONE download, so no host round trip separates the expiries.  inversion: "vanilla" (queue_capped_sums),
+    "qvar" (queue_qvar_sums: one set) or "gamma" (queue_gamma_slice, with gamma = (gammas, shortcut, type codes per expiry)
+    and the caller's risk_forwards launch queued before).  Expiry i's [n_sets][k_i] block sits at cumsum(n_sets * k_i): an
+    expiry without strikes takes no space.  -> sums[set][expiry], the views of the one downloaded array; under "gamma"
+    (sums, normalizers, gamma forwards) as download_risk_results gives them.  grid.last_given_up is set by the download."""
+    n_sets = grid.n_sets
+    strikes = [np.asarray(k, dtype=np.float64) for k in strikes_ttms]
+    offs = [0, *accumulate(n_sets * k.size for k in strikes)]
+    grid.reserve_results(offs[-1])
+    ttm0, n_exp = 0.0, 0
+    for i, (ttm, forward, k) in enumerate(zip(ttms, forwards, strikes)):
+        advance(i, ttm - ttm0)
+        if inversion == "vanilla":
+            grid.queue_capped_sums(float(forward), k, offs[i])
+        elif inversion == "qvar":
+            grid.queue_qvar_sums(float(ttm), k, offs[i])
+        else:
+            grid.queue_gamma_slice(gamma[0], gamma[1], i, float(forward), k.ravel(), gamma[2][i], offs[i])
+        ttm0, n_exp = ttm, i + 1
+    if inversion == "gamma":
+        flat, *risk = grid.download_risk_results(offs[-1])
+    else:
+        flat, risk = grid.download_results(offs[-1]), []
+    sums = [[flat[offs[i] + s * k.size:offs[i] + (s + 1) * k.size] for i, k in enumerate(strikes[:n_exp])] for s in range(n_sets)]
+    return (sums, *risk) if inversion == "gamma" else sums
+
+
+def chain_prices_from_sums(sums: List[List[np.ndarray]], inversion: str, ttms, forwards, discfactors, strikes_ttms,
+                           optiontypes_ttms, is_spot_measure: bool = True) -> List[List[np.ndarray]]:
+    """chain_sums' "vanilla" or "qvar" sums [set][expiry] -> prices [set][expiry] (vanilla_prices_from_capped,
+    qvar_prices_from_sums)"""
+    out = [[] for _ in sums]
+    for i, (ttm, forward, discfactor, strikes, types) in enumerate(zip(ttms, forwards, discfactors, strikes_ttms,
+                                                                       optiontypes_ttms)):
+        for s, of_set in enumerate(sums):
+            if inversion == "vanilla":
+                out[s].append(vanilla_prices_from_capped(of_set[i], float(forward), strikes, types, float(discfactor),
+                                                         is_spot_measure))
+            else:
+                out[s].append(qvar_prices_from_sums(of_set[i], float(ttm), types, float(discfactor)))
+    return out
 
 
 def gamma_slice_prices(phi: np.ndarray, log_mgf: np.ndarray, gamma: float, shortcut: bool, normalizer: float,

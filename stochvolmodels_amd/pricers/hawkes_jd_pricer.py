@@ -39,7 +39,7 @@ import numpy as np
 
 from .. import _lib
 from .. import dist as svdist
-from ..analytic import ODE_ATOL, ODE_RTOL, AnalyticGrid, AnalyticGridBatch, vanilla_prices_from_capped
+from ..analytic import ODE_ATOL, ODE_RTOL, AnalyticGrid, chain_prices_from_sums, chain_sums
 from ..data.option_chain import OptionChain
 from ..engine import DeviceBuffer, get_engine, marshalled_chain, option_type_codes
 from ..mc_chain import variable_type_code
@@ -375,18 +375,11 @@ def compute_hawkes_a_mgf_grid(ttm: float, phi_grid: np.ndarray, model_params: Ha
     grid = AnalyticGrid(phi_grid, psi_grid, 3)
     try:
         if a_t0 is not None:
-            grid.set_a(np.asarray(a_t0, dtype=np.complex128).reshape(-1, 3))
-        _advance(grid, float(ttm), _model_block(model_params), ode_rtol, ode_atol)
-        return grid.get_a(), grid.get_log_mgf()
+            grid.set_a(np.asarray(a_t0, dtype=np.complex128).reshape(1, -1, 3))
+        grid.hawkes_advance(float(ttm), _model_block(model_params)[None, :], ode_rtol, ode_atol)
+        return grid.get_a()[0], grid.get_log_mgf()[0]
     finally:
         grid.close()
-
-
-def _advance(grid: AnalyticGrid, ttm: float, block: np.ndarray, rtol, atol) -> None:
-    _lib.check(grid.lib.svmc_hawkesjd_mgf_grid(grid.phi.ptr, grid.psi.ptr, grid.n, float(ttm),
-                                               block.ctypes.data_as(C.POINTER(C.c_double)), grid.a.ptr, grid.log_mgf.ptr,
-                                               ODE_RTOL if rtol is None else float(rtol), ODE_ATOL if atol is None else float(atol),
-                                               None))
 
 
 def hawkesjd_chain_pricer(model_params: HawkesJDParams, ttms: np.ndarray, forwards: np.ndarray, discfactors: np.ndarray,
@@ -395,31 +388,12 @@ def hawkesjd_chain_pricer(model_params: HawkesJDParams, ttms: np.ndarray, forwar
                           variable_type: VariableType = VariableType.LOG_RETURN, vol_scaler: float = None,
                           ode_rtol: Optional[float] = None, ode_atol: Optional[float] = None) -> List[np.ndarray]:
     """analytic chain prices by Fourier inversion of the coefficient-ODE MGF (reference :365-417), a_t0 chained over the
-    expiries; ode_rtol / ode_atol: the integrator's tolerances (default 1e-10 / 1e-12)"""
-    if int(getattr(variable_type, "value", variable_type)) != LOG_RETURN:
-        raise NotImplementedError(f"variable_type={variable_type}")
-    ttms = np.asarray(ttms, dtype=np.float64)
-    if vol_scaler is None:
-        vol_scaler = set_vol_scaler(sigma0=model_params.sigma, ttm=np.min(ttms))
-    phi_grid, psi_grid, _ = mgfp.get_transform_var_grid(variable_type=variable_type, max_phi=MAX_PHI, vol_scaler=vol_scaler)
-    block = _model_block(model_params)
-    grid = AnalyticGrid.acquire(phi_grid, psi_grid, 3)
-    try:
-        ks = [int(np.asarray(k).size) for k in strikes_ttms]
-        offs = np.concatenate([[0], np.cumsum(ks)]).astype(int)
-        grid.reserve_results(int(offs[-1]))
-        ttm0 = 0.0
-        for i, (ttm, forward, strikes) in enumerate(zip(ttms, forwards, strikes_ttms)):
-            _advance(grid, float(ttm - ttm0), block, ode_rtol, ode_atol)
-            grid.queue_capped_sums(float(forward), np.asarray(strikes, dtype=np.float64), int(offs[i]))
-            ttm0 = ttm
-        sums = grid.download_results(int(offs[-1]))
-        return [vanilla_prices_from_capped(sums[offs[i]:offs[i + 1]], float(forward), np.asarray(strikes), types,
-                                           float(discfactor), is_spot_measure)
-                for i, (forward, discfactor, strikes, types) in enumerate(zip(forwards, discfactors, strikes_ttms,
-                                                                              optiontypes_ttms))]
-    finally:
-        grid.release()
+    expiries; ode_rtol / ode_atol: the integrator's tolerances (default 1e-10 / 1e-12).  This is hawkesjd_chain_pricer_batch
+    at one set."""
+    return hawkesjd_chain_pricer_batch(params_list=[model_params], ttms=ttms, forwards=forwards, discfactors=discfactors,
+                                       strikes_ttms=strikes_ttms, optiontypes_ttms=optiontypes_ttms,
+                                       is_spot_measure=is_spot_measure, variable_type=variable_type, vol_scaler=vol_scaler,
+                                       ode_rtol=ode_rtol, ode_atol=ode_atol)[0]
 
 
 def hawkesjd_chain_pricer_batch(params_list: Sequence[HawkesJDParams], ttms: np.ndarray, forwards: np.ndarray,
@@ -441,26 +415,13 @@ def hawkesjd_chain_pricer_batch(params_list: Sequence[HawkesJDParams], ttms: np.
                                          vol_scaler=(set_vol_scaler(sigma0=p.sigma, ttm=np.min(ttms))
                                                      if vol_scaler is None else vol_scaler)) for p in params_list]
     rows = np.stack([_model_block(p) for p in params_list])
-    batch = AnalyticGridBatch.acquire([g[0] for g in grids], [g[1] for g in grids], 3)
+    grid = AnalyticGrid.acquire([g[0] for g in grids], [g[1] for g in grids], 3)
     try:
-        ks = [int(np.asarray(k).size) for k in strikes_ttms]
-        offs = np.concatenate([[0], np.cumsum([n_sets * k for k in ks])]).astype(int)
-        batch.reserve_results(int(offs[-1]))
-        ttm0 = 0.0
-        for i, (ttm, forward, strikes) in enumerate(zip(ttms, forwards, strikes_ttms)):
-            batch.hawkes_advance(float(ttm - ttm0), rows, ode_rtol, ode_atol)
-            batch.queue_capped_sums(float(forward), np.asarray(strikes, dtype=np.float64), int(offs[i]))
-            ttm0 = ttm
-        sums = batch.download_results(int(offs[-1]))
-        out = [[] for _ in params_list]
-        for i, (forward, discfactor, strikes, types) in enumerate(zip(forwards, discfactors, strikes_ttms, optiontypes_ttms)):
-            capped = sums[offs[i]:offs[i + 1]].reshape(n_sets, ks[i])
-            for s in range(n_sets):
-                out[s].append(vanilla_prices_from_capped(capped[s], float(forward), np.asarray(strikes), types,
-                                                         float(discfactor), is_spot_measure))
-        return out
+        sums = chain_sums(grid, ttms, forwards, strikes_ttms,
+                          lambda i, dt: grid.hawkes_advance(float(dt), rows, ode_rtol, ode_atol))
     finally:
-        batch.release()
+        grid.release()
+    return chain_prices_from_sums(sums, "vanilla", ttms, forwards, discfactors, strikes_ttms, optiontypes_ttms, is_spot_measure)
 
 
 def _risk_ttms_forwards(ttms, forwards) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
@@ -565,27 +526,18 @@ def hawkesjd_chain_pricer_with_risk_premia_batch(params_list: Sequence[HawkesJDP
     out = [[] for _ in params_list]
     if t_fwd.size == 0:
         return (out, list(zip(normalizers, gamma_forwards))) if return_forwards else out
-    batch = AnalyticGridBatch.acquire([g[0] for g in grids], [g[1] for g in grids], 3)
+    grid = AnalyticGrid.acquire([g[0] for g in grids], [g[1] for g in grids], 3)
     try:
-        ks = [k.size for k in strikes]
-        offs = np.concatenate([[0], np.cumsum([n_sets * k for k in ks])]).astype(int)
-        batch.reserve_results(int(offs[-1]))
-        batch.risk_forwards(rows, gammas, t_fwd, f_fwd, ode_rtol, ode_atol)
-        ttm0 = 0.0
-        for i in range(n_exp):
-            batch.hawkes_advance(float(t_fwd[i] - ttm0), rows, ode_rtol, ode_atol)
-            batch.queue_gamma_slice(gammas, shortcut, i, float(f_fwd[i]), strikes[i].ravel(), codes[i], int(offs[i]))
-            ttm0 = t_fwd[i]
-        sums, norms, gfwds = batch.download_risk_results(int(offs[-1]))
+        grid.risk_forwards(rows, gammas, t_fwd, f_fwd, ode_rtol, ode_atol)
+        sums, norms, gfwds = chain_sums(grid, t_fwd, f_fwd, strikes,
+                                        lambda i, dt: grid.hawkes_advance(float(dt), rows, ode_rtol, ode_atol),
+                                        "gamma", (gammas, shortcut, codes))
     finally:
-        batch.release()
+        grid.release()
     for s in range(n_sets):
         normalizers[s].ravel()[:t_fwd.size] = norms[:, s]
         gamma_forwards[s].ravel()[:t_fwd.size] = gfwds[:, s]
-    for i in range(n_exp):
-        prices = sums[offs[i]:offs[i + 1]].reshape(n_sets, ks[i])
-        for s in range(n_sets):
-            out[s].append(prices[s].reshape(strikes[i].shape).copy())
+        out[s] = [prices.reshape(k.shape).copy() for prices, k in zip(sums[s], strikes)]
     return (out, list(zip(normalizers, gamma_forwards))) if return_forwards else out
 
 

@@ -22,7 +22,7 @@ from ..mc_chain import price_chain_on_engine, variable_type_code
 from ..utils.calibration import ImpliedVolObjective, chain_calibration_weights, minimize_slsqp
 from ..utils.config import VariableType
 from ..utils.funcs import next_rng_call, set_time_grid, time_grid_steps, timer
-from ..analytic import AnalyticGrid, qvar_prices_from_sums, vanilla_prices_from_capped
+from ..analytic import AnalyticGrid, chain_prices_from_sums, chain_sums
 from ..utils import mgf_pricer as mgfp
 from .logsv_pricer import _broadcast_state, check_many_args, many_job_streams
 from .model_pricer import ModelParams, ModelPricer
@@ -149,13 +149,13 @@ def compute_heston_mgf_grid(v0: float, theta: float, kappa: float, volvol: float
     grid = AnalyticGrid(np.asarray(phi_grid), np.asarray(psi_grid), 1)
     try:
         if a_t0 is not None:
-            grid.set_a(np.asarray(a_t0, dtype=np.complex128).reshape(-1, 1))
+            grid.set_a(np.asarray(a_t0, dtype=np.complex128).reshape(1, -1, 1))
         if b_t0 is not None:
             b0 = np.ascontiguousarray(b_t0, dtype=np.complex128)
             _lib.check(grid.lib.svmc_memcpy_h2d(grid.b.ptr, b0.ctypes.data, b0.nbytes, None))
             _lib.check(grid.lib.svmc_stream_synchronize(None))
         grid.heston_advance(ttm, v0, theta, kappa, volvol, rho, True)
-        return grid.get_log_mgf(), grid.get_a().ravel(), grid._down(grid.b, (grid.n,))
+        return grid.get_log_mgf()[0], grid.get_a().ravel(), grid._down(grid.b, (grid.n,))
     finally:
         grid.close()
 
@@ -174,28 +174,10 @@ def heston_chain_pricer(v0: float, theta: float, kappa: float, volvol: float, rh
     phi_grid, psi_grid, _ = mgfp.get_transform_var_grid(variable_type=variable_type, vol_scaler=vol_scaler)
     grid = AnalyticGrid.acquire(phi_grid, psi_grid, 1)
     try:
-        # the chain's launches queued back to back, one download of every expiry's sums at the end (AnalyticGrid.queue_*)
-        ks = [int(np.asarray(k).size) for k in strikes_ttms]
-        offs = np.concatenate([[0], np.cumsum(ks)]).astype(int)
-        grid.reserve_results(int(offs[-1]))
-        ttm0 = 0.0
-        for i, (ttm, forward, strikes) in enumerate(zip(ttms, forwards, strikes_ttms)):
-            grid.heston_advance(ttm - ttm0, v0, theta, kappa, volvol, rho, True)     # zero a, b == the None branch
-            if vt == 1:
-                grid.queue_capped_sums(float(forward), np.asarray(strikes, dtype=np.float64), int(offs[i]))
-            else:
-                grid.queue_qvar_sums(float(ttm), np.asarray(strikes, dtype=np.float64), int(offs[i]))
-            ttm0 = ttm
-        sums = grid.download_results(int(offs[-1]))
-        prices = []
-        for i, (ttm, forward, discfactor, strikes, types) in enumerate(zip(ttms, forwards, discfactors, strikes_ttms,
-                                                                           optiontypes_ttms)):
-            if vt == 1:
-                prices.append(vanilla_prices_from_capped(sums[offs[i]:offs[i + 1]], float(forward), strikes, types,
-                                                         float(discfactor), True))
-            else:
-                prices.append(qvar_prices_from_sums(sums[offs[i]:offs[i + 1]], float(ttm), types, float(discfactor)))
-        return prices
+        inversion = "vanilla" if vt == 1 else "qvar"
+        sums = chain_sums(grid, ttms, forwards, strikes_ttms,      # have_t0 on zeroed a, b == the reference's None branch
+                          lambda i, dt: grid.heston_advance(dt, v0, theta, kappa, volvol, rho, True), inversion)
+        return chain_prices_from_sums(sums, inversion, ttms, forwards, discfactors, strikes_ttms, optiontypes_ttms)[0]
     finally:
         grid.release()
 

@@ -94,8 +94,8 @@ def compute_logsv_a_mgf_grid(ttm: float, phi_grid: np.ndarray, psi_grid: np.ndar
             a_t0[:, 1] = -np.asarray(theta_grid)
     grid = AnalyticGrid(np.asarray(phi_grid), np.asarray(psi_grid), n)
     try:
-        grid.set_a(a_t0)
-        grid.logsv_advance(ttm, sigma0, theta, kappa1, kappa2, beta, volvol, is_spot_measure, order, vol_backbone_eta)
-        return grid.get_a(), grid.get_log_mgf()
+        grid.set_a(np.asarray(a_t0)[None])
+        grid.logsv_advance(ttm, [[sigma0, theta, kappa1, kappa2, beta, volvol, vol_backbone_eta, 0.0]], is_spot_measure, order)
+        return grid.get_a()[0], grid.get_log_mgf()[0]
     finally:
         grid.close()

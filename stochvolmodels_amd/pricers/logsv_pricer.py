@@ -24,8 +24,7 @@ from ..mc_chain import price_chain_on_engine, variable_type_code
 from ..utils.calibration import ImpliedVolObjective, chain_calibration_weights, minimize_slsqp
 from ..utils.config import VariableType
 from ..utils.funcs import histogram_series, next_rng_call, set_time_grid, time_grid_steps, timer
-from ..analytic import (AnalyticGrid, device_histograms, histogram_edges, qvar_prices_from_sums,
-                        vanilla_prices_from_capped)
+from ..analytic import AnalyticGrid, chain_prices_from_sums, chain_sums, device_histograms, histogram_edges
 from ..utils import mgf_pricer as mgfp
 from .logsv.affine_expansion import ExpansionOrder, _order_code, get_init_conditions_a, note_integrator_flags
 from .logsv.logsv_params import LogSvParams
@@ -144,6 +143,32 @@ def _note_given_up(count, n_grid: int) -> None:
                       RuntimeWarning, stacklevel=3)
 
 
+def _logsv_chain(params_list: Sequence[LogSvParams], ttms, forwards, discfactors, strikes_ttms, optiontypes_ttms,
+                 is_spot_measure: bool, expansion_order, variable_type, vol_scaler, kwargs):
+    """the analytic chain pricing behind logsv_chain_pricer and logsv_chain_pricer_batch: the sets' grids side by side on one
+    AnalyticGrid, the chain through chain_sums (the quadratic-variance inversion at one set only) -> the given-up counts
+    [n_sets], the grid length and finish(), which turns the sums into prices [set][expiry] once the caller has noted the counts"""
+    order = _order_code(expansion_order)
+    inversion = "qvar" if int(getattr(variable_type, "value", variable_type)) == 2 else "vanilla"
+    grids = [mgfp.get_transform_var_grid(variable_type=variable_type, is_spot_measure=is_spot_measure,
+                                         vol_scaler=(set_vol_scaler(sigma0=p.sigma0, ttm=np.min(ttms))
+                                                     if vol_scaler is None else vol_scaler)) for p in params_list]
+    grid = AnalyticGrid.acquire([g[0] for g in grids], [g[1] for g in grids], 5 if order == 2 else 3)
+    try:
+        # [expiry][set][8]: the vol backbone's eta follows the expiry
+        rows = np.array([[[p.sigma0, p.theta, p.kappa1, p.kappa2, p.beta, p.volvol, p.get_vol_backbone_eta(tau=ttm), 0.0]
+                          for p in params_list] for ttm in ttms])
+
+        def advance(i, dt):
+            grid.logsv_advance(dt, rows[i], is_spot_measure, order, rtol=kwargs.get("ode_rtol"), atol=kwargs.get("ode_atol"))
+
+        sums = chain_sums(grid, ttms, forwards, strikes_ttms, advance, inversion)
+        return grid.last_given_up, grid.n, lambda: chain_prices_from_sums(sums, inversion, ttms, forwards, discfactors,
+                                                                          strikes_ttms, optiontypes_ttms, is_spot_measure)
+    finally:
+        grid.release()
+
+
 def logsv_chain_pricer_batch(params_list: Sequence[LogSvParams], ttms: np.ndarray, forwards: np.ndarray,
                              discfactors: np.ndarray, strikes_ttms: Sequence[np.ndarray],
                              optiontypes_ttms: Sequence[np.ndarray], is_spot_measure: bool = True,
@@ -151,41 +176,13 @@ def logsv_chain_pricer_batch(params_list: Sequence[LogSvParams], ttms: np.ndarra
                              ) -> List[List[np.ndarray]]:
     """logsv_chain_pricer (LOG_RETURN, numerical ODE route) for SEVERAL parameter sets on one chain, all sets advanced
     by one launch per expiry and inverted by one launch per expiry: [set][expiry] -> prices.  Each set keeps its own
-    transform grid (set_vol_scaler follows its sigma0, reference :664-666); results are bit-identical to one
-    logsv_chain_pricer call per set.  Not in the reference API: the batched form of its per-set loop (config C5's five
-    sets; the bumped vectors of a finite-difference gradient)."""
-    from ..analytic import AnalyticGridBatch
-    order = _order_code(expansion_order)
-    grids = [mgfp.get_transform_var_grid(variable_type=VariableType.LOG_RETURN, is_spot_measure=is_spot_measure,
-                                         vol_scaler=(set_vol_scaler(sigma0=p.sigma0, ttm=np.min(ttms))
-                                                     if vol_scaler is None else vol_scaler)) for p in params_list]
-    batch = AnalyticGridBatch.acquire([g[0] for g in grids], [g[1] for g in grids], 5 if order == 2 else 3)
-    try:
-        # every expiry's launches are queued back to back (advance, invert, advance, invert, ...) and the sums come back in ONE
-        # download at the end of the chain: no host round trip between expiries
-        ks = [int(np.asarray(k).size) for k in strikes_ttms]
-        n_sets = len(params_list)
-        offs = np.concatenate([[0], np.cumsum([n_sets * k for k in ks])]).astype(int)
-        batch.reserve_results(int(offs[-1]))
-        ttm0 = 0.0
-        for i, (ttm, forward, strikes) in enumerate(zip(ttms, forwards, strikes_ttms)):
-            rows = np.array([[p.sigma0, p.theta, p.kappa1, p.kappa2, p.beta, p.volvol, p.get_vol_backbone_eta(tau=ttm), 0.0]
-                             for p in params_list])
-            batch.logsv_advance(ttm - ttm0, rows, is_spot_measure, order, rtol=kwargs.get("ode_rtol"),
-                                atol=kwargs.get("ode_atol"))
-            batch.queue_capped_sums(float(forward), np.asarray(strikes, dtype=np.float64), int(offs[i]))
-            ttm0 = ttm
-        sums = batch.download_results(int(offs[-1]))
-        _note_given_up(batch.last_given_up, len(grids[0][0]))
-        out = [[] for _ in params_list]
-        for i, (forward, strikes, types, discfactor) in enumerate(zip(forwards, strikes_ttms, optiontypes_ttms, discfactors)):
-            capped = sums[offs[i]:offs[i + 1]].reshape(n_sets, ks[i])
-            for s in range(n_sets):
-                out[s].append(vanilla_prices_from_capped(capped[s], float(forward), strikes, types, float(discfactor),
-                                                         is_spot_measure))
-        return out
-    finally:
-        batch.release()
+    transform grid (set_vol_scaler follows its sigma0, reference :664-666); logsv_chain_pricer is this at one set.  A
+    variable_type= keyword is swallowed by **kwargs and ignored.  Not in the reference API: the batched form of its per-set
+    loop (config C5's five sets; the bumped vectors of a finite-difference gradient)."""
+    given_up, n_grid, finish = _logsv_chain(params_list, ttms, forwards, discfactors, strikes_ttms, optiontypes_ttms,
+                                            is_spot_measure, expansion_order, VariableType.LOG_RETURN, vol_scaler, kwargs)
+    _note_given_up(given_up, n_grid)
+    return finish()
 
 
 class LogSVPricer(ModelPricer):
@@ -469,45 +466,13 @@ def logsv_chain_pricer(params: LogSvParams, ttms: np.ndarray, forwards: np.ndarr
     """analytic LogSV chain prices (reference :669-739): per expiry one launch integrating the coefficient ODEs of every
     transform-grid point from the previous expiry's A, then one launch of per-strike Simpson sums.  LOG_RETURN uses
     the 1000-point phi grid; Q_VAR (calls on the annualised quadratic variance) the 40 000-point psi grid."""
-    vt = int(getattr(variable_type, "value", variable_type))
-    if vt not in (1, 2):
+    if int(getattr(variable_type, "value", variable_type)) not in (1, 2):
         raise NotImplementedError
     note_integrator_flags(is_stiff_solver, is_analytic)       # both accepted: one device integrator answers them (warned once)
-    order = _order_code(expansion_order)
-    if vol_scaler is None:
-        vol_scaler = set_vol_scaler(sigma0=params.sigma0, ttm=np.min(ttms))
-    phi_grid, psi_grid, _ = mgfp.get_transform_var_grid(variable_type=variable_type, is_spot_measure=is_spot_measure,
-                                                        vol_scaler=vol_scaler)
-    grid = AnalyticGrid.acquire(phi_grid, psi_grid, 5 if order == 2 else 3)
-    try:
-        # the chain's launches queued back to back, one download of every expiry's sums at the end (AnalyticGrid.queue_*)
-        ks = [int(np.asarray(k).size) for k in strikes_ttms]
-        offs = np.concatenate([[0], np.cumsum(ks)]).astype(int)
-        grid.reserve_results(int(offs[-1]))
-        ttm0 = 0.0
-        for i, (ttm, forward, strikes) in enumerate(zip(ttms, forwards, strikes_ttms)):
-            eta = params.get_vol_backbone_eta(tau=ttm)
-            grid.logsv_advance(ttm - ttm0, params.sigma0, params.theta, params.kappa1, params.kappa2, params.beta,
-                               params.volvol, is_spot_measure, order, eta, rtol=kwargs.get("ode_rtol"),
-                               atol=kwargs.get("ode_atol"))
-            if vt == 1:
-                grid.queue_capped_sums(float(forward), np.asarray(strikes, dtype=np.float64), int(offs[i]))
-            else:
-                grid.queue_qvar_sums(float(ttm), np.asarray(strikes, dtype=np.float64), int(offs[i]))
-            ttm0 = ttm
-        sums = grid.download_results(int(offs[-1]))
-        _note_given_up(grid.last_given_up, grid.n)
-        prices = []
-        for i, (ttm, forward, strikes, types, discfactor) in enumerate(zip(ttms, forwards, strikes_ttms, optiontypes_ttms,
-                                                                           discfactors)):
-            if vt == 1:
-                prices.append(vanilla_prices_from_capped(sums[offs[i]:offs[i + 1]], float(forward), strikes, types,
-                                                         float(discfactor), is_spot_measure))
-            else:
-                prices.append(qvar_prices_from_sums(sums[offs[i]:offs[i + 1]], float(ttm), types, float(discfactor)))
-        return prices
-    finally:
-        grid.release()
+    given_up, n_grid, finish = _logsv_chain([params], ttms, forwards, discfactors, strikes_ttms, optiontypes_ttms,
+                                            is_spot_measure, expansion_order, variable_type, vol_scaler, kwargs)
+    _note_given_up(int(given_up[0]), n_grid)
+    return finish()[0]
 
 
 def _pdf_setup(params: LogSvParams, ttm: float, is_spot_measure: bool, order: int, variable_type, vol_scaler):
@@ -530,6 +495,35 @@ def _pdf_setup(params: LogSvParams, ttm: float, is_spot_measure: bool, order: in
     return phi_grid, psi_grid, a_t0, var_grid, resident, shift, scale
 
 
+def _logsv_pdfs(params_list: Sequence[LogSvParams], ttm: float, space_grids, orders: Sequence[int], is_spot_measure: bool,
+                variable_type, vol_scaler, kwargs) -> Tuple[List[np.ndarray], np.ndarray, int]:
+    """the density route behind logsv_pdfs and logsv_pdfs_batch: the cases of one expansion order share one AnalyticGrid, one
+    ODE launch and one inversion launch -> (bin masses per case, given-up counts per case, grid length)"""
+    out: List[Optional[np.ndarray]] = [None] * len(params_list)
+    given_up = np.zeros(len(params_list), dtype=int)
+    n_grid = 0
+    for order in sorted(set(orders)):
+        idx = [i for i, o in enumerate(orders) if o == order]
+        setups = [_pdf_setup(params_list[i], ttm, is_spot_measure, order, variable_type, vol_scaler) for i in idx]
+        grid = AnalyticGrid.acquire([s[0] for s in setups], [s[1] for s in setups], 5 if order == 2 else 3)
+        try:
+            if any(np.any(s[2]) for s in setups):
+                grid.set_a(np.stack([s[2] for s in setups]))
+            rows = np.array([[p.sigma0, p.theta, p.kappa1, p.kappa2, p.beta, p.volvol, 1.0, 0.0]
+                             for p in (params_list[i] for i in idx)])
+            grid.logsv_advance(ttm, rows, is_spot_measure, order, rtol=kwargs.get("ode_rtol"), atol=kwargs.get("ode_atol"))
+            spaces = [np.asarray(space_grids[i], dtype=np.float64) for i in idx]
+            scales = [s[6] for s in setups]
+            pdf = grid.pdf_sums([s[3] for s in setups], spaces, [s[5] for s in setups], scales, resident=setups[0][4])
+            n_grid = grid.n
+            for k, i in enumerate(idx):
+                out[i] = (pdf[k] / scales[k]).reshape(spaces[k].shape)
+                given_up[i] = grid.last_given_up[k]
+        finally:
+            grid.release()
+    return out, given_up, n_grid
+
+
 def logsv_pdfs(params: LogSvParams, ttm: float, space_grid: np.ndarray, is_stiff_solver: bool = False,
                is_analytic: bool = False, is_spot_measure: bool = True, expansion_order: ExpansionOrder = ExpansionOrder.SECOND,
                variable_type: VariableType = VariableType.LOG_RETURN, vol_scaler: float = None, **kwargs) -> np.ndarray:
@@ -538,22 +532,12 @@ def logsv_pdfs(params: LogSvParams, ttm: float, space_grid: np.ndarray, is_stiff
     integrating the coefficient ODEs from A(0) = get_init_conditions_a over ttm, one launch inverting over the space grid; the
     log-MGF stays on the device between them.  is_stiff_solver / is_analytic are accepted and answered by the one device
     integrator (warned once); grid points it gives up on are counted and warned about (LAST_ANALYTIC_GIVEN_UP).
-    ode_rtol= / ode_atol= as logsv_chain_pricer."""
+    ode_rtol= / ode_atol= as logsv_chain_pricer.  This is logsv_pdfs_batch at one case."""
     note_integrator_flags(is_stiff_solver, is_analytic)
-    order = _order_code(expansion_order)
-    phi_grid, psi_grid, a_t0, var_grid, resident, shift, scale = _pdf_setup(params, ttm, is_spot_measure, order, variable_type,
-                                                                            vol_scaler)
-    grid = AnalyticGrid.acquire(phi_grid, psi_grid, 5 if order == 2 else 3)
-    try:
-        if np.any(a_t0):
-            grid.set_a(a_t0)
-        grid.logsv_advance(ttm, params.sigma0, params.theta, params.kappa1, params.kappa2, params.beta, params.volvol,
-                           is_spot_measure, order, 1.0, rtol=kwargs.get("ode_rtol"), atol=kwargs.get("ode_atol"))
-        pdf = grid.pdf_sums(var_grid, np.asarray(space_grid, dtype=np.float64), shift=shift, scale=scale, resident=resident)
-        _note_given_up(grid.last_given_up, grid.n)
-        return (pdf / scale).reshape(np.shape(space_grid))
-    finally:
-        grid.release()
+    out, given_up, n_grid = _logsv_pdfs([params], ttm, [space_grid], [_order_code(expansion_order)], is_spot_measure,
+                                        variable_type, vol_scaler, kwargs)
+    _note_given_up(int(given_up[0]), n_grid)
+    return out[0]
 
 
 def logsv_pdfs_batch(params_list: Sequence[LogSvParams], ttm: float, space_grids: Sequence[np.ndarray],
@@ -563,9 +547,8 @@ def logsv_pdfs_batch(params_list: Sequence[LogSvParams], ttm: float, space_grids
     """logsv_pdfs for several cases of ONE variable, maturity and measure: case i has the parameters params_list[i], the space
     grid space_grids[i] (all of one length) and the expansion order expansion_orders[i] (one order for all when not a
     sequence).  The cases of one expansion order share one ODE launch and one inversion launch (the coefficient arrays of the
-    two orders differ in width, so a list holding both orders takes two launches of each); every result is bit-equal to its
-    single logsv_pdfs call.  Not in the reference API: the batched form of the six calls behind one panel of its density figure."""
-    from ..analytic import AnalyticGridBatch
+    two orders differ in width, so a list holding both orders takes two launches of each).  Not in the reference API: the
+    batched form of the six calls behind one panel of its density figure."""
     params_list = list(params_list)
     if not isinstance(expansion_orders, (list, tuple)):
         expansion_orders = [expansion_orders] * len(params_list)
@@ -575,29 +558,7 @@ def logsv_pdfs_batch(params_list: Sequence[LogSvParams], ttm: float, space_grids
     spaces = [np.asarray(g, dtype=np.float64) for g in space_grids]
     if len({g.size for g in spaces}) > 1:
         raise ValueError("logsv_pdfs_batch: the space grids must have one length")
-    out: List[Optional[np.ndarray]] = [None] * len(params_list)
-    given_up = np.zeros(len(params_list), dtype=int)
-    n_grid = 0
-    for order in sorted(set(orders)):
-        idx = [i for i, o in enumerate(orders) if o == order]
-        setups = [_pdf_setup(params_list[i], ttm, is_spot_measure, order, variable_type, vol_scaler) for i in idx]
-        batch = AnalyticGridBatch.acquire([s[0] for s in setups], [s[1] for s in setups], 5 if order == 2 else 3)
-        try:
-            a_t0 = np.stack([s[2] for s in setups])
-            if np.any(a_t0):
-                batch.set_a(a_t0)
-            rows = np.array([[p.sigma0, p.theta, p.kappa1, p.kappa2, p.beta, p.volvol, 1.0, 0.0]
-                             for p in (params_list[i] for i in idx)])
-            batch.logsv_advance(ttm, rows, is_spot_measure, order, rtol=kwargs.get("ode_rtol"), atol=kwargs.get("ode_atol"))
-            scales = [s[6] for s in setups]
-            pdf = batch.pdf_sums([s[3] for s in setups], [spaces[i].ravel() for i in idx], [s[5] for s in setups], scales,
-                                 resident=setups[0][4])
-            n_grid = batch.n
-            for k, i in enumerate(idx):
-                out[i] = (pdf[k] / scales[k]).reshape(spaces[i].shape)
-                given_up[i] = batch.last_given_up[k]
-        finally:
-            batch.release()
+    out, given_up, n_grid = _logsv_pdfs(params_list, ttm, spaces, orders, is_spot_measure, variable_type, vol_scaler, kwargs)
     _note_given_up(given_up, n_grid)
     return out
 

@@ -86,7 +86,7 @@ def vanilla_slice_pricer_with_mgf_grid(log_mgf_grid: np.ndarray, phi_grid: np.nd
     grid = AnalyticGrid(phi_grid, np.zeros_like(phi_grid), 1)
     try:
         lm = grid._up(np.ascontiguousarray(log_mgf_grid, dtype=np.complex128))
-        capped = grid.capped_sums(forward, np.asarray(strikes, dtype=np.float64), log_mgf_ptr=lm.ptr)
+        capped = grid.capped_sums(forward, np.asarray(strikes, dtype=np.float64), log_mgf_ptr=lm.ptr)[0]
         lm.free()
     finally:
         grid.close()

@@ -7,6 +7,7 @@ The analytic route's device kernels against independent high-precision truth:
     1e-18), every component A_k and log E, both measures, both expansion orders, 1/365 to 5 years, and a chained pair of
     slices with different vol_backbone_eta (the a_t0 carry);
   * the batch contract of logsv_chain_pricer_batch across the row / lane switch (8, 9, 16 and 17 sets);
+  * the single C entry points svmc_logsv_mgf_grid / svmc_mgf_vanilla_slice against their batch forms at one set, bit for bit;
   * the inversion kernels (mgf_vanilla_slice_kernel, mgf_qvar_slice_kernel, mgf_gamma_slice_kernel) against the same
     Simpson-weighted sum evaluated in mpmath from the same doubles, at grid lengths and strike counts around the kernels'
     256-thread and 32-strike boundaries, and the nansum contract (NaN terms dropped, inf kept, a -inf log E a zero term).
@@ -212,6 +213,32 @@ def test_logsv_batch_bit_identical_across_form_switch():
             batch = pricer.price_chain_batch(chain, sets[:n], is_spot_measure=spot)
             for i, (a, b) in enumerate(zip(batch, single[:n])):
                 np.testing.assert_array_equal(np.stack(a), b, err_msg=f"{n} sets, set {i}, spot {spot}")
+
+
+@pytest.mark.parametrize("order", [1, 2])
+def test_single_entry_points_are_their_batch_forms_at_one_set(L, order):
+    """svmc_logsv_mgf_grid and svmc_mgf_vanilla_slice, which the Python package no longer calls, against
+    svmc_logsv_mgf_grid_batch and svmc_mgf_vanilla_slice_batch at n_sets = 1: a 50-point grid (a partial last block of the row
+    form), two chained expiries, 3 strikes -- A, log E and the sums bit for bit"""
+    n, nc = 50, 5 if order == 2 else 3
+    phi = -0.5 + 1j * np.linspace(0.0, 5.6 / 0.16, n)
+    psi = np.zeros(n, dtype=np.complex128)
+    params = (0.8376, 1.0413, 3.1844, 3.058, 0.1514, 1.8458)
+    forward, strikes = 1.02, np.array([0.8, 1.0, 1.3])
+    dphi, dpsi = Dev(L, phi), Dev(L, psi)
+    single = [Dev(L, np.zeros((n, nc), dtype=np.complex128)), Dev(L, n_doubles=2 * n), Dev(L, n_doubles=3)]
+    batch = [Dev(L, np.zeros((n, nc), dtype=np.complex128)), Dev(L, n_doubles=2 * n), Dev(L, n_doubles=3)]
+    for dt, eta in ((0.1, 1.0), (0.15, 1.1)):
+        _check(L.svmc_logsv_mgf_grid(dphi.ptr, dpsi.ptr, n, dt, *params, 1, order, eta, single[0].ptr, single[1].ptr,
+                                     ODE_RTOL, ODE_ATOL, None))
+        _check(L.svmc_mgf_vanilla_slice(dphi.ptr, single[1].ptr, n, forward, _pf(strikes), 3, single[2].ptr, None))
+        _check(L.svmc_logsv_mgf_grid_batch(dphi.ptr, dpsi.ptr, n, 1, dt, _pf(set_row(params, eta)), 1, order, batch[0].ptr,
+                                           batch[1].ptr, ODE_RTOL, ODE_ATOL, None))
+        _check(L.svmc_mgf_vanilla_slice_batch(dphi.ptr, batch[1].ptr, n, 1, forward, _pf(strikes), 3, batch[2].ptr, None))
+        for a, b, shape, dtype in zip(single, batch, ((n, nc), n, 3), (np.complex128, np.complex128, np.float64)):
+            got = a.get(shape, dtype)
+            assert np.all(np.isfinite(got.view(np.float64)))
+            np.testing.assert_array_equal(got, b.get(shape, dtype))
 
 
 # ---- g: the inversion kernels against the exact Simpson-weighted sum ------------------------------------------------------

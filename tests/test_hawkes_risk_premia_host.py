@@ -31,7 +31,7 @@ def _params0(f):
 
 
 class FakeBatch:
-    """AnalyticGridBatch stand-in: records the host's calls, prices every strike at 0.1, normalizer 1, gamma forward 2"""
+    """AnalyticGrid stand-in: records the host's calls, prices every strike at 0.1, normalizer 1, gamma forward 2"""
     calls = []
 
     @classmethod
@@ -160,7 +160,7 @@ def test_fd_step_default_is_unchanged():
 def test_chain_orchestration_and_zip_truncation(golden, monkeypatch):
     hp = _hp()
     f = golden("hawkes_risk_premia")
-    monkeypatch.setattr(hp, "AnalyticGridBatch", FakeBatch)
+    monkeypatch.setattr(hp, "AnalyticGrid", FakeBatch)
     FakeBatch.calls = []
     chain = _chain(f)
     p = _params0(f)
@@ -204,7 +204,7 @@ def test_errors_before_any_device_call(golden, monkeypatch):
     from stochvolmodels_amd.utils.config import VariableType
     hp = _hp()
     f = golden("hawkes_risk_premia")
-    monkeypatch.setattr(hp, "AnalyticGridBatch", NoDevice)
+    monkeypatch.setattr(hp, "AnalyticGrid", NoDevice)
     monkeypatch.setattr(mgfp, "gamma_slice_prices", NoDevice.acquire)
     chain = _chain(f)
     p = hp.HawkesJDParams(risk_premia_gamma=1.0)

@@ -56,13 +56,13 @@ def split_call(vt, space, repeats):
         grid = AnalyticGrid.acquire(phi, psi, 5)
         try:
             if np.any(a_t0):
-                grid.set_a(a_t0)
+                grid.set_a(a_t0[None])
             _lib.check(L.svmc_stream_synchronize(None))
             t0 = time.perf_counter()
-            grid.logsv_advance(TTM, TEST.sigma0, TEST.theta, TEST.kappa1, TEST.kappa2, TEST.beta, TEST.volvol, True, 2, 1.0)
+            grid.logsv_advance(TTM, [[TEST.sigma0, TEST.theta, TEST.kappa1, TEST.kappa2, TEST.beta, TEST.volvol, 1.0, 0.0]], True, 2)
             _lib.check(L.svmc_stream_synchronize(None))
             t1 = time.perf_counter()
-            grid.pdf_sums(var, space, shift=shift, scale=scale, resident=resident)
+            grid.pdf_sums([var], [space], [shift], [scale], resident=resident)
             t2 = time.perf_counter()
         finally:
             grid.release()
