@@ -307,6 +307,39 @@ __device__ __forceinline__ void progress_priority(int stage)
     }
 }
 
+// where a launch stands on that ladder: wave-uniform counters, carried from slice to slice of a chain
+struct LogsvProgress {
+    int quarter;                       // a quarter of the launch's steps, rounded up
+    int stage = 0, next_stage_t = 0;
+};
+
+// what a slice's time loop leaves for logsv_fold_acc
+struct LogsvSliceSums {
+    double xacc, acc, s2_start;
+};
+
+// ONE slice of a LogSV path in the full-launch form, the statements every full-launch generator runs (logsv_rng_kernel, the
+// whole-chain kernels through logsv_chain_full_body): nb steps from step `step0` of the lane's stream on the volatility s, which
+// it advances; `t0` is how many steps the launch ran before this slice (the priority ladder's clock).  It returns the
+// accumulators instead of folding them: the whole-chain body keeps x and qvar in LDS while this runs.
+__device__ __forceinline__ LogsvSliceSums logsv_slice_full(const LogsvFast c, double &s, const PhiloxLane &lane, uint32_t step0, int t0,
+                                                           int nb, const RngTables &tab, const double *exp_table, LogsvProgress &prog)
+{
+    const auto exp_of = [&](double v) { return exp2u_tab(v, exp_table); };  // L is carried in units of ln2/256
+    double L = log_state(s) * LOG_UNITS_PER_NAT;                                                      // :1039
+    double s2 = square_rn(s), acc = 0.0, xacc = 0.0;
+    const double s2_start = s2;
+    rng_time_loop(
+        lane, step0, nb, tab, [&](double z0, double z1) { logsv_step_acc(c, xacc, L, s, s2, acc, z0, z1, exp_of); },
+        [&](int t) {
+            if (t0 + t >= prog.next_stage_t) {             // wave-uniform
+                progress_priority(prog.stage++);
+                prog.next_stage_t += prog.quarter;
+            }
+        });
+    return {xacc, acc, s2_start};
+}
+
 __global__ __launch_bounds__(RNG_BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8), amdgpu_num_sgpr(SVMC_RNG_SGPRS))) void logsv_rng_kernel(double *__restrict__ x, double *__restrict__ sigma,
                                                           double *__restrict__ qvar, size_t n, int nb_steps,
                                                           LogsvFast c, uint64_t seed, uint32_t c3,
@@ -317,7 +350,6 @@ __global__ __launch_bounds__(RNG_BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8)
     __shared__ double s_exp[256];
     const RngTables tab = stage_tables(s_tab, s_exp);
     clock_probe_stamp(probe, 0);
-    const auto exp_of = [&](double v) { return exp2u_tab(v, s_exp); };     // L is carried in units of ln2/256
     const size_t p = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
     const bool active = p < n;
     double xv = 0.0, s = 1.0, q = 0.0;
@@ -331,22 +363,10 @@ __global__ __launch_bounds__(RNG_BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8)
             s = sigma[p];
             q = qvar[p];
         }
-        double L = log_state(s) * LOG_UNITS_PER_NAT;                                                  // :1039
-        double s2 = square_rn(s), acc = 0.0, xacc = 0.0;
-        const double s2_start = s2;
         const PhiloxLane lane = philox_prepare(seed, c3, path_offset + p);
-        const int quarter = (nb_steps + 3) >> 2;
-        int stage = 0, next_stage_t = 0;
-        rng_time_loop(
-            lane, step_offset, nb_steps, tab,
-            [&](double z0, double z1) { logsv_step_acc(c, xacc, L, s, s2, acc, z0, z1, exp_of); },
-            [&](int t) {
-                if (t >= next_stage_t) {                   // wave-uniform
-                    progress_priority(stage++);
-                    next_stage_t += quarter;
-                }
-            });
-        logsv_fold_acc(c, xv, q, xacc, acc, s2_start, square_rn(s));
+        LogsvProgress prog = {(nb_steps + 3) >> 2};
+        const LogsvSliceSums a = logsv_slice_full(c, s, lane, step_offset, 0, nb_steps, tab, s_exp, prog);
+        logsv_fold_acc(c, xv, q, a.xacc, a.acc, a.s2_start, square_rn(s));
         x[p] = xv;
         sigma[p] = s;
         qvar[p] = q;
@@ -376,6 +396,19 @@ __device__ __forceinline__ void logsv_gen_time_loop(const PhiloxLane &lane, uint
         [&]() { logsv_step_acc_mid(h, k); }, [&]() { logsv_step_acc_back(s, acc, h); });
 }
 
+// ONE slice of a LogSV path in the few-waves form, the statements every few-waves generator runs (logsv_rng_lat_kernel, the
+// whole-chain kernels through logsv_chain_lat_body): logsv_slice_full's arithmetic on the pipelined loop, folded into (xv, q)
+template <int LOOP>
+__device__ __forceinline__ void logsv_slice_lat(const LogsvFast c, double &xv, double &s, double &q, const PhiloxLane &lane, uint32_t step0,
+                                                int nb, const RngTables &tab, const double *exp_table)
+{
+    double L = log_state(s) * LOG_UNITS_PER_NAT;                                                      // :1039
+    double acc = 0.0, xacc = 0.0;
+    const double s2_start = square_rn(s);
+    logsv_gen_time_loop<LOOP>(lane, step0, nb, tab, c, xacc, L, s, acc, exp_table);
+    logsv_fold_acc(c, xv, q, xacc, acc, s2_start, square_rn(s));
+}
+
 template <int LOOP, int WAVES, int TB>
 __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) void logsv_rng_lat_kernel(
     double *__restrict__ x, double *__restrict__ sigma, double *__restrict__ qvar, size_t n, int nb_steps, LogsvFast c,
@@ -398,12 +431,8 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
             s = sigma[p];
             q = qvar[p];
         }
-        double L = log_state(s) * LOG_UNITS_PER_NAT;                                                  // :1039
-        double acc = 0.0, xacc = 0.0;
-        const double s2_start = square_rn(s);
         const PhiloxLane lane = philox_prepare(seed, c3, path_offset + p);
-        logsv_gen_time_loop<LOOP>(lane, step_offset, nb_steps, tab, c, xacc, L, s, acc, s_exp);
-        logsv_fold_acc(c, xv, q, xacc, acc, s2_start, square_rn(s));
+        logsv_slice_lat<LOOP>(c, xv, s, q, lane, step_offset, nb_steps, tab, s_exp);
         x[p] = xv;
         sigma[p] = s;
         qvar[p] = q;
@@ -458,178 +487,19 @@ static bool few_waves_launch(size_t n_path)
 // constants (dt, vol backbone) and its own epilogue (snapshot row i, spot partials column pair i).  Eight 128-step
 // launches each pay their own ramp-up and ramp-down (C4: 8 x 1.03 ms against 7.44 ms for one 1024-step launch);
 // here the chain pays one.  L and sigma^2 are re-derived from sigma at every slice start exactly as a fresh launch
-// would, so the results are the bits of the slice-by-slice path.
+// would (the slice is the one function the single-slice kernels call), so the results are the bits of the slice-by-slice path.
 constexpr int MAX_CHAIN_SLICES = 16;
 struct ChainSlices {
     LogsvFast c[MAX_CHAIN_SLICES];
     double forward[MAX_CHAIN_SLICES];
     int nb_steps[MAX_CHAIN_SLICES];
     int m, total_steps = 0;
+    __device__ __forceinline__ LogsvFast consts(int i) const { return c[i]; }
 };
-
-#ifndef SVMC_CHAIN_WAVES
-#define SVMC_CHAIN_WAVES 8, 8          // A/B hook: residency of the whole-chain kernel (7, 8 lifts the 64-VGPR cap)
-#endif
-// The whole-chain kernel runs 1024-thread blocks: two blocks per CU share the CU's LDS, which leaves room -- beside the
-// draw's 32 KB table -- to PARK each path's x and qvar (16 KB per block) while the time loop runs.  They are dead inside
-// the loop (the loop advances the accumulators, logsv_fold_acc folds them in at the slice's end) but live across it, and
-// in registers they pushed the kernel over the 64 VGPRs that eight waves per SIMD allow: the round-2 kernel spilled 68
-// bytes per lane to scratch at every slice boundary (2.4 x its algorithmic HBM traffic).  Now: no scratch.
-#ifndef SVMC_CHAIN_BLOCK
-#define SVMC_CHAIN_BLOCK 1024
-#endif
-#ifndef SVMC_CHAIN_SGPRS
-#define SVMC_CHAIN_SGPRS 80            // the slice loop's scalars on top of the stepping loop's; 80 still admits 8 waves per SIMD
-#endif
-constexpr int CHAIN_BLOCK = SVMC_CHAIN_BLOCK;
-static inline unsigned chain_grid(size_t n) { return static_cast<unsigned>((n + CHAIN_BLOCK - 1) / CHAIN_BLOCK); }
-
-__global__ __launch_bounds__(CHAIN_BLOCK) __attribute__((amdgpu_waves_per_eu(SVMC_CHAIN_WAVES), amdgpu_num_sgpr(SVMC_CHAIN_SGPRS))) void logsv_chain_rng_kernel(
-    double *__restrict__ x, double *__restrict__ sigma, double *__restrict__ qvar, size_t n, ChainSlices cs, uint64_t seed,
-    uint32_t c3, uint64_t path_offset, uint32_t step_offset, double *__restrict__ x_snap, double *__restrict__ q_snap,
-    double *__restrict__ partials, StateInit init, uint64_t *probe)
-{
-    __shared__ RngTablesLds s_tab;
-    __shared__ double s_exp[256];
-    __shared__ double s_park[2 * CHAIN_BLOCK];             // [0, B): x, [B, 2B): qvar -- lane t owns elements t and B + t
-    const RngTables tab = stage_tables(s_tab, s_exp);
-    clock_probe_stamp(probe, 0);
-    const auto exp_of = [&](double v) { return exp2u_tab(v, s_exp); };     // L is carried in units of ln2/256
-    // the path index is re-derived from threadIdx.x wherever it is needed (opaque to CSE): one VGPR across the time loop
-    // instead of the 64-bit index and the addresses formed from it
-    const auto path_index = [&]() {
-        uint32_t t = threadIdx.x;
-        asm volatile("" : "+v"(t));
-        return static_cast<size_t>(blockIdx.x) * CHAIN_BLOCK + t;
-    };
-    const bool active = path_index() < n;
-    double s = 1.0;
-    {
-        double xv = 0.0, q = 0.0;
-        if (init.uniform) {                                // wave-uniform
-            xv = init.x0;
-            s = init.vol0;
-            q = init.qvar0;
-        } else if (active) {
-            const size_t p = path_index();
-            xv = x[p];
-            s = sigma[p];
-            q = qvar[p];
-        }
-        s_park[threadIdx.x] = xv;
-        s_park[CHAIN_BLOCK + threadIdx.x] = q;
-    }
-    const PhiloxLane lane = philox_prepare(seed, c3, path_offset + path_index());
-    const int quarter = (cs.total_steps + 3) >> 2;
-    int stage = 0, next_stage_t = 0, tg = 0;
-    for (int i = 0; i < cs.m; ++i) {
-        const int nb = cs.nb_steps[i];
-        double xv = 0.0, q = 0.0;
-        {   // every lane steps, the lanes past the last path on a dummy state: inside `if (active)` the progress counters
-            // would be divergent values (vector registers, exec-masked branches in the time loop)
-            const LogsvFast c = cs.c[i];
-            double L = log_state(s) * LOG_UNITS_PER_NAT;                                              // :1039
-            double s2 = square_rn(s), acc = 0.0, xacc = 0.0;
-            const double s2_start = s2;
-            rng_time_loop(
-                lane, step_offset + static_cast<uint32_t>(tg), nb, tab,
-                [&](double z0, double z1) { logsv_step_acc(c, xacc, L, s, s2, acc, z0, z1, exp_of); },
-                [&](int t) {
-                    if (tg + t >= next_stage_t) {          // wave-uniform
-                        progress_priority(stage++);
-                        next_stage_t += quarter;
-                    }
-                });
-            xv = s_park[threadIdx.x];                      // a lane reads back what it alone wrote: no barrier needed
-            q = s_park[CHAIN_BLOCK + threadIdx.x];
-            logsv_fold_acc(c, xv, q, xacc, acc, s2_start, square_rn(s));
-            s_park[threadIdx.x] = xv;
-            s_park[CHAIN_BLOCK + threadIdx.x] = q;
-        }
-        tg += nb;
-        const SliceOut so = {x_snap + static_cast<size_t>(i) * n, q_snap ? q_snap + static_cast<size_t>(i) * n : nullptr,
-                             partials + 2 * static_cast<size_t>(i) * ((n + 63) >> 6), cs.forward[i], (n + 63) >> 6};
-        slice_epilogue(so, path_index(), active, xv, q);
-    }
-    if (active) {
-        const size_t p = path_index();
-        x[p] = s_park[threadIdx.x];
-        sigma[p] = s;
-        qvar[p] = s_park[CHAIN_BLOCK + threadIdx.x];
-    }
-    clock_probe_stamp(probe, 1);
-}
-
-// logsv_chain_rng_kernel for a launch of a few waves per SIMD (see logsv_rng_lat_kernel): the same statements, the same bits
-template <int LOOP, int WAVES, int TB>
-__global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) void logsv_chain_rng_lat_kernel(
-    double *__restrict__ x, double *__restrict__ sigma, double *__restrict__ qvar, size_t n, ChainSlices cs, uint64_t seed,
-    uint32_t c3, uint64_t path_offset, uint32_t step_offset, double *__restrict__ x_snap, double *__restrict__ q_snap,
-    double *__restrict__ partials, StateInit init, uint64_t *probe)
-{
-    __shared__ RngTablesLds s_tab;
-    __shared__ double s_exp[256];
-    const RngTables tab = stage_tables(s_tab, s_exp);
-    clock_probe_stamp(probe, 0);
-    const size_t p = static_cast<size_t>(blockIdx.x) * TB + threadIdx.x;
-    const bool active = p < n;
-    double xv = 0.0, s = 1.0, q = 0.0;                     // (a few waves per SIMD: x and qvar stay in registers)
-    if (init.uniform) {
-        xv = init.x0;
-        s = init.vol0;
-        q = init.qvar0;
-    } else if (active) {
-        xv = x[p];
-        s = sigma[p];
-        q = qvar[p];
-    }
-    const PhiloxLane lane = philox_prepare(seed, c3, path_offset + p);
-    int tg = 0;
-    for (int i = 0; i < cs.m; ++i) {
-        const int nb = cs.nb_steps[i];
-        const LogsvFast c = cs.c[i];
-        double L = log_state(s) * LOG_UNITS_PER_NAT;                                                  // :1039
-        double acc = 0.0, xacc = 0.0;
-        const double s2_start = square_rn(s);
-        logsv_gen_time_loop<LOOP>(lane, step_offset + static_cast<uint32_t>(tg), nb, tab, c, xacc, L, s, acc, s_exp);
-        logsv_fold_acc(c, xv, q, xacc, acc, s2_start, square_rn(s));
-        tg += nb;
-        const SliceOut so = {x_snap + static_cast<size_t>(i) * n, q_snap ? q_snap + static_cast<size_t>(i) * n : nullptr,
-                             partials + 2 * static_cast<size_t>(i) * ((n + 63) >> 6), cs.forward[i], (n + 63) >> 6};
-        slice_epilogue(so, p, active, xv, q);
-    }
-    if (active) {
-        x[p] = xv;
-        sigma[p] = s;
-        qvar[p] = q;
-    }
-    clock_probe_stamp(probe, 1);
-}
-
-// The few-waves form of the LogSV generators.
-using LogsvSliceKernel = void (*)(double *, double *, double *, size_t, int, LogsvFast, uint64_t, uint32_t, uint64_t, uint32_t, SliceOut,
-                                  StateInit, uint64_t *);
-using LogsvChainKernel = void (*)(double *, double *, double *, size_t, ChainSlices, uint64_t, uint32_t, uint64_t, uint32_t, double *,
-                                  double *, double *, StateInit, uint64_t *);
-struct LogsvLatVariant {
-    LogsvSliceKernel slice;
-    LogsvChainKernel chain;
-    int block;
-};
-static const LogsvLatVariant LOGSV_FEW_WAVES_KERNELS = {logsv_rng_lat_kernel<GEN_LOOP_PIPE, 4, FEW_BLOCK>,
-                                                        logsv_chain_rng_lat_kernel<GEN_LOOP_PIPE, 4, FEW_BLOCK>, FEW_BLOCK};
-
-// -> the few-waves kernels a launch of n_path paths runs, or null: the full-launch kernels
-static const LogsvLatVariant *logsv_lat_variant(size_t n_path)
-{
-    return few_waves_launch(n_path) ? &LOGSV_FEW_WAVES_KERNELS : nullptr;
-}
-
-static inline unsigned lat_grid(size_t n, int block = FEW_BLOCK) { return static_cast<unsigned>((n + block - 1) / block); }
 
 // ---- many independent jobs of one chain in ONE stepping launch (svmc_logsv_chain_price_many / svmc_heston_chain_price_many)
 // blockIdx.y = job, blockIdx.x = block of that job's n paths; path p of job j draws philox_prepare(seed_j, c3_j, path_offset + p)
-// and runs the statements of the one-job kernels above from the start state (0, vol0_j, 0), so job j's snapshots and per-wave
+// and runs the body of the one-job kernels from the start state (0, vol0_j, 0), so job j's snapshots and per-wave
 // spot partials are those of a single call with (seed_j, call_id_j), bit for bit.  Outputs go to row j m + i (expiry i of job j)
 // in the set-major layout of logsv_chain_rng_sets_kernel: ONE payoff launch (blockIdx.z = job) and ONE finish launch serve
 // every job.  The terminal state is not written back (no job owns the session's state arrays).
@@ -639,7 +509,7 @@ struct ManySlices {
     int nb_steps[MAX_CHAIN_SLICES];
     int m, total_steps = 0;
 };
-// the per-job device table, one upload per call: the (job, expiry) constants [J][m] (LogsvFast, or HestonConsts + QeConsts),
+// the per-job device table, one upload per call: the (job, expiry) constants [J][m] (LogsvFast, or HestonManyConsts),
 // then per job the start vol (variance for Heston), the Philox key and the call id's counter word
 struct ManyJobs {
     const void *consts;
@@ -663,97 +533,236 @@ __device__ __forceinline__ T uniform_load(const T *p)
     return out;
 }
 
-__global__ __launch_bounds__(CHAIN_BLOCK) __attribute__((amdgpu_waves_per_eu(SVMC_CHAIN_WAVES), amdgpu_num_sgpr(SVMC_CHAIN_SGPRS))) void logsv_chain_rng_many_kernel(
-    size_t n, ManySlices cs, ManyJobs jobs, uint64_t path_offset, double *__restrict__ x_snap, double *__restrict__ q_snap,
-    double *__restrict__ partials, uint64_t *probe)
+// a (job, expiry) entry of the table.  Heston's: the constants of one slice, also what a one-job source hands the Heston body
+struct HestonManyConsts {
+    HestonConsts c;
+    QeConsts qc;
+};
+// LogSV's entry goes through uniform_load; Heston's step has no scalar-operand constraint and the compiler issues the plain load
+// of a job-uniform address as scalar loads on its own (forced through uniform_load the Heston kernels spill to scratch)
+__device__ __forceinline__ LogsvFast many_consts_load(const LogsvFast *p) { return uniform_load(p); }
+__device__ __forceinline__ HestonManyConsts many_consts_load(const HestonManyConsts *p) { return *p; }
+
+// Where a whole-chain body's job comes from.  The LogSV and Heston chain bodies are written once over a job source and run the
+// same statements -- hence give the same bits -- whichever one hands them the job:
+//   ChainArgs<Slices>   the one-job kernels: everything is a kernel argument (Slices = ChainSlices | HestonChainSlices); the path
+//                       starts from `init` or the state arrays at step `step_offset` of its stream, expiry i goes to row i, and
+//                       the terminal state is written back
+//   ManyTable<Consts>   the many-job kernels: job blockIdx.y of the device table (Consts = LogsvFast | HestonManyConsts); the path
+//                       starts from (0, vol0_j, 0) at step 0, expiry i goes to row j m + i, nothing is written back
+template <class Slices>
+struct ChainArgs {
+    const Slices &cs;
+    uint64_t seed_;
+    uint32_t c3_, step_offset;
+    const StateInit &init;
+    double *__restrict__ x, *__restrict__ vol, *__restrict__ qvar;
+
+    __device__ __forceinline__ int m() const { return cs.m; }
+    __device__ __forceinline__ int nb_steps(int i) const { return cs.nb_steps[i]; }
+    __device__ __forceinline__ int total_steps() const { return cs.total_steps; }
+    __device__ __forceinline__ double forward(int i) const { return cs.forward[i]; }
+    __device__ __forceinline__ auto consts(int i) const { return cs.consts(i); }
+    __device__ __forceinline__ uint64_t seed() const { return seed_; }
+    __device__ __forceinline__ uint32_t c3() const { return c3_; }
+    __device__ __forceinline__ uint32_t step_origin() const { return step_offset; }
+    __device__ __forceinline__ size_t row(int i) const { return static_cast<size_t>(i); }
+    // (the lanes past the last path get the uniform start too, or a dummy state: the LogSV bodies step them)
+    __device__ __forceinline__ void start(size_t p, bool active, double &xv, double &v, double &q) const
+    {
+        xv = 0.0;
+        v = 1.0;
+        q = 0.0;
+        if (init.uniform) {                               // wave-uniform
+            xv = init.x0;
+            v = init.vol0;
+            q = init.qvar0;
+        } else if (active) {
+            xv = x[p];
+            v = vol[p];
+            q = qvar[p];
+        }
+    }
+    __device__ __forceinline__ void finish(size_t p, double xv, double v, double q) const
+    {
+        x[p] = xv;
+        vol[p] = v;
+        qvar[p] = q;
+    }
+};
+
+template <class Consts>
+struct ManyTable {
+    const ManySlices &cs;
+    const ManyJobs &jobs;
+
+    __device__ __forceinline__ int job() const { return blockIdx.y; }
+    __device__ __forceinline__ int m() const { return cs.m; }
+    __device__ __forceinline__ int nb_steps(int i) const { return cs.nb_steps[i]; }
+    __device__ __forceinline__ int total_steps() const { return cs.total_steps; }
+    __device__ __forceinline__ double forward(int i) const { return cs.forward[i]; }
+    __device__ __forceinline__ Consts consts(int i) const
+    {
+        const Consts *__restrict__ cj = static_cast<const Consts *>(jobs.consts) + static_cast<size_t>(job()) * cs.m;
+        return many_consts_load(cj + i);
+    }
+    __device__ __forceinline__ uint64_t seed() const { return uniform_load(jobs.seed + job()); }
+    __device__ __forceinline__ uint32_t c3() const { return uniform_load(jobs.c3 + job()); }
+    __device__ __forceinline__ uint32_t step_origin() const { return 0u; }
+    __device__ __forceinline__ size_t row(int i) const { return static_cast<size_t>(job()) * cs.m + i; }
+    __device__ __forceinline__ void start(size_t, bool, double &xv, double &v, double &q) const
+    {
+        xv = 0.0;
+        v = uniform_load(jobs.vol0 + job());
+        q = 0.0;
+    }
+    __device__ __forceinline__ void finish(size_t, double, double, double) const {}
+};
+
+#ifndef SVMC_CHAIN_WAVES
+#define SVMC_CHAIN_WAVES 8, 8          // A/B hook: residency of the whole-chain kernel (7, 8 lifts the 64-VGPR cap)
+#endif
+// The whole-chain kernel runs 1024-thread blocks: two blocks per CU share the CU's LDS, which leaves room -- beside the
+// draw's 32 KB table -- to PARK each path's x and qvar (16 KB per block) while the time loop runs.  They are dead inside
+// the loop (the loop advances the accumulators, logsv_fold_acc folds them in at the slice's end) but live across it, and
+// in registers they pushed the kernel over the 64 VGPRs that eight waves per SIMD allow: the round-2 kernel spilled 68
+// bytes per lane to scratch at every slice boundary (2.4 x its algorithmic HBM traffic).  Now: no scratch.
+#ifndef SVMC_CHAIN_BLOCK
+#define SVMC_CHAIN_BLOCK 1024
+#endif
+#ifndef SVMC_CHAIN_SGPRS
+#define SVMC_CHAIN_SGPRS 80            // the slice loop's scalars on top of the stepping loop's; 80 still admits 8 waves per SIMD
+#endif
+constexpr int CHAIN_BLOCK = SVMC_CHAIN_BLOCK;
+static inline unsigned chain_grid(size_t n) { return static_cast<unsigned>((n + CHAIN_BLOCK - 1) / CHAIN_BLOCK); }
+
+// the body of the full-launch whole-chain kernels (logsv_chain_rng_kernel, logsv_chain_rng_many_kernel)
+template <class Source>
+__device__ __forceinline__ void logsv_chain_full_body(size_t n, const Source &src, uint64_t path_offset, double *__restrict__ x_snap,
+                                                      double *__restrict__ q_snap, double *__restrict__ partials, uint64_t *probe)
 {
-    // logsv_chain_rng_kernel's statements: x and qvar parked in LDS across the time loop, the lanes past the last path stepping
-    // on a dummy state
     __shared__ RngTablesLds s_tab;
     __shared__ double s_exp[256];
-    __shared__ double s_park[2 * CHAIN_BLOCK];
+    __shared__ double s_park[2 * CHAIN_BLOCK];             // [0, B): x, [B, 2B): qvar -- lane t owns elements t and B + t
     const RngTables tab = stage_tables(s_tab, s_exp);
     clock_probe_stamp(probe, 0);
-    const auto exp_of = [&](double v) { return exp2u_tab(v, s_exp); };
+    // the path index is re-derived from threadIdx.x wherever it is needed (opaque to CSE): one VGPR across the time loop
+    // instead of the 64-bit index and the addresses formed from it
     const auto path_index = [&]() {
         uint32_t t = threadIdx.x;
         asm volatile("" : "+v"(t));
         return static_cast<size_t>(blockIdx.x) * CHAIN_BLOCK + t;
     };
-    const int job = blockIdx.y;
-    const LogsvFast *__restrict__ cj = static_cast<const LogsvFast *>(jobs.consts) + static_cast<size_t>(job) * cs.m;
     const bool active = path_index() < n;
-    double s = uniform_load(jobs.vol0 + job);
-    s_park[threadIdx.x] = 0.0;
-    s_park[CHAIN_BLOCK + threadIdx.x] = 0.0;
-    const PhiloxLane lane = philox_prepare(uniform_load(jobs.seed + job), uniform_load(jobs.c3 + job), path_offset + path_index());
-    const int quarter = (cs.total_steps + 3) >> 2;
-    int stage = 0, next_stage_t = 0, tg = 0;
-    for (int i = 0; i < cs.m; ++i) {
-        const int nb = cs.nb_steps[i];
-        double xv = 0.0, q = 0.0;
-        {
-            const LogsvFast c = uniform_load(cj + i);
-            double L = log_state(s) * LOG_UNITS_PER_NAT;                                              // :1039
-            double s2 = square_rn(s), acc = 0.0, xacc = 0.0;
-            const double s2_start = s2;
-            rng_time_loop(
-                lane, static_cast<uint32_t>(tg), nb, tab,
-                [&](double z0, double z1) { logsv_step_acc(c, xacc, L, s, s2, acc, z0, z1, exp_of); },
-                [&](int t) {
-                    if (tg + t >= next_stage_t) {          // wave-uniform
-                        progress_priority(stage++);
-                        next_stage_t += quarter;
-                    }
-                });
-            xv = s_park[threadIdx.x];
-            q = s_park[CHAIN_BLOCK + threadIdx.x];
-            logsv_fold_acc(c, xv, q, xacc, acc, s2_start, square_rn(s));
-            s_park[threadIdx.x] = xv;
-            s_park[CHAIN_BLOCK + threadIdx.x] = q;
-        }
-        tg += nb;
-        const size_t row = static_cast<size_t>(job) * cs.m + i;
-        const SliceOut so = {x_snap + row * n, q_snap ? q_snap + row * n : nullptr, partials + 2 * row * ((n + 63) >> 6), cs.forward[i],
-                             (n + 63) >> 6};
-        slice_epilogue(so, path_index(), active, xv, q);
+    double s;
+    {
+        double xv, q;
+        src.start(path_index(), active, xv, s, q);
+        s_park[threadIdx.x] = xv;
+        s_park[CHAIN_BLOCK + threadIdx.x] = q;
     }
+    const PhiloxLane lane = philox_prepare(src.seed(), src.c3(), path_offset + path_index());
+    LogsvProgress prog = {(src.total_steps() + 3) >> 2};
+    int tg = 0;
+    for (int i = 0; i < src.m(); ++i) {
+        const int nb = src.nb_steps(i);
+        // every lane steps, the lanes past the last path on a dummy state: inside `if (active)` the progress counters
+        // would be divergent values (vector registers, exec-masked branches in the time loop)
+        const LogsvFast c = src.consts(i);
+        const LogsvSliceSums a = logsv_slice_full(c, s, lane, src.step_origin() + static_cast<uint32_t>(tg), tg, nb, tab, s_exp, prog);
+        double xv = s_park[threadIdx.x];                   // a lane reads back what it alone wrote: no barrier needed
+        double q = s_park[CHAIN_BLOCK + threadIdx.x];
+        logsv_fold_acc(c, xv, q, a.xacc, a.acc, a.s2_start, square_rn(s));
+        s_park[threadIdx.x] = xv;
+        s_park[CHAIN_BLOCK + threadIdx.x] = q;
+        tg += nb;
+        slice_epilogue(slice_out_row(x_snap, q_snap, partials, src.row(i), n, src.forward(i)), path_index(), active, xv, q);
+    }
+    if (active) src.finish(path_index(), s_park[threadIdx.x], s, s_park[CHAIN_BLOCK + threadIdx.x]);
     clock_probe_stamp(probe, 1);
 }
 
-// logsv_chain_rng_many_kernel for a launch of a few waves per SIMD in all (J x n paths): logsv_chain_rng_lat_kernel's statements
-template <int LOOP, int WAVES, int TB>
-__global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) void logsv_chain_rng_many_lat_kernel(
-    size_t n, ManySlices cs, ManyJobs jobs, uint64_t path_offset, double *__restrict__ x_snap, double *__restrict__ q_snap,
-    double *__restrict__ partials, uint64_t *probe)
+// ... and of the whole-chain kernels for a launch of a few waves per SIMD (see logsv_rng_lat_kernel): the same slice loop on
+// logsv_slice_lat -- the same bits -- with x and qvar in registers (there are registers to spare)
+template <int LOOP, int TB, class Source>
+__device__ __forceinline__ void logsv_chain_lat_body(size_t n, const Source &src, uint64_t path_offset, double *__restrict__ x_snap,
+                                                     double *__restrict__ q_snap, double *__restrict__ partials, uint64_t *probe)
 {
     __shared__ RngTablesLds s_tab;
     __shared__ double s_exp[256];
     const RngTables tab = stage_tables(s_tab, s_exp);
     clock_probe_stamp(probe, 0);
-    const int job = blockIdx.y;
-    const LogsvFast *__restrict__ cj = static_cast<const LogsvFast *>(jobs.consts) + static_cast<size_t>(job) * cs.m;
     const size_t p = static_cast<size_t>(blockIdx.x) * TB + threadIdx.x;
     const bool active = p < n;
-    double xv = 0.0, s = uniform_load(jobs.vol0 + job), q = 0.0;
-    const PhiloxLane lane = philox_prepare(uniform_load(jobs.seed + job), uniform_load(jobs.c3 + job), path_offset + p);
+    double xv, s, q;
+    src.start(p, active, xv, s, q);
+    const PhiloxLane lane = philox_prepare(src.seed(), src.c3(), path_offset + p);
     int tg = 0;
-    for (int i = 0; i < cs.m; ++i) {
-        const int nb = cs.nb_steps[i];
-        const LogsvFast c = uniform_load(cj + i);
-        double L = log_state(s) * LOG_UNITS_PER_NAT;                                                  // :1039
-        double acc = 0.0, xacc = 0.0;
-        const double s2_start = square_rn(s);
-        logsv_gen_time_loop<LOOP>(lane, static_cast<uint32_t>(tg), nb, tab, c, xacc, L, s, acc, s_exp);
-        logsv_fold_acc(c, xv, q, xacc, acc, s2_start, square_rn(s));
+    for (int i = 0; i < src.m(); ++i) {
+        const int nb = src.nb_steps(i);
+        logsv_slice_lat<LOOP>(src.consts(i), xv, s, q, lane, src.step_origin() + static_cast<uint32_t>(tg), nb, tab, s_exp);
         tg += nb;
-        const size_t row = static_cast<size_t>(job) * cs.m + i;
-        const SliceOut so = {x_snap + row * n, q_snap ? q_snap + row * n : nullptr, partials + 2 * row * ((n + 63) >> 6), cs.forward[i],
-                             (n + 63) >> 6};
-        slice_epilogue(so, p, active, xv, q);
+        slice_epilogue(slice_out_row(x_snap, q_snap, partials, src.row(i), n, src.forward(i)), p, active, xv, q);
     }
+    if (active) src.finish(p, xv, s, q);
     clock_probe_stamp(probe, 1);
 }
+
+__global__ __launch_bounds__(CHAIN_BLOCK) __attribute__((amdgpu_waves_per_eu(SVMC_CHAIN_WAVES), amdgpu_num_sgpr(SVMC_CHAIN_SGPRS))) void logsv_chain_rng_kernel(
+    double *__restrict__ x, double *__restrict__ sigma, double *__restrict__ qvar, size_t n, ChainSlices cs, uint64_t seed,
+    uint32_t c3, uint64_t path_offset, uint32_t step_offset, double *__restrict__ x_snap, double *__restrict__ q_snap,
+    double *__restrict__ partials, StateInit init, uint64_t *probe)
+{
+    logsv_chain_full_body(n, ChainArgs<ChainSlices>{cs, seed, c3, step_offset, init, x, sigma, qvar}, path_offset, x_snap, q_snap, partials,
+                          probe);
+}
+
+template <int LOOP, int WAVES, int TB>
+__global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) void logsv_chain_rng_lat_kernel(
+    double *__restrict__ x, double *__restrict__ sigma, double *__restrict__ qvar, size_t n, ChainSlices cs, uint64_t seed,
+    uint32_t c3, uint64_t path_offset, uint32_t step_offset, double *__restrict__ x_snap, double *__restrict__ q_snap,
+    double *__restrict__ partials, StateInit init, uint64_t *probe)
+{
+    logsv_chain_lat_body<LOOP, TB>(n, ChainArgs<ChainSlices>{cs, seed, c3, step_offset, init, x, sigma, qvar}, path_offset, x_snap, q_snap,
+                                   partials, probe);
+}
+
+__global__ __launch_bounds__(CHAIN_BLOCK) __attribute__((amdgpu_waves_per_eu(SVMC_CHAIN_WAVES), amdgpu_num_sgpr(SVMC_CHAIN_SGPRS))) void logsv_chain_rng_many_kernel(
+    size_t n, ManySlices cs, ManyJobs jobs, uint64_t path_offset, double *__restrict__ x_snap, double *__restrict__ q_snap,
+    double *__restrict__ partials, uint64_t *probe)
+{
+    logsv_chain_full_body(n, ManyTable<LogsvFast>{cs, jobs}, path_offset, x_snap, q_snap, partials, probe);
+}
+
+// (a few waves per SIMD in all: J x n paths)
+template <int LOOP, int WAVES, int TB>
+__global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) void logsv_chain_rng_many_lat_kernel(
+    size_t n, ManySlices cs, ManyJobs jobs, uint64_t path_offset, double *__restrict__ x_snap, double *__restrict__ q_snap,
+    double *__restrict__ partials, uint64_t *probe)
+{
+    logsv_chain_lat_body<LOOP, TB>(n, ManyTable<LogsvFast>{cs, jobs}, path_offset, x_snap, q_snap, partials, probe);
+}
+
+// The few-waves form of the LogSV generators.
+using LogsvSliceKernel = void (*)(double *, double *, double *, size_t, int, LogsvFast, uint64_t, uint32_t, uint64_t, uint32_t, SliceOut,
+                                  StateInit, uint64_t *);
+using LogsvChainKernel = void (*)(double *, double *, double *, size_t, ChainSlices, uint64_t, uint32_t, uint64_t, uint32_t, double *,
+                                  double *, double *, StateInit, uint64_t *);
+struct LogsvLatVariant {
+    LogsvSliceKernel slice;
+    LogsvChainKernel chain;
+    int block;
+};
+static const LogsvLatVariant LOGSV_FEW_WAVES_KERNELS = {logsv_rng_lat_kernel<GEN_LOOP_PIPE, 4, FEW_BLOCK>,
+                                                        logsv_chain_rng_lat_kernel<GEN_LOOP_PIPE, 4, FEW_BLOCK>, FEW_BLOCK};
+
+// -> the few-waves kernels a launch of n_path paths runs, or null: the full-launch kernels
+static const LogsvLatVariant *logsv_lat_variant(size_t n_path)
+{
+    return few_waves_launch(n_path) ? &LOGSV_FEW_WAVES_KERNELS : nullptr;
+}
+
+static inline unsigned lat_grid(size_t n, int block = FEW_BLOCK) { return static_cast<unsigned>((n + block - 1) / block); }
 
 // Streamed-randoms time loop: HBM-bound (8 B per supplied random per path-step).  Software-pipelined by hand:
 // the NARR*U loads of the next U steps are issued before the current U steps are computed, so every wave keeps
@@ -1097,9 +1106,7 @@ void logsv_chain_rng_sets_kernel(size_t n, ChainRngSetsSlices cs, const LogsvFas
                 s_park[(2 * s + 1) * BLOCK + threadIdx.x] = q[s];
             }
             const int row = (s0 + s) * cs.m + i;
-            const SliceOut so = {x_snap + static_cast<size_t>(row) * n, q_snap ? q_snap + static_cast<size_t>(row) * n : nullptr,
-                                 partials + 2 * static_cast<size_t>(row) * ((n + 63) >> 6), cs.forward[i], (n + 63) >> 6};
-            slice_epilogue(so, p, active, xv[s], q[s]);
+            slice_epilogue(slice_out_row(x_snap, q_snap, partials, static_cast<size_t>(row), n, cs.forward[i]), p, active, xv[s], q[s]);
         }
     }
     clock_probe_stamp(probe, 1);
@@ -1519,6 +1526,40 @@ __device__ __forceinline__ void heston_time_loop(const PhiloxLane &lane, uint32_
     gen_time_loop<LOOP>(lane, step0, nb, tab, step);
 }
 
+// ONE slice of a Heston path, the statements every on-device-RNG Heston generator runs (heston_rng_body, heston_chain_rng_body):
+// nb steps from step `step` of the lane's stream, then the slice's fold into (x, v, q).  lane_u and uc serve SVMC_HESTON_QE's
+// uniforms and are dead in the other schemes.
+template <int SCHEME, int LOOP>
+__device__ __forceinline__ void heston_slice(const PhiloxLane &lane, const PhiloxLane &lane_u, QeUniforms &uc, uint32_t step, int nb,
+                                             const RngTables &tab, const HestonConsts c, const QeConsts qc, double &xv, double &v, double &q)
+{
+    const HestonEulerFast ef = make_heston_euler_fast(c);
+    double xacc = 0.0, vacc = 0.0;
+    if constexpr (SCHEME == HESTON_QE_QUAD) {
+        double vsum = 0.0, ksum = 0.0;
+        const double v_first = v;
+        const QeVec qv = make_qe_vec(qc);
+        heston_time_loop<LOOP>(lane, step, nb, tab, [&](double w0, double w1) {
+            heston_qe_step<true>(qc, qv, tab.log, xv, v, vsum, ksum, w0, w1, []() { return 0.0; });
+        });
+        heston_qe_fold(qc, xv, q, vsum, ksum, v_first, v);
+    } else if constexpr (SCHEME == SVMC_HESTON_QE) {
+        double vsum = 0.0, ksum = 0.0;
+        const double v_first = v;
+        uint32_t st = step;
+        const QeVec qv = make_qe_vec(qc);
+        heston_time_loop<LOOP>(lane, step, nb, tab, [&](double w0, double w1) {
+            heston_qe_step(qc, qv, tab.log, xv, v, vsum, ksum, w0, w1, [&]() { return qe_uniform(lane_u, st, uc); });
+            ++st;
+        });
+        heston_qe_fold(qc, xv, q, vsum, ksum, v_first, v);
+    } else {
+        v = heston_euler_guard_zero(v);
+        heston_time_loop<LOOP>(lane, step, nb, tab, [&](double w0, double w1) { heston_euler_step_acc(ef, xacc, v, vacc, w0, w1); });
+        heston_fold_acc(ef, xv, q, v, xacc, vacc);
+    }
+}
+
 template <int SCHEME, int LOOP>
 __device__ __forceinline__ void heston_rng_body(double *__restrict__ x, double *__restrict__ var, double *__restrict__ qvar, size_t n,
                                                 int nb_steps, HestonConsts c, QeConsts qc, uint64_t seed, uint32_t c3,
@@ -1543,34 +1584,9 @@ __device__ __forceinline__ void heston_rng_body(double *__restrict__ x, double *
             q = qvar[p];
         }
         const PhiloxLane lane = philox_prepare(seed, heston_is_qe(SCHEME) ? (c3 | 4u) : c3, path_offset + p);
-        const HestonEulerFast ef = make_heston_euler_fast(c);
-        double xacc = 0.0, vacc = 0.0;
-        if constexpr (SCHEME == HESTON_QE_QUAD) {
-            double vsum = 0.0, ksum = 0.0;
-            const double v_first = v;
-            const QeVec qv = make_qe_vec(qc);
-            heston_time_loop<LOOP>(lane, step_offset, nb_steps, tab, [&](double w0, double w1) {
-                heston_qe_step<true>(qc, qv, tab.log, xv, v, vsum, ksum, w0, w1, []() { return 0.0; });
-            });
-            heston_qe_fold(qc, xv, q, vsum, ksum, v_first, v);
-        } else if constexpr (SCHEME == SVMC_HESTON_QE) {
-            const PhiloxLane lane_u = philox_prepare(seed, c3 | 5u, path_offset + p);
-            QeUniforms uc;
-            uint32_t step = step_offset;
-            double vsum = 0.0, ksum = 0.0;
-            const double v_first = v;
-            const QeVec qv = make_qe_vec(qc);
-            heston_time_loop<LOOP>(lane, step_offset, nb_steps, tab, [&](double w0, double w1) {
-                heston_qe_step(qc, qv, tab.log, xv, v, vsum, ksum, w0, w1, [&]() { return qe_uniform(lane_u, step, uc); });
-                ++step;
-            });
-            heston_qe_fold(qc, xv, q, vsum, ksum, v_first, v);
-        } else {
-            v = heston_euler_guard_zero(v);
-            heston_time_loop<LOOP>(lane, step_offset, nb_steps, tab,
-                                  [&](double w0, double w1) { heston_euler_step_acc(ef, xacc, v, vacc, w0, w1); });
-            heston_fold_acc(ef, xv, q, v, xacc, vacc);
-        }
+        const PhiloxLane lane_u = philox_prepare(seed, c3 | 5u, path_offset + p);  // QE's uniforms (dead in the other schemes)
+        QeUniforms uc;
+        heston_slice<SCHEME, LOOP>(lane, lane_u, uc, step_offset, nb_steps, tab, c, qc, xv, v, q);
         x[p] = xv;
         var[p] = v;
         qvar[p] = q;
@@ -1605,48 +1621,14 @@ struct HestonChainSlices {
     double forward[MAX_CHAIN_SLICES];
     int nb_steps[MAX_CHAIN_SLICES];
     int m;
+    __device__ __forceinline__ HestonManyConsts consts(int i) const { return {c[i], qc[i]}; }
 };
 
-// one slice of a many-job Heston path (heston_chain_rng_body's slice statements): nb steps from step `step` of the lane's stream,
-// then the slice's fold into (x, v, q)
-template <int SCHEME, int LOOP>
-__device__ __forceinline__ void heston_chain_slice(const PhiloxLane &lane, const PhiloxLane &lane_u, QeUniforms &uc, uint32_t step, int nb,
-                                                   const RngTables &tab, const HestonConsts c, const QeConsts qc, double &xv, double &v,
-                                                   double &q)
-{
-    const HestonEulerFast ef = make_heston_euler_fast(c);
-    double xacc = 0.0, vacc = 0.0;
-    if constexpr (SCHEME == HESTON_QE_QUAD) {
-        double vsum = 0.0, ksum = 0.0;
-        const double v_first = v;
-        const QeVec qv = make_qe_vec(qc);
-        heston_time_loop<LOOP>(lane, step, nb, tab, [&](double w0, double w1) {
-            heston_qe_step<true>(qc, qv, tab.log, xv, v, vsum, ksum, w0, w1, []() { return 0.0; });
-        });
-        heston_qe_fold(qc, xv, q, vsum, ksum, v_first, v);
-    } else if constexpr (SCHEME == SVMC_HESTON_QE) {
-        double vsum = 0.0, ksum = 0.0;
-        const double v_first = v;
-        uint32_t st = step;
-        const QeVec qv = make_qe_vec(qc);
-        heston_time_loop<LOOP>(lane, step, nb, tab, [&](double w0, double w1) {
-            heston_qe_step(qc, qv, tab.log, xv, v, vsum, ksum, w0, w1, [&]() { return qe_uniform(lane_u, st, uc); });
-            ++st;
-        });
-        heston_qe_fold(qc, xv, q, vsum, ksum, v_first, v);
-    } else {
-        v = heston_euler_guard_zero(v);
-        heston_time_loop<LOOP>(lane, step, nb, tab, [&](double w0, double w1) { heston_euler_step_acc(ef, xacc, v, vacc, w0, w1); });
-        heston_fold_acc(ef, xv, q, v, xacc, vacc);
-    }
-}
-
-template <int SCHEME, int LOOP>
-__device__ __forceinline__ void heston_chain_rng_body(double *__restrict__ x, double *__restrict__ var, double *__restrict__ qvar,
-                                                      size_t n, const HestonChainSlices &cs, uint64_t seed, uint32_t c3,
-                                                      uint64_t path_offset, uint32_t step_offset, double *__restrict__ x_snap,
-                                                      double *__restrict__ q_snap, double *__restrict__ partials,
-                                                      const StateInit &init)
+// the body of the whole-chain kernels over a job source (ChainArgs<HestonChainSlices>: one job from the kernel arguments;
+// ManyTable<HestonManyConsts>: job blockIdx.y of the many-job table, see logsv_chain_rng_many_kernel)
+template <int SCHEME, int LOOP, class Source>
+__device__ __forceinline__ void heston_chain_rng_body(size_t n, const Source &src, uint64_t path_offset, double *__restrict__ x_snap,
+                                                      double *__restrict__ q_snap, double *__restrict__ partials)
 {
     __shared__ RngTablesLds s_tab;
     __shared__ LogTabEntry s_log[heston_is_qe(SCHEME) ? 512 : 1];
@@ -1655,64 +1637,24 @@ __device__ __forceinline__ void heston_chain_rng_body(double *__restrict__ x, do
     else tab = stage_rng_tables(s_tab);
     const size_t p = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
     const bool active = p < n;
-    double xv = 0.0, v = 1.0, q = 0.0;
-    if (active) {
-        if (init.uniform) {                                // wave-uniform
-            xv = init.x0;
-            v = init.vol0;
-            q = init.qvar0;
-        } else {
-            xv = x[p];
-            v = var[p];
-            q = qvar[p];
-        }
-    }
+    double xv, v, q;
+    src.start(p, active, xv, v, q);
+    const uint64_t seed = src.seed();
+    const uint32_t c3 = src.c3();
     const PhiloxLane lane = philox_prepare(seed, heston_is_qe(SCHEME) ? (c3 | 4u) : c3, path_offset + p);
     const PhiloxLane lane_u = philox_prepare(seed, c3 | 5u, path_offset + p);      // QE's uniforms (dead in the other schemes)
     QeUniforms uc;
-    uint32_t step = step_offset;
-    for (int i = 0; i < cs.m; ++i) {
-        const int nb = cs.nb_steps[i];
+    uint32_t step = src.step_origin();
+    for (int i = 0; i < src.m(); ++i) {
+        const int nb = src.nb_steps(i);
         if (active) {
-            const HestonConsts c = cs.c[i];
-            const QeConsts qc = cs.qc[i];
-            const HestonEulerFast ef = make_heston_euler_fast(c);
-            double xacc = 0.0, vacc = 0.0;
-            if constexpr (SCHEME == HESTON_QE_QUAD) {
-                double vsum = 0.0, ksum = 0.0;
-                const double v_first = v;
-                const QeVec qv = make_qe_vec(qc);
-                heston_time_loop<LOOP>(lane, step, nb, tab, [&](double w0, double w1) {
-                    heston_qe_step<true>(qc, qv, tab.log, xv, v, vsum, ksum, w0, w1, []() { return 0.0; });
-                });
-                heston_qe_fold(qc, xv, q, vsum, ksum, v_first, v);
-            } else if constexpr (SCHEME == SVMC_HESTON_QE) {
-                double vsum = 0.0, ksum = 0.0;
-                const double v_first = v;
-                uint32_t st = step;
-                const QeVec qv = make_qe_vec(qc);
-                heston_time_loop<LOOP>(lane, step, nb, tab, [&](double w0, double w1) {
-                    heston_qe_step(qc, qv, tab.log, xv, v, vsum, ksum, w0, w1, [&]() { return qe_uniform(lane_u, st, uc); });
-                    ++st;
-                });
-                heston_qe_fold(qc, xv, q, vsum, ksum, v_first, v);
-            } else {
-                v = heston_euler_guard_zero(v);
-                heston_time_loop<LOOP>(lane, step, nb, tab,
-                                      [&](double w0, double w1) { heston_euler_step_acc(ef, xacc, v, vacc, w0, w1); });
-                heston_fold_acc(ef, xv, q, v, xacc, vacc);
-            }
+            const HestonManyConsts k = src.consts(i);
+            heston_slice<SCHEME, LOOP>(lane, lane_u, uc, step, nb, tab, k.c, k.qc, xv, v, q);
         }
         step += static_cast<uint32_t>(nb);
-        const SliceOut so = {x_snap + static_cast<size_t>(i) * n, q_snap ? q_snap + static_cast<size_t>(i) * n : nullptr,
-                             partials + 2 * static_cast<size_t>(i) * ((n + 63) >> 6), cs.forward[i], (n + 63) >> 6};
-        slice_epilogue(so, p, active, xv, q);
+        slice_epilogue(slice_out_row(x_snap, q_snap, partials, src.row(i), n, src.forward(i)), p, active, xv, q);
     }
-    if (active) {
-        x[p] = xv;
-        var[p] = v;
-        qvar[p] = q;
-    }
+    if (active) src.finish(p, xv, v, q);
 }
 
 template <int SCHEME>
@@ -1723,7 +1665,8 @@ __global__ __launch_bounds__(RNG_BLOCK) void heston_chain_rng_kernel(double *__r
                                                                  double *__restrict__ x_snap, double *__restrict__ q_snap,
                                                                  double *__restrict__ partials, StateInit init)
 {
-    heston_chain_rng_body<SCHEME, GEN_LOOP_FULL>(x, var, qvar, n, cs, seed, c3, path_offset, step_offset, x_snap, q_snap, partials, init);
+    heston_chain_rng_body<SCHEME, GEN_LOOP_FULL>(n, ChainArgs<HestonChainSlices>{cs, seed, c3, step_offset, init, x, var, qvar}, path_offset,
+                                                 x_snap, q_snap, partials);
 }
 
 template <int SCHEME, int LOOP, int WAVES, int TB>
@@ -1732,53 +1675,17 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
     uint32_t c3, uint64_t path_offset, uint32_t step_offset, double *__restrict__ x_snap, double *__restrict__ q_snap,
     double *__restrict__ partials, StateInit init)
 {
-    heston_chain_rng_body<SCHEME, LOOP>(x, var, qvar, n, cs, seed, c3, path_offset, step_offset, x_snap, q_snap, partials, init);
+    heston_chain_rng_body<SCHEME, LOOP>(n, ChainArgs<HestonChainSlices>{cs, seed, c3, step_offset, init, x, var, qvar}, path_offset, x_snap,
+                                        q_snap, partials);
 }
 
-// many jobs of one chain in one launch (see logsv_chain_rng_many_kernel): job blockIdx.y, heston_chain_rng_body's statements from
-// (0, v0_j, 0) on the stream (seed_j, c3_j), outputs at row j m + i; the job table's constants are HestonManyConsts [J][m]
-struct HestonManyConsts {
-    HestonConsts c;
-    QeConsts qc;
-};
-template <int SCHEME, int LOOP>
-__device__ __forceinline__ void heston_chain_rng_many_body(size_t n, const ManySlices &cs, const ManyJobs &jobs, uint64_t path_offset,
-                                                           double *__restrict__ x_snap, double *__restrict__ q_snap,
-                                                           double *__restrict__ partials)
-{
-    __shared__ RngTablesLds s_tab;
-    __shared__ LogTabEntry s_log[heston_is_qe(SCHEME) ? 512 : 1];
-    RngTables tab;
-    if constexpr (heston_is_qe(SCHEME)) tab = stage_rng_log_tables(s_tab, s_log);
-    else tab = stage_rng_tables(s_tab);
-    const int job = blockIdx.y;
-    const HestonManyConsts *__restrict__ cj = static_cast<const HestonManyConsts *>(jobs.consts) + static_cast<size_t>(job) * cs.m;
-    const size_t p = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-    const bool active = p < n;
-    double xv = 0.0, v = uniform_load(jobs.vol0 + job), q = 0.0;
-    const uint64_t seed = uniform_load(jobs.seed + job);
-    const uint32_t c3 = uniform_load(jobs.c3 + job);
-    const PhiloxLane lane = philox_prepare(seed, heston_is_qe(SCHEME) ? (c3 | 4u) : c3, path_offset + p);
-    const PhiloxLane lane_u = philox_prepare(seed, c3 | 5u, path_offset + p);      // QE's uniforms (dead in the other schemes)
-    QeUniforms uc;
-    uint32_t step = 0;
-    for (int i = 0; i < cs.m; ++i) {
-        const int nb = cs.nb_steps[i];
-        if (active) heston_chain_slice<SCHEME, LOOP>(lane, lane_u, uc, step, nb, tab, cj[i].c, cj[i].qc, xv, v, q);
-        step += static_cast<uint32_t>(nb);
-        const size_t row = static_cast<size_t>(job) * cs.m + i;
-        const SliceOut so = {x_snap + row * n, q_snap ? q_snap + row * n : nullptr, partials + 2 * row * ((n + 63) >> 6), cs.forward[i],
-                             (n + 63) >> 6};
-        slice_epilogue(so, p, active, xv, q);
-    }
-}
-
+// many jobs of one chain in one launch: the same body on job blockIdx.y of the table
 template <int SCHEME>
 __global__ __launch_bounds__(RNG_BLOCK) void heston_chain_rng_many_kernel(size_t n, ManySlices cs, ManyJobs jobs, uint64_t path_offset,
                                                                       double *__restrict__ x_snap, double *__restrict__ q_snap,
                                                                       double *__restrict__ partials)
 {
-    heston_chain_rng_many_body<SCHEME, GEN_LOOP_FULL>(n, cs, jobs, path_offset, x_snap, q_snap, partials);
+    heston_chain_rng_body<SCHEME, GEN_LOOP_FULL>(n, ManyTable<HestonManyConsts>{cs, jobs}, path_offset, x_snap, q_snap, partials);
 }
 
 template <int SCHEME, int LOOP, int WAVES, int TB>
@@ -1786,7 +1693,7 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
     size_t n, ManySlices cs, ManyJobs jobs, uint64_t path_offset, double *__restrict__ x_snap, double *__restrict__ q_snap,
     double *__restrict__ partials)
 {
-    heston_chain_rng_many_body<SCHEME, LOOP>(n, cs, jobs, path_offset, x_snap, q_snap, partials);
+    heston_chain_rng_body<SCHEME, LOOP>(n, ManyTable<HestonManyConsts>{cs, jobs}, path_offset, x_snap, q_snap, partials);
 }
 
 __global__ __launch_bounds__(BLOCK) void heston_w_kernel(double *__restrict__ x, double *__restrict__ var,

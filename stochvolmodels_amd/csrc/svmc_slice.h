@@ -29,6 +29,12 @@ struct SliceOut {
     size_t rows = 0;    // column stride of `partials`: wave_rows(n) of the launch
 };
 
+// the outputs of row `row` of a whole-chain launch of n paths: snapshots [rows][n], one column pair of per-wave partials per row
+__device__ __forceinline__ SliceOut slice_out_row(double *x_snap, double *q_snap, double *partials, size_t row, size_t n, double forward)
+{
+    const size_t waves = (n + 63) >> 6;
+    return {x_snap + row * n, q_snap ? q_snap + row * n : nullptr, partials + 2 * row * waves, forward, waves};
+}
 
 // Start state of a generator launch: read from x / vol / qvar (uniform = 0), or the same three constants for every path --
 // what a chain pricing starts from (x0 = 0, sigma0 | v0, qvar0 = 0: pricers/logsv_pricer.py:823-826, heston_pricer.py:303-305).

@@ -2301,6 +2301,28 @@ def test_heston_whole_chain_stepping_equals_slice_by_slice(sv, scheme, vt):
         np.testing.assert_array_equal(a, b)
 
 
+def test_full_launch_chain_kernels_equal_slices_and_many_job_batch():
+    """the two tests above run 30 001 and 20 011 paths: the few-waves kernels.  Here a fresh process with
+    SVMC_FEW_WAVES_MAX_PATHS=0 (read once per process) runs the FULL-LAUNCH kernels -- the LogSV whole-chain one with its LDS parking
+    and its dummy lanes -- at 1089 paths (a partial block, a partial wave, idle waves) on a 3-expiry ragged chain: whole-chain
+    stepping, slice-by-slice stepping and job 0 of a 2-job many-job batch give the same bits (prices, standard errors, and for the
+    first two the terminal state), LogSV in both measures, Heston Euler, QE general and QE quadratic-only
+    (tests/full_launch_worker.py)"""
+    import json
+    import subprocess
+    import sys as _sys
+    worker = os.path.join(os.path.dirname(os.path.abspath(__file__)), "full_launch_worker.py")
+    r = subprocess.run([_sys.executable, worker], env=dict(os.environ, SVMC_FEW_WAVES_MAX_PATHS="0"), capture_output=True, text=True,
+                       timeout=300)
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert lines, (r.returncode, r.stderr[-2000:])
+    got = json.loads(lines[-1])
+    assert sorted(got) == ["heston_euler", "heston_qe_general", "heston_qe_quad_only", "logsv_inverse_measure", "logsv_spot_measure"]
+    failed = [(case, check) for case, checks in got.items() for check, ok in checks.items() if ok is not True]
+    assert not failed and all(len(checks) == 6 for checks in got.values()), failed
+    assert r.returncode == 0, r.stderr[-2000:]
+
+
 @pytest.mark.parametrize("tag", ["base", "btc"])
 def test_heston_analytic_qvar_vs_reference(sv, golden, tag):
     """heston_chain_pricer(variable_type=Q_VAR): closed-form MGF on the 40 000-point psi grid (heston_mgf_grid_kernel)
