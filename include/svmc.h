@@ -692,6 +692,32 @@ SVMC_API int svmc_mgf_digital_slice_batch(const double *phi, const double *log_m
 SVMC_API int svmc_histogram_uniform(const double *values, size_t n, double divisor, const double *edges, int n_bins,
                                     uint64_t *counts, svmc_stream_t stream);
 
+/* ---- Gaussian kernel density estimate of a resident vector (src svmc_density.hip) -------------------------
+ * scipy.stats.gaussian_kde(kept)(points) of the samples values[i] / divisor (a division; 1 leaves them as they are):
+ *   1. a sample v is dropped if it is NaN, if v > limit or if v < -limit (strict: +-limit itself is kept);
+ *   2. mean = sum v / n_kept, then var = sum (v - mean)^2 / (n_kept - 1) over the kept samples (two passes, as np.cov);
+ *   3. h = sqrt(var) factor, factor = bandwidth_factor where that is positive and Scott's n_kept^(-1/5) otherwise;
+ *   4. density[j] = sum_i exp(-((points[j] - v_i) / h)^2 / 2) / (n_kept h sqrt(2 pi)).
+ * values: device [n]; points, density: device [n_points], 1 <= n_points <= SVMC_KDE_MAX_POINTS; stats: device
+ * [SVMC_KDE_STATS_DOUBLES] = {n_kept, n_nan, n_low, n_high, mean, var, h, factor}, the counts as doubles.  Six launches on
+ * `stream`, no allocation, and no host round trip: the later launches read mean, h and n_kept from `stats` on the device.
+ * Fewer than two kept samples, or a variance that is zero or not finite, are NOT errors of the call: the stats block reports
+ * them, the density is whatever the arithmetic gives (NaN or inf), and the host decides.  Refused with
+ * SVMC_ERR_INVALID_ARGUMENT: a null pointer, n < 1, n_points outside its range, a divisor or limit that is not positive and
+ * finite, a non-finite bandwidth factor; with SVMC_ERR_WORKSPACE: a workspace below 8 (1280 + n_chunks n_points) bytes.
+ * Deterministic: the order of every sum depends on n alone (the samples are cut into chunks whose length is a function of n;
+ * a chunk's sum and then the chunks are added in a fixed order), so the density at a point is the same bits whichever other
+ * points or vectors share the call.
+ *   svmc_kde_workspace_bytes   host only: the workspace that serves any n_points <= SVMC_KDE_MAX_POINTS at this n, and (where
+ *                              chunk_length is not NULL) the chunk length of this n. */
+#define SVMC_KDE_TILE 8            /* evaluation points a thread of the density kernel keeps in registers */
+#define SVMC_KDE_MAX_POINTS 4096
+#define SVMC_KDE_STATS_DOUBLES 8
+SVMC_API int svmc_kde_workspace_bytes(size_t n, size_t *bytes, size_t *chunk_length);
+SVMC_API int svmc_kde_gaussian(const double *values, size_t n, double divisor, double limit, const double *points, int n_points,
+                               double bandwidth_factor, double *density, double *stats, void *workspace, size_t workspace_bytes,
+                               svmc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

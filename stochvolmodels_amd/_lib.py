@@ -159,6 +159,8 @@ def _declare(L: C.CDLL) -> None:
         "svmc_mgf_pdf_slice_batch": ([vp, vp, sz, i32, vp, sz, pf64, pf64, i32, vp, vp], i32),
         "svmc_mgf_digital_slice_batch": ([vp, vp, sz, i32, f64, pf64, sz, i32, i32, vp, vp], i32),
         "svmc_histogram_uniform": ([vp, sz, f64, vp, i32, vp, vp], i32),
+        "svmc_kde_workspace_bytes": ([sz, psz, psz], i32),
+        "svmc_kde_gaussian": ([vp, sz, f64, f64, vp, i32, f64, vp, vp, vp, sz, vp], i32),
     }
     for name, (argtypes, restype) in sig.items():
         if os.environ.get("SVMC_ALLOW_OLD_ABI") == "1" and not hasattr(L, name):

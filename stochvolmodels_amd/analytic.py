@@ -492,6 +492,61 @@ def device_histograms(value_ptrs: Sequence[int], n: int, edges_list: Sequence[np
             b.free()
 
 
+KDE_TILE, KDE_MAX_POINTS, KDE_STATS_DOUBLES = 8, 4096, 8     # SVMC_KDE_* of include/svmc.h
+KDE_STATS_FIELDS = ("n_kept", "n_nan", "n_low", "n_high", "mean", "var", "h", "factor")
+
+
+def kde_workspace(n: int) -> Tuple[int, int]:
+    """(workspace bytes, chunk length) of svmc_kde_gaussian at `n` samples: both depend on n alone (svmc_kde_workspace_bytes)"""
+    nbytes, chunk = C.c_size_t(0), C.c_size_t(0)
+    _lib.check(_lib.load().svmc_kde_workspace_bytes(int(n), C.byref(nbytes), C.byref(chunk)))
+    return int(nbytes.value), int(chunk.value)
+
+
+def device_kdes(value_ptrs: Sequence[int], n: int, grids: Sequence[np.ndarray], divisors: Sequence[float], limit: float = 1e16,
+                bandwidth_factor: Optional[float] = None, stream=None) -> list:
+    """scipy.stats.gaussian_kde(kept)(grid) of several device vectors of `n` doubles (svmc_kde_gaussian): the sample is
+    values / divisor, NaNs and samples beyond +-limit are dropped and counted, the bandwidth is Scott's unless a positive
+    factor is given.  One upload of all the grids, the launches of all the vectors on one stream, ONE download of all the
+    densities and stats blocks: [(density [len(grid)], {n_kept, n_nan, n_low, n_high, mean, var, h, factor})] per vector.
+    Raises SciPy's two exceptions: ValueError with fewer than two kept samples, numpy.linalg.LinAlgError where their variance
+    is not positive and finite."""
+    lib = _lib.load()
+    grids = [np.ascontiguousarray(g, dtype=np.float64).ravel() for g in grids]
+    sizes = [g.size for g in grids]
+    goff = np.concatenate([[0], np.cumsum(sizes)]).astype(int)
+    total, n_vec = int(goff[-1]), len(grids)
+    all_grids = np.concatenate(grids) if grids else np.empty(0)
+    ws_bytes = kde_workspace(n)[0]
+    # results: the densities of all vectors, then their stats blocks -- one buffer, one download
+    bufs = [DeviceBuffer(max(total, 1)), DeviceBuffer(max(total + KDE_STATS_DOUBLES * n_vec, 1)), DeviceBuffer(max(ws_bytes // 8, 1))]
+    try:
+        _lib.check(lib.svmc_memcpy_h2d(bufs[0].ptr, all_grids.ctypes.data, all_grids.nbytes, stream))
+        for i, (ptr, div) in enumerate(zip(value_ptrs, divisors)):
+            _lib.check(lib.svmc_kde_gaussian(ptr, int(n), float(div), float(limit), bufs[0].offset(goff[i]), sizes[i],
+                                             float(bandwidth_factor or 0.0), bufs[1].offset(goff[i]),
+                                             bufs[1].offset(total + KDE_STATS_DOUBLES * i), bufs[2].ptr, ws_bytes, stream))
+        out = np.empty(total + KDE_STATS_DOUBLES * n_vec)
+        _lib.check(lib.svmc_memcpy_d2h(out.ctypes.data, bufs[1].ptr, out.nbytes, stream))
+        _lib.check(lib.svmc_stream_synchronize(stream))
+    finally:
+        for b in bufs:
+            b.free()
+    return [(out[goff[i]:goff[i + 1]].copy(), kde_stats(out[total + KDE_STATS_DOUBLES * i:total + KDE_STATS_DOUBLES * (i + 1)]))
+            for i in range(n_vec)]
+
+
+def kde_stats(block: np.ndarray) -> dict:
+    """a downloaded stats block of svmc_kde_gaussian as a dict (the four counts as ints), with gaussian_kde's refusals: ValueError
+    for fewer than two kept samples, LinAlgError for a variance that is not positive and finite"""
+    stats = {k: (int(v) if k.startswith("n_") and np.isfinite(v) else float(v)) for k, v in zip(KDE_STATS_FIELDS, block)}
+    if not stats["n_kept"] >= 2:
+        raise ValueError(f"kernel density estimate: {stats['n_kept']} samples kept, at least two are needed")
+    if not (np.isfinite(stats["var"]) and stats["var"] > 0.0):
+        raise np.linalg.LinAlgError(f"kernel density estimate: the variance of the kept samples is {stats['var']}")
+    return stats
+
+
 def vanilla_prices_from_capped(capped: np.ndarray, forward: float, strikes: np.ndarray, optiontypes: Sequence,
                                discfactor: float, is_spot_measure: bool) -> np.ndarray:
     """the payoff algebra of vanilla_slice_pricer_with_mgf_grid, reference utils/mgf_pricer.py:199-219"""

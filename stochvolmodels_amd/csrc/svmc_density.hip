@@ -6,6 +6,7 @@
 //                              (utils/mgf_pricer.py:224-269; the C / P complement and the discount factor are the host's)
 //   histogram_uniform_kernel   integer counts of a state vector on equal bins with np.histogram's semantics: per-block counts in
 //                              LDS, one 64-bit integer atomic per non-empty bin and block
+//   kde_* kernels              the Gaussian kernel density estimate of a state vector (row f7; described where they stand)
 //
 // The weights w are the reference's LEGACY pricer weights (:157-171), as mgf_vanilla_slice_kernel forms them: Simpson 1,4,2,...
 // with every odd index 4 (an even-length grid keeps 4 on its last point), or for is_simpson = 0 half the first step on the
@@ -151,6 +152,160 @@ __global__ __launch_bounds__(HIST_BLOCK) void histogram_uniform_kernel(const dou
     }
 }
 
+// ---- Gaussian kernel density estimate of a resident state vector: DESIGN.md row f7 ------------------------------------------
+// scipy.stats.gaussian_kde(kept)(points) written out (reference pricers/model_pricer.py:243-265): the sample is a[i] / divisor;
+// NaNs and samples beyond +-limit (strict comparisons) are dropped and counted; mean and variance of the kept samples in two
+// passes as np.cov takes them; h = sqrt(var) factor with Scott's factor n_kept^(-1/5) unless one is given;
+// density_j = sum_i exp(-((g_j - v_i) / h)^2 / 2) / (n_kept h sqrt(2 pi)).
+//
+//   kde_moments_kernel<1>         per block [kept, NaN, low, high, sum v]          kde_moments_finish_kernel<1>   counts, mean
+//   kde_moments_kernel<2>         per block sum (v - mean)^2, mean from the block  kde_moments_finish_kernel<2>   var, h
+//   kde_gaussian_kernel           block (x, y): the KDE_TILE points of tile x against the samples of chunk y; a thread keeps the
+//                                 tile in registers and streams its samples past it (one 8-byte load and one division feed
+//                                 KDE_TILE exponentials); partials[y][point]
+//   kde_finish_kernel             a thread per point adds its chunks in order and scales by 1 / (n_kept h sqrt(2 pi))
+//
+// Every launch after the first reads what it needs (mean, h, n_kept) from the stats block on the device: no host round trip.
+// Order of every sum: a thread adds its samples in index order, the 64 lanes of a wave meet in one shuffle tree, the four waves
+// are added in order, the blocks / chunks in order.  The grids of the moment kernels and the chunk length are functions of n
+// alone (kde_chunk_length, kde_moment_blocks) and a point's sum does not depend on the tile it sits in: the density of a
+// vector at a point is the same bits whatever other points or vectors share the call.
+constexpr int KDE_BLOCK = 256;
+constexpr int KDE_TILE = SVMC_KDE_TILE;
+constexpr size_t KDE_MIN_CHUNK = 2048;       // samples per chunk up to 2^19 samples: 8 per thread, 64 exponentials against a
+constexpr size_t KDE_MAX_CHUNKS = 256;       // block reduction of ~200 instructions; beyond that 256 chunks of n / 256
+constexpr int KDE_MOMENT_BLOCKS = 256;       // most blocks of a moment pass (their partials fit one finishing block)
+constexpr size_t KDE_MOMENT_PER_BLOCK = 2048;
+constexpr int KDE_MOMENT_DOUBLES = 5 * KDE_MOMENT_BLOCKS;
+enum { KDE_N_KEPT = 0, KDE_N_NAN, KDE_N_LOW, KDE_N_HIGH, KDE_MEAN, KDE_VAR, KDE_H, KDE_FACTOR };
+static_assert(KDE_FACTOR + 1 == SVMC_KDE_STATS_DOUBLES, "stats block layout");
+static_assert(KDE_BLOCK == 256 && KDE_MOMENT_BLOCKS <= KDE_BLOCK, "block_sum_rows adds four waves");
+
+inline size_t kde_chunk_length(size_t n)
+{
+    const size_t per = (n + KDE_MAX_CHUNKS - 1) / KDE_MAX_CHUNKS;
+    const size_t len = (per + KDE_BLOCK - 1) / KDE_BLOCK * KDE_BLOCK;
+    return len < KDE_MIN_CHUNK ? KDE_MIN_CHUNK : len;
+}
+
+inline unsigned kde_moment_blocks(size_t n)
+{
+    const size_t want = (n + KDE_MOMENT_PER_BLOCK - 1) / KDE_MOMENT_PER_BLOCK;
+    return static_cast<unsigned>(want < static_cast<size_t>(KDE_MOMENT_BLOCKS) ? want : KDE_MOMENT_BLOCKS);
+}
+
+// NV block sums in the fixed order of block_sum; every thread of the first NV holds sum k in thread k
+template <int NV>
+__device__ __forceinline__ void block_sum_rows(double (&v)[NV], double (*lds)[4])
+{
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+        const double s = wave_sum(v[k]);
+        if ((threadIdx.x & 63) == 0) lds[k][threadIdx.x >> 6] = s;
+    }
+    __syncthreads();
+}
+
+__device__ __forceinline__ double rows_total(const double (*lds)[4], int k) { return ((lds[k][0] + lds[k][1]) + lds[k][2]) + lds[k][3]; }
+
+template <int PASS>
+__global__ __launch_bounds__(KDE_BLOCK) void kde_moments_kernel(const double *__restrict__ a, size_t n, double divisor, double limit,
+                                                                const double *__restrict__ stats, double *__restrict__ partials)
+{
+    constexpr int NV = (PASS == 1) ? 5 : 1;
+    __shared__ double lds[NV][4];
+    const double mean = (PASS == 2) ? stats[KDE_MEAN] : 0.0;
+    double acc[NV] = {};
+    for (size_t p = static_cast<size_t>(blockIdx.x) * KDE_BLOCK + threadIdx.x; p < n; p += static_cast<size_t>(gridDim.x) * KDE_BLOCK) {
+        const double v = a[p] / divisor;
+        const bool is_nan = v != v, high = v > limit, low = v < -limit;
+        const bool kept = !(is_nan || high || low);
+        if (PASS == 1) {
+            acc[0] += kept ? 1.0 : 0.0;
+            acc[1] += is_nan ? 1.0 : 0.0;
+            acc[2] += low ? 1.0 : 0.0;
+            acc[3] += high ? 1.0 : 0.0;
+            acc[4] += kept ? v : 0.0;
+        } else {
+            const double d = v - mean;
+            acc[0] += kept ? d * d : 0.0;
+        }
+    }
+    block_sum_rows<NV>(acc, lds);
+    if (threadIdx.x < NV) partials[threadIdx.x * gridDim.x + blockIdx.x] = rows_total(lds, threadIdx.x);
+}
+
+// one block: the blocks' partials in order (thread t holds block t's), then the stats the later launches read
+template <int PASS>
+__global__ __launch_bounds__(KDE_BLOCK) void kde_moments_finish_kernel(const double *__restrict__ partials, int n_blocks, double factor,
+                                                                       double *__restrict__ stats)
+{
+    constexpr int NV = (PASS == 1) ? 5 : 1;
+    __shared__ double lds[NV][4];
+    double v[NV];
+#pragma unroll
+    for (int k = 0; k < NV; ++k) v[k] = (static_cast<int>(threadIdx.x) < n_blocks) ? partials[k * n_blocks + threadIdx.x] : 0.0;
+    block_sum_rows<NV>(v, lds);
+    if (threadIdx.x != 0) return;
+    if (PASS == 1) {
+        const double n_kept = rows_total(lds, 0);
+        stats[KDE_N_KEPT] = n_kept;
+        stats[KDE_N_NAN] = rows_total(lds, 1);
+        stats[KDE_N_LOW] = rows_total(lds, 2);
+        stats[KDE_N_HIGH] = rows_total(lds, 3);
+        stats[KDE_MEAN] = rows_total(lds, 4) / n_kept;
+    } else {
+        const double n_kept = stats[KDE_N_KEPT];
+        const double var = rows_total(lds, 0) / (n_kept - 1.0);
+        const double f = (factor > 0.0) ? factor : pow(n_kept, -0.2);         // Scott's rule in one dimension
+        stats[KDE_VAR] = var;
+        stats[KDE_H] = sqrt(var) * f;
+        stats[KDE_FACTOR] = f;
+    }
+}
+
+__global__ __launch_bounds__(KDE_BLOCK) void kde_gaussian_kernel(const double *__restrict__ a, size_t n, size_t chunk_len,
+                                                                 double divisor, double limit, const double *__restrict__ points,
+                                                                 int m, const double *__restrict__ stats,
+                                                                 double *__restrict__ partials)
+{
+    __shared__ double lds[KDE_TILE][4];
+    const int j0 = blockIdx.x * KDE_TILE;
+    double g[KDE_TILE], acc[KDE_TILE];
+#pragma unroll
+    for (int j = 0; j < KDE_TILE; ++j) {
+        g[j] = points[(j0 + j < m) ? j0 + j : m - 1];                 // the last tile repeats the last point: read in bounds, not stored
+        acc[j] = 0.0;
+    }
+    const double inv_h = 1.0 / stats[KDE_H];
+    const size_t begin = static_cast<size_t>(blockIdx.y) * chunk_len;
+    const size_t end = (begin + chunk_len < n) ? begin + chunk_len : n;
+    for (size_t p = begin + threadIdx.x; p < end; p += KDE_BLOCK) {
+        const double v = a[p] / divisor;
+        const bool kept = (v == v) && !(v > limit) && !(v < -limit);
+#pragma unroll
+        for (int j = 0; j < KDE_TILE; ++j) {
+            const double d = (g[j] - v) * inv_h;
+            const double e = exp_full((-0.5 * d) * d);                // <= 0: +0 below -746
+            acc[j] += kept ? e : 0.0;
+        }
+    }
+    block_sum_rows<KDE_TILE>(acc, lds);
+    if (threadIdx.x < KDE_TILE && j0 + static_cast<int>(threadIdx.x) < m)
+        partials[static_cast<size_t>(blockIdx.y) * m + j0 + threadIdx.x] = rows_total(lds, threadIdx.x);
+}
+
+__global__ __launch_bounds__(KDE_BLOCK) void kde_finish_kernel(const double *__restrict__ partials, int n_chunks, int m,
+                                                               const double *__restrict__ stats, double *__restrict__ density)
+{
+    const int j = blockIdx.x * KDE_BLOCK + threadIdx.x;
+    if (j >= m) return;
+    double s = 0.0;
+#pragma unroll 16
+    for (int c = 0; c < n_chunks; ++c) s += partials[static_cast<size_t>(c) * m + j];
+    density[j] = s / (stats[KDE_N_KEPT] * stats[KDE_H] * 2.5066282746310002);                  // sqrt(2 pi)
+}
+
 }  // namespace svmc
 
 using namespace svmc;
@@ -224,6 +379,46 @@ int svmc_histogram_uniform(const double *values, size_t n, double divisor, const
     hipLaunchKernelGGL(histogram_uniform_kernel, dim3(blocks), dim3(HIST_BLOCK), sizeof(unsigned int) * static_cast<size_t>(n_bins),
                        as_stream(stream), values, n, divisor, edges, n_bins, reinterpret_cast<unsigned long long *>(counts));
     return check_launch("svmc_histogram_uniform");
+}
+
+int svmc_kde_workspace_bytes(size_t n, size_t *bytes, size_t *chunk_length)
+{
+    SVMC_REQUIRE(bytes, "svmc_kde_workspace_bytes: null pointer");
+    SVMC_REQUIRE(n >= 1 && n < (static_cast<size_t>(1) << 40), "svmc_kde_workspace_bytes: n must be in 1 .. 2^40 - 1");
+    const size_t len = kde_chunk_length(n), n_chunks = (n + len - 1) / len;
+    *bytes = sizeof(double) * (KDE_MOMENT_DOUBLES + n_chunks * SVMC_KDE_MAX_POINTS);
+    if (chunk_length) *chunk_length = len;
+    return SVMC_OK;
+}
+
+int svmc_kde_gaussian(const double *values, size_t n, double divisor, double limit, const double *points, int n_points,
+                      double bandwidth_factor, double *density, double *stats, void *workspace, size_t workspace_bytes,
+                      svmc_stream_t stream)
+{
+    SVMC_REQUIRE(values && points && density && stats && workspace, "svmc_kde_gaussian: null pointer");
+    SVMC_REQUIRE(n >= 1 && n < (static_cast<size_t>(1) << 40), "svmc_kde_gaussian: n must be in 1 .. 2^40 - 1");
+    SVMC_REQUIRE(n_points >= 1, "svmc_kde_gaussian: n_points must be at least 1");
+    SVMC_REQUIRE(n_points <= SVMC_KDE_MAX_POINTS, "svmc_kde_gaussian: n_points above SVMC_KDE_MAX_POINTS");
+    SVMC_REQUIRE(divisor > 0.0 && divisor < HUGE_VAL, "svmc_kde_gaussian: divisor must be positive and finite");
+    SVMC_REQUIRE(limit > 0.0 && limit < HUGE_VAL, "svmc_kde_gaussian: limit must be positive and finite");
+    SVMC_REQUIRE(bandwidth_factor == bandwidth_factor && bandwidth_factor < HUGE_VAL, "svmc_kde_gaussian: bandwidth factor must be finite");
+    const size_t len = kde_chunk_length(n), n_chunks = (n + len - 1) / len;
+    if (workspace_bytes < sizeof(double) * (KDE_MOMENT_DOUBLES + n_chunks * static_cast<size_t>(n_points)))
+        return fail(SVMC_ERR_WORKSPACE, "svmc_kde_gaussian: workspace too small (svmc_kde_workspace_bytes)");
+    double *moment_partials = static_cast<double *>(workspace), *partials = moment_partials + KDE_MOMENT_DOUBLES;
+    const unsigned mb = kde_moment_blocks(n);
+    hipStream_t s = as_stream(stream);
+    hipLaunchKernelGGL(kde_moments_kernel<1>, dim3(mb), dim3(KDE_BLOCK), 0, s, values, n, divisor, limit, stats, moment_partials);
+    hipLaunchKernelGGL(kde_moments_finish_kernel<1>, dim3(1), dim3(KDE_BLOCK), 0, s, moment_partials, static_cast<int>(mb),
+                       bandwidth_factor, stats);
+    hipLaunchKernelGGL(kde_moments_kernel<2>, dim3(mb), dim3(KDE_BLOCK), 0, s, values, n, divisor, limit, stats, moment_partials);
+    hipLaunchKernelGGL(kde_moments_finish_kernel<2>, dim3(1), dim3(KDE_BLOCK), 0, s, moment_partials, static_cast<int>(mb),
+                       bandwidth_factor, stats);
+    hipLaunchKernelGGL(kde_gaussian_kernel, dim3((n_points + KDE_TILE - 1) / KDE_TILE, static_cast<unsigned>(n_chunks)), dim3(KDE_BLOCK),
+                       0, s, values, n, len, divisor, limit, points, n_points, stats, partials);
+    hipLaunchKernelGGL(kde_finish_kernel, dim3((n_points + KDE_BLOCK - 1) / KDE_BLOCK), dim3(KDE_BLOCK), 0, s, partials,
+                       static_cast<int>(n_chunks), n_points, stats, density);
+    return check_launch("svmc_kde_gaussian");
 }
 
 }  // extern "C"

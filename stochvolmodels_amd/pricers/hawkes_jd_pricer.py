@@ -302,6 +302,21 @@ class HawkesJDPricer(ModelPricer):
                                           nb_steps_per_year=kwargs.get("nb_steps_per_year", NB_STEPS_PER_YEAR),
                                           seed=kwargs.get("seed"))
 
+    def get_log_return_mc_pdf_device(self, ttm: float, params: HawkesJDParams, x_grid: np.ndarray, nb_path: int = 100000,
+                                     **kwargs) -> np.ndarray:
+        """get_log_return_mc_pdf (LOG_RETURN, the model's one priced variable) with the state left on the device and the
+        kernel estimate summed there; seed= / nb_steps_per_year= as simulate_terminal_values"""
+        from .logsv_pricer import engine_log_return_mc_pdf, refuse_sharded_kde
+        refuse_sharded_kde("get_log_return_mc_pdf_device", kwargs)
+        p = params.to_dict()
+        p.pop("risk_premia_gamma")
+        lambda_p, lambda_m = p.pop("lambda_p"), p.pop("lambda_m")
+        eng = hawkesjd_terminal_on_engine(ttm=ttm, x0=np.zeros(nb_path), lambda_p0=lambda_p * np.ones(nb_path),
+                                          lambda_m0=lambda_m * np.ones(nb_path), nb_path=nb_path, **p,
+                                          nb_steps_per_year=kwargs.get("nb_steps_per_year", NB_STEPS_PER_YEAR),
+                                          seed=kwargs.get("seed"))
+        return engine_log_return_mc_pdf(eng, x_grid)
+
 
 # ---- the calibration's codec (reference :246-290): the optimizer's 8-vector <-> HawkesJDParams --------------------------------
 # (sigma, mean_p, mean_m, theta_p, theta_m, kappa, beta_p, beta_m)
@@ -588,6 +603,17 @@ def simulate_hawkesjd_terminal(ttm: float, x0: np.ndarray, lambda_p0: np.ndarray
                                ) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     """terminal (x, lambda_p, lambda_m) after ttm from the given state (reference :715-776); a length-1 x0 becomes x0 * zeros,
     length-1 intensities lambda * ones, as there"""
+    return hawkesjd_terminal_on_engine(ttm, x0, lambda_p0, lambda_m0, mu, sigma, shift_p, mean_p, shift_m, mean_m, theta_p,
+                                       kappa_p, beta1_p, beta2_p, theta_m, kappa_m, beta1_m, beta2_m, nb_path,
+                                       nb_steps_per_year, seed).get_state()
+
+
+def hawkesjd_terminal_on_engine(ttm: float, x0: np.ndarray, lambda_p0: np.ndarray, lambda_m0: np.ndarray, mu: float,
+                                sigma: float, shift_p: float, mean_p: float, shift_m: float, mean_m: float, theta_p: float,
+                                kappa_p: float, beta1_p: float, beta2_p: float, theta_m: float, kappa_m: float,
+                                beta1_m: float, beta2_m: float, nb_path: int = 100000,
+                                nb_steps_per_year: int = NB_STEPS_PER_YEAR, seed: Optional[int] = None):
+    """simulate_hawkesjd_terminal with the terminal state left on the engine it returns"""
     x0 = _broadcast(x0, nb_path, np.zeros)
     lambda_p0 = _broadcast(lambda_p0, nb_path, np.ones)
     lambda_m0 = _broadcast(lambda_m0, nb_path, np.ones)
@@ -599,4 +625,4 @@ def simulate_hawkesjd_terminal(ttm: float, x0: np.ndarray, lambda_p0: np.ndarray
     eng = get_engine(int(nb_path))
     eng.set_state(x0, lambda_p0, lambda_m0)
     eng.hawkesjd_rng(nb_steps, dt, block, rng_seed, call_id, 0)
-    return eng.get_state()
+    return eng

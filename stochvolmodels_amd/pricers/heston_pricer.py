@@ -139,6 +139,26 @@ class HestonPricer(ModelPricer):
         eng = self._simulate_on_engine(params, ttm, nb_path, kwargs.get("scheme", "euler"), kwargs.get("seed"))
         return engine_state_histograms(eng, space_grids, ttm)
 
+    def terminal_value_kdes(self, params: HestonParams, space_grids: dict, ttm: float = 1.0, nb_path: int = 100000, **kwargs):
+        """simulate_terminal_values followed by scipy.stats.gaussian_kde of x, qvar / ttm and the VARIANCE (keyed
+        VariableType.SIGMA) on the given space grids, summed on the device -- LogSVPricer.terminal_value_kdes for this model.
+        seed= / scheme= as simulate_terminal_values; bandwidth_factor= and return_stats= as there."""
+        from .logsv_pricer import engine_state_kdes, refuse_sharded_kde
+        refuse_sharded_kde("terminal_value_kdes", kwargs)
+        eng = self._simulate_on_engine(params, ttm, nb_path, kwargs.get("scheme", "euler"), kwargs.get("seed"))
+        out = engine_state_kdes(eng, space_grids, ttm, bandwidth_factor=kwargs.get("bandwidth_factor"))
+        densities = {k: d for k, (d, _) in out.items()}
+        return (densities, {k: s for k, (_, s) in out.items()}) if kwargs.get("return_stats", False) else densities
+
+    def get_log_return_mc_pdf_device(self, ttm: float, params: HestonParams, x_grid: np.ndarray, nb_path: int = 100000,
+                                     **kwargs) -> np.ndarray:
+        """get_log_return_mc_pdf with the state left on the device and the kernel estimate summed there (seed= / scheme= as
+        simulate_terminal_values)"""
+        from .logsv_pricer import engine_log_return_mc_pdf, refuse_sharded_kde
+        refuse_sharded_kde("get_log_return_mc_pdf_device", kwargs)
+        eng = self._simulate_on_engine(params, ttm, nb_path, kwargs.get("scheme", "euler"), kwargs.get("seed"))
+        return engine_log_return_mc_pdf(eng, x_grid)
+
 
 def compute_heston_mgf_grid(v0: float, theta: float, kappa: float, volvol: float, rho: float, ttm: float,
                             phi_grid: np.ndarray, psi_grid: np.ndarray, a_t0: np.ndarray = None, b_t0: np.ndarray = None

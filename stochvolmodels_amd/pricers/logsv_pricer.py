@@ -24,7 +24,7 @@ from ..mc_chain import price_chain_on_engine, variable_type_code
 from ..utils.calibration import ImpliedVolObjective, chain_calibration_weights, minimize_slsqp
 from ..utils.config import VariableType
 from ..utils.funcs import histogram_series, next_rng_call, set_time_grid, time_grid_steps, timer
-from ..analytic import AnalyticGrid, chain_prices_from_sums, chain_sums, device_histograms, histogram_edges
+from ..analytic import AnalyticGrid, chain_prices_from_sums, chain_sums, device_histograms, device_kdes, histogram_edges
 from ..utils import mgf_pricer as mgfp
 from .logsv.affine_expansion import ExpansionOrder, _order_code, get_init_conditions_a, note_integrator_flags
 from .logsv.logsv_params import LogSvParams
@@ -437,6 +437,31 @@ class LogSVPricer(ModelPricer):
         eng = self._simulate_on_engine(params, ttm, nb_path, is_spot_measure, kwargs.get("seed"))
         return engine_state_histograms(eng, space_grids, ttm)
 
+    def terminal_value_kdes(self, params: LogSvParams, ttm: float = 1.0, nb_path: int = 100000,
+                            is_spot_measure: bool = True, space_grids: Optional[dict] = None, n: int = 200,
+                            n_stdevs: float = 3.0, **kwargs):
+        """simulate_terminal_values followed by scipy.stats.gaussian_kde of x, qvar / ttm and sigma on their space grids, with the
+        n_path x n_grid exponentials summed on the device: {VariableType: density per unit of the variable}.  space_grids, n,
+        n_stdevs and seed= as terminal_value_histograms; bandwidth_factor= a positive factor in place of Scott's;
+        return_stats=True also returns {VariableType: {n_kept, n_nan, n_low, n_high, mean, var, h, factor}}.  Not in the
+        reference API."""
+        refuse_sharded_kde("terminal_value_kdes", kwargs)
+        if space_grids is None:
+            space_grids = {vt: params.get_variable_space_grid(variable_type=vt, ttm=ttm, n=n, n_stdevs=n_stdevs)
+                           for vt in (VariableType.LOG_RETURN, VariableType.Q_VAR, VariableType.SIGMA)}
+        eng = self._simulate_on_engine(params, ttm, nb_path, is_spot_measure, kwargs.get("seed"))
+        out = engine_state_kdes(eng, space_grids, ttm, bandwidth_factor=kwargs.get("bandwidth_factor"))
+        densities = {k: d for k, (d, _) in out.items()}
+        return (densities, {k: s for k, (_, s) in out.items()}) if kwargs.get("return_stats", False) else densities
+
+    def get_log_return_mc_pdf_device(self, ttm: float, params: LogSvParams, x_grid: np.ndarray, nb_path: int = 100000,
+                                     **kwargs) -> np.ndarray:
+        """get_log_return_mc_pdf with the state left on the device and the kernel estimate summed there (seed= and
+        is_spot_measure= as simulate_terminal_values)"""
+        refuse_sharded_kde("get_log_return_mc_pdf_device", kwargs)
+        eng = self._simulate_on_engine(params, ttm, nb_path, kwargs.get("is_spot_measure", True), kwargs.get("seed"))
+        return engine_log_return_mc_pdf(eng, x_grid)
+
 
 def engine_state_histograms(eng, space_grids: dict, ttm: float) -> dict:
     """compute_histogram_data of the engine's resident state on the given grids, counted on the device (svmc_histogram_uniform):
@@ -450,6 +475,36 @@ def engine_state_histograms(eng, space_grids: dict, ttm: float) -> dict:
     edges = [histogram_edges(g[0], g[-1], len(g) - 1) for g in grids]
     counts = device_histograms([src[c][0] for c in codes], eng.n_path, edges, [src[c][1] for c in codes], eng.stream)
     return {k: histogram_series(cnt, e, g[0], eng.n_path) for k, g, e, cnt in zip(keys, grids, edges, counts)}
+
+
+def engine_state_kdes(eng, space_grids: dict, ttm: float, limit: float = 1e16, bandwidth_factor: Optional[float] = None) -> dict:
+    """scipy.stats.gaussian_kde of the engine's resident state on the given grids, summed on the device (svmc_kde_gaussian), with
+    engine_state_histograms' sources: LOG_RETURN -> x, Q_VAR -> qvar / ttm, SIGMA -> the second state vector.
+    {key: (density per unit of the variable, stats)}"""
+    src = {1: (eng.x.ptr, 1.0), 2: (eng.qvar.ptr, float(ttm)), 3: (eng.vol.ptr, 1.0)}
+    keys = list(space_grids)
+    codes = [int(getattr(k, "value", k)) for k in keys]
+    if any(c not in src for c in codes):
+        raise NotImplementedError
+    out = device_kdes([src[c][0] for c in codes], eng.n_path, [space_grids[k] for k in keys], [src[c][1] for c in codes],
+                      limit=limit, bandwidth_factor=bandwidth_factor, stream=eng.stream)
+    return dict(zip(keys, out))
+
+
+def refuse_sharded_kde(who: str, kwargs: dict) -> None:
+    """the kernel density estimate runs on one engine: a sharded request (comm= of world > 1, devices=, or a default
+    communicator of world > 1) raises rather than estimate from one rank's paths"""
+    comm = kwargs.get("comm")
+    if kwargs.get("devices") is not None or (comm.world if comm is not None else svdist.get_default_comm().world) > 1:
+        raise NotImplementedError(f"{who}: the kernel density estimate is not sharded over ranks or devices")
+
+
+def engine_log_return_mc_pdf(eng, x_grid: np.ndarray) -> np.ndarray:
+    """ModelPricer.get_log_return_mc_pdf's arithmetic on the engine's resident x: the reference's line about the dropped paths
+    from the device counts, then density / nansum(density)"""
+    density, stats = engine_state_kdes(eng, {1: np.asarray(x_grid, dtype=np.float64)}, 1.0)[1]
+    print(f"in mc: num -inf = {stats['n_low']}, num +inf = {stats['n_high']}, num nans = {stats['n_nan']}")
+    return density / np.nansum(density)
 
 
 def set_vol_scaler(sigma0: float, ttm: float) -> float:
