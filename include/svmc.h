@@ -718,6 +718,53 @@ SVMC_API int svmc_kde_gaussian(const double *values, size_t n, double divisor, d
                                double bandwidth_factor, double *density, double *stats, void *workspace, size_t workspace_bytes,
                                svmc_stream_t stream);
 
+/* ---- Monte Carlo prices under the exponential risk-premia kernel (src svmc_kernels.hip, svmc_chain.hip) ----
+ * For one expiry with terminal log-returns x_j, forward F, strikes K_k of type 'C' / 'P' and one risk-premia gamma:
+ *   w_j = exp(gamma x_j),  spot_j = F exp(x_j) - corr,  corr = 0, or with recenter != 0 the recentring of svmc_payoff_sums,
+ *   spot_sums[0] / spot_sums[1] - F (the UNWEIGHTED mean of F exp(x) over the paths where it is not NaN, minus F);
+ *   KEEP RULE: path j is kept iff x_j, w_j^2 and (w_j spot_j)^2 are all finite.  A dropped path adds nothing to any sum and is
+ *   counted; every sum below runs over the kept paths.
+ *   pay_jk = max(spot_j - K_k, 0) ('C') or max(K_k - spot_j, 0) ('P');
+ *   price_k = sum_j w_j pay_jk / sum_j w_j  (undiscounted);
+ *   stderr_k = sqrt(sum_j (w_j (pay_jk - price_k))^2) / sum_j w_j, the delta-method error of that ratio of sums, formed from
+ *   sums of w d, (w d)^2 and w^2 d with d = pay - shift_k (shift_k: a host constant near the price, e.g. the intrinsic value at
+ *   the forward; any finite value gives the same estimate, a near one keeps its error free of cancellation).
+ * Per gamma and expiry the statistics block, SVMC_TILTED_STATS_DOUBLES doubles:
+ *   {normalizer = n_kept / sum w, its error sqrt(sum (1 - normalizer w)^2) / sum w, gamma_forward = sum w spot / sum w, its error
+ *    sqrt(sum (w (spot - gamma_forward))^2) / sum w, effective sample size (sum w)^2 / sum w^2, n_kept, n_dropped, sum w}.
+ * No kept path, or kept paths of zero weight only, are NOT errors of the call: the prices are then 0/0 = NaN and the block says so.
+ *   svmc_tilted_payoff_chain   model-agnostic: x_snapshots_host is a HOST array of n_expiries DEVICE pointers (as in
+ *                              svmc_payoff_sums_chain); strikes / types / shifts concatenated, expiry i owning
+ *                              [strike_offsets_host[i], strike_offsets_host[i + 1]); spot_sums: device [2 n_expiries], read
+ *                              only when recenter != 0 (NULL otherwise).  prices, stderrs: [n_gammas][n_strikes], stats:
+ *                              [n_gammas][n_expiries][SVMC_TILTED_STATS_DOUBLES], device memory or device-visible pinned host
+ *                              memory.  Two launches on `stream` for a chain of up to 8 strike groups (a group: up to 22
+ *                              strikes of one expiry) whose partial sums fit the workspace (svmc_payoff_workspace_bytes
+ *                              always holds one gamma's), a pair more per further 8 groups or batch of gammas.  Every sum has
+ *                              a fixed order that depends on n_path alone: a gamma's and an expiry's results are the same bits
+ *                              whichever other gammas, strikes or expiries share the call.
+ *   svmc_hawkesjd_chain_price_tilted   svmc_hawkesjd_chain_price's stepping launch ONCE for all gammas, then the launches above on
+ *                              the session's snapshots; no path leaves the device.  Results land in host arrays of the shapes
+ *                              above.  gamma = 0 with recenter != 0 is the plain measure (svmc_hawkesjd_chain_price at discount
+ *                              factors 1).  Single-device sessions only.
+ * Everything is checked before anything is launched: SVMC_ERR_INVALID_ARGUMENT for a null pointer, n_path < 1, n_expiries < 1,
+ * n_gammas outside 1 .. SVMC_TILTED_MAX_GAMMAS, a gamma, forward, strike or shift that is not finite, recenter without
+ * spot_sums; SVMC_ERR_UNKNOWN_PAYOFF for a type code other than SVMC_CALL / SVMC_PUT; SVMC_ERR_WORKSPACE for a workspace below
+ * svmc_payoff_workspace_bytes. */
+#define SVMC_TILTED_MAX_GAMMAS 16
+#define SVMC_TILTED_STATS_DOUBLES 8
+SVMC_API int svmc_tilted_payoff_chain(const double *const *x_snapshots_host, size_t n_path, const double *forwards_host,
+                                      int n_expiries, const double *strikes_host, const int8_t *types_host,
+                                      const double *shifts_host, const size_t *strike_offsets_host, const double *gammas_host,
+                                      int n_gammas, int recenter, const double *spot_sums, double *prices, double *stderrs,
+                                      double *stats, void *workspace, size_t workspace_bytes, svmc_stream_t stream);
+SVMC_API int svmc_hawkesjd_chain_price_tilted(svmc_session_t session, const double *ttms_host, const double *forwards_host,
+                                              int n_expiries, const double *strikes_host, const int8_t *types_host,
+                                              const size_t *strike_offsets_host, const double *params_host,
+                                              int nb_steps_per_year, uint64_t seed, uint32_t call_id, const double *gammas_host,
+                                              int n_gammas, int recenter, double *prices_host, double *stderrs_host,
+                                              double *stats_host);
+
 #ifdef __cplusplus
 }
 #endif

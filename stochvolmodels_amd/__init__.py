@@ -9,8 +9,9 @@ Module layout and public names mirror the reference package (`stochvolmodels`) f
     stochvolmodels_amd.pricers.hawkes_jd_pricer  HawkesJDPricer, HawkesJDParams, hawkesjd_mc_chain_pricer,
                                               hawkesjd_chain_pricer(_batch), simulate_hawkesjd_terminal,
                                               hawkesjd_forwards_under_risk_kernel,
-                                              hawkesjd_chain_pricer_with_risk_premia(_batch)
-    stochvolmodels_amd.utils.mc_payoffs       compute_mc_vars_payoff
+                                              hawkesjd_chain_pricer_with_risk_premia(_batch),
+                                              hawkesjd_mc_chain_pricer_with_risk_premia(_gammas)
+    stochvolmodels_amd.utils.mc_payoffs       compute_mc_vars_payoff, compute_mc_vars_payoff_with_gamma
     stochvolmodels_amd.utils.funcs            set_time_grid, set_seed, timer
     stochvolmodels_amd.utils.config           OptionType, VariableType
     stochvolmodels_amd.data.option_chain      OptionChain
@@ -29,6 +30,9 @@ _EXPORTS = {
     "set_time_grid": "utils.funcs", "set_seed": "utils.funcs", "timer": "utils.funcs",
     "to_flat_np_array": "utils.funcs",
     "compute_mc_vars_payoff": "utils.mc_payoffs",
+    "compute_mc_vars_payoff_with_gamma": "utils.mc_payoffs",
+    "hawkesjd_mc_chain_pricer_with_risk_premia": "pricers.hawkes_jd_pricer",
+    "hawkesjd_mc_chain_pricer_with_risk_premia_gammas": "pricers.hawkes_jd_pricer",
     "OptionChain": "data.option_chain",
     "ModelParams": "pricers.model_pricer", "ModelPricer": "pricers.model_pricer",
     "LogSvParams": "pricers.logsv.logsv_params",

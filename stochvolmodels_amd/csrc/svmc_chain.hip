@@ -81,6 +81,9 @@ struct Session {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     float last_stepping_ms = -1.0f;
     ManyBuffers many;
+    // svmc_hawkesjd_chain_price_tilted: the page-locked landing buffer of its prices, errors and statistics, grown on demand
+    double *tilted_pinned = nullptr;
+    size_t tilted_pinned_bytes = 0;
 };
 
 // events around a stepping call of a timed session (no-ops otherwise)
@@ -128,6 +131,7 @@ static void session_release(Session *s)
                     static_cast<void *>(s->spot_ws)})
         if (p != nullptr) (void)hipFree(p);
     if (s->sums_pinned != nullptr) (void)hipHostFree(s->sums_pinned);
+    if (s->tilted_pinned != nullptr) (void)hipHostFree(s->tilted_pinned);
     ManyBuffers &mb = s->many;
     for (void *p : {static_cast<void *>(mb.snap), static_cast<void *>(mb.spot_ws), static_cast<void *>(mb.spot),
                     static_cast<void *>(mb.sums), mb.ws, mb.table_dev})
@@ -170,11 +174,12 @@ static void expiry_grids(const ChainView &c, int nb_steps_per_year, std::vector<
     }
 }
 
+// (needs_discfactors false: the undiscounted pricers, whose view carries no discount factors)
 static int check_chain(const char *fn, const Session *s, const ChainView &c, int variable_type, const double *prices,
-                       const double *stderrs)
+                       const double *stderrs, bool needs_discfactors = true)
 {
     if (s == nullptr) return fail(SVMC_ERR_INVALID_ARGUMENT, std::string(fn) + ": null session");
-    if (!c.ttms || !c.forwards || !c.discfactors || !c.strikes || !c.types || !c.offsets || !prices || !stderrs)
+    if (!c.ttms || !c.forwards || (needs_discfactors && !c.discfactors) || !c.strikes || !c.types || !c.offsets || !prices || !stderrs)
         return fail(SVMC_ERR_INVALID_ARGUMENT, std::string(fn) + ": null pointer");
     if (c.m < 1 || c.m > s->max_expiries) return fail(SVMC_ERR_INVALID_ARGUMENT, std::string(fn) + ": expiries exceed the session");
     if (c.offsets[c.m] > s->max_strikes) return fail(SVMC_ERR_INVALID_ARGUMENT, std::string(fn) + ": strikes exceed the session");
@@ -933,6 +938,70 @@ int svmc_hawkesjd_chain_price(svmc_session_t session, const double *ttms_host, c
         return rc;
     stepping_end(s);
     return reduce_and_finalize(s, c, variable_type, prices_host, stderrs_host, pending);
+}
+
+int svmc_hawkesjd_chain_price_tilted(svmc_session_t session, const double *ttms_host, const double *forwards_host, int n_expiries,
+                                     const double *strikes_host, const int8_t *types_host, const size_t *strike_offsets_host,
+                                     const double *params_host, int nb_steps_per_year, uint64_t seed, uint32_t call_id,
+                                     const double *gammas_host, int n_gammas, int recenter, double *prices_host, double *stderrs_host,
+                                     double *stats_host)
+{
+    const char *fn = "svmc_hawkesjd_chain_price_tilted";
+    Session *s = reinterpret_cast<Session *>(session);
+    // the chain's own checks (the discount factors play no part: the prices are undiscounted)
+    const ChainView c = {n_expiries, ttms_host, forwards_host, nullptr, strikes_host, types_host, strike_offsets_host};
+    if (int rc = check_chain(fn, s, c, SVMC_LOG_RETURN, prices_host, stderrs_host, false)) return rc;
+    SVMC_REQUIRE(!s->sharded(), std::string(fn) + ": single-device sessions only");
+    SVMC_REQUIRE(params_host != nullptr && gammas_host != nullptr && stats_host != nullptr, std::string(fn) + ": null pointer");
+    SVMC_REQUIRE(nb_steps_per_year > 0, std::string(fn) + ": nb_steps_per_year must be positive");
+    SVMC_REQUIRE(n_gammas >= 1 && n_gammas <= SVMC_TILTED_MAX_GAMMAS, std::string(fn) + ": n_gammas outside 1 .. SVMC_TILTED_MAX_GAMMAS");
+    for (int g = 0; g < n_gammas; ++g) SVMC_REQUIRE(std::isfinite(gammas_host[g]), std::string(fn) + ": a gamma is not finite");
+    const size_t K = c.offsets[c.m];
+    for (int i = 0; i < c.m; ++i) {
+        SVMC_REQUIRE(std::isfinite(c.forwards[i]), std::string(fn) + ": a forward is not finite");
+        SVMC_REQUIRE(c.offsets[i] <= c.offsets[i + 1], std::string(fn) + ": strike offsets must not decrease");
+    }
+    for (size_t k = 0; k < K; ++k) {
+        if (c.types[k] != SVMC_CALL && c.types[k] != SVMC_PUT) return fail(SVMC_ERR_UNKNOWN_PAYOFF, "unknown option payoff code");
+        SVMC_REQUIRE(std::isfinite(c.strikes[k]), std::string(fn) + ": a strike is not finite");
+    }
+    size_t need_ws = 0;
+    if (int rc = svmc_payoff_workspace_bytes(&need_ws)) return rc;
+    if (s->ws_bytes < need_ws) return fail(SVMC_ERR_WORKSPACE, std::string(fn) + ": the session's workspace is too small");
+    const size_t G = static_cast<size_t>(n_gammas), n_stats = G * c.m * SVMC_TILTED_STATS_DOUBLES;
+    const size_t out_bytes = (2 * G * K + n_stats) * sizeof(double);
+    if (s->tilted_pinned_bytes < out_bytes) {
+        if (s->tilted_pinned != nullptr) (void)hipHostFree(s->tilted_pinned);
+        s->tilted_pinned = nullptr;
+        s->tilted_pinned_bytes = 0;
+        SVMC_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&s->tilted_pinned), out_bytes, hipHostMallocDefault));
+        s->tilted_pinned_bytes = out_bytes;
+    }
+    std::vector<int> nbs;
+    std::vector<double> dts, shifts;
+    expiry_grids(c, nb_steps_per_year, nbs, dts);
+    payoff_shifts_of(c, SVMC_LOG_RETURN, shifts);
+    // the stepping launch of svmc_hawkesjd_chain_price, once for every gamma; its spot sums are reduced only where the recentring
+    // reads them
+    const bool pending = !recenter && c.m <= MAX_FUSED_SLICES;
+    stepping_begin(s);
+    if (int rc = hawkes_step_partials(params_host, s->x, s->vol, s->qvar, s->n_path, c.m, nbs.data(), dts.data(), c.forwards, seed,
+                                      call_id, s->path_offset, s->snap, pending ? nullptr : s->spot, pending ? s->spot_ws : s->ws,
+                                      pending ? s->spot_ws_bytes : s->ws_bytes, s->stream))
+        return rc;
+    stepping_end(s);
+    const SnapshotRows r = snapshot_rows(s, c, 0, 1);
+    double *prices = s->tilted_pinned, *stderrs = prices + G * K, *stats = stderrs + G * K;
+    if (int rc = svmc_tilted_payoff_chain(r.x.data(), s->n_path, c.forwards, c.m, c.strikes, c.types, shifts.data(), c.offsets, gammas_host,
+                                          n_gammas, recenter, recenter ? s->spot : nullptr, prices, stderrs, stats, s->ws, s->ws_bytes,
+                                          reinterpret_cast<svmc_stream_t>(s->stream)))
+        return rc;
+    SVMC_HIP_TRY(hipStreamSynchronize(s->stream));
+    stepping_read(s);
+    memcpy(prices_host, prices, G * K * sizeof(double));
+    memcpy(stderrs_host, stderrs, G * K * sizeof(double));
+    memcpy(stats_host, stats, n_stats * sizeof(double));
+    return SVMC_OK;
 }
 
 }  // extern "C"

@@ -3138,6 +3138,290 @@ int chain_payoff_and_finish(const double *const *x_snapshots_host, const double 
     return check_launch(fn);
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Exponentially weighted payoff sums: Monte Carlo prices under the exponential risk-premia kernel (svmc_tilted_payoff_chain,
+// include/svmc.h states the estimator and the keep rule).  payoff_group_kernel's sibling: a block column is a group of up to
+// KT strikes of one expiry, blockIdx.z a gamma; a thread reads a path's x once, exponentiates it twice (spot, weight), applies
+// the keep rule by zeroing the weight of a dropped path (no branch: a zero weight adds nothing to any sum) and adds, per strike,
+// w d, (w d)^2 and w (w d) with d = payoff - shift -- the sums the ratio estimator's delta-method error is formed from without
+// cancellation -- and per expiry the seven statistics columns below, shifted the same way (w - 1, spot - forward).  Sums are the
+// payoff kernel's: per-block partials in the fixed tree order, partials[path block][gamma][column], no atomics.  The path blocks
+// of a launch are a function of the path count ALONE (tilted_path_blocks), so that a gamma's and an expiry's sums are the same
+// bits whatever else shares the launch.
+// ---------------------------------------------------------------------------------------------------
+constexpr int TILTED_KT = 22;          // strikes per group, as PAYOFF_KT
+constexpr int TILTED_NSTAT = 7;        // [sum w, sum w^2, sum (w-1)^2, sum w ds, sum w^2 ds, sum (w ds)^2, kept], ds = spot - forward
+constexpr int TILTED_STAT_COLS = 8;    // ... padded: the statistics columns of an expiry start at a multiple of 64 bytes
+constexpr unsigned TILTED_BLOCKS = 512;        // path blocks at most: one resident round at the kernel's two waves per SIMD
+
+struct TiltedGroup {
+    const double *x, *spot_sums;       // spot_sums: [sum F exp(x), count] of the expiry for the recentring; null: corr = 0
+    double forward;
+    double c[TILTED_KT];               // -sg K - shift; -inf for the unused strikes of a group (d = 0)
+    double nshift[TILTED_KT];          // -shift: d = max(sg spot - sg K, 0) - shift = max(fma(sg, spot, c), -shift)
+    uint32_t put_mask;                 // bit k set: put, sg = -1
+    int k;                             // live strikes in this group
+    int col;                           // first strike column of the group within this launch
+    int slot;                          // statistics columns of the group's expiry within this launch
+    int expiry;                        // the expiry's index in the chain (output row of its statistics)
+    int first;                         // the group that writes the statistics columns of its expiry in this launch
+};
+struct TiltedGroupPack {
+    TiltedGroup g[PAYOFF_GROUPS];
+};
+struct TiltedGammas {
+    double g[SVMC_TILTED_MAX_GAMMAS];
+};
+static_assert(sizeof(TiltedGroupPack) + sizeof(TiltedGammas) + 128 <= 4096, "the tilted descriptors travel in the kernel arguments");
+
+// as payoff_min_waves: the widest groups whose build metadata shows no scratch at three waves per SIMD
+constexpr int tilted_min_waves(int kt) { return kt <= 4 ? 3 : 2; }
+
+template <int KT>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(tilted_min_waves(KT), tilted_min_waves(KT)))) void tilted_payoff_group_kernel(
+    TiltedGroupPack pack, TiltedGammas gammas, size_t n, double *__restrict__ partials, int ld, int stats_col0)
+{
+    constexpr int NV = 3 * KT + TILTED_NSTAT;
+    constexpr int NSUM = block_sum_padded(NV);
+    __shared__ double lds[4 * NSUM];
+    const TiltedGroup &d = pack.g[blockIdx.y];
+    const double gamma = gammas.g[blockIdx.z];
+    const double *__restrict__ x = d.x;
+    const double forward = d.forward;
+    const double corr = (d.spot_sums != nullptr) ? d.spot_sums[0] / d.spot_sums[1] - forward : 0.0;    // (block-uniform)
+    const size_t stride = static_cast<size_t>(gridDim.x) * BLOCK;
+    const int nk = d.k;
+    double acc[NSUM], sg[KT], c[KT], nshift[KT];
+#pragma unroll
+    for (int k = 0; k < KT; ++k) {
+        sg[k] = ((d.put_mask >> k) & 1u) ? -1.0 : 1.0;     // stays wave-uniform: the scalar operand of the FMA
+        c[k] = d.c[k];
+        nshift[k] = d.nshift[k];
+    }
+#pragma unroll
+    for (int j = 0; j < NSUM; ++j) acc[j] = 0.0;
+    constexpr double INF = __builtin_huge_val();
+
+    const auto add_path = [&](double xi) {
+        double w = exp_full(gamma * xi);
+        double spot = forward * exp_full(xi) - corr;
+        const double ws = w * spot;
+        // the keep rule: x, w^2 and (w spot)^2 all finite (a NaN fails every comparison)
+        const bool keep = (fabs(xi) < INF) && (w * w < INF) && (ws * ws < INF);
+        w = keep ? w : 0.0;
+        spot = keep ? spot : 0.0;
+        const double v = keep ? w - 1.0 : 0.0;
+        const double wds = w * (spot - forward);
+        acc[3 * KT] += w;
+        acc[3 * KT + 1] = fma(w, w, acc[3 * KT + 1]);
+        acc[3 * KT + 2] = fma(v, v, acc[3 * KT + 2]);
+        acc[3 * KT + 3] += wds;
+        acc[3 * KT + 4] = fma(w, wds, acc[3 * KT + 4]);
+        acc[3 * KT + 5] = fma(wds, wds, acc[3 * KT + 5]);
+        acc[3 * KT + 6] += keep ? 1.0 : 0.0;
+#pragma unroll
+        for (int k = 0; k < KT; ++k) {
+            const double wd = w * fmax(fma(sg[k], spot, c[k]), nshift[k]);
+            acc[k] += wd;
+            acc[KT + k] = fma(wd, wd, acc[KT + k]);
+            acc[2 * KT + k] = fma(w, wd, acc[2 * KT + k]);
+        }
+    };
+    // the trips of payoff_group_kernel: the ones every lane of the block makes through the batched double buffer, the ragged last
+    const size_t i0 = static_cast<size_t>(blockIdx.x) * BLOCK + threadIdx.x;
+    const size_t block_last = static_cast<size_t>(blockIdx.x) * BLOCK + (BLOCK - 1);
+    const int full_trips = (n > block_last) ? static_cast<int>((n - 1 - block_last) / stride + 1) : 0;     // block-uniform
+    constexpr int PF = (KT > 16) ? 1 : PAYOFF_PREFETCH;        // 22 strikes: 66 accumulators; two trips of prefetch spilled 44 B per lane
+    const double *const wsrc[1] = {x + i0};
+    streamed_time_loop<1, PF>(wsrc, stride, full_trips, [&](const double(&v)[1]) { add_path(v[0]); });
+    for (size_t i = i0 + static_cast<size_t>(full_trips) * stride; i < n; i += stride) add_path(x[i]);
+    // row layout: [sum w d, sum (w d)^2, sum w^2 d] per strike at column 3 (col + k), the expiry's statistics from stats_col0 on
+    double *row = partials + (static_cast<size_t>(blockIdx.x) * gridDim.z + blockIdx.z) * ld;
+    const int col = d.col, slot = d.slot, first = d.first;
+    block_sum_apply<NSUM>(acc, lds, NV, [&](int j, double t) {
+        if (j < 3 * KT) {
+            const int which = j / KT, k = j - which * KT;
+            if (k < nk) row[3 * (col + k) + which] = t;
+        } else if (first) {
+            row[stats_col0 + TILTED_STAT_COLS * slot + (j - 3 * KT)] = t;
+        }
+    });
+}
+
+// the sums of NC columns by one wave, in block_column_sum's order of additions (chain_finish_kernel's way: lane l plays the
+// threads l, 64 + l, 128 + l, 192 + l one after the other), the loads of all of them in flight before the first addition
+template <int NC>
+__device__ __forceinline__ void wave_column_sums(const double *__restrict__ first_col, unsigned n_rows, size_t ld, unsigned lane,
+                                                 double (&out)[NC])
+{
+    double t[NC][4][4];
+#pragma unroll
+    for (int cc = 0; cc < NC; ++cc)
+#pragma unroll
+        for (int vw = 0; vw < 4; ++vw) column_rows_load<4>(first_col + cc, vw * 64u + lane, n_rows, ld, t[cc][vw]);
+#pragma unroll
+    for (int cc = 0; cc < NC; ++cc) {
+        double total = 0.0;
+#pragma unroll
+        for (int vw = 0; vw < 4; ++vw) {
+            const double w = wave_sum(column_rows_add<4>(t[cc][vw], vw * 64u + lane, n_rows));
+            total = (vw == 0) ? w : total + w;
+        }
+        out[cc] = total;
+    }
+}
+
+// the second and last launch: a wave per quote sums the quote's three columns and its expiry's [sum w, sum w^2] in row order
+// and forms the price and its delta-method error; one more wave per expiry forms the statistics.  Block (7 g + s, gamma): the
+// strikes 4 s .. 4 s + 3 of group g for s < 6 (TILTED_KT <= 24), the statistics of the group's expiry for s = 6.  The results
+// are stored where the caller reads them (device memory, or the session's pinned host buffer).
+constexpr int TILTED_FINISH_SUBS = 7;
+static_assert(TILTED_KT <= 4 * (TILTED_FINISH_SUBS - 1) && TILTED_BLOCKS <= 4u * BLOCK, "tilted_finish_kernel's block map and row count");
+__global__ __launch_bounds__(BLOCK) void tilted_finish_kernel(TiltedGroupPack pack, const double *__restrict__ partials, unsigned n_rows,
+                                                              int ld, int stats_col0, double n_path, double *__restrict__ prices,
+                                                              double *__restrict__ stderrs, double *__restrict__ stats,
+                                                              size_t n_strikes, int n_expiries, size_t first_strike, int gamma0)
+{
+    const TiltedGroup &d = pack.g[blockIdx.x / TILTED_FINISH_SUBS];
+    const int sub = blockIdx.x % TILTED_FINISH_SUBS;
+    const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const size_t row_ld = static_cast<size_t>(gridDim.y) * ld;                   // partials[path block][gamma][column]
+    const double *__restrict__ base = partials + static_cast<size_t>(blockIdx.y) * ld;
+    const double *__restrict__ st = base + stats_col0 + TILTED_STAT_COLS * d.slot;
+    const size_t g = static_cast<size_t>(gamma0) + blockIdx.y;                  // the gamma's index in the call
+    if (sub < TILTED_FINISH_SUBS - 1) {
+        const int k = 4 * sub + static_cast<int>(wave);
+        if (k >= d.k) return;                                                   // (wave-uniform)
+        double wq[2], s[3], kept[1];
+        wave_column_sums<2>(st, n_rows, row_ld, lane, wq);
+        wave_column_sums<1>(st + 6, n_rows, row_ld, lane, kept);
+        wave_column_sums<3>(base + 3 * (d.col + k), n_rows, row_ld, lane, s);
+        if (lane != 0u) return;
+        // price = shift + sum w d / sum w; sum (w (pay - price))^2 = sum (w d)^2 - 2 e sum w^2 d + e^2 sum w^2, e = price - shift.
+        // One kept path: the estimate IS that path's payoff and the squares about it are zero identically, where the sums would
+        // leave the square root of their rounding
+        const double e = s[0] / wq[0];
+        const double var = (kept[0] > 1.0) ? fma(e, fma(e, wq[1], -2.0 * s[2]), s[1]) : 0.0;
+        const size_t q = g * n_strikes + first_strike + static_cast<size_t>(d.col + k);
+        prices[q] = e - d.nshift[k];
+        stderrs[q] = sqrt(fmax(var, 0.0)) / wq[0];
+        return;
+    }
+    if (!d.first || wave != 0u) return;
+    double a[4], b[3];
+    wave_column_sums<4>(st, n_rows, row_ld, lane, a);
+    wave_column_sums<3>(st + 4, n_rows, row_ld, lane, b);
+    if (lane != 0u) return;
+    const double W = a[0], Q = a[1], V2 = a[2], D0 = a[3], D1 = b[0], D2 = b[1], kept = b[2];
+    // normalizer n / sum w, a ratio of sums: error sqrt(sum (1 - N w)^2) / sum w = N sqrt(sum (w - mean w)^2) / sum w, the
+    // squares about the mean from the sums of w - 1
+    const double N = kept / W, sv = W - kept;
+    const double dev2 = (kept > 1.0) ? V2 - sv * sv / kept : 0.0;                  // one kept path: zero identically, as above
+    // gamma forward sum w spot / sum w = forward + sum w ds / sum w, its error as a strike's
+    const double gd = D0 / W;
+    const double varg = (kept > 1.0) ? fma(gd, fma(gd, Q, -2.0 * D1), D2) : 0.0;
+    double *out = stats + (g * static_cast<size_t>(n_expiries) + static_cast<size_t>(d.expiry)) * SVMC_TILTED_STATS_DOUBLES;
+    out[0] = N;
+    out[1] = N * sqrt(fmax(dev2, 0.0)) / W;
+    out[2] = d.forward + gd;
+    out[3] = sqrt(fmax(varg, 0.0)) / W;
+    out[4] = (W / Q) * W;                                                      // effective sample size (sum w)^2 / sum w^2
+    out[5] = kept;
+    out[6] = n_path - kept;
+    out[7] = W;
+}
+
+// path blocks of a tilted launch: no block with fewer than SVMC_PAYOFF_MIN_TRIPS paths per lane, TILTED_BLOCKS at most -- a
+// function of the path count alone
+static inline unsigned tilted_path_blocks(size_t n_path)
+{
+    const size_t per = static_cast<size_t>(BLOCK) * SVMC_PAYOFF_MIN_TRIPS;
+    const size_t g = (n_path + per - 1) / per;
+    return static_cast<unsigned>(g < 1 ? 1 : (g > TILTED_BLOCKS ? TILTED_BLOCKS : g));
+}
+
+using TiltedKernel = void (*)(TiltedGroupPack, TiltedGammas, size_t, double *, int, int);
+static TiltedKernel tilted_kernel_for(int kt)
+{
+    if (kt <= 4) return tilted_payoff_group_kernel<4>;
+    if (kt <= 8) return tilted_payoff_group_kernel<8>;
+    if (kt <= 16) return tilted_payoff_group_kernel<16>;
+    return tilted_payoff_group_kernel<TILTED_KT>;
+}
+
+// the launches of svmc_tilted_payoff_chain (its arguments are checked there): up to PAYOFF_GROUPS groups per launch pair, and per
+// pair as many gammas as the workspace holds partials for -- either split leaves every sum's bits alone
+static int tilted_payoff_impl(const char *fn, const double *const *xs, size_t n_path, const double *forwards, int n_expiries,
+                              const double *strikes, const int8_t *types, const double *shifts, const size_t *offsets,
+                              const double *gammas, int n_gammas, const double *spot_sums, double *prices, double *stderrs,
+                              double *stats, void *workspace, size_t workspace_bytes, hipStream_t stream)
+{
+    const size_t total = offsets[n_expiries];
+    const unsigned gx = tilted_path_blocks(n_path);
+    double *partials = static_cast<double *>(workspace);
+    TiltedGroupPack pack;
+    memset(&pack, 0, sizeof(pack));
+    int n_groups = 0, cols = 0, kt = 0, slots = 0;
+    size_t first_strike = 0;
+    auto flush = [&]() -> int {
+        if (n_groups == 0) return SVMC_OK;
+        const int stats_col0 = (3 * cols + 7) / 8 * 8;
+        const int ld = stats_col0 + TILTED_STAT_COLS * slots;
+        const size_t per_gamma = static_cast<size_t>(gx) * ld * sizeof(double);
+        if (per_gamma > workspace_bytes) return fail(SVMC_ERR_WORKSPACE, std::string(fn) + ": workspace too small (svmc_payoff_workspace_bytes)");
+        const int batch = static_cast<int>(workspace_bytes / per_gamma < static_cast<size_t>(n_gammas) ? workspace_bytes / per_gamma : n_gammas);
+        for (int g0 = 0; g0 < n_gammas; g0 += batch) {
+            const int zb = (n_gammas - g0 < batch) ? n_gammas - g0 : batch;
+            TiltedGammas gm;
+            for (int z = 0; z < SVMC_TILTED_MAX_GAMMAS; ++z) gm.g[z] = (z < zb) ? gammas[g0 + z] : 0.0;
+            hipLaunchKernelGGL(tilted_kernel_for(kt), dim3(gx, static_cast<unsigned>(n_groups), static_cast<unsigned>(zb)), dim3(BLOCK), 0,
+                               stream, pack, gm, n_path, partials, ld, stats_col0);
+            hipLaunchKernelGGL(tilted_finish_kernel, dim3(static_cast<unsigned>(n_groups * TILTED_FINISH_SUBS), static_cast<unsigned>(zb)),
+                               dim3(BLOCK), 0, stream, pack, static_cast<const double *>(partials), gx, ld, stats_col0,
+                               static_cast<double>(n_path), prices, stderrs, stats, total, n_expiries, first_strike, g0);
+            if (int rc = check_launch(fn)) return rc;
+        }
+        first_strike += static_cast<size_t>(cols);
+        n_groups = cols = kt = slots = 0;
+        return SVMC_OK;
+    };
+    for (int i = 0; i < n_expiries; ++i) {
+        bool first = true;                      // of this expiry in the pending launch
+        size_t k0 = offsets[i];
+        do {
+            TiltedGroup &d = pack.g[n_groups];
+            d.x = xs[i];
+            d.spot_sums = spot_sums ? spot_sums + 2 * i : nullptr;
+            d.forward = forwards[i];
+            const size_t left = offsets[i + 1] - k0;
+            d.k = static_cast<int>(left < static_cast<size_t>(TILTED_KT) ? left : TILTED_KT);
+            d.col = cols;
+            d.expiry = i;
+            d.first = first ? 1 : 0;
+            if (first) ++slots;
+            d.slot = slots - 1;
+            d.put_mask = 0u;
+            for (int k = 0; k < TILTED_KT; ++k) {
+                const bool on = k < d.k;
+                const double sgn = (on && types[k0 + k] == SVMC_PUT) ? -1.0 : 1.0;
+                const double shift = (on && shifts != nullptr) ? shifts[k0 + k] : 0.0;
+                if (sgn < 0.0) d.put_mask |= 1u << k;
+                d.c[k] = on ? -sgn * strikes[k0 + k] - shift : -__builtin_huge_val();
+                d.nshift[k] = 0.0 - shift;
+            }
+            cols += d.k;
+            kt = (d.k > kt) ? d.k : kt;
+            k0 += static_cast<size_t>(d.k);
+            first = false;
+            if (++n_groups == PAYOFF_GROUPS) {
+                if (int rc = flush()) return rc;
+                first = true;                   // what is left of this expiry writes its statistics again, the same bits
+            }
+        } while (k0 < offsets[i + 1]);
+    }
+    return flush();
+}
+
 // the stepping of svmc_chain.hip's fused chains from the start state (0, sigma0 | var0, 0): svmc_*_chain_rng_from, or the slice
 // kernel for a single expiry; spot_sums null leaves the per-wave partial columns in `workspace` for the one-device tail
 int logsv_step_partials(double sigma0, double *x, double *sigma, double *qvar, size_t n_path, int n_slices, const int *nb_steps_host,
@@ -3393,6 +3677,38 @@ int svmc_payoff_sums_chain(const double *const *x_snapshots_host, const double *
     return payoff_sums_impl("svmc_payoff_sums_chain", x_snapshots_host, qvar_snapshots_host, n_path, forwards_host, ttms_host,
                             spot_sums, n_expiries, strikes_host, types_host, shifts_host, strike_offsets_host, variable_type,
                             sums, workspace, workspace_bytes, stream);
+}
+
+int svmc_tilted_payoff_chain(const double *const *x_snapshots_host, size_t n_path, const double *forwards_host, int n_expiries,
+                             const double *strikes_host, const int8_t *types_host, const double *shifts_host,
+                             const size_t *strike_offsets_host, const double *gammas_host, int n_gammas, int recenter,
+                             const double *spot_sums, double *prices, double *stderrs, double *stats, void *workspace,
+                             size_t workspace_bytes, svmc_stream_t stream)
+{
+    const char *fn = "svmc_tilted_payoff_chain";
+    SVMC_REQUIRE(x_snapshots_host && forwards_host && strike_offsets_host && gammas_host && prices && stderrs && stats && workspace,
+                 std::string(fn) + ": null pointer");
+    SVMC_REQUIRE(n_path >= 1 && n_expiries >= 1, std::string(fn) + ": n_path and n_expiries must be positive");
+    SVMC_REQUIRE(n_gammas >= 1 && n_gammas <= SVMC_TILTED_MAX_GAMMAS, std::string(fn) + ": n_gammas outside 1 .. SVMC_TILTED_MAX_GAMMAS");
+    SVMC_REQUIRE(!recenter || spot_sums != nullptr, std::string(fn) + ": recenter needs spot_sums");
+    const size_t total = strike_offsets_host[n_expiries];
+    SVMC_REQUIRE(total == 0 || (strikes_host && types_host), std::string(fn) + ": null strikes/types");
+    for (int g = 0; g < n_gammas; ++g) SVMC_REQUIRE(std::isfinite(gammas_host[g]), std::string(fn) + ": a gamma is not finite");
+    for (int i = 0; i < n_expiries; ++i) {
+        SVMC_REQUIRE(x_snapshots_host[i] != nullptr, std::string(fn) + ": null snapshot");
+        SVMC_REQUIRE(std::isfinite(forwards_host[i]), std::string(fn) + ": a forward is not finite");
+        SVMC_REQUIRE(strike_offsets_host[i] <= strike_offsets_host[i + 1], std::string(fn) + ": strike offsets must not decrease");
+    }
+    for (size_t k = 0; k < total; ++k) {
+        if (types_host[k] != SVMC_CALL && types_host[k] != SVMC_PUT) return fail(SVMC_ERR_UNKNOWN_PAYOFF, "unknown option payoff code");
+        SVMC_REQUIRE(std::isfinite(strikes_host[k]) && (shifts_host == nullptr || std::isfinite(shifts_host[k])),
+                     std::string(fn) + ": a strike or shift is not finite");
+    }
+    if (workspace_bytes < static_cast<size_t>(MAX_REDUCE_GRID) * 3 * PAYOFF_KT * PAYOFF_GROUPS * sizeof(double))
+        return fail(SVMC_ERR_WORKSPACE, std::string(fn) + ": workspace too small (svmc_payoff_workspace_bytes)");
+    return tilted_payoff_impl(fn, x_snapshots_host, n_path, forwards_host, n_expiries, strikes_host, types_host, shifts_host,
+                              strike_offsets_host, gammas_host, n_gammas, recenter ? spot_sums : nullptr, prices, stderrs, stats,
+                              workspace, workspace_bytes, as_stream(stream));
 }
 
 int svmc_payoff_finalize(const double *sums_host, const double *shifts_host, size_t n_strikes, double discfactor,

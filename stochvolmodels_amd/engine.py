@@ -356,6 +356,79 @@ def marshalled_chain(ttms, forwards, discfactors, strikes: Sequence[np.ndarray],
     return hit
 
 
+# ---- prices under the exponential risk-premia kernel (include/svmc.h, svmc_tilted_payoff_chain): host side, no library -------
+TILTED_MAX_GAMMAS = 16         # SVMC_TILTED_MAX_GAMMAS
+TILTED_STATS_DOUBLES = 8       # SVMC_TILTED_STATS_DOUBLES
+TILTED_STATS_FIELDS = ("normalizer", "normalizer_stderr", "gamma_forward", "gamma_forward_stderr", "effective_sample_size",
+                       "n_kept", "n_dropped", "sum_weights")
+
+
+def tilted_type_codes(optiontypes) -> np.ndarray:
+    """'C' -> 0, 'P' -> 1 as int8; any other type raises ValueError("not implemented"), as the Fourier risk-premia slice pricer"""
+    types = np.asarray(optiontypes).ravel()
+    codes = np.empty(types.size, dtype=np.int8)
+    for i, t in enumerate(types):
+        t = str(t)
+        if t not in ("C", "P"):
+            raise ValueError("not implemented")
+        codes[i] = 0 if t == "C" else 1
+    return codes
+
+
+def tilted_gammas(gammas) -> np.ndarray:
+    """the gammas of one call as a float64 vector: 1 .. TILTED_MAX_GAMMAS finite values, else ValueError"""
+    g = np.ascontiguousarray(np.atleast_1d(np.asarray(gammas, dtype=np.float64))).ravel()
+    if not 1 <= g.size <= TILTED_MAX_GAMMAS:
+        raise ValueError(f"between 1 and {TILTED_MAX_GAMMAS} risk-premia gammas per call, got {g.size}")
+    if not np.all(np.isfinite(g)):
+        raise ValueError("risk-premia gammas must be finite")
+    return g
+
+
+def tilted_chain_arrays(forwards, strikes: Sequence[np.ndarray], codes: Sequence[np.ndarray], gammas, ttms=None) -> dict:
+    """the host arrays of a tilted call, checked: one forward (and ttm) per expiry, finite forwards and strikes, codes 0 / 1 of
+    the strikes' sizes, the gammas of tilted_gammas"""
+    g = tilted_gammas(gammas)
+    strikes = [np.asarray(k, dtype=np.float64) for k in strikes]
+    codes = [np.ascontiguousarray(np.asarray(c).ravel(), dtype=np.int8) for c in codes]
+    f = np.ascontiguousarray(np.asarray(forwards, dtype=np.float64)).ravel()
+    m = len(strikes)
+    if not (f.size == m == len(codes)) or m < 1:
+        raise ValueError("chain arrays must have one entry per maturity")
+    for k, c in zip(strikes, codes):
+        if k.size != c.size:
+            raise ValueError("strikes and optiontypes of a slice differ in length")
+        if c.size and (c.min() < 0 or c.max() > 1):
+            raise ValueError("not implemented")
+    offs = np.concatenate([[0], np.cumsum([k.size for k in strikes])]).astype(np.uintp)
+    total = int(offs[-1])
+    k_all = np.ascontiguousarray(np.concatenate([k.ravel() for k in strikes])) if total else np.zeros(1)
+    c_all = np.ascontiguousarray(np.concatenate(codes)) if total else np.zeros(1, dtype=np.int8)
+    if not (np.all(np.isfinite(f)) and np.all(np.isfinite(k_all))):
+        raise ValueError("forwards and strikes must be finite")
+    out = {"m": m, "total": total, "offs": offs, "forwards": f, "strikes": k_all, "codes": c_all, "gammas": g,
+           "strikes_ttms": [k.ravel() for k in strikes], "codes_ttms": codes, "shapes": [k.shape for k in strikes]}
+    if ttms is not None:
+        t = np.ascontiguousarray(np.asarray(ttms, dtype=np.float64)).ravel()
+        if t.size != m:
+            raise ValueError("chain arrays must have one entry per maturity")
+        out["ttms"] = t
+    return out
+
+
+def tilted_results(prices: np.ndarray, stderrs: np.ndarray, stats: np.ndarray, ch: dict):
+    """flat [G][K] prices / errors and [G][m][8] statistics -> ([G][m] arrays in the strikes' shapes, the same, stats [G, m, 8])"""
+    G, K, offs = ch["gammas"].size, ch["total"], ch["offs"]
+    cut = lambda a: [[a[g * K + int(offs[i]):g * K + int(offs[i + 1])].reshape(ch["shapes"][i]).copy()    # noqa: E731
+                      for i in range(ch["m"])] for g in range(G)]
+    return cut(prices), cut(stderrs), np.array(stats, dtype=np.float64).reshape(G, ch["m"], TILTED_STATS_DOUBLES)
+
+
+def tilted_stats_dicts(stats: np.ndarray) -> list:
+    """stats [m, 8] of one gamma -> one dict per expiry, keys TILTED_STATS_FIELDS (the two counts as ints)"""
+    return [{k: (int(v) if k in ("n_kept", "n_dropped") else float(v)) for k, v in zip(TILTED_STATS_FIELDS, row)} for row in stats]
+
+
 MANY_MAX_JOBS = 64             # jobs per svmc_*_chain_price_many call: SVMC_MANY_MAX_JOBS of include/svmc.h
 BULK_KEEP_FRACTION = 0.125     # of the device's memory: what an engine's cached bulk buffers may hold between calls (trim_bulk)
 
@@ -499,19 +572,25 @@ class HipEngine:
     def _fused_call(self, ch: dict, call, kernel_name: str):
         """run call(session, prices_ptr, stderrs_ptr) and cut the two result rows into per-expiry arrays; while kernel timing is
         on (start_kernel_timing) the session brackets its stepping launch with HIP events and the time is kept under kernel_name"""
+        res = np.empty((2, max(ch["total"], 1)))
+        dp = C.POINTER(C.c_double)
+        self._session_call(ch, lambda sess: call(sess, C.cast(res.ctypes.data, dp), C.cast(res.ctypes.data + res.strides[0], dp)),
+                           kernel_name)
+        return [res[0, sl] for sl in ch["slices"]], [res[1, sl] for sl in ch["slices"]]
+
+    def _session_call(self, ch: dict, call, kernel_name: str) -> None:
+        """run call(session) on the fused chain session of ch's size, the stepping launch timed under kernel_name while kernel
+        timing is on"""
         sess = self.fused_chain_session(ch["m"], ch["total"])
         timing = self._prof is not None
         if timing != self._fused_timing:
             _lib.check(self.lib.svmc_session_time_stepping(sess, int(timing)))
             self._fused_timing = timing
-        res = np.empty((2, max(ch["total"], 1)))
-        dp = C.POINTER(C.c_double)
-        _lib.check(call(sess, C.cast(res.ctypes.data, dp), C.cast(res.ctypes.data + res.strides[0], dp)))
+        _lib.check(call(sess))
         if timing:
             ms = C.c_float()
             _lib.check(self.lib.svmc_session_last_stepping_ms(sess, C.byref(ms)))
             self._prof.append((kernel_name, float(ms.value), None))
-        return [res[0, sl] for sl in ch["slices"]], [res[1, sl] for sl in ch["slices"]]
 
     def price_logsv_chain_fused(self, ch: dict, v0, theta, kappa1, kappa2, beta, volvol, etas, is_spot_measure, nb_steps_per_year,
                                 variable_type: int, seed: int, call_id: int):
@@ -878,6 +957,53 @@ class HipEngine:
             xs, qs, self.n_path, fw.ctypes.data_as(dp), tt.ctypes.data_as(dp), spot_sums_ptr, m, k_all.ctypes.data_as(dp),
             c_all.ctypes.data_as(C.POINTER(C.c_int8)), s_all.ctypes.data_as(dp), offs.ctypes.data_as(C.POINTER(C.c_size_t)),
             int(variable_type), out_ptr, self.ws.ptr, self.ws_bytes, self.stream))
+
+    def tilted_payoffs(self, forwards, strikes: Sequence[np.ndarray], codes: Sequence[np.ndarray], gammas, recenter: bool = False,
+                       snap_rows: Optional[Sequence[int]] = None):
+        """prices under the exponential risk-premia kernel exp(gamma x) (svmc_tilted_payoff_chain, include/svmc.h) of the
+        resident log-returns, whichever generator left them: expiry i reads snapshot row snap_rows[i], or, with snap_rows None,
+        the one expiry reads the current state x.  codes: 0 ('C') / 1 ('P') per strike.  Returns (prices [G][m] -> [K_i],
+        stderrs the same, stats [G, m, TILTED_STATS_FIELDS]) for the G gammas; one download."""
+        ch = tilted_chain_arrays(forwards, strikes, codes, gammas)
+        m, K, G = ch["m"], ch["total"], ch["gammas"].size
+        if (m != 1) if snap_rows is None else (len(snap_rows) != m):
+            raise ValueError("one snapshot row per expiry (the current state serves one expiry)")
+        ptrs = [self.x.ptr] if snap_rows is None else [self.snapshot_ptr(r) for r in snap_rows]
+        dp = C.POINTER(C.c_double)
+        shifts = np.ascontiguousarray(np.concatenate([payoff_shifts(k, c, float(f), LOG_RETURN)
+                                                      for k, c, f in zip(ch["strikes_ttms"], ch["codes_ttms"], ch["forwards"])]))
+        spot_ptr = None
+        if recenter:
+            spot_ptr, _ = self.alloc_sums(2 * m, "tilted_spot")
+            for i, p in enumerate(ptrs):
+                self.spot_sums(p, float(ch["forwards"][i]), spot_ptr + 16 * i)
+        n_out = 2 * G * K + G * m * TILTED_STATS_DOUBLES
+        out_ptr, _ = self.alloc_sums(n_out, "tilted")
+        xs = (C.c_void_p * m)(*ptrs)
+        _lib.check(self.lib.svmc_tilted_payoff_chain(
+            xs, self.n_path, ch["forwards"].ctypes.data_as(dp), m, ch["strikes"].ctypes.data_as(dp),
+            ch["codes"].ctypes.data_as(C.POINTER(C.c_int8)), shifts.ctypes.data_as(dp), ch["offs"].ctypes.data_as(C.POINTER(C.c_size_t)),
+            ch["gammas"].ctypes.data_as(dp), G, int(bool(recenter)), spot_ptr, out_ptr, out_ptr + 8 * G * K, out_ptr + 16 * G * K,
+            self.ws.ptr, self.ws_bytes, self.stream))
+        out = self.download(out_ptr, n_out)
+        return tilted_results(out[:G * K], out[G * K:2 * G * K], out[2 * G * K:], ch)
+
+    def price_hawkesjd_chain_tilted_fused(self, ch: dict, params: np.ndarray, nb_steps_per_year: int, seed: int, call_id: int,
+                                          gammas, recenter: bool):
+        """the Hawkes chain under the risk-premia kernel for every gamma from ONE stepping launch, as one
+        svmc_hawkesjd_chain_price_tilted call on this engine's state (ch: tilted_chain_arrays); returns as tilted_payoffs.  The
+        plain measure is not a separate output: gamma = 0 with recenter is svmc_hawkesjd_chain_price at discount factors 1, so a
+        caller who wants both measures puts 0 among the gammas"""
+        params = np.ascontiguousarray(params, dtype=np.float64)
+        m, K, G = ch["m"], ch["total"], ch["gammas"].size
+        dp = C.POINTER(C.c_double)
+        prices, stderrs, stats = np.empty(max(G * K, 1)), np.empty(max(G * K, 1)), np.empty(G * m * TILTED_STATS_DOUBLES)
+        self._session_call(ch, lambda sess: self.lib.svmc_hawkesjd_chain_price_tilted(
+            sess, ch["ttms"].ctypes.data_as(dp), ch["forwards"].ctypes.data_as(dp), m, ch["strikes"].ctypes.data_as(dp),
+            ch["codes"].ctypes.data_as(C.POINTER(C.c_int8)), ch["offs"].ctypes.data_as(C.POINTER(C.c_size_t)), params.ctypes.data_as(dp),
+            int(nb_steps_per_year), int(seed), int(call_id), ch["gammas"].ctypes.data_as(dp), G, int(bool(recenter)),
+            prices.ctypes.data_as(dp), stderrs.ctypes.data_as(dp), stats.ctypes.data_as(dp)), "hawkesjd_chain_rng_kernel")
+        return tilted_results(prices[:G * K], stderrs[:G * K], stats, ch)
 
     def close(self) -> None:
         """free every HBM buffer of the engine; any later launch through it fails in the C ABI's null-pointer

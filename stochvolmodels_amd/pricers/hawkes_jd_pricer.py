@@ -20,7 +20,11 @@ one launch (hawkes_risk_forwards_kernel: the coefficient ODEs from zero over eac
 the chained coefficient ODEs on the grid of real part -0.5 - gamma, and per expiry one inversion launch that finishes the
 prices on the device (mgf_gamma_slice_kernel); hawkesjd_chain_pricer_with_risk_premia_batch prices several (sigma, gamma) sets
 side by side for the calibration's gradient.
-The reference's quirks are kept: `risk_premia_gamma` is accepted and unused by the Monte Carlo, `is_spot_measure` is ignored
+Monte Carlo under that kernel (hawkesjd_mc_chain_pricer_with_risk_premia(_gammas), not in the reference, whose users weight
+downloaded paths by hand): one stepping launch, then the exponentially weighted payoff reduction of the resident snapshots for
+every gamma at once (tilted_payoff_group_kernel), with delta-method standard errors, the normalizer, the gamma forward and the
+effective sample size per expiry.
+The reference's quirks are kept: `risk_premia_gamma` is accepted and unused by hawkesjd_mc_chain_pricer, `is_spot_measure` is ignored
 by it, and a variable_type other than LOG_RETURN raises (the reference would price the log-return as a variance).  Under the
 risk-premia kernel: the forwards follow zip(ttms, forwards) (entries beyond the shorter stay 1.0), discfactors are ignored
 (the prices are undiscounted), and the calibration mutates and returns params0.
@@ -41,7 +45,7 @@ from .. import _lib
 from .. import dist as svdist
 from ..analytic import ODE_ATOL, ODE_RTOL, AnalyticGrid, chain_prices_from_sums, chain_sums
 from ..data.option_chain import OptionChain
-from ..engine import DeviceBuffer, get_engine, marshalled_chain, option_type_codes
+from ..engine import DeviceBuffer, get_engine, marshalled_chain, option_type_codes, tilted_chain_arrays, tilted_type_codes
 from ..mc_chain import variable_type_code
 from ..utils import mgf_pricer as mgfp
 from ..utils.calibration import ImpliedVolObjective, chain_calibration_weights
@@ -289,6 +293,19 @@ class HawkesJDPricer(ModelPricer):
         if print_iter:
             print(f"unpack_pars: sigma={res.x[0]}, gamma={fit.risk_premia_gamma}")
         return fit
+
+    @timer
+    def model_mc_price_chain_with_risk_premia(self, option_chain: OptionChain, params: HawkesJDParams, nb_path: int = 100000,
+                                              **kwargs) -> Tuple[List[np.ndarray], List[np.ndarray]]:
+        """Monte Carlo chain prices under the risk-premia kernel of params.risk_premia_gamma
+        (hawkesjd_mc_chain_pricer_with_risk_premia); extensions seed=, nb_steps_per_year=, recenter_forward=, return_forwards="""
+        if params.risk_premia_gamma is None:
+            raise ValueError("risk_premia_gamma must be set for the risk-premia pricer")
+        return hawkesjd_mc_chain_pricer_with_risk_premia(ttms=option_chain.ttms, forwards=option_chain.forwards,
+                                                         discfactors=option_chain.discfactors,
+                                                         strikes_ttms=option_chain.strikes_ttms,
+                                                         optiontypes_ttms=option_chain.optiontypes_ttms, nb_path=nb_path,
+                                                         **params.to_dict(), **kwargs)
 
     @timer
     def simulate_terminal_values(self, params: HawkesJDParams, ttm: float = 1.0, nb_path: int = 100000,
@@ -585,6 +602,69 @@ def hawkesjd_mc_chain_pricer(ttms: np.ndarray, forwards: np.ndarray, discfactors
     prices, stderrs = eng.price_hawkesjd_chain_fused(ch, block, int(nb_steps_per_year), LOG_RETURN, rng_seed, call_id)
     return ([a.reshape(np.shape(k)) for a, k in zip(prices, strikes_ttms)],
             [a.reshape(np.shape(k)) for a, k in zip(stderrs, strikes_ttms)])
+
+
+def hawkesjd_mc_chain_pricer_with_risk_premia_gammas(ttms: np.ndarray, forwards: np.ndarray, discfactors: np.ndarray,
+                                                     strikes_ttms: Sequence[np.ndarray], optiontypes_ttms: Sequence[np.ndarray],
+                                                     lambda_p: float, lambda_m: float, mu: float, sigma: float, shift_p: float,
+                                                     mean_p: float, shift_m: float, mean_m: float, theta_p: float,
+                                                     kappa_p: float, beta1_p: float, beta2_p: float, theta_m: float,
+                                                     kappa_m: float, beta1_m: float, beta2_m: float,
+                                                     risk_premia_gammas: Sequence[float] = (0.0,), nb_path: int = 100000,
+                                                     variable_type: VariableType = VariableType.LOG_RETURN,
+                                                     nb_steps_per_year: int = NB_STEPS_PER_YEAR, seed: Optional[int] = None,
+                                                     recenter_forward: bool = False, return_forwards: bool = False, comm=None,
+                                                     devices=None, risk_premia_gamma=None):
+    """Monte Carlo chain prices under the exponential risk-premia kernel exp(gamma x) for SEVERAL gammas from ONE stepping launch
+    (svmc_hawkesjd_chain_price_tilted): the paths of hawkesjd_mc_chain_pricer on this seed, then per gamma the weighted payoff
+    reduction of include/svmc.h (svmc_tilted_payoff_chain: the estimator, its keep rule and its delta-method errors) on the
+    resident snapshots -- no path leaves the device.  Returns (prices, stderrs), each [gamma][expiry] in the strikes' shapes;
+    with return_forwards=True a third item [gamma] -> (normalizers, gamma_forwards, stats), the Monte Carlo counterparts of
+    hawkesjd_forwards_under_risk_kernel per expiry and stats [n_expiries, 8] in the order of engine.TILTED_STATS_FIELDS
+    (normalizer, its error, gamma forward, its error, effective sample size, n_kept, n_dropped, sum of weights).
+    Prices are UNDISCOUNTED like the Fourier risk-premia pricer's: discfactors are accepted and ignored.  'C' / 'P' only (others:
+    ValueError("not implemented")), LOG_RETURN only.  recenter_forward: spot = F exp(x) - (nanmean(F exp(x)) - F), as
+    compute_mc_vars_payoff recentres; gamma = 0 with it is hawkesjd_mc_chain_pricer at discount factors 1.  A gamma's results
+    are the same bits whichever other gammas share the call.  risk_premia_gamma= is accepted and unused here (the keyword of
+    HawkesJDParams.to_dict()).
+    Against the Fourier pricer: hawkesjd_chain_pricer_with_risk_premia multiplies its capped sum by K^(1+gamma), not
+    K^(1+gamma) F^(-gamma), so it equals the payoff expectation priced here only at F = 1 (the paper's case); this function
+    prices the payoff as written for any F."""
+    _check_variable_type(variable_type)
+    if devices is not None or (comm.world if comm is not None else svdist.get_default_comm().world) > 1:
+        raise NotImplementedError("hawkesjd_mc_chain_pricer_with_risk_premia: not sharded over ranks or devices")
+    strikes_ttms = [np.asarray(k, dtype=np.float64) for k in strikes_ttms]
+    codes = [tilted_type_codes(t) for t in optiontypes_ttms]                # ValueError("not implemented")
+    ch = tilted_chain_arrays(forwards, strikes_ttms, codes, risk_premia_gammas, ttms=ttms)
+    block = params_block(lambda_p=lambda_p, lambda_m=lambda_m, mu=mu, sigma=sigma, shift_p=shift_p, mean_p=mean_p,
+                         shift_m=shift_m, mean_m=mean_m, theta_p=theta_p, kappa_p=kappa_p, beta1_p=beta1_p, beta2_p=beta2_p,
+                         theta_m=theta_m, kappa_m=kappa_m, beta1_m=beta1_m, beta2_m=beta2_m)
+    eng = get_engine(int(nb_path))
+    rng_seed, call_id = next_rng_call(seed)
+    prices, stderrs, stats = eng.price_hawkesjd_chain_tilted_fused(ch, block, int(nb_steps_per_year), rng_seed, call_id,
+                                                                   ch["gammas"], bool(recenter_forward))
+    if not return_forwards:
+        return prices, stderrs
+    return prices, stderrs, [(st[:, 0].copy(), st[:, 2].copy(), st) for st in stats]
+
+
+def hawkesjd_mc_chain_pricer_with_risk_premia(ttms: np.ndarray, forwards: np.ndarray, discfactors: np.ndarray,
+                                              strikes_ttms: Sequence[np.ndarray], optiontypes_ttms: Sequence[np.ndarray],
+                                              risk_premia_gamma: float = None, nb_path: int = 100000,
+                                              nb_steps_per_year: int = NB_STEPS_PER_YEAR, seed: Optional[int] = None,
+                                              recenter_forward: bool = False, return_forwards: bool = False, **kwargs):
+    """hawkesjd_mc_chain_pricer_with_risk_premia_gammas at ONE gamma, so the two agree bit for bit: (prices, stderrs) per
+    expiry, with return_forwards=True also (normalizers, gamma_forwards, stats).  kwargs: the model parameters (and
+    variable_type=, comm=, devices=) of that function."""
+    if risk_premia_gamma is None:
+        raise ValueError("risk_premia_gamma must be set for the risk-premia pricer")
+    out = hawkesjd_mc_chain_pricer_with_risk_premia_gammas(ttms=ttms, forwards=forwards, discfactors=discfactors,
+                                                           strikes_ttms=strikes_ttms, optiontypes_ttms=optiontypes_ttms,
+                                                           risk_premia_gammas=[risk_premia_gamma], nb_path=nb_path,
+                                                           nb_steps_per_year=nb_steps_per_year, seed=seed,
+                                                           recenter_forward=recenter_forward, return_forwards=return_forwards,
+                                                           **kwargs)
+    return tuple(o[0] for o in out)
 
 
 def _broadcast(v, nb_path: int, fill) -> np.ndarray:

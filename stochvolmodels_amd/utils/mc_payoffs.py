@@ -11,7 +11,8 @@ from typing import Tuple
 
 import numpy as np
 
-from ..engine import get_engine, option_type_codes, payoff_finalize, payoff_shifts
+from ..engine import (get_engine, option_type_codes, payoff_finalize, payoff_shifts, tilted_chain_arrays, tilted_stats_dicts,
+                      tilted_type_codes)
 from ..mc_chain import variable_type_code
 from .config import VariableType
 
@@ -38,3 +39,28 @@ def compute_mc_vars_payoff(x0: np.ndarray, sigma0: np.ndarray, qvar0: np.ndarray
     sums = eng.download(ptr + 16, 3 * strikes.size)
     prices, stderrs = payoff_finalize(sums, shifts, float(discfactor), float(n))
     return prices.reshape(strikes.shape), stderrs.reshape(strikes.shape)
+
+
+def compute_mc_vars_payoff_with_gamma(x0: np.ndarray, forward: float, strikes_ttm: np.ndarray, optiontypes_ttm: np.ndarray,
+                                      risk_premia_gamma: float, recenter_forward: bool = False, return_stats: bool = False,
+                                      variable_type: VariableType = VariableType.LOG_RETURN):
+    """option prices under the exponential risk-premia kernel from terminal log-returns x0 (host array), the estimator of
+    include/svmc.h's svmc_tilted_payoff_chain: w = exp(gamma x), spot = forward exp(x) - corr (corr = 0, or
+    compute_mc_vars_payoff's recentring nanmean(forward exp(x)) - forward with recenter_forward), a path kept iff x, w^2 and
+    (w spot)^2 are finite, price = sum w pay / sum w (undiscounted) and its delta-method standard error.  'C' / 'P' only (others:
+    ValueError("not implemented")), LOG_RETURN only (NotImplementedError).  Returns (prices, stderrs) in the strikes' shape, and
+    with return_stats=True a third item: the dict of engine.TILTED_STATS_FIELDS (normalizer, gamma forward, their errors, the
+    effective sample size, n_kept, n_dropped, sum of weights).  Follows compute_mc_vars_payoff's route: upload, reduce on the
+    device, K prices back."""
+    if variable_type_code(variable_type) != 1:
+        raise NotImplementedError(f"variable_type={variable_type}: the risk-premia kernel weights the log-return only")
+    codes = tilted_type_codes(optiontypes_ttm)                   # ValueError("not implemented")
+    strikes = np.asarray(strikes_ttm, dtype=np.float64)
+    ch = tilted_chain_arrays([float(forward)], [strikes], [codes], [float(risk_premia_gamma)])
+    x0 = np.ascontiguousarray(x0, dtype=np.float64)
+    eng = get_engine(x0.shape[0])
+    eng.upload(eng.x.ptr, x0)
+    prices, stderrs, stats = eng.tilted_payoffs(ch["forwards"], [strikes], [codes], ch["gammas"], bool(recenter_forward))
+    if return_stats:
+        return prices[0][0], stderrs[0][0], tilted_stats_dicts(stats[0])[0]
+    return prices[0][0], stderrs[0][0]
