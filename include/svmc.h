@@ -718,6 +718,42 @@ SVMC_API int svmc_kde_gaussian(const double *values, size_t n, double divisor, d
                                double bandwidth_factor, double *density, double *stats, void *workspace, size_t workspace_bytes,
                                svmc_stream_t stream);
 
+/* ---- weighted Gaussian kernel density estimate of a resident vector (src svmc_density.hip) ---------------
+ * scipy.stats.gaussian_kde(kept, weights=w_kept)(points): svmc_kde_gaussian with a non-negative weight per sample.
+ *   1. sample: v_i = values[i] / divisor (a division, as above);
+ *   2. weight: w_i = (weights ? weights[i] : 1) * (tilt ? exp(gamma tilt[i]) : 1).  weights and tilt are device [n] or NULL;
+ *      tilt is the UNdivided log-return, so qvar / ttm or the volatility can be weighted by exp(gamma x).  The exponential is
+ *      inf above 746, +0 below -746 and NaN at NaN.  With both NULL no exponential is taken and w_i is the literal 1.0;
+ *   3. sample i is kept iff v_i passes step 1 of svmc_kde_gaussian (not NaN, not beyond +-limit, strict comparisons), w_i >= 0,
+ *      and w_i and w_i^2 are finite.  A dropped sample adds +0 to every sum.  A sample whose value fails is counted in n_nan /
+ *      n_low / n_high whatever its weight; a sample whose value passes and whose weight fails (a NaN weight or tilt, a negative
+ *      weight, an infinite weight, an overflowed exponential or square) is counted in n_bad_weight.  A zero weight is kept;
+ *   4. sw = sum w, sw2 = sum w^2, neff = sw^2 / sw2 (formed as sw (sw / sw2)), mean = sum w v / sw, then var = sum w (v - mean)^2
+ *      / (sw - sw2 / sw) over the kept samples (two passes, as np.cov(aweights=w, ddof=1));
+ *   5. h = sqrt(var) factor, factor = bandwidth_factor where that is positive and Scott's neff^(-1/5) otherwise;
+ *   6. density[j] = sum_i w_i exp(-((points[j] - v_i) / h)^2 / 2) / (sw h sqrt(2 pi)).
+ * points, density: device [n_points], 1 <= n_points <= SVMC_KDE_MAX_POINTS; stats: device [SVMC_KDE_WEIGHTED_STATS_DOUBLES] =
+ * {n_kept, n_nan, n_low, n_high, n_bad_weight, sum_w, neff, mean, var, h, factor, sum_w2}, the counts as doubles.  Six launches
+ * on `stream`, no allocation, no host round trip.  Fewer than two kept samples, or a variance that is not positive and finite
+ * (a single non-zero weight gives sw - sw2 / sw = 0), are NOT errors of the call: the stats block reports them, the density is
+ * whatever the arithmetic gives, and the host decides.  Refused with SVMC_ERR_INVALID_ARGUMENT: a null values, points, density,
+ * stats or workspace pointer, n < 1, n_points outside its range, a divisor or limit that is not positive and finite, a
+ * non-finite bandwidth factor, a non-finite gamma (also where tilt is NULL); with SVMC_ERR_WORKSPACE: a workspace below
+ * 8 (2048 + n_chunks n_points) bytes.
+ * Deterministic: the chunk length and the order of every sum are svmc_kde_gaussian's and depend on n alone, so the density of a
+ * (vector, weights, tilt, gamma) at a point is the same bits whichever other points, vectors or gammas share the stream.  With
+ * weights == NULL and tilt == NULL every product with w = 1.0 is exact: the density, the four counts, mean, var, h and factor
+ * EQUAL svmc_kde_gaussian's bit for bit (n_bad_weight = 0, sum_w = sum_w2 = neff = n_kept).  Several gammas are several calls.
+ *   svmc_kde_weighted_workspace_bytes   host only: the workspace that serves any n_points <= SVMC_KDE_MAX_POINTS at this n (the
+ *                                       first moment pass carries eight rows, so it is larger than svmc_kde_workspace_bytes),
+ *                                       and (where chunk_length is not NULL) the chunk length, which is svmc_kde_gaussian's. */
+#define SVMC_KDE_WEIGHTED_STATS_DOUBLES 12
+SVMC_API int svmc_kde_weighted_workspace_bytes(size_t n, size_t *bytes, size_t *chunk_length);
+SVMC_API int svmc_kde_gaussian_weighted(const double *values, const double *weights, const double *tilt, double gamma, size_t n,
+                                        double divisor, double limit, const double *points, int n_points,
+                                        double bandwidth_factor, double *density, double *stats, void *workspace,
+                                        size_t workspace_bytes, svmc_stream_t stream);
+
 /* ---- Monte Carlo prices under the exponential risk-premia kernel (src svmc_kernels.hip, svmc_chain.hip) ----
  * For one expiry with terminal log-returns x_j, forward F, strikes K_k of type 'C' / 'P' and one risk-premia gamma:
  *   w_j = exp(gamma x_j),  spot_j = F exp(x_j) - corr,  corr = 0, or with recenter != 0 the recentring of svmc_payoff_sums,

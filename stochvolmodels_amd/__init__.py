@@ -8,7 +8,7 @@ Module layout and public names mirror the reference package (`stochvolmodels`) f
                                               simulate_heston_x_vol_terminal
     stochvolmodels_amd.pricers.hawkes_jd_pricer  HawkesJDPricer, HawkesJDParams, hawkesjd_mc_chain_pricer,
                                               hawkesjd_chain_pricer(_batch), simulate_hawkesjd_terminal,
-                                              hawkesjd_forwards_under_risk_kernel,
+                                              hawkesjd_forwards_under_risk_kernel, hawkesjd_pdf_under_risk_kernel,
                                               hawkesjd_chain_pricer_with_risk_premia(_batch),
                                               hawkesjd_mc_chain_pricer_with_risk_premia(_gammas)
     stochvolmodels_amd.utils.mc_payoffs       compute_mc_vars_payoff, compute_mc_vars_payoff_with_gamma
@@ -33,6 +33,7 @@ _EXPORTS = {
     "compute_mc_vars_payoff_with_gamma": "utils.mc_payoffs",
     "hawkesjd_mc_chain_pricer_with_risk_premia": "pricers.hawkes_jd_pricer",
     "hawkesjd_mc_chain_pricer_with_risk_premia_gammas": "pricers.hawkes_jd_pricer",
+    "hawkesjd_pdf_under_risk_kernel": "pricers.hawkes_jd_pricer",
     "OptionChain": "data.option_chain",
     "ModelParams": "pricers.model_pricer", "ModelPricer": "pricers.model_pricer",
     "LogSvParams": "pricers.logsv.logsv_params",

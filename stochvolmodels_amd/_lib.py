@@ -161,6 +161,8 @@ def _declare(L: C.CDLL) -> None:
         "svmc_histogram_uniform": ([vp, sz, f64, vp, i32, vp, vp], i32),
         "svmc_kde_workspace_bytes": ([sz, psz, psz], i32),
         "svmc_kde_gaussian": ([vp, sz, f64, f64, vp, i32, f64, vp, vp, vp, sz, vp], i32),
+        "svmc_kde_weighted_workspace_bytes": ([sz, psz, psz], i32),
+        "svmc_kde_gaussian_weighted": ([vp, vp, vp, f64, sz, f64, f64, vp, i32, f64, vp, vp, vp, sz, vp], i32),
         "svmc_tilted_payoff_chain": ([C.POINTER(vp), sz, pf64, i32, pf64, pi8, pf64, psz, pf64, i32, i32, vp, vp, vp, vp, vp, sz, vp],
                                      i32),
         "svmc_hawkesjd_chain_price_tilted": ([vp, pf64, pf64, i32, pf64, pi8, psz, pf64, i32, u64, u32, pf64, i32, i32, pf64, pf64,

@@ -536,15 +536,75 @@ def device_kdes(value_ptrs: Sequence[int], n: int, grids: Sequence[np.ndarray], 
             for i in range(n_vec)]
 
 
-def kde_stats(block: np.ndarray) -> dict:
-    """a downloaded stats block of svmc_kde_gaussian as a dict (the four counts as ints), with gaussian_kde's refusals: ValueError
-    for fewer than two kept samples, LinAlgError for a variance that is not positive and finite"""
-    stats = {k: (int(v) if k.startswith("n_") and np.isfinite(v) else float(v)) for k, v in zip(KDE_STATS_FIELDS, block)}
+def kde_stats(block: np.ndarray, fields: Sequence[str] = KDE_STATS_FIELDS) -> dict:
+    """a downloaded stats block of svmc_kde_gaussian (or, with KDE_WEIGHTED_STATS_FIELDS, of svmc_kde_gaussian_weighted) as a dict
+    (the counts as ints), with gaussian_kde's refusals: ValueError for fewer than two kept samples, LinAlgError for a variance
+    that is not positive and finite"""
+    stats = {k: (int(v) if k.startswith("n_") and np.isfinite(v) else float(v)) for k, v in zip(fields, block)}
     if not stats["n_kept"] >= 2:
         raise ValueError(f"kernel density estimate: {stats['n_kept']} samples kept, at least two are needed")
     if not (np.isfinite(stats["var"]) and stats["var"] > 0.0):
         raise np.linalg.LinAlgError(f"kernel density estimate: the variance of the kept samples is {stats['var']}")
     return stats
+
+
+KDE_WEIGHTED_STATS_DOUBLES = 12                             # SVMC_KDE_WEIGHTED_STATS_DOUBLES of include/svmc.h
+KDE_WEIGHTED_STATS_FIELDS = ("n_kept", "n_nan", "n_low", "n_high", "n_bad_weight", "sum_w", "neff", "mean", "var", "h", "factor",
+                             "sum_w2")
+
+
+def kde_weighted_workspace(n: int) -> Tuple[int, int]:
+    """(workspace bytes, chunk length) of svmc_kde_gaussian_weighted at `n` samples (svmc_kde_weighted_workspace_bytes): the
+    chunk length is kde_workspace's, the workspace is larger (eight rows of moment partials)"""
+    nbytes, chunk = C.c_size_t(0), C.c_size_t(0)
+    _lib.check(_lib.load().svmc_kde_weighted_workspace_bytes(int(n), C.byref(nbytes), C.byref(chunk)))
+    return int(nbytes.value), int(chunk.value)
+
+
+def device_kdes_weighted(value_ptrs: Sequence[int], n: int, grids: Sequence[np.ndarray], divisors: Sequence[float],
+                         weight_ptrs: Optional[Sequence[Optional[int]]] = None, tilt_ptrs: Optional[Sequence[Optional[int]]] = None,
+                         gammas: Optional[Sequence[float]] = None, limit: float = 1e16, bandwidth_factor: Optional[float] = None,
+                         stream=None) -> list:
+    """scipy.stats.gaussian_kde(kept, weights=w_kept)(grid) of several device vectors of `n` doubles
+    (svmc_kde_gaussian_weighted): device_kdes with the weight w = weights exp(gamma tilt) per sample.  weight_ptrs, tilt_ptrs:
+    per vector a device pointer to `n` doubles or None (the factor is then 1; a whole argument of None means None for every
+    vector); gammas: per vector the gamma of its tilt (default 0).  The tilt is NOT divided by the divisor.  Samples with a
+    weight that is NaN, negative or not finite (an overflowed exponential included) are dropped and counted in n_bad_weight.
+    One upload of all the grids, the launches of all the vectors on one stream, ONE download: [(density [len(grid)],
+    {KDE_WEIGHTED_STATS_FIELDS})] per vector.  Raises ValueError with fewer than two kept samples and numpy.linalg.LinAlgError
+    where the weighted variance is not positive and finite -- a single non-zero weight among them.  That is this project's own
+    rule: SciPy 1.15.3 raises ValueError("array must not contain infs or NaNs") in that corner, and parity of exceptions
+    there is not claimed."""
+    lib = _lib.load()
+    grids = [np.ascontiguousarray(g, dtype=np.float64).ravel() for g in grids]
+    sizes = [g.size for g in grids]
+    goff = np.concatenate([[0], np.cumsum(sizes)]).astype(int)
+    total, n_vec = int(goff[-1]), len(grids)
+    weight_ptrs = [None] * n_vec if weight_ptrs is None else list(weight_ptrs)
+    tilt_ptrs = [None] * n_vec if tilt_ptrs is None else list(tilt_ptrs)
+    gammas = [0.0] * n_vec if gammas is None else [float(g) for g in gammas]
+    if not (len(value_ptrs) == len(divisors) == len(weight_ptrs) == len(tilt_ptrs) == len(gammas) == n_vec):
+        raise ValueError("device_kdes_weighted: one grid, divisor, weights pointer, tilt pointer and gamma per vector")
+    all_grids = np.concatenate(grids) if grids else np.empty(0)
+    ws_bytes = kde_weighted_workspace(n)[0]
+    nst = KDE_WEIGHTED_STATS_DOUBLES
+    # results: the densities of all vectors, then their stats blocks -- one buffer, one download
+    bufs = [DeviceBuffer(max(total, 1)), DeviceBuffer(max(total + nst * n_vec, 1)), DeviceBuffer(max(ws_bytes // 8, 1))]
+    try:
+        _lib.check(lib.svmc_memcpy_h2d(bufs[0].ptr, all_grids.ctypes.data, all_grids.nbytes, stream))
+        for i, (ptr, div) in enumerate(zip(value_ptrs, divisors)):
+            _lib.check(lib.svmc_kde_gaussian_weighted(ptr, weight_ptrs[i] or None, tilt_ptrs[i] or None, gammas[i], int(n), float(div),
+                                                      float(limit), bufs[0].offset(goff[i]), sizes[i], float(bandwidth_factor or 0.0),
+                                                      bufs[1].offset(goff[i]), bufs[1].offset(total + nst * i), bufs[2].ptr,
+                                                      ws_bytes, stream))
+        out = np.empty(total + nst * n_vec)
+        _lib.check(lib.svmc_memcpy_d2h(out.ctypes.data, bufs[1].ptr, out.nbytes, stream))
+        _lib.check(lib.svmc_stream_synchronize(stream))
+    finally:
+        for b in bufs:
+            b.free()
+    return [(out[goff[i]:goff[i + 1]].copy(), kde_stats(out[total + nst * i:total + nst * (i + 1)], KDE_WEIGHTED_STATS_FIELDS))
+            for i in range(n_vec)]
 
 
 def vanilla_prices_from_capped(capped: np.ndarray, forward: float, strikes: np.ndarray, optiontypes: Sequence,

@@ -7,6 +7,7 @@
 //   histogram_uniform_kernel   integer counts of a state vector on equal bins with np.histogram's semantics: per-block counts in
 //                              LDS, one 64-bit integer atomic per non-empty bin and block
 //   kde_* kernels              the Gaussian kernel density estimate of a state vector (row f7; described where they stand)
+//   kde_weighted_* kernels     the same estimate with a weight per sample (row f9; described where they stand)
 //
 // The weights w are the reference's LEGACY pricer weights (:157-171), as mgf_vanilla_slice_kernel forms them: Simpson 1,4,2,...
 // with every odd index 4 (an even-length grid keeps 4 on its last point), or for is_simpson = 0 half the first step on the
@@ -306,6 +307,148 @@ __global__ __launch_bounds__(KDE_BLOCK) void kde_finish_kernel(const double *__r
     density[j] = s / (stats[KDE_N_KEPT] * stats[KDE_H] * 2.5066282746310002);                  // sqrt(2 pi)
 }
 
+// ---- weighted Gaussian kernel density estimate: DESIGN.md row f9 ------------------------------------------------------------
+// scipy.stats.gaussian_kde(kept, weights=w_kept)(points) written out (include/svmc.h states the semantics): row f7's sample and
+// filter; the weight w = weights[i] exp_full(gamma tilt[i]), either factor 1 where its vector is NULL; a sample whose value
+// passes the filter is dropped for its weight, and counted, unless w >= 0 with w and w^2 finite; sw = sum w, sw2 = sum w^2,
+// mean = sum w v / sw, var = sum w (v - mean)^2 / (sw - sw2 / sw) as np.cov(aweights=w, ddof=1), neff = sw^2 / sw2 in Scott's
+// factor, density_j = sum_i w_i exp(-((g_j - v_i) / h)^2 / 2) / (sw h sqrt(2 pi)).
+//
+//   kde_weighted_moments_kernel<1>   per block [kept, NaN, low, high, bad weight, sum w, sum w^2, sum w v]
+//   kde_weighted_moments_kernel<2>   per block sum w (v - mean)^2, mean from the block
+//   kde_weighted_moments_finish_kernel<1, 2>, kde_weighted_gaussian_kernel, kde_weighted_finish_kernel   as their f7 namesakes
+//
+// The siblings of row f7's kernels, which stay as they are: the same grids, chunk length (kde_chunk_length, kde_moment_blocks)
+// and order of every sum, so the bits of a (vector, gamma) pair do not depend on the company it keeps.  A weight is formed once
+// per sample (one or two more 8-byte loads, with a tilt one more exp_full) and multiplies the sample's KDE_TILE exponentials.
+// With both vectors NULL w is the literal 1.0 and every product with it is exact: sum w = sum w^2 = n_kept, sum w v = sum v,
+// sw - sw2 / sw = n_kept - 1 and neff = sw (sw / sw2) = n_kept, so the density and the stats EQUAL svmc_kde_gaussian's.
+constexpr int KDE_WEIGHTED_ROWS = 8;
+constexpr int KDE_WEIGHTED_MOMENT_DOUBLES = KDE_WEIGHTED_ROWS * KDE_MOMENT_BLOCKS;
+enum { KDW_N_KEPT = 0, KDW_N_NAN, KDW_N_LOW, KDW_N_HIGH, KDW_N_BAD_WEIGHT, KDW_SUM_W, KDW_NEFF, KDW_MEAN, KDW_VAR, KDW_H,
+       KDW_FACTOR, KDW_SUM_W2 };
+static_assert(KDW_SUM_W2 + 1 == SVMC_KDE_WEIGHTED_STATS_DOUBLES, "weighted stats block layout");
+
+// w_i; NaN, negative and overflowed weights come out as they are and fail kde_weight_kept
+__device__ __forceinline__ double kde_weight(const double *__restrict__ weights, const double *__restrict__ tilt, double gamma, size_t p)
+{
+    double w = weights ? weights[p] : 1.0;
+    if (tilt) w *= exp_full(gamma * tilt[p]);
+    return w;
+}
+
+__device__ __forceinline__ bool kde_weight_kept(double w) { return w >= 0.0 && w * w < __builtin_huge_val(); }     // w^2 finite: so is w
+
+template <int PASS>
+__global__ __launch_bounds__(KDE_BLOCK) void kde_weighted_moments_kernel(const double *__restrict__ a, const double *__restrict__ weights,
+                                                                         const double *__restrict__ tilt, double gamma, size_t n,
+                                                                         double divisor, double limit, const double *__restrict__ stats,
+                                                                         double *__restrict__ partials)
+{
+    constexpr int NV = (PASS == 1) ? KDE_WEIGHTED_ROWS : 1;
+    __shared__ double lds[NV][4];
+    const double mean = (PASS == 2) ? stats[KDW_MEAN] : 0.0;
+    double acc[NV] = {};
+    for (size_t p = static_cast<size_t>(blockIdx.x) * KDE_BLOCK + threadIdx.x; p < n; p += static_cast<size_t>(gridDim.x) * KDE_BLOCK) {
+        const double v = a[p] / divisor;
+        const double w = kde_weight(weights, tilt, gamma, p);
+        const bool is_nan = v != v, high = v > limit, low = v < -limit;
+        const bool passed = !(is_nan || high || low);
+        const bool kept = passed && kde_weight_kept(w);
+        if (PASS == 1) {
+            acc[0] += kept ? 1.0 : 0.0;
+            acc[1] += is_nan ? 1.0 : 0.0;
+            acc[2] += low ? 1.0 : 0.0;
+            acc[3] += high ? 1.0 : 0.0;
+            acc[4] += (passed && !kept) ? 1.0 : 0.0;
+            acc[5] += kept ? w : 0.0;
+            acc[6] += kept ? w * w : 0.0;
+            acc[7] += kept ? w * v : 0.0;
+        } else {
+            const double d = v - mean;
+            acc[0] += kept ? w * (d * d) : 0.0;
+        }
+    }
+    block_sum_rows<NV>(acc, lds);
+    if (threadIdx.x < NV) partials[threadIdx.x * gridDim.x + blockIdx.x] = rows_total(lds, threadIdx.x);
+}
+
+template <int PASS>
+__global__ __launch_bounds__(KDE_BLOCK) void kde_weighted_moments_finish_kernel(const double *__restrict__ partials, int n_blocks,
+                                                                                double factor, double *__restrict__ stats)
+{
+    constexpr int NV = (PASS == 1) ? KDE_WEIGHTED_ROWS : 1;
+    __shared__ double lds[NV][4];
+    double v[NV];
+#pragma unroll
+    for (int k = 0; k < NV; ++k) v[k] = (static_cast<int>(threadIdx.x) < n_blocks) ? partials[k * n_blocks + threadIdx.x] : 0.0;
+    block_sum_rows<NV>(v, lds);
+    if (threadIdx.x != 0) return;
+    if (PASS == 1) {
+        const double sw = rows_total(lds, 5), sw2 = rows_total(lds, 6);
+        stats[KDW_N_KEPT] = rows_total(lds, 0);
+        stats[KDW_N_NAN] = rows_total(lds, 1);
+        stats[KDW_N_LOW] = rows_total(lds, 2);
+        stats[KDW_N_HIGH] = rows_total(lds, 3);
+        stats[KDW_N_BAD_WEIGHT] = rows_total(lds, 4);
+        stats[KDW_SUM_W] = sw;
+        stats[KDW_SUM_W2] = sw2;
+        stats[KDW_NEFF] = sw * (sw / sw2);                                    // sw^2 / sw2; at unit weights n (n / n), exact for any n
+        stats[KDW_MEAN] = rows_total(lds, 7) / sw;
+    } else {
+        const double sw = stats[KDW_SUM_W], sw2 = stats[KDW_SUM_W2];
+        const double var = rows_total(lds, 0) / (sw - sw2 / sw);              // np.cov(aweights=w, ddof=1)
+        const double f = (factor > 0.0) ? factor : pow(stats[KDW_NEFF], -0.2);
+        stats[KDW_VAR] = var;
+        stats[KDW_H] = sqrt(var) * f;
+        stats[KDW_FACTOR] = f;
+    }
+}
+
+__global__ __launch_bounds__(KDE_BLOCK) void kde_weighted_gaussian_kernel(const double *__restrict__ a, const double *__restrict__ weights,
+                                                                          const double *__restrict__ tilt, double gamma, size_t n,
+                                                                          size_t chunk_len, double divisor, double limit,
+                                                                          const double *__restrict__ points, int m,
+                                                                          const double *__restrict__ stats, double *__restrict__ partials)
+{
+    __shared__ double lds[KDE_TILE][4];
+    const int j0 = blockIdx.x * KDE_TILE;
+    double g[KDE_TILE], acc[KDE_TILE];
+#pragma unroll
+    for (int j = 0; j < KDE_TILE; ++j) {
+        g[j] = points[(j0 + j < m) ? j0 + j : m - 1];                 // the last tile repeats the last point: read in bounds, not stored
+        acc[j] = 0.0;
+    }
+    const double inv_h = 1.0 / stats[KDW_H];
+    const size_t begin = static_cast<size_t>(blockIdx.y) * chunk_len;
+    const size_t end = (begin + chunk_len < n) ? begin + chunk_len : n;
+    for (size_t p = begin + threadIdx.x; p < end; p += KDE_BLOCK) {
+        const double v = a[p] / divisor;
+        const double w = kde_weight(weights, tilt, gamma, p);
+        const bool kept = (v == v) && !(v > limit) && !(v < -limit) && kde_weight_kept(w);
+#pragma unroll
+        for (int j = 0; j < KDE_TILE; ++j) {
+            const double d = (g[j] - v) * inv_h;
+            const double e = exp_full((-0.5 * d) * d);                // <= 0: +0 below -746
+            acc[j] += kept ? w * e : 0.0;
+        }
+    }
+    block_sum_rows<KDE_TILE>(acc, lds);
+    if (threadIdx.x < KDE_TILE && j0 + static_cast<int>(threadIdx.x) < m)
+        partials[static_cast<size_t>(blockIdx.y) * m + j0 + threadIdx.x] = rows_total(lds, threadIdx.x);
+}
+
+__global__ __launch_bounds__(KDE_BLOCK) void kde_weighted_finish_kernel(const double *__restrict__ partials, int n_chunks, int m,
+                                                                        const double *__restrict__ stats, double *__restrict__ density)
+{
+    const int j = blockIdx.x * KDE_BLOCK + threadIdx.x;
+    if (j >= m) return;
+    double s = 0.0;
+#pragma unroll 16
+    for (int c = 0; c < n_chunks; ++c) s += partials[static_cast<size_t>(c) * m + j];
+    density[j] = s / (stats[KDW_SUM_W] * stats[KDW_H] * 2.5066282746310002);                   // sqrt(2 pi)
+}
+
 }  // namespace svmc
 
 using namespace svmc;
@@ -419,6 +562,50 @@ int svmc_kde_gaussian(const double *values, size_t n, double divisor, double lim
     hipLaunchKernelGGL(kde_finish_kernel, dim3((n_points + KDE_BLOCK - 1) / KDE_BLOCK), dim3(KDE_BLOCK), 0, s, partials,
                        static_cast<int>(n_chunks), n_points, stats, density);
     return check_launch("svmc_kde_gaussian");
+}
+
+int svmc_kde_weighted_workspace_bytes(size_t n, size_t *bytes, size_t *chunk_length)
+{
+    SVMC_REQUIRE(bytes, "svmc_kde_weighted_workspace_bytes: null pointer");
+    SVMC_REQUIRE(n >= 1 && n < (static_cast<size_t>(1) << 40), "svmc_kde_weighted_workspace_bytes: n must be in 1 .. 2^40 - 1");
+    const size_t len = kde_chunk_length(n), n_chunks = (n + len - 1) / len;
+    *bytes = sizeof(double) * (KDE_WEIGHTED_MOMENT_DOUBLES + n_chunks * SVMC_KDE_MAX_POINTS);
+    if (chunk_length) *chunk_length = len;
+    return SVMC_OK;
+}
+
+int svmc_kde_gaussian_weighted(const double *values, const double *weights, const double *tilt, double gamma, size_t n,
+                               double divisor, double limit, const double *points, int n_points, double bandwidth_factor,
+                               double *density, double *stats, void *workspace, size_t workspace_bytes, svmc_stream_t stream)
+{
+    SVMC_REQUIRE(values && points && density && stats && workspace, "svmc_kde_gaussian_weighted: null pointer");
+    SVMC_REQUIRE(n >= 1 && n < (static_cast<size_t>(1) << 40), "svmc_kde_gaussian_weighted: n must be in 1 .. 2^40 - 1");
+    SVMC_REQUIRE(n_points >= 1, "svmc_kde_gaussian_weighted: n_points must be at least 1");
+    SVMC_REQUIRE(n_points <= SVMC_KDE_MAX_POINTS, "svmc_kde_gaussian_weighted: n_points above SVMC_KDE_MAX_POINTS");
+    SVMC_REQUIRE(divisor > 0.0 && divisor < HUGE_VAL, "svmc_kde_gaussian_weighted: divisor must be positive and finite");
+    SVMC_REQUIRE(limit > 0.0 && limit < HUGE_VAL, "svmc_kde_gaussian_weighted: limit must be positive and finite");
+    SVMC_REQUIRE(bandwidth_factor == bandwidth_factor && bandwidth_factor < HUGE_VAL,
+                 "svmc_kde_gaussian_weighted: bandwidth factor must be finite");
+    SVMC_REQUIRE(gamma > -HUGE_VAL && gamma < HUGE_VAL, "svmc_kde_gaussian_weighted: gamma must be finite");
+    const size_t len = kde_chunk_length(n), n_chunks = (n + len - 1) / len;
+    if (workspace_bytes < sizeof(double) * (KDE_WEIGHTED_MOMENT_DOUBLES + n_chunks * static_cast<size_t>(n_points)))
+        return fail(SVMC_ERR_WORKSPACE, "svmc_kde_gaussian_weighted: workspace too small (svmc_kde_weighted_workspace_bytes)");
+    double *moment_partials = static_cast<double *>(workspace), *partials = moment_partials + KDE_WEIGHTED_MOMENT_DOUBLES;
+    const unsigned mb = kde_moment_blocks(n);
+    hipStream_t s = as_stream(stream);
+    hipLaunchKernelGGL(kde_weighted_moments_kernel<1>, dim3(mb), dim3(KDE_BLOCK), 0, s, values, weights, tilt, gamma, n, divisor, limit,
+                       stats, moment_partials);
+    hipLaunchKernelGGL(kde_weighted_moments_finish_kernel<1>, dim3(1), dim3(KDE_BLOCK), 0, s, moment_partials, static_cast<int>(mb),
+                       bandwidth_factor, stats);
+    hipLaunchKernelGGL(kde_weighted_moments_kernel<2>, dim3(mb), dim3(KDE_BLOCK), 0, s, values, weights, tilt, gamma, n, divisor, limit,
+                       stats, moment_partials);
+    hipLaunchKernelGGL(kde_weighted_moments_finish_kernel<2>, dim3(1), dim3(KDE_BLOCK), 0, s, moment_partials, static_cast<int>(mb),
+                       bandwidth_factor, stats);
+    hipLaunchKernelGGL(kde_weighted_gaussian_kernel, dim3((n_points + KDE_TILE - 1) / KDE_TILE, static_cast<unsigned>(n_chunks)),
+                       dim3(KDE_BLOCK), 0, s, values, weights, tilt, gamma, n, len, divisor, limit, points, n_points, stats, partials);
+    hipLaunchKernelGGL(kde_weighted_finish_kernel, dim3((n_points + KDE_BLOCK - 1) / KDE_BLOCK), dim3(KDE_BLOCK), 0, s, partials,
+                       static_cast<int>(n_chunks), n_points, stats, density);
+    return check_launch("svmc_kde_gaussian_weighted");
 }
 
 }  // extern "C"

@@ -14,7 +14,7 @@ Calibration (HawkesJDPricer.calibrate_model_params_to_chain; :230-302): SLSQP on
 parameters, each objective evaluation one Fourier chain pricing on the device.  The forward-difference gradient SLSQP needs at
 an iterate (the base point and 8 bumped vectors) is priced in one batch of launches per expiry (hawkesjd_chain_pricer_batch,
 csrc/svmc_hawkes.hip's hawkes_mgf_grid_batch_kernel), bit-identical to one pricing per vector.
-Risk-premia (Esscher-type) kernel (hawkesjd_forwards_under_risk_kernel, hawkesjd_chain_pricer_with_risk_premia,
+Risk-premia (Esscher-type) kernel (hawkesjd_forwards_under_risk_kernel, hawkesjd_pdf_under_risk_kernel, hawkesjd_chain_pricer_with_risk_premia,
 HawkesJDPricer.calibrate_risk_premia_gamma_to_chain; :304-357, :420-515): the normalizers and gamma forwards of every expiry in
 one launch (hawkes_risk_forwards_kernel: the coefficient ODEs from zero over each whole ttm at phi = -gamma and -gamma - 1),
 the chained coefficient ODEs on the grid of real part -0.5 - gamma, and per expiry one inversion launch that finishes the
@@ -322,7 +322,9 @@ class HawkesJDPricer(ModelPricer):
     def get_log_return_mc_pdf_device(self, ttm: float, params: HawkesJDParams, x_grid: np.ndarray, nb_path: int = 100000,
                                      **kwargs) -> np.ndarray:
         """get_log_return_mc_pdf (LOG_RETURN, the model's one priced variable) with the state left on the device and the
-        kernel estimate summed there; seed= / nb_steps_per_year= as simulate_terminal_values"""
+        kernel estimate summed there; seed= / nb_steps_per_year= as simulate_terminal_values.  params.risk_premia_gamma is
+        IGNORED, as it always was here; only the explicit keyword risk_premia_gamma= (a float or up to 16 gammas) weights the
+        estimate by exp(gamma x) -> [n_gammas][n_grid]; return_stats= as engine_log_return_mc_pdf"""
         from .logsv_pricer import engine_log_return_mc_pdf, refuse_sharded_kde
         refuse_sharded_kde("get_log_return_mc_pdf_device", kwargs)
         p = params.to_dict()
@@ -332,7 +334,7 @@ class HawkesJDPricer(ModelPricer):
                                           lambda_m0=lambda_m * np.ones(nb_path), nb_path=nb_path, **p,
                                           nb_steps_per_year=kwargs.get("nb_steps_per_year", NB_STEPS_PER_YEAR),
                                           seed=kwargs.get("seed"))
-        return engine_log_return_mc_pdf(eng, x_grid)
+        return engine_log_return_mc_pdf(eng, x_grid, kwargs.get("risk_premia_gamma"), kwargs.get("return_stats", False))
 
 
 # ---- the calibration's codec (reference :246-290): the optimizer's 8-vector <-> HawkesJDParams --------------------------------
@@ -495,6 +497,26 @@ def hawkesjd_forwards_under_risk_kernel(model_params: HawkesJDParams, risk_premi
     normalizers.ravel()[:t.size] = out[:t.size]
     gamma_forwards.ravel()[:t.size] = out[t.size:]
     return normalizers, gamma_forwards
+
+
+def hawkesjd_pdf_under_risk_kernel(model_params: HawkesJDParams, risk_premia_gamma: float, ttm: float, x_grid: np.ndarray,
+                                   vol_scaler: float = None, ode_rtol: Optional[float] = None, ode_atol: Optional[float] = None
+                                   ) -> np.ndarray:
+    """the model density of the log-return under the risk-premia kernel on `x_grid`, as bin masses: exp(gamma x) p(x) normalizer,
+    p the bin masses pdf_with_mgf_grid gives from the Hawkes log-MGF on the transform grid of hawkesjd_chain_pricer
+    (compute_hawkes_a_mgf_grid over [0, ttm]) and normalizer = 1 / E[exp(gamma x)] from hawkesjd_forwards_under_risk_kernel.
+    Host composition of existing launches; the Fourier counterpart of get_log_return_mc_pdf_device(risk_premia_gamma=).  Not in
+    the reference API."""
+    x_grid = np.asarray(x_grid, dtype=np.float64)
+    if vol_scaler is None:
+        vol_scaler = set_vol_scaler(sigma0=model_params.sigma, ttm=ttm)
+    phi_grid = mgfp.get_transform_var_grid(variable_type=VariableType.LOG_RETURN, max_phi=MAX_PHI, vol_scaler=vol_scaler)[0]
+    log_mgf = compute_hawkes_a_mgf_grid(ttm=ttm, phi_grid=phi_grid, model_params=model_params, ode_rtol=ode_rtol,
+                                        ode_atol=ode_atol)[1]
+    pdf = mgfp.pdf_with_mgf_grid(log_mgf_grid=log_mgf, transform_var_grid=phi_grid, space_grid=x_grid)
+    normalizers, _ = hawkesjd_forwards_under_risk_kernel(model_params, risk_premia_gamma, np.array([float(ttm)]), np.array([1.0]),
+                                                         ode_rtol=ode_rtol, ode_atol=ode_atol)
+    return np.exp(float(risk_premia_gamma) * x_grid) * pdf * normalizers[0]
 
 
 def hawkesjd_chain_pricer_with_risk_premia(model_params: HawkesJDParams, ttms: np.ndarray, forwards: np.ndarray,

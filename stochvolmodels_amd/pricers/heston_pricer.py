@@ -142,22 +142,20 @@ class HestonPricer(ModelPricer):
     def terminal_value_kdes(self, params: HestonParams, space_grids: dict, ttm: float = 1.0, nb_path: int = 100000, **kwargs):
         """simulate_terminal_values followed by scipy.stats.gaussian_kde of x, qvar / ttm and the VARIANCE (keyed
         VariableType.SIGMA) on the given space grids, summed on the device -- LogSVPricer.terminal_value_kdes for this model.
-        seed= / scheme= as simulate_terminal_values; bandwidth_factor= and return_stats= as there."""
-        from .logsv_pricer import engine_state_kdes, refuse_sharded_kde
+        seed= / scheme= as simulate_terminal_values; bandwidth_factor=, return_stats= and risk_premia_gamma= as there."""
+        from .logsv_pricer import engine_state_kdes, kde_keywords, refuse_sharded_kde, split_kde_results
         refuse_sharded_kde("terminal_value_kdes", kwargs)
         eng = self._simulate_on_engine(params, ttm, nb_path, kwargs.get("scheme", "euler"), kwargs.get("seed"))
-        out = engine_state_kdes(eng, space_grids, ttm, bandwidth_factor=kwargs.get("bandwidth_factor"))
-        densities = {k: d for k, (d, _) in out.items()}
-        return (densities, {k: s for k, (_, s) in out.items()}) if kwargs.get("return_stats", False) else densities
+        return split_kde_results(engine_state_kdes(eng, space_grids, ttm, **kde_keywords(kwargs)), kwargs.get("return_stats", False))
 
     def get_log_return_mc_pdf_device(self, ttm: float, params: HestonParams, x_grid: np.ndarray, nb_path: int = 100000,
                                      **kwargs) -> np.ndarray:
         """get_log_return_mc_pdf with the state left on the device and the kernel estimate summed there (seed= / scheme= as
-        simulate_terminal_values)"""
+        simulate_terminal_values; risk_premia_gamma= and return_stats= as engine_log_return_mc_pdf)"""
         from .logsv_pricer import engine_log_return_mc_pdf, refuse_sharded_kde
         refuse_sharded_kde("get_log_return_mc_pdf_device", kwargs)
         eng = self._simulate_on_engine(params, ttm, nb_path, kwargs.get("scheme", "euler"), kwargs.get("seed"))
-        return engine_log_return_mc_pdf(eng, x_grid)
+        return engine_log_return_mc_pdf(eng, x_grid, kwargs.get("risk_premia_gamma"), kwargs.get("return_stats", False))
 
 
 def compute_heston_mgf_grid(v0: float, theta: float, kappa: float, volvol: float, rho: float, ttm: float,

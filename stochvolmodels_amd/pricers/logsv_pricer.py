@@ -24,7 +24,7 @@ from ..mc_chain import price_chain_on_engine, variable_type_code
 from ..utils.calibration import ImpliedVolObjective, chain_calibration_weights, minimize_slsqp
 from ..utils.config import VariableType
 from ..utils.funcs import histogram_series, next_rng_call, set_time_grid, time_grid_steps, timer
-from ..analytic import AnalyticGrid, chain_prices_from_sums, chain_sums, device_histograms, device_kdes, histogram_edges
+from ..analytic import AnalyticGrid, chain_prices_from_sums, chain_sums, device_histograms, device_kdes, device_kdes_weighted, histogram_edges
 from ..utils import mgf_pricer as mgfp
 from .logsv.affine_expansion import ExpansionOrder, _order_code, get_init_conditions_a, note_integrator_flags
 from .logsv.logsv_params import LogSvParams
@@ -443,24 +443,23 @@ class LogSVPricer(ModelPricer):
         """simulate_terminal_values followed by scipy.stats.gaussian_kde of x, qvar / ttm and sigma on their space grids, with the
         n_path x n_grid exponentials summed on the device: {VariableType: density per unit of the variable}.  space_grids, n,
         n_stdevs and seed= as terminal_value_histograms; bandwidth_factor= a positive factor in place of Scott's;
-        return_stats=True also returns {VariableType: {n_kept, n_nan, n_low, n_high, mean, var, h, factor}}.  Not in the
-        reference API."""
+        return_stats=True also returns {VariableType: {n_kept, n_nan, n_low, n_high, mean, var, h, factor}}.
+        risk_premia_gamma= a float or up to 16 gammas: every variable weighted by exp(gamma x) (engine_state_kdes), the densities
+        [n_gammas][n_grid] and the stats a list per gamma.  Not in the reference API."""
         refuse_sharded_kde("terminal_value_kdes", kwargs)
         if space_grids is None:
             space_grids = {vt: params.get_variable_space_grid(variable_type=vt, ttm=ttm, n=n, n_stdevs=n_stdevs)
                            for vt in (VariableType.LOG_RETURN, VariableType.Q_VAR, VariableType.SIGMA)}
         eng = self._simulate_on_engine(params, ttm, nb_path, is_spot_measure, kwargs.get("seed"))
-        out = engine_state_kdes(eng, space_grids, ttm, bandwidth_factor=kwargs.get("bandwidth_factor"))
-        densities = {k: d for k, (d, _) in out.items()}
-        return (densities, {k: s for k, (_, s) in out.items()}) if kwargs.get("return_stats", False) else densities
+        return split_kde_results(engine_state_kdes(eng, space_grids, ttm, **kde_keywords(kwargs)), kwargs.get("return_stats", False))
 
     def get_log_return_mc_pdf_device(self, ttm: float, params: LogSvParams, x_grid: np.ndarray, nb_path: int = 100000,
                                      **kwargs) -> np.ndarray:
         """get_log_return_mc_pdf with the state left on the device and the kernel estimate summed there (seed= and
-        is_spot_measure= as simulate_terminal_values)"""
+        is_spot_measure= as simulate_terminal_values; risk_premia_gamma= and return_stats= as engine_log_return_mc_pdf)"""
         refuse_sharded_kde("get_log_return_mc_pdf_device", kwargs)
         eng = self._simulate_on_engine(params, ttm, nb_path, kwargs.get("is_spot_measure", True), kwargs.get("seed"))
-        return engine_log_return_mc_pdf(eng, x_grid)
+        return engine_log_return_mc_pdf(eng, x_grid, kwargs.get("risk_premia_gamma"), kwargs.get("return_stats", False))
 
 
 def engine_state_histograms(eng, space_grids: dict, ttm: float) -> dict:
@@ -477,18 +476,51 @@ def engine_state_histograms(eng, space_grids: dict, ttm: float) -> dict:
     return {k: histogram_series(cnt, e, g[0], eng.n_path) for k, g, e, cnt in zip(keys, grids, edges, counts)}
 
 
-def engine_state_kdes(eng, space_grids: dict, ttm: float, limit: float = 1e16, bandwidth_factor: Optional[float] = None) -> dict:
+MAX_KDE_GAMMAS = 16
+
+
+def engine_state_kdes(eng, space_grids: dict, ttm: float, limit: float = 1e16, bandwidth_factor: Optional[float] = None,
+                      risk_premia_gamma=None) -> dict:
     """scipy.stats.gaussian_kde of the engine's resident state on the given grids, summed on the device (svmc_kde_gaussian), with
     engine_state_histograms' sources: LOG_RETURN -> x, Q_VAR -> qvar / ttm, SIGMA -> the second state vector.
-    {key: (density per unit of the variable, stats)}"""
+    {key: (density per unit of the variable, stats)}.  risk_premia_gamma: None, or a float or a sequence of up to 16 gammas;
+    then every variable is weighted by exp(gamma x) of the resident (undivided) x (svmc_kde_gaussian_weighted, one call per
+    variable and gamma on the engine's stream, one upload and one download) and the result gains a leading gamma axis, also for
+    a float: {key: (density [n_gammas][n_grid], [stats per gamma])}"""
     src = {1: (eng.x.ptr, 1.0), 2: (eng.qvar.ptr, float(ttm)), 3: (eng.vol.ptr, 1.0)}
     keys = list(space_grids)
     codes = [int(getattr(k, "value", k)) for k in keys]
     if any(c not in src for c in codes):
         raise NotImplementedError
-    out = device_kdes([src[c][0] for c in codes], eng.n_path, [space_grids[k] for k in keys], [src[c][1] for c in codes],
-                      limit=limit, bandwidth_factor=bandwidth_factor, stream=eng.stream)
-    return dict(zip(keys, out))
+    if risk_premia_gamma is None:
+        out = device_kdes([src[c][0] for c in codes], eng.n_path, [space_grids[k] for k in keys], [src[c][1] for c in codes],
+                          limit=limit, bandwidth_factor=bandwidth_factor, stream=eng.stream)
+        return dict(zip(keys, out))
+    gammas = [float(g) for g in np.atleast_1d(np.asarray(risk_premia_gamma, dtype=np.float64)).ravel()]
+    if not 1 <= len(gammas) <= MAX_KDE_GAMMAS:
+        raise ValueError(f"risk_premia_gamma: between 1 and {MAX_KDE_GAMMAS} gammas, got {len(gammas)}")
+    n_g, n_k = len(gammas), len(keys)
+    out = device_kdes_weighted([src[c][0] for c in codes] * n_g, eng.n_path, [space_grids[k] for k in keys] * n_g,
+                               [src[c][1] for c in codes] * n_g, tilt_ptrs=[eng.x.ptr] * (n_g * n_k),
+                               gammas=[g for g in gammas for _ in keys], limit=limit, bandwidth_factor=bandwidth_factor,
+                               stream=eng.stream)
+    return {k: (np.stack([out[g * n_k + i][0] for g in range(n_g)]), [out[g * n_k + i][1] for g in range(n_g)])
+            for i, k in enumerate(keys)}
+
+
+def kde_keywords(kwargs: dict) -> dict:
+    """the keywords a pricer's terminal_value_kdes hands on to engine_state_kdes; risk_premia_gamma only where it is given, so
+    that a call without it is the call it was"""
+    kw = {"bandwidth_factor": kwargs.get("bandwidth_factor")}
+    if kwargs.get("risk_premia_gamma") is not None:
+        kw["risk_premia_gamma"] = kwargs["risk_premia_gamma"]
+    return kw
+
+
+def split_kde_results(out: dict, return_stats: bool):
+    """engine_state_kdes' {key: (density, stats)} as {key: density}, or with return_stats ({key: density}, {key: stats})"""
+    densities = {k: d for k, (d, _) in out.items()}
+    return (densities, {k: s for k, (_, s) in out.items()}) if return_stats else densities
 
 
 def refuse_sharded_kde(who: str, kwargs: dict) -> None:
@@ -499,12 +531,21 @@ def refuse_sharded_kde(who: str, kwargs: dict) -> None:
         raise NotImplementedError(f"{who}: the kernel density estimate is not sharded over ranks or devices")
 
 
-def engine_log_return_mc_pdf(eng, x_grid: np.ndarray) -> np.ndarray:
+def engine_log_return_mc_pdf(eng, x_grid: np.ndarray, risk_premia_gamma=None, return_stats: bool = False):
     """ModelPricer.get_log_return_mc_pdf's arithmetic on the engine's resident x: the reference's line about the dropped paths
-    from the device counts, then density / nansum(density)"""
-    density, stats = engine_state_kdes(eng, {1: np.asarray(x_grid, dtype=np.float64)}, 1.0)[1]
-    print(f"in mc: num -inf = {stats['n_low']}, num +inf = {stats['n_high']}, num nans = {stats['n_nan']}")
-    return density / np.nansum(density)
+    from the device counts, then density / nansum(density).  risk_premia_gamma: None, or a float or up to 16 gammas; then the
+    estimate is weighted by exp(gamma x) (engine_state_kdes), the line is printed once (the counts of x do not depend on gamma)
+    and every gamma's row is normalised on its own: [n_gammas][n_grid].  return_stats=True -> (pdf, stats), the stats a dict, or
+    a list of dicts per gamma"""
+    grids = {1: np.asarray(x_grid, dtype=np.float64)}
+    if risk_premia_gamma is None:
+        density, stats = engine_state_kdes(eng, grids, 1.0)[1]
+        first, total = stats, np.nansum(density)
+    else:
+        density, stats = engine_state_kdes(eng, grids, 1.0, risk_premia_gamma=risk_premia_gamma)[1]
+        first, total = stats[0], np.nansum(density, axis=1, keepdims=True)
+    print(f"in mc: num -inf = {first['n_low']}, num +inf = {first['n_high']}, num nans = {first['n_nan']}")
+    return (density / total, stats) if return_stats else density / total
 
 
 def set_vol_scaler(sigma0: float, ttm: float) -> float:
