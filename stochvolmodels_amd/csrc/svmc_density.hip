@@ -111,7 +111,12 @@ __global__ __launch_bounds__(DB) void mgf_digital_slice_kernel(const cd *__restr
             p = cd{(a * rat) * scl, -a * scl};
         }
         if (negative_contour) p = -p;                                                           // calls :244, puts :247
-        const cd e = cexp_(log_mgf[j] - x * b);
+        const cd arg = log_mgf[j] - x * b;
+        cd e = cexp_(arg);
+        // exp(r + 0i) = exp(r) + 0i as C99's cexp and NumPy's: at r = +inf (a log E of +inf at the money, x = 0, or on the
+        // grid's first point, Im phi = 0) inf * sin(0) is NaN, and with the complex p the whole term would be dropped where the
+        // reference keeps Re[p] inf.  For a finite r the product is this signed zero already: no other term changes a bit.
+        if (arg.im == 0.0) e.im = arg.im;
         const double term = p.re * e.re - p.im * e.im;
         if (term == term) s += term;                                                            // nansum :253
     }

@@ -10,7 +10,13 @@ The analytic route's device kernels against independent high-precision truth:
   * the single C entry points svmc_logsv_mgf_grid / svmc_mgf_vanilla_slice against their batch forms at one set, bit for bit;
   * the inversion kernels (mgf_vanilla_slice_kernel, mgf_qvar_slice_kernel, mgf_gamma_slice_kernel) against the same
     Simpson-weighted sum evaluated in mpmath from the same doubles, at grid lengths and strike counts around the kernels'
-    256-thread and 32-strike boundaries, and the nansum contract (NaN terms dropped, inf kept, a -inf log E a zero term).
+    256-thread and 32-strike boundaries, and the nansum contract (NaN terms dropped, inf kept, a -inf log E a zero term);
+  * the density slices (mgf_pdf_slice_kernel, mgf_digital_slice_kernel of csrc/svmc_density.hip) against the sums of the
+    reference's pdf_with_mgf_grid and digital_slice_pricer_with_mgf_grid in mpmath, under the same error model: the
+    256-thread stride loop at 255, 256 and 257 points, both branches of legacy_weight (Simpson, and the local-step weights on
+    a geometrically stretched grid), both arms of the digital kernel's Smith division (|Re phi| >= |Im phi| at the first
+    grid points only), both contours, the 64-set launch boundary of the pdf entry (64, 65 and 129 sets, each bit-equal to its
+    single call), the 32-strike chunks of the digital entry, a negative scale, and the nansum contract of both.
 
 Errors of the ODE are |dev - mp| / max(1, |mp|), the largest over a point's components and log E; every report() line
 prints the measured worst value against its bound.
@@ -279,7 +285,9 @@ def mp_sum(terms):
 
 
 def _term(w, lm, x, z):
-    """(Re[w exp(log E - x z)] in mp, a_j); inf / NaN as IEEE arithmetic gives them (the real part decides)"""
+    """(Re[w exp(log E - x z)] in mp, a_j); inf / NaN as IEEE arithmetic gives them.  At Re log E = +inf the exponential is
+    (inf cos, inf sin) of the phase -- (inf, 0) at a phase of exactly 0, as C99's cexp and NumPy's -- and the real part of the
+    product is Re[w] inf cos - Im[w] inf sin: that infinity, or NaN where the two are infinities of opposite sign"""
     a = abs(lm.real) + abs(lm.imag) + abs(x) * (abs(z.real) + abs(z.imag))
     if math.isnan(lm.real) or math.isnan(lm.imag):
         return mp.nan, a
@@ -287,8 +295,8 @@ def _term(w, lm, x, z):
         return mp.mpf(0), 0.0
     arg = mp.mpc(lm) - mp.mpf(x) * mp.mpc(z)
     if lm.real == math.inf:
-        c = w.real * mp.cos(arg.imag) - w.imag * mp.sin(arg.imag)
-        return (mp.inf if c > 0 else (-mp.inf if c < 0 else mp.nan)), a
+        parts = {mp.sign(v) for v in (w.real * mp.cos(arg.imag), -w.imag * mp.sin(arg.imag))} - {0}
+        return (mp.inf * parts.pop() if len(parts) == 1 else mp.nan), a
     return (w * mp.exp(arg)).real, a
 
 
@@ -481,3 +489,236 @@ def test_gamma_slice_kernel_vs_exact_sum(L, n):
                 assert err <= bound, (n, k, s, i, float(err), float(bound))
                 worst = max(worst, float(err / bound))
     report(f"gamma slice n={n} error / bound", worst, 1.0)
+
+
+# ---- the density slices against the exact sum ----------------------------------------------------------------------------
+# The sums are written from the reference: utils/mgf_pricer.py:375-383 (pdf_with_mgf_grid: dx nansum Re[(dp / pi) exp(z u +
+# log E)], z = (space - shift) / scale) and :244-253 (digital_slice_pricer_with_mgf_grid: nansum Re[-+(dp / pi) / phi
+# exp(-x phi + log E)]), dp the legacy weights of :157-171 -- Simpson's, or 0.5 (p_1 - p_0) on the first point and p_j - p_(j-1)
+# on the others.  The same error model as above, unchanged; the density's final product with dx is one more rounding of the
+# result.
+MAX_PDF_SETS = 64              # csrc/svmc_density.hip
+
+
+def density_grid(n, vol_scaler, spot, seed, is_simpson):
+    """synthetic_grid, its spacing stretched geometrically (the last step e^2 times the first) for the local-step weights"""
+    phi, lm = synthetic_grid(n, vol_scaler, spot=spot, seed=seed)
+    if is_simpson:
+        return phi, lm
+    p = phi.imag[-1] * np.expm1(2.0 * np.linspace(0.0, 1.0, n)) / math.expm1(2.0)
+    rng = np.random.default_rng(seed)
+    lm = -0.5 * (vol_scaler * p) ** 2 * (1 + 0.1 * rng.uniform(size=n)) + 1j * 0.3 * p * rng.uniform(size=n)
+    return phi.real + 1j * p, lm
+
+
+def dp_mp(grid, j, is_simpson):
+    """the legacy weight dp_j in mp from the grid's doubles (the Simpson step h as the double the reference forms)"""
+    n, p = grid.size, grid.imag
+    if is_simpson:
+        return mp.mpf(p[1] - p[0]) / 3 * legacy_weight(j, n)
+    return (mp.mpf(p[1]) - mp.mpf(p[0])) / 2 if j == 0 else mp.mpf(p[j]) - mp.mpf(p[j - 1])
+
+
+def dp_np(grid, is_simpson):
+    p = grid.imag
+    if is_simpson:
+        return (p[1] - p[0]) / 3 * simpson_weights(grid.size)
+    return np.append(0.5 * (p[1] - p[0]), p[1:] - p[:-1])
+
+
+def pdf_ref(u, lm, z, is_simpson):
+    """the sum of :381 at one z (a double, formed as the reference forms it), before the product with dx"""
+    with mp.workdps(50):
+        return mp_sum([_term(mp.mpc(dp_mp(u, j, is_simpson) / mp.pi), lm[j], -z, u[j]) for j in range(u.size)])
+
+
+def pdf_np(u, lm, z, is_simpson):
+    t = (dp_np(u, is_simpson)[None, :] / np.pi * np.exp(z[:, None] * u[None, :] + lm[None, :])).real
+    return t.sum(axis=1), np.abs(t).sum(axis=1)
+
+
+def check_pdf(name, dev, ref, dx, n):
+    """check_sum for dx * sum: the bound scaled by |dx|, plus the product's own rounding"""
+    val, absum, absum_a = ref
+    if mp.isinf(val):
+        assert dev == float(val) * math.copysign(1.0, dx), (name, dev, val)
+        return 0.0
+    with mp.workdps(50):
+        err = abs(mp.mpf(dev) - mp.mpf(dx) * val)
+        bound = abs(mp.mpf(dx)) * (EPS * (C_SUM * n * absum + 2 * absum_a) + EPS * abs(val))
+    assert err <= bound, (name, float(err), float(bound))
+    return float(err / bound) if bound > 0 else 0.0
+
+
+def pdf_batch(L, u, lm, space, shifts, scales, is_simpson):
+    """svmc_mgf_pdf_slice_batch on [n_sets][n_grid] grids and [n_sets][n_space] space grids -> [n_sets][n_space]"""
+    u, lm, space = (np.ascontiguousarray(np.atleast_2d(v)) for v in (u, lm, space))
+    shifts, scales = (np.ascontiguousarray(np.atleast_1d(v), dtype=np.float64) for v in (shifts, scales))
+    s, n = u.shape
+    du, dlm, dsp, out = Dev(L, u), Dev(L, lm), Dev(L, space), Dev(L, n_doubles=space.size)
+    _check(L.svmc_mgf_pdf_slice_batch(du.ptr, dlm.ptr, n, s, dsp.ptr, space.shape[1], _pf(shifts), _pf(scales), int(is_simpson),
+                                      out.ptr, None))
+    return out.get(space.shape, np.float64)
+
+
+def pdf_set(n, i, is_simpson, n_space):
+    """set i of a pdf batch: its own grid, space grid, shift and scale (every third scale negative)"""
+    v = (0.16, 0.05, 0.3)[i % 3] * (1.0 + 0.03 * (i // 3))
+    u, lm = density_grid(n, v, spot=bool(i % 2), seed=100 + i, is_simpson=is_simpson)
+    scale = (-1.0 if i % 3 == 1 else 1.0) * v * (1.5 + 0.1 * (i % 5))
+    shift = 0.01 * (i % 7) - 0.02
+    space = shift + abs(scale) * np.linspace(-2.5 + 0.1 * (i % 4), 2.0, n_space)
+    return u, lm, space, shift, scale
+
+
+@pytest.mark.parametrize("is_simpson", [1, 0])
+@pytest.mark.parametrize("n", [3, 4, 255, 256, 257, 1000, 1001])
+def test_pdf_slice_kernel_vs_exact_sum(L, n, is_simpson):
+    """three sets, each its own grid, space grid, shift and scale (one scale negative); 2 and 33 space points"""
+    worst = 0.0
+    for n_space in (2, 33):
+        sets = [pdf_set(n, i, is_simpson, n_space) for i in range(3)]
+        assert any(s[4] < 0 for s in sets)
+        got = pdf_batch(L, *(np.stack([s[k] for s in sets]) for k in range(3)), [s[3] for s in sets], [s[4] for s in sets],
+                        is_simpson)
+        for i, (u, lm, space, shift, scale) in enumerate(sets):
+            z = (space - shift) / scale                                   # :379, in double as the reference
+            dx = space[1] - space[0]
+            val, absum = pdf_np(u, lm, z, is_simpson)
+            np_sum_check(f"pdf n={n} simpson={is_simpson} n_space={n_space} set={i}", got[i], (dx * val, abs(dx) * absum))
+            for k in (0, n_space - 1):
+                worst = max(worst, check_pdf(f"pdf n={n} simpson={is_simpson} n_space={n_space} set={i} point={k}", got[i, k],
+                                             pdf_ref(u, lm, float(z[k]), is_simpson), float(dx), n))
+    report(f"pdf slice n={n} simpson={is_simpson} error / bound", worst, 1.0)
+
+
+@pytest.mark.parametrize("n_sets", [MAX_PDF_SETS, MAX_PDF_SETS + 1, 2 * MAX_PDF_SETS + 1])
+def test_pdf_slice_sets_across_the_launch_boundary(L, n_sets):
+    """64 sets a launch: set s of the batch equals its single call bit for bit; the first and the last set against mp"""
+    n, n_space, worst = 4, 3, 0.0
+    for is_simpson in (1, 0):
+        sets = [pdf_set(n, i, is_simpson, n_space) for i in range(n_sets)]
+        got = pdf_batch(L, *(np.stack([s[k] for s in sets]) for k in range(3)), [s[3] for s in sets], [s[4] for s in sets],
+                        is_simpson)
+        for i, (u, lm, space, shift, scale) in enumerate(sets):
+            np.testing.assert_array_equal(got[i], pdf_batch(L, u, lm, space, shift, scale, is_simpson)[0],
+                                          err_msg=f"{n_sets} sets, set {i}, simpson {is_simpson}")
+        for i in (0, n_sets - 1):
+            u, lm, space, shift, scale = sets[i]
+            z = (space - shift) / scale
+            for k in range(n_space):
+                worst = max(worst, check_pdf(f"pdf {n_sets} sets, set {i}, point {k}", got[i, k],
+                                             pdf_ref(u, lm, float(z[k]), is_simpson), float(space[1] - space[0]), n))
+    report(f"pdf slice, {n_sets} sets, error / bound", worst, 1.0)
+
+
+def digital_ref(phi, lm, x, negative_contour, is_simpson):
+    """the sum of :253 for one x, with the payoff transform of :244 (calls, Re phi < 0) or :247 (puts)"""
+    with mp.workdps(50):
+        sign = -1 if negative_contour else 1
+        return mp_sum([_term(sign * (dp_mp(phi, j, is_simpson) / mp.pi) / mp.mpc(phi[j]), lm[j], x, phi[j])
+                       for j in range(phi.size)])
+
+
+def digital_np(phi, lm, x, negative_contour, is_simpson):
+    pw = (-1.0 if negative_contour else 1.0) * (dp_np(phi, is_simpson) / np.pi) / phi
+    t = (pw[None, :] * np.exp(lm[None, :] - x[:, None] * phi[None, :])).real
+    return t.sum(axis=1), np.abs(t).sum(axis=1)
+
+
+def digital_batch(L, phi, lm, forward, strikes, negative_contour, is_simpson):
+    """svmc_mgf_digital_slice_batch: phi, log E [n_sets][n_grid], the same strikes and forward for every set -> [n_sets][k]"""
+    phi, lm = np.ascontiguousarray(np.atleast_2d(phi)), np.ascontiguousarray(np.atleast_2d(lm))
+    strikes = np.ascontiguousarray(strikes, dtype=np.float64)
+    s, n = phi.shape
+    dphi, dlm, out = Dev(L, phi), Dev(L, lm), Dev(L, n_doubles=s * strikes.size)
+    _check(L.svmc_mgf_digital_slice_batch(dphi.ptr, dlm.ptr, n, s, float(forward), _pf(strikes), strikes.size,
+                                          int(negative_contour), int(is_simpson), out.ptr, None))
+    return out.get((s, strikes.size), np.float64)
+
+
+@pytest.mark.parametrize("is_simpson", [1, 0])
+@pytest.mark.parametrize("spot", [True, False])
+@pytest.mark.parametrize("n", [3, 4, 255, 256, 257, 1000, 1001])
+def test_digital_slice_kernel_vs_exact_sum(L, n, spot, is_simpson):
+    """three sets on grids of different spacing, Re phi = -0.5 (the calls' contour) or +0.5 (the puts'), Im phi from 0: the
+    first points have |Re phi| >= |Im phi| and the rest do not, so both arms of the Smith division are taken"""
+    grids = [density_grid(n, v, spot, 20 + i, is_simpson) for i, v in enumerate((0.16, 0.05, 0.3))]
+    phi, lm = np.stack([g[0] for g in grids]), np.stack([g[1] for g in grids])
+    first_arm = np.abs(phi.real) >= np.abs(phi.imag)
+    assert np.all(first_arm.any(axis=1)) and np.all((~first_arm).any(axis=1)), "one arm of the Smith division is not taken"
+    negative_contour = bool(np.all(phi.real < 0.0))                       # :242
+    assert negative_contour == spot
+    forward, worst = 1.3, 0.0
+    for k in (1, 32, 33, 65):
+        strikes = forward * np.exp(np.linspace(-0.6, 0.6, k))
+        got = digital_batch(L, phi, lm, forward, strikes, negative_contour, is_simpson)
+        x = np.array([math.log(forward / float(K)) for K in strikes])
+        for s in range(3):
+            name = f"digital n={n} spot={spot} simpson={is_simpson} k={k} set={s}"
+            np_sum_check(name, got[s], digital_np(phi[s], lm[s], x, negative_contour, is_simpson))
+            for i in checked_strikes(k):
+                worst = max(worst, check_sum(f"{name} strike={i}", got[s, i],
+                                             digital_ref(phi[s], lm[s], x[i], negative_contour, is_simpson), n))
+    report(f"digital slice n={n} spot={spot} simpson={is_simpson} error / bound", worst, 1.0)
+
+
+NANSUM_EDITS = {"nan": {5: complex(np.nan, 0.0)}, "neg_inf": {5: complex(-np.inf, 0.0), 200: complex(-np.inf, 0.0)},
+                "pos_inf": {7: complex(np.inf, 0.0)}}
+
+
+@pytest.mark.parametrize("is_simpson", [1, 0])
+def test_pdf_slice_kernel_nansum_contract(L, is_simpson):
+    """NaN terms dropped, +inf kept, a -inf log E a zero term.  z = 0 first: the inf term's phase is exactly 0"""
+    n = 257
+    u, lm = density_grid(n, 0.16, True, 0, is_simpson)
+    shift, scale = 0.05, 0.2
+    space = np.array([shift, shift + 0.07, shift - 0.11])
+    z = (space - shift) / scale
+    assert z[0] == 0.0
+    dx = float(space[1] - space[0])
+    for name, edits in NANSUM_EDITS.items():
+        e = lm.copy()
+        for j, v in edits.items():
+            e[j] = v
+        got = pdf_batch(L, u, e, space, shift, scale, is_simpson)[0]
+        for i in range(space.size):
+            ref = pdf_ref(u, e, float(z[i]), is_simpson)
+            if name == "pos_inf":
+                assert np.isinf(got[i]) and got[i] == float(ref[0]), (i, got[i], ref[0])
+                assert i > 0 or got[i] == np.inf
+            else:
+                assert np.isfinite(got[i]), (name, got[i])
+                check_pdf(f"pdf {name} point {i}", got[i], ref, dx, n)
+
+
+@pytest.mark.parametrize("is_simpson", [1, 0])
+@pytest.mark.parametrize("spot", [True, False])
+def test_digital_slice_kernel_nansum_contract(L, spot, is_simpson):
+    """as above.  The weight p = -+(dp / pi) / phi is complex here: Re p > 0 on both contours, Im p > 0 for the calls (Re phi
+    < 0) and < 0 for the puts.  A +inf log E at point 7 gives Re[p] inf cos(theta) - Im[p] inf sin(theta) with the phase theta
+    = -x Im phi_7, as NumPy's product.  The strikes, in order:
+      strike == forward, x = 0: theta is exactly 0, the exponential is (inf, 0) and the sum +inf (the sign of Re p);
+      theta = -+0.7 and +-2.4: both parts have the same sign, the sum is +inf and -inf;
+      0.8: theta < 0 in the fourth quadrant -- the parts agree for the calls (+inf) and are inf - inf = NaN for the puts, a term
+      that nansum drops: the sum of the other terms"""
+    n = 257
+    phi, lm = density_grid(n, 0.16, spot, 0, is_simpson)
+    forward = 1.0
+    theta = (-0.7, 2.4) if spot else (0.7, -2.4)
+    strikes = np.array([forward] + [forward * math.exp(t / phi[7].imag) for t in theta] + [0.8])
+    x = np.array([math.log(forward / float(K)) for K in strikes])
+    assert x[0] == 0.0
+    pos_inf = (np.inf, np.inf, -np.inf, np.inf if spot else None)
+    for name, edits in NANSUM_EDITS.items():
+        e = lm.copy()
+        for j, v in edits.items():
+            e[j] = v
+        got = digital_batch(L, phi, e, forward, strikes, spot, is_simpson)[0]
+        for i in range(strikes.size):
+            ref = digital_ref(phi, e, float(x[i]), spot, is_simpson)
+            if name == "pos_inf" and pos_inf[i] is not None:
+                assert got[i] == pos_inf[i] and got[i] == float(ref[0]), (i, got[i], ref[0])
+            else:
+                assert np.isfinite(got[i]) and mp.isfinite(ref[0]), (name, i, got[i], ref[0])
+                check_sum(f"digital {name} strike {i}", got[i], ref, n)
