@@ -496,11 +496,44 @@ KDE_TILE, KDE_MAX_POINTS, KDE_STATS_DOUBLES = 8, 4096, 8     # SVMC_KDE_* of inc
 KDE_STATS_FIELDS = ("n_kept", "n_nan", "n_low", "n_high", "mean", "var", "h", "factor")
 
 
+def _kde_workspace(size_fn: str, n: int) -> Tuple[int, int]:
+    nbytes, chunk = C.c_size_t(0), C.c_size_t(0)
+    _lib.check(getattr(_lib.load(), size_fn)(int(n), C.byref(nbytes), C.byref(chunk)))
+    return int(nbytes.value), int(chunk.value)
+
+
 def kde_workspace(n: int) -> Tuple[int, int]:
     """(workspace bytes, chunk length) of svmc_kde_gaussian at `n` samples: both depend on n alone (svmc_kde_workspace_bytes)"""
-    nbytes, chunk = C.c_size_t(0), C.c_size_t(0)
-    _lib.check(_lib.load().svmc_kde_workspace_bytes(int(n), C.byref(nbytes), C.byref(chunk)))
-    return int(nbytes.value), int(chunk.value)
+    return _kde_workspace("svmc_kde_workspace_bytes", n)
+
+
+def _device_kdes(entry: str, size_fn: str, fields: Sequence[str], weight_args, value_ptrs, n, grids, divisors, limit, bandwidth_factor,
+                 stream) -> list:
+    """the body of device_kdes and device_kdes_weighted: one upload of all the grids, per vector one call of the library's
+    `entry` -- weight_args(i) are the arguments it takes between the values and n -- with the workspace of `size_fn`, one
+    download, the slicing into [(density, kde_stats of the `fields`)]"""
+    lib = _lib.load()
+    grids = [np.ascontiguousarray(g, dtype=np.float64).ravel() for g in grids]
+    sizes = [g.size for g in grids]
+    goff = np.concatenate([[0], np.cumsum(sizes)]).astype(int)
+    total, n_vec, nst = int(goff[-1]), len(grids), len(fields)
+    all_grids = np.concatenate(grids) if grids else np.empty(0)
+    ws_bytes = _kde_workspace(size_fn, n)[0]
+    # results: the densities of all vectors, then their stats blocks -- one buffer, one download
+    bufs = [DeviceBuffer(max(total, 1)), DeviceBuffer(max(total + nst * n_vec, 1)), DeviceBuffer(max(ws_bytes // 8, 1))]
+    try:
+        _lib.check(lib.svmc_memcpy_h2d(bufs[0].ptr, all_grids.ctypes.data, all_grids.nbytes, stream))
+        for i, (ptr, div) in enumerate(zip(value_ptrs, divisors)):
+            _lib.check(getattr(lib, entry)(ptr, *weight_args(i), int(n), float(div), float(limit), bufs[0].offset(goff[i]), sizes[i],
+                                           float(bandwidth_factor or 0.0), bufs[1].offset(goff[i]), bufs[1].offset(total + nst * i),
+                                           bufs[2].ptr, ws_bytes, stream))
+        out = np.empty(total + nst * n_vec)
+        _lib.check(lib.svmc_memcpy_d2h(out.ctypes.data, bufs[1].ptr, out.nbytes, stream))
+        _lib.check(lib.svmc_stream_synchronize(stream))
+    finally:
+        for b in bufs:
+            b.free()
+    return [(out[goff[i]:goff[i + 1]].copy(), kde_stats(out[total + nst * i:total + nst * (i + 1)], fields)) for i in range(n_vec)]
 
 
 def device_kdes(value_ptrs: Sequence[int], n: int, grids: Sequence[np.ndarray], divisors: Sequence[float], limit: float = 1e16,
@@ -511,29 +544,8 @@ def device_kdes(value_ptrs: Sequence[int], n: int, grids: Sequence[np.ndarray], 
     densities and stats blocks: [(density [len(grid)], {n_kept, n_nan, n_low, n_high, mean, var, h, factor})] per vector.
     Raises SciPy's two exceptions: ValueError with fewer than two kept samples, numpy.linalg.LinAlgError where their variance
     is not positive and finite."""
-    lib = _lib.load()
-    grids = [np.ascontiguousarray(g, dtype=np.float64).ravel() for g in grids]
-    sizes = [g.size for g in grids]
-    goff = np.concatenate([[0], np.cumsum(sizes)]).astype(int)
-    total, n_vec = int(goff[-1]), len(grids)
-    all_grids = np.concatenate(grids) if grids else np.empty(0)
-    ws_bytes = kde_workspace(n)[0]
-    # results: the densities of all vectors, then their stats blocks -- one buffer, one download
-    bufs = [DeviceBuffer(max(total, 1)), DeviceBuffer(max(total + KDE_STATS_DOUBLES * n_vec, 1)), DeviceBuffer(max(ws_bytes // 8, 1))]
-    try:
-        _lib.check(lib.svmc_memcpy_h2d(bufs[0].ptr, all_grids.ctypes.data, all_grids.nbytes, stream))
-        for i, (ptr, div) in enumerate(zip(value_ptrs, divisors)):
-            _lib.check(lib.svmc_kde_gaussian(ptr, int(n), float(div), float(limit), bufs[0].offset(goff[i]), sizes[i],
-                                             float(bandwidth_factor or 0.0), bufs[1].offset(goff[i]),
-                                             bufs[1].offset(total + KDE_STATS_DOUBLES * i), bufs[2].ptr, ws_bytes, stream))
-        out = np.empty(total + KDE_STATS_DOUBLES * n_vec)
-        _lib.check(lib.svmc_memcpy_d2h(out.ctypes.data, bufs[1].ptr, out.nbytes, stream))
-        _lib.check(lib.svmc_stream_synchronize(stream))
-    finally:
-        for b in bufs:
-            b.free()
-    return [(out[goff[i]:goff[i + 1]].copy(), kde_stats(out[total + KDE_STATS_DOUBLES * i:total + KDE_STATS_DOUBLES * (i + 1)]))
-            for i in range(n_vec)]
+    return _device_kdes("svmc_kde_gaussian", "svmc_kde_workspace_bytes", KDE_STATS_FIELDS, lambda i: (), value_ptrs, n, grids, divisors,
+                        limit, bandwidth_factor, stream)
 
 
 def kde_stats(block: np.ndarray, fields: Sequence[str] = KDE_STATS_FIELDS) -> dict:
@@ -556,9 +568,7 @@ KDE_WEIGHTED_STATS_FIELDS = ("n_kept", "n_nan", "n_low", "n_high", "n_bad_weight
 def kde_weighted_workspace(n: int) -> Tuple[int, int]:
     """(workspace bytes, chunk length) of svmc_kde_gaussian_weighted at `n` samples (svmc_kde_weighted_workspace_bytes): the
     chunk length is kde_workspace's, the workspace is larger (eight rows of moment partials)"""
-    nbytes, chunk = C.c_size_t(0), C.c_size_t(0)
-    _lib.check(_lib.load().svmc_kde_weighted_workspace_bytes(int(n), C.byref(nbytes), C.byref(chunk)))
-    return int(nbytes.value), int(chunk.value)
+    return _kde_workspace("svmc_kde_weighted_workspace_bytes", n)
 
 
 def device_kdes_weighted(value_ptrs: Sequence[int], n: int, grids: Sequence[np.ndarray], divisors: Sequence[float],
@@ -575,36 +585,15 @@ def device_kdes_weighted(value_ptrs: Sequence[int], n: int, grids: Sequence[np.n
     where the weighted variance is not positive and finite -- a single non-zero weight among them.  That is this project's own
     rule: SciPy 1.15.3 raises ValueError("array must not contain infs or NaNs") in that corner, and parity of exceptions
     there is not claimed."""
-    lib = _lib.load()
-    grids = [np.ascontiguousarray(g, dtype=np.float64).ravel() for g in grids]
-    sizes = [g.size for g in grids]
-    goff = np.concatenate([[0], np.cumsum(sizes)]).astype(int)
-    total, n_vec = int(goff[-1]), len(grids)
+    n_vec = len(grids)
     weight_ptrs = [None] * n_vec if weight_ptrs is None else list(weight_ptrs)
     tilt_ptrs = [None] * n_vec if tilt_ptrs is None else list(tilt_ptrs)
     gammas = [0.0] * n_vec if gammas is None else [float(g) for g in gammas]
     if not (len(value_ptrs) == len(divisors) == len(weight_ptrs) == len(tilt_ptrs) == len(gammas) == n_vec):
         raise ValueError("device_kdes_weighted: one grid, divisor, weights pointer, tilt pointer and gamma per vector")
-    all_grids = np.concatenate(grids) if grids else np.empty(0)
-    ws_bytes = kde_weighted_workspace(n)[0]
-    nst = KDE_WEIGHTED_STATS_DOUBLES
-    # results: the densities of all vectors, then their stats blocks -- one buffer, one download
-    bufs = [DeviceBuffer(max(total, 1)), DeviceBuffer(max(total + nst * n_vec, 1)), DeviceBuffer(max(ws_bytes // 8, 1))]
-    try:
-        _lib.check(lib.svmc_memcpy_h2d(bufs[0].ptr, all_grids.ctypes.data, all_grids.nbytes, stream))
-        for i, (ptr, div) in enumerate(zip(value_ptrs, divisors)):
-            _lib.check(lib.svmc_kde_gaussian_weighted(ptr, weight_ptrs[i] or None, tilt_ptrs[i] or None, gammas[i], int(n), float(div),
-                                                      float(limit), bufs[0].offset(goff[i]), sizes[i], float(bandwidth_factor or 0.0),
-                                                      bufs[1].offset(goff[i]), bufs[1].offset(total + nst * i), bufs[2].ptr,
-                                                      ws_bytes, stream))
-        out = np.empty(total + nst * n_vec)
-        _lib.check(lib.svmc_memcpy_d2h(out.ctypes.data, bufs[1].ptr, out.nbytes, stream))
-        _lib.check(lib.svmc_stream_synchronize(stream))
-    finally:
-        for b in bufs:
-            b.free()
-    return [(out[goff[i]:goff[i + 1]].copy(), kde_stats(out[total + nst * i:total + nst * (i + 1)], KDE_WEIGHTED_STATS_FIELDS))
-            for i in range(n_vec)]
+    return _device_kdes("svmc_kde_gaussian_weighted", "svmc_kde_weighted_workspace_bytes", KDE_WEIGHTED_STATS_FIELDS,
+                        lambda i: (weight_ptrs[i] or None, tilt_ptrs[i] or None, gammas[i]), value_ptrs, n, grids, divisors, limit,
+                        bandwidth_factor, stream)
 
 
 def vanilla_prices_from_capped(capped: np.ndarray, forward: float, strikes: np.ndarray, optiontypes: Sequence,

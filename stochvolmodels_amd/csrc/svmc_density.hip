@@ -6,8 +6,8 @@
 //                              (utils/mgf_pricer.py:224-269; the C / P complement and the discount factor are the host's)
 //   histogram_uniform_kernel   integer counts of a state vector on equal bins with np.histogram's semantics: per-block counts in
 //                              LDS, one 64-bit integer atomic per non-empty bin and block
-//   kde_* kernels              the Gaussian kernel density estimate of a state vector (row f7; described where they stand)
-//   kde_weighted_* kernels     the same estimate with a weight per sample (row f9; described where they stand)
+//   kde_* kernels              the Gaussian kernel density estimate of a state vector, plain (row f7) and, as their WEIGHTED
+//                              instantiation, with a weight per sample (row f9); described where they stand
 //
 // The weights w are the reference's LEGACY pricer weights (:157-171), as mgf_vanilla_slice_kernel forms them: Simpson 1,4,2,...
 // with every odd index 4 (an even-length grid keeps 4 on its last point), or for is_simpson = 0 half the first step on the
@@ -158,34 +158,53 @@ __global__ __launch_bounds__(HIST_BLOCK) void histogram_uniform_kernel(const dou
     }
 }
 
-// ---- Gaussian kernel density estimate of a resident state vector: DESIGN.md row f7 ------------------------------------------
+// ---- Gaussian kernel density estimate of a resident state vector, plain and weighted: DESIGN.md rows f7 and f9 ---------------
 // scipy.stats.gaussian_kde(kept)(points) written out (reference pricers/model_pricer.py:243-265): the sample is a[i] / divisor;
 // NaNs and samples beyond +-limit (strict comparisons) are dropped and counted; mean and variance of the kept samples in two
 // passes as np.cov takes them; h = sqrt(var) factor with Scott's factor n_kept^(-1/5) unless one is given;
-// density_j = sum_i exp(-((g_j - v_i) / h)^2 / 2) / (n_kept h sqrt(2 pi)).
+// density_j = sum_i exp(-((g_j - v_i) / h)^2 / 2) / (n_kept h sqrt(2 pi)).  The six launches (W: the template argument WEIGHTED):
 //
-//   kde_moments_kernel<1>         per block [kept, NaN, low, high, sum v]          kde_moments_finish_kernel<1>   counts, mean
-//   kde_moments_kernel<2>         per block sum (v - mean)^2, mean from the block  kde_moments_finish_kernel<2>   var, h
-//   kde_gaussian_kernel           block (x, y): the KDE_TILE points of tile x against the samples of chunk y; a thread keeps the
+//   kde_moments_kernel<W, 1>      per block [kept, NaN, low, high, sum v]          kde_moments_finish_kernel<W, 1>   counts, mean
+//   kde_moments_kernel<W, 2>      per block sum (v - mean)^2, mean from the block  kde_moments_finish_kernel<W, 2>   var, h
+//   kde_gaussian_kernel<W>        block (x, y): the KDE_TILE points of tile x against the samples of chunk y; a thread keeps the
 //                                 tile in registers and streams its samples past it (one 8-byte load and one division feed
 //                                 KDE_TILE exponentials); partials[y][point]
-//   kde_finish_kernel             a thread per point adds its chunks in order and scales by 1 / (n_kept h sqrt(2 pi))
+//   kde_finish_kernel<W>          a thread per point adds its chunks in order and scales by 1 / (n_kept h sqrt(2 pi))
 //
 // Every launch after the first reads what it needs (mean, h, n_kept) from the stats block on the device: no host round trip.
 // Order of every sum: a thread adds its samples in index order, the 64 lanes of a wave meet in one shuffle tree, the four waves
 // are added in order, the blocks / chunks in order.  The grids of the moment kernels and the chunk length are functions of n
 // alone (kde_chunk_length, kde_moment_blocks) and a point's sum does not depend on the tile it sits in: the density of a
-// vector at a point is the same bits whatever other points or vectors share the call.
+// vector at a point is the same bits whatever other points, vectors or gammas share the call.
+//
+// WEIGHTED is scipy.stats.gaussian_kde(kept, weights=w_kept)(points) (include/svmc.h states the semantics): the weight
+// w = weights[i] exp_full(gamma tilt[i]), either factor 1 where its vector is NULL, is formed once per sample (one or two more
+// 8-byte loads, with a tilt one more exp_full) and multiplies the sample's terms; a sample whose value passes the filter is dropped
+// for its weight, and counted, unless w >= 0 with w and w^2 finite.  The first moment pass carries [kept, NaN, low, high, bad
+// weight, sum w, sum w^2, sum w v]; sw = sum w, sw2 = sum w^2, mean = sum w v / sw, var = sum w (v - mean)^2 / (sw - sw2 / sw) as
+// np.cov(aweights=w, ddof=1), neff = sw^2 / sw2 in Scott's factor, and sw takes n_kept's place in the last scaling.  KdeLayout
+// and the `if constexpr (WEIGHTED)` branches are all that differs: the plain instantiation has no weight to load, test or
+// multiply by.  With both vectors NULL the weighted one has w the literal 1.0 and every product with it is exact: sum w =
+// sum w^2 = n_kept, sum w v = sum v, sw - sw2 / sw = n_kept - 1 and neff = sw (sw / sw2) = n_kept, so its density and stats
+// EQUAL the plain instantiation's.
 constexpr int KDE_BLOCK = 256;
 constexpr int KDE_TILE = SVMC_KDE_TILE;
 constexpr size_t KDE_MIN_CHUNK = 2048;       // samples per chunk up to 2^19 samples: 8 per thread, 64 exponentials against a
 constexpr size_t KDE_MAX_CHUNKS = 256;       // block reduction of ~200 instructions; beyond that 256 chunks of n / 256
 constexpr int KDE_MOMENT_BLOCKS = 256;       // most blocks of a moment pass (their partials fit one finishing block)
 constexpr size_t KDE_MOMENT_PER_BLOCK = 2048;
-constexpr int KDE_MOMENT_DOUBLES = 5 * KDE_MOMENT_BLOCKS;
-enum { KDE_N_KEPT = 0, KDE_N_NAN, KDE_N_LOW, KDE_N_HIGH, KDE_MEAN, KDE_VAR, KDE_H, KDE_FACTOR };
-static_assert(KDE_FACTOR + 1 == SVMC_KDE_STATS_DOUBLES, "stats block layout");
 static_assert(KDE_BLOCK == 256 && KDE_MOMENT_BLOCKS <= KDE_BLOCK, "block_sum_rows adds four waves");
+
+// rows of the first moment pass, the stats block (the first four entries are shared) and the normaliser of the last scaling
+template <bool WEIGHTED> struct KdeLayout;
+template <> struct KdeLayout<false> {
+    enum { N_KEPT = 0, N_NAN, N_LOW, N_HIGH, MEAN, VAR, H, FACTOR, ROWS = 5, NORM = N_KEPT };
+    static_assert(FACTOR + 1 == SVMC_KDE_STATS_DOUBLES, "stats block layout");
+};
+template <> struct KdeLayout<true> {
+    enum { N_KEPT = 0, N_NAN, N_LOW, N_HIGH, N_BAD_WEIGHT, SUM_W, NEFF, MEAN, VAR, H, FACTOR, SUM_W2, ROWS = 8, NORM = SUM_W };
+    static_assert(SUM_W2 + 1 == SVMC_KDE_WEIGHTED_STATS_DOUBLES, "weighted stats block layout");
+};
 
 inline size_t kde_chunk_length(size_t n)
 {
@@ -214,27 +233,70 @@ __device__ __forceinline__ void block_sum_rows(double (&v)[NV], double (*lds)[4]
 
 __device__ __forceinline__ double rows_total(const double (*lds)[4], int k) { return ((lds[k][0] + lds[k][1]) + lds[k][2]) + lds[k][3]; }
 
-template <int PASS>
-__global__ __launch_bounds__(KDE_BLOCK) void kde_moments_kernel(const double *__restrict__ a, size_t n, double divisor, double limit,
-                                                                const double *__restrict__ stats, double *__restrict__ partials)
+struct KdeWeight {                           // what WEIGHTED reads; the plain kernels carry it unread
+    const double *weights, *tilt;
+    double gamma;
+};
+
+// w_i; NaN, negative and overflowed weights come out as they are and fail kde_weight_kept
+template <bool WEIGHTED>
+__device__ __forceinline__ double kde_weight(const KdeWeight &wt, size_t p)
 {
-    constexpr int NV = (PASS == 1) ? 5 : 1;
+    if constexpr (!WEIGHTED) return 1.0;
+    else {
+        double w = wt.weights ? wt.weights[p] : 1.0;
+        if (wt.tilt) w *= exp_full(wt.gamma * wt.tilt[p]);
+        return w;
+    }
+}
+
+template <bool WEIGHTED>
+__device__ __forceinline__ bool kde_weight_kept(double w)
+{
+    if constexpr (!WEIGHTED) return true;
+    else return w >= 0.0 && w * w < __builtin_huge_val();                      // w^2 finite: so is w
+}
+
+// w e, or e as it stands: the plain sums hold no product with 1.0 for the compiler to fold
+template <bool WEIGHTED>
+__device__ __forceinline__ double kde_times_weight(double w, double e)
+{
+    if constexpr (WEIGHTED) return w * e;
+    else return e;
+}
+
+template <bool WEIGHTED, int PASS>
+__global__ __launch_bounds__(KDE_BLOCK) void kde_moments_kernel(const double *__restrict__ a, KdeWeight wt, size_t n, double divisor,
+                                                                double limit, const double *__restrict__ stats,
+                                                                double *__restrict__ partials)
+{
+    using L = KdeLayout<WEIGHTED>;
+    constexpr int NV = (PASS == 1) ? L::ROWS : 1;
     __shared__ double lds[NV][4];
-    const double mean = (PASS == 2) ? stats[KDE_MEAN] : 0.0;
+    const double mean = (PASS == 2) ? stats[L::MEAN] : 0.0;
     double acc[NV] = {};
     for (size_t p = static_cast<size_t>(blockIdx.x) * KDE_BLOCK + threadIdx.x; p < n; p += static_cast<size_t>(gridDim.x) * KDE_BLOCK) {
         const double v = a[p] / divisor;
+        const double w = kde_weight<WEIGHTED>(wt, p);
         const bool is_nan = v != v, high = v > limit, low = v < -limit;
-        const bool kept = !(is_nan || high || low);
-        if (PASS == 1) {
+        const bool passed = !(is_nan || high || low);
+        const bool kept = passed && kde_weight_kept<WEIGHTED>(w);
+        if constexpr (PASS == 1) {
             acc[0] += kept ? 1.0 : 0.0;
             acc[1] += is_nan ? 1.0 : 0.0;
             acc[2] += low ? 1.0 : 0.0;
             acc[3] += high ? 1.0 : 0.0;
-            acc[4] += kept ? v : 0.0;
+            if constexpr (WEIGHTED) {
+                acc[4] += (passed && !kept) ? 1.0 : 0.0;
+                acc[5] += kept ? w : 0.0;
+                acc[6] += kept ? w * w : 0.0;
+                acc[7] += kept ? w * v : 0.0;
+            } else {
+                acc[4] += kept ? v : 0.0;
+            }
         } else {
             const double d = v - mean;
-            acc[0] += kept ? d * d : 0.0;
+            acc[0] += kept ? kde_times_weight<WEIGHTED>(w, d * d) : 0.0;
         }
     }
     block_sum_rows<NV>(acc, lds);
@@ -242,35 +304,54 @@ __global__ __launch_bounds__(KDE_BLOCK) void kde_moments_kernel(const double *__
 }
 
 // one block: the blocks' partials in order (thread t holds block t's), then the stats the later launches read
-template <int PASS>
+template <bool WEIGHTED, int PASS>
 __global__ __launch_bounds__(KDE_BLOCK) void kde_moments_finish_kernel(const double *__restrict__ partials, int n_blocks, double factor,
                                                                        double *__restrict__ stats)
 {
-    constexpr int NV = (PASS == 1) ? 5 : 1;
+    using L = KdeLayout<WEIGHTED>;
+    constexpr int NV = (PASS == 1) ? L::ROWS : 1;
     __shared__ double lds[NV][4];
     double v[NV];
 #pragma unroll
     for (int k = 0; k < NV; ++k) v[k] = (static_cast<int>(threadIdx.x) < n_blocks) ? partials[k * n_blocks + threadIdx.x] : 0.0;
     block_sum_rows<NV>(v, lds);
     if (threadIdx.x != 0) return;
-    if (PASS == 1) {
+    if constexpr (PASS == 1) {
         const double n_kept = rows_total(lds, 0);
-        stats[KDE_N_KEPT] = n_kept;
-        stats[KDE_N_NAN] = rows_total(lds, 1);
-        stats[KDE_N_LOW] = rows_total(lds, 2);
-        stats[KDE_N_HIGH] = rows_total(lds, 3);
-        stats[KDE_MEAN] = rows_total(lds, 4) / n_kept;
+        stats[L::N_KEPT] = n_kept;
+        stats[L::N_NAN] = rows_total(lds, 1);
+        stats[L::N_LOW] = rows_total(lds, 2);
+        stats[L::N_HIGH] = rows_total(lds, 3);
+        if constexpr (WEIGHTED) {
+            const double sw = rows_total(lds, 5), sw2 = rows_total(lds, 6);
+            stats[L::N_BAD_WEIGHT] = rows_total(lds, 4);
+            stats[L::SUM_W] = sw;
+            stats[L::SUM_W2] = sw2;
+            stats[L::NEFF] = sw * (sw / sw2);                                 // sw^2 / sw2; at unit weights n (n / n), exact for any n
+            stats[L::MEAN] = rows_total(lds, 7) / sw;
+        } else {
+            stats[L::MEAN] = rows_total(lds, 4) / n_kept;
+        }
     } else {
-        const double n_kept = stats[KDE_N_KEPT];
-        const double var = rows_total(lds, 0) / (n_kept - 1.0);
-        const double f = (factor > 0.0) ? factor : pow(n_kept, -0.2);         // Scott's rule in one dimension
-        stats[KDE_VAR] = var;
-        stats[KDE_H] = sqrt(var) * f;
-        stats[KDE_FACTOR] = f;
+        double neff, dof;                                                     // Scott's n and np.cov's ddof=1 divisor
+        if constexpr (WEIGHTED) {
+            const double sw = stats[L::SUM_W], sw2 = stats[L::SUM_W2];
+            neff = stats[L::NEFF];
+            dof = sw - sw2 / sw;                                              // np.cov(aweights=w, ddof=1)
+        } else {
+            neff = stats[L::N_KEPT];
+            dof = neff - 1.0;
+        }
+        const double var = rows_total(lds, 0) / dof;
+        const double f = (factor > 0.0) ? factor : pow(neff, -0.2);           // Scott's rule in one dimension
+        stats[L::VAR] = var;
+        stats[L::H] = sqrt(var) * f;
+        stats[L::FACTOR] = f;
     }
 }
 
-__global__ __launch_bounds__(KDE_BLOCK) void kde_gaussian_kernel(const double *__restrict__ a, size_t n, size_t chunk_len,
+template <bool WEIGHTED>
+__global__ __launch_bounds__(KDE_BLOCK) void kde_gaussian_kernel(const double *__restrict__ a, KdeWeight wt, size_t n, size_t chunk_len,
                                                                  double divisor, double limit, const double *__restrict__ points,
                                                                  int m, const double *__restrict__ stats,
                                                                  double *__restrict__ partials)
@@ -283,17 +364,18 @@ __global__ __launch_bounds__(KDE_BLOCK) void kde_gaussian_kernel(const double *_
         g[j] = points[(j0 + j < m) ? j0 + j : m - 1];                 // the last tile repeats the last point: read in bounds, not stored
         acc[j] = 0.0;
     }
-    const double inv_h = 1.0 / stats[KDE_H];
+    const double inv_h = 1.0 / stats[KdeLayout<WEIGHTED>::H];
     const size_t begin = static_cast<size_t>(blockIdx.y) * chunk_len;
     const size_t end = (begin + chunk_len < n) ? begin + chunk_len : n;
     for (size_t p = begin + threadIdx.x; p < end; p += KDE_BLOCK) {
         const double v = a[p] / divisor;
-        const bool kept = (v == v) && !(v > limit) && !(v < -limit);
+        const double w = kde_weight<WEIGHTED>(wt, p);
+        const bool kept = (v == v) && !(v > limit) && !(v < -limit) && kde_weight_kept<WEIGHTED>(w);
 #pragma unroll
         for (int j = 0; j < KDE_TILE; ++j) {
             const double d = (g[j] - v) * inv_h;
             const double e = exp_full((-0.5 * d) * d);                // <= 0: +0 below -746
-            acc[j] += kept ? e : 0.0;
+            acc[j] += kept ? kde_times_weight<WEIGHTED>(w, e) : 0.0;
         }
     }
     block_sum_rows<KDE_TILE>(acc, lds);
@@ -301,158 +383,66 @@ __global__ __launch_bounds__(KDE_BLOCK) void kde_gaussian_kernel(const double *_
         partials[static_cast<size_t>(blockIdx.y) * m + j0 + threadIdx.x] = rows_total(lds, threadIdx.x);
 }
 
+template <bool WEIGHTED>
 __global__ __launch_bounds__(KDE_BLOCK) void kde_finish_kernel(const double *__restrict__ partials, int n_chunks, int m,
                                                                const double *__restrict__ stats, double *__restrict__ density)
 {
+    using L = KdeLayout<WEIGHTED>;
     const int j = blockIdx.x * KDE_BLOCK + threadIdx.x;
     if (j >= m) return;
     double s = 0.0;
 #pragma unroll 16
     for (int c = 0; c < n_chunks; ++c) s += partials[static_cast<size_t>(c) * m + j];
-    density[j] = s / (stats[KDE_N_KEPT] * stats[KDE_H] * 2.5066282746310002);                  // sqrt(2 pi)
+    density[j] = s / (stats[L::NORM] * stats[L::H] * 2.5066282746310002);                      // sqrt(2 pi)
 }
 
-// ---- weighted Gaussian kernel density estimate: DESIGN.md row f9 ------------------------------------------------------------
-// scipy.stats.gaussian_kde(kept, weights=w_kept)(points) written out (include/svmc.h states the semantics): row f7's sample and
-// filter; the weight w = weights[i] exp_full(gamma tilt[i]), either factor 1 where its vector is NULL; a sample whose value
-// passes the filter is dropped for its weight, and counted, unless w >= 0 with w and w^2 finite; sw = sum w, sw2 = sum w^2,
-// mean = sum w v / sw, var = sum w (v - mean)^2 / (sw - sw2 / sw) as np.cov(aweights=w, ddof=1), neff = sw^2 / sw2 in Scott's
-// factor, density_j = sum_i w_i exp(-((g_j - v_i) / h)^2 / 2) / (sw h sqrt(2 pi)).
-//
-//   kde_weighted_moments_kernel<1>   per block [kept, NaN, low, high, bad weight, sum w, sum w^2, sum w v]
-//   kde_weighted_moments_kernel<2>   per block sum w (v - mean)^2, mean from the block
-//   kde_weighted_moments_finish_kernel<1, 2>, kde_weighted_gaussian_kernel, kde_weighted_finish_kernel   as their f7 namesakes
-//
-// The siblings of row f7's kernels, which stay as they are: the same grids, chunk length (kde_chunk_length, kde_moment_blocks)
-// and order of every sum, so the bits of a (vector, gamma) pair do not depend on the company it keeps.  A weight is formed once
-// per sample (one or two more 8-byte loads, with a tilt one more exp_full) and multiplies the sample's KDE_TILE exponentials.
-// With both vectors NULL w is the literal 1.0 and every product with it is exact: sum w = sum w^2 = n_kept, sum w v = sum v,
-// sw - sw2 / sw = n_kept - 1 and neff = sw (sw / sw2) = n_kept, so the density and the stats EQUAL svmc_kde_gaussian's.
-constexpr int KDE_WEIGHTED_ROWS = 8;
-constexpr int KDE_WEIGHTED_MOMENT_DOUBLES = KDE_WEIGHTED_ROWS * KDE_MOMENT_BLOCKS;
-enum { KDW_N_KEPT = 0, KDW_N_NAN, KDW_N_LOW, KDW_N_HIGH, KDW_N_BAD_WEIGHT, KDW_SUM_W, KDW_NEFF, KDW_MEAN, KDW_VAR, KDW_H,
-       KDW_FACTOR, KDW_SUM_W2 };
-static_assert(KDW_SUM_W2 + 1 == SVMC_KDE_WEIGHTED_STATS_DOUBLES, "weighted stats block layout");
-
-// w_i; NaN, negative and overflowed weights come out as they are and fail kde_weight_kept
-__device__ __forceinline__ double kde_weight(const double *__restrict__ weights, const double *__restrict__ tilt, double gamma, size_t p)
+// host side of both entry points: `fn` names the entry in every message, `ws_fn` its workspace function
+template <bool WEIGHTED>
+int kde_workspace_bytes(const char *fn, size_t n, size_t *bytes, size_t *chunk_length)
 {
-    double w = weights ? weights[p] : 1.0;
-    if (tilt) w *= exp_full(gamma * tilt[p]);
-    return w;
+    SVMC_REQUIRE(bytes, std::string(fn) + ": null pointer");
+    SVMC_REQUIRE(n >= 1 && n < (static_cast<size_t>(1) << 40), std::string(fn) + ": n must be in 1 .. 2^40 - 1");
+    const size_t len = kde_chunk_length(n), n_chunks = (n + len - 1) / len;
+    *bytes = sizeof(double) * (KdeLayout<WEIGHTED>::ROWS * KDE_MOMENT_BLOCKS + n_chunks * SVMC_KDE_MAX_POINTS);
+    if (chunk_length) *chunk_length = len;
+    return SVMC_OK;
 }
 
-__device__ __forceinline__ bool kde_weight_kept(double w) { return w >= 0.0 && w * w < __builtin_huge_val(); }     // w^2 finite: so is w
-
-template <int PASS>
-__global__ __launch_bounds__(KDE_BLOCK) void kde_weighted_moments_kernel(const double *__restrict__ a, const double *__restrict__ weights,
-                                                                         const double *__restrict__ tilt, double gamma, size_t n,
-                                                                         double divisor, double limit, const double *__restrict__ stats,
-                                                                         double *__restrict__ partials)
+template <bool WEIGHTED>
+int kde_launch(const char *fn, const char *ws_fn, const double *values, KdeWeight wt, size_t n, double divisor, double limit,
+               const double *points, int n_points, double bandwidth_factor, double *density, double *stats, void *workspace,
+               size_t workspace_bytes, svmc_stream_t stream)
 {
-    constexpr int NV = (PASS == 1) ? KDE_WEIGHTED_ROWS : 1;
-    __shared__ double lds[NV][4];
-    const double mean = (PASS == 2) ? stats[KDW_MEAN] : 0.0;
-    double acc[NV] = {};
-    for (size_t p = static_cast<size_t>(blockIdx.x) * KDE_BLOCK + threadIdx.x; p < n; p += static_cast<size_t>(gridDim.x) * KDE_BLOCK) {
-        const double v = a[p] / divisor;
-        const double w = kde_weight(weights, tilt, gamma, p);
-        const bool is_nan = v != v, high = v > limit, low = v < -limit;
-        const bool passed = !(is_nan || high || low);
-        const bool kept = passed && kde_weight_kept(w);
-        if (PASS == 1) {
-            acc[0] += kept ? 1.0 : 0.0;
-            acc[1] += is_nan ? 1.0 : 0.0;
-            acc[2] += low ? 1.0 : 0.0;
-            acc[3] += high ? 1.0 : 0.0;
-            acc[4] += (passed && !kept) ? 1.0 : 0.0;
-            acc[5] += kept ? w : 0.0;
-            acc[6] += kept ? w * w : 0.0;
-            acc[7] += kept ? w * v : 0.0;
-        } else {
-            const double d = v - mean;
-            acc[0] += kept ? w * (d * d) : 0.0;
-        }
-    }
-    block_sum_rows<NV>(acc, lds);
-    if (threadIdx.x < NV) partials[threadIdx.x * gridDim.x + blockIdx.x] = rows_total(lds, threadIdx.x);
+    constexpr size_t MOMENT_DOUBLES = KdeLayout<WEIGHTED>::ROWS * KDE_MOMENT_BLOCKS;
+    SVMC_REQUIRE(values && points && density && stats && workspace, std::string(fn) + ": null pointer");
+    SVMC_REQUIRE(n >= 1 && n < (static_cast<size_t>(1) << 40), std::string(fn) + ": n must be in 1 .. 2^40 - 1");
+    SVMC_REQUIRE(n_points >= 1, std::string(fn) + ": n_points must be at least 1");
+    SVMC_REQUIRE(n_points <= SVMC_KDE_MAX_POINTS, std::string(fn) + ": n_points above SVMC_KDE_MAX_POINTS");
+    SVMC_REQUIRE(divisor > 0.0 && divisor < HUGE_VAL, std::string(fn) + ": divisor must be positive and finite");
+    SVMC_REQUIRE(limit > 0.0 && limit < HUGE_VAL, std::string(fn) + ": limit must be positive and finite");
+    SVMC_REQUIRE(bandwidth_factor == bandwidth_factor && bandwidth_factor < HUGE_VAL, std::string(fn) + ": bandwidth factor must be finite");
+    if constexpr (WEIGHTED) SVMC_REQUIRE(wt.gamma > -HUGE_VAL && wt.gamma < HUGE_VAL, std::string(fn) + ": gamma must be finite");
+    const size_t len = kde_chunk_length(n), n_chunks = (n + len - 1) / len;
+    if (workspace_bytes < sizeof(double) * (MOMENT_DOUBLES + n_chunks * static_cast<size_t>(n_points)))
+        return fail(SVMC_ERR_WORKSPACE, std::string(fn) + ": workspace too small (" + ws_fn + ")");
+    double *moment_partials = static_cast<double *>(workspace), *partials = moment_partials + MOMENT_DOUBLES;
+    const unsigned mb = kde_moment_blocks(n);
+    hipStream_t s = as_stream(stream);
+    hipLaunchKernelGGL((kde_moments_kernel<WEIGHTED, 1>), dim3(mb), dim3(KDE_BLOCK), 0, s, values, wt, n, divisor, limit, stats,
+                       moment_partials);
+    hipLaunchKernelGGL((kde_moments_finish_kernel<WEIGHTED, 1>), dim3(1), dim3(KDE_BLOCK), 0, s, moment_partials, static_cast<int>(mb),
+                       bandwidth_factor, stats);
+    hipLaunchKernelGGL((kde_moments_kernel<WEIGHTED, 2>), dim3(mb), dim3(KDE_BLOCK), 0, s, values, wt, n, divisor, limit, stats,
+                       moment_partials);
+    hipLaunchKernelGGL((kde_moments_finish_kernel<WEIGHTED, 2>), dim3(1), dim3(KDE_BLOCK), 0, s, moment_partials, static_cast<int>(mb),
+                       bandwidth_factor, stats);
+    hipLaunchKernelGGL(kde_gaussian_kernel<WEIGHTED>, dim3((n_points + KDE_TILE - 1) / KDE_TILE, static_cast<unsigned>(n_chunks)),
+                       dim3(KDE_BLOCK), 0, s, values, wt, n, len, divisor, limit, points, n_points, stats, partials);
+    hipLaunchKernelGGL(kde_finish_kernel<WEIGHTED>, dim3((n_points + KDE_BLOCK - 1) / KDE_BLOCK), dim3(KDE_BLOCK), 0, s, partials,
+                       static_cast<int>(n_chunks), n_points, stats, density);
+    return check_launch(fn);
 }
 
-template <int PASS>
-__global__ __launch_bounds__(KDE_BLOCK) void kde_weighted_moments_finish_kernel(const double *__restrict__ partials, int n_blocks,
-                                                                                double factor, double *__restrict__ stats)
-{
-    constexpr int NV = (PASS == 1) ? KDE_WEIGHTED_ROWS : 1;
-    __shared__ double lds[NV][4];
-    double v[NV];
-#pragma unroll
-    for (int k = 0; k < NV; ++k) v[k] = (static_cast<int>(threadIdx.x) < n_blocks) ? partials[k * n_blocks + threadIdx.x] : 0.0;
-    block_sum_rows<NV>(v, lds);
-    if (threadIdx.x != 0) return;
-    if (PASS == 1) {
-        const double sw = rows_total(lds, 5), sw2 = rows_total(lds, 6);
-        stats[KDW_N_KEPT] = rows_total(lds, 0);
-        stats[KDW_N_NAN] = rows_total(lds, 1);
-        stats[KDW_N_LOW] = rows_total(lds, 2);
-        stats[KDW_N_HIGH] = rows_total(lds, 3);
-        stats[KDW_N_BAD_WEIGHT] = rows_total(lds, 4);
-        stats[KDW_SUM_W] = sw;
-        stats[KDW_SUM_W2] = sw2;
-        stats[KDW_NEFF] = sw * (sw / sw2);                                    // sw^2 / sw2; at unit weights n (n / n), exact for any n
-        stats[KDW_MEAN] = rows_total(lds, 7) / sw;
-    } else {
-        const double sw = stats[KDW_SUM_W], sw2 = stats[KDW_SUM_W2];
-        const double var = rows_total(lds, 0) / (sw - sw2 / sw);              // np.cov(aweights=w, ddof=1)
-        const double f = (factor > 0.0) ? factor : pow(stats[KDW_NEFF], -0.2);
-        stats[KDW_VAR] = var;
-        stats[KDW_H] = sqrt(var) * f;
-        stats[KDW_FACTOR] = f;
-    }
-}
-
-__global__ __launch_bounds__(KDE_BLOCK) void kde_weighted_gaussian_kernel(const double *__restrict__ a, const double *__restrict__ weights,
-                                                                          const double *__restrict__ tilt, double gamma, size_t n,
-                                                                          size_t chunk_len, double divisor, double limit,
-                                                                          const double *__restrict__ points, int m,
-                                                                          const double *__restrict__ stats, double *__restrict__ partials)
-{
-    __shared__ double lds[KDE_TILE][4];
-    const int j0 = blockIdx.x * KDE_TILE;
-    double g[KDE_TILE], acc[KDE_TILE];
-#pragma unroll
-    for (int j = 0; j < KDE_TILE; ++j) {
-        g[j] = points[(j0 + j < m) ? j0 + j : m - 1];                 // the last tile repeats the last point: read in bounds, not stored
-        acc[j] = 0.0;
-    }
-    const double inv_h = 1.0 / stats[KDW_H];
-    const size_t begin = static_cast<size_t>(blockIdx.y) * chunk_len;
-    const size_t end = (begin + chunk_len < n) ? begin + chunk_len : n;
-    for (size_t p = begin + threadIdx.x; p < end; p += KDE_BLOCK) {
-        const double v = a[p] / divisor;
-        const double w = kde_weight(weights, tilt, gamma, p);
-        const bool kept = (v == v) && !(v > limit) && !(v < -limit) && kde_weight_kept(w);
-#pragma unroll
-        for (int j = 0; j < KDE_TILE; ++j) {
-            const double d = (g[j] - v) * inv_h;
-            const double e = exp_full((-0.5 * d) * d);                // <= 0: +0 below -746
-            acc[j] += kept ? w * e : 0.0;
-        }
-    }
-    block_sum_rows<KDE_TILE>(acc, lds);
-    if (threadIdx.x < KDE_TILE && j0 + static_cast<int>(threadIdx.x) < m)
-        partials[static_cast<size_t>(blockIdx.y) * m + j0 + threadIdx.x] = rows_total(lds, threadIdx.x);
-}
-
-__global__ __launch_bounds__(KDE_BLOCK) void kde_weighted_finish_kernel(const double *__restrict__ partials, int n_chunks, int m,
-                                                                        const double *__restrict__ stats, double *__restrict__ density)
-{
-    const int j = blockIdx.x * KDE_BLOCK + threadIdx.x;
-    if (j >= m) return;
-    double s = 0.0;
-#pragma unroll 16
-    for (int c = 0; c < n_chunks; ++c) s += partials[static_cast<size_t>(c) * m + j];
-    density[j] = s / (stats[KDW_SUM_W] * stats[KDW_H] * 2.5066282746310002);                   // sqrt(2 pi)
-}
 
 }  // namespace svmc
 
@@ -531,86 +521,28 @@ int svmc_histogram_uniform(const double *values, size_t n, double divisor, const
 
 int svmc_kde_workspace_bytes(size_t n, size_t *bytes, size_t *chunk_length)
 {
-    SVMC_REQUIRE(bytes, "svmc_kde_workspace_bytes: null pointer");
-    SVMC_REQUIRE(n >= 1 && n < (static_cast<size_t>(1) << 40), "svmc_kde_workspace_bytes: n must be in 1 .. 2^40 - 1");
-    const size_t len = kde_chunk_length(n), n_chunks = (n + len - 1) / len;
-    *bytes = sizeof(double) * (KDE_MOMENT_DOUBLES + n_chunks * SVMC_KDE_MAX_POINTS);
-    if (chunk_length) *chunk_length = len;
-    return SVMC_OK;
+    return kde_workspace_bytes<false>("svmc_kde_workspace_bytes", n, bytes, chunk_length);
 }
 
 int svmc_kde_gaussian(const double *values, size_t n, double divisor, double limit, const double *points, int n_points,
                       double bandwidth_factor, double *density, double *stats, void *workspace, size_t workspace_bytes,
                       svmc_stream_t stream)
 {
-    SVMC_REQUIRE(values && points && density && stats && workspace, "svmc_kde_gaussian: null pointer");
-    SVMC_REQUIRE(n >= 1 && n < (static_cast<size_t>(1) << 40), "svmc_kde_gaussian: n must be in 1 .. 2^40 - 1");
-    SVMC_REQUIRE(n_points >= 1, "svmc_kde_gaussian: n_points must be at least 1");
-    SVMC_REQUIRE(n_points <= SVMC_KDE_MAX_POINTS, "svmc_kde_gaussian: n_points above SVMC_KDE_MAX_POINTS");
-    SVMC_REQUIRE(divisor > 0.0 && divisor < HUGE_VAL, "svmc_kde_gaussian: divisor must be positive and finite");
-    SVMC_REQUIRE(limit > 0.0 && limit < HUGE_VAL, "svmc_kde_gaussian: limit must be positive and finite");
-    SVMC_REQUIRE(bandwidth_factor == bandwidth_factor && bandwidth_factor < HUGE_VAL, "svmc_kde_gaussian: bandwidth factor must be finite");
-    const size_t len = kde_chunk_length(n), n_chunks = (n + len - 1) / len;
-    if (workspace_bytes < sizeof(double) * (KDE_MOMENT_DOUBLES + n_chunks * static_cast<size_t>(n_points)))
-        return fail(SVMC_ERR_WORKSPACE, "svmc_kde_gaussian: workspace too small (svmc_kde_workspace_bytes)");
-    double *moment_partials = static_cast<double *>(workspace), *partials = moment_partials + KDE_MOMENT_DOUBLES;
-    const unsigned mb = kde_moment_blocks(n);
-    hipStream_t s = as_stream(stream);
-    hipLaunchKernelGGL(kde_moments_kernel<1>, dim3(mb), dim3(KDE_BLOCK), 0, s, values, n, divisor, limit, stats, moment_partials);
-    hipLaunchKernelGGL(kde_moments_finish_kernel<1>, dim3(1), dim3(KDE_BLOCK), 0, s, moment_partials, static_cast<int>(mb),
-                       bandwidth_factor, stats);
-    hipLaunchKernelGGL(kde_moments_kernel<2>, dim3(mb), dim3(KDE_BLOCK), 0, s, values, n, divisor, limit, stats, moment_partials);
-    hipLaunchKernelGGL(kde_moments_finish_kernel<2>, dim3(1), dim3(KDE_BLOCK), 0, s, moment_partials, static_cast<int>(mb),
-                       bandwidth_factor, stats);
-    hipLaunchKernelGGL(kde_gaussian_kernel, dim3((n_points + KDE_TILE - 1) / KDE_TILE, static_cast<unsigned>(n_chunks)), dim3(KDE_BLOCK),
-                       0, s, values, n, len, divisor, limit, points, n_points, stats, partials);
-    hipLaunchKernelGGL(kde_finish_kernel, dim3((n_points + KDE_BLOCK - 1) / KDE_BLOCK), dim3(KDE_BLOCK), 0, s, partials,
-                       static_cast<int>(n_chunks), n_points, stats, density);
-    return check_launch("svmc_kde_gaussian");
+    return kde_launch<false>("svmc_kde_gaussian", "svmc_kde_workspace_bytes", values, KdeWeight{nullptr, nullptr, 0.0}, n, divisor, limit,
+                             points, n_points, bandwidth_factor, density, stats, workspace, workspace_bytes, stream);
 }
 
 int svmc_kde_weighted_workspace_bytes(size_t n, size_t *bytes, size_t *chunk_length)
 {
-    SVMC_REQUIRE(bytes, "svmc_kde_weighted_workspace_bytes: null pointer");
-    SVMC_REQUIRE(n >= 1 && n < (static_cast<size_t>(1) << 40), "svmc_kde_weighted_workspace_bytes: n must be in 1 .. 2^40 - 1");
-    const size_t len = kde_chunk_length(n), n_chunks = (n + len - 1) / len;
-    *bytes = sizeof(double) * (KDE_WEIGHTED_MOMENT_DOUBLES + n_chunks * SVMC_KDE_MAX_POINTS);
-    if (chunk_length) *chunk_length = len;
-    return SVMC_OK;
+    return kde_workspace_bytes<true>("svmc_kde_weighted_workspace_bytes", n, bytes, chunk_length);
 }
 
 int svmc_kde_gaussian_weighted(const double *values, const double *weights, const double *tilt, double gamma, size_t n,
                                double divisor, double limit, const double *points, int n_points, double bandwidth_factor,
                                double *density, double *stats, void *workspace, size_t workspace_bytes, svmc_stream_t stream)
 {
-    SVMC_REQUIRE(values && points && density && stats && workspace, "svmc_kde_gaussian_weighted: null pointer");
-    SVMC_REQUIRE(n >= 1 && n < (static_cast<size_t>(1) << 40), "svmc_kde_gaussian_weighted: n must be in 1 .. 2^40 - 1");
-    SVMC_REQUIRE(n_points >= 1, "svmc_kde_gaussian_weighted: n_points must be at least 1");
-    SVMC_REQUIRE(n_points <= SVMC_KDE_MAX_POINTS, "svmc_kde_gaussian_weighted: n_points above SVMC_KDE_MAX_POINTS");
-    SVMC_REQUIRE(divisor > 0.0 && divisor < HUGE_VAL, "svmc_kde_gaussian_weighted: divisor must be positive and finite");
-    SVMC_REQUIRE(limit > 0.0 && limit < HUGE_VAL, "svmc_kde_gaussian_weighted: limit must be positive and finite");
-    SVMC_REQUIRE(bandwidth_factor == bandwidth_factor && bandwidth_factor < HUGE_VAL,
-                 "svmc_kde_gaussian_weighted: bandwidth factor must be finite");
-    SVMC_REQUIRE(gamma > -HUGE_VAL && gamma < HUGE_VAL, "svmc_kde_gaussian_weighted: gamma must be finite");
-    const size_t len = kde_chunk_length(n), n_chunks = (n + len - 1) / len;
-    if (workspace_bytes < sizeof(double) * (KDE_WEIGHTED_MOMENT_DOUBLES + n_chunks * static_cast<size_t>(n_points)))
-        return fail(SVMC_ERR_WORKSPACE, "svmc_kde_gaussian_weighted: workspace too small (svmc_kde_weighted_workspace_bytes)");
-    double *moment_partials = static_cast<double *>(workspace), *partials = moment_partials + KDE_WEIGHTED_MOMENT_DOUBLES;
-    const unsigned mb = kde_moment_blocks(n);
-    hipStream_t s = as_stream(stream);
-    hipLaunchKernelGGL(kde_weighted_moments_kernel<1>, dim3(mb), dim3(KDE_BLOCK), 0, s, values, weights, tilt, gamma, n, divisor, limit,
-                       stats, moment_partials);
-    hipLaunchKernelGGL(kde_weighted_moments_finish_kernel<1>, dim3(1), dim3(KDE_BLOCK), 0, s, moment_partials, static_cast<int>(mb),
-                       bandwidth_factor, stats);
-    hipLaunchKernelGGL(kde_weighted_moments_kernel<2>, dim3(mb), dim3(KDE_BLOCK), 0, s, values, weights, tilt, gamma, n, divisor, limit,
-                       stats, moment_partials);
-    hipLaunchKernelGGL(kde_weighted_moments_finish_kernel<2>, dim3(1), dim3(KDE_BLOCK), 0, s, moment_partials, static_cast<int>(mb),
-                       bandwidth_factor, stats);
-    hipLaunchKernelGGL(kde_weighted_gaussian_kernel, dim3((n_points + KDE_TILE - 1) / KDE_TILE, static_cast<unsigned>(n_chunks)),
-                       dim3(KDE_BLOCK), 0, s, values, weights, tilt, gamma, n, len, divisor, limit, points, n_points, stats, partials);
-    hipLaunchKernelGGL(kde_weighted_finish_kernel, dim3((n_points + KDE_BLOCK - 1) / KDE_BLOCK), dim3(KDE_BLOCK), 0, s, partials,
-                       static_cast<int>(n_chunks), n_points, stats, density);
-    return check_launch("svmc_kde_gaussian_weighted");
+    return kde_launch<true>("svmc_kde_gaussian_weighted", "svmc_kde_weighted_workspace_bytes", values, KdeWeight{weights, tilt, gamma}, n,
+                            divisor, limit, points, n_points, bandwidth_factor, density, stats, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"
