@@ -444,12 +444,20 @@ SVMC_API int svmc_heston_chain_price(svmc_session_t session, const double *ttms_
 
 /* ---- many independent jobs of one chain in one call ---------------------------------------------------------------
  * n_jobs jobs share the chain (ttms .. strike_offsets, n_expiries <= 16), the session's path count, the step grid and the
- * variable type (LogSV also is_spot_measure, Heston the scheme); each has its own parameters and random stream.  Job j's
- * prices and standard errors (row j of prices_host / stderrs_host [n_jobs][sum K_i]) are those of svmc_logsv_chain_price /
- * svmc_heston_chain_price on the same session with job j's parameters, seeds_host[j] and call_ids_host[j], BIT FOR BIT: ONE
- * stepping launch steps every job (blockIdx.y = job), one payoff launch and one finish launch serve them all.
- *   params_host  LogSV:  [n_jobs][6 + n_expiries]  v0 theta kappa1 kappa2 beta volvol, then the expiries' vol-backbone etas
- *                Heston: [n_jobs][5]               v0 theta kappa rho volvol
+ * variable type (LogSV also is_spot_measure, Heston the scheme; Hawkes: SVMC_LOG_RETURN only); each has its own parameters and
+ * random stream.  Job j's prices and standard errors (row j of prices_host / stderrs_host [n_jobs][sum K_i]) are those of
+ * svmc_logsv_chain_price / svmc_heston_chain_price / svmc_hawkesjd_chain_price on the same session with job j's parameters,
+ * seeds_host[j] and call_ids_host[j], BIT FOR BIT: ONE stepping launch steps every job (blockIdx.y = job), one payoff launch
+ * and one finish launch serve them all.
+ *   params_host  LogSV:  [n_jobs][6 + n_expiries]       v0 theta kappa1 kappa2 beta volvol, then the expiries' vol-backbone etas
+ *                Heston: [n_jobs][5]                    v0 theta kappa rho volvol
+ *                Hawkes: [n_jobs][SVMC_HAWKESJD_PARAMS] the block of svmc_hawkesjd_chain_price; both start intensities
+ *                                                       (lambda_p, lambda_m) are per job
+ * svmc_hawkesjd_chain_price_tilted_many is the same stepping launch followed, per job, by svmc_tilted_payoff_chain on that job's
+ * snapshot rows (with recenter != 0 also its rows of the reduced spot sums), all on the session's stream and one synchronise:
+ * job j equals svmc_hawkesjd_chain_price_tilted with its parameters, stream and gammas_host[j][0 .. n_gammas), bit for bit.
+ * As there, no discount factors and no variable type (undiscounted prices of the log-return).  Outputs: prices_host /
+ * stderrs_host [n_jobs][n_gammas][sum K_i], stats_host [n_jobs][n_gammas][n_expiries][SVMC_TILTED_STATS_DOUBLES].
  * Session: any single-GPU session whose max_expiries / max_strikes_total hold the chain (the sizes a single call of the chain
  * needs); the driver grows a per-job workspace of its own inside the session on demand -- about (1 or 2 with Q_VAR) x
  * n_jobs x n_expiries x n_path doubles of snapshots, kept until the session is destroyed -- and touches none of the
@@ -457,7 +465,12 @@ SVMC_API int svmc_heston_chain_price(svmc_session_t session, const double *ttms_
  * At most SVMC_MANY_MAX_JOBS jobs per call (split longer lists).  Errors, all before anything is launched:
  *   SVMC_ERR_INVALID_ARGUMENT  n_jobs < 1 or > SVMC_MANY_MAX_JOBS, a null pointer (session included), n_expiries outside
  *                              [1, 16], a call id of 24 bits or more, an unknown scheme, a session with a communicator
- *                              or reducer attached (no sharded batch);
+ *                              or reducer attached (no sharded batch); Hawkes: a parameter block of ANY job that
+ *                              svmc_hawkesjd_chain_price refuses (non-finite, sigma < 0, mean_p outside [0, 1), mean_m > 0),
+ *                              and for the tilted call n_gammas outside 1 .. SVMC_TILTED_MAX_GAMMAS or a gamma, forward or
+ *                              strike that is not finite;
+ *   SVMC_ERR_UNSUPPORTED_VARIABLE  Hawkes: a variable_type other than SVMC_LOG_RETURN;
+ *   SVMC_ERR_UNKNOWN_PAYOFF    the tilted call: a type code other than SVMC_CALL / SVMC_PUT;
  *   SVMC_ERR_WORKSPACE         a session too small for the chain (n_expiries > max_expiries or sum K_i > max_strikes_total);
  *   SVMC_ERR_HIP               the per-job workspace could not be allocated. */
 #define SVMC_MANY_MAX_JOBS 64
@@ -473,6 +486,17 @@ SVMC_API int svmc_heston_chain_price_many(svmc_session_t session, const double *
                                           const double *params_host, const uint64_t *seeds_host, const uint32_t *call_ids_host,
                                           int scheme, int nb_steps_per_year, int variable_type, double *prices_host,
                                           double *stderrs_host);
+SVMC_API int svmc_hawkesjd_chain_price_many(svmc_session_t session, const double *ttms_host, const double *forwards_host,
+                                            const double *discfactors_host, int n_expiries, const double *strikes_host,
+                                            const int8_t *types_host, const size_t *strike_offsets_host, int n_jobs,
+                                            const double *params_host, const uint64_t *seeds_host, const uint32_t *call_ids_host,
+                                            int nb_steps_per_year, int variable_type, double *prices_host, double *stderrs_host);
+SVMC_API int svmc_hawkesjd_chain_price_tilted_many(svmc_session_t session, const double *ttms_host, const double *forwards_host,
+                                                   int n_expiries, const double *strikes_host, const int8_t *types_host,
+                                                   const size_t *strike_offsets_host, int n_jobs, const double *params_host,
+                                                   const uint64_t *seeds_host, const uint32_t *call_ids_host,
+                                                   int nb_steps_per_year, const double *gammas_host, int n_gammas, int recenter,
+                                                   double *prices_host, double *stderrs_host, double *stats_host);
 
 /* ---- multi-GPU below the host language: RCCL over xGMI ----------------------------------------------------------
  * One process (or thread) per GPU.  Paths are independent, so rank r holds the global path ids

@@ -10,7 +10,9 @@ Module layout and public names mirror the reference package (`stochvolmodels`) f
                                               hawkesjd_chain_pricer(_batch), simulate_hawkesjd_terminal,
                                               hawkesjd_forwards_under_risk_kernel, hawkesjd_pdf_under_risk_kernel,
                                               hawkesjd_chain_pricer_with_risk_premia(_batch),
-                                              hawkesjd_mc_chain_pricer_with_risk_premia(_gammas)
+                                              hawkesjd_mc_chain_pricer_with_risk_premia(_gammas),
+                                              hawkesjd_mc_chain_pricer_many,
+                                              hawkesjd_mc_chain_pricer_with_risk_premia_gammas_many
     stochvolmodels_amd.utils.mc_payoffs       compute_mc_vars_payoff, compute_mc_vars_payoff_with_gamma
     stochvolmodels_amd.utils.funcs            set_time_grid, set_seed, timer
     stochvolmodels_amd.utils.config           OptionType, VariableType
@@ -33,6 +35,8 @@ _EXPORTS = {
     "compute_mc_vars_payoff_with_gamma": "utils.mc_payoffs",
     "hawkesjd_mc_chain_pricer_with_risk_premia": "pricers.hawkes_jd_pricer",
     "hawkesjd_mc_chain_pricer_with_risk_premia_gammas": "pricers.hawkes_jd_pricer",
+    "hawkesjd_mc_chain_pricer_many": "pricers.hawkes_jd_pricer",
+    "hawkesjd_mc_chain_pricer_with_risk_premia_gammas_many": "pricers.hawkes_jd_pricer",
     "hawkesjd_pdf_under_risk_kernel": "pricers.hawkes_jd_pricer",
     "OptionChain": "data.option_chain",
     "ModelParams": "pricers.model_pricer", "ModelPricer": "pricers.model_pricer",

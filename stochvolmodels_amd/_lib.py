@@ -130,6 +130,10 @@ def _declare(L: C.CDLL) -> None:
                                          i32, i32, pf64, pf64], i32),
         "svmc_heston_chain_price_many": ([vp, pf64, pf64, pf64, i32, pf64, pi8, psz, i32, pf64, C.POINTER(u64), C.POINTER(u32),
                                           i32, i32, i32, pf64, pf64], i32),
+        "svmc_hawkesjd_chain_price_many": ([vp, pf64, pf64, pf64, i32, pf64, pi8, psz, i32, pf64, C.POINTER(u64), C.POINTER(u32),
+                                            i32, i32, pf64, pf64], i32),
+        "svmc_hawkesjd_chain_price_tilted_many": ([vp, pf64, pf64, i32, pf64, pi8, psz, i32, pf64, C.POINTER(u64), C.POINTER(u32), i32,
+                                                   pf64, i32, i32, pf64, pf64, pf64], i32),
         "svmc_payoff_finalize": ([pf64, pf64, sz, f64, f64, pf64, pf64], i32),
         "svmc_payoff_finalize_chain": ([pf64, pf64, pf64, sz, f64, pf64, pf64], i32),
         "svmc_rccl_available": ([], i32),

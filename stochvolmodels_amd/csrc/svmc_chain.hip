@@ -1006,7 +1006,7 @@ int svmc_hawkesjd_chain_price_tilted(svmc_session_t session, const double *ttms_
 
 }  // extern "C"
 
-// ---- many jobs of one chain (svmc_logsv_chain_price_many / svmc_heston_chain_price_many)
+// ---- many jobs of one chain (svmc_logsv_chain_price_many / svmc_heston_chain_price_many / svmc_hawkesjd_chain_price[_tilted]_many)
 
 // *p at least `need` bytes (its contents are not kept); every many-call ends synchronised, so nothing still reads the old buffer
 static hipError_t grow(void **p, size_t &cap, size_t need, bool pinned)
@@ -1020,9 +1020,11 @@ static hipError_t grow(void **p, size_t &cap, size_t need, bool pinned)
     return e;
 }
 
-static int grow_many(const char *fn, ManyBuffers &mb, size_t n, size_t J, size_t m, size_t K, bool need_q)
+// (min_ws_bytes: a floor for the payoff workspace, for a tail other than chain_payoff_and_finish_sets)
+static int grow_many(const char *fn, ManyBuffers &mb, size_t n, size_t J, size_t m, size_t K, bool need_q, size_t min_ws_bytes = 0)
 {
     const size_t d = sizeof(double), sums = (3 * K * J > 0 ? 3 * K * J : 1) * d;
+    const size_t sets_ws = payoff_sets_workspace_bytes(n, K, static_cast<int>(J)), ws = sets_ws > min_ws_bytes ? sets_ws : min_ws_bytes;
     const struct {
         void **p;
         size_t *cap, need;
@@ -1032,7 +1034,7 @@ static int grow_many(const char *fn, ManyBuffers &mb, size_t n, size_t J, size_t
         {reinterpret_cast<void **>(&mb.spot_ws), &mb.spot_ws_bytes, static_cast<size_t>(wave_rows(n)) * 2 * m * J * d, false},
         {reinterpret_cast<void **>(&mb.spot), &mb.spot_bytes, 2 * m * J * d, false},
         {reinterpret_cast<void **>(&mb.sums), &mb.sums_bytes, sums, false},
-        {&mb.ws, &mb.ws_bytes, payoff_sets_workspace_bytes(n, K, static_cast<int>(J)), false},
+        {&mb.ws, &mb.ws_bytes, ws, false},
         {&mb.table_dev, &mb.table_bytes, many_table_bytes(static_cast<int>(J), static_cast<int>(m)), false},
         {&mb.table_host, &mb.table_host_bytes, many_table_bytes(static_cast<int>(J), static_cast<int>(m)), true},
         {reinterpret_cast<void **>(&mb.sums_pinned), &mb.sums_pinned_bytes, sums, true},
@@ -1043,19 +1045,19 @@ static int grow_many(const char *fn, ManyBuffers &mb, size_t n, size_t J, size_t
     return SVMC_OK;
 }
 
-// The driver of both models: the checks (all before any device work), the per-job workspace, step(nbs, dts, qsnap) -- the model's
-// ONE stepping launch of every job into the ManyBuffers -- then the jobs' spot sums (one column reduce), ONE payoff launch and ONE
-// finish launch for all jobs (a payoff launch per job where the chain does not fit one), and the host finalisation per job.
-template <class Step>
-static int chain_price_many(const char *fn, svmc_session_t session, const ChainView &c, int n_jobs, const void *params,
-                            const uint64_t *seeds, const uint32_t *call_ids, int nb_steps_per_year, int variable_type, double *prices,
-                            double *stderrs, Step &&step)
+// The first half of every many-job driver: the checks (all before any device work; check(): the model's own, once the shared
+// ones have found every pointer and size in order), the per-job workspace, then step(nbs, dts, qsnap) -- the model's ONE
+// stepping launch of every job into the ManyBuffers -- and the jobs' spot sums (one column reduce).  `shifts` gets the chain's
+// payoff shifts.
+template <class Check, class Step>
+static int many_step(const char *fn, Session *s, const ChainView &c, int n_jobs, const void *params, const uint64_t *seeds,
+                     const uint32_t *call_ids, int nb_steps_per_year, int variable_type, const double *prices, const double *stderrs,
+                     bool needs_discfactors, size_t min_ws_bytes, std::vector<double> &shifts, Check &&check, Step &&step)
 {
-    Session *s = reinterpret_cast<Session *>(session);
     SVMC_REQUIRE(s != nullptr, std::string(fn) + ": null session");
     SVMC_REQUIRE(n_jobs >= 1 && n_jobs <= SVMC_MANY_MAX_JOBS, std::string(fn) + ": n_jobs must be in [1, SVMC_MANY_MAX_JOBS]");
-    SVMC_REQUIRE(params && seeds && call_ids && c.ttms && c.forwards && c.discfactors && c.strikes && c.types && c.offsets && prices &&
-                     stderrs,
+    SVMC_REQUIRE(params && seeds && call_ids && c.ttms && c.forwards && (c.discfactors || !needs_discfactors) && c.strikes && c.types &&
+                     c.offsets && prices && stderrs,
                  std::string(fn) + ": null pointer");
     SVMC_REQUIRE(c.m >= 1 && c.m <= MAX_FUSED_SLICES, std::string(fn) + ": 1 to 16 expiries");
     if (c.m > s->max_expiries || c.offsets[c.m] > s->max_strikes)
@@ -1063,20 +1065,39 @@ static int chain_price_many(const char *fn, svmc_session_t session, const ChainV
     SVMC_REQUIRE(!s->sharded(), std::string(fn) + ": no sharded batch: detach the communicator / reducer");
     SVMC_REQUIRE(nb_steps_per_year > 0, std::string(fn) + ": nb_steps_per_year must be positive");
     for (int j = 0; j < n_jobs; ++j) SVMC_REQUIRE(call_ids[j] < (1u << 24), std::string(fn) + ": call_id must fit 24 bits");
-    if (int rc = check_chain(fn, s, c, variable_type, prices, stderrs)) return rc;
+    if (int rc = check()) return rc;
+    if (int rc = check_chain(fn, s, c, variable_type, prices, stderrs, needs_discfactors)) return rc;
     const size_t n = s->n_path, J = static_cast<size_t>(n_jobs), m = static_cast<size_t>(c.m), K = c.offsets[c.m];
     const bool need_q = variable_type == SVMC_Q_VAR;
     ManyBuffers &mb = s->many;
-    if (int rc = grow_many(fn, mb, n, J, m, K, need_q)) return rc;
+    if (int rc = grow_many(fn, mb, n, J, m, K, need_q, min_ws_bytes)) return rc;
     std::vector<int> nbs;
-    std::vector<double> dts, shifts;
+    std::vector<double> dts;
     expiry_grids(c, nb_steps_per_year, nbs, dts);
     payoff_shifts_of(c, variable_type, shifts);
-    double *qsnap = need_q ? mb.snap + J * m * n : nullptr;
     stepping_begin(s);
-    if (int rc = step(nbs, dts, qsnap)) return rc;
+    if (int rc = step(nbs, dts, need_q ? mb.snap + J * m * n : nullptr)) return rc;
     if (int rc = reduce_spot_partials(mb.spot_ws, n, static_cast<int>(2 * m * J), mb.spot, s->stream)) return rc;
     stepping_end(s);
+    return SVMC_OK;
+}
+
+// The driver of the plain many-job calls: many_step, then ONE payoff launch and ONE finish launch for all jobs (a payoff launch
+// per job where the chain does not fit one), and the host finalisation per job.
+template <class Check, class Step>
+static int chain_price_many(const char *fn, svmc_session_t session, const ChainView &c, int n_jobs, const void *params,
+                            const uint64_t *seeds, const uint32_t *call_ids, int nb_steps_per_year, int variable_type, double *prices,
+                            double *stderrs, Check &&check, Step &&step)
+{
+    Session *s = reinterpret_cast<Session *>(session);
+    std::vector<double> shifts;
+    if (int rc = many_step(fn, s, c, n_jobs, params, seeds, call_ids, nb_steps_per_year, variable_type, prices, stderrs, true, 0, shifts,
+                           check, step))
+        return rc;
+    const size_t n = s->n_path, J = static_cast<size_t>(n_jobs), m = static_cast<size_t>(c.m), K = c.offsets[c.m];
+    const bool need_q = variable_type == SVMC_Q_VAR;
+    ManyBuffers &mb = s->many;
+    double *qsnap = need_q ? mb.snap + J * m * n : nullptr;
     std::vector<const double *> xs(m), qs(m);
     for (size_t i = 0; i < m; ++i) {
         xs[i] = mb.snap + i * n;
@@ -1118,7 +1139,7 @@ int svmc_logsv_chain_price_many(svmc_session_t session, const double *ttms_host,
     const ChainView c = {n_expiries, ttms_host, forwards_host, discfactors_host, strikes_host, types_host, strike_offsets_host};
     Session *s = reinterpret_cast<Session *>(session);
     return chain_price_many("svmc_logsv_chain_price_many", session, c, n_jobs, params_host, seeds_host, call_ids_host, nb_steps_per_year,
-                            variable_type, prices_host, stderrs_host,
+                            variable_type, prices_host, stderrs_host, [] { return SVMC_OK; },
                             [&](const std::vector<int> &nbs, const std::vector<double> &dts, double *qsnap) {
         ManyBuffers &mb = s->many;
         return logsv_chain_rng_many(s->n_path, n_jobs, c.m, nbs.data(), dts.data(), c.forwards, params_host, is_spot_measure, seeds_host,
@@ -1136,12 +1157,106 @@ int svmc_heston_chain_price_many(svmc_session_t session, const double *ttms_host
     Session *s = reinterpret_cast<Session *>(session);
     SVMC_REQUIRE(scheme == SVMC_HESTON_EULER_FLOOR || scheme == SVMC_HESTON_QE, "svmc_heston_chain_price_many: unknown scheme");
     return chain_price_many("svmc_heston_chain_price_many", session, c, n_jobs, params_host, seeds_host, call_ids_host,
-                            nb_steps_per_year, variable_type, prices_host, stderrs_host,
+                            nb_steps_per_year, variable_type, prices_host, stderrs_host, [] { return SVMC_OK; },
                             [&](const std::vector<int> &nbs, const std::vector<double> &dts, double *qsnap) {
         ManyBuffers &mb = s->many;
         return heston_chain_rng_many(s->n_path, n_jobs, c.m, nbs.data(), dts.data(), c.forwards, params_host, scheme, seeds_host,
                                      call_ids_host, s->path_offset, mb.table_host, mb.table_dev, mb.snap, qsnap, mb.spot_ws, s->stream);
     });
+}
+
+int svmc_hawkesjd_chain_price_many(svmc_session_t session, const double *ttms_host, const double *forwards_host,
+                                   const double *discfactors_host, int n_expiries, const double *strikes_host, const int8_t *types_host,
+                                   const size_t *strike_offsets_host, int n_jobs, const double *params_host, const uint64_t *seeds_host,
+                                   const uint32_t *call_ids_host, int nb_steps_per_year, int variable_type, double *prices_host,
+                                   double *stderrs_host)
+{
+    const char *fn = "svmc_hawkesjd_chain_price_many";
+    const ChainView c = {n_expiries, ttms_host, forwards_host, discfactors_host, strikes_host, types_host, strike_offsets_host};
+    Session *s = reinterpret_cast<Session *>(session);
+    return chain_price_many(fn, session, c, n_jobs, params_host, seeds_host, call_ids_host, nb_steps_per_year, variable_type, prices_host,
+                            stderrs_host,
+                            [&]() -> int {
+        if (variable_type != SVMC_LOG_RETURN)  // the reference would price the log-return as a variance (:701-707)
+            return fail(SVMC_ERR_UNSUPPORTED_VARIABLE, std::string(fn) + ": LOG_RETURN only");
+        return hawkes_check_many(fn, n_jobs, params_host);
+    },
+                            [&](const std::vector<int> &nbs, const std::vector<double> &dts, double *) {
+        ManyBuffers &mb = s->many;
+        return hawkes_chain_rng_many(s->n_path, n_jobs, c.m, nbs.data(), dts.data(), c.forwards, params_host, seeds_host, call_ids_host,
+                                     s->path_offset, mb.table_host, mb.table_dev, mb.snap, mb.spot_ws, s->stream);
+    });
+}
+
+int svmc_hawkesjd_chain_price_tilted_many(svmc_session_t session, const double *ttms_host, const double *forwards_host, int n_expiries,
+                                          const double *strikes_host, const int8_t *types_host, const size_t *strike_offsets_host,
+                                          int n_jobs, const double *params_host, const uint64_t *seeds_host,
+                                          const uint32_t *call_ids_host, int nb_steps_per_year, const double *gammas_host, int n_gammas,
+                                          int recenter, double *prices_host, double *stderrs_host, double *stats_host)
+{
+    const char *fn = "svmc_hawkesjd_chain_price_tilted_many";
+    const ChainView c = {n_expiries, ttms_host, forwards_host, nullptr, strikes_host, types_host, strike_offsets_host};
+    Session *s = reinterpret_cast<Session *>(session);
+    size_t need_ws = 0;
+    if (int rc = svmc_payoff_workspace_bytes(&need_ws)) return rc;
+    std::vector<double> shifts;
+    if (int rc = many_step(fn, s, c, n_jobs, params_host, seeds_host, call_ids_host, nb_steps_per_year, SVMC_LOG_RETURN, prices_host,
+                           stderrs_host, false, need_ws, shifts,
+                           [&]() -> int {
+        // svmc_hawkesjd_chain_price_tilted's checks, for every job
+        SVMC_REQUIRE(gammas_host != nullptr && stats_host != nullptr, std::string(fn) + ": null pointer");
+        SVMC_REQUIRE(n_gammas >= 1 && n_gammas <= SVMC_TILTED_MAX_GAMMAS, std::string(fn) + ": n_gammas outside 1 .. SVMC_TILTED_MAX_GAMMAS");
+        for (size_t g = 0; g < static_cast<size_t>(n_jobs) * n_gammas; ++g)
+            SVMC_REQUIRE(std::isfinite(gammas_host[g]), std::string(fn) + ": a gamma is not finite");
+        for (int i = 0; i < c.m; ++i) {
+            SVMC_REQUIRE(std::isfinite(c.forwards[i]), std::string(fn) + ": a forward is not finite");
+            SVMC_REQUIRE(c.offsets[i] <= c.offsets[i + 1], std::string(fn) + ": strike offsets must not decrease");
+        }
+        for (size_t k = 0; k < c.offsets[c.m]; ++k) {
+            if (c.types[k] != SVMC_CALL && c.types[k] != SVMC_PUT) return fail(SVMC_ERR_UNKNOWN_PAYOFF, "unknown option payoff code");
+            SVMC_REQUIRE(std::isfinite(c.strikes[k]), std::string(fn) + ": a strike is not finite");
+        }
+        if (int rc = hawkes_check_many(fn, n_jobs, params_host)) return rc;
+        // the pinned landing buffer of every job's prices, errors and statistics, grown as the single call grows it
+        const size_t G = static_cast<size_t>(n_gammas);
+        const size_t out_bytes = static_cast<size_t>(n_jobs) * (2 * G * c.offsets[c.m] + G * c.m * SVMC_TILTED_STATS_DOUBLES) * sizeof(double);
+        if (s->tilted_pinned_bytes < out_bytes) {
+            if (s->tilted_pinned != nullptr) (void)hipHostFree(s->tilted_pinned);
+            s->tilted_pinned = nullptr;
+            s->tilted_pinned_bytes = 0;
+            SVMC_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&s->tilted_pinned), out_bytes, hipHostMallocDefault));
+            s->tilted_pinned_bytes = out_bytes;
+        }
+        return SVMC_OK;
+    },
+                           [&](const std::vector<int> &nbs, const std::vector<double> &dts, double *) {
+        ManyBuffers &mb = s->many;
+        return hawkes_chain_rng_many(s->n_path, n_jobs, c.m, nbs.data(), dts.data(), c.forwards, params_host, seeds_host, call_ids_host,
+                                     s->path_offset, mb.table_host, mb.table_dev, mb.snap, mb.spot_ws, s->stream);
+    }))
+        return rc;
+    ManyBuffers &mb = s->many;
+    const size_t n = s->n_path, J = static_cast<size_t>(n_jobs), m = static_cast<size_t>(c.m), K = c.offsets[c.m];
+    const size_t G = static_cast<size_t>(n_gammas), n_stats = G * m * SVMC_TILTED_STATS_DOUBLES, per_job = 2 * G * K + n_stats;
+    // per job the tilted launches of the single call on that job's snapshot rows (and, recentring, its rows of the spot sums)
+    std::vector<const double *> xs(m);
+    for (size_t j = 0; j < J; ++j) {
+        for (size_t i = 0; i < m; ++i) xs[i] = mb.snap + (j * m + i) * n;
+        double *prices = s->tilted_pinned + j * per_job, *stderrs = prices + G * K, *stats = stderrs + G * K;
+        if (int rc = svmc_tilted_payoff_chain(xs.data(), n, c.forwards, c.m, c.strikes, c.types, shifts.data(), c.offsets,
+                                              gammas_host + j * G, n_gammas, recenter, recenter ? mb.spot + 2 * m * j : nullptr, prices,
+                                              stderrs, stats, mb.ws, mb.ws_bytes, reinterpret_cast<svmc_stream_t>(s->stream)))
+            return rc;
+    }
+    SVMC_HIP_TRY(hipStreamSynchronize(s->stream));
+    stepping_read(s);
+    for (size_t j = 0; j < J; ++j) {
+        const double *prices = s->tilted_pinned + j * per_job, *stderrs = prices + G * K, *stats = stderrs + G * K;
+        memcpy(prices_host + j * G * K, prices, G * K * sizeof(double));
+        memcpy(stderrs_host + j * G * K, stderrs, G * K * sizeof(double));
+        memcpy(stats_host + j * n_stats, stats, n_stats * sizeof(double));
+    }
+    return SVMC_OK;
 }
 
 int svmc_session_state(svmc_session_t session, double *x_host, double *vol_host, double *qvar_host)

@@ -5,6 +5,9 @@
 //                              one launch: the step of simulate_hawkesjd_terminal (:715-779) in its order, the slice epilogue of
 //                              svmc_slice.h per expiry (snapshot + per-wave spot partials for the chain payoff tail)
 //   hawkesjd_rng_kernel        the same body for one slice on caller-owned state (simulate_hawkesjd_terminal)
+//   hawkesjd_chain_rng_many_kernel  the same body for J independent jobs of one chain (blockIdx.y = job): each job's model, start
+//                              intensities, step constants and Philox key from a device table, its expiries to snapshot rows
+//                              j m + i; job j's bits are those of hawkesjd_chain_rng_kernel on its parameters and stream
 //   hawkes_mgf_grid_batch_kernel  one lane per transform-grid point of up to 16 parameter sets per launch (blockIdx.y = set;
 //                              one set, or the base point and bumped vectors of a calibration's finite-difference gradient):
 //                              the three complex Riccati ODEs of solve_ode_for_a (:582-640) with the DOP853 pair of
@@ -109,18 +112,47 @@ __device__ __forceinline__ void hawkes_step(const HawkesModel &md, const HawkesS
     lm = (lm + c.kappa_m_dt * (md.theta_m - lm)) + load_m;
 }
 
-// x_snap / partials null: a single slice on caller-owned state (no epilogue)
-__device__ __forceinline__ void hawkes_body(double *__restrict__ x, double *__restrict__ lam_p, double *__restrict__ lam_m, size_t n,
-                                            const HawkesChainSlices &cs, const HawkesModel &md, uint64_t seed, uint32_t c3,
-                                            uint64_t path_offset, uint32_t step_offset, double *__restrict__ x_snap,
-                                            double *__restrict__ partials, const StateInit &init)
-{
-    __shared__ RngTablesLds s_tab;
-    const RngTables tab = stage_rng_tables(s_tab);
-    const size_t p = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-    const bool active = p < n;
-    double xv = 0.0, lp = 0.0, lm = 0.0;
-    if (active) {
+// ---- many independent jobs of one chain in ONE stepping launch (svmc_hawkesjd_chain_price_many): blockIdx.y = job,
+// blockIdx.x = block of that job's n paths.  The per-job device table, one upload per call: [J] HawkesJob, then the
+// (job, expiry) step constants [J][m].
+struct HawkesJob {
+    HawkesModel md;
+    double lambda_p, lambda_m;             // both start intensities
+    uint64_t seed;
+    uint32_t c3, pad;                      // the call id's counter word
+};
+struct HawkesManySlices {
+    double forward[HAWKES_MAX_SLICES];
+    int nb_steps[HAWKES_MAX_SLICES];
+    int m;
+};
+
+// Where hawkes_body's job comes from (as ChainArgs / ManyTable of svmc_kernels.hip).  The body is written once over a job source
+// and runs the same statements -- hence gives the same bits -- whichever one hands it the job:
+//   HawkesArgs   the one-job kernels: everything is a kernel argument; the path starts from `init` or the state arrays at step
+//                `step_offset` of its streams, expiry i goes to row i, and the terminal state is written back
+//   HawkesTable  the many-job kernel: job blockIdx.y of the device table; the path starts from (0, lambda_p_j, lambda_m_j) at
+//                step 0, expiry i goes to row j m + i, nothing is written back.  The job's constants are job-uniform and the
+//                table is read-only for the launch (__restrict__ const): the compiler issues these plain loads as scalar loads
+struct HawkesArgs {
+    const HawkesChainSlices &cs;
+    const HawkesModel &md;
+    uint64_t seed_;
+    uint32_t c3_, step_offset;
+    const StateInit &init;
+    double *__restrict__ x, *__restrict__ lam_p, *__restrict__ lam_m;
+
+    __device__ __forceinline__ int m() const { return cs.m; }
+    __device__ __forceinline__ int nb_steps(int i) const { return cs.nb_steps[i]; }
+    __device__ __forceinline__ double forward(int i) const { return cs.forward[i]; }
+    __device__ __forceinline__ HawkesStep step(int i) const { return cs.c[i]; }
+    __device__ __forceinline__ HawkesModel model() const { return md; }
+    __device__ __forceinline__ uint64_t seed() const { return seed_; }
+    __device__ __forceinline__ uint32_t c3() const { return c3_; }
+    __device__ __forceinline__ uint32_t step_origin() const { return step_offset; }
+    __device__ __forceinline__ size_t row(int i) const { return static_cast<size_t>(i); }
+    __device__ __forceinline__ void start(size_t p, double &xv, double &lp, double &lm) const
+    {
         if (init.uniform) {                                    // wave-uniform
             xv = init.x0;
             lp = init.vol0;
@@ -131,28 +163,68 @@ __device__ __forceinline__ void hawkes_body(double *__restrict__ x, double *__re
             lm = lam_m[p];
         }
     }
-    const PhiloxLane lane = philox_prepare(seed, c3 | HAWKES_STREAM, path_offset + p);
-    const PhiloxLane lane_j = philox_prepare(seed, c3 | HAWKES_JUMP_STREAM, path_offset + p);
-    uint32_t step = step_offset;
-    for (int i = 0; i < cs.m; ++i) {
-        const uint32_t end = step + static_cast<uint32_t>(cs.nb_steps[i]);
-        if (active) {
-            const HawkesStep c = cs.c[i];
-            for (uint32_t s = step; s < end; ++s) hawkes_step(md, c, lane, lane_j, s, tab, xv, lp, lm);
-        }
-        step = end;
-        if (x_snap != nullptr) {
-            const size_t rows = (n + 63) >> 6;
-            const SliceOut so = {x_snap + static_cast<size_t>(i) * n, nullptr, partials + 2 * static_cast<size_t>(i) * rows,
-                                 cs.forward[i], rows};
-            slice_epilogue(so, p, active, xv, 0.0);
-        }
-    }
-    if (active) {
+    __device__ __forceinline__ void finish(size_t p, double xv, double lp, double lm) const
+    {
         x[p] = xv;
         lam_p[p] = lp;
         lam_m[p] = lm;
     }
+};
+
+struct HawkesTable {
+    const HawkesManySlices &cs;
+    const HawkesJob *__restrict__ jobs;
+    const HawkesStep *__restrict__ steps;
+
+    __device__ __forceinline__ int job() const { return blockIdx.y; }
+    __device__ __forceinline__ int m() const { return cs.m; }
+    __device__ __forceinline__ int nb_steps(int i) const { return cs.nb_steps[i]; }
+    __device__ __forceinline__ double forward(int i) const { return cs.forward[i]; }
+    __device__ __forceinline__ HawkesStep step(int i) const { return steps[static_cast<size_t>(job()) * cs.m + i]; }
+    __device__ __forceinline__ HawkesModel model() const { return jobs[job()].md; }
+    __device__ __forceinline__ uint64_t seed() const { return jobs[job()].seed; }
+    __device__ __forceinline__ uint32_t c3() const { return jobs[job()].c3; }
+    __device__ __forceinline__ uint32_t step_origin() const { return 0u; }
+    __device__ __forceinline__ size_t row(int i) const { return static_cast<size_t>(job()) * cs.m + i; }
+    __device__ __forceinline__ void start(size_t, double &xv, double &lp, double &lm) const
+    {
+        xv = 0.0;
+        lp = jobs[job()].lambda_p;
+        lm = jobs[job()].lambda_m;
+    }
+    __device__ __forceinline__ void finish(size_t, double, double, double) const {}
+};
+
+// x_snap / partials null: a single slice on caller-owned state (no epilogue)
+template <class Source>
+__device__ __forceinline__ void hawkes_body(size_t n, const Source &src, uint64_t path_offset, double *__restrict__ x_snap,
+                                            double *__restrict__ partials)
+{
+    __shared__ RngTablesLds s_tab;
+    const RngTables tab = stage_rng_tables(s_tab);
+    const size_t p = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    const bool active = p < n;
+    const HawkesModel md = src.model();
+    double xv = 0.0, lp = 0.0, lm = 0.0;
+    if (active) src.start(p, xv, lp, lm);
+    const PhiloxLane lane = philox_prepare(src.seed(), src.c3() | HAWKES_STREAM, path_offset + p);
+    const PhiloxLane lane_j = philox_prepare(src.seed(), src.c3() | HAWKES_JUMP_STREAM, path_offset + p);
+    uint32_t step = src.step_origin();
+    const int m = src.m();
+    for (int i = 0; i < m; ++i) {
+        const uint32_t end = step + static_cast<uint32_t>(src.nb_steps(i));
+        if (active) {
+            const HawkesStep c = src.step(i);
+            for (uint32_t s = step; s < end; ++s) hawkes_step(md, c, lane, lane_j, s, tab, xv, lp, lm);
+        }
+        step = end;
+        if (x_snap != nullptr) {
+            const size_t rows = (n + 63) >> 6, row = src.row(i);
+            const SliceOut so = {x_snap + row * n, nullptr, partials + 2 * row * rows, src.forward(i), rows};
+            slice_epilogue(so, p, active, xv, 0.0);
+        }
+    }
+    if (active) src.finish(p, xv, lp, lm);
 }
 
 __global__ __launch_bounds__(HAWKES_BLOCK) void hawkesjd_chain_rng_kernel(double *__restrict__ x, double *__restrict__ lam_p,
@@ -162,7 +234,7 @@ __global__ __launch_bounds__(HAWKES_BLOCK) void hawkesjd_chain_rng_kernel(double
                                                                          double *__restrict__ x_snap, double *__restrict__ partials,
                                                                          StateInit init)
 {
-    hawkes_body(x, lam_p, lam_m, n, cs, md, seed, c3, path_offset, step_offset, x_snap, partials, init);
+    hawkes_body(n, HawkesArgs{cs, md, seed, c3, step_offset, init, x, lam_p, lam_m}, path_offset, x_snap, partials);
 }
 
 __global__ __launch_bounds__(HAWKES_BLOCK) void hawkesjd_rng_kernel(double *__restrict__ x, double *__restrict__ lam_p,
@@ -170,7 +242,17 @@ __global__ __launch_bounds__(HAWKES_BLOCK) void hawkesjd_rng_kernel(double *__re
                                                                    HawkesModel md, uint64_t seed, uint32_t c3, uint64_t path_offset,
                                                                    uint32_t step_offset)
 {
-    hawkes_body(x, lam_p, lam_m, n, cs, md, seed, c3, path_offset, step_offset, nullptr, nullptr, StateInit());
+    const StateInit init;
+    hawkes_body(n, HawkesArgs{cs, md, seed, c3, step_offset, init, x, lam_p, lam_m}, path_offset, nullptr, nullptr);
+}
+
+__global__ __launch_bounds__(HAWKES_BLOCK) void hawkesjd_chain_rng_many_kernel(size_t n, HawkesManySlices cs,
+                                                                              const HawkesJob *__restrict__ jobs,
+                                                                              const HawkesStep *__restrict__ steps,
+                                                                              uint64_t path_offset, double *__restrict__ x_snap,
+                                                                              double *__restrict__ partials)
+{
+    hawkes_body(n, HawkesTable{cs, jobs, steps}, path_offset, x_snap, partials);
 }
 
 int check_params(const char *fn, const double *p)
@@ -466,6 +548,61 @@ int hawkes_step_partials(const double *params_host, double *x, double *lam_p, do
     };
     return step_chain<HawkesChainSlices>(fn, init, x, lam_p, lam_m, n_path, n_slices, nb_steps_host, dts_host, forwards_host, call_id,
                                          0, x_snapshots, nullptr, spot_sums, workspace, workspace_bytes, stream, fill, launch);
+}
+
+// ---- many jobs of one chain (svmc_chain.hip's svmc_hawkesjd_chain_price_many / _tilted_many)
+
+size_t hawkes_many_table_bytes(int n_jobs, int n_slices)
+{
+    const size_t J = static_cast<size_t>(n_jobs);
+    return J * sizeof(HawkesJob) + J * static_cast<size_t>(n_slices) * sizeof(HawkesStep);
+}
+
+// every job's parameter block, before anything is launched
+int hawkes_check_many(const char *fn, int n_jobs, const double *params_host)
+{
+    for (int j = 0; j < n_jobs; ++j)
+        if (int rc = check_params((std::string(fn) + " job " + std::to_string(j)).c_str(),
+                                  params_host + static_cast<size_t>(SVMC_HAWKESJD_PARAMS) * j))
+            return rc;
+    return SVMC_OK;
+}
+
+int hawkes_chain_rng_many(size_t n_path, int n_jobs, int n_slices, const int *nb_steps_host, const double *dts_host,
+                          const double *forwards_host, const double *params_host, const uint64_t *seeds, const uint32_t *call_ids,
+                          uint64_t path_offset, void *table_host, void *table_dev, double *x_snapshots, double *spot_partials,
+                          hipStream_t stream)
+{
+    const char *fn = "hawkes_chain_rng_many";
+    SVMC_REQUIRE(n_path > 0 && n_jobs >= 1 && n_jobs <= SVMC_MANY_MAX_JOBS && n_slices >= 1 && n_slices <= HAWKES_MAX_SLICES,
+                 std::string(fn) + ": bad sizes");
+    SVMC_REQUIRE(nb_steps_host && dts_host && forwards_host && params_host && seeds && call_ids && table_host && table_dev &&
+                     x_snapshots && spot_partials,
+                 std::string(fn) + ": null pointer");
+    for (int i = 0; i < n_slices; ++i)
+        SVMC_REQUIRE(nb_steps_host[i] > 0 && dts_host[i] > 0.0, std::string(fn) + ": nb_steps and dt must be positive");
+    for (int j = 0; j < n_jobs; ++j) SVMC_REQUIRE(call_ids[j] < (1u << 24), std::string(fn) + ": call_id must fit 24 bits");
+    if (int rc = hawkes_check_many(fn, n_jobs, params_host)) return rc;
+    // the pinned table in the device table's byte layout: [J] jobs, then [J][m] step constants
+    HawkesJob *jobs = static_cast<HawkesJob *>(table_host);
+    HawkesStep *steps = reinterpret_cast<HawkesStep *>(jobs + n_jobs);
+    for (int j = 0; j < n_jobs; ++j) {
+        const double *p = params_host + static_cast<size_t>(SVMC_HAWKESJD_PARAMS) * j;
+        jobs[j] = HawkesJob{make_hawkes_model(p), p[P_LAMBDA_P], p[P_LAMBDA_M], seeds[j], call_ids[j] << 8, 0u};      // :672-674
+        for (int i = 0; i < n_slices; ++i) steps[static_cast<size_t>(j) * n_slices + i] = make_hawkes_step(dts_host[i], p);
+    }
+    SVMC_HIP_TRY(hipMemcpyAsync(table_dev, table_host, hawkes_many_table_bytes(n_jobs, n_slices), hipMemcpyHostToDevice, stream));
+    HawkesManySlices cs;
+    cs.m = n_slices;
+    for (int i = 0; i < HAWKES_MAX_SLICES; ++i) {
+        cs.forward[i] = forwards_host[i < n_slices ? i : 0];
+        cs.nb_steps[i] = i < n_slices ? nb_steps_host[i] : 0;
+    }
+    const HawkesJob *jobs_dev = static_cast<const HawkesJob *>(table_dev);
+    hipLaunchKernelGGL(hawkesjd_chain_rng_many_kernel, dim3(hawkes_grid(n_path), static_cast<unsigned>(n_jobs)), dim3(HAWKES_BLOCK), 0,
+                       stream, n_path, cs, jobs_dev, reinterpret_cast<const HawkesStep *>(jobs_dev + n_jobs), path_offset, x_snapshots,
+                       spot_partials);
+    return check_launch(fn);
 }
 
 }  // namespace svmc

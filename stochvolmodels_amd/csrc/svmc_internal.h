@@ -95,6 +95,14 @@ int heston_chain_rng_many(size_t n_path, int n_jobs, int n_slices, const int *nb
                           const double *forwards_host, const double *params_host, int scheme, const uint64_t *seeds,
                           const uint32_t *call_ids, uint64_t path_offset, void *table_host, void *table_dev, double *x_snapshots,
                           double *qvar_snapshots, double *spot_partials, hipStream_t stream);
+// svmc_hawkes.hip: the Hawkes jobs (params_host [n_jobs][SVMC_HAWKESJD_PARAMS], no qvar rows); hawkes_many_table_bytes is its share
+// of many_table_bytes, hawkes_check_many the parameter checks of every job (made before anything is launched)
+size_t hawkes_many_table_bytes(int n_jobs, int n_slices);
+int hawkes_check_many(const char *fn, int n_jobs, const double *params_host);
+int hawkes_chain_rng_many(size_t n_path, int n_jobs, int n_slices, const int *nb_steps_host, const double *dts_host,
+                          const double *forwards_host, const double *params_host, const uint64_t *seeds, const uint32_t *call_ids,
+                          uint64_t path_offset, void *table_host, void *table_dev, double *x_snapshots, double *spot_partials,
+                          hipStream_t stream);
 size_t payoff_sets_workspace_bytes(size_t n_path, size_t total_strikes, int n_sets);
 int chain_payoff_and_finish_sets(const double *const *x_snapshots_host, const double *const *qvar_snapshots_host, size_t n_path,
                                  const double *forwards_host, const double *ttms_host, const double *spot_sums, int n_expiries,

@@ -3474,7 +3474,8 @@ int reduce_spot_partials(const void *workspace, size_t n_path, int n_cols, doubl
 
 // ---- many jobs of one chain (svmc_chain.hip's svmc_*_chain_price_many)
 
-// the job table of n_jobs jobs of n_slices expiries: [J][m] constants, [J] start vols, [J] seeds, [J] counter words
+// the job table of n_jobs jobs of n_slices expiries: [J][m] constants, [J] start vols, [J] seeds, [J] counter words -- or the
+// Hawkes table of svmc_hawkes.hip, whichever is larger (one pinned and one device buffer serve every model)
 static size_t many_consts_bytes()
 {
     return sizeof(HestonManyConsts) > sizeof(LogsvFast) ? sizeof(HestonManyConsts) : sizeof(LogsvFast);
@@ -3482,7 +3483,9 @@ static size_t many_consts_bytes()
 size_t many_table_bytes(int n_jobs, int n_slices)
 {
     const size_t J = static_cast<size_t>(n_jobs);
-    return J * static_cast<size_t>(n_slices) * many_consts_bytes() + J * (sizeof(double) + sizeof(uint64_t) + sizeof(uint32_t));
+    const size_t here = J * static_cast<size_t>(n_slices) * many_consts_bytes() + J * (sizeof(double) + sizeof(uint64_t) + sizeof(uint32_t));
+    const size_t hawkes = hawkes_many_table_bytes(n_jobs, n_slices);
+    return here > hawkes ? here : hawkes;
 }
 
 // fills the pinned table_host (the table's byte layout, constants of CONSTS each), queues its upload and returns the device view

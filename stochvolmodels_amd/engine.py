@@ -617,9 +617,12 @@ class HipEngine:
 
     def price_chain_many_fused(self, ch: dict, model: str, params: np.ndarray, seeds: Sequence[int], call_ids: Sequence[int],
                                mode: int, nb_steps_per_year: int, variable_type: int):
-        """J jobs of one chain as ONE svmc_logsv_chain_price_many (model "logsv", mode = is_spot_measure, params [J][6 + m]) or
-        svmc_heston_chain_price_many ("heston", mode = scheme code, params [J][5]) call on this engine's session, J at most
-        MANY_MAX_JOBS: per job the (prices, stderrs) of the single fused call with its (seed, call id), cut into expiries"""
+        """J jobs of one chain as ONE svmc_logsv_chain_price_many (model "logsv", mode = is_spot_measure, params [J][6 + m]),
+        svmc_heston_chain_price_many ("heston", mode = scheme code, params [J][5]) or svmc_hawkesjd_chain_price_many ("hawkesjd",
+        mode unused, params [J][SVMC_HAWKESJD_PARAMS]) call on this engine's session, J at most MANY_MAX_JOBS: per job the
+        (prices, stderrs) of the single fused call with its (seed, call id), cut into expiries"""
+        if model not in ("logsv", "heston", "hawkesjd"):
+            raise ValueError(f"price_chain_many_fused: unknown model {model!r}")
         params = np.ascontiguousarray(params, dtype=np.float64)
         n_jobs = params.shape[0]
         seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
@@ -629,10 +632,12 @@ class HipEngine:
         sess = self.fused_chain_session(ch["m"], ch["total"])
         res = np.empty((2, n_jobs, max(ch["total"], 1)))
         dp = C.POINTER(C.c_double)
-        fn = self.lib.svmc_logsv_chain_price_many if model == "logsv" else self.lib.svmc_heston_chain_price_many
+        fn = {"logsv": self.lib.svmc_logsv_chain_price_many, "heston": self.lib.svmc_heston_chain_price_many,
+              "hawkesjd": self.lib.svmc_hawkesjd_chain_price_many}[model]
+        modes = () if model == "hawkesjd" else (int(mode),)
         _lib.check(fn(sess, ch["ttms"], ch["forwards"], ch["discfactors"], ch["m"], ch["strikes"], ch["codes"], ch["offsets"], n_jobs,
                       params.ctypes.data_as(dp), seeds.ctypes.data_as(C.POINTER(C.c_uint64)),
-                      ids.ctypes.data_as(C.POINTER(C.c_uint32)), int(mode), int(nb_steps_per_year), int(variable_type),
+                      ids.ctypes.data_as(C.POINTER(C.c_uint32)), *modes, int(nb_steps_per_year), int(variable_type),
                       C.cast(res.ctypes.data, dp), C.cast(res.ctypes.data + res.strides[0], dp)))
         return [([res[0, j, sl] for sl in ch["slices"]], [res[1, j, sl] for sl in ch["slices"]]) for j in range(n_jobs)]
 
@@ -1004,6 +1009,37 @@ class HipEngine:
             int(nb_steps_per_year), int(seed), int(call_id), ch["gammas"].ctypes.data_as(dp), G, int(bool(recenter)),
             prices.ctypes.data_as(dp), stderrs.ctypes.data_as(dp), stats.ctypes.data_as(dp)), "hawkesjd_chain_rng_kernel")
         return tilted_results(prices[:G * K], stderrs[:G * K], stats, ch)
+
+    def price_hawkesjd_chain_tilted_many_fused(self, ch: dict, params: np.ndarray, nb_steps_per_year: int, seeds: Sequence[int],
+                                               call_ids: Sequence[int], gammas: np.ndarray, recenter: bool):
+        """J Hawkes jobs of one chain under the risk-premia kernel as ONE svmc_hawkesjd_chain_price_tilted_many call on this
+        engine's session (ch: tilted_chain_arrays; params [J][SVMC_HAWKESJD_PARAMS]; gammas [J][G], every row a job's gammas):
+        one stepping launch for all jobs, then each job's tilted payoff launches.  Returns per job what
+        price_hawkesjd_chain_tilted_fused returns for it, J at most MANY_MAX_JOBS"""
+        params = np.ascontiguousarray(params, dtype=np.float64)
+        gammas = np.ascontiguousarray(gammas, dtype=np.float64)
+        n_jobs = params.shape[0]
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
+        ids = np.ascontiguousarray(call_ids, dtype=np.uint32)
+        if not (seeds.size == ids.size == n_jobs) or gammas.ndim != 2 or gammas.shape[0] != n_jobs:
+            raise ValueError("one seed, one call id and one row of gammas per job")
+        m, K, G = ch["m"], ch["total"], gammas.shape[1]
+        dp = C.POINTER(C.c_double)
+        prices, stderrs = np.empty((n_jobs, max(G * K, 1))), np.empty((n_jobs, max(G * K, 1)))
+        stats = np.empty((n_jobs, G * m * TILTED_STATS_DOUBLES))
+        sess = self.fused_chain_session(m, K)
+        _lib.check(self.lib.svmc_hawkesjd_chain_price_tilted_many(
+            sess, ch["ttms"].ctypes.data_as(dp), ch["forwards"].ctypes.data_as(dp), m, ch["strikes"].ctypes.data_as(dp),
+            ch["codes"].ctypes.data_as(C.POINTER(C.c_int8)), ch["offs"].ctypes.data_as(C.POINTER(C.c_size_t)), n_jobs,
+            params.ctypes.data_as(dp), seeds.ctypes.data_as(C.POINTER(C.c_uint64)), ids.ctypes.data_as(C.POINTER(C.c_uint32)),
+            int(nb_steps_per_year), gammas.ctypes.data_as(dp), G, int(bool(recenter)), prices.ctypes.data_as(dp),
+            stderrs.ctypes.data_as(dp), stats.ctypes.data_as(dp)))
+        # the C rows are [G K] with no padding; the host arrays above are padded to one double for an empty chain only
+        out = []
+        for j in range(n_jobs):
+            out.append(tilted_results(prices.ravel()[j * G * K:(j + 1) * G * K], stderrs.ravel()[j * G * K:(j + 1) * G * K],
+                                      stats[j], dict(ch, gammas=gammas[j])))
+        return out
 
     def close(self) -> None:
         """free every HBM buffer of the engine; any later launch through it fails in the C ABI's null-pointer

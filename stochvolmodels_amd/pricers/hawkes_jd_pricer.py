@@ -24,6 +24,10 @@ Monte Carlo under that kernel (hawkesjd_mc_chain_pricer_with_risk_premia(_gammas
 downloaded paths by hand): one stepping launch, then the exponentially weighted payoff reduction of the resident snapshots for
 every gamma at once (tilted_payoff_group_kernel), with delta-method standard errors, the normalizer, the gamma forward and the
 effective sample size per expiry.
+Many independent Monte Carlo jobs of one chain (hawkesjd_mc_chain_pricer_many, hawkesjd_mc_chain_pricer_with_risk_premia_gammas_many
+and the pricer methods over them; not in the reference): every job has its own parameter set -- both start intensities included --
+and its own random stream, ONE launch steps them all (hawkesjd_chain_rng_many_kernel), and each job's results are bit-equal to
+its single call.
 The reference's quirks are kept: `risk_premia_gamma` is accepted and unused by hawkesjd_mc_chain_pricer, `is_spot_measure` is ignored
 by it, and a variable_type other than LOG_RETURN raises (the reference would price the log-return as a variance).  Under the
 risk-premia kernel: the forwards follow zip(ttms, forwards) (entries beyond the shorter stay 1.0), discfactors are ignored
@@ -45,7 +49,8 @@ from .. import _lib
 from .. import dist as svdist
 from ..analytic import ODE_ATOL, ODE_RTOL, AnalyticGrid, chain_prices_from_sums, chain_sums
 from ..data.option_chain import OptionChain
-from ..engine import DeviceBuffer, get_engine, marshalled_chain, option_type_codes, tilted_chain_arrays, tilted_type_codes
+from ..engine import (MANY_MAX_JOBS, DeviceBuffer, get_engine, marshalled_chain, option_type_codes, tilted_chain_arrays,
+                      tilted_gammas, tilted_type_codes)
 from ..mc_chain import variable_type_code
 from ..utils import mgf_pricer as mgfp
 from ..utils.calibration import ImpliedVolObjective, chain_calibration_weights
@@ -306,6 +311,32 @@ class HawkesJDPricer(ModelPricer):
                                                          strikes_ttms=option_chain.strikes_ttms,
                                                          optiontypes_ttms=option_chain.optiontypes_ttms, nb_path=nb_path,
                                                          **params.to_dict(), **kwargs)
+
+    def model_mc_price_chain_many(self, option_chain: OptionChain, params_list: Sequence[HawkesJDParams], nb_path: int = 100000,
+                                  seeds: Optional[Sequence[int]] = None, nb_steps_per_year: int = NB_STEPS_PER_YEAR, **kwargs
+                                  ) -> List[Tuple[List[np.ndarray], List[np.ndarray]]]:
+        """model_mc_price_chain for several parameter sets, each with its own stream (hawkesjd_mc_chain_pricer_many): job j
+        equals model_mc_price_chain(option_chain, params_list[j], seed=seeds[j]) bit for bit"""
+        return hawkesjd_mc_chain_pricer_many(params_list=params_list, ttms=option_chain.ttms, forwards=option_chain.forwards,
+                                             discfactors=option_chain.discfactors, strikes_ttms=option_chain.strikes_ttms,
+                                             optiontypes_ttms=option_chain.optiontypes_ttms, nb_path=nb_path, seeds=seeds,
+                                             nb_steps_per_year=nb_steps_per_year, **kwargs)
+
+    def model_mc_price_chain_with_risk_premia_many(self, option_chain: OptionChain, params_list: Sequence[HawkesJDParams],
+                                                   nb_path: int = 100000, seeds: Optional[Sequence[int]] = None,
+                                                   nb_steps_per_year: int = NB_STEPS_PER_YEAR, **kwargs):
+        """model_mc_price_chain_with_risk_premia for several parameter sets, job j under its own params_list[j].risk_premia_gamma
+        (hawkesjd_mc_chain_pricer_with_risk_premia_gammas_many at one gamma per job): per job what the single method returns,
+        bit for bit; extensions recenter_forward=, return_forwards="""
+        params_list = list(params_list)
+        if any(p.risk_premia_gamma is None for p in params_list):
+            raise ValueError("risk_premia_gamma must be set for the risk-premia pricer")
+        out = hawkesjd_mc_chain_pricer_with_risk_premia_gammas_many(
+            params_list=params_list, ttms=option_chain.ttms, forwards=option_chain.forwards, discfactors=option_chain.discfactors,
+            strikes_ttms=option_chain.strikes_ttms, optiontypes_ttms=option_chain.optiontypes_ttms,
+            risk_premia_gammas=[[p.risk_premia_gamma] for p in params_list], nb_path=nb_path, seeds=seeds,
+            nb_steps_per_year=nb_steps_per_year, **kwargs)
+        return [tuple(o[0] for o in job) for job in out]
 
     @timer
     def simulate_terminal_values(self, params: HawkesJDParams, ttm: float = 1.0, nb_path: int = 100000,
@@ -687,6 +718,122 @@ def hawkesjd_mc_chain_pricer_with_risk_premia(ttms: np.ndarray, forwards: np.nda
                                                            recenter_forward=recenter_forward, return_forwards=return_forwards,
                                                            **kwargs)
     return tuple(o[0] for o in out)
+
+
+def _model_kwargs(params: HawkesJDParams) -> Dict[str, Any]:
+    """the keyword parameters of the single Monte Carlo pricers from a parameter set (risk_premia_gamma left out)"""
+    kw = params.to_dict()
+    kw.pop("risk_premia_gamma", None)
+    return kw
+
+
+def _refuse_sharded_many(name: str, comm, devices) -> None:
+    """a sharded request raises what the single pricer raises"""
+    if devices is not None or (comm.world if comm is not None else svdist.get_default_comm().world) > 1:
+        raise NotImplementedError(f"{name}: not sharded over ranks or devices")
+
+
+def hawkesjd_mc_chain_pricer_many(params_list: Sequence[HawkesJDParams], ttms: np.ndarray, forwards: np.ndarray,
+                                  discfactors: np.ndarray, strikes_ttms: Sequence[np.ndarray],
+                                  optiontypes_ttms: Sequence[np.ndarray], nb_path: int = 100000,
+                                  variable_type: VariableType = VariableType.LOG_RETURN,
+                                  nb_steps_per_year: int = NB_STEPS_PER_YEAR, seeds: Optional[Sequence[int]] = None, comm=None,
+                                  devices=None) -> List[Tuple[List[np.ndarray], List[np.ndarray]]]:
+    """hawkesjd_mc_chain_pricer for several independent jobs of ONE chain, as logsv_mc_chain_pricer_many: job j has the
+    parameters params_list[j] (its start intensities lambda_p, lambda_m included) and its own random stream -- seeds[j] (call id
+    0), or with seeds=None the process seed and the next call id, taken in list order.  Returns [(prices, stderrs)] per job, each
+    BIT-EQUAL to hawkesjd_mc_chain_pricer(..., seed=seeds[j]) (or to the j-th of as many consecutive unseeded calls).  Up to
+    MANY_MAX_JOBS jobs are stepped by ONE launch (svmc_hawkesjd_chain_price_many; longer lists in several calls, in order); more
+    than 16 expiries is a loop of single calls -- the same numbers.  Sharded requests (devices=, a world above one) raise as the
+    single pricer does; params' risk_premia_gamma is ignored, as there.  Not in the reference API."""
+    from .logsv_pricer import check_many_args, many_job_streams
+    params_list = check_many_args(params_list, seeds)
+    if not params_list:
+        return []
+    _check_variable_type(variable_type)
+    _refuse_sharded_many("hawkesjd_mc_chain_pricer_many", comm, devices)
+    strikes_ttms = [np.asarray(k, dtype=np.float64) for k in strikes_ttms]
+    optiontypes_ttms = [np.asarray(t) for t in optiontypes_ttms]
+    if len(ttms) > 16:
+        return [hawkesjd_mc_chain_pricer(ttms=ttms, forwards=forwards, discfactors=discfactors, strikes_ttms=strikes_ttms,
+                                         optiontypes_ttms=optiontypes_ttms, nb_path=nb_path, variable_type=variable_type,
+                                         nb_steps_per_year=nb_steps_per_year, seed=None if seeds is None else seeds[j],
+                                         **_model_kwargs(p))
+                for j, p in enumerate(params_list)]
+    streams = many_job_streams(len(params_list), seeds)
+    rows = np.stack([_model_block(p) for p in params_list])
+    ch = marshalled_chain(np.asarray(ttms), np.asarray(forwards), np.asarray(discfactors), strikes_ttms,
+                          [option_type_codes(t) for t in optiontypes_ttms])
+    eng = get_engine(int(nb_path))
+    out = []
+    for q0 in range(0, len(rows), MANY_MAX_JOBS):
+        part = streams[q0:q0 + MANY_MAX_JOBS]
+        out += eng.price_chain_many_fused(ch, "hawkesjd", rows[q0:q0 + MANY_MAX_JOBS], [s for s, _ in part], [c for _, c in part],
+                                          0, int(nb_steps_per_year), LOG_RETURN)
+    return [([a.reshape(np.shape(k)) for a, k in zip(pr, strikes_ttms)], [a.reshape(np.shape(k)) for a, k in zip(se, strikes_ttms)])
+            for pr, se in out]
+
+
+def many_job_gammas(risk_premia_gammas, n_jobs: int) -> np.ndarray:
+    """the gammas of a many-job tilted call as [n_jobs][n_gammas]: one flat sequence shared by all jobs, or one sequence per job,
+    all of the same length (1 .. TILTED_MAX_GAMMAS finite values each); anything else raises ValueError"""
+    g = list(risk_premia_gammas)
+    per_job = len(g) > 0 and all(np.ndim(v) > 0 for v in g)
+    if not per_job:
+        if any(np.ndim(v) > 0 for v in g):
+            raise ValueError("risk_premia_gammas: one flat sequence, or one sequence per job")
+        return np.tile(tilted_gammas(g), (n_jobs, 1))
+    if len(g) != n_jobs:
+        raise ValueError(f"risk_premia_gammas has {len(g)} rows for {n_jobs} parameter sets")
+    rows = [tilted_gammas(v) for v in g]
+    if any(r.size != rows[0].size for r in rows):
+        raise ValueError("risk_premia_gammas: every job needs the same number of gammas")
+    return np.ascontiguousarray(np.stack(rows))
+
+
+def hawkesjd_mc_chain_pricer_with_risk_premia_gammas_many(params_list: Sequence[HawkesJDParams], ttms: np.ndarray,
+                                                          forwards: np.ndarray, discfactors: np.ndarray,
+                                                          strikes_ttms: Sequence[np.ndarray],
+                                                          optiontypes_ttms: Sequence[np.ndarray],
+                                                          risk_premia_gammas: Sequence = (0.0,), nb_path: int = 100000,
+                                                          variable_type: VariableType = VariableType.LOG_RETURN,
+                                                          nb_steps_per_year: int = NB_STEPS_PER_YEAR,
+                                                          recenter_forward: bool = False, return_forwards: bool = False,
+                                                          seeds: Optional[Sequence[int]] = None, comm=None, devices=None) -> list:
+    """hawkesjd_mc_chain_pricer_with_risk_premia_gammas for several independent jobs of ONE chain: ONE stepping launch for all
+    jobs (svmc_hawkesjd_chain_price_tilted_many), then each job's weighted payoff reduction on its own snapshots.
+    risk_premia_gammas: one flat sequence shared by all jobs, or one sequence per job, all of the same length.  Returns per job
+    what the single function returns for (params_list[j], seeds[j], its gammas) -- (prices, stderrs), with return_forwards=True a
+    third item [gamma] -> (normalizers, gamma_forwards, stats) -- bit for bit; streams as hawkesjd_mc_chain_pricer_many.  The
+    single function's checks: 'C' / 'P' only (ValueError("not implemented")), LOG_RETURN only, not sharded; discfactors and the
+    params' risk_premia_gamma are accepted and ignored.  More than 16 expiries is a loop of single calls."""
+    from .logsv_pricer import check_many_args, many_job_streams
+    params_list = check_many_args(params_list, seeds)
+    if not params_list:
+        return []
+    _check_variable_type(variable_type)
+    _refuse_sharded_many("hawkesjd_mc_chain_pricer_with_risk_premia_gammas_many", comm, devices)
+    gammas = many_job_gammas(risk_premia_gammas, len(params_list))
+    strikes_ttms = [np.asarray(k, dtype=np.float64) for k in strikes_ttms]
+    codes = [tilted_type_codes(t) for t in optiontypes_ttms]                # ValueError("not implemented")
+    ch = tilted_chain_arrays(forwards, strikes_ttms, codes, gammas[0], ttms=ttms)
+    if ch["m"] > 16:
+        return [hawkesjd_mc_chain_pricer_with_risk_premia_gammas(
+            ttms=ttms, forwards=forwards, discfactors=discfactors, strikes_ttms=strikes_ttms, optiontypes_ttms=optiontypes_ttms,
+            risk_premia_gammas=gammas[j], nb_path=nb_path, variable_type=variable_type, nb_steps_per_year=nb_steps_per_year,
+            seed=None if seeds is None else seeds[j], recenter_forward=recenter_forward, return_forwards=return_forwards,
+            **_model_kwargs(p)) for j, p in enumerate(params_list)]
+    streams = many_job_streams(len(params_list), seeds)
+    rows = np.stack([_model_block(p) for p in params_list])
+    eng = get_engine(int(nb_path))
+    out = []
+    for q0 in range(0, len(rows), MANY_MAX_JOBS):
+        part = streams[q0:q0 + MANY_MAX_JOBS]
+        out += eng.price_hawkesjd_chain_tilted_many_fused(ch, rows[q0:q0 + MANY_MAX_JOBS], int(nb_steps_per_year), [s for s, _ in part],
+                                                          [c for _, c in part], gammas[q0:q0 + MANY_MAX_JOBS], bool(recenter_forward))
+    if not return_forwards:
+        return [(prices, stderrs) for prices, stderrs, _ in out]
+    return [(prices, stderrs, [(st[:, 0].copy(), st[:, 2].copy(), st) for st in stats]) for prices, stderrs, stats in out]
 
 
 def _broadcast(v, nb_path: int, fill) -> np.ndarray:
