@@ -470,6 +470,86 @@ static std::vector<unsigned char> fixed_key(const ChainView &c, int P, int varia
     return key;
 }
 
+// The stepping half of every single-chain driver on device randoms: the chain's checks, the entry point's own ahead of the step
+// count's (check()) and after it (prepare(): also its set-up before the launch), the step grids and the model's stepping call step(nbs,
+// dts, qsnap, spot, ws, ws_bytes).  One launch may leave (may_pend) its spot partials unreduced in s->spot_ws for the tail: `pending`.
+struct Stepped { int rc; bool pending; };
+static int no_check() { return SVMC_OK; }
+template <class Step, class Check = int (*)(), class Prepare = int (*)()>
+static Stepped single_step(const char *fn, Session *s, const ChainView &c, int nb_steps_per_year, int variable_type, const double *prices,
+                           const double *stderrs, bool needs_discfactors, bool may_pend, Step &&step, Check &&check = no_check,
+                           Prepare &&prepare = no_check)
+{
+    if (int rc = check_chain(fn, s, c, variable_type, prices, stderrs, needs_discfactors)) return {rc, false};
+    if (int rc = check()) return {rc, false};
+    if (nb_steps_per_year <= 0) return {fail(SVMC_ERR_INVALID_ARGUMENT, std::string(fn) + ": nb_steps_per_year must be positive"), false};
+    if (int rc = prepare()) return {rc, false};
+    std::vector<int> nbs;       // (the start state of every path travels to the first launch as three constants: no fill launch)
+    std::vector<double> dts;
+    expiry_grids(c, nb_steps_per_year, nbs, dts);
+    double *qsnap = (variable_type == SVMC_Q_VAR) ? s->snap + static_cast<size_t>(c.m) * s->n_path : nullptr;
+    const bool pending = may_pend && c.m <= MAX_FUSED_SLICES;
+    stepping_begin(s);
+    const int rc = step(nbs.data(), dts.data(), qsnap, pending ? nullptr : s->spot, pending ? s->spot_ws : s->ws,
+                        pending ? s->spot_ws_bytes : s->ws_bytes);
+    if (rc == SVMC_OK) stepping_end(s);
+    return {rc, pending};
+}
+
+// *p at least `need` bytes (its contents are not kept); every call that grows one ends synchronised, so nothing still reads the old
+static hipError_t grow(void **p, size_t &cap, size_t need, bool pinned)
+{
+    if (*p != nullptr && need <= cap) return hipSuccess;
+    if (*p != nullptr) (void)(pinned ? hipHostFree(*p) : hipFree(*p));
+    *p = nullptr;
+    cap = 0;
+    const hipError_t e = pinned ? hipHostMalloc(p, need, hipHostMallocDefault) : hipMalloc(p, need);
+    if (e == hipSuccess) cap = need;
+    return e;
+}
+
+// what the tilted calls check beyond the chain's own checks, for n_gamma_values gammas (n_gammas per job)
+static int check_tilted(const char *fn, const ChainView &c, const double *gammas, size_t n_gamma_values, int n_gammas, const double *stats)
+{
+    SVMC_REQUIRE(gammas != nullptr && stats != nullptr, std::string(fn) + ": null pointer");
+    SVMC_REQUIRE(n_gammas >= 1 && n_gammas <= SVMC_TILTED_MAX_GAMMAS, std::string(fn) + ": n_gammas outside 1 .. SVMC_TILTED_MAX_GAMMAS");
+    for (size_t g = 0; g < n_gamma_values; ++g) SVMC_REQUIRE(std::isfinite(gammas[g]), std::string(fn) + ": a gamma is not finite");
+    for (int i = 0; i < c.m; ++i) {
+        SVMC_REQUIRE(std::isfinite(c.forwards[i]), std::string(fn) + ": a forward is not finite");
+        SVMC_REQUIRE(c.offsets[i] <= c.offsets[i + 1], std::string(fn) + ": strike offsets must not decrease");
+    }
+    for (size_t k = 0; k < c.offsets[c.m]; ++k) {
+        if (c.types[k] != SVMC_CALL && c.types[k] != SVMC_PUT) return fail(SVMC_ERR_UNKNOWN_PAYOFF, "unknown option payoff code");
+        SVMC_REQUIRE(std::isfinite(c.strikes[k]), std::string(fn) + ": a strike is not finite");
+    }
+    return SVMC_OK;
+}
+
+// the page-locked landing block of the tilted calls in s->tilted_pinned: per job [prices G K | stderrs G K | stats G m 8]; after
+// the synchronisation copy_home puts job j's pieces into the caller's [J][G K], [J][G K] and [J][G m 8] arrays
+struct TiltedBlock {
+    double *base;
+    size_t GK, n_stats;
+    double *prices(size_t j) const { return base + j * (2 * GK + n_stats); }
+    double *stderrs(size_t j) const { return prices(j) + GK; }
+    double *stats(size_t j) const { return stderrs(j) + GK; }
+    void copy_home(size_t j, double *prices_host, double *stderrs_host, double *stats_host) const
+    {
+        memcpy(prices_host + j * GK, prices(j), GK * sizeof(double));
+        memcpy(stderrs_host + j * GK, stderrs(j), GK * sizeof(double));
+        memcpy(stats_host + j * n_stats, stats(j), n_stats * sizeof(double));
+    }
+};
+static int tilted_block(Session *s, const ChainView &c, int n_gammas, int n_jobs, TiltedBlock &b)
+{
+    b.GK = static_cast<size_t>(n_gammas) * c.offsets[c.m];
+    b.n_stats = static_cast<size_t>(n_gammas) * c.m * SVMC_TILTED_STATS_DOUBLES;
+    SVMC_HIP_TRY(grow(reinterpret_cast<void **>(&s->tilted_pinned), s->tilted_pinned_bytes,
+                      static_cast<size_t>(n_jobs) * (2 * b.GK + b.n_stats) * sizeof(double), true));
+    b.base = s->tilted_pinned;
+    return SVMC_OK;
+}
+
 }  // namespace svmc
 
 using namespace svmc;
@@ -620,25 +700,14 @@ int svmc_logsv_chain_price(svmc_session_t session, const double *ttms_host, cons
     const char *fn = "svmc_logsv_chain_price";
     Session *s = reinterpret_cast<Session *>(session);
     const ChainView c = {n_expiries, ttms_host, forwards_host, discfactors_host, strikes_host, types_host, strike_offsets_host};
-    if (int rc = check_chain(fn, s, c, variable_type, prices_host, stderrs_host)) return rc;
-    SVMC_REQUIRE(nb_steps_per_year > 0, "svmc_logsv_chain_price: nb_steps_per_year must be positive");
-    const size_t n = s->n_path;
-    // the start state (0, v0, 0) of every path (:832-834) travels as three constants: no fill launch
-    std::vector<int> nbs;
-    std::vector<double> dts;
-    expiry_grids(c, nb_steps_per_year, nbs, dts);                                                        // :840-865
-    // the stepping (a single expiry: the plain slice kernel -- the same bits, and the one bench.py profiles); with one launch its
-    // per-wave spot partials stay in s->spot_ws and reduce_and_finalize decides who sums them, with more each launch reduces its own
-    double *qsnap = (variable_type == SVMC_Q_VAR) ? s->snap + static_cast<size_t>(c.m) * n : nullptr;
-    const bool pending = c.m <= MAX_FUSED_SLICES;
-    stepping_begin(s);
-    if (int rc = logsv_step_partials(v0, s->x, s->vol, s->qvar, n, c.m, nbs.data(), dts.data(), vol_backbone_etas_host, c.forwards, theta,
-                                     kappa1, kappa2, beta, volvol, is_spot_measure, seed, call_id, s->path_offset, s->snap, qsnap,
-                                     pending ? nullptr : s->spot, pending ? s->spot_ws : s->ws, pending ? s->spot_ws_bytes : s->ws_bytes,
-                                     s->stream))
-        return rc;
-    stepping_end(s);
-    return reduce_and_finalize(s, c, variable_type, prices_host, stderrs_host, pending);
+    // the stepping of :832-865 (a single expiry: the plain slice kernel -- the same bits, the one bench.py profiles)
+    const Stepped st = single_step(fn, s, c, nb_steps_per_year, variable_type, prices_host, stderrs_host, true, true,
+                                   [&](const int *nbs, const double *dts, double *qsnap, double *spot, void *ws, size_t ws_bytes) {
+        return logsv_step_partials(v0, s->x, s->vol, s->qvar, s->n_path, c.m, nbs, dts, vol_backbone_etas_host, c.forwards, theta, kappa1,
+                                   kappa2, beta, volvol, is_spot_measure, seed, call_id, s->path_offset, s->snap, qsnap, spot, ws,
+                                   ws_bytes, s->stream);
+    });
+    return st.rc ? st.rc : reduce_and_finalize(s, c, variable_type, prices_host, stderrs_host, st.pending);
 }
 
 int svmc_logsv_chain_price_fixed(svmc_session_t session, const double *ttms_host, const double *forwards_host,
@@ -894,22 +963,13 @@ int svmc_heston_chain_price(svmc_session_t session, const double *ttms_host, con
     const char *fn = "svmc_heston_chain_price";
     Session *s = reinterpret_cast<Session *>(session);
     const ChainView c = {n_expiries, ttms_host, forwards_host, discfactors_host, strikes_host, types_host, strike_offsets_host};
-    if (int rc = check_chain(fn, s, c, variable_type, prices_host, stderrs_host)) return rc;
-    SVMC_REQUIRE(nb_steps_per_year > 0, "svmc_heston_chain_price: nb_steps_per_year must be positive");
-    const size_t n = s->n_path;
-    // the start state (0, v0, 0) of every path (:303-305) travels as three constants: no fill launch
-    std::vector<int> nbs;
-    std::vector<double> dts;
-    expiry_grids(c, nb_steps_per_year, nbs, dts);                                                        // :308-329
-    double *qsnap = (variable_type == SVMC_Q_VAR) ? s->snap + static_cast<size_t>(c.m) * n : nullptr;
-    const bool pending = c.m <= MAX_FUSED_SLICES;
-    stepping_begin(s);
-    if (int rc = heston_step_partials(v0, s->x, s->vol, s->qvar, n, c.m, nbs.data(), dts.data(), c.forwards, theta, kappa, rho, volvol, scheme,
-                                      seed, call_id, s->path_offset, s->snap, qsnap, pending ? nullptr : s->spot,
-                                      pending ? s->spot_ws : s->ws, pending ? s->spot_ws_bytes : s->ws_bytes, s->stream))
-        return rc;
-    stepping_end(s);
-    return reduce_and_finalize(s, c, variable_type, prices_host, stderrs_host, pending);
+    // the stepping of :303-329
+    const Stepped st = single_step(fn, s, c, nb_steps_per_year, variable_type, prices_host, stderrs_host, true, true,
+                                   [&](const int *nbs, const double *dts, double *qsnap, double *spot, void *ws, size_t ws_bytes) {
+        return heston_step_partials(v0, s->x, s->vol, s->qvar, s->n_path, c.m, nbs, dts, c.forwards, theta, kappa, rho, volvol, scheme, seed,
+                                    call_id, s->path_offset, s->snap, qsnap, spot, ws, ws_bytes, s->stream);
+    });
+    return st.rc ? st.rc : reduce_and_finalize(s, c, variable_type, prices_host, stderrs_host, st.pending);
 }
 
 int svmc_hawkesjd_chain_price(svmc_session_t session, const double *ttms_host, const double *forwards_host,
@@ -921,23 +981,18 @@ int svmc_hawkesjd_chain_price(svmc_session_t session, const double *ttms_host, c
     const char *fn = "svmc_hawkesjd_chain_price";
     Session *s = reinterpret_cast<Session *>(session);
     const ChainView c = {n_expiries, ttms_host, forwards_host, discfactors_host, strikes_host, types_host, strike_offsets_host};
-    if (int rc = check_chain(fn, s, c, variable_type, prices_host, stderrs_host)) return rc;
-    if (variable_type != SVMC_LOG_RETURN)      // the reference would price the log-return as a variance (:701-707)
-        return fail(SVMC_ERR_UNSUPPORTED_VARIABLE, "svmc_hawkesjd_chain_price: LOG_RETURN only");
-    SVMC_REQUIRE(params_host != nullptr, "svmc_hawkesjd_chain_price: null params");
-    SVMC_REQUIRE(nb_steps_per_year > 0, "svmc_hawkesjd_chain_price: nb_steps_per_year must be positive");
-    std::vector<int> nbs;
-    std::vector<double> dts;
-    expiry_grids(c, nb_steps_per_year, nbs, dts);                                                        // :680-700
-    // the session's vol / qvar slots hold lambda_p / lambda_m
-    const bool pending = c.m <= MAX_FUSED_SLICES;
-    stepping_begin(s);
-    if (int rc = hawkes_step_partials(params_host, s->x, s->vol, s->qvar, s->n_path, c.m, nbs.data(), dts.data(), c.forwards, seed,
-                                      call_id, s->path_offset, s->snap, pending ? nullptr : s->spot, pending ? s->spot_ws : s->ws,
-                                      pending ? s->spot_ws_bytes : s->ws_bytes, s->stream))
-        return rc;
-    stepping_end(s);
-    return reduce_and_finalize(s, c, variable_type, prices_host, stderrs_host, pending);
+    const auto check = [&]() -> int {          // (the reference would price the log-return as a variance, :701-707)
+        if (variable_type != SVMC_LOG_RETURN) return fail(SVMC_ERR_UNSUPPORTED_VARIABLE, "svmc_hawkesjd_chain_price: LOG_RETURN only");
+        SVMC_REQUIRE(params_host != nullptr, "svmc_hawkesjd_chain_price: null params");
+        return SVMC_OK;
+    };
+    // the stepping of :680-700; the session's vol / qvar slots hold lambda_p / lambda_m
+    const Stepped st = single_step(fn, s, c, nb_steps_per_year, variable_type, prices_host, stderrs_host, true, true,
+                                   [&](const int *nbs, const double *dts, double *, double *spot, void *ws, size_t ws_bytes) {
+        return hawkes_step_partials(params_host, s->x, s->vol, s->qvar, s->n_path, c.m, nbs, dts, c.forwards, seed, call_id,
+                                    s->path_offset, s->snap, spot, ws, ws_bytes, s->stream);
+    }, check);
+    return st.rc ? st.rc : reduce_and_finalize(s, c, variable_type, prices_host, stderrs_host, st.pending);
 }
 
 int svmc_hawkesjd_chain_price_tilted(svmc_session_t session, const double *ttms_host, const double *forwards_host, int n_expiries,
@@ -950,75 +1005,42 @@ int svmc_hawkesjd_chain_price_tilted(svmc_session_t session, const double *ttms_
     Session *s = reinterpret_cast<Session *>(session);
     // the chain's own checks (the discount factors play no part: the prices are undiscounted)
     const ChainView c = {n_expiries, ttms_host, forwards_host, nullptr, strikes_host, types_host, strike_offsets_host};
-    if (int rc = check_chain(fn, s, c, SVMC_LOG_RETURN, prices_host, stderrs_host, false)) return rc;
-    SVMC_REQUIRE(!s->sharded(), std::string(fn) + ": single-device sessions only");
-    SVMC_REQUIRE(params_host != nullptr && gammas_host != nullptr && stats_host != nullptr, std::string(fn) + ": null pointer");
-    SVMC_REQUIRE(nb_steps_per_year > 0, std::string(fn) + ": nb_steps_per_year must be positive");
-    SVMC_REQUIRE(n_gammas >= 1 && n_gammas <= SVMC_TILTED_MAX_GAMMAS, std::string(fn) + ": n_gammas outside 1 .. SVMC_TILTED_MAX_GAMMAS");
-    for (int g = 0; g < n_gammas; ++g) SVMC_REQUIRE(std::isfinite(gammas_host[g]), std::string(fn) + ": a gamma is not finite");
-    const size_t K = c.offsets[c.m];
-    for (int i = 0; i < c.m; ++i) {
-        SVMC_REQUIRE(std::isfinite(c.forwards[i]), std::string(fn) + ": a forward is not finite");
-        SVMC_REQUIRE(c.offsets[i] <= c.offsets[i + 1], std::string(fn) + ": strike offsets must not decrease");
-    }
-    for (size_t k = 0; k < K; ++k) {
-        if (c.types[k] != SVMC_CALL && c.types[k] != SVMC_PUT) return fail(SVMC_ERR_UNKNOWN_PAYOFF, "unknown option payoff code");
-        SVMC_REQUIRE(std::isfinite(c.strikes[k]), std::string(fn) + ": a strike is not finite");
-    }
-    size_t need_ws = 0;
-    if (int rc = svmc_payoff_workspace_bytes(&need_ws)) return rc;
-    if (s->ws_bytes < need_ws) return fail(SVMC_ERR_WORKSPACE, std::string(fn) + ": the session's workspace is too small");
-    const size_t G = static_cast<size_t>(n_gammas), n_stats = G * c.m * SVMC_TILTED_STATS_DOUBLES;
-    const size_t out_bytes = (2 * G * K + n_stats) * sizeof(double);
-    if (s->tilted_pinned_bytes < out_bytes) {
-        if (s->tilted_pinned != nullptr) (void)hipHostFree(s->tilted_pinned);
-        s->tilted_pinned = nullptr;
-        s->tilted_pinned_bytes = 0;
-        SVMC_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&s->tilted_pinned), out_bytes, hipHostMallocDefault));
-        s->tilted_pinned_bytes = out_bytes;
-    }
-    std::vector<int> nbs;
-    std::vector<double> dts, shifts;
-    expiry_grids(c, nb_steps_per_year, nbs, dts);
-    payoff_shifts_of(c, SVMC_LOG_RETURN, shifts);
-    // the stepping launch of svmc_hawkesjd_chain_price, once for every gamma; its spot sums are reduced only where the recentring
-    // reads them
-    const bool pending = !recenter && c.m <= MAX_FUSED_SLICES;
-    stepping_begin(s);
-    if (int rc = hawkes_step_partials(params_host, s->x, s->vol, s->qvar, s->n_path, c.m, nbs.data(), dts.data(), c.forwards, seed,
-                                      call_id, s->path_offset, s->snap, pending ? nullptr : s->spot, pending ? s->spot_ws : s->ws,
-                                      pending ? s->spot_ws_bytes : s->ws_bytes, s->stream))
-        return rc;
-    stepping_end(s);
+    TiltedBlock out;
+    std::vector<double> shifts;
+    const auto check = [&]() -> int {
+        SVMC_REQUIRE(!s->sharded(), std::string(fn) + ": single-device sessions only");
+        SVMC_REQUIRE(params_host != nullptr && gammas_host != nullptr && stats_host != nullptr, std::string(fn) + ": null pointer");
+        return SVMC_OK;
+    };
+    const auto prepare = [&]() -> int {        // the gammas' checks come after the step count's; then the shifts and the pinned block
+        if (int rc = check_tilted(fn, c, gammas_host, static_cast<size_t>(n_gammas), n_gammas, stats_host)) return rc;
+        size_t need_ws = 0;
+        if (int rc = svmc_payoff_workspace_bytes(&need_ws)) return rc;
+        if (s->ws_bytes < need_ws) return fail(SVMC_ERR_WORKSPACE, std::string(fn) + ": the session's workspace is too small");
+        payoff_shifts_of(c, SVMC_LOG_RETURN, shifts);
+        return tilted_block(s, c, n_gammas, 1, out);
+    };
+    // svmc_hawkesjd_chain_price's stepping launch, once for every gamma; its spot sums are reduced only where the recentring reads them
+    const Stepped st = single_step(fn, s, c, nb_steps_per_year, SVMC_LOG_RETURN, prices_host, stderrs_host, false, !recenter,
+                                   [&](const int *nbs, const double *dts, double *, double *spot, void *ws, size_t ws_bytes) {
+        return hawkes_step_partials(params_host, s->x, s->vol, s->qvar, s->n_path, c.m, nbs, dts, c.forwards, seed, call_id,
+                                    s->path_offset, s->snap, spot, ws, ws_bytes, s->stream);
+    }, check, prepare);
+    if (st.rc) return st.rc;
     const SnapshotRows r = snapshot_rows(s, c, 0, 1);
-    double *prices = s->tilted_pinned, *stderrs = prices + G * K, *stats = stderrs + G * K;
     if (int rc = svmc_tilted_payoff_chain(r.x.data(), s->n_path, c.forwards, c.m, c.strikes, c.types, shifts.data(), c.offsets, gammas_host,
-                                          n_gammas, recenter, recenter ? s->spot : nullptr, prices, stderrs, stats, s->ws, s->ws_bytes,
-                                          reinterpret_cast<svmc_stream_t>(s->stream)))
+                                          n_gammas, recenter, recenter ? s->spot : nullptr, out.prices(0), out.stderrs(0), out.stats(0),
+                                          s->ws, s->ws_bytes, reinterpret_cast<svmc_stream_t>(s->stream)))
         return rc;
     SVMC_HIP_TRY(hipStreamSynchronize(s->stream));
     stepping_read(s);
-    memcpy(prices_host, prices, G * K * sizeof(double));
-    memcpy(stderrs_host, stderrs, G * K * sizeof(double));
-    memcpy(stats_host, stats, n_stats * sizeof(double));
+    out.copy_home(0, prices_host, stderrs_host, stats_host);
     return SVMC_OK;
 }
 
 }  // extern "C"
 
 // ---- many jobs of one chain (svmc_logsv_chain_price_many / svmc_heston_chain_price_many / svmc_hawkesjd_chain_price[_tilted]_many)
-
-// *p at least `need` bytes (its contents are not kept); every many-call ends synchronised, so nothing still reads the old buffer
-static hipError_t grow(void **p, size_t &cap, size_t need, bool pinned)
-{
-    if (*p != nullptr && need <= cap) return hipSuccess;
-    if (*p != nullptr) (void)(pinned ? hipHostFree(*p) : hipFree(*p));
-    *p = nullptr;
-    cap = 0;
-    const hipError_t e = pinned ? hipHostMalloc(p, need, hipHostMallocDefault) : hipMalloc(p, need);
-    if (e == hipSuccess) cap = need;
-    return e;
-}
 
 // (min_ws_bytes: a floor for the payoff workspace, for a tail other than chain_payoff_and_finish_sets)
 static int grow_many(const char *fn, ManyBuffers &mb, size_t n, size_t J, size_t m, size_t K, bool need_q, size_t min_ws_bytes = 0)
@@ -1128,6 +1150,16 @@ static int chain_price_many(const char *fn, svmc_session_t session, const ChainV
     return finish_sets(s, c, mb.sums_pinned, shifts, n_jobs, variable_type, prices, stderrs, nullptr, nullptr);
 }
 
+// the step() of the two Hawkes many-job drivers: every job's paths from ONE launch into the ManyBuffers
+static auto hawkes_many_stepper(Session *s, const ChainView &c, int n_jobs, const double *params, const uint64_t *seeds, const uint32_t *call_ids)
+{
+    return [=](const std::vector<int> &nbs, const std::vector<double> &dts, double *) {
+        ManyBuffers &mb = s->many;
+        return hawkes_chain_rng_many(s->n_path, n_jobs, c.m, nbs.data(), dts.data(), c.forwards, params, seeds, call_ids, s->path_offset,
+                                     mb.table_host, mb.table_dev, mb.snap, mb.spot_ws, s->stream);
+    };
+}
+
 extern "C" {
 
 int svmc_logsv_chain_price_many(svmc_session_t session, const double *ttms_host, const double *forwards_host,
@@ -1175,17 +1207,12 @@ int svmc_hawkesjd_chain_price_many(svmc_session_t session, const double *ttms_ho
     const ChainView c = {n_expiries, ttms_host, forwards_host, discfactors_host, strikes_host, types_host, strike_offsets_host};
     Session *s = reinterpret_cast<Session *>(session);
     return chain_price_many(fn, session, c, n_jobs, params_host, seeds_host, call_ids_host, nb_steps_per_year, variable_type, prices_host,
-                            stderrs_host,
-                            [&]() -> int {
+                            stderrs_host, [&]() -> int {
         if (variable_type != SVMC_LOG_RETURN)  // the reference would price the log-return as a variance (:701-707)
             return fail(SVMC_ERR_UNSUPPORTED_VARIABLE, std::string(fn) + ": LOG_RETURN only");
         return hawkes_check_many(fn, n_jobs, params_host);
     },
-                            [&](const std::vector<int> &nbs, const std::vector<double> &dts, double *) {
-        ManyBuffers &mb = s->many;
-        return hawkes_chain_rng_many(s->n_path, n_jobs, c.m, nbs.data(), dts.data(), c.forwards, params_host, seeds_host, call_ids_host,
-                                     s->path_offset, mb.table_host, mb.table_dev, mb.snap, mb.spot_ws, s->stream);
-    });
+                            hawkes_many_stepper(s, c, n_jobs, params_host, seeds_host, call_ids_host));
 }
 
 int svmc_hawkesjd_chain_price_tilted_many(svmc_session_t session, const double *ttms_host, const double *forwards_host, int n_expiries,
@@ -1200,62 +1227,32 @@ int svmc_hawkesjd_chain_price_tilted_many(svmc_session_t session, const double *
     size_t need_ws = 0;
     if (int rc = svmc_payoff_workspace_bytes(&need_ws)) return rc;
     std::vector<double> shifts;
+    TiltedBlock out;
     if (int rc = many_step(fn, s, c, n_jobs, params_host, seeds_host, call_ids_host, nb_steps_per_year, SVMC_LOG_RETURN, prices_host,
                            stderrs_host, false, need_ws, shifts,
                            [&]() -> int {
         // svmc_hawkesjd_chain_price_tilted's checks, for every job
-        SVMC_REQUIRE(gammas_host != nullptr && stats_host != nullptr, std::string(fn) + ": null pointer");
-        SVMC_REQUIRE(n_gammas >= 1 && n_gammas <= SVMC_TILTED_MAX_GAMMAS, std::string(fn) + ": n_gammas outside 1 .. SVMC_TILTED_MAX_GAMMAS");
-        for (size_t g = 0; g < static_cast<size_t>(n_jobs) * n_gammas; ++g)
-            SVMC_REQUIRE(std::isfinite(gammas_host[g]), std::string(fn) + ": a gamma is not finite");
-        for (int i = 0; i < c.m; ++i) {
-            SVMC_REQUIRE(std::isfinite(c.forwards[i]), std::string(fn) + ": a forward is not finite");
-            SVMC_REQUIRE(c.offsets[i] <= c.offsets[i + 1], std::string(fn) + ": strike offsets must not decrease");
-        }
-        for (size_t k = 0; k < c.offsets[c.m]; ++k) {
-            if (c.types[k] != SVMC_CALL && c.types[k] != SVMC_PUT) return fail(SVMC_ERR_UNKNOWN_PAYOFF, "unknown option payoff code");
-            SVMC_REQUIRE(std::isfinite(c.strikes[k]), std::string(fn) + ": a strike is not finite");
-        }
+        if (int rc = check_tilted(fn, c, gammas_host, static_cast<size_t>(n_jobs) * n_gammas, n_gammas, stats_host)) return rc;
         if (int rc = hawkes_check_many(fn, n_jobs, params_host)) return rc;
-        // the pinned landing buffer of every job's prices, errors and statistics, grown as the single call grows it
-        const size_t G = static_cast<size_t>(n_gammas);
-        const size_t out_bytes = static_cast<size_t>(n_jobs) * (2 * G * c.offsets[c.m] + G * c.m * SVMC_TILTED_STATS_DOUBLES) * sizeof(double);
-        if (s->tilted_pinned_bytes < out_bytes) {
-            if (s->tilted_pinned != nullptr) (void)hipHostFree(s->tilted_pinned);
-            s->tilted_pinned = nullptr;
-            s->tilted_pinned_bytes = 0;
-            SVMC_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&s->tilted_pinned), out_bytes, hipHostMallocDefault));
-            s->tilted_pinned_bytes = out_bytes;
-        }
-        return SVMC_OK;
+        return tilted_block(s, c, n_gammas, n_jobs, out);
     },
-                           [&](const std::vector<int> &nbs, const std::vector<double> &dts, double *) {
-        ManyBuffers &mb = s->many;
-        return hawkes_chain_rng_many(s->n_path, n_jobs, c.m, nbs.data(), dts.data(), c.forwards, params_host, seeds_host, call_ids_host,
-                                     s->path_offset, mb.table_host, mb.table_dev, mb.snap, mb.spot_ws, s->stream);
-    }))
+                           hawkes_many_stepper(s, c, n_jobs, params_host, seeds_host, call_ids_host)))
         return rc;
     ManyBuffers &mb = s->many;
-    const size_t n = s->n_path, J = static_cast<size_t>(n_jobs), m = static_cast<size_t>(c.m), K = c.offsets[c.m];
-    const size_t G = static_cast<size_t>(n_gammas), n_stats = G * m * SVMC_TILTED_STATS_DOUBLES, per_job = 2 * G * K + n_stats;
+    const size_t n = s->n_path, J = static_cast<size_t>(n_jobs), m = static_cast<size_t>(c.m), G = static_cast<size_t>(n_gammas);
     // per job the tilted launches of the single call on that job's snapshot rows (and, recentring, its rows of the spot sums)
     std::vector<const double *> xs(m);
     for (size_t j = 0; j < J; ++j) {
         for (size_t i = 0; i < m; ++i) xs[i] = mb.snap + (j * m + i) * n;
-        double *prices = s->tilted_pinned + j * per_job, *stderrs = prices + G * K, *stats = stderrs + G * K;
         if (int rc = svmc_tilted_payoff_chain(xs.data(), n, c.forwards, c.m, c.strikes, c.types, shifts.data(), c.offsets,
-                                              gammas_host + j * G, n_gammas, recenter, recenter ? mb.spot + 2 * m * j : nullptr, prices,
-                                              stderrs, stats, mb.ws, mb.ws_bytes, reinterpret_cast<svmc_stream_t>(s->stream)))
+                                              gammas_host + j * G, n_gammas, recenter, recenter ? mb.spot + 2 * m * j : nullptr,
+                                              out.prices(j), out.stderrs(j), out.stats(j), mb.ws, mb.ws_bytes,
+                                              reinterpret_cast<svmc_stream_t>(s->stream)))
             return rc;
     }
     SVMC_HIP_TRY(hipStreamSynchronize(s->stream));
     stepping_read(s);
-    for (size_t j = 0; j < J; ++j) {
-        const double *prices = s->tilted_pinned + j * per_job, *stderrs = prices + G * K, *stats = stderrs + G * K;
-        memcpy(prices_host + j * G * K, prices, G * K * sizeof(double));
-        memcpy(stderrs_host + j * G * K, stderrs, G * K * sizeof(double));
-        memcpy(stats_host + j * n_stats, stats, n_stats * sizeof(double));
-    }
+    for (size_t j = 0; j < J; ++j) out.copy_home(j, prices_host, stderrs_host, stats_host);
     return SVMC_OK;
 }
 

@@ -615,6 +615,17 @@ class HipEngine:
             float(theta), float(kappa), float(rho), float(volvol), int(scheme), int(nb_steps_per_year), int(variable_type),
             int(seed), int(call_id), p, e), "heston_rng_kernel" if ch["m"] == 1 else "heston_chain_rng_kernel")
 
+    @staticmethod
+    def _many_jobs(params, seeds: Sequence[int], call_ids: Sequence[int], what: str = "one seed and one call id per job"):
+        """(J, the C pointers of params [J][...], seeds [J] and call ids [J] as contiguous arrays, each keeping its array alive)"""
+        params = np.ascontiguousarray(params, dtype=np.float64)
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
+        ids = np.ascontiguousarray(call_ids, dtype=np.uint32)
+        if not (seeds.size == ids.size == params.shape[0]):
+            raise ValueError(what)
+        return params.shape[0], (params.ctypes.data_as(C.POINTER(C.c_double)), seeds.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                 ids.ctypes.data_as(C.POINTER(C.c_uint32)))
+
     def price_chain_many_fused(self, ch: dict, model: str, params: np.ndarray, seeds: Sequence[int], call_ids: Sequence[int],
                                mode: int, nb_steps_per_year: int, variable_type: int):
         """J jobs of one chain as ONE svmc_logsv_chain_price_many (model "logsv", mode = is_spot_measure, params [J][6 + m]),
@@ -623,12 +634,7 @@ class HipEngine:
         (prices, stderrs) of the single fused call with its (seed, call id), cut into expiries"""
         if model not in ("logsv", "heston", "hawkesjd"):
             raise ValueError(f"price_chain_many_fused: unknown model {model!r}")
-        params = np.ascontiguousarray(params, dtype=np.float64)
-        n_jobs = params.shape[0]
-        seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
-        ids = np.ascontiguousarray(call_ids, dtype=np.uint32)
-        if not (seeds.size == ids.size == n_jobs):
-            raise ValueError("one seed and one call id per job")
+        n_jobs, jobs = self._many_jobs(params, seeds, call_ids)
         sess = self.fused_chain_session(ch["m"], ch["total"])
         res = np.empty((2, n_jobs, max(ch["total"], 1)))
         dp = C.POINTER(C.c_double)
@@ -636,9 +642,8 @@ class HipEngine:
               "hawkesjd": self.lib.svmc_hawkesjd_chain_price_many}[model]
         modes = () if model == "hawkesjd" else (int(mode),)
         _lib.check(fn(sess, ch["ttms"], ch["forwards"], ch["discfactors"], ch["m"], ch["strikes"], ch["codes"], ch["offsets"], n_jobs,
-                      params.ctypes.data_as(dp), seeds.ctypes.data_as(C.POINTER(C.c_uint64)),
-                      ids.ctypes.data_as(C.POINTER(C.c_uint32)), *modes, int(nb_steps_per_year), int(variable_type),
-                      C.cast(res.ctypes.data, dp), C.cast(res.ctypes.data + res.strides[0], dp)))
+                      *jobs, *modes, int(nb_steps_per_year), int(variable_type), C.cast(res.ctypes.data, dp),
+                      C.cast(res.ctypes.data + res.strides[0], dp)))
         return [([res[0, j, sl] for sl in ch["slices"]], [res[1, j, sl] for sl in ch["slices"]]) for j in range(n_jobs)]
 
     def price_hawkesjd_chain_fused(self, ch: dict, params: np.ndarray, nb_steps_per_year: int, variable_type: int, seed: int,
@@ -1016,12 +1021,9 @@ class HipEngine:
         engine's session (ch: tilted_chain_arrays; params [J][SVMC_HAWKESJD_PARAMS]; gammas [J][G], every row a job's gammas):
         one stepping launch for all jobs, then each job's tilted payoff launches.  Returns per job what
         price_hawkesjd_chain_tilted_fused returns for it, J at most MANY_MAX_JOBS"""
-        params = np.ascontiguousarray(params, dtype=np.float64)
+        n_jobs, jobs = self._many_jobs(params, seeds, call_ids, "one seed, one call id and one row of gammas per job")
         gammas = np.ascontiguousarray(gammas, dtype=np.float64)
-        n_jobs = params.shape[0]
-        seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
-        ids = np.ascontiguousarray(call_ids, dtype=np.uint32)
-        if not (seeds.size == ids.size == n_jobs) or gammas.ndim != 2 or gammas.shape[0] != n_jobs:
+        if gammas.ndim != 2 or gammas.shape[0] != n_jobs:
             raise ValueError("one seed, one call id and one row of gammas per job")
         m, K, G = ch["m"], ch["total"], gammas.shape[1]
         dp = C.POINTER(C.c_double)
@@ -1030,8 +1032,7 @@ class HipEngine:
         sess = self.fused_chain_session(m, K)
         _lib.check(self.lib.svmc_hawkesjd_chain_price_tilted_many(
             sess, ch["ttms"].ctypes.data_as(dp), ch["forwards"].ctypes.data_as(dp), m, ch["strikes"].ctypes.data_as(dp),
-            ch["codes"].ctypes.data_as(C.POINTER(C.c_int8)), ch["offs"].ctypes.data_as(C.POINTER(C.c_size_t)), n_jobs,
-            params.ctypes.data_as(dp), seeds.ctypes.data_as(C.POINTER(C.c_uint64)), ids.ctypes.data_as(C.POINTER(C.c_uint32)),
+            ch["codes"].ctypes.data_as(C.POINTER(C.c_int8)), ch["offs"].ctypes.data_as(C.POINTER(C.c_size_t)), n_jobs, *jobs,
             int(nb_steps_per_year), gammas.ctypes.data_as(dp), G, int(bool(recenter)), prices.ctypes.data_as(dp),
             stderrs.ctypes.data_as(dp), stats.ctypes.data_as(dp)))
         # the C rows are [G K] with no padding; the host arrays above are padded to one double for an empty chain only

@@ -1,5 +1,6 @@
 """
-Chain driver shared by the LogSV and Heston Monte Carlo pricers.
+Chain drivers shared by the LogSV, Heston and Hawkes jump-diffusion Monte Carlo pricers: price_chain_on_engine, the phases
+of one chain on an engine, and the steps the four *_mc_chain_pricer*_many functions share (checks, streams, chunks, shapes).
 
 Restates the expiry loop of logsv_mc_chain_pricer / logsv_mc_chain_pricer_fixed_randoms /
 heston_mc_chain_pricer (reference pricers/logsv_pricer.py:806-867, :1100-1162,
@@ -17,11 +18,12 @@ pass a double to exercise the sharding logic on CPU.
 """
 from __future__ import annotations
 
-from typing import Callable, List, Sequence, Tuple
+from typing import Callable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .engine import LOG_RETURN, Q_VAR, option_type_codes, payoff_finalize, payoff_finalize_chain, payoff_shifts
+from .engine import LOG_RETURN, MANY_MAX_JOBS, Q_VAR, option_type_codes, payoff_finalize, payoff_finalize_chain, payoff_shifts
+from .utils.funcs import next_rng_call
 
 
 def variable_type_code(variable_type) -> int:
@@ -73,23 +75,51 @@ def price_chain_on_engine(engine, comm, n_path_total: int, ttms: np.ndarray, for
 
     # phase 4
     sums = comm.to_host(engine, sums_ptr, sums_handle, int(offs[-1]))
-    prices, stderrs = [], []
     if finalize is payoff_finalize and m > 1:
         # all expiries in one call into the library (the per-expiry loop below costs ~15 us of interpreter per expiry, time
         # in which the GPU has nothing queued: 120 -> 40 us for C4's 8 x 21 strikes); the same arithmetic, the same bits
         counts = [k.size for k in strikes]
         p_all, e_all = payoff_finalize_chain(sums, np.concatenate([s.ravel() for s in shifts]),
                                              np.repeat(np.asarray(discfactors, dtype=np.float64), counts), float(n_path_total))
-        lo = 0
-        for i in range(m):
-            hi = lo + counts[i]
-            shape = np.shape(strikes_ttms[i])
-            prices.append(p_all[lo:hi] if len(shape) == 1 else p_all[lo:hi].reshape(shape))
-            stderrs.append(e_all[lo:hi] if len(shape) == 1 else e_all[lo:hi].reshape(shape))
-            lo = hi
-        return prices, stderrs
-    for i in range(m):
-        p, e = finalize(sums[offs[i]:offs[i + 1]], shifts[i], float(discfactors[i]), float(n_path_total))
-        prices.append(p.reshape(np.shape(strikes_ttms[i])))
-        stderrs.append(e.reshape(np.shape(strikes_ttms[i])))
-    return prices, stderrs
+        hi = np.cumsum(counts)
+        cuts = list(zip(hi - counts, hi))
+        return chain_shaped([p_all[a:b] for a, b in cuts], strikes_ttms), chain_shaped([e_all[a:b] for a, b in cuts], strikes_ttms)
+    parts = [finalize(sums[offs[i]:offs[i + 1]], shifts[i], float(discfactors[i]), float(n_path_total)) for i in range(m)]
+    return chain_shaped([p for p, _ in parts], strikes_ttms), chain_shaped([e for _, e in parts], strikes_ttms)
+
+
+def chain_shaped(rows: Sequence[np.ndarray], strikes_ttms: Sequence[np.ndarray], shapes: Optional[list] = None) -> List[np.ndarray]:
+    """per-expiry result rows in the shapes of their strikes, as the reference returns them (a row that fits is returned itself);
+    shapes: those shapes, where a caller has many rows of one chain"""
+    if shapes is None:
+        shapes = [k.shape if isinstance(k, np.ndarray) else np.shape(k) for k in strikes_ttms]
+    return [a if a.shape == shape else a.reshape(shape) for a, shape in zip(rows, shapes)]
+
+
+# ---- the steps the four *_mc_chain_pricer*_many functions share; each function keeps its own checks, its loop of single calls and
+# its engine call inline, in its own order
+
+def check_many_args(params_list, seeds) -> list:
+    """the checks of a many-job call, made before any device work"""
+    params_list = list(params_list)
+    if seeds is not None and len(seeds) != len(params_list):
+        raise ValueError(f"seeds has {len(seeds)} entries for {len(params_list)} parameter sets")
+    return params_list
+
+
+def many_job_streams(n_params: int, seeds: Optional[Sequence[int]]) -> List[Tuple[int, int]]:
+    """the (seed, call id) of each job of a many-job call: seeds given -> (seed_j, 0); seeds None -> the process seed and
+    n_params consecutive call ids, in list order -- what as many single calls would take"""
+    return [next_rng_call(None if seeds is None else seeds[j]) for j in range(n_params)]
+
+
+def many_job_chunks(streams: List[Tuple[int, int]], rows: np.ndarray) -> List[tuple]:
+    """the jobs in engine calls of up to MANY_MAX_JOBS, in order: [(first job, its rows, their seeds, their call ids)]"""
+    parts = [(q0, streams[q0:q0 + MANY_MAX_JOBS]) for q0 in range(0, len(rows), MANY_MAX_JOBS)]
+    return [(q0, rows[q0:q0 + MANY_MAX_JOBS], [s for s, _ in part], [c for _, c in part]) for q0, part in parts]
+
+
+def many_jobs_shaped(out: list, strikes_ttms: Sequence[np.ndarray]) -> list:
+    """every job's (prices, stderrs) of the engine's many-job call in the shapes of the strikes"""
+    shapes = [k.shape if isinstance(k, np.ndarray) else np.shape(k) for k in strikes_ttms]
+    return [(chain_shaped(pr, strikes_ttms, shapes), chain_shaped(se, strikes_ttms, shapes)) for pr, se in out]

@@ -49,9 +49,9 @@ from .. import _lib
 from .. import dist as svdist
 from ..analytic import ODE_ATOL, ODE_RTOL, AnalyticGrid, chain_prices_from_sums, chain_sums
 from ..data.option_chain import OptionChain
-from ..engine import (MANY_MAX_JOBS, DeviceBuffer, get_engine, marshalled_chain, option_type_codes, tilted_chain_arrays,
+from ..engine import (DeviceBuffer, get_engine, marshalled_chain, option_type_codes, tilted_chain_arrays,
                       tilted_gammas, tilted_type_codes)
-from ..mc_chain import variable_type_code
+from ..mc_chain import chain_shaped, check_many_args, many_job_chunks, many_job_streams, many_jobs_shaped, variable_type_code
 from ..utils import mgf_pricer as mgfp
 from ..utils.calibration import ImpliedVolObjective, chain_calibration_weights
 from ..utils.config import VariableType
@@ -653,8 +653,7 @@ def hawkesjd_mc_chain_pricer(ttms: np.ndarray, forwards: np.ndarray, discfactors
     ch = marshalled_chain(np.asarray(ttms), np.asarray(forwards), np.asarray(discfactors), strikes_ttms,
                           [option_type_codes(t) for t in optiontypes_ttms])
     prices, stderrs = eng.price_hawkesjd_chain_fused(ch, block, int(nb_steps_per_year), LOG_RETURN, rng_seed, call_id)
-    return ([a.reshape(np.shape(k)) for a, k in zip(prices, strikes_ttms)],
-            [a.reshape(np.shape(k)) for a, k in zip(stderrs, strikes_ttms)])
+    return chain_shaped(prices, strikes_ttms), chain_shaped(stderrs, strikes_ttms)
 
 
 def hawkesjd_mc_chain_pricer_with_risk_premia_gammas(ttms: np.ndarray, forwards: np.ndarray, discfactors: np.ndarray,
@@ -684,8 +683,7 @@ def hawkesjd_mc_chain_pricer_with_risk_premia_gammas(ttms: np.ndarray, forwards:
     K^(1+gamma) F^(-gamma), so it equals the payoff expectation priced here only at F = 1 (the paper's case); this function
     prices the payoff as written for any F."""
     _check_variable_type(variable_type)
-    if devices is not None or (comm.world if comm is not None else svdist.get_default_comm().world) > 1:
-        raise NotImplementedError("hawkesjd_mc_chain_pricer_with_risk_premia: not sharded over ranks or devices")
+    _refuse_sharded("hawkesjd_mc_chain_pricer_with_risk_premia", comm, devices)
     strikes_ttms = [np.asarray(k, dtype=np.float64) for k in strikes_ttms]
     codes = [tilted_type_codes(t) for t in optiontypes_ttms]                # ValueError("not implemented")
     ch = tilted_chain_arrays(forwards, strikes_ttms, codes, risk_premia_gammas, ttms=ttms)
@@ -727,8 +725,8 @@ def _model_kwargs(params: HawkesJDParams) -> Dict[str, Any]:
     return kw
 
 
-def _refuse_sharded_many(name: str, comm, devices) -> None:
-    """a sharded request raises what the single pricer raises"""
+def _refuse_sharded(name: str, comm, devices) -> None:
+    """the tilted pricers and the many-job ones run on one device only"""
     if devices is not None or (comm.world if comm is not None else svdist.get_default_comm().world) > 1:
         raise NotImplementedError(f"{name}: not sharded over ranks or devices")
 
@@ -746,12 +744,11 @@ def hawkesjd_mc_chain_pricer_many(params_list: Sequence[HawkesJDParams], ttms: n
     MANY_MAX_JOBS jobs are stepped by ONE launch (svmc_hawkesjd_chain_price_many; longer lists in several calls, in order); more
     than 16 expiries is a loop of single calls -- the same numbers.  Sharded requests (devices=, a world above one) raise as the
     single pricer does; params' risk_premia_gamma is ignored, as there.  Not in the reference API."""
-    from .logsv_pricer import check_many_args, many_job_streams
     params_list = check_many_args(params_list, seeds)
     if not params_list:
         return []
     _check_variable_type(variable_type)
-    _refuse_sharded_many("hawkesjd_mc_chain_pricer_many", comm, devices)
+    _refuse_sharded("hawkesjd_mc_chain_pricer_many", comm, devices)
     strikes_ttms = [np.asarray(k, dtype=np.float64) for k in strikes_ttms]
     optiontypes_ttms = [np.asarray(t) for t in optiontypes_ttms]
     if len(ttms) > 16:
@@ -766,12 +763,9 @@ def hawkesjd_mc_chain_pricer_many(params_list: Sequence[HawkesJDParams], ttms: n
                           [option_type_codes(t) for t in optiontypes_ttms])
     eng = get_engine(int(nb_path))
     out = []
-    for q0 in range(0, len(rows), MANY_MAX_JOBS):
-        part = streams[q0:q0 + MANY_MAX_JOBS]
-        out += eng.price_chain_many_fused(ch, "hawkesjd", rows[q0:q0 + MANY_MAX_JOBS], [s for s, _ in part], [c for _, c in part],
-                                          0, int(nb_steps_per_year), LOG_RETURN)
-    return [([a.reshape(np.shape(k)) for a, k in zip(pr, strikes_ttms)], [a.reshape(np.shape(k)) for a, k in zip(se, strikes_ttms)])
-            for pr, se in out]
+    for _, part, job_seeds, ids in many_job_chunks(streams, rows):
+        out += eng.price_chain_many_fused(ch, "hawkesjd", part, job_seeds, ids, 0, int(nb_steps_per_year), LOG_RETURN)
+    return many_jobs_shaped(out, strikes_ttms)
 
 
 def many_job_gammas(risk_premia_gammas, n_jobs: int) -> np.ndarray:
@@ -807,12 +801,11 @@ def hawkesjd_mc_chain_pricer_with_risk_premia_gammas_many(params_list: Sequence[
     third item [gamma] -> (normalizers, gamma_forwards, stats) -- bit for bit; streams as hawkesjd_mc_chain_pricer_many.  The
     single function's checks: 'C' / 'P' only (ValueError("not implemented")), LOG_RETURN only, not sharded; discfactors and the
     params' risk_premia_gamma are accepted and ignored.  More than 16 expiries is a loop of single calls."""
-    from .logsv_pricer import check_many_args, many_job_streams
     params_list = check_many_args(params_list, seeds)
     if not params_list:
         return []
     _check_variable_type(variable_type)
-    _refuse_sharded_many("hawkesjd_mc_chain_pricer_with_risk_premia_gammas_many", comm, devices)
+    _refuse_sharded("hawkesjd_mc_chain_pricer_with_risk_premia_gammas_many", comm, devices)
     gammas = many_job_gammas(risk_premia_gammas, len(params_list))
     strikes_ttms = [np.asarray(k, dtype=np.float64) for k in strikes_ttms]
     codes = [tilted_type_codes(t) for t in optiontypes_ttms]                # ValueError("not implemented")
@@ -827,10 +820,9 @@ def hawkesjd_mc_chain_pricer_with_risk_premia_gammas_many(params_list: Sequence[
     rows = np.stack([_model_block(p) for p in params_list])
     eng = get_engine(int(nb_path))
     out = []
-    for q0 in range(0, len(rows), MANY_MAX_JOBS):
-        part = streams[q0:q0 + MANY_MAX_JOBS]
-        out += eng.price_hawkesjd_chain_tilted_many_fused(ch, rows[q0:q0 + MANY_MAX_JOBS], int(nb_steps_per_year), [s for s, _ in part],
-                                                          [c for _, c in part], gammas[q0:q0 + MANY_MAX_JOBS], bool(recenter_forward))
+    for q0, part, job_seeds, ids in many_job_chunks(streams, rows):
+        out += eng.price_hawkesjd_chain_tilted_many_fused(ch, part, int(nb_steps_per_year), job_seeds, ids, gammas[q0:q0 + len(part)],
+                                                          bool(recenter_forward))
     if not return_forwards:
         return [(prices, stderrs) for prices, stderrs, _ in out]
     return [(prices, stderrs, [(st[:, 0].copy(), st[:, 2].copy(), st) for st in stats]) for prices, stderrs, stats in out]

@@ -17,14 +17,15 @@ import numpy as np
 
 from .. import dist as svdist
 from ..data.option_chain import OptionChain
-from ..engine import HESTON_EULER_FLOOR, HESTON_QE, MANY_MAX_JOBS, get_engine, marshalled_chain, option_type_codes
-from ..mc_chain import price_chain_on_engine, variable_type_code
+from ..engine import HESTON_EULER_FLOOR, HESTON_QE, get_engine, marshalled_chain, option_type_codes
+from ..mc_chain import (chain_shaped, check_many_args, many_job_chunks, many_job_streams, many_jobs_shaped, price_chain_on_engine,
+                        variable_type_code)
 from ..utils.calibration import ImpliedVolObjective, chain_calibration_weights, minimize_slsqp
 from ..utils.config import VariableType
 from ..utils.funcs import next_rng_call, set_time_grid, time_grid_steps, timer
 from ..analytic import AnalyticGrid, chain_prices_from_sums, chain_sums
 from ..utils import mgf_pricer as mgfp
-from .logsv_pricer import _broadcast_state, check_many_args, many_job_streams
+from .logsv_pricer import _broadcast_state
 from .model_pricer import ModelParams, ModelPricer
 
 
@@ -228,12 +229,9 @@ def heston_mc_chain_pricer_many(params_list: Sequence[HestonParams], ttms: np.nd
     ch = marshalled_chain(ttms, forwards, discfactors, strikes_ttms, [option_type_codes(t) for t in optiontypes_ttms])
     eng = get_engine(nb_path)
     out = []
-    for q0 in range(0, len(rows), MANY_MAX_JOBS):
-        part = streams[q0:q0 + MANY_MAX_JOBS]
-        out += eng.price_chain_many_fused(ch, "heston", rows[q0:q0 + MANY_MAX_JOBS], [s for s, _ in part], [c for _, c in part],
-                                          code, nb_steps_per_year, variable_type_code(variable_type))
-    return [([a.reshape(np.shape(k)) for a, k in zip(pr, strikes_ttms)], [a.reshape(np.shape(k)) for a, k in zip(se, strikes_ttms)])
-            for pr, se in out]
+    for _, part, job_seeds, ids in many_job_chunks(streams, rows):
+        out += eng.price_chain_many_fused(ch, "heston", part, job_seeds, ids, code, nb_steps_per_year, variable_type_code(variable_type))
+    return many_jobs_shaped(out, strikes_ttms)
 
 
 def simulate_heston_x_vol_terminal(ttm: float, x0: np.ndarray, var0: np.ndarray, qvar0: np.ndarray, theta: float,
@@ -290,8 +288,7 @@ def heston_mc_chain_pricer(ttms: np.ndarray, forwards: np.ndarray, discfactors: 
         ch = marshalled_chain(ttms, forwards, discfactors, strikes_ttms, [option_type_codes(t) for t in optiontypes_ttms])
         prices, stderrs = eng.price_heston_chain_fused(ch, v0, theta, kappa, rho, volvol, code, nb_steps_per_year, vt_code,
                                                        rng_seed, call_id)
-        return ([a.reshape(np.shape(k)) for a, k in zip(prices, strikes_ttms)],
-                [a.reshape(np.shape(k)) for a, k in zip(stderrs, strikes_ttms)])
+        return chain_shaped(prices, strikes_ttms), chain_shaped(stderrs, strikes_ttms)
     grids, t0 = [], 0.0
     for ttm in ttms:
         nb, dt = time_grid_steps(ttm=ttm - t0, nb_steps_per_year=nb_steps_per_year)

@@ -19,8 +19,9 @@ import pandas as pd
 
 from .. import dist as svdist
 from ..data.option_chain import OptionChain
-from ..engine import MANY_MAX_JOBS, DeviceRandoms, get_engine, marshalled_chain, option_type_codes, payoff_finalize
-from ..mc_chain import price_chain_on_engine, variable_type_code
+from ..engine import DeviceRandoms, get_engine, marshalled_chain, option_type_codes, payoff_finalize
+from ..mc_chain import (chain_shaped, check_many_args, many_job_chunks, many_job_streams, many_jobs_shaped, price_chain_on_engine,
+                        variable_type_code)
 from ..utils.calibration import ImpliedVolObjective, chain_calibration_weights, minimize_slsqp
 from ..utils.config import VariableType
 from ..utils.funcs import histogram_series, next_rng_call, set_time_grid, time_grid_steps, timer
@@ -785,8 +786,7 @@ def logsv_mc_chain_pricer(ttms: np.ndarray, forwards: np.ndarray, discfactors: n
             ch = marshalled_chain(ttms, forwards, discfactors, strikes_ttms, [option_type_codes(t) for t in optiontypes_ttms])
             prices, stderrs = eng.price_logsv_chain_fused(ch, v0, theta, kappa1, kappa2, beta, volvol, vol_backbone_etas,
                                                           is_spot_measure, nb_steps_per_year, vt_code, rng_seed, call_id)
-            return ([_shaped_like(a, k) for a, k in zip(prices, strikes_ttms)],
-                    [_shaped_like(a, k) for a, k in zip(stderrs, strikes_ttms)])
+            return chain_shaped(prices, strikes_ttms), chain_shaped(stderrs, strikes_ttms)
     grids, t0 = [], 0.0
     for ttm in ttms:
         nb, dt = time_grid_steps(ttm=ttm - t0, nb_steps_per_year=nb_steps_per_year)
@@ -795,20 +795,6 @@ def logsv_mc_chain_pricer(ttms: np.ndarray, forwards: np.ndarray, discfactors: n
     return _logsv_mc_chain_on_grids(grids, rng_seed, call_id, comm, ttms, forwards, discfactors, strikes_ttms, optiontypes_ttms,
                                     v0, theta, kappa1, kappa2, beta, volvol, vol_backbone_etas, is_spot_measure, nb_path,
                                     variable_type)
-
-
-def many_job_streams(n_params: int, seeds: Optional[Sequence[int]]) -> List[Tuple[int, int]]:
-    """the (seed, call id) of each job of a many-job call: seeds given -> (seed_j, 0); seeds None -> the process seed and
-    n_params consecutive call ids, in list order -- what as many single calls would take"""
-    return [next_rng_call(None if seeds is None else seeds[j]) for j in range(n_params)]
-
-
-def check_many_args(params_list, seeds) -> list:
-    """the checks of a many-job call, made before any device work"""
-    params_list = list(params_list)
-    if seeds is not None and len(seeds) != len(params_list):
-        raise ValueError(f"seeds has {len(seeds)} entries for {len(params_list)} parameter sets")
-    return params_list
 
 
 def logsv_mc_chain_pricer_many(params_list: Sequence[LogSvParams], ttms: np.ndarray, forwards: np.ndarray,
@@ -846,12 +832,10 @@ def logsv_mc_chain_pricer_many(params_list: Sequence[LogSvParams], ttms: np.ndar
     ch = marshalled_chain(ttms, forwards, discfactors, strikes_ttms, [option_type_codes(t) for t in optiontypes_ttms])
     eng = get_engine(nb_path)
     out = []
-    for q0 in range(0, len(rows), MANY_MAX_JOBS):
-        part = streams[q0:q0 + MANY_MAX_JOBS]
-        out += eng.price_chain_many_fused(ch, "logsv", rows[q0:q0 + MANY_MAX_JOBS], [s for s, _ in part], [c for _, c in part],
-                                          int(bool(is_spot_measure)), nb_steps_per_year, variable_type_code(variable_type))
-    return [([_shaped_like(a, k) for a, k in zip(pr, strikes_ttms)], [_shaped_like(a, k) for a, k in zip(se, strikes_ttms)])
-            for pr, se in out]
+    for _, part, job_seeds, ids in many_job_chunks(streams, rows):
+        out += eng.price_chain_many_fused(ch, "logsv", part, job_seeds, ids, int(bool(is_spot_measure)), nb_steps_per_year,
+                                          variable_type_code(variable_type))
+    return many_jobs_shaped(out, strikes_ttms)
 
 
 def _logsv_mc_chain_on_grids(grids, rng_seed: int, call_id: int, comm, ttms, forwards, discfactors, strikes_ttms,
@@ -953,7 +937,7 @@ def logsv_mc_chain_pricer_fixed_randoms(ttms: np.ndarray, forwards: np.ndarray, 
                                          [c.ravel() for c in codes], v0, theta, kappa1, kappa2, beta, volvol,
                                          vol_backbone_etas, is_spot_measure, variable_type_code(variable_type),
                                          want_ivols=return_ivols)
-        return tuple([_shaped_like(a, k) for a, k in zip(part, strikes_ttms)] for part in out)
+        return tuple(chain_shaped(part, strikes_ttms) for part in out)
     if resident and resident.is_frozen:
         # frozen randoms, sharded over ranks (or the fused driver switched off): the on-device-RNG chain on the stream the
         # object names -- the same numbers the fused route gives on one GPU
@@ -986,12 +970,6 @@ def logsv_mc_chain_pricer_fixed_randoms(ttms: np.ndarray, forwards: np.ndarray, 
     if not return_ivols:
         return prices, stderrs
     return prices, stderrs, _host_ivols(prices, ttms, forwards, strikes_ttms, optiontypes_ttms, discfactors)
-
-
-def _shaped_like(a: np.ndarray, k) -> np.ndarray:
-    """a result row in the shape of the strikes it belongs to (the reference returns arrays shaped like strikes_ttms[i])"""
-    shape = k.shape if isinstance(k, np.ndarray) else np.shape(k)
-    return a if a.shape == shape else a.reshape(shape)
 
 
 def _host_ivols(prices, ttms, forwards, strikes_ttms, optiontypes_ttms, discfactors) -> List[np.ndarray]:
@@ -1031,7 +1009,7 @@ def logsv_mc_chain_pricer_fixed_randoms_batch(params_list: Sequence[LogSvParams]
                                               want_ivols=return_ivols)
         if all(np.ndim(k) == 1 for k in strikes_ttms):
             return out
-        return [tuple([_shaped_like(a, k) for a, k in zip(part, strikes_ttms)] for part in res) for res in out]
+        return [tuple(chain_shaped(part, strikes_ttms) for part in res) for res in out]
     return [logsv_mc_chain_pricer_fixed_randoms(ttms=ttms, forwards=forwards, discfactors=discfactors,
                                                 strikes_ttms=strikes_ttms, optiontypes_ttms=optiontypes_ttms, W0s=W0s,
                                                 W1s=None, dts=None, v0=p.sigma0, theta=p.theta, kappa1=p.kappa1,
