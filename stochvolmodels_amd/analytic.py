@@ -358,33 +358,44 @@ def chain_prices_from_sums(sums: List[List[np.ndarray]], inversion: str, ttms, f
     return out
 
 
+def _given_log_mgf_call(sizes: Sequence[int], uploads: Sequence[np.ndarray], out_shape, launch: Callable) -> np.ndarray:
+    """the scaffold of the three given-log-MGF functions below: scratch DeviceBuffers of `sizes` doubles -- the first
+    len(uploads) of them filled from those host arrays, the last one the result's -- then launch(lib, *buffers), ONE download of
+    `out_shape` doubles from the last buffer, one synchronize, and the frees whatever happened"""
+    lib = _lib.load()
+    bufs = [DeviceBuffer(n) for n in sizes]
+    try:
+        for buf, z in zip(bufs, uploads):
+            _lib.check(lib.svmc_memcpy_h2d(buf.ptr, z.ctypes.data, z.nbytes, None))
+        launch(lib, *bufs)
+        out = np.empty(out_shape)
+        if out.size:
+            _lib.check(lib.svmc_memcpy_d2h(out.ctypes.data, bufs[-1].ptr, out.nbytes, None))
+        _lib.check(lib.svmc_stream_synchronize(None))
+        return out
+    finally:
+        for b in bufs:
+            b.free()
+
+
 def gamma_slice_prices(phi: np.ndarray, log_mgf: np.ndarray, gamma: float, shortcut: bool, normalizer: float,
                        gamma_forward: float, forward: float, strikes: np.ndarray, type_codes: np.ndarray) -> np.ndarray:
     """one slice under the risk-premia kernel from a given log-MGF (svmc_mgf_gamma_slice_batch at one set): uploads the grid,
     the log-MGF and the slice's normalizer / gamma forward, returns the undiscounted prices"""
-    lib = _lib.load()
     phi = np.ascontiguousarray(phi, dtype=np.complex128)
     log_mgf = np.ascontiguousarray(log_mgf, dtype=np.complex128)
     strikes = np.ascontiguousarray(strikes, dtype=np.float64)
     codes = np.ascontiguousarray(type_codes, dtype=np.int32)
     nf = np.array([normalizer, gamma_forward], dtype=np.float64)
     gammas, short = np.array([gamma], dtype=np.float64), np.array([int(bool(shortcut))], dtype=np.int32)
-    bufs = [DeviceBuffer(2 * phi.size), DeviceBuffer(2 * log_mgf.size), DeviceBuffer(2), DeviceBuffer(max(strikes.size, 1))]
-    try:
-        for buf, z in zip(bufs[:3], (phi, log_mgf, nf)):
-            _lib.check(lib.svmc_memcpy_h2d(buf.ptr, z.ctypes.data, z.nbytes, None))
-        pf, pi = C.POINTER(C.c_double), C.POINTER(C.c_int)
-        _lib.check(lib.svmc_mgf_gamma_slice_batch(bufs[0].ptr, bufs[1].ptr, phi.size, 1, gammas.ctypes.data_as(pf),
-                                                  short.ctypes.data_as(pi), bufs[2].ptr, bufs[2].offset(1), 0, float(forward),
-                                                  strikes.ctypes.data_as(pf), codes.ctypes.data_as(pi), strikes.size,
-                                                  bufs[3].ptr, None))
-        out = np.empty(strikes.size)
-        _lib.check(lib.svmc_memcpy_d2h(out.ctypes.data, bufs[3].ptr, out.nbytes, None))
-        _lib.check(lib.svmc_stream_synchronize(None))
-        return out
-    finally:
-        for b in bufs:
-            b.free()
+    pf, pi = C.POINTER(C.c_double), C.POINTER(C.c_int)
+
+    def launch(lib, dphi, dlm, dnf, out):
+        _lib.check(lib.svmc_mgf_gamma_slice_batch(dphi.ptr, dlm.ptr, phi.size, 1, gammas.ctypes.data_as(pf),
+                                                  short.ctypes.data_as(pi), dnf.ptr, dnf.offset(1), 0, float(forward),
+                                                  strikes.ctypes.data_as(pf), codes.ctypes.data_as(pi), strikes.size, out.ptr, None))
+
+    return _given_log_mgf_call((2 * phi.size, 2 * log_mgf.size, 2, max(strikes.size, 1)), (phi, log_mgf, nf), strikes.size, launch)
 
 
 def pdf_slices(var_grids: np.ndarray, log_mgfs: np.ndarray, space_grids: np.ndarray, shifts, scales,
@@ -392,7 +403,6 @@ def pdf_slices(var_grids: np.ndarray, log_mgfs: np.ndarray, space_grids: np.ndar
     """pdf_with_mgf_grid for [n_sets] given log-MGFs in one launch (svmc_mgf_pdf_slice_batch): var_grids, log_mgfs
     [n_sets][n_grid] complex, space_grids [n_sets][n_space], shifts / scales [n_sets] -> [n_sets][n_space].  Uploads its
     inputs; the pricers keep the log-MGF on the device instead (AnalyticGrid.pdf_sums)."""
-    lib = _lib.load()
     var = np.ascontiguousarray(var_grids, dtype=np.complex128)
     lm = np.ascontiguousarray(log_mgfs, dtype=np.complex128)
     space = np.ascontiguousarray(space_grids, dtype=np.float64)
@@ -400,49 +410,33 @@ def pdf_slices(var_grids: np.ndarray, log_mgfs: np.ndarray, space_grids: np.ndar
     if not (var.ndim == 2 and var.shape == lm.shape and space.ndim == 2 and space.shape[0] == var.shape[0]
             and sh.shape == sc.shape == (var.shape[0],)):
         raise ValueError("pdf_slices: var_grids / log_mgfs [n_sets][n_grid], space_grids [n_sets][n_space], shifts / scales [n_sets]")
-    bufs = [DeviceBuffer(2 * var.size), DeviceBuffer(2 * lm.size), DeviceBuffer(max(space.size, 1)), DeviceBuffer(max(space.size, 1))]
-    try:
-        for buf, z in zip(bufs[:3], (var, lm, space)):
-            _lib.check(lib.svmc_memcpy_h2d(buf.ptr, z.ctypes.data, z.nbytes, None))
-        pf = C.POINTER(C.c_double)
-        _lib.check(lib.svmc_mgf_pdf_slice_batch(bufs[0].ptr, bufs[1].ptr, var.shape[1], var.shape[0], bufs[2].ptr, space.shape[1],
-                                                sh.ctypes.data_as(pf), sc.ctypes.data_as(pf), int(bool(is_simpson)), bufs[3].ptr,
-                                                None))
-        out = np.empty(space.shape)
-        if out.size:
-            _lib.check(lib.svmc_memcpy_d2h(out.ctypes.data, bufs[3].ptr, out.nbytes, None))
-        _lib.check(lib.svmc_stream_synchronize(None))
-        return out
-    finally:
-        for b in bufs:
-            b.free()
+    pf = C.POINTER(C.c_double)
+
+    def launch(lib, dvar, dlm, dspace, out):
+        _lib.check(lib.svmc_mgf_pdf_slice_batch(dvar.ptr, dlm.ptr, var.shape[1], var.shape[0], dspace.ptr, space.shape[1],
+                                                sh.ctypes.data_as(pf), sc.ctypes.data_as(pf), int(bool(is_simpson)), out.ptr, None))
+
+    return _given_log_mgf_call((2 * var.size, 2 * lm.size, max(space.size, 1), max(space.size, 1)), (var, lm, space), space.shape,
+                               launch)
 
 
 def digital_slice_sums(phis: np.ndarray, log_mgfs: np.ndarray, forward: float, strikes: np.ndarray, negative_contour: bool,
                        is_simpson: bool = True) -> np.ndarray:
     """the strike sums of digital_slice_pricer_with_mgf_grid for [n_sets] given log-MGFs in one launch
     (svmc_mgf_digital_slice_batch) -> [n_sets][n_strikes]"""
-    lib = _lib.load()
     phi = np.ascontiguousarray(phis, dtype=np.complex128)
     lm = np.ascontiguousarray(log_mgfs, dtype=np.complex128)
     strikes = np.ascontiguousarray(strikes, dtype=np.float64).ravel()
     if not (phi.ndim == 2 and phi.shape == lm.shape):
         raise ValueError("digital_slice_sums: phis / log_mgfs [n_sets][n_grid]")
-    bufs = [DeviceBuffer(2 * phi.size), DeviceBuffer(2 * lm.size), DeviceBuffer(max(strikes.size * phi.shape[0], 1))]
-    try:
-        for buf, z in zip(bufs[:2], (phi, lm)):
-            _lib.check(lib.svmc_memcpy_h2d(buf.ptr, z.ctypes.data, z.nbytes, None))
-        _lib.check(lib.svmc_mgf_digital_slice_batch(bufs[0].ptr, bufs[1].ptr, phi.shape[1], phi.shape[0], float(forward),
+
+    def launch(lib, dphi, dlm, out):
+        _lib.check(lib.svmc_mgf_digital_slice_batch(dphi.ptr, dlm.ptr, phi.shape[1], phi.shape[0], float(forward),
                                                     strikes.ctypes.data_as(C.POINTER(C.c_double)), strikes.size,
-                                                    int(bool(negative_contour)), int(bool(is_simpson)), bufs[2].ptr, None))
-        out = np.empty((phi.shape[0], strikes.size))
-        if out.size:
-            _lib.check(lib.svmc_memcpy_d2h(out.ctypes.data, bufs[2].ptr, out.nbytes, None))
-        _lib.check(lib.svmc_stream_synchronize(None))
-        return out
-    finally:
-        for b in bufs:
-            b.free()
+                                                    int(bool(negative_contour)), int(bool(is_simpson)), out.ptr, None))
+
+    return _given_log_mgf_call((2 * phi.size, 2 * lm.size, max(strikes.size * phi.shape[0], 1)), (phi, lm),
+                               (phi.shape[0], strikes.size), launch)
 
 
 def digital_prices_from_sums(sums: np.ndarray, optiontypes: Sequence, discfactor: float, is_all_calls: bool) -> np.ndarray:

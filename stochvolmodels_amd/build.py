@@ -30,7 +30,7 @@ ISA_KERNELS = ("logsv_rng_kernel", "logsv_chain_rng_kernel", "heston_rng_kernelI
 SOURCES = ("svmc_runtime.hip", "svmc_kernels.hip", "svmc_analytic.hip", "svmc_chain.hip", "svmc_comm.hip", "svmc_multi.hip",
            "svmc_hawkes.hip", "svmc_density.hip")
 HEADERS = ("svmc_internal.h", "svmc_models.h", "svmc_rng.h", "svmc_math.h", "svmc_log_table.h", "svmc_icdf_table.h", "svmc_black.h", "svmc_ode.h", "svmc_dop853.h",
-           "svmc_slice.h", "svmc_complex.h")
+           "svmc_slice.h", "svmc_complex.h", "svmc_mgf_slice.h")
 ARCH = "gfx950"
 # the test-only device build of the math, complex and Black-76 helpers (tests/test_gpu_device_math.py): not part of the
 # package or its C ABI, built here so that it is compiled whenever the library is, with the library's flags

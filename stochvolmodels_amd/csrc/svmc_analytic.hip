@@ -20,6 +20,7 @@
 #include "svmc_complex.h"
 #include "svmc_ode.h"
 #include "svmc_dop853.h"
+#include "svmc_mgf_slice.h"
 
 #ifndef SVMC_ODE_DOP853
 #define SVMC_ODE_DOP853 1              // A/B hook: 0 = the Dormand-Prince 5(4) pair of rounds 1-3
@@ -487,71 +488,41 @@ __global__ __launch_bounds__(AB) void heston_mgf_grid_kernel(const cd *__restric
     log_mgf[j] = a_t1 + v0 * b_t1;
 }
 
-struct StrikeArgs {
-    double x[32];   // log(forward / strike)
-    int k;
-};
-
 // one block per strike; legacy Simpson weights (utils/mgf_pricer.py:158-171): 1,4,2,...,  every odd index 4
-__global__ __launch_bounds__(256) void mgf_vanilla_slice_kernel(const cd *__restrict__ phi, const cd *__restrict__ log_mgf,
-                                                                int n_grid, StrikeArgs sa, double *__restrict__ capped,
-                                                                int capped_ld)
+__global__ __launch_bounds__(MGF_SLICE_BLOCK) void mgf_vanilla_slice_kernel(const cd *__restrict__ phi,
+                                                                            const cd *__restrict__ log_mgf, int n_grid,
+                                                                            SliceStrikes sa, double *__restrict__ capped,
+                                                                            int capped_ld)
 {
     __shared__ double lds[4];
-    const double PI = 3.14159265358979323846;
     phi += static_cast<size_t>(blockIdx.y) * n_grid;                 // blockIdx.y: the parameter set of a batched call
     log_mgf += static_cast<size_t>(blockIdx.y) * n_grid;
     capped += static_cast<size_t>(blockIdx.y) * capped_ld;
     const double x = sa.x[blockIdx.x];
     const double h = phi[1].im - phi[0].im;
-    double s = 0.0;
-    for (int j = threadIdx.x; j < n_grid; j += 256) {
-        double w = 2.0;
-        if (j == 0 || j == n_grid - 1) w = 1.0;
-        if (j & 1) w = 4.0;
+    const double total = mgf_slice_nansum(n_grid, lds, [&](int j) {
         const double p = phi[j].im;
-        const double pw = ((h / 3.0) * w / PI) / (p * p + 0.25);
+        const double pw = (legacy_weight(phi, j, n_grid, h, 1) / PI) / (p * p + 0.25);
         const cd e = cexp_(log_mgf[j] - x * phi[j]);
-        const double term = pw * e.re;
-        if (term == term) s += term;                                                            // nansum
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) capped[blockIdx.x] = ((lds[0] + lds[1]) + lds[2]) + lds[3];
+        return pw * e.re;
+    });
+    if (threadIdx.x == 0) capped[blockIdx.x] = total;
 }
 
 // options on quadratic variance, utils/mgf_pricer.py:322-356: one block per strike,
 // sum_j Re[ w_j / (pi psi_j^2) exp(K ttm psi_j + log E_j) ] over the 40 000-point psi grid
-__global__ __launch_bounds__(256) void mgf_qvar_slice_kernel(const cd *__restrict__ psi, const cd *__restrict__ log_mgf,
-                                                             int n_grid, StrikeArgs sa, double *__restrict__ capped)
+__global__ __launch_bounds__(MGF_SLICE_BLOCK) void mgf_qvar_slice_kernel(const cd *__restrict__ psi, const cd *__restrict__ log_mgf,
+                                                                         int n_grid, SliceStrikes sa, double *__restrict__ capped)
 {
     __shared__ double lds[4];
-    const double PI = 3.14159265358979323846;
     const double kt = sa.x[blockIdx.x];                  // strike * ttm
     const double h = psi[1].im - psi[0].im;
-    double s = 0.0;
-    for (int j = threadIdx.x; j < n_grid; j += 256) {
-        double w = 2.0;
-        if (j == 0 || j == n_grid - 1) w = 1.0;
-        if (j & 1) w = 4.0;
+    const double total = mgf_slice_nansum(n_grid, lds, [&](int j) {
         const cd ps = psi[j];
-        const cd term = (C((h / 3.0) * w / PI) / (ps * ps)) * cexp_(kt * ps + log_mgf[j]);
-        if (term.re == term.re) s += term.re;                                                   // nansum
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) capped[blockIdx.x] = ((lds[0] + lds[1]) + lds[2]) + lds[3];
-}
-
-static int check_launch_a(const char *what)
-{
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(SVMC_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
-    return SVMC_OK;
+        const cd term = (C(legacy_weight(psi, j, n_grid, h, 1) / PI) / (ps * ps)) * cexp_(kt * ps + log_mgf[j]);
+        return term.re;
+    });
+    if (threadIdx.x == 0) capped[blockIdx.x] = total;
 }
 
 }  // namespace svmc
@@ -597,7 +568,7 @@ int svmc_logsv_mgf_grid_batch(const double *phi, const double *psi, size_t n_gri
                                reinterpret_cast<const cd *>(psi) + off, n_grid, ttm, sets, reinterpret_cast<cd *>(a) + off * n_coef,
                                reinterpret_cast<cd *>(log_mgf) + off, rtol, atol);
     }
-    return check_launch_a(fn);
+    return check_launch(fn);
 }
 
 int svmc_logsv_mgf_grid(const double *phi, const double *psi, size_t n_grid, double ttm, double sigma0, double theta,
@@ -620,7 +591,7 @@ int svmc_heston_mgf_grid(const double *phi, const double *psi, size_t n_grid, do
                        as_stream(stream), reinterpret_cast<const cd *>(phi), reinterpret_cast<const cd *>(psi), n_grid, ttm,
                        v0, theta, kappa, volvol, rho, reinterpret_cast<cd *>(a), reinterpret_cast<cd *>(b), have_t0,
                        reinterpret_cast<cd *>(log_mgf));
-    return check_launch_a("svmc_heston_mgf_grid");
+    return check_launch("svmc_heston_mgf_grid");
 }
 
 int svmc_mgf_vanilla_slice_batch(const double *phi, const double *log_mgf, size_t n_grid, int n_sets, double forward,
@@ -630,15 +601,15 @@ int svmc_mgf_vanilla_slice_batch(const double *phi, const double *log_mgf, size_
     SVMC_REQUIRE(n_grid >= 3 && n_grid < (1u << 30), "svmc_mgf_vanilla_slice: grid too short or too long");
     SVMC_REQUIRE(n_strikes == 0 || strikes_host, "svmc_mgf_vanilla_slice: null strikes");
     SVMC_REQUIRE(n_sets >= 1 && n_sets <= 65535, "svmc_mgf_vanilla_slice: n_sets out of range");
-    for (size_t k0 = 0; k0 < n_strikes; k0 += 32) {
-        StrikeArgs sa;
-        sa.k = static_cast<int>((n_strikes - k0 < 32) ? (n_strikes - k0) : 32);
-        for (int k = 0; k < 32; ++k) sa.x[k] = (k < sa.k) ? log(forward / strikes_host[k0 + k]) : 0.0;    // :199
-        hipLaunchKernelGGL(mgf_vanilla_slice_kernel, dim3(sa.k, static_cast<unsigned>(n_sets)), dim3(256), 0,
+    for (size_t k0 = 0; k0 < n_strikes; k0 += MGF_SLICE_STRIKES) {
+        SliceStrikes sa;
+        const int k_here = fill_strike_chunk(sa.x, strikes_host, k0, n_strikes,
+                                             [&](double strike) { return log(forward / strike); });           // :199
+        hipLaunchKernelGGL(mgf_vanilla_slice_kernel, dim3(k_here, static_cast<unsigned>(n_sets)), dim3(MGF_SLICE_BLOCK), 0,
                            as_stream(stream), reinterpret_cast<const cd *>(phi), reinterpret_cast<const cd *>(log_mgf),
                            static_cast<int>(n_grid), sa, capped + k0, static_cast<int>(n_strikes));
     }
-    return check_launch_a("svmc_mgf_vanilla_slice");
+    return check_launch("svmc_mgf_vanilla_slice");
 }
 
 int svmc_mgf_vanilla_slice(const double *phi, const double *log_mgf, size_t n_grid, double forward,
@@ -653,15 +624,15 @@ int svmc_mgf_qvar_slice(const double *psi, const double *log_mgf, size_t n_grid,
     SVMC_REQUIRE(psi && log_mgf && capped, "svmc_mgf_qvar_slice: null pointer");
     SVMC_REQUIRE(n_grid >= 3 && n_grid < (1u << 30), "svmc_mgf_qvar_slice: grid too short or too long");
     SVMC_REQUIRE(n_strikes == 0 || strikes_host, "svmc_mgf_qvar_slice: null strikes");
-    for (size_t k0 = 0; k0 < n_strikes; k0 += 32) {
-        StrikeArgs sa;
-        sa.k = static_cast<int>((n_strikes - k0 < 32) ? (n_strikes - k0) : 32);
-        for (int k = 0; k < 32; ++k) sa.x[k] = (k < sa.k) ? strikes_host[k0 + k] * ttm : 0.0;             // :343
-        hipLaunchKernelGGL(mgf_qvar_slice_kernel, dim3(sa.k), dim3(256), 0, as_stream(stream),
+    for (size_t k0 = 0; k0 < n_strikes; k0 += MGF_SLICE_STRIKES) {
+        SliceStrikes sa;
+        const int k_here = fill_strike_chunk(sa.x, strikes_host, k0, n_strikes,
+                                             [&](double strike) { return strike * ttm; });                    // :343
+        hipLaunchKernelGGL(mgf_qvar_slice_kernel, dim3(k_here), dim3(MGF_SLICE_BLOCK), 0, as_stream(stream),
                            reinterpret_cast<const cd *>(psi), reinterpret_cast<const cd *>(log_mgf),
                            static_cast<int>(n_grid), sa, capped + k0);
     }
-    return check_launch_a("svmc_mgf_qvar_slice");
+    return check_launch("svmc_mgf_qvar_slice");
 }
 
 }  // extern "C"

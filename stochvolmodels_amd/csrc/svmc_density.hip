@@ -26,42 +26,20 @@
 #include "svmc_math.h"
 #include "svmc_complex.h"
 #include "svmc_slice.h"
+#include "svmc_mgf_slice.h"
 
 namespace svmc {
 
-constexpr int DB = 256;                  // threads per block of the two slice kernels
 constexpr int MAX_PDF_SETS = 64;         // parameter sets per launch (kernel-argument block: 64 x 16 B)
-constexpr double PI = 3.14159265358979323846;
-
-// w_j of the legacy pricer weights, BEFORE the division by pi
-__device__ __forceinline__ double legacy_weight(const cd *__restrict__ u, int j, int n_grid, double h, int is_simpson)
-{
-    if (is_simpson) {
-        double w = 2.0;
-        if (j == 0 || j == n_grid - 1) w = 1.0;
-        if (j & 1) w = 4.0;
-        return (h / 3.0) * w;
-    }
-    return (j == 0) ? 0.5 * h : u[j].im - u[j - 1].im;
-}
-
-// the block's sum in its fixed order; thread 0 holds it
-__device__ __forceinline__ double block_sum(double s, double *lds)
-{
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = s;
-    __syncthreads();
-    return ((lds[0] + lds[1]) + lds[2]) + lds[3];
-}
 
 struct PdfSets {
     double shift[MAX_PDF_SETS];
     double scale[MAX_PDF_SETS];
 };
 
-__global__ __launch_bounds__(DB) void mgf_pdf_slice_kernel(const cd *__restrict__ u, const cd *__restrict__ log_mgf, int n_grid,
-                                                           const double *__restrict__ space, int n_space, PdfSets ps,
-                                                           int is_simpson, double *__restrict__ pdf)
+__global__ __launch_bounds__(MGF_SLICE_BLOCK) void mgf_pdf_slice_kernel(const cd *__restrict__ u, const cd *__restrict__ log_mgf,
+                                                                        int n_grid, const double *__restrict__ space, int n_space,
+                                                                        PdfSets ps, int is_simpson, double *__restrict__ pdf)
 {
     __shared__ double lds[4];
     const int set = blockIdx.y;                                       // the parameter set of a batched call
@@ -71,25 +49,19 @@ __global__ __launch_bounds__(DB) void mgf_pdf_slice_kernel(const cd *__restrict_
     pdf += static_cast<size_t>(set) * n_space;
     const double z = (space[blockIdx.x] - ps.shift[set]) / ps.scale[set];                       // :379
     const double h = u[1].im - u[0].im;
-    double s = 0.0;
-    for (int j = threadIdx.x; j < n_grid; j += DB) {
+    const double total = mgf_slice_nansum(n_grid, lds, [&](int j) {
         const double w = legacy_weight(u, j, n_grid, h, is_simpson) / PI;                       // :375-377
         const cd uj = u[j], lm = log_mgf[j];
         const cd e = cexp_(cd{z * uj.re + lm.re, z * uj.im + lm.im});
-        const double term = w * e.re;
-        if (term == term) s += term;                                                            // nansum :381
-    }
-    const double total = block_sum(s, lds);
+        return w * e.re;                                                                        // nansum :381
+    });
     if (threadIdx.x == 0) pdf[blockIdx.x] = (space[1] - space[0]) * total;                      // :382-383
 }
 
-struct DigitalArgs {
-    double x[32];   // log(forward / strike)
-};
-
-__global__ __launch_bounds__(DB) void mgf_digital_slice_kernel(const cd *__restrict__ phi, const cd *__restrict__ log_mgf,
-                                                               int n_grid, DigitalArgs da, int negative_contour, int is_simpson,
-                                                               double *__restrict__ sums, int sums_ld)
+__global__ __launch_bounds__(MGF_SLICE_BLOCK) void mgf_digital_slice_kernel(const cd *__restrict__ phi,
+                                                                            const cd *__restrict__ log_mgf, int n_grid,
+                                                                            SliceStrikes da, int negative_contour, int is_simpson,
+                                                                            double *__restrict__ sums, int sums_ld)
 {
     __shared__ double lds[4];
     phi += static_cast<size_t>(blockIdx.y) * n_grid;                  // blockIdx.y: the parameter set of a batched call
@@ -97,8 +69,7 @@ __global__ __launch_bounds__(DB) void mgf_digital_slice_kernel(const cd *__restr
     sums += static_cast<size_t>(blockIdx.y) * sums_ld;
     const double x = da.x[blockIdx.x];
     const double h = phi[1].im - phi[0].im;
-    double s = 0.0;
-    for (int j = threadIdx.x; j < n_grid; j += DB) {
+    const double total = mgf_slice_nansum(n_grid, lds, [&](int j) {
         const double a = legacy_weight(phi, j, n_grid, h, is_simpson) / PI;
         const cd b = phi[j];
         // (a + 0i) / b as NumPy divides (Smith's form: the larger component of b scales the other)
@@ -117,10 +88,8 @@ __global__ __launch_bounds__(DB) void mgf_digital_slice_kernel(const cd *__restr
         // grid's first point, Im phi = 0) inf * sin(0) is NaN, and with the complex p the whole term would be dropped where the
         // reference keeps Re[p] inf.  For a finite r the product is this signed zero already: no other term changes a bit.
         if (arg.im == 0.0) e.im = arg.im;
-        const double term = p.re * e.re - p.im * e.im;
-        if (term == term) s += term;                                                            // nansum :253
-    }
-    const double total = block_sum(s, lds);
+        return p.re * e.re - p.im * e.im;                                                       // nansum :253
+    });
     if (threadIdx.x == 0) sums[blockIdx.x] = total;
 }
 
@@ -470,8 +439,8 @@ int svmc_mgf_pdf_slice_batch(const double *var_grid, const double *log_mgf, size
             ps.scale[i] = (i < m) ? scales_host[s0 + i] : 1.0;
         }
         const size_t goff = static_cast<size_t>(s0) * n_grid, soff = static_cast<size_t>(s0) * n_space;
-        hipLaunchKernelGGL(mgf_pdf_slice_kernel, dim3(static_cast<unsigned>(n_space), static_cast<unsigned>(m)), dim3(DB), 0,
-                           as_stream(stream), reinterpret_cast<const cd *>(var_grid) + goff,
+        hipLaunchKernelGGL(mgf_pdf_slice_kernel, dim3(static_cast<unsigned>(n_space), static_cast<unsigned>(m)),
+                           dim3(MGF_SLICE_BLOCK), 0, as_stream(stream), reinterpret_cast<const cd *>(var_grid) + goff,
                            reinterpret_cast<const cd *>(log_mgf) + goff, static_cast<int>(n_grid), space + soff,
                            static_cast<int>(n_space), ps, is_simpson ? 1 : 0, pdf + soff);
     }
@@ -491,11 +460,11 @@ int svmc_mgf_digital_slice_batch(const double *phi, const double *log_mgf, size_
     for (size_t k = 0; k < n_strikes; ++k)           // log(forward / strike) of any other strike is NaN or inf: every term dropped, a silent 0
         SVMC_REQUIRE(strikes_host[k] > 0.0 && strikes_host[k] < HUGE_VAL,
                      "svmc_mgf_digital_slice_batch: strikes must be positive and finite");
-    for (size_t k0 = 0; k0 < n_strikes; k0 += 32) {
-        DigitalArgs da;
-        const int k_here = static_cast<int>((n_strikes - k0 < 32) ? (n_strikes - k0) : 32);
-        for (int k = 0; k < 32; ++k) da.x[k] = (k < k_here) ? log(forward / strikes_host[k0 + k]) : 0.0;      // :249
-        hipLaunchKernelGGL(mgf_digital_slice_kernel, dim3(k_here, static_cast<unsigned>(n_sets)), dim3(DB), 0,
+    for (size_t k0 = 0; k0 < n_strikes; k0 += MGF_SLICE_STRIKES) {
+        SliceStrikes da;
+        const int k_here = fill_strike_chunk(da.x, strikes_host, k0, n_strikes,
+                                             [&](double strike) { return log(forward / strike); });           // :249
+        hipLaunchKernelGGL(mgf_digital_slice_kernel, dim3(k_here, static_cast<unsigned>(n_sets)), dim3(MGF_SLICE_BLOCK), 0,
                            as_stream(stream), reinterpret_cast<const cd *>(phi), reinterpret_cast<const cd *>(log_mgf),
                            static_cast<int>(n_grid), da, negative_contour ? 1 : 0, is_simpson ? 1 : 0, sums + k0,
                            static_cast<int>(n_strikes));

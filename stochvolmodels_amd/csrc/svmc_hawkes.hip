@@ -33,6 +33,7 @@
 #include "svmc_complex.h"
 #include "svmc_ode.h"
 #include "svmc_dop853.h"
+#include "svmc_mgf_slice.h"
 
 namespace svmc {
 
@@ -466,9 +467,9 @@ __global__ __launch_bounds__(HK_AB) void hawkes_risk_forwards_kernel(HawkesOdeBa
 }
 
 struct GammaSliceArgs {
-    double x[32];                              // log(forward / strike)
-    double strike[32];
-    int type[32];                              // 0 'C', 1 'P'
+    double x[MGF_SLICE_STRIKES];               // log(forward / strike)
+    double strike[MGF_SLICE_STRIKES];
+    int type[MGF_SLICE_STRIKES];               // 0 'C', 1 'P'
     double gamma[HK_MAX_SETS];
     int shortcut[HK_MAX_SETS];                 // 1: every |Re phi - (0.5 + gamma)| < 1e-10 (:296), decided on the host
     int k;
@@ -479,13 +480,13 @@ struct GammaSliceArgs {
 // nansum Re[w exp(-x phi + log E)] (NaN terms dropped, inf kept).  Thread 0 finishes the price from this expiry's normalizer and
 // gamma forward (hawkes_risk_forwards_kernel's output, [expiry][set]): 'C' gamma_forward - normalizer K^(1 + gamma) cap,
 // 'P' K - normalizer K^(1 + gamma) cap (:313-317).
-__global__ __launch_bounds__(256) void mgf_gamma_slice_kernel(const cd *__restrict__ phi, const cd *__restrict__ log_mgf, int n_grid,
-                                                              GammaSliceArgs sa, const double *__restrict__ normalizers,
-                                                              const double *__restrict__ gamma_forwards, size_t nf_at,
-                                                              double *__restrict__ prices, int prices_ld)
+__global__ __launch_bounds__(MGF_SLICE_BLOCK) void mgf_gamma_slice_kernel(const cd *__restrict__ phi, const cd *__restrict__ log_mgf,
+                                                                          int n_grid, GammaSliceArgs sa,
+                                                                          const double *__restrict__ normalizers,
+                                                                          const double *__restrict__ gamma_forwards, size_t nf_at,
+                                                                          double *__restrict__ prices, int prices_ld)
 {
     __shared__ double lds[4];
-    const double PI = 3.14159265358979323846;
     const int s = blockIdx.y;
     phi += static_cast<size_t>(s) * n_grid;
     log_mgf += static_cast<size_t>(s) * n_grid;
@@ -493,13 +494,9 @@ __global__ __launch_bounds__(256) void mgf_gamma_slice_kernel(const cd *__restri
     const double gamma = sa.gamma[s];
     const bool shortcut = sa.shortcut[s] != 0;
     const double h = phi[1].im - phi[0].im;
-    double acc = 0.0;
-    for (int j = threadIdx.x; j < n_grid; j += 256) {
-        double w = 2.0;
-        if (j == 0 || j == n_grid - 1) w = 1.0;
-        if (j & 1) w = 4.0;
+    const double cap = mgf_slice_nansum(n_grid, lds, [&](int j) {
         const cd ph = phi[j];
-        const double dp_pi = ((h / 3.0) * w) / PI;
+        const double dp_pi = legacy_weight(phi, j, n_grid, h, 1) / PI;
         cd pw;
         if (shortcut) {
             pw = C(dp_pi / (ph.im * ph.im + 0.25));
@@ -508,15 +505,9 @@ __global__ __launch_bounds__(256) void mgf_gamma_slice_kernel(const cd *__restri
             pw = C(-dp_pi) / ((pg + 1.0) * pg);
         }
         const cd e = cexp_(log_mgf[j] - x * ph);
-        const double term = pw.re * e.re - pw.im * e.im;
-        if (term == term) acc += term;                                                          // nansum
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = acc;
-    __syncthreads();
+        return pw.re * e.re - pw.im * e.im;
+    });
     if (threadIdx.x == 0) {
-        const double cap = ((lds[0] + lds[1]) + lds[2]) + lds[3];
         const double strike = sa.strike[blockIdx.x];
         const double nk = normalizers[nf_at + s] * pow(strike, 1.0 + gamma);
         prices[static_cast<size_t>(s) * prices_ld + blockIdx.x] =
@@ -739,11 +730,11 @@ int svmc_mgf_gamma_slice_batch(const double *phi, const double *log_mgf, size_t 
     const size_t nf_at = static_cast<size_t>(expiry) * static_cast<size_t>(n_sets);
     for (int s0 = 0; s0 < n_sets; s0 += HK_MAX_SETS) {
         const int m = (n_sets - s0 < HK_MAX_SETS) ? (n_sets - s0) : HK_MAX_SETS;
-        for (size_t k0 = 0; k0 < n_strikes; k0 += 32) {
+        for (size_t k0 = 0; k0 < n_strikes; k0 += MGF_SLICE_STRIKES) {
             GammaSliceArgs sa;
-            sa.k = static_cast<int>((n_strikes - k0 < 32) ? (n_strikes - k0) : 32);
-            for (int k = 0; k < 32; ++k) {
-                sa.x[k] = (k < sa.k) ? log(forward / strikes_host[k0 + k]) : 0.0;                // :304
+            sa.k = fill_strike_chunk(sa.x, strikes_host, k0, n_strikes,
+                                     [&](double strike) { return log(forward / strike); });               // :304
+            for (int k = 0; k < MGF_SLICE_STRIKES; ++k) {
                 sa.strike[k] = (k < sa.k) ? strikes_host[k0 + k] : 1.0;
                 sa.type[k] = (k < sa.k) ? type_codes_host[k0 + k] : 0;
             }
@@ -752,8 +743,8 @@ int svmc_mgf_gamma_slice_batch(const double *phi, const double *log_mgf, size_t 
                 sa.shortcut[i] = shortcut_host[s0 + (i < m ? i : 0)] != 0;
             }
             const size_t off = static_cast<size_t>(s0) * n_grid;
-            hipLaunchKernelGGL(mgf_gamma_slice_kernel, dim3(sa.k, static_cast<unsigned>(m)), dim3(256), 0, as_stream(stream),
-                               reinterpret_cast<const cd *>(phi) + off, reinterpret_cast<const cd *>(log_mgf) + off,
+            hipLaunchKernelGGL(mgf_gamma_slice_kernel, dim3(sa.k, static_cast<unsigned>(m)), dim3(MGF_SLICE_BLOCK), 0,
+                               as_stream(stream), reinterpret_cast<const cd *>(phi) + off, reinterpret_cast<const cd *>(log_mgf) + off,
                                static_cast<int>(n_grid), sa, normalizers + s0, gamma_forwards + s0, nf_at,
                                prices + static_cast<size_t>(s0) * n_strikes + k0, static_cast<int>(n_strikes));
         }

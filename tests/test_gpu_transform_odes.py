@@ -16,12 +16,16 @@ The analytic route's device kernels against independent high-precision truth:
     256-thread stride loop at 255, 256 and 257 points, both branches of legacy_weight (Simpson, and the local-step weights on
     a geometrically stretched grid), both arms of the digital kernel's Smith division (|Re phi| >= |Im phi| at the first
     grid points only), both contours, the 64-set launch boundary of the pdf entry (64, 65 and 129 sets, each bit-equal to its
-    single call), the 32-strike chunks of the digital entry, a negative scale, and the nansum contract of both.
+    single call), the 32-strike chunks of the digital entry, a negative scale, and the nansum contract of both;
+  * all five slice kernels against the bits recorded in tests/golden/mgf_slice_bits.npz (make_golden_mgf_slice_bits.py) before
+    they came to share one sum loop (csrc/svmc_mgf_slice.h): the loop's trip counts, the strike chunk and the pdf launch
+    boundary, every weight rule and contour, and non-finite log E entries.
 
 Errors of the ODE are |dev - mp| / max(1, |mp|), the largest over a point's components and log E; every report() line
 prints the measured worst value against its bound.
 """
 import ctypes as C
+import json
 import math
 import os
 
@@ -722,3 +726,53 @@ def test_digital_slice_kernel_nansum_contract(L, spot, is_simpson):
             else:
                 assert np.isfinite(got[i]) and mp.isfinite(ref[0]), (name, i, got[i], ref[0])
                 check_sum(f"digital {name} strike {i}", got[i], ref, n)
+
+
+# ---- the five slice kernels against their recorded bits -------------------------------------------------------------------
+# tests/golden/mgf_slice_bits.npz holds, per grid length n, the imaginary parts p_n [3][n] of three transform grids and their
+# log E lm_n [3][n] (NaN, -inf and +inf planted at n = 257), and per case the rows of them it takes (`sets`), the grids' real
+# parts, the entry point's small arguments and the output the library gave when the fixture was made.
+SLICE_KERNELS = ("vanilla", "qvar", "gamma", "pdf", "digital")
+
+
+def slice_case_output(L, g, c):
+    """case `c` (an entry of the fixture's index) through its C entry point -> the doubles it wrote"""
+    key, n = c["id"] + "/", c["n"]
+    sets = g[key + "sets"]
+    grid = np.empty((sets.size, n), dtype=np.complex128)
+    grid.real = g[key + "re"][:, None]
+    grid.imag = g[f"p_{n}"][sets]
+    lm = np.ascontiguousarray(g[f"lm_{n}"][sets])
+    s = sets.size
+    if c["kernel"] == "pdf":
+        return pdf_batch(L, grid, lm, g[key + "space"], g[key + "shifts"], g[key + "scales"], c["is_simpson"])
+    strikes = np.ascontiguousarray(g[key + "strikes"])
+    k = strikes.size
+    if c["kernel"] == "digital":
+        return digital_batch(L, grid, lm, c["forward"], strikes, c["negative_contour"], c["is_simpson"])
+    dgrid, dlm, out = Dev(L, grid), Dev(L, lm), Dev(L, n_doubles=s * k)
+    if c["kernel"] == "vanilla":
+        _check(L.svmc_mgf_vanilla_slice_batch(dgrid.ptr, dlm.ptr, n, s, c["forward"], _pf(strikes), k, out.ptr, None))
+    elif c["kernel"] == "qvar":
+        assert s == 1
+        _check(L.svmc_mgf_qvar_slice(dgrid.ptr, dlm.ptr, n, c["ttm"], _pf(strikes), k, out.ptr, None))
+    else:
+        gammas, shortcut, codes = (np.ascontiguousarray(g[key + v]) for v in ("gammas", "shortcut", "codes"))
+        norm, gfwd = Dev(L, g[key + "normalizers"]), Dev(L, g[key + "gamma_forwards"])
+        pi = C.POINTER(C.c_int)
+        _check(L.svmc_mgf_gamma_slice_batch(dgrid.ptr, dlm.ptr, n, s, _pf(gammas), shortcut.ctypes.data_as(pi), norm.ptr,
+                                            gfwd.ptr, 0, c["forward"], _pf(strikes), codes.ctypes.data_as(pi), k, out.ptr, None))
+    return out.get((s, k), np.float64)
+
+
+@pytest.mark.parametrize("kernel", SLICE_KERNELS)
+def test_slice_kernels_bit_equal_to_recorded(L, kernel):
+    """raw bits, so NaN and the sign of zero count"""
+    g = np.load(os.path.join(HERE, "golden", "mgf_slice_bits.npz"))
+    cases_ = [c for c in json.loads(str(g["index"])) if c["kernel"] == kernel]
+    assert {c["n"] for c in cases_} == {3, 256, 257, 1001}
+    for c in cases_:
+        got, want = slice_case_output(L, g, c), g[c["id"] + "/out"]
+        assert got.shape == want.shape, c["id"]
+        differ = np.flatnonzero(got.view(np.uint64).ravel() != want.view(np.uint64).ravel())
+        assert differ.size == 0, (c["id"], differ[:8], got.ravel()[differ[:8]], want.ravel()[differ[:8]])

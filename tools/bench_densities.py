@@ -5,8 +5,9 @@ Times of the density row on the GPU -> profiles/densities_bench.j
     inversion (upload of the space grid, launch, download of the masses and the log-MGF);
   * the six calls of one density figure (three variables x two expansion orders) as single calls and through logsv_pdfs_batch;
   * terminal_value_histograms' counting against downloading the three state vectors, at 400 000 and 2^22 paths;
-  * exp evaluations per second of mgf_pdf_slice_kernel against mgf_vanilla_slice_kernel on the same 1000-point grid and the
-    same number of blocks (32), by device events around 200 queued launches of each.
+  * exp evaluations per second of mgf_pdf_slice_kernel against mgf_vanilla_slice_kernel (and mgf_digital_slice_kernel,
+    mgf_qvar_slice_kernel) on the same 1000-point grid and the same number of blocks (32), by device events around 200 queued
+    launches of each.
 
 Host clocks around work that ends in a synchronise; medians of --repeats runs after a warm-up.  The reference's CPU seconds
 come from the fixture (timed when it was generated; the reference never runs on the GPU machine).
@@ -93,12 +94,20 @@ def kernel_rates(repeats=200):
     def vanilla():
         _lib.check(L.svmc_mgf_vanilla_slice(bufs[0].ptr, bufs[1].ptr, phi.size, 1.0, strikes.ctypes.data_as(pf), 32, bufs[3].ptr, None))
 
+    def digital():
+        _lib.check(L.svmc_mgf_digital_slice_batch(bufs[0].ptr, bufs[1].ptr, phi.size, 1, 1.0, strikes.ctypes.data_as(pf), 32, 1, 1,
+                                                  bufs[3].ptr, None))
+
+    def qvar():                                              # the phi grid standing in for psi: the same 32 x 1000 terms
+        _lib.check(L.svmc_mgf_qvar_slice(bufs[0].ptr, bufs[1].ptr, phi.size, 1.0, strikes.ctypes.data_as(pf), 32, bufs[3].ptr, None))
+
     out = {}
     ev = [C.c_void_p(), C.c_void_p()]
     for e in ev:
         _lib.check(L.svmc_event_create(C.byref(e)))
-    for _ in range(3):                                       # alternate the two kernels: other work shares the machine
-        for name, fn in (("mgf_pdf_slice_kernel", pdf), ("mgf_vanilla_slice_kernel", vanilla)):
+    for _ in range(3):                                       # alternate the kernels: other work shares the machine
+        for name, fn in (("mgf_pdf_slice_kernel", pdf), ("mgf_vanilla_slice_kernel", vanilla),
+                         ("mgf_digital_slice_kernel", digital), ("mgf_qvar_slice_kernel", qvar)):
             fn()
             _lib.check(L.svmc_event_record(ev[0], None))
             for _ in range(repeats):
