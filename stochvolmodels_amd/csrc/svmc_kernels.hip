@@ -392,8 +392,8 @@ __device__ __forceinline__ void logsv_gen_time_loop(const PhiloxLane &lane, uint
     LogsvStepInFlight h;
     const Exp2uTailV k = exp2u_tail_consts();
     rng_time_loop_pipelined(
-        lane, step0, nb, tab, [&](double z0, double z1) { logsv_step_acc_front(c, xacc, L, s, z0, z1, exp_table, h); },
-        [&]() { logsv_step_acc_mid(h, k); }, [&]() { logsv_step_acc_back(s, acc, h); });
+        lane, step0, nb, tab, [&](double z0, double z1) { logsv_step_acc_front(c, xacc, L, s, acc, z0, z1, exp_table, h); },
+        [&]() { logsv_step_acc_mid(h, k); }, [&]() { logsv_step_acc_back(s, h); });
 }
 
 // ONE slice of a LogSV path in the few-waves form, the statements every few-waves generator runs (logsv_rng_lat_kernel, the
@@ -1084,13 +1084,13 @@ void logsv_chain_rng_sets_kernel(size_t n, ChainRngSetsSlices cs, const LogsvFas
             const Exp2uTailV tail_k = exp2u_tail_consts();
             rng_time_loop_pipelined(
                 lane, tg, nb, tab,
-                [&](double z0, double z1) { logsv_step_acc_sets_front<P>(k1, k2, k3, kb, ke, xacc, L, sg, z0, z1, s_exp, h); },
-                [&]() { logsv_step_acc_sets_mid<P>(h, tail_k); }, [&]() { logsv_step_acc_sets_back<P, true>(sg, acc, h); });
+                [&](double z0, double z1) { logsv_step_acc_sets_front<P>(k1, k2, k3, kb, ke, xacc, L, sg, acc, z0, z1, s_exp, h); },
+                [&]() { logsv_step_acc_sets_mid<P>(h, tail_k); }, [&]() { logsv_step_acc_sets_back<P, true>(sg, h); });
         } else {
             rng_time_loop_pipelined(
                 lane, tg, nb, tab,
-                [&](double z0, double z1) { logsv_step_acc_sets_front<P>(k1, k2, k3, kb, ke, xacc, L, sg, z0, z1, s_exp, h); },
-                [&]() { logsv_step_acc_sets_back<P>(sg, acc, h); });
+                [&](double z0, double z1) { logsv_step_acc_sets_front<P>(k1, k2, k3, kb, ke, xacc, L, sg, acc, z0, z1, s_exp, h); },
+                [&]() { logsv_step_acc_sets_back<P>(sg, h); });
         }
         tg += static_cast<uint32_t>(nb);
 #pragma unroll

@@ -129,9 +129,14 @@ __device__ __forceinline__ void logsv_step_fast(const LogsvFast &f, double &x, d
 }
 
 // The same step with the two running sums of sigma^2 (the drift of x and the quadratic variance) replaced by ONE
-// accumulator acc = sum_{t=1..T} sigma_t^2; the caller folds it in where x and qvar are needed (logsv_fold_acc):
-//     x_T    = x_0 + B xacc + ahA (acc + sigma_0^2 - sigma_T^2),  xacc = sum_t sigma_t z0_t
-//     qvar_T = qvar_0 + hA (2 acc + sigma_0^2 - sigma_T^2)                          [= hA sum (sigma_t^2 + sigma_{t+1}^2)]
+// accumulator acc = sum_{t=0..T-1} sigma_t^2, the squares the steps START from; the caller folds it in where x and qvar are
+// needed (logsv_fold_acc):
+//     x_T    = x_0 + B xacc + ahA acc,  xacc = sum_t sigma_t z0_t
+//     qvar_T = qvar_0 + hA (2 acc - sigma_0^2 + sigma_T^2)                          [= hA sum (sigma_t^2 + sigma_{t+1}^2)]
+// (Summing the squares the steps END with and folding x with acc + sigma_0^2 - sigma_T^2 is the same in exact arithmetic, but it
+// rebuilds sum_{t<T} sigma_t^2 by subtracting sigma_T^2 from a sum that holds it: where the last volatility dwarfs the earlier
+// ones -- a path bouncing off a collapsed volatility, kappa1 theta dt / sigma large -- x kept ulp(sigma_T^2), not ulp(x).
+// tests/test_gpu_mc_steps.py, the far-states cases: order 1 in x after two such steps.)
 // and L is advanced by single FMAs (no constant has to be moved into a vector register): 9 arithmetic instructions
 // around the exp and the reciprocal instead of 12.  Identical in exact arithmetic; rounding differs at 1e-16.
 template <class Exp>
@@ -141,14 +146,13 @@ __device__ __forceinline__ void logsv_step_acc(const LogsvFast &f, double &xacc,
     const double s = sigma;
     const double y = rcp_1n(s);
     xacc = fma(s, z0, xacc);                      // sum sigma_t z0_t; the factor B = eta sqrt(dt) is applied in the fold
+    acc = fma(s, s, acc);
     L = fma(f.c2, s, L);
     L = fma(f.c1, y, L);
     L = L + f.c3;
     L = fma(f.bs, z0, L);
     L = fma(f.es, z1, L);
-    const double sn = exp_of(L);
-    acc = fma(sn, sn, acc);
-    sigma = sn;
+    sigma = exp_of(L);
     (void)s2;                                     // sigma^2 is not carried: the fold squares the terminal sigma itself
 }
 
@@ -159,11 +163,12 @@ struct LogsvStepInFlight {
     double r, t, p;
     int ni;
 };
-__device__ __forceinline__ void logsv_step_acc_front(const LogsvFast &f, double &xacc, double &L, double sigma, double z0, double z1,
-                                                     const double *exp_table, LogsvStepInFlight &h)
+__device__ __forceinline__ void logsv_step_acc_front(const LogsvFast &f, double &xacc, double &L, double sigma, double &acc, double z0,
+                                                     double z1, const double *exp_table, LogsvStepInFlight &h)
 {
     const double y = rcp_1n(sigma);
     xacc = fma(sigma, z0, xacc);
+    acc = fma(sigma, sigma, acc);
     L = fma(f.c2, sigma, L);
     L = fma(f.c1, y, L);
     L = L + f.c3;
@@ -178,11 +183,9 @@ __device__ __forceinline__ void logsv_step_acc_mid(LogsvStepInFlight &h, const E
 {
     h.p = exp2u_tail_v(h.r, k);
 }
-__device__ __forceinline__ void logsv_step_acc_back(double &sigma, double &acc, const LogsvStepInFlight &h)
+__device__ __forceinline__ void logsv_step_acc_back(double &sigma, const LogsvStepInFlight &h)
 {
-    const double sn = exp2u_scale(h.t, h.p, h.ni);
-    acc = fma(sn, sn, acc);
-    sigma = sn;
+    sigma = exp2u_scale(h.t, h.p, h.ni);
 }
 
 // logsv_step_acc for P independent states of one lane (P parameter sets on the same two normals), piece by piece ACROSS the
@@ -198,14 +201,16 @@ struct LogsvSetsInFlight {
 template <int P>
 __device__ __forceinline__ void logsv_step_acc_sets_front(const double (&c1)[P], const double (&c2)[P], const double (&c3)[P],
                                                           const double (&bs)[P], const double (&es)[P], double (&xacc)[P],
-                                                          double (&L)[P], const double (&sigma)[P], double z0, double z1,
-                                                          const double *exp_table, LogsvSetsInFlight<P> &h)
+                                                          double (&L)[P], const double (&sigma)[P], double (&acc)[P], double z0,
+                                                          double z1, const double *exp_table, LogsvSetsInFlight<P> &h)
 {
     double y[P];
 #pragma unroll
     for (int s = 0; s < P; ++s) y[s] = rcp_1n(sigma[s]);
 #pragma unroll
     for (int s = 0; s < P; ++s) xacc[s] = fma(sigma[s], z0, xacc[s]);
+#pragma unroll
+    for (int s = 0; s < P; ++s) acc[s] = fma(sigma[s], sigma[s], acc[s]);
 #pragma unroll
     for (int s = 0; s < P; ++s) {
         double l = fma(c2[s], sigma[s], L[s]);
@@ -227,22 +232,18 @@ __device__ __forceinline__ void logsv_step_acc_sets_mid(LogsvSetsInFlight<P> &h,
     for (int s = 0; s < P; ++s) h.r[s] = exp2u_tail_v(h.r[s], k);
 }
 template <int P, bool TAILS_DONE = false>
-__device__ __forceinline__ void logsv_step_acc_sets_back(double (&sigma)[P], double (&acc)[P], LogsvSetsInFlight<P> &h)
+__device__ __forceinline__ void logsv_step_acc_sets_back(double (&sigma)[P], LogsvSetsInFlight<P> &h)
 {
     if constexpr (!TAILS_DONE) {
 #pragma unroll
         for (int s = 0; s < P; ++s) h.r[s] = exp2u_tail(h.r[s]);
     }
 #pragma unroll
-    for (int s = 0; s < P; ++s) {
-        const double sn = exp2u_scale(h.t[s], h.r[s], h.ni[s]);
-        acc[s] = fma(sn, sn, acc[s]);
-        sigma[s] = sn;
-    }
+    for (int s = 0; s < P; ++s) sigma[s] = exp2u_scale(h.t[s], h.r[s], h.ni[s]);
 }
 
 // sigma^2 as a rounded product of its own: without this the compiler may fuse the multiplication into the subtraction of
-// logsv_fold_acc (s2_start - sigma_T^2 as one FMA) in one kernel and not in another -- whichever way the inlined code around
+// logsv_fold_acc (sigma_T^2 - s2_start as one FMA) in one kernel and not in another -- whichever way the inlined code around
 // it falls -- and the one-slice, whole-chain and streamed generators must agree to the bit (a persistent-launch variant of
 // the generator differed from the one-round kernel in 180 of 2^20 paths by exactly this, profiles/r03_launch_tail.txt)
 __device__ __forceinline__ double square_rn(double v)
@@ -254,16 +255,16 @@ __device__ __forceinline__ double square_rn(double v)
 }
 
 // fold the accumulator of logsv_step_acc into x and qvar (s2_start = sigma^2 when acc was last zero); a path whose
-// sigma overflowed keeps the reference's outcome (x -> -+inf, qvar -> inf) instead of inf - inf
+// sigma^2 overflowed keeps the reference's outcome (x -> -+inf, qvar -> inf) instead of inf - inf.  2 acc - s2_start is at
+// least acc: nothing cancels
 __device__ __forceinline__ void logsv_fold_acc(const LogsvFast &f, double &x, double &qvar, double xacc, double acc,
                                                double s2_start, double s2_now)
 {
     x = fma(f.B, xacc, x);
-    const double tail = s2_start - s2_now;
+    const double tail = s2_now - s2_start;
     const bool finite = acc < __builtin_huge_val();
-    const double d = finite ? acc + tail : acc;
     const double e = finite ? (acc + acc) + tail : acc;
-    x = fma(f.ahA, d, x);
+    x = fma(f.ahA, acc, x);
     qvar = fma(f.hA, e, qvar);
 }
 
@@ -483,7 +484,7 @@ __device__ __forceinline__ double qe_martingale_kd(double e, double al, double m
 //     v1 = ln(2 m^2 / (D (1 - u))) D / (2 m);   1/(D (1 - u)) and 1/m from rcp(D (1 - u) m);
 //     p + beta (1 - p)/(beta - A) = ((s2 - m^2) e + 4 m m^2) / (D e),  e = 2 m - A D;   1/(D e) is the second reciprocal.
 // Identical in exact arithmetic to the CPU twin (oracle/svmc_oracle.c, the textbook form); reciprocals are seed + one Newton
-// step (2^-48), square roots stop after the Goldschmidt step (2^-47: the scheme matches two moments of the variance, not its
+// step (2^-48; two in the exponential branch, see there), square roots stop after the Goldschmidt step (2^-47: the scheme matches two moments of the variance, not its
 // bits), logs go through the LDS table.  x advances by sqrt(K3 v0 + K4 v1) z0 alone; the drift terms are SUMS over the
 // steps -- K1m sum v0 + K2 sum v1 + sum K0* -- and are folded in once (heston_qe_fold: `vsum` = sum v1, `ksum` = sum 2 K0*,
 // sum v0 = v_first + vsum - v_last), as is the quadratic variance dt (vsum + (v_first - v_last)/2).
@@ -537,7 +538,11 @@ __device__ __forceinline__ void heston_qe_step(const QeConsts &c, const QeVec &c
         const double D = s2 + m2, dm = s2 - m2;
         const bool zero = (u * D <= dm);                  // u <= p
         const double q1 = D * (1.0 - u);
-        const double r = rcp_1n(q1 * m);
+        // rcp_fast, not rcp_1n, for both reciprocals of this branch: one Newton step leaves 1 - e^2 times the quotient, e the
+        // seed's error -- up to 2^-48 and always BELOW it.  Through the logarithms' arguments that is a drift of up to 7e-15
+        // per step of one sign in x (1.6e-12 after 1024 steps of the exponential-branch set of tests/test_gpu_mc_steps.py,
+        // nineteen times the textbook form's own rounding); the second step costs two FMAs each, in this branch only.
+        const double r = rcp_fast(q1 * m);
         const double iq1 = m * r, im = q1 * r;            // 1/(D (1 - u)),  1/m
         const double lg = neg_log_tab((m2 + m2) * iq1, tab);   // -ln((1 - p)/(1 - u)): <= 0 wherever u > p
         v1 = zero ? 0.0 : (-lg) * ((0.5 * D) * im);
@@ -546,7 +551,7 @@ __device__ __forceinline__ void heston_qe_step(const QeConsts &c, const QeVec &c
         } else {
             const double e = fma(-c.A, D, m + m);         // D (beta - A)
             if (e > 0.0) {
-                const double r2 = rcp_1n(D * e);
+                const double r2 = rcp_fast(D * e);
                 Kd = 2.0 * neg_log_tab(fma(dm, e, 4.0 * m * m2) * r2, tab);
             } else {
                 Kd = fma(c.K13_2, v0, c.K0_plain2);

@@ -1,6 +1,9 @@
 """Overflow / collapse regimes (checker script, run by hand on a GPU box: python tests/stress_extremes.py): LogSV with volvol 6-8
 over 6-8 years, terminal-state classes (finite / +inf / -inf / NaN) of the GPU generator against the CPU oracle on the same
-stream.  Lives under tests/ because it drives the oracle (test infrastructure)."""
+stream.  Lives under tests/ because it drives the oracle (test infrastructure).
+What a single step does at the states these runs pass through is asserted: the far-states cases of tests/golden/mc_steps.npz
+(one and two steps from oracle states sampled along the "explosive" and "collapse" runs, against a 256-bit recursion;
+tests/test_gpu_mc_steps.py, profiles/mc_step_observed_tolerances.txt).  This script stays a hand tool for whole runs."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
