@@ -825,6 +825,53 @@ SVMC_API int svmc_hawkesjd_chain_price_tilted(svmc_session_t session, const doub
                                               int n_gammas, int recenter, double *prices_host, double *stderrs_host,
                                               double *stats_host);
 
+/* ---- impermanent loss of a concentrated-liquidity range [pa, pb] (src svmc_density.hip, svmc_kernels.hip) ----
+ * The payoff is the hold-minus-pool value of a unit-liquidity position opened at p0, per terminal spot S:
+ *   pay(S) = -2 sqrt(S) 1{pa <= S <= pb} + sqrt(p0) (S / p0 + 1) + (pa - S)^+ / sqrt(pa) - (S - pb)^+ / sqrt(pb)
+ *            - 2 sqrt(pa) 1{S < pa} - 2 sqrt(pb) 1{S > pb},
+ * and the price is -(notional0 notional) E[pay], notional0 = 1 / (2 sqrt(p0) - p0 / sqrt(pb) - sqrt(pa)) (reference
+ * papers/il_hedging/run_logsv_for_il_payoff.py: a put, a call, two digitals and a square-root payoff).
+ *
+ * TRANSFORM SIDE.  svmc_mgf_il_slice_batch: phi, log_mgf device [n_sets][n_grid] complex; x_host, xa_host, xb_host [n_cases] =
+ * log p1, log pa, log pb (finite, xa < xb); sums: device [n_sets][n_cases][SVMC_IL_SLICE_SUMS], per case
+ *   [0] nansum_j Re[ (v_j / pi) (exp((phi_j + 1/2) xb - phi_j x) - exp((phi_j + 1/2) xa - phi_j x)) / (phi_j + 1/2) exp(log_mgf_j) ]
+ *   [1] nansum_j Re[ -(w_j / pi) / ((phi_j + 1) phi_j) exp(-(x - xa) phi_j + log_mgf_j) ]      [2] the same with xb
+ *   [3] nansum_j Re[ (w_j / pi) / phi_j exp(-(x - xa) phi_j + log_mgf_j) ]                     [4] the same with xb
+ * w: the legacy weights above; v: the validated weights of compute_integration_weights (utils/mgf_pricer.py:97-155) -- Simpson's
+ * equal the legacy ones on the odd grids that rule accepts, with is_simpson = 0 one step on every point and half a step on the
+ * first and the last (the host refuses the grids compute_integration_weights refuses).  [3], [4] are
+ * svmc_mgf_digital_slice_batch's sums at negative_contour = 0; on a contour with every Re phi < 0 the host changes the sign of
+ * the sum (the same bits as negated terms).  x - xa stands for the reference's log(p1 / pa): they differ by the rounding of the
+ * logarithms.  The complement, forward - strike capped, the discount factor and the composition are host code.  Cases travel 32
+ * to a launch; a case of a batch and a set of a batch are bit-equal to the case and the set alone.
+ *
+ * MONTE CARLO SIDE.  svmc_il_payoff on terminal log-returns x (device [n_path]) and the HOST table cases_host
+ * [n_cases][SVMC_IL_CASE_DOUBLES] = {p1, p0, pa, pb, notional}, all positive and finite with pa < p0 < pb:
+ *   KEEP RULE: path j is kept iff x_j and exp(x_j) are finite; a dropped path adds nothing and is counted;
+ *   M = sum exp(x_j) / n_kept over the kept paths, ONE pass for all cases of the call;
+ *   spot_j = p1 exp(x_j) - corr, corr = p1 M - p1 (compute_mc_vars_payoff's recentring: the spots' mean is p1).  Formed once per
+ *   call, it differs from recentring every case by its own mean of p1 exp(x) by rounding only;
+ *   pieces per kept path: sqrt(spot) where pa <= spot <= pb and 0 elsewhere (a negative recentred spot never reaches the square
+ *   root), sqrt(p0) (spot / p0 + 1), (pa - spot)^+, (spot - pb)^+, 1{spot < pa}, 1{spot > pb}; pay_j as above;
+ *   value = -(notional0 notional) mean(pay), formed as pay(p1) + mean(d), d_j = pay_j - pay(p1);
+ *   stderr = (notional0 notional) sqrt(var / n_kept), var = max(mean(d^2) - mean(d)^2, 0) the population variance (0 at one kept path).
+ * out_host [n_cases][SVMC_IL_OUT_DOUBLES] = {value, stderr, mean sqrt piece, mean linear piece, mean put, mean call, mean digital
+ * put, mean digital call, n_kept, n_dropped}.  No kept path is not an error: the means are 0/0 = NaN and n_kept says so.  Three
+ * launches on `stream`, one upload of the table, one download, one synchronize; `workspace` is device memory of
+ * svmc_il_payoff_workspace_bytes(n_path, n_cases).  Every sum has a fixed order that depends on n_path alone: a case's results
+ * are the same bits whichever other cases share the call.  Refused before anything is launched: SVMC_ERR_INVALID_ARGUMENT for a
+ * null pointer, n_path < 1, n_cases outside 1 .. SVMC_IL_MAX_CASES, a case that breaks the conditions above; SVMC_ERR_WORKSPACE. */
+#define SVMC_IL_SLICE_SUMS 5
+#define SVMC_IL_CASE_DOUBLES 5
+#define SVMC_IL_OUT_DOUBLES 10
+#define SVMC_IL_MAX_CASES 65536
+SVMC_API int svmc_mgf_il_slice_batch(const double *phi, const double *log_mgf, size_t n_grid, int n_sets, const double *x_host,
+                                     const double *xa_host, const double *xb_host, size_t n_cases, int is_simpson, double *sums,
+                                     svmc_stream_t stream);
+SVMC_API int svmc_il_payoff_workspace_bytes(size_t n_path, size_t n_cases, size_t *bytes);
+SVMC_API int svmc_il_payoff(const double *x, size_t n_path, const double *cases_host, size_t n_cases, double *out_host,
+                            void *workspace, size_t workspace_bytes, svmc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,6 +13,8 @@ Module layout and public names mirror the reference package (`stochvolmodels`) f
                                               hawkesjd_mc_chain_pricer_with_risk_premia(_gammas),
                                               hawkesjd_mc_chain_pricer_many,
                                               hawkesjd_mc_chain_pricer_with_risk_premia_gammas_many
+    stochvolmodels_amd.pricers.il_pricer      logsv_il_pricer(_vector, _batch), square_root_payoff_pricer_with_mgf_grid,
+                                              compute_mc_il_payoff
     stochvolmodels_amd.utils.mc_payoffs       compute_mc_vars_payoff, compute_mc_vars_payoff_with_gamma
     stochvolmodels_amd.utils.funcs            set_time_grid, set_seed, timer
     stochvolmodels_amd.utils.config           OptionType, VariableType
@@ -77,6 +79,10 @@ _EXPORTS = {
     "get_init_conditions_a": "pricers.logsv.affine_expansion",
     "pdf_with_mgf_grid": "utils.mgf_pricer", "digital_slice_pricer_with_mgf_grid": "utils.mgf_pricer",
     "compute_histogram_data": "utils.funcs",
+    "logsv_il_pricer": "pricers.il_pricer", "logsv_il_pricer_vector": "pricers.il_pricer",
+    "logsv_il_pricer_batch": "pricers.il_pricer", "square_root_payoff_pricer_with_mgf_grid": "pricers.il_pricer",
+    "compute_mc_il_payoff": "pricers.il_pricer", "il_payoff": "pricers.il_pricer",
+    "get_transform_var_grid": "utils.mgf_pricer", "compute_integration_weights": "utils.mgf_pricer",
 }
 
 __all__ = sorted(_EXPORTS)

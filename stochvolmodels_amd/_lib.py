@@ -162,6 +162,9 @@ def _declare(L: C.CDLL) -> None:
         "svmc_mgf_gamma_slice_batch": ([vp, vp, sz, i32, pf64, pi32, vp, vp, i32, f64, pf64, pi32, sz, vp, vp], i32),
         "svmc_mgf_pdf_slice_batch": ([vp, vp, sz, i32, vp, sz, pf64, pf64, i32, vp, vp], i32),
         "svmc_mgf_digital_slice_batch": ([vp, vp, sz, i32, f64, pf64, sz, i32, i32, vp, vp], i32),
+        "svmc_mgf_il_slice_batch": ([vp, vp, sz, i32, pf64, pf64, pf64, sz, i32, vp, vp], i32),
+        "svmc_il_payoff_workspace_bytes": ([sz, sz, psz], i32),
+        "svmc_il_payoff": ([vp, sz, pf64, sz, pf64, vp, sz, vp], i32),
         "svmc_histogram_uniform": ([vp, sz, f64, vp, i32, vp, vp], i32),
         "svmc_kde_workspace_bytes": ([sz, psz, psz], i32),
         "svmc_kde_gaussian": ([vp, sz, f64, f64, vp, i32, f64, vp, vp, vp, sz, vp], i32),

@@ -4,6 +4,7 @@
 //                              dx sum_j Re[ (w_j / pi) exp(z_i u_j + log E_j) ] over the transform grid u   (utils/mgf_pricer.py:361-384)
 //   mgf_digital_slice_kernel   one block per strike: sum_j Re[ p_j exp(-x_K phi_j + log E_j) ], p_j = -+(w_j / pi) / phi_j
 //                              (utils/mgf_pricer.py:224-269; the C / P complement and the discount factor are the host's)
+//   mgf_il_slice_kernel        one block per impermanent-loss case (forward, range): the five sums of row f10, described where it stands
 //   histogram_uniform_kernel   integer counts of a state vector on equal bins with np.histogram's semantics: per-block counts in
 //                              LDS, one 64-bit integer atomic per non-empty bin and block
 //   kde_* kernels              the Gaussian kernel density estimate of a state vector, plain (row f7) and, as their WEIGHTED
@@ -72,15 +73,7 @@ __global__ __launch_bounds__(MGF_SLICE_BLOCK) void mgf_digital_slice_kernel(cons
     const double total = mgf_slice_nansum(n_grid, lds, [&](int j) {
         const double a = legacy_weight(phi, j, n_grid, h, is_simpson) / PI;
         const cd b = phi[j];
-        // (a + 0i) / b as NumPy divides (Smith's form: the larger component of b scales the other)
-        cd p;
-        if (fabs(b.re) >= fabs(b.im)) {
-            const double rat = b.im / b.re, scl = 1.0 / (b.re + b.im * rat);
-            p = cd{a * scl, -(a * rat) * scl};
-        } else {
-            const double rat = b.re / b.im, scl = 1.0 / (b.im + b.re * rat);
-            p = cd{(a * rat) * scl, -a * scl};
-        }
+        cd p = real_over_complex(a, b);                                                         // as NumPy divides
         if (negative_contour) p = -p;                                                           // calls :244, puts :247
         const cd arg = log_mgf[j] - x * b;
         cd e = cexp_(arg);
@@ -91,6 +84,73 @@ __global__ __launch_bounds__(MGF_SLICE_BLOCK) void mgf_digital_slice_kernel(cons
         return p.re * e.re - p.im * e.im;                                                       // nansum :253
     });
     if (threadIdx.x == 0) sums[blockIdx.x] = total;
+}
+
+// ---- impermanent loss of a liquidity range [pa, pb] from the transform: DESIGN.md row f10 -------------------------------------
+// The five sums the reference's logsv_il_pricer composes (papers/il_hedging/run_logsv_for_il_payoff.py), for the case
+// (x, xa, xb) = (log p1, log pa, log pb) of blockIdx.x and the parameter set of blockIdx.y, each through mgf_slice_nansum -- five
+// passes over the grid, every one in the family's fixed order, so a case of a batch is bit-equal to the case alone:
+//   0  square root   Re[ (v_j / pi) (exp((phi + 1/2) xb - phi x) - exp((phi + 1/2) xa - phi x)) / (phi + 1/2) exp(log E_j) ]  (:113-120)
+//   1  vanilla, pa   Re[ -(w_j / pi) / ((phi + 1) phi) exp(-(x - xa) phi + log E_j) ]   (utils/mgf_pricer.py:197, spot measure)
+//   2  vanilla, pb   the same with x - xb
+//   3  digital, pa   Re[ (w_j / pi) / phi exp(-(x - xa) phi + log E_j) ]: mgf_digital_slice_kernel's term on its put side; the
+//   4  digital, pb   host changes the sign of the SUM on a contour with every Re phi < 0 (the same bits as negated terms)
+// w: the legacy weights; v: the validated weights of compute_integration_weights -- Simpson's are the legacy ones on the odd
+// grids that rule accepts, the trapezoid's are one step with half a step on the first AND the last point.  The complex divisions
+// are NumPy's (Smith's form).  NaN terms are dropped, inf is kept, a log E of -inf gives a zero term.  A log E of +inf: the
+// exponential's real part is inf cos and its imaginary part inf sin, and where the imaginary part of the exponent is exactly 0
+// it is kept 0 as C99's cexp and NumPy's do (mgf_digital_slice_kernel's rule), so that point contributes Re[p] inf and not NaN;
+// elsewhere the product is inf - inf = NaN (dropped) or a signed inf (kept), as NumPy's product of the same factors gives.
+// Five passes and not one pass of five sums: mgf_slice_nansum stays the family's only sum loop.  They do show: 256 cases x 1 001
+// points take 154 us in eight launches where the digital entry takes 43 us for 256 strikes (profiles/il_bench.json: 19 us a
+// launch against a launch floor of 5).  A profile of 1 001 forwards is 1.1 ms with the ODE launch against the reference's second
+// per forward; widening the loop to carry five sums is the step after this one and is not taken here.
+constexpr int IL_SLICE_SUMS = SVMC_IL_SLICE_SUMS;
+
+struct IlSliceCases {
+    double x[MGF_SLICE_STRIKES], xa[MGF_SLICE_STRIKES], xb[MGF_SLICE_STRIKES];     // 768 B of kernel arguments
+};
+
+__global__ __launch_bounds__(MGF_SLICE_BLOCK) void mgf_il_slice_kernel(const cd *__restrict__ phi, const cd *__restrict__ log_mgf,
+                                                                       int n_grid, IlSliceCases ca, int is_simpson,
+                                                                       double *__restrict__ sums, int sums_ld)
+{
+    __shared__ double lds[4];
+    phi += static_cast<size_t>(blockIdx.y) * n_grid;                  // blockIdx.y: the parameter set of a batched call
+    log_mgf += static_cast<size_t>(blockIdx.y) * n_grid;
+    sums += static_cast<size_t>(blockIdx.y) * sums_ld + static_cast<size_t>(IL_SLICE_SUMS) * blockIdx.x;
+    const double x = ca.x[blockIdx.x], xa = ca.xa[blockIdx.x], xb = ca.xb[blockIdx.x];
+    const double h = phi[1].im - phi[0].im;
+    const auto store = [&](int k, double total) {
+        if (threadIdx.x == 0) sums[k] = total;
+        __syncthreads();                                              // every thread has read the wave totals: lds may be written again
+    };
+    // exp(arg) with the imaginary part of a real exponent kept (see above)
+    const auto cexp_real_kept = [](cd arg) {
+        cd e = cexp_(arg);
+        if (arg.im == 0.0) e.im = arg.im;
+        return e;
+    };
+    store(0, mgf_slice_nansum(n_grid, lds, [&](int j) {
+        const double v = (is_simpson ? legacy_weight(phi, j, n_grid, h, 1) : ((j == 0 || j == n_grid - 1) ? 0.5 * h : h)) / PI;
+        const cd b = phi[j], bh = b + 0.5;
+        const cd eb = cexp_(cd{bh.re * xb - b.re * x, bh.im * xb - b.im * x});
+        const cd ea = cexp_(cd{bh.re * xa - b.re * x, bh.im * xa - b.im * x});
+        const cd p = complex_over_complex(v * (eb - ea), bh);                                   // :118-119
+        const cd e = cexp_real_kept(log_mgf[j]);
+        return p.re * e.re - p.im * e.im;                                                       // nansum :120
+    }));
+    for (int piece = 0; piece < 4; ++piece) {                         // (block-uniform)
+        const double xk = x - ((piece & 1) ? xb : xa);
+        const bool vanilla = piece < 2;
+        store(1 + piece, mgf_slice_nansum(n_grid, lds, [&](int j) {
+            const double a = legacy_weight(phi, j, n_grid, h, is_simpson) / PI;
+            const cd b = phi[j];
+            const cd p = vanilla ? -real_over_complex(a, (b + 1.0) * b) : real_over_complex(a, b);
+            const cd e = cexp_real_kept(log_mgf[j] - xk * b);
+            return p.re * e.re - p.im * e.im;
+        }));
+    }
 }
 
 // np.histogram(a, bins=n_bins, range=(lo, hi)) on equal bins, NumPy's own steps: values outside [lo, hi] and NaNs are dropped; the
@@ -470,6 +530,32 @@ int svmc_mgf_digital_slice_batch(const double *phi, const double *log_mgf, size_
                            static_cast<int>(n_strikes));
     }
     return check_launch("svmc_mgf_digital_slice_batch");
+}
+
+int svmc_mgf_il_slice_batch(const double *phi, const double *log_mgf, size_t n_grid, int n_sets, const double *x_host,
+                            const double *xa_host, const double *xb_host, size_t n_cases, int is_simpson, double *sums,
+                            svmc_stream_t stream)
+{
+    SVMC_REQUIRE(phi && log_mgf && sums, "svmc_mgf_il_slice_batch: null pointer");
+    SVMC_REQUIRE(n_grid >= 3 && n_grid < (1u << 30), "svmc_mgf_il_slice_batch: grid too short or too long");
+    SVMC_REQUIRE(n_cases == 0 || (x_host && xa_host && xb_host), "svmc_mgf_il_slice_batch: null cases");
+    SVMC_REQUIRE(n_cases < (1u << 28), "svmc_mgf_il_slice_batch: too many cases");
+    SVMC_REQUIRE(n_sets >= 1 && n_sets <= 65535, "svmc_mgf_il_slice_batch: n_sets out of range");
+    for (size_t k = 0; k < n_cases; ++k)             // the logarithm of any price that is not positive and finite: every term dropped, a silent 0
+        SVMC_REQUIRE(std::isfinite(x_host[k]) && std::isfinite(xa_host[k]) && std::isfinite(xb_host[k]) && xa_host[k] < xb_host[k],
+                     "svmc_mgf_il_slice_batch: log p1, log pa < log pb must be finite");
+    for (size_t k0 = 0; k0 < n_cases; k0 += MGF_SLICE_STRIKES) {
+        IlSliceCases ca;
+        const auto same = [](double v) { return v; };
+        const int k_here = fill_strike_chunk(ca.x, x_host, k0, n_cases, same);
+        fill_strike_chunk(ca.xa, xa_host, k0, n_cases, same);
+        fill_strike_chunk(ca.xb, xb_host, k0, n_cases, same);
+        hipLaunchKernelGGL(mgf_il_slice_kernel, dim3(k_here, static_cast<unsigned>(n_sets)), dim3(MGF_SLICE_BLOCK), 0,
+                           as_stream(stream), reinterpret_cast<const cd *>(phi), reinterpret_cast<const cd *>(log_mgf),
+                           static_cast<int>(n_grid), ca, is_simpson ? 1 : 0, sums + IL_SLICE_SUMS * k0,
+                           static_cast<int>(IL_SLICE_SUMS * n_cases));
+    }
+    return check_launch("svmc_mgf_il_slice_batch");
 }
 
 int svmc_histogram_uniform(const double *values, size_t n, double divisor, const double *edges, int n_bins, uint64_t *counts,

@@ -3422,6 +3422,152 @@ static int tilted_payoff_impl(const char *fn, const double *const *xs, size_t n_
     return flush();
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Impermanent loss of a concentrated-liquidity range on the resident terminal state (svmc_il_payoff; include/svmc.h states the
+// estimator and the keep rule).  Three launches: il_moment_kernel, one pass for [sum exp(x), kept] per path
+// block; il_payoff_kernel, block (path block, group of IL_G cases): every block adds the moment rows in block_column_sum2's
+// order -- the same bits in every block -- for the mean M, then per kept path and case the six pieces, d = pay - pay(p1) and d^2
+// (the shift keeps the variance free of the cancellation of pay^2 against its mean); il_finish_kernel, a block per case: the
+// case's eight columns in row order, then the value, its error, the piece means and the counts.  The path blocks are a function
+// of the path count alone (il_path_blocks), a case's accumulators do not look at its neighbours' and the block sum's tree is the
+// same for every accumulator index: a case's results are the same bits whichever other cases share the call.
+// ---------------------------------------------------------------------------------------------------
+constexpr int IL_G = 4;                 // cases per block: 32 accumulators; no scratch (the build's kernel metadata)
+constexpr int IL_NV = 8;                // per case [sqrt, linear, put, call, digital put, digital call, d, d^2]
+constexpr unsigned IL_BLOCKS = 256;     // path blocks at most: il_finish_kernel reads one row per thread
+constexpr size_t IL_PATHS_PER_BLOCK = 2048;
+
+static inline unsigned il_path_blocks(size_t n_path)
+{
+    const size_t g = (n_path + IL_PATHS_PER_BLOCK - 1) / IL_PATHS_PER_BLOCK;
+    return static_cast<unsigned>(g < 1 ? 1 : (g > IL_BLOCKS ? IL_BLOCKS : g));
+}
+
+struct IlCase {                         // a row of the device table, SVMC_IL_CASE_DOUBLES doubles
+    double p1, p0, pa, pb, notional;
+};
+static_assert(sizeof(IlCase) == SVMC_IL_CASE_DOUBLES * sizeof(double), "the case table's row");
+
+struct IlConsts {
+    double p0, pa, pb, sp0, inv_spa, inv_spb, two_spa, two_spb;
+};
+
+__device__ __forceinline__ IlConsts il_consts(const IlCase &c)
+{
+    const double sp0 = sqrt_pos(c.p0), spa = sqrt_pos(c.pa), spb = sqrt_pos(c.pb);
+    return IlConsts{c.p0, c.pa, c.pb, sp0, 1.0 / spa, 1.0 / spb, 2.0 * spa, 2.0 * spb};
+}
+
+// the six pieces of a spot and the hold-minus-pool value they compose (the reference's order of terms)
+__device__ __forceinline__ double il_pieces(const IlConsts &k, double spot, double (&pc)[6])
+{
+    const bool below = spot < k.pa, above = spot > k.pb;
+    pc[0] = (below || above) ? 0.0 : sqrt_pos(spot);               // pa <= spot <= pb: a negative recentred spot never gets here
+    pc[1] = k.sp0 * (spot / k.p0 + 1.0);
+    pc[2] = fmax(k.pa - spot, 0.0);
+    pc[3] = fmax(spot - k.pb, 0.0);
+    pc[4] = below ? 1.0 : 0.0;
+    pc[5] = above ? 1.0 : 0.0;
+    return -2.0 * pc[0] + pc[1] + k.inv_spa * pc[2] - k.inv_spb * pc[3] - k.two_spa * pc[4] - k.two_spb * pc[5];
+}
+
+__global__ __launch_bounds__(BLOCK) void il_moment_kernel(const double *__restrict__ x, size_t n, double *__restrict__ moments)
+{
+    __shared__ double lds[4 * 2];
+    constexpr double INF = __builtin_huge_val();
+    double acc[2] = {0.0, 0.0};
+    for (size_t i = static_cast<size_t>(blockIdx.x) * BLOCK + threadIdx.x; i < n; i += static_cast<size_t>(gridDim.x) * BLOCK) {
+        const double xi = x[i], e = exp_full(xi);
+        const bool keep = (fabs(xi) < INF) && (e < INF);             // a NaN fails both
+        acc[0] += keep ? e : 0.0;
+        acc[1] += keep ? 1.0 : 0.0;
+    }
+    block_sum_apply<2>(acc, lds, 2, [&](int j, double t) { moments[static_cast<size_t>(j) * gridDim.x + blockIdx.x] = t; });
+}
+
+__global__ __launch_bounds__(BLOCK) void il_payoff_kernel(const double *__restrict__ x, size_t n, const IlCase *__restrict__ cases,
+                                                          int n_cases, const double *__restrict__ moments, unsigned n_rows,
+                                                          double *__restrict__ partials)
+{
+    constexpr int NSUM = IL_G * IL_NV;
+    static_assert(NSUM % 8 == 0, "block_sum_apply's halving tree");
+    __shared__ double lds[4 * NSUM];
+    __shared__ double mean_exp;
+    constexpr double INF = __builtin_huge_val();
+    double s0, s1;
+    block_column_sum2(moments, moments + n_rows, n_rows, lds, s0, s1);
+    if (threadIdx.x == 0) mean_exp = s0 / s1;
+    __syncthreads();                                                 // ... and lds may be written again
+    const double M = mean_exp;
+    IlConsts k[IL_G];
+    double p1[IL_G], corr[IL_G], ref[IL_G], acc[NSUM];
+#pragma unroll
+    for (int g = 0; g < IL_G; ++g) {
+        const int c = static_cast<int>(blockIdx.y) * IL_G + g;
+        const IlCase cs = cases[c < n_cases ? c : n_cases - 1];      // a group's unused slots repeat the last case, unstored
+        k[g] = il_consts(cs);
+        p1[g] = cs.p1;
+        corr[g] = cs.p1 * M - cs.p1;
+        double pc[6];
+        ref[g] = il_pieces(k[g], cs.p1, pc);
+    }
+#pragma unroll
+    for (int j = 0; j < NSUM; ++j) acc[j] = 0.0;
+    for (size_t i = static_cast<size_t>(blockIdx.x) * BLOCK + threadIdx.x; i < n; i += static_cast<size_t>(gridDim.x) * BLOCK) {
+        const double xi = x[i], e = exp_full(xi);
+        const bool keep = (fabs(xi) < INF) && (e < INF);
+        if (!keep) continue;
+#pragma unroll
+        for (int g = 0; g < IL_G; ++g) {
+            double pc[6];
+            const double d = il_pieces(k[g], p1[g] * e - corr[g], pc) - ref[g];
+#pragma unroll
+            for (int q = 0; q < 6; ++q) acc[IL_NV * g + q] += pc[q];
+            acc[IL_NV * g + 6] += d;
+            acc[IL_NV * g + 7] = fma(d, d, acc[IL_NV * g + 7]);
+        }
+    }
+    // partials[path block][case][IL_NV]
+    double *row = partials + static_cast<size_t>(blockIdx.x) * n_cases * IL_NV;
+    block_sum_apply<NSUM>(acc, lds, NSUM, [&](int j, double t) {
+        const int c = static_cast<int>(blockIdx.y) * IL_G + j / IL_NV;
+        if (c < n_cases) row[static_cast<size_t>(c) * IL_NV + (j % IL_NV)] = t;
+    });
+}
+
+__global__ __launch_bounds__(BLOCK) void il_finish_kernel(const IlCase *__restrict__ cases, int n_cases,
+                                                          const double *__restrict__ moments, const double *__restrict__ partials,
+                                                          unsigned n_rows, double n_path, double *__restrict__ out)
+{
+    __shared__ double lds[4];
+    const int c = blockIdx.x;
+    const size_t ld = static_cast<size_t>(n_cases) * IL_NV;
+    double tot[IL_NV + 1];
+#pragma unroll
+    for (int q = 0; q <= IL_NV; ++q) {
+        tot[q] = (q < IL_NV) ? block_column_sum(partials + static_cast<size_t>(c) * IL_NV + q, n_rows, ld, lds)
+                             : block_column_sum(moments + n_rows, n_rows, 1, lds);
+        __syncthreads();                                             // thread 0 has read the wave totals
+    }
+    if (threadIdx.x != 0) return;
+    const IlCase cs = cases[c];
+    const IlConsts k = il_consts(cs);
+    double pc[6];
+    const double ref = il_pieces(k, cs.p1, pc);
+    const double kept = tot[IL_NV];
+    const double spa = 0.5 * k.two_spa, spb = 0.5 * k.two_spb;                                      // exact halves
+    const double scale = (1.0 / (2.0 * k.sp0 - cs.p0 / spb - spa)) * cs.notional;                   // notional0 notional
+    const double md = tot[6] / kept;
+    const double var = (kept > 1.0) ? fmax(tot[7] / kept - md * md, 0.0) : 0.0;     // one kept path: zero identically
+    double *o = out + static_cast<size_t>(c) * SVMC_IL_OUT_DOUBLES;
+    o[0] = -scale * (ref + md);
+    o[1] = scale * sqrt(var / kept);
+#pragma unroll
+    for (int q = 0; q < 6; ++q) o[2 + q] = tot[q] / kept;
+    o[8] = kept;
+    o[9] = n_path - kept;
+}
+
 // the stepping of svmc_chain.hip's fused chains from the start state (0, sigma0 | var0, 0): svmc_*_chain_rng_from, or the slice
 // kernel for a single expiry; spot_sums null leaves the per-wave partial columns in `workspace` for the one-device tail
 int logsv_step_partials(double sigma0, double *x, double *sigma, double *qvar, size_t n_path, int n_slices, const int *nb_steps_host,
@@ -3712,6 +3858,51 @@ int svmc_tilted_payoff_chain(const double *const *x_snapshots_host, size_t n_pat
     return tilted_payoff_impl(fn, x_snapshots_host, n_path, forwards_host, n_expiries, strikes_host, types_host, shifts_host,
                               strike_offsets_host, gammas_host, n_gammas, recenter ? spot_sums : nullptr, prices, stderrs, stats,
                               workspace, workspace_bytes, as_stream(stream));
+}
+
+int svmc_il_payoff_workspace_bytes(size_t n_path, size_t n_cases, size_t *bytes)
+{
+    SVMC_REQUIRE(bytes, "svmc_il_payoff_workspace_bytes: null pointer");
+    SVMC_REQUIRE(n_path >= 1 && n_cases >= 1 && n_cases <= SVMC_IL_MAX_CASES, "svmc_il_payoff_workspace_bytes: n_path or n_cases out of range");
+    const size_t rows = il_path_blocks(n_path);
+    // [moments 2 x rows | case table | results | partials rows x n_cases x 8]
+    *bytes = sizeof(double) * (2 * rows + n_cases * (SVMC_IL_CASE_DOUBLES + SVMC_IL_OUT_DOUBLES) + rows * n_cases * IL_NV);
+    return SVMC_OK;
+}
+
+int svmc_il_payoff(const double *x, size_t n_path, const double *cases_host, size_t n_cases, double *out_host, void *workspace,
+                   size_t workspace_bytes, svmc_stream_t stream)
+{
+    const char *fn = "svmc_il_payoff";
+    SVMC_REQUIRE(x && cases_host && out_host && workspace, std::string(fn) + ": null pointer");
+    SVMC_REQUIRE(n_path >= 1 && n_path < (static_cast<size_t>(1) << 40), std::string(fn) + ": n_path must be in 1 .. 2^40 - 1");
+    SVMC_REQUIRE(n_cases >= 1 && n_cases <= SVMC_IL_MAX_CASES, std::string(fn) + ": n_cases outside 1 .. SVMC_IL_MAX_CASES");
+    for (size_t c = 0; c < n_cases; ++c) {
+        const double *r = cases_host + SVMC_IL_CASE_DOUBLES * c;
+        for (int q = 0; q < SVMC_IL_CASE_DOUBLES; ++q)
+            SVMC_REQUIRE(r[q] > 0.0 && r[q] < HUGE_VAL, std::string(fn) + ": p1, p0, pa, pb and the notional must be positive and finite");
+        SVMC_REQUIRE(r[2] < r[1] && r[1] < r[3], std::string(fn) + ": a case needs pa < p0 < pb");
+    }
+    size_t need = 0;
+    svmc_il_payoff_workspace_bytes(n_path, n_cases, &need);
+    if (workspace_bytes < need) return fail(SVMC_ERR_WORKSPACE, std::string(fn) + ": workspace too small (svmc_il_payoff_workspace_bytes)");
+    const unsigned rows = il_path_blocks(n_path);
+    double *moments = static_cast<double *>(workspace);
+    IlCase *cases = reinterpret_cast<IlCase *>(moments + 2 * static_cast<size_t>(rows));
+    double *out = reinterpret_cast<double *>(cases + n_cases);
+    double *partials = out + n_cases * SVMC_IL_OUT_DOUBLES;
+    hipStream_t s = as_stream(stream);
+    SVMC_HIP_TRY(hipMemcpyAsync(cases, cases_host, sizeof(IlCase) * n_cases, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(il_moment_kernel, dim3(rows), dim3(BLOCK), 0, s, x, n_path, moments);
+    hipLaunchKernelGGL(il_payoff_kernel, dim3(rows, static_cast<unsigned>((n_cases + IL_G - 1) / IL_G)), dim3(BLOCK), 0, s, x, n_path,
+                       static_cast<const IlCase *>(cases), static_cast<int>(n_cases), static_cast<const double *>(moments), rows, partials);
+    hipLaunchKernelGGL(il_finish_kernel, dim3(static_cast<unsigned>(n_cases)), dim3(BLOCK), 0, s, static_cast<const IlCase *>(cases),
+                       static_cast<int>(n_cases), static_cast<const double *>(moments), static_cast<const double *>(partials), rows,
+                       static_cast<double>(n_path), out);
+    if (int rc = check_launch(fn)) return rc;
+    SVMC_HIP_TRY(hipMemcpyAsync(out_host, out, sizeof(double) * n_cases * SVMC_IL_OUT_DOUBLES, hipMemcpyDeviceToHost, s));
+    SVMC_HIP_TRY(hipStreamSynchronize(s));
+    return SVMC_OK;
 }
 
 int svmc_payoff_finalize(const double *sums_host, const double *shifts_host, size_t n_strikes, double discfactor,

@@ -1,5 +1,6 @@
-// svmc_mgf_slice.h -- what the five transform-inversion slice kernels share (mgf_vanilla_slice_kernel, mgf_qvar_slice_kernel:
-// svmc_analytic.hip; mgf_gamma_slice_kernel: svmc_hawkes.hip; mgf_pdf_slice_kernel, mgf_digital_slice_kernel: svmc_density.hip).
+// svmc_mgf_slice.h -- what the six transform-inversion slice kernels share (mgf_vanilla_slice_kernel, mgf_qvar_slice_kernel:
+// svmc_analytic.hip; mgf_gamma_slice_kernel: svmc_hawkes.hip; mgf_pdf_slice_kernel, mgf_digital_slice_kernel,
+// mgf_il_slice_kernel: svmc_density.hip).
 // A block handles one strike (or space point) of one parameter set (blockIdx.y), MGF_SLICE_BLOCK threads stride the transform
 // grid and NaN terms are dropped, as the reference's np.nansum does.  The order of the sum depends on the grid length alone --
 // thread t adds j = t, t + 256, ... in order, the 64 lanes of a wave meet in one shuffle tree and the four waves are added in
@@ -13,7 +14,7 @@
 namespace svmc {
 
 constexpr double PI = 3.14159265358979323846;
-constexpr int MGF_SLICE_BLOCK = 256;         // threads per block of the five kernels
+constexpr int MGF_SLICE_BLOCK = 256;         // threads per block of the six kernels
 constexpr int MGF_SLICE_STRIKES = 32;        // strikes per launch (kernel-argument block)
 static_assert(MGF_SLICE_BLOCK == 256, "block_sum adds four waves");
 
@@ -28,6 +29,28 @@ __device__ __forceinline__ double legacy_weight(const cd *__restrict__ u, int j,
         return (h / 3.0) * w;
     }
     return (j == 0) ? 0.5 * h : u[j].im - u[j - 1].im;
+}
+
+// (a + 0i) / b as NumPy divides (Smith's form: the larger component of b scales the other)
+__device__ __forceinline__ cd real_over_complex(double a, cd b)
+{
+    if (fabs(b.re) >= fabs(b.im)) {
+        const double rat = b.im / b.re, scl = 1.0 / (b.re + b.im * rat);
+        return cd{a * scl, -(a * rat) * scl};
+    }
+    const double rat = b.re / b.im, scl = 1.0 / (b.im + b.re * rat);
+    return cd{(a * rat) * scl, -a * scl};
+}
+
+// a / b of two complex numbers, the same form
+__device__ __forceinline__ cd complex_over_complex(cd a, cd b)
+{
+    if (fabs(b.re) >= fabs(b.im)) {
+        const double rat = b.im / b.re, scl = 1.0 / (b.re + b.im * rat);
+        return cd{(a.re + a.im * rat) * scl, (a.im - a.re * rat) * scl};
+    }
+    const double rat = b.re / b.im, scl = 1.0 / (b.im + b.re * rat);
+    return cd{(a.re * rat + a.im) * scl, (a.im * rat - a.re) * scl};
 }
 
 // the block's sum in its fixed order; thread 0 holds it

@@ -998,6 +998,24 @@ class HipEngine:
         out = self.download(out_ptr, n_out)
         return tilted_results(out[:G * K], out[G * K:2 * G * K], out[2 * G * K:], ch)
 
+    def il_payoffs(self, p1, p0, pa, pb, notional=1000000, snap_row: Optional[int] = None, return_pieces: bool = False):
+        """the Monte Carlo impermanent loss of the ranges [pa, pb] opened at p0, at the forwards p1, from the resident
+        log-returns, whichever generator left them (svmc_il_payoff, include/svmc.h): the current state x, or snapshot row
+        snap_row.  p1, p0, pa, pb, notional broadcast together and share one path set, one recentring and one pass.  Returns
+        (value, stderr) in the broadcast shape (scalars for scalar input), and with return_pieces a dict of the six piece means,
+        n_kept and n_dropped.  ValueError before any device work for an invalid case."""
+        from .pricers.il_pricer import IL_OUT_DOUBLES, il_cases, il_mc_results
+        cases, shape = il_cases(p1, p0, pa, pb, notional)
+        n = cases.shape[0]
+        nbytes = C.c_size_t(0)
+        _lib.check(self.lib.svmc_il_payoff_workspace_bytes(self.n_path, n, C.byref(nbytes)))
+        ws_ptr, _ = self.alloc_sums((nbytes.value + 7) // 8, "il_workspace")
+        out = np.empty((n, IL_OUT_DOUBLES))
+        dp = C.POINTER(C.c_double)
+        _lib.check(self.lib.svmc_il_payoff(self.x.ptr if snap_row is None else self.snapshot_ptr(snap_row), self.n_path,
+                                           cases.ctypes.data_as(dp), n, out.ctypes.data_as(dp), ws_ptr, nbytes.value, self.stream))
+        return il_mc_results(out, shape, return_pieces)
+
     def price_hawkesjd_chain_tilted_fused(self, ch: dict, params: np.ndarray, nb_steps_per_year: int, seed: int, call_id: int,
                                           gammas, recenter: bool):
         """the Hawkes chain under the risk-premia kernel for every gamma from ONE stepping launch, as one

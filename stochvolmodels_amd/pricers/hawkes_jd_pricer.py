@@ -350,6 +350,24 @@ class HawkesJDPricer(ModelPricer):
                                           nb_steps_per_year=kwargs.get("nb_steps_per_year", NB_STEPS_PER_YEAR),
                                           seed=kwargs.get("seed"))
 
+    def model_mc_il_payoff(self, params: HawkesJDParams, ttm: float, p1, p0, pa, pb, nb_path: int = 100000, nb_steps: Optional[int] = None,
+                           seed: Optional[int] = None, notional=1000000, return_pieces: bool = False, **kwargs):
+        """the Monte Carlo impermanent loss of the range [pa, pb] opened at p0, at the forward p1, under this model: the terminal
+        log-returns of simulate_terminal_values stay on the device and svmc_il_payoff reduces them (include/svmc.h: recentred
+        spots, value = -(notional0 notional) mean(pay), its standard error).  p1, p0, pa, pb, notional broadcast together and
+        share one path set.  nb_steps: the number of time steps (default: the model's daily grid).  Returns (value, stderr), and
+        with return_pieces=True a dict of the six piece means, n_kept and n_dropped.  params.risk_premia_gamma is not applied.  A sharded request (comm=, devices=) raises
+        NotImplementedError.  Not in the reference, which has no Monte Carlo side for this payoff."""
+        from .il_pricer import il_cases, refuse_sharded_il
+        refuse_sharded_il("model_mc_il_payoff", kwargs)
+        il_cases(p1, p0, pa, pb, notional)                       # ValueError before any device work
+        p = params.to_dict()
+        p.pop("risk_premia_gamma")
+        lambda_p, lambda_m = p.pop("lambda_p"), p.pop("lambda_m")
+        eng = hawkesjd_terminal_on_engine(ttm=ttm, x0=np.zeros(nb_path), lambda_p0=lambda_p * np.ones(nb_path),
+                                          lambda_m0=lambda_m * np.ones(nb_path), nb_path=nb_path, **p, seed=seed, nb_steps=nb_steps)
+        return eng.il_payoffs(p1, p0, pa, pb, notional, return_pieces=return_pieces)
+
     def get_log_return_mc_pdf_device(self, ttm: float, params: HawkesJDParams, x_grid: np.ndarray, nb_path: int = 100000,
                                      **kwargs) -> np.ndarray:
         """get_log_return_mc_pdf (LOG_RETURN, the model's one priced variable) with the state left on the device and the
@@ -853,15 +871,18 @@ def hawkesjd_terminal_on_engine(ttm: float, x0: np.ndarray, lambda_p0: np.ndarra
                                 sigma: float, shift_p: float, mean_p: float, shift_m: float, mean_m: float, theta_p: float,
                                 kappa_p: float, beta1_p: float, beta2_p: float, theta_m: float, kappa_m: float,
                                 beta1_m: float, beta2_m: float, nb_path: int = 100000,
-                                nb_steps_per_year: int = NB_STEPS_PER_YEAR, seed: Optional[int] = None):
-    """simulate_hawkesjd_terminal with the terminal state left on the engine it returns"""
+                                nb_steps_per_year: int = NB_STEPS_PER_YEAR, seed: Optional[int] = None,
+                                nb_steps: Optional[int] = None):
+    """simulate_hawkesjd_terminal with the terminal state left on the engine it returns; nb_steps: a number of equal time steps
+    in place of the grid of nb_steps_per_year"""
     x0 = _broadcast(x0, nb_path, np.zeros)
     lambda_p0 = _broadcast(lambda_p0, nb_path, np.ones)
     lambda_m0 = _broadcast(lambda_m0, nb_path, np.ones)
     block = params_block(lambda_p=0.0, lambda_m=0.0, mu=mu, sigma=sigma, shift_p=shift_p, mean_p=mean_p, shift_m=shift_m,
                          mean_m=mean_m, theta_p=theta_p, kappa_p=kappa_p, beta1_p=beta1_p, beta2_p=beta2_p, theta_m=theta_m,
                          kappa_m=kappa_m, beta1_m=beta1_m, beta2_m=beta2_m)
-    nb_steps, dt = time_grid_steps(ttm=ttm, nb_steps_per_year=nb_steps_per_year)
+    nb_steps, dt = (time_grid_steps(ttm=ttm, nb_steps_per_year=nb_steps_per_year) if nb_steps is None
+                    else (int(nb_steps), float(ttm) / int(nb_steps)))
     rng_seed, call_id = next_rng_call(seed)
     eng = get_engine(int(nb_path))
     eng.set_state(x0, lambda_p0, lambda_m0)

@@ -121,15 +121,30 @@ class HestonPricer(ModelPricer):
         return self._simulate_on_engine(params, ttm, nb_path, kwargs.get("scheme", "euler"), kwargs.get("seed")).get_state()
 
     @staticmethod
-    def _simulate_on_engine(params: HestonParams, ttm: float, nb_path: int, scheme, seed):
-        """the terminal state of simulate_terminal_values left on the engine it returns (the state stays on the device)"""
-        nb_steps, dt = time_grid_steps(ttm=ttm, nb_steps_per_year=360)
+    def _simulate_on_engine(params: HestonParams, ttm: float, nb_path: int, scheme, seed, nb_steps: Optional[int] = None):
+        """the terminal state of simulate_terminal_values left on the engine it returns (the state stays on the device);
+        nb_steps: a number of equal time steps in place of the daily grid's"""
+        nb_steps, dt = time_grid_steps(ttm=ttm, nb_steps_per_year=360) if nb_steps is None else (int(nb_steps), float(ttm) / int(nb_steps))
         rng_seed, call_id = next_rng_call(seed)
         eng = get_engine(nb_path)
         eng.fill_state(0.0, params.v0, 0.0)           # constant initial state written on the device (reference :98-107)
         eng.heston_rng(nb_steps, dt, params.theta, params.kappa, params.rho, params.volvol, _scheme_code(scheme), rng_seed,
                        call_id, 0)
         return eng
+
+    def model_mc_il_payoff(self, params: HestonParams, ttm: float, p1, p0, pa, pb, nb_path: int = 100000, nb_steps: Optional[int] = None,
+                           seed: Optional[int] = None, notional=1000000, return_pieces: bool = False, **kwargs):
+        """the Monte Carlo impermanent loss of the range [pa, pb] opened at p0, at the forward p1, under this model: the terminal
+        log-returns of simulate_terminal_values stay on the device and svmc_il_payoff reduces them (include/svmc.h: recentred
+        spots, value = -(notional0 notional) mean(pay), its standard error).  p1, p0, pa, pb, notional broadcast together and
+        share one path set.  nb_steps: the number of time steps (default: the model's daily grid).  Returns (value, stderr), and
+        with return_pieces=True a dict of the six piece means, n_kept and n_dropped.  scheme= as simulate_terminal_values.  A sharded request (comm=, devices=) raises
+        NotImplementedError.  Not in the reference, which has no Monte Carlo side for this payoff."""
+        from .il_pricer import il_cases, refuse_sharded_il
+        refuse_sharded_il("model_mc_il_payoff", kwargs)
+        il_cases(p1, p0, pa, pb, notional)                       # ValueError before any device work
+        eng = self._simulate_on_engine(params, ttm, nb_path, kwargs.get("scheme", "euler"), seed, nb_steps)
+        return eng.il_payoffs(p1, p0, pa, pb, notional, return_pieces=return_pieces)
 
     def terminal_value_histograms(self, params: HestonParams, space_grids: dict, ttm: float = 1.0, nb_path: int = 100000,
                                   **kwargs) -> dict:
