@@ -8,6 +8,7 @@ hipcc cross-compiles without a GPU; the resulting .so files are git-ignored but 
 """
 from __future__ import annotations
 
+import glob
 import hashlib
 import json
 import os
@@ -27,15 +28,19 @@ LIB = os.path.join(PKG, "libsvmc.so")
 ISA_JSON = os.path.join(PKG, "libsvmc.isa.json")
 ISA_KERNELS = ("logsv_rng_kernel", "logsv_chain_rng_kernel", "heston_rng_kernelILi0", "heston_rng_kernelILi1", "heston_rng_kernelILi2",
                "logsv_rng_lat_kernelILi4ELi4ELi256", "logsv_chain_rng_lat_kernelILi4ELi4ELi256", "hawkesjd_chain_rng_kernel")
-SOURCES = ("svmc_runtime.hip", "svmc_kernels.hip", "svmc_analytic.hip", "svmc_chain.hip", "svmc_comm.hip", "svmc_multi.hip",
-           "svmc_hawkes.hip", "svmc_density.hip")
-HEADERS = ("svmc_internal.h", "svmc_models.h", "svmc_rng.h", "svmc_math.h", "svmc_log_table.h", "svmc_icdf_table.h", "svmc_black.h", "svmc_ode.h", "svmc_dop853.h",
-           "svmc_slice.h", "svmc_complex.h", "svmc_mgf_slice.h")
+SOURCES = ("svmc_runtime.hip", "svmc_kernels.hip", "svmc_heston.hip", "svmc_rough.hip", "svmc_analytic.hip", "svmc_chain.hip",
+           "svmc_comm.hip", "svmc_multi.hip", "svmc_hawkes.hip", "svmc_density.hip")
+ASM_GLOB = "*-hip-amdgcn-amd-amdhsa-gfx950.s"       # the device assembly --save-temps leaves, one file per unit
 ARCH = "gfx950"
 # the test-only device build of the math, complex and Black-76 helpers (tests/test_gpu_device_math.py): not part of the
 # package or its C ABI, built here so that it is compiled whenever the library is, with the library's flags
 PROBE_SRC = os.path.join(ROOT, "tests", "native", "device_math_probe.hip")
 PROBE_LIB = os.path.join(ROOT, "tests", "native", "libsvmc_device_probe.so")
+
+
+def headers() -> list:
+    """every header of csrc/: a header nobody listed cannot leave a stale library behind"""
+    return sorted(glob.glob(os.path.join(CSRC, "*.h")))
 
 
 def hipcc() -> str:
@@ -59,7 +64,7 @@ def is_stale() -> bool:
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, f) for f in SOURCES + HEADERS] + [os.path.join(INCLUDE, "svmc.h"), __file__]
+    deps = [os.path.join(CSRC, f) for f in SOURCES] + headers() + [os.path.join(INCLUDE, "svmc.h"), __file__]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -67,7 +72,7 @@ def probe_is_stale() -> bool:
     if not os.path.exists(PROBE_LIB):
         return True
     t = os.path.getmtime(PROBE_LIB)
-    deps = [PROBE_SRC, os.path.join(INCLUDE, "svmc.h"), __file__] + [os.path.join(CSRC, f) for f in HEADERS]
+    deps = [PROBE_SRC, os.path.join(INCLUDE, "svmc.h"), __file__] + headers()
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -101,10 +106,9 @@ def file_sha256(path: str) -> str:
 def kernel_metadata(asm_dir: str) -> dict:
     """{kernel symbol: {vgpr, sgpr, scratch_bytes, lds_bytes}} of every kernel of this build, read off the amdhsa metadata the
     compiler appends to its assembly -- a spill (scratch_bytes > 0) is visible in the build, not only in a profile"""
-    import glob
     import re
     out = {}
-    for path in sorted(glob.glob(os.path.join(asm_dir, "*-hip-amdgcn-amd-amdhsa-gfx950.s"))):
+    for path in sorted(glob.glob(os.path.join(asm_dir, ASM_GLOB))):
         text = open(path).read()
         start = text.find("amdhsa.kernels:")
         if start < 0:
@@ -122,15 +126,15 @@ def kernel_metadata(asm_dir: str) -> dict:
     return out
 
 
-def write_isa_json(asm_path: str, *more_asm: str) -> None:
+def write_isa_json(asm_dir: str) -> None:
     """per-kernel instruction histogram of the time loops (tools/isa_histogram.py) + the library's hash; the kernels are looked
-    up in the assembly of every translation unit given"""
+    up in the device assembly of every translation unit (asm_dir: where --save-temps left it)"""
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     try:
         import isa_histogram
     finally:
         sys.path.pop(0)
-    text = "\n".join(open(p).read() for p in (asm_path,) + more_asm)
+    text = "\n".join(open(p).read() for p in sorted(glob.glob(os.path.join(asm_dir, ASM_GLOB))))
     kernels = {}
     for name in ISA_KERNELS:
         try:
@@ -139,7 +143,7 @@ def write_isa_json(asm_path: str, *more_asm: str) -> None:
             kernels[name] = {"error": str(exc)}
     with open(ISA_JSON, "w") as fh:
         json.dump({"lib_sha256": file_sha256(LIB), "flags": flags(), "kernels": kernels,
-                   "metadata": kernel_metadata(os.path.dirname(asm_path))}, fh, indent=1)
+                   "metadata": kernel_metadata(asm_dir)}, fh, indent=1)
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
@@ -156,9 +160,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
             raise RuntimeError("hipcc failed:\n" + res.stdout + res.stderr)
         if verbose and res.stderr:
             print(res.stderr)
-        asm = os.path.join(tmp, "svmc_kernels-hip-amdgcn-amd-amdhsa-gfx950.s")
         try:
-            write_isa_json(asm, os.path.join(tmp, "svmc_hawkes-hip-amdgcn-amd-amdhsa-gfx950.s"))
+            write_isa_json(tmp)
         except Exception as exc:                             # the histogram is measurement metadata, never a build failure
             if verbose:
                 print("isa histogram skipped:", exc)

@@ -1,6 +1,6 @@
 // svmc_chain.hip -- fused single-GPU chain drivers of the C ABI: one call prices a whole option chain.
 //
-// Restates, in host C++ over the kernels of svmc_kernels.hip, the expiry loop of logsv_mc_chain_pricer
+// Restates, in host C++ over the kernels of svmc_kernels.hip and svmc_heston.hip, the expiry loop of logsv_mc_chain_pricer
 // (pricers/logsv_pricer.py:806-867) and heston_mc_chain_pricer (pricers/heston_pricer.py:285-331): state
 // x0 = 0, vol0 = v0, qvar0 = 0; per slice nb_steps_i = int((T_i - T_{i-1}) * spy) + 1 (utils/funcs.py:44) and
 // dt_i = (T_i - T_{i-1}) / nb_steps_i; the state is carried slice to slice in HBM; payoffs per slice by

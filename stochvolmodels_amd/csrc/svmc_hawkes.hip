@@ -128,7 +128,7 @@ struct HawkesManySlices {
     int m;
 };
 
-// Where hawkes_body's job comes from (as ChainArgs / ManyTable of svmc_kernels.hip).  The body is written once over a job source
+// Where hawkes_body's job comes from (as ChainArgs / ManyTable of svmc_jobs.h).  The body is written once over a job source
 // and runs the same statements -- hence gives the same bits -- whichever one hands it the job:
 //   HawkesArgs   the one-job kernels: everything is a kernel argument; the path starts from `init` or the state arrays at step
 //                `step_offset` of its streams, expiry i goes to row i, and the terminal state is written back

@@ -26,9 +26,31 @@ int fail(int code, const std::string &msg);
 
 inline hipStream_t as_stream(svmc_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
-// rows of the generators' per-WAVE spot partials ([column][wave], svmc_kernels.hip SliceOut): one per 64 paths.  A fused launch
+// rows of the generators' per-WAVE spot partials ([column][wave], svmc_slice.h SliceOut): one per 64 paths.  A fused launch
 // writes 2 columns per (expiry, parameter set), so its workspace holds wave_rows(n) x 2 x columns doubles
 inline unsigned wave_rows(size_t n) { return static_cast<unsigned>((n + 63) / 64); }
+
+// ---- svmc_kernels.hip: host functions every Monte Carlo unit shares, each defined once
+// the calling host thread's armed clock-probe buffer (svmc_clock_probe_arm), or null: a launcher that passes the probe (the LogSV
+// on-device-RNG generators and the volatility paths; no other family) passes this -- one function, one thread_local, whichever unit
+uint64_t *&armed_probe();
+// true: a launch of n_path paths runs the few-waves form of its generator (per-device cache; SVMC_FEW_WAVES_MAX_PATHS read
+// once): ONE function for every unit
+size_t device_simds();
+bool few_waves_launch(size_t n_path);
+// the argument checks of the stepping entry points; allow_null_spot: the on-device-RNG slice launchers' internal callers
+int check_state(const char *fn, const double *x, const double *v, const double *q, int nb_steps, double dt);
+int check_slice_args(const char *fn, size_t n_path, const double *x_snapshot, const double *spot_sums, const void *workspace,
+                     size_t workspace_bytes, bool allow_null_spot = false);
+// reduce_columns_kernel is launched from svmc_kernels.hip only: out[j] = sum_r partials_base[r row_stride + j col_stride],
+// j < n_cols (no launch check)
+void reduce_columns(unsigned n_cols, hipStream_t stream, const double *partials_base, unsigned n_rows, size_t row_stride,
+                    size_t col_stride, double *out);
+// the host side of the many-job table (svmc_jobs.h): the launch's slices and the checks every family makes first
+struct ManySlices;
+ManySlices many_slices(int n_slices, const int *nb_steps_host, const double *forwards_host);
+int check_many(const char *fn, size_t n_path, int n_jobs, int n_slices, const int *nb_steps_host, const double *dts_host,
+               const uint32_t *call_ids);
 
 // svmc_kernels.hip: launches whose model constants live in device memory (graph replay, svmc_chain.hip)
 constexpr int LOGSV_CONSTS_DOUBLES = 13;
@@ -37,7 +59,7 @@ int logsv_slice_w_indirect(double *x, double *sigma, double *qvar, size_t n_path
                            const double *W0, const double *W1, size_t ldw, double forward, double *x_snapshot,
                            double *qvar_snapshot, double *spot_sums, void *workspace, size_t workspace_bytes,
                            hipStream_t stream);
-constexpr int MAX_FUSED_SLICES = 16;    // = MAX_CHAIN_SLICES of svmc_kernels.hip
+constexpr int MAX_FUSED_SLICES = 16;    // = MAX_CHAIN_SLICES of svmc_jobs.h
 int logsv_chain_w_indirect(double *x, double *sigma, double *qvar, size_t n_path, int n_slices, const int *nb_steps_host,
                            const double *consts_dev, const double *vol0_dev, const double *const *W0s, const double *const *W1s,
                            size_t ldw, const double *forwards_host, double *x_snapshots, double *qvar_snapshots,
@@ -86,7 +108,10 @@ int hawkes_step_partials(const double *params_host, double *x, double *lam_p, do
 // (many_table_bytes, from the pinned table_host into table_dev) and writes job j's snapshot rows j m + i ([J m][n], qvar rows the
 // same at qvar_snapshots) and per-wave spot partial column pairs 2 (j m + i) ([2 J m][wave_rows(n)]); params_host rows as in
 // svmc.h.  payoff_sets_workspace_bytes bounds the workspace chain_payoff_and_finish_sets needs for the jobs' payoff partials.
+// many_table_bytes is the largest of the families' *_many_table_bytes (svmc_kernels.hip, svmc_heston.hip, svmc_hawkes.hip).
 size_t many_table_bytes(int n_jobs, int n_slices);
+size_t logsv_many_table_bytes(int n_jobs, int n_slices);
+size_t heston_many_table_bytes(int n_jobs, int n_slices);
 int logsv_chain_rng_many(size_t n_path, int n_jobs, int n_slices, const int *nb_steps_host, const double *dts_host,
                          const double *forwards_host, const double *params_host, int is_spot_measure, const uint64_t *seeds,
                          const uint32_t *call_ids, uint64_t path_offset, void *table_host, void *table_dev, double *x_snapshots,
@@ -114,7 +139,7 @@ bool spot_sums_in_payoff_kernel(size_t n_path);
 int reduce_spot_partials(const void *workspace, size_t n_path, int n_cols, double *spot_sums, hipStream_t stream);
 int check_launch(const char *what);          // hipGetLastError -> SVMC_ERR_HIP "what: ..."
 
-// The chain stepping of every on-device-RNG generator (LogSV, Heston: svmc_kernels.hip; Hawkes: svmc_hawkes.hip): the argument
+// The chain stepping of every on-device-RNG generator (LogSV: svmc_kernels.hip; Heston: svmc_heston.hip; Hawkes: svmc_hawkes.hip): the argument
 // checks, launches of at most MAX_FUSED_SLICES expiries whose unused slice entries repeat a valid one, the step offset carried
 // from launch to launch, and the reduce of each launch's per-wave spot partials into spot_sums -- with spot_sums null (one launch
 // at most) they stay in `workspace`.  The model supplies fill(cs, i, j): entry i of its slices struct from expiry j (nb_steps and

@@ -5,66 +5,32 @@
 // on-device-RNG kernels, and 16 B per path-step (the two supplied normals, coalesced 512 B per wave
 // per load) in the streamed-randoms kernels.  No MFMA: the work is elementwise fp64 VALU +
 // transcendentals (DESIGN.md "Rooflines").
+//
+// The Heston and the rough-LogSV families are units of their own (svmc_heston.hip, svmc_rough.hip); what they share with this
+// file is in svmc_block.h and svmc_jobs.h, and the host functions they call here are declared in svmc_internal.h.
 #include "svmc_internal.h"
 
+#include <algorithm>
 #include <atomic>
 #include <cstdlib>
 #include <cstring>
 #include <type_traits>
 #include <utility>
 #include "svmc_black.h"
+#include "svmc_block.h"
+#include "svmc_jobs.h"
 #include "svmc_models.h"
 #include "svmc_rng.h"
 #include "svmc_slice.h"
 
 namespace svmc {
 
-constexpr int BLOCK = 256;             // 4 waves of 64 lanes
-#ifndef SVMC_MAX_REDUCE_GRID
-#define SVMC_MAX_REDUCE_GRID 1024
-#endif
-constexpr int MAX_REDUCE_GRID = SVMC_MAX_REDUCE_GRID;  // 256 CUs x 4 blocks: cap for grid-stride reductions
-
-// block size of the on-device-RNG generators: a block stages the draw's tables in LDS once for all of its waves
-#ifndef SVMC_RNG_BLOCK
-#define SVMC_RNG_BLOCK 512
-#endif
-constexpr int RNG_BLOCK = SVMC_RNG_BLOCK;
-static constexpr int rng_block() { return RNG_BLOCK; }
 #ifndef SVMC_RNG_SGPRS
 #define SVMC_RNG_SGPRS 72              // SGPR budget of the LogSV stepping kernels (tools/ubench/ab_kernels.py sweeps it)
 #endif
-static inline unsigned rng_grid(size_t n) { return static_cast<unsigned>((n + rng_block() - 1) / rng_block()); }
-
-static inline unsigned grid_for(size_t n) { return static_cast<unsigned>((n + BLOCK - 1) / BLOCK); }
-
-// In-kernel clock probe of the on-device-RNG LogSV generators (svmc_clock_probe_arm / _read; bench.py
-// roofline.clock_mhz_in_kernel): measurement plumbing, OFF unless the calling host thread armed it.  The stepping kernels
-// take a nullable `probe` argument -- null in every product launch: one scalar test, nothing else.  When a thread has armed
-// the probe, ITS launches pass that thread's own 8-word device buffer and thread 0 of the launch's FIRST and LAST block stamp
-// s_memtime (tick = shader cycle) and s_memrealtime (100 MHz, chip-wide) at kernel entry and again after the time loop:
-// (t_exit - t_entry) / (r_exit - r_entry) x 100 MHz is the shader clock that wave saw while it stepped -- measured in the
-// timed launch itself, where the SMU's sysfs sensor (absent on some boxes of the pool) lags and averages.  No global: two
-// engines on two streams (tests/test_gpu_parity.py::test_two_engines_on_their_own_streams) never share stamps, and a
-// thread that did not arm the probe never writes any (round 4 kept one __device__ array every launch of three kernels
-// wrote: a race between engines and bench-only code on the hot path).
-// Layout: [which = 0 first block | 1 last block][t_entry, r_entry, t_exit, r_exit]; the latest armed launch wins.
-__device__ __forceinline__ void clock_probe_stamp(uint64_t *probe, int at_exit)
-{
-    if (probe == nullptr) return;                                                    // wave-uniform (a kernel argument)
-    const bool first = blockIdx.x == 0u, last = blockIdx.x == gridDim.x - 1u;        // wave-uniform
-    if (first || last) {
-        const uint64_t t = __builtin_readcyclecounter(), r = wall_clock64();
-        if (threadIdx.x == 0u) {
-            uint64_t *o = probe + (first ? 0 : 4) + 2 * at_exit;
-            o[0] = t;
-            o[1] = r;
-        }
-    }
-}
 
 // the calling host thread's armed probe buffer (device memory of the device that was current at svmc_clock_probe_arm), or null
-static uint64_t *&armed_probe()
+uint64_t *&armed_probe()
 {
     thread_local uint64_t *p = nullptr;
     return p;
@@ -110,183 +76,6 @@ __global__ __launch_bounds__(BLOCK) void fill_uniforms_kernel(double *__restrict
     const uint64_t gp = path_offset + p;
     for (int t = 0; t < nb_steps; ++t)
         U[static_cast<size_t>(t) * ldw + p] = draw_uniform(seed, c3, gp, step_offset + static_cast<uint32_t>(t));
-}
-
-// ---------------------------------------------------------------------------------------------------
-// Deterministic block reductions: wave shuffles in a fixed tree, one LDS exchange, ONE barrier for any number of
-// values (the first version paid two barriers per value: 96 per payoff block).
-// ---------------------------------------------------------------------------------------------------
-// One halving level of the multi-value butterfly: lanes with (lane & MASK) set keep the upper half of v[0..2H),
-// the others the lower half, and add the partner lane's copy of the half they keep.
-template <int H, int MASK>
-__device__ __forceinline__ void butterfly_halve(const double *v, double *w, int lane)
-{
-    const bool hi = (lane & MASK) != 0;
-#pragma unroll
-    for (int j = 0; j < H; ++j) {
-        const double mine = hi ? v[H + j] : v[j];
-        const double other = hi ? v[j] : v[H + j];
-        w[j] = mine + __shfl_xor(other, MASK, 64);
-    }
-}
-
-// values a block sum works on: NV rounded up to a multiple of 8 from 8 on (the halving tree below wants it; zeros fill up)
-constexpr int block_sum_padded(int nv) { return nv >= 8 ? (nv + 7) / 8 * 8 : nv; }
-
-// every thread of the block calls; thread j < n_out ends up with the block total of v[j] and hands it to store(j, total)
-template <int NV, class Store>
-__device__ __forceinline__ void block_sum_apply(double (&v)[NV], double *lds /* [4 * block_sum_padded(NV)] */, int n_out,
-                                                Store &&store)
-{
-    constexpr int NP = block_sum_padded(NV);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n_waves = blockDim.x >> 6;
-    if constexpr (NP % 8 == 0) {
-        // NP values over 64 lanes in NP/2 + NP/4 + NP/8 + 3*NP/8 shuffles instead of 6*NP: three halving levels
-        // (xor 32, 16, 8) leave every lane with NP/8 partial sums of the index block its bits 5..3 select, three
-        // plain levels (xor 4, 2, 1) finish them.  Fixed tree, hence deterministic.
-        double vp[NP], a[NP / 2], b[NP / 4], c[NP / 8];
-#pragma unroll
-        for (int j = 0; j < NP; ++j) vp[j] = (j < NV) ? v[j] : 0.0;
-        butterfly_halve<NP / 2, 32>(vp, a, lane);
-        butterfly_halve<NP / 4, 16>(a, b, lane);
-        butterfly_halve<NP / 8, 8>(b, c, lane);
-#pragma unroll
-        for (int j = 0; j < NP / 8; ++j) {
-            c[j] += __shfl_xor(c[j], 4, 64);
-            c[j] += __shfl_xor(c[j], 2, 64);
-            c[j] += __shfl_xor(c[j], 1, 64);
-        }
-        if ((lane & 7) == 0) {
-            const int off = ((lane & 32) ? NP / 2 : 0) + ((lane & 16) ? NP / 4 : 0) + ((lane & 8) ? NP / 8 : 0);
-#pragma unroll
-            for (int j = 0; j < NP / 8; ++j) lds[wave * NP + off + j] = c[j];
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < NV; ++j) v[j] = wave_sum(v[j]);
-        if (lane == 0) {
-#pragma unroll
-            for (int j = 0; j < NV; ++j) lds[wave * NP + j] = v[j];
-        }
-    }
-    __syncthreads();
-    if (static_cast<int>(threadIdx.x) < n_out) {
-        const int j = threadIdx.x;
-        double t = lds[j];
-        for (int w = 1; w < n_waves; ++w) t += lds[w * NP + j];      // fixed order: wave 0, 1, 2, 3
-        store(j, t);
-    }
-}
-
-// thread j < n_out writes the block total of v[j] to out[j]
-template <int NV>
-__device__ __forceinline__ void block_sum_store(double (&v)[NV], double *lds /* [4 * block_sum_padded(NV)] */, double *out, int n_out)
-{
-    block_sum_apply<NV>(v, lds, n_out, [&](int j, double t) { out[j] = t; });
-}
-
-// The sum of one column, the ONE order of additions every column reduction of the library uses (so that a sum does not depend on
-// which kernel formed it).  256 (virtual) threads: thread t adds rows t, t + 256, ... into four accumulators -- sixteen rows at a
-// time into a[k mod 4] while sixteen remain, then four at a time into a[0..3], then the last three or fewer into a[0] --, forms
-// (a0 + a1) + (a2 + a3), each wave adds its 64 lanes in a fixed shuffle tree and the four wave totals are added in wave order.
-// A row is one 8-byte read at a stride of ld -- latency, not bandwidth: what a reduction costs is how many DEPENDENT round trips
-// it makes, so the loads are batched (sixteen per trip in the long loop; a column of up to NR x 256 rows has ALL its loads in
-// flight before the first addition -- round 6: the spot columns of a 10^5-path launch were 1 + 3 dependent round trips, 4.7 us of
-// a 5 us kernel) and the additions keep the order above: the same bits whichever route.
-template <int NR>
-__device__ __forceinline__ void column_rows_load(const double *__restrict__ partials, unsigned r, unsigned n_rows, size_t ld, double (&t)[NR])
-{
-#pragma unroll
-    for (int k = 0; k < NR; ++k) {
-        const unsigned rk = r + static_cast<unsigned>(k) * BLOCK;
-        t[k] = (rk < n_rows) ? partials[static_cast<size_t>(rk) * ld] : 0.0;
-    }
-}
-// ... for n_rows <= NR x 256 (NR = 4 or 8: the sixteen-row loop never runs): the additions of the loops, on the preloaded rows
-template <int NR>
-__device__ __forceinline__ double column_rows_add(const double (&t)[NR], unsigned r, unsigned n_rows)
-{
-    static_assert(NR == 4 || NR == 8, "one or two trips of the four-row loop");
-    const unsigned cnt = (n_rows > r) ? (n_rows - r + BLOCK - 1) / BLOCK : 0u;        // rows of this thread
-    double a[4] = {0.0, 0.0, 0.0, 0.0};
-    unsigned k = 0;
-    if (cnt >= 4u) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) a[u] += t[u];
-        k = 4;
-        if constexpr (NR == 8) {
-            if (cnt >= 8u) {
-#pragma unroll
-                for (int u = 0; u < 4; ++u) a[u] += t[4 + u];
-                k = 8;
-            }
-        }
-    }
-#pragma unroll
-    for (int kk = 0; kk < NR; ++kk)
-        if (static_cast<unsigned>(kk) >= k && static_cast<unsigned>(kk) < cnt) a[0] += t[kk];
-    return (a[0] + a[1]) + (a[2] + a[3]);
-}
-// any n_rows: the loops themselves
-__device__ __forceinline__ double column_rows_sum(const double *__restrict__ partials, unsigned r, unsigned n_rows, size_t ld)
-{
-    double a[4] = {0.0, 0.0, 0.0, 0.0};
-    for (; r + 15 * BLOCK < n_rows; r += 16 * BLOCK) {
-        double t[16];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) t[u] = partials[static_cast<size_t>(r + u * BLOCK) * ld];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-#pragma unroll
-            for (int u = 0; u < 4; ++u) a[u] += t[4 * k + u];
-        }
-    }
-    for (; r + 3 * BLOCK < n_rows; r += 4 * BLOCK) {
-        double t[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) t[u] = partials[static_cast<size_t>(r + u * BLOCK) * ld];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) a[u] += t[u];
-    }
-    for (; r < n_rows; r += BLOCK) a[0] += partials[static_cast<size_t>(r) * ld];
-    return (a[0] + a[1]) + (a[2] + a[3]);
-}
-
-// by a 256-thread block: every thread calls; thread 0 returns the total (the others a partial)
-__device__ __forceinline__ double block_column_sum(const double *__restrict__ partials, unsigned n_rows, size_t ld, double *lds /* [4] */)
-{
-    double v[1];
-    if (n_rows <= 8u * BLOCK) {                             // (block-uniform)
-        double t[8];
-        column_rows_load<8>(partials, threadIdx.x, n_rows, ld, t);
-        v[0] = column_rows_add<8>(t, threadIdx.x, n_rows);
-    } else {
-        v[0] = column_rows_sum(partials, threadIdx.x, n_rows, ld);
-    }
-    double total = 0.0;
-    block_sum_apply<1>(v, lds, 1, [&](int, double t) { total = t; });
-    return total;
-}
-
-// two columns by one block with the loads of BOTH in flight together (the payoff kernel's spot sums: [sum F exp(x), count])
-__device__ __forceinline__ void block_column_sum2(const double *__restrict__ p0, const double *__restrict__ p1, unsigned n_rows, double *lds,
-                                                  double &s0, double &s1)
-{
-    double v0[1], v1[1];
-    if (n_rows <= 8u * BLOCK) {
-        double t0[8], t1[8];
-        column_rows_load<8>(p0, threadIdx.x, n_rows, 1, t0);
-        column_rows_load<8>(p1, threadIdx.x, n_rows, 1, t1);
-        v0[0] = column_rows_add<8>(t0, threadIdx.x, n_rows);
-        v1[0] = column_rows_add<8>(t1, threadIdx.x, n_rows);
-    } else {
-        v0[0] = column_rows_sum(p0, threadIdx.x, n_rows, 1);
-        v1[0] = column_rows_sum(p1, threadIdx.x, n_rows, 1);
-    }
-    s0 = s1 = 0.0;
-    block_sum_apply<1>(v0, lds, 1, [&](int, double t) { s0 = t; });
-    __syncthreads();                                        // thread 0 has read the wave totals: lds may be written again
-    block_sum_apply<1>(v1, lds, 1, [&](int, double t) { s1 = t; });
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -382,7 +171,6 @@ __global__ __launch_bounds__(RNG_BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8)
 // next Philox call and the issue of the pair after that between them -- a wave overlaps its own LDS round trips with its own
 // arithmetic, and the waves of a CU cannot fall into a common LDS phase.  The forms it was measured against:
 // profiles/r06_mid_waves_sweep.json.
-constexpr int FEW_BLOCK = 256;
 // the time loop of a LogSV generator: the pipelined form, the step in its two halves
 template <int LOOP>
 __device__ __forceinline__ void logsv_gen_time_loop(const PhiloxLane &lane, uint32_t step0, int nb, const RngTables &tab, const LogsvFast &c,
@@ -454,7 +242,7 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
 // the reference's default 10^5 paths) and the block shape in between (256-thread blocks spread 6.1 waves per SIMD evenly where
 // 1024-thread blocks leave a third of the CUs with eight).
 // SVMC_FEW_WAVES_MAX_PATHS overrides the limit as a path count (0: the full-launch kernels always).
-static size_t device_simds()
+size_t device_simds()
 {
     // per device of the calling thread's current context; the attribute query costs microseconds, so it is cached per device
     static std::atomic<size_t> cache[64];
@@ -473,7 +261,7 @@ static size_t device_simds()
 constexpr int LAT_WAVES_PER_SIMD = 7;
 
 // true: the launch runs the few-waves form of its generator
-static bool few_waves_launch(size_t n_path)
+bool few_waves_launch(size_t n_path)
 {
     static const long long env_max = [] {
         const char *e = getenv("SVMC_FEW_WAVES_MAX_PATHS");
@@ -488,7 +276,6 @@ static bool few_waves_launch(size_t n_path)
 // launches each pay their own ramp-up and ramp-down (C4: 8 x 1.03 ms against 7.44 ms for one 1024-step launch);
 // here the chain pays one.  L and sigma^2 are re-derived from sigma at every slice start exactly as a fresh launch
 // would (the slice is the one function the single-slice kernels call), so the results are the bits of the slice-by-slice path.
-constexpr int MAX_CHAIN_SLICES = 16;
 struct ChainSlices {
     LogsvFast c[MAX_CHAIN_SLICES];
     double forward[MAX_CHAIN_SLICES];
@@ -497,127 +284,9 @@ struct ChainSlices {
     __device__ __forceinline__ LogsvFast consts(int i) const { return c[i]; }
 };
 
-// ---- many independent jobs of one chain in ONE stepping launch (svmc_logsv_chain_price_many / svmc_heston_chain_price_many)
-// blockIdx.y = job, blockIdx.x = block of that job's n paths; path p of job j draws philox_prepare(seed_j, c3_j, path_offset + p)
-// and runs the body of the one-job kernels from the start state (0, vol0_j, 0), so job j's snapshots and per-wave
-// spot partials are those of a single call with (seed_j, call_id_j), bit for bit.  Outputs go to row j m + i (expiry i of job j)
-// in the set-major layout of logsv_chain_rng_sets_kernel: ONE payoff launch (blockIdx.z = job) and ONE finish launch serve
-// every job.  The terminal state is not written back (no job owns the session's state arrays).
-constexpr int MAX_MANY_JOBS = SVMC_MANY_MAX_JOBS;
-struct ManySlices {
-    double forward[MAX_CHAIN_SLICES];
-    int nb_steps[MAX_CHAIN_SLICES];
-    int m, total_steps = 0;
-};
-// the per-job device table, one upload per call: the (job, expiry) constants [J][m] (LogsvFast, or HestonManyConsts),
-// then per job the start vol (variance for Heston), the Philox key and the call id's counter word
-struct ManyJobs {
-    const void *consts;
-    const double *vol0;
-    const uint64_t *seed;
-    const uint32_t *c3;
-};
-
-// a job-uniform value read from the job table, word by word into scalar registers: the step takes its constants as scalar
-// operands (fma_k's "s" constraint), which a table load the compiler issued as a vector load would not satisfy
-template <class T>
-__device__ __forceinline__ T uniform_load(const T *p)
-{
-    static_assert(sizeof(T) % 4 == 0, "whole 32-bit words");
-    uint32_t w[sizeof(T) / 4];
-    memcpy(w, p, sizeof(T));
-#pragma unroll
-    for (int k = 0; k < static_cast<int>(sizeof(T) / 4); ++k) w[k] = __builtin_amdgcn_readfirstlane(w[k]);
-    T out;
-    memcpy(&out, w, sizeof(T));
-    return out;
-}
-
-// a (job, expiry) entry of the table.  Heston's: the constants of one slice, also what a one-job source hands the Heston body
-struct HestonManyConsts {
-    HestonConsts c;
-    QeConsts qc;
-};
-// LogSV's entry goes through uniform_load; Heston's step has no scalar-operand constraint and the compiler issues the plain load
-// of a job-uniform address as scalar loads on its own (forced through uniform_load the Heston kernels spill to scratch)
+// a (job, expiry) entry of the many-job table (ManyTable<LogsvFast>, svmc_jobs.h) goes through uniform_load: the step takes its
+// constants as scalar operands
 __device__ __forceinline__ LogsvFast many_consts_load(const LogsvFast *p) { return uniform_load(p); }
-__device__ __forceinline__ HestonManyConsts many_consts_load(const HestonManyConsts *p) { return *p; }
-
-// Where a whole-chain body's job comes from.  The LogSV and Heston chain bodies are written once over a job source and run the
-// same statements -- hence give the same bits -- whichever one hands them the job:
-//   ChainArgs<Slices>   the one-job kernels: everything is a kernel argument (Slices = ChainSlices | HestonChainSlices); the path
-//                       starts from `init` or the state arrays at step `step_offset` of its stream, expiry i goes to row i, and
-//                       the terminal state is written back
-//   ManyTable<Consts>   the many-job kernels: job blockIdx.y of the device table (Consts = LogsvFast | HestonManyConsts); the path
-//                       starts from (0, vol0_j, 0) at step 0, expiry i goes to row j m + i, nothing is written back
-template <class Slices>
-struct ChainArgs {
-    const Slices &cs;
-    uint64_t seed_;
-    uint32_t c3_, step_offset;
-    const StateInit &init;
-    double *__restrict__ x, *__restrict__ vol, *__restrict__ qvar;
-
-    __device__ __forceinline__ int m() const { return cs.m; }
-    __device__ __forceinline__ int nb_steps(int i) const { return cs.nb_steps[i]; }
-    __device__ __forceinline__ int total_steps() const { return cs.total_steps; }
-    __device__ __forceinline__ double forward(int i) const { return cs.forward[i]; }
-    __device__ __forceinline__ auto consts(int i) const { return cs.consts(i); }
-    __device__ __forceinline__ uint64_t seed() const { return seed_; }
-    __device__ __forceinline__ uint32_t c3() const { return c3_; }
-    __device__ __forceinline__ uint32_t step_origin() const { return step_offset; }
-    __device__ __forceinline__ size_t row(int i) const { return static_cast<size_t>(i); }
-    // (the lanes past the last path get the uniform start too, or a dummy state: the LogSV bodies step them)
-    __device__ __forceinline__ void start(size_t p, bool active, double &xv, double &v, double &q) const
-    {
-        xv = 0.0;
-        v = 1.0;
-        q = 0.0;
-        if (init.uniform) {                               // wave-uniform
-            xv = init.x0;
-            v = init.vol0;
-            q = init.qvar0;
-        } else if (active) {
-            xv = x[p];
-            v = vol[p];
-            q = qvar[p];
-        }
-    }
-    __device__ __forceinline__ void finish(size_t p, double xv, double v, double q) const
-    {
-        x[p] = xv;
-        vol[p] = v;
-        qvar[p] = q;
-    }
-};
-
-template <class Consts>
-struct ManyTable {
-    const ManySlices &cs;
-    const ManyJobs &jobs;
-
-    __device__ __forceinline__ int job() const { return blockIdx.y; }
-    __device__ __forceinline__ int m() const { return cs.m; }
-    __device__ __forceinline__ int nb_steps(int i) const { return cs.nb_steps[i]; }
-    __device__ __forceinline__ int total_steps() const { return cs.total_steps; }
-    __device__ __forceinline__ double forward(int i) const { return cs.forward[i]; }
-    __device__ __forceinline__ Consts consts(int i) const
-    {
-        const Consts *__restrict__ cj = static_cast<const Consts *>(jobs.consts) + static_cast<size_t>(job()) * cs.m;
-        return many_consts_load(cj + i);
-    }
-    __device__ __forceinline__ uint64_t seed() const { return uniform_load(jobs.seed + job()); }
-    __device__ __forceinline__ uint32_t c3() const { return uniform_load(jobs.c3 + job()); }
-    __device__ __forceinline__ uint32_t step_origin() const { return 0u; }
-    __device__ __forceinline__ size_t row(int i) const { return static_cast<size_t>(job()) * cs.m + i; }
-    __device__ __forceinline__ void start(size_t, bool, double &xv, double &v, double &q) const
-    {
-        xv = 0.0;
-        v = uniform_load(jobs.vol0 + job());
-        q = 0.0;
-    }
-    __device__ __forceinline__ void finish(size_t, double, double, double) const {}
-};
 
 #ifndef SVMC_CHAIN_WAVES
 #define SVMC_CHAIN_WAVES 8, 8          // A/B hook: residency of the whole-chain kernel (7, 8 lifts the 64-VGPR cap)
@@ -760,62 +429,6 @@ static const LogsvLatVariant LOGSV_FEW_WAVES_KERNELS = {logsv_rng_lat_kernel<GEN
 static const LogsvLatVariant *logsv_lat_variant(size_t n_path)
 {
     return few_waves_launch(n_path) ? &LOGSV_FEW_WAVES_KERNELS : nullptr;
-}
-
-static inline unsigned lat_grid(size_t n, int block = FEW_BLOCK) { return static_cast<unsigned>((n + block - 1) / block); }
-
-// Streamed-randoms time loop: HBM-bound (8 B per supplied random per path-step).  Software-pipelined by hand:
-// the NARR*U loads of the next U steps are issued before the current U steps are computed, so every wave keeps
-// NARR*U x 512 B in flight (hipcc does not unroll a loop that contains inline asm, and one load per array in
-// flight leaves the memory system latency-bound: 5.3 -> 5.7 TB/s for LogSV at U = 4; U = 8, 16 give no more).
-constexpr int STREAM_U = 4;
-#ifndef SVMC_ROUGH_STREAM_U
-#define SVMC_ROUGH_STREAM_U 4          // A/B hook: prefetch depth of the rough kernel's streamed normals
-#endif
-
-template <int NARR, int U = STREAM_U, class Step>
-__device__ __forceinline__ void streamed_time_loop(const double *const (&w)[NARR], size_t ldw, int nb_steps,
-                                                   Step &&step)
-{
-    double a[NARR][U], b[NARR][U];
-    int t = 0;
-    if (nb_steps >= U) {
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-#pragma unroll
-            for (int k = 0; k < NARR; ++k) a[k][u] = w[k][static_cast<size_t>(u) * ldw];
-        for (; t + 2 * U <= nb_steps; t += U) {
-#pragma unroll
-            for (int u = 0; u < U; ++u)                         // prefetch steps t+U .. t+2U-1
-#pragma unroll
-                for (int k = 0; k < NARR; ++k) b[k][u] = w[k][static_cast<size_t>(t + U + u) * ldw];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                double v[NARR];
-#pragma unroll
-                for (int k = 0; k < NARR; ++k) v[k] = a[k][u];
-                step(v);
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u)
-#pragma unroll
-                for (int k = 0; k < NARR; ++k) a[k][u] = b[k][u];
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            double v[NARR];
-#pragma unroll
-            for (int k = 0; k < NARR; ++k) v[k] = a[k][u];
-            step(v);
-        }
-        t += U;
-    }
-    for (; t < nb_steps; ++t) {
-        double v[NARR];
-#pragma unroll
-        for (int k = 0; k < NARR; ++k) v[k] = w[k][static_cast<size_t>(t) * ldw];
-        step(v);
-    }
 }
 
 __device__ __forceinline__ void logsv_w_body(double *__restrict__ x, double *__restrict__ sigma,
@@ -1344,399 +957,6 @@ __global__ __launch_bounds__(BLOCK) void expanding_mean_sq_kernel(const double *
 }
 
 // ---------------------------------------------------------------------------------------------------
-// Rough LogSV, Markovian lift with N <= 3 factors (pricers/rough_logsv/split_simulation.py:86-128, 228-356):
-// Strang splitting D(h/2) S(h) D(h/2) per step -- RK4 on the factor drift, exact lognormal step of the weighted
-// factor sum -- then the log-spot / quadratic-variance update.  One lane per path, the N factors in registers.
-// ---------------------------------------------------------------------------------------------------
-struct RoughConsts {
-    double nodes[3], w[3], v0[3], wlam[3];
-    double theta, kappa1, kappa2, rho, rho_comp, volvol, inv_volvol, h, inv_h, sqrt_h, wsum, w_inv, volvol_w, w_lam_v0;
-    double ito, volvol_w_sqrt_h;   // -0.5 (volvol wsum)^2 h,  volvol wsum sqrt(h)
-};
-
-template <int N>
-__device__ __forceinline__ void rough_rk4_drift(const RoughConsts &c, const double (&z0)[N], double h, double (&zh)[N])
-{
-    double s1[N], s2[N], s3[N], s4[N], zt[N], zw, g;
-    zw = 0.0;
-#pragma unroll
-    for (int i = 0; i < N; ++i) zw += c.w[i] * z0[i];
-    g = (c.kappa1 + c.kappa2 * zw) * (c.theta - zw);
-#pragma unroll
-    for (int i = 0; i < N; ++i) s1[i] = -c.nodes[i] * (z0[i] - c.v0[i]) + g;                         // :101-103
-    zw = 0.0;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        zt[i] = z0[i] + 0.5 * h * s1[i];
-        zw += c.w[i] * zt[i];
-    }
-    g = (c.kappa1 + c.kappa2 * zw) * (c.theta - zw);
-#pragma unroll
-    for (int i = 0; i < N; ++i) s2[i] = -c.nodes[i] * (zt[i] - c.v0[i]) + g;                         // :106-109
-    zw = 0.0;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        zt[i] = z0[i] + 0.5 * h * s2[i];
-        zw += c.w[i] * zt[i];
-    }
-    g = (c.kappa1 + c.kappa2 * zw) * (c.theta - zw);
-#pragma unroll
-    for (int i = 0; i < N; ++i) s3[i] = -c.nodes[i] * (zt[i] - c.v0[i]) + g;                         // :112-115
-    zw = 0.0;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        zt[i] = z0[i] + h * s3[i];
-        zw += c.w[i] * zt[i];
-    }
-    g = (c.kappa1 + c.kappa2 * zw) * (c.theta - zw);
-#pragma unroll
-    for (int i = 0; i < N; ++i) s4[i] = -c.nodes[i] * (zt[i] - c.v0[i]) + g;                         // :118-121
-#pragma unroll
-    for (int i = 0; i < N; ++i) zh[i] = z0[i] + (h / 6.0) * (s1[i] + 2.0 * s2[i] + 2.0 * s3[i] + s4[i]);
-}
-
-template <int N, class Exp>
-__device__ __forceinline__ void rough_step(const RoughConsts &c, double (&v)[N], double &ls, double &y, double z0, double z1,
-                                           Exp &&exp_of)
-{
-    double d[N], sn[N], vh[N];
-    rough_rk4_drift<N>(c, v, 0.5 * c.h, d);                                                      // :273
-    double yw = 0.0;
-#pragma unroll
-    for (int i = 0; i < N; ++i) yw += c.w[i] * d[i];
-    const double Yh = yw * exp_of(c.ito + c.volvol_w_sqrt_h * z0);   // :238-239
-    const double Q = c.w_inv * (Yh - yw);
-#pragma unroll
-    for (int i = 0; i < N; ++i) sn[i] = d[i] + Q;
-    rough_rk4_drift<N>(c, sn, 0.5 * c.h, vh);                                                    // :275
-    double volw_h = 0.0;
-#pragma unroll
-    for (int i = 0; i < N; ++i) volw_h += c.w[i] * vh[i];
-    if (!(volw_h > 0.0)) {                                                                       // NaN or <= 0, :299-300
-        volw_h = 0.0;
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-            vh[i] = 1e-6;
-            volw_h += c.w[i] * vh[i];
-        }
-    }
-    double vw = 0.0, w_lam_vol = 0.0, w_lam_vol_h = 0.0;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        vw += c.w[i] * v[i];
-        w_lam_vol += c.wlam[i] * v[i];
-        w_lam_vol_h += c.wlam[i] * vh[i];
-    }
-    const double sq_vw = vw * vw, sq_vhw = volw_h * volw_h;
-    const double term1 = c.inv_volvol * (((volw_h - vw) * c.inv_h + 0.5 * w_lam_vol + 0.5 * w_lam_vol_h - c.w_lam_v0) * c.w_inv
-                                         - c.kappa1 * c.theta + (c.kappa1 - c.kappa2 * c.theta) * (0.5 * vw + 0.5 * volw_h)
-                                         + c.kappa2 * (0.5 * sq_vw + 0.5 * sq_vhw)) * c.h;       // :319-321
-    const double term2 = 0.5 * c.h * sq_vw + 0.5 * c.h * sq_vhw;
-    ls = ls - 0.5 * term2 + c.rho * term1 + c.rho_comp * sqrt_pos(term2) * z1;                         // :324
-    y = y + 0.5 * c.h * (vw * vw + volw_h * volw_h);                                               // :326
-#pragma unroll
-    for (int i = 0; i < N; ++i) v[i] = vh[i];
-}
-
-// ALL expiries of a rough-LogSV chain in ONE launch: the reference re-simulates every expiry from time 0 on its own step
-// (pricers/logsv_pricer.py:1206-1216), so the expiries are INDEPENDENT simulations -- blockIdx.y picks one.  A calibration-
-// sized path set (4 000-10 000 paths: 63-157 waves) fills a sixteenth of the chip, and m such launches one after the other
-// each pay their own latency-bound time loop; side by side they cost the longest one.  Per expiry the arithmetic is
-// the same on the same constants (the step-dependent ones travel per expiry).  Snapshot row i / m + i and partial column pair i
-// belong to expiry i; the state arrays receive the LAST expiry's terminal state, as the expiry-by-expiry loop leaves them.
-// This is the ONLY rough kernel: a single expiry is grid.y = 1, and a continuation from the resident state (from_origin = 0,
-// the draw's steps starting at step_offset) is the same launch reading the state first -- so one launch per expiry, all
-// expiries in one launch and a run cut into continued halves execute the same code and agree to the bit by construction.
-// RNG = false: Z0/Z1 supplied (the reference's only interface for this model); true: counter-based draw.
-struct RoughExpiries {
-    double h[MAX_CHAIN_SLICES], inv_h[MAX_CHAIN_SLICES], sqrt_h[MAX_CHAIN_SLICES], ito[MAX_CHAIN_SLICES],
-        volvol_w_sqrt_h[MAX_CHAIN_SLICES], forward[MAX_CHAIN_SLICES];
-    int nb_steps[MAX_CHAIN_SLICES];
-    int m;
-};
-
-template <int N, bool RNG>
-__global__ __launch_bounds__(RNG ? RNG_BLOCK : BLOCK) void rough_logsv_expiries_kernel(
-    double *__restrict__ log_s, double *__restrict__ vol, double *__restrict__ yq, size_t n, RoughConsts c, RoughExpiries e,
-    const double *__restrict__ Z0, const double *__restrict__ Z1, size_t ldw, uint64_t seed, uint32_t c3, uint64_t path_offset,
-    uint32_t step_offset, int from_origin, double *__restrict__ x_snap, double *__restrict__ q_snap, double *__restrict__ partials)
-{
-    __shared__ RngTablesLdsIf<RNG> s_tab;                  // the draw's table only where the kernel draws
-    __shared__ double s_exp[256];
-    const RngTables tab = stage_tables_if(s_tab, s_exp);
-    const auto exp_of = [&](double a) { return exp_tab(a, s_exp); };
-    const int i = blockIdx.y;                              // the expiry: block-uniform
-    c.h = e.h[i];
-    c.inv_h = e.inv_h[i];
-    c.sqrt_h = e.sqrt_h[i];
-    c.ito = e.ito[i];
-    c.volvol_w_sqrt_h = e.volvol_w_sqrt_h[i];
-    const int nb_steps = e.nb_steps[i];
-    const size_t p = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-    const bool active = p < n;
-    double ls = 0.0, y = 0.0;
-    if (active) {
-        double v[N];
-        if (from_origin) {                                 // (log_s, v, y) = (0, v0, 0)                   :1206-1208
-#pragma unroll
-            for (int k = 0; k < N; ++k) v[k] = c.v0[k];
-        } else {                                           // continue from the resident state (single-expiry launches)
-            ls = log_s[p];
-            y = yq[p];
-#pragma unroll
-            for (int k = 0; k < N; ++k) v[k] = vol[static_cast<size_t>(k) * n + p];
-        }
-        if (RNG) {
-            const PhiloxLane lane = philox_prepare(seed, c3, path_offset + p);
-            rng_time_loop(lane, step_offset, nb_steps, tab, [&](double z0, double z1) { rough_step<N>(c, v, ls, y, z0, z1, exp_of); });
-        } else {
-            const double *const w[2] = {Z0 + p, Z1 + p};
-            streamed_time_loop<2, SVMC_ROUGH_STREAM_U>(w, ldw, nb_steps,
-                                                       [&](const double(&z)[2]) { rough_step<N>(c, v, ls, y, z[0], z[1], exp_of); });
-        }
-        if (i == e.m - 1) {
-#pragma unroll
-            for (int k = 0; k < N; ++k) vol[static_cast<size_t>(k) * n + p] = v[k];
-            log_s[p] = ls;
-            yq[p] = y;
-        }
-    }
-    const SliceOut so = {x_snap + static_cast<size_t>(i) * n, q_snap ? q_snap + static_cast<size_t>(i) * n : nullptr,
-                         partials + 2 * static_cast<size_t>(i) * ((n + 63) >> 6), e.forward[i], (n + 63) >> 6};
-    slice_epilogue(so, p, active, ls, y);
-}
-
-// ---------------------------------------------------------------------------------------------------
-// Heston generators (pricers/heston_pricer.py:334-381; QE is new)
-// ---------------------------------------------------------------------------------------------------
-// LOOP: the form of the time loop (svmc_rng.h GenLoop): the full-launch kernels run GEN_LOOP_FULL, the few-waves ones GEN_LOOP_PAIR
-// kernel-template scheme ids: the C ABI's two (SVMC_HESTON_EULER_FLOOR = 0, SVMC_HESTON_QE = 1) and QE specialised at compile
-// time for parameter sets that never leave the quadratic branch and keep the martingale correction defined (QeConsts::quad_only
-// && e_below_one; heston_qe_step<true>) -- the host picks it, the caller never sees it
-constexpr int HESTON_QE_QUAD = 2;
-constexpr bool heston_is_qe(int scheme) { return scheme == SVMC_HESTON_QE || scheme == HESTON_QE_QUAD; }
-static inline int heston_kernel_scheme(int scheme, const QeConsts &qc)
-{
-    return (scheme == SVMC_HESTON_QE && qc.quad_only && qc.e_below_one) ? HESTON_QE_QUAD : scheme;
-}
-
-template <int LOOP, class Step>
-__device__ __forceinline__ void heston_time_loop(const PhiloxLane &lane, uint32_t step0, int nb, const RngTables &tab, Step &&step)
-{
-    gen_time_loop<LOOP>(lane, step0, nb, tab, step);
-}
-
-// ONE slice of a Heston path, the statements every on-device-RNG Heston generator runs (heston_rng_body, heston_chain_rng_body):
-// nb steps from step `step` of the lane's stream, then the slice's fold into (x, v, q).  lane_u and uc serve SVMC_HESTON_QE's
-// uniforms and are dead in the other schemes.
-template <int SCHEME, int LOOP>
-__device__ __forceinline__ void heston_slice(const PhiloxLane &lane, const PhiloxLane &lane_u, QeUniforms &uc, uint32_t step, int nb,
-                                             const RngTables &tab, const HestonConsts c, const QeConsts qc, double &xv, double &v, double &q)
-{
-    const HestonEulerFast ef = make_heston_euler_fast(c);
-    double xacc = 0.0, vacc = 0.0;
-    if constexpr (SCHEME == HESTON_QE_QUAD) {
-        double vsum = 0.0, ksum = 0.0;
-        const double v_first = v;
-        const QeVec qv = make_qe_vec(qc);
-        heston_time_loop<LOOP>(lane, step, nb, tab, [&](double w0, double w1) {
-            heston_qe_step<true>(qc, qv, tab.log, xv, v, vsum, ksum, w0, w1, []() { return 0.0; });
-        });
-        heston_qe_fold(qc, xv, q, vsum, ksum, v_first, v);
-    } else if constexpr (SCHEME == SVMC_HESTON_QE) {
-        double vsum = 0.0, ksum = 0.0;
-        const double v_first = v;
-        uint32_t st = step;
-        const QeVec qv = make_qe_vec(qc);
-        heston_time_loop<LOOP>(lane, step, nb, tab, [&](double w0, double w1) {
-            heston_qe_step(qc, qv, tab.log, xv, v, vsum, ksum, w0, w1, [&]() { return qe_uniform(lane_u, st, uc); });
-            ++st;
-        });
-        heston_qe_fold(qc, xv, q, vsum, ksum, v_first, v);
-    } else {
-        v = heston_euler_guard_zero(v);
-        heston_time_loop<LOOP>(lane, step, nb, tab, [&](double w0, double w1) { heston_euler_step_acc(ef, xacc, v, vacc, w0, w1); });
-        heston_fold_acc(ef, xv, q, v, xacc, vacc);
-    }
-}
-
-template <int SCHEME, int LOOP>
-__device__ __forceinline__ void heston_rng_body(double *__restrict__ x, double *__restrict__ var, double *__restrict__ qvar, size_t n,
-                                                int nb_steps, HestonConsts c, QeConsts qc, uint64_t seed, uint32_t c3,
-                                                uint64_t path_offset, uint32_t step_offset, SliceOut so, StateInit init)
-{
-    __shared__ RngTablesLds s_tab;
-    __shared__ LogTabEntry s_log[heston_is_qe(SCHEME) ? 512 : 1];
-    RngTables tab;
-    if constexpr (heston_is_qe(SCHEME)) tab = stage_rng_log_tables(s_tab, s_log);
-    else tab = stage_rng_tables(s_tab);
-    const size_t p = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-    const bool active = p < n;
-    double xv = 0.0, v = 1.0, q = 0.0;
-    if (active) {
-        if (init.uniform) {                                // wave-uniform
-            xv = init.x0;
-            v = init.vol0;
-            q = init.qvar0;
-        } else {
-            xv = x[p];
-            v = var[p];
-            q = qvar[p];
-        }
-        const PhiloxLane lane = philox_prepare(seed, heston_is_qe(SCHEME) ? (c3 | 4u) : c3, path_offset + p);
-        const PhiloxLane lane_u = philox_prepare(seed, c3 | 5u, path_offset + p);  // QE's uniforms (dead in the other schemes)
-        QeUniforms uc;
-        heston_slice<SCHEME, LOOP>(lane, lane_u, uc, step_offset, nb_steps, tab, c, qc, xv, v, q);
-        x[p] = xv;
-        var[p] = v;
-        qvar[p] = q;
-    }
-    slice_epilogue(so, p, active, xv, q);
-}
-
-template <int SCHEME>
-__global__ __launch_bounds__(RNG_BLOCK) void heston_rng_kernel(double *__restrict__ x, double *__restrict__ var,
-                                                           double *__restrict__ qvar, size_t n, int nb_steps,
-                                                           HestonConsts c, QeConsts qc, uint64_t seed,
-                                                           uint32_t c3, uint64_t path_offset,
-                                                           uint32_t step_offset, SliceOut so, StateInit init)
-{
-    heston_rng_body<SCHEME, GEN_LOOP_FULL>(x, var, qvar, n, nb_steps, c, qc, seed, c3, path_offset, step_offset, so, init);
-}
-
-// the same generator for a launch of a few waves per SIMD (few_waves_launch(); the reference's default is 10^5 paths): the
-// statements -- and the bits -- of heston_rng_kernel, compiled for latency (see logsv_rng_lat_kernel)
-template <int SCHEME, int LOOP, int WAVES, int TB>
-__global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) void heston_rng_lat_kernel(
-    double *__restrict__ x, double *__restrict__ var, double *__restrict__ qvar, size_t n, int nb_steps, HestonConsts c, QeConsts qc,
-    uint64_t seed, uint32_t c3, uint64_t path_offset, uint32_t step_offset, SliceOut so, StateInit init)
-{
-    heston_rng_body<SCHEME, LOOP>(x, var, qvar, n, nb_steps, c, qc, seed, c3, path_offset, step_offset, so, init);
-}
-
-// whole-chain variant, as logsv_chain_rng_kernel: the slice loop inside the kernel, one launch tail per chain
-struct HestonChainSlices {
-    HestonConsts c[MAX_CHAIN_SLICES];
-    QeConsts qc[MAX_CHAIN_SLICES];
-    double forward[MAX_CHAIN_SLICES];
-    int nb_steps[MAX_CHAIN_SLICES];
-    int m;
-    __device__ __forceinline__ HestonManyConsts consts(int i) const { return {c[i], qc[i]}; }
-};
-
-// the body of the whole-chain kernels over a job source (ChainArgs<HestonChainSlices>: one job from the kernel arguments;
-// ManyTable<HestonManyConsts>: job blockIdx.y of the many-job table, see logsv_chain_rng_many_kernel)
-template <int SCHEME, int LOOP, class Source>
-__device__ __forceinline__ void heston_chain_rng_body(size_t n, const Source &src, uint64_t path_offset, double *__restrict__ x_snap,
-                                                      double *__restrict__ q_snap, double *__restrict__ partials)
-{
-    __shared__ RngTablesLds s_tab;
-    __shared__ LogTabEntry s_log[heston_is_qe(SCHEME) ? 512 : 1];
-    RngTables tab;
-    if constexpr (heston_is_qe(SCHEME)) tab = stage_rng_log_tables(s_tab, s_log);
-    else tab = stage_rng_tables(s_tab);
-    const size_t p = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-    const bool active = p < n;
-    double xv, v, q;
-    src.start(p, active, xv, v, q);
-    const uint64_t seed = src.seed();
-    const uint32_t c3 = src.c3();
-    const PhiloxLane lane = philox_prepare(seed, heston_is_qe(SCHEME) ? (c3 | 4u) : c3, path_offset + p);
-    const PhiloxLane lane_u = philox_prepare(seed, c3 | 5u, path_offset + p);      // QE's uniforms (dead in the other schemes)
-    QeUniforms uc;
-    uint32_t step = src.step_origin();
-    for (int i = 0; i < src.m(); ++i) {
-        const int nb = src.nb_steps(i);
-        if (active) {
-            const HestonManyConsts k = src.consts(i);
-            heston_slice<SCHEME, LOOP>(lane, lane_u, uc, step, nb, tab, k.c, k.qc, xv, v, q);
-        }
-        step += static_cast<uint32_t>(nb);
-        slice_epilogue(slice_out_row(x_snap, q_snap, partials, src.row(i), n, src.forward(i)), p, active, xv, q);
-    }
-    if (active) src.finish(p, xv, v, q);
-}
-
-template <int SCHEME>
-__global__ __launch_bounds__(RNG_BLOCK) void heston_chain_rng_kernel(double *__restrict__ x, double *__restrict__ var,
-                                                                 double *__restrict__ qvar, size_t n,
-                                                                 HestonChainSlices cs, uint64_t seed, uint32_t c3,
-                                                                 uint64_t path_offset, uint32_t step_offset,
-                                                                 double *__restrict__ x_snap, double *__restrict__ q_snap,
-                                                                 double *__restrict__ partials, StateInit init)
-{
-    heston_chain_rng_body<SCHEME, GEN_LOOP_FULL>(n, ChainArgs<HestonChainSlices>{cs, seed, c3, step_offset, init, x, var, qvar}, path_offset,
-                                                 x_snap, q_snap, partials);
-}
-
-template <int SCHEME, int LOOP, int WAVES, int TB>
-__global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) void heston_chain_rng_lat_kernel(
-    double *__restrict__ x, double *__restrict__ var, double *__restrict__ qvar, size_t n, HestonChainSlices cs, uint64_t seed,
-    uint32_t c3, uint64_t path_offset, uint32_t step_offset, double *__restrict__ x_snap, double *__restrict__ q_snap,
-    double *__restrict__ partials, StateInit init)
-{
-    heston_chain_rng_body<SCHEME, LOOP>(n, ChainArgs<HestonChainSlices>{cs, seed, c3, step_offset, init, x, var, qvar}, path_offset, x_snap,
-                                        q_snap, partials);
-}
-
-// many jobs of one chain in one launch: the same body on job blockIdx.y of the table
-template <int SCHEME>
-__global__ __launch_bounds__(RNG_BLOCK) void heston_chain_rng_many_kernel(size_t n, ManySlices cs, ManyJobs jobs, uint64_t path_offset,
-                                                                      double *__restrict__ x_snap, double *__restrict__ q_snap,
-                                                                      double *__restrict__ partials)
-{
-    heston_chain_rng_body<SCHEME, GEN_LOOP_FULL>(n, ManyTable<HestonManyConsts>{cs, jobs}, path_offset, x_snap, q_snap, partials);
-}
-
-template <int SCHEME, int LOOP, int WAVES, int TB>
-__global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) void heston_chain_rng_many_lat_kernel(
-    size_t n, ManySlices cs, ManyJobs jobs, uint64_t path_offset, double *__restrict__ x_snap, double *__restrict__ q_snap,
-    double *__restrict__ partials)
-{
-    heston_chain_rng_body<SCHEME, LOOP>(n, ManyTable<HestonManyConsts>{cs, jobs}, path_offset, x_snap, q_snap, partials);
-}
-
-__global__ __launch_bounds__(BLOCK) void heston_w_kernel(double *__restrict__ x, double *__restrict__ var,
-                                                         double *__restrict__ qvar, size_t n, int nb_steps,
-                                                         HestonConsts c, const double *__restrict__ W0,
-                                                         const double *__restrict__ W1, size_t ldw)
-{
-    const size_t p = static_cast<size_t>(blockIdx.x) * BLOCK + threadIdx.x;
-    if (p >= n) return;
-    double xv = x[p], v = var[p], q = qvar[p];
-    const double *const w[2] = {W0 + p, W1 + p};
-    streamed_time_loop<2>(w, ldw, nb_steps, [&](const double(&z)[2]) {
-        heston_euler_step(c, xv, v, q, c.sdt * z[0], c.sdt * z[1]);
-    });
-    x[p] = xv;
-    var[p] = v;
-    qvar[p] = q;
-}
-
-__global__ __launch_bounds__(BLOCK) void heston_qe_w_kernel(double *__restrict__ x, double *__restrict__ var,
-                                                            double *__restrict__ qvar, size_t n, int nb_steps,
-                                                            QeConsts qc, const double *__restrict__ Z0,
-                                                            const double *__restrict__ Z1,
-                                                            const double *__restrict__ U, size_t ldw)
-{
-    __shared__ LogTabEntry s_tab[512];
-    const LogTabEntry *tab = stage_log_table(s_tab);
-    const size_t p = static_cast<size_t>(blockIdx.x) * BLOCK + threadIdx.x;
-    if (p >= n) return;
-    double xv = x[p], v = var[p], q = qvar[p], vsum = 0.0, ksum = 0.0;
-    const double v_first = v;
-    const double *const w[3] = {Z0 + p, Z1 + p, U + p};
-    const QeVec qv = make_qe_vec(qc);
-    streamed_time_loop<3>(w, ldw, nb_steps, [&](const double(&z)[3]) {
-        heston_qe_step(qc, qv, tab, xv, v, vsum, ksum, z[0], z[1], [&]() { return z[2]; });
-    });
-    heston_qe_fold(qc, xv, q, vsum, ksum, v_first, v);
-    x[p] = xv;
-    var[p] = v;
-    qvar[p] = q;
-}
-
-// ---------------------------------------------------------------------------------------------------
 // Payoff reduction (utils/mc_payoffs.py:61-88).  Deterministic two-stage sums: per-block partials in a
 // fixed tree order, then one block per output column adds the partials -- no fp64 atomics, so a given
 // (n_path, grid) always reproduces the same bits.
@@ -1947,6 +1167,13 @@ __global__ __launch_bounds__(BLOCK) void reduce_columns_kernel(const double *__r
     if (threadIdx.x == 0) out[j] = t;
 }
 
+// what every other unit launches reduce_columns_kernel through: out[j] for j < n_cols, queued on `stream`; the caller checks the launch
+void reduce_columns(unsigned n_cols, hipStream_t stream, const double *partials_base, unsigned n_rows, size_t row_stride,
+                    size_t col_stride, double *out)
+{
+    hipLaunchKernelGGL(reduce_columns_kernel, dim3(n_cols), dim3(BLOCK), 0, stream, partials_base, n_rows, row_stride, col_stride, out);
+}
+
 static inline unsigned reduce_grid(size_t n)
 {
     const size_t g = (n + BLOCK - 1) / BLOCK;
@@ -1960,7 +1187,7 @@ int check_launch(const char *what)
     return SVMC_OK;
 }
 
-static int check_state(const char *fn, const double *x, const double *v, const double *q, int nb_steps, double dt)
+int check_state(const char *fn, const double *x, const double *v, const double *q, int nb_steps, double dt)
 {
     if (x == nullptr || v == nullptr || q == nullptr) return fail(SVMC_ERR_INVALID_ARGUMENT, std::string(fn) + ": null state pointer");
     if (nb_steps < 0) return fail(SVMC_ERR_INVALID_ARGUMENT, std::string(fn) + ": nb_steps < 0");
@@ -1968,7 +1195,18 @@ static int check_state(const char *fn, const double *x, const double *v, const d
     return SVMC_OK;
 }
 
-static inline uint32_t make_c3(uint32_t call_id) { return (call_id << 8); }
+// allow_null_spot (the two on-device-RNG slice launchers, for their internal callers only -- the public entry points reject a null
+// spot_sums first): with spot_sums == nullptr the launch leaves its per-wave partial columns in the workspace unreduced, and the
+// payoff kernel of svmc_chain.hip's one-device tail sums them itself
+int check_slice_args(const char *fn, size_t n_path, const double *x_snapshot, const double *spot_sums,
+                     const void *workspace, size_t workspace_bytes, bool allow_null_spot)
+{
+    if (x_snapshot == nullptr || (spot_sums == nullptr && !allow_null_spot) || workspace == nullptr)
+        return fail(SVMC_ERR_INVALID_ARGUMENT, std::string(fn) + ": null snapshot / spot_sums / workspace");
+    if (workspace_bytes < static_cast<size_t>(wave_rows(n_path)) * 2 * sizeof(double))
+        return fail(SVMC_ERR_WORKSPACE, std::string(fn) + ": workspace too small (svmc_slice_workspace_bytes)");
+    return SVMC_OK;
+}
 
 }  // namespace svmc
 
@@ -2028,19 +1266,6 @@ static int logsv_rng_launch(const char *fn, double *x, double *sigma, double *qv
         hipLaunchKernelGGL(logsv_rng_kernel, dim3(rng_grid(n_path)), dim3(rng_block()), 0, as_stream(stream), x, sigma, qvar,
                            n_path, nb_steps, c, seed, make_c3(call_id), path_offset, step_offset, so, init, armed_probe());
     return check_launch(fn);
-}
-
-// allow_null_spot (the two on-device-RNG slice launchers, for their internal callers only -- the public entry points reject a null
-// spot_sums first): with spot_sums == nullptr the launch leaves its per-wave partial columns in the workspace unreduced, and the
-// payoff kernel of svmc_chain.hip's one-device tail sums them itself
-static int check_slice_args(const char *fn, size_t n_path, const double *x_snapshot, const double *spot_sums,
-                            const void *workspace, size_t workspace_bytes, bool allow_null_spot = false)
-{
-    if (x_snapshot == nullptr || (spot_sums == nullptr && !allow_null_spot) || workspace == nullptr)
-        return fail(SVMC_ERR_INVALID_ARGUMENT, std::string(fn) + ": null snapshot / spot_sums / workspace");
-    if (workspace_bytes < static_cast<size_t>(wave_rows(n_path)) * 2 * sizeof(double))
-        return fail(SVMC_ERR_WORKSPACE, std::string(fn) + ": workspace too small (svmc_slice_workspace_bytes)");
-    return SVMC_OK;
 }
 
 int svmc_logsv_terminal_rng(double *x, double *sigma, double *qvar, size_t n_path, int nb_steps, double dt,
@@ -2258,8 +1483,8 @@ int logsv_chain_w_indirect(double *x, double *sigma, double *qvar, size_t n_path
     hipLaunchKernelGGL(logsv_chain_w_indirect_kernel, dim3(g), dim3(BLOCK), 0, stream, x, sigma, qvar, n_path, cs,
                        reinterpret_cast<const LogsvConsts *>(consts_dev), vol0_dev, ldw, x_snapshots, qvar_snapshots,
                        static_cast<double *>(workspace));
-    hipLaunchKernelGGL(reduce_columns_kernel, dim3(2 * n_slices), dim3(BLOCK), 0, stream,
-                       static_cast<const double *>(workspace), wave_rows(n_path), size_t(1), static_cast<size_t>(wave_rows(n_path)), spot_sums);
+    reduce_columns(2 * n_slices, stream, static_cast<const double *>(workspace), wave_rows(n_path), size_t(1),
+                   static_cast<size_t>(wave_rows(n_path)), spot_sums);
     return check_launch(fn);
 }
 
@@ -2306,8 +1531,8 @@ int logsv_chain_w_sets(size_t n_path, int n_sets, int n_slices, const int *nb_st
     case 7: launch_chain_w_sets<7>(g, stream, n_path, cs, consts_dev, vol0_dev, ldw, x_snapshots, qvar_snapshots, workspace); break;
     default: launch_chain_w_sets<8>(g, stream, n_path, cs, consts_dev, vol0_dev, ldw, x_snapshots, qvar_snapshots, workspace); break;
     }
-    hipLaunchKernelGGL(reduce_columns_kernel, dim3(cols), dim3(BLOCK), 0, stream, static_cast<const double *>(workspace),
-                       wave_rows(n_path), size_t(1), static_cast<size_t>(wave_rows(n_path)), spot_sums);
+    reduce_columns(cols, stream, static_cast<const double *>(workspace), wave_rows(n_path), size_t(1),
+                   static_cast<size_t>(wave_rows(n_path)), spot_sums);
     return check_launch(fn);
 }
 
@@ -2366,8 +1591,8 @@ int logsv_chain_rng_sets(size_t n_path, int n_sets, int n_slices, const int *nb_
     }
 #undef SVMC_RNG_SETS_CASE
     if (spot_sums != nullptr)                  // (null: the caller's payoff kernel sums the partial columns itself)
-        hipLaunchKernelGGL(reduce_columns_kernel, dim3(cols), dim3(BLOCK), 0, stream, static_cast<const double *>(workspace),
-                           wave_rows(n_path), size_t(1), static_cast<size_t>(wave_rows(n_path)), spot_sums);
+        reduce_columns(cols, stream, static_cast<const double *>(workspace), wave_rows(n_path), size_t(1),
+                       static_cast<size_t>(wave_rows(n_path)), spot_sums);
     return check_launch(fn);
 }
 
@@ -2479,9 +1704,8 @@ int svmc_row_power_sums(const double *a, size_t ld, size_t n_rows, size_t n_cols
     // [row][seg][j] makes output (row, j) the column sum over seg with row stride 2K and column base row * 4 * 2K + j
     const int K2 = 2 * n_moments;
     for (int j = 0; j < K2; ++j)
-        hipLaunchKernelGGL(reduce_columns_kernel, dim3(static_cast<unsigned>(n_rows)), dim3(BLOCK), 0, as_stream(stream), partials + j,
-                           static_cast<unsigned>(ROW_SEGMENTS), static_cast<size_t>(K2), static_cast<size_t>(ROW_SEGMENTS) * K2,
-                           sums + static_cast<size_t>(j) * n_rows);
+        reduce_columns(static_cast<unsigned>(n_rows), as_stream(stream), partials + j, static_cast<unsigned>(ROW_SEGMENTS),
+                       static_cast<size_t>(K2), static_cast<size_t>(ROW_SEGMENTS) * K2, sums + static_cast<size_t>(j) * n_rows);
     return check_launch("svmc_row_power_sums");
 }
 
@@ -2501,345 +1725,6 @@ int svmc_expanding_mean_squares(const double *a, size_t ld, size_t n_rows, size_
         hipLaunchKernelGGL(expanding_mean_sq_kernel<false>, dim3(grid_for(n_cols)), dim3(BLOCK), 0, as_stream(stream), a, ld, n_rows,
                            n_cols, out, ldo);
     return check_launch("svmc_expanding_mean_squares");
-}
-
-// the few-waves forms of the Heston generators, per kernel scheme id (the forms they were measured against:
-// profiles/r06_mid_waves_sweep.json).  The Euler step has no LDS read of its own, so one pair ahead hides the draw's round trip
-// completely; QE (100 registers by itself) runs the same loop at the 128-register budget.
-using HestonSliceKernel = void (*)(double *, double *, double *, size_t, int, HestonConsts, QeConsts, uint64_t, uint32_t, uint64_t, uint32_t,
-                                   SliceOut, StateInit);
-using HestonChainKernel = void (*)(double *, double *, double *, size_t, HestonChainSlices, uint64_t, uint32_t, uint64_t, uint32_t, double *,
-                                   double *, double *, StateInit);
-struct HestonLatVariant {
-    HestonSliceKernel slice;
-    HestonChainKernel chain;
-    int block;
-};
-#define SVMC_HESTON_LAT(S, WAVES) \
-    {heston_rng_lat_kernel<S, GEN_LOOP_PAIR, WAVES, FEW_BLOCK>, heston_chain_rng_lat_kernel<S, GEN_LOOP_PAIR, WAVES, FEW_BLOCK>, FEW_BLOCK}
-static const HestonLatVariant HESTON_FEW_WAVES_KERNELS[3] = {
-    SVMC_HESTON_LAT(SVMC_HESTON_EULER_FLOOR, 4),           // Euler with the reference's floor
-    SVMC_HESTON_LAT(SVMC_HESTON_QE, 3),                    // QE
-    SVMC_HESTON_LAT(HESTON_QE_QUAD, 4)};                   // QE, quadratic branch only
-#undef SVMC_HESTON_LAT
-
-// the full-launch kernels, per kernel scheme id (0, 1 or HESTON_QE_QUAD)
-static const HestonLatVariant HESTON_FULL_KERNELS[3] = {
-    {heston_rng_kernel<SVMC_HESTON_EULER_FLOOR>, heston_chain_rng_kernel<SVMC_HESTON_EULER_FLOOR>, RNG_BLOCK},
-    {heston_rng_kernel<SVMC_HESTON_QE>, heston_chain_rng_kernel<SVMC_HESTON_QE>, RNG_BLOCK},
-    {heston_rng_kernel<HESTON_QE_QUAD>, heston_chain_rng_kernel<HESTON_QE_QUAD>, RNG_BLOCK}};
-
-// -> the kernels a launch of n_path paths of kernel scheme `scheme` runs: a few-waves form or the full-launch ones
-static const HestonLatVariant *heston_variant(int scheme, size_t n_path)
-{
-    return few_waves_launch(n_path) ? &HESTON_FEW_WAVES_KERNELS[scheme] : &HESTON_FULL_KERNELS[scheme];
-}
-
-static int heston_rng_launch(const char *fn, double *x, double *var, double *qvar, size_t n_path, int nb_steps, double dt,
-                             double theta, double kappa, double rho, double volvol, int scheme, uint64_t seed,
-                             uint32_t call_id, uint64_t path_offset, uint32_t step_offset, const SliceOut &so,
-                             svmc_stream_t stream, const StateInit &init = StateInit())
-{
-    if (int rc = check_state(fn, x, var, qvar, nb_steps, dt)) return rc;
-    if (scheme != SVMC_HESTON_EULER_FLOOR && scheme != SVMC_HESTON_QE)
-        return fail(SVMC_ERR_INVALID_ARGUMENT, std::string(fn) + ": unknown scheme");
-    if (call_id >= (1u << 24)) return fail(SVMC_ERR_INVALID_ARGUMENT, std::string(fn) + ": call_id must fit 24 bits");
-    if (n_path == 0) return SVMC_OK;
-    const HestonConsts c = make_heston_consts(dt, theta, kappa, rho, volvol);
-    const QeConsts qc = make_qe_consts(dt, theta, kappa, rho, volvol);
-    const HestonLatVariant *v = heston_variant(heston_kernel_scheme(scheme, qc), n_path);
-    hipLaunchKernelGGL(v->slice, dim3(lat_grid(n_path, v->block)), dim3(v->block), 0, as_stream(stream), x, var, qvar, n_path, nb_steps, c,
-                       qc, seed, make_c3(call_id), path_offset, step_offset, so, init);
-    return check_launch(fn);
-}
-
-int svmc_heston_terminal_rng(double *x, double *var, double *qvar, size_t n_path, int nb_steps, double dt,
-                             double theta, double kappa, double rho, double volvol, int scheme, uint64_t seed,
-                             uint32_t call_id, uint64_t path_offset, uint32_t step_offset, svmc_stream_t stream)
-{
-    const SliceOut none = {nullptr, nullptr, nullptr, 0.0};
-    if (nb_steps == 0) return check_state("svmc_heston_terminal_rng", x, var, qvar, nb_steps, dt);
-    return heston_rng_launch("svmc_heston_terminal_rng", x, var, qvar, n_path, nb_steps, dt, theta, kappa, rho, volvol,
-                             scheme, seed, call_id, path_offset, step_offset, none, stream);
-}
-
-}  // extern "C"
-
-static int heston_slice_rng_impl(const char *fn, const StateInit &init, double *x, double *var, double *qvar, size_t n_path, int nb_steps, double dt, double theta,
-                          double kappa, double rho, double volvol, int scheme, uint64_t seed, uint32_t call_id,
-                          uint64_t path_offset, uint32_t step_offset, double forward, double *x_snapshot,
-                          double *qvar_snapshot, double *spot_sums, void *workspace, size_t workspace_bytes,
-                          svmc_stream_t stream)
-{
-    if (int rc = check_slice_args(fn, n_path, x_snapshot, spot_sums, workspace, workspace_bytes, true)) return rc;
-    SVMC_REQUIRE(n_path > 0 && nb_steps > 0, std::string(fn) + ": n_path and nb_steps must be positive");
-    const SliceOut so = {x_snapshot, qvar_snapshot, static_cast<double *>(workspace), forward, wave_rows(n_path)};
-    if (int rc = heston_rng_launch(fn, x, var, qvar, n_path, nb_steps, dt, theta, kappa, rho, volvol, scheme, seed,
-                                   call_id, path_offset, step_offset, so, stream, init))
-        return rc;
-    if (spot_sums == nullptr) return SVMC_OK;
-    return reduce_spot_partials(workspace, n_path, 2, spot_sums, as_stream(stream));
-}
-
-extern "C" {
-
-int svmc_heston_slice_rng(double *x, double *var, double *qvar, size_t n_path, int nb_steps, double dt, double theta,
-                          double kappa, double rho, double volvol, int scheme, uint64_t seed, uint32_t call_id,
-                          uint64_t path_offset, uint32_t step_offset, double forward, double *x_snapshot,
-                          double *qvar_snapshot, double *spot_sums, void *workspace, size_t workspace_bytes,
-                          svmc_stream_t stream)
-{
-    SVMC_REQUIRE(spot_sums != nullptr, "svmc_heston_slice_rng: null spot_sums");
-    return heston_slice_rng_impl("svmc_heston_slice_rng", StateInit(), x, var, qvar, n_path, nb_steps, dt, theta, kappa, rho,
-                                 volvol, scheme, seed, call_id, path_offset, step_offset, forward, x_snapshot, qvar_snapshot,
-                                 spot_sums, workspace, workspace_bytes, stream);
-}
-
-int svmc_heston_slice_rng_from(double x0, double var0, double qvar0, double *x, double *var, double *qvar, size_t n_path,
-                               int nb_steps, double dt, double theta, double kappa, double rho, double volvol, int scheme,
-                               uint64_t seed, uint32_t call_id, uint64_t path_offset, uint32_t step_offset, double forward,
-                               double *x_snapshot, double *qvar_snapshot, double *spot_sums, void *workspace,
-                               size_t workspace_bytes, svmc_stream_t stream)
-{
-    SVMC_REQUIRE(spot_sums != nullptr, "svmc_heston_slice_rng_from: null spot_sums");
-    const StateInit init = {1, x0, var0, qvar0};
-    return heston_slice_rng_impl("svmc_heston_slice_rng_from", init, x, var, qvar, n_path, nb_steps, dt, theta, kappa, rho,
-                                 volvol, scheme, seed, call_id, path_offset, step_offset, forward, x_snapshot, qvar_snapshot,
-                                 spot_sums, workspace, workspace_bytes, stream);
-}
-
-}  // extern "C"
-
-static int heston_chain_rng_impl(const char *fn, const StateInit &init, double *x, double *var, double *qvar, size_t n_path, int n_slices, const int *nb_steps_host,
-                          const double *dts_host, const double *forwards_host, double theta, double kappa, double rho,
-                          double volvol, int scheme, uint64_t seed, uint32_t call_id, uint64_t path_offset,
-                          uint32_t step_offset, double *x_snapshots, double *qvar_snapshots, double *spot_sums,
-                          void *workspace, size_t workspace_bytes, svmc_stream_t stream)
-{
-    SVMC_REQUIRE(scheme == SVMC_HESTON_EULER_FLOOR || scheme == SVMC_HESTON_QE, std::string(fn) + ": unknown scheme");
-    const auto fill = [&](HestonChainSlices &cs, int i, int j) {
-        cs.c[i] = make_heston_consts(dts_host[j], theta, kappa, rho, volvol);
-        cs.qc[i] = make_qe_consts(dts_host[j], theta, kappa, rho, volvol);
-        cs.forward[i] = forwards_host[j];
-    };
-    const auto launch = [&](const HestonChainSlices &cs, double *xs, double *qs, const StateInit &init_i, uint32_t step0) {
-        int ks = scheme;
-        if (scheme == SVMC_HESTON_QE) {                    // the specialised kernel only if EVERY slice of the launch allows it
-            ks = HESTON_QE_QUAD;
-            for (int i = 0; i < cs.m; ++i)
-                if (heston_kernel_scheme(scheme, cs.qc[i]) != HESTON_QE_QUAD) ks = scheme;
-        }
-        const HestonLatVariant *v = heston_variant(ks, n_path);
-        hipLaunchKernelGGL(v->chain, dim3(lat_grid(n_path, v->block)), dim3(v->block), 0, as_stream(stream), x, var, qvar, n_path, cs, seed,
-                           make_c3(call_id), path_offset, step0, xs, qs, static_cast<double *>(workspace), init_i);
-    };
-    return step_chain<HestonChainSlices>(fn, init, x, var, qvar, n_path, n_slices, nb_steps_host, dts_host, forwards_host, call_id,
-                                         step_offset, x_snapshots, qvar_snapshots, spot_sums, workspace, workspace_bytes,
-                                         as_stream(stream), fill, launch);
-}
-
-extern "C" {
-
-int svmc_heston_chain_rng(double *x, double *var, double *qvar, size_t n_path, int n_slices, const int *nb_steps_host,
-                          const double *dts_host, const double *forwards_host, double theta, double kappa, double rho,
-                          double volvol, int scheme, uint64_t seed, uint32_t call_id, uint64_t path_offset,
-                          uint32_t step_offset, double *x_snapshots, double *qvar_snapshots, double *spot_sums,
-                          void *workspace, size_t workspace_bytes, svmc_stream_t stream)
-{
-    SVMC_REQUIRE(spot_sums != nullptr, "svmc_heston_chain_rng: null spot_sums");
-    return heston_chain_rng_impl("svmc_heston_chain_rng", StateInit(), x, var, qvar, n_path, n_slices, nb_steps_host, dts_host,
-                                 forwards_host, theta, kappa, rho, volvol, scheme, seed, call_id, path_offset, step_offset,
-                                 x_snapshots, qvar_snapshots, spot_sums, workspace, workspace_bytes, stream);
-}
-
-int svmc_heston_chain_rng_from(double x0, double var0, double qvar0, double *x, double *var, double *qvar, size_t n_path,
-                               int n_slices, const int *nb_steps_host, const double *dts_host, const double *forwards_host,
-                               double theta, double kappa, double rho, double volvol, int scheme, uint64_t seed,
-                               uint32_t call_id, uint64_t path_offset, uint32_t step_offset, double *x_snapshots,
-                               double *qvar_snapshots, double *spot_sums, void *workspace, size_t workspace_bytes,
-                               svmc_stream_t stream)
-{
-    SVMC_REQUIRE(spot_sums != nullptr, "svmc_heston_chain_rng_from: null spot_sums");
-    const StateInit init = {1, x0, var0, qvar0};
-    return heston_chain_rng_impl("svmc_heston_chain_rng_from", init, x, var, qvar, n_path, n_slices, nb_steps_host, dts_host,
-                                 forwards_host, theta, kappa, rho, volvol, scheme, seed, call_id, path_offset, step_offset,
-                                 x_snapshots, qvar_snapshots, spot_sums, workspace, workspace_bytes, stream);
-}
-
-// launch of rough_logsv_expiries_kernel: n_expiries simulations from time 0 side by side (grid.y).  EVERY from-origin launch of
-// the rough model goes through this kernel -- the chain (svmc_rough_logsv_chain) and a single expiry (svmc_rough_logsv_slice /
-// _terminal with from_origin != 0: grid.y = 1) -- so that one launch per expiry and all expiries in one launch are the same
-// code on the same constants: identical bits by construction, not by how two kernels happen to be contracted.
-static void launch_rough_expiries(const RoughConsts &c_in, int n_factors, int n_expiries, const int *nb_steps_host,
-                                  const double *hs_host, const double *forwards_host, double *log_s, double *vol, double *qvar,
-                                  size_t n_path, const double *Z0, const double *Z1, size_t ldw, uint64_t seed, uint32_t call_id,
-                                  uint64_t path_offset, uint32_t step_offset, int from_origin, double *x_snapshots,
-                                  double *qvar_snapshots, double *partials, hipStream_t st)
-{
-    RoughConsts c = c_in;
-    RoughExpiries e{};
-    e.m = n_expiries;
-    for (int i = 0; i < MAX_CHAIN_SLICES; ++i) {
-        const int j = i < n_expiries ? i : 0;
-        const double h = hs_host[j];
-        e.h[i] = h;
-        e.inv_h[i] = 1.0 / h;
-        e.sqrt_h[i] = sqrt(h);
-        e.ito[i] = -0.5 * c.volvol_w * c.volvol_w * h;
-        e.volvol_w_sqrt_h[i] = c.volvol_w * e.sqrt_h[i];
-        e.forward[i] = forwards_host ? forwards_host[j] : 0.0;
-        e.nb_steps[i] = nb_steps_host[j];
-    }
-    const bool draw = Z0 == nullptr;                        // the drawing kernels run the generators' block size
-    const dim3 g(draw ? rng_grid(n_path) : grid_for(n_path), static_cast<unsigned>(n_expiries)), b(draw ? rng_block() : BLOCK);
-    const uint32_t c3 = make_c3(call_id) | 3u;              // stream tag 3: the rough model's normals
-#define SVMC_ROUGH_CHAIN_LAUNCH(NF)                                                                                          \
-    do {                                                                                                                     \
-        if (!draw)                                                                                                           \
-            hipLaunchKernelGGL((rough_logsv_expiries_kernel<NF, false>), g, b, 0, st, log_s, vol, qvar, n_path, c, e, Z0, Z1, \
-                               ldw, seed, c3, path_offset, step_offset, from_origin, x_snapshots, qvar_snapshots, partials); \
-        else                                                                                                                 \
-            hipLaunchKernelGGL((rough_logsv_expiries_kernel<NF, true>), g, b, 0, st, log_s, vol, qvar, n_path, c, e, Z0, Z1,  \
-                               ldw, seed, c3, path_offset, step_offset, from_origin, x_snapshots, qvar_snapshots, partials); \
-    } while (0)
-    if (n_factors == 1) SVMC_ROUGH_CHAIN_LAUNCH(1);
-    else if (n_factors == 2) SVMC_ROUGH_CHAIN_LAUNCH(2);
-    else SVMC_ROUGH_CHAIN_LAUNCH(3);
-#undef SVMC_ROUGH_CHAIN_LAUNCH
-}
-
-// the step-independent constants of the rough model
-static RoughConsts make_rough_consts(int n_factors, const double *nodes_host, const double *weights_host, const double *v0_host,
-                                     double theta, double kappa1, double kappa2, double rho, double volvol)
-{
-    RoughConsts c{};
-    c.wsum = 0.0;
-    c.w_lam_v0 = 0.0;
-    for (int i = 0; i < n_factors; ++i) {
-        c.nodes[i] = nodes_host[i];
-        c.w[i] = weights_host[i];
-        c.v0[i] = v0_host[i];
-        c.wlam[i] = weights_host[i] * nodes_host[i];
-        c.wsum += weights_host[i];
-        c.w_lam_v0 += c.wlam[i] * v0_host[i];
-    }
-    c.theta = theta; c.kappa1 = kappa1; c.kappa2 = kappa2; c.rho = rho; c.rho_comp = sqrt(1.0 - rho * rho);
-    c.volvol = volvol; c.inv_volvol = 1.0 / volvol; c.w_inv = 1.0 / c.wsum;
-    c.volvol_w = volvol * c.wsum;
-    return c;
-}
-
-static int rough_logsv_launch(const char *name, double *log_s, double *vol, double *qvar, size_t n_path, int nb_steps,
-                              double h, int n_factors, const double *nodes_host, const double *weights_host,
-                              const double *v0_host, double theta, double kappa1, double kappa2, double rho,
-                              double volvol, const double *Z0, const double *Z1, size_t ldw, uint64_t seed,
-                              uint32_t call_id, uint64_t path_offset, uint32_t step_offset, int from_origin,
-                              const SliceOut &so, svmc_stream_t stream)
-{
-    const std::string fn(name);
-    if (int rc = check_state(name, log_s, vol, qvar, nb_steps, h)) return rc;
-    SVMC_REQUIRE(n_factors >= 1 && n_factors <= 3, fn + ": 1 <= n_factors <= 3");
-    SVMC_REQUIRE(nodes_host && weights_host && v0_host, fn + ": null nodes/weights/v0");
-    SVMC_REQUIRE((Z0 == nullptr) == (Z1 == nullptr), fn + ": Z0 and Z1 go together");
-    SVMC_REQUIRE(Z0 == nullptr || ldw >= n_path, fn + ": ldw < n_path");
-    SVMC_REQUIRE(call_id < (1u << 24), fn + ": call_id must fit 24 bits");
-    SVMC_REQUIRE(volvol > 0.0 && rho * rho <= 1.0, fn + ": volvol > 0 and |rho| <= 1");
-    if (n_path == 0 || (nb_steps == 0 && !from_origin && so.partials == nullptr)) return SVMC_OK;
-    const RoughConsts c = make_rough_consts(n_factors, nodes_host, weights_host, v0_host, theta, kappa1, kappa2, rho, volvol);
-    launch_rough_expiries(c, n_factors, 1, &nb_steps, &h, &so.forward, log_s, vol, qvar, n_path, Z0, Z1, ldw, seed, call_id,
-                          path_offset, step_offset, from_origin, so.x_snap, so.q_snap, so.partials, as_stream(stream));
-    return check_launch(name);
-}
-
-int svmc_rough_logsv_terminal(double *log_s, double *vol, double *qvar, size_t n_path, int nb_steps, double h,
-                              int n_factors, const double *nodes_host, const double *weights_host,
-                              const double *v0_host, double theta, double kappa1, double kappa2, double rho,
-                              double volvol, const double *Z0, const double *Z1, size_t ldw, uint64_t seed,
-                              uint32_t call_id, uint64_t path_offset, uint32_t step_offset, int from_origin,
-                              svmc_stream_t stream)
-{
-    const SliceOut none = {nullptr, nullptr, nullptr, 0.0};
-    return rough_logsv_launch("svmc_rough_logsv_terminal", log_s, vol, qvar, n_path, nb_steps, h, n_factors, nodes_host,
-                              weights_host, v0_host, theta, kappa1, kappa2, rho, volvol, Z0, Z1, ldw, seed, call_id,
-                              path_offset, step_offset, from_origin, none, stream);
-}
-
-int svmc_rough_logsv_slice(double *log_s, double *vol, double *qvar, size_t n_path, int nb_steps, double h,
-                           int n_factors, const double *nodes_host, const double *weights_host, const double *v0_host,
-                           double theta, double kappa1, double kappa2, double rho, double volvol, const double *Z0,
-                           const double *Z1, size_t ldw, uint64_t seed, uint32_t call_id, uint64_t path_offset,
-                           uint32_t step_offset, int from_origin, double forward, double *x_snapshot,
-                           double *qvar_snapshot, double *spot_sums, void *workspace, size_t workspace_bytes,
-                           svmc_stream_t stream)
-{
-    const char *fn = "svmc_rough_logsv_slice";
-    if (int rc = check_slice_args(fn, n_path, x_snapshot, spot_sums, workspace, workspace_bytes)) return rc;
-    SVMC_REQUIRE(n_path > 0 && nb_steps > 0, "svmc_rough_logsv_slice: n_path and nb_steps must be positive");
-    const SliceOut so = {x_snapshot, qvar_snapshot, static_cast<double *>(workspace), forward, wave_rows(n_path)};
-    if (int rc = rough_logsv_launch(fn, log_s, vol, qvar, n_path, nb_steps, h, n_factors, nodes_host, weights_host,
-                                    v0_host, theta, kappa1, kappa2, rho, volvol, Z0, Z1, ldw, seed, call_id,
-                                    path_offset, step_offset, from_origin, so, stream))
-        return rc;
-    return reduce_spot_partials(workspace, n_path, 2, spot_sums, as_stream(stream));
-}
-
-int svmc_rough_logsv_chain(double *log_s, double *vol, double *qvar, size_t n_path, int n_expiries, const int *nb_steps_host,
-                           const double *hs_host, const double *forwards_host, int n_factors, const double *nodes_host,
-                           const double *weights_host, const double *v0_host, double theta, double kappa1, double kappa2,
-                           double rho, double volvol, const double *Z0, const double *Z1, size_t ldw, uint64_t seed,
-                           uint32_t call_id, uint64_t path_offset, double *x_snapshots, double *qvar_snapshots,
-                           double *spot_sums, void *workspace, size_t workspace_bytes, svmc_stream_t stream)
-{
-    const std::string fn("svmc_rough_logsv_chain");
-    SVMC_REQUIRE(log_s && vol && qvar && x_snapshots && spot_sums && workspace, fn + ": null state / snapshot / spot_sums / workspace");
-    SVMC_REQUIRE(nb_steps_host && hs_host && forwards_host, fn + ": null step counts / steps / forwards");
-    SVMC_REQUIRE(n_expiries >= 1 && n_expiries <= MAX_CHAIN_SLICES, fn + ": 1 <= n_expiries <= 16");
-    SVMC_REQUIRE(n_factors >= 1 && n_factors <= 3, fn + ": 1 <= n_factors <= 3");
-    SVMC_REQUIRE(nodes_host && weights_host && v0_host, fn + ": null nodes/weights/v0");
-    SVMC_REQUIRE((Z0 == nullptr) == (Z1 == nullptr), fn + ": Z0 and Z1 go together");
-    SVMC_REQUIRE(Z0 == nullptr || ldw >= n_path, fn + ": ldw < n_path");
-    SVMC_REQUIRE(call_id < (1u << 24), fn + ": call_id must fit 24 bits");
-    SVMC_REQUIRE(volvol > 0.0 && rho * rho <= 1.0, fn + ": volvol > 0 and |rho| <= 1");
-    SVMC_REQUIRE(n_path > 0, fn + ": n_path must be positive");
-    if (workspace_bytes < static_cast<size_t>(wave_rows(n_path)) * 2 * n_expiries * sizeof(double))
-        return fail(SVMC_ERR_WORKSPACE, fn + ": workspace too small (svmc_slice_workspace_bytes)");
-    for (int i = 0; i < n_expiries; ++i)
-        SVMC_REQUIRE(hs_host[i] > 0.0 && nb_steps_host[i] > 0, fn + ": steps and step counts must be positive");
-    const RoughConsts c = make_rough_consts(n_factors, nodes_host, weights_host, v0_host, theta, kappa1, kappa2, rho, volvol);
-    const hipStream_t st = as_stream(stream);
-    launch_rough_expiries(c, n_factors, n_expiries, nb_steps_host, hs_host, forwards_host, log_s, vol, qvar, n_path, Z0, Z1, ldw,
-                          seed, call_id, path_offset, 0u, 1, x_snapshots, qvar_snapshots, static_cast<double *>(workspace), st);
-    hipLaunchKernelGGL(reduce_columns_kernel, dim3(2 * n_expiries), dim3(BLOCK), 0, st, static_cast<const double *>(workspace),
-                       wave_rows(n_path), size_t(1), static_cast<size_t>(wave_rows(n_path)), spot_sums);
-    return check_launch("svmc_rough_logsv_chain");
-}
-
-int svmc_heston_terminal_w(double *x, double *var, double *qvar, size_t n_path, int nb_steps, double dt,
-                           double theta, double kappa, double rho, double volvol, const double *W0,
-                           const double *W1, size_t ldw, svmc_stream_t stream)
-{
-    if (int rc = check_state("svmc_heston_terminal_w", x, var, qvar, nb_steps, dt)) return rc;
-    SVMC_REQUIRE(W0 && W1, "svmc_heston_terminal_w: null W0/W1");
-    SVMC_REQUIRE(ldw >= n_path, "svmc_heston_terminal_w: ldw < n_path");
-    if (n_path == 0 || nb_steps == 0) return SVMC_OK;
-    const HestonConsts c = make_heston_consts(dt, theta, kappa, rho, volvol);
-    hipLaunchKernelGGL(heston_w_kernel, dim3(grid_for(n_path)), dim3(BLOCK), 0, as_stream(stream), x, var, qvar,
-                       n_path, nb_steps, c, W0, W1, ldw);
-    return check_launch("svmc_heston_terminal_w");
-}
-
-int svmc_heston_qe_terminal_w(double *x, double *var, double *qvar, size_t n_path, int nb_steps, double dt,
-                              double theta, double kappa, double rho, double volvol, const double *Z0,
-                              const double *Z1, const double *U, size_t ldw, svmc_stream_t stream)
-{
-    if (int rc = check_state("svmc_heston_qe_terminal_w", x, var, qvar, nb_steps, dt)) return rc;
-    SVMC_REQUIRE(Z0 && Z1 && U, "svmc_heston_qe_terminal_w: null Z0/Z1/U");
-    SVMC_REQUIRE(ldw >= n_path, "svmc_heston_qe_terminal_w: ldw < n_path");
-    if (n_path == 0 || nb_steps == 0) return SVMC_OK;
-    const QeConsts qc = make_qe_consts(dt, theta, kappa, rho, volvol);
-    hipLaunchKernelGGL(heston_qe_w_kernel, dim3(grid_for(n_path)), dim3(BLOCK), 0, as_stream(stream), x, var, qvar,
-                       n_path, nb_steps, qc, Z0, Z1, U, ldw);
-    return check_launch("svmc_heston_qe_terminal_w");
 }
 
 int svmc_clock_probe_arm(int enable)
@@ -2890,8 +1775,7 @@ int svmc_spot_sums(const double *x, size_t n_path, double forward, double *spot_
         return fail(SVMC_ERR_WORKSPACE, "svmc_spot_sums: workspace too small (svmc_payoff_workspace_bytes)");
     double *partials = static_cast<double *>(workspace);
     hipLaunchKernelGGL(spot_sums_kernel, dim3(g), dim3(BLOCK), 0, as_stream(stream), x, n_path, forward, partials);
-    hipLaunchKernelGGL(reduce_columns_kernel, dim3(2), dim3(BLOCK), 0, as_stream(stream), partials, g,
-                       size_t(2), size_t(1), spot_sums);
+    reduce_columns(2, as_stream(stream), partials, g, size_t(2), size_t(1), spot_sums);
     return check_launch("svmc_spot_sums");
 }
 
@@ -2997,8 +1881,8 @@ static int payoff_sums_impl(const char *fn, const double *const *xs, const doubl
             partials_out->rows = gx;
             partials_out->cols = cols;
         } else {
-            hipLaunchKernelGGL(reduce_columns_kernel, dim3(3 * cols * n_sets), dim3(BLOCK), 0, as_stream(stream), partials,
-                               static_cast<unsigned>(gx), static_cast<size_t>(3 * cols) * n_sets, size_t(1), sums + 3 * first_strike);
+            reduce_columns(3 * cols * n_sets, as_stream(stream), partials, static_cast<unsigned>(gx),
+                           static_cast<size_t>(3 * cols) * n_sets, size_t(1), sums + 3 * first_strike);
         }
         first_strike += static_cast<size_t>(cols);
         n_groups = cols = kt = 0;
@@ -3587,22 +2471,6 @@ int logsv_step_partials(double sigma0, double *x, double *sigma, double *qvar, s
                                 x_snapshots, qvar_snapshots, spot_sums, workspace, workspace_bytes, st);
 }
 
-int heston_step_partials(double var0, double *x, double *var, double *qvar, size_t n_path, int n_slices, const int *nb_steps_host,
-                         const double *dts_host, const double *forwards_host, double theta, double kappa, double rho, double volvol,
-                         int scheme, uint64_t seed, uint32_t call_id, uint64_t path_offset, double *x_snapshots,
-                         double *qvar_snapshots, double *spot_sums, void *workspace, size_t workspace_bytes, hipStream_t stream)
-{
-    const StateInit init = {1, 0.0, var0, 0.0};
-    const svmc_stream_t st = reinterpret_cast<svmc_stream_t>(stream);
-    if (n_slices == 1)
-        return heston_slice_rng_impl("heston_step_partials", init, x, var, qvar, n_path, nb_steps_host[0], dts_host[0], theta, kappa, rho,
-                                     volvol, scheme, seed, call_id, path_offset, 0, forwards_host[0], x_snapshots, qvar_snapshots,
-                                     spot_sums, workspace, workspace_bytes, st);
-    return heston_chain_rng_impl("heston_step_partials", init, x, var, qvar, n_path, n_slices, nb_steps_host, dts_host, forwards_host,
-                                 theta, kappa, rho, volvol, scheme, seed, call_id, path_offset, 0, x_snapshots, qvar_snapshots, spot_sums,
-                                 workspace, workspace_bytes, st);
-}
-
 // the largest launch whose payoff blocks form their spot sums themselves: 2048 rows = 131072 paths, ONE batched round trip of
 // loads per block (block_column_sum2); above, the reduce launch is cheaper than what every block would repeat (see above)
 bool spot_sums_in_payoff_kernel(size_t n_path) { return wave_rows(n_path) <= 8u * BLOCK; }
@@ -3620,45 +2488,16 @@ int reduce_spot_partials(const void *workspace, size_t n_path, int n_cols, doubl
 
 // ---- many jobs of one chain (svmc_chain.hip's svmc_*_chain_price_many)
 
-// the job table of n_jobs jobs of n_slices expiries: [J][m] constants, [J] start vols, [J] seeds, [J] counter words -- or the
-// Hawkes table of svmc_hawkes.hip, whichever is larger (one pinned and one device buffer serve every model)
-static size_t many_consts_bytes()
-{
-    return sizeof(HestonManyConsts) > sizeof(LogsvFast) ? sizeof(HestonManyConsts) : sizeof(LogsvFast);
-}
+// the job table of n_jobs jobs of n_slices expiries, whichever family's is the largest (one pinned and one device buffer serve
+// every model)
+size_t logsv_many_table_bytes(int n_jobs, int n_slices) { return many_table_bytes_of<LogsvFast>(n_jobs, n_slices); }
 size_t many_table_bytes(int n_jobs, int n_slices)
 {
-    const size_t J = static_cast<size_t>(n_jobs);
-    const size_t here = J * static_cast<size_t>(n_slices) * many_consts_bytes() + J * (sizeof(double) + sizeof(uint64_t) + sizeof(uint32_t));
-    const size_t hawkes = hawkes_many_table_bytes(n_jobs, n_slices);
-    return here > hawkes ? here : hawkes;
+    return std::max({logsv_many_table_bytes(n_jobs, n_slices), heston_many_table_bytes(n_jobs, n_slices),
+                     hawkes_many_table_bytes(n_jobs, n_slices)});
 }
 
-// fills the pinned table_host (the table's byte layout, constants of CONSTS each), queues its upload and returns the device view
-template <class Consts, class Fill>
-static ManyJobs many_table(int n_jobs, int n_slices, const uint64_t *seeds, const uint32_t *call_ids, void *table_host, void *table_dev,
-                           hipStream_t stream, Fill &&fill, hipError_t &err)
-{
-    const size_t J = static_cast<size_t>(n_jobs), nc = J * static_cast<size_t>(n_slices);
-    unsigned char *h = static_cast<unsigned char *>(table_host);
-    Consts *consts = reinterpret_cast<Consts *>(h);
-    double *vol0 = reinterpret_cast<double *>(h + nc * sizeof(Consts));
-    uint64_t *seed = reinterpret_cast<uint64_t *>(vol0 + J);
-    uint32_t *c3 = reinterpret_cast<uint32_t *>(seed + J);
-    for (int j = 0; j < n_jobs; ++j) {
-        vol0[j] = fill(j, consts + static_cast<size_t>(j) * n_slices);
-        seed[j] = seeds[j];
-        c3[j] = make_c3(call_ids[j]);
-    }
-    const size_t bytes = reinterpret_cast<unsigned char *>(c3 + J) - h;
-    err = hipMemcpyAsync(table_dev, table_host, bytes, hipMemcpyHostToDevice, stream);
-    const unsigned char *d = static_cast<const unsigned char *>(table_dev);
-    const size_t o_vol = nc * sizeof(Consts), o_seed = o_vol + J * sizeof(double), o_c3 = o_seed + J * sizeof(uint64_t);
-    return ManyJobs{d, reinterpret_cast<const double *>(d + o_vol), reinterpret_cast<const uint64_t *>(d + o_seed),
-                    reinterpret_cast<const uint32_t *>(d + o_c3)};
-}
-
-static ManySlices many_slices(int n_slices, const int *nb_steps_host, const double *forwards_host)
+ManySlices many_slices(int n_slices, const int *nb_steps_host, const double *forwards_host)
 {
     ManySlices cs;
     cs.m = n_slices;
@@ -3670,8 +2509,8 @@ static ManySlices many_slices(int n_slices, const int *nb_steps_host, const doub
     return cs;
 }
 
-static int check_many(const char *fn, size_t n_path, int n_jobs, int n_slices, const int *nb_steps_host, const double *dts_host,
-                      const uint32_t *call_ids)
+int check_many(const char *fn, size_t n_path, int n_jobs, int n_slices, const int *nb_steps_host, const double *dts_host,
+               const uint32_t *call_ids)
 {
     SVMC_REQUIRE(n_path > 0 && n_jobs >= 1 && n_jobs <= MAX_MANY_JOBS && n_slices >= 1 && n_slices <= MAX_CHAIN_SLICES,
                  std::string(fn) + ": bad sizes");
@@ -3711,47 +2550,6 @@ int logsv_chain_rng_many(size_t n_path, int n_jobs, int n_slices, const int *nb_
     return check_launch(fn);
 }
 
-using HestonManyKernel = void (*)(size_t, ManySlices, ManyJobs, uint64_t, double *, double *, double *);
-#define SVMC_HESTON_MANY_LAT(S, WAVES) heston_chain_rng_many_lat_kernel<S, GEN_LOOP_PAIR, WAVES, FEW_BLOCK>
-static const HestonManyKernel HESTON_MANY_FEW_WAVES_KERNELS[3] = {
-    SVMC_HESTON_MANY_LAT(SVMC_HESTON_EULER_FLOOR, 4), SVMC_HESTON_MANY_LAT(SVMC_HESTON_QE, 3), SVMC_HESTON_MANY_LAT(HESTON_QE_QUAD, 4)};
-#undef SVMC_HESTON_MANY_LAT
-static const HestonManyKernel HESTON_MANY_FULL_KERNELS[3] = {
-    heston_chain_rng_many_kernel<SVMC_HESTON_EULER_FLOOR>, heston_chain_rng_many_kernel<SVMC_HESTON_QE>,
-    heston_chain_rng_many_kernel<HESTON_QE_QUAD>};
-
-int heston_chain_rng_many(size_t n_path, int n_jobs, int n_slices, const int *nb_steps_host, const double *dts_host,
-                          const double *forwards_host, const double *params_host, int scheme, const uint64_t *seeds,
-                          const uint32_t *call_ids, uint64_t path_offset, void *table_host, void *table_dev, double *x_snapshots,
-                          double *qvar_snapshots, double *spot_partials, hipStream_t stream)
-{
-    const char *fn = "heston_chain_rng_many";
-    if (int rc = check_many(fn, n_path, n_jobs, n_slices, nb_steps_host, dts_host, call_ids)) return rc;
-    SVMC_REQUIRE(scheme == SVMC_HESTON_EULER_FLOOR || scheme == SVMC_HESTON_QE, std::string(fn) + ": unknown scheme");
-    // the QE specialisation only if EVERY (job, expiry) of the launch allows it (as heston_chain_rng_impl per launch)
-    bool quad = scheme == SVMC_HESTON_QE;
-    hipError_t e = hipSuccess;
-    const ManyJobs jobs = many_table<HestonManyConsts>(n_jobs, n_slices, seeds, call_ids, table_host, table_dev, stream,
-                                                       [&](int j, HestonManyConsts *c) {
-        const double *p = params_host + 5 * static_cast<size_t>(j);    // v0 theta kappa rho volvol
-        for (int i = 0; i < n_slices; ++i) {
-            c[i].c = make_heston_consts(dts_host[i], p[1], p[2], p[3], p[4]);
-            c[i].qc = make_qe_consts(dts_host[i], p[1], p[2], p[3], p[4]);
-            quad = quad && heston_kernel_scheme(scheme, c[i].qc) == HESTON_QE_QUAD;
-        }
-        return p[0];
-    }, e);
-    SVMC_HIP_TRY(e);
-    const ManySlices cs = many_slices(n_slices, nb_steps_host, forwards_host);
-    const int ks = quad ? HESTON_QE_QUAD : scheme;
-    const bool few = few_waves_launch(static_cast<size_t>(n_jobs) * n_path);
-    const HestonManyKernel k = few ? HESTON_MANY_FEW_WAVES_KERNELS[ks] : HESTON_MANY_FULL_KERNELS[ks];
-    const unsigned block = few ? FEW_BLOCK : RNG_BLOCK;
-    hipLaunchKernelGGL(k, dim3(lat_grid(n_path, block), static_cast<unsigned>(n_jobs)), dim3(block), 0, stream, n_path, cs, jobs,
-                       path_offset, x_snapshots, qvar_snapshots, spot_partials);
-    return check_launch(fn);
-}
-
 // an upper bound of the payoff workspace chain_payoff_and_finish_sets needs for n_sets sets of total_strikes quotes
 size_t payoff_sets_workspace_bytes(size_t n_path, size_t total_strikes, int n_sets)
 {
@@ -3783,8 +2581,8 @@ int chain_payoff_and_finish_sets(const double *const *x_snapshots_host, const do
         hipLaunchKernelGGL(chain_finish_kernel, dim3(static_cast<unsigned>((cols + BLOCK / 64 - 1) / (BLOCK / 64))), dim3(BLOCK), 0,
                            stream, static_cast<const double *>(workspace), po.rows, static_cast<int>(cols), sums_out);
     } else {
-        hipLaunchKernelGGL(reduce_columns_kernel, dim3(static_cast<unsigned>(3 * cols)), dim3(BLOCK), 0, stream,
-                           static_cast<const double *>(workspace), po.rows, 3 * cols, size_t(1), sums_dev);
+        reduce_columns(static_cast<unsigned>(3 * cols), stream, static_cast<const double *>(workspace), po.rows, 3 * cols, size_t(1),
+                       sums_dev);
         SVMC_HIP_TRY(hipMemcpyAsync(sums_out, sums_dev, 3 * cols * sizeof(double), hipMemcpyDeviceToHost, stream));
     }
     return check_launch(fn);

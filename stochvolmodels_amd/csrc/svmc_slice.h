@@ -1,5 +1,5 @@
-// svmc_slice.h -- the slice epilogue every on-device-RNG generator shares (svmc_kernels.hip, svmc_hawkes.hip): the terminal
-// snapshot and the per-wave spot partials the chain payoff tail (payoff_group_kernel / chain_finish_kernel) reads.
+// svmc_slice.h -- the slice epilogue every on-device-RNG generator shares (svmc_kernels.hip, svmc_heston.hip, svmc_rough.hip,
+// svmc_hawkes.hip): the terminal snapshot and the per-wave spot partials the chain payoff tail (payoff_group_kernel / chain_finish_kernel) reads.
 #pragma once
 #include <hip/hip_runtime.h>
 
