@@ -872,6 +872,76 @@ SVMC_API int svmc_il_payoff_workspace_bytes(size_t n_path, size_t n_cases, size_
 SVMC_API int svmc_il_payoff(const double *x, size_t n_path, const double *cases_host, size_t n_cases, double *out_host,
                             void *workspace, size_t workspace_bytes, svmc_stream_t stream);
 
+/* ---- conditional Monte Carlo chain pricers, LogSV and Heston Euler (src svmc_cmc.hip, svmc_chain.hip) ----
+ * Given the path of the volatility's driver b the log-return of the DISCRETISED schemes is exactly Gaussian.  LogSV
+ * (pricers/logsv_pricer.py:1037-1045): the volatility moves on beta w0 + volvol w1 = vartheta b, the return on
+ * w0 = rho b + sqrt(1 - rho^2) b_perp, rho = beta / vartheta, vartheta^2 = beta^2 + volvol^2 (vartheta = 0: rho = 0).  Heston Euler
+ * (pricers/heston_pricer.py:372-379): the variance moves on b = rho w0 + rho_1 w1, the return on w0 = rho b + rho_1 b_perp.  So
+ *   x_T | {b_t} ~ N(mu, cv),  mu = sum_t (alpha/2 eta^2 sigma_t^2 dt + rho eta sigma_t sqrt(dt) b_t),  cv = (1 - rho^2) sum_t eta^2 sigma_t^2 dt
+ * over the values the steps START from (Heston: eta = 1, sigma_t^2 = v_t, alpha = -1), and integrating b_perp out leaves a Black-76
+ * price per path: the estimator has the plain pricer's expectation for the same discretised model and a smaller variance.
+ *
+ * STEPPING.  svmc_logsv_chain_cmc / svmc_heston_chain_cmc advance the state (mu, cv, sigma | var, qvar), device [n_path] each, through
+ * n_slices slices (any number: launches of 16) and write expiry i's mu and cv -- and qvar where qvar_snapshots is not null -- to row
+ * i of mu_snapshots / cv_snapshots / qvar_snapshots ([n_slices][n_path]).  Arguments as svmc_logsv_chain_rng / svmc_heston_chain_rng
+ * (Euler scheme) without the forwards, spot sums and workspace: the forward's statistics are svmc_cmc_payoff_chain's.  Randoms:
+ * stream 8 of (seed, call_id), ONE normal per step, word step & 3 of call step >> 2 (chain-global step = step_offset + local
+ * step); a chain sliced or continued differently sees the same bits.  Consecutive slices of one launch whose step constants (dt,
+ * eta) are bit-equal are joined: the sums run on across the boundary and an expiry's values are the fold of the sums since the last
+ * boundary that was not joined, so equal steps give the same values however they are cut into slices; ln sigma is derived once per
+ * launch.  LogSV forms cv with the factor volvol^2 / vartheta^2 (1 when
+ * vartheta = 0), Heston with 1 - rho^2.
+ *
+ * PAYOFF.  svmc_cmc_payoff_chain on any device arrays mu_snapshots_host[i], cv_snapshots_host[i] ([n_path], host arrays of device
+ * pointers), strikes / types (SVMC_CALL | SVMC_PUT only: SVMC_ERR_UNKNOWN_PAYOFF otherwise) / strike_offsets as
+ * svmc_payoff_sums_chain:
+ *   KEEP RULE: a path is kept iff mu, cv and e = exp(mu + cv / 2) are finite and cv >= 0; a dropped path adds nothing and is counted;
+ *   F_c = F e;  RECENTRING: corr = mean_kept(F_c) - F with recenter != 0 -- what the reference's nanmean(F exp(x)) - F becomes when
+ *   b_perp is integrated out; it makes C - P = discfactor (F - K) hold per strike as the reference's does -- and corr = 0 otherwise;
+ *   per (path, strike) the undiscounted Black-76 price of F_c against K' = K + corr at total variance cv, the call's formula for a
+ *   call and the put's for a put, with ln F_c = ln F + mu + cv / 2 and ln K' formed once per strike;
+ *   DEGENERATE: cv == 0 gives the intrinsic value of F_c against K'; K' <= 0 gives F_c - K' for a call and 0 for a put;
+ *   price = discfactor x mean over the kept paths; error = discfactor x population deviation / sqrt(n_path), as
+ *   compute_mc_vars_payoff divides.  The sums are taken of (price_j - shift), shift = the price of the expiry's path 0 (paths that
+ *   agree to the bit then have error exactly 0), or the intrinsic value at F where that path is dropped.
+ * prices_host, stderrs_host: [K] host; stats_host (nullable): [n_expiries][SVMC_CMC_STATS_DOUBLES] = {mean F_c, its standard error
+ * (F x population deviation of e / sqrt(n_path)), corr, n_kept, n_dropped}.  One upload of the chain's table, four launches on
+ * `stream` with no host round trip between them, the downloads, one synchronize.  Every sum has a fixed order that depends on
+ * n_path alone (the path blocks of a launch are min(ceil(n_path / 256), 1024)): a strike's results are the same bits whichever other
+ * strikes share the call.  `workspace`: device memory of svmc_cmc_payoff_workspace_bytes(n_path, n_expiries, total_strikes).
+ *
+ * FUSED.  svmc_logsv_chain_price_cmc / svmc_heston_chain_price_cmc: stepping from (0, 0, v0, 0) on the session's own state (its x
+ * holds mu, its volatility array sigma | var afterwards) and the payoff in one call, arguments as svmc_logsv_chain_price /
+ * svmc_heston_chain_price; stats_host as above, nullable.  LOG_RETURN only; a session that is part of a sharded job is refused
+ * (SVMC_ERR_INVALID_ARGUMENT): cross-rank sums of the conditional estimator are a separate step. */
+#define SVMC_CMC_STATS_DOUBLES 5
+SVMC_API int svmc_logsv_chain_cmc(double *mu, double *cv, double *sigma, double *qvar, size_t n_path, int n_slices,
+                                  const int *nb_steps_host, const double *dts_host, const double *etas_host, double theta,
+                                  double kappa1, double kappa2, double beta, double volvol, int is_spot_measure, uint64_t seed,
+                                  uint32_t call_id, uint64_t path_offset, uint32_t step_offset, double *mu_snapshots,
+                                  double *cv_snapshots, double *qvar_snapshots, svmc_stream_t stream);
+SVMC_API int svmc_heston_chain_cmc(double *mu, double *cv, double *var, double *qvar, size_t n_path, int n_slices,
+                                   const int *nb_steps_host, const double *dts_host, double theta, double kappa, double rho,
+                                   double volvol, uint64_t seed, uint32_t call_id, uint64_t path_offset, uint32_t step_offset,
+                                   double *mu_snapshots, double *cv_snapshots, double *qvar_snapshots, svmc_stream_t stream);
+SVMC_API int svmc_cmc_payoff_workspace_bytes(size_t n_path, int n_expiries, size_t total_strikes, size_t *bytes);
+SVMC_API int svmc_cmc_payoff_chain(const double *const *mu_snapshots_host, const double *const *cv_snapshots_host, size_t n_path,
+                                   const double *forwards_host, const double *discfactors_host, int n_expiries,
+                                   const double *strikes_host, const int8_t *types_host, const size_t *strike_offsets_host,
+                                   int recenter, double *prices_host, double *stderrs_host, double *stats_host, void *workspace,
+                                   size_t workspace_bytes, svmc_stream_t stream);
+SVMC_API int svmc_logsv_chain_price_cmc(svmc_session_t session, const double *ttms_host, const double *forwards_host,
+                                        const double *discfactors_host, const double *vol_backbone_etas_host, int n_expiries,
+                                        const double *strikes_host, const int8_t *types_host, const size_t *strike_offsets_host,
+                                        double v0, double theta, double kappa1, double kappa2, double beta, double volvol,
+                                        int is_spot_measure, int nb_steps_per_year, int recenter, uint64_t seed, uint32_t call_id,
+                                        double *prices_host, double *stderrs_host, double *stats_host);
+SVMC_API int svmc_heston_chain_price_cmc(svmc_session_t session, const double *ttms_host, const double *forwards_host,
+                                         const double *discfactors_host, int n_expiries, const double *strikes_host,
+                                         const int8_t *types_host, const size_t *strike_offsets_host, double v0, double theta,
+                                         double kappa, double rho, double volvol, int nb_steps_per_year, int recenter, uint64_t seed,
+                                         uint32_t call_id, double *prices_host, double *stderrs_host, double *stats_host);
+
 #ifdef __cplusplus
 }
 #endif

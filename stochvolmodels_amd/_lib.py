@@ -172,6 +172,17 @@ def _declare(L: C.CDLL) -> None:
         "svmc_kde_gaussian_weighted": ([vp, vp, vp, f64, sz, f64, f64, vp, i32, f64, vp, vp, vp, sz, vp], i32),
         "svmc_tilted_payoff_chain": ([C.POINTER(vp), sz, pf64, i32, pf64, pi8, pf64, psz, pf64, i32, i32, vp, vp, vp, vp, vp, sz, vp],
                                      i32),
+        "svmc_logsv_chain_cmc": ([vp, vp, vp, vp, sz, i32, C.POINTER(i32), pf64, pf64, f64, f64, f64, f64, f64, i32, u64, u32, u64, u32,
+                                  vp, vp, vp, vp], i32),
+        "svmc_heston_chain_cmc": ([vp, vp, vp, vp, sz, i32, C.POINTER(i32), pf64, f64, f64, f64, f64, u64, u32, u64, u32, vp, vp, vp,
+                                   vp], i32),
+        "svmc_cmc_payoff_workspace_bytes": ([sz, i32, sz, psz], i32),
+        "svmc_cmc_payoff_chain": ([C.POINTER(vp), C.POINTER(vp), sz, pf64, pf64, i32, pf64, pi8, psz, i32, pf64, pf64, pf64, vp, sz,
+                                   vp], i32),
+        "svmc_logsv_chain_price_cmc": ([vp, pf64, pf64, pf64, pf64, i32, pf64, pi8, psz, f64, f64, f64, f64, f64, f64, i32, i32, i32,
+                                        u64, u32, pf64, pf64, pf64], i32),
+        "svmc_heston_chain_price_cmc": ([vp, pf64, pf64, pf64, i32, pf64, pi8, psz, f64, f64, f64, f64, f64, i32, i32, u64, u32, pf64,
+                                         pf64, pf64], i32),
         "svmc_hawkesjd_chain_price_tilted": ([vp, pf64, pf64, i32, pf64, pi8, psz, pf64, i32, u64, u32, pf64, i32, i32, pf64, pf64,
                                               pf64], i32),
     }

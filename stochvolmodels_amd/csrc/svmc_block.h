@@ -65,6 +65,28 @@ __device__ __forceinline__ void clock_probe_stamp(uint64_t *probe, int at_exit)
     }
 }
 
+// Least-progress-first wave priority (the LogSV stepping loops of svmc_kernels.hip and svmc_cmc.hip).  The SIMD arbiter picks by
+// priority, then age; with equal priorities the
+// oldest wave always wins, younger waves starve and each launch ends in a long ramp-down where lone, late waves run
+// at ~60 % of the saturated rate (tools/ubench/tail_probe.hip).  Dropping a wave's own priority as it progresses
+// through the time loop (3 -> 0 at the quarter points) lets waves that are behind catch up: residency stays at 8
+// waves per SIMD and the ramp-down shrinks from ~30 % to ~10 % of the launch.
+__device__ __forceinline__ void progress_priority(int stage)
+{
+    switch (stage) {
+    case 0: __builtin_amdgcn_s_setprio(3); break;
+    case 1: __builtin_amdgcn_s_setprio(2); break;
+    case 2: __builtin_amdgcn_s_setprio(1); break;
+    default: __builtin_amdgcn_s_setprio(0); break;
+    }
+}
+
+// where a launch stands on that ladder: wave-uniform counters, carried from slice to slice of a chain
+struct LogsvProgress {
+    int quarter;                       // a quarter of the launch's steps, rounded up
+    int stage = 0, next_stage_t = 0;
+};
+
 // ---------------------------------------------------------------------------------------------------
 // Deterministic block reductions: wave shuffles in a fixed tree, one LDS exchange, ONE barrier for any number of
 // values (the first version paid two barriers per value: 96 per payoff block).

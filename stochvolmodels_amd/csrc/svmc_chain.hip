@@ -84,6 +84,10 @@ struct Session {
     // svmc_hawkesjd_chain_price_tilted: the page-locked landing buffer of its prices, errors and statistics, grown on demand
     double *tilted_pinned = nullptr;
     size_t tilted_pinned_bytes = 0;
+    // svmc_*_chain_price_cmc: the fourth state array (cv) and the payoff tail's workspace, grown on demand
+    double *cmc_cv = nullptr;
+    void *cmc_ws = nullptr, *cmc_pinned = nullptr;          // device, device, pinned (the chain table's image and the results)
+    size_t cmc_cv_bytes = 0, cmc_ws_bytes = 0, cmc_pinned_bytes = 0;
 };
 
 // events around a stepping call of a timed session (no-ops otherwise)
@@ -132,6 +136,9 @@ static void session_release(Session *s)
         if (p != nullptr) (void)hipFree(p);
     if (s->sums_pinned != nullptr) (void)hipHostFree(s->sums_pinned);
     if (s->tilted_pinned != nullptr) (void)hipHostFree(s->tilted_pinned);
+    if (s->cmc_cv != nullptr) (void)hipFree(s->cmc_cv);
+    if (s->cmc_ws != nullptr) (void)hipFree(s->cmc_ws);
+    if (s->cmc_pinned != nullptr) (void)hipHostFree(s->cmc_pinned);
     ManyBuffers &mb = s->many;
     for (void *p : {static_cast<void *>(mb.snap), static_cast<void *>(mb.spot_ws), static_cast<void *>(mb.spot),
                     static_cast<void *>(mb.sums), mb.ws, mb.table_dev})
@@ -548,6 +555,45 @@ static int tilted_block(Session *s, const ChainView &c, int n_gammas, int n_jobs
                       static_cast<size_t>(n_jobs) * (2 * b.GK + b.n_stats) * sizeof(double), true));
     b.base = s->tilted_pinned;
     return SVMC_OK;
+}
+
+// ---- conditional Monte Carlo (include/svmc.h; kernels and the payoff tail: svmc_cmc.hip).  The chain's checks and step grids are
+// single_step's; mu rides in the session's x, cv in an array of its own, expiry i's snapshots in rows i and m + i of s->snap.
+template <class Step>
+static int chain_price_cmc(const char *fn, Session *s, const ChainView &c, int nb_steps_per_year, int recenter, double *prices_host,
+                           double *stderrs_host, double *stats_host, Step &&step)
+{
+    double *mu_snap = nullptr, *cv_snap = nullptr;
+    const Stepped st = single_step(fn, s, c, nb_steps_per_year, SVMC_LOG_RETURN, prices_host, stderrs_host, true, false,
+                                   [&](const int *nbs, const double *dts, double *, double *, void *, size_t) {
+                                       return step(nbs, dts, mu_snap, cv_snap);
+                                   },
+                                   [&]() {
+                                       SVMC_REQUIRE(!s->sharded(), std::string(fn) + ": the conditional estimator is not sharded");
+                                       for (size_t k = 0; k < c.offsets[c.m]; ++k)
+                                           if (c.types[k] != SVMC_CALL && c.types[k] != SVMC_PUT)
+                                               return fail(SVMC_ERR_UNKNOWN_PAYOFF, "unknown option payoff code");
+                                       return SVMC_OK;
+                                   },
+                                   [&]() {
+                                       SVMC_HIP_TRY(grow(reinterpret_cast<void **>(&s->cmc_cv), s->cmc_cv_bytes, s->n_path * sizeof(double), false));
+                                       SVMC_HIP_TRY(grow(&s->cmc_ws, s->cmc_ws_bytes, cmc_payoff_workspace_bytes_of(s->n_path, c.m, c.offsets[c.m]), false));
+                                       SVMC_HIP_TRY(grow(&s->cmc_pinned, s->cmc_pinned_bytes, cmc_payoff_pinned_bytes_of(c.m, c.offsets[c.m]), true));
+                                       mu_snap = s->snap;
+                                       cv_snap = s->snap + static_cast<size_t>(c.m) * s->n_path;
+                                       return SVMC_OK;
+                                   });
+    if (st.rc) return st.rc;
+    std::vector<const double *> mus(c.m), cvs(c.m);
+    for (int i = 0; i < c.m; ++i) {
+        mus[i] = mu_snap + static_cast<size_t>(i) * s->n_path;
+        cvs[i] = cv_snap + static_cast<size_t>(i) * s->n_path;
+    }
+    const int rc = cmc_payoff_chain(fn, mus.data(), cvs.data(), s->n_path, c.forwards, c.discfactors, c.m, c.strikes, c.types, c.offsets,
+                                    recenter, prices_host, stderrs_host, stats_host, s->cmc_ws, s->cmc_ws_bytes, s->stream, s->cmc_pinned,
+                                    s->cmc_pinned_bytes);
+    if (rc == SVMC_OK) stepping_read(s);
+    return rc;
 }
 
 }  // namespace svmc
@@ -970,6 +1016,37 @@ int svmc_heston_chain_price(svmc_session_t session, const double *ttms_host, con
                                     call_id, s->path_offset, s->snap, qsnap, spot, ws, ws_bytes, s->stream);
     });
     return st.rc ? st.rc : reduce_and_finalize(s, c, variable_type, prices_host, stderrs_host, st.pending);
+}
+
+int svmc_logsv_chain_price_cmc(svmc_session_t session, const double *ttms_host, const double *forwards_host,
+                               const double *discfactors_host, const double *vol_backbone_etas_host, int n_expiries,
+                               const double *strikes_host, const int8_t *types_host, const size_t *strike_offsets_host, double v0,
+                               double theta, double kappa1, double kappa2, double beta, double volvol, int is_spot_measure,
+                               int nb_steps_per_year, int recenter, uint64_t seed, uint32_t call_id, double *prices_host,
+                               double *stderrs_host, double *stats_host)
+{
+    Session *s = reinterpret_cast<Session *>(session);
+    const ChainView c = {n_expiries, ttms_host, forwards_host, discfactors_host, strikes_host, types_host, strike_offsets_host};
+    return chain_price_cmc("svmc_logsv_chain_price_cmc", s, c, nb_steps_per_year, recenter, prices_host, stderrs_host, stats_host,
+                           [&](const int *nbs, const double *dts, double *mu_snap, double *cv_snap) {
+        return logsv_cmc_step_from(v0, s->x, s->cmc_cv, s->vol, s->qvar, s->n_path, c.m, nbs, dts, vol_backbone_etas_host, theta, kappa1,
+                                   kappa2, beta, volvol, is_spot_measure, seed, call_id, s->path_offset, mu_snap, cv_snap, s->stream);
+    });
+}
+
+int svmc_heston_chain_price_cmc(svmc_session_t session, const double *ttms_host, const double *forwards_host,
+                                const double *discfactors_host, int n_expiries, const double *strikes_host, const int8_t *types_host,
+                                const size_t *strike_offsets_host, double v0, double theta, double kappa, double rho, double volvol,
+                                int nb_steps_per_year, int recenter, uint64_t seed, uint32_t call_id, double *prices_host,
+                                double *stderrs_host, double *stats_host)
+{
+    Session *s = reinterpret_cast<Session *>(session);
+    const ChainView c = {n_expiries, ttms_host, forwards_host, discfactors_host, strikes_host, types_host, strike_offsets_host};
+    return chain_price_cmc("svmc_heston_chain_price_cmc", s, c, nb_steps_per_year, recenter, prices_host, stderrs_host, stats_host,
+                           [&](const int *nbs, const double *dts, double *mu_snap, double *cv_snap) {
+        return heston_cmc_step_from(v0, s->x, s->cmc_cv, s->vol, s->qvar, s->n_path, c.m, nbs, dts, theta, kappa, rho, volvol, seed,
+                                    call_id, s->path_offset, mu_snap, cv_snap, s->stream);
+    });
 }
 
 int svmc_hawkesjd_chain_price(svmc_session_t session, const double *ttms_host, const double *forwards_host,

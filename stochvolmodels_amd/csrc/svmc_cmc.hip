@@ -1,0 +1,813 @@
+// svmc_cmc.hip -- conditional Monte Carlo chain pricers for LogSV and Heston Euler (include/svmc.h states the
+// estimator, the recentring, the keep rule and the degenerate cases).
+//
+// Given the path of the volatility's driver b the log-return of both discretised schemes is Gaussian, x_T | {b_t} ~ N(mu, cv):
+// the stepping kernels here draw ONE normal per step (stream 8, four steps per Philox call), advance the volatility on it and
+// carry (mu, cv, sigma | v, qvar) per path; the payoff kernels integrate the orthogonal Brownian motion out in closed form, a
+// Black-76 price per (path, strike) of F_c = F exp(mu + cv / 2) at total variance cv.
+//
+//   logsv_chain_cmc_kernel / _lat_kernel     all expiries of a chain in one stepping launch (full-launch / few-waves form)
+//   heston_chain_cmc_kernel / _lat_kernel    the same for the reference's Heston Euler step
+//   cmc_forward_kernel, cmc_forward_finish_kernel   per expiry the sums of exp(mu + cv/2) - 1, its square and the kept count;
+//                                                   then, in row order, the forward statistics and the per-strike constants
+//   cmc_payoff_kernel                        a block column per group of up to CMC_KT strikes of one expiry
+//   cmc_finish_kernel                        a block per quote: column sums in row order, price and error
+#include "svmc_internal.h"
+
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "svmc_black.h"
+#include "svmc_block.h"
+#include "svmc_models.h"
+#include "svmc_rng.h"
+#include "svmc_slice.h"
+
+namespace svmc {
+
+constexpr uint32_t CMC_STREAM = 8u;    // svmc_rng.h: one normal per step, word step & 3 of call step >> 2
+
+// ---------------------------------------------------------------------------------------------------
+// stepping
+// ---------------------------------------------------------------------------------------------------
+// Time steps [0, nb) of a lane whose first step has the chain-global index step0, ONE unscaled normal each.  A Philox call serves
+// the four steps 4c .. 4c + 3 and each word is guarded by a wave-uniform test: a slice that starts or ends inside a call uses
+// the words that are its own, so slicing a chain differently never changes what a (path, step) sees.  tick(t) runs once per call
+// with the local index of the call's first step (the progress priorities).
+template <class Step, class Tick>
+__device__ __forceinline__ void cmc_time_loop(const PhiloxLane &lane, uint32_t step0, int nb, const RngTables &tab, Step &&step, Tick &&tick)
+{
+    if (nb <= 0) return;
+    const uint32_t first = step0, last = step0 + static_cast<uint32_t>(nb) - 1u;
+    for (uint32_t c = first >> 2; c <= (last >> 2); ++c) {
+        tick(static_cast<int>(4u * c - first));
+        uint32_t r[4];
+        philox_draw(lane, c, r);
+#pragma unroll
+        for (uint32_t k = 0; k < 4u; ++k) {
+            const uint32_t s = 4u * c + k;
+            if (s >= first && s <= last)
+                step(normal_icdf32<SVMC_ICDF_M, SVMC_ICDF_SEGMENTS, SVMC_ICDF_DEG, SVMC_ICDF_EDGE != 0, SVMC_ICDF_RAW != 0>(r[k], tab.icdf));
+        }
+    }
+}
+
+// start state of a launch: read from the four state arrays (uniform = 0) or the same constants for every path
+struct CmcInit {
+    int uniform = 0;
+    double mu0 = 0.0, cv0 = 0.0, vol0 = 0.0, qvar0 = 0.0;
+};
+
+// ---- LogSV: logsv_step_acc with the two noise FMAs replaced by one (the volatility moves on beta w0 + volvol w1 = vartheta b)
+// and the drift added to L in one piece (logsv_cmc_step)
+struct LogsvCmc {
+    double c1, c2, c3;   // LogsvFast's drift constants, in log units
+    double vs;           // vartheta sqrt(dt), in log units
+    double hA, ahA;      // eta^2 dt / 2, alpha/2 eta^2 dt
+    double rhoB;         // rho eta sqrt(dt), rho = beta / vartheta (0 when vartheta == 0)
+    double cvA;          // (volvol^2 / vartheta^2) eta^2 dt (factor 1 when vartheta == 0): the quotient, not 1 - rho^2
+};
+
+static LogsvCmc make_logsv_cmc(double dt, double theta, double kappa1, double kappa2, double beta, double volvol, double eta,
+                               int is_spot_measure)
+{
+    const LogsvFast f = logsv_fast_in_log_units(make_logsv_fast(make_logsv_consts(dt, theta, kappa1, kappa2, beta, volvol, eta, is_spot_measure)));
+    const double vartheta2 = beta * beta + volvol * volvol, vartheta = sqrt(vartheta2);
+    LogsvCmc c;
+    c.c1 = f.c1;
+    c.c2 = f.c2;
+    c.c3 = f.c3;
+    c.vs = vartheta * sqrt(dt) * LOG_UNITS_PER_NAT;
+    c.hA = f.hA;
+    c.ahA = f.ahA;
+    c.rhoB = (vartheta > 0.0) ? (beta / vartheta) * f.B : 0.0;
+    c.cvA = (vartheta > 0.0) ? ((volvol * volvol) / vartheta2) * f.A : f.A;
+    return c;
+}
+
+// The drift is formed apart from L and added once (c3v: c3 in a vector register, so that fma(c2, s, c3) has one scalar operand):
+// the instruction count of logsv_step_acc's three updates of L, but two roundings at L's magnitude per step instead of four.
+// Where the noise is small against the drift (beta = volvol = 0: L hardly moves) the roundings of consecutive steps are the
+// same ones and add up instead of averaging out -- 18 ulp in sigma after 64 steps of the zero-noise set of
+// tests/golden/cmc_steps.npz with the drift added term by term, 2.5 with it added once.
+__device__ __forceinline__ void logsv_cmc_step(const LogsvCmc &c, double c3v, double &xacc, double &L, double &sigma, double &acc, double b,
+                                               const double *exp_table)
+{
+    const double s = sigma;
+    const double y = rcp_1n(s);
+    xacc = fma(s, b, xacc);                      // sum sigma_t b_t
+    acc = fma(s, s, acc);                        // sum sigma_t^2, the squares the steps START from
+    double d = fma(c.c2, s, c3v);
+    d = fma(c.c1, y, d);
+    L = L + d;
+    L = fma(c.vs, b, L);
+    sigma = exp2u_tab(L, exp_table);
+}
+
+// the fold at a slice's end: mu += ahA acc + rho B xacc, cv += (volvol^2 / vartheta^2) A acc, qvar as logsv_fold_acc
+__device__ __forceinline__ void logsv_cmc_fold(const LogsvCmc &c, double &mu, double &cv, double &qvar, double xacc, double acc,
+                                               double s2_start, double s2_now)
+{
+    mu = fma(c.rhoB, xacc, mu);
+    mu = fma(c.ahA, acc, mu);
+    cv = fma(c.cvA, acc, cv);
+    const double tail = s2_now - s2_start;
+    const bool finite = acc < __builtin_huge_val();
+    const double e = finite ? (acc + acc) + tail : acc;
+    qvar = fma(c.hA, e, qvar);
+}
+
+// `joined`, bit i: slice i has the bit-equal constants of slice i - 1 of the same launch.  Such a boundary is a snapshot and nothing
+// else: the accumulators (and LogSV's L) run on and the snapshot is the fold of the sums since the last boundary that was not
+// joined, so a chain's values do not depend on how a stretch of equal steps is cut into slices (3 + 5 + 8 steps = 16 steps, to
+// the bit).  Set on the host (cmc_step_chain).
+struct LogsvCmcSlices {
+    LogsvCmc c[MAX_CHAIN_SLICES];
+    int nb_steps[MAX_CHAIN_SLICES];
+    int m, total_steps = 0;
+    unsigned joined = 0;
+};
+
+// One body for both launch forms.  PARK (the full-launch form, 1024-thread blocks at eight waves per SIMD): the base values of mu, cv
+// and qvar are dead inside the time loop but live across it, and wait in LDS as logsv_chain_rng_kernel parks x and qvar; the few-waves form keeps
+// them in registers.  The statements on the state are the same, hence the bits.
+template <bool PARK, int TB>
+__device__ __forceinline__ void logsv_chain_cmc_body(double *__restrict__ mu, double *__restrict__ cv, double *__restrict__ sigma,
+                                                     double *__restrict__ qvar, size_t n, const LogsvCmcSlices &cs, uint64_t seed,
+                                                     uint32_t c3, uint64_t path_offset, uint32_t step_offset,
+                                                     double *__restrict__ mu_snap, double *__restrict__ cv_snap,
+                                                     double *__restrict__ q_snap, const CmcInit &init)
+{
+    __shared__ RngTablesLds s_tab;
+    __shared__ double s_exp[256];
+    __shared__ double s_park[PARK ? 3 * TB : 1];           // [0, TB): mu, [TB, 2 TB): cv, [2 TB, 3 TB): qvar -- lane t owns its three
+    const RngTables tab = stage_tables(s_tab, s_exp);
+    const auto path_index = [&]() {                        // re-derived where needed: one VGPR across the time loop
+        uint32_t t = threadIdx.x;
+        asm volatile("" : "+v"(t));
+        return static_cast<size_t>(blockIdx.x) * TB + t;
+    };
+    const bool active = path_index() < n;
+    double m_ = 0.0, v_ = 0.0, s = 1.0, q_ = 0.0;          // lanes past the last path step a dummy state
+    if (init.uniform) {                                    // wave-uniform
+        m_ = init.mu0;
+        v_ = init.cv0;
+        s = init.vol0;
+        q_ = init.qvar0;
+    } else if (active) {
+        const size_t p = path_index();
+        m_ = mu[p];
+        v_ = cv[p];
+        s = sigma[p];
+        q_ = qvar[p];
+    }
+    if constexpr (PARK) {
+        s_park[threadIdx.x] = m_;
+        s_park[TB + threadIdx.x] = v_;
+        s_park[2 * TB + threadIdx.x] = q_;
+    }
+    const PhiloxLane lane = philox_prepare(seed, c3 | CMC_STREAM, path_offset + path_index());
+    LogsvProgress prog = {(cs.total_steps + 3) >> 2};
+    int tg = 0;
+    // L = ln sigma in log units is derived once per LAUNCH and carried from slice to slice.  One Newton step on exp(L) = sigma:
+    // log_state is good to 4 ULP of ln sigma, which is up to 4 ulp(ln sigma) RELATIVE in the volatility the first step ends with
+    double L = log_state(s) * LOG_UNITS_PER_NAT;
+    {
+        const double back = exp2u_tab(L, s_exp);
+        if (back > 0.0 && back < __builtin_huge_val() && s < __builtin_huge_val())
+            L = fma(LOG_UNITS_PER_NAT, (s - back) / back, L);
+    }
+    // the sums since the last boundary that was not joined; (m_, v_, q_) -- parked in LDS in the PARK form -- is the state AT it
+    double acc = 0.0, xacc = 0.0, s2_start = square_rn(s);
+    for (int i = 0; i < cs.m; ++i) {
+        const int nb = cs.nb_steps[i];
+        const LogsvCmc c = cs.c[i];
+        double c3v = c.c3;
+        asm volatile("" : "+v"(c3v));
+        cmc_time_loop(
+            lane, step_offset + static_cast<uint32_t>(tg), nb, tab, [&](double b) { logsv_cmc_step(c, c3v, xacc, L, s, acc, b, s_exp); },
+            [&](int t) {
+                if (tg + t >= prog.next_stage_t) {         // wave-uniform
+                    progress_priority(prog.stage++);
+                    prog.next_stage_t += prog.quarter;
+                }
+            });
+        double ms, vs, qs;                                 // the expiry's values: the base folded with the sums so far
+        if constexpr (PARK) {
+            ms = s_park[threadIdx.x];                      // a lane reads back what it alone wrote: no barrier needed
+            vs = s_park[TB + threadIdx.x];
+            qs = s_park[2 * TB + threadIdx.x];
+        } else {
+            ms = m_;
+            vs = v_;
+            qs = q_;
+        }
+        logsv_cmc_fold(c, ms, vs, qs, xacc, acc, s2_start, square_rn(s));
+        tg += nb;
+        if (active) {
+            const size_t o = static_cast<size_t>(i) * n + path_index();
+            mu_snap[o] = ms;
+            cv_snap[o] = vs;
+            if (q_snap != nullptr) q_snap[o] = qs;
+        }
+        const bool runs_on = i + 1 < cs.m && ((cs.joined >> (i + 1)) & 1u) != 0u;      // wave-uniform
+        if (!runs_on) {                                    // a real boundary (the launch's end is one): the values become the base
+            if constexpr (PARK) {
+                s_park[threadIdx.x] = ms;
+                s_park[TB + threadIdx.x] = vs;
+                s_park[2 * TB + threadIdx.x] = qs;
+            } else {
+                m_ = ms;
+                v_ = vs;
+                q_ = qs;
+            }
+            acc = 0.0;
+            xacc = 0.0;
+            s2_start = square_rn(s);
+        }
+    }
+    if (active) {
+        const size_t p = path_index();
+        if constexpr (PARK) {
+            m_ = s_park[threadIdx.x];
+            v_ = s_park[TB + threadIdx.x];
+            q_ = s_park[2 * TB + threadIdx.x];
+        }
+        mu[p] = m_;
+        cv[p] = v_;
+        sigma[p] = s;
+        qvar[p] = q_;
+    }
+}
+
+constexpr int CMC_CHAIN_BLOCK = 1024;  // as logsv_chain_rng_kernel: two blocks per CU share its LDS (table 32 KB + exp 2 KB + park 24 KB each)
+__global__ __launch_bounds__(CMC_CHAIN_BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8), amdgpu_num_sgpr(80))) void logsv_chain_cmc_kernel(
+    double *__restrict__ mu, double *__restrict__ cv, double *__restrict__ sigma, double *__restrict__ qvar, size_t n, LogsvCmcSlices cs,
+    uint64_t seed, uint32_t c3, uint64_t path_offset, uint32_t step_offset, double *__restrict__ mu_snap, double *__restrict__ cv_snap,
+    double *__restrict__ q_snap, CmcInit init)
+{
+    logsv_chain_cmc_body<true, CMC_CHAIN_BLOCK>(mu, cv, sigma, qvar, n, cs, seed, c3, path_offset, step_offset, mu_snap, cv_snap, q_snap, init);
+}
+
+// the few-waves form (few_waves_launch()): 256-thread blocks so that every CU gets work, registers to spare
+__global__ __launch_bounds__(FEW_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 4))) void logsv_chain_cmc_lat_kernel(
+    double *__restrict__ mu, double *__restrict__ cv, double *__restrict__ sigma, double *__restrict__ qvar, size_t n, LogsvCmcSlices cs,
+    uint64_t seed, uint32_t c3, uint64_t path_offset, uint32_t step_offset, double *__restrict__ mu_snap, double *__restrict__ cv_snap,
+    double *__restrict__ q_snap, CmcInit init)
+{
+    logsv_chain_cmc_body<false, FEW_BLOCK>(mu, cv, sigma, qvar, n, cs, seed, c3, path_offset, step_offset, mu_snap, cv_snap, q_snap, init);
+}
+
+// ---- Heston: the reference's Euler step with its 1e-4 floor, the variance driven by b = rho w0 + rho_1 w1
+struct HestonCmc {
+    double dt, one_m_kdt, ktdt;   // 1 - kappa dt, kappa theta dt
+    double a;                     // volvol sqrt(dt)
+    double rho_sdt;               // rho sqrt(dt)
+    double rho1sq;                // rho_1^2 = 1 - rho^2
+};
+
+static HestonCmc make_heston_cmc(double dt, double theta, double kappa, double rho, double volvol)
+{
+    HestonCmc c;
+    c.dt = dt;
+    c.one_m_kdt = 1.0 - kappa * dt;
+    c.ktdt = kappa * theta * dt;
+    c.a = volvol * sqrt(dt);
+    c.rho_sdt = rho * sqrt(dt);
+    c.rho1sq = 1.0 - rho * rho;
+    return c;
+}
+
+__device__ __forceinline__ void heston_cmc_step(const HestonCmc &c, double &xacc, double &var, double &vacc, double b)
+{
+    const double v = var;
+    const double s = sqrt_pos_1g(v);                       // v > 0: heston_euler_guard_zero + the floor
+    vacc = vacc + v;
+    xacc = fma(s, b, xacc);
+    const double vn = fma(s, c.a * b, fma(v, c.one_m_kdt, c.ktdt));
+    var = fmax(vn, 1e-4);                                  // np.maximum(v, 1e-4); a NaN is put back by the fold
+}
+
+// mu += -dt sum v / 2 + rho sqrt(dt) sum sqrt(v) b, cv += rho_1^2 dt sum v, qvar += dt sum v
+__device__ __forceinline__ void heston_cmc_fold(const HestonCmc &c, double &mu, double &cv, double &qvar, double &var, double xacc, double vacc)
+{
+    const double q = c.dt * vacc;
+    mu = fma(c.rho_sdt, xacc, fma(-0.5, q, mu));
+    cv = fma(c.rho1sq, q, cv);
+    qvar = qvar + q;
+    const double finite_or_nan = ((c.one_m_kdt * 0.0 + c.ktdt * 0.0) + c.a * 0.0) + vacc * 0.0;   // 0 or NaN (heston_fold_acc)
+    var = var + finite_or_nan;
+}
+
+struct HestonCmcSlices {
+    HestonCmc c[MAX_CHAIN_SLICES];
+    int nb_steps[MAX_CHAIN_SLICES];
+    int m, total_steps = 0;
+    unsigned joined = 0;               // as LogsvCmcSlices
+};
+
+__device__ __forceinline__ void heston_chain_cmc_body(double *__restrict__ mu, double *__restrict__ cv, double *__restrict__ var,
+                                                      double *__restrict__ qvar, size_t n, const HestonCmcSlices &cs, uint64_t seed,
+                                                      uint32_t c3, uint64_t path_offset, uint32_t step_offset,
+                                                      double *__restrict__ mu_snap, double *__restrict__ cv_snap,
+                                                      double *__restrict__ q_snap, const CmcInit &init)
+{
+    __shared__ RngTablesLds s_tab;
+    const RngTables tab = stage_rng_tables(s_tab);
+    const size_t p = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    const bool active = p < n;
+    if (!active) return;                                   // (after the block's only barrier)
+    double m_, c_, v, q_;
+    if (init.uniform) {                                    // wave-uniform
+        m_ = init.mu0;
+        c_ = init.cv0;
+        v = init.vol0;
+        q_ = init.qvar0;
+    } else {
+        m_ = mu[p];
+        c_ = cv[p];
+        v = var[p];
+        q_ = qvar[p];
+    }
+    const PhiloxLane lane = philox_prepare(seed, c3 | CMC_STREAM, path_offset + p);
+    uint32_t step = step_offset;
+    double xacc = 0.0, vacc = 0.0;                         // the sums since the last boundary that was not joined (HestonCmcSlices)
+    for (int i = 0; i < cs.m; ++i) {
+        const int nb = cs.nb_steps[i];
+        const HestonCmc c = cs.c[i];
+        v = heston_euler_guard_zero(v);
+        cmc_time_loop(lane, step, nb, tab, [&](double b) { heston_cmc_step(c, xacc, v, vacc, b); }, [](int) {});
+        double ms = m_, vs = c_, qs = q_;
+        heston_cmc_fold(c, ms, vs, qs, v, xacc, vacc);
+        step += static_cast<uint32_t>(nb);
+        const size_t o = static_cast<size_t>(i) * n + p;
+        mu_snap[o] = ms;
+        cv_snap[o] = vs;
+        if (q_snap != nullptr) q_snap[o] = qs;
+        const bool runs_on = i + 1 < cs.m && ((cs.joined >> (i + 1)) & 1u) != 0u;      // wave-uniform
+        if (!runs_on) {
+            m_ = ms;
+            c_ = vs;
+            q_ = qs;
+            xacc = 0.0;
+            vacc = 0.0;
+        }
+    }
+    mu[p] = m_;
+    cv[p] = c_;
+    var[p] = v;
+    qvar[p] = q_;
+}
+
+__global__ __launch_bounds__(RNG_BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) void heston_chain_cmc_kernel(
+    double *__restrict__ mu, double *__restrict__ cv, double *__restrict__ var, double *__restrict__ qvar, size_t n, HestonCmcSlices cs,
+    uint64_t seed, uint32_t c3, uint64_t path_offset, uint32_t step_offset, double *__restrict__ mu_snap, double *__restrict__ cv_snap,
+    double *__restrict__ q_snap, CmcInit init)
+{
+    heston_chain_cmc_body(mu, cv, var, qvar, n, cs, seed, c3, path_offset, step_offset, mu_snap, cv_snap, q_snap, init);
+}
+
+__global__ __launch_bounds__(FEW_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 4))) void heston_chain_cmc_lat_kernel(
+    double *__restrict__ mu, double *__restrict__ cv, double *__restrict__ var, double *__restrict__ qvar, size_t n, HestonCmcSlices cs,
+    uint64_t seed, uint32_t c3, uint64_t path_offset, uint32_t step_offset, double *__restrict__ mu_snap, double *__restrict__ cv_snap,
+    double *__restrict__ q_snap, CmcInit init)
+{
+    heston_chain_cmc_body(mu, cv, var, qvar, n, cs, seed, c3, path_offset, step_offset, mu_snap, cv_snap, q_snap, init);
+}
+
+// ---- host side of the stepping: launches of at most MAX_CHAIN_SLICES expiries, the step offset carried from launch to launch
+template <class Slices, class Fill, class Launch>
+static int cmc_step_chain(const char *fn, const CmcInit &init, const double *mu, const double *cv, const double *vol, const double *qvar,
+                          size_t n_path, int n_slices, const int *nb_steps_host, const double *dts_host, uint32_t call_id,
+                          uint32_t step_offset, double *mu_snapshots, double *cv_snapshots, double *qvar_snapshots, Fill &&fill,
+                          Launch &&launch)
+{
+    SVMC_REQUIRE(mu && cv && vol && qvar && mu_snapshots && cv_snapshots, std::string(fn) + ": null pointer");
+    SVMC_REQUIRE(nb_steps_host && dts_host && n_slices >= 1, std::string(fn) + ": null grids / no slices");
+    SVMC_REQUIRE(call_id < (1u << 24), std::string(fn) + ": call_id must fit 24 bits");
+    SVMC_REQUIRE(n_path > 0, std::string(fn) + ": n_path must be positive");
+    for (int i = 0; i < n_slices; ++i)
+        SVMC_REQUIRE(nb_steps_host[i] > 0 && dts_host[i] > 0.0, std::string(fn) + ": nb_steps and dt must be positive");
+    for (int i0 = 0; i0 < n_slices; i0 += MAX_CHAIN_SLICES) {
+        Slices cs;
+        cs.m = (n_slices - i0 < MAX_CHAIN_SLICES) ? (n_slices - i0) : MAX_CHAIN_SLICES;
+        uint32_t steps = 0;
+        for (int i = 0; i < MAX_CHAIN_SLICES; ++i) {
+            const int j = (i < cs.m) ? i0 + i : i0;        // unused entries repeat a valid one
+            cs.nb_steps[i] = (i < cs.m) ? nb_steps_host[j] : 0;
+            steps += static_cast<uint32_t>(cs.nb_steps[i]);
+            fill(cs, i, j);
+        }
+        cs.total_steps = static_cast<int>(steps);
+        cs.joined = 0u;
+        for (int i = 1; i < cs.m; ++i)
+            if (memcmp(&cs.c[i], &cs.c[i - 1], sizeof(cs.c[i])) == 0) cs.joined |= 1u << i;
+        const size_t row = static_cast<size_t>(i0) * n_path;
+        launch(cs, mu_snapshots + row, cv_snapshots + row, qvar_snapshots ? qvar_snapshots + row : nullptr, (i0 == 0) ? init : CmcInit(),
+               step_offset);
+        if (int rc = check_launch(fn)) return rc;
+        step_offset += steps;
+    }
+    return SVMC_OK;
+}
+
+int logsv_cmc_step_chain(const char *fn, const CmcInit &init, double *mu, double *cv, double *sigma, double *qvar, size_t n_path,
+                         int n_slices, const int *nb_steps_host, const double *dts_host, const double *etas_host, double theta,
+                         double kappa1, double kappa2, double beta, double volvol, int is_spot_measure, uint64_t seed, uint32_t call_id,
+                         uint64_t path_offset, uint32_t step_offset, double *mu_snapshots, double *cv_snapshots, double *qvar_snapshots,
+                         hipStream_t stream)
+{
+    const auto fill = [&](LogsvCmcSlices &cs, int i, int j) {
+        cs.c[i] = make_logsv_cmc(dts_host[j], theta, kappa1, kappa2, beta, volvol, etas_host ? etas_host[j] : 1.0, is_spot_measure);
+    };
+    const auto launch = [&](const LogsvCmcSlices &cs, double *ms, double *vs, double *qs, const CmcInit &init_i, uint32_t step0) {
+        if (few_waves_launch(n_path))
+            hipLaunchKernelGGL(logsv_chain_cmc_lat_kernel, dim3(lat_grid(n_path)), dim3(FEW_BLOCK), 0, stream, mu, cv, sigma, qvar, n_path,
+                               cs, seed, make_c3(call_id), path_offset, step0, ms, vs, qs, init_i);
+        else
+            hipLaunchKernelGGL(logsv_chain_cmc_kernel, dim3(static_cast<unsigned>((n_path + CMC_CHAIN_BLOCK - 1) / CMC_CHAIN_BLOCK)),
+                               dim3(CMC_CHAIN_BLOCK), 0, stream, mu, cv, sigma, qvar, n_path, cs, seed, make_c3(call_id), path_offset, step0,
+                               ms, vs, qs, init_i);
+    };
+    return cmc_step_chain<LogsvCmcSlices>(fn, init, mu, cv, sigma, qvar, n_path, n_slices, nb_steps_host, dts_host, call_id, step_offset,
+                                          mu_snapshots, cv_snapshots, qvar_snapshots, fill, launch);
+}
+
+int heston_cmc_step_chain(const char *fn, const CmcInit &init, double *mu, double *cv, double *var, double *qvar, size_t n_path,
+                          int n_slices, const int *nb_steps_host, const double *dts_host, double theta, double kappa, double rho,
+                          double volvol, uint64_t seed, uint32_t call_id, uint64_t path_offset, uint32_t step_offset,
+                          double *mu_snapshots, double *cv_snapshots, double *qvar_snapshots, hipStream_t stream)
+{
+    const auto fill = [&](HestonCmcSlices &cs, int i, int j) { cs.c[i] = make_heston_cmc(dts_host[j], theta, kappa, rho, volvol); };
+    const auto launch = [&](const HestonCmcSlices &cs, double *ms, double *vs, double *qs, const CmcInit &init_i, uint32_t step0) {
+        if (few_waves_launch(n_path))
+            hipLaunchKernelGGL(heston_chain_cmc_lat_kernel, dim3(lat_grid(n_path)), dim3(FEW_BLOCK), 0, stream, mu, cv, var, qvar, n_path,
+                               cs, seed, make_c3(call_id), path_offset, step0, ms, vs, qs, init_i);
+        else
+            hipLaunchKernelGGL(heston_chain_cmc_kernel, dim3(rng_grid(n_path)), dim3(rng_block()), 0, stream, mu, cv, var, qvar, n_path, cs,
+                               seed, make_c3(call_id), path_offset, step0, ms, vs, qs, init_i);
+    };
+    return cmc_step_chain<HestonCmcSlices>(fn, init, mu, cv, var, qvar, n_path, n_slices, nb_steps_host, dts_host, call_id, step_offset,
+                                           mu_snapshots, cv_snapshots, qvar_snapshots, fill, launch);
+}
+
+// the fused drivers' stepping (svmc_chain.hip) from the start state (0, 0, vol0, 0)
+int logsv_cmc_step_from(double sigma0, double *mu, double *cv, double *sigma, double *qvar, size_t n_path, int n_slices,
+                        const int *nb_steps_host, const double *dts_host, const double *etas_host, double theta, double kappa1,
+                        double kappa2, double beta, double volvol, int is_spot_measure, uint64_t seed, uint32_t call_id,
+                        uint64_t path_offset, double *mu_snapshots, double *cv_snapshots, hipStream_t stream)
+{
+    const CmcInit init = {1, 0.0, 0.0, sigma0, 0.0};
+    return logsv_cmc_step_chain("svmc_logsv_chain_price_cmc", init, mu, cv, sigma, qvar, n_path, n_slices, nb_steps_host, dts_host,
+                                etas_host, theta, kappa1, kappa2, beta, volvol, is_spot_measure, seed, call_id, path_offset, 0u,
+                                mu_snapshots, cv_snapshots, nullptr, stream);
+}
+
+int heston_cmc_step_from(double var0, double *mu, double *cv, double *var, double *qvar, size_t n_path, int n_slices,
+                         const int *nb_steps_host, const double *dts_host, double theta, double kappa, double rho, double volvol,
+                         uint64_t seed, uint32_t call_id, uint64_t path_offset, double *mu_snapshots, double *cv_snapshots,
+                         hipStream_t stream)
+{
+    const CmcInit init = {1, 0.0, 0.0, var0, 0.0};
+    return heston_cmc_step_chain("svmc_heston_chain_price_cmc", init, mu, cv, var, qvar, n_path, n_slices, nb_steps_host, dts_host, theta,
+                                 kappa, rho, volvol, seed, call_id, path_offset, 0u, mu_snapshots, cv_snapshots, nullptr, stream);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// payoff reduction
+// ---------------------------------------------------------------------------------------------------
+constexpr int CMC_KT = 8;              // strikes per group: two accumulators and three constants per strike in vector registers
+constexpr unsigned CMC_ROWS = 1024;    // path blocks per launch at most: rows(n) is a function of n_path alone
+static inline unsigned cmc_rows(size_t n) { return static_cast<unsigned>(std::min<size_t>((n + BLOCK - 1) / BLOCK, CMC_ROWS)); }
+
+// the device table of a chain, uploaded once per call
+struct CmcExpiry {
+    const double *mu, *cv;
+    double forward, ln_forward, discfactor;
+    int k0, k1;                        // its strikes [k0, k1)
+};
+struct CmcGroup {
+    int expiry, k0, nk, pad;           // strikes [k0, k0 + nk) of `expiry`
+};
+struct CmcTable {
+    const CmcExpiry *expiries;
+    const CmcGroup *groups;
+    const double *strikes;             // [K]
+    const double *is_put;              // [K] 0 | 1
+    const double *intrinsic;           // [K] max(+-(F - K), 0): the shift where path 0 of the expiry is dropped
+    double *kp, *ln_kp, *shift;        // [K] device-computed: K + corr, its logarithm (0 where K + corr <= 0), the sums' shift
+    double *fwd;                       // [m][4]: sum (e - 1), sum (e - 1)^2, kept count, corr
+    double *stats;                     // [m][SVMC_CMC_STATS_DOUBLES]
+    double *fwd_partials;              // [rows][m][3]
+    double *pay_partials;              // [rows][K][2]
+    double *out;                       // [2][K]: prices, errors
+    int m, K;
+    unsigned rows;
+};
+
+// a path is kept iff mu, cv and e = exp(mu + cv / 2) are finite and cv >= 0 (include/svmc.h); h = mu + cv / 2
+__device__ __forceinline__ bool cmc_keep(double mu, double cv, double &h, double &e)
+{
+    h = fma(0.5, cv, mu);
+    e = exp_full(h);
+    const double inf = __builtin_huge_val();
+    return fabs(mu) < inf && cv >= 0.0 && cv < inf && e < inf;     // a NaN fails a comparison
+}
+
+// the undiscounted Black-76 price of F_c = F e against K' at total variance cv, on the quoted side's own formula
+__device__ __forceinline__ double cmc_black(double fc, double ln_fc, double cv, double sd, double inv_sd, double kp, double ln_kp, bool put)
+{
+    if (!(kp > 0.0)) return put ? 0.0 : fc - kp;
+    if (cv == 0.0) return put ? fmax(kp - fc, 0.0) : fmax(fc - kp, 0.0);
+    const double d1 = fma(ln_fc - ln_kp, inv_sd, 0.5 * sd), d2 = d1 - sd;
+    return put ? kp * black_norm_cdf(-d2) - fc * black_norm_cdf(-d1) : fc * black_norm_cdf(d1) - kp * black_norm_cdf(d2);
+}
+
+__global__ __launch_bounds__(BLOCK) void cmc_forward_kernel(CmcTable t, size_t n)
+{
+    __shared__ double lds[4 * 3];
+    const CmcExpiry ex = t.expiries[blockIdx.y];
+    const size_t stride = static_cast<size_t>(gridDim.x) * BLOCK;
+    double v[3] = {0.0, 0.0, 0.0};
+    for (size_t i = static_cast<size_t>(blockIdx.x) * BLOCK + threadIdx.x; i < n; i += stride) {
+        double h, e;
+        if (cmc_keep(ex.mu[i], ex.cv[i], h, e)) {
+            const double d = e - 1.0;
+            v[0] += d;
+            v[1] = fma(d, d, v[1]);
+            v[2] += 1.0;
+        }
+    }
+    block_sum_store<3>(v, lds, t.fwd_partials + (static_cast<size_t>(blockIdx.x) * t.m + blockIdx.y) * 3, 3);
+}
+
+// its in-order finish, a block per expiry: the three column sums in row order, the forward statistics, and -- once per strike --
+// K' = K + corr, ln K' and the shift of the strike's sums: the price of the expiry's path 0 (identical paths then leave sums
+// that are exactly zero), or the intrinsic value at the forward where that path is dropped
+__global__ __launch_bounds__(BLOCK) void cmc_forward_finish_kernel(CmcTable t, size_t n, int recenter)
+{
+    __shared__ double lds[4];
+    __shared__ double s_corr;
+    const int i = blockIdx.x;
+    const CmcExpiry ex = t.expiries[i];
+    const size_t ld = 3 * static_cast<size_t>(t.m);
+    const double *base = t.fwd_partials + 3 * static_cast<size_t>(i);
+    const double s0 = block_column_sum(base, t.rows, ld, lds);
+    __syncthreads();
+    const double s1 = block_column_sum(base + 1, t.rows, ld, lds);
+    __syncthreads();
+    const double cnt = block_column_sum(base + 2, t.rows, ld, lds);
+    if (threadIdx.x == 0) {
+        const double dmean = s0 / cnt;                     // 0 / 0 -> NaN like nanmean of an empty slice
+        double var = s1 / cnt - dmean * dmean;
+        if (var < 0.0) var = 0.0;
+        const double fmean = fma(ex.forward, dmean, ex.forward);
+        const double corr = recenter ? ex.forward * dmean : 0.0;       // mean_kept(F_c) - F
+        double *f = t.fwd + 4 * i, *st = t.stats + SVMC_CMC_STATS_DOUBLES * i;
+        f[0] = s0;
+        f[1] = s1;
+        f[2] = cnt;
+        f[3] = corr;
+        st[0] = fmean;
+        st[1] = fabs(ex.forward) * sqrt(var) / sqrt(static_cast<double>(n));
+        st[2] = corr;
+        st[3] = cnt;
+        st[4] = static_cast<double>(n) - cnt;
+        s_corr = corr;
+    }
+    __syncthreads();
+    const double corr = s_corr;
+    double h, e;
+    const double mu0 = ex.mu[0], cv0 = ex.cv[0];
+    const bool keep0 = cmc_keep(mu0, cv0, h, e);
+    const double fc = ex.forward * e, ln_fc = ex.ln_forward + h, sd = sqrt(cv0), inv_sd = 1.0 / sd;
+    for (int k = ex.k0 + static_cast<int>(threadIdx.x); k < ex.k1; k += BLOCK) {
+        const double kp = t.strikes[k] + corr;
+        const double ln_kp = (kp > 0.0) ? log(kp) : 0.0;
+        t.kp[k] = kp;
+        t.ln_kp[k] = ln_kp;
+        t.shift[k] = keep0 ? cmc_black(fc, ln_fc, cv0, sd, inv_sd, kp, ln_kp, t.is_put[k] != 0.0) : t.intrinsic[k];
+    }
+}
+
+__global__ __launch_bounds__(BLOCK) void cmc_payoff_kernel(CmcTable t, size_t n)
+{
+    __shared__ double lds[4 * block_sum_padded(2 * CMC_KT)];
+    const CmcGroup g = t.groups[blockIdx.y];
+    const CmcExpiry ex = t.expiries[g.expiry];
+    double kp[CMC_KT], ln_kp[CMC_KT], shift[CMC_KT], acc[2 * CMC_KT];
+    bool put[CMC_KT];
+#pragma unroll
+    for (int k = 0; k < CMC_KT; ++k) {
+        const int kk = g.k0 + ((k < g.nk) ? k : 0);        // the unused strikes of a group repeat its first; their sums are dropped
+        kp[k] = t.kp[kk];
+        ln_kp[k] = t.ln_kp[kk];
+        shift[k] = t.shift[kk];
+        put[k] = t.is_put[kk] != 0.0;
+        acc[k] = acc[CMC_KT + k] = 0.0;
+    }
+    const double forward = ex.forward, ln_forward = ex.ln_forward;
+    const size_t stride = static_cast<size_t>(gridDim.x) * BLOCK;
+    for (size_t i = static_cast<size_t>(blockIdx.x) * BLOCK + threadIdx.x; i < n; i += stride) {
+        const double cv = ex.cv[i];
+        double h, e;
+        if (!cmc_keep(ex.mu[i], cv, h, e)) continue;
+        const double fc = forward * e, ln_fc = ln_forward + h;
+        const double sd = sqrt(cv), inv_sd = 1.0 / sd;
+#pragma unroll
+        for (int k = 0; k < CMC_KT; ++k) {
+            const double d = cmc_black(fc, ln_fc, cv, sd, inv_sd, kp[k], ln_kp[k], put[k]) - shift[k];
+            acc[k] += d;
+            acc[CMC_KT + k] = fma(d, d, acc[CMC_KT + k]);
+        }
+    }
+    double *out = t.pay_partials + (static_cast<size_t>(blockIdx.x) * t.K + g.k0) * 2;
+    const int nk = g.nk;
+    block_sum_apply<2 * CMC_KT>(acc, lds, 2 * CMC_KT, [&](int j, double s) {
+        const int k = (j < CMC_KT) ? j : j - CMC_KT;
+        if (k < nk) out[2 * k + ((j < CMC_KT) ? 0 : 1)] = s;
+    });
+}
+
+// a block per quote: its two column sums in row order, then utils/mc_payoffs.py:85-88 on them (payoff_finalize_one): price =
+// discfactor (shift + mean), error = discfactor x population deviation / sqrt(n_path)
+__global__ __launch_bounds__(BLOCK) void cmc_finish_kernel(CmcTable t, size_t n)
+{
+    __shared__ double lds[4];
+    const int k = blockIdx.x;
+    int i = 0;
+    while (i + 1 < t.m && k >= t.expiries[i].k1) ++i;      // (block-uniform; expiries without strikes are skipped over)
+    const size_t ld = 2 * static_cast<size_t>(t.K);
+    const double s = block_column_sum(t.pay_partials + 2 * static_cast<size_t>(k), t.rows, ld, lds);
+    __syncthreads();
+    const double s2 = block_column_sum(t.pay_partials + 2 * static_cast<size_t>(k) + 1, t.rows, ld, lds);
+    if (threadIdx.x == 0) {
+        double price, err;
+        payoff_finalize_one(s, s2, t.fwd[4 * i + 2], t.shift[k], t.expiries[i].discfactor, static_cast<double>(n), &price, &err);
+        t.out[k] = price;
+        t.out[t.K + k] = err;
+    }
+}
+
+static size_t align8(size_t b) { return (b + 7) & ~static_cast<size_t>(7); }
+static int cmc_groups(int n_expiries, const size_t *offsets)
+{
+    int g = 0;
+    for (int i = 0; i < n_expiries; ++i) g += static_cast<int>((offsets[i + 1] - offsets[i] + CMC_KT - 1) / CMC_KT);
+    return g;
+}
+static size_t cmc_workspace_bytes(size_t n_path, int m, size_t K, int groups)
+{
+    const size_t rows = cmc_rows(n_path);
+    return align8(sizeof(CmcExpiry) * m) + align8(sizeof(CmcGroup) * groups) + sizeof(double) * (6 * K + 4 * m + SVMC_CMC_STATS_DOUBLES * m +
+           rows * 3 * m + rows * 2 * K + 2 * K);
+}
+
+// prices_host, stderrs_host [K], stats_host [m][SVMC_CMC_STATS_DOUBLES] (nullable); returns after the stream is synchronised.
+// pinned (nullable): page-locked host memory of cmc_payoff_pinned_bytes_of(m, K) for the table's image and the results
+int cmc_payoff_chain(const char *fn, const double *const *mu_snapshots_host, const double *const *cv_snapshots_host, size_t n_path,
+                     const double *forwards_host, const double *discfactors_host, int n_expiries, const double *strikes_host,
+                     const int8_t *types_host, const size_t *strike_offsets_host, int recenter, double *prices_host, double *stderrs_host,
+                     double *stats_host, void *workspace, size_t workspace_bytes, hipStream_t stream, void *pinned, size_t pinned_bytes)
+{
+    SVMC_REQUIRE(mu_snapshots_host && cv_snapshots_host && forwards_host && discfactors_host && strikes_host && types_host &&
+                     strike_offsets_host && prices_host && stderrs_host && workspace,
+                 std::string(fn) + ": null pointer");
+    SVMC_REQUIRE(n_path > 0 && n_expiries >= 1, std::string(fn) + ": n_path and n_expiries must be positive");
+    const int m = n_expiries;
+    const size_t K = strike_offsets_host[m];
+    for (int i = 0; i < m; ++i) {
+        SVMC_REQUIRE(mu_snapshots_host[i] && cv_snapshots_host[i], std::string(fn) + ": null snapshot");
+        SVMC_REQUIRE(strike_offsets_host[i] <= strike_offsets_host[i + 1], std::string(fn) + ": strike offsets must not decrease");
+        SVMC_REQUIRE(std::isfinite(forwards_host[i]) && forwards_host[i] > 0.0, std::string(fn) + ": a forward is not positive and finite");
+    }
+    for (size_t k = 0; k < K; ++k) {
+        if (types_host[k] != SVMC_CALL && types_host[k] != SVMC_PUT) return fail(SVMC_ERR_UNKNOWN_PAYOFF, "unknown option payoff code");
+        SVMC_REQUIRE(std::isfinite(strikes_host[k]), std::string(fn) + ": a strike is not finite");
+    }
+    SVMC_REQUIRE(K < (1u << 30), std::string(fn) + ": too many strikes");
+    const int G = cmc_groups(m, strike_offsets_host);
+    if (workspace_bytes < cmc_workspace_bytes(n_path, m, K, G))
+        return fail(SVMC_ERR_WORKSPACE, std::string(fn) + ": workspace too small (svmc_cmc_payoff_workspace_bytes)");
+
+    // the table's host image: expiries, groups, then strikes / is_put / intrinsic
+    const size_t o_groups = align8(sizeof(CmcExpiry) * m), o_k = o_groups + align8(sizeof(CmcGroup) * G), up_bytes = o_k + 3 * K * sizeof(double);
+    // ... built in the caller's page-locked staging block where it gave one that holds the image and the results (the fused
+    // drivers: an upload from and downloads into pageable memory go through the runtime's staging path, 16 us apiece)
+    const size_t n_res = 2 * K + static_cast<size_t>(SVMC_CMC_STATS_DOUBLES) * m;
+    const bool staged = pinned != nullptr && pinned_bytes >= up_bytes + n_res * sizeof(double);
+    std::vector<unsigned char> pageable(staged ? 0 : up_bytes + n_res * sizeof(double));
+    unsigned char *img = staged ? static_cast<unsigned char *>(pinned) : pageable.data();
+    double *res = reinterpret_cast<double *>(img + up_bytes);
+    CmcExpiry *ex = reinterpret_cast<CmcExpiry *>(img);
+    CmcGroup *gr = reinterpret_cast<CmcGroup *>(img + o_groups);
+    double *kd = reinterpret_cast<double *>(img + o_k);
+    int g = 0;
+    for (int i = 0; i < m; ++i) {
+        const int k0 = static_cast<int>(strike_offsets_host[i]), k1 = static_cast<int>(strike_offsets_host[i + 1]);
+        ex[i] = CmcExpiry{mu_snapshots_host[i], cv_snapshots_host[i], forwards_host[i], std::log(forwards_host[i]), discfactors_host[i], k0, k1};
+        for (int k = k0; k < k1; k += CMC_KT) gr[g++] = CmcGroup{i, k, (k1 - k < CMC_KT) ? k1 - k : CMC_KT, 0};
+        for (int k = k0; k < k1; ++k) {
+            const bool put = types_host[k] == SVMC_PUT;
+            kd[k] = strikes_host[k];
+            kd[K + k] = put ? 1.0 : 0.0;
+            kd[2 * K + k] = put ? std::fmax(strikes_host[k] - forwards_host[i], 0.0) : std::fmax(forwards_host[i] - strikes_host[k], 0.0);
+        }
+    }
+    unsigned char *w = static_cast<unsigned char *>(workspace);
+    SVMC_HIP_TRY(hipMemcpyAsync(w, img, up_bytes, hipMemcpyHostToDevice, stream));
+    double *d = reinterpret_cast<double *>(w + o_k);
+    CmcTable t;
+    t.expiries = reinterpret_cast<const CmcExpiry *>(w);
+    t.groups = reinterpret_cast<const CmcGroup *>(w + o_groups);
+    t.strikes = d;
+    t.is_put = d + K;
+    t.intrinsic = d + 2 * K;
+    t.kp = d + 3 * K;
+    t.ln_kp = d + 4 * K;
+    t.shift = d + 5 * K;
+    t.fwd = d + 6 * K;
+    t.out = t.fwd + 4 * m;                                 // the results, one block: prices [K], errors [K], statistics [m][5]
+    t.stats = t.out + 2 * K;
+    t.m = m;
+    t.K = static_cast<int>(K);
+    t.rows = cmc_rows(n_path);
+    t.fwd_partials = t.stats + SVMC_CMC_STATS_DOUBLES * m;
+    t.pay_partials = t.fwd_partials + static_cast<size_t>(t.rows) * 3 * m;
+
+    hipLaunchKernelGGL(cmc_forward_kernel, dim3(t.rows, m), dim3(BLOCK), 0, stream, t, n_path);
+    if (int rc = check_launch(fn)) return rc;
+    hipLaunchKernelGGL(cmc_forward_finish_kernel, dim3(m), dim3(BLOCK), 0, stream, t, n_path, recenter ? 1 : 0);
+    if (int rc = check_launch(fn)) return rc;
+    if (K > 0) {
+        hipLaunchKernelGGL(cmc_payoff_kernel, dim3(t.rows, G), dim3(BLOCK), 0, stream, t, n_path);
+        if (int rc = check_launch(fn)) return rc;
+        hipLaunchKernelGGL(cmc_finish_kernel, dim3(static_cast<unsigned>(K)), dim3(BLOCK), 0, stream, t, n_path);
+        if (int rc = check_launch(fn)) return rc;
+    }
+    SVMC_HIP_TRY(hipMemcpyAsync(res, t.out, n_res * sizeof(double), hipMemcpyDeviceToHost, stream));
+    SVMC_HIP_TRY(hipStreamSynchronize(stream));            // the table's host image and the results' landing
+    memcpy(prices_host, res, K * sizeof(double));
+    memcpy(stderrs_host, res + K, K * sizeof(double));
+    if (stats_host != nullptr) memcpy(stats_host, res + 2 * K, static_cast<size_t>(SVMC_CMC_STATS_DOUBLES) * m * sizeof(double));
+    return SVMC_OK;
+}
+
+size_t cmc_payoff_pinned_bytes_of(int n_expiries, size_t total_strikes)
+{
+    const int groups = static_cast<int>(total_strikes / CMC_KT) + n_expiries;
+    return align8(sizeof(CmcExpiry) * n_expiries) + align8(sizeof(CmcGroup) * groups) +
+           sizeof(double) * (5 * total_strikes + static_cast<size_t>(SVMC_CMC_STATS_DOUBLES) * n_expiries);
+}
+
+size_t cmc_payoff_workspace_bytes_of(size_t n_path, int n_expiries, size_t total_strikes)
+{
+    // every expiry may end in a ragged group
+    return cmc_workspace_bytes(n_path, n_expiries, total_strikes, static_cast<int>(total_strikes / CMC_KT) + n_expiries);
+}
+
+}  // namespace svmc
+
+using namespace svmc;
+
+extern "C" {
+
+int svmc_logsv_chain_cmc(double *mu, double *cv, double *sigma, double *qvar, size_t n_path, int n_slices, const int *nb_steps_host,
+                         const double *dts_host, const double *etas_host, double theta, double kappa1, double kappa2, double beta,
+                         double volvol, int is_spot_measure, uint64_t seed, uint32_t call_id, uint64_t path_offset, uint32_t step_offset,
+                         double *mu_snapshots, double *cv_snapshots, double *qvar_snapshots, svmc_stream_t stream)
+{
+    return logsv_cmc_step_chain("svmc_logsv_chain_cmc", CmcInit(), mu, cv, sigma, qvar, n_path, n_slices, nb_steps_host, dts_host, etas_host,
+                                theta, kappa1, kappa2, beta, volvol, is_spot_measure, seed, call_id, path_offset, step_offset, mu_snapshots,
+                                cv_snapshots, qvar_snapshots, as_stream(stream));
+}
+
+int svmc_heston_chain_cmc(double *mu, double *cv, double *var, double *qvar, size_t n_path, int n_slices, const int *nb_steps_host,
+                          const double *dts_host, double theta, double kappa, double rho, double volvol, uint64_t seed, uint32_t call_id,
+                          uint64_t path_offset, uint32_t step_offset, double *mu_snapshots, double *cv_snapshots, double *qvar_snapshots,
+                          svmc_stream_t stream)
+{
+    return heston_cmc_step_chain("svmc_heston_chain_cmc", CmcInit(), mu, cv, var, qvar, n_path, n_slices, nb_steps_host, dts_host, theta,
+                                 kappa, rho, volvol, seed, call_id, path_offset, step_offset, mu_snapshots, cv_snapshots, qvar_snapshots,
+                                 as_stream(stream));
+}
+
+int svmc_cmc_payoff_workspace_bytes(size_t n_path, int n_expiries, size_t total_strikes, size_t *bytes)
+{
+    SVMC_REQUIRE(bytes != nullptr && n_expiries >= 1, "svmc_cmc_payoff_workspace_bytes: null output or no expiries");
+    *bytes = cmc_payoff_workspace_bytes_of(n_path, n_expiries, total_strikes);
+    return SVMC_OK;
+}
+
+int svmc_cmc_payoff_chain(const double *const *mu_snapshots_host, const double *const *cv_snapshots_host, size_t n_path,
+                          const double *forwards_host, const double *discfactors_host, int n_expiries, const double *strikes_host,
+                          const int8_t *types_host, const size_t *strike_offsets_host, int recenter, double *prices_host,
+                          double *stderrs_host, double *stats_host, void *workspace, size_t workspace_bytes, svmc_stream_t stream)
+{
+    return cmc_payoff_chain("svmc_cmc_payoff_chain", mu_snapshots_host, cv_snapshots_host, n_path, forwards_host, discfactors_host,
+                            n_expiries, strikes_host, types_host, strike_offsets_host, recenter, prices_host, stderrs_host, stats_host,
+                            workspace, workspace_bytes, as_stream(stream), nullptr, 0);
+}
+
+}  // extern "C"

@@ -128,6 +128,22 @@ int hawkes_chain_rng_many(size_t n_path, int n_jobs, int n_slices, const int *nb
                           const double *forwards_host, const double *params_host, const uint64_t *seeds, const uint32_t *call_ids,
                           uint64_t path_offset, void *table_host, void *table_dev, double *x_snapshots, double *spot_partials,
                           hipStream_t stream);
+// svmc_cmc.hip: the conditional Monte Carlo chain (svmc_*_chain_price_cmc) -- stepping from (mu, cv, vol, qvar) = (0, 0, vol0, 0)
+// into the mu / cv snapshot rows, the payoff tail (svmc_cmc_payoff_chain's body: returns synchronised) and its workspace
+int logsv_cmc_step_from(double sigma0, double *mu, double *cv, double *sigma, double *qvar, size_t n_path, int n_slices,
+                        const int *nb_steps_host, const double *dts_host, const double *etas_host, double theta, double kappa1,
+                        double kappa2, double beta, double volvol, int is_spot_measure, uint64_t seed, uint32_t call_id,
+                        uint64_t path_offset, double *mu_snapshots, double *cv_snapshots, hipStream_t stream);
+int heston_cmc_step_from(double var0, double *mu, double *cv, double *var, double *qvar, size_t n_path, int n_slices,
+                         const int *nb_steps_host, const double *dts_host, double theta, double kappa, double rho, double volvol,
+                         uint64_t seed, uint32_t call_id, uint64_t path_offset, double *mu_snapshots, double *cv_snapshots,
+                         hipStream_t stream);
+size_t cmc_payoff_workspace_bytes_of(size_t n_path, int n_expiries, size_t total_strikes);
+int cmc_payoff_chain(const char *fn, const double *const *mu_snapshots_host, const double *const *cv_snapshots_host, size_t n_path,
+                     const double *forwards_host, const double *discfactors_host, int n_expiries, const double *strikes_host,
+                     const int8_t *types_host, const size_t *strike_offsets_host, int recenter, double *prices_host, double *stderrs_host,
+                     double *stats_host, void *workspace, size_t workspace_bytes, hipStream_t stream, void *pinned, size_t pinned_bytes);
+size_t cmc_payoff_pinned_bytes_of(int n_expiries, size_t total_strikes);
 size_t payoff_sets_workspace_bytes(size_t n_path, size_t total_strikes, int n_sets);
 int chain_payoff_and_finish_sets(const double *const *x_snapshots_host, const double *const *qvar_snapshots_host, size_t n_path,
                                  const double *forwards_host, const double *ttms_host, const double *spot_sums, int n_expiries,

@@ -81,27 +81,7 @@ __global__ __launch_bounds__(BLOCK) void fill_uniforms_kernel(double *__restrict
 // ---------------------------------------------------------------------------------------------------
 // LogSV generators (pricers/logsv_pricer.py:950-1047)
 // ---------------------------------------------------------------------------------------------------
-// Least-progress-first wave priority.  The SIMD arbiter picks by priority, then age; with equal priorities the
-// oldest wave always wins, younger waves starve and each launch ends in a long ramp-down where lone, late waves run
-// at ~60 % of the saturated rate (tools/ubench/tail_probe.hip).  Dropping a wave's own priority as it progresses
-// through the time loop (3 -> 0 at the quarter points) lets waves that are behind catch up: residency stays at 8
-// waves per SIMD and the ramp-down shrinks from ~30 % to ~10 % of the launch.
-__device__ __forceinline__ void progress_priority(int stage)
-{
-    switch (stage) {
-    case 0: __builtin_amdgcn_s_setprio(3); break;
-    case 1: __builtin_amdgcn_s_setprio(2); break;
-    case 2: __builtin_amdgcn_s_setprio(1); break;
-    default: __builtin_amdgcn_s_setprio(0); break;
-    }
-}
-
-// where a launch stands on that ladder: wave-uniform counters, carried from slice to slice of a chain
-struct LogsvProgress {
-    int quarter;                       // a quarter of the launch's steps, rounded up
-    int stage = 0, next_stage_t = 0;
-};
-
+// (the least-progress-first wave priority of the time loops, progress_priority / LogsvProgress: svmc_block.h)
 // what a slice's time loop leaves for logsv_fold_acc
 struct LogsvSliceSums {
     double xacc, acc, s2_start;

@@ -20,6 +20,9 @@
 //   Hawkes jump-diffusion (svmc_hawkes.hip): ONE call of stream 6 per step at index = the chain-global step (not step >> 1):
 //   z(r0) the diffusion's normal, u_p = (r1 + 1/2) 2^-32, u_m = (r2 + 1/2) 2^-32, r3 unused; on a step where a side jumps (and
 //   only there, lazily) stream 7's call at the same index: E_p = -ln((r0 + 1/2) 2^-32), E_m = -ln((r1 + 1/2) 2^-32).
+//   Conditional Monte Carlo (svmc_cmc.hip): stream 8, ONE normal per step -- a call carries FOUR steps, laid out as stream 5's
+//   uniforms are: step s (chain-global) takes z(r[s & 3]) of the call at index s >> 2, so a slice may begin or end anywhere inside
+//   a call without changing what a (path, step) sees.  Streams 0 .. 7 are untouched: the stream version stays 4.
 // Resolution: a normal carries 32 random bits (as in version 2, whose Box-Muller pair spent 32 on the radius and 32 on
 // the angle); the lattice is 2^-32 in probability, symmetric about 0 (every magnitude 1 .. 2^31 - 1 with both signs, two words
 // at 0), largest |z| = -Phi^-1(2^-32) = 6.23 (truncated mass 4.7e-10 per normal).  The cubic deviates from the exact inverse CDF by at most SVMC_ICDF_MAX_ABS_ERROR (7.431e-10,

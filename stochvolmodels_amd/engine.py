@@ -363,6 +363,21 @@ TILTED_STATS_FIELDS = ("normalizer", "normalizer_stderr", "gamma_forward", "gamm
                        "n_kept", "n_dropped", "sum_weights")
 
 
+# ---- conditional Monte Carlo (include/svmc.h, svmc_cmc_payoff_chain): the per-expiry statistics ----------------------------------
+CMC_STATS_DOUBLES = 5          # SVMC_CMC_STATS_DOUBLES
+CMC_STATS_FIELDS = ("forward_mc", "forward_mc_stderr", "corr", "n_kept", "n_dropped")
+
+
+def cmc_stats_dicts(stats: np.ndarray) -> list:
+    """[m][CMC_STATS_DOUBLES] -> one dict of CMC_STATS_FIELDS per expiry (the counts as ints)"""
+    out = []
+    for row in np.asarray(stats, dtype=np.float64).reshape(-1, CMC_STATS_DOUBLES):
+        d = dict(zip(CMC_STATS_FIELDS, (float(v) for v in row)))
+        d["n_kept"], d["n_dropped"] = int(d["n_kept"]), int(d["n_dropped"])
+        out.append(d)
+    return out
+
+
 def tilted_type_codes(optiontypes) -> np.ndarray:
     """'C' -> 0, 'P' -> 1 as int8; any other type raises ValueError("not implemented"), as the Fourier risk-premia slice pricer"""
     types = np.asarray(optiontypes).ravel()
@@ -460,6 +475,7 @@ class HipEngine:
         self._snap_rows = 0
         self._rand: Optional[DeviceBuffer] = None
         self._factors: Optional[DeviceBuffer] = None   # rough LogSV: [n_factors][n_path]
+        self._cv: Optional[DeviceBuffer] = None        # conditional Monte Carlo: the fourth state array (self.cv)
         self._sums = {}
         self._pinned, self._pinned_doubles = None, 0    # page-locked staging of the small result downloads
         self._bulk = {}                                 # slot -> DeviceBuffer: multi-GB results kept between calls (_bulk_buffer)
@@ -998,6 +1014,109 @@ class HipEngine:
         out = self.download(out_ptr, n_out)
         return tilted_results(out[:G * K], out[G * K:2 * G * K], out[2 * G * K:], ch)
 
+    # ---- conditional Monte Carlo (include/svmc.h, svmc_cmc.hip): the state is (mu, cv, sigma | var, qvar), mu in self.x ---------
+    @property
+    def cv(self) -> DeviceBuffer:
+        """the fourth state array of the conditional generators, allocated on first use"""
+        if self._cv is None:
+            self._cv = DeviceBuffer(self.n_path)
+        return self._cv
+
+    def set_state_cmc(self, mu: np.ndarray, cv: np.ndarray, vol: np.ndarray, qvar: np.ndarray) -> None:
+        self.set_state(mu, vol, qvar)
+        a = np.ascontiguousarray(cv, dtype=np.float64)
+        assert a.shape == (self.n_path,)
+        self.upload(self.cv.ptr, a)
+
+    def get_state_cmc(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        mu, vol, qvar = self.get_state()
+        return mu, self.download(self.cv.ptr, self.n_path), vol, qvar
+
+    def _cmc_rows(self, n: int, mu_row: int, cv_row: int, qvar_row: Optional[int]):
+        self.reserve_snapshots(max(mu_row, cv_row, -1 if qvar_row is None else qvar_row) + n)
+        return (self.snapshot_ptr(mu_row), self.snapshot_ptr(cv_row), None if qvar_row is None else self.snapshot_ptr(qvar_row))
+
+    def logsv_chain_cmc(self, nb_steps: Sequence[int], dts: Sequence[float], etas: Sequence[float], theta, kappa1, kappa2, beta,
+                        volvol, is_spot_measure, seed, call_id, step_offset: int = 0, mu_row: int = 0,
+                        cv_row: Optional[int] = None, qvar_row: Optional[int] = None) -> None:
+        """svmc_logsv_chain_cmc on this engine's (mu, cv, sigma, qvar): expiry i's mu and cv go to snapshot rows mu_row + i and
+        cv_row + i (default: right after the mu rows), its qvar to qvar_row + i when asked"""
+        n = len(nb_steps)
+        cv_row = mu_row + n if cv_row is None else cv_row
+        nb = np.ascontiguousarray(nb_steps, dtype=np.int32)
+        dt, et = np.ascontiguousarray(dts, dtype=np.float64), np.ascontiguousarray(etas, dtype=np.float64)
+        dp = C.POINTER(C.c_double)
+        rows = self._cmc_rows(n, mu_row, cv_row, qvar_row)
+        self._timed("logsv_chain_cmc_kernel", lambda: _lib.check(self.lib.svmc_logsv_chain_cmc(
+            self.x.ptr, self.cv.ptr, self.vol.ptr, self.qvar.ptr, self.n_path, n, nb.ctypes.data_as(C.POINTER(C.c_int)),
+            dt.ctypes.data_as(dp), et.ctypes.data_as(dp), float(theta), float(kappa1), float(kappa2), float(beta), float(volvol),
+            int(bool(is_spot_measure)), int(seed), int(call_id), self.path_offset, int(step_offset), *rows, self.stream)))
+
+    def heston_chain_cmc(self, nb_steps: Sequence[int], dts: Sequence[float], theta, kappa, rho, volvol, seed, call_id,
+                         step_offset: int = 0, mu_row: int = 0, cv_row: Optional[int] = None,
+                         qvar_row: Optional[int] = None) -> None:
+        """svmc_heston_chain_cmc (the reference's Euler step) on this engine's (mu, cv, var, qvar); rows as logsv_chain_cmc"""
+        n = len(nb_steps)
+        cv_row = mu_row + n if cv_row is None else cv_row
+        nb = np.ascontiguousarray(nb_steps, dtype=np.int32)
+        dt = np.ascontiguousarray(dts, dtype=np.float64)
+        rows = self._cmc_rows(n, mu_row, cv_row, qvar_row)
+        self._timed("heston_chain_cmc_kernel", lambda: _lib.check(self.lib.svmc_heston_chain_cmc(
+            self.x.ptr, self.cv.ptr, self.vol.ptr, self.qvar.ptr, self.n_path, n, nb.ctypes.data_as(C.POINTER(C.c_int)),
+            dt.ctypes.data_as(C.POINTER(C.c_double)), float(theta), float(kappa), float(rho), float(volvol), int(seed), int(call_id),
+            self.path_offset, int(step_offset), *rows, self.stream)))
+
+    def conditional_payoffs(self, forwards, discfactors, strikes: Sequence[np.ndarray], codes: Sequence[np.ndarray],
+                            recenter: bool = True, mu_rows: Optional[Sequence[int]] = None,
+                            cv_rows: Optional[Sequence[int]] = None):
+        """the conditional estimator (svmc_cmc_payoff_chain, include/svmc.h) on resident (mu, cv): expiry i reads snapshot rows
+        mu_rows[i] and cv_rows[i], or, with both None, the one expiry reads the current state.  codes: 0 ('C') / 1 ('P') per
+        strike.  Returns (prices [m] -> [K_i], stderrs the same, stats [m] dicts of CMC_STATS_FIELDS)."""
+        ch = marshalled_chain(np.zeros(len(strikes)), forwards, discfactors, strikes, codes)
+        m, K = ch["m"], ch["total"]
+        if (mu_rows is None) != (cv_rows is None) or ((m != 1) if mu_rows is None else (len(mu_rows) != m or len(cv_rows) != m)):
+            raise ValueError("one mu row and one cv row per expiry (the current state serves one expiry)")
+        mus = [self.x.ptr] if mu_rows is None else [self.snapshot_ptr(r) for r in mu_rows]
+        cvs = [self.cv.ptr] if cv_rows is None else [self.snapshot_ptr(r) for r in cv_rows]
+        nbytes = C.c_size_t(0)
+        _lib.check(self.lib.svmc_cmc_payoff_workspace_bytes(self.n_path, m, K, C.byref(nbytes)))
+        ws_ptr, _ = self.alloc_sums((nbytes.value + 7) // 8, "cmc_workspace")
+        res, stats = np.empty((2, max(K, 1))), np.empty((m, CMC_STATS_DOUBLES))
+        dp = C.POINTER(C.c_double)
+        _lib.check(self.lib.svmc_cmc_payoff_chain(
+            (C.c_void_p * m)(*mus), (C.c_void_p * m)(*cvs), self.n_path, ch["forwards"], ch["discfactors"], m, ch["strikes"],
+            ch["codes"], ch["offsets"], int(bool(recenter)), C.cast(res.ctypes.data, dp), C.cast(res.ctypes.data + res.strides[0], dp),
+            stats.ctypes.data_as(dp), ws_ptr, nbytes.value, self.stream))
+        return [res[0, sl] for sl in ch["slices"]], [res[1, sl] for sl in ch["slices"]], cmc_stats_dicts(stats)
+
+    def _fused_cmc_call(self, ch: dict, call, kernel_name: str):
+        res, stats = np.empty((2, max(ch["total"], 1))), np.empty((ch["m"], CMC_STATS_DOUBLES))
+        dp = C.POINTER(C.c_double)
+        self._session_call(ch, lambda sess: call(sess, C.cast(res.ctypes.data, dp), C.cast(res.ctypes.data + res.strides[0], dp),
+                                                 stats.ctypes.data_as(dp)), kernel_name)
+        return [res[0, sl] for sl in ch["slices"]], [res[1, sl] for sl in ch["slices"]], cmc_stats_dicts(stats)
+
+    def price_logsv_chain_cmc_fused(self, ch: dict, v0, theta, kappa1, kappa2, beta, volvol, etas, is_spot_measure,
+                                    nb_steps_per_year, recenter: bool, seed: int, call_id: int):
+        """logsv_mc_chain_pricer_conditional as ONE svmc_logsv_chain_price_cmc call on this engine's state; returns (prices,
+        stderrs, stats) cut into expiries"""
+        etas = np.ascontiguousarray(etas, dtype=np.float64)
+        if etas.size != ch["m"]:
+            raise ValueError("vol_backbone_etas must have one entry per maturity")
+        return self._fused_cmc_call(ch, lambda sess, p, e, st: self.lib.svmc_logsv_chain_price_cmc(
+            sess, ch["ttms"], ch["forwards"], ch["discfactors"], etas.ctypes.data_as(C.POINTER(C.c_double)), ch["m"], ch["strikes"],
+            ch["codes"], ch["offsets"], float(v0), float(theta), float(kappa1), float(kappa2), float(beta), float(volvol),
+            int(bool(is_spot_measure)), int(nb_steps_per_year), int(bool(recenter)), int(seed), int(call_id), p, e, st),
+            "logsv_chain_cmc_kernel")
+
+    def price_heston_chain_cmc_fused(self, ch: dict, v0, theta, kappa, rho, volvol, nb_steps_per_year, recenter: bool, seed: int,
+                                     call_id: int):
+        """heston_mc_chain_pricer_conditional as ONE svmc_heston_chain_price_cmc call on this engine's state"""
+        return self._fused_cmc_call(ch, lambda sess, p, e, st: self.lib.svmc_heston_chain_price_cmc(
+            sess, ch["ttms"], ch["forwards"], ch["discfactors"], ch["m"], ch["strikes"], ch["codes"], ch["offsets"], float(v0),
+            float(theta), float(kappa), float(rho), float(volvol), int(nb_steps_per_year), int(bool(recenter)), int(seed),
+            int(call_id), p, e, st), "heston_chain_cmc_kernel")
+
     def il_payoffs(self, p1, p0, pa, pb, notional=1000000, snap_row: Optional[int] = None, return_pieces: bool = False):
         """the Monte Carlo impermanent loss of the ranges [pa, pb] opened at p0, at the forwards p1, from the resident
         log-returns, whichever generator left them (svmc_il_payoff, include/svmc.h): the current state x, or snapshot row
@@ -1068,7 +1187,7 @@ class HipEngine:
             self.lib.svmc_session_destroy(self._fused)
             self._fused, self._fused_size = None, (0, 0)
         self.__dict__.pop("_comm_bufs", None)       # a communicator's reduction tensors that lived on this engine (dist.TorchComm)
-        for b in (self.x, self.vol, self.qvar, self.ws, self._snap, self._rand, self._factors, *self._sums.values(),
+        for b in (self.x, self.vol, self.qvar, self._cv, self.ws, self._snap, self._rand, self._factors, *self._sums.values(),
                   *self._bulk.values()):
             if b is not None:
                 b.free()

@@ -25,7 +25,7 @@ from ..utils.config import VariableType
 from ..utils.funcs import next_rng_call, set_time_grid, time_grid_steps, timer
 from ..analytic import AnalyticGrid, chain_prices_from_sums, chain_sums
 from ..utils import mgf_pricer as mgfp
-from .logsv_pricer import _broadcast_state
+from .logsv_pricer import _broadcast_state, check_conditional_request
 from .model_pricer import ModelParams, ModelPricer
 
 
@@ -77,6 +77,18 @@ class HestonPricer(ModelPricer):
                                       nb_steps_per_year=kwargs.get("nb_steps_per_year", 360),
                                       seed=kwargs.get("seed"), comm=kwargs.get("comm"), devices=kwargs.get("devices"),
                                       reduce=kwargs.get("reduce"))
+
+    def model_mc_price_chain_conditional(self, option_chain: OptionChain, params: HestonParams, nb_path: int = 100000,
+                                         variable_type: VariableType = VariableType.LOG_RETURN, **kwargs):
+        """model_mc_price_chain by conditional Monte Carlo (heston_mc_chain_pricer_conditional); recenter= and return_stats= are
+        passed on"""
+        return heston_mc_chain_pricer_conditional(
+            v0=params.v0, theta=params.theta, kappa=params.kappa, rho=params.rho, volvol=params.volvol, ttms=option_chain.ttms,
+            forwards=option_chain.forwards, discfactors=option_chain.discfactors, strikes_ttms=option_chain.strikes_ttms,
+            optiontypes_ttms=option_chain.optiontypes_ttms, nb_path=nb_path, variable_type=variable_type,
+            scheme=kwargs.get("scheme", "euler"), nb_steps_per_year=kwargs.get("nb_steps_per_year", 360), seed=kwargs.get("seed"),
+            comm=kwargs.get("comm"), devices=kwargs.get("devices"), recenter=kwargs.get("recenter", True),
+            return_stats=kwargs.get("return_stats", False))
 
     def model_mc_price_chain_many(self, option_chain: OptionChain, params_list: Sequence[HestonParams], nb_path: int = 100000,
                                   variable_type: VariableType = VariableType.LOG_RETURN, seeds: Optional[Sequence[int]] = None,
@@ -273,6 +285,28 @@ def simulate_heston_x_vol_terminal(ttm: float, x0: np.ndarray, var0: np.ndarray,
         w0, w1 = eng.upload_randoms((W0, W1))
         eng.heston_w(W0.shape[0], dt, theta, kappa, rho, volvol, w0, w1)
     return eng.get_state()
+
+
+def heston_mc_chain_pricer_conditional(ttms: np.ndarray, forwards: np.ndarray, discfactors: np.ndarray,
+                                       strikes_ttms: Sequence[np.ndarray], optiontypes_ttms: Sequence[np.ndarray], v0: float,
+                                       theta: float, kappa: float, rho: float, volvol: float, nb_path: int = 100000,
+                                       variable_type: VariableType = VariableType.LOG_RETURN, scheme="euler",
+                                       nb_steps_per_year: int = 360, seed: Optional[int] = None, comm=None, devices=None,
+                                       reduce: Optional[str] = None, recenter: bool = True, return_stats: bool = False):
+    """heston_mc_chain_pricer by CONDITIONAL Monte Carlo (include/svmc.h; see
+    logsv_mc_chain_pricer_conditional): the reference's Euler step with its floor, the variance driven by one normal per step, a
+    Black-76 price per path.  Same signature and (prices, stderrs) lists; return_stats=True adds the per-expiry dicts of
+    engine.CMC_STATS_FIELDS.  scheme="qe" raises NotImplementedError (the QE step's return is not Gaussian given the variance
+    path's driver as written here: a separate step); 'C' / 'P', LOG_RETURN and one GPU only.  Not in the reference API."""
+    codes = check_conditional_request("heston_mc_chain_pricer_conditional", variable_type, comm, devices, optiontypes_ttms)
+    if _scheme_code(scheme) != HESTON_EULER_FLOOR:
+        raise NotImplementedError("heston_mc_chain_pricer_conditional: scheme='qe' is not covered (Euler only)")
+    rng_seed, call_id = next_rng_call(seed)
+    ch = marshalled_chain(ttms, forwards, discfactors, strikes_ttms, codes)
+    prices, stderrs, stats = get_engine(nb_path).price_heston_chain_cmc_fused(ch, v0, theta, kappa, rho, volvol, nb_steps_per_year,
+                                                                               recenter, rng_seed, call_id)
+    out = (chain_shaped(prices, strikes_ttms), chain_shaped(stderrs, strikes_ttms))
+    return out + (stats,) if return_stats else out
 
 
 def heston_mc_chain_pricer(ttms: np.ndarray, forwards: np.ndarray, discfactors: np.ndarray,

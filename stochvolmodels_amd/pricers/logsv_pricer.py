@@ -19,7 +19,7 @@ import pandas as pd
 
 from .. import dist as svdist
 from ..data.option_chain import OptionChain
-from ..engine import DeviceRandoms, get_engine, marshalled_chain, option_type_codes, payoff_finalize
+from ..engine import DeviceRandoms, get_engine, marshalled_chain, option_type_codes, payoff_finalize, tilted_type_codes
 from ..mc_chain import (chain_shaped, check_many_args, many_job_chunks, many_job_streams, many_jobs_shaped, price_chain_on_engine,
                         variable_type_code)
 from ..utils.calibration import ImpliedVolObjective, chain_calibration_weights, minimize_slsqp
@@ -239,6 +239,20 @@ class LogSVPricer(ModelPricer):
                                      nb_steps_per_year=nb_steps or int(360 * np.max(option_chain.ttms)) + 1,
                                      seed=kwargs.get("seed"), comm=kwargs.get("comm"), devices=kwargs.get("devices"),
                                      reduce=kwargs.get("reduce"))
+
+    def model_mc_price_chain_conditional(self, option_chain: OptionChain, params: LogSvParams, is_spot_measure: bool = True,
+                                         variable_type: VariableType = VariableType.LOG_RETURN, nb_path: int = 100000,
+                                         nb_steps: Optional[int] = None, **kwargs):
+        """model_mc_price_chain by conditional Monte Carlo (logsv_mc_chain_pricer_conditional) on the same step rule;
+        recenter= and return_stats= are passed on"""
+        etas = params.get_vol_backbone_etas(ttms=option_chain.ttms)
+        return logsv_mc_chain_pricer_conditional(
+            v0=params.sigma0, theta=params.theta, kappa1=params.kappa1, kappa2=params.kappa2, beta=params.beta, volvol=params.volvol,
+            vol_backbone_etas=etas, ttms=option_chain.ttms, forwards=option_chain.forwards, discfactors=option_chain.discfactors,
+            strikes_ttms=option_chain.strikes_ttms, optiontypes_ttms=option_chain.optiontypes_ttms, is_spot_measure=is_spot_measure,
+            variable_type=variable_type, nb_path=nb_path, nb_steps_per_year=nb_steps or int(360 * np.max(option_chain.ttms)) + 1,
+            seed=kwargs.get("seed"), comm=kwargs.get("comm"), devices=kwargs.get("devices"),
+            recenter=kwargs.get("recenter", True), return_stats=kwargs.get("return_stats", False))
 
     def model_mc_price_chain_many(self, option_chain: OptionChain, params_list: Sequence[LogSvParams],
                                   is_spot_measure: bool = True, variable_type: VariableType = VariableType.LOG_RETURN,
@@ -810,6 +824,44 @@ def logsv_mc_chain_pricer(ttms: np.ndarray, forwards: np.ndarray, discfactors: n
     return _logsv_mc_chain_on_grids(grids, rng_seed, call_id, comm, ttms, forwards, discfactors, strikes_ttms, optiontypes_ttms,
                                     v0, theta, kappa1, kappa2, beta, volvol, vol_backbone_etas, is_spot_measure, nb_path,
                                     variable_type)
+
+
+def check_conditional_request(who: str, variable_type, comm, devices, optiontypes_ttms, is_spot_measure: bool = True) -> list:
+    """the requests the conditional Monte Carlo pricers refuse, before any device work (each a separate step):
+    'IC' / 'IP' (ValueError("not implemented")), another variable than LOG_RETURN, the inverse measure, sharded paths.  Returns
+    the per-expiry type codes."""
+    codes = [tilted_type_codes(t) for t in optiontypes_ttms]                # ValueError("not implemented")
+    if variable_type_code(variable_type) != 1:
+        raise NotImplementedError(f"{who}: variable_type={variable_type}: the conditional estimator prices the log-return only")
+    if not is_spot_measure:
+        raise NotImplementedError(f"{who}: is_spot_measure=False: the conditional estimator covers the spot measure")
+    if devices is not None or (comm or svdist.get_default_comm()).world > 1:
+        raise NotImplementedError(f"{who}: sharded paths (comm.world > 1, devices=) are not covered")
+    return codes
+
+
+def logsv_mc_chain_pricer_conditional(ttms: np.ndarray, forwards: np.ndarray, discfactors: np.ndarray,
+                                      strikes_ttms: Sequence[np.ndarray], optiontypes_ttms: Sequence[np.ndarray], v0: float,
+                                      theta: float, kappa1: float, kappa2: float, beta: float, volvol: float,
+                                      vol_backbone_etas: np.ndarray, is_spot_measure: bool = True, nb_path: int = 100000,
+                                      nb_steps_per_year: int = 360, variable_type: VariableType = VariableType.LOG_RETURN,
+                                      seed: Optional[int] = None, comm=None, devices=None, reduce: Optional[str] = None,
+                                      recenter: bool = True, return_stats: bool = False):
+    """logsv_mc_chain_pricer by CONDITIONAL Monte Carlo (include/svmc.h): given the path of the volatility's
+    driver the discretised log-return is Gaussian, so each path contributes a Black-76 price instead of a payoff -- the same
+    expectation for the same discretised model, a smaller variance, one normal per step (random stream 8, not the plain pricer's:
+    the two are independent estimates at equal seeds).  Same signature and (prices, stderrs) lists; return_stats=True adds per
+    expiry the dict of engine.CMC_STATS_FIELDS (forward_mc = mean F_c, its standard error, corr, n_kept, n_dropped).
+    recenter=False prices against the unrecentred strikes.  'C' / 'P', LOG_RETURN, the spot measure and one GPU only
+    (check_conditional_request).  Not in the reference API."""
+    codes = check_conditional_request("logsv_mc_chain_pricer_conditional", variable_type, comm, devices, optiontypes_ttms,
+                                      is_spot_measure)
+    rng_seed, call_id = next_rng_call(seed)
+    ch = marshalled_chain(ttms, forwards, discfactors, strikes_ttms, codes)
+    prices, stderrs, stats = get_engine(nb_path).price_logsv_chain_cmc_fused(
+        ch, v0, theta, kappa1, kappa2, beta, volvol, vol_backbone_etas, is_spot_measure, nb_steps_per_year, recenter, rng_seed, call_id)
+    out = (chain_shaped(prices, strikes_ttms), chain_shaped(stderrs, strikes_ttms))
+    return out + (stats,) if return_stats else out
 
 
 def logsv_mc_chain_pricer_many(params_list: Sequence[LogSvParams], ttms: np.ndarray, forwards: np.ndarray,

@@ -64,3 +64,27 @@ def compute_mc_vars_payoff_with_gamma(x0: np.ndarray, forward: float, strikes_tt
     if return_stats:
         return prices[0][0], stderrs[0][0], tilted_stats_dicts(stats[0])[0]
     return prices[0][0], stderrs[0][0]
+
+
+def compute_mc_vars_payoff_conditional(mu: np.ndarray, cv: np.ndarray, ttm: float, forward: float, strikes_ttm: np.ndarray,
+                                       optiontypes_ttm: np.ndarray, discfactor: float = 1.0, recenter: bool = True,
+                                       return_stats: bool = False):
+    """option prices by conditional Monte Carlo from per-path conditional means and variances of the log-return (host arrays), the
+    estimator of include/svmc.h's svmc_cmc_payoff_chain: a path is kept iff mu, cv and exp(mu + cv / 2) are finite and cv >= 0;
+    per kept path the Black-76 price of F_c = forward exp(mu + cv / 2) against K + corr at total variance cv, corr =
+    mean_kept(F_c) - forward (0 with recenter=False); price = discfactor x mean, error = discfactor x population deviation /
+    sqrt(n_path).  ttm is accepted for signature symmetry with compute_mc_vars_payoff and unused (cv is a TOTAL variance).  'C' /
+    'P' only (others: ValueError("not implemented")).  Returns (prices, stderrs) in the strikes' shape, and with
+    return_stats=True the dict of engine.CMC_STATS_FIELDS as a third item."""
+    codes = tilted_type_codes(optiontypes_ttm)                   # ValueError("not implemented")
+    strikes = np.asarray(strikes_ttm, dtype=np.float64)
+    mu = np.ascontiguousarray(mu, dtype=np.float64).ravel()
+    cv = np.ascontiguousarray(cv, dtype=np.float64).ravel()
+    if mu.size != cv.size or mu.size == 0:
+        raise ValueError("mu and cv must be non-empty and of one length")
+    eng = get_engine(mu.size)
+    eng.upload(eng.x.ptr, mu)
+    eng.upload(eng.cv.ptr, cv)
+    prices, stderrs, stats = eng.conditional_payoffs([float(forward)], [float(discfactor)], [strikes.ravel()], [codes], bool(recenter))
+    out = (prices[0].reshape(strikes.shape), stderrs[0].reshape(strikes.shape))
+    return out + (stats[0],) if return_stats else out
