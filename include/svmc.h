@@ -942,6 +942,76 @@ SVMC_API int svmc_heston_chain_price_cmc(svmc_session_t session, const double *t
                                          double kappa, double rho, double volvol, int nb_steps_per_year, int recenter, uint64_t seed,
                                          uint32_t call_id, double *prices_host, double *stderrs_host, double *stats_host);
 
+/* ---- Monte Carlo chain Greeks on common random numbers, LogSV and Heston (src svmc_greeks.hip, svmc_chain.hip) ----
+ * One base job and, per requested parameter p with step h_p, a pair of jobs at theta_p + h_p (up) and theta_p - h_p (dn), all on
+ * ONE random stream (the many-jobs block above: jobs of one (seed, call id) see the same draws and each is bit-equal to its single
+ * call).  SVMC_CALL / SVMC_PUT on the log-return only.  Per expiry with forward F and discount factor DF, job j with terminal
+ * log-returns x and reduced spot sums [sum F exp(x), count] over the paths where F exp(x) is not NaN:
+ *   M_j = (sum / count) / F, the kept-path mean of exp(x);   e = (exp(x) - M_j) + 1;   spot = F e
+ * -- compute_mc_vars_payoff's recentring F exp(x) - (mean - F) in its homogeneous form (it differs by rounding).  s = +1 for a
+ * call, -1 for a put; pay = max(s (spot - K), 0), NaN where the spot is NaN.
+ *   PRICE, STDERR of the base job: svmc_*_chain_price's own tail on job 0, bit-equal to the single call at the same seed.
+ *   FORWARD DELTA (pathwise): g = s e 1{s (spot - K) > 0}; delta = DF mean(g), the exact derivative in F of the estimator the plain
+ *     pricer computes (M does not depend on F); error = DF x population deviation of g / sqrt(n_path).  Means over ALL n_path paths:
+ *     a path whose spot is NaN is out of the money (g = 0), as the plain payoff counts it.  The sums are taken of g - shift, shift =
+ *     s 1{s (F - K) > 0}, g at the forward.
+ *   DUAL DELTA: dual_delta = -s DF n_itm / n_path, n_itm the count of 1{s (spot - K) > 0}; error DF sqrt(q (1 - q) / n_path), q =
+ *     n_itm / n_path (binomial).  The indicator is STRICT: a tie spot == K has payoff 0 and indicator 0.  By construction
+ *     price = F delta + K dual_delta up to rounding.
+ *   SENSITIVITY to parameter p: d = pay(x_up) - pay(x_dn) per path, each job recentred by its own M; KEEP RULE: a pair is kept iff
+ *     both payoffs are not NaN; sens_p = DF mean_pairs(d) / (2 h_p); n_pairs is returned.  No kept pair is not an error: 0/0 = NaN
+ *     and n_pairs says so.  ERROR: DF x population deviation over the pairs of dt / sqrt(n_path) / (2 h_p), dt = d - s (q_up
+ *     (spot_up - F) - q_dn (spot_dn - F)), q_up / q_dn = n_itm / n_path of the up / dn job.  M_up and M_dn are sample means and a
+ *     payoff moves by -s F 1{in the money} per unit of its M: dt is d with that delta-method term (its mean is 0 when every path
+ *     is kept), without which the deviation of d misstates the error of the difference wherever paths end in the money -- an
+ *     in-the-money call's several times over.
+ * Left out: gamma (on this estimator a density estimate at the strike: a step for the conditional estimator), SVMC_INV_CALL /
+ * SVMC_INV_PUT, variables other than the log-return, the inverse measure's payoffs, Hawkes, sharded sessions.
+ *   svmc_greeks_payoff_chain   model-agnostic, on any device arrays: base_rows_host [n_expiries], up_rows_host / dn_rows_host
+ *                              [n_params][n_expiries] HOST arrays of DEVICE pointers ([n_path] each); spot_sums: device
+ *                              [1 + 2 n_params][n_expiries][2], the jobs in the order base, up_0, dn_0, up_1, ...; steps_host
+ *                              [n_params] positive and finite.  greeks_host [SVMC_GREEKS_BASE_ROWS][K] = {delta, its error,
+ *                              dual delta, its error, n_itm}, sens_host [n_params][SVMC_GREEKS_SENS_ROWS][K] = {sens, its error,
+ *                              n_pairs} (counts as doubles; K = sum K_i).  One upload of the table, four launches on `stream`
+ *                              (greeks_payoff_kernel: path blocks x groups of up to SVMC_GREEKS_KT strikes of one expiry, and
+ *                              greeks_finish_kernel, over the 1 + 2 n_params jobs -- the deltas and every job's q; then the
+ *                              same two over the n_params pairs), the downloads, one synchronize.  Every sum has a fixed
+ *                              order that depends on n_path alone (path blocks: min(ceil(n_path / 256), 1024)): a quote's numbers
+ *                              are the same bits whichever other strikes, expiries or bump pairs share the call.  `workspace`:
+ *                              device memory of svmc_greeks_payoff_workspace_bytes(n_path, n_expiries, K, n_params).
+ *   svmc_logsv_chain_price_greeks / svmc_heston_chain_price_greeks   the many-job stepping launch with the 1 + 2 n_params rows of
+ *                              params_host (rows as svmc_*_chain_price_many: base, then up, dn per parameter; all on `seed` and
+ *                              `call_id`), then the plain tail on job 0 and the tail above on the session's stream, the values
+ *                              stored by the finish kernels in page-locked memory, ONE synchronize.  Session and workspace as
+ *                              the many-job calls; later single calls are undisturbed.  sens_host may be NULL at n_params = 0.
+ * Everything is checked before anything is launched: SVMC_ERR_INVALID_ARGUMENT for a null pointer, n_path < 1, n_expiries < 1 (the
+ * fused calls: outside [1, 16]), n_params outside 0 .. SVMC_GREEKS_MAX_PARAMS, a step that is not positive and finite, a forward
+ * that is not positive and finite, a discount factor or strike that is not finite, a sharded session; SVMC_ERR_UNKNOWN_PAYOFF for
+ * a type code other than SVMC_CALL / SVMC_PUT; SVMC_ERR_WORKSPACE for a workspace (a session) too small. */
+#define SVMC_GREEKS_KT 8
+#define SVMC_GREEKS_MAX_PARAMS 31
+#define SVMC_GREEKS_BASE_ROWS 5
+#define SVMC_GREEKS_SENS_ROWS 3
+SVMC_API int svmc_greeks_payoff_workspace_bytes(size_t n_path, int n_expiries, size_t total_strikes, int n_params, size_t *bytes);
+SVMC_API int svmc_greeks_payoff_chain(const double *const *base_rows_host, const double *const *up_rows_host,
+                                      const double *const *dn_rows_host, size_t n_path, const double *forwards_host,
+                                      const double *discfactors_host, int n_expiries, const double *strikes_host,
+                                      const int8_t *types_host, const size_t *strike_offsets_host, int n_params,
+                                      const double *steps_host, const double *spot_sums, double *greeks_host, double *sens_host,
+                                      void *workspace, size_t workspace_bytes, svmc_stream_t stream);
+SVMC_API int svmc_logsv_chain_price_greeks(svmc_session_t session, const double *ttms_host, const double *forwards_host,
+                                           const double *discfactors_host, int n_expiries, const double *strikes_host,
+                                           const int8_t *types_host, const size_t *strike_offsets_host, int n_params,
+                                           const double *params_host, const double *steps_host, int is_spot_measure,
+                                           int nb_steps_per_year, uint64_t seed, uint32_t call_id, double *prices_host,
+                                           double *stderrs_host, double *greeks_host, double *sens_host);
+SVMC_API int svmc_heston_chain_price_greeks(svmc_session_t session, const double *ttms_host, const double *forwards_host,
+                                            const double *discfactors_host, int n_expiries, const double *strikes_host,
+                                            const int8_t *types_host, const size_t *strike_offsets_host, int n_params,
+                                            const double *params_host, const double *steps_host, int scheme, int nb_steps_per_year,
+                                            uint64_t seed, uint32_t call_id, double *prices_host, double *stderrs_host,
+                                            double *greeks_host, double *sens_host);
+
 #ifdef __cplusplus
 }
 #endif

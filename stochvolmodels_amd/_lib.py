@@ -185,6 +185,13 @@ def _declare(L: C.CDLL) -> None:
                                          pf64, pf64], i32),
         "svmc_hawkesjd_chain_price_tilted": ([vp, pf64, pf64, i32, pf64, pi8, psz, pf64, i32, u64, u32, pf64, i32, i32, pf64, pf64,
                                               pf64], i32),
+        "svmc_greeks_payoff_workspace_bytes": ([sz, i32, sz, i32, psz], i32),
+        "svmc_greeks_payoff_chain": ([C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), sz, pf64, pf64, i32, pf64, pi8, psz, i32, pf64, vp,
+                                      pf64, pf64, vp, sz, vp], i32),
+        "svmc_logsv_chain_price_greeks": ([vp, pf64, pf64, pf64, i32, pf64, pi8, psz, i32, pf64, pf64, i32, i32, u64, u32, pf64, pf64,
+                                           pf64, pf64], i32),
+        "svmc_heston_chain_price_greeks": ([vp, pf64, pf64, pf64, i32, pf64, pi8, psz, i32, pf64, pf64, i32, i32, u64, u32, pf64, pf64,
+                                            pf64, pf64], i32),
     }
     for name, (argtypes, restype) in sig.items():
         if os.environ.get("SVMC_ALLOW_OLD_ABI") == "1" and not hasattr(L, name):

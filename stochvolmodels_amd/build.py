@@ -30,7 +30,7 @@ ISA_KERNELS = ("logsv_rng_kernel", "logsv_chain_rng_kernel", "heston_rng_kernelI
                "logsv_rng_lat_kernelILi4ELi4ELi256", "logsv_chain_rng_lat_kernelILi4ELi4ELi256", "hawkesjd_chain_rng_kernel",
                "logsv_chain_cmc_kernel", "heston_chain_cmc_kernel")
 SOURCES = ("svmc_runtime.hip", "svmc_kernels.hip", "svmc_heston.hip", "svmc_rough.hip", "svmc_analytic.hip", "svmc_chain.hip",
-           "svmc_comm.hip", "svmc_multi.hip", "svmc_hawkes.hip", "svmc_density.hip", "svmc_cmc.hip")
+           "svmc_comm.hip", "svmc_multi.hip", "svmc_hawkes.hip", "svmc_density.hip", "svmc_cmc.hip", "svmc_greeks.hip")
 ASM_GLOB = "*-hip-amdgcn-amd-amdhsa-gfx950.s"       # the device assembly --save-temps leaves, one file per unit
 ARCH = "gfx950"
 # the test-only device build of the math, complex and Black-76 helpers (tests/test_gpu_device_math.py): not part of the

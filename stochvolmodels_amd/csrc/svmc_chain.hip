@@ -88,6 +88,9 @@ struct Session {
     double *cmc_cv = nullptr;
     void *cmc_ws = nullptr, *cmc_pinned = nullptr;          // device, device, pinned (the chain table's image and the results)
     size_t cmc_cv_bytes = 0, cmc_ws_bytes = 0, cmc_pinned_bytes = 0;
+    // svmc_*_chain_price_greeks: the Greeks tail's workspace and its page-locked block (the table's image, then the results)
+    void *greeks_ws = nullptr, *greeks_pinned = nullptr;   // device, pinned
+    size_t greeks_ws_bytes = 0, greeks_pinned_bytes = 0;
 };
 
 // events around a stepping call of a timed session (no-ops otherwise)
@@ -139,6 +142,8 @@ static void session_release(Session *s)
     if (s->cmc_cv != nullptr) (void)hipFree(s->cmc_cv);
     if (s->cmc_ws != nullptr) (void)hipFree(s->cmc_ws);
     if (s->cmc_pinned != nullptr) (void)hipHostFree(s->cmc_pinned);
+    if (s->greeks_ws != nullptr) (void)hipFree(s->greeks_ws);
+    if (s->greeks_pinned != nullptr) (void)hipHostFree(s->greeks_pinned);
     ManyBuffers &mb = s->many;
     for (void *p : {static_cast<void *>(mb.snap), static_cast<void *>(mb.spot_ws), static_cast<void *>(mb.spot),
                     static_cast<void *>(mb.sums), mb.ws, mb.table_dev})
@@ -1236,6 +1241,105 @@ static auto hawkes_many_stepper(Session *s, const ChainView &c, int n_jobs, cons
                                      mb.table_host, mb.table_dev, mb.snap, mb.spot_ws, s->stream);
     };
 }
+
+// ---- Monte Carlo chain Greeks (include/svmc.h; the tail: svmc_greeks.hip): many_step with the 1 + 2P rows of `params` on one
+// (seed, call id) -- step(nbs, dts, seeds, call_ids) is the model's many-job launch --, then job 0's plain tail -- the launches the many-job driver gives a job, hence the single call's bits -- and
+// the Greeks tail on the jobs' rows and spot sums, everything on the session's stream and one synchronise.
+template <class Step>
+static int chain_price_greeks(const char *fn, Session *s, const ChainView &c, int n_params, const double *params, const double *steps,
+                              int nb_steps_per_year, uint64_t seed, uint32_t call_id, double *prices, double *stderrs, double *greeks,
+                              double *sens, Step &&step)
+{
+    SVMC_REQUIRE(n_params >= 0 && n_params <= SVMC_GREEKS_MAX_PARAMS, std::string(fn) + ": n_params must be in [0, SVMC_GREEKS_MAX_PARAMS]");
+    SVMC_REQUIRE(greeks != nullptr && (n_params == 0 || sens != nullptr), std::string(fn) + ": null pointer");
+    const int P = n_params, J = 1 + 2 * P;
+    const std::vector<uint64_t> seeds(J, seed);
+    const std::vector<uint32_t> call_ids(J, call_id);
+    std::vector<double> shifts;
+    size_t image_bytes = 0;
+    if (int rc = many_step(fn, s, c, J, params, seeds.data(), call_ids.data(), nb_steps_per_year, SVMC_LOG_RETURN, prices, stderrs, true, 0,
+                           shifts,
+                           [&]() -> int {
+        if (int rc = greeks_check(fn, s->n_path, c.forwards, c.discfactors, c.m, c.strikes, c.types, c.offsets, P, steps)) return rc;
+        const size_t K = c.offsets[c.m];
+        image_bytes = greeks_payoff_image_bytes_of(c.m, K, P);
+        SVMC_HIP_TRY(grow(&s->greeks_ws, s->greeks_ws_bytes, greeks_payoff_workspace_bytes_of(s->n_path, c.m, K, P), false));
+        SVMC_HIP_TRY(grow(&s->greeks_pinned, s->greeks_pinned_bytes,
+                          image_bytes + (SVMC_GREEKS_BASE_ROWS + static_cast<size_t>(SVMC_GREEKS_SENS_ROWS) * P) * (K > 0 ? K : 1) * sizeof(double),
+                          true));
+        return SVMC_OK;
+    },
+                           [&](const std::vector<int> &nbs, const std::vector<double> &dts, double *) {
+        return step(nbs, dts, seeds.data(), call_ids.data());
+    }))
+        return rc;
+    const size_t n = s->n_path, m = static_cast<size_t>(c.m), K = c.offsets[c.m];
+    ManyBuffers &mb = s->many;
+    std::vector<const double *> rows(static_cast<size_t>(J) * m);
+    for (size_t r = 0; r < rows.size(); ++r) rows[r] = mb.snap + r * n;
+    if (payoff_sets_fit(n, c.m, c.offsets, c.types, 1, mb.ws_bytes)) {
+        if (int rc = chain_payoff_and_finish_sets(rows.data(), nullptr, n, c.forwards, c.ttms, mb.spot, c.m, c.strikes, c.types, shifts.data(),
+                                                  c.offsets, SVMC_LOG_RETURN, mb.ws, mb.ws_bytes, s->stream, 1, m * n, m * n, 2 * m, mb.sums,
+                                                  mb.sums_pinned))
+            return rc;
+    } else {
+        if (int rc = svmc_payoff_sums_chain(rows.data(), nullptr, n, c.forwards, c.ttms, mb.spot, c.m, c.strikes, c.types, shifts.data(),
+                                            c.offsets, SVMC_LOG_RETURN, mb.sums, mb.ws, mb.ws_bytes, reinterpret_cast<svmc_stream_t>(s->stream)))
+            return rc;
+        SVMC_HIP_TRY(hipMemcpyAsync(mb.sums_pinned, mb.sums, 3 * K * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    }
+    double *base_out = reinterpret_cast<double *>(static_cast<unsigned char *>(s->greeks_pinned) + image_bytes);
+    double *sens_out = base_out + SVMC_GREEKS_BASE_ROWS * K;
+    if (int rc = greeks_payoff_enqueue(fn, rows.data(), n, c.forwards, c.discfactors, c.m, c.strikes, c.types, c.offsets, P, steps, mb.spot,
+                                       base_out, sens_out, s->greeks_pinned, s->greeks_ws, s->greeks_ws_bytes, s->stream, nullptr))
+        return rc;
+    SVMC_HIP_TRY(hipStreamSynchronize(s->stream));
+    stepping_read(s);
+    memcpy(greeks, base_out, SVMC_GREEKS_BASE_ROWS * K * sizeof(double));
+    if (P > 0) memcpy(sens, sens_out, static_cast<size_t>(SVMC_GREEKS_SENS_ROWS) * P * K * sizeof(double));
+    return finish_sets(s, c, mb.sums_pinned, shifts, 1, SVMC_LOG_RETURN, prices, stderrs, nullptr, nullptr);
+}
+
+extern "C" {
+
+int svmc_logsv_chain_price_greeks(svmc_session_t session, const double *ttms_host, const double *forwards_host,
+                                  const double *discfactors_host, int n_expiries, const double *strikes_host, const int8_t *types_host,
+                                  const size_t *strike_offsets_host, int n_params, const double *params_host, const double *steps_host,
+                                  int is_spot_measure, int nb_steps_per_year, uint64_t seed, uint32_t call_id, double *prices_host,
+                                  double *stderrs_host, double *greeks_host, double *sens_host)
+{
+    const ChainView c = {n_expiries, ttms_host, forwards_host, discfactors_host, strikes_host, types_host, strike_offsets_host};
+    Session *s = reinterpret_cast<Session *>(session);
+    const int n_jobs = 1 + 2 * n_params;
+    return chain_price_greeks("svmc_logsv_chain_price_greeks", s, c, n_params, params_host, steps_host, nb_steps_per_year, seed, call_id,
+                              prices_host, stderrs_host, greeks_host, sens_host,
+                              [&](const std::vector<int> &nbs, const std::vector<double> &dts, const uint64_t *seeds, const uint32_t *call_ids) {
+        ManyBuffers &mb = s->many;
+        return logsv_chain_rng_many(s->n_path, n_jobs, c.m, nbs.data(), dts.data(), c.forwards, params_host, is_spot_measure, seeds, call_ids,
+                                    s->path_offset, mb.table_host, mb.table_dev, mb.snap, nullptr, mb.spot_ws, s->stream);
+    });
+}
+
+int svmc_heston_chain_price_greeks(svmc_session_t session, const double *ttms_host, const double *forwards_host,
+                                   const double *discfactors_host, int n_expiries, const double *strikes_host, const int8_t *types_host,
+                                   const size_t *strike_offsets_host, int n_params, const double *params_host, const double *steps_host,
+                                   int scheme, int nb_steps_per_year, uint64_t seed, uint32_t call_id, double *prices_host,
+                                   double *stderrs_host, double *greeks_host, double *sens_host)
+{
+    const ChainView c = {n_expiries, ttms_host, forwards_host, discfactors_host, strikes_host, types_host, strike_offsets_host};
+    Session *s = reinterpret_cast<Session *>(session);
+    SVMC_REQUIRE(scheme == SVMC_HESTON_EULER_FLOOR || scheme == SVMC_HESTON_QE, "svmc_heston_chain_price_greeks: unknown scheme");
+    const int n_jobs = 1 + 2 * n_params;
+    return chain_price_greeks("svmc_heston_chain_price_greeks", s, c, n_params, params_host, steps_host, nb_steps_per_year, seed, call_id,
+                              prices_host, stderrs_host, greeks_host, sens_host,
+                              [&](const std::vector<int> &nbs, const std::vector<double> &dts, const uint64_t *seeds, const uint32_t *call_ids) {
+        ManyBuffers &mb = s->many;
+        return heston_chain_rng_many(s->n_path, n_jobs, c.m, nbs.data(), dts.data(), c.forwards, params_host, scheme, seeds, call_ids,
+                                     s->path_offset, mb.table_host, mb.table_dev, mb.snap, nullptr, mb.spot_ws, s->stream);
+    });
+}
+
+}  // extern "C"
 
 extern "C" {
 

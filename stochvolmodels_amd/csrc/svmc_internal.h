@@ -144,6 +144,19 @@ int cmc_payoff_chain(const char *fn, const double *const *mu_snapshots_host, con
                      const int8_t *types_host, const size_t *strike_offsets_host, int recenter, double *prices_host, double *stderrs_host,
                      double *stats_host, void *workspace, size_t workspace_bytes, hipStream_t stream, void *pinned, size_t pinned_bytes);
 size_t cmc_payoff_pinned_bytes_of(int n_expiries, size_t total_strikes);
+// svmc_greeks.hip: the Greeks tail (svmc_greeks_payoff_chain's body) -- its checks, the two launches queued on `stream` from a host
+// image the caller keeps until the stream has passed the upload (rows_host [1 + 2P][m] job-major; base_out / sens_out device or
+// pinned, null: inside the workspace at *results_dev), and the sizes of the workspace and the image
+int greeks_check(const char *fn, size_t n_path, const double *forwards_host, const double *discfactors_host, int n_expiries,
+                 const double *strikes_host, const int8_t *types_host, const size_t *strike_offsets_host, int n_params,
+                 const double *steps_host);
+int greeks_payoff_enqueue(const char *fn, const double *const *rows_host, size_t n_path, const double *forwards_host,
+                          const double *discfactors_host, int n_expiries, const double *strikes_host, const int8_t *types_host,
+                          const size_t *strike_offsets_host, int n_params, const double *steps_host, const double *spot_sums,
+                          double *base_out, double *sens_out, void *image, void *workspace, size_t workspace_bytes, hipStream_t stream,
+                          double **results_dev);
+size_t greeks_payoff_workspace_bytes_of(size_t n_path, int n_expiries, size_t total_strikes, int n_params);
+size_t greeks_payoff_image_bytes_of(int n_expiries, size_t total_strikes, int n_params);
 size_t payoff_sets_workspace_bytes(size_t n_path, size_t total_strikes, int n_sets);
 int chain_payoff_and_finish_sets(const double *const *x_snapshots_host, const double *const *qvar_snapshots_host, size_t n_path,
                                  const double *forwards_host, const double *ttms_host, const double *spot_sums, int n_expiries,

@@ -444,6 +444,12 @@ def tilted_stats_dicts(stats: np.ndarray) -> list:
     return [{k: (int(v) if k in ("n_kept", "n_dropped") else float(v)) for k, v in zip(TILTED_STATS_FIELDS, row)} for row in stats]
 
 
+# ---- Monte Carlo chain Greeks (include/svmc.h, svmc_greeks_payoff_chain): the rows of the two result blocks ----------------------
+GREEKS_MAX_PARAMS = 31         # SVMC_GREEKS_MAX_PARAMS
+GREEKS_BASE_FIELDS = ("delta", "delta_stderr", "dual_delta", "dual_delta_stderr", "n_itm")    # SVMC_GREEKS_BASE_ROWS
+GREEKS_SENS_FIELDS = ("sens", "sens_stderr", "n_pairs")                                       # SVMC_GREEKS_SENS_ROWS
+
+
 MANY_MAX_JOBS = 64             # jobs per svmc_*_chain_price_many call: SVMC_MANY_MAX_JOBS of include/svmc.h
 BULK_KEEP_FRACTION = 0.125     # of the device's memory: what an engine's cached bulk buffers may hold between calls (trim_bulk)
 
@@ -1116,6 +1122,83 @@ class HipEngine:
             sess, ch["ttms"], ch["forwards"], ch["discfactors"], ch["m"], ch["strikes"], ch["codes"], ch["offsets"], float(v0),
             float(theta), float(kappa), float(rho), float(volvol), int(nb_steps_per_year), int(bool(recenter)), int(seed),
             int(call_id), p, e, st), "heston_chain_cmc_kernel")
+
+    # ---- Monte Carlo chain Greeks on common random numbers (include/svmc.h, svmc_greeks.hip) ------------------------------------
+    def greeks_payoffs(self, forwards, discfactors, strikes: Sequence[np.ndarray], codes: Sequence[np.ndarray], steps=(),
+                       base_rows: Optional[Sequence[int]] = None, up_rows: Optional[Sequence[Sequence[int]]] = None,
+                       dn_rows: Optional[Sequence[Sequence[int]]] = None, host_rows=None) -> dict:
+        """the Greeks tail (svmc_greeks_payoff_chain) on resident log-returns: expiry i of the base job reads snapshot row
+        base_rows[i], of parameter p's bumped jobs rows up_rows[p][i] and dn_rows[p][i]; steps: the P step sizes h_p.  host_rows =
+        (base [m], up [P][m], dn [P][m]) host arrays instead: uploaded to snapshot rows 0 .. (1 + 2P) m - 1 in job order (base, up_0,
+        dn_0, ...).  Each job's spot sums are formed on the device (svmc_spot_sums).  codes: 0 ('C') / 1 ('P') per strike.  Returns
+        {field: [m] -> [K_i]} for delta, delta_stderr, dual_delta, dual_delta_stderr, n_itm; "sens", "sens_stderr", "n_pairs":
+        [P][m] -> [K_i]; "spot_sums": [1 + 2P, m, 2], the jobs' [sum F exp(x), count]."""
+        ch = marshalled_chain(np.zeros(len(strikes)), forwards, discfactors, strikes, codes)
+        m, K = ch["m"], ch["total"]
+        h = np.ascontiguousarray(np.atleast_1d(np.asarray(steps, dtype=np.float64))).ravel()
+        P = h.size
+        if host_rows is not None:
+            base, up, dn = host_rows
+            jobs = [list(base)] + [job for p in range(P) for job in (list(up[p]), list(dn[p]))]
+            if len(jobs) != 1 + 2 * P or any(len(job) != m for job in jobs):
+                raise ValueError("one host array per expiry for the base job and for each up / dn job of the P steps")
+            self.reserve_snapshots((1 + 2 * P) * m)
+            for j, job in enumerate(jobs):
+                for i, x in enumerate(job):
+                    a = np.ascontiguousarray(x, dtype=np.float64)
+                    if a.shape != (self.n_path,):
+                        raise ValueError("a host row must hold one value per path of the engine")
+                    self.upload(self.snapshot_ptr(j * m + i), a)
+            base_rows = list(range(m))
+            up_rows = [list(range((1 + 2 * p) * m, (2 + 2 * p) * m)) for p in range(P)]
+            dn_rows = [list(range((2 + 2 * p) * m, (3 + 2 * p) * m)) for p in range(P)]
+        up_rows, dn_rows = list(up_rows or []), list(dn_rows or [])
+        if base_rows is None or len(base_rows) != m or len(up_rows) != P or len(dn_rows) != P or \
+                any(len(r) != m for r in up_rows + dn_rows):
+            raise ValueError("one snapshot row per expiry for the base job and for each up / dn job of the P steps")
+        job_rows = [list(base_rows)] + [r for p in range(P) for r in (list(up_rows[p]), list(dn_rows[p]))]
+        spot_ptr, _ = self.alloc_sums(2 * m * (1 + 2 * P), "greeks_spot")
+        f = ch["keep"][1]
+        for j, rows in enumerate(job_rows):
+            for i, r in enumerate(rows):
+                self.spot_sums(self.snapshot_ptr(r), float(f[i]), spot_ptr + 16 * (j * m + i))
+        nbytes = C.c_size_t(0)
+        _lib.check(self.lib.svmc_greeks_payoff_workspace_bytes(self.n_path, m, K, P, C.byref(nbytes)))
+        ws_ptr, _ = self.alloc_sums((nbytes.value + 7) // 8, "greeks_workspace")
+        base_out, sens_out = np.empty((len(GREEKS_BASE_FIELDS), max(K, 1))), np.empty((max(P, 1), len(GREEKS_SENS_FIELDS), max(K, 1)))
+        dp = C.POINTER(C.c_double)
+        ptrs = lambda rows: (C.c_void_p * max(len(rows), 1))(*[self.snapshot_ptr(r) for r in rows])      # noqa: E731
+        _lib.check(self.lib.svmc_greeks_payoff_chain(
+            ptrs(job_rows[0]), ptrs([r for rows in up_rows for r in rows]), ptrs([r for rows in dn_rows for r in rows]), self.n_path,
+            ch["forwards"], ch["discfactors"], m, ch["strikes"], ch["codes"], ch["offsets"], P, h.ctypes.data_as(dp), spot_ptr,
+            base_out.ctypes.data_as(dp), sens_out.ctypes.data_as(dp), ws_ptr, nbytes.value, self.stream))
+        out = {field: [base_out[r, sl] for sl in ch["slices"]] for r, field in enumerate(GREEKS_BASE_FIELDS)}
+        for r, field in enumerate(GREEKS_SENS_FIELDS):
+            out[field] = [[sens_out[p, r, sl] for sl in ch["slices"]] for p in range(P)]
+        out["spot_sums"] = self.download(spot_ptr, 2 * m * (1 + 2 * P)).reshape(1 + 2 * P, m, 2)
+        return out
+
+    def price_chain_greeks_fused(self, ch: dict, model: str, rows: np.ndarray, steps: np.ndarray, mode: int, nb_steps_per_year: int,
+                                 seed: int, call_id: int):
+        """svmc_logsv_chain_price_greeks (model "logsv", mode = is_spot_measure, rows [1 + 2P][6 + m]) or
+        svmc_heston_chain_price_greeks ("heston", mode = scheme code, rows [1 + 2P][5]) on this engine's session: the job table's
+        rows on ONE (seed, call id).  Returns (prices [m] -> [K_i], stderrs the same, base [5][K], sens [P][3][K])."""
+        if model not in ("logsv", "heston"):
+            raise ValueError(f"price_chain_greeks_fused: unknown model {model!r}")
+        rows = np.ascontiguousarray(rows, dtype=np.float64)
+        h = np.ascontiguousarray(steps, dtype=np.float64).ravel()
+        P, K = h.size, max(ch["total"], 1)
+        if rows.ndim != 2 or rows.shape[0] != 1 + 2 * P:
+            raise ValueError("the job table has one base row and an up and a dn row per step")
+        res, base, sens = np.empty((2, K)), np.empty((len(GREEKS_BASE_FIELDS), K)), np.empty((max(P, 1), len(GREEKS_SENS_FIELDS), K))
+        dp = C.POINTER(C.c_double)
+        fn = {"logsv": self.lib.svmc_logsv_chain_price_greeks, "heston": self.lib.svmc_heston_chain_price_greeks}[model]
+        self._session_call(ch, lambda sess: fn(
+            sess, ch["ttms"], ch["forwards"], ch["discfactors"], ch["m"], ch["strikes"], ch["codes"], ch["offsets"], P,
+            rows.ctypes.data_as(dp), h.ctypes.data_as(dp), int(mode), int(nb_steps_per_year), int(seed), int(call_id),
+            C.cast(res.ctypes.data, dp), C.cast(res.ctypes.data + res.strides[0], dp), base.ctypes.data_as(dp), sens.ctypes.data_as(dp)),
+            f"{model}_chain_rng_many_kernel")
+        return [res[0, sl] for sl in ch["slices"]], [res[1, sl] for sl in ch["slices"]], base, sens[:P]
 
     def il_payoffs(self, p1, p0, pa, pb, notional=1000000, snap_row: Optional[int] = None, return_pieces: bool = False):
         """the Monte Carlo impermanent loss of the ranges [pa, pb] opened at p0, at the forwards p1, from the resident

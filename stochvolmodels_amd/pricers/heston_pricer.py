@@ -20,6 +20,7 @@ from ..data.option_chain import OptionChain
 from ..engine import HESTON_EULER_FLOOR, HESTON_QE, get_engine, marshalled_chain, option_type_codes
 from ..mc_chain import (chain_shaped, check_many_args, many_job_chunks, many_job_streams, many_jobs_shaped, price_chain_on_engine,
                         variable_type_code)
+from ..mc_greeks import HESTON_GREEK_PARAMS, check_greeks_request, greeks_bumps, greeks_job_table, greeks_shaped
 from ..utils.calibration import ImpliedVolObjective, chain_calibration_weights, minimize_slsqp
 from ..utils.config import VariableType
 from ..utils.funcs import next_rng_call, set_time_grid, time_grid_steps, timer
@@ -89,6 +90,16 @@ class HestonPricer(ModelPricer):
             scheme=kwargs.get("scheme", "euler"), nb_steps_per_year=kwargs.get("nb_steps_per_year", 360), seed=kwargs.get("seed"),
             comm=kwargs.get("comm"), devices=kwargs.get("devices"), recenter=kwargs.get("recenter", True),
             return_stats=kwargs.get("return_stats", False))
+
+    def model_mc_chain_greeks(self, option_chain: OptionChain, params: HestonParams, nb_path: int = 100000,
+                              variable_type: VariableType = VariableType.LOG_RETURN, **kwargs) -> dict:
+        """model_mc_price_chain with its Greeks (heston_mc_chain_greeks); wrt=, rel_bump=, bumps=, scheme= and seed= are passed on"""
+        return heston_mc_chain_greeks(
+            params=params, ttms=option_chain.ttms, forwards=option_chain.forwards, discfactors=option_chain.discfactors,
+            strikes_ttms=option_chain.strikes_ttms, optiontypes_ttms=option_chain.optiontypes_ttms, wrt=kwargs.get("wrt"),
+            rel_bump=kwargs.get("rel_bump", 1e-3), bumps=kwargs.get("bumps"), nb_path=nb_path,
+            nb_steps_per_year=kwargs.get("nb_steps_per_year", 360), seed=kwargs.get("seed"), scheme=kwargs.get("scheme", "euler"),
+            variable_type=variable_type, comm=kwargs.get("comm"), devices=kwargs.get("devices"))
 
     def model_mc_price_chain_many(self, option_chain: OptionChain, params_list: Sequence[HestonParams], nb_path: int = 100000,
                                   variable_type: VariableType = VariableType.LOG_RETURN, seeds: Optional[Sequence[int]] = None,
@@ -259,6 +270,26 @@ def heston_mc_chain_pricer_many(params_list: Sequence[HestonParams], ttms: np.nd
     for _, part, job_seeds, ids in many_job_chunks(streams, rows):
         out += eng.price_chain_many_fused(ch, "heston", part, job_seeds, ids, code, nb_steps_per_year, variable_type_code(variable_type))
     return many_jobs_shaped(out, strikes_ttms)
+
+
+def heston_mc_chain_greeks(params: HestonParams, ttms: np.ndarray, forwards: np.ndarray, discfactors: np.ndarray,
+                           strikes_ttms: Sequence[np.ndarray], optiontypes_ttms: Sequence[np.ndarray],
+                           wrt: Optional[Sequence[str]] = None, rel_bump: float = 1e-3, bumps: Optional[dict] = None,
+                           nb_path: int = 100000, nb_steps_per_year: int = 360, seed: Optional[int] = None, scheme="euler",
+                           variable_type: VariableType = VariableType.LOG_RETURN, comm=None, devices=None) -> dict:
+    """heston_mc_chain_pricer with its Greeks (include/svmc.h; see logsv_mc_chain_greeks): wrt defaults to v0 theta
+    kappa rho volvol, either scheme.  Returns the same dict of chain-shaped lists; price / stderr are bit-equal to
+    heston_mc_chain_pricer at the same seed and scheme.  A bump that takes |rho| to 1 or beyond, or a variance or the vol-of-vol
+    below zero, raises ValueError naming the parameter.  Not in the reference API."""
+    codes = check_greeks_request("heston_mc_chain_greeks", variable_type, comm, devices, optiontypes_ttms)
+    code = _scheme_code(scheme)
+    names, h = greeks_bumps("heston", {k: getattr(params, k) for k in HESTON_GREEK_PARAMS}, wrt, rel_bump, bumps)
+    rows = greeks_job_table("heston", [getattr(params, k) for k in HESTON_GREEK_PARAMS], names, h)
+    rng_seed, call_id = next_rng_call(seed)
+    ch = marshalled_chain(ttms, forwards, discfactors, strikes_ttms, codes)
+    prices, stderrs, base, sens = get_engine(nb_path).price_chain_greeks_fused(ch, "heston", rows, h, code, nb_steps_per_year, rng_seed,
+                                                                               call_id)
+    return greeks_shaped(prices, stderrs, base, sens, names, ch["slices"], strikes_ttms)
 
 
 def simulate_heston_x_vol_terminal(ttm: float, x0: np.ndarray, var0: np.ndarray, qvar0: np.ndarray, theta: float,

@@ -22,6 +22,7 @@ from ..data.option_chain import OptionChain
 from ..engine import DeviceRandoms, get_engine, marshalled_chain, option_type_codes, payoff_finalize, tilted_type_codes
 from ..mc_chain import (chain_shaped, check_many_args, many_job_chunks, many_job_streams, many_jobs_shaped, price_chain_on_engine,
                         variable_type_code)
+from ..mc_greeks import LOGSV_GREEK_PARAMS, check_greeks_request, greeks_bumps, greeks_job_table, greeks_shaped
 from ..utils.calibration import ImpliedVolObjective, chain_calibration_weights, minimize_slsqp
 from ..utils.config import VariableType
 from ..utils.funcs import histogram_series, next_rng_call, set_time_grid, time_grid_steps, timer
@@ -253,6 +254,18 @@ class LogSVPricer(ModelPricer):
             variable_type=variable_type, nb_path=nb_path, nb_steps_per_year=nb_steps or int(360 * np.max(option_chain.ttms)) + 1,
             seed=kwargs.get("seed"), comm=kwargs.get("comm"), devices=kwargs.get("devices"),
             recenter=kwargs.get("recenter", True), return_stats=kwargs.get("return_stats", False))
+
+    def model_mc_chain_greeks(self, option_chain: OptionChain, params: LogSvParams, is_spot_measure: bool = True,
+                              variable_type: VariableType = VariableType.LOG_RETURN, nb_path: int = 100000,
+                              nb_steps: Optional[int] = None, **kwargs) -> dict:
+        """model_mc_price_chain with its Greeks (logsv_mc_chain_greeks) on the same step rule; wrt=, rel_bump=, bumps= and seed= are
+        passed on"""
+        return logsv_mc_chain_greeks(
+            params=params, ttms=option_chain.ttms, forwards=option_chain.forwards, discfactors=option_chain.discfactors,
+            strikes_ttms=option_chain.strikes_ttms, optiontypes_ttms=option_chain.optiontypes_ttms, wrt=kwargs.get("wrt"),
+            rel_bump=kwargs.get("rel_bump", 1e-3), bumps=kwargs.get("bumps"), nb_path=nb_path,
+            nb_steps_per_year=nb_steps or int(360 * np.max(option_chain.ttms)) + 1, seed=kwargs.get("seed"),
+            is_spot_measure=is_spot_measure, variable_type=variable_type, comm=kwargs.get("comm"), devices=kwargs.get("devices"))
 
     def model_mc_price_chain_many(self, option_chain: OptionChain, params_list: Sequence[LogSvParams],
                                   is_spot_measure: bool = True, variable_type: VariableType = VariableType.LOG_RETURN,
@@ -862,6 +875,31 @@ def logsv_mc_chain_pricer_conditional(ttms: np.ndarray, forwards: np.ndarray, di
         ch, v0, theta, kappa1, kappa2, beta, volvol, vol_backbone_etas, is_spot_measure, nb_steps_per_year, recenter, rng_seed, call_id)
     out = (chain_shaped(prices, strikes_ttms), chain_shaped(stderrs, strikes_ttms))
     return out + (stats,) if return_stats else out
+
+
+def logsv_mc_chain_greeks(params: LogSvParams, ttms: np.ndarray, forwards: np.ndarray, discfactors: np.ndarray,
+                          strikes_ttms: Sequence[np.ndarray], optiontypes_ttms: Sequence[np.ndarray],
+                          wrt: Optional[Sequence[str]] = None, rel_bump: float = 1e-3, bumps: Optional[dict] = None,
+                          nb_path: int = 100000, nb_steps_per_year: int = 360, seed: Optional[int] = None,
+                          is_spot_measure: bool = True, variable_type: VariableType = VariableType.LOG_RETURN, comm=None,
+                          devices=None) -> dict:
+    """logsv_mc_chain_pricer with its Greeks (include/svmc.h), on common random numbers: the base parameters and,
+    per name in wrt (default: sigma0 theta kappa1 kappa2 beta volvol), the pair at +- h (h = rel_bump |value|, or bumps[name]) are
+    stepped by ONE launch on one random stream.  Returns a dict of chain-shaped lists: price, stderr (bit-equal to
+    logsv_mc_chain_pricer at the same seed), delta, delta_stderr (the pathwise forward delta), dual_delta, dual_delta_stderr, n_itm,
+    and per name sens[name], sens_stderr[name], n_pairs[name] -- the central difference of the two bumped prices and the error of
+    that DIFFERENCE, from the per-path paired differences.  No gamma; 'C' / 'P', LOG_RETURN, the spot measure and one GPU only; a
+    zero parameter needs an explicit bump and no bump may leave the parameter's domain (ValueError naming the parameter; mc_greeks.
+    greeks_bumps).  The vol-backbone etas are held fixed.  Not in the reference API."""
+    codes = check_greeks_request("logsv_mc_chain_greeks", variable_type, comm, devices, optiontypes_ttms, is_spot_measure)
+    names, h = greeks_bumps("logsv", {k: getattr(params, k) for k in LOGSV_GREEK_PARAMS}, wrt, rel_bump, bumps)
+    etas = np.asarray(params.get_vol_backbone_etas(ttms=np.asarray(ttms, dtype=float)), dtype=np.float64)
+    rows = greeks_job_table("logsv", np.concatenate([[getattr(params, k) for k in LOGSV_GREEK_PARAMS], etas]), names, h)
+    rng_seed, call_id = next_rng_call(seed)
+    ch = marshalled_chain(ttms, forwards, discfactors, strikes_ttms, codes)
+    prices, stderrs, base, sens = get_engine(nb_path).price_chain_greeks_fused(ch, "logsv", rows, h, int(bool(is_spot_measure)),
+                                                                               nb_steps_per_year, rng_seed, call_id)
+    return greeks_shaped(prices, stderrs, base, sens, names, ch["slices"], strikes_ttms)
 
 
 def logsv_mc_chain_pricer_many(params_list: Sequence[LogSvParams], ttms: np.ndarray, forwards: np.ndarray,

@@ -88,3 +88,30 @@ def compute_mc_vars_payoff_conditional(mu: np.ndarray, cv: np.ndarray, ttm: floa
     prices, stderrs, stats = eng.conditional_payoffs([float(forward)], [float(discfactor)], [strikes.ravel()], [codes], bool(recenter))
     out = (prices[0].reshape(strikes.shape), stderrs[0].reshape(strikes.shape))
     return out + (stats[0],) if return_stats else out
+
+
+def compute_mc_vars_greeks(x0: np.ndarray, forward: float, strikes_ttm: np.ndarray, optiontypes_ttm: np.ndarray,
+                           discfactor: float = 1.0, x_up=(), x_dn=(), steps=()) -> dict:
+    """the Greeks tail of include/svmc.h's svmc_greeks_payoff_chain on host arrays of one expiry: x0 the base job's terminal
+    log-returns, x_up[p] / x_dn[p] those of the jobs at theta_p + steps[p] / theta_p - steps[p] ON THE SAME RANDOMS (the paired
+    differences are meaningless otherwise).  Every job is recentred by its own kept-path mean of exp(x).  Returns, in the strikes'
+    shape: delta, delta_stderr (pathwise forward delta), dual_delta, dual_delta_stderr, n_itm, and lists over p of sens,
+    sens_stderr, n_pairs.  'C' / 'P' only (others: ValueError("not implemented")).  Follows compute_mc_vars_payoff's route: upload,
+    reduce on the device, the figures back."""
+    codes = tilted_type_codes(optiontypes_ttm)                   # ValueError("not implemented")
+    strikes = np.asarray(strikes_ttm, dtype=np.float64)
+    x0 = np.ascontiguousarray(x0, dtype=np.float64).ravel()
+    h = np.atleast_1d(np.asarray(steps, dtype=np.float64)).ravel()
+    if not (len(x_up) == len(x_dn) == h.size):
+        raise ValueError("one up row, one dn row and one step per sensitivity")
+    if x0.size == 0:
+        raise ValueError("x0 must not be empty")
+    out = get_engine(x0.size).greeks_payoffs([float(forward)], [float(discfactor)], [strikes.ravel()], [codes], h,
+                                             host_rows=([x0], [[u] for u in x_up], [[d] for d in x_dn]))
+    shaped = lambda a: a.reshape(strikes.shape)                  # noqa: E731
+    res = {k: shaped(out[k][0]) for k in ("delta", "delta_stderr", "dual_delta", "dual_delta_stderr")}
+    res["n_itm"] = shaped(out["n_itm"][0]).astype(np.int64)
+    res["sens"] = [shaped(p[0]) for p in out["sens"]]
+    res["sens_stderr"] = [shaped(p[0]) for p in out["sens_stderr"]]
+    res["n_pairs"] = [shaped(p[0]).astype(np.int64) for p in out["n_pairs"]]
+    return res
