@@ -942,6 +942,61 @@ SVMC_API int svmc_heston_chain_price_cmc(svmc_session_t session, const double *t
                                          double kappa, double rho, double volvol, int nb_steps_per_year, int recenter, uint64_t seed,
                                          uint32_t call_id, double *prices_host, double *stderrs_host, double *stats_host);
 
+/* ---- conditional Monte Carlo Greeks: delta, dual delta, gamma and dual gamma (src svmc_cmc.hip, svmc_chain.hip) ----
+ * The derivatives in F and K of the number svmc_cmc_payoff_chain returns, in closed form per path, each with a standard error.
+ * Everything of the estimator above stands: the keep rule, h = mu + cv / 2, e = exp(h), F_c = F e, the mean over the kept paths.
+ * c = mean_kept(e) - 1 with recentring and c = 0 without; K' = K + F c (= K + corr).  c depends on neither F nor K, so the formulas
+ * below are the exact derivatives of the returned price.  Per kept path, s = +1 for a call and -1 for a put:
+ *   sd = sqrt(cv);  d1 = (ln F_c - ln K') / sd + sd / 2;  d2 = d1 - sd
+ *   B_f = N(d1) (call) | N(d1) - 1 (put);   B_k = -N(d2) (call) | N(-d2) (put)
+ *   delta_i = e B_f + c B_k;   dual_delta_i = B_k;   dual_gamma_i = phi(d2) / (K' sd)
+ *   gamma_i = e phi(d1) K^2 / (F sd K'^2) = (K / F)^2 dual_gamma_i, because F_c phi(d1) = K' phi(d2): dual gamma is accumulated and
+ *   gamma and its error are scaled from it once per quote.
+ *   DEGENERATE: cv == 0: B_f = s 1{s (F_c - K') > 0} (strict), B_k = -B_f, both gammas 0; such kept paths are counted per expiry
+ *   (n_zero_cv).  K' <= 0: a call has B_f = 1, B_k = -1, a put has both 0; gammas 0.
+ * Per quote value = discfactor x mean over the kept paths, error = discfactor x population deviation over the kept paths /
+ * sqrt(n_path), the convention above.  The sums are taken of value_i - shift, shift = the value of the expiry's path 0 (paths that
+ * agree to the bit have errors of exactly 0), or, where that path is dropped, the value at (mu, cv) = (0, 0): the intrinsic
+ * quantities at F.  With recentring c is a sample mean and the errors ignore its noise, as the price's error does.  By construction,
+ * to rounding: price = F delta + K dual_delta and F^2 gamma = K^2 dual_gamma.  Undiscounted, dual gamma is the simulated density of
+ * the terminal spot at the strike, without a bandwidth.
+ *   svmc_cmc_greeks_chain   arguments as svmc_cmc_payoff_chain, greeks_host [SVMC_CMC_GREEKS_ROWS][K] = {price, stderr, delta, its
+ *                           error, dual delta, its error, gamma, its error, dual gamma, its error} in place of the two result
+ *                           arrays; stats_host (nullable) [n_expiries][SVMC_CMC_GREEKS_STATS_DOUBLES]: the five statistics above,
+ *                           then n_zero_cv.  price and stderr are the payoff entry's own four launches (bit-equal to it); then a
+ *                           block column per path block and group of up to SVMC_CMC_GREEKS_KT strikes of one expiry and a finish
+ *                           block per quote and expiry.  One upload, six launches, one download, one synchronize; every sum's
+ *                           order depends on n_path alone, a quote's ten numbers are the same bits whichever strikes or expiries
+ *                           share the call.  Refusals and status codes are svmc_cmc_payoff_chain's; `workspace`: device memory of
+ *                           svmc_cmc_greeks_workspace_bytes(n_path, n_expiries, total_strikes).
+ *   svmc_logsv_chain_price_cmc_greeks / svmc_heston_chain_price_cmc_greeks   the fused drivers: arguments as svmc_*_chain_price_cmc
+ *                           with greeks_host for the two arrays; the session's workspace and page-locked block grow as theirs do;
+ *                           a sharded session is refused.
+ * Left out: parameter sensitivities on this estimator (a many-job conditional stepping kernel), SVMC_INV_CALL / SVMC_INV_PUT,
+ * variables other than the log-return, the inverse measure, Heston QE, Hawkes, sharded sessions. */
+#define SVMC_CMC_GREEKS_KT 4
+#define SVMC_CMC_GREEKS_ROWS 10
+#define SVMC_CMC_GREEKS_STATS_DOUBLES 6
+SVMC_API int svmc_cmc_greeks_workspace_bytes(size_t n_path, int n_expiries, size_t total_strikes, size_t *bytes);
+SVMC_API int svmc_cmc_greeks_chain(const double *const *mu_snapshots_host, const double *const *cv_snapshots_host, size_t n_path,
+                                   const double *forwards_host, const double *discfactors_host, int n_expiries,
+                                   const double *strikes_host, const int8_t *types_host, const size_t *strike_offsets_host,
+                                   int recenter, double *greeks_host, double *stats_host, void *workspace, size_t workspace_bytes,
+                                   svmc_stream_t stream);
+SVMC_API int svmc_logsv_chain_price_cmc_greeks(svmc_session_t session, const double *ttms_host, const double *forwards_host,
+                                               const double *discfactors_host, const double *vol_backbone_etas_host, int n_expiries,
+                                               const double *strikes_host, const int8_t *types_host,
+                                               const size_t *strike_offsets_host, double v0, double theta, double kappa1,
+                                               double kappa2, double beta, double volvol, int is_spot_measure, int nb_steps_per_year,
+                                               int recenter, uint64_t seed, uint32_t call_id, double *greeks_host,
+                                               double *stats_host);
+SVMC_API int svmc_heston_chain_price_cmc_greeks(svmc_session_t session, const double *ttms_host, const double *forwards_host,
+                                                const double *discfactors_host, int n_expiries, const double *strikes_host,
+                                                const int8_t *types_host, const size_t *strike_offsets_host, double v0,
+                                                double theta, double kappa, double rho, double volvol, int nb_steps_per_year,
+                                                int recenter, uint64_t seed, uint32_t call_id, double *greeks_host,
+                                                double *stats_host);
+
 /* ---- Monte Carlo chain Greeks on common random numbers, LogSV and Heston (src svmc_greeks.hip, svmc_chain.hip) ----
  * One base job and, per requested parameter p with step h_p, a pair of jobs at theta_p + h_p (up) and theta_p - h_p (dn), all on
  * ONE random stream (the many-jobs block above: jobs of one (seed, call id) see the same draws and each is bit-equal to its single
@@ -965,8 +1020,8 @@ SVMC_API int svmc_heston_chain_price_cmc(svmc_session_t session, const double *t
  *     payoff moves by -s F 1{in the money} per unit of its M: dt is d with that delta-method term (its mean is 0 when every path
  *     is kept), without which the deviation of d misstates the error of the difference wherever paths end in the money -- an
  *     in-the-money call's several times over.
- * Left out: gamma (on this estimator a density estimate at the strike: a step for the conditional estimator), SVMC_INV_CALL /
- * SVMC_INV_PUT, variables other than the log-return, the inverse measure's payoffs, Hawkes, sharded sessions.
+ * Left out: gamma (on this estimator a density estimate at the strike: the conditional estimator returns it, svmc_cmc_greeks_chain
+ * above), SVMC_INV_CALL / SVMC_INV_PUT, variables other than the log-return, the inverse measure's payoffs, Hawkes, sharded sessions.
  *   svmc_greeks_payoff_chain   model-agnostic, on any device arrays: base_rows_host [n_expiries], up_rows_host / dn_rows_host
  *                              [n_params][n_expiries] HOST arrays of DEVICE pointers ([n_path] each); spot_sums: device
  *                              [1 + 2 n_params][n_expiries][2], the jobs in the order base, up_0, dn_0, up_1, ...; steps_host

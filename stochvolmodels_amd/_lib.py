@@ -183,6 +183,12 @@ def _declare(L: C.CDLL) -> None:
                                         u64, u32, pf64, pf64, pf64], i32),
         "svmc_heston_chain_price_cmc": ([vp, pf64, pf64, pf64, i32, pf64, pi8, psz, f64, f64, f64, f64, f64, i32, i32, u64, u32, pf64,
                                          pf64, pf64], i32),
+        "svmc_cmc_greeks_workspace_bytes": ([sz, i32, sz, psz], i32),
+        "svmc_cmc_greeks_chain": ([C.POINTER(vp), C.POINTER(vp), sz, pf64, pf64, i32, pf64, pi8, psz, i32, pf64, pf64, vp, sz, vp], i32),
+        "svmc_logsv_chain_price_cmc_greeks": ([vp, pf64, pf64, pf64, pf64, i32, pf64, pi8, psz, f64, f64, f64, f64, f64, f64, i32, i32,
+                                               i32, u64, u32, pf64, pf64], i32),
+        "svmc_heston_chain_price_cmc_greeks": ([vp, pf64, pf64, pf64, i32, pf64, pi8, psz, f64, f64, f64, f64, f64, i32, i32, u64, u32,
+                                                pf64, pf64], i32),
         "svmc_hawkesjd_chain_price_tilted": ([vp, pf64, pf64, i32, pf64, pi8, psz, pf64, i32, u64, u32, pf64, i32, i32, pf64, pf64,
                                               pf64], i32),
         "svmc_greeks_payoff_workspace_bytes": ([sz, i32, sz, i32, psz], i32),

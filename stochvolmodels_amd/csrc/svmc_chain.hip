@@ -566,9 +566,12 @@ static int tilted_block(Session *s, const ChainView &c, int n_gammas, int n_jobs
 // single_step's; mu rides in the session's x, cv in an array of its own, expiry i's snapshots in rows i and m + i of s->snap.
 template <class Step>
 static int chain_price_cmc(const char *fn, Session *s, const ChainView &c, int nb_steps_per_year, int recenter, double *prices_host,
-                           double *stderrs_host, double *stats_host, Step &&step)
+                           double *stderrs_host, double *greeks_host, double *stats_host, Step &&step)
 {
+    // greeks_host (svmc_*_chain_price_cmc_greeks) [SVMC_CMC_GREEKS_ROWS][K]: the tail with the derivatives; prices_host and
+    // stderrs_host are then its first two rows
     double *mu_snap = nullptr, *cv_snap = nullptr;
+    const bool deriv = greeks_host != nullptr;
     const Stepped st = single_step(fn, s, c, nb_steps_per_year, SVMC_LOG_RETURN, prices_host, stderrs_host, true, false,
                                    [&](const int *nbs, const double *dts, double *, double *, void *, size_t) {
                                        return step(nbs, dts, mu_snap, cv_snap);
@@ -582,8 +585,11 @@ static int chain_price_cmc(const char *fn, Session *s, const ChainView &c, int n
                                    },
                                    [&]() {
                                        SVMC_HIP_TRY(grow(reinterpret_cast<void **>(&s->cmc_cv), s->cmc_cv_bytes, s->n_path * sizeof(double), false));
-                                       SVMC_HIP_TRY(grow(&s->cmc_ws, s->cmc_ws_bytes, cmc_payoff_workspace_bytes_of(s->n_path, c.m, c.offsets[c.m]), false));
-                                       SVMC_HIP_TRY(grow(&s->cmc_pinned, s->cmc_pinned_bytes, cmc_payoff_pinned_bytes_of(c.m, c.offsets[c.m]), true));
+                                       const size_t K = c.offsets[c.m];
+                                       SVMC_HIP_TRY(grow(&s->cmc_ws, s->cmc_ws_bytes, deriv ? cmc_greeks_workspace_bytes_of(s->n_path, c.m, K)
+                                                                                           : cmc_payoff_workspace_bytes_of(s->n_path, c.m, K), false));
+                                       SVMC_HIP_TRY(grow(&s->cmc_pinned, s->cmc_pinned_bytes, deriv ? cmc_greeks_pinned_bytes_of(c.m, K)
+                                                                                                   : cmc_payoff_pinned_bytes_of(c.m, K), true));
                                        mu_snap = s->snap;
                                        cv_snap = s->snap + static_cast<size_t>(c.m) * s->n_path;
                                        return SVMC_OK;
@@ -594,9 +600,12 @@ static int chain_price_cmc(const char *fn, Session *s, const ChainView &c, int n
         mus[i] = mu_snap + static_cast<size_t>(i) * s->n_path;
         cvs[i] = cv_snap + static_cast<size_t>(i) * s->n_path;
     }
-    const int rc = cmc_payoff_chain(fn, mus.data(), cvs.data(), s->n_path, c.forwards, c.discfactors, c.m, c.strikes, c.types, c.offsets,
-                                    recenter, prices_host, stderrs_host, stats_host, s->cmc_ws, s->cmc_ws_bytes, s->stream, s->cmc_pinned,
-                                    s->cmc_pinned_bytes);
+    const int rc = deriv ? cmc_greeks_chain(fn, mus.data(), cvs.data(), s->n_path, c.forwards, c.discfactors, c.m, c.strikes, c.types,
+                                            c.offsets, recenter, greeks_host, stats_host, s->cmc_ws, s->cmc_ws_bytes, s->stream,
+                                            s->cmc_pinned, s->cmc_pinned_bytes)
+                         : cmc_payoff_chain(fn, mus.data(), cvs.data(), s->n_path, c.forwards, c.discfactors, c.m, c.strikes, c.types,
+                                            c.offsets, recenter, prices_host, stderrs_host, stats_host, s->cmc_ws, s->cmc_ws_bytes,
+                                            s->stream, s->cmc_pinned, s->cmc_pinned_bytes);
     if (rc == SVMC_OK) stepping_read(s);
     return rc;
 }
@@ -1032,7 +1041,7 @@ int svmc_logsv_chain_price_cmc(svmc_session_t session, const double *ttms_host, 
 {
     Session *s = reinterpret_cast<Session *>(session);
     const ChainView c = {n_expiries, ttms_host, forwards_host, discfactors_host, strikes_host, types_host, strike_offsets_host};
-    return chain_price_cmc("svmc_logsv_chain_price_cmc", s, c, nb_steps_per_year, recenter, prices_host, stderrs_host, stats_host,
+    return chain_price_cmc("svmc_logsv_chain_price_cmc", s, c, nb_steps_per_year, recenter, prices_host, stderrs_host, nullptr, stats_host,
                            [&](const int *nbs, const double *dts, double *mu_snap, double *cv_snap) {
         return logsv_cmc_step_from(v0, s->x, s->cmc_cv, s->vol, s->qvar, s->n_path, c.m, nbs, dts, vol_backbone_etas_host, theta, kappa1,
                                    kappa2, beta, volvol, is_spot_measure, seed, call_id, s->path_offset, mu_snap, cv_snap, s->stream);
@@ -1047,8 +1056,43 @@ int svmc_heston_chain_price_cmc(svmc_session_t session, const double *ttms_host,
 {
     Session *s = reinterpret_cast<Session *>(session);
     const ChainView c = {n_expiries, ttms_host, forwards_host, discfactors_host, strikes_host, types_host, strike_offsets_host};
-    return chain_price_cmc("svmc_heston_chain_price_cmc", s, c, nb_steps_per_year, recenter, prices_host, stderrs_host, stats_host,
+    return chain_price_cmc("svmc_heston_chain_price_cmc", s, c, nb_steps_per_year, recenter, prices_host, stderrs_host, nullptr, stats_host,
                            [&](const int *nbs, const double *dts, double *mu_snap, double *cv_snap) {
+        return heston_cmc_step_from(v0, s->x, s->cmc_cv, s->vol, s->qvar, s->n_path, c.m, nbs, dts, theta, kappa, rho, volvol, seed,
+                                    call_id, s->path_offset, mu_snap, cv_snap, s->stream);
+    });
+}
+
+int svmc_logsv_chain_price_cmc_greeks(svmc_session_t session, const double *ttms_host, const double *forwards_host,
+                                      const double *discfactors_host, const double *vol_backbone_etas_host, int n_expiries,
+                                      const double *strikes_host, const int8_t *types_host, const size_t *strike_offsets_host, double v0,
+                                      double theta, double kappa1, double kappa2, double beta, double volvol, int is_spot_measure,
+                                      int nb_steps_per_year, int recenter, uint64_t seed, uint32_t call_id, double *greeks_host,
+                                      double *stats_host)
+{
+    const char *fn = "svmc_logsv_chain_price_cmc_greeks";
+    SVMC_REQUIRE(greeks_host != nullptr && strike_offsets_host != nullptr && n_expiries >= 1, std::string(fn) + ": null pointer or no expiries");
+    Session *s = reinterpret_cast<Session *>(session);
+    const ChainView c = {n_expiries, ttms_host, forwards_host, discfactors_host, strikes_host, types_host, strike_offsets_host};
+    return chain_price_cmc(fn, s, c, nb_steps_per_year, recenter, greeks_host, greeks_host + strike_offsets_host[n_expiries], greeks_host,
+                           stats_host, [&](const int *nbs, const double *dts, double *mu_snap, double *cv_snap) {
+        return logsv_cmc_step_from(v0, s->x, s->cmc_cv, s->vol, s->qvar, s->n_path, c.m, nbs, dts, vol_backbone_etas_host, theta, kappa1,
+                                   kappa2, beta, volvol, is_spot_measure, seed, call_id, s->path_offset, mu_snap, cv_snap, s->stream);
+    });
+}
+
+int svmc_heston_chain_price_cmc_greeks(svmc_session_t session, const double *ttms_host, const double *forwards_host,
+                                       const double *discfactors_host, int n_expiries, const double *strikes_host,
+                                       const int8_t *types_host, const size_t *strike_offsets_host, double v0, double theta, double kappa,
+                                       double rho, double volvol, int nb_steps_per_year, int recenter, uint64_t seed, uint32_t call_id,
+                                       double *greeks_host, double *stats_host)
+{
+    const char *fn = "svmc_heston_chain_price_cmc_greeks";
+    SVMC_REQUIRE(greeks_host != nullptr && strike_offsets_host != nullptr && n_expiries >= 1, std::string(fn) + ": null pointer or no expiries");
+    Session *s = reinterpret_cast<Session *>(session);
+    const ChainView c = {n_expiries, ttms_host, forwards_host, discfactors_host, strikes_host, types_host, strike_offsets_host};
+    return chain_price_cmc(fn, s, c, nb_steps_per_year, recenter, greeks_host, greeks_host + strike_offsets_host[n_expiries], greeks_host,
+                           stats_host, [&](const int *nbs, const double *dts, double *mu_snap, double *cv_snap) {
         return heston_cmc_step_from(v0, s->x, s->cmc_cv, s->vol, s->qvar, s->n_path, c.m, nbs, dts, theta, kappa, rho, volvol, seed,
                                     call_id, s->path_offset, mu_snap, cv_snap, s->stream);
     });

@@ -650,6 +650,174 @@ __global__ __launch_bounds__(BLOCK) void cmc_finish_kernel(CmcTable t, size_t n)
     }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// derivatives of the conditional estimator in F and K (include/svmc.h states the formulas)
+// ---------------------------------------------------------------------------------------------------
+// The kernels' names carry neither of the words the f11 and f12 metadata tests count kernels by.
+constexpr int CMC_DKT = SVMC_CMC_GREEKS_KT;    // strikes per group: six accumulators, three shifts and three constants per strike
+constexpr int CMC_DQ = 6;                      // per strike: sum and sum of squares of delta, dual delta, dual gamma (minus their shifts)
+
+// what the derivative launches add to a chain's CmcTable
+struct CmcDerivTable {
+    const CmcGroup *groups;            // groups of up to CMC_DKT strikes; pad = 1: the expiry's first group, which counts its cv == 0
+                                       // paths (an expiry without strikes has one group of nk = 0 for that count)
+    double *shift;                     // [K][3]: delta, dual delta and dual gamma of the expiry's path 0 -- or of (mu, cv) = (0, 0)
+    double *partials;                  // [rows][K][CMC_DQ]
+    double *zero_partials;             // [rows][m]
+    double *out;                       // [8][K]: delta, dual delta, gamma, dual gamma, each followed by its error
+    double *zero;                      // [m]: kept paths with cv == 0
+};
+
+// Per kept path and strike: delta_i = e B_f + c B_k, dual_delta_i = B_k, dual_gamma_i = phi(d2) / (K' sd), with d1 and d2 formed as
+// cmc_black forms them.  Each side's B_f and B_k come from its own tail (put: B_f = -N(-d1), B_k = N(-d2)), as its price does.
+// Every multiply-add is written out, so that the value does not depend on the call site's contraction: the shift is this
+// function on path 0 and identical paths must give differences that are exactly zero.
+__device__ __forceinline__ void cmc_derivs(double e, double c, double fc, double ln_fc, double cv, double sd, double inv_sd, double kp,
+                                           double ln_kp, double inv_kp, bool put, double &delta, double &dual_delta, double &dual_gamma)
+{
+    double bf, bk, dg = 0.0;
+    if (!(kp > 0.0)) {
+        bf = put ? 0.0 : 1.0;
+        bk = -bf;
+    } else if (cv == 0.0) {
+        const bool itm = put ? (fc < kp) : (fc > kp);      // strict: a tie has payoff 0 and indicator 0
+        bf = itm ? (put ? -1.0 : 1.0) : 0.0;
+        bk = -bf;
+    } else {
+        const double d1 = fma(ln_fc - ln_kp, inv_sd, 0.5 * sd), d2 = d1 - sd;
+        bf = put ? -black_norm_cdf(-d1) : black_norm_cdf(d1);
+        bk = put ? black_norm_cdf(-d2) : -black_norm_cdf(d2);
+        dg = (exp_full((-0.5 * d2) * d2) * 0.39894228040143267794) * (inv_sd * inv_kp);
+    }
+    delta = fma(e, bf, c * bk);
+    dual_delta = bk;
+    dual_gamma = dg;
+}
+
+// the shift of a strike's sums: cmc_derivs on the expiry's path 0, or at (mu, cv) = (0, 0) where that path is dropped
+struct CmcPath0 {
+    double e, fc, ln_fc, cv, sd, inv_sd;
+};
+__device__ __forceinline__ CmcPath0 cmc_path0(const CmcExpiry &ex)
+{
+    double h, e;
+    double cv = ex.cv[0];
+    if (!cmc_keep(ex.mu[0], cv, h, e)) {
+        h = 0.0;
+        e = 1.0;
+        cv = 0.0;
+    }
+    const double sd = sqrt(cv);
+    return CmcPath0{e, ex.forward * e, ex.ln_forward + h, cv, sd, 1.0 / sd};
+}
+
+template <int KT>
+__global__ __launch_bounds__(BLOCK) void cond_deriv_kernel(CmcTable t, CmcDerivTable dt, size_t n, int recenter)
+{
+    constexpr int NV = CMC_DQ * KT + 1;                    // the last value: the count of cv == 0 paths
+    __shared__ double lds[4 * block_sum_padded(NV)];
+    const CmcGroup g = dt.groups[blockIdx.y];
+    const CmcExpiry ex = t.expiries[g.expiry];
+    const int nk = g.nk;                                   // (block-uniform; 0: the group only counts)
+    const double *fw = t.fwd + 4 * g.expiry;
+    const double c = recenter ? fw[0] / fw[2] : 0.0;       // mean_kept(e) - 1, the quotient cmc_forward_finish_kernel forms
+    double kp[KT], ln_kp[KT], inv_kp[KT], sh[3][KT], acc[NV];
+    bool put[KT];
+#pragma unroll
+    for (int j = 0; j < NV; ++j) acc[j] = 0.0;
+    if (nk > 0) {
+        const CmcPath0 p0 = cmc_path0(ex);
+#pragma unroll
+        for (int k = 0; k < KT; ++k) {
+            const int kk = g.k0 + ((k < nk) ? k : 0);      // the unused strikes of a group repeat its first; their sums are dropped
+            kp[k] = t.kp[kk];
+            ln_kp[k] = t.ln_kp[kk];
+            inv_kp[k] = 1.0 / kp[k];
+            put[k] = t.is_put[kk] != 0.0;
+            cmc_derivs(p0.e, c, p0.fc, p0.ln_fc, p0.cv, p0.sd, p0.inv_sd, kp[k], ln_kp[k], inv_kp[k], put[k], sh[0][k], sh[1][k], sh[2][k]);
+            if (blockIdx.x == 0 && threadIdx.x == 0 && k < nk) {
+                dt.shift[3 * kk] = sh[0][k];
+                dt.shift[3 * kk + 1] = sh[1][k];
+                dt.shift[3 * kk + 2] = sh[2][k];
+            }
+        }
+    }
+    const double forward = ex.forward, ln_forward = ex.ln_forward;
+    const size_t stride = static_cast<size_t>(gridDim.x) * BLOCK;
+    for (size_t i = static_cast<size_t>(blockIdx.x) * BLOCK + threadIdx.x; i < n; i += stride) {
+        const double cv = ex.cv[i];
+        double h, e;
+        if (!cmc_keep(ex.mu[i], cv, h, e)) continue;
+        if (cv == 0.0) acc[NV - 1] += 1.0;
+        if (nk > 0) {
+            const double fc = forward * e, ln_fc = ln_forward + h;
+            const double sd = sqrt(cv), inv_sd = 1.0 / sd;
+#pragma unroll
+            for (int k = 0; k < KT; ++k) {
+                double v[3];
+                cmc_derivs(e, c, fc, ln_fc, cv, sd, inv_sd, kp[k], ln_kp[k], inv_kp[k], put[k], v[0], v[1], v[2]);
+#pragma unroll
+                for (int q = 0; q < 3; ++q) {
+                    const double d = v[q] - sh[q][k];
+                    acc[(2 * q) * KT + k] += d;
+                    acc[(2 * q + 1) * KT + k] = fma(d, d, acc[(2 * q + 1) * KT + k]);
+                }
+            }
+        }
+    }
+    double *out = dt.partials + (static_cast<size_t>(blockIdx.x) * t.K + g.k0) * CMC_DQ;
+    double *zero = (g.pad != 0) ? dt.zero_partials + static_cast<size_t>(blockIdx.x) * t.m + g.expiry : nullptr;
+    block_sum_apply<NV>(acc, lds, NV, [&](int j, double s) {
+        if (j == NV - 1) {
+            if (zero != nullptr) *zero = s;
+        } else {
+            const int q = j / KT, k = j - q * KT;
+            if (k < nk) out[CMC_DQ * k + q] = s;
+        }
+    });
+}
+
+// a block per quote, then a block per expiry.  Quote k: its six column sums in row order, payoff_finalize_one on each pair (value =
+// discfactor (shift + mean over the kept paths), error = discfactor x population deviation / sqrt(n_path)), gamma and its error
+// from dual gamma by (K / F)^2.  Expiry i (block K + i): the column sum of its cv == 0 counts.
+__global__ __launch_bounds__(BLOCK) void cond_deriv_finish_kernel(CmcTable t, CmcDerivTable dt, size_t n)
+{
+    __shared__ double lds[4];
+    const int k = blockIdx.x;
+    if (k >= t.K) {                                        // (block-uniform)
+        const int i = k - t.K;
+        const double z = block_column_sum(dt.zero_partials + i, t.rows, static_cast<size_t>(t.m), lds);
+        if (threadIdx.x == 0) dt.zero[i] = z;
+        return;
+    }
+    int i = 0;
+    while (i + 1 < t.m && k >= t.expiries[i].k1) ++i;
+    const size_t ld = CMC_DQ * static_cast<size_t>(t.K);
+    const double *base = dt.partials + CMC_DQ * static_cast<size_t>(k);
+    double s[CMC_DQ];
+#pragma unroll
+    for (int q = 0; q < CMC_DQ; ++q) {
+        if (q > 0) __syncthreads();
+        s[q] = block_column_sum(base + q, t.rows, ld, lds);
+    }
+    if (threadIdx.x == 0) {
+        const double cnt = t.fwd[4 * i + 2], df = t.expiries[i].discfactor, nn = static_cast<double>(n);
+        double v[3], err[3];
+#pragma unroll
+        for (int q = 0; q < 3; ++q) payoff_finalize_one(s[2 * q], s[2 * q + 1], cnt, dt.shift[3 * k + q], df, nn, &v[q], &err[q]);
+        const double r = t.strikes[k] / t.expiries[i].forward, r2 = r * r;
+        const size_t K = static_cast<size_t>(t.K);
+        dt.out[k] = v[0];
+        dt.out[K + k] = err[0];
+        dt.out[2 * K + k] = v[1];
+        dt.out[3 * K + k] = err[1];
+        dt.out[4 * K + k] = r2 * v[2];
+        dt.out[5 * K + k] = r2 * err[2];
+        dt.out[6 * K + k] = v[2];
+        dt.out[7 * K + k] = err[2];
+    }
+}
+
 static size_t align8(size_t b) { return (b + 7) & ~static_cast<size_t>(7); }
 static int cmc_groups(int n_expiries, const size_t *offsets)
 {
@@ -657,22 +825,34 @@ static int cmc_groups(int n_expiries, const size_t *offsets)
     for (int i = 0; i < n_expiries; ++i) g += static_cast<int>((offsets[i + 1] - offsets[i] + CMC_KT - 1) / CMC_KT);
     return g;
 }
-static size_t cmc_workspace_bytes(size_t n_path, int m, size_t K, int groups)
+static int cmc_deriv_groups(int n_expiries, const size_t *offsets)     // at least one per expiry: the count of cv == 0 paths
+{
+    int g = 0;
+    for (int i = 0; i < n_expiries; ++i) g += std::max(1, static_cast<int>((offsets[i + 1] - offsets[i] + CMC_DKT - 1) / CMC_DKT));
+    return g;
+}
+// deriv_groups = 0: the payoff tail alone
+static size_t cmc_workspace_bytes(size_t n_path, int m, size_t K, int groups, int deriv_groups = 0)
 {
     const size_t rows = cmc_rows(n_path);
+    const size_t deriv = deriv_groups ? align8(sizeof(CmcGroup) * deriv_groups) + sizeof(double) * (8 * K + m + 3 * K + rows * CMC_DQ * K + rows * m) : 0;
     return align8(sizeof(CmcExpiry) * m) + align8(sizeof(CmcGroup) * groups) + sizeof(double) * (6 * K + 4 * m + SVMC_CMC_STATS_DOUBLES * m +
-           rows * 3 * m + rows * 2 * K + 2 * K);
+           rows * 3 * m + rows * 2 * K + 2 * K) + deriv;
 }
 
 // prices_host, stderrs_host [K], stats_host [m][SVMC_CMC_STATS_DOUBLES] (nullable); returns after the stream is synchronised.
 // pinned (nullable): page-locked host memory of cmc_payoff_pinned_bytes_of(m, K) for the table's image and the results
-int cmc_payoff_chain(const char *fn, const double *const *mu_snapshots_host, const double *const *cv_snapshots_host, size_t n_path,
-                     const double *forwards_host, const double *discfactors_host, int n_expiries, const double *strikes_host,
-                     const int8_t *types_host, const size_t *strike_offsets_host, int recenter, double *prices_host, double *stderrs_host,
-                     double *stats_host, void *workspace, size_t workspace_bytes, hipStream_t stream, void *pinned, size_t pinned_bytes)
+// greeks_host (nullable) [SVMC_CMC_GREEKS_ROWS][K]: the derivative launches run after the payoff tail's, prices_host and stderrs_host
+// are not read and stats_host is [m][SVMC_CMC_GREEKS_STATS_DOUBLES]
+static int cmc_tail(const char *fn, const double *const *mu_snapshots_host, const double *const *cv_snapshots_host, size_t n_path,
+                    const double *forwards_host, const double *discfactors_host, int n_expiries, const double *strikes_host,
+                    const int8_t *types_host, const size_t *strike_offsets_host, int recenter, double *prices_host, double *stderrs_host,
+                    double *greeks_host, double *stats_host, void *workspace, size_t workspace_bytes, hipStream_t stream, void *pinned,
+                    size_t pinned_bytes)
 {
+    const bool deriv = greeks_host != nullptr;
     SVMC_REQUIRE(mu_snapshots_host && cv_snapshots_host && forwards_host && discfactors_host && strikes_host && types_host &&
-                     strike_offsets_host && prices_host && stderrs_host && workspace,
+                     strike_offsets_host && (deriv || (prices_host && stderrs_host)) && workspace,
                  std::string(fn) + ": null pointer");
     SVMC_REQUIRE(n_path > 0 && n_expiries >= 1, std::string(fn) + ": n_path and n_expiries must be positive");
     const int m = n_expiries;
@@ -687,27 +867,33 @@ int cmc_payoff_chain(const char *fn, const double *const *mu_snapshots_host, con
         SVMC_REQUIRE(std::isfinite(strikes_host[k]), std::string(fn) + ": a strike is not finite");
     }
     SVMC_REQUIRE(K < (1u << 30), std::string(fn) + ": too many strikes");
-    const int G = cmc_groups(m, strike_offsets_host);
-    if (workspace_bytes < cmc_workspace_bytes(n_path, m, K, G))
-        return fail(SVMC_ERR_WORKSPACE, std::string(fn) + ": workspace too small (svmc_cmc_payoff_workspace_bytes)");
+    const int G = cmc_groups(m, strike_offsets_host), GD = deriv ? cmc_deriv_groups(m, strike_offsets_host) : 0;
+    if (workspace_bytes < cmc_workspace_bytes(n_path, m, K, G, GD))
+        return fail(SVMC_ERR_WORKSPACE, std::string(fn) + ": workspace too small (svmc_cmc_payoff_workspace_bytes / svmc_cmc_greeks_workspace_bytes)");
 
-    // the table's host image: expiries, groups, then strikes / is_put / intrinsic
-    const size_t o_groups = align8(sizeof(CmcExpiry) * m), o_k = o_groups + align8(sizeof(CmcGroup) * G), up_bytes = o_k + 3 * K * sizeof(double);
+    // the table's host image: expiries, groups (the derivative launches' after the payoff's), then strikes / is_put / intrinsic
+    const size_t o_groups = align8(sizeof(CmcExpiry) * m), o_dgroups = o_groups + align8(sizeof(CmcGroup) * G),
+                 o_k = o_dgroups + align8(sizeof(CmcGroup) * GD), up_bytes = o_k + 3 * K * sizeof(double);
     // ... built in the caller's page-locked staging block where it gave one that holds the image and the results (the fused
     // drivers: an upload from and downloads into pageable memory go through the runtime's staging path, 16 us apiece)
-    const size_t n_res = 2 * K + static_cast<size_t>(SVMC_CMC_STATS_DOUBLES) * m;
+    const size_t n_deriv = deriv ? 8 * K : 0, n_zero = deriv ? static_cast<size_t>(m) : 0;
+    const size_t n_res = 2 * K + n_deriv + static_cast<size_t>(SVMC_CMC_STATS_DOUBLES) * m + n_zero;
     const bool staged = pinned != nullptr && pinned_bytes >= up_bytes + n_res * sizeof(double);
     std::vector<unsigned char> pageable(staged ? 0 : up_bytes + n_res * sizeof(double));
     unsigned char *img = staged ? static_cast<unsigned char *>(pinned) : pageable.data();
     double *res = reinterpret_cast<double *>(img + up_bytes);
     CmcExpiry *ex = reinterpret_cast<CmcExpiry *>(img);
-    CmcGroup *gr = reinterpret_cast<CmcGroup *>(img + o_groups);
+    CmcGroup *gr = reinterpret_cast<CmcGroup *>(img + o_groups), *dgr = reinterpret_cast<CmcGroup *>(img + o_dgroups);
     double *kd = reinterpret_cast<double *>(img + o_k);
-    int g = 0;
+    int g = 0, gd = 0;
     for (int i = 0; i < m; ++i) {
         const int k0 = static_cast<int>(strike_offsets_host[i]), k1 = static_cast<int>(strike_offsets_host[i + 1]);
         ex[i] = CmcExpiry{mu_snapshots_host[i], cv_snapshots_host[i], forwards_host[i], std::log(forwards_host[i]), discfactors_host[i], k0, k1};
         for (int k = k0; k < k1; k += CMC_KT) gr[g++] = CmcGroup{i, k, (k1 - k < CMC_KT) ? k1 - k : CMC_KT, 0};
+        if (deriv) {
+            if (k0 == k1) dgr[gd++] = CmcGroup{i, 0, 0, 1};
+            for (int k = k0; k < k1; k += CMC_DKT) dgr[gd++] = CmcGroup{i, k, (k1 - k < CMC_DKT) ? k1 - k : CMC_DKT, (k == k0) ? 1 : 0};
+        }
         for (int k = k0; k < k1; ++k) {
             const bool put = types_host[k] == SVMC_PUT;
             kd[k] = strikes_host[k];
@@ -728,13 +914,21 @@ int cmc_payoff_chain(const char *fn, const double *const *mu_snapshots_host, con
     t.ln_kp = d + 4 * K;
     t.shift = d + 5 * K;
     t.fwd = d + 6 * K;
-    t.out = t.fwd + 4 * m;                                 // the results, one block: prices [K], errors [K], statistics [m][5]
-    t.stats = t.out + 2 * K;
+    // the results, one block: prices [K], errors [K], (the derivatives [8][K],) statistics [m][5] (, the cv == 0 counts [m])
+    t.out = t.fwd + 4 * m;
+    t.stats = t.out + 2 * K + n_deriv;
     t.m = m;
     t.K = static_cast<int>(K);
     t.rows = cmc_rows(n_path);
-    t.fwd_partials = t.stats + SVMC_CMC_STATS_DOUBLES * m;
+    t.fwd_partials = t.stats + SVMC_CMC_STATS_DOUBLES * m + n_zero;
     t.pay_partials = t.fwd_partials + static_cast<size_t>(t.rows) * 3 * m;
+    CmcDerivTable dt;
+    dt.groups = reinterpret_cast<const CmcGroup *>(w + o_dgroups);
+    dt.out = t.out + 2 * K;
+    dt.zero = t.stats + SVMC_CMC_STATS_DOUBLES * m;
+    dt.shift = t.pay_partials + static_cast<size_t>(t.rows) * 2 * K;
+    dt.partials = dt.shift + 3 * K;
+    dt.zero_partials = dt.partials + static_cast<size_t>(t.rows) * CMC_DQ * K;
 
     hipLaunchKernelGGL(cmc_forward_kernel, dim3(t.rows, m), dim3(BLOCK), 0, stream, t, n_path);
     if (int rc = check_launch(fn)) return rc;
@@ -746,12 +940,66 @@ int cmc_payoff_chain(const char *fn, const double *const *mu_snapshots_host, con
         hipLaunchKernelGGL(cmc_finish_kernel, dim3(static_cast<unsigned>(K)), dim3(BLOCK), 0, stream, t, n_path);
         if (int rc = check_launch(fn)) return rc;
     }
+    if (deriv) {
+        // price and error are the payoff tail's own launches above (bit-equal to svmc_cmc_payoff_chain by construction); the
+        // derivative kernels evaluate the two normal CDFs again
+        hipLaunchKernelGGL(cond_deriv_kernel<CMC_DKT>, dim3(t.rows, GD), dim3(BLOCK), 0, stream, t, dt, n_path, recenter ? 1 : 0);
+        if (int rc = check_launch(fn)) return rc;
+        hipLaunchKernelGGL(cond_deriv_finish_kernel, dim3(static_cast<unsigned>(K) + m), dim3(BLOCK), 0, stream, t, dt, n_path);
+        if (int rc = check_launch(fn)) return rc;
+    }
     SVMC_HIP_TRY(hipMemcpyAsync(res, t.out, n_res * sizeof(double), hipMemcpyDeviceToHost, stream));
     SVMC_HIP_TRY(hipStreamSynchronize(stream));            // the table's host image and the results' landing
-    memcpy(prices_host, res, K * sizeof(double));
-    memcpy(stderrs_host, res + K, K * sizeof(double));
-    if (stats_host != nullptr) memcpy(stats_host, res + 2 * K, static_cast<size_t>(SVMC_CMC_STATS_DOUBLES) * m * sizeof(double));
+    if (!deriv) {
+        memcpy(prices_host, res, K * sizeof(double));
+        memcpy(stderrs_host, res + K, K * sizeof(double));
+        if (stats_host != nullptr) memcpy(stats_host, res + 2 * K, static_cast<size_t>(SVMC_CMC_STATS_DOUBLES) * m * sizeof(double));
+        return SVMC_OK;
+    }
+    memcpy(greeks_host, res, static_cast<size_t>(SVMC_CMC_GREEKS_ROWS) * K * sizeof(double));
+    if (stats_host != nullptr) {
+        const double *st = res + static_cast<size_t>(SVMC_CMC_GREEKS_ROWS) * K, *zero = st + static_cast<size_t>(SVMC_CMC_STATS_DOUBLES) * m;
+        for (int i = 0; i < m; ++i) {
+            memcpy(stats_host + static_cast<size_t>(SVMC_CMC_GREEKS_STATS_DOUBLES) * i, st + SVMC_CMC_STATS_DOUBLES * i,
+                   SVMC_CMC_STATS_DOUBLES * sizeof(double));
+            stats_host[static_cast<size_t>(SVMC_CMC_GREEKS_STATS_DOUBLES) * i + SVMC_CMC_STATS_DOUBLES] = zero[i];
+        }
+    }
     return SVMC_OK;
+}
+
+int cmc_payoff_chain(const char *fn, const double *const *mu_snapshots_host, const double *const *cv_snapshots_host, size_t n_path,
+                     const double *forwards_host, const double *discfactors_host, int n_expiries, const double *strikes_host,
+                     const int8_t *types_host, const size_t *strike_offsets_host, int recenter, double *prices_host, double *stderrs_host,
+                     double *stats_host, void *workspace, size_t workspace_bytes, hipStream_t stream, void *pinned, size_t pinned_bytes)
+{
+    return cmc_tail(fn, mu_snapshots_host, cv_snapshots_host, n_path, forwards_host, discfactors_host, n_expiries, strikes_host, types_host,
+                    strike_offsets_host, recenter, prices_host, stderrs_host, nullptr, stats_host, workspace, workspace_bytes, stream, pinned,
+                    pinned_bytes);
+}
+
+int cmc_greeks_chain(const char *fn, const double *const *mu_snapshots_host, const double *const *cv_snapshots_host, size_t n_path,
+                     const double *forwards_host, const double *discfactors_host, int n_expiries, const double *strikes_host,
+                     const int8_t *types_host, const size_t *strike_offsets_host, int recenter, double *greeks_host, double *stats_host,
+                     void *workspace, size_t workspace_bytes, hipStream_t stream, void *pinned, size_t pinned_bytes)
+{
+    SVMC_REQUIRE(greeks_host != nullptr, std::string(fn) + ": null pointer");
+    return cmc_tail(fn, mu_snapshots_host, cv_snapshots_host, n_path, forwards_host, discfactors_host, n_expiries, strikes_host, types_host,
+                    strike_offsets_host, recenter, nullptr, nullptr, greeks_host, stats_host, workspace, workspace_bytes, stream, pinned,
+                    pinned_bytes);
+}
+
+size_t cmc_greeks_pinned_bytes_of(int n_expiries, size_t total_strikes)
+{
+    const int groups = static_cast<int>(total_strikes / CMC_KT) + n_expiries, dgroups = static_cast<int>(total_strikes / CMC_DKT) + n_expiries;
+    return align8(sizeof(CmcExpiry) * n_expiries) + align8(sizeof(CmcGroup) * groups) + align8(sizeof(CmcGroup) * dgroups) +
+           sizeof(double) * ((3 + SVMC_CMC_GREEKS_ROWS) * total_strikes + static_cast<size_t>(SVMC_CMC_GREEKS_STATS_DOUBLES) * n_expiries);
+}
+
+size_t cmc_greeks_workspace_bytes_of(size_t n_path, int n_expiries, size_t total_strikes)
+{
+    return cmc_workspace_bytes(n_path, n_expiries, total_strikes, static_cast<int>(total_strikes / CMC_KT) + n_expiries,
+                               static_cast<int>(total_strikes / CMC_DKT) + n_expiries);
 }
 
 size_t cmc_payoff_pinned_bytes_of(int n_expiries, size_t total_strikes)
@@ -808,6 +1056,23 @@ int svmc_cmc_payoff_chain(const double *const *mu_snapshots_host, const double *
     return cmc_payoff_chain("svmc_cmc_payoff_chain", mu_snapshots_host, cv_snapshots_host, n_path, forwards_host, discfactors_host,
                             n_expiries, strikes_host, types_host, strike_offsets_host, recenter, prices_host, stderrs_host, stats_host,
                             workspace, workspace_bytes, as_stream(stream), nullptr, 0);
+}
+
+int svmc_cmc_greeks_workspace_bytes(size_t n_path, int n_expiries, size_t total_strikes, size_t *bytes)
+{
+    SVMC_REQUIRE(bytes != nullptr && n_expiries >= 1, "svmc_cmc_greeks_workspace_bytes: null output or no expiries");
+    *bytes = cmc_greeks_workspace_bytes_of(n_path, n_expiries, total_strikes);
+    return SVMC_OK;
+}
+
+int svmc_cmc_greeks_chain(const double *const *mu_snapshots_host, const double *const *cv_snapshots_host, size_t n_path,
+                          const double *forwards_host, const double *discfactors_host, int n_expiries, const double *strikes_host,
+                          const int8_t *types_host, const size_t *strike_offsets_host, int recenter, double *greeks_host,
+                          double *stats_host, void *workspace, size_t workspace_bytes, svmc_stream_t stream)
+{
+    return cmc_greeks_chain("svmc_cmc_greeks_chain", mu_snapshots_host, cv_snapshots_host, n_path, forwards_host, discfactors_host,
+                            n_expiries, strikes_host, types_host, strike_offsets_host, recenter, greeks_host, stats_host, workspace,
+                            workspace_bytes, as_stream(stream), nullptr, 0);
 }
 
 }  // extern "C"

@@ -144,6 +144,14 @@ int cmc_payoff_chain(const char *fn, const double *const *mu_snapshots_host, con
                      const int8_t *types_host, const size_t *strike_offsets_host, int recenter, double *prices_host, double *stderrs_host,
                      double *stats_host, void *workspace, size_t workspace_bytes, hipStream_t stream, void *pinned, size_t pinned_bytes);
 size_t cmc_payoff_pinned_bytes_of(int n_expiries, size_t total_strikes);
+// ... and the tail with the derivatives in F and K (svmc_cmc_greeks_chain's body): greeks_host [SVMC_CMC_GREEKS_ROWS][K], stats_host
+// [m][SVMC_CMC_GREEKS_STATS_DOUBLES]
+size_t cmc_greeks_workspace_bytes_of(size_t n_path, int n_expiries, size_t total_strikes);
+int cmc_greeks_chain(const char *fn, const double *const *mu_snapshots_host, const double *const *cv_snapshots_host, size_t n_path,
+                     const double *forwards_host, const double *discfactors_host, int n_expiries, const double *strikes_host,
+                     const int8_t *types_host, const size_t *strike_offsets_host, int recenter, double *greeks_host, double *stats_host,
+                     void *workspace, size_t workspace_bytes, hipStream_t stream, void *pinned, size_t pinned_bytes);
+size_t cmc_greeks_pinned_bytes_of(int n_expiries, size_t total_strikes);
 // svmc_greeks.hip: the Greeks tail (svmc_greeks_payoff_chain's body) -- its checks, the two launches queued on `stream` from a host
 // image the caller keeps until the stream has passed the upload (rows_host [1 + 2P][m] job-major; base_out / sens_out device or
 // pinned, null: inside the workspace at *results_dev), and the sizes of the workspace and the image

@@ -378,6 +378,30 @@ def cmc_stats_dicts(stats: np.ndarray) -> list:
     return out
 
 
+# ... and its derivatives in F and K (svmc_cmc_greeks_chain): the result rows and the statistics with the count of cv == 0 paths
+CMC_GREEKS_ROWS = 10           # SVMC_CMC_GREEKS_ROWS
+CMC_GREEKS_STATS_DOUBLES = 6   # SVMC_CMC_GREEKS_STATS_DOUBLES
+CMC_GREEKS_FIELDS = ("price", "stderr", "delta", "delta_stderr", "dual_delta", "dual_delta_stderr", "gamma", "gamma_stderr",
+                     "dual_gamma", "dual_gamma_stderr")
+CMC_GREEKS_STATS_FIELDS = CMC_STATS_FIELDS + ("n_zero_cv",)
+
+
+def cmc_greeks_dict(res: np.ndarray, slices: Sequence[slice]) -> dict:
+    """[CMC_GREEKS_ROWS][K] -> {field: [m] -> [K_i]}"""
+    return {name: [res[r, sl] for sl in slices] for r, name in enumerate(CMC_GREEKS_FIELDS)}
+
+
+def cmc_greeks_stats_dicts(stats: np.ndarray) -> list:
+    """[m][CMC_GREEKS_STATS_DOUBLES] -> one dict of CMC_GREEKS_STATS_FIELDS per expiry (the counts as ints)"""
+    out = []
+    for row in np.asarray(stats, dtype=np.float64).reshape(-1, CMC_GREEKS_STATS_DOUBLES):
+        d = dict(zip(CMC_GREEKS_STATS_FIELDS, (float(v) for v in row)))
+        for k in ("n_kept", "n_dropped", "n_zero_cv"):
+            d[k] = int(d[k])
+        out.append(d)
+    return out
+
+
 def tilted_type_codes(optiontypes) -> np.ndarray:
     """'C' -> 0, 'P' -> 1 as int8; any other type raises ValueError("not implemented"), as the Fourier risk-premia slice pricer"""
     types = np.asarray(optiontypes).ravel()
@@ -1122,6 +1146,56 @@ class HipEngine:
             sess, ch["ttms"], ch["forwards"], ch["discfactors"], ch["m"], ch["strikes"], ch["codes"], ch["offsets"], float(v0),
             float(theta), float(kappa), float(rho), float(volvol), int(nb_steps_per_year), int(bool(recenter)), int(seed),
             int(call_id), p, e, st), "heston_chain_cmc_kernel")
+
+    # ---- conditional Monte Carlo Greeks (include/svmc.h): delta, dual delta, gamma, dual gamma ----------------
+    def conditional_greeks(self, forwards, discfactors, strikes: Sequence[np.ndarray], codes: Sequence[np.ndarray],
+                           recenter: bool = True, mu_rows: Optional[Sequence[int]] = None,
+                           cv_rows: Optional[Sequence[int]] = None):
+        """svmc_cmc_greeks_chain on resident (mu, cv), rows as conditional_payoffs.  Returns ({field of CMC_GREEKS_FIELDS: [m] ->
+        [K_i]}, stats [m] dicts of CMC_GREEKS_STATS_FIELDS)."""
+        ch = marshalled_chain(np.zeros(len(strikes)), forwards, discfactors, strikes, codes)
+        m, K = ch["m"], ch["total"]
+        if (mu_rows is None) != (cv_rows is None) or ((m != 1) if mu_rows is None else (len(mu_rows) != m or len(cv_rows) != m)):
+            raise ValueError("one mu row and one cv row per expiry (the current state serves one expiry)")
+        mus = [self.x.ptr] if mu_rows is None else [self.snapshot_ptr(r) for r in mu_rows]
+        cvs = [self.cv.ptr] if cv_rows is None else [self.snapshot_ptr(r) for r in cv_rows]
+        nbytes = C.c_size_t(0)
+        _lib.check(self.lib.svmc_cmc_greeks_workspace_bytes(self.n_path, m, K, C.byref(nbytes)))
+        ws_ptr, _ = self.alloc_sums((nbytes.value + 7) // 8, "cmc_greeks_workspace")
+        res, stats = np.empty((CMC_GREEKS_ROWS, max(K, 1))), np.empty((m, CMC_GREEKS_STATS_DOUBLES))
+        dp = C.POINTER(C.c_double)
+        _lib.check(self.lib.svmc_cmc_greeks_chain(
+            (C.c_void_p * m)(*mus), (C.c_void_p * m)(*cvs), self.n_path, ch["forwards"], ch["discfactors"], m, ch["strikes"],
+            ch["codes"], ch["offsets"], int(bool(recenter)), res.ctypes.data_as(dp), stats.ctypes.data_as(dp), ws_ptr, nbytes.value,
+            self.stream))
+        return cmc_greeks_dict(res, ch["slices"]), cmc_greeks_stats_dicts(stats)
+
+    def _fused_cmc_greeks_call(self, ch: dict, call, kernel_name: str):
+        res, stats = np.empty((CMC_GREEKS_ROWS, max(ch["total"], 1))), np.empty((ch["m"], CMC_GREEKS_STATS_DOUBLES))
+        dp = C.POINTER(C.c_double)
+        self._session_call(ch, lambda sess: call(sess, res.ctypes.data_as(dp), stats.ctypes.data_as(dp)), kernel_name)
+        return cmc_greeks_dict(res, ch["slices"]), cmc_greeks_stats_dicts(stats)
+
+    def price_logsv_chain_cmc_greeks_fused(self, ch: dict, v0, theta, kappa1, kappa2, beta, volvol, etas, is_spot_measure,
+                                           nb_steps_per_year, recenter: bool, seed: int, call_id: int):
+        """logsv_mc_chain_greeks_conditional as ONE svmc_logsv_chain_price_cmc_greeks call on this engine's state; returns
+        (fields, stats) as conditional_greeks"""
+        etas = np.ascontiguousarray(etas, dtype=np.float64)
+        if etas.size != ch["m"]:
+            raise ValueError("vol_backbone_etas must have one entry per maturity")
+        return self._fused_cmc_greeks_call(ch, lambda sess, g, st: self.lib.svmc_logsv_chain_price_cmc_greeks(
+            sess, ch["ttms"], ch["forwards"], ch["discfactors"], etas.ctypes.data_as(C.POINTER(C.c_double)), ch["m"], ch["strikes"],
+            ch["codes"], ch["offsets"], float(v0), float(theta), float(kappa1), float(kappa2), float(beta), float(volvol),
+            int(bool(is_spot_measure)), int(nb_steps_per_year), int(bool(recenter)), int(seed), int(call_id), g, st),
+            "logsv_chain_cmc_kernel")
+
+    def price_heston_chain_cmc_greeks_fused(self, ch: dict, v0, theta, kappa, rho, volvol, nb_steps_per_year, recenter: bool,
+                                            seed: int, call_id: int):
+        """heston_mc_chain_greeks_conditional as ONE svmc_heston_chain_price_cmc_greeks call on this engine's state"""
+        return self._fused_cmc_greeks_call(ch, lambda sess, g, st: self.lib.svmc_heston_chain_price_cmc_greeks(
+            sess, ch["ttms"], ch["forwards"], ch["discfactors"], ch["m"], ch["strikes"], ch["codes"], ch["offsets"], float(v0),
+            float(theta), float(kappa), float(rho), float(volvol), int(nb_steps_per_year), int(bool(recenter)), int(seed),
+            int(call_id), g, st), "heston_chain_cmc_kernel")
 
     # ---- Monte Carlo chain Greeks on common random numbers (include/svmc.h, svmc_greeks.hip) ------------------------------------
     def greeks_payoffs(self, forwards, discfactors, strikes: Sequence[np.ndarray], codes: Sequence[np.ndarray], steps=(),

@@ -26,7 +26,7 @@ from ..utils.config import VariableType
 from ..utils.funcs import next_rng_call, set_time_grid, time_grid_steps, timer
 from ..analytic import AnalyticGrid, chain_prices_from_sums, chain_sums
 from ..utils import mgf_pricer as mgfp
-from .logsv_pricer import _broadcast_state, check_conditional_request
+from .logsv_pricer import _broadcast_state, check_conditional_request, conditional_greeks_shaped, conditional_log_return_pdf
 from .model_pricer import ModelParams, ModelPricer
 
 
@@ -90,6 +90,31 @@ class HestonPricer(ModelPricer):
             scheme=kwargs.get("scheme", "euler"), nb_steps_per_year=kwargs.get("nb_steps_per_year", 360), seed=kwargs.get("seed"),
             comm=kwargs.get("comm"), devices=kwargs.get("devices"), recenter=kwargs.get("recenter", True),
             return_stats=kwargs.get("return_stats", False))
+
+    def model_mc_chain_greeks_conditional(self, option_chain: OptionChain, params: HestonParams, nb_path: int = 100000,
+                                          variable_type: VariableType = VariableType.LOG_RETURN, **kwargs) -> dict:
+        """model_mc_price_chain_conditional with delta, dual delta, gamma and dual gamma (heston_mc_chain_greeks_conditional);
+        recenter= and return_stats= are passed on"""
+        return heston_mc_chain_greeks_conditional(
+            v0=params.v0, theta=params.theta, kappa=params.kappa, rho=params.rho, volvol=params.volvol, ttms=option_chain.ttms,
+            forwards=option_chain.forwards, discfactors=option_chain.discfactors, strikes_ttms=option_chain.strikes_ttms,
+            optiontypes_ttms=option_chain.optiontypes_ttms, nb_path=nb_path, variable_type=variable_type,
+            scheme=kwargs.get("scheme", "euler"), nb_steps_per_year=kwargs.get("nb_steps_per_year", 360), seed=kwargs.get("seed"),
+            comm=kwargs.get("comm"), devices=kwargs.get("devices"), recenter=kwargs.get("recenter", True),
+            return_stats=kwargs.get("return_stats", False))
+
+    def get_log_return_mc_pdf_conditional(self, params: HestonParams, ttm: float, x_grid: np.ndarray, nb_path: int = 100000,
+                                          seed: Optional[int] = None, recenter: bool = False, return_stderr: bool = False,
+                                          nb_steps_per_year: int = 360):
+        """the density of the simulated log-return at x_grid from the conditional estimator's dual gamma, without a bandwidth
+        (logsv_pricer.conditional_log_return_pdf): UN-NORMALISED -- the KDE routes divide by their sum, this one integrates by
+        itself to n_kept_nonzero_cv / n_kept.  recenter=False: the density of the simulated x itself.  With return_stderr=True
+        (pdf, its standard error).  Euler scheme."""
+        def route(**chain):
+            return heston_mc_chain_greeks_conditional(v0=params.v0, theta=params.theta, kappa=params.kappa, rho=params.rho,
+                                                      volvol=params.volvol, nb_path=nb_path, nb_steps_per_year=nb_steps_per_year,
+                                                      seed=seed, recenter=recenter, **chain)
+        return conditional_log_return_pdf(route, ttm, x_grid, return_stderr)
 
     def model_mc_chain_greeks(self, option_chain: OptionChain, params: HestonParams, nb_path: int = 100000,
                               variable_type: VariableType = VariableType.LOG_RETURN, **kwargs) -> dict:
@@ -338,6 +363,25 @@ def heston_mc_chain_pricer_conditional(ttms: np.ndarray, forwards: np.ndarray, d
                                                                                recenter, rng_seed, call_id)
     out = (chain_shaped(prices, strikes_ttms), chain_shaped(stderrs, strikes_ttms))
     return out + (stats,) if return_stats else out
+
+
+def heston_mc_chain_greeks_conditional(ttms: np.ndarray, forwards: np.ndarray, discfactors: np.ndarray,
+                                       strikes_ttms: Sequence[np.ndarray], optiontypes_ttms: Sequence[np.ndarray], v0: float,
+                                       theta: float, kappa: float, rho: float, volvol: float, nb_path: int = 100000,
+                                       variable_type: VariableType = VariableType.LOG_RETURN, scheme="euler",
+                                       nb_steps_per_year: int = 360, seed: Optional[int] = None, comm=None, devices=None,
+                                       reduce: Optional[str] = None, recenter: bool = True, return_stats: bool = False) -> dict:
+    """heston_mc_chain_pricer_conditional with delta, dual delta, gamma and dual gamma and their standard errors (include/svmc.h,
+    DESIGN.md row f13; see logsv_mc_chain_greeks_conditional for the returned dict).  Same signature and refusals, scheme="qe"
+    among them.  Not in the reference API."""
+    codes = check_conditional_request("heston_mc_chain_greeks_conditional", variable_type, comm, devices, optiontypes_ttms)
+    if _scheme_code(scheme) != HESTON_EULER_FLOOR:
+        raise NotImplementedError("heston_mc_chain_greeks_conditional: scheme='qe' is not covered (Euler only)")
+    rng_seed, call_id = next_rng_call(seed)
+    ch = marshalled_chain(ttms, forwards, discfactors, strikes_ttms, codes)
+    fields, stats = get_engine(nb_path).price_heston_chain_cmc_greeks_fused(ch, v0, theta, kappa, rho, volvol, nb_steps_per_year,
+                                                                            recenter, rng_seed, call_id)
+    return conditional_greeks_shaped(fields, stats, strikes_ttms, return_stats)
 
 
 def heston_mc_chain_pricer(ttms: np.ndarray, forwards: np.ndarray, discfactors: np.ndarray,

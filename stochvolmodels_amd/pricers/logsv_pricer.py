@@ -255,6 +255,35 @@ class LogSVPricer(ModelPricer):
             seed=kwargs.get("seed"), comm=kwargs.get("comm"), devices=kwargs.get("devices"),
             recenter=kwargs.get("recenter", True), return_stats=kwargs.get("return_stats", False))
 
+    def model_mc_chain_greeks_conditional(self, option_chain: OptionChain, params: LogSvParams, is_spot_measure: bool = True,
+                                          variable_type: VariableType = VariableType.LOG_RETURN, nb_path: int = 100000,
+                                          nb_steps: Optional[int] = None, **kwargs) -> dict:
+        """model_mc_price_chain_conditional with delta, dual delta, gamma and dual gamma (logsv_mc_chain_greeks_conditional) on the
+        same step rule; recenter= and return_stats= are passed on"""
+        etas = params.get_vol_backbone_etas(ttms=option_chain.ttms)
+        return logsv_mc_chain_greeks_conditional(
+            v0=params.sigma0, theta=params.theta, kappa1=params.kappa1, kappa2=params.kappa2, beta=params.beta, volvol=params.volvol,
+            vol_backbone_etas=etas, ttms=option_chain.ttms, forwards=option_chain.forwards, discfactors=option_chain.discfactors,
+            strikes_ttms=option_chain.strikes_ttms, optiontypes_ttms=option_chain.optiontypes_ttms, is_spot_measure=is_spot_measure,
+            variable_type=variable_type, nb_path=nb_path, nb_steps_per_year=nb_steps or int(360 * np.max(option_chain.ttms)) + 1,
+            seed=kwargs.get("seed"), comm=kwargs.get("comm"), devices=kwargs.get("devices"),
+            recenter=kwargs.get("recenter", True), return_stats=kwargs.get("return_stats", False))
+
+    def get_log_return_mc_pdf_conditional(self, params: LogSvParams, ttm: float, x_grid: np.ndarray, nb_path: int = 100000,
+                                          seed: Optional[int] = None, recenter: bool = False, return_stderr: bool = False,
+                                          nb_steps: Optional[int] = None):
+        """the density of the simulated log-return at x_grid from the conditional estimator's dual gamma, without a bandwidth
+        (conditional_log_return_pdf): UN-NORMALISED -- the KDE routes divide by their sum, this one integrates by itself to
+        n_kept_nonzero_cv / n_kept, the share of the kept paths whose conditional variance is positive (a cv == 0 path is a point
+        mass and adds nothing).  recenter=False: the density of the simulated x itself, as get_log_return_mc_pdf's.  With
+        return_stderr=True (pdf, its standard error)."""
+        def route(**chain):
+            return logsv_mc_chain_greeks_conditional(
+                v0=params.sigma0, theta=params.theta, kappa1=params.kappa1, kappa2=params.kappa2, beta=params.beta,
+                volvol=params.volvol, vol_backbone_etas=params.get_vol_backbone_etas(ttms=np.array([ttm])), nb_path=nb_path,
+                nb_steps_per_year=nb_steps or int(360 * ttm) + 1, seed=seed, recenter=recenter, **chain)
+        return conditional_log_return_pdf(route, ttm, x_grid, return_stderr)
+
     def model_mc_chain_greeks(self, option_chain: OptionChain, params: LogSvParams, is_spot_measure: bool = True,
                               variable_type: VariableType = VariableType.LOG_RETURN, nb_path: int = 100000,
                               nb_steps: Optional[int] = None, **kwargs) -> dict:
@@ -875,6 +904,54 @@ def logsv_mc_chain_pricer_conditional(ttms: np.ndarray, forwards: np.ndarray, di
         ch, v0, theta, kappa1, kappa2, beta, volvol, vol_backbone_etas, is_spot_measure, nb_steps_per_year, recenter, rng_seed, call_id)
     out = (chain_shaped(prices, strikes_ttms), chain_shaped(stderrs, strikes_ttms))
     return out + (stats,) if return_stats else out
+
+
+def conditional_greeks_shaped(fields: dict, stats: list, strikes_ttms: Sequence[np.ndarray], return_stats: bool) -> dict:
+    """an engine's (fields, stats) of the conditional Greeks as the function routes return them: chain-shaped lists per field of
+    engine.CMC_GREEKS_FIELDS, and "stats" (per expiry the dict of engine.CMC_GREEKS_STATS_FIELDS) when asked"""
+    out = {name: chain_shaped(rows, strikes_ttms) for name, rows in fields.items()}
+    if return_stats:
+        out["stats"] = stats
+    return out
+
+
+def logsv_mc_chain_greeks_conditional(ttms: np.ndarray, forwards: np.ndarray, discfactors: np.ndarray,
+                                      strikes_ttms: Sequence[np.ndarray], optiontypes_ttms: Sequence[np.ndarray], v0: float,
+                                      theta: float, kappa1: float, kappa2: float, beta: float, volvol: float,
+                                      vol_backbone_etas: np.ndarray, is_spot_measure: bool = True, nb_path: int = 100000,
+                                      nb_steps_per_year: int = 360, variable_type: VariableType = VariableType.LOG_RETURN,
+                                      seed: Optional[int] = None, comm=None, devices=None, reduce: Optional[str] = None,
+                                      recenter: bool = True, return_stats: bool = False) -> dict:
+    """logsv_mc_chain_pricer_conditional with the derivatives of its prices in the forward and the strike (include/svmc.h, DESIGN.md
+    row f13): per path the Black-76 delta, dual delta and dual gamma in closed form, each with a standard error -- the exact
+    derivatives of the number the conditional pricer returns at the same seed.  Same signature; returns a dict of chain-shaped
+    lists: price, stderr (bit-equal to logsv_mc_chain_pricer_conditional), delta, delta_stderr, dual_delta, dual_delta_stderr,
+    gamma, gamma_stderr, dual_gamma, dual_gamma_stderr; return_stats=True adds "stats", per expiry the dict of
+    engine.CMC_GREEKS_STATS_FIELDS (the conditional pricer's and n_zero_cv, the kept paths whose conditional variance is zero: they
+    add no gamma).  price = F delta + K dual_delta and F^2 gamma = K^2 dual_gamma hold to rounding.  With recenter=True the errors
+    ignore the noise of the recentring mean, as the price's does.  Refusals: check_conditional_request's.  Not in the reference
+    API."""
+    codes = check_conditional_request("logsv_mc_chain_greeks_conditional", variable_type, comm, devices, optiontypes_ttms,
+                                      is_spot_measure)
+    rng_seed, call_id = next_rng_call(seed)
+    ch = marshalled_chain(ttms, forwards, discfactors, strikes_ttms, codes)
+    fields, stats = get_engine(nb_path).price_logsv_chain_cmc_greeks_fused(
+        ch, v0, theta, kappa1, kappa2, beta, volvol, vol_backbone_etas, is_spot_measure, nb_steps_per_year, recenter, rng_seed, call_id)
+    return conditional_greeks_shaped(fields, stats, strikes_ttms, return_stats)
+
+
+def conditional_log_return_pdf(route, ttm: float, x_grid: np.ndarray, return_stderr: bool = False):
+    """the density of the simulated log-return on x_grid from a conditional Greeks route (route(ttms=, forwards=, discfactors=,
+    strikes_ttms=, optiontypes_ttms=) -> its dict): one expiry at forward 1 and discount factor 1 with calls at K_j = exp(x_j), and
+    pdf(x_j) = K_j dual_gamma_j -- the density of the terminal spot at K_j times dK / dx.  Not normalised."""
+    x = np.asarray(x_grid, dtype=np.float64)
+    strikes = np.exp(x.ravel())
+    out = route(ttms=np.array([float(ttm)]), forwards=np.array([1.0]), discfactors=np.array([1.0]), strikes_ttms=[strikes],
+                optiontypes_ttms=[np.full(strikes.size, "C")])
+    pdf = (strikes * out["dual_gamma"][0]).reshape(x.shape)
+    if return_stderr:
+        return pdf, (strikes * out["dual_gamma_stderr"][0]).reshape(x.shape)
+    return pdf
 
 
 def logsv_mc_chain_greeks(params: LogSvParams, ttms: np.ndarray, forwards: np.ndarray, discfactors: np.ndarray,

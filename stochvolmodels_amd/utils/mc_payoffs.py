@@ -90,6 +90,30 @@ def compute_mc_vars_payoff_conditional(mu: np.ndarray, cv: np.ndarray, ttm: floa
     return out + (stats[0],) if return_stats else out
 
 
+def compute_mc_vars_greeks_conditional(mu: np.ndarray, cv: np.ndarray, ttm: float, forward: float, strikes_ttm: np.ndarray,
+                                       optiontypes_ttm: np.ndarray, discfactor: float = 1.0, recenter: bool = True,
+                                       return_stats: bool = False) -> dict:
+    """compute_mc_vars_payoff_conditional with the derivatives of its prices in the forward and the strike (include/svmc.h's
+    svmc_cmc_greeks_chain) from host arrays of one expiry: a dict, in the strikes' shape, of price, stderr, delta, delta_stderr,
+    dual_delta, dual_delta_stderr, gamma, gamma_stderr, dual_gamma, dual_gamma_stderr, and with return_stats=True "stats", the dict
+    of engine.CMC_GREEKS_STATS_FIELDS.  ttm is unused (cv is a TOTAL variance).  'C' / 'P' only (others: ValueError("not
+    implemented"))."""
+    codes = tilted_type_codes(optiontypes_ttm)                   # ValueError("not implemented")
+    strikes = np.asarray(strikes_ttm, dtype=np.float64)
+    mu = np.ascontiguousarray(mu, dtype=np.float64).ravel()
+    cv = np.ascontiguousarray(cv, dtype=np.float64).ravel()
+    if mu.size != cv.size or mu.size == 0:
+        raise ValueError("mu and cv must be non-empty and of one length")
+    eng = get_engine(mu.size)
+    eng.upload(eng.x.ptr, mu)
+    eng.upload(eng.cv.ptr, cv)
+    fields, stats = eng.conditional_greeks([float(forward)], [float(discfactor)], [strikes.ravel()], [codes], bool(recenter))
+    out = {name: rows[0].reshape(strikes.shape) for name, rows in fields.items()}
+    if return_stats:
+        out["stats"] = stats[0]
+    return out
+
+
 def compute_mc_vars_greeks(x0: np.ndarray, forward: float, strikes_ttm: np.ndarray, optiontypes_ttm: np.ndarray,
                            discfactor: float = 1.0, x_up=(), x_dn=(), steps=()) -> dict:
     """the Greeks tail of include/svmc.h's svmc_greeks_payoff_chain on host arrays of one expiry: x0 the base job's terminal
