@@ -972,8 +972,8 @@ SVMC_API int svmc_heston_chain_price_cmc(svmc_session_t session, const double *t
  *   svmc_logsv_chain_price_cmc_greeks / svmc_heston_chain_price_cmc_greeks   the fused drivers: arguments as svmc_*_chain_price_cmc
  *                           with greeks_host for the two arrays; the session's workspace and page-locked block grow as theirs do;
  *                           a sharded session is refused.
- * Left out: parameter sensitivities on this estimator (a many-job conditional stepping kernel), SVMC_INV_CALL / SVMC_INV_PUT,
- * variables other than the log-return, the inverse measure, Heston QE, Hawkes, sharded sessions. */
+ * Parameter sensitivities on this estimator: the row f14 block below.  Left out: SVMC_INV_CALL / SVMC_INV_PUT, variables other than
+ * the log-return, the inverse measure, Heston QE, Hawkes, sharded sessions, a conditional-MC calibration objective. */
 #define SVMC_CMC_GREEKS_KT 4
 #define SVMC_CMC_GREEKS_ROWS 10
 #define SVMC_CMC_GREEKS_STATS_DOUBLES 6
@@ -1066,6 +1066,93 @@ SVMC_API int svmc_heston_chain_price_greeks(svmc_session_t session, const double
                                             const double *params_host, const double *steps_host, int scheme, int nb_steps_per_year,
                                             uint64_t seed, uint32_t call_id, double *prices_host, double *stderrs_host,
                                             double *greeks_host, double *sens_host);
+
+/* ---- conditional Monte Carlo: many jobs in one stepping launch, parameter sensitivities (src svmc_cmc.hip, svmc_chain.hip) ----
+ * MANY JOBS.  svmc_logsv_chain_cmc_many / svmc_heston_chain_cmc_many step n_jobs independent conditional jobs of one step grid in ONE
+ * launch (blockIdx.y = job): a path of job j starts from (mu, cv, vol, qvar) = (0, 0, vol0_j, 0) at step 0 of stream 8 of
+ * (seeds_host[j], call_ids_host[j]) and expiry i goes to row j n_slices + i of mu_snapshots / cv_snapshots (device, caller-owned,
+ * [n_jobs][n_slices][n_path]); nothing is written back.  params_host rows as svmc_*_chain_price_many ([n_jobs][6 + n_slices] /
+ * [n_jobs][5]); every job has its own `joined` mask, by the rule of svmc_*_chain_cmc.  Row j n_slices + i is BIT-EQUAL to what
+ * svmc_logsv_chain_cmc / svmc_heston_chain_cmc write for that job alone from a uniform start, in both launch forms (chosen by
+ * n_jobs x n_path), whatever other jobs share the launch.  1 <= n_jobs <= SVMC_MANY_MAX_JOBS, 1 <= n_slices <= 16; `workspace`:
+ * device memory of svmc_cmc_many_workspace_bytes(n_jobs, n_slices) for the job table; returns after the stream is synchronised.
+ * svmc_logsv_chain_price_cmc_many / svmc_heston_chain_price_cmc_many: that launch on a session, then per job the tail of
+ * svmc_cmc_payoff_chain on its rows: job j's prices_host / stderrs_host row ([n_jobs][sum K_i]) and stats_host block (nullable,
+ * [n_jobs][n_expiries][SVMC_CMC_STATS_DOUBLES]) are those of svmc_*_chain_price_cmc with its parameters and stream, bit for bit.
+ *
+ * SENSITIVITIES.  The jobs are base, up_0, dn_0, up_1, ... as in the Greeks block above, on ONE (seed, call id) of stream 8 and
+ * stepped by one launch.  Everything of the conditional estimator stands PER JOB j: the keep rule, e = exp(mu + cv / 2), c_j =
+ * mean_kept_j(e) - 1 with recentring and 0 without, K'_j = K + F c_j, the degenerate cases.  B is the undiscounted per-path Black-76
+ * price of the payoff block, B_k the per-path dual delta of the Greeks block.
+ *   JOB PASS: every up and dn job gets its forward statistics as svmc_cmc_payoff_chain forms them (its own two kernels) and, per
+ *     quote, q_j = mean_kept_j(B_k); q_j stays on the device.
+ *   PAIR PASS, parameter p with step h_p: a pair (path i) is kept iff the path is kept in both jobs; d_i = B_i^up - B_i^dn;
+ *     sens_p = DF mean_pairs(d) / (2 h_p); n_pairs is returned; no kept pair gives NaN with n_pairs = 0 and is not an error.
+ *     ERROR: DF x population deviation over the pairs of dt / sqrt(n_path) / (2 h_p); with recentring dt_i = d_i + F (q_up (e_i^up
+ *     - 1) - q_dn (e_i^dn - 1)), without it dt_i = d_i.  c_up and c_dn are sample means and a price moves by F B_k per unit of its
+ *     own c: the extra term is the delta-method term of the two recentring means, without which the deviation of d misstates the
+ *     error of the difference (an at-the-money put's several times over).
+ *   The sums are taken of value_i - value_path0 (paths that agree to the bit give an error of exactly 0); where path 0 of the expiry
+ *   is not a kept pair the shift is 0.  Every sum's order depends on n_path alone (path blocks min(ceil(n_path / 256), 1024), columns
+ *   in row order): a quote's numbers are the same bits whichever strikes, expiries or pairs share the call.
+ *   svmc_cmc_sens_chain   model-agnostic, on any device arrays: up_mu / up_cv / dn_mu / dn_cv [n_params][n_expiries] HOST arrays of
+ *                         DEVICE pointers ([n_path] each); steps_host [n_params] positive and finite; sens_host
+ *                         [n_params][SVMC_CMC_SENS_ROWS][K] = {sens, its error, n_pairs}.  One upload, six launches whatever
+ *                         n_params (four without recentring: q is not read), one download, one synchronize.  `workspace`: device
+ *                         memory of svmc_cmc_sens_workspace_bytes(n_path, n_expiries, K, n_params).  n_params in [1,
+ *                         SVMC_GREEKS_MAX_PARAMS].
+ *   svmc_logsv_chain_price_cmc_sens / svmc_heston_chain_price_cmc_sens   the fused drivers: arguments as svmc_*_chain_price_greeks
+ *                         plus recenter; the 1 + 2 n_params rows of params_host on one stepping launch, the tail above on the bumped
+ *                         jobs' rows, then svmc_cmc_greeks_chain's six launches on job 0's rows: greeks_host
+ *                         [SVMC_CMC_GREEKS_ROWS][K] and stats_host (nullable) are bit-equal to svmc_*_chain_price_cmc_greeks at
+ *                         the same seed.  Everything on the session's stream, ONE synchronize; the session grows a workspace of
+ *                         its own on demand and later single calls are undisturbed.  sens_host may be NULL at n_params = 0.
+ * Checked before anything is launched, status codes as the Greeks block above: a null pointer, counts out of range (the fused and
+ * many-job calls: n_expiries outside [1, 16]), a step or forward that is not positive and finite, a strike or discount factor that
+ * is not finite, a sharded session (SVMC_ERR_INVALID_ARGUMENT); a type other than SVMC_CALL / SVMC_PUT (SVMC_ERR_UNKNOWN_PAYOFF); a
+ * workspace or session too small (SVMC_ERR_WORKSPACE).
+ * Left out: SVMC_INV_CALL / SVMC_INV_PUT, variables other than the log-return, the inverse measure, Heston QE, Hawkes, sharded
+ * sessions, a conditional-MC calibration objective. */
+#define SVMC_CMC_SENS_ROWS 3
+SVMC_API int svmc_cmc_many_workspace_bytes(int n_jobs, int n_slices, size_t *bytes);
+SVMC_API int svmc_logsv_chain_cmc_many(size_t n_path, int n_jobs, int n_slices, const int *nb_steps_host, const double *dts_host,
+                                       const double *params_host, int is_spot_measure, const uint64_t *seeds_host,
+                                       const uint32_t *call_ids_host, uint64_t path_offset, double *mu_snapshots,
+                                       double *cv_snapshots, void *workspace, size_t workspace_bytes, svmc_stream_t stream);
+SVMC_API int svmc_heston_chain_cmc_many(size_t n_path, int n_jobs, int n_slices, const int *nb_steps_host, const double *dts_host,
+                                        const double *params_host, const uint64_t *seeds_host, const uint32_t *call_ids_host,
+                                        uint64_t path_offset, double *mu_snapshots, double *cv_snapshots, void *workspace,
+                                        size_t workspace_bytes, svmc_stream_t stream);
+SVMC_API int svmc_cmc_sens_workspace_bytes(size_t n_path, int n_expiries, size_t total_strikes, int n_params, size_t *bytes);
+SVMC_API int svmc_cmc_sens_chain(const double *const *up_mu_host, const double *const *up_cv_host, const double *const *dn_mu_host,
+                                 const double *const *dn_cv_host, size_t n_path, const double *forwards_host,
+                                 const double *discfactors_host, int n_expiries, const double *strikes_host, const int8_t *types_host,
+                                 const size_t *strike_offsets_host, int n_params, const double *steps_host, int recenter,
+                                 double *sens_host, void *workspace, size_t workspace_bytes, svmc_stream_t stream);
+SVMC_API int svmc_logsv_chain_price_cmc_many(svmc_session_t session, const double *ttms_host, const double *forwards_host,
+                                             const double *discfactors_host, int n_expiries, const double *strikes_host,
+                                             const int8_t *types_host, const size_t *strike_offsets_host, int n_jobs,
+                                             const double *params_host, const uint64_t *seeds_host, const uint32_t *call_ids_host,
+                                             int is_spot_measure, int nb_steps_per_year, int recenter, double *prices_host,
+                                             double *stderrs_host, double *stats_host);
+SVMC_API int svmc_heston_chain_price_cmc_many(svmc_session_t session, const double *ttms_host, const double *forwards_host,
+                                              const double *discfactors_host, int n_expiries, const double *strikes_host,
+                                              const int8_t *types_host, const size_t *strike_offsets_host, int n_jobs,
+                                              const double *params_host, const uint64_t *seeds_host, const uint32_t *call_ids_host,
+                                              int nb_steps_per_year, int recenter, double *prices_host, double *stderrs_host,
+                                              double *stats_host);
+SVMC_API int svmc_logsv_chain_price_cmc_sens(svmc_session_t session, const double *ttms_host, const double *forwards_host,
+                                             const double *discfactors_host, int n_expiries, const double *strikes_host,
+                                             const int8_t *types_host, const size_t *strike_offsets_host, int n_params,
+                                             const double *params_host, const double *steps_host, int is_spot_measure,
+                                             int nb_steps_per_year, int recenter, uint64_t seed, uint32_t call_id,
+                                             double *greeks_host, double *stats_host, double *sens_host);
+SVMC_API int svmc_heston_chain_price_cmc_sens(svmc_session_t session, const double *ttms_host, const double *forwards_host,
+                                              const double *discfactors_host, int n_expiries, const double *strikes_host,
+                                              const int8_t *types_host, const size_t *strike_offsets_host, int n_params,
+                                              const double *params_host, const double *steps_host, int nb_steps_per_year,
+                                              int recenter, uint64_t seed, uint32_t call_id, double *greeks_host,
+                                              double *stats_host, double *sens_host);
 
 #ifdef __cplusplus
 }

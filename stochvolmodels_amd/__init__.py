@@ -2,10 +2,10 @@
 stochvolmodels_amd -- MI355X-native Monte Carlo engine for the StochVolModels hot path.
 
 Module layout and public names mirror the reference package (`stochvolmodels`) for the Monte Carlo path:
-    stochvolmodels_amd.pricers.logsv_pricer   LogSVPricer, logsv_mc_chain_pricer(_fixed_randoms, _many, _conditional),
+    stochvolmodels_amd.pricers.logsv_pricer   LogSVPricer, logsv_mc_chain_pricer(_fixed_randoms, _many, _conditional, _conditional_many),
                                               logsv_mc_chain_greeks(_conditional), simulate_logsv_x_vol_terminal,
                                               get_randoms_for_chain_valuation
-    stochvolmodels_amd.pricers.heston_pricer  HestonPricer, HestonParams, heston_mc_chain_pricer(_many, _conditional),
+    stochvolmodels_amd.pricers.heston_pricer  HestonPricer, HestonParams, heston_mc_chain_pricer(_many, _conditional, _conditional_many),
                                               heston_mc_chain_greeks(_conditional), simulate_heston_x_vol_terminal
     stochvolmodels_amd.pricers.hawkes_jd_pricer  HawkesJDPricer, HawkesJDParams, hawkesjd_mc_chain_pricer,
                                               hawkesjd_chain_pricer(_batch), simulate_hawkesjd_terminal,
@@ -17,7 +17,8 @@ Module layout and public names mirror the reference package (`stochvolmodels`) f
     stochvolmodels_amd.pricers.il_pricer      logsv_il_pricer(_vector, _batch), square_root_payoff_pricer_with_mgf_grid,
                                               compute_mc_il_payoff
     stochvolmodels_amd.utils.mc_payoffs       compute_mc_vars_payoff, compute_mc_vars_payoff_with_gamma,
-                                              compute_mc_vars_payoff_conditional, compute_mc_vars_greeks(_conditional)
+                                              compute_mc_vars_payoff_conditional, compute_mc_vars_greeks(_conditional),
+                                              compute_mc_vars_sens_conditional
     stochvolmodels_amd.utils.funcs            set_time_grid, set_seed, timer
     stochvolmodels_amd.utils.config           OptionType, VariableType
     stochvolmodels_amd.data.option_chain      OptionChain
@@ -40,6 +41,7 @@ _EXPORTS = {
     "compute_mc_vars_payoff_conditional": "utils.mc_payoffs",
     "compute_mc_vars_greeks": "utils.mc_payoffs",
     "compute_mc_vars_greeks_conditional": "utils.mc_payoffs",
+    "compute_mc_vars_sens_conditional": "utils.mc_payoffs",
     "hawkesjd_mc_chain_pricer_with_risk_premia": "pricers.hawkes_jd_pricer",
     "hawkesjd_mc_chain_pricer_with_risk_premia_gammas": "pricers.hawkes_jd_pricer",
     "hawkesjd_mc_chain_pricer_many": "pricers.hawkes_jd_pricer",
@@ -54,6 +56,7 @@ _EXPORTS = {
     "logsv_mc_chain_pricer_conditional": "pricers.logsv_pricer",
     "logsv_mc_chain_greeks": "pricers.logsv_pricer",
     "logsv_mc_chain_greeks_conditional": "pricers.logsv_pricer",
+    "logsv_mc_chain_pricer_conditional_many": "pricers.logsv_pricer",
     "logsv_mc_chain_pricer_fixed_randoms": "pricers.logsv_pricer",
     "simulate_logsv_x_vol_terminal": "pricers.logsv_pricer",
     "simulate_vol_paths": "pricers.logsv_pricer",
@@ -80,6 +83,7 @@ _EXPORTS = {
     "heston_mc_chain_pricer_conditional": "pricers.heston_pricer",
     "heston_mc_chain_greeks": "pricers.heston_pricer",
     "heston_mc_chain_greeks_conditional": "pricers.heston_pricer",
+    "heston_mc_chain_pricer_conditional_many": "pricers.heston_pricer",
     "simulate_heston_x_vol_terminal": "pricers.heston_pricer",
     "compute_analytic_qvar": "pricers.logsv.vol_moments_ode",
     "compute_analytic_vol_moments": "pricers.logsv.vol_moments_ode",

@@ -189,6 +189,22 @@ def _declare(L: C.CDLL) -> None:
                                                i32, u64, u32, pf64, pf64], i32),
         "svmc_heston_chain_price_cmc_greeks": ([vp, pf64, pf64, pf64, i32, pf64, pi8, psz, f64, f64, f64, f64, f64, i32, i32, u64, u32,
                                                 pf64, pf64], i32),
+        "svmc_cmc_many_workspace_bytes": ([i32, i32, psz], i32),
+        "svmc_logsv_chain_cmc_many": ([sz, i32, i32, C.POINTER(i32), pf64, pf64, i32, C.POINTER(u64), C.POINTER(u32), u64, vp, vp, vp, sz,
+                                       vp], i32),
+        "svmc_heston_chain_cmc_many": ([sz, i32, i32, C.POINTER(i32), pf64, pf64, C.POINTER(u64), C.POINTER(u32), u64, vp, vp, vp, sz,
+                                        vp], i32),
+        "svmc_cmc_sens_workspace_bytes": ([sz, i32, sz, i32, psz], i32),
+        "svmc_cmc_sens_chain": ([C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), sz, pf64, pf64, i32, pf64, pi8, psz, i32,
+                                 pf64, i32, pf64, vp, sz, vp], i32),
+        "svmc_logsv_chain_price_cmc_many": ([vp, pf64, pf64, pf64, i32, pf64, pi8, psz, i32, pf64, C.POINTER(u64), C.POINTER(u32), i32,
+                                             i32, i32, pf64, pf64, pf64], i32),
+        "svmc_heston_chain_price_cmc_many": ([vp, pf64, pf64, pf64, i32, pf64, pi8, psz, i32, pf64, C.POINTER(u64), C.POINTER(u32), i32,
+                                              i32, pf64, pf64, pf64], i32),
+        "svmc_logsv_chain_price_cmc_sens": ([vp, pf64, pf64, pf64, i32, pf64, pi8, psz, i32, pf64, pf64, i32, i32, i32, u64, u32, pf64,
+                                             pf64, pf64], i32),
+        "svmc_heston_chain_price_cmc_sens": ([vp, pf64, pf64, pf64, i32, pf64, pi8, psz, i32, pf64, pf64, i32, i32, u64, u32, pf64,
+                                              pf64, pf64], i32),
         "svmc_hawkesjd_chain_price_tilted": ([vp, pf64, pf64, i32, pf64, pi8, psz, pf64, i32, u64, u32, pf64, i32, i32, pf64, pf64,
                                               pf64], i32),
         "svmc_greeks_payoff_workspace_bytes": ([sz, i32, sz, i32, psz], i32),

@@ -91,6 +91,11 @@ struct Session {
     // svmc_*_chain_price_greeks: the Greeks tail's workspace and its page-locked block (the table's image, then the results)
     void *greeks_ws = nullptr, *greeks_pinned = nullptr;   // device, pinned
     size_t greeks_ws_bytes = 0, greeks_pinned_bytes = 0;
+    // svmc_*_chain_price_cmc_many / _cmc_sens: the jobs' mu and cv rows, the job table (device, pinned), the sensitivity tail's
+    // workspace and its page-locked block (the table's image, then the results), grown on demand
+    double *cmany_snap = nullptr;
+    void *cmany_table_dev = nullptr, *cmany_table_host = nullptr, *csens_ws = nullptr, *csens_pinned = nullptr;
+    size_t cmany_snap_bytes = 0, cmany_table_bytes = 0, cmany_table_host_bytes = 0, csens_ws_bytes = 0, csens_pinned_bytes = 0;
 };
 
 // events around a stepping call of a timed session (no-ops otherwise)
@@ -144,6 +149,10 @@ static void session_release(Session *s)
     if (s->cmc_pinned != nullptr) (void)hipHostFree(s->cmc_pinned);
     if (s->greeks_ws != nullptr) (void)hipFree(s->greeks_ws);
     if (s->greeks_pinned != nullptr) (void)hipHostFree(s->greeks_pinned);
+    for (void *p : {static_cast<void *>(s->cmany_snap), s->cmany_table_dev, s->csens_ws})
+        if (p != nullptr) (void)hipFree(p);
+    for (void *p : {s->cmany_table_host, s->csens_pinned})
+        if (p != nullptr) (void)hipHostFree(p);
     ManyBuffers &mb = s->many;
     for (void *p : {static_cast<void *>(mb.snap), static_cast<void *>(mb.spot_ws), static_cast<void *>(mb.spot),
                     static_cast<void *>(mb.sums), mb.ws, mb.table_dev})
@@ -1491,6 +1500,228 @@ int svmc_session_state(svmc_session_t session, double *x_host, double *vol_host,
     if (qvar_host) SVMC_HIP_TRY(hipMemcpyAsync(qvar_host, s->qvar, nb, hipMemcpyDeviceToHost, s->stream));
     SVMC_HIP_TRY(hipStreamSynchronize(s->stream));
     return SVMC_OK;
+}
+
+}  // extern "C"
+
+// ---- many conditional jobs of one chain and the conditional estimator's parameter sensitivities (include/svmc.h, DESIGN.md row
+// f14; kernels and tails: svmc_cmc.hip).  The first half of both drivers: every check (check(): the caller's own), the session's
+// buffers -- job j's mu rows at j m + i of s->cmany_snap, its cv rows J m rows further --, then step(nbs, dts, mu, cv): the model's ONE
+// stepping launch of every job.
+template <class Check, class Step>
+static int cmc_many_step(const char *fn, Session *s, const ChainView &c, int n_jobs, const void *params, const uint64_t *seeds,
+                         const uint32_t *call_ids, int nb_steps_per_year, const double *out_a, const double *out_b, Check &&check,
+                         Step &&step)
+{
+    SVMC_REQUIRE(s != nullptr, std::string(fn) + ": null session");
+    SVMC_REQUIRE(n_jobs >= 1 && n_jobs <= SVMC_MANY_MAX_JOBS, std::string(fn) + ": n_jobs must be in [1, SVMC_MANY_MAX_JOBS]");
+    SVMC_REQUIRE(params && seeds && call_ids && c.ttms && c.forwards && c.discfactors && c.strikes && c.types && c.offsets && out_a && out_b,
+                 std::string(fn) + ": null pointer");
+    SVMC_REQUIRE(c.m >= 1 && c.m <= MAX_FUSED_SLICES, std::string(fn) + ": 1 to 16 expiries");
+    if (c.m > s->max_expiries || c.offsets[c.m] > s->max_strikes)
+        return fail(SVMC_ERR_WORKSPACE, std::string(fn) + ": the chain exceeds the session (max_expiries / max_strikes_total)");
+    SVMC_REQUIRE(!s->sharded(), std::string(fn) + ": the conditional estimator is not sharded");
+    SVMC_REQUIRE(nb_steps_per_year > 0, std::string(fn) + ": nb_steps_per_year must be positive");
+    for (int j = 0; j < n_jobs; ++j) SVMC_REQUIRE(call_ids[j] < (1u << 24), std::string(fn) + ": call_id must fit 24 bits");
+    for (int i = 0; i < c.m; ++i) {
+        SVMC_REQUIRE(c.offsets[i] <= c.offsets[i + 1], std::string(fn) + ": strike offsets must not decrease");
+        SVMC_REQUIRE(std::isfinite(c.forwards[i]) && c.forwards[i] > 0.0, std::string(fn) + ": a forward is not positive and finite");
+        SVMC_REQUIRE(std::isfinite(c.discfactors[i]), std::string(fn) + ": a discount factor is not finite");
+    }
+    for (size_t k = 0; k < c.offsets[c.m]; ++k) {
+        if (c.types[k] != SVMC_CALL && c.types[k] != SVMC_PUT) return fail(SVMC_ERR_UNKNOWN_PAYOFF, "unknown option payoff code");
+        SVMC_REQUIRE(std::isfinite(c.strikes[k]), std::string(fn) + ": a strike is not finite");
+    }
+    if (int rc = check()) return rc;
+    if (int rc = check_chain(fn, s, c, SVMC_LOG_RETURN, out_a, out_b, true)) return rc;
+    const size_t n = s->n_path, J = static_cast<size_t>(n_jobs), m = static_cast<size_t>(c.m);
+    const size_t table = cmc_many_table_bytes(n_jobs, c.m);
+    SVMC_HIP_TRY(grow(reinterpret_cast<void **>(&s->cmany_snap), s->cmany_snap_bytes, 2 * J * m * n * sizeof(double), false));
+    SVMC_HIP_TRY(grow(&s->cmany_table_dev, s->cmany_table_bytes, table, false));
+    SVMC_HIP_TRY(grow(&s->cmany_table_host, s->cmany_table_host_bytes, table, true));
+    std::vector<int> nbs;
+    std::vector<double> dts;
+    expiry_grids(c, nb_steps_per_year, nbs, dts);
+    stepping_begin(s);
+    if (int rc = step(nbs, dts, s->cmany_snap, s->cmany_snap + J * m * n)) return rc;
+    stepping_end(s);
+    return SVMC_OK;
+}
+
+// job j's mu and cv rows after cmc_many_step
+static void cmc_many_rows(const Session *s, const ChainView &c, int n_jobs, int j, std::vector<const double *> &mus, std::vector<const double *> &cvs)
+{
+    const size_t n = s->n_path, m = static_cast<size_t>(c.m), J = static_cast<size_t>(n_jobs);
+    mus.resize(m);
+    cvs.resize(m);
+    for (size_t i = 0; i < m; ++i) {
+        mus[i] = s->cmany_snap + (static_cast<size_t>(j) * m + i) * n;
+        cvs[i] = s->cmany_snap + ((J + static_cast<size_t>(j)) * m + i) * n;
+    }
+}
+
+// the many-job conditional pricer: cmc_many_step, then per job svmc_cmc_payoff_chain's tail on its rows (each ends synchronised)
+template <class Step>
+static int chain_price_cmc_many(const char *fn, Session *s, const ChainView &c, int n_jobs, const void *params, const uint64_t *seeds,
+                                const uint32_t *call_ids, int nb_steps_per_year, int recenter, double *prices, double *stderrs,
+                                double *stats, Step &&step)
+{
+    if (int rc = cmc_many_step(fn, s, c, n_jobs, params, seeds, call_ids, nb_steps_per_year, prices, stderrs, [&]() -> int {
+        const size_t K = c.offsets[c.m];
+        SVMC_HIP_TRY(grow(&s->cmc_ws, s->cmc_ws_bytes, cmc_payoff_workspace_bytes_of(s->n_path, c.m, K), false));
+        SVMC_HIP_TRY(grow(&s->cmc_pinned, s->cmc_pinned_bytes, cmc_payoff_pinned_bytes_of(c.m, K), true));
+        return SVMC_OK;
+    }, step))
+        return rc;
+    const size_t K = c.offsets[c.m];
+    std::vector<const double *> mus, cvs;
+    for (int j = 0; j < n_jobs; ++j) {
+        cmc_many_rows(s, c, n_jobs, j, mus, cvs);
+        if (int rc = cmc_payoff_chain(fn, mus.data(), cvs.data(), s->n_path, c.forwards, c.discfactors, c.m, c.strikes, c.types, c.offsets,
+                                      recenter, prices + K * j, stderrs + K * j,
+                                      stats ? stats + static_cast<size_t>(SVMC_CMC_STATS_DOUBLES) * c.m * j : nullptr, s->cmc_ws,
+                                      s->cmc_ws_bytes, s->stream, s->cmc_pinned, s->cmc_pinned_bytes))
+            return rc;
+    }
+    stepping_read(s);
+    return SVMC_OK;
+}
+
+// the fused sensitivity driver: the 1 + 2P rows of `params` on one (seed, call id) and one stepping launch, the sensitivity tail on
+// the bumped jobs' rows with its results copied into page-locked memory, then svmc_cmc_greeks_chain's tail on job 0's rows, whose
+// synchronisation is the call's only one
+template <class Step>
+static int chain_price_cmc_sens(const char *fn, Session *s, const ChainView &c, int n_params, const double *params, const double *steps,
+                                int nb_steps_per_year, int recenter, uint64_t seed, uint32_t call_id, double *greeks, double *stats,
+                                double *sens, Step &&step)
+{
+    SVMC_REQUIRE(n_params >= 0 && n_params <= SVMC_GREEKS_MAX_PARAMS, std::string(fn) + ": n_params must be in [0, SVMC_GREEKS_MAX_PARAMS]");
+    SVMC_REQUIRE(greeks != nullptr && (n_params == 0 || (sens != nullptr && steps != nullptr)), std::string(fn) + ": null pointer");
+    const int P = n_params, J = 1 + 2 * P;
+    const std::vector<uint64_t> seeds(J, seed);
+    const std::vector<uint32_t> call_ids(J, call_id);
+    size_t image_bytes = 0;
+    if (int rc = cmc_many_step(fn, s, c, J, params, seeds.data(), call_ids.data(), nb_steps_per_year, greeks, greeks, [&]() -> int {
+        const size_t K = c.offsets[c.m];
+        if (P > 0) {
+            if (int rc = cmc_sens_check(fn, s->n_path, c.forwards, c.discfactors, c.m, c.strikes, c.types, c.offsets, P, steps)) return rc;
+            image_bytes = cmc_sens_image_bytes_of(c.m, K, P);
+            SVMC_HIP_TRY(grow(&s->csens_ws, s->csens_ws_bytes, cmc_sens_workspace_bytes_of(s->n_path, c.m, K, P), false));
+            SVMC_HIP_TRY(grow(&s->csens_pinned, s->csens_pinned_bytes,
+                              image_bytes + static_cast<size_t>(SVMC_CMC_SENS_ROWS) * P * (K > 0 ? K : 1) * sizeof(double), true));
+        }
+        SVMC_HIP_TRY(grow(&s->cmc_ws, s->cmc_ws_bytes, cmc_greeks_workspace_bytes_of(s->n_path, c.m, K), false));
+        SVMC_HIP_TRY(grow(&s->cmc_pinned, s->cmc_pinned_bytes, cmc_greeks_pinned_bytes_of(c.m, K), true));
+        return SVMC_OK;
+    },
+                               [&](const std::vector<int> &nbs, const std::vector<double> &dts, double *mu, double *cv) {
+        return step(nbs, dts, seeds.data(), call_ids.data(), mu, cv);
+    }))
+        return rc;
+    const size_t n = s->n_path, m = static_cast<size_t>(c.m), K = c.offsets[c.m];
+    double *sens_out = nullptr;
+    if (P > 0) {
+        std::vector<const double *> up_mu(P * m), up_cv(P * m), dn_mu(P * m), dn_cv(P * m);
+        const double *mu0 = s->cmany_snap, *cv0 = s->cmany_snap + static_cast<size_t>(J) * m * n;
+        for (size_t p = 0; p < static_cast<size_t>(P); ++p)
+            for (size_t i = 0; i < m; ++i) {
+                const size_t up = ((1 + 2 * p) * m + i) * n, dn = ((2 + 2 * p) * m + i) * n;
+                up_mu[p * m + i] = mu0 + up;
+                up_cv[p * m + i] = cv0 + up;
+                dn_mu[p * m + i] = mu0 + dn;
+                dn_cv[p * m + i] = cv0 + dn;
+            }
+        double *res = nullptr;
+        if (int rc = cmc_sens_enqueue(fn, up_mu.data(), up_cv.data(), dn_mu.data(), dn_cv.data(), n, c.forwards, c.discfactors, c.m, c.strikes,
+                                      c.types, c.offsets, P, steps, recenter, s->csens_pinned, s->csens_ws, s->csens_ws_bytes, s->stream, &res))
+            return rc;
+        sens_out = reinterpret_cast<double *>(static_cast<unsigned char *>(s->csens_pinned) + image_bytes);
+        if (K > 0)
+            SVMC_HIP_TRY(hipMemcpyAsync(sens_out, res, static_cast<size_t>(SVMC_CMC_SENS_ROWS) * P * K * sizeof(double), hipMemcpyDeviceToHost,
+                                        s->stream));
+    }
+    std::vector<const double *> mus, cvs;
+    cmc_many_rows(s, c, J, 0, mus, cvs);
+    if (int rc = cmc_greeks_chain(fn, mus.data(), cvs.data(), n, c.forwards, c.discfactors, c.m, c.strikes, c.types, c.offsets, recenter,
+                                  greeks, stats, s->cmc_ws, s->cmc_ws_bytes, s->stream, s->cmc_pinned, s->cmc_pinned_bytes))
+        return rc;                                         // (returns synchronised: the sensitivities have landed too)
+    stepping_read(s);
+    if (P > 0 && K > 0) memcpy(sens, sens_out, static_cast<size_t>(SVMC_CMC_SENS_ROWS) * P * K * sizeof(double));
+    return SVMC_OK;
+}
+
+extern "C" {
+
+int svmc_logsv_chain_price_cmc_many(svmc_session_t session, const double *ttms_host, const double *forwards_host,
+                                    const double *discfactors_host, int n_expiries, const double *strikes_host, const int8_t *types_host,
+                                    const size_t *strike_offsets_host, int n_jobs, const double *params_host, const uint64_t *seeds_host,
+                                    const uint32_t *call_ids_host, int is_spot_measure, int nb_steps_per_year, int recenter,
+                                    double *prices_host, double *stderrs_host, double *stats_host)
+{
+    const char *fn = "svmc_logsv_chain_price_cmc_many";
+    const ChainView c = {n_expiries, ttms_host, forwards_host, discfactors_host, strikes_host, types_host, strike_offsets_host};
+    Session *s = reinterpret_cast<Session *>(session);
+    return chain_price_cmc_many(fn, s, c, n_jobs, params_host, seeds_host, call_ids_host, nb_steps_per_year, recenter, prices_host,
+                                stderrs_host, stats_host,
+                                [&](const std::vector<int> &nbs, const std::vector<double> &dts, double *mu, double *cv) {
+        return logsv_cmc_step_many(fn, s->n_path, n_jobs, c.m, nbs.data(), dts.data(), params_host, is_spot_measure, seeds_host, call_ids_host,
+                                   s->path_offset, s->cmany_table_host, s->cmany_table_dev, mu, cv, s->stream);
+    });
+}
+
+int svmc_heston_chain_price_cmc_many(svmc_session_t session, const double *ttms_host, const double *forwards_host,
+                                     const double *discfactors_host, int n_expiries, const double *strikes_host, const int8_t *types_host,
+                                     const size_t *strike_offsets_host, int n_jobs, const double *params_host, const uint64_t *seeds_host,
+                                     const uint32_t *call_ids_host, int nb_steps_per_year, int recenter, double *prices_host,
+                                     double *stderrs_host, double *stats_host)
+{
+    const char *fn = "svmc_heston_chain_price_cmc_many";
+    const ChainView c = {n_expiries, ttms_host, forwards_host, discfactors_host, strikes_host, types_host, strike_offsets_host};
+    Session *s = reinterpret_cast<Session *>(session);
+    return chain_price_cmc_many(fn, s, c, n_jobs, params_host, seeds_host, call_ids_host, nb_steps_per_year, recenter, prices_host,
+                                stderrs_host, stats_host,
+                                [&](const std::vector<int> &nbs, const std::vector<double> &dts, double *mu, double *cv) {
+        return heston_cmc_step_many(fn, s->n_path, n_jobs, c.m, nbs.data(), dts.data(), params_host, seeds_host, call_ids_host,
+                                    s->path_offset, s->cmany_table_host, s->cmany_table_dev, mu, cv, s->stream);
+    });
+}
+
+int svmc_logsv_chain_price_cmc_sens(svmc_session_t session, const double *ttms_host, const double *forwards_host,
+                                    const double *discfactors_host, int n_expiries, const double *strikes_host, const int8_t *types_host,
+                                    const size_t *strike_offsets_host, int n_params, const double *params_host, const double *steps_host,
+                                    int is_spot_measure, int nb_steps_per_year, int recenter, uint64_t seed, uint32_t call_id,
+                                    double *greeks_host, double *stats_host, double *sens_host)
+{
+    const char *fn = "svmc_logsv_chain_price_cmc_sens";
+    const ChainView c = {n_expiries, ttms_host, forwards_host, discfactors_host, strikes_host, types_host, strike_offsets_host};
+    Session *s = reinterpret_cast<Session *>(session);
+    const int n_jobs = 1 + 2 * n_params;
+    return chain_price_cmc_sens(fn, s, c, n_params, params_host, steps_host, nb_steps_per_year, recenter, seed, call_id, greeks_host,
+                                stats_host, sens_host,
+                                [&](const std::vector<int> &nbs, const std::vector<double> &dts, const uint64_t *seeds, const uint32_t *call_ids,
+                                    double *mu, double *cv) {
+        return logsv_cmc_step_many(fn, s->n_path, n_jobs, c.m, nbs.data(), dts.data(), params_host, is_spot_measure, seeds, call_ids,
+                                   s->path_offset, s->cmany_table_host, s->cmany_table_dev, mu, cv, s->stream);
+    });
+}
+
+int svmc_heston_chain_price_cmc_sens(svmc_session_t session, const double *ttms_host, const double *forwards_host,
+                                     const double *discfactors_host, int n_expiries, const double *strikes_host, const int8_t *types_host,
+                                     const size_t *strike_offsets_host, int n_params, const double *params_host, const double *steps_host,
+                                     int nb_steps_per_year, int recenter, uint64_t seed, uint32_t call_id, double *greeks_host,
+                                     double *stats_host, double *sens_host)
+{
+    const char *fn = "svmc_heston_chain_price_cmc_sens";
+    const ChainView c = {n_expiries, ttms_host, forwards_host, discfactors_host, strikes_host, types_host, strike_offsets_host};
+    Session *s = reinterpret_cast<Session *>(session);
+    const int n_jobs = 1 + 2 * n_params;
+    return chain_price_cmc_sens(fn, s, c, n_params, params_host, steps_host, nb_steps_per_year, recenter, seed, call_id, greeks_host,
+                                stats_host, sens_host,
+                                [&](const std::vector<int> &nbs, const std::vector<double> &dts, const uint64_t *seeds, const uint32_t *call_ids,
+                                    double *mu, double *cv) {
+        return heston_cmc_step_many(fn, s->n_path, n_jobs, c.m, nbs.data(), dts.data(), params_host, seeds, call_ids, s->path_offset,
+                                    s->cmany_table_host, s->cmany_table_dev, mu, cv, s->stream);
+    });
 }
 
 }  // extern "C"

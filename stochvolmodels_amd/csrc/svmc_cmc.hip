@@ -12,6 +12,9 @@
 //                                                   then, in row order, the forward statistics and the per-strike constants
 //   cmc_payoff_kernel                        a block column per group of up to CMC_KT strikes of one expiry
 //   cmc_finish_kernel                        a block per quote: column sums in row order, price and error
+//   logsv_chain_cond_many_kernel / _lat_kernel, heston_chain_cond_many_kernel / _lat_kernel   many jobs of one chain in one stepping
+//                                            launch (row f14): the bodies above on job blockIdx.y of a device table
+//   cond_sens_jobs_kernel, cond_sens_pairs_kernel, cond_sens_finish_kernel   parameter sensitivities on common random numbers
 #include "svmc_internal.h"
 
 #include <cmath>
@@ -20,6 +23,7 @@
 
 #include "svmc_black.h"
 #include "svmc_block.h"
+#include "svmc_jobs.h"
 #include "svmc_models.h"
 #include "svmc_rng.h"
 #include "svmc_slice.h"
@@ -57,6 +61,108 @@ __device__ __forceinline__ void cmc_time_loop(const PhiloxLane &lane, uint32_t s
 struct CmcInit {
     int uniform = 0;
     double mu0 = 0.0, cv0 = 0.0, vol0 = 0.0, qvar0 = 0.0;
+};
+
+// Where a conditional chain body's job comes from, as svmc_jobs.h's ChainArgs / ManyTable are for the plain generators: the LogSV and
+// Heston bodies below are written once over a job source and run the same statements -- hence give the same bits -- whichever one
+// hands them the job:
+//   CmcChainArgs<Slices>   the one-job kernels: everything is a kernel argument (Slices = LogsvCmcSlices | HestonCmcSlices); the path
+//                          starts from `init` or the four state arrays at step `step_offset` of its stream, expiry i goes to row i
+//                          and the terminal state is written back
+//   CmcManyTable<Consts>   the many-job kernels: job blockIdx.y of the device table (Consts = LogsvCmc | HestonCmc); the path starts
+//                          from (0, 0, vol0_j, 0) at step 0 of (seed_j, call id_j), expiry i goes to row j m + i, nothing is
+//                          written back and there are no qvar rows
+template <class Slices>
+struct CmcChainArgs {
+    const Slices &cs;
+    uint64_t seed_;
+    uint32_t c3_, step_offset;
+    const CmcInit &init;
+    double *__restrict__ mu, *__restrict__ cv, *__restrict__ vol, *__restrict__ qvar, *__restrict__ q_snap;
+
+    __device__ __forceinline__ int m() const { return cs.m; }
+    __device__ __forceinline__ int nb_steps(int i) const { return cs.nb_steps[i]; }
+    __device__ __forceinline__ int total_steps() const { return cs.total_steps; }
+    __device__ __forceinline__ auto consts(int i) const { return cs.c[i]; }
+    __device__ __forceinline__ unsigned joined() const { return cs.joined; }
+    __device__ __forceinline__ uint64_t seed() const { return seed_; }
+    __device__ __forceinline__ uint32_t c3() const { return c3_; }
+    __device__ __forceinline__ uint32_t step_origin() const { return step_offset; }
+    __device__ __forceinline__ size_t row(int i) const { return static_cast<size_t>(i); }
+    __device__ __forceinline__ double *qvar_rows() const { return q_snap; }
+    // path(): the lane's path index, formed where it is needed (the LogSV bodies step the lanes past the last path on a dummy state)
+    template <class Path>
+    __device__ __forceinline__ void start(Path &&path, bool active, double &m_, double &v_, double &s, double &q_) const
+    {
+        m_ = 0.0;
+        v_ = 0.0;
+        s = 1.0;
+        q_ = 0.0;
+        if (init.uniform) {                                // wave-uniform
+            m_ = init.mu0;
+            v_ = init.cv0;
+            s = init.vol0;
+            q_ = init.qvar0;
+        } else if (active) {
+            const size_t p = path();
+            m_ = mu[p];
+            v_ = cv[p];
+            s = vol[p];
+            q_ = qvar[p];
+        }
+    }
+    __device__ __forceinline__ void finish(size_t p, double m_, double v_, double s, double q_) const
+    {
+        mu[p] = m_;
+        cv[p] = v_;
+        vol[p] = s;
+        qvar[p] = q_;
+    }
+};
+
+// the slices of a many-job launch and its per-job device table, one upload per call: the (job, expiry) constants [J][m] (LogsvCmc |
+// HestonCmc), then per job the start volatility (variance for Heston), the Philox key, the call id's counter word and the job's
+// own `joined` mask (cmc_joined_mask: the rule of cmc_step_chain)
+struct CmcManySlices {
+    int nb_steps[MAX_CHAIN_SLICES];
+    int m, total_steps = 0;
+};
+struct CmcManyJobs {
+    const void *consts;
+    const double *vol0;
+    const uint64_t *seed;
+    const uint32_t *c3, *joined;
+};
+
+template <class Consts>
+struct CmcManyTable {
+    const CmcManySlices &cs;
+    const CmcManyJobs &jobs;
+
+    __device__ __forceinline__ int job() const { return blockIdx.y; }
+    __device__ __forceinline__ int m() const { return cs.m; }
+    __device__ __forceinline__ int nb_steps(int i) const { return cs.nb_steps[i]; }
+    __device__ __forceinline__ int total_steps() const { return cs.total_steps; }
+    // job-uniform values go through uniform_load (svmc_jobs.h): the step keeps its scalar operands
+    __device__ __forceinline__ Consts consts(int i) const
+    {
+        return uniform_load(static_cast<const Consts *>(jobs.consts) + static_cast<size_t>(job()) * cs.m + i);
+    }
+    __device__ __forceinline__ unsigned joined() const { return uniform_load(jobs.joined + job()); }
+    __device__ __forceinline__ uint64_t seed() const { return uniform_load(jobs.seed + job()); }
+    __device__ __forceinline__ uint32_t c3() const { return uniform_load(jobs.c3 + job()); }
+    __device__ __forceinline__ uint32_t step_origin() const { return 0u; }
+    __device__ __forceinline__ size_t row(int i) const { return static_cast<size_t>(job()) * cs.m + i; }
+    __device__ __forceinline__ double *qvar_rows() const { return nullptr; }
+    template <class Path>
+    __device__ __forceinline__ void start(Path &&, bool, double &m_, double &v_, double &s, double &q_) const
+    {
+        m_ = 0.0;
+        v_ = 0.0;
+        s = uniform_load(jobs.vol0 + job());
+        q_ = 0.0;
+    }
+    __device__ __forceinline__ void finish(size_t, double, double, double, double) const {}
 };
 
 // ---- LogSV: logsv_step_acc with the two noise FMAs replaced by one (the volatility moves on beta w0 + volvol w1 = vartheta b)
@@ -132,12 +238,9 @@ struct LogsvCmcSlices {
 // One body for both launch forms.  PARK (the full-launch form, 1024-thread blocks at eight waves per SIMD): the base values of mu, cv
 // and qvar are dead inside the time loop but live across it, and wait in LDS as logsv_chain_rng_kernel parks x and qvar; the few-waves form keeps
 // them in registers.  The statements on the state are the same, hence the bits.
-template <bool PARK, int TB>
-__device__ __forceinline__ void logsv_chain_cmc_body(double *__restrict__ mu, double *__restrict__ cv, double *__restrict__ sigma,
-                                                     double *__restrict__ qvar, size_t n, const LogsvCmcSlices &cs, uint64_t seed,
-                                                     uint32_t c3, uint64_t path_offset, uint32_t step_offset,
-                                                     double *__restrict__ mu_snap, double *__restrict__ cv_snap,
-                                                     double *__restrict__ q_snap, const CmcInit &init)
+template <bool PARK, int TB, class Src>
+__device__ __forceinline__ void logsv_chain_cmc_body(const Src &src, size_t n, uint64_t path_offset, double *__restrict__ mu_snap,
+                                                     double *__restrict__ cv_snap)
 {
     __shared__ RngTablesLds s_tab;
     __shared__ double s_exp[256];
@@ -149,26 +252,19 @@ __device__ __forceinline__ void logsv_chain_cmc_body(double *__restrict__ mu, do
         return static_cast<size_t>(blockIdx.x) * TB + t;
     };
     const bool active = path_index() < n;
-    double m_ = 0.0, v_ = 0.0, s = 1.0, q_ = 0.0;          // lanes past the last path step a dummy state
-    if (init.uniform) {                                    // wave-uniform
-        m_ = init.mu0;
-        v_ = init.cv0;
-        s = init.vol0;
-        q_ = init.qvar0;
-    } else if (active) {
-        const size_t p = path_index();
-        m_ = mu[p];
-        v_ = cv[p];
-        s = sigma[p];
-        q_ = qvar[p];
-    }
+    double m_, v_, s, q_;                                  // lanes past the last path step a dummy state
+    src.start(path_index, active, m_, v_, s, q_);
     if constexpr (PARK) {
         s_park[threadIdx.x] = m_;
         s_park[TB + threadIdx.x] = v_;
         s_park[2 * TB + threadIdx.x] = q_;
     }
-    const PhiloxLane lane = philox_prepare(seed, c3 | CMC_STREAM, path_offset + path_index());
-    LogsvProgress prog = {(cs.total_steps + 3) >> 2};
+    const PhiloxLane lane = philox_prepare(src.seed(), src.c3() | CMC_STREAM, path_offset + path_index());
+    LogsvProgress prog = {(src.total_steps() + 3) >> 2};
+    const int n_slices = src.m();
+    const unsigned joined = src.joined();
+    const uint32_t step_offset = src.step_origin();
+    double *__restrict__ q_snap = src.qvar_rows();
     int tg = 0;
     // L = ln sigma in log units is derived once per LAUNCH and carried from slice to slice.  One Newton step on exp(L) = sigma:
     // log_state is good to 4 ULP of ln sigma, which is up to 4 ulp(ln sigma) RELATIVE in the volatility the first step ends with
@@ -180,9 +276,9 @@ __device__ __forceinline__ void logsv_chain_cmc_body(double *__restrict__ mu, do
     }
     // the sums since the last boundary that was not joined; (m_, v_, q_) -- parked in LDS in the PARK form -- is the state AT it
     double acc = 0.0, xacc = 0.0, s2_start = square_rn(s);
-    for (int i = 0; i < cs.m; ++i) {
-        const int nb = cs.nb_steps[i];
-        const LogsvCmc c = cs.c[i];
+    for (int i = 0; i < n_slices; ++i) {
+        const int nb = src.nb_steps(i);
+        const LogsvCmc c = src.consts(i);
         double c3v = c.c3;
         asm volatile("" : "+v"(c3v));
         cmc_time_loop(
@@ -206,12 +302,12 @@ __device__ __forceinline__ void logsv_chain_cmc_body(double *__restrict__ mu, do
         logsv_cmc_fold(c, ms, vs, qs, xacc, acc, s2_start, square_rn(s));
         tg += nb;
         if (active) {
-            const size_t o = static_cast<size_t>(i) * n + path_index();
+            const size_t o = src.row(i) * n + path_index();
             mu_snap[o] = ms;
             cv_snap[o] = vs;
             if (q_snap != nullptr) q_snap[o] = qs;
         }
-        const bool runs_on = i + 1 < cs.m && ((cs.joined >> (i + 1)) & 1u) != 0u;      // wave-uniform
+        const bool runs_on = i + 1 < n_slices && ((joined >> (i + 1)) & 1u) != 0u;     // wave-uniform
         if (!runs_on) {                                    // a real boundary (the launch's end is one): the values become the base
             if constexpr (PARK) {
                 s_park[threadIdx.x] = ms;
@@ -234,10 +330,7 @@ __device__ __forceinline__ void logsv_chain_cmc_body(double *__restrict__ mu, do
             v_ = s_park[TB + threadIdx.x];
             q_ = s_park[2 * TB + threadIdx.x];
         }
-        mu[p] = m_;
-        cv[p] = v_;
-        sigma[p] = s;
-        qvar[p] = q_;
+        src.finish(p, m_, v_, s, q_);
     }
 }
 
@@ -247,7 +340,8 @@ __global__ __launch_bounds__(CMC_CHAIN_BLOCK) __attribute__((amdgpu_waves_per_eu
     uint64_t seed, uint32_t c3, uint64_t path_offset, uint32_t step_offset, double *__restrict__ mu_snap, double *__restrict__ cv_snap,
     double *__restrict__ q_snap, CmcInit init)
 {
-    logsv_chain_cmc_body<true, CMC_CHAIN_BLOCK>(mu, cv, sigma, qvar, n, cs, seed, c3, path_offset, step_offset, mu_snap, cv_snap, q_snap, init);
+    logsv_chain_cmc_body<true, CMC_CHAIN_BLOCK>(CmcChainArgs<LogsvCmcSlices>{cs, seed, c3, step_offset, init, mu, cv, sigma, qvar, q_snap}, n,
+                                                path_offset, mu_snap, cv_snap);
 }
 
 // the few-waves form (few_waves_launch()): 256-thread blocks so that every CU gets work, registers to spare
@@ -256,7 +350,22 @@ __global__ __launch_bounds__(FEW_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 4)
     uint64_t seed, uint32_t c3, uint64_t path_offset, uint32_t step_offset, double *__restrict__ mu_snap, double *__restrict__ cv_snap,
     double *__restrict__ q_snap, CmcInit init)
 {
-    logsv_chain_cmc_body<false, FEW_BLOCK>(mu, cv, sigma, qvar, n, cs, seed, c3, path_offset, step_offset, mu_snap, cv_snap, q_snap, init);
+    logsv_chain_cmc_body<false, FEW_BLOCK>(CmcChainArgs<LogsvCmcSlices>{cs, seed, c3, step_offset, init, mu, cv, sigma, qvar, q_snap}, n,
+                                           path_offset, mu_snap, cv_snap);
+}
+
+// many jobs of one chain in ONE launch: blockIdx.y = job, blockIdx.x = block of that job's n paths.  The names
+// of these kernels carry none of the words the f11 to f13 metadata tests count kernels by.
+__global__ __launch_bounds__(CMC_CHAIN_BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8), amdgpu_num_sgpr(80))) void logsv_chain_cond_many_kernel(
+    size_t n, CmcManySlices cs, CmcManyJobs jobs, uint64_t path_offset, double *__restrict__ mu_snap, double *__restrict__ cv_snap)
+{
+    logsv_chain_cmc_body<true, CMC_CHAIN_BLOCK>(CmcManyTable<LogsvCmc>{cs, jobs}, n, path_offset, mu_snap, cv_snap);
+}
+
+__global__ __launch_bounds__(FEW_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 4))) void logsv_chain_cond_many_lat_kernel(
+    size_t n, CmcManySlices cs, CmcManyJobs jobs, uint64_t path_offset, double *__restrict__ mu_snap, double *__restrict__ cv_snap)
+{
+    logsv_chain_cmc_body<false, FEW_BLOCK>(CmcManyTable<LogsvCmc>{cs, jobs}, n, path_offset, mu_snap, cv_snap);
 }
 
 // ---- Heston: the reference's Euler step with its 1e-4 floor, the variance driven by b = rho w0 + rho_1 w1
@@ -307,11 +416,9 @@ struct HestonCmcSlices {
     unsigned joined = 0;               // as LogsvCmcSlices
 };
 
-__device__ __forceinline__ void heston_chain_cmc_body(double *__restrict__ mu, double *__restrict__ cv, double *__restrict__ var,
-                                                      double *__restrict__ qvar, size_t n, const HestonCmcSlices &cs, uint64_t seed,
-                                                      uint32_t c3, uint64_t path_offset, uint32_t step_offset,
-                                                      double *__restrict__ mu_snap, double *__restrict__ cv_snap,
-                                                      double *__restrict__ q_snap, const CmcInit &init)
+template <class Src>
+__device__ __forceinline__ void heston_chain_cmc_body(const Src &src, size_t n, uint64_t path_offset, double *__restrict__ mu_snap,
+                                                      double *__restrict__ cv_snap)
 {
     __shared__ RngTablesLds s_tab;
     const RngTables tab = stage_rng_tables(s_tab);
@@ -319,33 +426,26 @@ __device__ __forceinline__ void heston_chain_cmc_body(double *__restrict__ mu, d
     const bool active = p < n;
     if (!active) return;                                   // (after the block's only barrier)
     double m_, c_, v, q_;
-    if (init.uniform) {                                    // wave-uniform
-        m_ = init.mu0;
-        c_ = init.cv0;
-        v = init.vol0;
-        q_ = init.qvar0;
-    } else {
-        m_ = mu[p];
-        c_ = cv[p];
-        v = var[p];
-        q_ = qvar[p];
-    }
-    const PhiloxLane lane = philox_prepare(seed, c3 | CMC_STREAM, path_offset + p);
-    uint32_t step = step_offset;
+    src.start([&]() { return p; }, true, m_, c_, v, q_);
+    const PhiloxLane lane = philox_prepare(src.seed(), src.c3() | CMC_STREAM, path_offset + p);
+    const int n_slices = src.m();
+    const unsigned joined = src.joined();
+    double *__restrict__ q_snap = src.qvar_rows();
+    uint32_t step = src.step_origin();
     double xacc = 0.0, vacc = 0.0;                         // the sums since the last boundary that was not joined (HestonCmcSlices)
-    for (int i = 0; i < cs.m; ++i) {
-        const int nb = cs.nb_steps[i];
-        const HestonCmc c = cs.c[i];
+    for (int i = 0; i < n_slices; ++i) {
+        const int nb = src.nb_steps(i);
+        const HestonCmc c = src.consts(i);
         v = heston_euler_guard_zero(v);
         cmc_time_loop(lane, step, nb, tab, [&](double b) { heston_cmc_step(c, xacc, v, vacc, b); }, [](int) {});
         double ms = m_, vs = c_, qs = q_;
         heston_cmc_fold(c, ms, vs, qs, v, xacc, vacc);
         step += static_cast<uint32_t>(nb);
-        const size_t o = static_cast<size_t>(i) * n + p;
+        const size_t o = src.row(i) * n + p;
         mu_snap[o] = ms;
         cv_snap[o] = vs;
         if (q_snap != nullptr) q_snap[o] = qs;
-        const bool runs_on = i + 1 < cs.m && ((cs.joined >> (i + 1)) & 1u) != 0u;      // wave-uniform
+        const bool runs_on = i + 1 < n_slices && ((joined >> (i + 1)) & 1u) != 0u;     // wave-uniform
         if (!runs_on) {
             m_ = ms;
             c_ = vs;
@@ -354,10 +454,7 @@ __device__ __forceinline__ void heston_chain_cmc_body(double *__restrict__ mu, d
             vacc = 0.0;
         }
     }
-    mu[p] = m_;
-    cv[p] = c_;
-    var[p] = v;
-    qvar[p] = q_;
+    src.finish(p, m_, c_, v, q_);
 }
 
 __global__ __launch_bounds__(RNG_BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) void heston_chain_cmc_kernel(
@@ -365,7 +462,8 @@ __global__ __launch_bounds__(RNG_BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8)
     uint64_t seed, uint32_t c3, uint64_t path_offset, uint32_t step_offset, double *__restrict__ mu_snap, double *__restrict__ cv_snap,
     double *__restrict__ q_snap, CmcInit init)
 {
-    heston_chain_cmc_body(mu, cv, var, qvar, n, cs, seed, c3, path_offset, step_offset, mu_snap, cv_snap, q_snap, init);
+    heston_chain_cmc_body(CmcChainArgs<HestonCmcSlices>{cs, seed, c3, step_offset, init, mu, cv, var, qvar, q_snap}, n, path_offset, mu_snap,
+                          cv_snap);
 }
 
 __global__ __launch_bounds__(FEW_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 4))) void heston_chain_cmc_lat_kernel(
@@ -373,10 +471,32 @@ __global__ __launch_bounds__(FEW_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 4)
     uint64_t seed, uint32_t c3, uint64_t path_offset, uint32_t step_offset, double *__restrict__ mu_snap, double *__restrict__ cv_snap,
     double *__restrict__ q_snap, CmcInit init)
 {
-    heston_chain_cmc_body(mu, cv, var, qvar, n, cs, seed, c3, path_offset, step_offset, mu_snap, cv_snap, q_snap, init);
+    heston_chain_cmc_body(CmcChainArgs<HestonCmcSlices>{cs, seed, c3, step_offset, init, mu, cv, var, qvar, q_snap}, n, path_offset, mu_snap,
+                          cv_snap);
+}
+
+__global__ __launch_bounds__(RNG_BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) void heston_chain_cond_many_kernel(
+    size_t n, CmcManySlices cs, CmcManyJobs jobs, uint64_t path_offset, double *__restrict__ mu_snap, double *__restrict__ cv_snap)
+{
+    heston_chain_cmc_body(CmcManyTable<HestonCmc>{cs, jobs}, n, path_offset, mu_snap, cv_snap);
+}
+
+__global__ __launch_bounds__(FEW_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 4))) void heston_chain_cond_many_lat_kernel(
+    size_t n, CmcManySlices cs, CmcManyJobs jobs, uint64_t path_offset, double *__restrict__ mu_snap, double *__restrict__ cv_snap)
+{
+    heston_chain_cmc_body(CmcManyTable<HestonCmc>{cs, jobs}, n, path_offset, mu_snap, cv_snap);
 }
 
 // ---- host side of the stepping: launches of at most MAX_CHAIN_SLICES expiries, the step offset carried from launch to launch
+// bit i: slice i has the bit-equal constants of slice i - 1 (LogsvCmcSlices)
+template <class Consts>
+static unsigned cmc_joined_mask(const Consts *c, int m)
+{
+    unsigned joined = 0u;
+    for (int i = 1; i < m; ++i)
+        if (memcmp(&c[i], &c[i - 1], sizeof(Consts)) == 0) joined |= 1u << i;
+    return joined;
+}
 template <class Slices, class Fill, class Launch>
 static int cmc_step_chain(const char *fn, const CmcInit &init, const double *mu, const double *cv, const double *vol, const double *qvar,
                           size_t n_path, int n_slices, const int *nb_steps_host, const double *dts_host, uint32_t call_id,
@@ -400,9 +520,7 @@ static int cmc_step_chain(const char *fn, const CmcInit &init, const double *mu,
             fill(cs, i, j);
         }
         cs.total_steps = static_cast<int>(steps);
-        cs.joined = 0u;
-        for (int i = 1; i < cs.m; ++i)
-            if (memcmp(&cs.c[i], &cs.c[i - 1], sizeof(cs.c[i])) == 0) cs.joined |= 1u << i;
+        cs.joined = cmc_joined_mask(cs.c, cs.m);
         const size_t row = static_cast<size_t>(i0) * n_path;
         launch(cs, mu_snapshots + row, cv_snapshots + row, qvar_snapshots ? qvar_snapshots + row : nullptr, (i0 == 0) ? init : CmcInit(),
                step_offset);
@@ -472,6 +590,106 @@ int heston_cmc_step_from(double var0, double *mu, double *cv, double *var, doubl
     const CmcInit init = {1, 0.0, 0.0, var0, 0.0};
     return heston_cmc_step_chain("svmc_heston_chain_price_cmc", init, mu, cv, var, qvar, n_path, n_slices, nb_steps_host, dts_host, theta,
                                  kappa, rho, volvol, seed, call_id, path_offset, 0u, mu_snapshots, cv_snapshots, nullptr, stream);
+}
+
+// ---- many jobs of one chain in one stepping launch (svmc_*_chain_cmc_many and the fused drivers of svmc_chain.hip)
+template <class Consts>
+static size_t cmc_many_table_bytes_of(int n_jobs, int n_slices)
+{
+    const size_t J = static_cast<size_t>(n_jobs);
+    return J * static_cast<size_t>(n_slices) * sizeof(Consts) + J * (sizeof(double) + sizeof(uint64_t) + 2 * sizeof(uint32_t));
+}
+size_t cmc_many_table_bytes(int n_jobs, int n_slices)
+{
+    return std::max(cmc_many_table_bytes_of<LogsvCmc>(n_jobs, n_slices), cmc_many_table_bytes_of<HestonCmc>(n_jobs, n_slices));
+}
+
+// The checks, the job table -- filled in table_host (the table's byte layout; the caller keeps it until the stream has passed
+// the upload), uploaded to table_dev -- and launch(cs, jobs).  fill(j, consts) sets job j's n_slices constants and returns its
+// start volatility.
+template <class Consts, class Fill, class Launch>
+static int cmc_step_many(const char *fn, size_t n_path, int n_jobs, int n_slices, const int *nb_steps_host, const double *dts_host,
+                         const double *params_host, const uint64_t *seeds, const uint32_t *call_ids, void *table_host, void *table_dev,
+                         double *mu_snapshots, double *cv_snapshots, hipStream_t stream, Fill &&fill, Launch &&launch)
+{
+    SVMC_REQUIRE(nb_steps_host && dts_host && params_host && seeds && call_ids && table_host && table_dev && mu_snapshots && cv_snapshots,
+                 std::string(fn) + ": null pointer");
+    if (int rc = check_many(fn, n_path, n_jobs, n_slices, nb_steps_host, dts_host, call_ids)) return rc;
+    const size_t J = static_cast<size_t>(n_jobs), nc = J * static_cast<size_t>(n_slices);
+    unsigned char *h = static_cast<unsigned char *>(table_host);
+    Consts *consts = reinterpret_cast<Consts *>(h);
+    double *vol0 = reinterpret_cast<double *>(h + nc * sizeof(Consts));
+    uint64_t *seed = reinterpret_cast<uint64_t *>(vol0 + J);
+    uint32_t *c3 = reinterpret_cast<uint32_t *>(seed + J), *joined = c3 + J;
+    for (int j = 0; j < n_jobs; ++j) {
+        Consts *cj = consts + static_cast<size_t>(j) * n_slices;
+        vol0[j] = fill(j, cj);
+        seed[j] = seeds[j];
+        c3[j] = make_c3(call_ids[j]);
+        joined[j] = cmc_joined_mask(cj, n_slices);
+    }
+    const size_t bytes = cmc_many_table_bytes_of<Consts>(n_jobs, n_slices);
+    SVMC_HIP_TRY(hipMemcpyAsync(table_dev, table_host, bytes, hipMemcpyHostToDevice, stream));
+    const unsigned char *d = static_cast<const unsigned char *>(table_dev);
+    const size_t o_vol = nc * sizeof(Consts), o_seed = o_vol + J * sizeof(double), o_c3 = o_seed + J * sizeof(uint64_t),
+                 o_joined = o_c3 + J * sizeof(uint32_t);
+    const CmcManyJobs jobs = {d, reinterpret_cast<const double *>(d + o_vol), reinterpret_cast<const uint64_t *>(d + o_seed),
+                              reinterpret_cast<const uint32_t *>(d + o_c3), reinterpret_cast<const uint32_t *>(d + o_joined)};
+    CmcManySlices cs;
+    cs.m = n_slices;
+    for (int i = 0; i < MAX_CHAIN_SLICES; ++i) {
+        cs.nb_steps[i] = i < n_slices ? nb_steps_host[i] : 0;
+        cs.total_steps += cs.nb_steps[i];
+    }
+    // the form is chosen by the launch's TOTAL path count, as logsv_chain_rng_many chooses it
+    launch(cs, jobs, few_waves_launch(J * n_path));
+    return check_launch(fn);
+}
+
+int logsv_cmc_step_many(const char *fn, size_t n_path, int n_jobs, int n_slices, const int *nb_steps_host, const double *dts_host,
+                        const double *params_host, int is_spot_measure, const uint64_t *seeds, const uint32_t *call_ids,
+                        uint64_t path_offset, void *table_host, void *table_dev, double *mu_snapshots, double *cv_snapshots,
+                        hipStream_t stream)
+{
+    const size_t row = 6 + static_cast<size_t>(n_slices > 0 ? n_slices : 0);       // v0 theta kappa1 kappa2 beta volvol, etas
+    const unsigned J = static_cast<unsigned>(n_jobs);
+    return cmc_step_many<LogsvCmc>(fn, n_path, n_jobs, n_slices, nb_steps_host, dts_host, params_host, seeds, call_ids, table_host,
+                                   table_dev, mu_snapshots, cv_snapshots, stream,
+                                   [&](int j, LogsvCmc *c) {
+        const double *p = params_host + row * static_cast<size_t>(j);
+        for (int i = 0; i < n_slices; ++i) c[i] = make_logsv_cmc(dts_host[i], p[1], p[2], p[3], p[4], p[5], p[6 + i], is_spot_measure);
+        return p[0];
+    },
+                                   [&](const CmcManySlices &cs, const CmcManyJobs &jobs, bool few) {
+        if (few)
+            hipLaunchKernelGGL(logsv_chain_cond_many_lat_kernel, dim3(lat_grid(n_path), J), dim3(FEW_BLOCK), 0, stream, n_path, cs, jobs,
+                               path_offset, mu_snapshots, cv_snapshots);
+        else
+            hipLaunchKernelGGL(logsv_chain_cond_many_kernel, dim3(lat_grid(n_path, CMC_CHAIN_BLOCK), J), dim3(CMC_CHAIN_BLOCK), 0, stream,
+                               n_path, cs, jobs, path_offset, mu_snapshots, cv_snapshots);
+    });
+}
+
+int heston_cmc_step_many(const char *fn, size_t n_path, int n_jobs, int n_slices, const int *nb_steps_host, const double *dts_host,
+                         const double *params_host, const uint64_t *seeds, const uint32_t *call_ids, uint64_t path_offset,
+                         void *table_host, void *table_dev, double *mu_snapshots, double *cv_snapshots, hipStream_t stream)
+{
+    const unsigned J = static_cast<unsigned>(n_jobs);
+    return cmc_step_many<HestonCmc>(fn, n_path, n_jobs, n_slices, nb_steps_host, dts_host, params_host, seeds, call_ids, table_host,
+                                    table_dev, mu_snapshots, cv_snapshots, stream,
+                                    [&](int j, HestonCmc *c) {
+        const double *p = params_host + 5 * static_cast<size_t>(j);               // v0 theta kappa rho volvol
+        for (int i = 0; i < n_slices; ++i) c[i] = make_heston_cmc(dts_host[i], p[1], p[2], p[3], p[4]);
+        return p[0];
+    },
+                                    [&](const CmcManySlices &cs, const CmcManyJobs &jobs, bool few) {
+        if (few)
+            hipLaunchKernelGGL(heston_chain_cond_many_lat_kernel, dim3(lat_grid(n_path), J), dim3(FEW_BLOCK), 0, stream, n_path, cs, jobs,
+                               path_offset, mu_snapshots, cv_snapshots);
+        else
+            hipLaunchKernelGGL(heston_chain_cond_many_kernel, dim3(rng_grid(n_path), J), dim3(rng_block()), 0, stream, n_path, cs, jobs,
+                               path_offset, mu_snapshots, cv_snapshots);
+    });
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1015,6 +1233,335 @@ size_t cmc_payoff_workspace_bytes_of(size_t n_path, int n_expiries, size_t total
     return cmc_workspace_bytes(n_path, n_expiries, total_strikes, static_cast<int>(total_strikes / CMC_KT) + n_expiries);
 }
 
+// ---------------------------------------------------------------------------------------------------
+// parameter sensitivities of the conditional estimator on common random numbers (include/svmc.h states the
+// estimator, the delta-method term of its error and the shift convention)
+// ---------------------------------------------------------------------------------------------------
+// The 2P bumped jobs (up_0, dn_0, up_1, ...) of a chain of m expiries and K quotes are laid out as ONE CmcTable of 2P m expiries and
+// 2P K strikes, job-major: cmc_forward_kernel and cmc_forward_finish_kernel then form every job's forward statistics, K' and ln K'
+// as they form a single job's -- the same statements, hence the same bits.  The kernels below put the job and pair axes on
+// blockIdx.z (blockIdx.y in the finish), so the launch count does not grow with P.
+constexpr int SENS_KT = SVMC_CMC_GREEKS_KT;    // strikes per group
+constexpr int SENS_PQ = 4;                     // per (pair, quote): sum (d - d0), sum (dt - dt0), its squares, the kept pairs
+
+struct CmcSensTable {
+    const CmcGroup *groups;            // groups of up to SENS_KT strikes of one expiry of the CHAIN: k0 in [0, K)
+    const double *steps;               // [P]
+    double *q_partials;                // [rows][2P K]
+    double *q;                         // [2P K]: mean_kept_j(B_k), the job's dual delta before discounting
+    double *pair_shift;                // [P K][2]: d and dt of the expiry's path 0, or 0 where it is not a kept pair
+    double *pair_partials;             // [rows][P K][SENS_PQ]
+    double *out;                       // [P][SVMC_CMC_SENS_ROWS][K]
+    int P, m, K;                       // the chain's expiries and quotes
+};
+
+// the job pass: per kept path of job blockIdx.z the dual delta B_k of cmc_derivs against the job's own K'
+__global__ __launch_bounds__(BLOCK) void cond_sens_jobs_kernel(CmcTable t, CmcSensTable st, size_t n)
+{
+    __shared__ double lds[4 * block_sum_padded(SENS_KT)];
+    const CmcGroup g = st.groups[blockIdx.y];
+    const int job = blockIdx.z, nk = g.nk;
+    const CmcExpiry ex = t.expiries[job * st.m + g.expiry];
+    const size_t kbase = static_cast<size_t>(job) * st.K + g.k0;
+    double kp[SENS_KT], ln_kp[SENS_KT], acc[SENS_KT];
+    bool put[SENS_KT];
+#pragma unroll
+    for (int k = 0; k < SENS_KT; ++k) {
+        const size_t kk = kbase + ((k < nk) ? k : 0);      // the unused strikes of a group repeat its first; their sums are dropped
+        kp[k] = t.kp[kk];
+        ln_kp[k] = t.ln_kp[kk];
+        put[k] = t.is_put[kk] != 0.0;
+        acc[k] = 0.0;
+    }
+    const double forward = ex.forward, ln_forward = ex.ln_forward;
+    const size_t stride = static_cast<size_t>(gridDim.x) * BLOCK;
+    for (size_t i = static_cast<size_t>(blockIdx.x) * BLOCK + threadIdx.x; i < n; i += stride) {
+        const double cv = ex.cv[i];
+        double h, e;
+        if (!cmc_keep(ex.mu[i], cv, h, e)) continue;
+        const double fc = forward * e, ln_fc = ln_forward + h;
+        const double sd = sqrt(cv), inv_sd = 1.0 / sd;
+#pragma unroll
+        for (int k = 0; k < SENS_KT; ++k) {
+            double delta, bk, dg;
+            cmc_derivs(e, 0.0, fc, ln_fc, cv, sd, inv_sd, kp[k], ln_kp[k], 0.0, put[k], delta, bk, dg);
+            acc[k] += bk;
+        }
+    }
+    double *out = st.q_partials + static_cast<size_t>(blockIdx.x) * (2 * static_cast<size_t>(st.P) * st.K) + kbase;
+    block_sum_apply<SENS_KT>(acc, lds, SENS_KT, [&](int j, double s) {
+        if (j < nk) out[j] = s;
+    });
+}
+
+// what a group of the pair pass holds per strike: each job's K', ln K' and q (0 without recentring)
+struct CmcSensStrikes {
+    double kpu[SENS_KT], lku[SENS_KT], kpd[SENS_KT], lkd[SENS_KT], qu[SENS_KT], qd[SENS_KT];
+    bool put[SENS_KT];
+};
+
+// d = B_up - B_dn and dt = d + F (q_up (e_up - 1) - q_dn (e_dn - 1)) of path i for the strikes of a group; false: not a kept pair.
+// The shift is this function on path 0: the multiply-adds are written out so that identical paths give differences of exactly 0.
+__device__ __forceinline__ bool cond_sens_path(const CmcExpiry &xu, const CmcExpiry &xd, size_t i, const CmcSensStrikes &s,
+                                               double (&d)[SENS_KT], double (&dt)[SENS_KT])
+{
+    const double cvu = xu.cv[i], cvd = xd.cv[i];
+    double hu, eu, hd, ed;
+    const bool keep_u = cmc_keep(xu.mu[i], cvu, hu, eu), keep_d = cmc_keep(xd.mu[i], cvd, hd, ed);
+    if (!(keep_u && keep_d)) return false;
+    const double fcu = xu.forward * eu, lfu = xu.ln_forward + hu, sdu = sqrt(cvu), isu = 1.0 / sdu;
+    const double fcd = xd.forward * ed, lfd = xd.ln_forward + hd, sdd = sqrt(cvd), isd = 1.0 / sdd;
+    const double du = eu - 1.0, dd = ed - 1.0;
+#pragma unroll
+    for (int k = 0; k < SENS_KT; ++k) {
+        const double bu = cmc_black(fcu, lfu, cvu, sdu, isu, s.kpu[k], s.lku[k], s.put[k]);
+        const double bd = cmc_black(fcd, lfd, cvd, sdd, isd, s.kpd[k], s.lkd[k], s.put[k]);
+        d[k] = bu - bd;
+        dt[k] = fma(xu.forward, fma(s.qu[k], du, -(s.qd[k] * dd)), d[k]);
+    }
+    return true;
+}
+
+// the pair pass: path blocks x groups x pairs
+__global__ __launch_bounds__(BLOCK) void cond_sens_pairs_kernel(CmcTable t, CmcSensTable st, size_t n, int recenter)
+{
+    constexpr int NV = 3 * SENS_KT + 1;                    // the last value: the kept pairs
+    __shared__ double lds[4 * block_sum_padded(NV)];
+    const CmcGroup g = st.groups[blockIdx.y];
+    const int p = blockIdx.z, nk = g.nk;
+    const CmcExpiry xu = t.expiries[(2 * p) * st.m + g.expiry], xd = t.expiries[(2 * p + 1) * st.m + g.expiry];
+    const size_t ku = static_cast<size_t>(2 * p) * st.K + g.k0, kd = ku + st.K;
+    CmcSensStrikes s;
+    double acc[NV], sh_d[SENS_KT], sh_t[SENS_KT];
+#pragma unroll
+    for (int j = 0; j < NV; ++j) acc[j] = 0.0;
+#pragma unroll
+    for (int k = 0; k < SENS_KT; ++k) {
+        const int o = (k < nk) ? k : 0;
+        s.kpu[k] = t.kp[ku + o];
+        s.lku[k] = t.ln_kp[ku + o];
+        s.kpd[k] = t.kp[kd + o];
+        s.lkd[k] = t.ln_kp[kd + o];
+        s.qu[k] = recenter ? st.q[ku + o] : 0.0;
+        s.qd[k] = recenter ? st.q[kd + o] : 0.0;
+        s.put[k] = t.is_put[ku + o] != 0.0;
+    }
+    if (!cond_sens_path(xu, xd, 0, s, sh_d, sh_t)) {
+#pragma unroll
+        for (int k = 0; k < SENS_KT; ++k) sh_d[k] = sh_t[k] = 0.0;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        double *sh = st.pair_shift + 2 * (static_cast<size_t>(p) * st.K + g.k0);
+#pragma unroll
+        for (int k = 0; k < SENS_KT; ++k)
+            if (k < nk) {
+                sh[2 * k] = sh_d[k];
+                sh[2 * k + 1] = sh_t[k];
+            }
+    }
+    const size_t stride = static_cast<size_t>(gridDim.x) * BLOCK;
+    for (size_t i = static_cast<size_t>(blockIdx.x) * BLOCK + threadIdx.x; i < n; i += stride) {
+        double d[SENS_KT], dt[SENS_KT];
+        if (!cond_sens_path(xu, xd, i, s, d, dt)) continue;
+        acc[NV - 1] += 1.0;
+#pragma unroll
+        for (int k = 0; k < SENS_KT; ++k) {
+            const double a = d[k] - sh_d[k], b = dt[k] - sh_t[k];
+            acc[k] += a;
+            acc[SENS_KT + k] += b;
+            acc[2 * SENS_KT + k] = fma(b, b, acc[2 * SENS_KT + k]);
+        }
+    }
+    double *out = st.pair_partials + ((static_cast<size_t>(blockIdx.x) * st.P + p) * st.K + g.k0) * SENS_PQ;
+    block_sum_apply<NV>(acc, lds, NV, [&](int j, double v) {
+        if (j == NV - 1) {
+            for (int k = 0; k < nk; ++k) out[SENS_PQ * k + 3] = v;
+        } else {
+            const int q = j / SENS_KT, k = j - q * SENS_KT;
+            if (k < nk) out[SENS_PQ * k + q] = v;
+        }
+    });
+}
+
+// a block per (quote, job) -- phase 0: q = the column sum of the job's dual deltas in row order over its kept count -- or per (quote,
+// pair) -- phase 1: the four column sums in row order, then sens = DF (d0 + mean_pairs(d - d0)) / (2 h), its error DF x population
+// deviation of dt over the pairs / sqrt(n_path) / (2 h) and the kept pairs; no kept pair: 0 / 0 = NaN and a count of 0
+__global__ __launch_bounds__(BLOCK) void cond_sens_finish_kernel(CmcTable t, CmcSensTable st, size_t n, int phase)
+{
+    __shared__ double lds[4];
+    const int k = blockIdx.x, z = blockIdx.y;
+    int i = 0;
+    while (i + 1 < st.m && k >= t.expiries[i].k1) ++i;     // (block-uniform; the first m expiries of the table are job 0's)
+    const size_t col = static_cast<size_t>(z) * st.K + k;
+    if (phase == 0) {                                      // (block-uniform)
+        const double s = block_column_sum(st.q_partials + col, t.rows, 2 * static_cast<size_t>(st.P) * st.K, lds);
+        if (threadIdx.x == 0) st.q[col] = s / t.fwd[4 * (z * st.m + i) + 2];
+        return;
+    }
+    const size_t ld = SENS_PQ * static_cast<size_t>(st.P) * st.K;
+    const double *base = st.pair_partials + SENS_PQ * col;
+    double s[SENS_PQ];
+#pragma unroll
+    for (int q = 0; q < SENS_PQ; ++q) {
+        if (q > 0) __syncthreads();
+        s[q] = block_column_sum(base + q, t.rows, ld, lds);
+    }
+    if (threadIdx.x == 0) {
+        const double cnt = s[3], df = t.expiries[i].discfactor, h2 = 2.0 * st.steps[z];
+        const double mean_d = st.pair_shift[2 * col] + s[0] / cnt;
+        const double mean_t = s[1] / cnt;
+        double var = s[2] / cnt - mean_t * mean_t;
+        if (var < 0.0) var = 0.0;
+        double *out = st.out + static_cast<size_t>(z) * SVMC_CMC_SENS_ROWS * st.K + k;
+        out[0] = df * mean_d / h2;
+        out[st.K] = df * sqrt(var) / sqrt(static_cast<double>(n)) / h2;
+        out[2 * static_cast<size_t>(st.K)] = cnt;
+    }
+}
+
+int cmc_sens_check(const char *fn, size_t n_path, const double *forwards_host, const double *discfactors_host, int n_expiries,
+                   const double *strikes_host, const int8_t *types_host, const size_t *strike_offsets_host, int n_params,
+                   const double *steps_host)
+{
+    SVMC_REQUIRE(forwards_host && discfactors_host && strikes_host && types_host && strike_offsets_host && steps_host,
+                 std::string(fn) + ": null pointer");
+    SVMC_REQUIRE(n_path > 0 && n_expiries >= 1, std::string(fn) + ": n_path and n_expiries must be positive");
+    SVMC_REQUIRE(n_params >= 1 && n_params <= SVMC_GREEKS_MAX_PARAMS, std::string(fn) + ": n_params must be in [1, SVMC_GREEKS_MAX_PARAMS]");
+    for (int p = 0; p < n_params; ++p)
+        SVMC_REQUIRE(std::isfinite(steps_host[p]) && steps_host[p] > 0.0, std::string(fn) + ": a step is not positive and finite");
+    for (int i = 0; i < n_expiries; ++i) {
+        SVMC_REQUIRE(strike_offsets_host[i] <= strike_offsets_host[i + 1], std::string(fn) + ": strike offsets must not decrease");
+        SVMC_REQUIRE(std::isfinite(forwards_host[i]) && forwards_host[i] > 0.0, std::string(fn) + ": a forward is not positive and finite");
+        SVMC_REQUIRE(std::isfinite(discfactors_host[i]), std::string(fn) + ": a discount factor is not finite");
+    }
+    const size_t K = strike_offsets_host[n_expiries];
+    for (size_t k = 0; k < K; ++k) {
+        if (types_host[k] != SVMC_CALL && types_host[k] != SVMC_PUT) return fail(SVMC_ERR_UNKNOWN_PAYOFF, "unknown option payoff code");
+        SVMC_REQUIRE(std::isfinite(strikes_host[k]), std::string(fn) + ": a strike is not finite");
+    }
+    SVMC_REQUIRE(2 * static_cast<size_t>(n_params) * K < (1u << 30), std::string(fn) + ": too many strikes");
+    return SVMC_OK;
+}
+
+// the byte offsets of the table's host image: expiries [2P m], groups, then strikes / is_put / intrinsic [2P K] and the steps [P]
+struct CmcSensImage {
+    size_t o_groups, o_k, bytes;
+    int max_groups;
+};
+static CmcSensImage cmc_sens_image(int m, size_t K, int P)
+{
+    CmcSensImage im;
+    im.max_groups = static_cast<int>(K / SENS_KT) + m;     // every expiry may end in a ragged group
+    im.o_groups = align8(sizeof(CmcExpiry) * 2 * P * m);
+    im.o_k = im.o_groups + align8(sizeof(CmcGroup) * im.max_groups);
+    im.bytes = im.o_k + sizeof(double) * (6 * P * K + P);
+    return im;
+}
+size_t cmc_sens_image_bytes_of(int n_expiries, size_t total_strikes, int n_params)
+{
+    return cmc_sens_image(n_expiries, total_strikes, n_params).bytes;
+}
+size_t cmc_sens_workspace_bytes_of(size_t n_path, int n_expiries, size_t total_strikes, int n_params)
+{
+    const size_t rows = cmc_rows(n_path), P = static_cast<size_t>(n_params), K = total_strikes, m = static_cast<size_t>(n_expiries);
+    // kp, ln_kp, shift [2P K]; fwd [2P m][4]; stats; the forward partials; q partials and q; the pair shifts and partials; the results
+    return cmc_sens_image(n_expiries, total_strikes, n_params).bytes +
+           sizeof(double) * (6 * P * K + 8 * P * m + 2 * P * m * SVMC_CMC_STATS_DOUBLES + rows * 6 * P * m + rows * 2 * P * K + 2 * P * K +
+                             2 * P * K + rows * SENS_PQ * P * K + SVMC_CMC_SENS_ROWS * P * K);
+}
+
+// The sensitivity tail queued on `stream` (no synchronisation): the table's image is built in `image` (cmc_sens_image_bytes_of; the
+// caller keeps it until the stream has passed the upload), *results_dev gets the device address of the [P][3][K] results.  The
+// arguments are cmc_sens_check'ed by the caller.
+int cmc_sens_enqueue(const char *fn, const double *const *up_mu, const double *const *up_cv, const double *const *dn_mu,
+                     const double *const *dn_cv, size_t n_path, const double *forwards_host, const double *discfactors_host, int n_expiries,
+                     const double *strikes_host, const int8_t *types_host, const size_t *strike_offsets_host, int n_params,
+                     const double *steps_host, int recenter, void *image, void *workspace, size_t workspace_bytes, hipStream_t stream,
+                     double **results_dev)
+{
+    SVMC_REQUIRE(up_mu && up_cv && dn_mu && dn_cv && image && workspace && results_dev, std::string(fn) + ": null pointer");
+    const int m = n_expiries, P = n_params, J = 2 * P;
+    const size_t K = strike_offsets_host[m];
+    for (int r = 0; r < P * m; ++r)
+        SVMC_REQUIRE(up_mu[r] && up_cv[r] && dn_mu[r] && dn_cv[r], std::string(fn) + ": null snapshot");
+    if (workspace_bytes < cmc_sens_workspace_bytes_of(n_path, m, K, P))
+        return fail(SVMC_ERR_WORKSPACE, std::string(fn) + ": workspace too small (svmc_cmc_sens_workspace_bytes)");
+    const CmcSensImage im = cmc_sens_image(m, K, P);
+    unsigned char *img = static_cast<unsigned char *>(image);
+    CmcExpiry *ex = reinterpret_cast<CmcExpiry *>(img);
+    CmcGroup *gr = reinterpret_cast<CmcGroup *>(img + im.o_groups);
+    double *kd = reinterpret_cast<double *>(img + im.o_k);
+    const size_t JK = static_cast<size_t>(J) * K;
+    int G = 0;
+    for (int i = 0; i < m; ++i) {
+        const int k0 = static_cast<int>(strike_offsets_host[i]), k1 = static_cast<int>(strike_offsets_host[i + 1]);
+        for (int k = k0; k < k1; k += SENS_KT) gr[G++] = CmcGroup{i, k, (k1 - k < SENS_KT) ? k1 - k : SENS_KT, 0};
+        for (int j = 0; j < J; ++j) {
+            const int p = j / 2, r = p * m + i, o = j * static_cast<int>(K);
+            const bool up = (j & 1) == 0;
+            ex[j * m + i] = CmcExpiry{up ? up_mu[r] : dn_mu[r], up ? up_cv[r] : dn_cv[r], forwards_host[i], std::log(forwards_host[i]),
+                                      discfactors_host[i], o + k0, o + k1};
+            for (int k = k0; k < k1; ++k) {
+                const bool put = types_host[k] == SVMC_PUT;
+                kd[o + k] = strikes_host[k];
+                kd[JK + o + k] = put ? 1.0 : 0.0;
+                kd[2 * JK + o + k] = put ? std::fmax(strikes_host[k] - forwards_host[i], 0.0) : std::fmax(forwards_host[i] - strikes_host[k], 0.0);
+            }
+        }
+    }
+    for (int p = 0; p < P; ++p) kd[3 * JK + p] = steps_host[p];
+    unsigned char *w = static_cast<unsigned char *>(workspace);
+    SVMC_HIP_TRY(hipMemcpyAsync(w, img, im.bytes, hipMemcpyHostToDevice, stream));
+    double *d = reinterpret_cast<double *>(w + im.o_k);
+    const size_t Jm = static_cast<size_t>(J) * m;
+    CmcTable t;
+    t.expiries = reinterpret_cast<const CmcExpiry *>(w);
+    t.groups = nullptr;
+    t.strikes = d;
+    t.is_put = d + JK;
+    t.intrinsic = d + 2 * JK;
+    t.kp = d + 3 * JK + P;
+    t.ln_kp = t.kp + JK;
+    t.shift = t.ln_kp + JK;
+    t.fwd = t.shift + JK;
+    t.stats = t.fwd + 4 * Jm;
+    t.fwd_partials = t.stats + SVMC_CMC_STATS_DOUBLES * Jm;
+    t.pay_partials = nullptr;
+    t.out = nullptr;
+    t.m = static_cast<int>(Jm);
+    t.K = static_cast<int>(JK);
+    t.rows = cmc_rows(n_path);
+    CmcSensTable st;
+    st.groups = reinterpret_cast<const CmcGroup *>(w + im.o_groups);
+    st.steps = d + 3 * JK;
+    st.q_partials = t.fwd_partials + static_cast<size_t>(t.rows) * 3 * Jm;
+    st.q = st.q_partials + static_cast<size_t>(t.rows) * JK;
+    st.pair_shift = st.q + JK;
+    st.pair_partials = st.pair_shift + JK;
+    st.out = st.pair_partials + static_cast<size_t>(t.rows) * SENS_PQ * P * K;
+    st.P = P;
+    st.m = m;
+    st.K = static_cast<int>(K);
+    *results_dev = st.out;
+
+    hipLaunchKernelGGL(cmc_forward_kernel, dim3(t.rows, static_cast<unsigned>(Jm)), dim3(BLOCK), 0, stream, t, n_path);
+    if (int rc = check_launch(fn)) return rc;
+    hipLaunchKernelGGL(cmc_forward_finish_kernel, dim3(static_cast<unsigned>(Jm)), dim3(BLOCK), 0, stream, t, n_path, recenter ? 1 : 0);
+    if (int rc = check_launch(fn)) return rc;
+    if (K == 0) return SVMC_OK;
+    const unsigned uG = static_cast<unsigned>(G), uK = static_cast<unsigned>(K);
+    if (recenter) {                                        // (without recentring q is not read)
+        hipLaunchKernelGGL(cond_sens_jobs_kernel, dim3(t.rows, uG, static_cast<unsigned>(J)), dim3(BLOCK), 0, stream, t, st, n_path);
+        if (int rc = check_launch(fn)) return rc;
+        hipLaunchKernelGGL(cond_sens_finish_kernel, dim3(uK, static_cast<unsigned>(J)), dim3(BLOCK), 0, stream, t, st, n_path, 0);
+        if (int rc = check_launch(fn)) return rc;
+    }
+    hipLaunchKernelGGL(cond_sens_pairs_kernel, dim3(t.rows, uG, static_cast<unsigned>(P)), dim3(BLOCK), 0, stream, t, st, n_path, recenter ? 1 : 0);
+    if (int rc = check_launch(fn)) return rc;
+    hipLaunchKernelGGL(cond_sens_finish_kernel, dim3(uK, static_cast<unsigned>(P)), dim3(BLOCK), 0, stream, t, st, n_path, 1);
+    return check_launch(fn);
+}
+
 }  // namespace svmc
 
 using namespace svmc;
@@ -1073,6 +1620,83 @@ int svmc_cmc_greeks_chain(const double *const *mu_snapshots_host, const double *
     return cmc_greeks_chain("svmc_cmc_greeks_chain", mu_snapshots_host, cv_snapshots_host, n_path, forwards_host, discfactors_host,
                             n_expiries, strikes_host, types_host, strike_offsets_host, recenter, greeks_host, stats_host, workspace,
                             workspace_bytes, as_stream(stream), nullptr, 0);
+}
+
+int svmc_cmc_many_workspace_bytes(int n_jobs, int n_slices, size_t *bytes)
+{
+    SVMC_REQUIRE(bytes != nullptr && n_jobs >= 1 && n_jobs <= SVMC_MANY_MAX_JOBS && n_slices >= 1 && n_slices <= MAX_CHAIN_SLICES,
+                 "svmc_cmc_many_workspace_bytes: null output, n_jobs outside [1, SVMC_MANY_MAX_JOBS] or n_slices outside [1, 16]");
+    *bytes = cmc_many_table_bytes(n_jobs, n_slices);
+    return SVMC_OK;
+}
+
+// (the job table is built in pageable memory here: the call returns after the stream is synchronised)
+int svmc_logsv_chain_cmc_many(size_t n_path, int n_jobs, int n_slices, const int *nb_steps_host, const double *dts_host,
+                              const double *params_host, int is_spot_measure, const uint64_t *seeds_host, const uint32_t *call_ids_host,
+                              uint64_t path_offset, double *mu_snapshots, double *cv_snapshots, void *workspace, size_t workspace_bytes,
+                              svmc_stream_t stream)
+{
+    const char *fn = "svmc_logsv_chain_cmc_many";
+    SVMC_REQUIRE(n_jobs >= 1 && n_jobs <= SVMC_MANY_MAX_JOBS && n_slices >= 1 && n_slices <= MAX_CHAIN_SLICES,
+                 std::string(fn) + ": n_jobs outside [1, SVMC_MANY_MAX_JOBS] or n_slices outside [1, 16]");
+    if (workspace == nullptr || workspace_bytes < cmc_many_table_bytes(n_jobs, n_slices))
+        return fail(workspace ? SVMC_ERR_WORKSPACE : SVMC_ERR_INVALID_ARGUMENT, std::string(fn) + ": workspace null or too small (svmc_cmc_many_workspace_bytes)");
+    std::vector<unsigned char> table(cmc_many_table_bytes(n_jobs, n_slices));
+    if (int rc = logsv_cmc_step_many(fn, n_path, n_jobs, n_slices, nb_steps_host, dts_host, params_host, is_spot_measure, seeds_host,
+                                     call_ids_host, path_offset, table.data(), workspace, mu_snapshots, cv_snapshots, as_stream(stream)))
+        return rc;
+    SVMC_HIP_TRY(hipStreamSynchronize(as_stream(stream)));
+    return SVMC_OK;
+}
+
+int svmc_heston_chain_cmc_many(size_t n_path, int n_jobs, int n_slices, const int *nb_steps_host, const double *dts_host,
+                               const double *params_host, const uint64_t *seeds_host, const uint32_t *call_ids_host, uint64_t path_offset,
+                               double *mu_snapshots, double *cv_snapshots, void *workspace, size_t workspace_bytes, svmc_stream_t stream)
+{
+    const char *fn = "svmc_heston_chain_cmc_many";
+    SVMC_REQUIRE(n_jobs >= 1 && n_jobs <= SVMC_MANY_MAX_JOBS && n_slices >= 1 && n_slices <= MAX_CHAIN_SLICES,
+                 std::string(fn) + ": n_jobs outside [1, SVMC_MANY_MAX_JOBS] or n_slices outside [1, 16]");
+    if (workspace == nullptr || workspace_bytes < cmc_many_table_bytes(n_jobs, n_slices))
+        return fail(workspace ? SVMC_ERR_WORKSPACE : SVMC_ERR_INVALID_ARGUMENT, std::string(fn) + ": workspace null or too small (svmc_cmc_many_workspace_bytes)");
+    std::vector<unsigned char> table(cmc_many_table_bytes(n_jobs, n_slices));
+    if (int rc = heston_cmc_step_many(fn, n_path, n_jobs, n_slices, nb_steps_host, dts_host, params_host, seeds_host, call_ids_host,
+                                      path_offset, table.data(), workspace, mu_snapshots, cv_snapshots, as_stream(stream)))
+        return rc;
+    SVMC_HIP_TRY(hipStreamSynchronize(as_stream(stream)));
+    return SVMC_OK;
+}
+
+int svmc_cmc_sens_workspace_bytes(size_t n_path, int n_expiries, size_t total_strikes, int n_params, size_t *bytes)
+{
+    SVMC_REQUIRE(bytes != nullptr && n_expiries >= 1 && n_params >= 1 && n_params <= SVMC_GREEKS_MAX_PARAMS,
+                 "svmc_cmc_sens_workspace_bytes: null output, no expiries or n_params outside [1, SVMC_GREEKS_MAX_PARAMS]");
+    *bytes = cmc_sens_workspace_bytes_of(n_path, n_expiries, total_strikes, n_params);
+    return SVMC_OK;
+}
+
+int svmc_cmc_sens_chain(const double *const *up_mu_host, const double *const *up_cv_host, const double *const *dn_mu_host,
+                        const double *const *dn_cv_host, size_t n_path, const double *forwards_host, const double *discfactors_host,
+                        int n_expiries, const double *strikes_host, const int8_t *types_host, const size_t *strike_offsets_host,
+                        int n_params, const double *steps_host, int recenter, double *sens_host, void *workspace, size_t workspace_bytes,
+                        svmc_stream_t stream)
+{
+    const char *fn = "svmc_cmc_sens_chain";
+    SVMC_REQUIRE(sens_host != nullptr, std::string(fn) + ": null pointer");
+    if (int rc = cmc_sens_check(fn, n_path, forwards_host, discfactors_host, n_expiries, strikes_host, types_host, strike_offsets_host,
+                                n_params, steps_host))
+        return rc;
+    const size_t K = strike_offsets_host[n_expiries];
+    std::vector<unsigned char> image(cmc_sens_image_bytes_of(n_expiries, K, n_params));
+    double *res = nullptr;
+    if (int rc = cmc_sens_enqueue(fn, up_mu_host, up_cv_host, dn_mu_host, dn_cv_host, n_path, forwards_host, discfactors_host, n_expiries,
+                                  strikes_host, types_host, strike_offsets_host, n_params, steps_host, recenter, image.data(), workspace,
+                                  workspace_bytes, as_stream(stream), &res))
+        return rc;
+    if (K > 0)
+        SVMC_HIP_TRY(hipMemcpyAsync(sens_host, res, static_cast<size_t>(SVMC_CMC_SENS_ROWS) * n_params * K * sizeof(double),
+                                    hipMemcpyDeviceToHost, as_stream(stream)));
+    SVMC_HIP_TRY(hipStreamSynchronize(as_stream(stream)));     // the table's host image and the results' landing
+    return SVMC_OK;
 }
 
 }  // extern "C"

@@ -152,6 +152,30 @@ int cmc_greeks_chain(const char *fn, const double *const *mu_snapshots_host, con
                      const int8_t *types_host, const size_t *strike_offsets_host, int recenter, double *greeks_host, double *stats_host,
                      void *workspace, size_t workspace_bytes, hipStream_t stream, void *pinned, size_t pinned_bytes);
 size_t cmc_greeks_pinned_bytes_of(int n_expiries, size_t total_strikes);
+// ... many conditional jobs of one chain in ONE stepping launch (svmc_*_chain_cmc_many's body): the job table is filled in
+// table_host (cmc_many_table_bytes; kept by the caller until the stream has passed the upload) and uploaded to table_dev, job j's
+// rows are j m + i of mu_snapshots / cv_snapshots; params_host rows as svmc_*_chain_price_many
+size_t cmc_many_table_bytes(int n_jobs, int n_slices);
+int logsv_cmc_step_many(const char *fn, size_t n_path, int n_jobs, int n_slices, const int *nb_steps_host, const double *dts_host,
+                        const double *params_host, int is_spot_measure, const uint64_t *seeds, const uint32_t *call_ids,
+                        uint64_t path_offset, void *table_host, void *table_dev, double *mu_snapshots, double *cv_snapshots,
+                        hipStream_t stream);
+int heston_cmc_step_many(const char *fn, size_t n_path, int n_jobs, int n_slices, const int *nb_steps_host, const double *dts_host,
+                         const double *params_host, const uint64_t *seeds, const uint32_t *call_ids, uint64_t path_offset,
+                         void *table_host, void *table_dev, double *mu_snapshots, double *cv_snapshots, hipStream_t stream);
+// ... and the sensitivity tail (svmc_cmc_sens_chain's body): its checks, the launches queued on `stream` from a host image the caller
+// keeps until the stream has passed the upload (up / dn rows [P][m]; *results_dev: the [P][SVMC_CMC_SENS_ROWS][K] results on the
+// device), and the sizes of the image and the workspace
+int cmc_sens_check(const char *fn, size_t n_path, const double *forwards_host, const double *discfactors_host, int n_expiries,
+                   const double *strikes_host, const int8_t *types_host, const size_t *strike_offsets_host, int n_params,
+                   const double *steps_host);
+int cmc_sens_enqueue(const char *fn, const double *const *up_mu, const double *const *up_cv, const double *const *dn_mu,
+                     const double *const *dn_cv, size_t n_path, const double *forwards_host, const double *discfactors_host, int n_expiries,
+                     const double *strikes_host, const int8_t *types_host, const size_t *strike_offsets_host, int n_params,
+                     const double *steps_host, int recenter, void *image, void *workspace, size_t workspace_bytes, hipStream_t stream,
+                     double **results_dev);
+size_t cmc_sens_image_bytes_of(int n_expiries, size_t total_strikes, int n_params);
+size_t cmc_sens_workspace_bytes_of(size_t n_path, int n_expiries, size_t total_strikes, int n_params);
 // svmc_greeks.hip: the Greeks tail (svmc_greeks_payoff_chain's body) -- its checks, the two launches queued on `stream` from a host
 // image the caller keeps until the stream has passed the upload (rows_host [1 + 2P][m] job-major; base_out / sens_out device or
 // pinned, null: inside the workspace at *results_dev), and the sizes of the workspace and the image

@@ -384,6 +384,7 @@ CMC_GREEKS_STATS_DOUBLES = 6   # SVMC_CMC_GREEKS_STATS_DOUBLES
 CMC_GREEKS_FIELDS = ("price", "stderr", "delta", "delta_stderr", "dual_delta", "dual_delta_stderr", "gamma", "gamma_stderr",
                      "dual_gamma", "dual_gamma_stderr")
 CMC_GREEKS_STATS_FIELDS = CMC_STATS_FIELDS + ("n_zero_cv",)
+CMC_SENS_ROWS = 3              # SVMC_CMC_SENS_ROWS: sens, its error, n_pairs (row f14)
 
 
 def cmc_greeks_dict(res: np.ndarray, slices: Sequence[slice]) -> dict:
@@ -1196,6 +1197,112 @@ class HipEngine:
             sess, ch["ttms"], ch["forwards"], ch["discfactors"], ch["m"], ch["strikes"], ch["codes"], ch["offsets"], float(v0),
             float(theta), float(kappa), float(rho), float(volvol), int(nb_steps_per_year), int(bool(recenter)), int(seed),
             int(call_id), g, st), "heston_chain_cmc_kernel")
+
+    # ---- many conditional jobs in one stepping launch and the parameter sensitivities (include/svmc.h) ---------
+    def chain_cmc_many(self, model: str, nb_steps: Sequence[int], dts: Sequence[float], params: np.ndarray, seeds: Sequence[int],
+                       call_ids: Sequence[int], mode: int = 1, mu_row: int = 0) -> None:
+        """svmc_logsv_chain_cmc_many (model "logsv", mode = is_spot_measure, params [J][6 + m]) or svmc_heston_chain_cmc_many
+        ("heston", params [J][5]): expiry i of job j goes to snapshot rows mu_row + j m + i (mu) and mu_row + (J + j) m + i (cv)"""
+        if model not in ("logsv", "heston"):
+            raise ValueError(f"chain_cmc_many: unknown model {model!r}")
+        n_jobs, jobs = self._many_jobs(params, seeds, call_ids)
+        m = len(nb_steps)
+        nb = np.ascontiguousarray(nb_steps, dtype=np.int32)
+        dt = np.ascontiguousarray(dts, dtype=np.float64)
+        self.reserve_snapshots(mu_row + 2 * n_jobs * m)
+        nbytes = C.c_size_t(0)
+        _lib.check(self.lib.svmc_cmc_many_workspace_bytes(n_jobs, m, C.byref(nbytes)))
+        ws_ptr, _ = self.alloc_sums((nbytes.value + 7) // 8, "cmc_many_table")
+        head = (self.n_path, n_jobs, m, nb.ctypes.data_as(C.POINTER(C.c_int)), dt.ctypes.data_as(C.POINTER(C.c_double)), jobs[0])
+        tail = (jobs[1], jobs[2], self.path_offset, self.snapshot_ptr(mu_row), self.snapshot_ptr(mu_row + n_jobs * m), ws_ptr,
+                nbytes.value, self.stream)
+        if model == "logsv":
+            _lib.check(self.lib.svmc_logsv_chain_cmc_many(*head, int(bool(mode)), *tail))
+        else:
+            _lib.check(self.lib.svmc_heston_chain_cmc_many(*head, *tail))
+
+    def conditional_sens(self, forwards, discfactors, strikes: Sequence[np.ndarray], codes: Sequence[np.ndarray], steps,
+                         recenter: bool = True, up_rows=None, dn_rows=None, host_rows=None):
+        """the sensitivity tail (svmc_cmc_sens_chain) on resident (mu, cv): parameter p's up job reads snapshot rows up_rows[p] =
+        (mu rows [m], cv rows [m]), its dn job dn_rows[p].  host_rows = (mu_up, cv_up, mu_dn, cv_dn), each [P][m] host arrays,
+        instead: uploaded to snapshot rows first.  Returns sens [P][CMC_SENS_ROWS][K] and the chain's slices."""
+        ch = marshalled_chain(np.zeros(len(strikes)), forwards, discfactors, strikes, codes)
+        m, K = ch["m"], ch["total"]
+        h = np.ascontiguousarray(np.atleast_1d(np.asarray(steps, dtype=np.float64))).ravel()
+        P = h.size
+        if host_rows is not None:
+            self.reserve_snapshots(4 * P * m)
+            rows = [[[0] * m for _ in range(P)] for _ in range(4)]
+            r = 0
+            for a, block in enumerate(host_rows):
+                if len(block) != P or any(len(job) != m for job in block):
+                    raise ValueError("one host array per (parameter, expiry) for each of mu_up, cv_up, mu_dn, cv_dn")
+                for p in range(P):
+                    for i in range(m):
+                        x = np.ascontiguousarray(block[p][i], dtype=np.float64)
+                        if x.shape != (self.n_path,):
+                            raise ValueError("a host row must hold one value per path of the engine")
+                        self.upload(self.snapshot_ptr(r), x)
+                        rows[a][p][i] = r
+                        r += 1
+            up_rows = [(rows[0][p], rows[1][p]) for p in range(P)]
+            dn_rows = [(rows[2][p], rows[3][p]) for p in range(P)]
+        if up_rows is None or dn_rows is None or len(up_rows) != P or len(dn_rows) != P or \
+                any(len(mu) != m or len(cv) != m for mu, cv in list(up_rows) + list(dn_rows)):
+            raise ValueError("one mu row and one cv row per expiry for each up / dn job of the P steps")
+        ptrs = lambda which, jobs: (C.c_void_p * max(P * m, 1))(*[self.snapshot_ptr(r) for job in jobs for r in job[which]])  # noqa: E731
+        nbytes = C.c_size_t(0)
+        _lib.check(self.lib.svmc_cmc_sens_workspace_bytes(self.n_path, m, K, P, C.byref(nbytes)))
+        ws_ptr, _ = self.alloc_sums((nbytes.value + 7) // 8, "cmc_sens_workspace")
+        sens = np.empty((max(P, 1), CMC_SENS_ROWS, max(K, 1)))
+        dp = C.POINTER(C.c_double)
+        _lib.check(self.lib.svmc_cmc_sens_chain(
+            ptrs(0, up_rows), ptrs(1, up_rows), ptrs(0, dn_rows), ptrs(1, dn_rows), self.n_path, ch["forwards"], ch["discfactors"], m,
+            ch["strikes"], ch["codes"], ch["offsets"], P, h.ctypes.data_as(dp), int(bool(recenter)), sens.ctypes.data_as(dp), ws_ptr,
+            nbytes.value, self.stream))
+        return sens[:P, :, :K], ch["slices"]
+
+    def price_chain_cmc_many_fused(self, ch: dict, model: str, params: np.ndarray, seeds: Sequence[int], call_ids: Sequence[int],
+                                   mode: int, nb_steps_per_year: int, recenter: bool):
+        """J conditional jobs of one chain as ONE svmc_logsv_chain_price_cmc_many (model "logsv", mode = is_spot_measure, params
+        [J][6 + m]) or svmc_heston_chain_price_cmc_many ("heston", params [J][5]) call on this engine's session, J at most
+        MANY_MAX_JOBS: per job the (prices, stderrs, stats) of the single fused call with its (seed, call id)"""
+        if model not in ("logsv", "heston"):
+            raise ValueError(f"price_chain_cmc_many_fused: unknown model {model!r}")
+        n_jobs, jobs = self._many_jobs(params, seeds, call_ids)
+        res, stats = np.empty((2, n_jobs, max(ch["total"], 1))), np.empty((n_jobs, ch["m"], CMC_STATS_DOUBLES))
+        dp = C.POINTER(C.c_double)
+        fn = {"logsv": self.lib.svmc_logsv_chain_price_cmc_many, "heston": self.lib.svmc_heston_chain_price_cmc_many}[model]
+        modes = (int(bool(mode)),) if model == "logsv" else ()
+        self._session_call(ch, lambda sess: fn(
+            sess, ch["ttms"], ch["forwards"], ch["discfactors"], ch["m"], ch["strikes"], ch["codes"], ch["offsets"], n_jobs, *jobs, *modes,
+            int(nb_steps_per_year), int(bool(recenter)), C.cast(res.ctypes.data, dp), C.cast(res.ctypes.data + res.strides[0], dp),
+            stats.ctypes.data_as(dp)), f"{model}_chain_cond_many_kernel")
+        return [([res[0, j, sl] for sl in ch["slices"]], [res[1, j, sl] for sl in ch["slices"]], cmc_stats_dicts(stats[j]))
+                for j in range(n_jobs)]
+
+    def price_chain_cmc_sens_fused(self, ch: dict, model: str, rows: np.ndarray, steps: np.ndarray, mode: int, nb_steps_per_year: int,
+                                   recenter: bool, seed: int, call_id: int):
+        """svmc_logsv_chain_price_cmc_sens (model "logsv", mode = is_spot_measure, rows [1 + 2P][6 + m]) or
+        svmc_heston_chain_price_cmc_sens ("heston", rows [1 + 2P][5]) on this engine's session: the job table's rows on ONE (seed,
+        call id).  Returns (fields, stats) as conditional_greeks for the base job, and sens [P][CMC_SENS_ROWS][K]."""
+        if model not in ("logsv", "heston"):
+            raise ValueError(f"price_chain_cmc_sens_fused: unknown model {model!r}")
+        rows = np.ascontiguousarray(rows, dtype=np.float64)
+        h = np.ascontiguousarray(steps, dtype=np.float64).ravel()
+        P, K = h.size, max(ch["total"], 1)
+        if rows.ndim != 2 or rows.shape[0] != 1 + 2 * P:
+            raise ValueError("the job table has one base row and an up and a dn row per step")
+        res, stats = np.empty((CMC_GREEKS_ROWS, K)), np.empty((ch["m"], CMC_GREEKS_STATS_DOUBLES))
+        sens = np.empty((max(P, 1), CMC_SENS_ROWS, K))
+        dp = C.POINTER(C.c_double)
+        fn = {"logsv": self.lib.svmc_logsv_chain_price_cmc_sens, "heston": self.lib.svmc_heston_chain_price_cmc_sens}[model]
+        modes = (int(bool(mode)),) if model == "logsv" else ()
+        self._session_call(ch, lambda sess: fn(
+            sess, ch["ttms"], ch["forwards"], ch["discfactors"], ch["m"], ch["strikes"], ch["codes"], ch["offsets"], P,
+            rows.ctypes.data_as(dp), h.ctypes.data_as(dp), *modes, int(nb_steps_per_year), int(bool(recenter)), int(seed), int(call_id),
+            res.ctypes.data_as(dp), stats.ctypes.data_as(dp), sens.ctypes.data_as(dp)), f"{model}_chain_cond_many_kernel")
+        return cmc_greeks_dict(res, ch["slices"]), cmc_greeks_stats_dicts(stats), sens[:P]
 
     # ---- Monte Carlo chain Greeks on common random numbers (include/svmc.h, svmc_greeks.hip) ------------------------------------
     def greeks_payoffs(self, forwards, discfactors, strikes: Sequence[np.ndarray], codes: Sequence[np.ndarray], steps=(),

@@ -26,7 +26,8 @@ from ..utils.config import VariableType
 from ..utils.funcs import next_rng_call, set_time_grid, time_grid_steps, timer
 from ..analytic import AnalyticGrid, chain_prices_from_sums, chain_sums
 from ..utils import mgf_pricer as mgfp
-from .logsv_pricer import _broadcast_state, check_conditional_request, conditional_greeks_shaped, conditional_log_return_pdf
+from .logsv_pricer import (_broadcast_state, check_conditional_request, check_conditional_sens_expiries, conditional_greeks_shaped,
+                           conditional_log_return_pdf, conditional_many_shaped, conditional_sens_shaped)
 from .model_pricer import ModelParams, ModelPricer
 
 
@@ -94,13 +95,26 @@ class HestonPricer(ModelPricer):
     def model_mc_chain_greeks_conditional(self, option_chain: OptionChain, params: HestonParams, nb_path: int = 100000,
                                           variable_type: VariableType = VariableType.LOG_RETURN, **kwargs) -> dict:
         """model_mc_price_chain_conditional with delta, dual delta, gamma and dual gamma (heston_mc_chain_greeks_conditional);
-        recenter= and return_stats= are passed on"""
+        recenter=, return_stats=, wrt=, rel_bump= and bumps= are passed on"""
         return heston_mc_chain_greeks_conditional(
             v0=params.v0, theta=params.theta, kappa=params.kappa, rho=params.rho, volvol=params.volvol, ttms=option_chain.ttms,
             forwards=option_chain.forwards, discfactors=option_chain.discfactors, strikes_ttms=option_chain.strikes_ttms,
             optiontypes_ttms=option_chain.optiontypes_ttms, nb_path=nb_path, variable_type=variable_type,
             scheme=kwargs.get("scheme", "euler"), nb_steps_per_year=kwargs.get("nb_steps_per_year", 360), seed=kwargs.get("seed"),
             comm=kwargs.get("comm"), devices=kwargs.get("devices"), recenter=kwargs.get("recenter", True),
+            return_stats=kwargs.get("return_stats", False), wrt=kwargs.get("wrt", ()), rel_bump=kwargs.get("rel_bump", 1e-3),
+            bumps=kwargs.get("bumps"))
+
+    def model_mc_price_chain_conditional_many(self, option_chain: OptionChain, params_list: Sequence[HestonParams],
+                                              nb_path: int = 100000, variable_type: VariableType = VariableType.LOG_RETURN,
+                                              seeds: Optional[Sequence[int]] = None, **kwargs) -> list:
+        """model_mc_price_chain_conditional for several parameter sets, each with its own stream
+        (heston_mc_chain_pricer_conditional_many); recenter= and return_stats= are passed on"""
+        return heston_mc_chain_pricer_conditional_many(
+            params_list=params_list, ttms=option_chain.ttms, forwards=option_chain.forwards, discfactors=option_chain.discfactors,
+            strikes_ttms=option_chain.strikes_ttms, optiontypes_ttms=option_chain.optiontypes_ttms, nb_path=nb_path,
+            variable_type=variable_type, scheme=kwargs.get("scheme", "euler"), nb_steps_per_year=kwargs.get("nb_steps_per_year", 360),
+            seeds=seeds, comm=kwargs.get("comm"), devices=kwargs.get("devices"), recenter=kwargs.get("recenter", True),
             return_stats=kwargs.get("return_stats", False))
 
     def get_log_return_mc_pdf_conditional(self, params: HestonParams, ttm: float, x_grid: np.ndarray, nb_path: int = 100000,
@@ -370,18 +384,65 @@ def heston_mc_chain_greeks_conditional(ttms: np.ndarray, forwards: np.ndarray, d
                                        theta: float, kappa: float, rho: float, volvol: float, nb_path: int = 100000,
                                        variable_type: VariableType = VariableType.LOG_RETURN, scheme="euler",
                                        nb_steps_per_year: int = 360, seed: Optional[int] = None, comm=None, devices=None,
-                                       reduce: Optional[str] = None, recenter: bool = True, return_stats: bool = False) -> dict:
+                                       reduce: Optional[str] = None, recenter: bool = True, return_stats: bool = False,
+                                       wrt: Optional[Sequence[str]] = (), rel_bump: float = 1e-3, bumps: Optional[dict] = None) -> dict:
     """heston_mc_chain_pricer_conditional with delta, dual delta, gamma and dual gamma and their standard errors (include/svmc.h,
     DESIGN.md row f13; see logsv_mc_chain_greeks_conditional for the returned dict).  Same signature and refusals, scheme="qe"
-    among them.  Not in the reference API."""
-    codes = check_conditional_request("heston_mc_chain_greeks_conditional", variable_type, comm, devices, optiontypes_ttms)
+    among them.  wrt (row f14; default (): nothing changes): names among v0 theta kappa rho volvol, or None / "all" -- the
+    dict gains sens[name], sens_stderr[name], n_pairs[name] as logsv_mc_chain_greeks_conditional's does.  Not in the reference
+    API."""
+    who = "heston_mc_chain_greeks_conditional"
+    codes = check_conditional_request(who, variable_type, comm, devices, optiontypes_ttms)
     if _scheme_code(scheme) != HESTON_EULER_FLOOR:
         raise NotImplementedError("heston_mc_chain_greeks_conditional: scheme='qe' is not covered (Euler only)")
+    if not (wrt is None or isinstance(wrt, str) or len(wrt) > 0):
+        rng_seed, call_id = next_rng_call(seed)
+        ch = marshalled_chain(ttms, forwards, discfactors, strikes_ttms, codes)
+        fields, stats = get_engine(nb_path).price_heston_chain_cmc_greeks_fused(ch, v0, theta, kappa, rho, volvol, nb_steps_per_year,
+                                                                                recenter, rng_seed, call_id)
+        return conditional_greeks_shaped(fields, stats, strikes_ttms, return_stats)
+    values = dict(v0=v0, theta=theta, kappa=kappa, rho=rho, volvol=volvol)
+    names, h = greeks_bumps("heston", values, None if isinstance(wrt, str) and wrt == "all" else wrt, rel_bump, bumps)
+    check_conditional_sens_expiries(who, ttms)
+    rows = greeks_job_table("heston", [values[k] for k in HESTON_GREEK_PARAMS], names, h)
     rng_seed, call_id = next_rng_call(seed)
     ch = marshalled_chain(ttms, forwards, discfactors, strikes_ttms, codes)
-    fields, stats = get_engine(nb_path).price_heston_chain_cmc_greeks_fused(ch, v0, theta, kappa, rho, volvol, nb_steps_per_year,
-                                                                            recenter, rng_seed, call_id)
-    return conditional_greeks_shaped(fields, stats, strikes_ttms, return_stats)
+    fields, stats, sens = get_engine(nb_path).price_chain_cmc_sens_fused(ch, "heston", rows, h, 0, nb_steps_per_year, recenter, rng_seed,
+                                                                         call_id)
+    return conditional_sens_shaped(conditional_greeks_shaped(fields, stats, strikes_ttms, return_stats), sens, names, ch["slices"],
+                                   strikes_ttms)
+
+
+def heston_mc_chain_pricer_conditional_many(params_list: Sequence[HestonParams], ttms: np.ndarray, forwards: np.ndarray,
+                                            discfactors: np.ndarray, strikes_ttms: Sequence[np.ndarray],
+                                            optiontypes_ttms: Sequence[np.ndarray], nb_path: int = 100000,
+                                            variable_type: VariableType = VariableType.LOG_RETURN, scheme="euler",
+                                            nb_steps_per_year: int = 360, seeds: Optional[Sequence[int]] = None, comm=None,
+                                            devices=None, recenter: bool = True, return_stats: bool = False) -> list:
+    """heston_mc_chain_pricer_conditional for several independent jobs of ONE chain (see
+    logsv_mc_chain_pricer_conditional_many): job j is bit-equal to heston_mc_chain_pricer_conditional with (params_list[j],
+    seeds[j]); up to MANY_MAX_JOBS jobs per stepping launch, more than 16 expiries as a loop of single calls.  Not in the reference
+    API."""
+    codes = check_conditional_request("heston_mc_chain_pricer_conditional_many", variable_type, comm, devices, optiontypes_ttms)
+    if _scheme_code(scheme) != HESTON_EULER_FLOOR:
+        raise NotImplementedError("heston_mc_chain_pricer_conditional_many: scheme='qe' is not covered (Euler only)")
+    params_list = check_many_args(params_list, seeds)
+    if not params_list:
+        return []
+    if len(ttms) > 16:
+        return [heston_mc_chain_pricer_conditional(
+            ttms=ttms, forwards=forwards, discfactors=discfactors, strikes_ttms=strikes_ttms, optiontypes_ttms=optiontypes_ttms,
+            v0=p.v0, theta=p.theta, kappa=p.kappa, rho=p.rho, volvol=p.volvol, nb_path=nb_path, variable_type=variable_type,
+            nb_steps_per_year=nb_steps_per_year, seed=None if seeds is None else seeds[j], recenter=recenter, return_stats=return_stats)
+            for j, p in enumerate(params_list)]
+    streams = many_job_streams(len(params_list), seeds)
+    rows = np.array([[p.v0, p.theta, p.kappa, p.rho, p.volvol] for p in params_list], dtype=np.float64)
+    ch = marshalled_chain(ttms, forwards, discfactors, strikes_ttms, codes)
+    eng = get_engine(nb_path)
+    out = []
+    for _, part, job_seeds, ids in many_job_chunks(streams, rows):
+        out += eng.price_chain_cmc_many_fused(ch, "heston", part, job_seeds, ids, 0, nb_steps_per_year, recenter)
+    return conditional_many_shaped(out, strikes_ttms, return_stats)
 
 
 def heston_mc_chain_pricer(ttms: np.ndarray, forwards: np.ndarray, discfactors: np.ndarray,

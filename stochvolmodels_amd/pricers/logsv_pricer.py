@@ -259,7 +259,7 @@ class LogSVPricer(ModelPricer):
                                           variable_type: VariableType = VariableType.LOG_RETURN, nb_path: int = 100000,
                                           nb_steps: Optional[int] = None, **kwargs) -> dict:
         """model_mc_price_chain_conditional with delta, dual delta, gamma and dual gamma (logsv_mc_chain_greeks_conditional) on the
-        same step rule; recenter= and return_stats= are passed on"""
+        same step rule; recenter=, return_stats=, wrt=, rel_bump= and bumps= are passed on"""
         etas = params.get_vol_backbone_etas(ttms=option_chain.ttms)
         return logsv_mc_chain_greeks_conditional(
             v0=params.sigma0, theta=params.theta, kappa1=params.kappa1, kappa2=params.kappa2, beta=params.beta, volvol=params.volvol,
@@ -267,7 +267,21 @@ class LogSVPricer(ModelPricer):
             strikes_ttms=option_chain.strikes_ttms, optiontypes_ttms=option_chain.optiontypes_ttms, is_spot_measure=is_spot_measure,
             variable_type=variable_type, nb_path=nb_path, nb_steps_per_year=nb_steps or int(360 * np.max(option_chain.ttms)) + 1,
             seed=kwargs.get("seed"), comm=kwargs.get("comm"), devices=kwargs.get("devices"),
-            recenter=kwargs.get("recenter", True), return_stats=kwargs.get("return_stats", False))
+            recenter=kwargs.get("recenter", True), return_stats=kwargs.get("return_stats", False), wrt=kwargs.get("wrt", ()),
+            rel_bump=kwargs.get("rel_bump", 1e-3), bumps=kwargs.get("bumps"))
+
+    def model_mc_price_chain_conditional_many(self, option_chain: OptionChain, params_list: Sequence[LogSvParams],
+                                              is_spot_measure: bool = True, variable_type: VariableType = VariableType.LOG_RETURN,
+                                              nb_path: int = 100000, nb_steps: Optional[int] = None,
+                                              seeds: Optional[Sequence[int]] = None, **kwargs) -> list:
+        """model_mc_price_chain_conditional for several parameter sets, each with its own stream
+        (logsv_mc_chain_pricer_conditional_many), on the same step rule; recenter= and return_stats= are passed on"""
+        return logsv_mc_chain_pricer_conditional_many(
+            params_list=params_list, ttms=option_chain.ttms, forwards=option_chain.forwards, discfactors=option_chain.discfactors,
+            strikes_ttms=option_chain.strikes_ttms, optiontypes_ttms=option_chain.optiontypes_ttms, is_spot_measure=is_spot_measure,
+            nb_path=nb_path, nb_steps_per_year=nb_steps or int(360 * np.max(option_chain.ttms)) + 1, variable_type=variable_type,
+            seeds=seeds, comm=kwargs.get("comm"), devices=kwargs.get("devices"), recenter=kwargs.get("recenter", True),
+            return_stats=kwargs.get("return_stats", False))
 
     def get_log_return_mc_pdf_conditional(self, params: LogSvParams, ttm: float, x_grid: np.ndarray, nb_path: int = 100000,
                                           seed: Optional[int] = None, recenter: bool = False, return_stderr: bool = False,
@@ -921,7 +935,8 @@ def logsv_mc_chain_greeks_conditional(ttms: np.ndarray, forwards: np.ndarray, di
                                       vol_backbone_etas: np.ndarray, is_spot_measure: bool = True, nb_path: int = 100000,
                                       nb_steps_per_year: int = 360, variable_type: VariableType = VariableType.LOG_RETURN,
                                       seed: Optional[int] = None, comm=None, devices=None, reduce: Optional[str] = None,
-                                      recenter: bool = True, return_stats: bool = False) -> dict:
+                                      recenter: bool = True, return_stats: bool = False, wrt: Optional[Sequence[str]] = (),
+                                      rel_bump: float = 1e-3, bumps: Optional[dict] = None) -> dict:
     """logsv_mc_chain_pricer_conditional with the derivatives of its prices in the forward and the strike (include/svmc.h, DESIGN.md
     row f13): per path the Black-76 delta, dual delta and dual gamma in closed form, each with a standard error -- the exact
     derivatives of the number the conditional pricer returns at the same seed.  Same signature; returns a dict of chain-shaped
@@ -930,14 +945,97 @@ def logsv_mc_chain_greeks_conditional(ttms: np.ndarray, forwards: np.ndarray, di
     engine.CMC_GREEKS_STATS_FIELDS (the conditional pricer's and n_zero_cv, the kept paths whose conditional variance is zero: they
     add no gamma).  price = F delta + K dual_delta and F^2 gamma = K^2 dual_gamma hold to rounding.  With recenter=True the errors
     ignore the noise of the recentring mean, as the price's does.  Refusals: check_conditional_request's.  Not in the reference
-    API."""
-    codes = check_conditional_request("logsv_mc_chain_greeks_conditional", variable_type, comm, devices, optiontypes_ttms,
-                                      is_spot_measure)
+    API.
+
+    wrt (row f14; default (): nothing above changes): a sequence of parameter names, or None / "all" for sigma0 theta kappa1 kappa2
+    beta volvol -- the parameter sensitivities of this estimator on common random numbers.  The base job and per name the pair at
+    +- h (h = rel_bump |value| or bumps[name]; names, bump rules and ValueErrors are mc_greeks.greeks_bumps's) are stepped by ONE
+    launch on one stream; the dict gains sens[name], sens_stderr[name] and n_pairs[name], chain-shaped: the central difference of
+    the two bumped conditional prices and the error of that DIFFERENCE, with the delta-method term of the two recentring means.
+    The ten fields above stay bit-equal to the call with wrt=().  At most 16 expiries."""
+    who = "logsv_mc_chain_greeks_conditional"
+    codes = check_conditional_request(who, variable_type, comm, devices, optiontypes_ttms, is_spot_measure)
+    if not (wrt is None or isinstance(wrt, str) or len(wrt) > 0):
+        rng_seed, call_id = next_rng_call(seed)
+        ch = marshalled_chain(ttms, forwards, discfactors, strikes_ttms, codes)
+        fields, stats = get_engine(nb_path).price_logsv_chain_cmc_greeks_fused(
+            ch, v0, theta, kappa1, kappa2, beta, volvol, vol_backbone_etas, is_spot_measure, nb_steps_per_year, recenter, rng_seed,
+            call_id)
+        return conditional_greeks_shaped(fields, stats, strikes_ttms, return_stats)
+    values = dict(sigma0=v0, theta=theta, kappa1=kappa1, kappa2=kappa2, beta=beta, volvol=volvol)
+    names, h = greeks_bumps("logsv", values, None if isinstance(wrt, str) and wrt == "all" else wrt, rel_bump, bumps)
+    check_conditional_sens_expiries(who, ttms)
+    etas = np.asarray(vol_backbone_etas, dtype=np.float64).ravel()
+    if etas.size != len(ttms):
+        raise ValueError("vol_backbone_etas must have one entry per maturity")
+    rows = greeks_job_table("logsv", np.concatenate([[values[k] for k in LOGSV_GREEK_PARAMS], etas]), names, h)
     rng_seed, call_id = next_rng_call(seed)
     ch = marshalled_chain(ttms, forwards, discfactors, strikes_ttms, codes)
-    fields, stats = get_engine(nb_path).price_logsv_chain_cmc_greeks_fused(
-        ch, v0, theta, kappa1, kappa2, beta, volvol, vol_backbone_etas, is_spot_measure, nb_steps_per_year, recenter, rng_seed, call_id)
-    return conditional_greeks_shaped(fields, stats, strikes_ttms, return_stats)
+    fields, stats, sens = get_engine(nb_path).price_chain_cmc_sens_fused(ch, "logsv", rows, h, int(bool(is_spot_measure)),
+                                                                         nb_steps_per_year, recenter, rng_seed, call_id)
+    return conditional_sens_shaped(conditional_greeks_shaped(fields, stats, strikes_ttms, return_stats), sens, names, ch["slices"],
+                                   strikes_ttms)
+
+
+def check_conditional_sens_expiries(who: str, ttms) -> None:
+    """the sensitivities ride on the many-job stepping launch: at most 16 expiries (refused before any device work)"""
+    if len(ttms) > 16:
+        raise NotImplementedError(f"{who}: wrt= takes at most 16 expiries, got {len(ttms)}")
+
+
+def conditional_sens_shaped(out: dict, sens: np.ndarray, names: Sequence[str], slices, strikes_ttms) -> dict:
+    """adds sens[name], sens_stderr[name] and n_pairs[name] (chain-shaped; the counts as integer arrays) from sens [P][3][K]"""
+    cut = lambda row: chain_shaped([row[sl] for sl in slices], strikes_ttms)         # noqa: E731
+    out["sens"] = {name: cut(sens[j, 0]) for j, name in enumerate(names)}
+    out["sens_stderr"] = {name: cut(sens[j, 1]) for j, name in enumerate(names)}
+    out["n_pairs"] = {name: [p.astype(np.int64) for p in cut(sens[j, 2])] for j, name in enumerate(names)}
+    return out
+
+
+def logsv_mc_chain_pricer_conditional_many(params_list: Sequence[LogSvParams], ttms: np.ndarray, forwards: np.ndarray,
+                                           discfactors: np.ndarray, strikes_ttms: Sequence[np.ndarray],
+                                           optiontypes_ttms: Sequence[np.ndarray], is_spot_measure: bool = True,
+                                           nb_path: int = 100000, nb_steps_per_year: int = 360,
+                                           variable_type: VariableType = VariableType.LOG_RETURN,
+                                           seeds: Optional[Sequence[int]] = None, comm=None, devices=None, recenter: bool = True,
+                                           return_stats: bool = False) -> list:
+    """logsv_mc_chain_pricer_conditional for several independent jobs of ONE chain: job j has the parameters
+    params_list[j] (with their vol-backbone etas) and its own random stream -- seeds[j] (call id 0), or with seeds=None the process
+    seed and the next call id, taken in list order.  Returns per job what logsv_mc_chain_pricer_conditional(..., seed=seeds[j])
+    returns, BIT FOR BIT: (prices, stderrs), with return_stats=True also the statistics.  Up to MANY_MAX_JOBS jobs are stepped by ONE
+    launch (svmc_logsv_chain_price_cmc_many; longer lists in several calls, in order); more than 16 expiries run as a loop of single
+    calls.  Refusals: check_conditional_request's.  Not in the reference API."""
+    codes = check_conditional_request("logsv_mc_chain_pricer_conditional_many", variable_type, comm, devices, optiontypes_ttms,
+                                      is_spot_measure)
+    params_list = check_many_args(params_list, seeds)
+    if not params_list:
+        return []
+    m = len(ttms)
+    etas = [p.get_vol_backbone_etas(ttms=np.asarray(ttms, dtype=float)) for p in params_list]
+    if m > 16:
+        return [logsv_mc_chain_pricer_conditional(
+            ttms=ttms, forwards=forwards, discfactors=discfactors, strikes_ttms=strikes_ttms, optiontypes_ttms=optiontypes_ttms,
+            v0=p.sigma0, theta=p.theta, kappa1=p.kappa1, kappa2=p.kappa2, beta=p.beta, volvol=p.volvol, vol_backbone_etas=e,
+            is_spot_measure=is_spot_measure, nb_path=nb_path, nb_steps_per_year=nb_steps_per_year, variable_type=variable_type,
+            seed=None if seeds is None else seeds[j], recenter=recenter, return_stats=return_stats)
+            for j, (p, e) in enumerate(zip(params_list, etas))]
+    streams = many_job_streams(len(params_list), seeds)
+    rows = np.ones((len(params_list), 6 + m))
+    for row, p in zip(rows, params_list):
+        row[:6] = (p.sigma0, p.theta, p.kappa1, p.kappa2, p.beta, p.volvol)
+    rows[:, 6:] = np.reshape(etas, (len(params_list), m))
+    ch = marshalled_chain(ttms, forwards, discfactors, strikes_ttms, codes)
+    eng = get_engine(nb_path)
+    out = []
+    for _, part, job_seeds, ids in many_job_chunks(streams, rows):
+        out += eng.price_chain_cmc_many_fused(ch, "logsv", part, job_seeds, ids, int(bool(is_spot_measure)), nb_steps_per_year, recenter)
+    return conditional_many_shaped(out, strikes_ttms, return_stats)
+
+
+def conditional_many_shaped(out: list, strikes_ttms: Sequence[np.ndarray], return_stats: bool) -> list:
+    """every job's (prices, stderrs, stats) of the engine's many-job conditional call as the single function returns them"""
+    shaped = [(chain_shaped(pr, strikes_ttms), chain_shaped(se, strikes_ttms), st) for pr, se, st in out]
+    return shaped if return_stats else [(pr, se) for pr, se, _ in shaped]
 
 
 def conditional_log_return_pdf(route, ttm: float, x_grid: np.ndarray, return_stderr: bool = False):

@@ -114,6 +114,26 @@ def compute_mc_vars_greeks_conditional(mu: np.ndarray, cv: np.ndarray, ttm: floa
     return out
 
 
+def compute_mc_vars_sens_conditional(mu_up: np.ndarray, cv_up: np.ndarray, mu_dn: np.ndarray, cv_dn: np.ndarray, step: float,
+                                     forward: float, strikes: np.ndarray, types: np.ndarray, discfactor: float = 1.0,
+                                     recenter: bool = True):
+    """the central difference of two conditional estimates ON THE SAME RANDOMS and the error of that difference (include/svmc.h's
+    svmc_cmc_sens_chain) from host arrays of one expiry: (mu_up, cv_up) the job at theta + step, (mu_dn, cv_dn)
+    the job at theta - step.  Each job is recentred by its own kept-path mean; a pair is kept iff the path is kept in both jobs;
+    with recenter=True the error carries the delta-method term of the two recentring means.  Returns (sens, sens_stderr, n_pairs)
+    in the strikes' shape (n_pairs as integers).  'C' / 'P' only (others: ValueError("not implemented"))."""
+    codes = tilted_type_codes(types)                             # ValueError("not implemented")
+    k = np.asarray(strikes, dtype=np.float64)
+    rows = [np.ascontiguousarray(a, dtype=np.float64).ravel() for a in (mu_up, cv_up, mu_dn, cv_dn)]
+    if rows[0].size == 0 or any(a.size != rows[0].size for a in rows):
+        raise ValueError("mu_up, cv_up, mu_dn and cv_dn must be non-empty and of one length")
+    if not (np.isfinite(step) and step > 0.0):
+        raise ValueError("step must be positive and finite")
+    sens, _ = get_engine(rows[0].size).conditional_sens([float(forward)], [float(discfactor)], [k.ravel()], [codes], [float(step)],
+                                                        bool(recenter), host_rows=[[[a]] for a in rows])
+    return sens[0, 0].reshape(k.shape), sens[0, 1].reshape(k.shape), sens[0, 2].astype(np.int64).reshape(k.shape)
+
+
 def compute_mc_vars_greeks(x0: np.ndarray, forward: float, strikes_ttm: np.ndarray, optiontypes_ttm: np.ndarray,
                            discfactor: float = 1.0, x_up=(), x_dn=(), steps=()) -> dict:
     """the Greeks tail of include/svmc.h's svmc_greeks_payoff_chain on host arrays of one expiry: x0 the base job's terminal
