@@ -731,9 +731,12 @@ __global__ __launch_bounds__(BLOCK) void fill_state_indirect_kernel(double *__re
 //     more power than the store issue it saves -- and were removed again; so were non-temporal and write-through policies.
 //   * what did help is a SHORTER step, the generators' form: ln sigma carried in units of ln2/256 so that exp2u_tab's
 //     reduction is exact, the drift regrouped into four FMAs on host-scaled constants (logsv_step_acc's), rcp_1n for the
-//     1/sigma term (it enters L at 1e-3 of its size): 48 -> 33 VALU instructions per path-step, 2.10 -> 1.95 ms on one box.
-//     Identical in exact arithmetic to :942; rounding differs at the 1e-16 level per step (the tests hold both instantiations
-//     against the reference's golden paths at 1e-12).
+//     1/sigma term (near theta it enters L at 1e-3 of its size): 48 -> 33 VALU instructions per path-step, 2.10 -> 1.95 ms on
+//     one box.  Identical in exact arithmetic to :942; rounding differs at the 1e-16 level per step.  Both instantiations are
+//     held to the recursion in 256-bit arithmetic within the LogSV generator's margins (tests/test_gpu_vol_paths_steps.py),
+//     starts at theta / 50 and theta / 1000 included, where the 1/sigma term moves ln sigma by 0.44 and 8.8 in one step and
+//     the reciprocal's error enters at full size: measured there within 2.9 times the fp64 recursion's own error
+//     (profiles/vol_paths_step_observed_tolerances.txt).
 //   * supplied brownians are loaded a group of four steps ahead.
 //   * round 6: the next call's reads ahead and four steps with their four stores back to back were measured and not kept
 //     (profiles/r06_vol_paths_ab.jsonl).
