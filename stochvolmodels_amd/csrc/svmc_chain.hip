@@ -15,6 +15,7 @@
 
 #include "svmc_internal.h"
 #include "svmc_black.h"
+#include "svmc_quotes.h"
 #include <limits>
 #include <cstring>
 
@@ -595,10 +596,8 @@ static int chain_price_cmc(const char *fn, Session *s, const ChainView &c, int n
                                    [&]() {
                                        SVMC_HIP_TRY(grow(reinterpret_cast<void **>(&s->cmc_cv), s->cmc_cv_bytes, s->n_path * sizeof(double), false));
                                        const size_t K = c.offsets[c.m];
-                                       SVMC_HIP_TRY(grow(&s->cmc_ws, s->cmc_ws_bytes, deriv ? cmc_greeks_workspace_bytes_of(s->n_path, c.m, K)
-                                                                                           : cmc_payoff_workspace_bytes_of(s->n_path, c.m, K), false));
-                                       SVMC_HIP_TRY(grow(&s->cmc_pinned, s->cmc_pinned_bytes, deriv ? cmc_greeks_pinned_bytes_of(c.m, K)
-                                                                                                   : cmc_payoff_pinned_bytes_of(c.m, K), true));
+                                       SVMC_HIP_TRY(grow(&s->cmc_ws, s->cmc_ws_bytes, cmc_workspace_bytes_of(s->n_path, c.m, K, deriv), false));
+                                       SVMC_HIP_TRY(grow(&s->cmc_pinned, s->cmc_pinned_bytes, cmc_pinned_bytes_of(c.m, K, deriv), true));
                                        mu_snap = s->snap;
                                        cv_snap = s->snap + static_cast<size_t>(c.m) * s->n_path;
                                        return SVMC_OK;
@@ -609,12 +608,9 @@ static int chain_price_cmc(const char *fn, Session *s, const ChainView &c, int n
         mus[i] = mu_snap + static_cast<size_t>(i) * s->n_path;
         cvs[i] = cv_snap + static_cast<size_t>(i) * s->n_path;
     }
-    const int rc = deriv ? cmc_greeks_chain(fn, mus.data(), cvs.data(), s->n_path, c.forwards, c.discfactors, c.m, c.strikes, c.types,
-                                            c.offsets, recenter, greeks_host, stats_host, s->cmc_ws, s->cmc_ws_bytes, s->stream,
-                                            s->cmc_pinned, s->cmc_pinned_bytes)
-                         : cmc_payoff_chain(fn, mus.data(), cvs.data(), s->n_path, c.forwards, c.discfactors, c.m, c.strikes, c.types,
-                                            c.offsets, recenter, prices_host, stderrs_host, stats_host, s->cmc_ws, s->cmc_ws_bytes,
-                                            s->stream, s->cmc_pinned, s->cmc_pinned_bytes);
+    const int rc = cmc_tail(fn, mus.data(), cvs.data(), s->n_path, c.forwards, c.discfactors, c.m, c.strikes, c.types, c.offsets, recenter,
+                            prices_host, stderrs_host, greeks_host, stats_host, s->cmc_ws, s->cmc_ws_bytes, s->stream, s->cmc_pinned,
+                            s->cmc_pinned_bytes);
     if (rc == SVMC_OK) stepping_read(s);
     return rc;
 }
@@ -1309,17 +1305,14 @@ static int chain_price_greeks(const char *fn, Session *s, const ChainView &c, in
     const std::vector<uint64_t> seeds(J, seed);
     const std::vector<uint32_t> call_ids(J, call_id);
     std::vector<double> shifts;
-    size_t image_bytes = 0;
     if (int rc = many_step(fn, s, c, J, params, seeds.data(), call_ids.data(), nb_steps_per_year, SVMC_LOG_RETURN, prices, stderrs, true, 0,
                            shifts,
                            [&]() -> int {
-        if (int rc = greeks_check(fn, s->n_path, c.forwards, c.discfactors, c.m, c.strikes, c.types, c.offsets, P, steps)) return rc;
+        if (int rc = check_steps(fn, P, steps, 0)) return rc;
+        if (int rc = check_quotes(fn, s->n_path, c.forwards, c.discfactors, c.m, c.strikes, c.types, c.offsets, 1u << 24, 1)) return rc;
         const size_t K = c.offsets[c.m];
-        image_bytes = greeks_payoff_image_bytes_of(c.m, K, P);
         SVMC_HIP_TRY(grow(&s->greeks_ws, s->greeks_ws_bytes, greeks_payoff_workspace_bytes_of(s->n_path, c.m, K, P), false));
-        SVMC_HIP_TRY(grow(&s->greeks_pinned, s->greeks_pinned_bytes,
-                          image_bytes + (SVMC_GREEKS_BASE_ROWS + static_cast<size_t>(SVMC_GREEKS_SENS_ROWS) * P) * (K > 0 ? K : 1) * sizeof(double),
-                          true));
+        SVMC_HIP_TRY(grow(&s->greeks_pinned, s->greeks_pinned_bytes, greeks_pinned(nullptr, c.m, K, P, nullptr), true));
         return SVMC_OK;
     },
                            [&](const std::vector<int> &nbs, const std::vector<double> &dts, double *) {
@@ -1341,15 +1334,15 @@ static int chain_price_greeks(const char *fn, Session *s, const ChainView &c, in
             return rc;
         SVMC_HIP_TRY(hipMemcpyAsync(mb.sums_pinned, mb.sums, 3 * K * sizeof(double), hipMemcpyDeviceToHost, s->stream));
     }
-    double *base_out = reinterpret_cast<double *>(static_cast<unsigned char *>(s->greeks_pinned) + image_bytes);
-    double *sens_out = base_out + SVMC_GREEKS_BASE_ROWS * K;
+    GreeksResults out;                                     // (the kernels store the results in the page-locked block themselves)
+    greeks_pinned(s->greeks_pinned, c.m, K, P, &out);
     if (int rc = greeks_payoff_enqueue(fn, rows.data(), n, c.forwards, c.discfactors, c.m, c.strikes, c.types, c.offsets, P, steps, mb.spot,
-                                       base_out, sens_out, s->greeks_pinned, s->greeks_ws, s->greeks_ws_bytes, s->stream, nullptr))
+                                       out.base, out.sens, s->greeks_pinned, s->greeks_ws, s->greeks_ws_bytes, s->stream, nullptr))
         return rc;
     SVMC_HIP_TRY(hipStreamSynchronize(s->stream));
     stepping_read(s);
-    memcpy(greeks, base_out, SVMC_GREEKS_BASE_ROWS * K * sizeof(double));
-    if (P > 0) memcpy(sens, sens_out, static_cast<size_t>(SVMC_GREEKS_SENS_ROWS) * P * K * sizeof(double));
+    memcpy(greeks, out.base, SVMC_GREEKS_BASE_ROWS * K * sizeof(double));
+    if (P > 0) memcpy(sens, out.sens, static_cast<size_t>(SVMC_GREEKS_SENS_ROWS) * P * K * sizeof(double));
     return finish_sets(s, c, mb.sums_pinned, shifts, 1, SVMC_LOG_RETURN, prices, stderrs, nullptr, nullptr);
 }
 
@@ -1510,8 +1503,8 @@ int svmc_session_state(svmc_session_t session, double *x_host, double *vol_host,
 // stepping launch of every job.
 template <class Check, class Step>
 static int cmc_many_step(const char *fn, Session *s, const ChainView &c, int n_jobs, const void *params, const uint64_t *seeds,
-                         const uint32_t *call_ids, int nb_steps_per_year, const double *out_a, const double *out_b, Check &&check,
-                         Step &&step)
+                         const uint32_t *call_ids, int nb_steps_per_year, const double *out_a, const double *out_b, size_t quotes_per_strike,
+                         Check &&check, Step &&step)
 {
     SVMC_REQUIRE(s != nullptr, std::string(fn) + ": null session");
     SVMC_REQUIRE(n_jobs >= 1 && n_jobs <= SVMC_MANY_MAX_JOBS, std::string(fn) + ": n_jobs must be in [1, SVMC_MANY_MAX_JOBS]");
@@ -1523,15 +1516,8 @@ static int cmc_many_step(const char *fn, Session *s, const ChainView &c, int n_j
     SVMC_REQUIRE(!s->sharded(), std::string(fn) + ": the conditional estimator is not sharded");
     SVMC_REQUIRE(nb_steps_per_year > 0, std::string(fn) + ": nb_steps_per_year must be positive");
     for (int j = 0; j < n_jobs; ++j) SVMC_REQUIRE(call_ids[j] < (1u << 24), std::string(fn) + ": call_id must fit 24 bits");
-    for (int i = 0; i < c.m; ++i) {
-        SVMC_REQUIRE(c.offsets[i] <= c.offsets[i + 1], std::string(fn) + ": strike offsets must not decrease");
-        SVMC_REQUIRE(std::isfinite(c.forwards[i]) && c.forwards[i] > 0.0, std::string(fn) + ": a forward is not positive and finite");
-        SVMC_REQUIRE(std::isfinite(c.discfactors[i]), std::string(fn) + ": a discount factor is not finite");
-    }
-    for (size_t k = 0; k < c.offsets[c.m]; ++k) {
-        if (c.types[k] != SVMC_CALL && c.types[k] != SVMC_PUT) return fail(SVMC_ERR_UNKNOWN_PAYOFF, "unknown option payoff code");
-        SVMC_REQUIRE(std::isfinite(c.strikes[k]), std::string(fn) + ": a strike is not finite");
-    }
+    if (int rc = check_quotes(fn, s->n_path, c.forwards, c.discfactors, c.m, c.strikes, c.types, c.offsets, 1u << 30, quotes_per_strike))
+        return rc;
     if (int rc = check()) return rc;
     if (int rc = check_chain(fn, s, c, SVMC_LOG_RETURN, out_a, out_b, true)) return rc;
     const size_t n = s->n_path, J = static_cast<size_t>(n_jobs), m = static_cast<size_t>(c.m);
@@ -1566,10 +1552,10 @@ static int chain_price_cmc_many(const char *fn, Session *s, const ChainView &c, 
                                 const uint32_t *call_ids, int nb_steps_per_year, int recenter, double *prices, double *stderrs,
                                 double *stats, Step &&step)
 {
-    if (int rc = cmc_many_step(fn, s, c, n_jobs, params, seeds, call_ids, nb_steps_per_year, prices, stderrs, [&]() -> int {
+    if (int rc = cmc_many_step(fn, s, c, n_jobs, params, seeds, call_ids, nb_steps_per_year, prices, stderrs, 1, [&]() -> int {
         const size_t K = c.offsets[c.m];
-        SVMC_HIP_TRY(grow(&s->cmc_ws, s->cmc_ws_bytes, cmc_payoff_workspace_bytes_of(s->n_path, c.m, K), false));
-        SVMC_HIP_TRY(grow(&s->cmc_pinned, s->cmc_pinned_bytes, cmc_payoff_pinned_bytes_of(c.m, K), true));
+        SVMC_HIP_TRY(grow(&s->cmc_ws, s->cmc_ws_bytes, cmc_workspace_bytes_of(s->n_path, c.m, K, false), false));
+        SVMC_HIP_TRY(grow(&s->cmc_pinned, s->cmc_pinned_bytes, cmc_pinned_bytes_of(c.m, K, false), true));
         return SVMC_OK;
     }, step))
         return rc;
@@ -1577,10 +1563,10 @@ static int chain_price_cmc_many(const char *fn, Session *s, const ChainView &c, 
     std::vector<const double *> mus, cvs;
     for (int j = 0; j < n_jobs; ++j) {
         cmc_many_rows(s, c, n_jobs, j, mus, cvs);
-        if (int rc = cmc_payoff_chain(fn, mus.data(), cvs.data(), s->n_path, c.forwards, c.discfactors, c.m, c.strikes, c.types, c.offsets,
-                                      recenter, prices + K * j, stderrs + K * j,
-                                      stats ? stats + static_cast<size_t>(SVMC_CMC_STATS_DOUBLES) * c.m * j : nullptr, s->cmc_ws,
-                                      s->cmc_ws_bytes, s->stream, s->cmc_pinned, s->cmc_pinned_bytes))
+        if (int rc = cmc_tail(fn, mus.data(), cvs.data(), s->n_path, c.forwards, c.discfactors, c.m, c.strikes, c.types, c.offsets, recenter,
+                              prices + K * j, stderrs + K * j, nullptr,
+                              stats ? stats + static_cast<size_t>(SVMC_CMC_STATS_DOUBLES) * c.m * j : nullptr, s->cmc_ws, s->cmc_ws_bytes,
+                              s->stream, s->cmc_pinned, s->cmc_pinned_bytes))
             return rc;
     }
     stepping_read(s);
@@ -1600,18 +1586,17 @@ static int chain_price_cmc_sens(const char *fn, Session *s, const ChainView &c, 
     const int P = n_params, J = 1 + 2 * P;
     const std::vector<uint64_t> seeds(J, seed);
     const std::vector<uint32_t> call_ids(J, call_id);
-    size_t image_bytes = 0;
-    if (int rc = cmc_many_step(fn, s, c, J, params, seeds.data(), call_ids.data(), nb_steps_per_year, greeks, greeks, [&]() -> int {
+    // (the sensitivity tail's table holds every quote once per bumped job: 2 P K strikes)
+    if (int rc = cmc_many_step(fn, s, c, J, params, seeds.data(), call_ids.data(), nb_steps_per_year, greeks, greeks, 2 * static_cast<size_t>(P),
+                               [&]() -> int {
         const size_t K = c.offsets[c.m];
         if (P > 0) {
-            if (int rc = cmc_sens_check(fn, s->n_path, c.forwards, c.discfactors, c.m, c.strikes, c.types, c.offsets, P, steps)) return rc;
-            image_bytes = cmc_sens_image_bytes_of(c.m, K, P);
+            if (int rc = check_steps(fn, P, steps, 1)) return rc;
             SVMC_HIP_TRY(grow(&s->csens_ws, s->csens_ws_bytes, cmc_sens_workspace_bytes_of(s->n_path, c.m, K, P), false));
-            SVMC_HIP_TRY(grow(&s->csens_pinned, s->csens_pinned_bytes,
-                              image_bytes + static_cast<size_t>(SVMC_CMC_SENS_ROWS) * P * (K > 0 ? K : 1) * sizeof(double), true));
+            SVMC_HIP_TRY(grow(&s->csens_pinned, s->csens_pinned_bytes, cmc_sens_pinned(nullptr, c.m, K, P, nullptr), true));
         }
-        SVMC_HIP_TRY(grow(&s->cmc_ws, s->cmc_ws_bytes, cmc_greeks_workspace_bytes_of(s->n_path, c.m, K), false));
-        SVMC_HIP_TRY(grow(&s->cmc_pinned, s->cmc_pinned_bytes, cmc_greeks_pinned_bytes_of(c.m, K), true));
+        SVMC_HIP_TRY(grow(&s->cmc_ws, s->cmc_ws_bytes, cmc_workspace_bytes_of(s->n_path, c.m, K, true), false));
+        SVMC_HIP_TRY(grow(&s->cmc_pinned, s->cmc_pinned_bytes, cmc_pinned_bytes_of(c.m, K, true), true));
         return SVMC_OK;
     },
                                [&](const std::vector<int> &nbs, const std::vector<double> &dts, double *mu, double *cv) {
@@ -1635,15 +1620,15 @@ static int chain_price_cmc_sens(const char *fn, Session *s, const ChainView &c, 
         if (int rc = cmc_sens_enqueue(fn, up_mu.data(), up_cv.data(), dn_mu.data(), dn_cv.data(), n, c.forwards, c.discfactors, c.m, c.strikes,
                                       c.types, c.offsets, P, steps, recenter, s->csens_pinned, s->csens_ws, s->csens_ws_bytes, s->stream, &res))
             return rc;
-        sens_out = reinterpret_cast<double *>(static_cast<unsigned char *>(s->csens_pinned) + image_bytes);
+        cmc_sens_pinned(s->csens_pinned, c.m, K, P, &sens_out);
         if (K > 0)
             SVMC_HIP_TRY(hipMemcpyAsync(sens_out, res, static_cast<size_t>(SVMC_CMC_SENS_ROWS) * P * K * sizeof(double), hipMemcpyDeviceToHost,
                                         s->stream));
     }
     std::vector<const double *> mus, cvs;
     cmc_many_rows(s, c, J, 0, mus, cvs);
-    if (int rc = cmc_greeks_chain(fn, mus.data(), cvs.data(), n, c.forwards, c.discfactors, c.m, c.strikes, c.types, c.offsets, recenter,
-                                  greeks, stats, s->cmc_ws, s->cmc_ws_bytes, s->stream, s->cmc_pinned, s->cmc_pinned_bytes))
+    if (int rc = cmc_tail(fn, mus.data(), cvs.data(), n, c.forwards, c.discfactors, c.m, c.strikes, c.types, c.offsets, recenter, nullptr,
+                          nullptr, greeks, stats, s->cmc_ws, s->cmc_ws_bytes, s->stream, s->cmc_pinned, s->cmc_pinned_bytes))
         return rc;                                         // (returns synchronised: the sensitivities have landed too)
     stepping_read(s);
     if (P > 0 && K > 0) memcpy(sens, sens_out, static_cast<size_t>(SVMC_CMC_SENS_ROWS) * P * K * sizeof(double));

@@ -25,6 +25,7 @@
 #include "svmc_block.h"
 #include "svmc_jobs.h"
 #include "svmc_models.h"
+#include "svmc_quotes.h"
 #include "svmc_rng.h"
 #include "svmc_slice.h"
 
@@ -695,34 +696,7 @@ int heston_cmc_step_many(const char *fn, size_t n_path, int n_jobs, int n_slices
 // ---------------------------------------------------------------------------------------------------
 // payoff reduction
 // ---------------------------------------------------------------------------------------------------
-constexpr int CMC_KT = 8;              // strikes per group: two accumulators and three constants per strike in vector registers
-constexpr unsigned CMC_ROWS = 1024;    // path blocks per launch at most: rows(n) is a function of n_path alone
-static inline unsigned cmc_rows(size_t n) { return static_cast<unsigned>(std::min<size_t>((n + BLOCK - 1) / BLOCK, CMC_ROWS)); }
-
-// the device table of a chain, uploaded once per call
-struct CmcExpiry {
-    const double *mu, *cv;
-    double forward, ln_forward, discfactor;
-    int k0, k1;                        // its strikes [k0, k1)
-};
-struct CmcGroup {
-    int expiry, k0, nk, pad;           // strikes [k0, k0 + nk) of `expiry`
-};
-struct CmcTable {
-    const CmcExpiry *expiries;
-    const CmcGroup *groups;
-    const double *strikes;             // [K]
-    const double *is_put;              // [K] 0 | 1
-    const double *intrinsic;           // [K] max(+-(F - K), 0): the shift where path 0 of the expiry is dropped
-    double *kp, *ln_kp, *shift;        // [K] device-computed: K + corr, its logarithm (0 where K + corr <= 0), the sums' shift
-    double *fwd;                       // [m][4]: sum (e - 1), sum (e - 1)^2, kept count, corr
-    double *stats;                     // [m][SVMC_CMC_STATS_DOUBLES]
-    double *fwd_partials;              // [rows][m][3]
-    double *pay_partials;              // [rows][K][2]
-    double *out;                       // [2][K]: prices, errors
-    int m, K;
-    unsigned rows;
-};
+static_assert(QUOTE_BLOCK == BLOCK, "svmc_quotes.h sizes the partial rows for blocks of BLOCK paths");
 
 // a path is kept iff mu, cv and e = exp(mu + cv / 2) are finite and cv >= 0 (include/svmc.h); h = mu + cv / 2
 __device__ __forceinline__ bool cmc_keep(double mu, double cv, double &h, double &e)
@@ -812,7 +786,7 @@ __global__ __launch_bounds__(BLOCK) void cmc_forward_finish_kernel(CmcTable t, s
 __global__ __launch_bounds__(BLOCK) void cmc_payoff_kernel(CmcTable t, size_t n)
 {
     __shared__ double lds[4 * block_sum_padded(2 * CMC_KT)];
-    const CmcGroup g = t.groups[blockIdx.y];
+    const QuoteGroup g = t.groups[blockIdx.y];
     const CmcExpiry ex = t.expiries[g.expiry];
     double kp[CMC_KT], ln_kp[CMC_KT], shift[CMC_KT], acc[2 * CMC_KT];
     bool put[CMC_KT];
@@ -872,19 +846,6 @@ __global__ __launch_bounds__(BLOCK) void cmc_finish_kernel(CmcTable t, size_t n)
 // derivatives of the conditional estimator in F and K (include/svmc.h states the formulas)
 // ---------------------------------------------------------------------------------------------------
 // The kernels' names carry neither of the words the f11 and f12 metadata tests count kernels by.
-constexpr int CMC_DKT = SVMC_CMC_GREEKS_KT;    // strikes per group: six accumulators, three shifts and three constants per strike
-constexpr int CMC_DQ = 6;                      // per strike: sum and sum of squares of delta, dual delta, dual gamma (minus their shifts)
-
-// what the derivative launches add to a chain's CmcTable
-struct CmcDerivTable {
-    const CmcGroup *groups;            // groups of up to CMC_DKT strikes; pad = 1: the expiry's first group, which counts its cv == 0
-                                       // paths (an expiry without strikes has one group of nk = 0 for that count)
-    double *shift;                     // [K][3]: delta, dual delta and dual gamma of the expiry's path 0 -- or of (mu, cv) = (0, 0)
-    double *partials;                  // [rows][K][CMC_DQ]
-    double *zero_partials;             // [rows][m]
-    double *out;                       // [8][K]: delta, dual delta, gamma, dual gamma, each followed by its error
-    double *zero;                      // [m]: kept paths with cv == 0
-};
 
 // Per kept path and strike: delta_i = e B_f + c B_k, dual_delta_i = B_k, dual_gamma_i = phi(d2) / (K' sd), with d1 and d2 formed as
 // cmc_black forms them.  Each side's B_f and B_k come from its own tail (put: B_f = -N(-d1), B_k = N(-d2)), as its price does.
@@ -934,7 +895,7 @@ __global__ __launch_bounds__(BLOCK) void cond_deriv_kernel(CmcTable t, CmcDerivT
 {
     constexpr int NV = CMC_DQ * KT + 1;                    // the last value: the count of cv == 0 paths
     __shared__ double lds[4 * block_sum_padded(NV)];
-    const CmcGroup g = dt.groups[blockIdx.y];
+    const QuoteGroup g = dt.groups[blockIdx.y];
     const CmcExpiry ex = t.expiries[g.expiry];
     const int nk = g.nk;                                   // (block-uniform; 0: the group only counts)
     const double *fw = t.fwd + 4 * g.expiry;
@@ -1036,117 +997,44 @@ __global__ __launch_bounds__(BLOCK) void cond_deriv_finish_kernel(CmcTable t, Cm
     }
 }
 
-static size_t align8(size_t b) { return (b + 7) & ~static_cast<size_t>(7); }
-static int cmc_groups(int n_expiries, const size_t *offsets)
-{
-    int g = 0;
-    for (int i = 0; i < n_expiries; ++i) g += static_cast<int>((offsets[i + 1] - offsets[i] + CMC_KT - 1) / CMC_KT);
-    return g;
-}
-static int cmc_deriv_groups(int n_expiries, const size_t *offsets)     // at least one per expiry: the count of cv == 0 paths
-{
-    int g = 0;
-    for (int i = 0; i < n_expiries; ++i) g += std::max(1, static_cast<int>((offsets[i + 1] - offsets[i] + CMC_DKT - 1) / CMC_DKT));
-    return g;
-}
-// deriv_groups = 0: the payoff tail alone
-static size_t cmc_workspace_bytes(size_t n_path, int m, size_t K, int groups, int deriv_groups = 0)
-{
-    const size_t rows = cmc_rows(n_path);
-    const size_t deriv = deriv_groups ? align8(sizeof(CmcGroup) * deriv_groups) + sizeof(double) * (8 * K + m + 3 * K + rows * CMC_DQ * K + rows * m) : 0;
-    return align8(sizeof(CmcExpiry) * m) + align8(sizeof(CmcGroup) * groups) + sizeof(double) * (6 * K + 4 * m + SVMC_CMC_STATS_DOUBLES * m +
-           rows * 3 * m + rows * 2 * K + 2 * K) + deriv;
-}
-
 // prices_host, stderrs_host [K], stats_host [m][SVMC_CMC_STATS_DOUBLES] (nullable); returns after the stream is synchronised.
-// pinned (nullable): page-locked host memory of cmc_payoff_pinned_bytes_of(m, K) for the table's image and the results
+// pinned (nullable): page-locked host memory of cmc_pinned_bytes_of(m, K, deriv) for the table's image and the results
 // greeks_host (nullable) [SVMC_CMC_GREEKS_ROWS][K]: the derivative launches run after the payoff tail's, prices_host and stderrs_host
 // are not read and stats_host is [m][SVMC_CMC_GREEKS_STATS_DOUBLES]
-static int cmc_tail(const char *fn, const double *const *mu_snapshots_host, const double *const *cv_snapshots_host, size_t n_path,
+int cmc_tail(const char *fn, const double *const *mu_snapshots_host, const double *const *cv_snapshots_host, size_t n_path,
                     const double *forwards_host, const double *discfactors_host, int n_expiries, const double *strikes_host,
                     const int8_t *types_host, const size_t *strike_offsets_host, int recenter, double *prices_host, double *stderrs_host,
                     double *greeks_host, double *stats_host, void *workspace, size_t workspace_bytes, hipStream_t stream, void *pinned,
                     size_t pinned_bytes)
 {
     const bool deriv = greeks_host != nullptr;
-    SVMC_REQUIRE(mu_snapshots_host && cv_snapshots_host && forwards_host && discfactors_host && strikes_host && types_host &&
-                     strike_offsets_host && (deriv || (prices_host && stderrs_host)) && workspace,
+    SVMC_REQUIRE(mu_snapshots_host && cv_snapshots_host && discfactors_host && (deriv || (prices_host && stderrs_host)) && workspace,
                  std::string(fn) + ": null pointer");
-    SVMC_REQUIRE(n_path > 0 && n_expiries >= 1, std::string(fn) + ": n_path and n_expiries must be positive");
+    if (int rc = check_quotes(fn, n_path, forwards_host, nullptr, n_expiries, strikes_host, types_host, strike_offsets_host, 1u << 30, 1))
+        return rc;                                         // (any discount factor is taken: a non-finite one gives non-finite prices)
     const int m = n_expiries;
     const size_t K = strike_offsets_host[m];
-    for (int i = 0; i < m; ++i) {
-        SVMC_REQUIRE(mu_snapshots_host[i] && cv_snapshots_host[i], std::string(fn) + ": null snapshot");
-        SVMC_REQUIRE(strike_offsets_host[i] <= strike_offsets_host[i + 1], std::string(fn) + ": strike offsets must not decrease");
-        SVMC_REQUIRE(std::isfinite(forwards_host[i]) && forwards_host[i] > 0.0, std::string(fn) + ": a forward is not positive and finite");
-    }
-    for (size_t k = 0; k < K; ++k) {
-        if (types_host[k] != SVMC_CALL && types_host[k] != SVMC_PUT) return fail(SVMC_ERR_UNKNOWN_PAYOFF, "unknown option payoff code");
-        SVMC_REQUIRE(std::isfinite(strikes_host[k]), std::string(fn) + ": a strike is not finite");
-    }
-    SVMC_REQUIRE(K < (1u << 30), std::string(fn) + ": too many strikes");
-    const int G = cmc_groups(m, strike_offsets_host), GD = deriv ? cmc_deriv_groups(m, strike_offsets_host) : 0;
-    if (workspace_bytes < cmc_workspace_bytes(n_path, m, K, G, GD))
+    for (int i = 0; i < m; ++i) SVMC_REQUIRE(mu_snapshots_host[i] && cv_snapshots_host[i], std::string(fn) + ": null snapshot");
+    const int G = quote_groups(m, strike_offsets_host, CMC_KT, false), GD = deriv ? quote_groups(m, strike_offsets_host, CMC_DKT, true) : 0;
+    CmcTable t;
+    CmcDerivTable dt;
+    Layout w{static_cast<unsigned char *>(workspace)};
+    const size_t up_bytes = cmc_workspace(w, n_path, m, K, G, GD, t, dt);
+    if (workspace_bytes < w.bytes())
         return fail(SVMC_ERR_WORKSPACE, std::string(fn) + ": workspace too small (svmc_cmc_payoff_workspace_bytes / svmc_cmc_greeks_workspace_bytes)");
 
-    // the table's host image: expiries, groups (the derivative launches' after the payoff's), then strikes / is_put / intrinsic
-    const size_t o_groups = align8(sizeof(CmcExpiry) * m), o_dgroups = o_groups + align8(sizeof(CmcGroup) * G),
-                 o_k = o_dgroups + align8(sizeof(CmcGroup) * GD), up_bytes = o_k + 3 * K * sizeof(double);
-    // ... built in the caller's page-locked staging block where it gave one that holds the image and the results (the fused
-    // drivers: an upload from and downloads into pageable memory go through the runtime's staging path, 16 us apiece)
-    const size_t n_deriv = deriv ? 8 * K : 0, n_zero = deriv ? static_cast<size_t>(m) : 0;
-    const size_t n_res = 2 * K + n_deriv + static_cast<size_t>(SVMC_CMC_STATS_DOUBLES) * m + n_zero;
-    const bool staged = pinned != nullptr && pinned_bytes >= up_bytes + n_res * sizeof(double);
-    std::vector<unsigned char> pageable(staged ? 0 : up_bytes + n_res * sizeof(double));
-    unsigned char *img = staged ? static_cast<unsigned char *>(pinned) : pageable.data();
-    double *res = reinterpret_cast<double *>(img + up_bytes);
-    CmcExpiry *ex = reinterpret_cast<CmcExpiry *>(img);
-    CmcGroup *gr = reinterpret_cast<CmcGroup *>(img + o_groups), *dgr = reinterpret_cast<CmcGroup *>(img + o_dgroups);
-    double *kd = reinterpret_cast<double *>(img + o_k);
-    int g = 0, gd = 0;
-    for (int i = 0; i < m; ++i) {
-        const int k0 = static_cast<int>(strike_offsets_host[i]), k1 = static_cast<int>(strike_offsets_host[i + 1]);
-        ex[i] = CmcExpiry{mu_snapshots_host[i], cv_snapshots_host[i], forwards_host[i], std::log(forwards_host[i]), discfactors_host[i], k0, k1};
-        for (int k = k0; k < k1; k += CMC_KT) gr[g++] = CmcGroup{i, k, (k1 - k < CMC_KT) ? k1 - k : CMC_KT, 0};
-        if (deriv) {
-            if (k0 == k1) dgr[gd++] = CmcGroup{i, 0, 0, 1};
-            for (int k = k0; k < k1; k += CMC_DKT) dgr[gd++] = CmcGroup{i, k, (k1 - k < CMC_DKT) ? k1 - k : CMC_DKT, (k == k0) ? 1 : 0};
-        }
-        for (int k = k0; k < k1; ++k) {
-            const bool put = types_host[k] == SVMC_PUT;
-            kd[k] = strikes_host[k];
-            kd[K + k] = put ? 1.0 : 0.0;
-            kd[2 * K + k] = put ? std::fmax(strikes_host[k] - forwards_host[i], 0.0) : std::fmax(forwards_host[i] - strikes_host[k], 0.0);
-        }
-    }
-    unsigned char *w = static_cast<unsigned char *>(workspace);
-    SVMC_HIP_TRY(hipMemcpyAsync(w, img, up_bytes, hipMemcpyHostToDevice, stream));
-    double *d = reinterpret_cast<double *>(w + o_k);
-    CmcTable t;
-    t.expiries = reinterpret_cast<const CmcExpiry *>(w);
-    t.groups = reinterpret_cast<const CmcGroup *>(w + o_groups);
-    t.strikes = d;
-    t.is_put = d + K;
-    t.intrinsic = d + 2 * K;
-    t.kp = d + 3 * K;
-    t.ln_kp = d + 4 * K;
-    t.shift = d + 5 * K;
-    t.fwd = d + 6 * K;
-    // the results, one block: prices [K], errors [K], (the derivatives [8][K],) statistics [m][5] (, the cv == 0 counts [m])
-    t.out = t.fwd + 4 * m;
-    t.stats = t.out + 2 * K + n_deriv;
-    t.m = m;
-    t.K = static_cast<int>(K);
-    t.rows = cmc_rows(n_path);
-    t.fwd_partials = t.stats + SVMC_CMC_STATS_DOUBLES * m + n_zero;
-    t.pay_partials = t.fwd_partials + static_cast<size_t>(t.rows) * 3 * m;
-    CmcDerivTable dt;
-    dt.groups = reinterpret_cast<const CmcGroup *>(w + o_dgroups);
-    dt.out = t.out + 2 * K;
-    dt.zero = t.stats + SVMC_CMC_STATS_DOUBLES * m;
-    dt.shift = t.pay_partials + static_cast<size_t>(t.rows) * 2 * K;
-    dt.partials = dt.shift + 3 * K;
-    dt.zero_partials = dt.partials + static_cast<size_t>(t.rows) * CMC_DQ * K;
+    // the table's host image and the results' landing: in the caller's page-locked staging block where it gave one that holds both
+    // (the fused drivers: an upload from and downloads into pageable memory go through the runtime's staging path, 16 us apiece)
+    CmcImage im;
+    Layout need{nullptr};
+    cmc_pinned(need, m, K, G, GD, im);
+    const bool staged = pinned != nullptr && pinned_bytes >= need.bytes();
+    std::vector<unsigned char> pageable(staged ? 0 : need.bytes());
+    Layout h{staged ? static_cast<unsigned char *>(pinned) : pageable.data()};
+    const CmcResults res = cmc_pinned(h, m, K, G, GD, im);
+    cmc_fill_image(im, mu_snapshots_host, cv_snapshots_host, forwards_host, discfactors_host, m, strikes_host, types_host, strike_offsets_host,
+                   deriv);
+    SVMC_HIP_TRY(hipMemcpyAsync(workspace, h.base, up_bytes, hipMemcpyHostToDevice, stream));
 
     hipLaunchKernelGGL(cmc_forward_kernel, dim3(t.rows, m), dim3(BLOCK), 0, stream, t, n_path);
     if (int rc = check_launch(fn)) return rc;
@@ -1166,71 +1054,23 @@ static int cmc_tail(const char *fn, const double *const *mu_snapshots_host, cons
         hipLaunchKernelGGL(cond_deriv_finish_kernel, dim3(static_cast<unsigned>(K) + m), dim3(BLOCK), 0, stream, t, dt, n_path);
         if (int rc = check_launch(fn)) return rc;
     }
-    SVMC_HIP_TRY(hipMemcpyAsync(res, t.out, n_res * sizeof(double), hipMemcpyDeviceToHost, stream));
+    SVMC_HIP_TRY(hipMemcpyAsync(res.out, t.out, need.bytes() - up_bytes, hipMemcpyDeviceToHost, stream));     // (the results are one block)
     SVMC_HIP_TRY(hipStreamSynchronize(stream));            // the table's host image and the results' landing
     if (!deriv) {
-        memcpy(prices_host, res, K * sizeof(double));
-        memcpy(stderrs_host, res + K, K * sizeof(double));
-        if (stats_host != nullptr) memcpy(stats_host, res + 2 * K, static_cast<size_t>(SVMC_CMC_STATS_DOUBLES) * m * sizeof(double));
+        memcpy(prices_host, res.out, K * sizeof(double));
+        memcpy(stderrs_host, res.out + K, K * sizeof(double));
+        if (stats_host != nullptr) memcpy(stats_host, res.stats, static_cast<size_t>(SVMC_CMC_STATS_DOUBLES) * m * sizeof(double));
         return SVMC_OK;
     }
-    memcpy(greeks_host, res, static_cast<size_t>(SVMC_CMC_GREEKS_ROWS) * K * sizeof(double));
+    memcpy(greeks_host, res.out, static_cast<size_t>(SVMC_CMC_GREEKS_ROWS) * K * sizeof(double));     // prices, errors, then deriv_out
     if (stats_host != nullptr) {
-        const double *st = res + static_cast<size_t>(SVMC_CMC_GREEKS_ROWS) * K, *zero = st + static_cast<size_t>(SVMC_CMC_STATS_DOUBLES) * m;
         for (int i = 0; i < m; ++i) {
-            memcpy(stats_host + static_cast<size_t>(SVMC_CMC_GREEKS_STATS_DOUBLES) * i, st + SVMC_CMC_STATS_DOUBLES * i,
+            memcpy(stats_host + static_cast<size_t>(SVMC_CMC_GREEKS_STATS_DOUBLES) * i, res.stats + SVMC_CMC_STATS_DOUBLES * i,
                    SVMC_CMC_STATS_DOUBLES * sizeof(double));
-            stats_host[static_cast<size_t>(SVMC_CMC_GREEKS_STATS_DOUBLES) * i + SVMC_CMC_STATS_DOUBLES] = zero[i];
+            stats_host[static_cast<size_t>(SVMC_CMC_GREEKS_STATS_DOUBLES) * i + SVMC_CMC_STATS_DOUBLES] = res.zero[i];
         }
     }
     return SVMC_OK;
-}
-
-int cmc_payoff_chain(const char *fn, const double *const *mu_snapshots_host, const double *const *cv_snapshots_host, size_t n_path,
-                     const double *forwards_host, const double *discfactors_host, int n_expiries, const double *strikes_host,
-                     const int8_t *types_host, const size_t *strike_offsets_host, int recenter, double *prices_host, double *stderrs_host,
-                     double *stats_host, void *workspace, size_t workspace_bytes, hipStream_t stream, void *pinned, size_t pinned_bytes)
-{
-    return cmc_tail(fn, mu_snapshots_host, cv_snapshots_host, n_path, forwards_host, discfactors_host, n_expiries, strikes_host, types_host,
-                    strike_offsets_host, recenter, prices_host, stderrs_host, nullptr, stats_host, workspace, workspace_bytes, stream, pinned,
-                    pinned_bytes);
-}
-
-int cmc_greeks_chain(const char *fn, const double *const *mu_snapshots_host, const double *const *cv_snapshots_host, size_t n_path,
-                     const double *forwards_host, const double *discfactors_host, int n_expiries, const double *strikes_host,
-                     const int8_t *types_host, const size_t *strike_offsets_host, int recenter, double *greeks_host, double *stats_host,
-                     void *workspace, size_t workspace_bytes, hipStream_t stream, void *pinned, size_t pinned_bytes)
-{
-    SVMC_REQUIRE(greeks_host != nullptr, std::string(fn) + ": null pointer");
-    return cmc_tail(fn, mu_snapshots_host, cv_snapshots_host, n_path, forwards_host, discfactors_host, n_expiries, strikes_host, types_host,
-                    strike_offsets_host, recenter, nullptr, nullptr, greeks_host, stats_host, workspace, workspace_bytes, stream, pinned,
-                    pinned_bytes);
-}
-
-size_t cmc_greeks_pinned_bytes_of(int n_expiries, size_t total_strikes)
-{
-    const int groups = static_cast<int>(total_strikes / CMC_KT) + n_expiries, dgroups = static_cast<int>(total_strikes / CMC_DKT) + n_expiries;
-    return align8(sizeof(CmcExpiry) * n_expiries) + align8(sizeof(CmcGroup) * groups) + align8(sizeof(CmcGroup) * dgroups) +
-           sizeof(double) * ((3 + SVMC_CMC_GREEKS_ROWS) * total_strikes + static_cast<size_t>(SVMC_CMC_GREEKS_STATS_DOUBLES) * n_expiries);
-}
-
-size_t cmc_greeks_workspace_bytes_of(size_t n_path, int n_expiries, size_t total_strikes)
-{
-    return cmc_workspace_bytes(n_path, n_expiries, total_strikes, static_cast<int>(total_strikes / CMC_KT) + n_expiries,
-                               static_cast<int>(total_strikes / CMC_DKT) + n_expiries);
-}
-
-size_t cmc_payoff_pinned_bytes_of(int n_expiries, size_t total_strikes)
-{
-    const int groups = static_cast<int>(total_strikes / CMC_KT) + n_expiries;
-    return align8(sizeof(CmcExpiry) * n_expiries) + align8(sizeof(CmcGroup) * groups) +
-           sizeof(double) * (5 * total_strikes + static_cast<size_t>(SVMC_CMC_STATS_DOUBLES) * n_expiries);
-}
-
-size_t cmc_payoff_workspace_bytes_of(size_t n_path, int n_expiries, size_t total_strikes)
-{
-    // every expiry may end in a ragged group
-    return cmc_workspace_bytes(n_path, n_expiries, total_strikes, static_cast<int>(total_strikes / CMC_KT) + n_expiries);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1241,25 +1081,12 @@ size_t cmc_payoff_workspace_bytes_of(size_t n_path, int n_expiries, size_t total
 // 2P K strikes, job-major: cmc_forward_kernel and cmc_forward_finish_kernel then form every job's forward statistics, K' and ln K'
 // as they form a single job's -- the same statements, hence the same bits.  The kernels below put the job and pair axes on
 // blockIdx.z (blockIdx.y in the finish), so the launch count does not grow with P.
-constexpr int SENS_KT = SVMC_CMC_GREEKS_KT;    // strikes per group
-constexpr int SENS_PQ = 4;                     // per (pair, quote): sum (d - d0), sum (dt - dt0), its squares, the kept pairs
-
-struct CmcSensTable {
-    const CmcGroup *groups;            // groups of up to SENS_KT strikes of one expiry of the CHAIN: k0 in [0, K)
-    const double *steps;               // [P]
-    double *q_partials;                // [rows][2P K]
-    double *q;                         // [2P K]: mean_kept_j(B_k), the job's dual delta before discounting
-    double *pair_shift;                // [P K][2]: d and dt of the expiry's path 0, or 0 where it is not a kept pair
-    double *pair_partials;             // [rows][P K][SENS_PQ]
-    double *out;                       // [P][SVMC_CMC_SENS_ROWS][K]
-    int P, m, K;                       // the chain's expiries and quotes
-};
 
 // the job pass: per kept path of job blockIdx.z the dual delta B_k of cmc_derivs against the job's own K'
 __global__ __launch_bounds__(BLOCK) void cond_sens_jobs_kernel(CmcTable t, CmcSensTable st, size_t n)
 {
     __shared__ double lds[4 * block_sum_padded(SENS_KT)];
-    const CmcGroup g = st.groups[blockIdx.y];
+    const QuoteGroup g = st.groups[blockIdx.y];
     const int job = blockIdx.z, nk = g.nk;
     const CmcExpiry ex = t.expiries[job * st.m + g.expiry];
     const size_t kbase = static_cast<size_t>(job) * st.K + g.k0;
@@ -1327,7 +1154,7 @@ __global__ __launch_bounds__(BLOCK) void cond_sens_pairs_kernel(CmcTable t, CmcS
 {
     constexpr int NV = 3 * SENS_KT + 1;                    // the last value: the kept pairs
     __shared__ double lds[4 * block_sum_padded(NV)];
-    const CmcGroup g = st.groups[blockIdx.y];
+    const QuoteGroup g = st.groups[blockIdx.y];
     const int p = blockIdx.z, nk = g.nk;
     const CmcExpiry xu = t.expiries[(2 * p) * st.m + g.expiry], xd = t.expiries[(2 * p + 1) * st.m + g.expiry];
     const size_t ku = static_cast<size_t>(2 * p) * st.K + g.k0, kd = ku + st.K;
@@ -1419,60 +1246,9 @@ __global__ __launch_bounds__(BLOCK) void cond_sens_finish_kernel(CmcTable t, Cmc
     }
 }
 
-int cmc_sens_check(const char *fn, size_t n_path, const double *forwards_host, const double *discfactors_host, int n_expiries,
-                   const double *strikes_host, const int8_t *types_host, const size_t *strike_offsets_host, int n_params,
-                   const double *steps_host)
-{
-    SVMC_REQUIRE(forwards_host && discfactors_host && strikes_host && types_host && strike_offsets_host && steps_host,
-                 std::string(fn) + ": null pointer");
-    SVMC_REQUIRE(n_path > 0 && n_expiries >= 1, std::string(fn) + ": n_path and n_expiries must be positive");
-    SVMC_REQUIRE(n_params >= 1 && n_params <= SVMC_GREEKS_MAX_PARAMS, std::string(fn) + ": n_params must be in [1, SVMC_GREEKS_MAX_PARAMS]");
-    for (int p = 0; p < n_params; ++p)
-        SVMC_REQUIRE(std::isfinite(steps_host[p]) && steps_host[p] > 0.0, std::string(fn) + ": a step is not positive and finite");
-    for (int i = 0; i < n_expiries; ++i) {
-        SVMC_REQUIRE(strike_offsets_host[i] <= strike_offsets_host[i + 1], std::string(fn) + ": strike offsets must not decrease");
-        SVMC_REQUIRE(std::isfinite(forwards_host[i]) && forwards_host[i] > 0.0, std::string(fn) + ": a forward is not positive and finite");
-        SVMC_REQUIRE(std::isfinite(discfactors_host[i]), std::string(fn) + ": a discount factor is not finite");
-    }
-    const size_t K = strike_offsets_host[n_expiries];
-    for (size_t k = 0; k < K; ++k) {
-        if (types_host[k] != SVMC_CALL && types_host[k] != SVMC_PUT) return fail(SVMC_ERR_UNKNOWN_PAYOFF, "unknown option payoff code");
-        SVMC_REQUIRE(std::isfinite(strikes_host[k]), std::string(fn) + ": a strike is not finite");
-    }
-    SVMC_REQUIRE(2 * static_cast<size_t>(n_params) * K < (1u << 30), std::string(fn) + ": too many strikes");
-    return SVMC_OK;
-}
-
-// the byte offsets of the table's host image: expiries [2P m], groups, then strikes / is_put / intrinsic [2P K] and the steps [P]
-struct CmcSensImage {
-    size_t o_groups, o_k, bytes;
-    int max_groups;
-};
-static CmcSensImage cmc_sens_image(int m, size_t K, int P)
-{
-    CmcSensImage im;
-    im.max_groups = static_cast<int>(K / SENS_KT) + m;     // every expiry may end in a ragged group
-    im.o_groups = align8(sizeof(CmcExpiry) * 2 * P * m);
-    im.o_k = im.o_groups + align8(sizeof(CmcGroup) * im.max_groups);
-    im.bytes = im.o_k + sizeof(double) * (6 * P * K + P);
-    return im;
-}
-size_t cmc_sens_image_bytes_of(int n_expiries, size_t total_strikes, int n_params)
-{
-    return cmc_sens_image(n_expiries, total_strikes, n_params).bytes;
-}
-size_t cmc_sens_workspace_bytes_of(size_t n_path, int n_expiries, size_t total_strikes, int n_params)
-{
-    const size_t rows = cmc_rows(n_path), P = static_cast<size_t>(n_params), K = total_strikes, m = static_cast<size_t>(n_expiries);
-    // kp, ln_kp, shift [2P K]; fwd [2P m][4]; stats; the forward partials; q partials and q; the pair shifts and partials; the results
-    return cmc_sens_image(n_expiries, total_strikes, n_params).bytes +
-           sizeof(double) * (6 * P * K + 8 * P * m + 2 * P * m * SVMC_CMC_STATS_DOUBLES + rows * 6 * P * m + rows * 2 * P * K + 2 * P * K +
-                             2 * P * K + rows * SENS_PQ * P * K + SVMC_CMC_SENS_ROWS * P * K);
-}
-
-// The sensitivity tail queued on `stream` (no synchronisation): the table's image is built in `image` (cmc_sens_image_bytes_of; the
-// caller keeps it until the stream has passed the upload), *results_dev gets the device address of the [P][3][K] results.  The
-// arguments are cmc_sens_check'ed by the caller.
+// The sensitivity tail queued on `stream` (no synchronisation): the table's image is built in `image` (the head of cmc_sens_pinned's
+// block; the caller keeps it until the stream has passed the upload), *results_dev gets the device address of the [P][3][K] results.
+// The arguments are check_quotes'ed and check_steps'ed by the caller.
 int cmc_sens_enqueue(const char *fn, const double *const *up_mu, const double *const *up_cv, const double *const *dn_mu,
                      const double *const *dn_cv, size_t n_path, const double *forwards_host, const double *discfactors_host, int n_expiries,
                      const double *strikes_host, const int8_t *types_host, const size_t *strike_offsets_host, int n_params,
@@ -1484,69 +1260,21 @@ int cmc_sens_enqueue(const char *fn, const double *const *up_mu, const double *c
     const size_t K = strike_offsets_host[m];
     for (int r = 0; r < P * m; ++r)
         SVMC_REQUIRE(up_mu[r] && up_cv[r] && dn_mu[r] && dn_cv[r], std::string(fn) + ": null snapshot");
-    if (workspace_bytes < cmc_sens_workspace_bytes_of(n_path, m, K, P))
-        return fail(SVMC_ERR_WORKSPACE, std::string(fn) + ": workspace too small (svmc_cmc_sens_workspace_bytes)");
-    const CmcSensImage im = cmc_sens_image(m, K, P);
-    unsigned char *img = static_cast<unsigned char *>(image);
-    CmcExpiry *ex = reinterpret_cast<CmcExpiry *>(img);
-    CmcGroup *gr = reinterpret_cast<CmcGroup *>(img + im.o_groups);
-    double *kd = reinterpret_cast<double *>(img + im.o_k);
-    const size_t JK = static_cast<size_t>(J) * K;
-    int G = 0;
-    for (int i = 0; i < m; ++i) {
-        const int k0 = static_cast<int>(strike_offsets_host[i]), k1 = static_cast<int>(strike_offsets_host[i + 1]);
-        for (int k = k0; k < k1; k += SENS_KT) gr[G++] = CmcGroup{i, k, (k1 - k < SENS_KT) ? k1 - k : SENS_KT, 0};
-        for (int j = 0; j < J; ++j) {
-            const int p = j / 2, r = p * m + i, o = j * static_cast<int>(K);
-            const bool up = (j & 1) == 0;
-            ex[j * m + i] = CmcExpiry{up ? up_mu[r] : dn_mu[r], up ? up_cv[r] : dn_cv[r], forwards_host[i], std::log(forwards_host[i]),
-                                      discfactors_host[i], o + k0, o + k1};
-            for (int k = k0; k < k1; ++k) {
-                const bool put = types_host[k] == SVMC_PUT;
-                kd[o + k] = strikes_host[k];
-                kd[JK + o + k] = put ? 1.0 : 0.0;
-                kd[2 * JK + o + k] = put ? std::fmax(strikes_host[k] - forwards_host[i], 0.0) : std::fmax(forwards_host[i] - strikes_host[k], 0.0);
-            }
-        }
-    }
-    for (int p = 0; p < P; ++p) kd[3 * JK + p] = steps_host[p];
-    unsigned char *w = static_cast<unsigned char *>(workspace);
-    SVMC_HIP_TRY(hipMemcpyAsync(w, img, im.bytes, hipMemcpyHostToDevice, stream));
-    double *d = reinterpret_cast<double *>(w + im.o_k);
-    const size_t Jm = static_cast<size_t>(J) * m;
+    const int G = quote_groups(m, strike_offsets_host, SENS_KT, false);
     CmcTable t;
-    t.expiries = reinterpret_cast<const CmcExpiry *>(w);
-    t.groups = nullptr;
-    t.strikes = d;
-    t.is_put = d + JK;
-    t.intrinsic = d + 2 * JK;
-    t.kp = d + 3 * JK + P;
-    t.ln_kp = t.kp + JK;
-    t.shift = t.ln_kp + JK;
-    t.fwd = t.shift + JK;
-    t.stats = t.fwd + 4 * Jm;
-    t.fwd_partials = t.stats + SVMC_CMC_STATS_DOUBLES * Jm;
-    t.pay_partials = nullptr;
-    t.out = nullptr;
-    t.m = static_cast<int>(Jm);
-    t.K = static_cast<int>(JK);
-    t.rows = cmc_rows(n_path);
     CmcSensTable st;
-    st.groups = reinterpret_cast<const CmcGroup *>(w + im.o_groups);
-    st.steps = d + 3 * JK;
-    st.q_partials = t.fwd_partials + static_cast<size_t>(t.rows) * 3 * Jm;
-    st.q = st.q_partials + static_cast<size_t>(t.rows) * JK;
-    st.pair_shift = st.q + JK;
-    st.pair_partials = st.pair_shift + JK;
-    st.out = st.pair_partials + static_cast<size_t>(t.rows) * SENS_PQ * P * K;
-    st.P = P;
-    st.m = m;
-    st.K = static_cast<int>(K);
+    Layout w{static_cast<unsigned char *>(workspace)}, h{static_cast<unsigned char *>(image)};
+    const size_t image_bytes = cmc_sens_workspace(w, n_path, m, K, G, P, t, st);
+    if (workspace_bytes < w.bytes())
+        return fail(SVMC_ERR_WORKSPACE, std::string(fn) + ": workspace too small (svmc_cmc_sens_workspace_bytes)");
+    cmc_sens_fill_image(cmc_sens_image(h, m, K, G, P), up_mu, up_cv, dn_mu, dn_cv, forwards_host, discfactors_host, m, strikes_host,
+                        types_host, strike_offsets_host, P, steps_host);
+    SVMC_HIP_TRY(hipMemcpyAsync(workspace, image, image_bytes, hipMemcpyHostToDevice, stream));
     *results_dev = st.out;
 
-    hipLaunchKernelGGL(cmc_forward_kernel, dim3(t.rows, static_cast<unsigned>(Jm)), dim3(BLOCK), 0, stream, t, n_path);
+    hipLaunchKernelGGL(cmc_forward_kernel, dim3(t.rows, static_cast<unsigned>(t.m)), dim3(BLOCK), 0, stream, t, n_path);
     if (int rc = check_launch(fn)) return rc;
-    hipLaunchKernelGGL(cmc_forward_finish_kernel, dim3(static_cast<unsigned>(Jm)), dim3(BLOCK), 0, stream, t, n_path, recenter ? 1 : 0);
+    hipLaunchKernelGGL(cmc_forward_finish_kernel, dim3(static_cast<unsigned>(t.m)), dim3(BLOCK), 0, stream, t, n_path, recenter ? 1 : 0);
     if (int rc = check_launch(fn)) return rc;
     if (K == 0) return SVMC_OK;
     const unsigned uG = static_cast<unsigned>(G), uK = static_cast<unsigned>(K);
@@ -1591,7 +1319,7 @@ int svmc_heston_chain_cmc(double *mu, double *cv, double *var, double *qvar, siz
 int svmc_cmc_payoff_workspace_bytes(size_t n_path, int n_expiries, size_t total_strikes, size_t *bytes)
 {
     SVMC_REQUIRE(bytes != nullptr && n_expiries >= 1, "svmc_cmc_payoff_workspace_bytes: null output or no expiries");
-    *bytes = cmc_payoff_workspace_bytes_of(n_path, n_expiries, total_strikes);
+    *bytes = cmc_workspace_bytes_of(n_path, n_expiries, total_strikes, false);
     return SVMC_OK;
 }
 
@@ -1600,15 +1328,15 @@ int svmc_cmc_payoff_chain(const double *const *mu_snapshots_host, const double *
                           const int8_t *types_host, const size_t *strike_offsets_host, int recenter, double *prices_host,
                           double *stderrs_host, double *stats_host, void *workspace, size_t workspace_bytes, svmc_stream_t stream)
 {
-    return cmc_payoff_chain("svmc_cmc_payoff_chain", mu_snapshots_host, cv_snapshots_host, n_path, forwards_host, discfactors_host,
-                            n_expiries, strikes_host, types_host, strike_offsets_host, recenter, prices_host, stderrs_host, stats_host,
-                            workspace, workspace_bytes, as_stream(stream), nullptr, 0);
+    return cmc_tail("svmc_cmc_payoff_chain", mu_snapshots_host, cv_snapshots_host, n_path, forwards_host, discfactors_host, n_expiries,
+                    strikes_host, types_host, strike_offsets_host, recenter, prices_host, stderrs_host, nullptr, stats_host, workspace,
+                    workspace_bytes, as_stream(stream), nullptr, 0);
 }
 
 int svmc_cmc_greeks_workspace_bytes(size_t n_path, int n_expiries, size_t total_strikes, size_t *bytes)
 {
     SVMC_REQUIRE(bytes != nullptr && n_expiries >= 1, "svmc_cmc_greeks_workspace_bytes: null output or no expiries");
-    *bytes = cmc_greeks_workspace_bytes_of(n_path, n_expiries, total_strikes);
+    *bytes = cmc_workspace_bytes_of(n_path, n_expiries, total_strikes, true);
     return SVMC_OK;
 }
 
@@ -1617,9 +1345,10 @@ int svmc_cmc_greeks_chain(const double *const *mu_snapshots_host, const double *
                           const int8_t *types_host, const size_t *strike_offsets_host, int recenter, double *greeks_host,
                           double *stats_host, void *workspace, size_t workspace_bytes, svmc_stream_t stream)
 {
-    return cmc_greeks_chain("svmc_cmc_greeks_chain", mu_snapshots_host, cv_snapshots_host, n_path, forwards_host, discfactors_host,
-                            n_expiries, strikes_host, types_host, strike_offsets_host, recenter, greeks_host, stats_host, workspace,
-                            workspace_bytes, as_stream(stream), nullptr, 0);
+    SVMC_REQUIRE(greeks_host != nullptr, "svmc_cmc_greeks_chain: null pointer");
+    return cmc_tail("svmc_cmc_greeks_chain", mu_snapshots_host, cv_snapshots_host, n_path, forwards_host, discfactors_host, n_expiries,
+                    strikes_host, types_host, strike_offsets_host, recenter, nullptr, nullptr, greeks_host, stats_host, workspace,
+                    workspace_bytes, as_stream(stream), nullptr, 0);
 }
 
 int svmc_cmc_many_workspace_bytes(int n_jobs, int n_slices, size_t *bytes)
@@ -1681,12 +1410,13 @@ int svmc_cmc_sens_chain(const double *const *up_mu_host, const double *const *up
                         svmc_stream_t stream)
 {
     const char *fn = "svmc_cmc_sens_chain";
-    SVMC_REQUIRE(sens_host != nullptr, std::string(fn) + ": null pointer");
-    if (int rc = cmc_sens_check(fn, n_path, forwards_host, discfactors_host, n_expiries, strikes_host, types_host, strike_offsets_host,
-                                n_params, steps_host))
+    SVMC_REQUIRE(sens_host && discfactors_host && steps_host, std::string(fn) + ": null pointer");
+    if (int rc = check_steps(fn, n_params, steps_host, 1)) return rc;
+    if (int rc = check_quotes(fn, n_path, forwards_host, discfactors_host, n_expiries, strikes_host, types_host, strike_offsets_host, 1u << 30,
+                              2 * static_cast<size_t>(n_params)))
         return rc;
     const size_t K = strike_offsets_host[n_expiries];
-    std::vector<unsigned char> image(cmc_sens_image_bytes_of(n_expiries, K, n_params));
+    std::vector<unsigned char> image(cmc_sens_pinned(nullptr, n_expiries, K, n_params, nullptr));
     double *res = nullptr;
     if (int rc = cmc_sens_enqueue(fn, up_mu_host, up_cv_host, dn_mu_host, dn_cv_host, n_path, forwards_host, discfactors_host, n_expiries,
                                   strikes_host, types_host, strike_offsets_host, n_params, steps_host, recenter, image.data(), workspace,

@@ -25,39 +25,12 @@
 
 #include "svmc_block.h"
 #include "svmc_math.h"
+#include "svmc_quotes.h"
 
 namespace svmc {
 
-constexpr int GREEKS_KT = SVMC_GREEKS_KT;      // strikes per group: three accumulators and four constants per strike
-constexpr unsigned GREEKS_ROWS = 1024;         // path blocks per launch at most: rows(n) is a function of n_path alone
+static_assert(QUOTE_BLOCK == BLOCK, "svmc_quotes.h sizes the partial rows for blocks of BLOCK paths");
 constexpr int GREEKS_PREFETCH = 2;             // trips between a path's load and its use
-constexpr int GREEKS_COLS = 4;                 // partial columns per quote: job pass [g - shift, its square, itm, -], pair pass [d, dt, dt^2, count]
-static inline unsigned greeks_rows(size_t n) { return static_cast<unsigned>(std::min<size_t>((n + BLOCK - 1) / BLOCK, GREEKS_ROWS)); }
-
-// the device table of a call, uploaded once
-struct GreeksExpiry {
-    double forward, discfactor;
-    int k0, k1;                        // its strikes [k0, k1)
-};
-struct GreeksGroup {
-    int expiry, k0, nk, pad;           // strikes [k0, k0 + nk) of `expiry`
-};
-struct GreeksTable {
-    const GreeksExpiry *expiries;      // [m]
-    const GreeksGroup *groups;         // [G]
-    const double *const *rows;         // [1 + 2P][m]: the jobs' snapshot rows -- base, then up, dn per parameter
-    const double *spot_sums;           // [1 + 2P][m][2]: the jobs' [sum F exp(x), count]
-    const double *sg;                  // [K] +1 call, -1 put
-    const double *c;                   // [K] -sg K
-    const double *gshift;              // [K] sg 1{sg (F - K) > 0}: g at the forward, the shift of the delta's sums
-    const double *steps;               // [P] h_p
-    double *itm_fraction;              // [1 + 2P][K] q = n_itm / n_path of every job, written by the job pass's finish
-    double *partials;                  // [rows][slots][K][GREEKS_COLS], slots = 1 + 2P (job pass) | P (pair pass)
-    double *base_out;                  // [SVMC_GREEKS_BASE_ROWS][K]
-    double *sens_out;                  // [P][SVMC_GREEKS_SENS_ROWS][K]
-    int m, K, P;
-    unsigned n_rows;
-};
 
 // the kept-path mean of exp(x) of a job's expiry, from its reduced spot sums [sum F exp(x), count]
 __device__ __forceinline__ double greeks_mean_exp(const double *__restrict__ spot_sums, double forward)
@@ -73,7 +46,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(greeks_mi
 {
     constexpr int NSUM = block_sum_padded(3 * KT + 1);
     __shared__ double lds[4 * NSUM];
-    const GreeksGroup g = t.groups[blockIdx.y];
+    const QuoteGroup g = t.groups[blockIdx.y];
     const GreeksExpiry ex = t.expiries[g.expiry];
     const int z = blockIdx.z, m = t.m;                      // job pass: the job; pair pass: the parameter (block-uniform)
     const double forward = ex.forward;
@@ -215,76 +188,11 @@ __global__ __launch_bounds__(BLOCK) void greeks_finish_kernel(GreeksTable t, siz
     }
 }
 
-static size_t greeks_align8(size_t b) { return (b + 7) & ~static_cast<size_t>(7); }
-static int greeks_groups(int n_expiries, const size_t *offsets)
-{
-    int g = 0;
-    for (int i = 0; i < n_expiries; ++i) g += static_cast<int>((offsets[i + 1] - offsets[i] + GREEKS_KT - 1) / GREEKS_KT);
-    return g;
-}
-// the table's image: expiries, groups, row pointers, then the doubles sg / c / gshift [K] and steps [P]
-struct GreeksImage {
-    size_t o_groups, o_rows, o_doubles, bytes;
-};
-static GreeksImage greeks_image(int m, size_t K, int groups, int P)
-{
-    GreeksImage im;
-    im.o_groups = greeks_align8(sizeof(GreeksExpiry) * m);
-    im.o_rows = im.o_groups + greeks_align8(sizeof(GreeksGroup) * groups);
-    im.o_doubles = im.o_rows + sizeof(double *) * static_cast<size_t>(1 + 2 * P) * m;
-    im.bytes = im.o_doubles + sizeof(double) * (3 * K + static_cast<size_t>(P));
-    return im;
-}
-static size_t greeks_results_doubles(size_t K, int P)
-{
-    return (SVMC_GREEKS_BASE_ROWS + static_cast<size_t>(SVMC_GREEKS_SENS_ROWS) * P) * K;
-}
-static size_t greeks_workspace_bytes(size_t n_path, int m, size_t K, int groups, int P)
-{
-    return greeks_image(m, K, groups, P).bytes +
-           sizeof(double) * (static_cast<size_t>(greeks_rows(n_path)) * (1 + 2 * P) * GREEKS_COLS * K + greeks_results_doubles(K, P) +
-                             static_cast<size_t>(1 + 2 * P) * K);
-}
-// (every expiry may end in a ragged group)
-size_t greeks_payoff_workspace_bytes_of(size_t n_path, int n_expiries, size_t total_strikes, int n_params)
-{
-    return greeks_workspace_bytes(n_path, n_expiries, total_strikes, static_cast<int>(total_strikes / GREEKS_KT) + n_expiries, n_params);
-}
-size_t greeks_payoff_image_bytes_of(int n_expiries, size_t total_strikes, int n_params)
-{
-    return greeks_image(n_expiries, total_strikes, static_cast<int>(total_strikes / GREEKS_KT) + n_expiries, n_params).bytes;
-}
-
-// The checks of the tail, all before any device work (the fused drivers make them ahead of their stepping launch).
-int greeks_check(const char *fn, size_t n_path, const double *forwards_host, const double *discfactors_host, int n_expiries,
-                 const double *strikes_host, const int8_t *types_host, const size_t *strike_offsets_host, int n_params,
-                 const double *steps_host)
-{
-    SVMC_REQUIRE(forwards_host && discfactors_host && strikes_host && types_host && strike_offsets_host, std::string(fn) + ": null pointer");
-    SVMC_REQUIRE(n_path > 0 && n_expiries >= 1, std::string(fn) + ": n_path and n_expiries must be positive");
-    SVMC_REQUIRE(n_params >= 0 && n_params <= SVMC_GREEKS_MAX_PARAMS, std::string(fn) + ": n_params must be in [0, SVMC_GREEKS_MAX_PARAMS]");
-    SVMC_REQUIRE(n_params == 0 || steps_host != nullptr, std::string(fn) + ": null steps");
-    for (int p = 0; p < n_params; ++p)
-        SVMC_REQUIRE(std::isfinite(steps_host[p]) && steps_host[p] > 0.0, std::string(fn) + ": a step is not positive and finite");
-    for (int i = 0; i < n_expiries; ++i) {
-        SVMC_REQUIRE(strike_offsets_host[i] <= strike_offsets_host[i + 1], std::string(fn) + ": strike offsets must not decrease");
-        SVMC_REQUIRE(std::isfinite(forwards_host[i]) && forwards_host[i] > 0.0, std::string(fn) + ": a forward is not positive and finite");
-        SVMC_REQUIRE(std::isfinite(discfactors_host[i]), std::string(fn) + ": a discount factor is not finite");
-    }
-    const size_t K = strike_offsets_host[n_expiries];
-    SVMC_REQUIRE(K < (1u << 24), std::string(fn) + ": too many strikes");
-    for (size_t k = 0; k < K; ++k) {
-        if (types_host[k] != SVMC_CALL && types_host[k] != SVMC_PUT) return fail(SVMC_ERR_UNKNOWN_PAYOFF, "unknown option payoff code");
-        SVMC_REQUIRE(std::isfinite(strikes_host[k]), std::string(fn) + ": a strike is not finite");
-    }
-    return SVMC_OK;
-}
-
-// The launches of the tail (the job pass and its finish, then the pair pass and its finish), queued on `stream` (arguments checked by greeks_check).  rows_host: [1 + 2P][m] device pointers,
-// job-major.  image: host memory of greeks_payoff_image_bytes_of that must stay untouched until the stream has passed the upload
-// -- page-locked in the fused drivers, which synchronise once for everything they queued.  base_out [SVMC_GREEKS_BASE_ROWS][K],
-// sens_out [P][SVMC_GREEKS_SENS_ROWS][K]: device memory or device-visible pinned host memory; null: the block inside the
-// workspace that *results_dev reports.
+// The launches of the tail (the job pass and its finish, then the pair pass and its finish), queued on `stream` (arguments checked by
+// the caller: check_steps, check_quotes).  rows_host: [1 + 2P][m] device pointers, job-major.  image: host memory, the head of
+// greeks_pinned's block, that must stay untouched until the stream has passed the upload -- page-locked in the fused drivers, which
+// synchronise once for everything they queued.  base_out [SVMC_GREEKS_BASE_ROWS][K], sens_out [P][SVMC_GREEKS_SENS_ROWS][K]: device
+// memory or device-visible pinned host memory; null: the block inside the workspace that *results_dev reports.
 int greeks_payoff_enqueue(const char *fn, const double *const *rows_host, size_t n_path, const double *forwards_host,
                           const double *discfactors_host, int n_expiries, const double *strikes_host, const int8_t *types_host,
                           const size_t *strike_offsets_host, int n_params, const double *steps_host, const double *spot_sums,
@@ -293,54 +201,20 @@ int greeks_payoff_enqueue(const char *fn, const double *const *rows_host, size_t
 {
     const int m = n_expiries, P = n_params;
     const size_t K = strike_offsets_host[m];
-    const int G = greeks_groups(m, strike_offsets_host);
-    if (workspace_bytes < greeks_workspace_bytes(n_path, m, K, G, P))
-        return fail(SVMC_ERR_WORKSPACE, std::string(fn) + ": workspace too small (svmc_greeks_payoff_workspace_bytes)");
-    const GreeksImage im = greeks_image(m, K, G, P);
-    unsigned char *img = static_cast<unsigned char *>(image);
-    GreeksExpiry *ex = reinterpret_cast<GreeksExpiry *>(img);
-    GreeksGroup *gr = reinterpret_cast<GreeksGroup *>(img + im.o_groups);
-    const double **rows = reinterpret_cast<const double **>(img + im.o_rows);
-    double *kd = reinterpret_cast<double *>(img + im.o_doubles);
-    int g = 0;
-    for (int i = 0; i < m; ++i) {
-        const int k0 = static_cast<int>(strike_offsets_host[i]), k1 = static_cast<int>(strike_offsets_host[i + 1]);
-        ex[i] = GreeksExpiry{forwards_host[i], discfactors_host[i], k0, k1};
-        for (int k = k0; k < k1; k += GREEKS_KT) gr[g++] = GreeksGroup{i, k, (k1 - k < GREEKS_KT) ? k1 - k : GREEKS_KT, 0};
-        for (int k = k0; k < k1; ++k) {
-            const double sgn = (types_host[k] == SVMC_PUT) ? -1.0 : 1.0;
-            kd[k] = sgn;
-            kd[K + k] = -sgn * strikes_host[k];
-            kd[2 * K + k] = (sgn * (forwards_host[i] - strikes_host[k]) > 0.0) ? sgn : 0.0;
-        }
-    }
-    for (int j = 0; j < (1 + 2 * P) * m; ++j) {
-        SVMC_REQUIRE(rows_host[j] != nullptr, std::string(fn) + ": null snapshot");
-        rows[j] = rows_host[j];
-    }
-    for (int p = 0; p < P; ++p) kd[3 * K + p] = steps_host[p];
-    unsigned char *w = static_cast<unsigned char *>(workspace);
-    SVMC_HIP_TRY(hipMemcpyAsync(w, img, im.bytes, hipMemcpyHostToDevice, stream));
-    const double *d = reinterpret_cast<const double *>(w + im.o_doubles);
+    const int G = quote_groups(m, strike_offsets_host, GREEKS_KT, false);
     GreeksTable t;
-    t.expiries = reinterpret_cast<const GreeksExpiry *>(w);
-    t.groups = reinterpret_cast<const GreeksGroup *>(w + im.o_groups);
-    t.rows = reinterpret_cast<const double *const *>(w + im.o_rows);
+    Layout w{static_cast<unsigned char *>(workspace)}, h{static_cast<unsigned char *>(image)};
+    const size_t image_bytes = greeks_workspace(w, n_path, m, K, G, P, t);
+    if (workspace_bytes < w.bytes())
+        return fail(SVMC_ERR_WORKSPACE, std::string(fn) + ": workspace too small (svmc_greeks_payoff_workspace_bytes)");
+    for (int j = 0; j < (1 + 2 * P) * m; ++j) SVMC_REQUIRE(rows_host[j] != nullptr, std::string(fn) + ": null snapshot");
+    greeks_fill_image(greeks_image(h, m, K, G, P), rows_host, forwards_host, discfactors_host, m, strikes_host, types_host,
+                      strike_offsets_host, P, steps_host);
+    SVMC_HIP_TRY(hipMemcpyAsync(workspace, image, image_bytes, hipMemcpyHostToDevice, stream));
     t.spot_sums = spot_sums;
-    t.sg = d;
-    t.c = d + K;
-    t.gshift = d + 2 * K;
-    t.steps = d + 3 * K;
-    double *res = reinterpret_cast<double *>(w + im.bytes);
-    t.base_out = base_out ? base_out : res;
-    t.sens_out = sens_out ? sens_out : res + SVMC_GREEKS_BASE_ROWS * K;
-    t.itm_fraction = res + greeks_results_doubles(K, P);
-    t.partials = t.itm_fraction + static_cast<size_t>(1 + 2 * P) * K;
-    t.m = m;
-    t.K = static_cast<int>(K);
-    t.P = P;
-    t.n_rows = greeks_rows(n_path);
-    if (results_dev != nullptr) *results_dev = res;
+    if (results_dev != nullptr) *results_dev = t.base_out;
+    if (base_out != nullptr) t.base_out = base_out;
+    if (sens_out != nullptr) t.sens_out = sens_out;
     if (K == 0) return SVMC_OK;
     // the job pass first: its finish leaves every job's in-the-money fractions where the pair pass reads them
     for (int pair_pass = 0; pair_pass <= (P > 0 ? 1 : 0); ++pair_pass) {
@@ -375,9 +249,9 @@ int svmc_greeks_payoff_chain(const double *const *base_rows_host, const double *
                              size_t workspace_bytes, svmc_stream_t stream)
 {
     const char *fn = "svmc_greeks_payoff_chain";
-    SVMC_REQUIRE(base_rows_host && spot_sums && greeks_host && workspace, std::string(fn) + ": null pointer");
-    if (int rc = greeks_check(fn, n_path, forwards_host, discfactors_host, n_expiries, strikes_host, types_host, strike_offsets_host,
-                              n_params, steps_host))
+    SVMC_REQUIRE(base_rows_host && spot_sums && greeks_host && workspace && discfactors_host, std::string(fn) + ": null pointer");
+    if (int rc = check_steps(fn, n_params, steps_host, 0)) return rc;
+    if (int rc = check_quotes(fn, n_path, forwards_host, discfactors_host, n_expiries, strikes_host, types_host, strike_offsets_host, 1u << 24, 1))
         return rc;
     SVMC_REQUIRE(n_params == 0 || (up_rows_host && dn_rows_host && sens_host), std::string(fn) + ": null pointer");
     const int m = n_expiries, P = n_params;
@@ -390,7 +264,7 @@ int svmc_greeks_payoff_chain(const double *const *base_rows_host, const double *
             rows[static_cast<size_t>(2 + 2 * p) * m + i] = dn_rows_host[static_cast<size_t>(p) * m + i];
         }
     }
-    std::vector<unsigned char> image(greeks_payoff_image_bytes_of(m, K, P));
+    std::vector<unsigned char> image(greeks_pinned(nullptr, m, K, P, nullptr));
     double *res = nullptr;
     if (int rc = greeks_payoff_enqueue(fn, rows.data(), n_path, forwards_host, discfactors_host, m, strikes_host, types_host,
                                        strike_offsets_host, P, steps_host, spot_sums, nullptr, nullptr, image.data(), workspace,

@@ -51,6 +51,12 @@ struct ManySlices;
 ManySlices many_slices(int n_slices, const int *nb_steps_host, const double *forwards_host);
 int check_many(const char *fn, size_t n_path, int n_jobs, int n_slices, const int *nb_steps_host, const double *dts_host,
                const uint32_t *call_ids);
+// the checks of a chain's quotes that the Greeks and the conditional tails and their fused drivers make (discfactors_host null: not
+// checked; "too many strikes": quotes_per_strike x K reaches strike_limit), and of n_params in [min_params, max] and its steps
+int check_quotes(const char *fn, size_t n_path, const double *forwards_host, const double *discfactors_host, int n_expiries,
+                 const double *strikes_host, const int8_t *types_host, const size_t *strike_offsets_host, size_t strike_limit,
+                 size_t quotes_per_strike);
+int check_steps(const char *fn, int n_params, const double *steps_host, int min_params);
 
 // svmc_kernels.hip: launches whose model constants live in device memory (graph replay, svmc_chain.hip)
 constexpr int LOGSV_CONSTS_DOUBLES = 13;
@@ -129,7 +135,9 @@ int hawkes_chain_rng_many(size_t n_path, int n_jobs, int n_slices, const int *nb
                           uint64_t path_offset, void *table_host, void *table_dev, double *x_snapshots, double *spot_partials,
                           hipStream_t stream);
 // svmc_cmc.hip: the conditional Monte Carlo chain (svmc_*_chain_price_cmc) -- stepping from (mu, cv, vol, qvar) = (0, 0, vol0, 0)
-// into the mu / cv snapshot rows, the payoff tail (svmc_cmc_payoff_chain's body: returns synchronised) and its workspace
+// into the mu / cv snapshot rows, and the payoff tail: svmc_cmc_payoff_chain's body, or, with greeks_host [SVMC_CMC_GREEKS_ROWS][K]
+// not null, svmc_cmc_greeks_chain's (prices_host and stderrs_host are then not read, stats_host is
+// [m][SVMC_CMC_GREEKS_STATS_DOUBLES]); returns synchronised.  The sizes of its workspace and its page-locked block: svmc_quotes.h.
 int logsv_cmc_step_from(double sigma0, double *mu, double *cv, double *sigma, double *qvar, size_t n_path, int n_slices,
                         const int *nb_steps_host, const double *dts_host, const double *etas_host, double theta, double kappa1,
                         double kappa2, double beta, double volvol, int is_spot_measure, uint64_t seed, uint32_t call_id,
@@ -138,20 +146,11 @@ int heston_cmc_step_from(double var0, double *mu, double *cv, double *var, doubl
                          const int *nb_steps_host, const double *dts_host, double theta, double kappa, double rho, double volvol,
                          uint64_t seed, uint32_t call_id, uint64_t path_offset, double *mu_snapshots, double *cv_snapshots,
                          hipStream_t stream);
-size_t cmc_payoff_workspace_bytes_of(size_t n_path, int n_expiries, size_t total_strikes);
-int cmc_payoff_chain(const char *fn, const double *const *mu_snapshots_host, const double *const *cv_snapshots_host, size_t n_path,
-                     const double *forwards_host, const double *discfactors_host, int n_expiries, const double *strikes_host,
-                     const int8_t *types_host, const size_t *strike_offsets_host, int recenter, double *prices_host, double *stderrs_host,
-                     double *stats_host, void *workspace, size_t workspace_bytes, hipStream_t stream, void *pinned, size_t pinned_bytes);
-size_t cmc_payoff_pinned_bytes_of(int n_expiries, size_t total_strikes);
-// ... and the tail with the derivatives in F and K (svmc_cmc_greeks_chain's body): greeks_host [SVMC_CMC_GREEKS_ROWS][K], stats_host
-// [m][SVMC_CMC_GREEKS_STATS_DOUBLES]
-size_t cmc_greeks_workspace_bytes_of(size_t n_path, int n_expiries, size_t total_strikes);
-int cmc_greeks_chain(const char *fn, const double *const *mu_snapshots_host, const double *const *cv_snapshots_host, size_t n_path,
-                     const double *forwards_host, const double *discfactors_host, int n_expiries, const double *strikes_host,
-                     const int8_t *types_host, const size_t *strike_offsets_host, int recenter, double *greeks_host, double *stats_host,
-                     void *workspace, size_t workspace_bytes, hipStream_t stream, void *pinned, size_t pinned_bytes);
-size_t cmc_greeks_pinned_bytes_of(int n_expiries, size_t total_strikes);
+int cmc_tail(const char *fn, const double *const *mu_snapshots_host, const double *const *cv_snapshots_host, size_t n_path,
+             const double *forwards_host, const double *discfactors_host, int n_expiries, const double *strikes_host,
+             const int8_t *types_host, const size_t *strike_offsets_host, int recenter, double *prices_host, double *stderrs_host,
+             double *greeks_host, double *stats_host, void *workspace, size_t workspace_bytes, hipStream_t stream, void *pinned,
+             size_t pinned_bytes);
 // ... many conditional jobs of one chain in ONE stepping launch (svmc_*_chain_cmc_many's body): the job table is filled in
 // table_host (cmc_many_table_bytes; kept by the caller until the stream has passed the upload) and uploaded to table_dev, job j's
 // rows are j m + i of mu_snapshots / cv_snapshots; params_host rows as svmc_*_chain_price_many
@@ -163,32 +162,22 @@ int logsv_cmc_step_many(const char *fn, size_t n_path, int n_jobs, int n_slices,
 int heston_cmc_step_many(const char *fn, size_t n_path, int n_jobs, int n_slices, const int *nb_steps_host, const double *dts_host,
                          const double *params_host, const uint64_t *seeds, const uint32_t *call_ids, uint64_t path_offset,
                          void *table_host, void *table_dev, double *mu_snapshots, double *cv_snapshots, hipStream_t stream);
-// ... and the sensitivity tail (svmc_cmc_sens_chain's body): its checks, the launches queued on `stream` from a host image the caller
-// keeps until the stream has passed the upload (up / dn rows [P][m]; *results_dev: the [P][SVMC_CMC_SENS_ROWS][K] results on the
-// device), and the sizes of the image and the workspace
-int cmc_sens_check(const char *fn, size_t n_path, const double *forwards_host, const double *discfactors_host, int n_expiries,
-                   const double *strikes_host, const int8_t *types_host, const size_t *strike_offsets_host, int n_params,
-                   const double *steps_host);
+// ... and the sensitivity tail (svmc_cmc_sens_chain's body): the launches queued on `stream` from a host image the caller keeps
+// until the stream has passed the upload (up / dn rows [P][m]; *results_dev: the [P][SVMC_CMC_SENS_ROWS][K] results on the
+// device); the sizes of the workspace and of the host block [image | results' landing]: svmc_quotes.h
 int cmc_sens_enqueue(const char *fn, const double *const *up_mu, const double *const *up_cv, const double *const *dn_mu,
                      const double *const *dn_cv, size_t n_path, const double *forwards_host, const double *discfactors_host, int n_expiries,
                      const double *strikes_host, const int8_t *types_host, const size_t *strike_offsets_host, int n_params,
                      const double *steps_host, int recenter, void *image, void *workspace, size_t workspace_bytes, hipStream_t stream,
                      double **results_dev);
-size_t cmc_sens_image_bytes_of(int n_expiries, size_t total_strikes, int n_params);
-size_t cmc_sens_workspace_bytes_of(size_t n_path, int n_expiries, size_t total_strikes, int n_params);
-// svmc_greeks.hip: the Greeks tail (svmc_greeks_payoff_chain's body) -- its checks, the two launches queued on `stream` from a host
-// image the caller keeps until the stream has passed the upload (rows_host [1 + 2P][m] job-major; base_out / sens_out device or
-// pinned, null: inside the workspace at *results_dev), and the sizes of the workspace and the image
-int greeks_check(const char *fn, size_t n_path, const double *forwards_host, const double *discfactors_host, int n_expiries,
-                 const double *strikes_host, const int8_t *types_host, const size_t *strike_offsets_host, int n_params,
-                 const double *steps_host);
+// svmc_greeks.hip: the Greeks tail (svmc_greeks_payoff_chain's body) -- the launches queued on `stream` from a host image the
+// caller keeps until the stream has passed the upload (rows_host [1 + 2P][m] job-major; base_out / sens_out device or pinned,
+// null: inside the workspace at *results_dev); the sizes of the workspace and of the host block [image | results]: svmc_quotes.h
 int greeks_payoff_enqueue(const char *fn, const double *const *rows_host, size_t n_path, const double *forwards_host,
                           const double *discfactors_host, int n_expiries, const double *strikes_host, const int8_t *types_host,
                           const size_t *strike_offsets_host, int n_params, const double *steps_host, const double *spot_sums,
                           double *base_out, double *sens_out, void *image, void *workspace, size_t workspace_bytes, hipStream_t stream,
                           double **results_dev);
-size_t greeks_payoff_workspace_bytes_of(size_t n_path, int n_expiries, size_t total_strikes, int n_params);
-size_t greeks_payoff_image_bytes_of(int n_expiries, size_t total_strikes, int n_params);
 size_t payoff_sets_workspace_bytes(size_t n_path, size_t total_strikes, int n_sets);
 int chain_payoff_and_finish_sets(const double *const *x_snapshots_host, const double *const *qvar_snapshots_host, size_t n_path,
                                  const double *forwards_host, const double *ttms_host, const double *spot_sums, int n_expiries,

@@ -2503,6 +2503,36 @@ int check_many(const char *fn, size_t n_path, int n_jobs, int n_slices, const in
     return SVMC_OK;
 }
 
+int check_quotes(const char *fn, size_t n_path, const double *forwards_host, const double *discfactors_host, int n_expiries,
+                 const double *strikes_host, const int8_t *types_host, const size_t *strike_offsets_host, size_t strike_limit,
+                 size_t quotes_per_strike)
+{
+    SVMC_REQUIRE(forwards_host && strikes_host && types_host && strike_offsets_host, std::string(fn) + ": null pointer");
+    SVMC_REQUIRE(n_path > 0 && n_expiries >= 1, std::string(fn) + ": n_path and n_expiries must be positive");
+    for (int i = 0; i < n_expiries; ++i) {
+        SVMC_REQUIRE(strike_offsets_host[i] <= strike_offsets_host[i + 1], std::string(fn) + ": strike offsets must not decrease");
+        SVMC_REQUIRE(std::isfinite(forwards_host[i]) && forwards_host[i] > 0.0, std::string(fn) + ": a forward is not positive and finite");
+        SVMC_REQUIRE(!discfactors_host || std::isfinite(discfactors_host[i]), std::string(fn) + ": a discount factor is not finite");
+    }
+    const size_t K = strike_offsets_host[n_expiries];
+    SVMC_REQUIRE(quotes_per_strike * K < strike_limit, std::string(fn) + ": too many strikes");      // (before the loop over them)
+    for (size_t k = 0; k < K; ++k) {
+        if (types_host[k] != SVMC_CALL && types_host[k] != SVMC_PUT) return fail(SVMC_ERR_UNKNOWN_PAYOFF, "unknown option payoff code");
+        SVMC_REQUIRE(std::isfinite(strikes_host[k]), std::string(fn) + ": a strike is not finite");
+    }
+    return SVMC_OK;
+}
+
+int check_steps(const char *fn, int n_params, const double *steps_host, int min_params)
+{
+    SVMC_REQUIRE(n_params >= min_params && n_params <= SVMC_GREEKS_MAX_PARAMS,
+                 std::string(fn) + ": n_params must be in [" + std::to_string(min_params) + ", SVMC_GREEKS_MAX_PARAMS]");
+    SVMC_REQUIRE(n_params == 0 || steps_host != nullptr, std::string(fn) + ": null steps");
+    for (int p = 0; p < n_params; ++p)
+        SVMC_REQUIRE(std::isfinite(steps_host[p]) && steps_host[p] > 0.0, std::string(fn) + ": a step is not positive and finite");
+    return SVMC_OK;
+}
+
 int logsv_chain_rng_many(size_t n_path, int n_jobs, int n_slices, const int *nb_steps_host, const double *dts_host,
                          const double *forwards_host, const double *params_host, int is_spot_measure, const uint64_t *seeds,
                          const uint32_t *call_ids, uint64_t path_offset, void *table_host, void *table_dev, double *x_snapshots,
