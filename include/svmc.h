@@ -972,8 +972,8 @@ SVMC_API int svmc_heston_chain_price_cmc(svmc_session_t session, const double *t
  *   svmc_logsv_chain_price_cmc_greeks / svmc_heston_chain_price_cmc_greeks   the fused drivers: arguments as svmc_*_chain_price_cmc
  *                           with greeks_host for the two arrays; the session's workspace and page-locked block grow as theirs do;
  *                           a sharded session is refused.
- * Parameter sensitivities on this estimator: the row f14 block below.  Left out: SVMC_INV_CALL / SVMC_INV_PUT, variables other than
- * the log-return, the inverse measure, Heston QE, Hawkes, sharded sessions, a conditional-MC calibration objective. */
+ * Parameter sensitivities on this estimator: the row f14 block below; its calibration objective: the row f15 block.  Left out:
+ * SVMC_INV_CALL / SVMC_INV_PUT, variables other than the log-return, the inverse measure, Heston QE, Hawkes, sharded sessions. */
 #define SVMC_CMC_GREEKS_KT 4
 #define SVMC_CMC_GREEKS_ROWS 10
 #define SVMC_CMC_GREEKS_STATS_DOUBLES 6
@@ -1112,7 +1112,7 @@ SVMC_API int svmc_heston_chain_price_greeks(svmc_session_t session, const double
  * is not finite, a sharded session (SVMC_ERR_INVALID_ARGUMENT); a type other than SVMC_CALL / SVMC_PUT (SVMC_ERR_UNKNOWN_PAYOFF); a
  * workspace or session too small (SVMC_ERR_WORKSPACE).
  * Left out: SVMC_INV_CALL / SVMC_INV_PUT, variables other than the log-return, the inverse measure, Heston QE, Hawkes, sharded
- * sessions, a conditional-MC calibration objective. */
+ * sessions.  The conditional-MC calibration objective: the row f15 block below. */
 #define SVMC_CMC_SENS_ROWS 3
 SVMC_API int svmc_cmc_many_workspace_bytes(int n_jobs, int n_slices, size_t *bytes);
 SVMC_API int svmc_logsv_chain_cmc_many(size_t n_path, int n_jobs, int n_slices, const int *nb_steps_host, const double *dts_host,
@@ -1153,6 +1153,50 @@ SVMC_API int svmc_heston_chain_price_cmc_sens(svmc_session_t session, const doub
                                               const double *params_host, const double *steps_host, int nb_steps_per_year,
                                               int recenter, uint64_t seed, uint32_t call_id, double *greeks_host,
                                               double *stats_host, double *sens_host);
+
+/* ---- conditional Monte Carlo: the calibration objective on one replayed graph (src svmc_chain.hip, svmc_cmc.hip) ----
+ * svmc_logsv_chain_price_cmc_sets / svmc_heston_chain_price_cmc_sets price one chain for n_sets parameter sets on ONE (seed, call_id)
+ * of stream 8 and return, per set, prices, errors, forward statistics and Black-76 implied vols: what an optimizer iterate of a
+ * calibration on a frozen stream needs -- its base point (one set) or the bumped neighbours of a forward-difference gradient.
+ * params_host rows as svmc_*_chain_price_cmc_many ([n_sets][6 + n_expiries]: v0 theta kappa1 kappa2 beta volvol, then the expiries'
+ * vol-backbone etas / [n_sets][5]: v0 theta kappa rho volvol); 1 <= n_sets <= SVMC_CMC_SETS_MAX.  Outputs [n_sets][sum K_i];
+ * stats_host (nullable) [n_sets][n_expiries][SVMC_CMC_STATS_DOUBLES]; ivols_host (nullable) [n_sets][sum K_i].
+ * CONTRACT.  Set q's prices, errors and statistics are those of svmc_*_chain_price_cmc(seed, call_id) with set q's parameters, BIT
+ * FOR BIT, in both launch forms of the stepping kernel (chosen by n_sets x n_path).  Its vols are the library's Black-76 inversion
+ * (svmc_black_implied_vols' routine, compiled for the device) of those prices on [1e-6, 10]: NaN outside the bracket, for a NaN
+ * price and for K <= 0.  A set's numbers do not depend on which other sets share the call.
+ * ONE EVALUATION IS ONE GRAPH REPLAY: a linear chain of nodes, no parallel branches -- (1) the upload of the job table, filled in
+ * page-locked memory, so that a replay re-prices the chain for new parameters without a new capture; (2) the many-job stepping launch
+ * of the row f14 block, whose arguments do not depend on the parameters; (3) the payoff tail ONCE for all sets, which are laid out as
+ * one table of n_sets x n_expiries expiries and n_sets x sum K_i strikes, set-major, as row f14 lays out its bumped jobs: the forward,
+ * forward-finish and payoff kernels of svmc_cmc_payoff_chain with a single call's statements; (4) cond_vols_finish_kernel, a block
+ * per (set, quote): the two column sums in row order, price and error stored straight into the session's page-locked result block
+ * with the statistics; (5) with ivols_host, cond_vols_invert_kernel, a lane per quote and 64 quotes side by side in a wave, which
+ * stores the vols there too.  No copy node.  The table's image (expiry records with the snapshot rows' addresses, strike groups,
+ * columns) depends on the chain and the buffers alone and is uploaded once per capture, outside the graph, into a workspace no other
+ * call writes.  The session keeps one graph per n_sets; its key covers the chain's content, the model, n_sets, is_spot_measure, the
+ * step grid, recenter, seed, call_id, whether vols are asked for and the address of every device and page-locked buffer the graph
+ * captured.  The stepping buffers are shared with the row f14 calls: a call that regrows one drops the graphs that captured it.
+ * svmc_session_use_graphs(s, 0) issues the same launches directly (the same bits); svmc_session_graph_launches counts the replays.
+ * Checks and status codes are those of svmc_*_chain_price_cmc_many (1 to 16 expiries, an unsharded session, SVMC_CALL / SVMC_PUT, ...),
+ * made before anything is launched; n_sets out of range: SVMC_ERR_INVALID_ARGUMENT.
+ * Left out: a stepping kernel that shares the draw across sets (the conditional step consumes a quarter of a Philox call where the
+ * plain step consumes two normals, so the share that made the plain sets kernel worth building is small here, and the many-job
+ * kernel keeps the bit-equality for free); the objective summed on the device; SVMC_INV_CALL / SVMC_INV_PUT, variables other than the
+ * log-return, the inverse measure, Heston QE, Hawkes, several GPUs. */
+#define SVMC_CMC_SETS_MAX 8
+SVMC_API int svmc_logsv_chain_price_cmc_sets(svmc_session_t session, const double *ttms_host, const double *forwards_host,
+                                             const double *discfactors_host, int n_expiries, const double *strikes_host,
+                                             const int8_t *types_host, const size_t *strike_offsets_host, int n_sets,
+                                             const double *params_host, int is_spot_measure, int nb_steps_per_year, int recenter,
+                                             uint64_t seed, uint32_t call_id, double *prices_host, double *stderrs_host,
+                                             double *stats_host, double *ivols_host);
+SVMC_API int svmc_heston_chain_price_cmc_sets(svmc_session_t session, const double *ttms_host, const double *forwards_host,
+                                              const double *discfactors_host, int n_expiries, const double *strikes_host,
+                                              const int8_t *types_host, const size_t *strike_offsets_host, int n_sets,
+                                              const double *params_host, int nb_steps_per_year, int recenter, uint64_t seed,
+                                              uint32_t call_id, double *prices_host, double *stderrs_host, double *stats_host,
+                                              double *ivols_host);
 
 #ifdef __cplusplus
 }

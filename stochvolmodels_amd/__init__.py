@@ -2,10 +2,10 @@
 stochvolmodels_amd -- MI355X-native Monte Carlo engine for the StochVolModels hot path.
 
 Module layout and public names mirror the reference package (`stochvolmodels`) for the Monte Carlo path:
-    stochvolmodels_amd.pricers.logsv_pricer   LogSVPricer, logsv_mc_chain_pricer(_fixed_randoms, _many, _conditional, _conditional_many),
+    stochvolmodels_amd.pricers.logsv_pricer   LogSVPricer, logsv_mc_chain_pricer(_fixed_randoms, _many, _conditional, _conditional_many, _conditional_sets),
                                               logsv_mc_chain_greeks(_conditional), simulate_logsv_x_vol_terminal,
                                               get_randoms_for_chain_valuation
-    stochvolmodels_amd.pricers.heston_pricer  HestonPricer, HestonParams, heston_mc_chain_pricer(_many, _conditional, _conditional_many),
+    stochvolmodels_amd.pricers.heston_pricer  HestonPricer, HestonParams, heston_mc_chain_pricer(_many, _conditional, _conditional_many, _conditional_sets),
                                               heston_mc_chain_greeks(_conditional), simulate_heston_x_vol_terminal
     stochvolmodels_amd.pricers.hawkes_jd_pricer  HawkesJDPricer, HawkesJDParams, hawkesjd_mc_chain_pricer,
                                               hawkesjd_chain_pricer(_batch), simulate_hawkesjd_terminal,
@@ -57,6 +57,7 @@ _EXPORTS = {
     "logsv_mc_chain_greeks": "pricers.logsv_pricer",
     "logsv_mc_chain_greeks_conditional": "pricers.logsv_pricer",
     "logsv_mc_chain_pricer_conditional_many": "pricers.logsv_pricer",
+    "logsv_mc_chain_pricer_conditional_sets": "pricers.logsv_pricer",
     "logsv_mc_chain_pricer_fixed_randoms": "pricers.logsv_pricer",
     "simulate_logsv_x_vol_terminal": "pricers.logsv_pricer",
     "simulate_vol_paths": "pricers.logsv_pricer",
@@ -84,6 +85,7 @@ _EXPORTS = {
     "heston_mc_chain_greeks": "pricers.heston_pricer",
     "heston_mc_chain_greeks_conditional": "pricers.heston_pricer",
     "heston_mc_chain_pricer_conditional_many": "pricers.heston_pricer",
+    "heston_mc_chain_pricer_conditional_sets": "pricers.heston_pricer",
     "simulate_heston_x_vol_terminal": "pricers.heston_pricer",
     "compute_analytic_qvar": "pricers.logsv.vol_moments_ode",
     "compute_analytic_vol_moments": "pricers.logsv.vol_moments_ode",

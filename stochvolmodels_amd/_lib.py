@@ -205,6 +205,10 @@ def _declare(L: C.CDLL) -> None:
                                              pf64, pf64], i32),
         "svmc_heston_chain_price_cmc_sens": ([vp, pf64, pf64, pf64, i32, pf64, pi8, psz, i32, pf64, pf64, i32, i32, u64, u32, pf64,
                                               pf64, pf64], i32),
+        "svmc_logsv_chain_price_cmc_sets": ([vp, pf64, pf64, pf64, i32, pf64, pi8, psz, i32, pf64, i32, i32, i32, u64, u32, pf64, pf64,
+                                             pf64, pf64], i32),
+        "svmc_heston_chain_price_cmc_sets": ([vp, pf64, pf64, pf64, i32, pf64, pi8, psz, i32, pf64, i32, i32, u64, u32, pf64, pf64,
+                                              pf64, pf64], i32),
         "svmc_hawkesjd_chain_price_tilted": ([vp, pf64, pf64, i32, pf64, pi8, psz, pf64, i32, u64, u32, pf64, i32, i32, pf64, pf64,
                                               pf64], i32),
         "svmc_greeks_payoff_workspace_bytes": ([sz, i32, sz, i32, psz], i32),

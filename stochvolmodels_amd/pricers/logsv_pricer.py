@@ -18,8 +18,8 @@ import numpy as np
 import pandas as pd
 
 from .. import dist as svdist
-from ..data.option_chain import OptionChain
-from ..engine import DeviceRandoms, get_engine, marshalled_chain, option_type_codes, payoff_finalize, tilted_type_codes
+from ..data.option_chain import OptionChain, black_ivols_native
+from ..engine import CMC_SETS_MAX, DeviceRandoms, get_engine, marshalled_chain, option_type_codes, payoff_finalize, tilted_type_codes
 from ..mc_chain import (chain_shaped, check_many_args, many_job_chunks, many_job_streams, many_jobs_shaped, price_chain_on_engine,
                         variable_type_code)
 from ..mc_greeks import LOGSV_GREEK_PARAMS, check_greeks_request, greeks_bumps, greeks_job_table, greeks_shaped
@@ -346,7 +346,11 @@ class LogSVPricer(ModelPricer):
         (reference :440-557).  The MC engines draw the reference's RandomState(seed) randoms once, upload this rank's
         columns to HBM once, and every objective evaluation re-prices the chain from those resident randoms -- the
         optimizer loop is kernel-bound, not PCIe-bound.  `kwargs`: comm=, disp= (SLSQP printing, default True as in
-        the reference).  `self.last_calibration` keeps {"n_eval", "objective"} of the run."""
+        the reference).  `self.last_calibration` keeps {"n_eval", "objective"} of the run.
+        calibration_engine=CalibrationEngine.MC with estimator="conditional" (DESIGN.md row f15): the objective on the conditional
+        Monte Carlo estimator (logsv_mc_chain_pricer_conditional_sets) on the frozen stream (seed, call 0) -- an order of magnitude
+        less noise per path, a smooth function under the forward differences, nothing stored in HBM (device_randoms="hbm" raises
+        ValueError, a sharded request NotImplementedError); recenter= is passed on (default True)."""
         vol_scaler = self.set_vol_scaler(option_chain=option_chain)
         _, market_vols_ttms = option_chain.get_chain_data_as_xy()
         market_vols = np.concatenate(market_vols_ttms).ravel()
@@ -376,6 +380,26 @@ class LogSVPricer(ModelPricer):
                 prices = self.price_chain_batch(option_chain=option_chain, params_list=[parse(p) for p in pars_list],
                                                 vol_scaler=vol_scaler, **tol)
                 return [option_chain.compute_model_ivols_from_chain_data(model_prices=pr) for pr in prices]
+            if not kwargs.get("batched_gradient", True):
+                model_vols_batch = None
+        elif calibration_engine == CalibrationEngine.MC and kwargs.get("estimator") is not None:
+            # estimator="conditional" (DESIGN.md row f15): the conditional estimator on the frozen stream (seed, call 0) -- an
+            # evaluation is one replayed graph with the implied vols as its last kernel, the bumped vectors of a gradient ride one
+            # stepping launch (logsv_mc_chain_pricer_conditional_sets).  Nothing is stored in HBM.
+            if kwargs["estimator"] != "conditional":
+                raise ValueError(f"estimator={kwargs['estimator']!r}: 'conditional', or no keyword for the plain estimator")
+            if kwargs.get("device_randoms") == "hbm":
+                raise ValueError('estimator="conditional" stores no randoms: device_randoms="hbm" does not apply')
+            sets_args = dict(chain_args, nb_path=nb_path, nb_steps_per_year=nb_steps, seed=seed, recenter=kwargs.get("recenter", True),
+                             return_ivols=True, comm=comm, devices=kwargs.get("devices"))
+            check_conditional_request("calibrate_model_params_to_chain", VariableType.LOG_RETURN, comm, kwargs.get("devices"),
+                                      option_chain.optiontypes_ttms)
+
+            def model_vols(pars):
+                return logsv_mc_chain_pricer_conditional_sets([parse(pars)], **sets_args)[0][2]
+
+            def model_vols_batch(pars_list):
+                return [res[2] for res in logsv_mc_chain_pricer_conditional_sets([parse(p) for p in pars_list], **sets_args)]
             if not kwargs.get("batched_gradient", True):
                 model_vols_batch = None
         elif calibration_engine == CalibrationEngine.MC:
@@ -1036,6 +1060,78 @@ def conditional_many_shaped(out: list, strikes_ttms: Sequence[np.ndarray], retur
     """every job's (prices, stderrs, stats) of the engine's many-job conditional call as the single function returns them"""
     shaped = [(chain_shaped(pr, strikes_ttms), chain_shaped(se, strikes_ttms), st) for pr, se, st in out]
     return shaped if return_stats else [(pr, se) for pr, se, _ in shaped]
+
+
+def conditional_sets_on_engine(model: str, rows: np.ndarray, single, chain: tuple, codes, is_spot_measure: bool, nb_path: int,
+                               nb_steps_per_year: int, seed: Optional[int], recenter: bool, return_ivols: bool,
+                               return_stats: bool) -> list:
+    """the body of the two *_mc_chain_pricer_conditional_sets functions: the sets `rows` ([P][6 + m] | [P][5]) of one chain on ONE
+    (seed, call id) -- seed None: the process seed and ONE next call id -- in engine calls of up to CMC_SETS_MAX sets, in order.
+    More than 16 expiries: single(q, seed, call_id) -> (prices, stderrs, stats), one conditional call per set on that stream, and
+    the host routine's vols.  chain: (ttms, forwards, discfactors, strikes_ttms, optiontypes_ttms).  Per set (prices, stderrs[,
+    ivols][, stats]), chain-shaped."""
+    if len(rows) == 0:
+        return []
+    rng_seed, call_id = next_rng_call(seed)
+    ttms, forwards, discfactors, strikes_ttms, optiontypes_ttms = chain
+    if len(ttms) > 16:
+        out = []
+        for q in range(len(rows)):
+            prices, stderrs, stats = single(q, rng_seed, call_id)
+            ivols = [black_ivols_native(p, float(t), float(f), np.ravel(k), np.ravel(ty), float(d))
+                     for p, t, f, k, ty, d in zip(prices, ttms, forwards, strikes_ttms, optiontypes_ttms, discfactors)] if return_ivols else None
+            out.append((prices, stderrs, ivols, stats))
+    else:
+        ch = marshalled_chain(ttms, forwards, discfactors, strikes_ttms, codes)
+        eng = get_engine(nb_path)
+        out = []
+        for q0 in range(0, len(rows), CMC_SETS_MAX):
+            out += eng.price_chain_cmc_sets_fused(ch, model, rows[q0:q0 + CMC_SETS_MAX], int(bool(is_spot_measure)), nb_steps_per_year,
+                                                  recenter, rng_seed, call_id, want_ivols=return_ivols)
+    shapes = [k.shape if isinstance(k, np.ndarray) else np.shape(k) for k in strikes_ttms]
+    shaped = []
+    for prices, stderrs, ivols, stats in out:
+        one = (chain_shaped(prices, strikes_ttms, shapes), chain_shaped(stderrs, strikes_ttms, shapes))
+        if return_ivols:
+            one += (chain_shaped(ivols, strikes_ttms, shapes),)
+        shaped.append(one + (stats,) if return_stats else one)
+    return shaped
+
+
+def logsv_mc_chain_pricer_conditional_sets(params_list: Sequence[LogSvParams], ttms: np.ndarray, forwards: np.ndarray,
+                                           discfactors: np.ndarray, strikes_ttms: Sequence[np.ndarray],
+                                           optiontypes_ttms: Sequence[np.ndarray], is_spot_measure: bool = True,
+                                           nb_path: int = 100000, nb_steps_per_year: int = 360,
+                                           variable_type: VariableType = VariableType.LOG_RETURN, seed: Optional[int] = None,
+                                           recenter: bool = True, return_ivols: bool = False, return_stats: bool = False, comm=None,
+                                           devices=None) -> list:
+    """logsv_mc_chain_pricer_conditional for several parameter sets of ONE chain on ONE random stream: the
+    evaluation of a calibration objective on a frozen stream.  Every set is priced on (seed, call 0) -- with seed=None on the process
+    seed and ONE next call id -- and returns what logsv_mc_chain_pricer_conditional returns on that stream, BIT FOR BIT: (prices,
+    stderrs), with return_ivols=True also the Black-76 implied vols of the prices (NaN outside [1e-6, 10]; computed by the graph's
+    last kernel), with return_stats=True also the statistics.  Up to CMC_SETS_MAX sets are ONE replayed graph
+    (svmc_logsv_chain_price_cmc_sets: the job table's upload, one stepping launch, one tail for all sets); longer lists go in
+    several calls, in order, on the same stream; more than 16 expiries run as single conditional calls with the host routine's
+    vols.  Refusals: check_conditional_request's.  Not in the reference API."""
+    who = "logsv_mc_chain_pricer_conditional_sets"
+    codes = check_conditional_request(who, variable_type, comm, devices, optiontypes_ttms, is_spot_measure)
+    params_list = list(params_list)
+    ttms = np.asarray(ttms, dtype=float)
+    m = len(ttms)
+    etas = [p.get_vol_backbone_etas(ttms=ttms) for p in params_list]
+    rows = np.ones((len(params_list), 6 + m))
+    for row, p, e in zip(rows, params_list, etas):
+        row[:6] = (p.sigma0, p.theta, p.kappa1, p.kappa2, p.beta, p.volvol)
+        row[6:] = np.ravel(e)
+    chain = (ttms, forwards, discfactors, strikes_ttms, optiontypes_ttms)
+
+    def single(q: int, rng_seed: int, call_id: int):
+        p = params_list[q]
+        ch = marshalled_chain(ttms, forwards, discfactors, strikes_ttms, codes)
+        return get_engine(nb_path).price_logsv_chain_cmc_fused(ch, p.sigma0, p.theta, p.kappa1, p.kappa2, p.beta, p.volvol, etas[q],
+                                                               is_spot_measure, nb_steps_per_year, recenter, rng_seed, call_id)
+    return conditional_sets_on_engine("logsv", rows, single, chain, codes, is_spot_measure, nb_path, nb_steps_per_year, seed, recenter,
+                                      return_ivols, return_stats)
 
 
 def conditional_log_return_pdf(route, ttm: float, x_grid: np.ndarray, return_stderr: bool = False):
