@@ -1198,6 +1198,57 @@ SVMC_API int svmc_heston_chain_price_cmc_sets(svmc_session_t session, const doub
                                               uint32_t call_id, double *prices_host, double *stderrs_host, double *stats_host,
                                               double *ivols_host);
 
+/* ---- conditional Monte Carlo for the Hawkes jump-diffusion (src svmc_hawkes.hip, svmc_chain.hip) ----
+ * The diffusion sigma w0 of the step of svmc_hawkesjd_terminal_rng has a constant sigma and is independent of both jump processes
+ * and both intensities.  Given a path's jumps its discretised log-return is therefore exactly Gaussian,
+ *   x_T | jumps ~ N(mu, cv),   mu = sum_t ((mu_drift - sigma^2 / 2) dt - comp_p dt lambda_p,t - comp_m dt lambda_m,t + J_P,t + J_M,t),
+ *   cv = sigma^2 T -- ONE number for every path,
+ * and integrating w0 out leaves a Black-76 price per path: the plain pricer's expectation for the same discretised model and a smaller
+ * variance.  A path carries (mu, lambda_p, lambda_m); the stepping draws no normal; svmc_cmc_payoff_chain and svmc_cmc_greeks_chain
+ * (rows f11, f13) serve unchanged on (mu, cv).
+ *
+ * STEPPING.  svmc_hawkesjd_chain_cond advances the caller's device state (mu, lambda_p, lambda_m), [n_path] each, through n_slices
+ * slices (any number: launches of 16) of nb_steps_host[i] steps of dts_host[i], by the statements of svmc_hawkesjd_terminal_rng's step
+ * without the normal: the jump tests on the intensities at the start of the step (1 - u < lambda dt screens the fp64 -ln u <
+ * lambda dt), drift = (drift dt - comp_p dt lambda_p) - comp_m dt lambda_m, mu = ((mu + drift) + jump_p) + jump_m, the two
+ * intensity statements with no floor; no product is fused into a sum.  Row i of mu_snapshots ([n_slices][n_path], device, nullable)
+ * is mu at the end of slice i; row i of cv_snapshots (the same, nullable) holds cv_i on every path; cvs_host ([n_slices], host,
+ * nullable) receives the cv_i.  The terminal state is written back.
+ * Randoms: stream 9 of (seed, call_id) carries the jump uniforms, ONE call per TWO steps -- chain-global step s = step_offset +
+ * local step reads words 2 (s & 1) and 2 (s & 1) + 1 of the call at index s >> 1 as u_p, u_m = (r + 1/2) 2^-32; stream 10's call at
+ * index s, drawn only on a step where a side jumps, gives E_p, E_m from its words 0 and 1 as stream 7's.  Both are independent of
+ * the plain pricer's streams 6 and 7 at equal (seed, call_id); streams 0 .. 8 are untouched: the stream version stays 4.
+ * VARIANCE.  cv_i = cv_(i-1) + nb_steps_i (sigma sigma dt_i), formed on the host in double in slice order from cv_(-1) = cv_start,
+ * each product and sum rounded once; the kernel does no variance arithmetic.
+ * CONTINUATION.  A chain cut into several calls -- each with step_offset = the steps taken so far and cv_start = the last cv of
+ * the call before -- gives the bits of the unbroken call, also where a cut falls between the two steps of one stream-9 call;
+ * path_offset shards a job by the global path index the same way.
+ * Refusals (SVMC_ERR_INVALID_ARGUMENT, before any launch): those of svmc_hawkesjd_terminal_rng (the parameter block, a null state
+ * array, n_path = 0, a negative step count, a dt that is not positive and finite, call_id past 24 bits), no slices or null grids,
+ * cv_start negative or not finite.
+ *
+ * FUSED.  svmc_hawkesjd_chain_price_cmc / svmc_hawkesjd_chain_price_cmc_greeks: the stepping from (0, lambda_p, lambda_m) on the
+ * session's own state (x holds mu, its two other arrays lambda_p and lambda_m afterwards) on the step grid of
+ * svmc_hawkesjd_chain_price, then the tail of svmc_cmc_payoff_chain / svmc_cmc_greeks_chain; arguments, outputs, refusals and status
+ * codes as svmc_heston_chain_price_cmc / svmc_heston_chain_price_cmc_greeks with params_host for the model (its checks are made
+ * first).  Bit-equal to svmc_hawkesjd_chain_cond followed by the tail entry on its rows.
+ * Left out, each a later step: the estimator under the risk-premia kernel, many-job and few-waves stepping forms, parameter
+ * sensitivities, a calibration objective, SVMC_INV_CALL / SVMC_INV_PUT, variables other than the log-return, several GPUs. */
+SVMC_API int svmc_hawkesjd_chain_cond(double *mu, double *lambda_p, double *lambda_m, size_t n_path, int n_slices,
+                                      const int *nb_steps_host, const double *dts_host, const double *params_host, double cv_start,
+                                      uint64_t seed, uint32_t call_id, uint64_t path_offset, uint32_t step_offset,
+                                      double *mu_snapshots, double *cv_snapshots, double *cvs_host, svmc_stream_t stream);
+SVMC_API int svmc_hawkesjd_chain_price_cmc(svmc_session_t session, const double *ttms_host, const double *forwards_host,
+                                           const double *discfactors_host, int n_expiries, const double *strikes_host,
+                                           const int8_t *types_host, const size_t *strike_offsets_host, const double *params_host,
+                                           int nb_steps_per_year, int recenter, uint64_t seed, uint32_t call_id, double *prices_host,
+                                           double *stderrs_host, double *stats_host);
+SVMC_API int svmc_hawkesjd_chain_price_cmc_greeks(svmc_session_t session, const double *ttms_host, const double *forwards_host,
+                                                  const double *discfactors_host, int n_expiries, const double *strikes_host,
+                                                  const int8_t *types_host, const size_t *strike_offsets_host,
+                                                  const double *params_host, int nb_steps_per_year, int recenter, uint64_t seed,
+                                                  uint32_t call_id, double *greeks_host, double *stats_host);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,7 +13,8 @@ Module layout and public names mirror the reference package (`stochvolmodels`) f
                                               hawkesjd_chain_pricer_with_risk_premia(_batch),
                                               hawkesjd_mc_chain_pricer_with_risk_premia(_gammas),
                                               hawkesjd_mc_chain_pricer_many,
-                                              hawkesjd_mc_chain_pricer_with_risk_premia_gammas_many
+                                              hawkesjd_mc_chain_pricer_with_risk_premia_gammas_many,
+                                              hawkesjd_mc_chain_pricer_conditional, hawkesjd_mc_chain_greeks_conditional
     stochvolmodels_amd.pricers.il_pricer      logsv_il_pricer(_vector, _batch), square_root_payoff_pricer_with_mgf_grid,
                                               compute_mc_il_payoff
     stochvolmodels_amd.utils.mc_payoffs       compute_mc_vars_payoff, compute_mc_vars_payoff_with_gamma,
@@ -47,6 +48,8 @@ _EXPORTS = {
     "hawkesjd_mc_chain_pricer_many": "pricers.hawkes_jd_pricer",
     "hawkesjd_mc_chain_pricer_with_risk_premia_gammas_many": "pricers.hawkes_jd_pricer",
     "hawkesjd_pdf_under_risk_kernel": "pricers.hawkes_jd_pricer",
+    "hawkesjd_mc_chain_pricer_conditional": "pricers.hawkes_jd_pricer",
+    "hawkesjd_mc_chain_greeks_conditional": "pricers.hawkes_jd_pricer",
     "OptionChain": "data.option_chain",
     "ModelParams": "pricers.model_pricer", "ModelPricer": "pricers.model_pricer",
     "LogSvParams": "pricers.logsv.logsv_params",

@@ -211,6 +211,9 @@ def _declare(L: C.CDLL) -> None:
                                               pf64, pf64], i32),
         "svmc_hawkesjd_chain_price_tilted": ([vp, pf64, pf64, i32, pf64, pi8, psz, pf64, i32, u64, u32, pf64, i32, i32, pf64, pf64,
                                               pf64], i32),
+        "svmc_hawkesjd_chain_cond": ([vp, vp, vp, sz, i32, C.POINTER(i32), pf64, pf64, f64, u64, u32, u64, u32, vp, vp, pf64, vp], i32),
+        "svmc_hawkesjd_chain_price_cmc": ([vp, pf64, pf64, pf64, i32, pf64, pi8, psz, pf64, i32, i32, u64, u32, pf64, pf64, pf64], i32),
+        "svmc_hawkesjd_chain_price_cmc_greeks": ([vp, pf64, pf64, pf64, i32, pf64, pi8, psz, pf64, i32, i32, u64, u32, pf64, pf64], i32),
         "svmc_greeks_payoff_workspace_bytes": ([sz, i32, sz, i32, psz], i32),
         "svmc_greeks_payoff_chain": ([C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), sz, pf64, pf64, i32, pf64, pi8, psz, i32, pf64, vp,
                                       pf64, pf64, vp, sz, vp], i32),

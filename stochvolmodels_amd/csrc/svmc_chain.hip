@@ -1191,6 +1191,42 @@ int svmc_hawkesjd_chain_price_tilted(svmc_session_t session, const double *ttms_
     return SVMC_OK;
 }
 
+// conditional Monte Carlo for the Hawkes jump-diffusion (row f16): chain_price_cmc on the session's x / vol / qvar as (mu, lambda_p,
+// lambda_m); every cv row is one double (hawkes_cond_step_from), the tail is the one of rows f11 / f13
+int svmc_hawkesjd_chain_price_cmc(svmc_session_t session, const double *ttms_host, const double *forwards_host,
+                                  const double *discfactors_host, int n_expiries, const double *strikes_host, const int8_t *types_host,
+                                  const size_t *strike_offsets_host, const double *params_host, int nb_steps_per_year, int recenter,
+                                  uint64_t seed, uint32_t call_id, double *prices_host, double *stderrs_host, double *stats_host)
+{
+    const char *fn = "svmc_hawkesjd_chain_price_cmc";
+    if (int rc = hawkes_check_params(fn, params_host)) return rc;
+    Session *s = reinterpret_cast<Session *>(session);
+    const ChainView c = {n_expiries, ttms_host, forwards_host, discfactors_host, strikes_host, types_host, strike_offsets_host};
+    return chain_price_cmc(fn, s, c, nb_steps_per_year, recenter, prices_host, stderrs_host, nullptr, stats_host,
+                           [&](const int *nbs, const double *dts, double *mu_snap, double *cv_snap) {
+        return hawkes_cond_step_from(fn, params_host, s->x, s->vol, s->qvar, s->n_path, c.m, nbs, dts, seed, call_id, s->path_offset,
+                                     mu_snap, cv_snap, s->stream);
+    });
+}
+
+int svmc_hawkesjd_chain_price_cmc_greeks(svmc_session_t session, const double *ttms_host, const double *forwards_host,
+                                         const double *discfactors_host, int n_expiries, const double *strikes_host,
+                                         const int8_t *types_host, const size_t *strike_offsets_host, const double *params_host,
+                                         int nb_steps_per_year, int recenter, uint64_t seed, uint32_t call_id, double *greeks_host,
+                                         double *stats_host)
+{
+    const char *fn = "svmc_hawkesjd_chain_price_cmc_greeks";
+    SVMC_REQUIRE(greeks_host != nullptr && strike_offsets_host != nullptr && n_expiries >= 1, std::string(fn) + ": null pointer or no expiries");
+    if (int rc = hawkes_check_params(fn, params_host)) return rc;
+    Session *s = reinterpret_cast<Session *>(session);
+    const ChainView c = {n_expiries, ttms_host, forwards_host, discfactors_host, strikes_host, types_host, strike_offsets_host};
+    return chain_price_cmc(fn, s, c, nb_steps_per_year, recenter, greeks_host, greeks_host + strike_offsets_host[n_expiries], greeks_host,
+                           stats_host, [&](const int *nbs, const double *dts, double *mu_snap, double *cv_snap) {
+        return hawkes_cond_step_from(fn, params_host, s->x, s->vol, s->qvar, s->n_path, c.m, nbs, dts, seed, call_id, s->path_offset,
+                                     mu_snap, cv_snap, s->stream);
+    });
+}
+
 }  // extern "C"
 
 // ---- many jobs of one chain (svmc_logsv_chain_price_many / svmc_heston_chain_price_many / svmc_hawkesjd_chain_price[_tilted]_many)

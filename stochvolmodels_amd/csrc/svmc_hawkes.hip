@@ -8,6 +8,8 @@
 //   hawkesjd_chain_rng_many_kernel  the same body for J independent jobs of one chain (blockIdx.y = job): each job's model, start
 //                              intensities, step constants and Philox key from a device table, its expiries to snapshot rows
 //                              j m + i; job j's bits are those of hawkesjd_chain_rng_kernel on its parameters and stream
+//   hawkes_chain_cond_kernel   conditional Monte Carlo: the same step without the diffusion's normal on the state
+//                              (mu, lambda_p, lambda_m), streams 9 and 10, no table and no LDS; per expiry a mu row and a cv row
 //   hawkes_mgf_grid_batch_kernel  one lane per transform-grid point of up to 16 parameter sets per launch (blockIdx.y = set;
 //                              one set, or the base point and bumped vectors of a calibration's finite-difference gradient):
 //                              the three complex Riccati ODEs of solve_ode_for_a (:582-640) with the DOP853 pair of
@@ -254,6 +256,103 @@ __global__ __launch_bounds__(HAWKES_BLOCK) void hawkesjd_chain_rng_many_kernel(s
                                                                               double *__restrict__ partials)
 {
     hawkes_body(n, HawkesTable{cs, jobs, steps}, path_offset, x_snap, partials);
+}
+
+// ---- conditional Monte Carlo (include/svmc.h).  The diffusion sigma w0 is independent of both jump processes
+// and both intensities, so given a path's jumps its discretised log-return is N(mu, cv) with ONE cv for every path: the lane
+// carries (mu, lambda_p, lambda_m), draws no normal, stages no table and uses no LDS; cv_i is a kernel argument per slice, formed
+// on the host.  Streams 9 and 10 (svmc_rng.h): the jump uniforms of TWO steps per call of stream 9, the jump sizes as stream 7's.
+#ifndef SVMC_HAWKES_COND_BLOCK
+#define SVMC_HAWKES_COND_BLOCK 256         // nothing is staged per block; an A/B build at 512: profiles/hawkes_cmc_bench.json
+#endif
+constexpr int HAWKES_COND_BLOCK = SVMC_HAWKES_COND_BLOCK;
+constexpr uint32_t HAWKES_COND_STREAM = 9u, HAWKES_COND_JUMP_STREAM = 10u;
+
+struct HawkesCondSlices {
+    HawkesStep c[HAWKES_MAX_SLICES];       // sigma_sqrt_dt is not read
+    double cv[HAWKES_MAX_SLICES];          // the conditional variance at the end of slice i
+    int nb_steps[HAWKES_MAX_SLICES];
+    int m;
+};
+
+// one time step on the words (wp, wm) of stream 9: hawkes_step's statements without the diffusion's normal
+__device__ __forceinline__ void hawkes_cond_step(const HawkesModel &md, const HawkesStep &c, const PhiloxLane &lane_j, uint32_t s,
+                                                 uint32_t wp, uint32_t wm, double &mu, double &lp, double &lm)
+{
+    // no implicit contraction: the step is inlined as the first and the second step of a call and as a slice's head and tail, and
+    // which products the compiler would fuse with a following add depends on the code around each copy -- a chain must give the
+    // same bits however it is cut into slices and launches
+#pragma clang fp contract(off)
+    const double up = uniform_32(wp), um = uniform_32(wm);
+    const double hp = lp * c.dt, hm = lm * c.dt;
+    bool jp = (1.0 - up) < hp, jm = (1.0 - um) < hm;          // -ln u >= 1 - u: no jump without this (1 - u is exact)
+    if (jp) jp = neg_log(up) < hp;
+    if (jm) jm = neg_log(um) < hm;
+    double jump_p = 0.0, jump_m = 0.0;
+    if (jp || jm) {                                            // rare and divergent: the jump sizes of this step, stream 10
+        uint32_t e[4];
+        philox_draw(lane_j, s, e);
+        if (jp) jump_p = md.shift_p + md.mean_p * neg_log(uniform_32(e[0]));
+        if (jm) jump_m = md.shift_m - md.neg_mean_m * neg_log(uniform_32(e[1]));
+    }
+    const double drift = (c.drift_dt - c.comp_p_dt * lp) - c.comp_m_dt * lm;
+    mu = ((mu + drift) + jump_p) + jump_m;
+    const double load_p = md.beta1_p * jump_p + md.beta2_p * jump_m;
+    const double load_m = md.beta1_m * jump_p + md.beta2_m * jump_m;
+    lp = (lp + c.kappa_p_dt * (md.theta_p - lp)) + load_p;
+    lm = (lm + c.kappa_m_dt * (md.theta_m - lm)) + load_m;
+}
+
+// All slices of a launch.  Chain-global step s reads words 2 (s & 1), 2 (s & 1) + 1 of stream 9's call s >> 1; every branch on s
+// is wave-uniform.  A slice that begins on an odd step takes the second pair of the call its predecessor's tail drew -- carried
+// in r when that slice ran in this launch, re-drawn when the launch itself begins on the odd step.
+__global__ __launch_bounds__(HAWKES_COND_BLOCK) void hawkes_chain_cond_kernel(double *__restrict__ mu_state, double *__restrict__ lam_p,
+                                                                             double *__restrict__ lam_m, size_t n, HawkesCondSlices cs,
+                                                                             HawkesModel md, uint64_t seed, uint32_t c3,
+                                                                             uint64_t path_offset, uint32_t step_offset,
+                                                                             double *__restrict__ mu_snap, double *__restrict__ cv_snap,
+                                                                             StateInit init)
+{
+    const size_t p = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (p >= n) return;                                        // no barrier and no cross-lane traffic below
+    double mu, lp, lm;
+    if (init.uniform) {                                        // wave-uniform
+        mu = init.x0;
+        lp = init.vol0;
+        lm = init.qvar0;
+    } else {
+        mu = mu_state[p];
+        lp = lam_p[p];
+        lm = lam_m[p];
+    }
+    const PhiloxLane lane = philox_prepare(seed, c3 | HAWKES_COND_STREAM, path_offset + p);
+    const PhiloxLane lane_j = philox_prepare(seed, c3 | HAWKES_COND_JUMP_STREAM, path_offset + p);
+    uint32_t r[4] = {0u, 0u, 0u, 0u};
+    uint32_t s = step_offset;
+    for (int i = 0; i < cs.m; ++i) {
+        const uint32_t end = s + static_cast<uint32_t>(cs.nb_steps[i]);
+        const HawkesStep c = cs.c[i];
+        if (s < end && (s & 1u)) {                             // head: the second pair of call s >> 1
+            if (s == step_offset) philox_draw(lane, s >> 1, r);
+            hawkes_cond_step(md, c, lane_j, s, r[2], r[3], mu, lp, lm);
+            ++s;
+        }
+        for (; s + 1u < end; s += 2u) {                        // the hot loop: one call, its two steps
+            philox_draw(lane, s >> 1, r);
+            hawkes_cond_step(md, c, lane_j, s, r[0], r[1], mu, lp, lm);
+            hawkes_cond_step(md, c, lane_j, s + 1u, r[2], r[3], mu, lp, lm);
+        }
+        if (s < end) {                                         // tail: the first pair; the second waits in r for the next slice
+            philox_draw(lane, s >> 1, r);
+            hawkes_cond_step(md, c, lane_j, s, r[0], r[1], mu, lp, lm);
+            ++s;
+        }
+        if (mu_snap != nullptr) mu_snap[static_cast<size_t>(i) * n + p] = mu;
+        if (cv_snap != nullptr) cv_snap[static_cast<size_t>(i) * n + p] = cs.cv[i];
+    }
+    mu_state[p] = mu;
+    lam_p[p] = lp;
+    lam_m[p] = lm;
 }
 
 int check_params(const char *fn, const double *p)
@@ -541,6 +640,67 @@ int hawkes_step_partials(const double *params_host, double *x, double *lam_p, do
                                          0, x_snapshots, nullptr, spot_sums, workspace, workspace_bytes, stream, fill, launch);
 }
 
+// ---- conditional Monte Carlo: the stepping of svmc_hawkesjd_chain_cond (init not uniform: the state arrays) and of the fused
+// drivers of svmc_chain.hip (hawkes_cond_step_from: from (0, lambda_p, lambda_m)).  Every check comes before the first launch;
+// launches of at most 16 slices carry the step offset and the variance from one to the next.
+static int hawkes_cond_step_chain(const char *fn, const StateInit &init, const double *params_host, double *mu, double *lam_p,
+                                  double *lam_m, size_t n_path, int n_slices, const int *nb_steps_host, const double *dts_host,
+                                  double cv_start, uint64_t seed, uint32_t call_id, uint64_t path_offset, uint32_t step_offset,
+                                  double *mu_snapshots, double *cv_snapshots, double *cvs_host, hipStream_t stream)
+{
+#pragma clang fp contract(off)             // cv_i is rounded product by product and sum by sum, on any host
+    if (int rc = check_params(fn, params_host)) return rc;
+    SVMC_REQUIRE(mu && lam_p && lam_m, std::string(fn) + ": null state array");
+    SVMC_REQUIRE(n_path > 0, std::string(fn) + ": n_path must be positive");
+    SVMC_REQUIRE(n_slices >= 1 && nb_steps_host && dts_host, std::string(fn) + ": null grids / no slices");
+    for (int i = 0; i < n_slices; ++i)
+        SVMC_REQUIRE(nb_steps_host[i] >= 0 && dts_host[i] > 0.0 && std::isfinite(dts_host[i]),
+                     std::string(fn) + ": need nb_steps >= 0 and dt > 0");
+    SVMC_REQUIRE(call_id < (1u << 24), std::string(fn) + ": call_id must fit 24 bits");
+    SVMC_REQUIRE(cv_start >= 0.0 && std::isfinite(cv_start), std::string(fn) + ": cv_start must be non-negative and finite");
+    const HawkesModel md = make_hawkes_model(params_host);
+    const double sigma2 = params_host[P_SIGMA] * params_host[P_SIGMA];
+    double cv = cv_start;
+    for (int i0 = 0; i0 < n_slices; i0 += HAWKES_MAX_SLICES) {
+        HawkesCondSlices cs;
+        cs.m = (n_slices - i0 < HAWKES_MAX_SLICES) ? (n_slices - i0) : HAWKES_MAX_SLICES;
+        uint32_t steps = 0;
+        for (int i = 0; i < HAWKES_MAX_SLICES; ++i) {
+            const int j = (i < cs.m) ? i0 + i : i0;            // unused entries repeat a valid one
+            cs.c[i] = make_hawkes_step(dts_host[j], params_host);
+            cs.nb_steps[i] = (i < cs.m) ? nb_steps_host[j] : 0;
+            if (i < cs.m) {
+                const double per_step = sigma2 * dts_host[j];
+                const double added = static_cast<double>(nb_steps_host[j]) * per_step;
+                cv = cv + added;
+                if (cvs_host != nullptr) cvs_host[j] = cv;
+            }
+            cs.cv[i] = cv;
+            steps += static_cast<uint32_t>(cs.nb_steps[i]);
+        }
+        const size_t row = static_cast<size_t>(i0) * n_path;
+        hipLaunchKernelGGL(hawkes_chain_cond_kernel, dim3(static_cast<unsigned>((n_path + HAWKES_COND_BLOCK - 1) / HAWKES_COND_BLOCK)),
+                           dim3(HAWKES_COND_BLOCK), 0, stream, mu, lam_p, lam_m, n_path, cs, md, seed, call_id << 8, path_offset,
+                           step_offset, mu_snapshots ? mu_snapshots + row : nullptr, cv_snapshots ? cv_snapshots + row : nullptr,
+                           (i0 == 0) ? init : StateInit());
+        if (int rc = check_launch(fn)) return rc;
+        step_offset += steps;
+    }
+    return SVMC_OK;
+}
+
+int hawkes_cond_step_from(const char *fn, const double *params_host, double *mu, double *lam_p, double *lam_m, size_t n_path,
+                          int n_slices, const int *nb_steps_host, const double *dts_host, uint64_t seed, uint32_t call_id,
+                          uint64_t path_offset, double *mu_snapshots, double *cv_snapshots, hipStream_t stream)
+{
+    if (int rc = check_params(fn, params_host)) return rc;
+    const StateInit init = {1, 0.0, params_host[P_LAMBDA_P], params_host[P_LAMBDA_M]};
+    return hawkes_cond_step_chain(fn, init, params_host, mu, lam_p, lam_m, n_path, n_slices, nb_steps_host, dts_host, 0.0, seed,
+                                  call_id, path_offset, 0u, mu_snapshots, cv_snapshots, nullptr, stream);
+}
+
+int hawkes_check_params(const char *fn, const double *params_host) { return check_params(fn, params_host); }
+
 // ---- many jobs of one chain (svmc_chain.hip's svmc_hawkesjd_chain_price_many / _tilted_many)
 
 size_t hawkes_many_table_bytes(int n_jobs, int n_slices)
@@ -623,6 +783,16 @@ int svmc_hawkesjd_terminal_rng(double *x, double *lambda_p, double *lambda_m, si
     hipLaunchKernelGGL(hawkesjd_rng_kernel, dim3(hawkes_grid(n_path)), dim3(HAWKES_BLOCK), 0, as_stream(stream), x, lambda_p, lambda_m,
                        n_path, cs, make_hawkes_model(params_host), seed, call_id << 8, path_offset, step_offset);
     return check_launch(fn);
+}
+
+int svmc_hawkesjd_chain_cond(double *mu, double *lambda_p, double *lambda_m, size_t n_path, int n_slices, const int *nb_steps_host,
+                             const double *dts_host, const double *params_host, double cv_start, uint64_t seed, uint32_t call_id,
+                             uint64_t path_offset, uint32_t step_offset, double *mu_snapshots, double *cv_snapshots, double *cvs_host,
+                             svmc_stream_t stream)
+{
+    return hawkes_cond_step_chain("svmc_hawkesjd_chain_cond", StateInit(), params_host, mu, lambda_p, lambda_m, n_path, n_slices,
+                                  nb_steps_host, dts_host, cv_start, seed, call_id, path_offset, step_offset, mu_snapshots,
+                                  cv_snapshots, cvs_host, as_stream(stream));
 }
 
 int svmc_hawkesjd_mgf_grid(const double *phi, const double *psi, size_t n_grid, double ttm, const double *params_host, double *a,

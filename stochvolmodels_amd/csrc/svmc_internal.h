@@ -146,6 +146,12 @@ int heston_cmc_step_from(double var0, double *mu, double *cv, double *var, doubl
                          const int *nb_steps_host, const double *dts_host, double theta, double kappa, double rho, double volvol,
                          uint64_t seed, uint32_t call_id, uint64_t path_offset, double *mu_snapshots, double *cv_snapshots,
                          hipStream_t stream);
+// svmc_hawkes.hip: the Hawkes conditional stepping (row f16) from (0, lambda_p, lambda_m) into the mu / cv snapshot rows -- every
+// cv row one double, formed on the host -- and the parameter block's checks (made by the fused drivers before anything else)
+int hawkes_check_params(const char *fn, const double *params_host);
+int hawkes_cond_step_from(const char *fn, const double *params_host, double *mu, double *lam_p, double *lam_m, size_t n_path,
+                          int n_slices, const int *nb_steps_host, const double *dts_host, uint64_t seed, uint32_t call_id,
+                          uint64_t path_offset, double *mu_snapshots, double *cv_snapshots, hipStream_t stream);
 int cmc_tail(const char *fn, const double *const *mu_snapshots_host, const double *const *cv_snapshots_host, size_t n_path,
              const double *forwards_host, const double *discfactors_host, int n_expiries, const double *strikes_host,
              const int8_t *types_host, const size_t *strike_offsets_host, int recenter, double *prices_host, double *stderrs_host,

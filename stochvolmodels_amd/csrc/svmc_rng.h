@@ -23,6 +23,9 @@
 //   Conditional Monte Carlo (svmc_cmc.hip): stream 8, ONE normal per step -- a call carries FOUR steps, laid out as stream 5's
 //   uniforms are: step s (chain-global) takes z(r[s & 3]) of the call at index s >> 2, so a slice may begin or end anywhere inside
 //   a call without changing what a (path, step) sees.  Streams 0 .. 7 are untouched: the stream version stays 4.
+//   Conditional Monte Carlo for Hawkes (svmc_hawkes.hip hawkes_chain_cond_kernel): stream 9, the jump uniforms of TWO steps per call
+//   -- step s takes u_p, u_m from words 2 (s & 1), 2 (s & 1) + 1 of the call at index s >> 1 -- and stream 10 as stream 7: the call
+//   at index s, drawn lazily, E_p and E_m from words 0 and 1.  Streams 0 .. 8 are untouched.
 // Resolution: a normal carries 32 random bits (as in version 2, whose Box-Muller pair spent 32 on the radius and 32 on
 // the angle); the lattice is 2^-32 in probability, symmetric about 0 (every magnitude 1 .. 2^31 - 1 with both signs, two words
 // at 0), largest |z| = -Phi^-1(2^-32) = 6.23 (truncated mass 4.7e-10 per normal).  The cubic deviates from the exact inverse CDF by at most SVMC_ICDF_MAX_ABS_ERROR (7.431e-10,

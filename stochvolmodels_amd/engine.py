@@ -715,6 +715,52 @@ class HipEngine:
             params.ctypes.data_as(C.POINTER(C.c_double)), int(seed), int(call_id), self.path_offset, int(step_offset),
             self.stream)))
 
+    # ---- conditional Monte Carlo for the Hawkes jump-diffusion (include/svmc.h): the state is (mu, lambda_p,
+    # lambda_m) in x / vol / qvar; the conditional variance is one double per expiry, formed on the host
+    def hawkesjd_chain_cond(self, nb_steps: Sequence[int], dts: Sequence[float], params: np.ndarray, seed: int, call_id: int,
+                            step_offset: int = 0, cv_start: float = 0.0, mu_row: Optional[int] = 0,
+                            cv_row: Optional[int] = None) -> np.ndarray:
+        """svmc_hawkesjd_chain_cond on this engine's (mu, lambda_p, lambda_m): expiry i's mu goes to snapshot row mu_row + i and its
+        cv (the same double on every path) to row cv_row + i (default: right after the mu rows; mu_row=None: no snapshots at all).
+        Returns the host cv_i [n_slices]; a later call continues the chain with step_offset = the steps so far and cv_start = the
+        last of them"""
+        n = len(nb_steps)
+        nb = np.ascontiguousarray(nb_steps, dtype=np.int32)
+        dt, params = np.ascontiguousarray(dts, dtype=np.float64), np.ascontiguousarray(params, dtype=np.float64)
+        if dt.size != n:
+            raise ValueError("one dt per slice")
+        mu_ptr = cv_ptr = None
+        if mu_row is not None:
+            cv_row = mu_row + n if cv_row is None else cv_row
+            mu_ptr, cv_ptr, _ = self._cmc_rows(n, mu_row, cv_row, None)
+        cvs = np.empty(max(n, 1))
+        dp = C.POINTER(C.c_double)
+        self._timed("hawkes_chain_cond_kernel", lambda: _lib.check(self.lib.svmc_hawkesjd_chain_cond(
+            self.x.ptr, self.vol.ptr, self.qvar.ptr, self.n_path, n, nb.ctypes.data_as(C.POINTER(C.c_int)), dt.ctypes.data_as(dp),
+            params.ctypes.data_as(dp), float(cv_start), int(seed), int(call_id), self.path_offset, int(step_offset), mu_ptr, cv_ptr,
+            cvs.ctypes.data_as(dp), self.stream)))
+        return cvs[:n]
+
+    def price_hawkesjd_chain_cmc_fused(self, ch: dict, params: np.ndarray, nb_steps_per_year: int, recenter: bool, seed: int,
+                                       call_id: int):
+        """hawkesjd_mc_chain_pricer_conditional as ONE svmc_hawkesjd_chain_price_cmc call on this engine's state; returns (prices,
+        stderrs, stats) cut into expiries"""
+        params = np.ascontiguousarray(params, dtype=np.float64)
+        return self._fused_cmc_call(ch, lambda sess, p, e, st: self.lib.svmc_hawkesjd_chain_price_cmc(
+            sess, ch["ttms"], ch["forwards"], ch["discfactors"], ch["m"], ch["strikes"], ch["codes"], ch["offsets"],
+            params.ctypes.data_as(C.POINTER(C.c_double)), int(nb_steps_per_year), int(bool(recenter)), int(seed), int(call_id), p, e,
+            st), "hawkes_chain_cond_kernel")
+
+    def price_hawkesjd_chain_cmc_greeks_fused(self, ch: dict, params: np.ndarray, nb_steps_per_year: int, recenter: bool, seed: int,
+                                              call_id: int):
+        """hawkesjd_mc_chain_greeks_conditional as ONE svmc_hawkesjd_chain_price_cmc_greeks call on this engine's state; returns
+        (fields, stats) as conditional_greeks"""
+        params = np.ascontiguousarray(params, dtype=np.float64)
+        return self._fused_cmc_greeks_call(ch, lambda sess, g, st: self.lib.svmc_hawkesjd_chain_price_cmc_greeks(
+            sess, ch["ttms"], ch["forwards"], ch["discfactors"], ch["m"], ch["strikes"], ch["codes"], ch["offsets"],
+            params.ctypes.data_as(C.POINTER(C.c_double)), int(nb_steps_per_year), int(bool(recenter)), int(seed), int(call_id), g, st),
+            "hawkes_chain_cond_kernel")
+
     # ---- state ----------------------------------------------------------------------------------
     def fill_state(self, x0: float, vol0: float, qvar0: float) -> None:
         _lib.check(self.lib.svmc_fill_state(self.x.ptr, self.vol.ptr, self.qvar.ptr, self.n_path,

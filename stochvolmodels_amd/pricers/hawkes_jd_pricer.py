@@ -28,6 +28,11 @@ Many independent Monte Carlo jobs of one chain (hawkesjd_mc_chain_pricer_many, h
 and the pricer methods over them; not in the reference): every job has its own parameter set -- both start intensities included --
 and its own random stream, ONE launch steps them all (hawkesjd_chain_rng_many_kernel), and each job's results are bit-equal to
 its single call.
+Conditional Monte Carlo (hawkesjd_mc_chain_pricer_conditional, hawkesjd_mc_chain_greeks_conditional and the pricer methods over them;
+not in the reference): the diffusion is independent of the jumps and the intensities, so each path carries the conditional mean of
+its log-return, the variance sigma^2 T is one number per expiry, and a path contributes a Black-76 price, its delta and gammas and
+the density at the strike instead of a payoff (hawkes_chain_cond_kernel, streams 9 and 10; the tails of the LogSV / Heston
+conditional pricers).
 The reference's quirks are kept: `risk_premia_gamma` is accepted and unused by hawkesjd_mc_chain_pricer, `is_spot_measure` is ignored
 by it, and a variable_type other than LOG_RETURN raises (the reference would price the log-return as a variance).  Under the
 risk-premia kernel: the forwards follow zip(ttms, forwards) (entries beyond the shorter stay 1.0), discfactors are ignored
@@ -56,6 +61,7 @@ from ..utils import mgf_pricer as mgfp
 from ..utils.calibration import ImpliedVolObjective, chain_calibration_weights
 from ..utils.config import VariableType
 from ..utils.funcs import next_rng_call, time_grid_steps, timer, to_flat_np_array
+from .logsv_pricer import check_conditional_request, conditional_greeks_shaped, conditional_log_return_pdf
 from .model_pricer import ModelParams, ModelPricer
 
 MAX_PHI = 500
@@ -165,6 +171,35 @@ class HawkesJDPricer(ModelPricer):
                                         discfactors=option_chain.discfactors, strikes_ttms=option_chain.strikes_ttms,
                                         optiontypes_ttms=option_chain.optiontypes_ttms, nb_path=nb_path,
                                         **params.to_dict(), **kwargs)
+
+    def model_mc_price_chain_conditional(self, option_chain: OptionChain, params: HawkesJDParams, nb_path: int = 100000, **kwargs):
+        """model_mc_price_chain by conditional Monte Carlo (hawkesjd_mc_chain_pricer_conditional); seed=, nb_steps_per_year=,
+        recenter= and return_stats= are passed on"""
+        return hawkesjd_mc_chain_pricer_conditional(ttms=option_chain.ttms, forwards=option_chain.forwards,
+                                                    discfactors=option_chain.discfactors, strikes_ttms=option_chain.strikes_ttms,
+                                                    optiontypes_ttms=option_chain.optiontypes_ttms, nb_path=nb_path,
+                                                    **params.to_dict(), **kwargs)
+
+    def model_mc_chain_greeks_conditional(self, option_chain: OptionChain, params: HawkesJDParams, nb_path: int = 100000, **kwargs
+                                          ) -> dict:
+        """model_mc_price_chain_conditional with delta, dual delta, gamma and dual gamma (hawkesjd_mc_chain_greeks_conditional)"""
+        return hawkesjd_mc_chain_greeks_conditional(ttms=option_chain.ttms, forwards=option_chain.forwards,
+                                                    discfactors=option_chain.discfactors, strikes_ttms=option_chain.strikes_ttms,
+                                                    optiontypes_ttms=option_chain.optiontypes_ttms, nb_path=nb_path,
+                                                    **params.to_dict(), **kwargs)
+
+    def get_log_return_mc_pdf_conditional(self, params: HawkesJDParams, ttm: float, x_grid: np.ndarray, nb_path: int = 100000,
+                                          seed: Optional[int] = None, recenter: bool = False, return_stderr: bool = False,
+                                          nb_steps_per_year: int = NB_STEPS_PER_YEAR):
+        """the density of the simulated log-return at x_grid from the conditional estimator's dual gamma, without a bandwidth
+        (logsv_pricer.conditional_log_return_pdf): each path adds a Gaussian of variance sigma^2 ttm around its jump path.
+        UN-NORMALISED: it integrates by itself to the share of the kept paths (1 when none is dropped; 0 at sigma = 0, where every
+        path is a point mass).  recenter=False: the density of the simulated x itself.  With return_stderr=True (pdf, its standard
+        error)."""
+        def route(**chain):
+            return hawkesjd_mc_chain_greeks_conditional(nb_path=nb_path, nb_steps_per_year=nb_steps_per_year, seed=seed,
+                                                        recenter=recenter, **_model_kwargs(params), **chain)
+        return conditional_log_return_pdf(route, ttm, x_grid, return_stderr)
 
     def price_chain_batch(self, option_chain: OptionChain, params_list: Sequence[HawkesJDParams], is_spot_measure: bool = True,
                           **kwargs) -> List[List[np.ndarray]]:
@@ -672,6 +707,65 @@ def hawkesjd_mc_chain_pricer(ttms: np.ndarray, forwards: np.ndarray, discfactors
                           [option_type_codes(t) for t in optiontypes_ttms])
     prices, stderrs = eng.price_hawkesjd_chain_fused(ch, block, int(nb_steps_per_year), LOG_RETURN, rng_seed, call_id)
     return chain_shaped(prices, strikes_ttms), chain_shaped(stderrs, strikes_ttms)
+
+
+def hawkesjd_mc_chain_pricer_conditional(ttms: np.ndarray, forwards: np.ndarray, discfactors: np.ndarray,
+                                         strikes_ttms: Sequence[np.ndarray], optiontypes_ttms: Sequence[np.ndarray],
+                                         lambda_p: float, lambda_m: float, mu: float, sigma: float, shift_p: float, mean_p: float,
+                                         shift_m: float, mean_m: float, theta_p: float, kappa_p: float, beta1_p: float,
+                                         beta2_p: float, theta_m: float, kappa_m: float, beta1_m: float, beta2_m: float,
+                                         risk_premia_gamma: float = 0.0, nb_path: int = 100000,
+                                         variable_type: VariableType = VariableType.LOG_RETURN,
+                                         nb_steps_per_year: int = NB_STEPS_PER_YEAR, seed: Optional[int] = None, comm=None,
+                                         devices=None, recenter: bool = True, return_stats: bool = False):
+    """hawkesjd_mc_chain_pricer by CONDITIONAL Monte Carlo (include/svmc.h): the diffusion sigma w0 is independent
+    of the jumps and the intensities, so given a path's jumps the discretised log-return is Gaussian with one variance sigma^2 T for
+    every path, and each path contributes a Black-76 price instead of a payoff -- the same expectation for the same discretised
+    model, a smaller variance, no normal drawn (random streams 9 and 10, not the plain pricer's: the two are independent estimates
+    at equal seeds).  Same signature and (prices, stderrs) lists; return_stats=True adds per expiry the dict of
+    engine.CMC_STATS_FIELDS.  recenter=False prices against the unrecentred strikes.  risk_premia_gamma is accepted and unused, as
+    in the plain pricer.  'C' / 'P', LOG_RETURN and one GPU only (logsv_pricer.check_conditional_request).  Not in the reference
+    API."""
+    codes = check_conditional_request("hawkesjd_mc_chain_pricer_conditional", variable_type, comm, devices, optiontypes_ttms)
+    block = params_block(lambda_p=lambda_p, lambda_m=lambda_m, mu=mu, sigma=sigma, shift_p=shift_p, mean_p=mean_p,
+                         shift_m=shift_m, mean_m=mean_m, theta_p=theta_p, kappa_p=kappa_p, beta1_p=beta1_p, beta2_p=beta2_p,
+                         theta_m=theta_m, kappa_m=kappa_m, beta1_m=beta1_m, beta2_m=beta2_m)
+    rng_seed, call_id = next_rng_call(seed)
+    ch = marshalled_chain(ttms, forwards, discfactors, strikes_ttms, codes)
+    prices, stderrs, stats = get_engine(int(nb_path)).price_hawkesjd_chain_cmc_fused(ch, block, int(nb_steps_per_year), recenter,
+                                                                                     rng_seed, call_id)
+    out = (chain_shaped(prices, strikes_ttms), chain_shaped(stderrs, strikes_ttms))
+    return out + (stats,) if return_stats else out
+
+
+def hawkesjd_mc_chain_greeks_conditional(ttms: np.ndarray, forwards: np.ndarray, discfactors: np.ndarray,
+                                         strikes_ttms: Sequence[np.ndarray], optiontypes_ttms: Sequence[np.ndarray],
+                                         lambda_p: float, lambda_m: float, mu: float, sigma: float, shift_p: float, mean_p: float,
+                                         shift_m: float, mean_m: float, theta_p: float, kappa_p: float, beta1_p: float,
+                                         beta2_p: float, theta_m: float, kappa_m: float, beta1_m: float, beta2_m: float,
+                                         risk_premia_gamma: float = 0.0, nb_path: int = 100000,
+                                         variable_type: VariableType = VariableType.LOG_RETURN,
+                                         nb_steps_per_year: int = NB_STEPS_PER_YEAR, seed: Optional[int] = None, comm=None,
+                                         devices=None, recenter: bool = True, return_stats: bool = False,
+                                         wrt: Optional[Sequence[str]] = ()) -> dict:
+    """hawkesjd_mc_chain_pricer_conditional with the derivatives of its prices in the forward and the strike (DESIGN.md rows f13,
+    f16): a dict of chain-shaped lists -- price, stderr (bit-equal to hawkesjd_mc_chain_pricer_conditional at the same seed), delta,
+    dual_delta, gamma, dual_gamma, each with its _stderr -- and with return_stats=True "stats", per expiry the dict of
+    engine.CMC_GREEKS_STATS_FIELDS.  sigma = 0 makes every path a point mass: both gammas are then 0.  Parameter sensitivities are
+    not built: a non-empty wrt raises NotImplementedError.  Refusals: hawkesjd_mc_chain_pricer_conditional's.  Not in the reference
+    API."""
+    who = "hawkesjd_mc_chain_greeks_conditional"
+    codes = check_conditional_request(who, variable_type, comm, devices, optiontypes_ttms)
+    if wrt is None or isinstance(wrt, str) or len(wrt) > 0:
+        raise NotImplementedError(f"{who}: wrt=: parameter sensitivities of the Hawkes conditional estimator are not covered")
+    block = params_block(lambda_p=lambda_p, lambda_m=lambda_m, mu=mu, sigma=sigma, shift_p=shift_p, mean_p=mean_p,
+                         shift_m=shift_m, mean_m=mean_m, theta_p=theta_p, kappa_p=kappa_p, beta1_p=beta1_p, beta2_p=beta2_p,
+                         theta_m=theta_m, kappa_m=kappa_m, beta1_m=beta1_m, beta2_m=beta2_m)
+    rng_seed, call_id = next_rng_call(seed)
+    ch = marshalled_chain(ttms, forwards, discfactors, strikes_ttms, codes)
+    fields, stats = get_engine(int(nb_path)).price_hawkesjd_chain_cmc_greeks_fused(ch, block, int(nb_steps_per_year), recenter,
+                                                                                   rng_seed, call_id)
+    return conditional_greeks_shaped(fields, stats, strikes_ttms, return_stats)
 
 
 def hawkesjd_mc_chain_pricer_with_risk_premia_gammas(ttms: np.ndarray, forwards: np.ndarray, discfactors: np.ndarray,
