@@ -253,6 +253,55 @@ def load() -> C.CDLL:
     return _lib
 
 
+# ---- libsvmc_ext.so (C ABI: include/svmc_ext.h): the model-agnostic estimators beside the closed core ---------------------------
+EXT_LIB_PATH = os.environ.get("SVMC_EXT_LIB") or os.path.join(_PKG, "libsvmc_ext.so")
+_ext = None
+
+
+def _declare_ext(L: C.CDLL) -> None:
+    vp, sz, i32, f64 = C.c_void_p, C.c_size_t, C.c_int, C.c_double
+    psz, pvp, pf64, pi8 = C.POINTER(sz), C.POINTER(vp), C.POINTER(f64), C.POINTER(C.c_int8)
+    sig = {
+        "svmc_ext_version": ([], i32),
+        "svmc_tilted_cond_workspace_bytes": ([sz, i32, sz, i32, psz], i32),
+        "svmc_tilted_cond_payoff_chain": ([pvp, pvp, sz, pf64, i32, pf64, pi8, pf64, psz, pf64, i32, i32, pf64, pf64, pf64, vp, sz, vp],
+                                          i32),
+    }
+    for name, (argtypes, restype) in sig.items():
+        fn = getattr(L, name)          # AttributeError here = the .so does not match include/svmc_ext.h
+        fn.argtypes = argtypes
+        fn.restype = restype
+    L._svmc_ext_symbols = tuple(sig)
+
+
+def load_ext() -> C.CDLL:
+    """load libsvmc_ext.so once; raise loudly when it is not there (no fallback exists).  The core is loaded first, so that both
+    libraries resolve the one HIP runtime load() settles on."""
+    global _ext
+    load()
+    with _lock:
+        if _ext is None:
+            if not os.path.exists(EXT_LIB_PATH):
+                raise SvmcError(f"{EXT_LIB_PATH} is not built: run `python -m stochvolmodels_amd.build` (needs hipcc)")
+            L = C.CDLL(EXT_LIB_PATH, mode=C.RTLD_GLOBAL)
+            _declare_ext(L)
+            _ext = L
+    return _ext
+
+
+def check_ext(rc: int, what: str) -> None:
+    """map a status of libsvmc_ext.so, which keeps no message of its own, to check()'s exception types"""
+    if rc == OK:
+        return
+    if rc == ERR_UNKNOWN_PAYOFF:
+        raise ValueError("unknown option payoff code")
+    if rc == ERR_INVALID_ARGUMENT:
+        raise ValueError(f"{what}: invalid argument (include/svmc_ext.h lists the refusals)")
+    if rc == ERR_WORKSPACE:
+        raise SvmcError(f"{what}: workspace too small")
+    raise SvmcError(f"{what}: svmc status {rc}")
+
+
 def check(rc: int) -> None:
     """map an svmc status to the reference's exception types (utils/mc_payoffs.py:69-70,84)."""
     if rc == OK:

@@ -1,6 +1,7 @@
 """
-Build recipe of libsvmc.so (the only native artefact of the package): hipcc, gfx950 only, in-tree.  It also builds the
-test-only device probe tests/native/libsvmc_device_probe.so with the same flags.
+Build recipe of the package's native artefacts: libsvmc.so, the closed core (include/svmc.h), and libsvmc_ext.so, the estimators
+beside it (include/svmc_ext.h) -- hipcc, gfx950 only, in-tree.  It also builds the test-only device probe
+tests/native/libsvmc_device_probe.so with the same flags.
 
     python -m stochvolmodels_amd.build [--force]
 
@@ -37,6 +38,11 @@ ARCH = "gfx950"
 # package or its C ABI, built here so that it is compiled whenever the library is, with the library's flags
 PROBE_SRC = os.path.join(ROOT, "tests", "native", "device_math_probe.hip")
 PROBE_LIB = os.path.join(ROOT, "tests", "native", "libsvmc_device_probe.so")
+# libsvmc_ext.so (include/svmc_ext.h): the model-agnostic estimators beside the closed core -- one translation unit that links
+# nothing from libsvmc.so, built with the library's flags; its kernel metadata goes to a json of its own
+EXT_SRC = os.path.join(CSRC, "svmc_ext.hip")
+EXT_LIB = os.path.join(PKG, "libsvmc_ext.so")
+EXT_ISA_JSON = os.path.join(PKG, "libsvmc_ext.isa.json")
 
 
 def headers() -> list:
@@ -96,6 +102,33 @@ def build_device_probe(force: bool = False, verbose: bool = False) -> str:
     return PROBE_LIB
 
 
+def ext_is_stale() -> bool:
+    if not os.path.exists(EXT_LIB) or not os.path.exists(EXT_ISA_JSON):
+        return True
+    t = os.path.getmtime(EXT_LIB)
+    deps = [EXT_SRC, os.path.join(INCLUDE, "svmc.h"), os.path.join(INCLUDE, "svmc_ext.h"), __file__] + headers()
+    return any(os.path.getmtime(d) > t for d in deps)
+
+
+def build_ext(force: bool = False, verbose: bool = False) -> str:
+    """libsvmc_ext.so, rebuilt when its source, a header of csrc/, either public header or this file is newer; the kernel
+    metadata of the build (kernel_metadata) goes to libsvmc_ext.isa.json in libsvmc.isa.json's {"metadata": ...} form"""
+    if not force and not ext_is_stale():
+        return EXT_LIB
+    with tempfile.TemporaryDirectory(prefix="svmc_ext_build_") as tmp:
+        cmd = [hipcc()] + flags() + ["--save-temps", EXT_SRC, "-o", EXT_LIB]
+        if verbose:
+            print(" ".join(cmd))
+        res = subprocess.run(cmd, capture_output=True, text=True, cwd=tmp)
+        if res.returncode != 0:
+            raise RuntimeError("hipcc failed on svmc_ext.hip:\n" + res.stdout + res.stderr)
+        if verbose and res.stderr:
+            print(res.stderr)
+        with open(EXT_ISA_JSON, "w") as fh:
+            json.dump({"lib_sha256": file_sha256(EXT_LIB), "flags": flags(), "metadata": kernel_metadata(tmp)}, fh, indent=1)
+    return EXT_LIB
+
+
 def file_sha256(path: str) -> str:
     h = hashlib.sha256()
     with open(path, "rb") as fh:
@@ -149,6 +182,7 @@ def write_isa_json(asm_dir: str) -> None:
 
 def build(force: bool = False, verbose: bool = False) -> str:
     build_device_probe(force, verbose)
+    build_ext(force, verbose)
     if not force and not is_stale() and os.path.exists(ISA_JSON):
         return LIB
     # --save-temps: the device assembly of this very compilation is kept for the histogram (temporaries in a scratch dir)

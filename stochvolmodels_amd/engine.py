@@ -361,6 +361,8 @@ TILTED_MAX_GAMMAS = 16         # SVMC_TILTED_MAX_GAMMAS
 TILTED_STATS_DOUBLES = 8       # SVMC_TILTED_STATS_DOUBLES
 TILTED_STATS_FIELDS = ("normalizer", "normalizer_stderr", "gamma_forward", "gamma_forward_stderr", "effective_sample_size",
                        "n_kept", "n_dropped", "sum_weights")
+# the conditional estimator under the kernel (include/svmc_ext.h, svmc_tilted_cond_payoff_chain): the same block, the same meanings
+TILTED_COND_STATS_FIELDS = TILTED_STATS_FIELDS
 
 
 # ---- conditional Monte Carlo (include/svmc.h, svmc_cmc_payoff_chain): the per-expiry statistics ----------------------------------
@@ -1169,6 +1171,65 @@ class HipEngine:
             ch["codes"], ch["offsets"], int(bool(recenter)), C.cast(res.ctypes.data, dp), C.cast(res.ctypes.data + res.strides[0], dp),
             stats.ctypes.data_as(dp), ws_ptr, nbytes.value, self.stream))
         return [res[0, sl] for sl in ch["slices"]], [res[1, sl] for sl in ch["slices"]], cmc_stats_dicts(stats)
+
+    # ---- conditional Monte Carlo under the exponential risk-premia kernel (include/svmc_ext.h): libsvmc_ext.so,
+    # the library beside the closed core -- caller-owned device rows, no session
+    def tilted_conditional_payoffs(self, forwards, strikes: Sequence[np.ndarray], codes: Sequence[np.ndarray], gammas,
+                                   recenter: bool = False, mu_rows: Optional[Sequence[int]] = None,
+                                   cv_rows: Optional[Sequence[int]] = None, shifts: Optional[Sequence[np.ndarray]] = None):
+        """the conditional estimator under exp(gamma x) (svmc_tilted_cond_payoff_chain, include/svmc_ext.h) on resident (mu, cv),
+        whichever generator left them: expiry i reads snapshot rows mu_rows[i] and cv_rows[i], or, with both None, the one expiry
+        reads the current state (x, cv).  codes: 0 ('C') / 1 ('P') per strike.  shifts: the host constant of every strike's sums
+        (default: the intrinsic value at the forward, as tilted_payoffs; any finite value gives the same estimate).  Returns as
+        tilted_payoffs: (prices [G][m] -> [K_i], stderrs the same, stats [G, m, TILTED_COND_STATS_FIELDS]); prices are undiscounted."""
+        ch = tilted_chain_arrays(forwards, strikes, codes, gammas)
+        m, K, G = ch["m"], ch["total"], ch["gammas"].size
+        if (mu_rows is None) != (cv_rows is None) or ((m != 1) if mu_rows is None else (len(mu_rows) != m or len(cv_rows) != m)):
+            raise ValueError("one mu row and one cv row per expiry (the current state serves one expiry)")
+        mus = [self.x.ptr] if mu_rows is None else [self.snapshot_ptr(r) for r in mu_rows]
+        cvs = [self.cv.ptr] if cv_rows is None else [self.snapshot_ptr(r) for r in cv_rows]
+        if shifts is None:
+            shifts = [payoff_shifts(k, c, float(f), LOG_RETURN) for k, c, f in zip(ch["strikes_ttms"], ch["codes_ttms"], ch["forwards"])]
+        sh = np.ascontiguousarray(np.concatenate([np.asarray(s, dtype=np.float64).ravel() for s in shifts])) if K else np.zeros(1)
+        if K and sh.size != K:
+            raise ValueError("one shift per strike")
+        ext = _lib.load_ext()
+        what = "svmc_tilted_cond_payoff_chain"
+        nbytes = C.c_size_t(0)
+        _lib.check_ext(ext.svmc_tilted_cond_workspace_bytes(self.n_path, m, K, G, C.byref(nbytes)), what)
+        ws_ptr, _ = self.alloc_sums((nbytes.value + 7) // 8, "tilted_cond_workspace")
+        prices, stderrs, stats = np.empty(max(G * K, 1)), np.empty(max(G * K, 1)), np.empty(G * m * TILTED_STATS_DOUBLES)
+        dp = C.POINTER(C.c_double)
+        self._timed("tilted_cond_payoff_kernel", lambda: _lib.check_ext(ext.svmc_tilted_cond_payoff_chain(
+            (C.c_void_p * m)(*mus), (C.c_void_p * m)(*cvs), self.n_path, ch["forwards"].ctypes.data_as(dp), m,
+            ch["strikes"].ctypes.data_as(dp), ch["codes"].ctypes.data_as(C.POINTER(C.c_int8)), sh.ctypes.data_as(dp),
+            ch["offs"].ctypes.data_as(C.POINTER(C.c_size_t)), ch["gammas"].ctypes.data_as(dp), G, int(bool(recenter)),
+            prices.ctypes.data_as(dp), stderrs.ctypes.data_as(dp), stats.ctypes.data_as(dp), ws_ptr, nbytes.value, self.stream), what))
+        return tilted_results(prices[:G * K], stderrs[:G * K], stats, ch)
+
+    def price_hawkesjd_chain_tilted_cond(self, ch: dict, params: np.ndarray, nb_steps_per_year: int, seed: int, call_id: int, gammas,
+                                         recenter: bool):
+        """the Hawkes chain by conditional Monte Carlo under the risk-premia kernel for every gamma from ONE stepping launch (ch:
+        tilted_chain_arrays with ttms): hawkesjd_chain_cond from the origin (0, lambda_p, lambda_m) into snapshot rows [0, m) (mu)
+        and [m, 2m) (cv), then tilted_conditional_payoffs on them.  TWO C calls: there is no fused session entry, because sessions
+        belong to the closed core (libsvmc.so, 143 entry points) and the tail lives in libsvmc_ext.so.  The step grid is the fused
+        drivers' (svmc_chain.hip expiry_grids), so the mu rows are those svmc_hawkesjd_chain_price_cmc steps at this seed."""
+        params = np.ascontiguousarray(params, dtype=np.float64)
+        if int(nb_steps_per_year) <= 0:
+            raise ValueError("nb_steps_per_year must be positive")
+        m = ch["m"]
+        nbs, dts, t0 = [], [], 0.0
+        for t in ch["ttms"]:
+            d = float(t) - t0
+            nb = int(d * float(int(nb_steps_per_year))) + 1
+            nbs.append(nb)
+            dts.append(d if nb == 1 else d / float(nb))
+            t0 = float(t)
+        self.fill_state(0.0, float(params[6]), float(params[11]))         # SVMC_HAWKESJD_PARAMS: lambda_p, lambda_m
+        self.hawkesjd_chain_cond(nbs, dts, params, seed, call_id, mu_row=0, cv_row=m)
+        return self.tilted_conditional_payoffs(ch["forwards"], [k.reshape(s) for k, s in zip(ch["strikes_ttms"], ch["shapes"])],
+                                               ch["codes_ttms"], gammas, recenter, mu_rows=list(range(m)),
+                                               cv_rows=list(range(m, 2 * m)))
 
     def _fused_cmc_call(self, ch: dict, call, kernel_name: str):
         res, stats = np.empty((2, max(ch["total"], 1))), np.empty((ch["m"], CMC_STATS_DOUBLES))

@@ -33,6 +33,10 @@ not in the reference): the diffusion is independent of the jumps and the intensi
 its log-return, the variance sigma^2 T is one number per expiry, and a path contributes a Black-76 price, its delta and gammas and
 the density at the strike instead of a payoff (hawkes_chain_cond_kernel, streams 9 and 10; the tails of the LogSV / Heston
 conditional pricers).
+Conditional Monte Carlo under the risk-premia kernel (hawkesjd_mc_chain_pricer_conditional_with_risk_premia(_gammas); not in the
+reference): the two rows above joined by the Esscher identity -- a path's weight exp(gamma mu + gamma^2 cv / 2) carries no diffusion
+noise and multiplies a Black-76 price at the forward shifted by gamma cv (include/svmc_ext.h, libsvmc_ext.so's
+tilted_cond_payoff_kernel on the rows hawkes_chain_cond_kernel leaves).
 The reference's quirks are kept: `risk_premia_gamma` is accepted and unused by hawkesjd_mc_chain_pricer, `is_spot_measure` is ignored
 by it, and a variable_type other than LOG_RETURN raises (the reference would price the log-return as a variance).  Under the
 risk-premia kernel: the forwards follow zip(ttms, forwards) (entries beyond the shorter stay 1.0), discfactors are ignored
@@ -346,6 +350,19 @@ class HawkesJDPricer(ModelPricer):
                                                          strikes_ttms=option_chain.strikes_ttms,
                                                          optiontypes_ttms=option_chain.optiontypes_ttms, nb_path=nb_path,
                                                          **params.to_dict(), **kwargs)
+
+    def model_mc_price_chain_conditional_with_risk_premia(self, option_chain: OptionChain, params: HawkesJDParams,
+                                                          nb_path: int = 100000, **kwargs):
+        """model_mc_price_chain_with_risk_premia by conditional Monte Carlo
+        (hawkesjd_mc_chain_pricer_conditional_with_risk_premia); extensions seed=, nb_steps_per_year=, recenter_forward=,
+        return_forwards="""
+        if params.risk_premia_gamma is None:
+            raise ValueError("risk_premia_gamma must be set for the risk-premia pricer")
+        return hawkesjd_mc_chain_pricer_conditional_with_risk_premia(ttms=option_chain.ttms, forwards=option_chain.forwards,
+                                                                     discfactors=option_chain.discfactors,
+                                                                     strikes_ttms=option_chain.strikes_ttms,
+                                                                     optiontypes_ttms=option_chain.optiontypes_ttms, nb_path=nb_path,
+                                                                     **params.to_dict(), **kwargs)
 
     def model_mc_price_chain_many(self, option_chain: OptionChain, params_list: Sequence[HawkesJDParams], nb_path: int = 100000,
                                   seeds: Optional[Sequence[int]] = None, nb_steps_per_year: int = NB_STEPS_PER_YEAR, **kwargs
@@ -827,6 +844,66 @@ def hawkesjd_mc_chain_pricer_with_risk_premia(ttms: np.ndarray, forwards: np.nda
                                                            nb_steps_per_year=nb_steps_per_year, seed=seed,
                                                            recenter_forward=recenter_forward, return_forwards=return_forwards,
                                                            **kwargs)
+    return tuple(o[0] for o in out)
+
+
+def hawkesjd_mc_chain_pricer_conditional_with_risk_premia_gammas(ttms: np.ndarray, forwards: np.ndarray, discfactors: np.ndarray,
+                                                                 strikes_ttms: Sequence[np.ndarray],
+                                                                 optiontypes_ttms: Sequence[np.ndarray], lambda_p: float,
+                                                                 lambda_m: float, mu: float, sigma: float, shift_p: float,
+                                                                 mean_p: float, shift_m: float, mean_m: float, theta_p: float,
+                                                                 kappa_p: float, beta1_p: float, beta2_p: float, theta_m: float,
+                                                                 kappa_m: float, beta1_m: float, beta2_m: float,
+                                                                 risk_premia_gammas: Sequence[float] = (0.0,),
+                                                                 nb_path: int = 100000,
+                                                                 variable_type: VariableType = VariableType.LOG_RETURN,
+                                                                 nb_steps_per_year: int = NB_STEPS_PER_YEAR,
+                                                                 seed: Optional[int] = None, recenter_forward: bool = False,
+                                                                 return_forwards: bool = False, comm=None, devices=None,
+                                                                 risk_premia_gamma=None):
+    """hawkesjd_mc_chain_pricer_with_risk_premia_gammas by CONDITIONAL Monte Carlo (include/svmc_ext.h): given a
+    path's jumps x ~ N(mu, sigma^2 T), and the Esscher identity turns exp(gamma x) payoff(x) into the weight
+    exp(gamma mu + gamma^2 cv / 2) -- no diffusion noise in it -- times a Black-76 price at the forward shifted by gamma cv.  The
+    paths are those of hawkesjd_mc_chain_pricer_conditional at this seed (streams 9 and 10 of (seed, call id): no normal is drawn,
+    and the mu rows are bit-equal to that pricer's), stepped ONCE for all gammas; then svmc_tilted_cond_payoff_chain on the
+    resident rows.  Two C calls, not one: sessions belong to the closed core, the tail to the library beside it.
+    Signature, return shapes and return_forwards= are hawkesjd_mc_chain_pricer_with_risk_premia_gammas's: (prices, stderrs), each
+    [gamma][expiry] in the strikes' shapes, and with return_forwards=True a third item [gamma] -> (normalizers, gamma_forwards,
+    stats [n_expiries, 8] in the order of engine.TILTED_COND_STATS_FIELDS).  Prices are UNDISCOUNTED: discfactors are accepted
+    and ignored.  recenter_forward: K + (mean F exp(mu + cv / 2) - F), the conditional pricer's recentring, the same number
+    whatever gamma is.  'C' / 'P' only (others: ValueError("not implemented")), LOG_RETURN only, one GPU only
+    (NotImplementedError), each refused before any engine is asked for.  risk_premia_gamma= is accepted and unused here.  Not in
+    the reference API."""
+    codes = check_conditional_request("hawkesjd_mc_chain_pricer_conditional_with_risk_premia", variable_type, comm, devices,
+                                      optiontypes_ttms)
+    strikes_ttms = [np.asarray(k, dtype=np.float64) for k in strikes_ttms]
+    ch = tilted_chain_arrays(forwards, strikes_ttms, codes, risk_premia_gammas, ttms=ttms)
+    block = params_block(lambda_p=lambda_p, lambda_m=lambda_m, mu=mu, sigma=sigma, shift_p=shift_p, mean_p=mean_p,
+                         shift_m=shift_m, mean_m=mean_m, theta_p=theta_p, kappa_p=kappa_p, beta1_p=beta1_p, beta2_p=beta2_p,
+                         theta_m=theta_m, kappa_m=kappa_m, beta1_m=beta1_m, beta2_m=beta2_m)
+    eng = get_engine(int(nb_path))
+    rng_seed, call_id = next_rng_call(seed)
+    prices, stderrs, stats = eng.price_hawkesjd_chain_tilted_cond(ch, block, int(nb_steps_per_year), rng_seed, call_id, ch["gammas"],
+                                                                  bool(recenter_forward))
+    if not return_forwards:
+        return prices, stderrs
+    return prices, stderrs, [(st[:, 0].copy(), st[:, 2].copy(), st) for st in stats]
+
+
+def hawkesjd_mc_chain_pricer_conditional_with_risk_premia(ttms: np.ndarray, forwards: np.ndarray, discfactors: np.ndarray,
+                                                          strikes_ttms: Sequence[np.ndarray], optiontypes_ttms: Sequence[np.ndarray],
+                                                          risk_premia_gamma: float = None, nb_path: int = 100000,
+                                                          nb_steps_per_year: int = NB_STEPS_PER_YEAR, seed: Optional[int] = None,
+                                                          recenter_forward: bool = False, return_forwards: bool = False, **kwargs):
+    """hawkesjd_mc_chain_pricer_conditional_with_risk_premia_gammas at ONE gamma, so the two agree bit for bit: (prices, stderrs)
+    per expiry, with return_forwards=True also (normalizers, gamma_forwards, stats).  kwargs: the model parameters (and
+    variable_type=, comm=, devices=) of that function."""
+    if risk_premia_gamma is None:
+        raise ValueError("risk_premia_gamma must be set for the risk-premia pricer")
+    out = hawkesjd_mc_chain_pricer_conditional_with_risk_premia_gammas(
+        ttms=ttms, forwards=forwards, discfactors=discfactors, strikes_ttms=strikes_ttms, optiontypes_ttms=optiontypes_ttms,
+        risk_premia_gammas=[risk_premia_gamma], nb_path=nb_path, nb_steps_per_year=nb_steps_per_year, seed=seed,
+        recenter_forward=recenter_forward, return_forwards=return_forwards, **kwargs)
     return tuple(o[0] for o in out)
 
 

@@ -90,6 +90,39 @@ def compute_mc_vars_payoff_conditional(mu: np.ndarray, cv: np.ndarray, ttm: floa
     return out + (stats[0],) if return_stats else out
 
 
+def compute_mc_vars_payoff_conditional_with_gamma(mu: np.ndarray, cv: np.ndarray, forward: float, strikes_ttm: np.ndarray,
+                                                  optiontypes_ttm: np.ndarray, risk_premia_gamma, recenter: bool = False,
+                                                  return_stats: bool = False,
+                                                  variable_type: VariableType = VariableType.LOG_RETURN):
+    """option prices under the exponential risk-premia kernel by conditional Monte Carlo from per-path conditional means and
+    variances of the log-return (host arrays; any model's, cv may differ per path), the estimator of include/svmc_ext.h's
+    svmc_tilted_cond_payoff_chain: W = exp(gamma mu + gamma^2 cv / 2), F_t = forward exp(mu + (gamma + 1/2) cv), a path kept iff
+    compute_mc_vars_payoff_conditional keeps it and W^2 and (W F_t)^2 are finite, per kept path the Black-76 price of F_t against
+    K + corr at total variance cv (corr = compute_mc_vars_payoff_conditional's with recenter, else 0), price = sum W B / sum W
+    (undiscounted) and its delta-method standard error.  risk_premia_gamma: one gamma -- (prices, stderrs) in the strikes' shape,
+    with return_stats=True also the dict of engine.TILTED_COND_STATS_FIELDS -- or a sequence of up to 16 -- lists of those, one
+    entry per gamma, from one upload.  'C' / 'P' only (others: ValueError("not implemented")), LOG_RETURN only
+    (NotImplementedError)."""
+    if variable_type_code(variable_type) != 1:
+        raise NotImplementedError(f"variable_type={variable_type}: the risk-premia kernel weights the log-return only")
+    codes = tilted_type_codes(optiontypes_ttm)                   # ValueError("not implemented")
+    strikes = np.asarray(strikes_ttm, dtype=np.float64)
+    single = np.ndim(risk_premia_gamma) == 0
+    ch = tilted_chain_arrays([float(forward)], [strikes], [codes], [float(risk_premia_gamma)] if single else risk_premia_gamma)
+    mu = np.ascontiguousarray(mu, dtype=np.float64).ravel()
+    cv = np.ascontiguousarray(cv, dtype=np.float64).ravel()
+    if mu.size != cv.size or mu.size == 0:
+        raise ValueError("mu and cv must be non-empty and of one length")
+    eng = get_engine(mu.size)
+    eng.upload(eng.x.ptr, mu)
+    eng.upload(eng.cv.ptr, cv)
+    prices, stderrs, stats = eng.tilted_conditional_payoffs(ch["forwards"], [strikes], [codes], ch["gammas"], bool(recenter))
+    out = ([p[0] for p in prices], [e[0] for e in stderrs])
+    if return_stats:
+        out = out + ([tilted_stats_dicts(st)[0] for st in stats],)
+    return tuple(o[0] for o in out) if single else out
+
+
 def compute_mc_vars_greeks_conditional(mu: np.ndarray, cv: np.ndarray, ttm: float, forward: float, strikes_ttm: np.ndarray,
                                        optiontypes_ttm: np.ndarray, discfactor: float = 1.0, recenter: bool = True,
                                        return_stats: bool = False) -> dict:
