@@ -1,0 +1,109 @@
+/*
+ * svmc_est.h -- C ABI of libsvmc_est.so, "estimators beside the core": the OPEN library of model-agnostic estimators on
+ * caller-owned device arrays.
+ *
+ * libsvmc.so (svmc.h) is closed at 143 entry points and at its kernels; libsvmc_ext.so (svmc_ext.h) is closed at three exported
+ * symbols and four kernels: existing tests pin each by count and by name.  This library is where the next estimator goes, so that
+ * no fourth library is ever needed.  THE RULE that keeps it open:
+ *   - it is one translation unit (stochvolmodels_amd/csrc/svmc_est.hip) on the header-only parts of csrc/ and links nothing from
+ *     libsvmc.so or libsvmc_ext.so: no undefined svmc_ symbol;
+ *   - its tests compare its exports and its Python binding TO WHAT THIS HEADER DECLARES (every SVMC_EST_API line), never to a
+ *     literal list or a count, and ask of EVERY kernel in its metadata scratch_bytes == 0 without pinning how many kernels there
+ *     are.  A new entry point is a declaration here, a definition in svmc_est.hip and a line in _lib._declare_est; a new kernel
+ *     needs no test to change.
+ * svmc.h is included for the status codes, svmc_stream_t, SVMC_CALL / SVMC_PUT and SVMC_TILTED_MAX_GAMMAS.
+ *
+ * Conventions: svmc.h's.  Every function returns an svmc status code; this library keeps no error message (svmc_last_error
+ * belongs to the core), the refusals below say what each code means.  Device pointers are on the current HIP device.
+ */
+#ifndef SVMC_EST_H
+#define SVMC_EST_H
+
+#include "svmc.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define SVMC_EST_VERSION 100 /* 0.1.0 */
+
+#if defined(__GNUC__) || defined(__clang__)
+#define SVMC_EST_API __attribute__((visibility("default")))
+#else
+#define SVMC_EST_API
+#endif
+
+SVMC_EST_API int svmc_est_version(void);
+
+/* ---- conditional Monte Carlo Greeks under the exponential risk-premia kernel (src svmc_est.hip) ----------
+ * The derivatives in the forward and in the strike of svmc_tilted_cond_payoff_chain's price (svmc_ext.h, row f17), in closed form
+ * per path.  Notation, inputs, keep rule and recentring are that entry's: device rows mu[j], cv[j], the forward F, strikes K_k of
+ * type 'C' / 'P', up to SVMC_TILTED_MAX_GAMMAS gammas;
+ *   W_j = exp(gamma mu_j + gamma^2 cv_j / 2),   e_t,j = exp(mu_j + (gamma + 1/2) cv_j),   F_t,j = F e_t,j;
+ *   a path is kept iff f11's rule holds and W_j^2 and (W_j F_t,j)^2 are finite; a dropped path adds nothing to any sum;
+ *   c = mean_kept_f11(exp(mu + cv / 2)) - 1 with recenter != 0 -- f11's UNWEIGHTED mean over the paths f11 keeps, the same bits as
+ *   svmc_tilted_cond_payoff_chain's and svmc_cmc_payoff_chain's corr / F on these rows, whatever gamma is -- and 0 without;
+ *   corr = F c, K' = K + corr.  The weight depends on neither F nor K and c on neither, so what follows are the EXACT derivatives of
+ *   the price that entry returns on the same rows.
+ * Per kept path, s = +1 call / -1 put, sd = sqrt(cv):
+ *   d1 = (ln F_t - ln K') / sd + sd / 2,  d2 = d1 - sd
+ *   B_f = N(d1) (call) | N(d1) - 1 (put),   B_k = -N(d2) (call) | N(-d2) (put)
+ *   delta_j = e_t B_f + c B_k,   dual_delta_j = B_k,   dual_gamma_j = phi(d2) / (K' sd)
+ *   DEGENERATE (row f13's): cv == 0: B_f = s 1{s (F_t - K') > 0} (strict), B_k = -B_f, dual_gamma_j = 0, and the path is counted
+ *   per (expiry, gamma) as n_zero_cv;  K' <= 0: call B_f = 1, B_k = -1, put both 0, dual_gamma_j = 0.
+ *   value = sum_j W_j v_j / sum_j W_j,   error = sqrt(sum_j (W_j (v_j - value))^2) / sum_j W_j
+ *   gamma = (K / F)^2 dual_gamma, value and error scaled once per quote.
+ * The error comes from the sums of W d, (W d)^2 and W^2 d with d = v - shift, exactly as row f17 forms a price's error; the shifts
+ * are host constants per quote: s 1{s (F - K) > 0} for delta, its negative for dual delta, 0 for dual gamma.  One kept path gives
+ * error 0.  No kept path, or kept paths of zero weight only, give NaN values and are NOT errors of the call.  The errors ignore
+ * the noise of c, as f13's and f17's do.  All values are undiscounted.  An error is a difference of those sums: it keeps its digits where
+ * the values lie near their shift and loses them as sum (W d)^2 exceeds sum (W (v - value))^2 -- a handful of paths that all lie across the
+ * strike from the forward, or one dominating weight.
+ * Every sum has a fixed order that depends on n_path alone: a gamma's, an expiry's and a strike's results are the same bits
+ * whichever others share the call.  No atomics, no scratch, LDS for the block sums' exchange only.
+ *
+ * Two consequences, to rounding:
+ *   HOMOGENEITY  price = F delta + K dual_delta with svmc_tilted_cond_payoff_chain's price; at one strike
+ *                delta_C - delta_P = gamma_forward / F and dual_delta_C - dual_delta_P = -1 with its gamma_forward;
+ *   THE DENSITY  with recenter = 0 and K = F exp(x):  K dual_gamma = sum_j W_j N(x; mu_j + gamma cv_j, cv_j) / sum_j W_j, the
+ *                density of the simulated log-return under the kernel without a bandwidth, normalised by the weights: it
+ *                integrates to the weight share of the kept paths with cv > 0.  Because
+ *                W_j N(x; mu_j + gamma cv_j, cv_j) = e^{gamma x} N(x; mu_j, cv_j), the quantity pdf_gamma(x) sum W_gamma / e^{gamma x}
+ *                is the same number for every gamma when no path is dropped.
+ *
+ * Price and error are NOT recomputed here: they are svmc_tilted_cond_payoff_chain's on the same rows.  A C caller makes two calls
+ * (the Python routes call both tails).
+ *
+ *   svmc_tilted_cond_greeks_workspace_bytes   host only: the device workspace that serves any chain of n_expiries expiries and
+ *                              total_strikes strikes at this n_path and n_gammas.
+ *   svmc_tilted_cond_greeks_chain     mu_snapshots_host, cv_snapshots_host: HOST arrays of n_expiries DEVICE pointers; strikes /
+ *                              types concatenated, expiry i owning [strike_offsets_host[i], strike_offsets_host[i + 1]).
+ *                              greeks_host: [n_gammas][SVMC_TCG_ROWS][sum K_i] -- delta, its error, dual delta, its error, gamma,
+ *                              its error, dual gamma, its error; stats_host: [n_gammas][n_expiries][SVMC_TCG_STATS_DOUBLES] --
+ *                              sum W, n_kept, n_dropped, n_zero_cv; host arrays.  One upload of the chain's table, four launches
+ *                              on `stream` with no host round trip between them (the forward pass and its finish with the
+ *                              statements of rows f11 / f17, the Greeks kernel, the finish), one download, one synchronise.
+ * Everything is checked before anything is launched, and a refused call leaves the output arrays untouched:
+ * SVMC_ERR_INVALID_ARGUMENT for a null pointer (a null snapshot among them), n_path < 1, n_expiries < 1, n_gammas outside
+ * 1 .. SVMC_TILTED_MAX_GAMMAS, strike offsets that do not start at 0 or decrease, a gamma, forward or strike that is not finite, a
+ * forward that is not positive; SVMC_ERR_UNKNOWN_PAYOFF for a type code other than SVMC_CALL / SVMC_PUT; SVMC_ERR_WORKSPACE for a
+ * workspace below svmc_tilted_cond_greeks_workspace_bytes; SVMC_ERR_HIP for a failure of the runtime.
+ * Left out: a dedicated density kernel on the e^{gamma x} identity, the many-job form, parameter sensitivities, IC / IP, several
+ * GPUs. */
+#define SVMC_TCG_ROWS 8
+#define SVMC_TCG_STATS_DOUBLES 4
+
+SVMC_EST_API int svmc_tilted_cond_greeks_workspace_bytes(size_t n_path, int n_expiries, size_t total_strikes, int n_gammas,
+                                                         size_t *bytes);
+SVMC_EST_API int svmc_tilted_cond_greeks_chain(const double *const *mu_snapshots_host, const double *const *cv_snapshots_host,
+                                               size_t n_path, const double *forwards_host, int n_expiries,
+                                               const double *strikes_host, const int8_t *types_host,
+                                               const size_t *strike_offsets_host, const double *gammas_host, int n_gammas,
+                                               int recenter, double *greeks_host, double *stats_host, void *workspace,
+                                               size_t workspace_bytes, svmc_stream_t stream);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* SVMC_EST_H */

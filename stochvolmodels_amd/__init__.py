@@ -15,18 +15,19 @@ Module layout and public names mirror the reference package (`stochvolmodels`) f
                                               hawkesjd_mc_chain_pricer_many,
                                               hawkesjd_mc_chain_pricer_with_risk_premia_gammas_many,
                                               hawkesjd_mc_chain_pricer_conditional, hawkesjd_mc_chain_greeks_conditional,
-                                              hawkesjd_mc_chain_pricer_conditional_with_risk_premia(_gammas)
+                                              hawkesjd_mc_chain_pricer_conditional_with_risk_premia(_gammas),
+                                              hawkesjd_mc_chain_greeks_conditional_with_risk_premia(_gammas)
     stochvolmodels_amd.pricers.il_pricer      logsv_il_pricer(_vector, _batch), square_root_payoff_pricer_with_mgf_grid,
                                               compute_mc_il_payoff
     stochvolmodels_amd.utils.mc_payoffs       compute_mc_vars_payoff, compute_mc_vars_payoff_with_gamma,
-                                              compute_mc_vars_payoff_conditional(_with_gamma), compute_mc_vars_greeks(_conditional),
+                                              compute_mc_vars_payoff_conditional(_with_gamma), compute_mc_vars_greeks(_conditional(_with_gamma)),
                                               compute_mc_vars_sens_conditional
     stochvolmodels_amd.utils.funcs            set_time_grid, set_seed, timer
     stochvolmodels_amd.utils.config           OptionType, VariableType
     stochvolmodels_amd.data.option_chain      OptionChain
 All arithmetic runs in libsvmc.so (hand-written HIP for gfx950, C ABI in include/svmc.h, closed at 143 entry points) and in
-libsvmc_ext.so beside it (include/svmc_ext.h: estimators on caller-owned device arrays); there is no CPU
-fallback.  Names resolve lazily so importing the package does not load the GPU library.
+libsvmc_ext.so and libsvmc_est.so beside it (include/svmc_ext.h, include/svmc_est.h: estimators on caller-owned device arrays);
+there is no CPU fallback.  Names resolve lazily so importing the package does not load the GPU library.
 """
 import importlib
 
@@ -43,6 +44,7 @@ _EXPORTS = {
     "compute_mc_vars_payoff_with_gamma": "utils.mc_payoffs",
     "compute_mc_vars_payoff_conditional": "utils.mc_payoffs",
     "compute_mc_vars_payoff_conditional_with_gamma": "utils.mc_payoffs",
+    "compute_mc_vars_greeks_conditional_with_gamma": "utils.mc_payoffs",
     "compute_mc_vars_greeks": "utils.mc_payoffs",
     "compute_mc_vars_greeks_conditional": "utils.mc_payoffs",
     "compute_mc_vars_sens_conditional": "utils.mc_payoffs",
@@ -55,6 +57,8 @@ _EXPORTS = {
     "hawkesjd_mc_chain_greeks_conditional": "pricers.hawkes_jd_pricer",
     "hawkesjd_mc_chain_pricer_conditional_with_risk_premia": "pricers.hawkes_jd_pricer",
     "hawkesjd_mc_chain_pricer_conditional_with_risk_premia_gammas": "pricers.hawkes_jd_pricer",
+    "hawkesjd_mc_chain_greeks_conditional_with_risk_premia": "pricers.hawkes_jd_pricer",
+    "hawkesjd_mc_chain_greeks_conditional_with_risk_premia_gammas": "pricers.hawkes_jd_pricer",
     "OptionChain": "data.option_chain",
     "ModelParams": "pricers.model_pricer", "ModelPricer": "pricers.model_pricer",
     "LogSvParams": "pricers.logsv.logsv_params",

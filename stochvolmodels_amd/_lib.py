@@ -289,14 +289,49 @@ def load_ext() -> C.CDLL:
     return _ext
 
 
+# ---- libsvmc_est.so (C ABI: include/svmc_est.h): the open library of estimators beside the core -------------------------------------
+EST_LIB_PATH = os.environ.get("SVMC_EST_LIB") or os.path.join(_PKG, "libsvmc_est.so")
+_est = None
+
+
+def _declare_est(L: C.CDLL) -> None:
+    vp, sz, i32, f64 = C.c_void_p, C.c_size_t, C.c_int, C.c_double
+    psz, pvp, pf64, pi8 = C.POINTER(sz), C.POINTER(vp), C.POINTER(f64), C.POINTER(C.c_int8)
+    sig = {
+        "svmc_est_version": ([], i32),
+        "svmc_tilted_cond_greeks_workspace_bytes": ([sz, i32, sz, i32, psz], i32),
+        "svmc_tilted_cond_greeks_chain": ([pvp, pvp, sz, pf64, i32, pf64, pi8, psz, pf64, i32, i32, pf64, pf64, vp, sz, vp], i32),
+    }
+    for name, (argtypes, restype) in sig.items():
+        fn = getattr(L, name)          # AttributeError here = the .so does not match include/svmc_est.h
+        fn.argtypes = argtypes
+        fn.restype = restype
+    L._svmc_est_symbols = tuple(sig)
+
+
+def load_est() -> C.CDLL:
+    """load libsvmc_est.so once; raise loudly when it is not there (no fallback exists).  The core is loaded first, so that every
+    library resolves the one HIP runtime load() settles on."""
+    global _est
+    load()
+    with _lock:
+        if _est is None:
+            if not os.path.exists(EST_LIB_PATH):
+                raise SvmcError(f"{EST_LIB_PATH} is not built: run `python -m stochvolmodels_amd.build` (needs hipcc)")
+            L = C.CDLL(EST_LIB_PATH, mode=C.RTLD_GLOBAL)
+            _declare_est(L)
+            _est = L
+    return _est
+
+
 def check_ext(rc: int, what: str) -> None:
-    """map a status of libsvmc_ext.so, which keeps no message of its own, to check()'s exception types"""
+    """map a status of libsvmc_ext.so or libsvmc_est.so, which keep no message of their own, to check()'s exception types"""
     if rc == OK:
         return
     if rc == ERR_UNKNOWN_PAYOFF:
         raise ValueError("unknown option payoff code")
     if rc == ERR_INVALID_ARGUMENT:
-        raise ValueError(f"{what}: invalid argument (include/svmc_ext.h lists the refusals)")
+        raise ValueError(f"{what}: invalid argument (include/svmc_ext.h and include/svmc_est.h list the refusals)")
     if rc == ERR_WORKSPACE:
         raise SvmcError(f"{what}: workspace too small")
     raise SvmcError(f"{what}: svmc status {rc}")

@@ -1,6 +1,7 @@
 """
-Build recipe of the package's native artefacts: libsvmc.so, the closed core (include/svmc.h), and libsvmc_ext.so, the estimators
-beside it (include/svmc_ext.h) -- hipcc, gfx950 only, in-tree.  It also builds the test-only device probe
+Build recipe of the package's native artefacts: libsvmc.so, the closed core (include/svmc.h), libsvmc_ext.so, the first estimator
+beside it (include/svmc_ext.h, closed too), and libsvmc_est.so, the open library of estimators beside the core (include/svmc_est.h)
+-- hipcc, gfx950 only, in-tree.  It also builds the test-only device probe
 tests/native/libsvmc_device_probe.so with the same flags.
 
     python -m stochvolmodels_amd.build [--force]
@@ -43,6 +44,11 @@ PROBE_LIB = os.path.join(ROOT, "tests", "native", "libsvmc_device_probe.so")
 EXT_SRC = os.path.join(CSRC, "svmc_ext.hip")
 EXT_LIB = os.path.join(PKG, "libsvmc_ext.so")
 EXT_ISA_JSON = os.path.join(PKG, "libsvmc_ext.isa.json")
+# libsvmc_est.so (include/svmc_est.h): the estimators beside the core, built the way libsvmc_ext.so is.  libsvmc_ext.so is pinned at
+# three symbols and four kernels; this one is held to what its header declares, so the next estimator is added to it
+EST_SRC = os.path.join(CSRC, "svmc_est.hip")
+EST_LIB = os.path.join(PKG, "libsvmc_est.so")
+EST_ISA_JSON = os.path.join(PKG, "libsvmc_est.isa.json")
 
 
 def headers() -> list:
@@ -102,31 +108,53 @@ def build_device_probe(force: bool = False, verbose: bool = False) -> str:
     return PROBE_LIB
 
 
-def ext_is_stale() -> bool:
-    if not os.path.exists(EXT_LIB) or not os.path.exists(EXT_ISA_JSON):
+def side_is_stale(lib: str, isa_json: str, src: str, header: str) -> bool:
+    if not os.path.exists(lib) or not os.path.exists(isa_json):
         return True
-    t = os.path.getmtime(EXT_LIB)
-    deps = [EXT_SRC, os.path.join(INCLUDE, "svmc.h"), os.path.join(INCLUDE, "svmc_ext.h"), __file__] + headers()
+    t = os.path.getmtime(lib)
+    deps = [src, os.path.join(INCLUDE, "svmc.h"), os.path.join(INCLUDE, header), __file__] + headers()
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def build_ext(force: bool = False, verbose: bool = False) -> str:
-    """libsvmc_ext.so, rebuilt when its source, a header of csrc/, either public header or this file is newer; the kernel
-    metadata of the build (kernel_metadata) goes to libsvmc_ext.isa.json in libsvmc.isa.json's {"metadata": ...} form"""
-    if not force and not ext_is_stale():
-        return EXT_LIB
-    with tempfile.TemporaryDirectory(prefix="svmc_ext_build_") as tmp:
-        cmd = [hipcc()] + flags() + ["--save-temps", EXT_SRC, "-o", EXT_LIB]
+def build_side(lib: str, isa_json: str, src: str, verbose: bool, extra: tuple = ()) -> str:
+    """one translation unit -> a library beside the core; the kernel metadata of the build (kernel_metadata) goes to isa_json in
+    libsvmc.isa.json's {"metadata": ...} form"""
+    with tempfile.TemporaryDirectory(prefix="svmc_side_build_") as tmp:
+        cmd = [hipcc()] + flags() + list(extra) + ["--save-temps", src, "-o", lib]
         if verbose:
             print(" ".join(cmd))
         res = subprocess.run(cmd, capture_output=True, text=True, cwd=tmp)
         if res.returncode != 0:
-            raise RuntimeError("hipcc failed on svmc_ext.hip:\n" + res.stdout + res.stderr)
+            raise RuntimeError(f"hipcc failed on {os.path.basename(src)}:\n" + res.stdout + res.stderr)
         if verbose and res.stderr:
             print(res.stderr)
-        with open(EXT_ISA_JSON, "w") as fh:
-            json.dump({"lib_sha256": file_sha256(EXT_LIB), "flags": flags(), "metadata": kernel_metadata(tmp)}, fh, indent=1)
-    return EXT_LIB
+        with open(isa_json, "w") as fh:
+            json.dump({"lib_sha256": file_sha256(lib), "flags": flags() + list(extra), "metadata": kernel_metadata(tmp)}, fh, indent=1)
+    return lib
+
+
+def ext_is_stale() -> bool:
+    return side_is_stale(EXT_LIB, EXT_ISA_JSON, EXT_SRC, "svmc_ext.h")
+
+
+def build_ext(force: bool = False, verbose: bool = False) -> str:
+    """libsvmc_ext.so, rebuilt when its source, a header of csrc/, either public header or this file is newer; its kernel metadata
+    goes to libsvmc_ext.isa.json"""
+    if not force and not ext_is_stale():
+        return EXT_LIB
+    return build_side(EXT_LIB, EXT_ISA_JSON, EXT_SRC, verbose)
+
+
+def est_is_stale() -> bool:
+    return side_is_stale(EST_LIB, EST_ISA_JSON, EST_SRC, "svmc_est.h")
+
+
+def build_est(force: bool = False, verbose: bool = False) -> str:
+    """libsvmc_est.so, rebuilt when its source, a header of csrc/, svmc.h, svmc_est.h or this file is newer; its kernel metadata
+    goes to libsvmc_est.isa.json"""
+    if not force and not est_is_stale():
+        return EST_LIB
+    return build_side(EST_LIB, EST_ISA_JSON, EST_SRC, verbose)
 
 
 def file_sha256(path: str) -> str:
@@ -183,6 +211,7 @@ def write_isa_json(asm_dir: str) -> None:
 def build(force: bool = False, verbose: bool = False) -> str:
     build_device_probe(force, verbose)
     build_ext(force, verbose)
+    build_est(force, verbose)
     if not force and not is_stale() and os.path.exists(ISA_JSON):
         return LIB
     # --save-temps: the device assembly of this very compilation is kept for the histogram (temporaries in a scratch dir)

@@ -1,0 +1,371 @@
+// svmc_est.hip -- libsvmc_est.so, the estimators beside the core (include/svmc_est.h states the rule that keeps this library
+// open).  One translation unit on the header-only parts of csrc/; nothing of libsvmc.so or libsvmc_ext.so is
+// linked and no session is needed.
+//
+// Conditional Monte Carlo Greeks under the exponential risk-premia kernel (svmc_tilted_cond_greeks_chain; the header states the
+// estimator, the degenerate cases and the two identities).  Four launches on one uploaded table:
+//   tilted_cond_greeks_forward_kernel, tilted_cond_greeks_forward_finish_kernel
+//                                the forward pass of rows f11 / f17, the SAME statements (svmc_tilted_cond.h): corr, K' = K + corr
+//                                and ln K' are svmc_tilted_cond_payoff_chain's to the bit
+//   tilted_cond_greeks_kernel    block (path block, group of up to TCG_KT strikes of one expiry, gamma): a thread forms per path
+//                                sd and 1 / sd, the weight W, ln F_t and e_t once, then per strike two normal CDFs and one exp for
+//                                phi(d2) and, for each of delta, dual delta and dual gamma, the sums of W d, (W d)^2, W (W d),
+//                                d = v - shift: nine fused accumulations; the (expiry, gamma) statistics sums ride in the same
+//                                block sum and are stored by the expiry's first group
+//   tilted_cond_greeks_finish_kernel   a block per (quote | expiry, gamma): the column sums in row order, values, errors, statistics
+// The path blocks are quote_rows(n_path), a function of the path count alone; a strike's accumulators do not look at its
+// neighbours' and the block sum's tree is the same for every accumulator index: a gamma's, an expiry's and a strike's results
+// are the same bits whichever others share the call, and sum W and the kept count are row f17's bits.  No atomics, no scratch,
+// LDS for the block sums' exchange only.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "svmc_est.h"
+
+#include "svmc_tilted_cond.h"
+
+namespace svmc {
+
+// Strikes per group.  A strike carries nine accumulators and five constants in vector registers (row f17's payoff kernel: three and
+// three at eight strikes).  At 4 the kernel takes 160 VGPRs: THREE waves per SIMD, one fewer than row f17's payoff kernel has at 128 --
+// the occupancy is not kept.  Measured on the MI355X (profiles/hawkes_tilted_cond_greeks_bench.json, "kt"): 8 (262 VGPRs, one wave) takes
+// 1.5 to 1.9 times as long; 2 (107 VGPRs, four waves) is within 2 % of 4, mostly behind it: what a fourth wave hides, forming the
+// per-path terms twice as often costs.
+#ifndef SVMC_TCG_KT
+#define SVMC_TCG_KT 4
+#endif
+constexpr int TCG_KT = SVMC_TCG_KT;
+constexpr int TCG_COLS = 9;            // per quote, for v = delta, dual delta, dual gamma: [sum W d, sum (W d)^2, sum W^2 d]
+constexpr int TCG_NSTAT = 4;           // per (expiry, gamma): [sum W, sum W^2, kept, kept with cv == 0]
+constexpr int TCG_MAX_GROUPS = 65535;  // the groups are a grid's y dimension
+
+// the device table of a call; the image (expiries .. gammas) is uploaded once
+struct TcgTable {
+    const TcExpiry *expiries;          // [m]
+    const QuoteGroup *groups;          // [G] groups of up to TCG_KT strikes; pad = 1: the expiry's first, which stores its statistics
+                                       // sums (an expiry without strikes has one group of nk = 0 for them)
+    const double *strikes;             // [K]
+    const double *is_put;              // [K] 0 | 1
+    const double *dshift;              // [K] s 1{s (F - K) > 0}: the shift of delta's sums; dual delta's is its negative
+    const double *gammas;              // [NG]
+    double *kp, *ln_kp;                // [K] device-computed: K + corr, its logarithm (0 where K + corr <= 0)
+    double *fwd;                       // [m][4]: sum (e - 1), sum (e - 1)^2, kept count of f11's rule, corr
+    double *fwd_partials;              // [rows][m][3]
+    double *q_partials;                // [rows][NG][K][TCG_COLS]
+    double *stat_partials;             // [rows][NG][m][TCG_NSTAT]
+    double *out;                       // greeks [NG][SVMC_TCG_ROWS][K], statistics [NG][m][SVMC_TCG_STATS_DOUBLES]: one block
+    int m, K, NG;
+    unsigned rows;
+};
+struct TcgImage {
+    TcExpiry *expiries;
+    QuoteGroup *groups;
+    double *strikes, *is_put, *dshift, *gammas;
+};
+inline TcgImage tcg_image(Layout &w, int m, size_t K, int G, int NG)
+{
+    return TcgImage{w.take<TcExpiry>(m), w.take<QuoteGroup>(G), w.take<double>(K), w.take<double>(K), w.take<double>(K),
+                    w.take<double>(NG)};                   // (a braced list: in this order)
+}
+inline size_t tcg_out_doubles(int m, size_t K, int NG)
+{
+    return static_cast<size_t>(NG) * (SVMC_TCG_ROWS * K + static_cast<size_t>(SVMC_TCG_STATS_DOUBLES) * m);
+}
+// ONE walk that is both the workspace's byte count and its carving: the image, the forward pass's head, the results, the partials.
+// Returns the bytes of the image, which the walk starts with.
+inline size_t tcg_workspace(Layout &w, size_t n_path, int m, size_t K, int G, int NG, TcgTable &t)
+{
+    const size_t rows = quote_rows(n_path);
+    const TcgImage im = tcg_image(w, m, K, G, NG);
+    const size_t image_bytes = w.bytes();
+    t.expiries = im.expiries;
+    t.groups = im.groups;
+    t.strikes = im.strikes;
+    t.is_put = im.is_put;
+    t.dshift = im.dshift;
+    t.gammas = im.gammas;
+    t.kp = w.take<double>(K);
+    t.ln_kp = w.take<double>(K);
+    t.fwd = w.take<double>(4 * static_cast<size_t>(m));
+    t.out = w.take<double>(tcg_out_doubles(m, K, NG));
+    t.fwd_partials = w.take<double>(rows * 3 * m);
+    t.q_partials = w.take<double>(rows * NG * K * TCG_COLS);
+    t.stat_partials = w.take<double>(rows * NG * m * TCG_NSTAT);
+    t.m = m;
+    t.K = static_cast<int>(K);
+    t.NG = NG;
+    t.rows = static_cast<unsigned>(rows);
+    return image_bytes;
+}
+
+// ---- the forward pass: rows f11's / f17's statements (svmc_tilted_cond.h) ---------------------------------------------------------
+__global__ __launch_bounds__(BLOCK) void tilted_cond_greeks_forward_kernel(TcgTable t, size_t n)
+{
+    __shared__ double lds[4 * 3];
+    tc_forward_body(t, n, lds);
+}
+
+__global__ __launch_bounds__(BLOCK) void tilted_cond_greeks_forward_finish_kernel(TcgTable t, int recenter)
+{
+    __shared__ double lds[4];
+    tc_forward_finish_body(t, recenter, lds);
+}
+
+// ---- the weighted Black-76 derivatives ----------------------------------------------------------------------------------------------
+// Per kept path and strike (B_f, B_k, dual_gamma_j) as row f13's cmc_derivs forms them (svmc_cmc.hip), at the shifted forward: each
+// side's B_f and B_k come from its own tail (put: B_f = -N(-d1), B_k = N(-d2)), as its price does.
+__device__ __forceinline__ void tcg_derivs(double ft, double ln_ft, double cv, double sd, double inv_sd, double kp, double ln_kp,
+                                           double inv_kp, bool put, double &bf, double &bk, double &dg)
+{
+    dg = 0.0;
+    if (!(kp > 0.0)) {
+        bf = put ? 0.0 : 1.0;
+        bk = -bf;
+    } else if (cv == 0.0) {
+        const bool itm = put ? (ft < kp) : (ft > kp);      // strict: a tie has payoff 0 and indicator 0
+        bf = itm ? (put ? -1.0 : 1.0) : 0.0;
+        bk = -bf;
+    } else {
+        const double d1 = fma(ln_ft - ln_kp, inv_sd, 0.5 * sd), d2 = d1 - sd;
+        bf = put ? -black_norm_cdf(-d1) : black_norm_cdf(d1);
+        bk = put ? black_norm_cdf(-d2) : -black_norm_cdf(d2);
+        dg = (exp_full((-0.5 * d2) * d2) * 0.39894228040143267794) * (inv_sd * inv_kp);
+    }
+}
+
+template <int KT>
+__global__ __launch_bounds__(BLOCK) void tilted_cond_greeks_kernel(TcgTable t, size_t n, int recenter)
+{
+    constexpr int NQ = TCG_COLS * KT;
+    constexpr int NV = NQ + TCG_NSTAT;
+    constexpr int NSUM = block_sum_padded(NV);
+    __shared__ double lds[4 * NSUM];
+    const QuoteGroup g = t.groups[blockIdx.y];
+    const TcExpiry ex = t.expiries[g.expiry];
+    const int nk = g.nk;                                   // (block-uniform; 0: the group only forms the statistics)
+    const double gamma = t.gammas[blockIdx.z];
+    const double *fw = t.fwd + 4 * g.expiry;
+    const double c = recenter ? fw[0] / fw[2] : 0.0;       // mean_kept(e) - 1, the quotient the forward finish forms: corr = F c
+    const double half_g2 = 0.5 * gamma * gamma, g_half = gamma + 0.5;
+    double kp[KT], ln_kp[KT], inv_kp[KT], dshift[KT], acc[NSUM];
+    bool put[KT];
+#pragma unroll
+    for (int j = 0; j < NSUM; ++j) acc[j] = 0.0;
+#pragma unroll
+    for (int k = 0; k < KT; ++k) {
+        const int kk = g.k0 + ((k < nk) ? k : 0);          // the unused strikes of a group repeat its first; their sums are dropped
+        const bool on = nk > 0;                            // a group without strikes reads none
+        kp[k] = on ? t.kp[kk] : 1.0;
+        ln_kp[k] = on ? t.ln_kp[kk] : 0.0;
+        inv_kp[k] = 1.0 / kp[k];
+        dshift[k] = on ? t.dshift[kk] : 0.0;
+        put[k] = on ? t.is_put[kk] != 0.0 : false;
+    }
+    const double forward = ex.forward, ln_forward = ex.ln_forward;
+    const size_t stride = static_cast<size_t>(gridDim.x) * BLOCK;
+    for (size_t i = static_cast<size_t>(blockIdx.x) * BLOCK + threadIdx.x; i < n; i += stride) {
+        const double mu = ex.mu[i], cv = ex.cv[i];
+        double h, e;
+        if (!tc_keep_cmc(mu, cv, h, e)) continue;
+        // once per (path, gamma): the weight, e_t and the shifted forward with its logarithm
+        double w, et, ft, ln_ft;
+        if (!tc_weight_forward(mu, cv, gamma, half_g2, g_half, forward, ln_forward, w, et, ft, ln_ft)) continue;
+        const double sd = sqrt(cv), inv_sd = 1.0 / sd;     // once per path
+        acc[NQ] += w;
+        acc[NQ + 1] = fma(w, w, acc[NQ + 1]);
+        acc[NQ + 2] += 1.0;
+        if (cv == 0.0) acc[NQ + 3] += 1.0;
+        if (nk > 0) {
+#pragma unroll
+            for (int k = 0; k < KT; ++k) {
+                double bf, bk, dg;
+                tcg_derivs(ft, ln_ft, cv, sd, inv_sd, kp[k], ln_kp[k], inv_kp[k], put[k], bf, bk, dg);
+                const double v[3] = {fma(et, bf, c * bk) - dshift[k], bk + dshift[k], dg};
+#pragma unroll
+                for (int q = 0; q < 3; ++q) {
+                    const double wd = w * v[q];
+                    acc[(3 * q) * KT + k] += wd;
+                    acc[(3 * q + 1) * KT + k] = fma(wd, wd, acc[(3 * q + 1) * KT + k]);
+                    acc[(3 * q + 2) * KT + k] = fma(w, wd, acc[(3 * q + 2) * KT + k]);
+                }
+            }
+        }
+    }
+    const size_t slot = static_cast<size_t>(blockIdx.x) * t.NG + blockIdx.z;               // partials[path block][gamma]
+    double *qp = t.q_partials + (slot * t.K + g.k0) * TCG_COLS;
+    double *stat = (g.pad != 0) ? t.stat_partials + (slot * t.m + g.expiry) * TCG_NSTAT : nullptr;
+    block_sum_apply<NSUM>(acc, lds, NV, [&](int j, double s) {
+        if (j < NQ) {
+            const int which = j / KT, k = j - which * KT;
+            if (k < nk) qp[TCG_COLS * k + which] = s;
+        } else if (stat != nullptr) {
+            stat[j - NQ] = s;
+        }
+    });
+}
+
+// A block per (column, gamma): columns [0, K) are the quotes, [K, K + m) the expiries' statistics.  The sums are the column sums of
+// the partial rows in row order; a value and its error are formed as row f17's finish forms a price and its error.
+__global__ __launch_bounds__(BLOCK) void tilted_cond_greeks_finish_kernel(TcgTable t, size_t n)
+{
+    __shared__ double lds[4];
+    const int col = blockIdx.x, gi = blockIdx.y;
+    const size_t K = static_cast<size_t>(t.K), m = static_cast<size_t>(t.m), NG = static_cast<size_t>(t.NG);
+    const size_t ld_stat = NG * m * TCG_NSTAT, ld_q = NG * K * TCG_COLS;
+    int i = col - t.K;                                     // the expiry (block-uniform)
+    if (col < t.K) {
+        i = 0;
+        while (i + 1 < t.m && col >= t.expiries[i].k1) ++i;            // expiries without strikes are skipped over
+    }
+    const double *st = t.stat_partials + (static_cast<size_t>(gi) * m + i) * TCG_NSTAT;
+    double s[TCG_NSTAT];
+#pragma unroll
+    for (int q = 0; q < TCG_NSTAT; ++q) {
+        if (q > 0) __syncthreads();
+        s[q] = block_column_sum(st + q, t.rows, ld_stat, lds);
+    }
+    const double W = s[0], Q = s[1], kept = s[2];
+    if (col >= t.K) {
+        if (threadIdx.x != 0) return;
+        double *out = t.out + NG * SVMC_TCG_ROWS * K + (static_cast<size_t>(gi) * m + i) * SVMC_TCG_STATS_DOUBLES;
+        out[0] = W;
+        out[1] = kept;
+        out[2] = static_cast<double>(n) - kept;
+        out[3] = s[3];
+        return;
+    }
+    const double *qp = t.q_partials + (static_cast<size_t>(gi) * K + col) * TCG_COLS;
+    double c[TCG_COLS];
+#pragma unroll
+    for (int q = 0; q < TCG_COLS; ++q) {
+        __syncthreads();
+        c[q] = block_column_sum(qp + q, t.rows, ld_q, lds);
+    }
+    if (threadIdx.x != 0) return;
+    // value = shift + sum W d / sum W; sum (W (v - value))^2 = sum (W d)^2 - 2 e sum W^2 d + e^2 sum W^2, e = value - shift.
+    // One kept path: the estimate IS that path's value and the squares about it are zero identically
+    const double dshift = t.dshift[col];
+    const double shift[3] = {dshift, -dshift, 0.0};
+    double v[3], err[3];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        const double e = c[3 * q] / W;
+        const double var = (kept > 1.0) ? fma(e, fma(e, Q, -2.0 * c[3 * q + 2]), c[3 * q + 1]) : 0.0;
+        v[q] = e + shift[q];
+        err[q] = sqrt(fmax(var, 0.0)) / W;
+    }
+    const double r = t.strikes[col] / t.expiries[i].forward, r2 = r * r;
+    double *out = t.out + static_cast<size_t>(gi) * SVMC_TCG_ROWS * K + col;
+    out[0] = v[0];
+    out[K] = err[0];
+    out[2 * K] = v[1];
+    out[3 * K] = err[1];
+    out[4 * K] = r2 * v[2];
+    out[5 * K] = r2 * err[2];
+    out[6 * K] = v[2];
+    out[7 * K] = err[2];
+}
+
+// ---- host -----------------------------------------------------------------------------------------------------------------------
+static bool tcg_sizes_ok(size_t n_path, int n_expiries, int n_gammas)
+{
+    return n_path >= 1 && n_expiries >= 1 && n_gammas >= 1 && n_gammas <= SVMC_TILTED_MAX_GAMMAS;
+}
+
+}  // namespace svmc
+
+using namespace svmc;
+
+extern "C" {
+
+int svmc_est_version(void) { return SVMC_EST_VERSION; }
+
+int svmc_tilted_cond_greeks_workspace_bytes(size_t n_path, int n_expiries, size_t total_strikes, int n_gammas, size_t *bytes)
+{
+    if (bytes == nullptr || !tcg_sizes_ok(n_path, n_expiries, n_gammas)) return SVMC_ERR_INVALID_ARGUMENT;
+    TcgTable t;
+    Layout w{nullptr};
+    tcg_workspace(w, n_path, n_expiries, total_strikes, quote_groups_bound(n_expiries, total_strikes, TCG_KT), n_gammas, t);
+    *bytes = w.bytes();
+    return SVMC_OK;
+}
+
+int svmc_tilted_cond_greeks_chain(const double *const *mu_snapshots_host, const double *const *cv_snapshots_host, size_t n_path,
+                                  const double *forwards_host, int n_expiries, const double *strikes_host, const int8_t *types_host,
+                                  const size_t *strike_offsets_host, const double *gammas_host, int n_gammas, int recenter,
+                                  double *greeks_host, double *stats_host, void *workspace, size_t workspace_bytes,
+                                  svmc_stream_t stream_)
+{
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    // everything is checked before anything is launched
+    if (!mu_snapshots_host || !cv_snapshots_host || !forwards_host || !strikes_host || !types_host || !strike_offsets_host ||
+        !gammas_host || !greeks_host || !stats_host || !workspace)
+        return SVMC_ERR_INVALID_ARGUMENT;
+    if (!tcg_sizes_ok(n_path, n_expiries, n_gammas)) return SVMC_ERR_INVALID_ARGUMENT;
+    const int m = n_expiries, NG = n_gammas;
+    if (strike_offsets_host[0] != 0) return SVMC_ERR_INVALID_ARGUMENT;
+    for (int i = 0; i < m; ++i) {
+        if (strike_offsets_host[i + 1] < strike_offsets_host[i] || strike_offsets_host[i + 1] > (static_cast<size_t>(1) << 30))
+            return SVMC_ERR_INVALID_ARGUMENT;
+        if (!mu_snapshots_host[i] || !cv_snapshots_host[i]) return SVMC_ERR_INVALID_ARGUMENT;
+        if (!std::isfinite(forwards_host[i]) || !(forwards_host[i] > 0.0)) return SVMC_ERR_INVALID_ARGUMENT;
+    }
+    const size_t K = strike_offsets_host[m];
+    for (int z = 0; z < NG; ++z)
+        if (!std::isfinite(gammas_host[z])) return SVMC_ERR_INVALID_ARGUMENT;
+    for (size_t k = 0; k < K; ++k)
+        if (!std::isfinite(strikes_host[k])) return SVMC_ERR_INVALID_ARGUMENT;
+    for (size_t k = 0; k < K; ++k)
+        if (types_host[k] != SVMC_CALL && types_host[k] != SVMC_PUT) return SVMC_ERR_UNKNOWN_PAYOFF;
+    const int G = quote_groups(m, strike_offsets_host, TCG_KT, true);
+    if (G > TCG_MAX_GROUPS) return SVMC_ERR_INVALID_ARGUMENT;
+    TcgTable t;
+    Layout w{static_cast<unsigned char *>(workspace)};
+    const size_t image_bytes = tcg_workspace(w, n_path, m, K, G, NG, t);
+    if (workspace_bytes < w.bytes()) return SVMC_ERR_WORKSPACE;
+
+    // the table's host image, then ONE upload
+    std::vector<unsigned char> image(image_bytes);
+    Layout h{image.data()};
+    const TcgImage im = tcg_image(h, m, K, G, NG);
+    quote_image(
+        m, strike_offsets_host,
+        [&](int i, int k0, int k1) {
+            im.expiries[i] = TcExpiry{mu_snapshots_host[i], cv_snapshots_host[i], forwards_host[i], std::log(forwards_host[i]), k0, k1};
+        },
+        [&](int i, int k) {
+            const double sgn = (types_host[k] == SVMC_PUT) ? -1.0 : 1.0;
+            im.strikes[k] = strikes_host[k];
+            im.is_put[k] = (types_host[k] == SVMC_PUT) ? 1.0 : 0.0;
+            im.dshift[k] = (sgn * (forwards_host[i] - strikes_host[k]) > 0.0) ? sgn : 0.0;
+        });
+    quote_groups(m, strike_offsets_host, TCG_KT, true, im.groups);
+    for (int z = 0; z < NG; ++z) im.gammas[z] = gammas_host[z];
+#define SVMC_EST_TRY(call)                       \
+    do {                                         \
+        if ((call) != hipSuccess) return SVMC_ERR_HIP; \
+    } while (0)
+    SVMC_EST_TRY(hipMemcpyAsync(workspace, image.data(), image_bytes, hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(tilted_cond_greeks_forward_kernel, dim3(t.rows, m), dim3(BLOCK), 0, stream, t, n_path);
+    SVMC_EST_TRY(hipGetLastError());
+    hipLaunchKernelGGL(tilted_cond_greeks_forward_finish_kernel, dim3(m), dim3(BLOCK), 0, stream, t, recenter ? 1 : 0);
+    SVMC_EST_TRY(hipGetLastError());
+    hipLaunchKernelGGL(tilted_cond_greeks_kernel<TCG_KT>, dim3(t.rows, G, NG), dim3(BLOCK), 0, stream, t, n_path, recenter ? 1 : 0);
+    SVMC_EST_TRY(hipGetLastError());
+    hipLaunchKernelGGL(tilted_cond_greeks_finish_kernel, dim3(static_cast<unsigned>(K) + m, NG), dim3(BLOCK), 0, stream, t, n_path);
+    SVMC_EST_TRY(hipGetLastError());
+    // ONE download of the results' block, ONE synchronise
+    std::vector<double> out(tcg_out_doubles(m, K, NG));
+    SVMC_EST_TRY(hipMemcpyAsync(out.data(), t.out, out.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+    SVMC_EST_TRY(hipStreamSynchronize(stream));
+#undef SVMC_EST_TRY
+    const size_t GRK = static_cast<size_t>(NG) * SVMC_TCG_ROWS * K;
+    if (GRK > 0) memcpy(greeks_host, out.data(), GRK * sizeof(double));
+    memcpy(stats_host, out.data() + GRK, static_cast<size_t>(NG) * m * SVMC_TCG_STATS_DOUBLES * sizeof(double));
+    return SVMC_OK;
+}
+
+}  // extern "C"

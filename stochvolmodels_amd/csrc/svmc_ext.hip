@@ -22,10 +22,7 @@
 
 #include "svmc_ext.h"
 
-#include "svmc_black.h"
-#include "svmc_block.h"
-#include "svmc_math.h"
-#include "svmc_quotes.h"
+#include "svmc_tilted_cond.h"
 
 namespace svmc {
 
@@ -35,13 +32,6 @@ constexpr int TC_STAT_COLS = 8;        // ... padded: an expiry's statistics col
 constexpr int TC_PAY_COLS = 3;         // per quote [sum W d, sum (W d)^2, sum W^2 d]
 constexpr int TC_MAX_GROUPS = 65535;   // the groups are a grid's y dimension
 
-static_assert(QUOTE_BLOCK == BLOCK, "svmc_quotes.h sizes the partial rows for blocks of BLOCK paths");
-
-struct TcExpiry {
-    const double *mu, *cv;
-    double forward, ln_forward;
-    int k0, k1;                        // its strikes [k0, k1)
-};
 // the device table of a call; the image (expiries .. gammas) is uploaded once
 struct TcTable {
     const TcExpiry *expiries;          // [m]
@@ -101,75 +91,20 @@ inline size_t tc_workspace(Layout &w, size_t n_path, int m, size_t K, int G, int
     return image_bytes;
 }
 
-// ---- row f11's keep rule and Black-76 price, restated (svmc_cmc.hip: cmc_keep, cmc_black) --------------------------------------
-// a path passes f11's rule iff mu, cv and e = exp(mu + cv / 2) are finite and cv >= 0; h = mu + cv / 2
-__device__ __forceinline__ bool tc_keep_cmc(double mu, double cv, double &h, double &e)
-{
-    h = fma(0.5, cv, mu);
-    e = exp_full(h);
-    const double inf = __builtin_huge_val();
-    return fabs(mu) < inf && cv >= 0.0 && cv < inf && e < inf;     // a NaN fails a comparison
-}
-
-// the undiscounted Black-76 price of ft against K' at total variance cv, on the quoted side's own formula
-__device__ __forceinline__ double tc_black(double ft, double ln_ft, double cv, double sd, double inv_sd, double kp, double ln_kp, bool put)
-{
-    if (!(kp > 0.0)) return put ? 0.0 : ft - kp;
-    if (cv == 0.0) return put ? fmax(kp - ft, 0.0) : fmax(ft - kp, 0.0);
-    const double d1 = fma(ln_ft - ln_kp, inv_sd, 0.5 * sd), d2 = d1 - sd;
-    return put ? kp * black_norm_cdf(-d2) - ft * black_norm_cdf(-d1) : ft * black_norm_cdf(d1) - kp * black_norm_cdf(d2);
-}
+// tc_keep_cmc, tc_black, tc_weight_forward and the forward pass's two bodies: svmc_tilted_cond.h, shared with svmc_est.hip (row f18)
 
 // ---- the forward pass: cmc_forward_kernel's and cmc_forward_finish_kernel's statements ------------------------------------------
 __global__ __launch_bounds__(BLOCK) void tilted_cond_forward_kernel(TcTable t, size_t n)
 {
     __shared__ double lds[4 * 3];
-    const TcExpiry ex = t.expiries[blockIdx.y];
-    const size_t stride = static_cast<size_t>(gridDim.x) * BLOCK;
-    double v[3] = {0.0, 0.0, 0.0};
-    for (size_t i = static_cast<size_t>(blockIdx.x) * BLOCK + threadIdx.x; i < n; i += stride) {
-        double h, e;
-        if (tc_keep_cmc(ex.mu[i], ex.cv[i], h, e)) {
-            const double d = e - 1.0;
-            v[0] += d;
-            v[1] = fma(d, d, v[1]);
-            v[2] += 1.0;
-        }
-    }
-    block_sum_store<3>(v, lds, t.fwd_partials + (static_cast<size_t>(blockIdx.x) * t.m + blockIdx.y) * 3, 3);
+    tc_forward_body(t, n, lds);
 }
 
 // a block per expiry: the three column sums in row order, corr, and -- once per strike -- K' = K + corr and ln K'
 __global__ __launch_bounds__(BLOCK) void tilted_cond_forward_finish_kernel(TcTable t, int recenter)
 {
     __shared__ double lds[4];
-    const int i = blockIdx.x;
-    const TcExpiry ex = t.expiries[i];
-    const size_t ld = 3 * static_cast<size_t>(t.m);
-    const double *base = t.fwd_partials + 3 * static_cast<size_t>(i);
-    const double s0 = block_column_sum(base, t.rows, ld, lds);
-    __syncthreads();
-    const double s1 = block_column_sum(base + 1, t.rows, ld, lds);
-    __syncthreads();
-    const double cnt = block_column_sum(base + 2, t.rows, ld, lds);
-    __syncthreads();                                       // thread 0 has read the wave totals: lds[0] now carries corr to the block
-    if (threadIdx.x == 0) {
-        const double dmean = s0 / cnt;                     // 0 / 0 -> NaN like nanmean of an empty slice
-        const double corr = recenter ? ex.forward * dmean : 0.0;       // mean_kept(F e) - F
-        double *f = t.fwd + 4 * i;
-        f[0] = s0;
-        f[1] = s1;
-        f[2] = cnt;
-        f[3] = corr;
-        lds[0] = corr;
-    }
-    __syncthreads();
-    const double corr = lds[0];
-    for (int k = ex.k0 + static_cast<int>(threadIdx.x); k < ex.k1; k += BLOCK) {
-        const double kp = t.strikes[k] + corr;
-        t.kp[k] = kp;
-        t.ln_kp[k] = (kp > 0.0) ? log(kp) : 0.0;
-    }
+    tc_forward_finish_body(t, recenter, lds);
 }
 
 // ---- the weighted Black-76 sums -----------------------------------------------------------------------------------------------
@@ -198,18 +133,14 @@ __global__ __launch_bounds__(BLOCK) void tilted_cond_payoff_kernel(TcTable t, si
         put[k] = on ? t.is_put[kk] != 0.0 : false;
     }
     const double forward = ex.forward, ln_forward = ex.ln_forward;
-    constexpr double INF = __builtin_huge_val();
     const size_t stride = static_cast<size_t>(gridDim.x) * BLOCK;
     for (size_t i = static_cast<size_t>(blockIdx.x) * BLOCK + threadIdx.x; i < n; i += stride) {
         const double mu = ex.mu[i], cv = ex.cv[i];
         double h, e;
         if (!tc_keep_cmc(mu, cv, h, e)) continue;
         // once per (path, gamma): the weight and the shifted forward with its logarithm
-        const double w = exp_full(fma(half_g2, cv, gamma * mu));
-        const double lr = fma(g_half, cv, mu);
-        const double ft = forward * exp_full(lr), ln_ft = ln_forward + lr;
-        const double wf = w * ft;
-        if (!(w * w < INF && wf * wf < INF)) continue;     // W^2 and (W F_t)^2 finite (a NaN fails the comparison)
+        double w, et, ft, ln_ft;
+        if (!tc_weight_forward(mu, cv, gamma, half_g2, g_half, forward, ln_forward, w, et, ft, ln_ft)) continue;
         const double sd = sqrt(cv), inv_sd = 1.0 / sd;     // once per path
         const double v = w - 1.0;
         const double wds = w * ((ft - corr) - forward);

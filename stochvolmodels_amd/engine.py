@@ -363,6 +363,13 @@ TILTED_STATS_FIELDS = ("normalizer", "normalizer_stderr", "gamma_forward", "gamm
                        "n_kept", "n_dropped", "sum_weights")
 # the conditional estimator under the kernel (include/svmc_ext.h, svmc_tilted_cond_payoff_chain): the same block, the same meanings
 TILTED_COND_STATS_FIELDS = TILTED_STATS_FIELDS
+# ... and its Greeks (include/svmc_est.h, svmc_tilted_cond_greeks_chain): the result rows, its own statistics block, and the block the
+# routes return -- the payoff tail's with the count of cv == 0 paths
+TCG_ROWS = 8                   # SVMC_TCG_ROWS
+TCG_FIELDS = ("delta", "delta_stderr", "dual_delta", "dual_delta_stderr", "gamma", "gamma_stderr", "dual_gamma", "dual_gamma_stderr")
+TCG_STATS_DOUBLES = 4          # SVMC_TCG_STATS_DOUBLES
+TCG_STATS_FIELDS = ("sum_weights", "n_kept", "n_dropped", "n_zero_cv")
+TILTED_COND_GREEKS_STATS_FIELDS = TILTED_STATS_FIELDS + ("n_zero_cv",)
 
 
 # ---- conditional Monte Carlo (include/svmc.h, svmc_cmc_payoff_chain): the per-expiry statistics ----------------------------------
@@ -465,6 +472,22 @@ def tilted_results(prices: np.ndarray, stderrs: np.ndarray, stats: np.ndarray, c
     cut = lambda a: [[a[g * K + int(offs[i]):g * K + int(offs[i + 1])].reshape(ch["shapes"][i]).copy()    # noqa: E731
                       for i in range(ch["m"])] for g in range(G)]
     return cut(prices), cut(stderrs), np.array(stats, dtype=np.float64).reshape(G, ch["m"], TILTED_STATS_DOUBLES)
+
+
+def tilted_greeks_results(greeks: np.ndarray, stats: np.ndarray, ch: dict):
+    """flat [G][TCG_ROWS][K] Greeks and [G][m][TCG_STATS_DOUBLES] statistics -> ([G] dicts {field of TCG_FIELDS: [m] arrays in the
+    strikes' shapes}, stats [G, m, TCG_STATS_DOUBLES])"""
+    G, K, offs = ch["gammas"].size, ch["total"], ch["offs"]
+    rows = np.asarray(greeks, dtype=np.float64)[:G * TCG_ROWS * K].reshape(G, TCG_ROWS, K)
+    out = [{name: [rows[g, r, int(offs[i]):int(offs[i + 1])].reshape(ch["shapes"][i]).copy() for i in range(ch["m"])]
+            for r, name in enumerate(TCG_FIELDS)} for g in range(G)]
+    return out, np.array(stats, dtype=np.float64).reshape(G, ch["m"], TCG_STATS_DOUBLES)
+
+
+def tilted_greeks_stats_dicts(stats: np.ndarray) -> list:
+    """stats [m, 9] of one gamma -> one dict per expiry, keys TILTED_COND_GREEKS_STATS_FIELDS (the three counts as ints)"""
+    return [{k: (int(v) if k in ("n_kept", "n_dropped", "n_zero_cv") else float(v)) for k, v in zip(TILTED_COND_GREEKS_STATS_FIELDS, row)}
+            for row in stats]
 
 
 def tilted_stats_dicts(stats: np.ndarray) -> list:
@@ -1207,17 +1230,40 @@ class HipEngine:
             prices.ctypes.data_as(dp), stderrs.ctypes.data_as(dp), stats.ctypes.data_as(dp), ws_ptr, nbytes.value, self.stream), what))
         return tilted_results(prices[:G * K], stderrs[:G * K], stats, ch)
 
-    def price_hawkesjd_chain_tilted_cond(self, ch: dict, params: np.ndarray, nb_steps_per_year: int, seed: int, call_id: int, gammas,
-                                         recenter: bool):
-        """the Hawkes chain by conditional Monte Carlo under the risk-premia kernel for every gamma from ONE stepping launch (ch:
-        tilted_chain_arrays with ttms): hawkesjd_chain_cond from the origin (0, lambda_p, lambda_m) into snapshot rows [0, m) (mu)
-        and [m, 2m) (cv), then tilted_conditional_payoffs on them.  TWO C calls: there is no fused session entry, because sessions
-        belong to the closed core (libsvmc.so, 143 entry points) and the tail lives in libsvmc_ext.so.  The step grid is the fused
-        drivers' (svmc_chain.hip expiry_grids), so the mu rows are those svmc_hawkesjd_chain_price_cmc steps at this seed."""
-        params = np.ascontiguousarray(params, dtype=np.float64)
+    def tilted_conditional_greeks(self, forwards, strikes: Sequence[np.ndarray], codes: Sequence[np.ndarray], gammas,
+                                  recenter: bool = False, mu_rows: Optional[Sequence[int]] = None,
+                                  cv_rows: Optional[Sequence[int]] = None):
+        """delta, dual delta, gamma and dual gamma of tilted_conditional_payoffs' prices, each with its error
+        (svmc_tilted_cond_greeks_chain, include/svmc_est.h: libsvmc_est.so) on the same resident (mu, cv): expiry i reads snapshot
+        rows mu_rows[i] and cv_rows[i], or, with both None, the one expiry reads the current state (x, cv).  Returns ([G] dicts
+        {field of TCG_FIELDS: [m] -> [K_i]}, stats [G, m, TCG_STATS_FIELDS]); undiscounted.  Price and error are the payoff
+        tail's: call tilted_conditional_payoffs on the same rows."""
+        ch = tilted_chain_arrays(forwards, strikes, codes, gammas)
+        m, K, G = ch["m"], ch["total"], ch["gammas"].size
+        if (mu_rows is None) != (cv_rows is None) or ((m != 1) if mu_rows is None else (len(mu_rows) != m or len(cv_rows) != m)):
+            raise ValueError("one mu row and one cv row per expiry (the current state serves one expiry)")
+        mus = [self.x.ptr] if mu_rows is None else [self.snapshot_ptr(r) for r in mu_rows]
+        cvs = [self.cv.ptr] if cv_rows is None else [self.snapshot_ptr(r) for r in cv_rows]
+        est = _lib.load_est()
+        what = "svmc_tilted_cond_greeks_chain"
+        nbytes = C.c_size_t(0)
+        _lib.check_ext(est.svmc_tilted_cond_greeks_workspace_bytes(self.n_path, m, K, G, C.byref(nbytes)), what)
+        ws_ptr, _ = self.alloc_sums((nbytes.value + 7) // 8, "tilted_cond_greeks_workspace")
+        greeks, stats = np.empty(max(G * TCG_ROWS * K, 1)), np.empty(G * m * TCG_STATS_DOUBLES)
+        dp = C.POINTER(C.c_double)
+        self._timed("tilted_cond_greeks_kernel", lambda: _lib.check_ext(est.svmc_tilted_cond_greeks_chain(
+            (C.c_void_p * m)(*mus), (C.c_void_p * m)(*cvs), self.n_path, ch["forwards"].ctypes.data_as(dp), m,
+            ch["strikes"].ctypes.data_as(dp), ch["codes"].ctypes.data_as(C.POINTER(C.c_int8)),
+            ch["offs"].ctypes.data_as(C.POINTER(C.c_size_t)), ch["gammas"].ctypes.data_as(dp), G, int(bool(recenter)),
+            greeks.ctypes.data_as(dp), stats.ctypes.data_as(dp), ws_ptr, nbytes.value, self.stream), what))
+        return tilted_greeks_results(greeks, stats, ch)
+
+    def step_hawkesjd_chain_cond_rows(self, ch: dict, params: np.ndarray, nb_steps_per_year: int, seed: int, call_id: int) -> None:
+        """hawkesjd_chain_cond from the origin (0, lambda_p, lambda_m) into snapshot rows [0, m) (mu) and [m, 2m) (cv) for the
+        expiries of ch (tilted_chain_arrays with ttms).  The step grid is the fused drivers' (svmc_chain.hip expiry_grids), so the
+        mu rows are those svmc_hawkesjd_chain_price_cmc steps at this seed."""
         if int(nb_steps_per_year) <= 0:
             raise ValueError("nb_steps_per_year must be positive")
-        m = ch["m"]
         nbs, dts, t0 = [], [], 0.0
         for t in ch["ttms"]:
             d = float(t) - t0
@@ -1226,10 +1272,36 @@ class HipEngine:
             dts.append(d if nb == 1 else d / float(nb))
             t0 = float(t)
         self.fill_state(0.0, float(params[6]), float(params[11]))         # SVMC_HAWKESJD_PARAMS: lambda_p, lambda_m
-        self.hawkesjd_chain_cond(nbs, dts, params, seed, call_id, mu_row=0, cv_row=m)
+        self.hawkesjd_chain_cond(nbs, dts, params, seed, call_id, mu_row=0, cv_row=ch["m"])
+
+    def price_hawkesjd_chain_tilted_cond(self, ch: dict, params: np.ndarray, nb_steps_per_year: int, seed: int, call_id: int, gammas,
+                                         recenter: bool):
+        """the Hawkes chain by conditional Monte Carlo under the risk-premia kernel for every gamma from ONE stepping launch (ch:
+        tilted_chain_arrays with ttms): step_hawkesjd_chain_cond_rows, then tilted_conditional_payoffs on the rows.  TWO C calls:
+        there is no fused session entry, because sessions belong to the closed core (libsvmc.so, 143 entry points) and the tail
+        lives in libsvmc_ext.so."""
+        params = np.ascontiguousarray(params, dtype=np.float64)
+        m = ch["m"]
+        self.step_hawkesjd_chain_cond_rows(ch, params, nb_steps_per_year, seed, call_id)
         return self.tilted_conditional_payoffs(ch["forwards"], [k.reshape(s) for k, s in zip(ch["strikes_ttms"], ch["shapes"])],
                                                ch["codes_ttms"], gammas, recenter, mu_rows=list(range(m)),
                                                cv_rows=list(range(m, 2 * m)))
+
+    def price_hawkesjd_chain_tilted_cond_greeks(self, ch: dict, params: np.ndarray, nb_steps_per_year: int, seed: int, call_id: int,
+                                                gammas, recenter: bool):
+        """price_hawkesjd_chain_tilted_cond with the derivatives of its prices in the forward and the strike: ONE
+        stepping call for all gammas, then the two tails on the same rows -- svmc_tilted_cond_payoff_chain (libsvmc_ext.so: price,
+        error, statistics) and svmc_tilted_cond_greeks_chain (libsvmc_est.so).  Returns ([G] dicts {field of CMC_GREEKS_FIELDS:
+        [m] -> [K_i] in the strikes' shapes}, stats [G, m, TILTED_COND_GREEKS_STATS_FIELDS])."""
+        params = np.ascontiguousarray(params, dtype=np.float64)
+        m = ch["m"]
+        self.step_hawkesjd_chain_cond_rows(ch, params, nb_steps_per_year, seed, call_id)
+        strikes = [k.reshape(s) for k, s in zip(ch["strikes_ttms"], ch["shapes"])]
+        rows = dict(mu_rows=list(range(m)), cv_rows=list(range(m, 2 * m)))
+        prices, stderrs, stats = self.tilted_conditional_payoffs(ch["forwards"], strikes, ch["codes_ttms"], gammas, recenter, **rows)
+        greeks, gstats = self.tilted_conditional_greeks(ch["forwards"], strikes, ch["codes_ttms"], gammas, recenter, **rows)
+        out = [dict(price=p, stderr=e, **g) for p, e, g in zip(prices, stderrs, greeks)]
+        return out, np.concatenate([stats, gstats[:, :, 3:4]], axis=2)
 
     def _fused_cmc_call(self, ch: dict, call, kernel_name: str):
         res, stats = np.empty((2, max(ch["total"], 1))), np.empty((ch["m"], CMC_STATS_DOUBLES))

@@ -37,6 +37,10 @@ Conditional Monte Carlo under the risk-premia kernel (hawkesjd_mc_chain_pricer_c
 reference): the two rows above joined by the Esscher identity -- a path's weight exp(gamma mu + gamma^2 cv / 2) carries no diffusion
 noise and multiplies a Black-76 price at the forward shifted by gamma cv (include/svmc_ext.h, libsvmc_ext.so's
 tilted_cond_payoff_kernel on the rows hawkes_chain_cond_kernel leaves).
+Its Greeks and the bandwidth-free density under the kernel (hawkesjd_mc_chain_greeks_conditional_with_risk_premia(_gammas),
+HawkesJDPricer.get_log_return_mc_pdf_conditional_under_risk_kernel; not in the reference): the weight depends on neither the forward
+nor the strike, so the derivatives are weighted means of per-path Black-76 derivatives at the shifted forward (include/svmc_est.h,
+libsvmc_est.so's tilted_cond_greeks_kernel on the same rows).
 The reference's quirks are kept: `risk_premia_gamma` is accepted and unused by hawkesjd_mc_chain_pricer, `is_spot_measure` is ignored
 by it, and a variable_type other than LOG_RETURN raises (the reference would price the log-return as a variance).  Under the
 risk-premia kernel: the forwards follow zip(ttms, forwards) (entries beyond the shorter stay 1.0), discfactors are ignored
@@ -59,7 +63,7 @@ from .. import dist as svdist
 from ..analytic import ODE_ATOL, ODE_RTOL, AnalyticGrid, chain_prices_from_sums, chain_sums
 from ..data.option_chain import OptionChain
 from ..engine import (DeviceBuffer, get_engine, marshalled_chain, option_type_codes, tilted_chain_arrays,
-                      tilted_gammas, tilted_type_codes)
+                      tilted_gammas, tilted_greeks_stats_dicts, tilted_type_codes)
 from ..mc_chain import chain_shaped, check_many_args, many_job_chunks, many_job_streams, many_jobs_shaped, variable_type_code
 from ..utils import mgf_pricer as mgfp
 from ..utils.calibration import ImpliedVolObjective, chain_calibration_weights
@@ -363,6 +367,40 @@ class HawkesJDPricer(ModelPricer):
                                                                      strikes_ttms=option_chain.strikes_ttms,
                                                                      optiontypes_ttms=option_chain.optiontypes_ttms, nb_path=nb_path,
                                                                      **params.to_dict(), **kwargs)
+
+    def model_mc_chain_greeks_conditional_with_risk_premia(self, option_chain: OptionChain, params: HawkesJDParams,
+                                                           nb_path: int = 100000, **kwargs) -> dict:
+        """model_mc_price_chain_conditional_with_risk_premia with delta, dual delta, gamma and dual gamma under the kernel
+        (hawkesjd_mc_chain_greeks_conditional_with_risk_premia); the gamma is the parameter set's; extensions seed=,
+        nb_steps_per_year=, recenter_forward=, return_stats="""
+        if params.risk_premia_gamma is None:
+            raise ValueError("risk_premia_gamma must be set for the risk-premia pricer")
+        return hawkesjd_mc_chain_greeks_conditional_with_risk_premia(ttms=option_chain.ttms, forwards=option_chain.forwards,
+                                                                     discfactors=option_chain.discfactors,
+                                                                     strikes_ttms=option_chain.strikes_ttms,
+                                                                     optiontypes_ttms=option_chain.optiontypes_ttms, nb_path=nb_path,
+                                                                     **params.to_dict(), **kwargs)
+
+    def get_log_return_mc_pdf_conditional_under_risk_kernel(self, params: HawkesJDParams, ttm: float, x_grid: np.ndarray,
+                                                            risk_premia_gammas, nb_path: int = 100000, seed: Optional[int] = None,
+                                                            return_stderr: bool = False,
+                                                            nb_steps_per_year: int = NB_STEPS_PER_YEAR):
+        """the density of the simulated log-return under exp(gamma x) at x_grid for every gamma, WITHOUT a bandwidth: the dual
+        gamma of the conditional estimator under the kernel at K = exp(x), F = 1, no recentring --
+        pdf_gamma(x) = sum_j W_j N(x; mu_j + gamma sigma^2 ttm, sigma^2 ttm) / sum_j W_j.  Normalised by the weights: it integrates
+        to the weight share of the kept paths (1 when none is dropped; 0 at sigma = 0, where every path is a point mass).  One
+        stepping call for all gammas.  Returns pdf [gamma][x] (x in x_grid's shape), with return_stderr=True (pdf, its standard
+        error)."""
+        x = np.asarray(x_grid, dtype=np.float64)
+        strikes = np.exp(x.ravel())
+        out = hawkesjd_mc_chain_greeks_conditional_with_risk_premia_gammas(
+            ttms=np.array([float(ttm)]), forwards=np.array([1.0]), discfactors=np.array([1.0]), strikes_ttms=[strikes],
+            optiontypes_ttms=[np.full(strikes.size, "C")], risk_premia_gammas=risk_premia_gammas, nb_path=nb_path,
+            nb_steps_per_year=nb_steps_per_year, seed=seed, recenter_forward=False, **_model_kwargs(params))
+        pdf = np.array([(strikes * g["dual_gamma"][0]).reshape(x.shape) for g in out])
+        if return_stderr:
+            return pdf, np.array([(strikes * g["dual_gamma_stderr"][0]).reshape(x.shape) for g in out])
+        return pdf
 
     def model_mc_price_chain_many(self, option_chain: OptionChain, params_list: Sequence[HawkesJDParams], nb_path: int = 100000,
                                   seeds: Optional[Sequence[int]] = None, nb_steps_per_year: int = NB_STEPS_PER_YEAR, **kwargs
@@ -905,6 +943,71 @@ def hawkesjd_mc_chain_pricer_conditional_with_risk_premia(ttms: np.ndarray, forw
         risk_premia_gammas=[risk_premia_gamma], nb_path=nb_path, nb_steps_per_year=nb_steps_per_year, seed=seed,
         recenter_forward=recenter_forward, return_forwards=return_forwards, **kwargs)
     return tuple(o[0] for o in out)
+
+
+def hawkesjd_mc_chain_greeks_conditional_with_risk_premia_gammas(ttms: np.ndarray, forwards: np.ndarray, discfactors: np.ndarray,
+                                                                 strikes_ttms: Sequence[np.ndarray],
+                                                                 optiontypes_ttms: Sequence[np.ndarray], lambda_p: float,
+                                                                 lambda_m: float, mu: float, sigma: float, shift_p: float,
+                                                                 mean_p: float, shift_m: float, mean_m: float, theta_p: float,
+                                                                 kappa_p: float, beta1_p: float, beta2_p: float, theta_m: float,
+                                                                 kappa_m: float, beta1_m: float, beta2_m: float,
+                                                                 risk_premia_gammas: Sequence[float] = (0.0,),
+                                                                 nb_path: int = 100000,
+                                                                 variable_type: VariableType = VariableType.LOG_RETURN,
+                                                                 nb_steps_per_year: int = NB_STEPS_PER_YEAR,
+                                                                 seed: Optional[int] = None, recenter_forward: bool = False,
+                                                                 return_stats: bool = False, comm=None, devices=None,
+                                                                 risk_premia_gamma=None, wrt: Optional[Sequence[str]] = ()) -> list:
+    """hawkesjd_mc_chain_pricer_conditional_with_risk_premia_gammas with the derivatives of its prices in the forward and the
+    strike (include/svmc_est.h).  The weight exp(gamma mu + gamma^2 cv / 2) depends on neither, so each
+    derivative is the weighted mean of a per-path Black-76 derivative at the shifted forward, with the ratio estimator's error: the
+    EXACT derivatives of the price that pricer returns at the same seed.  The arguments are that pricer's, return_stats= in the
+    place of return_forwards=.  Returns one dict per gamma of chain-shaped lists with the ten keys of engine.CMC_GREEKS_FIELDS:
+    price, stderr (bit-equal to the conditional pricer under the kernel at the seed), delta, dual_delta, gamma, dual_gamma, each
+    with its _stderr; with return_stats=True also "stats", per expiry the dict of engine.TILTED_COND_GREEKS_STATS_FIELDS (that
+    pricer's block and n_zero_cv, the kept paths whose conditional variance is zero: they add no gamma).  All values are
+    UNDISCOUNTED.  price = F delta + K dual_delta and F^2 gamma = K^2 dual_gamma hold to rounding; with recenter_forward the
+    errors ignore the noise of the recentring mean, as the price's does.  ONE stepping call for all gammas, then the two tails
+    (libsvmc_ext.so's for price and error, libsvmc_est.so's for the derivatives).  Refusals, each before any engine is asked for:
+    that pricer's ('IC' / 'IP', variables other than the log-return, comm= / devices=) and any wrt= but the default () (parameter
+    sensitivities under the kernel are not built: NotImplementedError).  wrt=None is refused too: in the sibling routes
+    (logsv_mc_chain_greeks_conditional, hawkesjd_mc_chain_greeks_conditional) None and "all" ask for EVERY parameter, so it is a
+    request, not its absence.  risk_premia_gamma= is accepted and unused, as in that pricer: it is there only so that
+    **params.to_dict() can be passed; the gammas are risk_premia_gammas.  Not in the reference API."""
+    who = "hawkesjd_mc_chain_greeks_conditional_with_risk_premia"
+    codes = check_conditional_request(who, variable_type, comm, devices, optiontypes_ttms)
+    if wrt is None or isinstance(wrt, str) or len(wrt) > 0:
+        raise NotImplementedError(f"{who}: wrt=: parameter sensitivities under the risk-premia kernel are not covered")
+    strikes_ttms = [np.asarray(k, dtype=np.float64) for k in strikes_ttms]
+    ch = tilted_chain_arrays(forwards, strikes_ttms, codes, risk_premia_gammas, ttms=ttms)
+    block = params_block(lambda_p=lambda_p, lambda_m=lambda_m, mu=mu, sigma=sigma, shift_p=shift_p, mean_p=mean_p,
+                         shift_m=shift_m, mean_m=mean_m, theta_p=theta_p, kappa_p=kappa_p, beta1_p=beta1_p, beta2_p=beta2_p,
+                         theta_m=theta_m, kappa_m=kappa_m, beta1_m=beta1_m, beta2_m=beta2_m)
+    eng = get_engine(int(nb_path))
+    rng_seed, call_id = next_rng_call(seed)
+    fields, stats = eng.price_hawkesjd_chain_tilted_cond_greeks(ch, block, int(nb_steps_per_year), rng_seed, call_id, ch["gammas"],
+                                                                bool(recenter_forward))
+    out = [dict(f) for f in fields]
+    if return_stats:
+        for d, st in zip(out, stats):
+            d["stats"] = tilted_greeks_stats_dicts(st)
+    return out
+
+
+def hawkesjd_mc_chain_greeks_conditional_with_risk_premia(ttms: np.ndarray, forwards: np.ndarray, discfactors: np.ndarray,
+                                                          strikes_ttms: Sequence[np.ndarray], optiontypes_ttms: Sequence[np.ndarray],
+                                                          risk_premia_gamma: float = None, nb_path: int = 100000,
+                                                          nb_steps_per_year: int = NB_STEPS_PER_YEAR, seed: Optional[int] = None,
+                                                          recenter_forward: bool = False, return_stats: bool = False, **kwargs) -> dict:
+    """hawkesjd_mc_chain_greeks_conditional_with_risk_premia_gammas at ONE gamma, so the two agree bit for bit: its dict.  kwargs:
+    the model parameters (and variable_type=, comm=, devices=, wrt=) of that function."""
+    if risk_premia_gamma is None:
+        raise ValueError("risk_premia_gamma must be set for the risk-premia pricer")
+    return hawkesjd_mc_chain_greeks_conditional_with_risk_premia_gammas(
+        ttms=ttms, forwards=forwards, discfactors=discfactors, strikes_ttms=strikes_ttms, optiontypes_ttms=optiontypes_ttms,
+        risk_premia_gammas=[risk_premia_gamma], nb_path=nb_path, nb_steps_per_year=nb_steps_per_year, seed=seed,
+        recenter_forward=recenter_forward, return_stats=return_stats, **kwargs)[0]
 
 
 def _model_kwargs(params: HawkesJDParams) -> Dict[str, Any]:

@@ -11,8 +11,8 @@ from typing import Tuple
 
 import numpy as np
 
-from ..engine import (get_engine, option_type_codes, payoff_finalize, payoff_shifts, tilted_chain_arrays, tilted_stats_dicts,
-                      tilted_type_codes)
+from ..engine import (get_engine, option_type_codes, payoff_finalize, payoff_shifts, tilted_chain_arrays,
+                      tilted_greeks_stats_dicts, tilted_stats_dicts, tilted_type_codes)
 from ..mc_chain import variable_type_code
 from .config import VariableType
 
@@ -121,6 +121,40 @@ def compute_mc_vars_payoff_conditional_with_gamma(mu: np.ndarray, cv: np.ndarray
     if return_stats:
         out = out + ([tilted_stats_dicts(st)[0] for st in stats],)
     return tuple(o[0] for o in out) if single else out
+
+
+def compute_mc_vars_greeks_conditional_with_gamma(mu: np.ndarray, cv: np.ndarray, forward: float, strikes_ttm: np.ndarray,
+                                                  optiontypes_ttm: np.ndarray, risk_premia_gamma, recenter: bool = False,
+                                                  return_stats: bool = False,
+                                                  variable_type: VariableType = VariableType.LOG_RETURN):
+    """compute_mc_vars_payoff_conditional_with_gamma with the derivatives of its prices in the forward and the strike
+    (include/svmc_est.h's svmc_tilted_cond_greeks_chain; host arrays of any model's per-path (mu, cv)): a dict in the strikes'
+    shape with the ten keys of engine.CMC_GREEKS_FIELDS -- price, stderr (that function's), delta, dual_delta, gamma, dual_gamma,
+    each with its _stderr; undiscounted -- and with return_stats=True "stats", the dict of engine.TILTED_COND_GREEKS_STATS_FIELDS.
+    risk_premia_gamma: one gamma -- the dict -- or a sequence of up to 16 -- a list of dicts, one per gamma, from one upload.
+    'C' / 'P' only (others: ValueError("not implemented")), LOG_RETURN only (NotImplementedError)."""
+    if variable_type_code(variable_type) != 1:
+        raise NotImplementedError(f"variable_type={variable_type}: the risk-premia kernel weights the log-return only")
+    codes = tilted_type_codes(optiontypes_ttm)                   # ValueError("not implemented")
+    strikes = np.asarray(strikes_ttm, dtype=np.float64)
+    single = np.ndim(risk_premia_gamma) == 0
+    ch = tilted_chain_arrays([float(forward)], [strikes], [codes], [float(risk_premia_gamma)] if single else risk_premia_gamma)
+    mu = np.ascontiguousarray(mu, dtype=np.float64).ravel()
+    cv = np.ascontiguousarray(cv, dtype=np.float64).ravel()
+    if mu.size != cv.size or mu.size == 0:
+        raise ValueError("mu and cv must be non-empty and of one length")
+    eng = get_engine(mu.size)
+    eng.upload(eng.x.ptr, mu)
+    eng.upload(eng.cv.ptr, cv)
+    prices, stderrs, stats = eng.tilted_conditional_payoffs(ch["forwards"], [strikes], [codes], ch["gammas"], bool(recenter))
+    greeks, gstats = eng.tilted_conditional_greeks(ch["forwards"], [strikes], [codes], ch["gammas"], bool(recenter))
+    out = []
+    for p, e, g, st, gst in zip(prices, stderrs, greeks, stats, gstats):
+        d = dict(price=p[0], stderr=e[0], **{name: rows[0] for name, rows in g.items()})
+        if return_stats:
+            d["stats"] = tilted_greeks_stats_dicts(np.concatenate([st, gst[:, 3:4]], axis=1))[0]
+        out.append(d)
+    return out[0] if single else out
 
 
 def compute_mc_vars_greeks_conditional(mu: np.ndarray, cv: np.ndarray, ttm: float, forward: float, strikes_ttm: np.ndarray,
