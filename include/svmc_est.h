@@ -102,6 +102,60 @@ SVMC_EST_API int svmc_tilted_cond_greeks_chain(const double *const *mu_snapshots
                                                int recenter, double *greeks_host, double *stats_host, void *workspace,
                                                size_t workspace_bytes, svmc_stream_t stream);
 
+/* ---- the mixture density of the simulated log-return, under the kernel or not (src svmc_est.hip) -----------
+ * THE DENSITY above as an estimator of its own: the "dedicated density kernel on the e^{gamma x} identity" of row f18's list.
+ * Model-agnostic: any generator's per-path conditional mean mu[j] and variance cv[j] of the log-return.
+ * Inputs: device rows mu[j], cv[j] per expiry; points x_p per expiry, concatenated, expiry i owning [point_offsets_host[i],
+ * point_offsets_host[i + 1]) as strikes are laid out above; up to SVMC_TILTED_MAX_GAMMAS gammas.
+ * Which paths count: a path passes iff f11's rule holds (mu, cv and exp(mu + cv / 2) finite, cv >= 0: the statement the Greeks
+ * above share).  A passing path with cv == 0 is a point mass: it adds nothing to any x-sum, it is counted (n_zero_cv) and its
+ * weight still enters sum W, as above.
+ * Gamma-independent sums over the f11-kept paths with cv > 0, with n_jp = N(x_p; mu_j, cv_j) = exp(-z^2 / 2) / (sd_j sqrt(2 pi)),
+ * z = (x_p - mu_j) / sd_j:
+ *   S1_p = sum_j n_jp,   S2_p = sum_j n_jp^2                                   ONE exp per (path, point)
+ * Per gamma, W_gj = exp(gamma mu_j + gamma^2 cv_j / 2):
+ *   per (expiry, gamma): sum W, sum W^2 over the f11-kept paths whose W^2 is finite, and n_weight_dropped, the count of f11-kept
+ *   paths whose W^2 is not;   per (point, gamma): C_pg = sum_j W_gj n_jp       one FMA, no transcendental
+ * Results:
+ *   pdf_g(x_p) = e^{gamma x_p} S1_p / sum W_g
+ *   error      = sqrt(max(e^{2 gamma x_p} S2_p - 2 pdf e^{gamma x_p} C_pg + pdf^2 sum W_g^2, 0)) / sum W_g
+ * Because W_j N(x; mu_j + gamma cv_j, cv_j) = e^{gamma x} N(x; mu_j, cv_j), pdf_g is the Greeks entry's K dual_gamma at K = exp(x),
+ * F = 1, recenter = 0, and the error is its ratio-estimator error sqrt(sum_j (W_j (v_j - pdf))^2) / sum W, term for term (v_j the
+ * path's Gaussian under the kernel: W_j v_j = e^{gamma x} n_jp).  One kept path gives error 0.  gamma = 0 has W = 1 and
+ * e^{gamma x} = 1; 0 times anything is never formed.  pdf_g integrates to the weight share of the kept paths with cv > 0; it is not
+ * normalised further.  No kept path gives NaN and is NOT an error of the call.
+ * TWO DELIBERATE DIFFERENCES from the Greeks entry's keep rule:
+ *   - that entry drops a path PER GAMMA when W^2 or (W F_t)^2 overflows and re-sums without it.  Here S1 and S2 are shared by all
+ *     gammas, so a gamma with n_weight_dropped > 0 returns NaN for its pdf and its error and its statistics row says how many
+ *     paths failed; the other gammas of the call are untouched, and the call is not refused.  The Greeks entry still serves such
+ *     a gamma;
+ *   - (W F_t)^2 is not part of the rule: no forward enters a density.
+ * Statistics per (gamma, expiry): sum W, n_kept (f11's), n_dropped = n_path - n_kept, n_zero_cv, n_weight_dropped.
+ * Every sum has a fixed order that depends on n_path alone: a gamma's, an expiry's and a point's results are the same bits
+ * whichever others share the call; sum W, n_kept and n_zero_cv are the Greeks entry's bits on rows where it drops no weight.  No
+ * atomics, no scratch, LDS for the block sums' exchange only.
+ *
+ *   svmc_cond_density_workspace_bytes   host only: the device workspace that serves any call of n_expiries expiries and
+ *                              total_points points at this n_path and n_gammas (it holds a row of weights per (expiry, gamma)).
+ *   svmc_cond_density_chain    mu_snapshots_host, cv_snapshots_host: HOST arrays of n_expiries DEVICE pointers.  pdf_host,
+ *                              stderr_host: [n_gammas][sum P_i]; stats_host: [n_gammas][n_expiries][SVMC_CD_STATS_DOUBLES]; host
+ *                              arrays.  One upload of the call's table, three launches on `stream` with no host round trip between
+ *                              them (the weights with the statistics' sums, the Gaussians, the finish), one download, one
+ *                              synchronise.  An expiry without points is legal: its statistics are still returned.
+ * Everything is checked before anything is launched, and a refused call leaves the output arrays untouched:
+ * SVMC_ERR_INVALID_ARGUMENT for a null pointer (a null snapshot among them), n_path < 1, n_expiries < 1, n_gammas outside
+ * 1 .. SVMC_TILTED_MAX_GAMMAS, point offsets that do not start at 0 or decrease, a gamma or point that is not finite;
+ * SVMC_ERR_WORKSPACE for a workspace below svmc_cond_density_workspace_bytes; SVMC_ERR_HIP for a failure of the runtime.
+ * Left out: the many-job form, several GPUs, a derivative of the density. */
+#define SVMC_CD_STATS_DOUBLES 5
+
+SVMC_EST_API int svmc_cond_density_workspace_bytes(size_t n_path, int n_expiries, size_t total_points, int n_gammas, size_t *bytes);
+SVMC_EST_API int svmc_cond_density_chain(const double *const *mu_snapshots_host, const double *const *cv_snapshots_host,
+                                         size_t n_path, int n_expiries, const double *points_host,
+                                         const size_t *point_offsets_host, const double *gammas_host, int n_gammas,
+                                         double *pdf_host, double *stderr_host, double *stats_host, void *workspace,
+                                         size_t workspace_bytes, svmc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -47,6 +47,7 @@ _EXPORTS = {
     "compute_mc_vars_greeks_conditional_with_gamma": "utils.mc_payoffs",
     "compute_mc_vars_greeks": "utils.mc_payoffs",
     "compute_mc_vars_greeks_conditional": "utils.mc_payoffs",
+    "compute_mc_vars_pdf_conditional": "utils.mc_payoffs",
     "compute_mc_vars_sens_conditional": "utils.mc_payoffs",
     "hawkesjd_mc_chain_pricer_with_risk_premia": "pricers.hawkes_jd_pricer",
     "hawkesjd_mc_chain_pricer_with_risk_premia_gammas": "pricers.hawkes_jd_pricer",

@@ -1,6 +1,7 @@
 // svmc_est.hip -- libsvmc_est.so, the estimators beside the core (include/svmc_est.h states the rule that keeps this library
-// open).  One translation unit on the header-only parts of csrc/; nothing of libsvmc.so or libsvmc_ext.so is
-// linked and no session is needed.
+// open).  One translation unit on the header-only parts of csrc/; nothing of libsvmc.so or libsvmc_ext.so
+// is linked and no session is needed.  Two estimators: the Greeks under the risk-premia kernel (below) and the mixture density of
+// the log-return (svmc_cond_density_chain: its block further down states its three launches).
 //
 // Conditional Monte Carlo Greeks under the exponential risk-premia kernel (svmc_tilted_cond_greeks_chain; the header states the
 // estimator, the degenerate cases and the two identities).  Four launches on one uploaded table:
@@ -269,6 +270,255 @@ __global__ __launch_bounds__(BLOCK) void tilted_cond_greeks_finish_kernel(TcgTab
     out[7 * K] = err[2];
 }
 
+// ---- the mixture density of the log-return (svmc_cond_density_chain; the header states the estimator) --------------
+// Three launches on one uploaded table:
+//   cond_density_weight_kernel   block (path block, expiry, gamma): W = exp(gamma mu + gamma^2 cv / 2) once per (path, gamma), stored
+//                                as a row of the workspace (0 for a path that f11's rule drops or whose W^2 is not finite), with the
+//                                (expiry, gamma) statistics sums -- row f18's statements and order, hence its bits
+//   cond_density_kernel          block (path block, group of up to CD_XT points of one expiry, tile of gammas): a thread forms
+//                                per path 1 / sd and 1 / (sd sqrt(2 pi)) once and reads the tile's weights, then per point z and ONE exp
+//                                for n = N(x; mu, cv), n and n^2 into S1 and S2 (stored by the first tile only) and per gamma one FMA
+//                                into C: no exp and no CDF per (path, point, gamma)
+//   cond_density_finish_kernel   a block per (point | expiry, gamma): the column sums in row order, e^{gamma x} once, pdf, error, statistics
+// Every accumulator is one (point) or one (point, gamma) and the block sum's tree is the same for every accumulator index: a gamma's, an
+// expiry's and a point's results are the same bits whichever others share the call, whatever the tiles are.
+//
+// Points per thread and gammas per tile, chosen by measurement on the MI355X (profiles/cond_density_bench.json, "variants": the tail for
+// 200 points at 10^5 | 2^20 paths, ms for 1 / 5 / 16 gammas; VGPRs and waves per SIMD of this kernel from the ISA metadata).  The
+// accumulators are XT (2 + GT) doubles in the first tile.
+//   XT, GT   VGPRs  waves   10^5 paths             2^20 paths
+//   2, 4       68     7     0.163 0.267 0.545      0.668 1.317 3.048
+//   4, 2       76     6     0.129 0.239 0.559      0.474 1.209 3.001
+//   4, 4       96     5     0.139 0.214 0.421      0.523 0.941 2.019
+//   8, 4      153     3     0.151 0.230 0.434      0.469 0.852 1.664
+//   4, 8      141     3     0.196 0.216 0.401      0.661 0.724 1.525
+//   8, 8      223     2     0.202 0.219 0.405      0.643 0.725 1.394
+//   2, 16     137     3     0.325 0.349 0.437      1.190 1.344 2.703
+//   4, 16     215     2     0.312 0.325 0.403      1.004 1.121 1.411
+// No one tile serves every count: a tile wider than the call wastes its FMAs and its registers on gammas nobody asked for (one gamma at
+// GT = 8: 1.3 to 1.4 times GT = 4's time), a narrower one repeats the exp per tile (five gammas at GT = 4: 1.3 times GT = 8's at 2^20
+// paths).  So the host picks the tile by the call's gamma count -- CD_GT for up to CD_GT gammas, CD_GT_WIDE beyond: 0.141 0.210 0.378 |
+// 0.510 0.785 1.598 ms in that run -- which changes no bit: an accumulator is one (point, gamma) whatever the tile, and a thread adds the
+// same paths in the same order.  XT = 8 is no better than 4 at either tile beyond 10 % at one gamma and 2^20 paths, and costs the waves.
+// THE WEIGHTS.  The other design forms W in the block, one exp per (path, gamma) and point group, and needs no pre-pass and no rows.
+// Measured in the same run with a build that is not kept, the statistics pass left in: at (4, 4) 0.164 0.257 0.479 | 0.699 1.241 2.447 ms,
+// 1.14 to 1.34 times the pre-pass's; at (8, 8) 1.04 to 1.24 times; at (4, 16) 1.06 to 1.59 times.  With 200 points in groups of 4 a block
+// repeats for 50 groups what the pre-pass does once, and the row it reads back is 8 bytes per (path, gamma) beside XT exponentials.  The
+// pre-pass is kept.
+#ifndef SVMC_CD_XT
+#define SVMC_CD_XT 4
+#endif
+#ifndef SVMC_CD_GT
+#define SVMC_CD_GT 4
+#endif
+#ifndef SVMC_CD_GT_WIDE
+#define SVMC_CD_GT_WIDE 8
+#endif
+constexpr int CD_XT = SVMC_CD_XT;
+constexpr int CD_GT = SVMC_CD_GT;
+constexpr int CD_GT_WIDE = SVMC_CD_GT_WIDE;
+constexpr int CD_NSTAT = 8;            // per (expiry, gamma): [sum W, sum W^2, kept, kept with cv == 0, kept with W^2 not finite], zeros
+                                       // up to eight: the block sum's halving tree, row f18's
+
+struct CdExpiry {
+    const double *mu, *cv;
+    int p0, p1;                        // its points [p0, p1)
+};
+// the device table of a call; the image (expiries .. gammas) is uploaded once
+struct CdTable {
+    const CdExpiry *expiries;          // [m]
+    const QuoteGroup *groups;          // [G] groups of up to CD_XT points of one expiry
+    const double *points;              // [P]
+    const double *gammas;              // [NG]
+    double *weights;                   // [m][NG][n]
+    double *s_partials;                // [rows][P][2]: S1, S2
+    double *c_partials;                // [rows][NG][P]
+    double *stat_partials;             // [rows][NG][m][CD_NSTAT]
+    double *out;                       // pdf [NG][P], errors [NG][P], statistics [NG][m][SVMC_CD_STATS_DOUBLES]: one block
+    int m, P, NG;
+    unsigned rows;
+};
+struct CdImage {
+    CdExpiry *expiries;
+    QuoteGroup *groups;
+    double *points, *gammas;
+};
+inline CdImage cd_image(Layout &w, int m, size_t P, int G, int NG)
+{
+    return CdImage{w.take<CdExpiry>(m), w.take<QuoteGroup>(G), w.take<double>(P), w.take<double>(NG)};     // (in this order)
+}
+inline size_t cd_out_doubles(int m, size_t P, int NG) { return static_cast<size_t>(NG) * (2 * P + static_cast<size_t>(SVMC_CD_STATS_DOUBLES) * m); }
+// ONE walk that is both the workspace's byte count and its carving; returns the bytes of the image, which the walk starts with
+inline size_t cd_workspace(Layout &w, size_t n_path, int m, size_t P, int G, int NG, CdTable &t)
+{
+    const size_t rows = quote_rows(n_path);
+    const CdImage im = cd_image(w, m, P, G, NG);
+    const size_t image_bytes = w.bytes();
+    t.expiries = im.expiries;
+    t.groups = im.groups;
+    t.points = im.points;
+    t.gammas = im.gammas;
+    t.out = w.take<double>(cd_out_doubles(m, P, NG));
+    t.s_partials = w.take<double>(rows * P * 2);
+    t.c_partials = w.take<double>(rows * NG * P);
+    t.stat_partials = w.take<double>(rows * NG * m * CD_NSTAT);
+    t.weights = w.take<double>(static_cast<size_t>(m) * NG * n_path);
+    t.m = m;
+    t.P = static_cast<int>(P);
+    t.NG = NG;
+    t.rows = static_cast<unsigned>(rows);
+    return image_bytes;
+}
+
+// grid (path blocks, expiries, gammas)
+__global__ __launch_bounds__(BLOCK) void cond_density_weight_kernel(CdTable t, size_t n)
+{
+    __shared__ double lds[4 * CD_NSTAT];
+    constexpr double INF = __builtin_huge_val();
+    const CdExpiry ex = t.expiries[blockIdx.y];
+    const double gamma = t.gammas[blockIdx.z];
+    const double half_g2 = 0.5 * gamma * gamma;
+    double *wrow = t.weights + (static_cast<size_t>(blockIdx.y) * t.NG + blockIdx.z) * n;
+    double acc[CD_NSTAT];
+#pragma unroll
+    for (int j = 0; j < CD_NSTAT; ++j) acc[j] = 0.0;
+    const size_t stride = static_cast<size_t>(gridDim.x) * BLOCK;
+    for (size_t i = static_cast<size_t>(blockIdx.x) * BLOCK + threadIdx.x; i < n; i += stride) {
+        const double mu = ex.mu[i], cv = ex.cv[i];
+        double h, e, w = 0.0;
+        if (tc_keep_cmc(mu, cv, h, e)) {
+            w = exp_full(fma(half_g2, cv, gamma * mu));    // tc_weight_forward's statement: gamma = 0 gives exp(0) = 1
+            acc[2] += 1.0;
+            if (cv == 0.0) acc[3] += 1.0;
+            if (w * w < INF) {
+                acc[0] += w;
+                acc[1] = fma(w, w, acc[1]);
+            } else {
+                acc[4] += 1.0;
+                w = 0.0;
+            }
+        }
+        wrow[i] = w;
+    }
+    const size_t slot = static_cast<size_t>(blockIdx.x) * t.NG + blockIdx.z;               // partials[path block][gamma]
+    block_sum_store<CD_NSTAT>(acc, lds, t.stat_partials + (slot * t.m + blockIdx.y) * CD_NSTAT, CD_NSTAT);
+}
+
+// FIRST: the tile that holds S1 and S2
+template <int XT, int GT, bool FIRST>
+__device__ __forceinline__ void cond_density_body(const CdTable &t, size_t n, double *lds)
+{
+    constexpr int NS = FIRST ? 2 * XT : 0;
+    constexpr int NV = NS + XT * GT;
+    constexpr int NSUM = block_sum_padded(NV);
+    const QuoteGroup g = t.groups[blockIdx.y];
+    const CdExpiry ex = t.expiries[g.expiry];
+    const int nk = g.nk;                                   // (block-uniform, >= 1)
+    const int g0 = static_cast<int>(blockIdx.z) * GT, ng = min(GT, t.NG - g0);
+    double x[XT], acc[NSUM];
+    const double *wrow[GT];
+#pragma unroll
+    for (int j = 0; j < NSUM; ++j) acc[j] = 0.0;
+#pragma unroll
+    for (int k = 0; k < XT; ++k) x[k] = t.points[g.k0 + ((k < nk) ? k : 0)];      // the unused points of a group repeat its first
+#pragma unroll
+    for (int q = 0; q < GT; ++q)                                                  // ... and the unused gammas of a tile likewise
+        wrow[q] = t.weights + (static_cast<size_t>(g.expiry) * t.NG + g0 + ((q < ng) ? q : 0)) * n;
+    const size_t stride = static_cast<size_t>(gridDim.x) * BLOCK;
+    for (size_t i = static_cast<size_t>(blockIdx.x) * BLOCK + threadIdx.x; i < n; i += stride) {
+        const double mu = ex.mu[i], cv = ex.cv[i];
+        double w[GT];
+#pragma unroll
+        for (int q = 0; q < GT; ++q) w[q] = wrow[q][i];
+        double h, e;
+        if (!tc_keep_cmc(mu, cv, h, e) || cv == 0.0) continue;         // a point mass adds nothing to any x-sum
+        const double inv_sd = 1.0 / sqrt(cv), f = inv_sd * 0.39894228040143267794;         // once per path
+#pragma unroll
+        for (int k = 0; k < XT; ++k) {
+            const double z = (x[k] - mu) * inv_sd;
+            const double nn = exp_full((-0.5 * z) * z) * f;
+            if constexpr (FIRST) {
+                acc[k] += nn;
+                acc[XT + k] = fma(nn, nn, acc[XT + k]);
+            }
+#pragma unroll
+            for (int q = 0; q < GT; ++q) acc[NS + q * XT + k] = fma(w[q], nn, acc[NS + q * XT + k]);
+        }
+    }
+    double *sp = t.s_partials + (static_cast<size_t>(blockIdx.x) * t.P + g.k0) * 2;
+    double *cp = t.c_partials + (static_cast<size_t>(blockIdx.x) * t.NG + g0) * t.P + g.k0;
+    const size_t P = static_cast<size_t>(t.P);
+    block_sum_apply<NSUM>(acc, lds, NV, [&](int j, double s) {
+        if (j < NS) {
+            const int which = j / XT, k = j - which * XT;
+            if (k < nk) sp[2 * k + which] = s;
+        } else {
+            const int q = (j - NS) / XT, k = (j - NS) - q * XT;
+            if (k < nk && q < ng) cp[q * P + k] = s;
+        }
+    });
+}
+
+// grid (path blocks, point groups, gamma tiles)
+template <int XT, int GT>
+__global__ __launch_bounds__(BLOCK) void cond_density_kernel(CdTable t, size_t n)
+{
+    __shared__ double lds[4 * block_sum_padded(XT * (2 + GT))];
+    if (blockIdx.z == 0)                                   // (block-uniform)
+        cond_density_body<XT, GT, true>(t, n, lds);
+    else
+        cond_density_body<XT, GT, false>(t, n, lds);
+}
+
+// A block per (column, gamma): columns [0, P) are the points, [P, P + m) the expiries' statistics
+__global__ __launch_bounds__(BLOCK) void cond_density_finish_kernel(CdTable t, size_t n)
+{
+    __shared__ double lds[4];
+    const int col = blockIdx.x, gi = blockIdx.y;
+    const size_t P = static_cast<size_t>(t.P), m = static_cast<size_t>(t.m), NG = static_cast<size_t>(t.NG);
+    const size_t ld_stat = NG * m * CD_NSTAT;
+    int i = col - t.P;                                     // the expiry (block-uniform)
+    if (col < t.P) {
+        i = 0;
+        while (i + 1 < t.m && col >= t.expiries[i].p1) ++i;            // expiries without points are skipped over
+    }
+    const double *st = t.stat_partials + (static_cast<size_t>(gi) * m + i) * CD_NSTAT;
+    double s[5];
+#pragma unroll
+    for (int q = 0; q < 5; ++q) {
+        if (q > 0) __syncthreads();
+        s[q] = block_column_sum(st + q, t.rows, ld_stat, lds);
+    }
+    const double W = s[0], Q = s[1], kept = s[2], bad = s[4];
+    if (col >= t.P) {
+        if (threadIdx.x != 0) return;
+        double *out = t.out + 2 * NG * P + (static_cast<size_t>(gi) * m + i) * SVMC_CD_STATS_DOUBLES;
+        out[0] = W;
+        out[1] = kept;
+        out[2] = static_cast<double>(n) - kept;
+        out[3] = s[3];
+        out[4] = bad;
+        return;
+    }
+    __syncthreads();
+    const double s1 = block_column_sum(t.s_partials + 2 * col, t.rows, 2 * P, lds);
+    __syncthreads();
+    const double s2 = block_column_sum(t.s_partials + 2 * col + 1, t.rows, 2 * P, lds);
+    __syncthreads();
+    const double c = block_column_sum(t.c_partials + static_cast<size_t>(gi) * P + col, t.rows, NG * P, lds);
+    if (threadIdx.x != 0) return;
+    // sum (W (v - pdf))^2 with W v = e^{gamma x} n: e^{2 gamma x} S2 - 2 pdf e^{gamma x} C + pdf^2 sum W^2.  One kept path: the estimate IS
+    // that path's value and the squares about it are zero identically
+    const double gamma = t.gammas[gi];
+    const double eg = (gamma == 0.0) ? 1.0 : exp_full(gamma * t.points[col]);              // once per (point, gamma)
+    const double nan = __builtin_nan("");
+    const double pdf = eg * s1 / W;                        // 0 / 0 -> NaN: no kept path
+    const double var = (kept > 1.0) ? fma(pdf, fma(pdf, Q, -2.0 * (eg * c)), (eg * eg) * s2) : 0.0;
+    const bool ok = bad == 0.0;
+    t.out[static_cast<size_t>(gi) * P + col] = ok ? pdf : nan;
+    t.out[(NG + gi) * P + col] = ok ? sqrt(fmax(var, 0.0)) / W : nan;
+}
+
 // ---- host -----------------------------------------------------------------------------------------------------------------------
 static bool tcg_sizes_ok(size_t n_path, int n_expiries, int n_gammas)
 {
@@ -361,10 +611,85 @@ int svmc_tilted_cond_greeks_chain(const double *const *mu_snapshots_host, const 
     std::vector<double> out(tcg_out_doubles(m, K, NG));
     SVMC_EST_TRY(hipMemcpyAsync(out.data(), t.out, out.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
     SVMC_EST_TRY(hipStreamSynchronize(stream));
-#undef SVMC_EST_TRY
     const size_t GRK = static_cast<size_t>(NG) * SVMC_TCG_ROWS * K;
     if (GRK > 0) memcpy(greeks_host, out.data(), GRK * sizeof(double));
     memcpy(stats_host, out.data() + GRK, static_cast<size_t>(NG) * m * SVMC_TCG_STATS_DOUBLES * sizeof(double));
+    return SVMC_OK;
+}
+
+int svmc_cond_density_workspace_bytes(size_t n_path, int n_expiries, size_t total_points, int n_gammas, size_t *bytes)
+{
+    if (bytes == nullptr || !tcg_sizes_ok(n_path, n_expiries, n_gammas)) return SVMC_ERR_INVALID_ARGUMENT;
+    CdTable t;
+    Layout w{nullptr};
+    cd_workspace(w, n_path, n_expiries, total_points, quote_groups_bound(n_expiries, total_points, CD_XT), n_gammas, t);
+    *bytes = w.bytes();
+    return SVMC_OK;
+}
+
+int svmc_cond_density_chain(const double *const *mu_snapshots_host, const double *const *cv_snapshots_host, size_t n_path, int n_expiries,
+                            const double *points_host, const size_t *point_offsets_host, const double *gammas_host, int n_gammas,
+                            double *pdf_host, double *stderr_host, double *stats_host, void *workspace, size_t workspace_bytes,
+                            svmc_stream_t stream_)
+{
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    // everything is checked before anything is launched
+    if (!mu_snapshots_host || !cv_snapshots_host || !points_host || !point_offsets_host || !gammas_host || !pdf_host || !stderr_host ||
+        !stats_host || !workspace)
+        return SVMC_ERR_INVALID_ARGUMENT;
+    if (!tcg_sizes_ok(n_path, n_expiries, n_gammas)) return SVMC_ERR_INVALID_ARGUMENT;
+    const int m = n_expiries, NG = n_gammas;
+    if (point_offsets_host[0] != 0) return SVMC_ERR_INVALID_ARGUMENT;
+    for (int i = 0; i < m; ++i) {
+        if (point_offsets_host[i + 1] < point_offsets_host[i] || point_offsets_host[i + 1] > (static_cast<size_t>(1) << 30))
+            return SVMC_ERR_INVALID_ARGUMENT;
+        if (!mu_snapshots_host[i] || !cv_snapshots_host[i]) return SVMC_ERR_INVALID_ARGUMENT;
+    }
+    const size_t P = point_offsets_host[m];
+    for (int z = 0; z < NG; ++z)
+        if (!std::isfinite(gammas_host[z])) return SVMC_ERR_INVALID_ARGUMENT;
+    for (size_t p = 0; p < P; ++p)
+        if (!std::isfinite(points_host[p])) return SVMC_ERR_INVALID_ARGUMENT;
+    const int G = quote_groups(m, point_offsets_host, CD_XT, false);
+    if (G > TCG_MAX_GROUPS || m > TCG_MAX_GROUPS) return SVMC_ERR_INVALID_ARGUMENT;
+    CdTable t;
+    Layout w{static_cast<unsigned char *>(workspace)};
+    const size_t image_bytes = cd_workspace(w, n_path, m, P, G, NG, t);
+    if (workspace_bytes < w.bytes()) return SVMC_ERR_WORKSPACE;
+
+    // the table's host image, then ONE upload
+    std::vector<unsigned char> image(image_bytes);
+    Layout h{image.data()};
+    const CdImage im = cd_image(h, m, P, G, NG);
+    quote_image(
+        m, point_offsets_host, [&](int i, int p0, int p1) { im.expiries[i] = CdExpiry{mu_snapshots_host[i], cv_snapshots_host[i], p0, p1}; },
+        [&](int, int p) { im.points[p] = points_host[p]; });
+    quote_groups(m, point_offsets_host, CD_XT, false, im.groups);
+    for (int z = 0; z < NG; ++z) im.gammas[z] = gammas_host[z];
+    SVMC_EST_TRY(hipMemcpyAsync(workspace, image.data(), image_bytes, hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(cond_density_weight_kernel, dim3(t.rows, m, NG), dim3(BLOCK), 0, stream, t, n_path);
+    SVMC_EST_TRY(hipGetLastError());
+    if (G > 0) {
+        if (NG <= CD_GT)
+            hipLaunchKernelGGL((cond_density_kernel<CD_XT, CD_GT>), dim3(t.rows, G, 1), dim3(BLOCK), 0, stream, t, n_path);
+        else
+            hipLaunchKernelGGL((cond_density_kernel<CD_XT, CD_GT_WIDE>), dim3(t.rows, G, (NG + CD_GT_WIDE - 1) / CD_GT_WIDE), dim3(BLOCK), 0,
+                               stream, t, n_path);
+        SVMC_EST_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(cond_density_finish_kernel, dim3(static_cast<unsigned>(P) + m, NG), dim3(BLOCK), 0, stream, t, n_path);
+    SVMC_EST_TRY(hipGetLastError());
+    // ONE download of the results' block, ONE synchronise
+    std::vector<double> out(cd_out_doubles(m, P, NG));
+    SVMC_EST_TRY(hipMemcpyAsync(out.data(), t.out, out.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+    SVMC_EST_TRY(hipStreamSynchronize(stream));
+#undef SVMC_EST_TRY
+    const size_t GP = static_cast<size_t>(NG) * P;
+    if (GP > 0) {
+        memcpy(pdf_host, out.data(), GP * sizeof(double));
+        memcpy(stderr_host, out.data() + GP, GP * sizeof(double));
+    }
+    memcpy(stats_host, out.data() + 2 * GP, static_cast<size_t>(NG) * m * SVMC_CD_STATS_DOUBLES * sizeof(double));
     return SVMC_OK;
 }
 

@@ -370,6 +370,29 @@ TCG_FIELDS = ("delta", "delta_stderr", "dual_delta", "dual_delta_stderr", "gamma
 TCG_STATS_DOUBLES = 4          # SVMC_TCG_STATS_DOUBLES
 TCG_STATS_FIELDS = ("sum_weights", "n_kept", "n_dropped", "n_zero_cv")
 TILTED_COND_GREEKS_STATS_FIELDS = TILTED_STATS_FIELDS + ("n_zero_cv",)
+# the mixture density of the log-return (include/svmc_est.h, svmc_cond_density_chain): its statistics block
+CD_STATS_DOUBLES = 5           # SVMC_CD_STATS_DOUBLES
+CD_STATS_FIELDS = ("sum_weights", "n_kept", "n_dropped", "n_zero_cv", "n_weight_dropped")
+
+
+def cond_density_arrays(x_grids: Sequence[np.ndarray], gammas) -> dict:
+    """the host arrays of a mixture-density call, checked: at least one expiry, finite points, the gammas of tilted_gammas"""
+    g = tilted_gammas(gammas)
+    grids = [np.asarray(x, dtype=np.float64) for x in x_grids]
+    m = len(grids)
+    if m < 1:
+        raise ValueError("one grid of points per expiry, at least one expiry")
+    offs = np.concatenate([[0], np.cumsum([x.size for x in grids])]).astype(np.uintp)
+    total = int(offs[-1])
+    x_all = np.ascontiguousarray(np.concatenate([x.ravel() for x in grids])) if total else np.zeros(1)
+    if not np.all(np.isfinite(x_all)):
+        raise ValueError("the points of a density must be finite")
+    return {"m": m, "total": total, "offs": offs, "points": x_all, "gammas": g, "shapes": [x.shape for x in grids]}
+
+
+def cond_density_stats_dicts(stats: np.ndarray) -> list:
+    """stats [m, CD_STATS_DOUBLES] of one gamma -> one dict per expiry, keys CD_STATS_FIELDS (the four counts as ints)"""
+    return [{k: (float(v) if k == "sum_weights" else int(v)) for k, v in zip(CD_STATS_FIELDS, row)} for row in stats]
 
 
 # ---- conditional Monte Carlo (include/svmc.h, svmc_cmc_payoff_chain): the per-expiry statistics ----------------------------------
@@ -1134,6 +1157,11 @@ class HipEngine:
         assert a.shape == (self.n_path,)
         self.upload(self.cv.ptr, a)
 
+    def fill_state_cmc(self, mu0: float, vol0: float, qvar0: float) -> None:
+        """fill_state with the conditional variance at 0: what a conditional chain pricing begins with"""
+        self.fill_state(mu0, vol0, qvar0)
+        _lib.check(self.lib.svmc_memset(self.cv.ptr, 0, 8 * self.n_path, self.stream))
+
     def get_state_cmc(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
         mu, vol, qvar = self.get_state()
         return mu, self.download(self.cv.ptr, self.n_path), vol, qvar
@@ -1257,6 +1285,35 @@ class HipEngine:
             ch["offs"].ctypes.data_as(C.POINTER(C.c_size_t)), ch["gammas"].ctypes.data_as(dp), G, int(bool(recenter)),
             greeks.ctypes.data_as(dp), stats.ctypes.data_as(dp), ws_ptr, nbytes.value, self.stream), what))
         return tilted_greeks_results(greeks, stats, ch)
+
+    def conditional_densities(self, x_grids: Sequence[np.ndarray], gammas=(0.0,), mu_rows: Optional[Sequence[int]] = None,
+                              cv_rows: Optional[Sequence[int]] = None):
+        """the mixture density of the log-return at the points of x_grids, under exp(gamma x) for every gamma
+        (svmc_cond_density_chain, include/svmc_est.h: libsvmc_est.so) on resident (mu, cv), whichever generator
+        left them: expiry i reads snapshot rows mu_rows[i] and cv_rows[i], or, with both None, the one expiry reads the current
+        state (x, cv).  Returns (pdf [G][m] -> x_i's shape, stderr likewise, stats [G, m, CD_STATS_FIELDS]).  A gamma with
+        n_weight_dropped > 0 has NaN for its pdf and its error."""
+        ch = cond_density_arrays(x_grids, gammas)
+        m, P, G = ch["m"], ch["total"], ch["gammas"].size
+        if (mu_rows is None) != (cv_rows is None) or ((m != 1) if mu_rows is None else (len(mu_rows) != m or len(cv_rows) != m)):
+            raise ValueError("one mu row and one cv row per expiry (the current state serves one expiry)")
+        mus = [self.x.ptr] if mu_rows is None else [self.snapshot_ptr(r) for r in mu_rows]
+        cvs = [self.cv.ptr] if cv_rows is None else [self.snapshot_ptr(r) for r in cv_rows]
+        est = _lib.load_est()
+        what = "svmc_cond_density_chain"
+        nbytes = C.c_size_t(0)
+        _lib.check_ext(est.svmc_cond_density_workspace_bytes(self.n_path, m, P, G, C.byref(nbytes)), what)
+        ws_ptr, _ = self.alloc_sums((nbytes.value + 7) // 8, "cond_density_workspace")
+        pdf, err, stats = np.empty(max(G * P, 1)), np.empty(max(G * P, 1)), np.empty(G * m * CD_STATS_DOUBLES)
+        dp = C.POINTER(C.c_double)
+        self._timed("cond_density_kernel", lambda: _lib.check_ext(est.svmc_cond_density_chain(
+            (C.c_void_p * m)(*mus), (C.c_void_p * m)(*cvs), self.n_path, m, ch["points"].ctypes.data_as(dp),
+            ch["offs"].ctypes.data_as(C.POINTER(C.c_size_t)), ch["gammas"].ctypes.data_as(dp), G, pdf.ctypes.data_as(dp),
+            err.ctypes.data_as(dp), stats.ctypes.data_as(dp), ws_ptr, nbytes.value, self.stream), what))
+        offs = ch["offs"]
+        cut = lambda a: [[a[g * P + int(offs[i]):g * P + int(offs[i + 1])].reshape(ch["shapes"][i]).copy()    # noqa: E731
+                          for i in range(m)] for g in range(G)]
+        return cut(pdf), cut(err), stats.reshape(G, m, CD_STATS_DOUBLES)
 
     def step_hawkesjd_chain_cond_rows(self, ch: dict, params: np.ndarray, nb_steps_per_year: int, seed: int, call_id: int) -> None:
         """hawkesjd_chain_cond from the origin (0, lambda_p, lambda_m) into snapshot rows [0, m) (mu) and [m, 2m) (cv) for the

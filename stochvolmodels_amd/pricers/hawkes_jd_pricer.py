@@ -69,7 +69,8 @@ from ..utils import mgf_pricer as mgfp
 from ..utils.calibration import ImpliedVolObjective, chain_calibration_weights
 from ..utils.config import VariableType
 from ..utils.funcs import next_rng_call, time_grid_steps, timer, to_flat_np_array
-from .logsv_pricer import check_conditional_request, conditional_greeks_shaped, conditional_log_return_pdf
+from .logsv_pricer import (check_conditional_request, conditional_greeks_shaped, conditional_log_return_pdf,
+                           mixture_log_return_pdf)
 from .model_pricer import ModelParams, ModelPricer
 
 MAX_PHI = 500
@@ -401,6 +402,24 @@ class HawkesJDPricer(ModelPricer):
         if return_stderr:
             return pdf, np.array([(strikes * g["dual_gamma_stderr"][0]).reshape(x.shape) for g in out])
         return pdf
+
+    def get_log_return_mc_pdf_mixture(self, params: HawkesJDParams, ttm: float, x_grid: np.ndarray, risk_premia_gammas=None,
+                                      nb_path: int = 100000, seed: Optional[int] = None, return_stderr: bool = False,
+                                      return_stats: bool = False, nb_steps: Optional[int] = None,
+                                      variable_type: VariableType = VariableType.LOG_RETURN, comm=None, devices=None):
+        """the density of the simulated log-return at x_grid as the mixture of the paths' conditional Gaussians, without a bandwidth
+        (logsv_pricer.mixture_log_return_pdf; LogSVPricer.get_log_return_mc_pdf_mixture states the returns): the paths of
+        model_mc_price_chain_conditional at this seed, nb_steps steps per year (default NB_STEPS_PER_YEAR), each a Gaussian of
+        variance sigma^2 ttm around its jump path.  risk_premia_gammas: get_log_return_mc_pdf_conditional_under_risk_kernel's
+        densities, [gamma][x], with one exponential per (path, point) instead of that route's Greeks tail per gamma.  The
+        log-return and one GPU only."""
+        block = params_block(**_model_kwargs(params))
+
+        def step_rows(eng, rng_seed, call_id):
+            eng.step_hawkesjd_chain_cond_rows({"ttms": np.array([float(ttm)]), "m": 1}, np.ascontiguousarray(block, dtype=np.float64),
+                                              int(nb_steps or NB_STEPS_PER_YEAR), rng_seed, call_id)
+        return mixture_log_return_pdf("HawkesJDPricer.get_log_return_mc_pdf_mixture", step_rows, x_grid, risk_premia_gammas, nb_path, seed,
+                                      return_stderr, return_stats, variable_type, comm, devices)
 
     def model_mc_price_chain_many(self, option_chain: OptionChain, params_list: Sequence[HawkesJDParams], nb_path: int = 100000,
                                   seeds: Optional[Sequence[int]] = None, nb_steps_per_year: int = NB_STEPS_PER_YEAR, **kwargs

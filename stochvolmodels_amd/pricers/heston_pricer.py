@@ -27,7 +27,8 @@ from ..utils.funcs import next_rng_call, set_time_grid, time_grid_steps, timer
 from ..analytic import AnalyticGrid, chain_prices_from_sums, chain_sums
 from ..utils import mgf_pricer as mgfp
 from .logsv_pricer import (_broadcast_state, check_conditional_request, check_conditional_sens_expiries, conditional_greeks_shaped,
-                           conditional_log_return_pdf, conditional_many_shaped, conditional_sens_shaped, conditional_sets_on_engine)
+                           conditional_log_return_pdf, conditional_many_shaped, conditional_sens_shaped, conditional_sets_on_engine,
+                           mixture_log_return_pdf, one_expiry_grid)
 from .model_pricer import ModelParams, ModelPricer
 
 
@@ -129,6 +130,26 @@ class HestonPricer(ModelPricer):
                                                       volvol=params.volvol, nb_path=nb_path, nb_steps_per_year=nb_steps_per_year,
                                                       seed=seed, recenter=recenter, **chain)
         return conditional_log_return_pdf(route, ttm, x_grid, return_stderr)
+
+    def get_log_return_mc_pdf_mixture(self, params: HestonParams, ttm: float, x_grid: np.ndarray, risk_premia_gammas=None,
+                                      nb_path: int = 100000, seed: Optional[int] = None, return_stderr: bool = False,
+                                      return_stats: bool = False, nb_steps: Optional[int] = None, scheme="euler",
+                                      variable_type: VariableType = VariableType.LOG_RETURN, comm=None, devices=None):
+        """the density of the simulated log-return at x_grid as the mixture of the paths' conditional Gaussians, without a bandwidth
+        (logsv_pricer.mixture_log_return_pdf; LogSVPricer.get_log_return_mc_pdf_mixture states the returns): the paths of
+        model_mc_price_chain_conditional at this seed, nb_steps steps per year (default 360).  risk_premia_gammas: the densities
+        under exp(gamma x), [gamma][x].  Euler scheme (scheme="qe": NotImplementedError), the log-return and one GPU only."""
+        who = "HestonPricer.get_log_return_mc_pdf_mixture"
+        if _scheme_code(scheme) != HESTON_EULER_FLOOR:
+            raise NotImplementedError(f"{who}: scheme='qe' is not covered (Euler only)")
+
+        def step_rows(eng, rng_seed, call_id):
+            nb, dt = one_expiry_grid(ttm, nb_steps or 360)
+            eng.fill_state_cmc(0.0, params.v0, 0.0)
+            eng.heston_chain_cmc([nb], [dt], params.theta, params.kappa, params.rho, params.volvol, rng_seed, call_id, mu_row=0,
+                                 cv_row=1)
+        return mixture_log_return_pdf(who, step_rows, x_grid, risk_premia_gammas, nb_path, seed, return_stderr, return_stats,
+                                      variable_type, comm, devices)
 
     def model_mc_chain_greeks(self, option_chain: OptionChain, params: HestonParams, nb_path: int = 100000,
                               variable_type: VariableType = VariableType.LOG_RETURN, **kwargs) -> dict:

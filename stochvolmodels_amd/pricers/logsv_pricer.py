@@ -19,7 +19,8 @@ import pandas as pd
 
 from .. import dist as svdist
 from ..data.option_chain import OptionChain, black_ivols_native
-from ..engine import CMC_SETS_MAX, DeviceRandoms, get_engine, marshalled_chain, option_type_codes, payoff_finalize, tilted_type_codes
+from ..engine import (CMC_SETS_MAX, DeviceRandoms, cond_density_arrays, cond_density_stats_dicts, get_engine, marshalled_chain,
+                      option_type_codes, payoff_finalize, tilted_type_codes)
 from ..mc_chain import (chain_shaped, check_many_args, many_job_chunks, many_job_streams, many_jobs_shaped, price_chain_on_engine,
                         variable_type_code)
 from ..mc_greeks import LOGSV_GREEK_PARAMS, check_greeks_request, greeks_bumps, greeks_job_table, greeks_shaped
@@ -297,6 +298,28 @@ class LogSVPricer(ModelPricer):
                 volvol=params.volvol, vol_backbone_etas=params.get_vol_backbone_etas(ttms=np.array([ttm])), nb_path=nb_path,
                 nb_steps_per_year=nb_steps or int(360 * ttm) + 1, seed=seed, recenter=recenter, **chain)
         return conditional_log_return_pdf(route, ttm, x_grid, return_stderr)
+
+    def get_log_return_mc_pdf_mixture(self, params: LogSvParams, ttm: float, x_grid: np.ndarray, risk_premia_gammas=None,
+                                      nb_path: int = 100000, seed: Optional[int] = None, return_stderr: bool = False,
+                                      return_stats: bool = False, nb_steps: Optional[int] = None, is_spot_measure: bool = True,
+                                      variable_type: VariableType = VariableType.LOG_RETURN, comm=None, devices=None):
+        """the density of the simulated log-return at x_grid as the mixture of the paths' conditional Gaussians, without a bandwidth
+        (mixture_log_return_pdf; include/svmc_est.h's svmc_cond_density_chain): the paths of
+        model_mc_price_chain_conditional at this seed and step rule, one exponential per (path, point).  risk_premia_gammas=None:
+        pdf in x_grid's shape -- get_log_return_mc_pdf_conditional(recenter=False)'s number, UN-NORMALISED in the same way: it
+        integrates to the share of the kept paths whose conditional variance is positive.  A sequence of up to 16 gammas: the
+        densities under the exponential kernel exp(gamma x), [gamma][x], each normalised by its weights, from the same stepping
+        call (a gamma at which a path's squared weight overflows: NaN).  return_stderr=, return_stats= add the standard error and
+        the dict(s) of engine.CD_STATS_FIELDS.  The log-return, the spot measure and one GPU only."""
+        etas = params.get_vol_backbone_etas(ttms=np.array([ttm]))
+
+        def step_rows(eng, rng_seed, call_id):
+            nb, dt = one_expiry_grid(ttm, nb_steps or int(360 * ttm) + 1)
+            eng.fill_state_cmc(0.0, params.sigma0, 0.0)
+            eng.logsv_chain_cmc([nb], [dt], np.ravel(etas), params.theta, params.kappa1, params.kappa2, params.beta, params.volvol,
+                                True, rng_seed, call_id, mu_row=0, cv_row=1)
+        return mixture_log_return_pdf("LogSVPricer.get_log_return_mc_pdf_mixture", step_rows, x_grid, risk_premia_gammas, nb_path, seed,
+                                      return_stderr, return_stats, variable_type, comm, devices, is_spot_measure)
 
     def model_mc_chain_greeks(self, option_chain: OptionChain, params: LogSvParams, is_spot_measure: bool = True,
                               variable_type: VariableType = VariableType.LOG_RETURN, nb_path: int = 100000,
@@ -1146,6 +1169,42 @@ def conditional_log_return_pdf(route, ttm: float, x_grid: np.ndarray, return_std
     if return_stderr:
         return pdf, (strikes * out["dual_gamma_stderr"][0]).reshape(x.shape)
     return pdf
+
+
+def mixture_log_return_pdf(who: str, step_rows, x_grid: np.ndarray, risk_premia_gammas, nb_path: int, seed: Optional[int],
+                           return_stderr: bool, return_stats: bool, variable_type=VariableType.LOG_RETURN, comm=None, devices=None,
+                           is_spot_measure: bool = True):
+    """the body of the three pricers' get_log_return_mc_pdf_mixture: the refusals of the conditional routes
+    (check_conditional_request: variables other than the log-return, the inverse measure, comm= / devices=) and the checks of the
+    points and gammas, each before any engine is asked for; the next (seed, call id) exactly as the conditional pricer takes it;
+    step_rows(engine, seed, call_id) leaves the expiry's mu in snapshot row 0 and its cv in row 1 -- the rows the conditional pricer
+    steps on that stream --; then ONE svmc_cond_density_chain for all gammas (engine.conditional_densities).  Without gammas: pdf
+    in x_grid's shape (gamma 0); with: [gamma][x].  Then the standard error and the statistics (engine.CD_STATS_FIELDS; one dict,
+    or one per gamma) when asked."""
+    check_conditional_request(who, variable_type, comm, devices, [], is_spot_measure)
+    single = risk_premia_gammas is None
+    x = np.asarray(x_grid, dtype=np.float64)
+    ch = cond_density_arrays([x], [0.0] if single else risk_premia_gammas)         # ValueError
+    rng_seed, call_id = next_rng_call(seed)
+    eng = get_engine(int(nb_path))
+    step_rows(eng, rng_seed, call_id)
+    pdf, err, stats = eng.conditional_densities([x], ch["gammas"], mu_rows=[0], cv_rows=[1])
+    p, e = np.array([g[0] for g in pdf]), np.array([g[0] for g in err])
+    st = [cond_density_stats_dicts(s)[0] for s in stats]
+    out = (p[0] if single else p,)
+    if return_stderr:
+        out += (e[0] if single else e,)
+    if return_stats:
+        out += (st[0] if single else st,)
+    return out[0] if len(out) == 1 else out
+
+
+def one_expiry_grid(ttm: float, nb_steps_per_year: int) -> Tuple[int, float]:
+    """(steps, dt) of one expiry from the origin as the fused chain drivers cut it (svmc_chain.hip expiry_grids)"""
+    if int(nb_steps_per_year) <= 0:
+        raise ValueError("nb_steps_per_year must be positive")
+    nb = int(float(ttm) * float(int(nb_steps_per_year))) + 1
+    return nb, (float(ttm) if nb == 1 else float(ttm) / float(nb))
 
 
 def logsv_mc_chain_greeks(params: LogSvParams, ttms: np.ndarray, forwards: np.ndarray, discfactors: np.ndarray,

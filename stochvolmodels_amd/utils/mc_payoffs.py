@@ -11,8 +11,8 @@ from typing import Tuple
 
 import numpy as np
 
-from ..engine import (get_engine, option_type_codes, payoff_finalize, payoff_shifts, tilted_chain_arrays,
-                      tilted_greeks_stats_dicts, tilted_stats_dicts, tilted_type_codes)
+from ..engine import (cond_density_arrays, cond_density_stats_dicts, get_engine, option_type_codes, payoff_finalize, payoff_shifts,
+                      tilted_chain_arrays, tilted_greeks_stats_dicts, tilted_stats_dicts, tilted_type_codes)
 from ..mc_chain import variable_type_code
 from .config import VariableType
 
@@ -155,6 +155,40 @@ def compute_mc_vars_greeks_conditional_with_gamma(mu: np.ndarray, cv: np.ndarray
             d["stats"] = tilted_greeks_stats_dicts(np.concatenate([st, gst[:, 3:4]], axis=1))[0]
         out.append(d)
     return out[0] if single else out
+
+
+def compute_mc_vars_pdf_conditional(mu: np.ndarray, cv, x_grid: np.ndarray, gammas=None, return_stderr: bool = False,
+                                    return_stats: bool = False):
+    """the mixture density of the log-return at x_grid from per-path conditional means and variances (host arrays of any model;
+    cv per path or one scalar for all), the estimator of include/svmc_est.h's svmc_cond_density_chain: every path kept by
+    compute_mc_vars_payoff_conditional's rule with cv > 0 adds its Gaussian N(x; mu_j, cv_j) -- no bandwidth -- and under the
+    exponential risk-premia kernel exp(gamma x) the path's weight W_j = exp(gamma mu_j + gamma^2 cv_j / 2) times its Gaussian shifted
+    by gamma cv_j; pdf = sum / sum_j W_j.  One exponential per (path, point) whatever the number of gammas.  gammas=None: the density
+    itself (gamma 0) in x_grid's shape; a sequence of up to 16 gammas: [gamma][x].  Not normalised: it integrates to the weight
+    share of the kept paths with cv > 0.  A gamma at which a kept path's squared weight overflows returns NaN (its statistics say
+    how many: n_weight_dropped); compute_mc_vars_greeks_conditional_with_gamma's dual_gamma still serves it.  Returns pdf, then
+    with return_stderr=True its standard error in the same shape, then with return_stats=True the dict of engine.CD_STATS_FIELDS
+    (a list of them, one per gamma, with gammas given)."""
+    single = gammas is None
+    mu = np.ascontiguousarray(mu, dtype=np.float64).ravel()
+    cv = np.asarray(cv, dtype=np.float64)
+    cv = np.full(mu.size, float(cv)) if cv.ndim == 0 else np.ascontiguousarray(cv).ravel()
+    if mu.size != cv.size or mu.size == 0:
+        raise ValueError("mu and cv must be non-empty and of one length (or cv a scalar)")
+    x = np.asarray(x_grid, dtype=np.float64)
+    ch = cond_density_arrays([x], [0.0] if single else gammas)         # ValueError before any engine is asked for
+    eng = get_engine(mu.size)
+    eng.upload(eng.x.ptr, mu)
+    eng.upload(eng.cv.ptr, cv)
+    pdf, err, stats = eng.conditional_densities([x], ch["gammas"])
+    p, e = np.array([g[0] for g in pdf]), np.array([g[0] for g in err])
+    st = [cond_density_stats_dicts(s)[0] for s in stats]
+    out = (p[0] if single else p,)
+    if return_stderr:
+        out += (e[0] if single else e,)
+    if return_stats:
+        out += (st[0] if single else st,)
+    return out[0] if len(out) == 1 else out
 
 
 def compute_mc_vars_greeks_conditional(mu: np.ndarray, cv: np.ndarray, ttm: float, forward: float, strikes_ttm: np.ndarray,
