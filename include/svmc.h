@@ -1232,8 +1232,10 @@ SVMC_API int svmc_heston_chain_price_cmc_sets(svmc_session_t session, const doub
  * svmc_hawkesjd_chain_price, then the tail of svmc_cmc_payoff_chain / svmc_cmc_greeks_chain; arguments, outputs, refusals and status
  * codes as svmc_heston_chain_price_cmc / svmc_heston_chain_price_cmc_greeks with params_host for the model (its checks are made
  * first).  Bit-equal to svmc_hawkesjd_chain_cond followed by the tail entry on its rows.
- * Left out, each a later step: the estimator under the risk-premia kernel, many-job and few-waves stepping forms, parameter
- * sensitivities, a calibration objective, SVMC_INV_CALL / SVMC_INV_PUT, variables other than the log-return, several GPUs. */
+ * Left out, each a later step: many-job and few-waves stepping forms, parameter sensitivities, SVMC_INV_CALL / SVMC_INV_PUT,
+ * variables other than the log-return, several GPUs.  The estimator under the risk-premia kernel is DESIGN.md row f17 (svmc_ext.h);
+ * many (sigma, gamma) sets on ONE stepping call at sigma = 0 and a calibration objective on them are row f20 (svmc_est.h,
+ * svmc_jump_sets_payoff_chain). */
 SVMC_API int svmc_hawkesjd_chain_cond(double *mu, double *lambda_p, double *lambda_m, size_t n_path, int n_slices,
                                       const int *nb_steps_host, const double *dts_host, const double *params_host, double cv_start,
                                       uint64_t seed, uint32_t call_id, uint64_t path_offset, uint32_t step_offset,

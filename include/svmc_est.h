@@ -88,8 +88,9 @@ SVMC_EST_API int svmc_est_version(void);
  * 1 .. SVMC_TILTED_MAX_GAMMAS, strike offsets that do not start at 0 or decrease, a gamma, forward or strike that is not finite, a
  * forward that is not positive; SVMC_ERR_UNKNOWN_PAYOFF for a type code other than SVMC_CALL / SVMC_PUT; SVMC_ERR_WORKSPACE for a
  * workspace below svmc_tilted_cond_greeks_workspace_bytes; SVMC_ERR_HIP for a failure of the runtime.
- * Left out: a dedicated density kernel on the e^{gamma x} identity, the many-job form, parameter sensitivities, IC / IP, several
- * GPUs. */
+ * Left out: the many-job form (different jump parameters per job), parameter sensitivities, IC / IP, several GPUs.  Many
+ * (sigma, gamma) sets on one set of rows and the calibration objective on them: svmc_jump_sets_payoff_chain below (row f20), prices
+ * only. */
 #define SVMC_TCG_ROWS 8
 #define SVMC_TCG_STATS_DOUBLES 4
 
@@ -146,7 +147,8 @@ SVMC_EST_API int svmc_tilted_cond_greeks_chain(const double *const *mu_snapshots
  * SVMC_ERR_INVALID_ARGUMENT for a null pointer (a null snapshot among them), n_path < 1, n_expiries < 1, n_gammas outside
  * 1 .. SVMC_TILTED_MAX_GAMMAS, point offsets that do not start at 0 or decrease, a gamma or point that is not finite;
  * SVMC_ERR_WORKSPACE for a workspace below svmc_cond_density_workspace_bytes; SVMC_ERR_HIP for a failure of the runtime.
- * Left out: the many-job form, several GPUs, a derivative of the density. */
+ * Left out: the many-job form, several GPUs, a derivative of the density (many (sigma, gamma) sets on one set of rows: row f20 below,
+ * prices only). */
 #define SVMC_CD_STATS_DOUBLES 5
 
 SVMC_EST_API int svmc_cond_density_workspace_bytes(size_t n_path, int n_expiries, size_t total_points, int n_gammas, size_t *bytes);
@@ -155,6 +157,60 @@ SVMC_EST_API int svmc_cond_density_chain(const double *const *mu_snapshots_host,
                                          const size_t *point_offsets_host, const double *gammas_host, int n_gammas,
                                          double *pdf_host, double *stderr_host, double *stats_host, void *workspace,
                                          size_t workspace_bytes, svmc_stream_t stream);
+
+/* ---- many (sigma, gamma) sets on ONE set of jump rows (src svmc_est.hip) ---------------------------------------
+ * For a model whose conditional law of the log-return is N(a_j - v / 2, v) with v the SAME on every path -- the Hawkes
+ * jump-diffusion: svmc_hawkesjd_chain_cond at sigma = 0 leaves a_j (drift, compensators, jumps), which depends on neither sigma nor
+ * gamma, and v = cv_i(sigma) is one host number per expiry -- the estimator of svmc_tilted_cond_payoff_chain (svmc_ext.h, row f17)
+ * on the rows (a - v / 2, v), for up to SVMC_JUMP_SETS_MAX sets (gamma_q, v_qi) from one pass over the rows.  Model-agnostic: any
+ * rows a[j] serve.
+ * Inputs: per expiry i a device row a[j] [n_path], the forward F_i, strikes K_k of type SVMC_CALL / SVMC_PUT; per set q a gamma g_q
+ * and per (set, expiry) a variance v_qi >= 0.
+ * Per path and set:
+ *   e_j = exp(a_j),   w_qj = exp(g_q a_j),   c_qi = exp(g_q (g_q - 1) v_qi / 2),   W_qj = c_qi w_qj,
+ *   F_t = (F_i exp(g_q v_qi)) e_j,   ln F_t = (ln F_i + g_q v_qi) + a_j.
+ * c_qi, F_i exp(g_q v_qi), ln F_i + g_q v_qi, sd = sqrt(v_qi) and 1 / sd are host constants per (set, expiry); c_qi is the same on
+ * every path, cancels in every price and is applied once in the finish.  Per path that leaves one exp(a) and one exp(g a), per
+ * strike one Black-76 price: no sqrt, no division and one 8-byte load per path.
+ * Keep rule (row f17's on the rows (a - v / 2, v), restated): a_j and e_j finite -- f11's rule through tc_keep_cmc(a, 0) of
+ * csrc/svmc_tilted_cond.h -- and W^2 and (W F_t)^2 finite.  A dropped path adds nothing to any sum and is counted.
+ * Recentring: with recenter != 0, corr_i = F_i mean over the f11-kept paths of (e_j - 1), else 0: ONE forward pass per expiry for
+ * all sets, bit-equal to the corr that svmc_cmc_payoff_chain and svmc_tilted_cond_payoff_chain form on the rows (a, 0) (the forward
+ * pass has their statements and order).  K' = K + corr; ln K' once per strike.
+ * Price and error: B_qjk = Black-76 of F_t against K' at total variance v (tc_black, its degenerate cases included: v == 0 gives the
+ * intrinsic value at F_t; K' <= 0 gives F_t - K' for a call and 0 for a put);
+ *   price_qk = sum_j w B / sum_j w,   stderr_qk = sqrt(sum_j (w (B - price))^2) / sum_j w,
+ * from the sums of w d, (w d)^2, w^2 d with d = B - shift_k, exactly as row f17 forms them; the shifts are one host constant per
+ * strike, shared by the sets (any finite value gives the same estimate).
+ * Statistics per (set, expiry): row f17's block of SVMC_TILTED_STATS_DOUBLES with its meanings in terms of W = c w -- normalizer
+ * n_kept / sum W, its error, gamma forward F + sum W (F_t - corr - F) / sum W, its error, effective sample size, n_kept, n_dropped,
+ * sum W -- and corr_i per expiry.  No kept path, or kept paths of zero weight only, give NaN and are NOT an error of the call.  All
+ * values are undiscounted.
+ * Every sum has a fixed order that depends on n_path alone: a set's, an expiry's and a strike's results are the same bits whichever
+ * others share the call.  No atomics, no scratch, LDS for the block sums' exchange only.
+ *
+ *   svmc_jump_sets_workspace_bytes   host only: the device workspace that serves any chain of n_expiries expiries and
+ *                              total_strikes strikes at this n_path and n_sets.
+ *   svmc_jump_sets_payoff_chain   a_snapshots_host: a HOST array of n_expiries DEVICE pointers; strikes / types / shifts
+ *                              concatenated, expiry i owning [strike_offsets_host[i], strike_offsets_host[i + 1]);
+ *                              variances_host [n_sets][n_expiries], gammas_host [n_sets].  prices_host, stderrs_host:
+ *                              [n_sets][sum K_i]; stats_host: [n_sets][n_expiries][SVMC_TILTED_STATS_DOUBLES]; corr_host:
+ *                              [n_expiries]; host arrays.  One upload of the call's table, four launches on `stream` with no host
+ *                              round trip between them (the forward pass and its finish, the payoff kernel, the finish), one
+ *                              download, one synchronise.
+ * Everything is checked before anything is launched, and a refused call leaves the output arrays untouched: the status codes of
+ * svmc_tilted_cond_greeks_chain above (shifts must be finite as strikes must), and SVMC_ERR_INVALID_ARGUMENT for n_sets outside
+ * 1 .. SVMC_JUMP_SETS_MAX and for a variance that is negative or not finite.
+ * Left out: the many-JOB form (different jump parameters per job), parameter sensitivities, IC / IP, several GPUs. */
+#define SVMC_JUMP_SETS_MAX 16
+
+SVMC_EST_API int svmc_jump_sets_workspace_bytes(size_t n_path, int n_expiries, size_t total_strikes, int n_sets, size_t *bytes);
+SVMC_EST_API int svmc_jump_sets_payoff_chain(const double *const *a_snapshots_host, size_t n_path, const double *forwards_host,
+                                             int n_expiries, const double *strikes_host, const int8_t *types_host,
+                                             const double *shifts_host, const size_t *strike_offsets_host,
+                                             const double *variances_host, const double *gammas_host, int n_sets, int recenter,
+                                             double *prices_host, double *stderrs_host, double *stats_host, double *corr_host,
+                                             void *workspace, size_t workspace_bytes, svmc_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -70,7 +70,9 @@ SVMC_EXT_API int svmc_ext_version(void);
  * gamma, forward, strike or shift that is not finite, a forward that is not positive; SVMC_ERR_UNKNOWN_PAYOFF for a type code
  * other than SVMC_CALL / SVMC_PUT; SVMC_ERR_WORKSPACE for a workspace below svmc_tilted_cond_workspace_bytes; SVMC_ERR_HIP for
  * a failure of the runtime.
- * Left out: the many-job form, IC / IP, several GPUs.  Greeks and densities under the kernel are DESIGN.md row f18:
+ * Left out: the many-job form (different jump parameters per job), IC / IP, several GPUs.  Many (sigma, gamma) sets on one set of rows
+ * and the calibration objective on them are DESIGN.md row f20: svmc_jump_sets_payoff_chain of libsvmc_est.so (svmc_est.h).  Greeks
+ * and densities under the kernel are DESIGN.md row f18:
  * svmc_tilted_cond_greeks_chain of libsvmc_est.so (svmc_est.h), on the same rows and with this entry's keep rule, weight and corr. */
 SVMC_EXT_API int svmc_tilted_cond_workspace_bytes(size_t n_path, int n_expiries, size_t total_strikes, int n_gammas, size_t *bytes);
 SVMC_EXT_API int svmc_tilted_cond_payoff_chain(const double *const *mu_snapshots_host, const double *const *cv_snapshots_host,

@@ -16,12 +16,13 @@ Module layout and public names mirror the reference package (`stochvolmodels`) f
                                               hawkesjd_mc_chain_pricer_with_risk_premia_gammas_many,
                                               hawkesjd_mc_chain_pricer_conditional, hawkesjd_mc_chain_greeks_conditional,
                                               hawkesjd_mc_chain_pricer_conditional_with_risk_premia(_gammas),
-                                              hawkesjd_mc_chain_greeks_conditional_with_risk_premia(_gammas)
+                                              hawkesjd_mc_chain_greeks_conditional_with_risk_premia(_gammas),
+                                              hawkesjd_jump_rows, HawkesJumpRows, hawkesjd_mc_chain_pricer_conditional_sets
     stochvolmodels_amd.pricers.il_pricer      logsv_il_pricer(_vector, _batch), square_root_payoff_pricer_with_mgf_grid,
                                               compute_mc_il_payoff
     stochvolmodels_amd.utils.mc_payoffs       compute_mc_vars_payoff, compute_mc_vars_payoff_with_gamma,
                                               compute_mc_vars_payoff_conditional(_with_gamma), compute_mc_vars_greeks(_conditional(_with_gamma)),
-                                              compute_mc_vars_sens_conditional
+                                              compute_mc_vars_sens_conditional, compute_mc_vars_payoff_jump_sets
     stochvolmodels_amd.utils.funcs            set_time_grid, set_seed, timer
     stochvolmodels_amd.utils.config           OptionType, VariableType
     stochvolmodels_amd.data.option_chain      OptionChain
@@ -45,6 +46,7 @@ _EXPORTS = {
     "compute_mc_vars_payoff_conditional": "utils.mc_payoffs",
     "compute_mc_vars_payoff_conditional_with_gamma": "utils.mc_payoffs",
     "compute_mc_vars_greeks_conditional_with_gamma": "utils.mc_payoffs",
+    "compute_mc_vars_payoff_jump_sets": "utils.mc_payoffs",
     "compute_mc_vars_greeks": "utils.mc_payoffs",
     "compute_mc_vars_greeks_conditional": "utils.mc_payoffs",
     "compute_mc_vars_pdf_conditional": "utils.mc_payoffs",
@@ -60,6 +62,9 @@ _EXPORTS = {
     "hawkesjd_mc_chain_pricer_conditional_with_risk_premia_gammas": "pricers.hawkes_jd_pricer",
     "hawkesjd_mc_chain_greeks_conditional_with_risk_premia": "pricers.hawkes_jd_pricer",
     "hawkesjd_mc_chain_greeks_conditional_with_risk_premia_gammas": "pricers.hawkes_jd_pricer",
+    "HawkesJumpRows": "pricers.hawkes_jd_pricer",
+    "hawkesjd_jump_rows": "pricers.hawkes_jd_pricer",
+    "hawkesjd_mc_chain_pricer_conditional_sets": "pricers.hawkes_jd_pricer",
     "OptionChain": "data.option_chain",
     "ModelParams": "pricers.model_pricer", "ModelPricer": "pricers.model_pricer",
     "LogSvParams": "pricers.logsv.logsv_params",

@@ -303,6 +303,9 @@ def _declare_est(L: C.CDLL) -> None:
         "svmc_tilted_cond_greeks_chain": ([pvp, pvp, sz, pf64, i32, pf64, pi8, psz, pf64, i32, i32, pf64, pf64, vp, sz, vp], i32),
         "svmc_cond_density_workspace_bytes": ([sz, i32, sz, i32, psz], i32),
         "svmc_cond_density_chain": ([pvp, pvp, sz, i32, pf64, psz, pf64, i32, pf64, pf64, pf64, vp, sz, vp], i32),
+        "svmc_jump_sets_workspace_bytes": ([sz, i32, sz, i32, psz], i32),
+        "svmc_jump_sets_payoff_chain": ([pvp, sz, pf64, i32, pf64, pi8, pf64, psz, pf64, pf64, i32, i32, pf64, pf64, pf64, pf64, vp, sz, vp],
+                                        i32),
     }
     for name, (argtypes, restype) in sig.items():
         fn = getattr(L, name)          # AttributeError here = the .so does not match include/svmc_est.h

@@ -1,7 +1,8 @@
 // svmc_est.hip -- libsvmc_est.so, the estimators beside the core (include/svmc_est.h states the rule that keeps this library
 // open).  One translation unit on the header-only parts of csrc/; nothing of libsvmc.so or libsvmc_ext.so
-// is linked and no session is needed.  Two estimators: the Greeks under the risk-premia kernel (below) and the mixture density of
-// the log-return (svmc_cond_density_chain: its block further down states its three launches).
+// is linked and no session is needed.  Three estimators: the Greeks under the risk-premia kernel (below), the mixture density of
+// the log-return (svmc_cond_density_chain: its block further down states its three launches) and many (sigma, gamma) sets on one set
+// of jump rows (svmc_jump_sets_payoff_chain, row f20: its block after that).
 //
 // Conditional Monte Carlo Greeks under the exponential risk-premia kernel (svmc_tilted_cond_greeks_chain; the header states the
 // estimator, the degenerate cases and the two identities).  Four launches on one uploaded table:
@@ -519,6 +520,285 @@ __global__ __launch_bounds__(BLOCK) void cond_density_finish_kernel(CdTable t, s
     t.out[(NG + gi) * P + col] = ok ? sqrt(fmax(var, 0.0)) / W : nan;
 }
 
+// ---- many (sigma, gamma) sets on one set of jump rows (svmc_jump_sets_payoff_chain; the header states the estimator) ----
+// Four launches on one uploaded table:
+//   jump_sets_forward_kernel, jump_sets_forward_finish_kernel
+//                                the forward pass of rows f11 / f17 on the rows (a, 0): tc_forward_body's statements and order with
+//                                the constant 0.0 where it reads cv, then tc_forward_finish_body itself -- corr, K' = K + corr and ln K'
+//                                are svmc_cmc_payoff_chain's bits on (a, 0), ONCE for all sets
+//   jump_sets_payoff_kernel      block (path block, group of up to JS_KT strikes of one expiry, tile of JS_ST sets; 4 and 1, below): the set's constants
+//                                (g, c, v, sd, 1 / sd, F exp(g v), ln F + g v) come from the table at a block-uniform address; per path
+//                                ONE 8-byte load, exp(a) and exp(g a); per strike tc_black and the sums of w d, (w d)^2, w (w d); the
+//                                seven statistics sums ride in the same block sum and are stored by the expiry's first group
+//   jump_sets_finish_kernel      a block per (quote | expiry, set): the column sums in row order, price, error, statistics in terms of
+//                                W = c w, c applied here once
+// Every accumulator is one (set, strike) or one (set, statistic) whatever the tile, and a thread adds the same paths in the same order:
+// a set's, an expiry's and a strike's results are the same bits whichever others share the call.
+//
+// THE LAYOUT, measured on the MI355X (profiles/hawkes_jump_sets_bench.json, "layouts": the tail alone on the BTC chain's 49 strikes at
+// 10^5 | 2^20 paths, ms for 1 / 3 / 16 sets; VGPRs and waves per SIMD of the payoff kernel from the ISA metadata).  ST = 1 is row f17's
+// layout, a block per set; ST > 1 loops the sets of a tile inside the block, so that a path's load, its keep test and exp(a) are shared,
+// at ST times the accumulators.
+//   KT, ST   VGPRs  waves   10^5 paths             2^20 paths
+//   8, 1      119     4     0.188 0.308 1.125      0.603 1.468 7.215      row f17's group of eight
+//   4, 1       86     5     0.185 0.296 1.072      0.551 1.326 6.478      kept
+//   4, 2      130     3     0.241 0.351 1.091      1.000 1.875 6.900
+//   8, 2      187     2     0.283 0.429 1.365      1.288 2.405 9.232
+//   2, 4      158     3     0.351 0.355 1.082      1.815 1.822 6.933
+//   4, 4      211     2     0.387 0.385 1.177      2.058 2.069 7.880
+//   2, 8      270     1     0.969 0.971 1.895      6.714 6.721 13.37
+// Sharing the load and exp(a) buys nothing: per (path, set, strike) the kernel pays two normal CDFs, per (path, set) one exp, and the
+// load is 8 bytes against all of that; a tile wider than the call wastes its lanes' work on sets nobody asked for (one set at ST = 4:
+// twice to nearly four times ST = 1's time) and the accumulators cost the waves.  The set-per-block layout is kept.  Within it a group of
+// four strikes (19 accumulators, 86 VGPRs, five waves) is 2 to 10 % ahead of row f17's eight (31 accumulators, 119 VGPRs, four waves)
+// in all six cells, in two runs that agree within 2 %: forming w and F_t twice as often costs less than the fifth wave hides.  No bit depends on either choice.
+#ifndef SVMC_JS_KT
+#define SVMC_JS_KT 4
+#endif
+#ifndef SVMC_JS_ST
+#define SVMC_JS_ST 1
+#endif
+constexpr int JS_KT = SVMC_JS_KT;      // strikes per group
+constexpr int JS_ST = SVMC_JS_ST;      // sets per tile
+constexpr int JS_NSTAT = 7;            // [sum w, sum w^2, sum (w-1)^2, sum w ds, sum w^2 ds, sum (w ds)^2, kept], ds = F_t - corr - F
+constexpr int JS_STAT_COLS = 8;        // ... padded, as row f17's
+constexpr int JS_PAY_COLS = 3;         // per quote [sum w d, sum (w d)^2, sum w^2 d]
+
+// the host constants of one (set, expiry)
+struct JsSet {
+    double g, c, v, sd, inv_sd;        // gamma, exp(g (g - 1) v / 2), the variance, its root and the root's inverse (inf at v == 0: unused)
+    double fs, ln_fs;                  // F exp(g v), ln F + g v
+    double gv;                         // g v
+};
+// the device table of a call; the image (expiries .. sets) is uploaded once
+struct JsTable {
+    const TcExpiry *expiries;          // [m]; mu = a, cv = null: nothing reads it
+    const QuoteGroup *groups;          // [G] groups of up to JS_KT strikes; pad = 1: the expiry's first, which stores its statistics sums
+    const double *strikes;             // [K]
+    const double *is_put;              // [K] 0 | 1
+    const double *shift;               // [K] the host's shift of a strike's sums
+    const JsSet *sets;                 // [Q][m]
+    double *kp, *ln_kp;                // [K] device-computed: K + corr, its logarithm (0 where K + corr <= 0)
+    double *fwd;                       // [m][4]: sum (e - 1), sum (e - 1)^2, kept count of f11's rule, corr
+    double *fwd_partials;              // [rows][m][3]
+    double *pay_partials;              // [rows][Q][K][JS_PAY_COLS]
+    double *stat_partials;             // [rows][Q][m][JS_STAT_COLS]
+    double *out;                       // prices [Q][K], errors [Q][K], statistics [Q][m][SVMC_TILTED_STATS_DOUBLES], corr [m]: one block
+    int m, K, NG;                      // NG: the sets
+    unsigned rows;
+};
+struct JsImage {
+    TcExpiry *expiries;
+    QuoteGroup *groups;
+    double *strikes, *is_put, *shift;
+    JsSet *sets;
+};
+inline JsImage js_image(Layout &w, int m, size_t K, int G, int Q)
+{
+    return JsImage{w.take<TcExpiry>(m), w.take<QuoteGroup>(G), w.take<double>(K), w.take<double>(K), w.take<double>(K),
+                   w.take<JsSet>(static_cast<size_t>(Q) * m)};         // (a braced list: in this order)
+}
+inline size_t js_out_doubles(int m, size_t K, int Q)
+{
+    return static_cast<size_t>(Q) * (2 * K + static_cast<size_t>(SVMC_TILTED_STATS_DOUBLES) * m) + m;
+}
+// ONE walk that is both the workspace's byte count and its carving; returns the bytes of the image, which the walk starts with
+inline size_t js_workspace(Layout &w, size_t n_path, int m, size_t K, int G, int Q, JsTable &t)
+{
+    const size_t rows = quote_rows(n_path);
+    const JsImage im = js_image(w, m, K, G, Q);
+    const size_t image_bytes = w.bytes();
+    t.expiries = im.expiries;
+    t.groups = im.groups;
+    t.strikes = im.strikes;
+    t.is_put = im.is_put;
+    t.shift = im.shift;
+    t.sets = im.sets;
+    t.kp = w.take<double>(K);
+    t.ln_kp = w.take<double>(K);
+    t.fwd = w.take<double>(4 * static_cast<size_t>(m));
+    t.out = w.take<double>(js_out_doubles(m, K, Q));
+    t.fwd_partials = w.take<double>(rows * 3 * m);
+    t.pay_partials = w.take<double>(rows * Q * K * JS_PAY_COLS);
+    t.stat_partials = w.take<double>(rows * Q * m * JS_STAT_COLS);
+    t.m = m;
+    t.K = static_cast<int>(K);
+    t.NG = Q;
+    t.rows = static_cast<unsigned>(rows);
+    return image_bytes;
+}
+
+// tc_forward_body's statements and order (svmc_tilted_cond.h) on the rows (a, 0): the constant 0.0 stands where it reads cv[i].
+// grid (path blocks, expiries)
+__global__ __launch_bounds__(BLOCK) void jump_sets_forward_kernel(JsTable t, size_t n)
+{
+    __shared__ double lds[4 * 3];
+    const TcExpiry ex = t.expiries[blockIdx.y];
+    const size_t stride = static_cast<size_t>(gridDim.x) * BLOCK;
+    double v[3] = {0.0, 0.0, 0.0};
+    for (size_t i = static_cast<size_t>(blockIdx.x) * BLOCK + threadIdx.x; i < n; i += stride) {
+        double h, e;
+        if (tc_keep_cmc(ex.mu[i], 0.0, h, e)) {
+            const double d = e - 1.0;
+            v[0] += d;
+            v[1] = fma(d, d, v[1]);
+            v[2] += 1.0;
+        }
+    }
+    block_sum_store<3>(v, lds, t.fwd_partials + (static_cast<size_t>(blockIdx.x) * t.m + blockIdx.y) * 3, 3);
+}
+
+__global__ __launch_bounds__(BLOCK) void jump_sets_forward_finish_kernel(JsTable t, int recenter)
+{
+    __shared__ double lds[4];
+    tc_forward_finish_body(t, recenter, lds);
+}
+
+// grid (path blocks, strike groups, set tiles)
+template <int KT, int ST>
+__global__ __launch_bounds__(BLOCK) void jump_sets_payoff_kernel(JsTable t, size_t n)
+{
+    constexpr int NP = JS_PAY_COLS * KT;                   // a set's payoff accumulators, then its JS_NSTAT statistics
+    constexpr int NS = NP + JS_NSTAT;
+    constexpr int NV = ST * NS;
+    constexpr int NSUM = block_sum_padded(NV);
+    constexpr double INF = __builtin_huge_val();
+    __shared__ double lds[4 * NSUM];
+    const QuoteGroup g = t.groups[blockIdx.y];
+    const TcExpiry ex = t.expiries[g.expiry];
+    const int nk = g.nk;                                   // (block-uniform; 0: the group only forms the statistics)
+    const int q0 = static_cast<int>(blockIdx.z) * ST, nq = min(ST, t.NG - q0);
+    const double corr = t.fwd[4 * g.expiry + 3];
+    const double forward = ex.forward;
+    JsSet set[ST];
+#pragma unroll
+    for (int q = 0; q < ST; ++q) set[q] = t.sets[static_cast<size_t>(q0 + ((q < nq) ? q : 0)) * t.m + g.expiry];    // unused sets repeat the first
+    double kp[KT], ln_kp[KT], shift[KT], acc[NSUM];
+    bool put[KT];
+#pragma unroll
+    for (int j = 0; j < NSUM; ++j) acc[j] = 0.0;
+#pragma unroll
+    for (int k = 0; k < KT; ++k) {
+        const int kk = g.k0 + ((k < nk) ? k : 0);          // the unused strikes of a group repeat its first; their sums are dropped
+        const bool on = nk > 0;                            // a group without strikes reads none
+        kp[k] = on ? t.kp[kk] : 1.0;
+        ln_kp[k] = on ? t.ln_kp[kk] : 0.0;
+        shift[k] = on ? t.shift[kk] : 0.0;
+        put[k] = on ? t.is_put[kk] != 0.0 : false;
+    }
+    const size_t stride = static_cast<size_t>(gridDim.x) * BLOCK;
+    for (size_t i = static_cast<size_t>(blockIdx.x) * BLOCK + threadIdx.x; i < n; i += stride) {
+        const double a = ex.mu[i];
+        double h, e;
+        if (!tc_keep_cmc(a, 0.0, h, e)) continue;          // f11's rule on (a, 0): a and e = exp(a) finite
+#pragma unroll
+        for (int q = 0; q < ST; ++q) {
+            const JsSet &s = set[q];
+            // once per (path, set): the weight and the shifted forward with its logarithm
+            const double w = exp_full(s.g * a);
+            const double ft = s.fs * e, ln_ft = s.ln_fs + a;
+            const double W = s.c * w, wf = W * ft;
+            if (!(W * W < INF && wf * wf < INF)) continue; // (a NaN fails the comparison)
+            const double v = w - 1.0;
+            const double wds = w * ((ft - corr) - forward);
+            double *st = acc + q * NS + NP;
+            st[0] += w;
+            st[1] = fma(w, w, st[1]);
+            st[2] = fma(v, v, st[2]);
+            st[3] += wds;
+            st[4] = fma(w, wds, st[4]);
+            st[5] = fma(wds, wds, st[5]);
+            st[6] += 1.0;
+            if (nk > 0) {
+                double *pa = acc + q * NS;
+#pragma unroll
+                for (int k = 0; k < KT; ++k) {
+                    const double wd = w * (tc_black(ft, ln_ft, s.v, s.sd, s.inv_sd, kp[k], ln_kp[k], put[k]) - shift[k]);
+                    pa[k] += wd;
+                    pa[KT + k] = fma(wd, wd, pa[KT + k]);
+                    pa[2 * KT + k] = fma(w, wd, pa[2 * KT + k]);
+                }
+            }
+        }
+    }
+    const bool first = g.pad != 0;
+    block_sum_apply<NSUM>(acc, lds, NV, [&](int j, double sum) {
+        const int q = j / NS, r = j - q * NS;
+        if (q >= nq) return;
+        const size_t slot = static_cast<size_t>(blockIdx.x) * t.NG + (q0 + q);             // partials[path block][set]
+        if (r < NP) {
+            const int which = r / KT, k = r - which * KT;
+            if (k < nk) t.pay_partials[(slot * t.K + g.k0 + k) * JS_PAY_COLS + which] = sum;
+        } else if (first) {
+            t.stat_partials[(slot * t.m + g.expiry) * JS_STAT_COLS + (r - NP)] = sum;
+        }
+    });
+}
+
+// A block per (column, set): columns [0, K) are the quotes, [K, K + m) the expiries' statistics.  The sums are the column sums of
+// the partial rows in row order, in terms of w; c enters the statistics here, once.
+__global__ __launch_bounds__(BLOCK) void jump_sets_finish_kernel(JsTable t, size_t n)
+{
+    __shared__ double lds[4];
+    const int col = blockIdx.x, gi = blockIdx.y;
+    const size_t K = static_cast<size_t>(t.K), m = static_cast<size_t>(t.m), NG = static_cast<size_t>(t.NG);
+    const size_t ld_stat = NG * m * JS_STAT_COLS, ld_pay = NG * K * JS_PAY_COLS;
+    int i = col - t.K;                                     // the expiry (block-uniform)
+    if (col < t.K) {
+        i = 0;
+        while (i + 1 < t.m && col >= t.expiries[i].k1) ++i;            // expiries without strikes are skipped over
+    }
+    const double *st = t.stat_partials + (static_cast<size_t>(gi) * m + i) * JS_STAT_COLS;
+    double s[JS_NSTAT];
+    if (col < t.K) {
+        // the expiry's sum w, sum w^2 and kept count, then the quote's three columns
+        const double *pay = t.pay_partials + (static_cast<size_t>(gi) * K + col) * JS_PAY_COLS;
+        s[0] = block_column_sum(st, t.rows, ld_stat, lds);
+        __syncthreads();
+        s[1] = block_column_sum(st + 1, t.rows, ld_stat, lds);
+        __syncthreads();
+        s[2] = block_column_sum(st + 6, t.rows, ld_stat, lds);
+#pragma unroll
+        for (int q = 0; q < JS_PAY_COLS; ++q) {
+            __syncthreads();
+            s[3 + q] = block_column_sum(pay + q, t.rows, ld_pay, lds);
+        }
+        if (threadIdx.x != 0) return;
+        // price = shift + sum w d / sum w; sum (w (B - price))^2 = sum (w d)^2 - 2 e sum w^2 d + e^2 sum w^2, e = price - shift.
+        // One kept path: the estimate IS that path's price and the squares about it are zero identically
+        const double W = s[0], Q = s[1], kept = s[2];
+        const double e = s[3] / W;
+        const double var = (kept > 1.0) ? fma(e, fma(e, Q, -2.0 * s[5]), s[4]) : 0.0;
+        t.out[gi * K + col] = e + t.shift[col];
+        t.out[NG * K + gi * K + col] = sqrt(fmax(var, 0.0)) / W;
+        return;
+    }
+#pragma unroll
+    for (int q = 0; q < JS_NSTAT; ++q) {
+        if (q > 0) __syncthreads();
+        s[q] = block_column_sum(st + q, t.rows, ld_stat, lds);
+    }
+    if (threadIdx.x != 0) return;
+    const double w = s[0], Q = s[1], V2 = s[2], D0 = s[3], D1 = s[4], D2 = s[5], kept = s[6];
+    // row f17's statistics with W = c w: the normalizer and sum W carry c, every ratio of two weighted sums is free of it
+    const double c = t.sets[static_cast<size_t>(gi) * m + i].c;
+    const double W = c * w;
+    const double N = kept / W, sv = w - kept;
+    const double dev2 = (kept > 1.0) ? V2 - sv * sv / kept : 0.0;      // sum (w - mean w)^2
+    const double gd = D0 / w;
+    const double varg = (kept > 1.0) ? fma(gd, fma(gd, Q, -2.0 * D1), D2) : 0.0;
+    double *out = t.out + 2 * NG * K + (static_cast<size_t>(gi) * m + i) * SVMC_TILTED_STATS_DOUBLES;
+    out[0] = N;
+    out[1] = N * sqrt(fmax(dev2, 0.0)) / w;
+    out[2] = t.expiries[i].forward + gd;
+    out[3] = sqrt(fmax(varg, 0.0)) / w;
+    out[4] = (w / Q) * w;                                  // effective sample size (sum W)^2 / sum W^2
+    out[5] = kept;
+    out[6] = static_cast<double>(n) - kept;
+    out[7] = W;
+    if (gi == 0) t.out[NG * (2 * K + SVMC_TILTED_STATS_DOUBLES * m) + i] = t.fwd[4 * i + 3];       // corr, once per expiry
+}
+
 // ---- host -----------------------------------------------------------------------------------------------------------------------
 static bool tcg_sizes_ok(size_t n_path, int n_expiries, int n_gammas)
 {
@@ -690,6 +970,106 @@ int svmc_cond_density_chain(const double *const *mu_snapshots_host, const double
         memcpy(stderr_host, out.data() + GP, GP * sizeof(double));
     }
     memcpy(stats_host, out.data() + 2 * GP, static_cast<size_t>(NG) * m * SVMC_CD_STATS_DOUBLES * sizeof(double));
+    return SVMC_OK;
+}
+
+int svmc_jump_sets_workspace_bytes(size_t n_path, int n_expiries, size_t total_strikes, int n_sets, size_t *bytes)
+{
+    if (bytes == nullptr || n_path < 1 || n_expiries < 1 || n_sets < 1 || n_sets > SVMC_JUMP_SETS_MAX) return SVMC_ERR_INVALID_ARGUMENT;
+    JsTable t;
+    Layout w{nullptr};
+    js_workspace(w, n_path, n_expiries, total_strikes, quote_groups_bound(n_expiries, total_strikes, JS_KT), n_sets, t);
+    *bytes = w.bytes();
+    return SVMC_OK;
+}
+
+int svmc_jump_sets_payoff_chain(const double *const *a_snapshots_host, size_t n_path, const double *forwards_host, int n_expiries,
+                                const double *strikes_host, const int8_t *types_host, const double *shifts_host,
+                                const size_t *strike_offsets_host, const double *variances_host, const double *gammas_host, int n_sets,
+                                int recenter, double *prices_host, double *stderrs_host, double *stats_host, double *corr_host,
+                                void *workspace, size_t workspace_bytes, svmc_stream_t stream_)
+{
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    // everything is checked before anything is launched
+    if (!a_snapshots_host || !forwards_host || !strikes_host || !types_host || !shifts_host || !strike_offsets_host || !variances_host ||
+        !gammas_host || !prices_host || !stderrs_host || !stats_host || !corr_host || !workspace)
+        return SVMC_ERR_INVALID_ARGUMENT;
+    if (n_path < 1 || n_expiries < 1 || n_sets < 1 || n_sets > SVMC_JUMP_SETS_MAX) return SVMC_ERR_INVALID_ARGUMENT;
+    const int m = n_expiries, Q = n_sets;
+    if (strike_offsets_host[0] != 0) return SVMC_ERR_INVALID_ARGUMENT;
+    for (int i = 0; i < m; ++i) {
+        if (strike_offsets_host[i + 1] < strike_offsets_host[i] || strike_offsets_host[i + 1] > (static_cast<size_t>(1) << 30))
+            return SVMC_ERR_INVALID_ARGUMENT;
+        if (!a_snapshots_host[i]) return SVMC_ERR_INVALID_ARGUMENT;
+        if (!std::isfinite(forwards_host[i]) || !(forwards_host[i] > 0.0)) return SVMC_ERR_INVALID_ARGUMENT;
+    }
+    const size_t K = strike_offsets_host[m];
+    for (int q = 0; q < Q; ++q) {
+        if (!std::isfinite(gammas_host[q])) return SVMC_ERR_INVALID_ARGUMENT;
+        for (int i = 0; i < m; ++i) {
+            const double v = variances_host[static_cast<size_t>(q) * m + i];
+            if (!std::isfinite(v) || !(v >= 0.0)) return SVMC_ERR_INVALID_ARGUMENT;
+        }
+    }
+    for (size_t k = 0; k < K; ++k)
+        if (!std::isfinite(strikes_host[k]) || !std::isfinite(shifts_host[k])) return SVMC_ERR_INVALID_ARGUMENT;
+    for (size_t k = 0; k < K; ++k)
+        if (types_host[k] != SVMC_CALL && types_host[k] != SVMC_PUT) return SVMC_ERR_UNKNOWN_PAYOFF;
+    const int G = quote_groups(m, strike_offsets_host, JS_KT, true);
+    if (G > TCG_MAX_GROUPS) return SVMC_ERR_INVALID_ARGUMENT;
+    JsTable t;
+    Layout w{static_cast<unsigned char *>(workspace)};
+    const size_t image_bytes = js_workspace(w, n_path, m, K, G, Q, t);
+    if (workspace_bytes < w.bytes()) return SVMC_ERR_WORKSPACE;
+
+    // the table's host image, then ONE upload
+    std::vector<unsigned char> image(image_bytes);
+    Layout h{image.data()};
+    const JsImage im = js_image(h, m, K, G, Q);
+    quote_image(
+        m, strike_offsets_host,
+        [&](int i, int k0, int k1) {
+            im.expiries[i] = TcExpiry{a_snapshots_host[i], nullptr, forwards_host[i], std::log(forwards_host[i]), k0, k1};
+        },
+        [&](int, int k) {
+            im.strikes[k] = strikes_host[k];
+            im.is_put[k] = (types_host[k] == SVMC_PUT) ? 1.0 : 0.0;
+            im.shift[k] = shifts_host[k];
+        });
+    quote_groups(m, strike_offsets_host, JS_KT, true, im.groups);
+    for (int q = 0; q < Q; ++q)
+        for (int i = 0; i < m; ++i) {
+            // the constants of a (set, expiry), each rounded once, from the set's own numbers alone
+            const double g = gammas_host[q], v = variances_host[static_cast<size_t>(q) * m + i], gv = g * v, sd = std::sqrt(v);
+            im.sets[static_cast<size_t>(q) * m + i] = JsSet{g,  std::exp(0.5 * ((g * (g - 1.0)) * v)), v, sd, 1.0 / sd,
+                                                            forwards_host[i] * std::exp(gv), std::log(forwards_host[i]) + gv, gv};
+        }
+#define SVMC_EST_TRY(call)                       \
+    do {                                         \
+        if ((call) != hipSuccess) return SVMC_ERR_HIP; \
+    } while (0)
+    SVMC_EST_TRY(hipMemcpyAsync(workspace, image.data(), image_bytes, hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(jump_sets_forward_kernel, dim3(t.rows, m), dim3(BLOCK), 0, stream, t, n_path);
+    SVMC_EST_TRY(hipGetLastError());
+    hipLaunchKernelGGL(jump_sets_forward_finish_kernel, dim3(m), dim3(BLOCK), 0, stream, t, recenter ? 1 : 0);
+    SVMC_EST_TRY(hipGetLastError());
+    hipLaunchKernelGGL((jump_sets_payoff_kernel<JS_KT, JS_ST>), dim3(t.rows, G, (Q + JS_ST - 1) / JS_ST), dim3(BLOCK), 0, stream, t,
+                       n_path);
+    SVMC_EST_TRY(hipGetLastError());
+    hipLaunchKernelGGL(jump_sets_finish_kernel, dim3(static_cast<unsigned>(K) + m, Q), dim3(BLOCK), 0, stream, t, n_path);
+    SVMC_EST_TRY(hipGetLastError());
+    // ONE download of the results' block, ONE synchronise
+    std::vector<double> out(js_out_doubles(m, K, Q));
+    SVMC_EST_TRY(hipMemcpyAsync(out.data(), t.out, out.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+    SVMC_EST_TRY(hipStreamSynchronize(stream));
+#undef SVMC_EST_TRY
+    const size_t QK = static_cast<size_t>(Q) * K, QS = static_cast<size_t>(Q) * m * SVMC_TILTED_STATS_DOUBLES;
+    if (QK > 0) {
+        memcpy(prices_host, out.data(), QK * sizeof(double));
+        memcpy(stderrs_host, out.data() + QK, QK * sizeof(double));
+    }
+    memcpy(stats_host, out.data() + 2 * QK, QS * sizeof(double));
+    memcpy(corr_host, out.data() + 2 * QK + QS, static_cast<size_t>(m) * sizeof(double));
     return SVMC_OK;
 }
 

@@ -363,6 +363,7 @@ TILTED_STATS_FIELDS = ("normalizer", "normalizer_stderr", "gamma_forward", "gamm
                        "n_kept", "n_dropped", "sum_weights")
 # the conditional estimator under the kernel (include/svmc_ext.h, svmc_tilted_cond_payoff_chain): the same block, the same meanings
 TILTED_COND_STATS_FIELDS = TILTED_STATS_FIELDS
+JUMP_SETS_MAX = 16             # SVMC_JUMP_SETS_MAX of include/svmc_est.h: (sigma, gamma) sets per svmc_jump_sets_payoff_chain call
 # ... and its Greeks (include/svmc_est.h, svmc_tilted_cond_greeks_chain): the result rows, its own statistics block, and the block the
 # routes return -- the payoff tail's with the count of cv == 0 paths
 TCG_ROWS = 8                   # SVMC_TCG_ROWS
@@ -1330,6 +1331,65 @@ class HipEngine:
             t0 = float(t)
         self.fill_state(0.0, float(params[6]), float(params[11]))         # SVMC_HAWKESJD_PARAMS: lambda_p, lambda_m
         self.hawkesjd_chain_cond(nbs, dts, params, seed, call_id, mu_row=0, cv_row=ch["m"])
+
+    # ---- many (sigma, gamma) sets on one set of jump rows (include/svmc_est.h): libsvmc_est.so
+    def step_hawkesjd_jump_rows(self, ch: dict, params: np.ndarray, nb_steps_per_year: int, seed: int, call_id: int) -> None:
+        """step_hawkesjd_chain_cond_rows with the parameter block's sigma set to 0.0: snapshot rows [0, m) hold a_j -- drift,
+        compensators and jumps, which depend on neither sigma nor gamma -- and rows [m, 2m) zeros.  The jumps are those of
+        step_hawkesjd_chain_cond_rows at this (seed, call id) whatever its sigma."""
+        block = np.array(params, dtype=np.float64)
+        block[1] = 0.0                                                     # SVMC_HAWKESJD_PARAMS: sigma
+        self.step_hawkesjd_chain_cond_rows(ch, block, nb_steps_per_year, seed, call_id)
+
+    def copy_rows(self, dst_ptr: int, src_ptr: int, n_doubles: int) -> None:
+        """n_doubles from one device address to another on this engine's stream"""
+        _lib.check(self.lib.svmc_memcpy_d2d(dst_ptr, src_ptr, 8 * int(n_doubles), self.stream))
+
+    def jump_sets_payoffs(self, forwards, strikes: Sequence[np.ndarray], codes: Sequence[np.ndarray], variances, gammas,
+                          recenter: bool = False, a_rows: Optional[Sequence[int]] = None,
+                          shifts: Optional[Sequence[np.ndarray]] = None, a_ptrs: Optional[Sequence[int]] = None):
+        """the conditional estimator under exp(gamma x) for up to JUMP_SETS_MAX sets (gamma_q, v_qi) on rows a with
+        x | a ~ N(a - v / 2, v), v the same on every path (svmc_jump_sets_payoff_chain, include/svmc_est.h): expiry i reads snapshot
+        row a_rows[i], or the device pointer a_ptrs[i] of a caller-owned row of n_path doubles, or, with both None, the one expiry
+        reads the current state x.  variances: [Q][m], gammas: [Q].  codes: 0 ('C') / 1 ('P') per strike.  shifts: the host constant
+        of every strike's sums, shared by the sets (default payoff_shifts at the forward).  Returns (prices [Q][m] -> [K_i], stderrs
+        the same, stats [Q, m, TILTED_COND_STATS_FIELDS], corr [m]); prices are undiscounted."""
+        ch = tilted_chain_arrays(forwards, strikes, codes, gammas)
+        m, K, Q = ch["m"], ch["total"], ch["gammas"].size
+        var = np.ascontiguousarray(np.asarray(variances, dtype=np.float64))
+        if var.shape != (Q, m):
+            raise ValueError("variances: one per (set, expiry)")
+        if not (np.all(np.isfinite(var)) and np.all(var >= 0.0)):
+            raise ValueError("variances must be finite and not negative")
+        if a_rows is not None and a_ptrs is not None:
+            raise ValueError("a_rows or a_ptrs, not both")
+        if a_ptrs is not None:
+            ptrs = [int(p) for p in a_ptrs]
+        elif a_rows is not None:
+            ptrs = [self.snapshot_ptr(r) for r in a_rows]
+        else:
+            ptrs = [self.x.ptr]
+        if len(ptrs) != m:
+            raise ValueError("one row of a per expiry (the current state serves one expiry)")
+        if shifts is None:
+            shifts = [payoff_shifts(k, c, float(f), LOG_RETURN) for k, c, f in zip(ch["strikes_ttms"], ch["codes_ttms"], ch["forwards"])]
+        sh = np.ascontiguousarray(np.concatenate([np.asarray(s, dtype=np.float64).ravel() for s in shifts])) if K else np.zeros(1)
+        if K and sh.size != K:
+            raise ValueError("one shift per strike")
+        est = _lib.load_est()
+        what = "svmc_jump_sets_payoff_chain"
+        nbytes = C.c_size_t(0)
+        _lib.check_ext(est.svmc_jump_sets_workspace_bytes(self.n_path, m, K, Q, C.byref(nbytes)), what)
+        ws_ptr, _ = self.alloc_sums((nbytes.value + 7) // 8, "jump_sets_workspace")
+        prices, stderrs = np.empty(max(Q * K, 1)), np.empty(max(Q * K, 1))
+        stats, corr = np.empty(Q * m * TILTED_STATS_DOUBLES), np.empty(m)
+        dp = C.POINTER(C.c_double)
+        self._timed("jump_sets_payoff_kernel", lambda: _lib.check_ext(est.svmc_jump_sets_payoff_chain(
+            (C.c_void_p * m)(*ptrs), self.n_path, ch["forwards"].ctypes.data_as(dp), m, ch["strikes"].ctypes.data_as(dp),
+            ch["codes"].ctypes.data_as(C.POINTER(C.c_int8)), sh.ctypes.data_as(dp), ch["offs"].ctypes.data_as(C.POINTER(C.c_size_t)),
+            var.ctypes.data_as(dp), ch["gammas"].ctypes.data_as(dp), Q, int(bool(recenter)), prices.ctypes.data_as(dp),
+            stderrs.ctypes.data_as(dp), stats.ctypes.data_as(dp), corr.ctypes.data_as(dp), ws_ptr, nbytes.value, self.stream), what))
+        return tilted_results(prices[:Q * K], stderrs[:Q * K], stats, ch) + (corr,)
 
     def price_hawkesjd_chain_tilted_cond(self, ch: dict, params: np.ndarray, nb_steps_per_year: int, seed: int, call_id: int, gammas,
                                          recenter: bool):

@@ -62,7 +62,7 @@ from .. import _lib
 from .. import dist as svdist
 from ..analytic import ODE_ATOL, ODE_RTOL, AnalyticGrid, chain_prices_from_sums, chain_sums
 from ..data.option_chain import OptionChain
-from ..engine import (DeviceBuffer, get_engine, marshalled_chain, option_type_codes, tilted_chain_arrays,
+from ..engine import (JUMP_SETS_MAX, DeviceBuffer, get_engine, marshalled_chain, option_type_codes, tilted_chain_arrays,
                       tilted_gammas, tilted_greeks_stats_dicts, tilted_type_codes)
 from ..mc_chain import chain_shaped, check_many_args, many_job_chunks, many_job_streams, many_jobs_shaped, variable_type_code
 from ..utils import mgf_pricer as mgfp
@@ -273,7 +273,12 @@ class HawkesJDPricer(ModelPricer):
                                           print_iter: bool = True, **kwargs) -> ImpliedVolObjective:
         """the objective of calibrate_risk_premia_gamma_to_chain as a callable of the optimizer's (sigma, gamma / 8)
         (reference :336-342): every call unpacks into params0 IN PLACE, as there; with its batched gradient at SLSQP's step
-        0.025 unless batched_gradient=False; ode_rtol= / ode_atol= as in hawkesjd_chain_pricer"""
+        0.025 unless batched_gradient=False; ode_rtol= / ode_atol= as in hawkesjd_chain_pricer.  estimator="conditional" (with nb_path=,
+        nb_steps_per_year=, seed=, recenter_forward=): the model prices by conditional Monte Carlo on jump rows stepped once, here
+        (calibrate_risk_premia_gamma_to_chain states the mode); the handle is the returned objective's .jump_rows"""
+        estimator = kwargs.get("estimator", "fourier")
+        if estimator not in ("fourier", "conditional"):
+            raise ValueError(f"estimator={estimator!r}: 'fourier' or 'conditional'")
         if params0.risk_premia_gamma is None:
             raise ValueError("params0.risk_premia_gamma must be set: it is the start value of the fit")
         _, market_vols_ttms = option_chain.get_chain_data_as_xy()
@@ -297,19 +302,46 @@ class HawkesJDPricer(ModelPricer):
                                                                     forwards=np.where(ok, gamma_forwards, 1.0))
             return [v if good else np.full_like(v, np.nan) for v, good in zip(vols, ok)]
 
-        def model_vols(pars):
-            prices, (_, gamma_forwards) = hawkesjd_chain_pricer_with_risk_premia(model_params=unpack(pars), **chain)
-            return ivols(prices, gamma_forwards)
+        if estimator == "conditional":
+            # the model prices by conditional Monte Carlo on jump rows stepped ONCE, here, on one (seed, call id): an evaluation is a
+            # tail (HawkesJumpRows.price_sets); codec, bounds, weights and the inversion above are the Fourier objective's
+            check_conditional_request("risk_premia_calibration_objective", VariableType.LOG_RETURN, kwargs.get("comm"),
+                                      kwargs.get("devices"), option_chain.optiontypes_ttms)
+            model = {k: v for k, v in params0.to_dict().items() if k not in ("sigma", "risk_premia_gamma")}
+            rows = hawkesjd_jump_rows(option_chain.ttms, nb_path=int(kwargs.get("nb_path", 100000)),
+                                      nb_steps_per_year=int(kwargs.get("nb_steps_per_year", NB_STEPS_PER_YEAR)),
+                                      seed=kwargs.get("seed"), **model)
+            recenter = bool(kwargs.get("recenter_forward", False))
 
-        def model_vols_batch(pars_list):
-            # each vector priced with its own copy of params0 as unpack leaves it; params0 ends at the last vector
-            params_list = [dataclasses.replace(unpack(pars)) for pars in pars_list]
-            prices, forwards = hawkesjd_chain_pricer_with_risk_premia_batch(params_list=params_list, **chain)
-            return [ivols(pr, gf) for pr, (_, gf) in zip(prices, forwards)]
+            def sets_vols(params_list):
+                prices, _, fwds = rows.price_sets([p.sigma for p in params_list], [p.risk_premia_gamma for p in params_list],
+                                                  option_chain.forwards, option_chain.strikes_ttms, option_chain.optiontypes_ttms,
+                                                  recenter_forward=recenter, return_forwards=True)
+                return [ivols(pr, gf) for pr, (_, gf, _) in zip(prices, fwds)]
+
+            def model_vols(pars):
+                return sets_vols([unpack(pars)])[0]
+
+            def model_vols_batch(pars_list):
+                # each vector priced with its own copy of params0 as unpack leaves it; params0 ends at the last vector
+                return sets_vols([dataclasses.replace(unpack(pars)) for pars in pars_list])
+        else:
+            def model_vols(pars):
+                prices, (_, gamma_forwards) = hawkesjd_chain_pricer_with_risk_premia(model_params=unpack(pars), **chain)
+                return ivols(prices, gamma_forwards)
+
+            def model_vols_batch(pars_list):
+                # each vector priced with its own copy of params0 as unpack leaves it; params0 ends at the last vector
+                params_list = [dataclasses.replace(unpack(pars)) for pars in pars_list]
+                prices, forwards = hawkesjd_chain_pricer_with_risk_premia_batch(params_list=params_list, **chain)
+                return [ivols(pr, gf) for pr, (_, gf) in zip(prices, forwards)]
 
         batched = bool(kwargs.get("batched_gradient", True))
-        return ImpliedVolObjective(model_vols, market_vols, weights, model_vols_batch=model_vols_batch if batched else None,
-                                   bounds=RISK_PREMIA_BOUNDS, fd_step=RISK_PREMIA_FD_STEP)
+        objective = ImpliedVolObjective(model_vols, market_vols, weights, model_vols_batch=model_vols_batch if batched else None,
+                                        bounds=RISK_PREMIA_BOUNDS, fd_step=RISK_PREMIA_FD_STEP)
+        if estimator == "conditional":
+            objective.jump_rows = rows                           # the handle lives as long as the objective
+        return objective
 
     @timer
     def calibrate_risk_premia_gamma_to_chain(self, option_chain: OptionChain, params0: HawkesJDParams,
@@ -325,7 +357,11 @@ class HawkesJDPricer(ModelPricer):
         `kwargs`: disp= (SLSQP printing, default True); batched_gradient= (default True: SLSQP's forward-difference
         gradient at its step 0.025 -- the same points it would evaluate -- from one
         hawkesjd_chain_pricer_with_risk_premia_batch of the bumped vectors per iterate; False lets SLSQP difference itself);
-        ode_rtol= / ode_atol= (default 1e-10 / 1e-12).
+        ode_rtol= / ode_atol= (default 1e-10 / 1e-12); estimator= ("fourier", the default: everything above; "conditional": the
+        model prices by conditional Monte Carlo on jump rows stepped ONCE at construction -- hawkesjd_jump_rows with nb_path=,
+        nb_steps_per_year=, seed= -- so that every evaluation, and every gradient batch of SLSQP's bumped points, is
+        one HawkesJumpRows.price_sets with recenter_forward=; codec, bounds, weights, options and the inversion are unchanged,
+        and last_calibration gains estimator and n_stepping_calls = 1; any other value: ValueError).
         `self.last_calibration` keeps {"n_eval", "n_gradient_batches", "objective", "success", "status", "message", "nit",
         "nfev", "x"} of the run."""
         from scipy.optimize import minimize
@@ -338,6 +374,9 @@ class HawkesJDPricer(ModelPricer):
         self.last_calibration = dict(n_eval=objective.n_eval, n_gradient_batches=objective.n_batches, objective=float(res.fun),
                                      success=bool(res.success), status=int(res.status), message=str(res.message),
                                      nit=int(res.nit), nfev=int(res.nfev), x=np.array(res.x, dtype=float))
+        if kwargs.get("estimator", "fourier") == "conditional":
+            self.last_calibration.update(estimator="conditional", n_stepping_calls=1)
+            objective.jump_rows.free()
         fit = unpack_risk_premia_vector(res.x, params0)
         if print_iter:
             print(f"unpack_pars: sigma={res.x[0]}, gamma={fit.risk_premia_gamma}")
@@ -368,6 +407,16 @@ class HawkesJDPricer(ModelPricer):
                                                                      strikes_ttms=option_chain.strikes_ttms,
                                                                      optiontypes_ttms=option_chain.optiontypes_ttms, nb_path=nb_path,
                                                                      **params.to_dict(), **kwargs)
+
+    def model_mc_price_chain_conditional_sets(self, option_chain: OptionChain, params: HawkesJDParams, sigmas, risk_premia_gammas,
+                                              nb_path: int = 100000, **kwargs):
+        """the chain at every (sigma_q, gamma_q) with the other parameters from params, from ONE stepping launch
+        (hawkesjd_mc_chain_pricer_conditional_sets); extensions seed=, nb_steps_per_year=, recenter_forward=, return_forwards="""
+        return hawkesjd_mc_chain_pricer_conditional_sets(sigmas, risk_premia_gammas, ttms=option_chain.ttms,
+                                                         forwards=option_chain.forwards, discfactors=option_chain.discfactors,
+                                                         strikes_ttms=option_chain.strikes_ttms,
+                                                         optiontypes_ttms=option_chain.optiontypes_ttms, nb_path=nb_path,
+                                                         **params.to_dict(), **kwargs)
 
     def model_mc_chain_greeks_conditional_with_risk_premia(self, option_chain: OptionChain, params: HawkesJDParams,
                                                            nb_path: int = 100000, **kwargs) -> dict:
@@ -945,6 +994,165 @@ def hawkesjd_mc_chain_pricer_conditional_with_risk_premia_gammas(ttms: np.ndarra
     if not return_forwards:
         return prices, stderrs
     return prices, stderrs, [(st[:, 0].copy(), st[:, 2].copy(), st) for st in stats]
+
+
+def jump_sets_request(sigmas, risk_premia_gammas) -> Tuple[np.ndarray, np.ndarray]:
+    """the (sigma, gamma) sets of one request as two float64 vectors of one length >= 1: ValueError for unequal lengths, a negative
+    or non-finite sigma, a non-finite gamma"""
+    s = np.atleast_1d(np.asarray(sigmas, dtype=np.float64)).ravel()
+    g = np.atleast_1d(np.asarray(risk_premia_gammas, dtype=np.float64)).ravel()
+    if s.size != g.size or s.size < 1:
+        raise ValueError(f"one sigma and one risk-premia gamma per set, got {s.size} and {g.size}")
+    if not (np.all(np.isfinite(s)) and np.all(s >= 0.0)):
+        raise ValueError("sigmas must be finite and not negative")
+    if not np.all(np.isfinite(g)):
+        raise ValueError("risk-premia gammas must be finite")
+    return s, g
+
+
+def jump_step_grid(ttms, nb_steps_per_year: int) -> Tuple[List[int], List[float]]:
+    """(steps, dt) per expiry: the fused drivers' grid, the one engine.step_hawkesjd_chain_cond_rows steps on"""
+    if int(nb_steps_per_year) <= 0:
+        raise ValueError("nb_steps_per_year must be positive")
+    nbs, dts, t0 = [], [], 0.0
+    for t in np.asarray(ttms, dtype=np.float64).ravel():
+        d = float(t) - t0
+        nb = int(d * float(int(nb_steps_per_year))) + 1
+        nbs.append(nb)
+        dts.append(d if nb == 1 else d / float(nb))
+        t0 = float(t)
+    return nbs, dts
+
+
+def jump_sets_variances(sigma: float, nb_steps: Sequence[int], dts: Sequence[float]) -> np.ndarray:
+    """v_i = cv_i(sigma) per expiry by the host formula of svmc_hawkesjd_chain_cond (include/svmc.h): cv_i = cv_{i-1} +
+    nb_steps_i (sigma sigma dt_i) in double, in slice order from 0, each product and sum rounded once -- the bits of that entry's
+    cv row"""
+    sigma2 = float(sigma) * float(sigma)
+    out, cv = [], 0.0
+    for nb, dt in zip(nb_steps, dts):
+        cv = cv + float(int(nb)) * (sigma2 * float(dt))
+        out.append(cv)
+    return np.array(out, dtype=np.float64)
+
+
+class HawkesJumpRows:
+    """The jump rows of a Hawkes chain, stepped ONCE (hawkesjd_jump_rows): per expiry a_j = drift, compensators and jumps of path j,
+    which depend on neither sigma nor risk_premia_gamma, in a device buffer of its own (m x nb_path doubles: no other call on the
+    engine writes it), with the step grid, so that every (sigma, gamma) is priced by price_sets without another stepping launch
+    (include/svmc_est.h svmc_jump_sets_payoff_chain)."""
+
+    def __init__(self, engine, rows: DeviceBuffer, ttms: np.ndarray, nb_steps: Sequence[int], dts: Sequence[float], seed: int,
+                 call_id: int):
+        self.engine, self.rows = engine, rows
+        self.ttms = np.array(ttms, dtype=np.float64)
+        self.nb_steps, self.dts = [int(n) for n in nb_steps], [float(d) for d in dts]
+        self.nb_path, self.seed, self.call_id = int(engine.n_path), int(seed), int(call_id)
+
+    @property
+    def n_expiries(self) -> int:
+        return self.ttms.size
+
+    def row_ptrs(self) -> List[int]:
+        return [self.rows.offset(i * self.nb_path) for i in range(self.n_expiries)]
+
+    def variances(self, sigma: float) -> np.ndarray:
+        """v_i(sigma) per expiry: jump_sets_variances on this handle's step grid"""
+        return jump_sets_variances(sigma, self.nb_steps, self.dts)
+
+    def numpy(self) -> np.ndarray:
+        """the rows on the host, [n_expiries, nb_path]"""
+        return self.engine.download(self.rows.ptr, self.n_expiries * self.nb_path).reshape(self.n_expiries, self.nb_path)
+
+    def price_sets(self, sigmas, risk_premia_gammas, forwards, strikes_ttms: Sequence[np.ndarray],
+                   optiontypes_ttms: Sequence[np.ndarray], recenter_forward: bool = False, return_forwards: bool = False):
+        """the chain under exp(gamma x) by conditional Monte Carlo at every (sigma_q, gamma_q) on these rows: (prices, stderrs), each
+        [set][expiry] in the strikes' shapes, undiscounted; with return_forwards=True a third item [set] -> (normalizers,
+        gamma_forwards, stats [n_expiries, 8] in the order of engine.TILTED_COND_STATS_FIELDS), as
+        hawkesjd_mc_chain_pricer_conditional_with_risk_premia_gammas returns per gamma.  Any number of sets: calls of
+        engine.JUMP_SETS_MAX; a set's numbers are the same bits whichever others share the request.  'C' / 'P' only."""
+        codes = [tilted_type_codes(t) for t in optiontypes_ttms]            # ValueError("not implemented")
+        s, g = jump_sets_request(sigmas, risk_premia_gammas)
+        strikes_ttms = [np.asarray(k, dtype=np.float64) for k in strikes_ttms]
+        if len(strikes_ttms) != self.n_expiries:
+            raise ValueError("chain arrays must have one entry per maturity of the rows")
+        var = np.array([self.variances(x) for x in s]).reshape(s.size, self.n_expiries)
+        prices, stderrs, extra = [], [], []
+        for q0 in range(0, s.size, JUMP_SETS_MAX):
+            sl = slice(q0, q0 + JUMP_SETS_MAX)
+            p, e, stats, _ = self.engine.jump_sets_payoffs(forwards, strikes_ttms, codes, var[sl], g[sl], bool(recenter_forward),
+                                                           a_ptrs=self.row_ptrs())
+            prices += p
+            stderrs += e
+            extra += [(st[:, 0].copy(), st[:, 2].copy(), st) for st in stats]
+        return (prices, stderrs, extra) if return_forwards else (prices, stderrs)
+
+    def free(self) -> None:
+        self.rows.free()
+
+
+def hawkesjd_jump_rows(ttms: np.ndarray, lambda_p: float, lambda_m: float, mu: float, shift_p: float, mean_p: float, shift_m: float,
+                       mean_m: float, theta_p: float, kappa_p: float, beta1_p: float, beta2_p: float, theta_m: float, kappa_m: float,
+                       beta1_m: float, beta2_m: float, sigma: float = 0.0, risk_premia_gamma=None, nb_path: int = 100000,
+                       nb_steps_per_year: int = NB_STEPS_PER_YEAR, seed: Optional[int] = None, comm=None, devices=None
+                       ) -> HawkesJumpRows:
+    """step the jump part of the Hawkes chain ONCE for every (sigma, gamma): in the conditional step the jump
+    decisions, the jump sizes and both intensities depend on neither, and sigma enters a path's conditional mean only through the
+    deterministic -sigma^2 dt / 2 of every step, so svmc_hawkesjd_chain_cond at sigma = 0 leaves rows a_j with
+    x_T | jumps ~ N(a_j - v / 2, v), v = cv_i(sigma) one host number per expiry.  The jumps are those of
+    hawkesjd_mc_chain_pricer_conditional(_with_risk_premia) at this seed (streams 9 and 10).  sigma and risk_premia_gamma are
+    accepted and unused.  Returns a HawkesJumpRows; one GPU only (NotImplementedError).  Chains longer than 16 expiries step in
+    launches of 16."""
+    who = "hawkesjd_jump_rows"
+    if devices is not None or (comm or svdist.get_default_comm()).world > 1:
+        raise NotImplementedError(f"{who}: sharded paths (comm.world > 1, devices=) are not covered")
+    t = np.ascontiguousarray(np.asarray(ttms, dtype=np.float64)).ravel()
+    if t.size < 1:
+        raise ValueError("at least one expiry")
+    nbs, dts = jump_step_grid(t, nb_steps_per_year)
+    block = params_block(lambda_p=lambda_p, lambda_m=lambda_m, mu=mu, sigma=0.0, shift_p=shift_p, mean_p=mean_p, shift_m=shift_m,
+                         mean_m=mean_m, theta_p=theta_p, kappa_p=kappa_p, beta1_p=beta1_p, beta2_p=beta2_p, theta_m=theta_m,
+                         kappa_m=kappa_m, beta1_m=beta1_m, beta2_m=beta2_m)
+    eng = get_engine(int(nb_path))
+    rng_seed, call_id = next_rng_call(seed)
+    m, n = t.size, int(nb_path)
+    eng.step_hawkesjd_jump_rows({"ttms": t, "m": m}, block, int(nb_steps_per_year), rng_seed, call_id)
+    rows = DeviceBuffer(m * n)
+    # the snapshot rows are shared with every other call on the engine: the handle keeps its own copy
+    eng.copy_rows(rows.ptr, eng.snapshot_ptr(0), m * n)
+    eng.synchronize()
+    return HawkesJumpRows(eng, rows, t, nbs, dts, rng_seed, call_id)
+
+
+def hawkesjd_mc_chain_pricer_conditional_sets(sigmas, risk_premia_gammas, ttms: np.ndarray, forwards: np.ndarray,
+                                              discfactors: np.ndarray, strikes_ttms: Sequence[np.ndarray],
+                                              optiontypes_ttms: Sequence[np.ndarray], lambda_p: float, lambda_m: float, mu: float,
+                                              shift_p: float, mean_p: float, shift_m: float, mean_m: float, theta_p: float,
+                                              kappa_p: float, beta1_p: float, beta2_p: float, theta_m: float, kappa_m: float,
+                                              beta1_m: float, beta2_m: float, sigma=None, risk_premia_gamma=None,
+                                              nb_path: int = 100000, variable_type: VariableType = VariableType.LOG_RETURN,
+                                              nb_steps_per_year: int = NB_STEPS_PER_YEAR, seed: Optional[int] = None,
+                                              recenter_forward: bool = False, return_forwards: bool = False, comm=None,
+                                              devices=None):
+    """hawkesjd_mc_chain_pricer_conditional_with_risk_premia at EVERY (sigma_q, gamma_q) of two sequences of one length from ONE
+    stepping launch: one hawkesjd_jump_rows plus one HawkesJumpRows.price_sets.  At one seed a set's prices
+    differ from that pricer's at (sigma_q, gamma_q) by the rounding of the paths' conditional means only: the jumps are the same.
+    Returns as price_sets; prices are UNDISCOUNTED: discfactors are accepted and ignored.  sigma= and risk_premia_gamma= (the
+    parameter set's own) are accepted and unused.  'C' / 'P' only (others: ValueError("not implemented")), LOG_RETURN only, one GPU
+    only (NotImplementedError); a ValueError for sequences of unequal length, a negative or non-finite sigma, a non-finite gamma;
+    each raised before any engine is asked for.  Not in the reference API."""
+    check_conditional_request("hawkesjd_mc_chain_pricer_conditional_sets", variable_type, comm, devices, optiontypes_ttms)
+    s, g = jump_sets_request(sigmas, risk_premia_gammas)
+    strikes_ttms = [np.asarray(k, dtype=np.float64) for k in strikes_ttms]
+    tilted_chain_arrays(forwards, strikes_ttms, [tilted_type_codes(t) for t in optiontypes_ttms], g[:1], ttms=ttms)    # the chain's checks
+    rows = hawkesjd_jump_rows(ttms, lambda_p=lambda_p, lambda_m=lambda_m, mu=mu, shift_p=shift_p, mean_p=mean_p, shift_m=shift_m,
+                              mean_m=mean_m, theta_p=theta_p, kappa_p=kappa_p, beta1_p=beta1_p, beta2_p=beta2_p, theta_m=theta_m,
+                              kappa_m=kappa_m, beta1_m=beta1_m, beta2_m=beta2_m, nb_path=nb_path,
+                              nb_steps_per_year=nb_steps_per_year, seed=seed)
+    try:
+        return rows.price_sets(s, g, forwards, strikes_ttms, optiontypes_ttms, recenter_forward, return_forwards)
+    finally:
+        rows.free()
 
 
 def hawkesjd_mc_chain_pricer_conditional_with_risk_premia(ttms: np.ndarray, forwards: np.ndarray, discfactors: np.ndarray,

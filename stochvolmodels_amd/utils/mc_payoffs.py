@@ -11,7 +11,7 @@ from typing import Tuple
 
 import numpy as np
 
-from ..engine import (cond_density_arrays, cond_density_stats_dicts, get_engine, option_type_codes, payoff_finalize, payoff_shifts,
+from ..engine import (JUMP_SETS_MAX, cond_density_arrays, cond_density_stats_dicts, get_engine, option_type_codes, payoff_finalize, payoff_shifts,
                       tilted_chain_arrays, tilted_greeks_stats_dicts, tilted_stats_dicts, tilted_type_codes)
 from ..mc_chain import variable_type_code
 from .config import VariableType
@@ -121,6 +121,40 @@ def compute_mc_vars_payoff_conditional_with_gamma(mu: np.ndarray, cv: np.ndarray
     if return_stats:
         out = out + ([tilted_stats_dicts(st)[0] for st in stats],)
     return tuple(o[0] for o in out) if single else out
+
+
+def compute_mc_vars_payoff_jump_sets(a: np.ndarray, variances, gammas, forward: float, strikes_ttm: np.ndarray,
+                                     optiontypes_ttm: np.ndarray, recenter: bool = False, return_stats: bool = False):
+    """option prices under the exponential risk-premia kernel for MANY sets (variance v_q, gamma g_q) from ONE host row a with
+    x | a ~ N(a - v / 2, v), v the same on every path (the Hawkes jump-diffusion's rows at sigma = 0; any model of that form), the
+    estimator of include/svmc_est.h's svmc_jump_sets_payoff_chain: compute_mc_vars_payoff_conditional_with_gamma on
+    (a - v_q / 2, v_q) at gamma g_q for every q, from one upload and one pass.  variances, gammas: sequences of one length (any
+    number: calls of engine.JUMP_SETS_MAX).  Returns (prices, stderrs), each [set] in the strikes' shape, and with
+    return_stats=True a third item, [set] dicts of engine.TILTED_COND_STATS_FIELDS with "corr" added.  'C' / 'P' only (others:
+    ValueError("not implemented")); undiscounted."""
+    codes = tilted_type_codes(optiontypes_ttm)                   # ValueError("not implemented")
+    strikes = np.asarray(strikes_ttm, dtype=np.float64)
+    v = np.atleast_1d(np.asarray(variances, dtype=np.float64)).ravel()
+    g = np.atleast_1d(np.asarray(gammas, dtype=np.float64)).ravel()
+    if v.size != g.size or v.size == 0:
+        raise ValueError("variances and gammas must be non-empty and of one length")
+    if not (np.all(np.isfinite(v)) and np.all(v >= 0.0)):
+        raise ValueError("variances must be finite and not negative")
+    if not np.all(np.isfinite(g)):
+        raise ValueError("risk-premia gammas must be finite")
+    a = np.ascontiguousarray(a, dtype=np.float64).ravel()
+    if a.size == 0:
+        raise ValueError("a must be non-empty")
+    eng = get_engine(a.size)
+    eng.upload(eng.x.ptr, a)
+    prices, stderrs, stats = [], [], []
+    for q0 in range(0, v.size, JUMP_SETS_MAX):
+        sl = slice(q0, q0 + JUMP_SETS_MAX)
+        p, e, st, corr = eng.jump_sets_payoffs([float(forward)], [strikes], [codes], v[sl, None], g[sl], bool(recenter))
+        prices += [x[0] for x in p]
+        stderrs += [x[0] for x in e]
+        stats += [dict(tilted_stats_dicts(x)[0], corr=float(corr[0])) for x in st]
+    return (prices, stderrs, stats) if return_stats else (prices, stderrs)
 
 
 def compute_mc_vars_greeks_conditional_with_gamma(mu: np.ndarray, cv: np.ndarray, forward: float, strikes_ttm: np.ndarray,
