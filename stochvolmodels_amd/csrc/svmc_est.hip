@@ -19,11 +19,9 @@
 // neighbours' and the block sum's tree is the same for every accumulator index: a gamma's, an expiry's and a strike's results
 // are the same bits whichever others share the call, and sum W and the kept count are row f17's bits.  No atomics, no scratch,
 // LDS for the block sums' exchange only.
+// What the three share with each other and with libsvmc_ext.so -- the forward pass, the strike-group preload, the payoff and finish
+// bodies, the finish kernels' pieces, the table's walk and the host's check and driver -- is svmc_tilted_cond.h's.
 #include <hip/hip_runtime.h>
-
-#include <cmath>
-#include <cstring>
-#include <vector>
 
 #include "svmc_est.h"
 
@@ -42,72 +40,25 @@ namespace svmc {
 constexpr int TCG_KT = SVMC_TCG_KT;
 constexpr int TCG_COLS = 9;            // per quote, for v = delta, dual delta, dual gamma: [sum W d, sum (W d)^2, sum W^2 d]
 constexpr int TCG_NSTAT = 4;           // per (expiry, gamma): [sum W, sum W^2, kept, kept with cv == 0]
-constexpr int TCG_MAX_GROUPS = 65535;  // the groups are a grid's y dimension
 
-// the device table of a call; the image (expiries .. gammas) is uploaded once
-struct TcgTable {
-    const TcExpiry *expiries;          // [m]
-    const QuoteGroup *groups;          // [G] groups of up to TCG_KT strikes; pad = 1: the expiry's first, which stores its statistics
-                                       // sums (an expiry without strikes has one group of nk = 0 for them)
-    const double *strikes;             // [K]
-    const double *is_put;              // [K] 0 | 1
-    const double *dshift;              // [K] s 1{s (F - K) > 0}: the shift of delta's sums; dual delta's is its negative
-    const double *gammas;              // [NG]
-    double *kp, *ln_kp;                // [K] device-computed: K + corr, its logarithm (0 where K + corr <= 0)
-    double *fwd;                       // [m][4]: sum (e - 1), sum (e - 1)^2, kept count of f11's rule, corr
-    double *fwd_partials;              // [rows][m][3]
-    double *q_partials;                // [rows][NG][K][TCG_COLS]
-    double *stat_partials;             // [rows][NG][m][TCG_NSTAT]
-    double *out;                       // greeks [NG][SVMC_TCG_ROWS][K], statistics [NG][m][SVMC_TCG_STATS_DOUBLES]: one block
-    int m, K, NG;
-    unsigned rows;
-};
-struct TcgImage {
-    TcExpiry *expiries;
-    QuoteGroup *groups;
-    double *strikes, *is_put, *dshift, *gammas;
-};
-inline TcgImage tcg_image(Layout &w, int m, size_t K, int G, int NG)
-{
-    return TcgImage{w.take<TcExpiry>(m), w.take<QuoteGroup>(G), w.take<double>(K), w.take<double>(K), w.take<double>(K),
-                    w.take<double>(NG)};                   // (a braced list: in this order)
-}
+// the device table of a call (svmc_tilted_cond.h): zs the gammas [NG]; shift [K] s 1{s (F - K) > 0}, the shift of delta's sums (dual
+// delta's is its negative); q_partials [rows][NG][K][TCG_COLS], stat_partials [rows][NG][m][TCG_NSTAT]; out: greeks
+// [NG][SVMC_TCG_ROWS][K], statistics [NG][m][SVMC_TCG_STATS_DOUBLES]
+struct TcgTable : TcTableOf<double> {};
 inline size_t tcg_out_doubles(int m, size_t K, int NG)
 {
     return static_cast<size_t>(NG) * (SVMC_TCG_ROWS * K + static_cast<size_t>(SVMC_TCG_STATS_DOUBLES) * m);
 }
-// ONE walk that is both the workspace's byte count and its carving: the image, the forward pass's head, the results, the partials.
-// Returns the bytes of the image, which the walk starts with.
 inline size_t tcg_workspace(Layout &w, size_t n_path, int m, size_t K, int G, int NG, TcgTable &t)
 {
-    const size_t rows = quote_rows(n_path);
-    const TcgImage im = tcg_image(w, m, K, G, NG);
-    const size_t image_bytes = w.bytes();
-    t.expiries = im.expiries;
-    t.groups = im.groups;
-    t.strikes = im.strikes;
-    t.is_put = im.is_put;
-    t.dshift = im.dshift;
-    t.gammas = im.gammas;
-    t.kp = w.take<double>(K);
-    t.ln_kp = w.take<double>(K);
-    t.fwd = w.take<double>(4 * static_cast<size_t>(m));
-    t.out = w.take<double>(tcg_out_doubles(m, K, NG));
-    t.fwd_partials = w.take<double>(rows * 3 * m);
-    t.q_partials = w.take<double>(rows * NG * K * TCG_COLS);
-    t.stat_partials = w.take<double>(rows * NG * m * TCG_NSTAT);
-    t.m = m;
-    t.K = static_cast<int>(K);
-    t.NG = NG;
-    t.rows = static_cast<unsigned>(rows);
-    return image_bytes;
+    return tc_workspace(w, n_path, m, K, G, NG, NG, tcg_out_doubles(m, K, NG), TCG_COLS, TCG_NSTAT, t);
 }
 
 // ---- the forward pass: rows f11's / f17's statements (svmc_tilted_cond.h) ---------------------------------------------------------
 __global__ __launch_bounds__(BLOCK) void tilted_cond_greeks_forward_kernel(TcgTable t, size_t n)
 {
     __shared__ double lds[4 * 3];
-    tc_forward_body(t, n, lds);
+    tc_forward_body<false>(t, n, lds);
 }
 
 __global__ __launch_bounds__(BLOCK) void tilted_cond_greeks_forward_finish_kernel(TcgTable t, int recenter)
@@ -148,7 +99,7 @@ __global__ __launch_bounds__(BLOCK) void tilted_cond_greeks_kernel(TcgTable t, s
     const QuoteGroup g = t.groups[blockIdx.y];
     const TcExpiry ex = t.expiries[g.expiry];
     const int nk = g.nk;                                   // (block-uniform; 0: the group only forms the statistics)
-    const double gamma = t.gammas[blockIdx.z];
+    const double gamma = t.zs[blockIdx.z];
     const double *fw = t.fwd + 4 * g.expiry;
     const double c = recenter ? fw[0] / fw[2] : 0.0;       // mean_kept(e) - 1, the quotient the forward finish forms: corr = F c
     const double half_g2 = 0.5 * gamma * gamma, g_half = gamma + 0.5;
@@ -156,16 +107,9 @@ __global__ __launch_bounds__(BLOCK) void tilted_cond_greeks_kernel(TcgTable t, s
     bool put[KT];
 #pragma unroll
     for (int j = 0; j < NSUM; ++j) acc[j] = 0.0;
+    tc_group_preload(t, g, kp, ln_kp, dshift, put);
 #pragma unroll
-    for (int k = 0; k < KT; ++k) {
-        const int kk = g.k0 + ((k < nk) ? k : 0);          // the unused strikes of a group repeat its first; their sums are dropped
-        const bool on = nk > 0;                            // a group without strikes reads none
-        kp[k] = on ? t.kp[kk] : 1.0;
-        ln_kp[k] = on ? t.ln_kp[kk] : 0.0;
-        inv_kp[k] = 1.0 / kp[k];
-        dshift[k] = on ? t.dshift[kk] : 0.0;
-        put[k] = on ? t.is_put[kk] != 0.0 : false;
-    }
+    for (int k = 0; k < KT; ++k) inv_kp[k] = 1.0 / kp[k];
     const double forward = ex.forward, ln_forward = ex.ln_forward;
     const size_t stride = static_cast<size_t>(gridDim.x) * BLOCK;
     for (size_t i = static_cast<size_t>(blockIdx.x) * BLOCK + threadIdx.x; i < n; i += stride) {
@@ -217,18 +161,10 @@ __global__ __launch_bounds__(BLOCK) void tilted_cond_greeks_finish_kernel(TcgTab
     const int col = blockIdx.x, gi = blockIdx.y;
     const size_t K = static_cast<size_t>(t.K), m = static_cast<size_t>(t.m), NG = static_cast<size_t>(t.NG);
     const size_t ld_stat = NG * m * TCG_NSTAT, ld_q = NG * K * TCG_COLS;
-    int i = col - t.K;                                     // the expiry (block-uniform)
-    if (col < t.K) {
-        i = 0;
-        while (i + 1 < t.m && col >= t.expiries[i].k1) ++i;            // expiries without strikes are skipped over
-    }
+    const int i = tc_expiry_of_column(t.expiries, t.m, t.K, col);
     const double *st = t.stat_partials + (static_cast<size_t>(gi) * m + i) * TCG_NSTAT;
     double s[TCG_NSTAT];
-#pragma unroll
-    for (int q = 0; q < TCG_NSTAT; ++q) {
-        if (q > 0) __syncthreads();
-        s[q] = block_column_sum(st + q, t.rows, ld_stat, lds);
-    }
+    tc_column_sums(st, {0, 1, 2, 3}, t.rows, ld_stat, lds, s);
     const double W = s[0], Q = s[1], kept = s[2];
     if (col >= t.K) {
         if (threadIdx.x != 0) return;
@@ -247,17 +183,14 @@ __global__ __launch_bounds__(BLOCK) void tilted_cond_greeks_finish_kernel(TcgTab
         c[q] = block_column_sum(qp + q, t.rows, ld_q, lds);
     }
     if (threadIdx.x != 0) return;
-    // value = shift + sum W d / sum W; sum (W (v - value))^2 = sum (W d)^2 - 2 e sum W^2 d + e^2 sum W^2, e = value - shift.
-    // One kept path: the estimate IS that path's value and the squares about it are zero identically
-    const double dshift = t.dshift[col];
+    const double dshift = t.shift[col];
     const double shift[3] = {dshift, -dshift, 0.0};
     double v[3], err[3];
 #pragma unroll
     for (int q = 0; q < 3; ++q) {
-        const double e = c[3 * q] / W;
-        const double var = (kept > 1.0) ? fma(e, fma(e, Q, -2.0 * c[3 * q + 2]), c[3 * q + 1]) : 0.0;
+        double e;                                          // value = shift + e
+        tc_value_error(c[3 * q], c[3 * q + 1], c[3 * q + 2], W, Q, kept, e, err[q]);
         v[q] = e + shift[q];
-        err[q] = sqrt(fmax(var, 0.0)) / W;
     }
     const double r = t.strikes[col] / t.expiries[i].forward, r2 = r * r;
     double *out = t.out + static_cast<size_t>(gi) * SVMC_TCG_ROWS * K + col;
@@ -323,7 +256,7 @@ constexpr int CD_NSTAT = 8;            // per (expiry, gamma): [sum W, sum W^2, 
 
 struct CdExpiry {
     const double *mu, *cv;
-    int p0, p1;                        // its points [p0, p1)
+    int k0, k1;                        // its points [k0, k1)
 };
 // the device table of a call; the image (expiries .. gammas) is uploaded once
 struct CdTable {
@@ -478,18 +411,10 @@ __global__ __launch_bounds__(BLOCK) void cond_density_finish_kernel(CdTable t, s
     const int col = blockIdx.x, gi = blockIdx.y;
     const size_t P = static_cast<size_t>(t.P), m = static_cast<size_t>(t.m), NG = static_cast<size_t>(t.NG);
     const size_t ld_stat = NG * m * CD_NSTAT;
-    int i = col - t.P;                                     // the expiry (block-uniform)
-    if (col < t.P) {
-        i = 0;
-        while (i + 1 < t.m && col >= t.expiries[i].p1) ++i;            // expiries without points are skipped over
-    }
+    const int i = tc_expiry_of_column(t.expiries, t.m, t.P, col);
     const double *st = t.stat_partials + (static_cast<size_t>(gi) * m + i) * CD_NSTAT;
     double s[5];
-#pragma unroll
-    for (int q = 0; q < 5; ++q) {
-        if (q > 0) __syncthreads();
-        s[q] = block_column_sum(st + q, t.rows, ld_stat, lds);
-    }
+    tc_column_sums(st, {0, 1, 2, 3, 4}, t.rows, ld_stat, lds, s);
     const double W = s[0], Q = s[1], kept = s[2], bad = s[4];
     if (col >= t.P) {
         if (threadIdx.x != 0) return;
@@ -508,32 +433,35 @@ __global__ __launch_bounds__(BLOCK) void cond_density_finish_kernel(CdTable t, s
     __syncthreads();
     const double c = block_column_sum(t.c_partials + static_cast<size_t>(gi) * P + col, t.rows, NG * P, lds);
     if (threadIdx.x != 0) return;
-    // sum (W (v - pdf))^2 with W v = e^{gamma x} n: e^{2 gamma x} S2 - 2 pdf e^{gamma x} C + pdf^2 sum W^2.  One kept path: the estimate IS
-    // that path's value and the squares about it are zero identically
+    // tc_value_error's sums with W v = e^{gamma x} n: sum W v = e^{gamma x} S1, sum (W v)^2 = e^{2 gamma x} S2, sum W^2 v = e^{gamma x} C
     const double gamma = t.gammas[gi];
     const double eg = (gamma == 0.0) ? 1.0 : exp_full(gamma * t.points[col]);              // once per (point, gamma)
     const double nan = __builtin_nan("");
-    const double pdf = eg * s1 / W;                        // 0 / 0 -> NaN: no kept path
-    const double var = (kept > 1.0) ? fma(pdf, fma(pdf, Q, -2.0 * (eg * c)), (eg * eg) * s2) : 0.0;
+    double pdf, err;                                       // 0 / 0 -> NaN: no kept path
+    tc_value_error(eg * s1, (eg * eg) * s2, eg * c, W, Q, kept, pdf, err);
     const bool ok = bad == 0.0;
     t.out[static_cast<size_t>(gi) * P + col] = ok ? pdf : nan;
-    t.out[(NG + gi) * P + col] = ok ? sqrt(fmax(var, 0.0)) / W : nan;
+    t.out[(NG + gi) * P + col] = ok ? err : nan;
 }
 
 // ---- many (sigma, gamma) sets on one set of jump rows (svmc_jump_sets_payoff_chain; the header states the estimator) ----
 // Four launches on one uploaded table:
 //   jump_sets_forward_kernel, jump_sets_forward_finish_kernel
-//                                the forward pass of rows f11 / f17 on the rows (a, 0): tc_forward_body's statements and order with
-//                                the constant 0.0 where it reads cv, then tc_forward_finish_body itself -- corr, K' = K + corr and ln K'
-//                                are svmc_cmc_payoff_chain's bits on (a, 0), ONCE for all sets
-//   jump_sets_payoff_kernel      block (path block, group of up to JS_KT strikes of one expiry, tile of JS_ST sets; 4 and 1, below): the set's constants
+//                                the forward pass of rows f11 / f17 on the rows (a, 0): tc_forward_body with the constant 0.0 where it
+//                                reads cv (ZERO_CV: the table's cv is null), then tc_forward_finish_body -- corr, K' = K + corr and
+//                                ln K' are svmc_cmc_payoff_chain's bits on (a, 0), ONCE for all sets
+//   jump_sets_payoff_kernel      block (path block, group of up to JS_KT strikes of one expiry, set): the set's constants
 //                                (g, c, v, sd, 1 / sd, F exp(g v), ln F + g v) come from the table at a block-uniform address; per path
 //                                ONE 8-byte load, exp(a) and exp(g a); per strike tc_black and the sums of w d, (w d)^2, w (w d); the
-//                                seven statistics sums ride in the same block sum and are stored by the expiry's first group
-//   jump_sets_finish_kernel      a block per (quote | expiry, set): the column sums in row order, price, error, statistics in terms of
-//                                W = c w, c applied here once
-// Every accumulator is one (set, strike) or one (set, statistic) whatever the tile, and a thread adds the same paths in the same order:
-// a set's, an expiry's and a strike's results are the same bits whichever others share the call.
+//                                seven statistics sums ride in the same block sum and are stored by the expiry's first group.  The
+//                                statements are tc_payoff_body's (svmc_tilted_cond.h) with this path's terms typed in: on that body, with
+//                                the terms as a path policy, the kernel measured 2.3 % slower at 2^20 paths and 16 sets -- 88 to 92
+//                                VGPRs for 86 and more scalars parked in vector lanes (profiles/cond_tails_refactor.txt) -- so it keeps
+//                                its own
+//   jump_sets_finish_kernel      tc_finish_body, a block per (quote | expiry, set): the column sums in row order, price, error, statistics
+//                                in terms of W = c w, c applied here once (JsWeights), and the corr row
+// Every accumulator is one (set, strike) or one (set, statistic), and a thread adds the same paths in the same order: a set's, an
+// expiry's and a strike's results are the same bits whichever others share the call.
 //
 // THE LAYOUT, measured on the MI355X (profiles/hawkes_jump_sets_bench.json, "layouts": the tail alone on the BTC chain's 49 strikes at
 // 10^5 | 2^20 paths, ms for 1 / 3 / 16 sets; VGPRs and waves per SIMD of the payoff kernel from the ISA metadata).  ST = 1 is row f17's
@@ -552,17 +480,11 @@ __global__ __launch_bounds__(BLOCK) void cond_density_finish_kernel(CdTable t, s
 // twice to nearly four times ST = 1's time) and the accumulators cost the waves.  The set-per-block layout is kept.  Within it a group of
 // four strikes (19 accumulators, 86 VGPRs, five waves) is 2 to 10 % ahead of row f17's eight (31 accumulators, 119 VGPRs, four waves)
 // in all six cells, in two runs that agree within 2 %: forming w and F_t twice as often costs less than the fifth wave hides.  No bit depends on either choice.
+// The ST > 1 rows were measured with a build that is not kept: the kernel is a block per set and the grid's z is the set.
 #ifndef SVMC_JS_KT
 #define SVMC_JS_KT 4
 #endif
-#ifndef SVMC_JS_ST
-#define SVMC_JS_ST 1
-#endif
 constexpr int JS_KT = SVMC_JS_KT;      // strikes per group
-constexpr int JS_ST = SVMC_JS_ST;      // sets per tile
-constexpr int JS_NSTAT = 7;            // [sum w, sum w^2, sum (w-1)^2, sum w ds, sum w^2 ds, sum (w ds)^2, kept], ds = F_t - corr - F
-constexpr int JS_STAT_COLS = 8;        // ... padded, as row f17's
-constexpr int JS_PAY_COLS = 3;         // per quote [sum w d, sum (w d)^2, sum w^2 d]
 
 // the host constants of one (set, expiry)
 struct JsSet {
@@ -570,82 +492,37 @@ struct JsSet {
     double fs, ln_fs;                  // F exp(g v), ln F + g v
     double gv;                         // g v
 };
-// the device table of a call; the image (expiries .. sets) is uploaded once
-struct JsTable {
-    const TcExpiry *expiries;          // [m]; mu = a, cv = null: nothing reads it
-    const QuoteGroup *groups;          // [G] groups of up to JS_KT strikes; pad = 1: the expiry's first, which stores its statistics sums
-    const double *strikes;             // [K]
-    const double *is_put;              // [K] 0 | 1
-    const double *shift;               // [K] the host's shift of a strike's sums
-    const JsSet *sets;                 // [Q][m]
-    double *kp, *ln_kp;                // [K] device-computed: K + corr, its logarithm (0 where K + corr <= 0)
-    double *fwd;                       // [m][4]: sum (e - 1), sum (e - 1)^2, kept count of f11's rule, corr
-    double *fwd_partials;              // [rows][m][3]
-    double *pay_partials;              // [rows][Q][K][JS_PAY_COLS]
-    double *stat_partials;             // [rows][Q][m][JS_STAT_COLS]
-    double *out;                       // prices [Q][K], errors [Q][K], statistics [Q][m][SVMC_TILTED_STATS_DOUBLES], corr [m]: one block
-    int m, K, NG;                      // NG: the sets
-    unsigned rows;
-};
-struct JsImage {
-    TcExpiry *expiries;
-    QuoteGroup *groups;
-    double *strikes, *is_put, *shift;
-    JsSet *sets;
-};
-inline JsImage js_image(Layout &w, int m, size_t K, int G, int Q)
-{
-    return JsImage{w.take<TcExpiry>(m), w.take<QuoteGroup>(G), w.take<double>(K), w.take<double>(K), w.take<double>(K),
-                   w.take<JsSet>(static_cast<size_t>(Q) * m)};         // (a braced list: in this order)
-}
+// the device table of a call (svmc_tilted_cond.h): expiries with mu = a and cv = null, nothing reads it; zs the sets [Q][m];
+// q_partials [rows][Q][K][TC_PAY_COLS], stat_partials [rows][Q][m][TC_STAT_COLS]; NG: the sets; out: prices [Q][K], errors [Q][K],
+// statistics [Q][m][SVMC_TILTED_STATS_DOUBLES], corr [m]
+struct JsTable : TcTableOf<JsSet> {};
 inline size_t js_out_doubles(int m, size_t K, int Q)
 {
     return static_cast<size_t>(Q) * (2 * K + static_cast<size_t>(SVMC_TILTED_STATS_DOUBLES) * m) + m;
 }
-// ONE walk that is both the workspace's byte count and its carving; returns the bytes of the image, which the walk starts with
 inline size_t js_workspace(Layout &w, size_t n_path, int m, size_t K, int G, int Q, JsTable &t)
 {
-    const size_t rows = quote_rows(n_path);
-    const JsImage im = js_image(w, m, K, G, Q);
-    const size_t image_bytes = w.bytes();
-    t.expiries = im.expiries;
-    t.groups = im.groups;
-    t.strikes = im.strikes;
-    t.is_put = im.is_put;
-    t.shift = im.shift;
-    t.sets = im.sets;
-    t.kp = w.take<double>(K);
-    t.ln_kp = w.take<double>(K);
-    t.fwd = w.take<double>(4 * static_cast<size_t>(m));
-    t.out = w.take<double>(js_out_doubles(m, K, Q));
-    t.fwd_partials = w.take<double>(rows * 3 * m);
-    t.pay_partials = w.take<double>(rows * Q * K * JS_PAY_COLS);
-    t.stat_partials = w.take<double>(rows * Q * m * JS_STAT_COLS);
-    t.m = m;
-    t.K = static_cast<int>(K);
-    t.NG = Q;
-    t.rows = static_cast<unsigned>(rows);
-    return image_bytes;
+    return tc_workspace(w, n_path, m, K, G, Q, static_cast<size_t>(Q) * m, js_out_doubles(m, K, Q), TC_PAY_COLS, TC_STAT_COLS, t);
 }
 
-// tc_forward_body's statements and order (svmc_tilted_cond.h) on the rows (a, 0): the constant 0.0 stands where it reads cv[i].
+// row f17's statistics with W = c w, c applied once; the expiry's block of set 0 stores corr behind the statistics
+struct JsWeights {
+    __device__ __forceinline__ static double sum_w(const JsTable &t, int z, int i, double w)
+    {
+        return t.zs[static_cast<size_t>(z) * t.m + i].c * w;
+    }
+    __device__ __forceinline__ static void epilogue(const JsTable &t, int z, int i)
+    {
+        const size_t K = static_cast<size_t>(t.K), m = static_cast<size_t>(t.m), NG = static_cast<size_t>(t.NG);
+        if (z == 0) t.out[NG * (2 * K + SVMC_TILTED_STATS_DOUBLES * m) + i] = t.fwd[4 * i + 3];           // corr, once per expiry
+    }
+};
+
 // grid (path blocks, expiries)
 __global__ __launch_bounds__(BLOCK) void jump_sets_forward_kernel(JsTable t, size_t n)
 {
     __shared__ double lds[4 * 3];
-    const TcExpiry ex = t.expiries[blockIdx.y];
-    const size_t stride = static_cast<size_t>(gridDim.x) * BLOCK;
-    double v[3] = {0.0, 0.0, 0.0};
-    for (size_t i = static_cast<size_t>(blockIdx.x) * BLOCK + threadIdx.x; i < n; i += stride) {
-        double h, e;
-        if (tc_keep_cmc(ex.mu[i], 0.0, h, e)) {
-            const double d = e - 1.0;
-            v[0] += d;
-            v[1] = fma(d, d, v[1]);
-            v[2] += 1.0;
-        }
-    }
-    block_sum_store<3>(v, lds, t.fwd_partials + (static_cast<size_t>(blockIdx.x) * t.m + blockIdx.y) * 3, 3);
+    tc_forward_body<true>(t, n, lds);
 }
 
 __global__ __launch_bounds__(BLOCK) void jump_sets_forward_finish_kernel(JsTable t, int recenter)
@@ -654,25 +531,19 @@ __global__ __launch_bounds__(BLOCK) void jump_sets_forward_finish_kernel(JsTable
     tc_forward_finish_body(t, recenter, lds);
 }
 
-// grid (path blocks, strike groups, set tiles)
-template <int KT, int ST>
+// grid (path blocks, strike groups, sets); tc_payoff_body's statements, its path's terms and strike preload typed in (above)
+template <int KT>
 __global__ __launch_bounds__(BLOCK) void jump_sets_payoff_kernel(JsTable t, size_t n)
 {
-    constexpr int NP = JS_PAY_COLS * KT;                   // a set's payoff accumulators, then its JS_NSTAT statistics
-    constexpr int NS = NP + JS_NSTAT;
-    constexpr int NV = ST * NS;
-    constexpr int NSUM = block_sum_padded(NV);
+    constexpr int NP = TC_PAY_COLS * KT, NV = NP + TC_NSTAT, NSUM = tc_payoff_sums(KT);
     constexpr double INF = __builtin_huge_val();
     __shared__ double lds[4 * NSUM];
     const QuoteGroup g = t.groups[blockIdx.y];
     const TcExpiry ex = t.expiries[g.expiry];
     const int nk = g.nk;                                   // (block-uniform; 0: the group only forms the statistics)
-    const int q0 = static_cast<int>(blockIdx.z) * ST, nq = min(ST, t.NG - q0);
     const double corr = t.fwd[4 * g.expiry + 3];
     const double forward = ex.forward;
-    JsSet set[ST];
-#pragma unroll
-    for (int q = 0; q < ST; ++q) set[q] = t.sets[static_cast<size_t>(q0 + ((q < nq) ? q : 0)) * t.m + g.expiry];    // unused sets repeat the first
+    const JsSet s = t.zs[static_cast<size_t>(blockIdx.z) * t.m + g.expiry];
     double kp[KT], ln_kp[KT], shift[KT], acc[NSUM];
     bool put[KT];
 #pragma unroll
@@ -691,118 +562,58 @@ __global__ __launch_bounds__(BLOCK) void jump_sets_payoff_kernel(JsTable t, size
         const double a = ex.mu[i];
         double h, e;
         if (!tc_keep_cmc(a, 0.0, h, e)) continue;          // f11's rule on (a, 0): a and e = exp(a) finite
+        // once per (path, set): the weight and the shifted forward with its logarithm
+        const double w = exp_full(s.g * a);
+        const double ft = s.fs * e, ln_ft = s.ln_fs + a;
+        const double W = s.c * w, wf = W * ft;
+        if (!(W * W < INF && wf * wf < INF)) continue;     // (a NaN fails the comparison)
+        const double v = w - 1.0;
+        const double wds = w * ((ft - corr) - forward);
+        double *st = acc + NP;
+        st[0] += w;
+        st[1] = fma(w, w, st[1]);
+        st[2] = fma(v, v, st[2]);
+        st[3] += wds;
+        st[4] = fma(w, wds, st[4]);
+        st[5] = fma(wds, wds, st[5]);
+        st[6] += 1.0;
+        if (nk > 0) {
 #pragma unroll
-        for (int q = 0; q < ST; ++q) {
-            const JsSet &s = set[q];
-            // once per (path, set): the weight and the shifted forward with its logarithm
-            const double w = exp_full(s.g * a);
-            const double ft = s.fs * e, ln_ft = s.ln_fs + a;
-            const double W = s.c * w, wf = W * ft;
-            if (!(W * W < INF && wf * wf < INF)) continue; // (a NaN fails the comparison)
-            const double v = w - 1.0;
-            const double wds = w * ((ft - corr) - forward);
-            double *st = acc + q * NS + NP;
-            st[0] += w;
-            st[1] = fma(w, w, st[1]);
-            st[2] = fma(v, v, st[2]);
-            st[3] += wds;
-            st[4] = fma(w, wds, st[4]);
-            st[5] = fma(wds, wds, st[5]);
-            st[6] += 1.0;
-            if (nk > 0) {
-                double *pa = acc + q * NS;
-#pragma unroll
-                for (int k = 0; k < KT; ++k) {
-                    const double wd = w * (tc_black(ft, ln_ft, s.v, s.sd, s.inv_sd, kp[k], ln_kp[k], put[k]) - shift[k]);
-                    pa[k] += wd;
-                    pa[KT + k] = fma(wd, wd, pa[KT + k]);
-                    pa[2 * KT + k] = fma(w, wd, pa[2 * KT + k]);
-                }
+            for (int k = 0; k < KT; ++k) {
+                const double wd = w * (tc_black(ft, ln_ft, s.v, s.sd, s.inv_sd, kp[k], ln_kp[k], put[k]) - shift[k]);
+                acc[k] += wd;
+                acc[KT + k] = fma(wd, wd, acc[KT + k]);
+                acc[2 * KT + k] = fma(w, wd, acc[2 * KT + k]);
             }
         }
     }
     const bool first = g.pad != 0;
     block_sum_apply<NSUM>(acc, lds, NV, [&](int j, double sum) {
-        const int q = j / NS, r = j - q * NS;
-        if (q >= nq) return;
-        const size_t slot = static_cast<size_t>(blockIdx.x) * t.NG + (q0 + q);             // partials[path block][set]
-        if (r < NP) {
-            const int which = r / KT, k = r - which * KT;
-            if (k < nk) t.pay_partials[(slot * t.K + g.k0 + k) * JS_PAY_COLS + which] = sum;
+        const size_t slot = static_cast<size_t>(blockIdx.x) * t.NG + blockIdx.z;           // partials[path block][set]
+        if (j < NP) {
+            const int which = j / KT, k = j - which * KT;
+            if (k < nk) t.q_partials[(slot * t.K + g.k0 + k) * TC_PAY_COLS + which] = sum;
         } else if (first) {
-            t.stat_partials[(slot * t.m + g.expiry) * JS_STAT_COLS + (r - NP)] = sum;
+            t.stat_partials[(slot * t.m + g.expiry) * TC_STAT_COLS + (j - NP)] = sum;
         }
     });
 }
 
-// A block per (column, set): columns [0, K) are the quotes, [K, K + m) the expiries' statistics.  The sums are the column sums of
-// the partial rows in row order, in terms of w; c enters the statistics here, once.
+// a block per (column, set): columns [0, K) are the quotes, [K, K + m) the expiries' statistics
 __global__ __launch_bounds__(BLOCK) void jump_sets_finish_kernel(JsTable t, size_t n)
 {
     __shared__ double lds[4];
-    const int col = blockIdx.x, gi = blockIdx.y;
-    const size_t K = static_cast<size_t>(t.K), m = static_cast<size_t>(t.m), NG = static_cast<size_t>(t.NG);
-    const size_t ld_stat = NG * m * JS_STAT_COLS, ld_pay = NG * K * JS_PAY_COLS;
-    int i = col - t.K;                                     // the expiry (block-uniform)
-    if (col < t.K) {
-        i = 0;
-        while (i + 1 < t.m && col >= t.expiries[i].k1) ++i;            // expiries without strikes are skipped over
-    }
-    const double *st = t.stat_partials + (static_cast<size_t>(gi) * m + i) * JS_STAT_COLS;
-    double s[JS_NSTAT];
-    if (col < t.K) {
-        // the expiry's sum w, sum w^2 and kept count, then the quote's three columns
-        const double *pay = t.pay_partials + (static_cast<size_t>(gi) * K + col) * JS_PAY_COLS;
-        s[0] = block_column_sum(st, t.rows, ld_stat, lds);
-        __syncthreads();
-        s[1] = block_column_sum(st + 1, t.rows, ld_stat, lds);
-        __syncthreads();
-        s[2] = block_column_sum(st + 6, t.rows, ld_stat, lds);
-#pragma unroll
-        for (int q = 0; q < JS_PAY_COLS; ++q) {
-            __syncthreads();
-            s[3 + q] = block_column_sum(pay + q, t.rows, ld_pay, lds);
-        }
-        if (threadIdx.x != 0) return;
-        // price = shift + sum w d / sum w; sum (w (B - price))^2 = sum (w d)^2 - 2 e sum w^2 d + e^2 sum w^2, e = price - shift.
-        // One kept path: the estimate IS that path's price and the squares about it are zero identically
-        const double W = s[0], Q = s[1], kept = s[2];
-        const double e = s[3] / W;
-        const double var = (kept > 1.0) ? fma(e, fma(e, Q, -2.0 * s[5]), s[4]) : 0.0;
-        t.out[gi * K + col] = e + t.shift[col];
-        t.out[NG * K + gi * K + col] = sqrt(fmax(var, 0.0)) / W;
-        return;
-    }
-#pragma unroll
-    for (int q = 0; q < JS_NSTAT; ++q) {
-        if (q > 0) __syncthreads();
-        s[q] = block_column_sum(st + q, t.rows, ld_stat, lds);
-    }
-    if (threadIdx.x != 0) return;
-    const double w = s[0], Q = s[1], V2 = s[2], D0 = s[3], D1 = s[4], D2 = s[5], kept = s[6];
-    // row f17's statistics with W = c w: the normalizer and sum W carry c, every ratio of two weighted sums is free of it
-    const double c = t.sets[static_cast<size_t>(gi) * m + i].c;
-    const double W = c * w;
-    const double N = kept / W, sv = w - kept;
-    const double dev2 = (kept > 1.0) ? V2 - sv * sv / kept : 0.0;      // sum (w - mean w)^2
-    const double gd = D0 / w;
-    const double varg = (kept > 1.0) ? fma(gd, fma(gd, Q, -2.0 * D1), D2) : 0.0;
-    double *out = t.out + 2 * NG * K + (static_cast<size_t>(gi) * m + i) * SVMC_TILTED_STATS_DOUBLES;
-    out[0] = N;
-    out[1] = N * sqrt(fmax(dev2, 0.0)) / w;
-    out[2] = t.expiries[i].forward + gd;
-    out[3] = sqrt(fmax(varg, 0.0)) / w;
-    out[4] = (w / Q) * w;                                  // effective sample size (sum W)^2 / sum W^2
-    out[5] = kept;
-    out[6] = static_cast<double>(n) - kept;
-    out[7] = W;
-    if (gi == 0) t.out[NG * (2 * K + SVMC_TILTED_STATS_DOUBLES * m) + i] = t.fwd[4 * i + 3];       // corr, once per expiry
+    tc_finish_body<JsWeights>(t, n, lds);
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------
 static bool tcg_sizes_ok(size_t n_path, int n_expiries, int n_gammas)
 {
     return n_path >= 1 && n_expiries >= 1 && n_gammas >= 1 && n_gammas <= SVMC_TILTED_MAX_GAMMAS;
+}
+static bool js_sizes_ok(size_t n_path, int n_expiries, int n_sets)
+{
+    return n_path >= 1 && n_expiries >= 1 && n_sets >= 1 && n_sets <= SVMC_JUMP_SETS_MAX;
 }
 
 }  // namespace svmc
@@ -834,66 +645,42 @@ int svmc_tilted_cond_greeks_chain(const double *const *mu_snapshots_host, const 
     if (!mu_snapshots_host || !cv_snapshots_host || !forwards_host || !strikes_host || !types_host || !strike_offsets_host ||
         !gammas_host || !greeks_host || !stats_host || !workspace)
         return SVMC_ERR_INVALID_ARGUMENT;
-    if (!tcg_sizes_ok(n_path, n_expiries, n_gammas)) return SVMC_ERR_INVALID_ARGUMENT;
+    if (!tcg_sizes_ok(n_path, n_expiries, n_gammas) || !tc_all_finite(gammas_host, n_gammas)) return SVMC_ERR_INVALID_ARGUMENT;
     const int m = n_expiries, NG = n_gammas;
-    if (strike_offsets_host[0] != 0) return SVMC_ERR_INVALID_ARGUMENT;
-    for (int i = 0; i < m; ++i) {
-        if (strike_offsets_host[i + 1] < strike_offsets_host[i] || strike_offsets_host[i + 1] > (static_cast<size_t>(1) << 30))
-            return SVMC_ERR_INVALID_ARGUMENT;
-        if (!mu_snapshots_host[i] || !cv_snapshots_host[i]) return SVMC_ERR_INVALID_ARGUMENT;
-        if (!std::isfinite(forwards_host[i]) || !(forwards_host[i] > 0.0)) return SVMC_ERR_INVALID_ARGUMENT;
-    }
+    const int rc = tc_check_quotes(m, strike_offsets_host, mu_snapshots_host, cv_snapshots_host, forwards_host, strikes_host, nullptr,
+                                   types_host);
+    if (rc != SVMC_OK) return rc;
     const size_t K = strike_offsets_host[m];
-    for (int z = 0; z < NG; ++z)
-        if (!std::isfinite(gammas_host[z])) return SVMC_ERR_INVALID_ARGUMENT;
-    for (size_t k = 0; k < K; ++k)
-        if (!std::isfinite(strikes_host[k])) return SVMC_ERR_INVALID_ARGUMENT;
-    for (size_t k = 0; k < K; ++k)
-        if (types_host[k] != SVMC_CALL && types_host[k] != SVMC_PUT) return SVMC_ERR_UNKNOWN_PAYOFF;
     const int G = quote_groups(m, strike_offsets_host, TCG_KT, true);
-    if (G > TCG_MAX_GROUPS) return SVMC_ERR_INVALID_ARGUMENT;
+    if (G > TC_MAX_GROUPS) return SVMC_ERR_INVALID_ARGUMENT;
     TcgTable t;
     Layout w{static_cast<unsigned char *>(workspace)};
-    const size_t image_bytes = tcg_workspace(w, n_path, m, K, G, NG, t);
+    std::vector<unsigned char> image(tcg_workspace(w, n_path, m, K, G, NG, t));
     if (workspace_bytes < w.bytes()) return SVMC_ERR_WORKSPACE;
 
-    // the table's host image, then ONE upload
-    std::vector<unsigned char> image(image_bytes);
     Layout h{image.data()};
-    const TcgImage im = tcg_image(h, m, K, G, NG);
-    quote_image(
-        m, strike_offsets_host,
-        [&](int i, int k0, int k1) {
-            im.expiries[i] = TcExpiry{mu_snapshots_host[i], cv_snapshots_host[i], forwards_host[i], std::log(forwards_host[i]), k0, k1};
-        },
-        [&](int i, int k) {
-            const double sgn = (types_host[k] == SVMC_PUT) ? -1.0 : 1.0;
-            im.strikes[k] = strikes_host[k];
-            im.is_put[k] = (types_host[k] == SVMC_PUT) ? 1.0 : 0.0;
-            im.dshift[k] = (sgn * (forwards_host[i] - strikes_host[k]) > 0.0) ? sgn : 0.0;
-        });
-    quote_groups(m, strike_offsets_host, TCG_KT, true, im.groups);
-    for (int z = 0; z < NG; ++z) im.gammas[z] = gammas_host[z];
-#define SVMC_EST_TRY(call)                       \
-    do {                                         \
-        if ((call) != hipSuccess) return SVMC_ERR_HIP; \
-    } while (0)
-    SVMC_EST_TRY(hipMemcpyAsync(workspace, image.data(), image_bytes, hipMemcpyHostToDevice, stream));
-    hipLaunchKernelGGL(tilted_cond_greeks_forward_kernel, dim3(t.rows, m), dim3(BLOCK), 0, stream, t, n_path);
-    SVMC_EST_TRY(hipGetLastError());
-    hipLaunchKernelGGL(tilted_cond_greeks_forward_finish_kernel, dim3(m), dim3(BLOCK), 0, stream, t, recenter ? 1 : 0);
-    SVMC_EST_TRY(hipGetLastError());
-    hipLaunchKernelGGL(tilted_cond_greeks_kernel<TCG_KT>, dim3(t.rows, G, NG), dim3(BLOCK), 0, stream, t, n_path, recenter ? 1 : 0);
-    SVMC_EST_TRY(hipGetLastError());
-    hipLaunchKernelGGL(tilted_cond_greeks_finish_kernel, dim3(static_cast<unsigned>(K) + m, NG), dim3(BLOCK), 0, stream, t, n_path);
-    SVMC_EST_TRY(hipGetLastError());
-    // ONE download of the results' block, ONE synchronise
+    const TcImageOf<double> im = tc_image<double>(h, m, K, G, NG);
+    tc_fill_image(im, m, strike_offsets_host, TCG_KT, mu_snapshots_host, cv_snapshots_host, forwards_host, strikes_host, types_host,
+                  [&](int i, int k) {
+                      const double sgn = (types_host[k] == SVMC_PUT) ? -1.0 : 1.0;
+                      return (sgn * (forwards_host[i] - strikes_host[k]) > 0.0) ? sgn : 0.0;
+                  });
+    for (int z = 0; z < NG; ++z) im.zs[z] = gammas_host[z];
     std::vector<double> out(tcg_out_doubles(m, K, NG));
-    SVMC_EST_TRY(hipMemcpyAsync(out.data(), t.out, out.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
-    SVMC_EST_TRY(hipStreamSynchronize(stream));
-    const size_t GRK = static_cast<size_t>(NG) * SVMC_TCG_ROWS * K;
-    if (GRK > 0) memcpy(greeks_host, out.data(), GRK * sizeof(double));
-    memcpy(stats_host, out.data() + GRK, static_cast<size_t>(NG) * m * SVMC_TCG_STATS_DOUBLES * sizeof(double));
+    const int run = tc_run(workspace, image, t.out, out, stream, [&]() {
+        hipLaunchKernelGGL(tilted_cond_greeks_forward_kernel, dim3(t.rows, m), dim3(BLOCK), 0, stream, t, n_path);
+        SVMC_TC_TRY(hipGetLastError());
+        hipLaunchKernelGGL(tilted_cond_greeks_forward_finish_kernel, dim3(m), dim3(BLOCK), 0, stream, t, recenter ? 1 : 0);
+        SVMC_TC_TRY(hipGetLastError());
+        hipLaunchKernelGGL(tilted_cond_greeks_kernel<TCG_KT>, dim3(t.rows, G, NG), dim3(BLOCK), 0, stream, t, n_path, recenter ? 1 : 0);
+        SVMC_TC_TRY(hipGetLastError());
+        hipLaunchKernelGGL(tilted_cond_greeks_finish_kernel, dim3(static_cast<unsigned>(K) + m, NG), dim3(BLOCK), 0, stream, t, n_path);
+        SVMC_TC_TRY(hipGetLastError());
+        return SVMC_OK;
+    });
+    if (run != SVMC_OK) return run;
+    const double *block = tc_split(out.data(), greeks_host, static_cast<size_t>(NG) * SVMC_TCG_ROWS * K);
+    tc_split(block, stats_host, static_cast<size_t>(NG) * m * SVMC_TCG_STATS_DOUBLES);
     return SVMC_OK;
 }
 
@@ -917,28 +704,18 @@ int svmc_cond_density_chain(const double *const *mu_snapshots_host, const double
     if (!mu_snapshots_host || !cv_snapshots_host || !points_host || !point_offsets_host || !gammas_host || !pdf_host || !stderr_host ||
         !stats_host || !workspace)
         return SVMC_ERR_INVALID_ARGUMENT;
-    if (!tcg_sizes_ok(n_path, n_expiries, n_gammas)) return SVMC_ERR_INVALID_ARGUMENT;
+    if (!tcg_sizes_ok(n_path, n_expiries, n_gammas) || !tc_all_finite(gammas_host, n_gammas)) return SVMC_ERR_INVALID_ARGUMENT;
     const int m = n_expiries, NG = n_gammas;
-    if (point_offsets_host[0] != 0) return SVMC_ERR_INVALID_ARGUMENT;
-    for (int i = 0; i < m; ++i) {
-        if (point_offsets_host[i + 1] < point_offsets_host[i] || point_offsets_host[i + 1] > (static_cast<size_t>(1) << 30))
-            return SVMC_ERR_INVALID_ARGUMENT;
-        if (!mu_snapshots_host[i] || !cv_snapshots_host[i]) return SVMC_ERR_INVALID_ARGUMENT;
-    }
+    const int rc = tc_check_quotes(m, point_offsets_host, mu_snapshots_host, cv_snapshots_host, nullptr, points_host, nullptr, nullptr);
+    if (rc != SVMC_OK) return rc;
     const size_t P = point_offsets_host[m];
-    for (int z = 0; z < NG; ++z)
-        if (!std::isfinite(gammas_host[z])) return SVMC_ERR_INVALID_ARGUMENT;
-    for (size_t p = 0; p < P; ++p)
-        if (!std::isfinite(points_host[p])) return SVMC_ERR_INVALID_ARGUMENT;
     const int G = quote_groups(m, point_offsets_host, CD_XT, false);
-    if (G > TCG_MAX_GROUPS || m > TCG_MAX_GROUPS) return SVMC_ERR_INVALID_ARGUMENT;
+    if (G > TC_MAX_GROUPS || m > TC_MAX_GROUPS) return SVMC_ERR_INVALID_ARGUMENT;
     CdTable t;
     Layout w{static_cast<unsigned char *>(workspace)};
-    const size_t image_bytes = cd_workspace(w, n_path, m, P, G, NG, t);
+    std::vector<unsigned char> image(cd_workspace(w, n_path, m, P, G, NG, t));
     if (workspace_bytes < w.bytes()) return SVMC_ERR_WORKSPACE;
 
-    // the table's host image, then ONE upload
-    std::vector<unsigned char> image(image_bytes);
     Layout h{image.data()};
     const CdImage im = cd_image(h, m, P, G, NG);
     quote_image(
@@ -946,36 +723,32 @@ int svmc_cond_density_chain(const double *const *mu_snapshots_host, const double
         [&](int, int p) { im.points[p] = points_host[p]; });
     quote_groups(m, point_offsets_host, CD_XT, false, im.groups);
     for (int z = 0; z < NG; ++z) im.gammas[z] = gammas_host[z];
-    SVMC_EST_TRY(hipMemcpyAsync(workspace, image.data(), image_bytes, hipMemcpyHostToDevice, stream));
-    hipLaunchKernelGGL(cond_density_weight_kernel, dim3(t.rows, m, NG), dim3(BLOCK), 0, stream, t, n_path);
-    SVMC_EST_TRY(hipGetLastError());
-    if (G > 0) {
-        if (NG <= CD_GT)
-            hipLaunchKernelGGL((cond_density_kernel<CD_XT, CD_GT>), dim3(t.rows, G, 1), dim3(BLOCK), 0, stream, t, n_path);
-        else
-            hipLaunchKernelGGL((cond_density_kernel<CD_XT, CD_GT_WIDE>), dim3(t.rows, G, (NG + CD_GT_WIDE - 1) / CD_GT_WIDE), dim3(BLOCK), 0,
-                               stream, t, n_path);
-        SVMC_EST_TRY(hipGetLastError());
-    }
-    hipLaunchKernelGGL(cond_density_finish_kernel, dim3(static_cast<unsigned>(P) + m, NG), dim3(BLOCK), 0, stream, t, n_path);
-    SVMC_EST_TRY(hipGetLastError());
-    // ONE download of the results' block, ONE synchronise
     std::vector<double> out(cd_out_doubles(m, P, NG));
-    SVMC_EST_TRY(hipMemcpyAsync(out.data(), t.out, out.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
-    SVMC_EST_TRY(hipStreamSynchronize(stream));
-#undef SVMC_EST_TRY
+    const int run = tc_run(workspace, image, t.out, out, stream, [&]() {
+        hipLaunchKernelGGL(cond_density_weight_kernel, dim3(t.rows, m, NG), dim3(BLOCK), 0, stream, t, n_path);
+        SVMC_TC_TRY(hipGetLastError());
+        if (G > 0) {
+            if (NG <= CD_GT)
+                hipLaunchKernelGGL((cond_density_kernel<CD_XT, CD_GT>), dim3(t.rows, G, 1), dim3(BLOCK), 0, stream, t, n_path);
+            else
+                hipLaunchKernelGGL((cond_density_kernel<CD_XT, CD_GT_WIDE>), dim3(t.rows, G, (NG + CD_GT_WIDE - 1) / CD_GT_WIDE), dim3(BLOCK), 0,
+                                   stream, t, n_path);
+            SVMC_TC_TRY(hipGetLastError());
+        }
+        hipLaunchKernelGGL(cond_density_finish_kernel, dim3(static_cast<unsigned>(P) + m, NG), dim3(BLOCK), 0, stream, t, n_path);
+        SVMC_TC_TRY(hipGetLastError());
+        return SVMC_OK;
+    });
+    if (run != SVMC_OK) return run;
     const size_t GP = static_cast<size_t>(NG) * P;
-    if (GP > 0) {
-        memcpy(pdf_host, out.data(), GP * sizeof(double));
-        memcpy(stderr_host, out.data() + GP, GP * sizeof(double));
-    }
-    memcpy(stats_host, out.data() + 2 * GP, static_cast<size_t>(NG) * m * SVMC_CD_STATS_DOUBLES * sizeof(double));
+    const double *block = tc_split(tc_split(out.data(), pdf_host, GP), stderr_host, GP);
+    tc_split(block, stats_host, static_cast<size_t>(NG) * m * SVMC_CD_STATS_DOUBLES);
     return SVMC_OK;
 }
 
 int svmc_jump_sets_workspace_bytes(size_t n_path, int n_expiries, size_t total_strikes, int n_sets, size_t *bytes)
 {
-    if (bytes == nullptr || n_path < 1 || n_expiries < 1 || n_sets < 1 || n_sets > SVMC_JUMP_SETS_MAX) return SVMC_ERR_INVALID_ARGUMENT;
+    if (bytes == nullptr || !js_sizes_ok(n_path, n_expiries, n_sets)) return SVMC_ERR_INVALID_ARGUMENT;
     JsTable t;
     Layout w{nullptr};
     js_workspace(w, n_path, n_expiries, total_strikes, quote_groups_bound(n_expiries, total_strikes, JS_KT), n_sets, t);
@@ -994,82 +767,48 @@ int svmc_jump_sets_payoff_chain(const double *const *a_snapshots_host, size_t n_
     if (!a_snapshots_host || !forwards_host || !strikes_host || !types_host || !shifts_host || !strike_offsets_host || !variances_host ||
         !gammas_host || !prices_host || !stderrs_host || !stats_host || !corr_host || !workspace)
         return SVMC_ERR_INVALID_ARGUMENT;
-    if (n_path < 1 || n_expiries < 1 || n_sets < 1 || n_sets > SVMC_JUMP_SETS_MAX) return SVMC_ERR_INVALID_ARGUMENT;
+    if (!js_sizes_ok(n_path, n_expiries, n_sets) || !tc_all_finite(gammas_host, n_sets)) return SVMC_ERR_INVALID_ARGUMENT;
     const int m = n_expiries, Q = n_sets;
-    if (strike_offsets_host[0] != 0) return SVMC_ERR_INVALID_ARGUMENT;
-    for (int i = 0; i < m; ++i) {
-        if (strike_offsets_host[i + 1] < strike_offsets_host[i] || strike_offsets_host[i + 1] > (static_cast<size_t>(1) << 30))
-            return SVMC_ERR_INVALID_ARGUMENT;
-        if (!a_snapshots_host[i]) return SVMC_ERR_INVALID_ARGUMENT;
-        if (!std::isfinite(forwards_host[i]) || !(forwards_host[i] > 0.0)) return SVMC_ERR_INVALID_ARGUMENT;
-    }
+    for (int j = 0; j < Q * m; ++j)
+        if (!std::isfinite(variances_host[j]) || !(variances_host[j] >= 0.0)) return SVMC_ERR_INVALID_ARGUMENT;
+    const int rc = tc_check_quotes(m, strike_offsets_host, a_snapshots_host, nullptr, forwards_host, strikes_host, shifts_host, types_host);
+    if (rc != SVMC_OK) return rc;
     const size_t K = strike_offsets_host[m];
-    for (int q = 0; q < Q; ++q) {
-        if (!std::isfinite(gammas_host[q])) return SVMC_ERR_INVALID_ARGUMENT;
-        for (int i = 0; i < m; ++i) {
-            const double v = variances_host[static_cast<size_t>(q) * m + i];
-            if (!std::isfinite(v) || !(v >= 0.0)) return SVMC_ERR_INVALID_ARGUMENT;
-        }
-    }
-    for (size_t k = 0; k < K; ++k)
-        if (!std::isfinite(strikes_host[k]) || !std::isfinite(shifts_host[k])) return SVMC_ERR_INVALID_ARGUMENT;
-    for (size_t k = 0; k < K; ++k)
-        if (types_host[k] != SVMC_CALL && types_host[k] != SVMC_PUT) return SVMC_ERR_UNKNOWN_PAYOFF;
     const int G = quote_groups(m, strike_offsets_host, JS_KT, true);
-    if (G > TCG_MAX_GROUPS) return SVMC_ERR_INVALID_ARGUMENT;
+    if (G > TC_MAX_GROUPS) return SVMC_ERR_INVALID_ARGUMENT;
     JsTable t;
     Layout w{static_cast<unsigned char *>(workspace)};
-    const size_t image_bytes = js_workspace(w, n_path, m, K, G, Q, t);
+    std::vector<unsigned char> image(js_workspace(w, n_path, m, K, G, Q, t));
     if (workspace_bytes < w.bytes()) return SVMC_ERR_WORKSPACE;
 
-    // the table's host image, then ONE upload
-    std::vector<unsigned char> image(image_bytes);
     Layout h{image.data()};
-    const JsImage im = js_image(h, m, K, G, Q);
-    quote_image(
-        m, strike_offsets_host,
-        [&](int i, int k0, int k1) {
-            im.expiries[i] = TcExpiry{a_snapshots_host[i], nullptr, forwards_host[i], std::log(forwards_host[i]), k0, k1};
-        },
-        [&](int, int k) {
-            im.strikes[k] = strikes_host[k];
-            im.is_put[k] = (types_host[k] == SVMC_PUT) ? 1.0 : 0.0;
-            im.shift[k] = shifts_host[k];
-        });
-    quote_groups(m, strike_offsets_host, JS_KT, true, im.groups);
+    const TcImageOf<JsSet> im = tc_image<JsSet>(h, m, K, G, static_cast<size_t>(Q) * m);
+    tc_fill_image(im, m, strike_offsets_host, JS_KT, a_snapshots_host, nullptr, forwards_host, strikes_host, types_host,
+                  [&](int, int k) { return shifts_host[k]; });
     for (int q = 0; q < Q; ++q)
         for (int i = 0; i < m; ++i) {
             // the constants of a (set, expiry), each rounded once, from the set's own numbers alone
             const double g = gammas_host[q], v = variances_host[static_cast<size_t>(q) * m + i], gv = g * v, sd = std::sqrt(v);
-            im.sets[static_cast<size_t>(q) * m + i] = JsSet{g,  std::exp(0.5 * ((g * (g - 1.0)) * v)), v, sd, 1.0 / sd,
-                                                            forwards_host[i] * std::exp(gv), std::log(forwards_host[i]) + gv, gv};
+            im.zs[static_cast<size_t>(q) * m + i] = JsSet{g,  std::exp(0.5 * ((g * (g - 1.0)) * v)), v, sd, 1.0 / sd,
+                                                          forwards_host[i] * std::exp(gv), std::log(forwards_host[i]) + gv, gv};
         }
-#define SVMC_EST_TRY(call)                       \
-    do {                                         \
-        if ((call) != hipSuccess) return SVMC_ERR_HIP; \
-    } while (0)
-    SVMC_EST_TRY(hipMemcpyAsync(workspace, image.data(), image_bytes, hipMemcpyHostToDevice, stream));
-    hipLaunchKernelGGL(jump_sets_forward_kernel, dim3(t.rows, m), dim3(BLOCK), 0, stream, t, n_path);
-    SVMC_EST_TRY(hipGetLastError());
-    hipLaunchKernelGGL(jump_sets_forward_finish_kernel, dim3(m), dim3(BLOCK), 0, stream, t, recenter ? 1 : 0);
-    SVMC_EST_TRY(hipGetLastError());
-    hipLaunchKernelGGL((jump_sets_payoff_kernel<JS_KT, JS_ST>), dim3(t.rows, G, (Q + JS_ST - 1) / JS_ST), dim3(BLOCK), 0, stream, t,
-                       n_path);
-    SVMC_EST_TRY(hipGetLastError());
-    hipLaunchKernelGGL(jump_sets_finish_kernel, dim3(static_cast<unsigned>(K) + m, Q), dim3(BLOCK), 0, stream, t, n_path);
-    SVMC_EST_TRY(hipGetLastError());
-    // ONE download of the results' block, ONE synchronise
     std::vector<double> out(js_out_doubles(m, K, Q));
-    SVMC_EST_TRY(hipMemcpyAsync(out.data(), t.out, out.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
-    SVMC_EST_TRY(hipStreamSynchronize(stream));
-#undef SVMC_EST_TRY
-    const size_t QK = static_cast<size_t>(Q) * K, QS = static_cast<size_t>(Q) * m * SVMC_TILTED_STATS_DOUBLES;
-    if (QK > 0) {
-        memcpy(prices_host, out.data(), QK * sizeof(double));
-        memcpy(stderrs_host, out.data() + QK, QK * sizeof(double));
-    }
-    memcpy(stats_host, out.data() + 2 * QK, QS * sizeof(double));
-    memcpy(corr_host, out.data() + 2 * QK + QS, static_cast<size_t>(m) * sizeof(double));
+    const int run = tc_run(workspace, image, t.out, out, stream, [&]() {
+        hipLaunchKernelGGL(jump_sets_forward_kernel, dim3(t.rows, m), dim3(BLOCK), 0, stream, t, n_path);
+        SVMC_TC_TRY(hipGetLastError());
+        hipLaunchKernelGGL(jump_sets_forward_finish_kernel, dim3(m), dim3(BLOCK), 0, stream, t, recenter ? 1 : 0);
+        SVMC_TC_TRY(hipGetLastError());
+        hipLaunchKernelGGL(jump_sets_payoff_kernel<JS_KT>, dim3(t.rows, G, Q), dim3(BLOCK), 0, stream, t, n_path);
+        SVMC_TC_TRY(hipGetLastError());
+        hipLaunchKernelGGL(jump_sets_finish_kernel, dim3(static_cast<unsigned>(K) + m, Q), dim3(BLOCK), 0, stream, t, n_path);
+        SVMC_TC_TRY(hipGetLastError());
+        return SVMC_OK;
+    });
+    if (run != SVMC_OK) return run;
+    const size_t QK = static_cast<size_t>(Q) * K;
+    const double *block = tc_split(tc_split(out.data(), prices_host, QK), stderrs_host, QK);
+    block = tc_split(block, stats_host, static_cast<size_t>(Q) * m * SVMC_TILTED_STATS_DOUBLES);
+    tc_split(block, corr_host, m);
     return SVMC_OK;
 }
 

@@ -490,6 +490,18 @@ def tilted_chain_arrays(forwards, strikes: Sequence[np.ndarray], codes: Sequence
     return out
 
 
+def strike_shifts(ch: dict, shifts=None) -> np.ndarray:
+    """the host constant of every strike's sums of a tilted_chain_arrays chain, flat [K] (one zero for a chain without strikes);
+    default: the intrinsic value at the forward (payoff_shifts)"""
+    K = ch["total"]
+    if shifts is None:
+        shifts = [payoff_shifts(k, c, float(f), LOG_RETURN) for k, c, f in zip(ch["strikes_ttms"], ch["codes_ttms"], ch["forwards"])]
+    sh = np.ascontiguousarray(np.concatenate([np.asarray(s, dtype=np.float64).ravel() for s in shifts])) if K else np.zeros(1)
+    if K and sh.size != K:
+        raise ValueError("one shift per strike")
+    return sh
+
+
 def tilted_results(prices: np.ndarray, stderrs: np.ndarray, stats: np.ndarray, ch: dict):
     """flat [G][K] prices / errors and [G][m][8] statistics -> ([G][m] arrays in the strikes' shapes, the same, stats [G, m, 8])"""
     G, K, offs = ch["gammas"].size, ch["total"], ch["offs"]
@@ -1201,6 +1213,22 @@ class HipEngine:
             dt.ctypes.data_as(C.POINTER(C.c_double)), float(theta), float(kappa), float(rho), float(volvol), int(seed), int(call_id),
             self.path_offset, int(step_offset), *rows, self.stream)))
 
+    def _cond_row_ptrs(self, m: int, mu_rows, cv_rows):
+        """the device pointers of the (mu, cv) rows of m expiries: snapshot rows mu_rows[i] and cv_rows[i], or, with both None, the
+        current state (x, cv) for the one expiry"""
+        if (mu_rows is None) != (cv_rows is None) or ((m != 1) if mu_rows is None else (len(mu_rows) != m or len(cv_rows) != m)):
+            raise ValueError("one mu row and one cv row per expiry (the current state serves one expiry)")
+        mus = [self.x.ptr] if mu_rows is None else [self.snapshot_ptr(r) for r in mu_rows]
+        cvs = [self.cv.ptr] if cv_rows is None else [self.snapshot_ptr(r) for r in cv_rows]
+        return mus, cvs
+
+    def _side_workspace(self, size_fn, what: str, m: int, n_quotes: int, n_z: int, tag: str):
+        """(device pointer, bytes) of the workspace a tail of libsvmc_ext.so / libsvmc_est.so asks for, in this engine's `tag` buffer"""
+        nbytes = C.c_size_t(0)
+        _lib.check_ext(size_fn(self.n_path, m, n_quotes, n_z, C.byref(nbytes)), what)
+        ws_ptr, _ = self.alloc_sums((nbytes.value + 7) // 8, tag)
+        return ws_ptr, nbytes.value
+
     def conditional_payoffs(self, forwards, discfactors, strikes: Sequence[np.ndarray], codes: Sequence[np.ndarray],
                             recenter: bool = True, mu_rows: Optional[Sequence[int]] = None,
                             cv_rows: Optional[Sequence[int]] = None):
@@ -1209,10 +1237,7 @@ class HipEngine:
         strike.  Returns (prices [m] -> [K_i], stderrs the same, stats [m] dicts of CMC_STATS_FIELDS)."""
         ch = marshalled_chain(np.zeros(len(strikes)), forwards, discfactors, strikes, codes)
         m, K = ch["m"], ch["total"]
-        if (mu_rows is None) != (cv_rows is None) or ((m != 1) if mu_rows is None else (len(mu_rows) != m or len(cv_rows) != m)):
-            raise ValueError("one mu row and one cv row per expiry (the current state serves one expiry)")
-        mus = [self.x.ptr] if mu_rows is None else [self.snapshot_ptr(r) for r in mu_rows]
-        cvs = [self.cv.ptr] if cv_rows is None else [self.snapshot_ptr(r) for r in cv_rows]
+        mus, cvs = self._cond_row_ptrs(m, mu_rows, cv_rows)
         nbytes = C.c_size_t(0)
         _lib.check(self.lib.svmc_cmc_payoff_workspace_bytes(self.n_path, m, K, C.byref(nbytes)))
         ws_ptr, _ = self.alloc_sums((nbytes.value + 7) // 8, "cmc_workspace")
@@ -1236,27 +1261,18 @@ class HipEngine:
         tilted_payoffs: (prices [G][m] -> [K_i], stderrs the same, stats [G, m, TILTED_COND_STATS_FIELDS]); prices are undiscounted."""
         ch = tilted_chain_arrays(forwards, strikes, codes, gammas)
         m, K, G = ch["m"], ch["total"], ch["gammas"].size
-        if (mu_rows is None) != (cv_rows is None) or ((m != 1) if mu_rows is None else (len(mu_rows) != m or len(cv_rows) != m)):
-            raise ValueError("one mu row and one cv row per expiry (the current state serves one expiry)")
-        mus = [self.x.ptr] if mu_rows is None else [self.snapshot_ptr(r) for r in mu_rows]
-        cvs = [self.cv.ptr] if cv_rows is None else [self.snapshot_ptr(r) for r in cv_rows]
-        if shifts is None:
-            shifts = [payoff_shifts(k, c, float(f), LOG_RETURN) for k, c, f in zip(ch["strikes_ttms"], ch["codes_ttms"], ch["forwards"])]
-        sh = np.ascontiguousarray(np.concatenate([np.asarray(s, dtype=np.float64).ravel() for s in shifts])) if K else np.zeros(1)
-        if K and sh.size != K:
-            raise ValueError("one shift per strike")
+        mus, cvs = self._cond_row_ptrs(m, mu_rows, cv_rows)
+        sh = strike_shifts(ch, shifts)
         ext = _lib.load_ext()
         what = "svmc_tilted_cond_payoff_chain"
-        nbytes = C.c_size_t(0)
-        _lib.check_ext(ext.svmc_tilted_cond_workspace_bytes(self.n_path, m, K, G, C.byref(nbytes)), what)
-        ws_ptr, _ = self.alloc_sums((nbytes.value + 7) // 8, "tilted_cond_workspace")
+        ws_ptr, nbytes = self._side_workspace(ext.svmc_tilted_cond_workspace_bytes, what, m, K, G, "tilted_cond_workspace")
         prices, stderrs, stats = np.empty(max(G * K, 1)), np.empty(max(G * K, 1)), np.empty(G * m * TILTED_STATS_DOUBLES)
         dp = C.POINTER(C.c_double)
         self._timed("tilted_cond_payoff_kernel", lambda: _lib.check_ext(ext.svmc_tilted_cond_payoff_chain(
             (C.c_void_p * m)(*mus), (C.c_void_p * m)(*cvs), self.n_path, ch["forwards"].ctypes.data_as(dp), m,
             ch["strikes"].ctypes.data_as(dp), ch["codes"].ctypes.data_as(C.POINTER(C.c_int8)), sh.ctypes.data_as(dp),
             ch["offs"].ctypes.data_as(C.POINTER(C.c_size_t)), ch["gammas"].ctypes.data_as(dp), G, int(bool(recenter)),
-            prices.ctypes.data_as(dp), stderrs.ctypes.data_as(dp), stats.ctypes.data_as(dp), ws_ptr, nbytes.value, self.stream), what))
+            prices.ctypes.data_as(dp), stderrs.ctypes.data_as(dp), stats.ctypes.data_as(dp), ws_ptr, nbytes, self.stream), what))
         return tilted_results(prices[:G * K], stderrs[:G * K], stats, ch)
 
     def tilted_conditional_greeks(self, forwards, strikes: Sequence[np.ndarray], codes: Sequence[np.ndarray], gammas,
@@ -1269,22 +1285,17 @@ class HipEngine:
         tail's: call tilted_conditional_payoffs on the same rows."""
         ch = tilted_chain_arrays(forwards, strikes, codes, gammas)
         m, K, G = ch["m"], ch["total"], ch["gammas"].size
-        if (mu_rows is None) != (cv_rows is None) or ((m != 1) if mu_rows is None else (len(mu_rows) != m or len(cv_rows) != m)):
-            raise ValueError("one mu row and one cv row per expiry (the current state serves one expiry)")
-        mus = [self.x.ptr] if mu_rows is None else [self.snapshot_ptr(r) for r in mu_rows]
-        cvs = [self.cv.ptr] if cv_rows is None else [self.snapshot_ptr(r) for r in cv_rows]
+        mus, cvs = self._cond_row_ptrs(m, mu_rows, cv_rows)
         est = _lib.load_est()
         what = "svmc_tilted_cond_greeks_chain"
-        nbytes = C.c_size_t(0)
-        _lib.check_ext(est.svmc_tilted_cond_greeks_workspace_bytes(self.n_path, m, K, G, C.byref(nbytes)), what)
-        ws_ptr, _ = self.alloc_sums((nbytes.value + 7) // 8, "tilted_cond_greeks_workspace")
+        ws_ptr, nbytes = self._side_workspace(est.svmc_tilted_cond_greeks_workspace_bytes, what, m, K, G, "tilted_cond_greeks_workspace")
         greeks, stats = np.empty(max(G * TCG_ROWS * K, 1)), np.empty(G * m * TCG_STATS_DOUBLES)
         dp = C.POINTER(C.c_double)
         self._timed("tilted_cond_greeks_kernel", lambda: _lib.check_ext(est.svmc_tilted_cond_greeks_chain(
             (C.c_void_p * m)(*mus), (C.c_void_p * m)(*cvs), self.n_path, ch["forwards"].ctypes.data_as(dp), m,
             ch["strikes"].ctypes.data_as(dp), ch["codes"].ctypes.data_as(C.POINTER(C.c_int8)),
             ch["offs"].ctypes.data_as(C.POINTER(C.c_size_t)), ch["gammas"].ctypes.data_as(dp), G, int(bool(recenter)),
-            greeks.ctypes.data_as(dp), stats.ctypes.data_as(dp), ws_ptr, nbytes.value, self.stream), what))
+            greeks.ctypes.data_as(dp), stats.ctypes.data_as(dp), ws_ptr, nbytes, self.stream), what))
         return tilted_greeks_results(greeks, stats, ch)
 
     def conditional_densities(self, x_grids: Sequence[np.ndarray], gammas=(0.0,), mu_rows: Optional[Sequence[int]] = None,
@@ -1296,21 +1307,16 @@ class HipEngine:
         n_weight_dropped > 0 has NaN for its pdf and its error."""
         ch = cond_density_arrays(x_grids, gammas)
         m, P, G = ch["m"], ch["total"], ch["gammas"].size
-        if (mu_rows is None) != (cv_rows is None) or ((m != 1) if mu_rows is None else (len(mu_rows) != m or len(cv_rows) != m)):
-            raise ValueError("one mu row and one cv row per expiry (the current state serves one expiry)")
-        mus = [self.x.ptr] if mu_rows is None else [self.snapshot_ptr(r) for r in mu_rows]
-        cvs = [self.cv.ptr] if cv_rows is None else [self.snapshot_ptr(r) for r in cv_rows]
+        mus, cvs = self._cond_row_ptrs(m, mu_rows, cv_rows)
         est = _lib.load_est()
         what = "svmc_cond_density_chain"
-        nbytes = C.c_size_t(0)
-        _lib.check_ext(est.svmc_cond_density_workspace_bytes(self.n_path, m, P, G, C.byref(nbytes)), what)
-        ws_ptr, _ = self.alloc_sums((nbytes.value + 7) // 8, "cond_density_workspace")
+        ws_ptr, nbytes = self._side_workspace(est.svmc_cond_density_workspace_bytes, what, m, P, G, "cond_density_workspace")
         pdf, err, stats = np.empty(max(G * P, 1)), np.empty(max(G * P, 1)), np.empty(G * m * CD_STATS_DOUBLES)
         dp = C.POINTER(C.c_double)
         self._timed("cond_density_kernel", lambda: _lib.check_ext(est.svmc_cond_density_chain(
             (C.c_void_p * m)(*mus), (C.c_void_p * m)(*cvs), self.n_path, m, ch["points"].ctypes.data_as(dp),
             ch["offs"].ctypes.data_as(C.POINTER(C.c_size_t)), ch["gammas"].ctypes.data_as(dp), G, pdf.ctypes.data_as(dp),
-            err.ctypes.data_as(dp), stats.ctypes.data_as(dp), ws_ptr, nbytes.value, self.stream), what))
+            err.ctypes.data_as(dp), stats.ctypes.data_as(dp), ws_ptr, nbytes, self.stream), what))
         offs = ch["offs"]
         cut = lambda a: [[a[g * P + int(offs[i]):g * P + int(offs[i + 1])].reshape(ch["shapes"][i]).copy()    # noqa: E731
                           for i in range(m)] for g in range(G)]
@@ -1371,16 +1377,10 @@ class HipEngine:
             ptrs = [self.x.ptr]
         if len(ptrs) != m:
             raise ValueError("one row of a per expiry (the current state serves one expiry)")
-        if shifts is None:
-            shifts = [payoff_shifts(k, c, float(f), LOG_RETURN) for k, c, f in zip(ch["strikes_ttms"], ch["codes_ttms"], ch["forwards"])]
-        sh = np.ascontiguousarray(np.concatenate([np.asarray(s, dtype=np.float64).ravel() for s in shifts])) if K else np.zeros(1)
-        if K and sh.size != K:
-            raise ValueError("one shift per strike")
+        sh = strike_shifts(ch, shifts)
         est = _lib.load_est()
         what = "svmc_jump_sets_payoff_chain"
-        nbytes = C.c_size_t(0)
-        _lib.check_ext(est.svmc_jump_sets_workspace_bytes(self.n_path, m, K, Q, C.byref(nbytes)), what)
-        ws_ptr, _ = self.alloc_sums((nbytes.value + 7) // 8, "jump_sets_workspace")
+        ws_ptr, nbytes = self._side_workspace(est.svmc_jump_sets_workspace_bytes, what, m, K, Q, "jump_sets_workspace")
         prices, stderrs = np.empty(max(Q * K, 1)), np.empty(max(Q * K, 1))
         stats, corr = np.empty(Q * m * TILTED_STATS_DOUBLES), np.empty(m)
         dp = C.POINTER(C.c_double)
@@ -1388,7 +1388,7 @@ class HipEngine:
             (C.c_void_p * m)(*ptrs), self.n_path, ch["forwards"].ctypes.data_as(dp), m, ch["strikes"].ctypes.data_as(dp),
             ch["codes"].ctypes.data_as(C.POINTER(C.c_int8)), sh.ctypes.data_as(dp), ch["offs"].ctypes.data_as(C.POINTER(C.c_size_t)),
             var.ctypes.data_as(dp), ch["gammas"].ctypes.data_as(dp), Q, int(bool(recenter)), prices.ctypes.data_as(dp),
-            stderrs.ctypes.data_as(dp), stats.ctypes.data_as(dp), corr.ctypes.data_as(dp), ws_ptr, nbytes.value, self.stream), what))
+            stderrs.ctypes.data_as(dp), stats.ctypes.data_as(dp), corr.ctypes.data_as(dp), ws_ptr, nbytes, self.stream), what))
         return tilted_results(prices[:Q * K], stderrs[:Q * K], stats, ch) + (corr,)
 
     def price_hawkesjd_chain_tilted_cond(self, ch: dict, params: np.ndarray, nb_steps_per_year: int, seed: int, call_id: int, gammas,
@@ -1456,10 +1456,7 @@ class HipEngine:
         [K_i]}, stats [m] dicts of CMC_GREEKS_STATS_FIELDS)."""
         ch = marshalled_chain(np.zeros(len(strikes)), forwards, discfactors, strikes, codes)
         m, K = ch["m"], ch["total"]
-        if (mu_rows is None) != (cv_rows is None) or ((m != 1) if mu_rows is None else (len(mu_rows) != m or len(cv_rows) != m)):
-            raise ValueError("one mu row and one cv row per expiry (the current state serves one expiry)")
-        mus = [self.x.ptr] if mu_rows is None else [self.snapshot_ptr(r) for r in mu_rows]
-        cvs = [self.cv.ptr] if cv_rows is None else [self.snapshot_ptr(r) for r in cv_rows]
+        mus, cvs = self._cond_row_ptrs(m, mu_rows, cv_rows)
         nbytes = C.c_size_t(0)
         _lib.check(self.lib.svmc_cmc_greeks_workspace_bytes(self.n_path, m, K, C.byref(nbytes)))
         ws_ptr, _ = self.alloc_sums((nbytes.value + 7) // 8, "cmc_greeks_workspace")

@@ -17,10 +17,11 @@ object to --out (default profiles/hawkes_jump_sets_bench.json) and prints it:
                                  tests/golden/hawkes_risk_premia.npz (4 expiries, its mid vols) from (0.45, -1) in the two modes
                                  (estimator="fourier" | "conditional" at 10^5 paths): seconds, evaluations, the fitted (sigma, gamma),
                                  the final objective -- reported, not asserted
-  layouts[KT,ST][n][Q]           the tail alone (engine.jump_sets_payoffs on resident rows) with SVMC_JS_KT strikes per group and
-                                 SVMC_JS_ST sets per block tile, each build loaded by a process of its own through SVMC_EST_LIB, with the
-                                 payoff kernel's metadata (VGPRs; waves per SIMD = 512 // VGPRs, at most 8).  --layout-lib KT,ST=FILE
-                                 takes a prebuilt library; without any, the pairs of LAYOUTS are compiled into a temporary directory.
+  layouts[KT,ST][n][Q]           the tail alone (engine.jump_sets_payoffs on resident rows) with SVMC_JS_KT strikes per group, a block
+                                 per set (ST = 1), each build loaded by a process of its own through SVMC_EST_LIB, with the payoff
+                                 kernel's metadata (VGPRs; waves per SIMD = 512 // VGPRs, at most 8).  --layout-lib KT,ST=FILE takes a
+                                 prebuilt library -- of any build: the committed file's ST > 1 rows were measured with a tile of sets
+                                 per block that is not kept; without any, the widths of LAYOUTS are compiled into a temporary directory.
 
     python tools/bench_hawkes_jump_sets.py [--reps 10] [--layout-lib 8,1=FILE ...] [--no-layouts] [--no-calibration] [--out FILE]
 """
@@ -38,7 +39,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 SIZES = (100000, 1 << 20)
 SET_COUNTS = (1, 3, 16)
-LAYOUTS = ((8, 1), (4, 1), (4, 2), (8, 2), (4, 4), (2, 4), (2, 8))
+LAYOUTS = (8, 4, 2)                                        # SVMC_JS_KT
 
 
 def chain_and_params():
@@ -95,10 +96,10 @@ def layout_comparison(libs, reps):
     out = {}
     with tempfile.TemporaryDirectory(prefix="svmc_js_layouts_") as tmp:
         if not libs:
-            for kt, st in LAYOUTS:
-                lib = os.path.join(tmp, f"libsvmc_est_k{kt}_s{st}.so")
-                svbuild.build_side(lib, lib + ".isa.json", svbuild.EST_SRC, False, extra=(f"-DSVMC_JS_KT={kt}", f"-DSVMC_JS_ST={st}"))
-                libs.append((f"{kt},{st}", lib))
+            for kt in LAYOUTS:
+                lib = os.path.join(tmp, f"libsvmc_est_k{kt}.so")
+                svbuild.build_side(lib, lib + ".isa.json", svbuild.EST_SRC, False, extra=(f"-DSVMC_JS_KT={kt}",))
+                libs.append((f"{kt},1", lib))
         for label, lib in libs:
             res = subprocess.run([sys.executable, os.path.abspath(__file__), "--tail-only", "--reps", str(reps)],
                                  env=dict(os.environ, SVMC_EST_LIB=os.path.abspath(lib)), capture_output=True, text=True, timeout=300)
