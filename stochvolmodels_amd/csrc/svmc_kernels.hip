@@ -94,11 +94,16 @@ struct LogsvSliceSums {
 __device__ __forceinline__ LogsvSliceSums logsv_slice_full(const LogsvFast c, double &s, const PhiloxLane &lane, uint32_t step0, int t0,
                                                            int nb, const RngTables &tab, const double *exp_table, LogsvProgress &prog)
 {
-    const auto exp_of = [&](double v) { return exp2u_tab(v, exp_table); };  // L is carried in units of ln2/256
+    // the tail's leading coefficient stays in one register pair for the whole loop: left to the compiler, the second step of a trip
+    // overwrites it and every trip pays a v_mov_b64 to bring it back
+    double k0 = EXP2U_TAIL_K0;
+    asm volatile("" : "+v"(k0));
+    const auto exp_of = [&](double v) { return exp2u_tab(v, exp_table, k0); };  // L is carried in units of ln2/256
     double L = log_state(s) * LOG_UNITS_PER_NAT;                                                      // :1039
     double s2 = square_rn(s), acc = 0.0, xacc = 0.0;
     const double s2_start = s2;
-    rng_time_loop(
+    // one pair ahead, keys un-hoisted: the draw's reads land under the wave's own step (svmc_rng.h), the same bits as rng_time_loop
+    rng_time_loop_pair_ahead<false>(
         lane, step0, nb, tab, [&](double z0, double z1) { logsv_step_acc(c, xacc, L, s, s2, acc, z0, z1, exp_of); },
         [&](int t) {
             if (t0 + t >= prog.next_stage_t) {             // wave-uniform
@@ -117,7 +122,7 @@ __global__ __launch_bounds__(RNG_BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8)
 {
     __shared__ RngTablesLds s_tab;
     __shared__ double s_exp[256];
-    const RngTables tab = stage_tables(s_tab, s_exp);
+    const RngTables tab = stage_tables<RNG_BLOCK>(s_tab, s_exp);
     clock_probe_stamp(probe, 0);
     const size_t p = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
     const bool active = p < n;
@@ -293,7 +298,7 @@ __device__ __forceinline__ void logsv_chain_full_body(size_t n, const Source &sr
     __shared__ RngTablesLds s_tab;
     __shared__ double s_exp[256];
     __shared__ double s_park[2 * CHAIN_BLOCK];             // [0, B): x, [B, 2B): qvar -- lane t owns elements t and B + t
-    const RngTables tab = stage_tables(s_tab, s_exp);
+    const RngTables tab = stage_tables<CHAIN_BLOCK>(s_tab, s_exp);
     clock_probe_stamp(probe, 0);
     // the path index is re-derived from threadIdx.x wherever it is needed (opaque to CSE): one VGPR across the time loop
     // instead of the 64-bit index and the addresses formed from it

@@ -250,6 +250,17 @@ SVMC_HD double exp2u_tail(double r)
     return q * r;
 }
 
+// exp2u_tail with its leading coefficient handed in: the caller holds it in a vector register pair across its time loop (made
+// opaque there), so no trip re-materialises it -- fma_k takes it as a vector operand either way.  The same bits.
+SVMC_HD double exp2u_tail(double r, double k0)
+{
+    double q = fma_k(k0, r, 0x1.c6b0903967234p-29);
+    q = fma_k(q, r, 0x1.ebfbdff82c584p-19);
+    q = fma_k(q, r, 0x1.62e42fefa39d8p-9);
+    return q * r;
+}
+constexpr double EXP2U_TAIL_K0 = 0x1.3b2ab8452c312p-39;
+
 // exp2u_tail with its four coefficients in VECTOR registers the caller keeps across its time loop (the few-waves generators:
 // registers to spare, and every instruction of a lone wave is an issue slot): plain v_fma_f64 on the same operands -- the same
 // bits as exp2u_tail -- but no inline assembly in the loop, so the scheduler may interleave the chain with the draw's integer
@@ -285,6 +296,15 @@ SVMC_HD double exp2u_tab(double y, const double *tab)
     exp2u_reduce(y, ni, r);
     const double t = tab[ni & 255];
     return exp2u_scale(t, exp2u_tail(r), ni);
+}
+
+SVMC_HD double exp2u_tab(double y, const double *tab, double k0)
+{
+    int ni;
+    double r;
+    exp2u_reduce(y, ni, r);
+    const double t = tab[ni & 255];
+    return exp2u_scale(t, exp2u_tail(r, k0), ni);
 }
 
 // -ln(u) for any positive normal u (the RNG calls it on (0,1); Heston QE on arguments around 1).  u = m 2^k with m in [sqrt(1/2), sqrt(2)) taken from the exponent field,

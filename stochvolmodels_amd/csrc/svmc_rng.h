@@ -123,6 +123,39 @@ __device__ __forceinline__ RngTables stage_tables(RngTablesLds &lds, double (&ld
     return RngTables{lds.icdf, nullptr};
 }
 
+// stage_tables for a kernel whose block size TB is a compile-time constant (the launch must use it): a thread's loads of both
+// tables are all issued before its first LDS store, so a block pays ONE global round trip before the barrier, not one per
+// piece (the loop above compiles to load, s_waitcnt vmcnt(0), ds_write per trip: five dependent trips at 512 threads)
+template <unsigned TB>
+__device__ __forceinline__ RngTables stage_tables(RngTablesLds &lds, double (&lds_exp)[256])
+{
+    constexpr unsigned N = ICDF_PIECES * SVMC_ICDF_SEGMENTS, TRIPS = (N + TB - 1) / TB, EXP_TRIPS = (256u + TB - 1) / TB;
+    IcdfPiece piece[TRIPS];
+    double e[EXP_TRIPS];
+#pragma unroll
+    for (unsigned k = 0; k < TRIPS; ++k) {
+        const unsigned i = threadIdx.x + k * TB;
+        if (N % TB == 0 || i < N) piece[k] = g_icdf_table[i];
+    }
+#pragma unroll
+    for (unsigned k = 0; k < EXP_TRIPS; ++k) {
+        const unsigned i = threadIdx.x + k * TB;
+        if (i < 256u) e[k] = g_exp_table[i];
+    }
+#pragma unroll
+    for (unsigned k = 0; k < TRIPS; ++k) {
+        const unsigned i = threadIdx.x + k * TB;
+        if (N % TB == 0 || i < N) lds.icdf[i] = piece[k];
+    }
+#pragma unroll
+    for (unsigned k = 0; k < EXP_TRIPS; ++k) {
+        const unsigned i = threadIdx.x + k * TB;
+        if (i < 256u) lds_exp[i] = e[k];
+    }
+    __syncthreads();
+    return RngTables{lds.icdf, nullptr};
+}
+
 #ifndef SVMC_PHILOX_ROUNDS
 #define SVMC_PHILOX_ROUNDS 7
 #endif
@@ -326,15 +359,20 @@ __device__ __forceinline__ void pair_finish(const PairInFlight &d, double &z0, d
 // profiles/r06_mid_waves_sweep.json).  The last trip draws a call nobody uses rather than branching inside the trip (a branch
 // splits the scheduling region), and the round keys are hoisted out of the time loop (philox_draw<true>).  Same words, same
 // operations: the same bits.
-template <class Step>
+// tick(t) is rng_time_loop's: once per call whose steps run, before them, with the local index of the call's first step.
+// HOIST_KEYS = false (the full-launch LogSV kernels, eight waves per SIMD: philox_draw's note on their SGPR budget) leaves the
+// round keys re-derived in every trip.  There the loop is not for a lone wave's latency: with the pair's four reads landing under
+// the wave's own step, of a step's three LDS round trips only the exp-table read is left for the other seven waves to cover.
+template <bool HOIST_KEYS = true, class Step, class Tick>
 __device__ __forceinline__ void rng_time_loop_pair_ahead(const PhiloxLane &lane, uint32_t step0, int nb, const RngTables &tab,
-                                                         Step &&step)
+                                                         Step &&step, Tick &&tick)
 {
     if (nb <= 0) return;
     const uint32_t first = step0, last = step0 + static_cast<uint32_t>(nb) - 1u;
     uint32_t c = first >> 1, r[4];
     double a0, a1;
     if (first & 1u) {
+        tick(-1);
         philox_draw(lane, c, r);
         normals_from_words(r[2], r[3], tab, a0, a1);
         step(a0, a1);
@@ -347,23 +385,32 @@ __device__ __forceinline__ void rng_time_loop_pair_ahead(const PhiloxLane &lane,
         pair_issue(r[0], r[1], tab, d);
         __builtin_amdgcn_sched_barrier(0);
         for (; c < c_end; ++c) {
+            tick(static_cast<int>(2u * c - first));
             double z0, z1;
             pair_finish(d, z0, z1);
             pair_issue(r[2], r[3], tab, d);
             __builtin_amdgcn_sched_barrier(0);
             step(z0, z1);
             pair_finish(d, z0, z1);
-            philox_draw<true>(lane, c + 1u, r);            // the last trip draws a call nobody uses (no branch in the trip)
+            philox_draw<HOIST_KEYS>(lane, c + 1u, r);      // the last trip draws a call nobody uses (no branch in the trip)
             pair_issue(r[0], r[1], tab, d);
             __builtin_amdgcn_sched_barrier(0);
             step(z0, z1);
         }
     }
     if (!(last & 1u)) {
+        tick(static_cast<int>(last - first));
         philox_draw(lane, last >> 1, r);
         normals_from_words(r[0], r[1], tab, a0, a1);
         step(a0, a1);
     }
+}
+
+template <class Step>
+__device__ __forceinline__ void rng_time_loop_pair_ahead(const PhiloxLane &lane, uint32_t step0, int nb, const RngTables &tab,
+                                                         Step &&step)
+{
+    rng_time_loop_pair_ahead(lane, step0, nb, tab, step, [](int) {});
 }
 
 // The same idea one level finer, for a step that itself waits on an LDS read (LogSV: the exp table): the step comes in two
@@ -433,7 +480,8 @@ __device__ __forceinline__ void rng_time_loop_pipelined(const PhiloxLane &lane, 
 }
 
 // the forms of the generators' time loop, by launch size (few_waves_launch() in svmc_kernels.hip picks): full launches run
-// rng_time_loop, the few-waves Heston generators rng_time_loop_pair_ahead, the few-waves LogSV ones rng_time_loop_pipelined.
+// rng_time_loop (the LogSV ones rng_time_loop_pair_ahead with un-hoisted keys: logsv_slice_full), the few-waves Heston generators
+// rng_time_loop_pair_ahead, the few-waves LogSV ones rng_time_loop_pipelined.
 // The values are template arguments of the kernels, part of their symbol names: they stay as they are.
 enum GenLoop { GEN_LOOP_FULL = 0, GEN_LOOP_PAIR = 2, GEN_LOOP_PIPE = 4 };
 template <int LOOP, class Step>

@@ -60,22 +60,44 @@ def loops(body: str):
     """-> list of (first_label, [instruction lines]) for every backward branch, innermost first"""
     lines = body.split("\n")
     label_at = {}
+    innermost = set()                 # labels of the blocks the compiler's own comments place in an innermost loop
+    header_of = {}                    # label -> the header of the loop its block is in (from those comments)
+    last_label = None                 # the label whose comment lines are being read (until its first instruction)
     instrs = []                       # (index, opcode, full line)
+
+    def note(label, text):
+        if "Inner Loop Header" in text:
+            innermost.add(label)
+        m = re.search(r"in Loop: Header=(BB\d+_\d+)", text)
+        if m:
+            header_of[label] = ".L" + m.group(1)
+
     for ln in lines:
         s = ln.strip()
         if not s or s.startswith(";") or s.startswith("//"):
+            if last_label is not None:
+                note(last_label, s)
             continue
         m = re.match(r"^(\.LBB\d+_\d+):", s)
         if m:
             label_at[m.group(1)] = len(instrs)
+            last_label = m.group(1)
+            note(last_label, s)
             continue
         if s.startswith("."):
             continue
+        last_label = None
         instrs.append(s)
+    innermost |= {lab for lab, h in header_of.items() if h in innermost}
     out = []
     for i, s in enumerate(instrs):
         m = re.match(r"^s_cbranch_\w+\s+(\.LBB\d+_\d+)", s) or re.match(r"^s_branch\s+(\.LBB\d+_\d+)", s)
         if m and m.group(1) in label_at and label_at[m.group(1)] <= i:
+            # a backward branch to a block outside every innermost loop is block placement (a cold block laid out after the
+            # code it returns to) or the back edge of an outer loop, whose range need not hold the loop inside it; assembly
+            # without the compiler's loop comments keeps every backward branch
+            if innermost and m.group(1) not in innermost:
+                continue
             out.append((m.group(1), instrs[label_at[m.group(1)]:i + 1]))
     return out
 
