@@ -21,10 +21,49 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
+from .utils.funcs import chain_step_grid
 
 LOG_RETURN, Q_VAR, SIGMA = 1, 2, 3
 HESTON_EULER_FLOOR, HESTON_QE = 0, 1
 _TYPE_CODES = {"C": 0, "P": 1, "IC": 2, "IP": 3}
+
+
+_DP = C.POINTER(C.c_double)
+_POINTERS = {np.dtype(t): C.POINTER(c) for t, c in ((np.float64, C.c_double), (np.int8, C.c_int8), (np.int32, C.c_int),
+                                                    (np.uint32, C.c_uint32), (np.uint64, C.c_uint64))}
+
+
+def ptr(a: np.ndarray):
+    """the C pointer of a contiguous array, typed by the array's dtype; the pointer keeps the array alive"""
+    return a.ctypes.data_as(_POINTERS[a.dtype])
+
+
+def row_ptr(res: np.ndarray, r: int):
+    """the C pointer of row r (along the first axis) of a C-contiguous float64 result block"""
+    return C.cast(res.ctypes.data + r * res.strides[0], _DP)
+
+
+def _flag(v) -> int:
+    """a truth value as the C int the ABI takes"""
+    return int(bool(v))
+
+
+def expiry_rows(res: np.ndarray, slices: Sequence[slice]) -> tuple:
+    """a result block [R][K] cut into expiries: per row the list of its per-expiry views"""
+    return tuple([row[sl] for sl in slices] for row in res)
+
+
+def expiry_rows_per_job(res: np.ndarray, slices: Sequence[slice]) -> list:
+    """a result block [R][J][K] of J jobs (or parameter sets): per job what expiry_rows gives for its [R][K]"""
+    return [expiry_rows(res[:, j], slices) for j in range(res.shape[1])]
+
+
+def chain_etas(etas, m: int) -> np.ndarray:
+    """the vol-backbone etas of a LogSV chain of m expiries as a contiguous float64 vector"""
+    etas = np.ascontiguousarray(etas, dtype=np.float64).ravel()
+    if etas.size != m:
+        raise ValueError("vol_backbone_etas must have one entry per maturity")
+    return etas
 
 
 _CODES_CACHE = {}           # (dtype, bytes) of a NumPy array of option types -> its int8 codes (read-only)
@@ -334,7 +373,6 @@ def marshalled_chain(ttms, forwards, discfactors, strikes: Sequence[np.ndarray],
     if hit is not None:
         return hit
     m = len(strikes)
-    dp = C.POINTER(C.c_double)
     f64 = lambda a: np.array(a, dtype=np.float64, order="C", copy=True).ravel()      # noqa: E731  (private copies)
     offs = np.concatenate([[0], np.cumsum([int(np.size(k)) for k in strikes])]).astype(np.uintp)
     total = int(offs[-1])
@@ -346,10 +384,11 @@ def marshalled_chain(ttms, forwards, discfactors, strikes: Sequence[np.ndarray],
     hit = {
         "keep": (t, f, d, k_all, c_all, offs), "total": total, "offs": offs, "m": m,
         "slices": [slice(int(offs[i]), int(offs[i + 1])) for i in range(m)],
-        "ttms": t.ctypes.data_as(dp), "forwards": f.ctypes.data_as(dp), "discfactors": d.ctypes.data_as(dp),
-        "strikes": k_all.ctypes.data_as(dp), "codes": c_all.ctypes.data_as(C.POINTER(C.c_int8)),
+        "ttms": ptr(t), "forwards": ptr(f), "discfactors": ptr(d), "strikes": ptr(k_all), "codes": ptr(c_all),
         "offsets": offs.ctypes.data_as(C.POINTER(C.c_size_t)),
     }
+    # the C-argument run every chain entry takes (after its session): ttms, forwards, discfactors, n_expiries, strikes, types, offsets
+    hit["args"] = (hit["ttms"], hit["forwards"], hit["discfactors"], m, hit["strikes"], hit["codes"], hit["offsets"])
     if len(_CHAIN_CACHE) >= 16:
         _CHAIN_CACHE.clear()
     _CHAIN_CACHE[key] = hit
@@ -482,11 +521,16 @@ def tilted_chain_arrays(forwards, strikes: Sequence[np.ndarray], codes: Sequence
         raise ValueError("forwards and strikes must be finite")
     out = {"m": m, "total": total, "offs": offs, "forwards": f, "strikes": k_all, "codes": c_all, "gammas": g,
            "strikes_ttms": [k.ravel() for k in strikes], "codes_ttms": codes, "shapes": [k.shape for k in strikes]}
+    # the C-argument run of the tilted entries: forwards, n_expiries, strikes, types, offsets (no discount factors; the arrays above
+    # keep the pointers' memory alive), and the gammas with their count
+    out["args"] = (ptr(f), m, ptr(k_all), ptr(c_all), offs.ctypes.data_as(C.POINTER(C.c_size_t)))
+    out["gamma_args"] = (ptr(g), g.size)
     if ttms is not None:
         t = np.ascontiguousarray(np.asarray(ttms, dtype=np.float64)).ravel()
         if t.size != m:
             raise ValueError("chain arrays must have one entry per maturity")
         out["ttms"] = t
+        out["ttms_arg"] = ptr(t)                      # the session entries alone take the ttms
     return out
 
 
@@ -536,6 +580,45 @@ GREEKS_MAX_PARAMS = 31         # SVMC_GREEKS_MAX_PARAMS
 GREEKS_BASE_FIELDS = ("delta", "delta_stderr", "dual_delta", "dual_delta_stderr", "n_itm")    # SVMC_GREEKS_BASE_ROWS
 GREEKS_SENS_FIELDS = ("sens", "sens_stderr", "n_pairs")                                       # SVMC_GREEKS_SENS_ROWS
 
+
+# ---- the single-chain session entries svmc_<model>_chain_price{,_cmc,_cmc_greeks} (HipEngine._price_chain_fused) --------------------
+def _logsv_args(ch, v0, theta, kappa1, kappa2, beta, volvol, etas, is_spot_measure):
+    """LogSV: the etas go between the discount factors and the expiry count, six scalars and the measure after the quotes"""
+    return (ptr(chain_etas(etas, ch["m"])),), (float(v0), float(theta), float(kappa1), float(kappa2), float(beta), float(volvol),
+                                               int(bool(is_spot_measure)))
+
+
+def _heston_args(ch, v0, theta, kappa, rho, volvol, scheme=None):
+    """Heston: five scalars after the quotes, then the scheme code where the entry takes one (the conditional ones step Euler)"""
+    return (), (float(v0), float(theta), float(kappa), float(rho), float(volvol)) + (() if scheme is None else (int(scheme),))
+
+
+def _hawkesjd_args(ch, params):
+    """Hawkes: the SVMC_HAWKESJD_PARAMS doubles of include/svmc.h after the quotes"""
+    return (), (ptr(np.ascontiguousarray(params, dtype=np.float64)),)
+
+
+def _fused_names(model: str, step_one: str, step_chain: str, cond: str) -> dict:
+    """result kind -> (C symbol, the stepping kernel's name for one expiry, for a chain) as start_kernel_timing reports them"""
+    stem = f"svmc_{model}_chain_price"
+    return {"": (stem, step_one, step_chain), "_cmc": (stem + "_cmc", cond, cond), "_cmc_greeks": (stem + "_cmc_greeks", cond, cond)}
+
+
+# model -> (how the route's parameters become (arguments before the expiry count, arguments after the quotes), the names)
+FUSED_MODELS = {
+    "logsv": (_logsv_args, _fused_names("logsv", "logsv_rng_kernel", "logsv_chain_rng_kernel", "logsv_chain_cmc_kernel")),
+    "heston": (_heston_args, _fused_names("heston", "heston_rng_kernel", "heston_chain_rng_kernel", "heston_chain_cmc_kernel")),
+    "hawkesjd": (_hawkesjd_args, _fused_names("hawkesjd", "hawkesjd_chain_rng_kernel", "hawkesjd_chain_rng_kernel",
+                                              "hawkes_chain_cond_kernel")),
+}
+# result kind -> (rows of the result block, doubles per expiry of the statistics, their shaping): (prices, stderrs), the same with
+# statistics, (fields, statistics)
+FUSED_KINDS = {"": (2, 0, None), "_cmc": (2, CMC_STATS_DOUBLES, cmc_stats_dicts),
+               "_cmc_greeks": (CMC_GREEKS_ROWS, CMC_GREEKS_STATS_DOUBLES, cmc_greeks_stats_dicts)}
+# the models of the many-job, sensitivity and set routes (HipEngine._model_entry): model -> its entry takes a mode argument
+PLAIN_MANY_MODELS = {"logsv": True, "heston": True, "hawkesjd": False}      # is_spot_measure, the scheme code, nothing
+GREEKS_MODELS = {"logsv": True, "heston": True}
+CMC_MODELS = {"logsv": True, "heston": False}                               # the conditional Heston entries step Euler only
 
 MANY_MAX_JOBS = 64             # jobs per svmc_*_chain_price_many call: SVMC_MANY_MAX_JOBS of include/svmc.h
 BULK_KEEP_FRACTION = 0.125     # of the device's memory: what an engine's cached bulk buffers may hold between calls (trim_bulk)
@@ -681,14 +764,28 @@ class HipEngine:
                 _lib.check(self.lib.svmc_session_use_graphs(sess, 0))
         return self._fused
 
-    def _fused_call(self, ch: dict, call, kernel_name: str):
-        """run call(session, prices_ptr, stderrs_ptr) and cut the two result rows into per-expiry arrays; while kernel timing is
-        on (start_kernel_timing) the session brackets its stepping launch with HIP events and the time is kept under kernel_name"""
-        res = np.empty((2, max(ch["total"], 1)))
-        dp = C.POINTER(C.c_double)
-        self._session_call(ch, lambda sess: call(sess, C.cast(res.ctypes.data, dp), C.cast(res.ctypes.data + res.strides[0], dp)),
-                           kernel_name)
-        return [res[0, sl] for sl in ch["slices"]], [res[1, sl] for sl in ch["slices"]]
+    def _price_chain_fused(self, ch: dict, model: str, kind: str, params: tuple, nb_steps_per_year, flag: int, seed: int, call_id: int):
+        """ONE svmc_<model>_chain_price<kind> call on this engine's session (ch: marshalled_chain): the single-chain route of every
+        model (FUSED_MODELS: how `params` become C arguments, the stepping kernel's names) and result kind (FUSED_KINDS: the output
+        buffers and their shaping).  flag: the variable type of the plain kind, recenter of the conditional ones.  While kernel
+        timing is on (start_kernel_timing) the session brackets its stepping launch with HIP events and the time is kept under
+        the kernel's name"""
+        pack, names = FUSED_MODELS[model]
+        rows, stats_doubles, stats_dicts = FUSED_KINDS[kind]
+        mid, args = pack(ch, *params)
+        a = ch["args"]
+        res = np.empty((rows, max(ch["total"], 1)))
+        outs = (row_ptr(res, 0), row_ptr(res, 1)) if rows == 2 else (ptr(res),)
+        if stats_dicts is not None:
+            stats = np.empty((ch["m"], stats_doubles))
+            outs += (ptr(stats),)
+        fn = getattr(self.lib, names[kind][0])
+        self._session_call(ch, lambda sess: fn(sess, *a[:3], *mid, *a[3:], *args, int(nb_steps_per_year), flag, int(seed), int(call_id),
+                                               *outs), names[kind][1 if ch["m"] == 1 else 2])
+        if rows != 2:
+            return cmc_greeks_dict(res, ch["slices"]), stats_dicts(stats)
+        out = expiry_rows(res, ch["slices"])
+        return out if stats_dicts is None else out + (stats_dicts(stats),)
 
     def _session_call(self, ch: dict, call, kernel_name: str) -> None:
         """run call(session) on the fused chain session of ch's size, the stepping launch timed under kernel_name while kernel
@@ -710,22 +807,14 @@ class HipEngine:
         the kernels, their order and their arguments are those of mc_chain.price_chain_on_engine -- the same bits -- without
         the dozen ctypes calls and NumPy temporaries around them (tools/r06/chain_call_breakdown.py: 0.135 -> 0.114 ms for a
         4 x 13 chain at 2^16 paths)"""
-        etas = np.ascontiguousarray(etas, dtype=np.float64)
-        if etas.size != ch["m"]:
-            raise ValueError("vol_backbone_etas must have one entry per maturity")
-        return self._fused_call(ch, lambda sess, p, e: self.lib.svmc_logsv_chain_price(
-            sess, ch["ttms"], ch["forwards"], ch["discfactors"], etas.ctypes.data_as(C.POINTER(C.c_double)), ch["m"], ch["strikes"],
-            ch["codes"], ch["offsets"], float(v0), float(theta), float(kappa1), float(kappa2), float(beta), float(volvol),
-            int(bool(is_spot_measure)), int(nb_steps_per_year), int(variable_type), int(seed), int(call_id), p, e),
-            "logsv_rng_kernel" if ch["m"] == 1 else "logsv_chain_rng_kernel")
+        return self._price_chain_fused(ch, "logsv", "", (v0, theta, kappa1, kappa2, beta, volvol, etas, is_spot_measure),
+                                       nb_steps_per_year, int(variable_type), seed, call_id)
 
     def price_heston_chain_fused(self, ch: dict, v0, theta, kappa, rho, volvol, scheme: int, nb_steps_per_year, variable_type: int,
                                  seed: int, call_id: int):
         """heston_mc_chain_pricer on one GPU as ONE svmc_heston_chain_price call on this engine's state"""
-        return self._fused_call(ch, lambda sess, p, e: self.lib.svmc_heston_chain_price(
-            sess, ch["ttms"], ch["forwards"], ch["discfactors"], ch["m"], ch["strikes"], ch["codes"], ch["offsets"], float(v0),
-            float(theta), float(kappa), float(rho), float(volvol), int(scheme), int(nb_steps_per_year), int(variable_type),
-            int(seed), int(call_id), p, e), "heston_rng_kernel" if ch["m"] == 1 else "heston_chain_rng_kernel")
+        return self._price_chain_fused(ch, "heston", "", (v0, theta, kappa, rho, volvol, scheme), nb_steps_per_year, int(variable_type),
+                                       seed, call_id)
 
     @staticmethod
     def _many_jobs(params, seeds: Sequence[int], call_ids: Sequence[int], what: str = "one seed and one call id per job"):
@@ -735,8 +824,14 @@ class HipEngine:
         ids = np.ascontiguousarray(call_ids, dtype=np.uint32)
         if not (seeds.size == ids.size == params.shape[0]):
             raise ValueError(what)
-        return params.shape[0], (params.ctypes.data_as(C.POINTER(C.c_double)), seeds.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                 ids.ctypes.data_as(C.POINTER(C.c_uint32)))
+        return params.shape[0], (ptr(params), ptr(seeds), ptr(ids))
+
+    def _model_entry(self, who: str, model: str, stem: str, allowed: dict, mode, as_c=int):
+        """(the entry point svmc_<model>_<stem>, its mode arguments) of the route `who`, open to the models of `allowed` (model ->
+        the entry takes as_c(mode))"""
+        if model not in allowed:
+            raise ValueError(f"{who}: unknown model {model!r}")
+        return getattr(self.lib, f"svmc_{model}_{stem}"), ((as_c(mode),) if allowed[model] else ())
 
     def price_chain_many_fused(self, ch: dict, model: str, params: np.ndarray, seeds: Sequence[int], call_ids: Sequence[int],
                                mode: int, nb_steps_per_year: int, variable_type: int):
@@ -744,37 +839,26 @@ class HipEngine:
         svmc_heston_chain_price_many ("heston", mode = scheme code, params [J][5]) or svmc_hawkesjd_chain_price_many ("hawkesjd",
         mode unused, params [J][SVMC_HAWKESJD_PARAMS]) call on this engine's session, J at most MANY_MAX_JOBS: per job the
         (prices, stderrs) of the single fused call with its (seed, call id), cut into expiries"""
-        if model not in ("logsv", "heston", "hawkesjd"):
-            raise ValueError(f"price_chain_many_fused: unknown model {model!r}")
+        fn, modes = self._model_entry("price_chain_many_fused", model, "chain_price_many", PLAIN_MANY_MODELS, mode)
         n_jobs, jobs = self._many_jobs(params, seeds, call_ids)
         sess = self.fused_chain_session(ch["m"], ch["total"])
         res = np.empty((2, n_jobs, max(ch["total"], 1)))
-        dp = C.POINTER(C.c_double)
-        fn = {"logsv": self.lib.svmc_logsv_chain_price_many, "heston": self.lib.svmc_heston_chain_price_many,
-              "hawkesjd": self.lib.svmc_hawkesjd_chain_price_many}[model]
-        modes = () if model == "hawkesjd" else (int(mode),)
-        _lib.check(fn(sess, ch["ttms"], ch["forwards"], ch["discfactors"], ch["m"], ch["strikes"], ch["codes"], ch["offsets"], n_jobs,
-                      *jobs, *modes, int(nb_steps_per_year), int(variable_type), C.cast(res.ctypes.data, dp),
-                      C.cast(res.ctypes.data + res.strides[0], dp)))
-        return [([res[0, j, sl] for sl in ch["slices"]], [res[1, j, sl] for sl in ch["slices"]]) for j in range(n_jobs)]
+        _lib.check(fn(sess, *ch["args"], n_jobs, *jobs, *modes, int(nb_steps_per_year), int(variable_type), row_ptr(res, 0),
+                      row_ptr(res, 1)))
+        return expiry_rows_per_job(res, ch["slices"])
 
     def price_hawkesjd_chain_fused(self, ch: dict, params: np.ndarray, nb_steps_per_year: int, variable_type: int, seed: int,
                                    call_id: int):
         """hawkesjd_mc_chain_pricer on one GPU as ONE svmc_hawkesjd_chain_price call on this engine's state (vol / qvar hold
         lambda_p / lambda_m afterwards); params: the SVMC_HAWKESJD_PARAMS doubles of include/svmc.h"""
-        params = np.ascontiguousarray(params, dtype=np.float64)
-        return self._fused_call(ch, lambda sess, p, e: self.lib.svmc_hawkesjd_chain_price(
-            sess, ch["ttms"], ch["forwards"], ch["discfactors"], ch["m"], ch["strikes"], ch["codes"], ch["offsets"],
-            params.ctypes.data_as(C.POINTER(C.c_double)), int(nb_steps_per_year), int(variable_type), int(seed), int(call_id),
-            p, e), "hawkesjd_chain_rng_kernel")
+        return self._price_chain_fused(ch, "hawkesjd", "", (params,), nb_steps_per_year, int(variable_type), seed, call_id)
 
     def hawkesjd_rng(self, nb_steps: int, dt: float, params: np.ndarray, seed: int, call_id: int, step_offset: int = 0) -> None:
         """simulate_hawkesjd_terminal on this engine's state (x, lambda_p, lambda_m) in place"""
         params = np.ascontiguousarray(params, dtype=np.float64)
         self._timed("hawkesjd_rng_kernel", lambda: _lib.check(self.lib.svmc_hawkesjd_terminal_rng(
-            self.x.ptr, self.vol.ptr, self.qvar.ptr, self.n_path, int(nb_steps), float(dt),
-            params.ctypes.data_as(C.POINTER(C.c_double)), int(seed), int(call_id), self.path_offset, int(step_offset),
-            self.stream)))
+            self.x.ptr, self.vol.ptr, self.qvar.ptr, self.n_path, int(nb_steps), float(dt), ptr(params), int(seed), int(call_id),
+            self.path_offset, int(step_offset), self.stream)))
 
     # ---- conditional Monte Carlo for the Hawkes jump-diffusion (include/svmc.h, DESIGN.md row f16): the state is (mu, lambda_p,
     # lambda_m) in x / vol / qvar; the conditional variance is one double per expiry, formed on the host
@@ -795,32 +879,22 @@ class HipEngine:
             cv_row = mu_row + n if cv_row is None else cv_row
             mu_ptr, cv_ptr, _ = self._cmc_rows(n, mu_row, cv_row, None)
         cvs = np.empty(max(n, 1))
-        dp = C.POINTER(C.c_double)
         self._timed("hawkes_chain_cond_kernel", lambda: _lib.check(self.lib.svmc_hawkesjd_chain_cond(
-            self.x.ptr, self.vol.ptr, self.qvar.ptr, self.n_path, n, nb.ctypes.data_as(C.POINTER(C.c_int)), dt.ctypes.data_as(dp),
-            params.ctypes.data_as(dp), float(cv_start), int(seed), int(call_id), self.path_offset, int(step_offset), mu_ptr, cv_ptr,
-            cvs.ctypes.data_as(dp), self.stream)))
+            self.x.ptr, self.vol.ptr, self.qvar.ptr, self.n_path, n, ptr(nb), ptr(dt), ptr(params), float(cv_start), int(seed),
+            int(call_id), self.path_offset, int(step_offset), mu_ptr, cv_ptr, ptr(cvs), self.stream)))
         return cvs[:n]
 
     def price_hawkesjd_chain_cmc_fused(self, ch: dict, params: np.ndarray, nb_steps_per_year: int, recenter: bool, seed: int,
                                        call_id: int):
         """hawkesjd_mc_chain_pricer_conditional as ONE svmc_hawkesjd_chain_price_cmc call on this engine's state; returns (prices,
         stderrs, stats) cut into expiries"""
-        params = np.ascontiguousarray(params, dtype=np.float64)
-        return self._fused_cmc_call(ch, lambda sess, p, e, st: self.lib.svmc_hawkesjd_chain_price_cmc(
-            sess, ch["ttms"], ch["forwards"], ch["discfactors"], ch["m"], ch["strikes"], ch["codes"], ch["offsets"],
-            params.ctypes.data_as(C.POINTER(C.c_double)), int(nb_steps_per_year), int(bool(recenter)), int(seed), int(call_id), p, e,
-            st), "hawkes_chain_cond_kernel")
+        return self._price_chain_fused(ch, "hawkesjd", "_cmc", (params,), nb_steps_per_year, int(bool(recenter)), seed, call_id)
 
     def price_hawkesjd_chain_cmc_greeks_fused(self, ch: dict, params: np.ndarray, nb_steps_per_year: int, recenter: bool, seed: int,
                                               call_id: int):
         """hawkesjd_mc_chain_greeks_conditional as ONE svmc_hawkesjd_chain_price_cmc_greeks call on this engine's state; returns
         (fields, stats) as conditional_greeks"""
-        params = np.ascontiguousarray(params, dtype=np.float64)
-        return self._fused_cmc_greeks_call(ch, lambda sess, g, st: self.lib.svmc_hawkesjd_chain_price_cmc_greeks(
-            sess, ch["ttms"], ch["forwards"], ch["discfactors"], ch["m"], ch["strikes"], ch["codes"], ch["offsets"],
-            params.ctypes.data_as(C.POINTER(C.c_double)), int(nb_steps_per_year), int(bool(recenter)), int(seed), int(call_id), g, st),
-            "hawkes_chain_cond_kernel")
+        return self._price_chain_fused(ch, "hawkesjd", "_cmc_greeks", (params,), nb_steps_per_year, int(bool(recenter)), seed, call_id)
 
     # ---- state ----------------------------------------------------------------------------------
     def fill_state(self, x0: float, vol0: float, qvar0: float) -> None:
@@ -937,14 +1011,13 @@ class HipEngine:
         terminal x of each expiry, rows m..2m-1 the quadratic variance (need_qvar), spot_ptr the 2m spot sums;
         start = (x0, sigma0, qvar0) as in logsv_slice_rng"""
         m = len(nb_steps)
-        dp = C.POINTER(C.c_double)
         nbs = (C.c_int * m)(*[int(v) for v in nb_steps])
         d, e, f = (np.ascontiguousarray(a, dtype=np.float64) for a in (dts, etas, forwards))
         fn = self.lib.svmc_logsv_chain_rng if start is None else functools.partial(self.lib.svmc_logsv_chain_rng_from,
                                                                                    *[float(v) for v in start])
         self._timed("logsv_chain_rng_kernel", lambda: _lib.check(fn(
-            self.x.ptr, self.vol.ptr, self.qvar.ptr, self.n_path, m, nbs, d.ctypes.data_as(dp), e.ctypes.data_as(dp),
-            f.ctypes.data_as(dp), float(theta), float(kappa1), float(kappa2), float(beta), float(volvol),
+            self.x.ptr, self.vol.ptr, self.qvar.ptr, self.n_path, m, nbs, ptr(d), ptr(e),
+            ptr(f), float(theta), float(kappa1), float(kappa2), float(beta), float(volvol),
             int(bool(is_spot_measure)), int(seed), int(call_id), self.path_offset, int(step_offset), self.snapshot_ptr(0),
             self.snapshot_ptr(m) if need_qvar else None, spot_ptr, self.ws.ptr, self.ws_bytes, self.stream)))
 
@@ -953,13 +1026,12 @@ class HipEngine:
         """every expiry of a Heston chain in one stepping launch (svmc_heston_chain_rng); layout and `start` as
         logsv_chain_rng"""
         m = len(nb_steps)
-        dp = C.POINTER(C.c_double)
         nbs = (C.c_int * m)(*[int(v) for v in nb_steps])
         d, f = (np.ascontiguousarray(a, dtype=np.float64) for a in (dts, forwards))
         fn = self.lib.svmc_heston_chain_rng if start is None else functools.partial(self.lib.svmc_heston_chain_rng_from,
                                                                                     *[float(v) for v in start])
         self._timed("heston_chain_rng_kernel", lambda: _lib.check(fn(
-            self.x.ptr, self.vol.ptr, self.qvar.ptr, self.n_path, m, nbs, d.ctypes.data_as(dp), f.ctypes.data_as(dp),
+            self.x.ptr, self.vol.ptr, self.qvar.ptr, self.n_path, m, nbs, ptr(d), ptr(f),
             float(theta), float(kappa), float(rho), float(volvol), int(scheme), int(seed), int(call_id), self.path_offset,
             int(step_offset), self.snapshot_ptr(0), self.snapshot_ptr(m) if need_qvar else None, spot_ptr, self.ws.ptr,
             self.ws_bytes, self.stream)))
@@ -998,9 +1070,8 @@ class HipEngine:
             raise ValueError("nodes, weights and v0 must be 1-d arrays of one length")
         if self._factors is None:
             self._factors = DeviceBuffer(3 * self.n_path)
-        dp = C.POINTER(C.c_double)
         args = (self.x.ptr, self._factors.ptr, self.qvar.ptr, self.n_path, int(nb_steps), float(h), int(nodes.size),
-                nodes.ctypes.data_as(dp), weights.ctypes.data_as(dp), v0.ctypes.data_as(dp), float(theta), float(kappa1),
+                ptr(nodes), ptr(weights), ptr(v0), float(theta), float(kappa1),
                 float(kappa2), float(rho), float(volvol), z0_ptr, z1_ptr, self.n_path if ldw is None else int(ldw),
                 int(seed), int(call_id), self.path_offset, int(step_offset), int(bool(from_origin)))
         if slice_out is None:
@@ -1024,12 +1095,11 @@ class HipEngine:
         if self._factors is None:
             self._factors = DeviceBuffer(3 * self.n_path)
         m = len(nb_steps)
-        dp = C.POINTER(C.c_double)
         nbs = (C.c_int * m)(*[int(v) for v in nb_steps])
         h, f = (np.ascontiguousarray(a, dtype=np.float64) for a in (hs, forwards))
         self._timed("rough_logsv_expiries_kernel", lambda: _lib.check(self.lib.svmc_rough_logsv_chain(
-            self.x.ptr, self._factors.ptr, self.qvar.ptr, self.n_path, m, nbs, h.ctypes.data_as(dp), f.ctypes.data_as(dp),
-            int(nodes.size), nodes.ctypes.data_as(dp), weights.ctypes.data_as(dp), v0.ctypes.data_as(dp), float(theta),
+            self.x.ptr, self._factors.ptr, self.qvar.ptr, self.n_path, m, nbs, ptr(h), ptr(f),
+            int(nodes.size), ptr(nodes), ptr(weights), ptr(v0), float(theta),
             float(kappa1), float(kappa2), float(rho), float(volvol), z0_ptr, z1_ptr, self.n_path if ldw is None else int(ldw),
             int(seed), int(call_id), self.path_offset, self.snapshot_ptr(0), self.snapshot_ptr(m) if need_qvar else None,
             spot_ptr, self.ws.ptr, self.ws_bytes, self.stream)))
@@ -1113,7 +1183,6 @@ class HipEngine:
         offs = np.concatenate([[0], np.cumsum([len(k) for k in strikes])]).astype(np.uintp)
         if int(offs[-1]) == 0:
             return
-        dp = C.POINTER(C.c_double)
         k_all = np.ascontiguousarray(np.concatenate(strikes), dtype=np.float64)
         c_all = np.ascontiguousarray(np.concatenate(codes), dtype=np.int8)
         s_all = np.ascontiguousarray(np.concatenate(shifts), dtype=np.float64)
@@ -1122,8 +1191,8 @@ class HipEngine:
         xs = (C.c_void_p * m)(*[self.snapshot_ptr(r) for r in snap_rows])
         qs = None if qvar_rows is None else (C.c_void_p * m)(*[self.snapshot_ptr(r) for r in qvar_rows])
         _lib.check(self.lib.svmc_payoff_sums_chain(
-            xs, qs, self.n_path, fw.ctypes.data_as(dp), tt.ctypes.data_as(dp), spot_sums_ptr, m, k_all.ctypes.data_as(dp),
-            c_all.ctypes.data_as(C.POINTER(C.c_int8)), s_all.ctypes.data_as(dp), offs.ctypes.data_as(C.POINTER(C.c_size_t)),
+            xs, qs, self.n_path, ptr(fw), ptr(tt), spot_sums_ptr, m, ptr(k_all),
+            ptr(c_all), ptr(s_all), offs.ctypes.data_as(C.POINTER(C.c_size_t)),
             int(variable_type), out_ptr, self.ws.ptr, self.ws_bytes, self.stream))
 
     def tilted_payoffs(self, forwards, strikes: Sequence[np.ndarray], codes: Sequence[np.ndarray], gammas, recenter: bool = False,
@@ -1137,7 +1206,6 @@ class HipEngine:
         if (m != 1) if snap_rows is None else (len(snap_rows) != m):
             raise ValueError("one snapshot row per expiry (the current state serves one expiry)")
         ptrs = [self.x.ptr] if snap_rows is None else [self.snapshot_ptr(r) for r in snap_rows]
-        dp = C.POINTER(C.c_double)
         shifts = np.ascontiguousarray(np.concatenate([payoff_shifts(k, c, float(f), LOG_RETURN)
                                                       for k, c, f in zip(ch["strikes_ttms"], ch["codes_ttms"], ch["forwards"])]))
         spot_ptr = None
@@ -1147,12 +1215,10 @@ class HipEngine:
                 self.spot_sums(p, float(ch["forwards"][i]), spot_ptr + 16 * i)
         n_out = 2 * G * K + G * m * TILTED_STATS_DOUBLES
         out_ptr, _ = self.alloc_sums(n_out, "tilted")
-        xs = (C.c_void_p * m)(*ptrs)
+        xs, a = (C.c_void_p * m)(*ptrs), ch["args"]
         _lib.check(self.lib.svmc_tilted_payoff_chain(
-            xs, self.n_path, ch["forwards"].ctypes.data_as(dp), m, ch["strikes"].ctypes.data_as(dp),
-            ch["codes"].ctypes.data_as(C.POINTER(C.c_int8)), shifts.ctypes.data_as(dp), ch["offs"].ctypes.data_as(C.POINTER(C.c_size_t)),
-            ch["gammas"].ctypes.data_as(dp), G, int(bool(recenter)), spot_ptr, out_ptr, out_ptr + 8 * G * K, out_ptr + 16 * G * K,
-            self.ws.ptr, self.ws_bytes, self.stream))
+            xs, self.n_path, *a[:4], ptr(shifts), a[4], *ch["gamma_args"], int(bool(recenter)), spot_ptr, out_ptr, out_ptr + 8 * G * K,
+            out_ptr + 16 * G * K, self.ws.ptr, self.ws_bytes, self.stream))
         out = self.download(out_ptr, n_out)
         return tilted_results(out[:G * K], out[G * K:2 * G * K], out[2 * G * K:], ch)
 
@@ -1192,11 +1258,10 @@ class HipEngine:
         cv_row = mu_row + n if cv_row is None else cv_row
         nb = np.ascontiguousarray(nb_steps, dtype=np.int32)
         dt, et = np.ascontiguousarray(dts, dtype=np.float64), np.ascontiguousarray(etas, dtype=np.float64)
-        dp = C.POINTER(C.c_double)
         rows = self._cmc_rows(n, mu_row, cv_row, qvar_row)
         self._timed("logsv_chain_cmc_kernel", lambda: _lib.check(self.lib.svmc_logsv_chain_cmc(
-            self.x.ptr, self.cv.ptr, self.vol.ptr, self.qvar.ptr, self.n_path, n, nb.ctypes.data_as(C.POINTER(C.c_int)),
-            dt.ctypes.data_as(dp), et.ctypes.data_as(dp), float(theta), float(kappa1), float(kappa2), float(beta), float(volvol),
+            self.x.ptr, self.cv.ptr, self.vol.ptr, self.qvar.ptr, self.n_path, n, ptr(nb),
+            ptr(dt), ptr(et), float(theta), float(kappa1), float(kappa2), float(beta), float(volvol),
             int(bool(is_spot_measure)), int(seed), int(call_id), self.path_offset, int(step_offset), *rows, self.stream)))
 
     def heston_chain_cmc(self, nb_steps: Sequence[int], dts: Sequence[float], theta, kappa, rho, volvol, seed, call_id,
@@ -1209,8 +1274,8 @@ class HipEngine:
         dt = np.ascontiguousarray(dts, dtype=np.float64)
         rows = self._cmc_rows(n, mu_row, cv_row, qvar_row)
         self._timed("heston_chain_cmc_kernel", lambda: _lib.check(self.lib.svmc_heston_chain_cmc(
-            self.x.ptr, self.cv.ptr, self.vol.ptr, self.qvar.ptr, self.n_path, n, nb.ctypes.data_as(C.POINTER(C.c_int)),
-            dt.ctypes.data_as(C.POINTER(C.c_double)), float(theta), float(kappa), float(rho), float(volvol), int(seed), int(call_id),
+            self.x.ptr, self.cv.ptr, self.vol.ptr, self.qvar.ptr, self.n_path, n, ptr(nb),
+            ptr(dt), float(theta), float(kappa), float(rho), float(volvol), int(seed), int(call_id),
             self.path_offset, int(step_offset), *rows, self.stream)))
 
     def _cond_row_ptrs(self, m: int, mu_rows, cv_rows):
@@ -1222,10 +1287,12 @@ class HipEngine:
         cvs = [self.cv.ptr] if cv_rows is None else [self.snapshot_ptr(r) for r in cv_rows]
         return mus, cvs
 
-    def _side_workspace(self, size_fn, what: str, m: int, n_quotes: int, n_z: int, tag: str):
-        """(device pointer, bytes) of the workspace a tail of libsvmc_ext.so / libsvmc_est.so asks for, in this engine's `tag` buffer"""
+    def _side_workspace(self, size_fn, size_args: tuple, tag: str, what: Optional[str] = None):
+        """(device pointer, bytes) of the workspace size_fn(*size_args, &bytes) asks for, in this engine's `tag` buffer; what: the
+        entry's name for a tail of libsvmc_ext.so / libsvmc_est.so, which keep no message of their own (_lib.check_ext)"""
         nbytes = C.c_size_t(0)
-        _lib.check_ext(size_fn(self.n_path, m, n_quotes, n_z, C.byref(nbytes)), what)
+        rc = size_fn(*size_args, C.byref(nbytes))
+        _lib.check(rc) if what is None else _lib.check_ext(rc, what)
         ws_ptr, _ = self.alloc_sums((nbytes.value + 7) // 8, tag)
         return ws_ptr, nbytes.value
 
@@ -1238,16 +1305,12 @@ class HipEngine:
         ch = marshalled_chain(np.zeros(len(strikes)), forwards, discfactors, strikes, codes)
         m, K = ch["m"], ch["total"]
         mus, cvs = self._cond_row_ptrs(m, mu_rows, cv_rows)
-        nbytes = C.c_size_t(0)
-        _lib.check(self.lib.svmc_cmc_payoff_workspace_bytes(self.n_path, m, K, C.byref(nbytes)))
-        ws_ptr, _ = self.alloc_sums((nbytes.value + 7) // 8, "cmc_workspace")
+        ws_ptr, nbytes = self._side_workspace(self.lib.svmc_cmc_payoff_workspace_bytes, (self.n_path, m, K), "cmc_workspace")
         res, stats = np.empty((2, max(K, 1))), np.empty((m, CMC_STATS_DOUBLES))
-        dp = C.POINTER(C.c_double)
         _lib.check(self.lib.svmc_cmc_payoff_chain(
-            (C.c_void_p * m)(*mus), (C.c_void_p * m)(*cvs), self.n_path, ch["forwards"], ch["discfactors"], m, ch["strikes"],
-            ch["codes"], ch["offsets"], int(bool(recenter)), C.cast(res.ctypes.data, dp), C.cast(res.ctypes.data + res.strides[0], dp),
-            stats.ctypes.data_as(dp), ws_ptr, nbytes.value, self.stream))
-        return [res[0, sl] for sl in ch["slices"]], [res[1, sl] for sl in ch["slices"]], cmc_stats_dicts(stats)
+            (C.c_void_p * m)(*mus), (C.c_void_p * m)(*cvs), self.n_path, *ch["args"][1:], int(bool(recenter)), row_ptr(res, 0),
+            row_ptr(res, 1), ptr(stats), ws_ptr, nbytes, self.stream))
+        return expiry_rows(res, ch["slices"]) + (cmc_stats_dicts(stats),)
 
     # ---- conditional Monte Carlo under the exponential risk-premia kernel (include/svmc_ext.h): libsvmc_ext.so,
     # the library beside the closed core -- caller-owned device rows, no session
@@ -1265,14 +1328,12 @@ class HipEngine:
         sh = strike_shifts(ch, shifts)
         ext = _lib.load_ext()
         what = "svmc_tilted_cond_payoff_chain"
-        ws_ptr, nbytes = self._side_workspace(ext.svmc_tilted_cond_workspace_bytes, what, m, K, G, "tilted_cond_workspace")
+        ws_ptr, nbytes = self._side_workspace(ext.svmc_tilted_cond_workspace_bytes, (self.n_path, m, K, G), "tilted_cond_workspace", what)
         prices, stderrs, stats = np.empty(max(G * K, 1)), np.empty(max(G * K, 1)), np.empty(G * m * TILTED_STATS_DOUBLES)
-        dp = C.POINTER(C.c_double)
+        a = ch["args"]
         self._timed("tilted_cond_payoff_kernel", lambda: _lib.check_ext(ext.svmc_tilted_cond_payoff_chain(
-            (C.c_void_p * m)(*mus), (C.c_void_p * m)(*cvs), self.n_path, ch["forwards"].ctypes.data_as(dp), m,
-            ch["strikes"].ctypes.data_as(dp), ch["codes"].ctypes.data_as(C.POINTER(C.c_int8)), sh.ctypes.data_as(dp),
-            ch["offs"].ctypes.data_as(C.POINTER(C.c_size_t)), ch["gammas"].ctypes.data_as(dp), G, int(bool(recenter)),
-            prices.ctypes.data_as(dp), stderrs.ctypes.data_as(dp), stats.ctypes.data_as(dp), ws_ptr, nbytes, self.stream), what))
+            (C.c_void_p * m)(*mus), (C.c_void_p * m)(*cvs), self.n_path, *a[:4], ptr(sh), a[4], *ch["gamma_args"], int(bool(recenter)),
+            ptr(prices), ptr(stderrs), ptr(stats), ws_ptr, nbytes, self.stream), what))
         return tilted_results(prices[:G * K], stderrs[:G * K], stats, ch)
 
     def tilted_conditional_greeks(self, forwards, strikes: Sequence[np.ndarray], codes: Sequence[np.ndarray], gammas,
@@ -1288,14 +1349,12 @@ class HipEngine:
         mus, cvs = self._cond_row_ptrs(m, mu_rows, cv_rows)
         est = _lib.load_est()
         what = "svmc_tilted_cond_greeks_chain"
-        ws_ptr, nbytes = self._side_workspace(est.svmc_tilted_cond_greeks_workspace_bytes, what, m, K, G, "tilted_cond_greeks_workspace")
+        ws_ptr, nbytes = self._side_workspace(est.svmc_tilted_cond_greeks_workspace_bytes, (self.n_path, m, K, G),
+                                              "tilted_cond_greeks_workspace", what)
         greeks, stats = np.empty(max(G * TCG_ROWS * K, 1)), np.empty(G * m * TCG_STATS_DOUBLES)
-        dp = C.POINTER(C.c_double)
         self._timed("tilted_cond_greeks_kernel", lambda: _lib.check_ext(est.svmc_tilted_cond_greeks_chain(
-            (C.c_void_p * m)(*mus), (C.c_void_p * m)(*cvs), self.n_path, ch["forwards"].ctypes.data_as(dp), m,
-            ch["strikes"].ctypes.data_as(dp), ch["codes"].ctypes.data_as(C.POINTER(C.c_int8)),
-            ch["offs"].ctypes.data_as(C.POINTER(C.c_size_t)), ch["gammas"].ctypes.data_as(dp), G, int(bool(recenter)),
-            greeks.ctypes.data_as(dp), stats.ctypes.data_as(dp), ws_ptr, nbytes, self.stream), what))
+            (C.c_void_p * m)(*mus), (C.c_void_p * m)(*cvs), self.n_path, *ch["args"], *ch["gamma_args"], int(bool(recenter)),
+            ptr(greeks), ptr(stats), ws_ptr, nbytes, self.stream), what))
         return tilted_greeks_results(greeks, stats, ch)
 
     def conditional_densities(self, x_grids: Sequence[np.ndarray], gammas=(0.0,), mu_rows: Optional[Sequence[int]] = None,
@@ -1310,13 +1369,12 @@ class HipEngine:
         mus, cvs = self._cond_row_ptrs(m, mu_rows, cv_rows)
         est = _lib.load_est()
         what = "svmc_cond_density_chain"
-        ws_ptr, nbytes = self._side_workspace(est.svmc_cond_density_workspace_bytes, what, m, P, G, "cond_density_workspace")
+        ws_ptr, nbytes = self._side_workspace(est.svmc_cond_density_workspace_bytes, (self.n_path, m, P, G), "cond_density_workspace", what)
         pdf, err, stats = np.empty(max(G * P, 1)), np.empty(max(G * P, 1)), np.empty(G * m * CD_STATS_DOUBLES)
-        dp = C.POINTER(C.c_double)
         self._timed("cond_density_kernel", lambda: _lib.check_ext(est.svmc_cond_density_chain(
-            (C.c_void_p * m)(*mus), (C.c_void_p * m)(*cvs), self.n_path, m, ch["points"].ctypes.data_as(dp),
-            ch["offs"].ctypes.data_as(C.POINTER(C.c_size_t)), ch["gammas"].ctypes.data_as(dp), G, pdf.ctypes.data_as(dp),
-            err.ctypes.data_as(dp), stats.ctypes.data_as(dp), ws_ptr, nbytes, self.stream), what))
+            (C.c_void_p * m)(*mus), (C.c_void_p * m)(*cvs), self.n_path, m, ptr(ch["points"]),
+            ch["offs"].ctypes.data_as(C.POINTER(C.c_size_t)), ptr(ch["gammas"]), G, ptr(pdf), ptr(err), ptr(stats), ws_ptr, nbytes,
+            self.stream), what))
         offs = ch["offs"]
         cut = lambda a: [[a[g * P + int(offs[i]):g * P + int(offs[i + 1])].reshape(ch["shapes"][i]).copy()    # noqa: E731
                           for i in range(m)] for g in range(G)]
@@ -1326,15 +1384,7 @@ class HipEngine:
         """hawkesjd_chain_cond from the origin (0, lambda_p, lambda_m) into snapshot rows [0, m) (mu) and [m, 2m) (cv) for the
         expiries of ch (tilted_chain_arrays with ttms).  The step grid is the fused drivers' (svmc_chain.hip expiry_grids), so the
         mu rows are those svmc_hawkesjd_chain_price_cmc steps at this seed."""
-        if int(nb_steps_per_year) <= 0:
-            raise ValueError("nb_steps_per_year must be positive")
-        nbs, dts, t0 = [], [], 0.0
-        for t in ch["ttms"]:
-            d = float(t) - t0
-            nb = int(d * float(int(nb_steps_per_year))) + 1
-            nbs.append(nb)
-            dts.append(d if nb == 1 else d / float(nb))
-            t0 = float(t)
+        nbs, dts = chain_step_grid(ch["ttms"], nb_steps_per_year)
         self.fill_state(0.0, float(params[6]), float(params[11]))         # SVMC_HAWKESJD_PARAMS: lambda_p, lambda_m
         self.hawkesjd_chain_cond(nbs, dts, params, seed, call_id, mu_row=0, cv_row=ch["m"])
 
@@ -1380,15 +1430,13 @@ class HipEngine:
         sh = strike_shifts(ch, shifts)
         est = _lib.load_est()
         what = "svmc_jump_sets_payoff_chain"
-        ws_ptr, nbytes = self._side_workspace(est.svmc_jump_sets_workspace_bytes, what, m, K, Q, "jump_sets_workspace")
+        ws_ptr, nbytes = self._side_workspace(est.svmc_jump_sets_workspace_bytes, (self.n_path, m, K, Q), "jump_sets_workspace", what)
         prices, stderrs = np.empty(max(Q * K, 1)), np.empty(max(Q * K, 1))
         stats, corr = np.empty(Q * m * TILTED_STATS_DOUBLES), np.empty(m)
-        dp = C.POINTER(C.c_double)
+        a = ch["args"]
         self._timed("jump_sets_payoff_kernel", lambda: _lib.check_ext(est.svmc_jump_sets_payoff_chain(
-            (C.c_void_p * m)(*ptrs), self.n_path, ch["forwards"].ctypes.data_as(dp), m, ch["strikes"].ctypes.data_as(dp),
-            ch["codes"].ctypes.data_as(C.POINTER(C.c_int8)), sh.ctypes.data_as(dp), ch["offs"].ctypes.data_as(C.POINTER(C.c_size_t)),
-            var.ctypes.data_as(dp), ch["gammas"].ctypes.data_as(dp), Q, int(bool(recenter)), prices.ctypes.data_as(dp),
-            stderrs.ctypes.data_as(dp), stats.ctypes.data_as(dp), corr.ctypes.data_as(dp), ws_ptr, nbytes, self.stream), what))
+            (C.c_void_p * m)(*ptrs), self.n_path, *a[:4], ptr(sh), a[4], ptr(var), *ch["gamma_args"], int(bool(recenter)), ptr(prices),
+            ptr(stderrs), ptr(stats), ptr(corr), ws_ptr, nbytes, self.stream), what))
         return tilted_results(prices[:Q * K], stderrs[:Q * K], stats, ch) + (corr,)
 
     def price_hawkesjd_chain_tilted_cond(self, ch: dict, params: np.ndarray, nb_steps_per_year: int, seed: int, call_id: int, gammas,
@@ -1420,33 +1468,18 @@ class HipEngine:
         out = [dict(price=p, stderr=e, **g) for p, e, g in zip(prices, stderrs, greeks)]
         return out, np.concatenate([stats, gstats[:, :, 3:4]], axis=2)
 
-    def _fused_cmc_call(self, ch: dict, call, kernel_name: str):
-        res, stats = np.empty((2, max(ch["total"], 1))), np.empty((ch["m"], CMC_STATS_DOUBLES))
-        dp = C.POINTER(C.c_double)
-        self._session_call(ch, lambda sess: call(sess, C.cast(res.ctypes.data, dp), C.cast(res.ctypes.data + res.strides[0], dp),
-                                                 stats.ctypes.data_as(dp)), kernel_name)
-        return [res[0, sl] for sl in ch["slices"]], [res[1, sl] for sl in ch["slices"]], cmc_stats_dicts(stats)
-
     def price_logsv_chain_cmc_fused(self, ch: dict, v0, theta, kappa1, kappa2, beta, volvol, etas, is_spot_measure,
                                     nb_steps_per_year, recenter: bool, seed: int, call_id: int):
         """logsv_mc_chain_pricer_conditional as ONE svmc_logsv_chain_price_cmc call on this engine's state; returns (prices,
         stderrs, stats) cut into expiries"""
-        etas = np.ascontiguousarray(etas, dtype=np.float64)
-        if etas.size != ch["m"]:
-            raise ValueError("vol_backbone_etas must have one entry per maturity")
-        return self._fused_cmc_call(ch, lambda sess, p, e, st: self.lib.svmc_logsv_chain_price_cmc(
-            sess, ch["ttms"], ch["forwards"], ch["discfactors"], etas.ctypes.data_as(C.POINTER(C.c_double)), ch["m"], ch["strikes"],
-            ch["codes"], ch["offsets"], float(v0), float(theta), float(kappa1), float(kappa2), float(beta), float(volvol),
-            int(bool(is_spot_measure)), int(nb_steps_per_year), int(bool(recenter)), int(seed), int(call_id), p, e, st),
-            "logsv_chain_cmc_kernel")
+        return self._price_chain_fused(ch, "logsv", "_cmc", (v0, theta, kappa1, kappa2, beta, volvol, etas, is_spot_measure),
+                                       nb_steps_per_year, int(bool(recenter)), seed, call_id)
 
     def price_heston_chain_cmc_fused(self, ch: dict, v0, theta, kappa, rho, volvol, nb_steps_per_year, recenter: bool, seed: int,
                                      call_id: int):
         """heston_mc_chain_pricer_conditional as ONE svmc_heston_chain_price_cmc call on this engine's state"""
-        return self._fused_cmc_call(ch, lambda sess, p, e, st: self.lib.svmc_heston_chain_price_cmc(
-            sess, ch["ttms"], ch["forwards"], ch["discfactors"], ch["m"], ch["strikes"], ch["codes"], ch["offsets"], float(v0),
-            float(theta), float(kappa), float(rho), float(volvol), int(nb_steps_per_year), int(bool(recenter)), int(seed),
-            int(call_id), p, e, st), "heston_chain_cmc_kernel")
+        return self._price_chain_fused(ch, "heston", "_cmc", (v0, theta, kappa, rho, volvol), nb_steps_per_year, int(bool(recenter)),
+                                       seed, call_id)
 
     # ---- conditional Monte Carlo Greeks (include/svmc.h, DESIGN.md row f13): delta, dual delta, gamma, dual gamma ----------------
     def conditional_greeks(self, forwards, discfactors, strikes: Sequence[np.ndarray], codes: Sequence[np.ndarray],
@@ -1457,66 +1490,40 @@ class HipEngine:
         ch = marshalled_chain(np.zeros(len(strikes)), forwards, discfactors, strikes, codes)
         m, K = ch["m"], ch["total"]
         mus, cvs = self._cond_row_ptrs(m, mu_rows, cv_rows)
-        nbytes = C.c_size_t(0)
-        _lib.check(self.lib.svmc_cmc_greeks_workspace_bytes(self.n_path, m, K, C.byref(nbytes)))
-        ws_ptr, _ = self.alloc_sums((nbytes.value + 7) // 8, "cmc_greeks_workspace")
+        ws_ptr, nbytes = self._side_workspace(self.lib.svmc_cmc_greeks_workspace_bytes, (self.n_path, m, K), "cmc_greeks_workspace")
         res, stats = np.empty((CMC_GREEKS_ROWS, max(K, 1))), np.empty((m, CMC_GREEKS_STATS_DOUBLES))
-        dp = C.POINTER(C.c_double)
         _lib.check(self.lib.svmc_cmc_greeks_chain(
-            (C.c_void_p * m)(*mus), (C.c_void_p * m)(*cvs), self.n_path, ch["forwards"], ch["discfactors"], m, ch["strikes"],
-            ch["codes"], ch["offsets"], int(bool(recenter)), res.ctypes.data_as(dp), stats.ctypes.data_as(dp), ws_ptr, nbytes.value,
-            self.stream))
-        return cmc_greeks_dict(res, ch["slices"]), cmc_greeks_stats_dicts(stats)
-
-    def _fused_cmc_greeks_call(self, ch: dict, call, kernel_name: str):
-        res, stats = np.empty((CMC_GREEKS_ROWS, max(ch["total"], 1))), np.empty((ch["m"], CMC_GREEKS_STATS_DOUBLES))
-        dp = C.POINTER(C.c_double)
-        self._session_call(ch, lambda sess: call(sess, res.ctypes.data_as(dp), stats.ctypes.data_as(dp)), kernel_name)
+            (C.c_void_p * m)(*mus), (C.c_void_p * m)(*cvs), self.n_path, *ch["args"][1:], int(bool(recenter)), ptr(res), ptr(stats),
+            ws_ptr, nbytes, self.stream))
         return cmc_greeks_dict(res, ch["slices"]), cmc_greeks_stats_dicts(stats)
 
     def price_logsv_chain_cmc_greeks_fused(self, ch: dict, v0, theta, kappa1, kappa2, beta, volvol, etas, is_spot_measure,
                                            nb_steps_per_year, recenter: bool, seed: int, call_id: int):
         """logsv_mc_chain_greeks_conditional as ONE svmc_logsv_chain_price_cmc_greeks call on this engine's state; returns
         (fields, stats) as conditional_greeks"""
-        etas = np.ascontiguousarray(etas, dtype=np.float64)
-        if etas.size != ch["m"]:
-            raise ValueError("vol_backbone_etas must have one entry per maturity")
-        return self._fused_cmc_greeks_call(ch, lambda sess, g, st: self.lib.svmc_logsv_chain_price_cmc_greeks(
-            sess, ch["ttms"], ch["forwards"], ch["discfactors"], etas.ctypes.data_as(C.POINTER(C.c_double)), ch["m"], ch["strikes"],
-            ch["codes"], ch["offsets"], float(v0), float(theta), float(kappa1), float(kappa2), float(beta), float(volvol),
-            int(bool(is_spot_measure)), int(nb_steps_per_year), int(bool(recenter)), int(seed), int(call_id), g, st),
-            "logsv_chain_cmc_kernel")
+        return self._price_chain_fused(ch, "logsv", "_cmc_greeks", (v0, theta, kappa1, kappa2, beta, volvol, etas, is_spot_measure),
+                                       nb_steps_per_year, int(bool(recenter)), seed, call_id)
 
     def price_heston_chain_cmc_greeks_fused(self, ch: dict, v0, theta, kappa, rho, volvol, nb_steps_per_year, recenter: bool,
                                             seed: int, call_id: int):
         """heston_mc_chain_greeks_conditional as ONE svmc_heston_chain_price_cmc_greeks call on this engine's state"""
-        return self._fused_cmc_greeks_call(ch, lambda sess, g, st: self.lib.svmc_heston_chain_price_cmc_greeks(
-            sess, ch["ttms"], ch["forwards"], ch["discfactors"], ch["m"], ch["strikes"], ch["codes"], ch["offsets"], float(v0),
-            float(theta), float(kappa), float(rho), float(volvol), int(nb_steps_per_year), int(bool(recenter)), int(seed),
-            int(call_id), g, st), "heston_chain_cmc_kernel")
+        return self._price_chain_fused(ch, "heston", "_cmc_greeks", (v0, theta, kappa, rho, volvol), nb_steps_per_year,
+                                       int(bool(recenter)), seed, call_id)
 
     # ---- many conditional jobs in one stepping launch and the parameter sensitivities (include/svmc.h, DESIGN.md row f14) ---------
     def chain_cmc_many(self, model: str, nb_steps: Sequence[int], dts: Sequence[float], params: np.ndarray, seeds: Sequence[int],
                        call_ids: Sequence[int], mode: int = 1, mu_row: int = 0) -> None:
         """svmc_logsv_chain_cmc_many (model "logsv", mode = is_spot_measure, params [J][6 + m]) or svmc_heston_chain_cmc_many
         ("heston", params [J][5]): expiry i of job j goes to snapshot rows mu_row + j m + i (mu) and mu_row + (J + j) m + i (cv)"""
-        if model not in ("logsv", "heston"):
-            raise ValueError(f"chain_cmc_many: unknown model {model!r}")
+        fn, modes = self._model_entry("chain_cmc_many", model, "chain_cmc_many", CMC_MODELS, mode, _flag)
         n_jobs, jobs = self._many_jobs(params, seeds, call_ids)
         m = len(nb_steps)
         nb = np.ascontiguousarray(nb_steps, dtype=np.int32)
         dt = np.ascontiguousarray(dts, dtype=np.float64)
         self.reserve_snapshots(mu_row + 2 * n_jobs * m)
-        nbytes = C.c_size_t(0)
-        _lib.check(self.lib.svmc_cmc_many_workspace_bytes(n_jobs, m, C.byref(nbytes)))
-        ws_ptr, _ = self.alloc_sums((nbytes.value + 7) // 8, "cmc_many_table")
-        head = (self.n_path, n_jobs, m, nb.ctypes.data_as(C.POINTER(C.c_int)), dt.ctypes.data_as(C.POINTER(C.c_double)), jobs[0])
-        tail = (jobs[1], jobs[2], self.path_offset, self.snapshot_ptr(mu_row), self.snapshot_ptr(mu_row + n_jobs * m), ws_ptr,
-                nbytes.value, self.stream)
-        if model == "logsv":
-            _lib.check(self.lib.svmc_logsv_chain_cmc_many(*head, int(bool(mode)), *tail))
-        else:
-            _lib.check(self.lib.svmc_heston_chain_cmc_many(*head, *tail))
+        ws_ptr, nbytes = self._side_workspace(self.lib.svmc_cmc_many_workspace_bytes, (n_jobs, m), "cmc_many_table")
+        _lib.check(fn(self.n_path, n_jobs, m, ptr(nb), ptr(dt), jobs[0], *modes, jobs[1], jobs[2], self.path_offset,
+                      self.snapshot_ptr(mu_row), self.snapshot_ptr(mu_row + n_jobs * m), ws_ptr, nbytes, self.stream))
 
     def conditional_sens(self, forwards, discfactors, strikes: Sequence[np.ndarray], codes: Sequence[np.ndarray], steps,
                          recenter: bool = True, up_rows=None, dn_rows=None, host_rows=None):
@@ -1529,62 +1536,51 @@ class HipEngine:
         P = h.size
         if host_rows is not None:
             self.reserve_snapshots(4 * P * m)
-            rows = [[[0] * m for _ in range(P)] for _ in range(4)]
-            r = 0
-            for a, block in enumerate(host_rows):
+            for a, block in enumerate(host_rows):                          # block a's job p sits in rows (a P + p) m ...
                 if len(block) != P or any(len(job) != m for job in block):
                     raise ValueError("one host array per (parameter, expiry) for each of mu_up, cv_up, mu_dn, cv_dn")
-                for p in range(P):
-                    for i in range(m):
-                        x = np.ascontiguousarray(block[p][i], dtype=np.float64)
-                        if x.shape != (self.n_path,):
-                            raise ValueError("a host row must hold one value per path of the engine")
-                        self.upload(self.snapshot_ptr(r), x)
-                        rows[a][p][i] = r
-                        r += 1
-            up_rows = [(rows[0][p], rows[1][p]) for p in range(P)]
-            dn_rows = [(rows[2][p], rows[3][p]) for p in range(P)]
+                self._upload_snapshot_rows([x for job in block for x in job], a * P * m)
+            job_rows = lambda a, p: list(range((a * P + p) * m, (a * P + p + 1) * m))               # noqa: E731
+            up_rows = [(job_rows(0, p), job_rows(1, p)) for p in range(P)]
+            dn_rows = [(job_rows(2, p), job_rows(3, p)) for p in range(P)]
         if up_rows is None or dn_rows is None or len(up_rows) != P or len(dn_rows) != P or \
                 any(len(mu) != m or len(cv) != m for mu, cv in list(up_rows) + list(dn_rows)):
             raise ValueError("one mu row and one cv row per expiry for each up / dn job of the P steps")
         ptrs = lambda which, jobs: (C.c_void_p * max(P * m, 1))(*[self.snapshot_ptr(r) for job in jobs for r in job[which]])  # noqa: E731
-        nbytes = C.c_size_t(0)
-        _lib.check(self.lib.svmc_cmc_sens_workspace_bytes(self.n_path, m, K, P, C.byref(nbytes)))
-        ws_ptr, _ = self.alloc_sums((nbytes.value + 7) // 8, "cmc_sens_workspace")
+        ws_ptr, nbytes = self._side_workspace(self.lib.svmc_cmc_sens_workspace_bytes, (self.n_path, m, K, P), "cmc_sens_workspace")
         sens = np.empty((max(P, 1), CMC_SENS_ROWS, max(K, 1)))
-        dp = C.POINTER(C.c_double)
         _lib.check(self.lib.svmc_cmc_sens_chain(
-            ptrs(0, up_rows), ptrs(1, up_rows), ptrs(0, dn_rows), ptrs(1, dn_rows), self.n_path, ch["forwards"], ch["discfactors"], m,
-            ch["strikes"], ch["codes"], ch["offsets"], P, h.ctypes.data_as(dp), int(bool(recenter)), sens.ctypes.data_as(dp), ws_ptr,
-            nbytes.value, self.stream))
+            ptrs(0, up_rows), ptrs(1, up_rows), ptrs(0, dn_rows), ptrs(1, dn_rows), self.n_path, *ch["args"][1:], P, ptr(h),
+            int(bool(recenter)), ptr(sens), ws_ptr, nbytes, self.stream))
         return sens[:P, :, :K], ch["slices"]
+
+    def _upload_snapshot_rows(self, arrays, first_row: int) -> None:
+        """host arrays of one value per path into consecutive snapshot rows from first_row (reserved by the caller)"""
+        for r, x in enumerate(arrays, first_row):
+            a = np.ascontiguousarray(x, dtype=np.float64)
+            if a.shape != (self.n_path,):
+                raise ValueError("a host row must hold one value per path of the engine")
+            self.upload(self.snapshot_ptr(r), a)
 
     def price_chain_cmc_many_fused(self, ch: dict, model: str, params: np.ndarray, seeds: Sequence[int], call_ids: Sequence[int],
                                    mode: int, nb_steps_per_year: int, recenter: bool):
         """J conditional jobs of one chain as ONE svmc_logsv_chain_price_cmc_many (model "logsv", mode = is_spot_measure, params
         [J][6 + m]) or svmc_heston_chain_price_cmc_many ("heston", params [J][5]) call on this engine's session, J at most
         MANY_MAX_JOBS: per job the (prices, stderrs, stats) of the single fused call with its (seed, call id)"""
-        if model not in ("logsv", "heston"):
-            raise ValueError(f"price_chain_cmc_many_fused: unknown model {model!r}")
+        fn, modes = self._model_entry("price_chain_cmc_many_fused", model, "chain_price_cmc_many", CMC_MODELS, mode, _flag)
         n_jobs, jobs = self._many_jobs(params, seeds, call_ids)
         res, stats = np.empty((2, n_jobs, max(ch["total"], 1))), np.empty((n_jobs, ch["m"], CMC_STATS_DOUBLES))
-        dp = C.POINTER(C.c_double)
-        fn = {"logsv": self.lib.svmc_logsv_chain_price_cmc_many, "heston": self.lib.svmc_heston_chain_price_cmc_many}[model]
-        modes = (int(bool(mode)),) if model == "logsv" else ()
         self._session_call(ch, lambda sess: fn(
-            sess, ch["ttms"], ch["forwards"], ch["discfactors"], ch["m"], ch["strikes"], ch["codes"], ch["offsets"], n_jobs, *jobs, *modes,
-            int(nb_steps_per_year), int(bool(recenter)), C.cast(res.ctypes.data, dp), C.cast(res.ctypes.data + res.strides[0], dp),
-            stats.ctypes.data_as(dp)), f"{model}_chain_cond_many_kernel")
-        return [([res[0, j, sl] for sl in ch["slices"]], [res[1, j, sl] for sl in ch["slices"]], cmc_stats_dicts(stats[j]))
-                for j in range(n_jobs)]
+            sess, *ch["args"], n_jobs, *jobs, *modes, int(nb_steps_per_year), int(bool(recenter)), row_ptr(res, 0), row_ptr(res, 1),
+            ptr(stats)), f"{model}_chain_cond_many_kernel")
+        return [rows + (cmc_stats_dicts(st),) for rows, st in zip(expiry_rows_per_job(res, ch["slices"]), stats)]
 
     def price_chain_cmc_sens_fused(self, ch: dict, model: str, rows: np.ndarray, steps: np.ndarray, mode: int, nb_steps_per_year: int,
                                    recenter: bool, seed: int, call_id: int):
         """svmc_logsv_chain_price_cmc_sens (model "logsv", mode = is_spot_measure, rows [1 + 2P][6 + m]) or
         svmc_heston_chain_price_cmc_sens ("heston", rows [1 + 2P][5]) on this engine's session: the job table's rows on ONE (seed,
         call id).  Returns (fields, stats) as conditional_greeks for the base job, and sens [P][CMC_SENS_ROWS][K]."""
-        if model not in ("logsv", "heston"):
-            raise ValueError(f"price_chain_cmc_sens_fused: unknown model {model!r}")
+        fn, modes = self._model_entry("price_chain_cmc_sens_fused", model, "chain_price_cmc_sens", CMC_MODELS, mode, _flag)
         rows = np.ascontiguousarray(rows, dtype=np.float64)
         h = np.ascontiguousarray(steps, dtype=np.float64).ravel()
         P, K = h.size, max(ch["total"], 1)
@@ -1592,13 +1588,9 @@ class HipEngine:
             raise ValueError("the job table has one base row and an up and a dn row per step")
         res, stats = np.empty((CMC_GREEKS_ROWS, K)), np.empty((ch["m"], CMC_GREEKS_STATS_DOUBLES))
         sens = np.empty((max(P, 1), CMC_SENS_ROWS, K))
-        dp = C.POINTER(C.c_double)
-        fn = {"logsv": self.lib.svmc_logsv_chain_price_cmc_sens, "heston": self.lib.svmc_heston_chain_price_cmc_sens}[model]
-        modes = (int(bool(mode)),) if model == "logsv" else ()
         self._session_call(ch, lambda sess: fn(
-            sess, ch["ttms"], ch["forwards"], ch["discfactors"], ch["m"], ch["strikes"], ch["codes"], ch["offsets"], P,
-            rows.ctypes.data_as(dp), h.ctypes.data_as(dp), *modes, int(nb_steps_per_year), int(bool(recenter)), int(seed), int(call_id),
-            res.ctypes.data_as(dp), stats.ctypes.data_as(dp), sens.ctypes.data_as(dp)), f"{model}_chain_cond_many_kernel")
+            sess, *ch["args"], P, ptr(rows), ptr(h), *modes, int(nb_steps_per_year), int(bool(recenter)), int(seed), int(call_id),
+            ptr(res), ptr(stats), ptr(sens)), f"{model}_chain_cond_many_kernel")
         return cmc_greeks_dict(res, ch["slices"]), cmc_greeks_stats_dicts(stats), sens[:P]
 
     # ---- the conditional calibration objective: parameter sets of one chain on one replayed graph (include/svmc.h, row f15) ------
@@ -1608,23 +1600,17 @@ class HipEngine:
         "logsv", mode = is_spot_measure, params [P][6 + m]) or svmc_heston_chain_price_cmc_sets ("heston", params [P][5]) call on
         this engine's session -- one graph replay.  Per set (prices, stderrs, ivols or None, stats), the first three cut into
         expiries; ch is marshalled once per chain content (marshalled_chain)."""
-        if model not in ("logsv", "heston"):
-            raise ValueError(f"price_chain_cmc_sets_fused: unknown model {model!r}")
+        fn, modes = self._model_entry("price_chain_cmc_sets_fused", model, "chain_price_cmc_sets", CMC_MODELS, mode, _flag)
         params = np.ascontiguousarray(params, dtype=np.float64)
         if params.ndim != 2 or params.shape[1] != (6 + ch["m"] if model == "logsv" else 5):
             raise ValueError("one row per parameter set: [6 + n_expiries] for logsv, [5] for heston")
         P, K = params.shape[0], max(ch["total"], 1)
-        res, stats = np.empty((3, P, K)), np.empty((P, ch["m"], CMC_STATS_DOUBLES))
-        dp = C.POINTER(C.c_double)
-        row = lambda r: C.cast(res.ctypes.data + r * res.strides[0], dp)             # noqa: E731
-        fn = {"logsv": self.lib.svmc_logsv_chain_price_cmc_sets, "heston": self.lib.svmc_heston_chain_price_cmc_sets}[model]
-        modes = (int(bool(mode)),) if model == "logsv" else ()
+        res, stats = np.empty((3 if want_ivols else 2, P, K)), np.empty((P, ch["m"], CMC_STATS_DOUBLES))
         sess = self.fused_chain_session(ch["m"], ch["total"])
-        _lib.check(fn(sess, ch["ttms"], ch["forwards"], ch["discfactors"], ch["m"], ch["strikes"], ch["codes"], ch["offsets"], P,
-                      params.ctypes.data_as(dp), *modes, int(nb_steps_per_year), int(bool(recenter)), int(seed), int(call_id), row(0),
-                      row(1), stats.ctypes.data_as(dp), row(2) if want_ivols else None))
-        cut = lambda r, q: [res[r, q, sl] for sl in ch["slices"]]                    # noqa: E731
-        return [(cut(0, q), cut(1, q), cut(2, q) if want_ivols else None, cmc_stats_dicts(stats[q])) for q in range(P)]
+        _lib.check(fn(sess, *ch["args"], P, ptr(params), *modes, int(nb_steps_per_year), int(bool(recenter)), int(seed), int(call_id),
+                      row_ptr(res, 0), row_ptr(res, 1), ptr(stats), row_ptr(res, 2) if want_ivols else None))
+        return [rows[:2] + (rows[2] if want_ivols else None, cmc_stats_dicts(st))
+                for rows, st in zip(expiry_rows_per_job(res, ch["slices"]), stats)]
 
     def use_graphs(self, enable: bool) -> None:
         """whether the fused session's graph drivers replay a captured graph (default) or issue their launches directly"""
@@ -1660,12 +1646,7 @@ class HipEngine:
             if len(jobs) != 1 + 2 * P or any(len(job) != m for job in jobs):
                 raise ValueError("one host array per expiry for the base job and for each up / dn job of the P steps")
             self.reserve_snapshots((1 + 2 * P) * m)
-            for j, job in enumerate(jobs):
-                for i, x in enumerate(job):
-                    a = np.ascontiguousarray(x, dtype=np.float64)
-                    if a.shape != (self.n_path,):
-                        raise ValueError("a host row must hold one value per path of the engine")
-                    self.upload(self.snapshot_ptr(j * m + i), a)
+            self._upload_snapshot_rows([x for job in jobs for x in job], 0)
             base_rows = list(range(m))
             up_rows = [list(range((1 + 2 * p) * m, (2 + 2 * p) * m)) for p in range(P)]
             dn_rows = [list(range((2 + 2 * p) * m, (3 + 2 * p) * m)) for p in range(P)]
@@ -1679,17 +1660,13 @@ class HipEngine:
         for j, rows in enumerate(job_rows):
             for i, r in enumerate(rows):
                 self.spot_sums(self.snapshot_ptr(r), float(f[i]), spot_ptr + 16 * (j * m + i))
-        nbytes = C.c_size_t(0)
-        _lib.check(self.lib.svmc_greeks_payoff_workspace_bytes(self.n_path, m, K, P, C.byref(nbytes)))
-        ws_ptr, _ = self.alloc_sums((nbytes.value + 7) // 8, "greeks_workspace")
+        ws_ptr, nbytes = self._side_workspace(self.lib.svmc_greeks_payoff_workspace_bytes, (self.n_path, m, K, P), "greeks_workspace")
         base_out, sens_out = np.empty((len(GREEKS_BASE_FIELDS), max(K, 1))), np.empty((max(P, 1), len(GREEKS_SENS_FIELDS), max(K, 1)))
-        dp = C.POINTER(C.c_double)
         ptrs = lambda rows: (C.c_void_p * max(len(rows), 1))(*[self.snapshot_ptr(r) for r in rows])      # noqa: E731
         _lib.check(self.lib.svmc_greeks_payoff_chain(
             ptrs(job_rows[0]), ptrs([r for rows in up_rows for r in rows]), ptrs([r for rows in dn_rows for r in rows]), self.n_path,
-            ch["forwards"], ch["discfactors"], m, ch["strikes"], ch["codes"], ch["offsets"], P, h.ctypes.data_as(dp), spot_ptr,
-            base_out.ctypes.data_as(dp), sens_out.ctypes.data_as(dp), ws_ptr, nbytes.value, self.stream))
-        out = {field: [base_out[r, sl] for sl in ch["slices"]] for r, field in enumerate(GREEKS_BASE_FIELDS)}
+            *ch["args"][1:], P, ptr(h), spot_ptr, ptr(base_out), ptr(sens_out), ws_ptr, nbytes, self.stream))
+        out = dict(zip(GREEKS_BASE_FIELDS, expiry_rows(base_out, ch["slices"])))
         for r, field in enumerate(GREEKS_SENS_FIELDS):
             out[field] = [[sens_out[p, r, sl] for sl in ch["slices"]] for p in range(P)]
         out["spot_sums"] = self.download(spot_ptr, 2 * m * (1 + 2 * P)).reshape(1 + 2 * P, m, 2)
@@ -1700,22 +1677,17 @@ class HipEngine:
         """svmc_logsv_chain_price_greeks (model "logsv", mode = is_spot_measure, rows [1 + 2P][6 + m]) or
         svmc_heston_chain_price_greeks ("heston", mode = scheme code, rows [1 + 2P][5]) on this engine's session: the job table's
         rows on ONE (seed, call id).  Returns (prices [m] -> [K_i], stderrs the same, base [5][K], sens [P][3][K])."""
-        if model not in ("logsv", "heston"):
-            raise ValueError(f"price_chain_greeks_fused: unknown model {model!r}")
+        fn, modes = self._model_entry("price_chain_greeks_fused", model, "chain_price_greeks", GREEKS_MODELS, mode)
         rows = np.ascontiguousarray(rows, dtype=np.float64)
         h = np.ascontiguousarray(steps, dtype=np.float64).ravel()
         P, K = h.size, max(ch["total"], 1)
         if rows.ndim != 2 or rows.shape[0] != 1 + 2 * P:
             raise ValueError("the job table has one base row and an up and a dn row per step")
         res, base, sens = np.empty((2, K)), np.empty((len(GREEKS_BASE_FIELDS), K)), np.empty((max(P, 1), len(GREEKS_SENS_FIELDS), K))
-        dp = C.POINTER(C.c_double)
-        fn = {"logsv": self.lib.svmc_logsv_chain_price_greeks, "heston": self.lib.svmc_heston_chain_price_greeks}[model]
         self._session_call(ch, lambda sess: fn(
-            sess, ch["ttms"], ch["forwards"], ch["discfactors"], ch["m"], ch["strikes"], ch["codes"], ch["offsets"], P,
-            rows.ctypes.data_as(dp), h.ctypes.data_as(dp), int(mode), int(nb_steps_per_year), int(seed), int(call_id),
-            C.cast(res.ctypes.data, dp), C.cast(res.ctypes.data + res.strides[0], dp), base.ctypes.data_as(dp), sens.ctypes.data_as(dp)),
-            f"{model}_chain_rng_many_kernel")
-        return [res[0, sl] for sl in ch["slices"]], [res[1, sl] for sl in ch["slices"]], base, sens[:P]
+            sess, *ch["args"], P, ptr(rows), ptr(h), *modes, int(nb_steps_per_year), int(seed), int(call_id), row_ptr(res, 0),
+            row_ptr(res, 1), ptr(base), ptr(sens)), f"{model}_chain_rng_many_kernel")
+        return expiry_rows(res, ch["slices"]) + (base, sens[:P])
 
     def il_payoffs(self, p1, p0, pa, pb, notional=1000000, snap_row: Optional[int] = None, return_pieces: bool = False):
         """the Monte Carlo impermanent loss of the ranges [pa, pb] opened at p0, at the forwards p1, from the resident
@@ -1726,13 +1698,10 @@ class HipEngine:
         from .pricers.il_pricer import IL_OUT_DOUBLES, il_cases, il_mc_results
         cases, shape = il_cases(p1, p0, pa, pb, notional)
         n = cases.shape[0]
-        nbytes = C.c_size_t(0)
-        _lib.check(self.lib.svmc_il_payoff_workspace_bytes(self.n_path, n, C.byref(nbytes)))
-        ws_ptr, _ = self.alloc_sums((nbytes.value + 7) // 8, "il_workspace")
+        ws_ptr, nbytes = self._side_workspace(self.lib.svmc_il_payoff_workspace_bytes, (self.n_path, n), "il_workspace")
         out = np.empty((n, IL_OUT_DOUBLES))
-        dp = C.POINTER(C.c_double)
         _lib.check(self.lib.svmc_il_payoff(self.x.ptr if snap_row is None else self.snapshot_ptr(snap_row), self.n_path,
-                                           cases.ctypes.data_as(dp), n, out.ctypes.data_as(dp), ws_ptr, nbytes.value, self.stream))
+                                           ptr(cases), n, ptr(out), ws_ptr, nbytes, self.stream))
         return il_mc_results(out, shape, return_pieces)
 
     def price_hawkesjd_chain_tilted_fused(self, ch: dict, params: np.ndarray, nb_steps_per_year: int, seed: int, call_id: int,
@@ -1743,13 +1712,10 @@ class HipEngine:
         caller who wants both measures puts 0 among the gammas"""
         params = np.ascontiguousarray(params, dtype=np.float64)
         m, K, G = ch["m"], ch["total"], ch["gammas"].size
-        dp = C.POINTER(C.c_double)
         prices, stderrs, stats = np.empty(max(G * K, 1)), np.empty(max(G * K, 1)), np.empty(G * m * TILTED_STATS_DOUBLES)
         self._session_call(ch, lambda sess: self.lib.svmc_hawkesjd_chain_price_tilted(
-            sess, ch["ttms"].ctypes.data_as(dp), ch["forwards"].ctypes.data_as(dp), m, ch["strikes"].ctypes.data_as(dp),
-            ch["codes"].ctypes.data_as(C.POINTER(C.c_int8)), ch["offs"].ctypes.data_as(C.POINTER(C.c_size_t)), params.ctypes.data_as(dp),
-            int(nb_steps_per_year), int(seed), int(call_id), ch["gammas"].ctypes.data_as(dp), G, int(bool(recenter)),
-            prices.ctypes.data_as(dp), stderrs.ctypes.data_as(dp), stats.ctypes.data_as(dp)), "hawkesjd_chain_rng_kernel")
+            sess, ch["ttms_arg"], *ch["args"], ptr(params), int(nb_steps_per_year), int(seed), int(call_id), *ch["gamma_args"],
+            int(bool(recenter)), ptr(prices), ptr(stderrs), ptr(stats)), "hawkesjd_chain_rng_kernel")
         return tilted_results(prices[:G * K], stderrs[:G * K], stats, ch)
 
     def price_hawkesjd_chain_tilted_many_fused(self, ch: dict, params: np.ndarray, nb_steps_per_year: int, seeds: Sequence[int],
@@ -1763,15 +1729,12 @@ class HipEngine:
         if gammas.ndim != 2 or gammas.shape[0] != n_jobs:
             raise ValueError("one seed, one call id and one row of gammas per job")
         m, K, G = ch["m"], ch["total"], gammas.shape[1]
-        dp = C.POINTER(C.c_double)
         prices, stderrs = np.empty((n_jobs, max(G * K, 1))), np.empty((n_jobs, max(G * K, 1)))
         stats = np.empty((n_jobs, G * m * TILTED_STATS_DOUBLES))
         sess = self.fused_chain_session(m, K)
         _lib.check(self.lib.svmc_hawkesjd_chain_price_tilted_many(
-            sess, ch["ttms"].ctypes.data_as(dp), ch["forwards"].ctypes.data_as(dp), m, ch["strikes"].ctypes.data_as(dp),
-            ch["codes"].ctypes.data_as(C.POINTER(C.c_int8)), ch["offs"].ctypes.data_as(C.POINTER(C.c_size_t)), n_jobs, *jobs,
-            int(nb_steps_per_year), gammas.ctypes.data_as(dp), G, int(bool(recenter)), prices.ctypes.data_as(dp),
-            stderrs.ctypes.data_as(dp), stats.ctypes.data_as(dp)))
+            sess, ch["ttms_arg"], *ch["args"], n_jobs, *jobs, int(nb_steps_per_year), ptr(gammas), G, int(bool(recenter)), ptr(prices),
+            ptr(stderrs), ptr(stats)))
         # the C rows are [G K] with no padding; the host arrays above are padded to one double for an empty chain only
         out = []
         for j in range(n_jobs):

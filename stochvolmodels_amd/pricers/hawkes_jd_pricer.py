@@ -68,9 +68,9 @@ from ..mc_chain import chain_shaped, check_many_args, many_job_chunks, many_job_
 from ..utils import mgf_pricer as mgfp
 from ..utils.calibration import ImpliedVolObjective, chain_calibration_weights
 from ..utils.config import VariableType
-from ..utils.funcs import next_rng_call, time_grid_steps, timer, to_flat_np_array
+from ..utils.funcs import chain_step_grid, next_rng_call, time_grid_steps, timer, to_flat_np_array
 from .logsv_pricer import (check_conditional_request, conditional_greeks_shaped, conditional_log_return_pdf,
-                           mixture_log_return_pdf)
+                           mixture_log_return_pdf, refuse_sharded_paths)
 from .model_pricer import ModelParams, ModelPricer
 
 MAX_PHI = 500
@@ -149,7 +149,27 @@ class HawkesJDParams(ModelParams):
 
 def params_block(**kw) -> np.ndarray:
     """the SVMC_HAWKESJD_PARAMS doubles of the C ABI from keyword parameters (extra keywords are ignored)"""
-    return np.array([float(kw[k]) for k in PARAM_NAMES], dtype=np.float64)
+    return params_block_of(kw)
+
+
+def params_block_of(values) -> np.ndarray:
+    """params_block from a mapping that holds the sixteen names among others: a pricer passes its locals()"""
+    return np.array([float(values[k]) for k in PARAM_NAMES], dtype=np.float64)
+
+
+def forwards_triples(stats) -> list:
+    """what return_forwards=True adds: per gamma (or set) the (normalizers, gamma_forwards, stats) of stats [n_expiries, 8]"""
+    return [(st[:, 0].copy(), st[:, 2].copy(), st) for st in stats]
+
+
+def _at_one_gamma(gammas_pricer, args: dict):
+    """a *_gammas pricer at the ONE gamma of a single-gamma wrapper, so the two agree bit for bit; args: the wrapper's locals()"""
+    args = dict(args)
+    args.update(args.pop("kwargs"))
+    risk_premia_gamma = args.pop("risk_premia_gamma")
+    if risk_premia_gamma is None:
+        raise ValueError("risk_premia_gamma must be set for the risk-premia pricer")
+    return gammas_pricer(risk_premia_gammas=[risk_premia_gamma], **args)
 
 
 def _check_variable_type(variable_type) -> None:
@@ -821,9 +841,7 @@ def hawkesjd_mc_chain_pricer(ttms: np.ndarray, forwards: np.ndarray, discfactors
         raise NotImplementedError("hawkesjd_mc_chain_pricer: sharded runs go through the C ABI (svmc_session_set_comm)")
     strikes_ttms = [np.asarray(k, dtype=np.float64) for k in strikes_ttms]
     optiontypes_ttms = [np.asarray(t) for t in optiontypes_ttms]
-    block = params_block(lambda_p=lambda_p, lambda_m=lambda_m, mu=mu, sigma=sigma, shift_p=shift_p, mean_p=mean_p,
-                         shift_m=shift_m, mean_m=mean_m, theta_p=theta_p, kappa_p=kappa_p, beta1_p=beta1_p, beta2_p=beta2_p,
-                         theta_m=theta_m, kappa_m=kappa_m, beta1_m=beta1_m, beta2_m=beta2_m)
+    block = params_block_of(locals())
     eng = get_engine(int(nb_path))
     rng_seed, call_id = next_rng_call(seed)
     ch = marshalled_chain(np.asarray(ttms), np.asarray(forwards), np.asarray(discfactors), strikes_ttms,
@@ -850,9 +868,7 @@ def hawkesjd_mc_chain_pricer_conditional(ttms: np.ndarray, forwards: np.ndarray,
     in the plain pricer.  'C' / 'P', LOG_RETURN and one GPU only (logsv_pricer.check_conditional_request).  Not in the reference
     API."""
     codes = check_conditional_request("hawkesjd_mc_chain_pricer_conditional", variable_type, comm, devices, optiontypes_ttms)
-    block = params_block(lambda_p=lambda_p, lambda_m=lambda_m, mu=mu, sigma=sigma, shift_p=shift_p, mean_p=mean_p,
-                         shift_m=shift_m, mean_m=mean_m, theta_p=theta_p, kappa_p=kappa_p, beta1_p=beta1_p, beta2_p=beta2_p,
-                         theta_m=theta_m, kappa_m=kappa_m, beta1_m=beta1_m, beta2_m=beta2_m)
+    block = params_block_of(locals())
     rng_seed, call_id = next_rng_call(seed)
     ch = marshalled_chain(ttms, forwards, discfactors, strikes_ttms, codes)
     prices, stderrs, stats = get_engine(int(nb_path)).price_hawkesjd_chain_cmc_fused(ch, block, int(nb_steps_per_year), recenter,
@@ -881,9 +897,7 @@ def hawkesjd_mc_chain_greeks_conditional(ttms: np.ndarray, forwards: np.ndarray,
     codes = check_conditional_request(who, variable_type, comm, devices, optiontypes_ttms)
     if wrt is None or isinstance(wrt, str) or len(wrt) > 0:
         raise NotImplementedError(f"{who}: wrt=: parameter sensitivities of the Hawkes conditional estimator are not covered")
-    block = params_block(lambda_p=lambda_p, lambda_m=lambda_m, mu=mu, sigma=sigma, shift_p=shift_p, mean_p=mean_p,
-                         shift_m=shift_m, mean_m=mean_m, theta_p=theta_p, kappa_p=kappa_p, beta1_p=beta1_p, beta2_p=beta2_p,
-                         theta_m=theta_m, kappa_m=kappa_m, beta1_m=beta1_m, beta2_m=beta2_m)
+    block = params_block_of(locals())
     rng_seed, call_id = next_rng_call(seed)
     ch = marshalled_chain(ttms, forwards, discfactors, strikes_ttms, codes)
     fields, stats = get_engine(int(nb_path)).price_hawkesjd_chain_cmc_greeks_fused(ch, block, int(nb_steps_per_year), recenter,
@@ -922,16 +936,14 @@ def hawkesjd_mc_chain_pricer_with_risk_premia_gammas(ttms: np.ndarray, forwards:
     strikes_ttms = [np.asarray(k, dtype=np.float64) for k in strikes_ttms]
     codes = [tilted_type_codes(t) for t in optiontypes_ttms]                # ValueError("not implemented")
     ch = tilted_chain_arrays(forwards, strikes_ttms, codes, risk_premia_gammas, ttms=ttms)
-    block = params_block(lambda_p=lambda_p, lambda_m=lambda_m, mu=mu, sigma=sigma, shift_p=shift_p, mean_p=mean_p,
-                         shift_m=shift_m, mean_m=mean_m, theta_p=theta_p, kappa_p=kappa_p, beta1_p=beta1_p, beta2_p=beta2_p,
-                         theta_m=theta_m, kappa_m=kappa_m, beta1_m=beta1_m, beta2_m=beta2_m)
+    block = params_block_of(locals())
     eng = get_engine(int(nb_path))
     rng_seed, call_id = next_rng_call(seed)
     prices, stderrs, stats = eng.price_hawkesjd_chain_tilted_fused(ch, block, int(nb_steps_per_year), rng_seed, call_id,
                                                                    ch["gammas"], bool(recenter_forward))
     if not return_forwards:
         return prices, stderrs
-    return prices, stderrs, [(st[:, 0].copy(), st[:, 2].copy(), st) for st in stats]
+    return prices, stderrs, forwards_triples(stats)
 
 
 def hawkesjd_mc_chain_pricer_with_risk_premia(ttms: np.ndarray, forwards: np.ndarray, discfactors: np.ndarray,
@@ -942,15 +954,7 @@ def hawkesjd_mc_chain_pricer_with_risk_premia(ttms: np.ndarray, forwards: np.nda
     """hawkesjd_mc_chain_pricer_with_risk_premia_gammas at ONE gamma, so the two agree bit for bit: (prices, stderrs) per
     expiry, with return_forwards=True also (normalizers, gamma_forwards, stats).  kwargs: the model parameters (and
     variable_type=, comm=, devices=) of that function."""
-    if risk_premia_gamma is None:
-        raise ValueError("risk_premia_gamma must be set for the risk-premia pricer")
-    out = hawkesjd_mc_chain_pricer_with_risk_premia_gammas(ttms=ttms, forwards=forwards, discfactors=discfactors,
-                                                           strikes_ttms=strikes_ttms, optiontypes_ttms=optiontypes_ttms,
-                                                           risk_premia_gammas=[risk_premia_gamma], nb_path=nb_path,
-                                                           nb_steps_per_year=nb_steps_per_year, seed=seed,
-                                                           recenter_forward=recenter_forward, return_forwards=return_forwards,
-                                                           **kwargs)
-    return tuple(o[0] for o in out)
+    return tuple(o[0] for o in _at_one_gamma(hawkesjd_mc_chain_pricer_with_risk_premia_gammas, locals()))
 
 
 def hawkesjd_mc_chain_pricer_conditional_with_risk_premia_gammas(ttms: np.ndarray, forwards: np.ndarray, discfactors: np.ndarray,
@@ -984,16 +988,14 @@ def hawkesjd_mc_chain_pricer_conditional_with_risk_premia_gammas(ttms: np.ndarra
                                       optiontypes_ttms)
     strikes_ttms = [np.asarray(k, dtype=np.float64) for k in strikes_ttms]
     ch = tilted_chain_arrays(forwards, strikes_ttms, codes, risk_premia_gammas, ttms=ttms)
-    block = params_block(lambda_p=lambda_p, lambda_m=lambda_m, mu=mu, sigma=sigma, shift_p=shift_p, mean_p=mean_p,
-                         shift_m=shift_m, mean_m=mean_m, theta_p=theta_p, kappa_p=kappa_p, beta1_p=beta1_p, beta2_p=beta2_p,
-                         theta_m=theta_m, kappa_m=kappa_m, beta1_m=beta1_m, beta2_m=beta2_m)
+    block = params_block_of(locals())
     eng = get_engine(int(nb_path))
     rng_seed, call_id = next_rng_call(seed)
     prices, stderrs, stats = eng.price_hawkesjd_chain_tilted_cond(ch, block, int(nb_steps_per_year), rng_seed, call_id, ch["gammas"],
                                                                   bool(recenter_forward))
     if not return_forwards:
         return prices, stderrs
-    return prices, stderrs, [(st[:, 0].copy(), st[:, 2].copy(), st) for st in stats]
+    return prices, stderrs, forwards_triples(stats)
 
 
 def jump_sets_request(sigmas, risk_premia_gammas) -> Tuple[np.ndarray, np.ndarray]:
@@ -1010,18 +1012,8 @@ def jump_sets_request(sigmas, risk_premia_gammas) -> Tuple[np.ndarray, np.ndarra
     return s, g
 
 
-def jump_step_grid(ttms, nb_steps_per_year: int) -> Tuple[List[int], List[float]]:
-    """(steps, dt) per expiry: the fused drivers' grid, the one engine.step_hawkesjd_chain_cond_rows steps on"""
-    if int(nb_steps_per_year) <= 0:
-        raise ValueError("nb_steps_per_year must be positive")
-    nbs, dts, t0 = [], [], 0.0
-    for t in np.asarray(ttms, dtype=np.float64).ravel():
-        d = float(t) - t0
-        nb = int(d * float(int(nb_steps_per_year))) + 1
-        nbs.append(nb)
-        dts.append(d if nb == 1 else d / float(nb))
-        t0 = float(t)
-    return nbs, dts
+# (steps, dt) per expiry: the fused drivers' grid, the one engine.step_hawkesjd_chain_cond_rows steps on
+jump_step_grid = chain_step_grid
 
 
 def jump_sets_variances(sigma: float, nb_steps: Sequence[int], dts: Sequence[float]) -> np.ndarray:
@@ -1084,7 +1076,7 @@ class HawkesJumpRows:
                                                            a_ptrs=self.row_ptrs())
             prices += p
             stderrs += e
-            extra += [(st[:, 0].copy(), st[:, 2].copy(), st) for st in stats]
+            extra += forwards_triples(stats)
         return (prices, stderrs, extra) if return_forwards else (prices, stderrs)
 
     def free(self) -> None:
@@ -1103,16 +1095,12 @@ def hawkesjd_jump_rows(ttms: np.ndarray, lambda_p: float, lambda_m: float, mu: f
     hawkesjd_mc_chain_pricer_conditional(_with_risk_premia) at this seed (streams 9 and 10).  sigma and risk_premia_gamma are
     accepted and unused.  Returns a HawkesJumpRows; one GPU only (NotImplementedError).  Chains longer than 16 expiries step in
     launches of 16."""
-    who = "hawkesjd_jump_rows"
-    if devices is not None or (comm or svdist.get_default_comm()).world > 1:
-        raise NotImplementedError(f"{who}: sharded paths (comm.world > 1, devices=) are not covered")
+    refuse_sharded_paths("hawkesjd_jump_rows", comm, devices)
     t = np.ascontiguousarray(np.asarray(ttms, dtype=np.float64)).ravel()
     if t.size < 1:
         raise ValueError("at least one expiry")
     nbs, dts = jump_step_grid(t, nb_steps_per_year)
-    block = params_block(lambda_p=lambda_p, lambda_m=lambda_m, mu=mu, sigma=0.0, shift_p=shift_p, mean_p=mean_p, shift_m=shift_m,
-                         mean_m=mean_m, theta_p=theta_p, kappa_p=kappa_p, beta1_p=beta1_p, beta2_p=beta2_p, theta_m=theta_m,
-                         kappa_m=kappa_m, beta1_m=beta1_m, beta2_m=beta2_m)
+    block = params_block_of(dict(locals(), sigma=0.0))
     eng = get_engine(int(nb_path))
     rng_seed, call_id = next_rng_call(seed)
     m, n = t.size, int(nb_path)
@@ -1163,13 +1151,7 @@ def hawkesjd_mc_chain_pricer_conditional_with_risk_premia(ttms: np.ndarray, forw
     """hawkesjd_mc_chain_pricer_conditional_with_risk_premia_gammas at ONE gamma, so the two agree bit for bit: (prices, stderrs)
     per expiry, with return_forwards=True also (normalizers, gamma_forwards, stats).  kwargs: the model parameters (and
     variable_type=, comm=, devices=) of that function."""
-    if risk_premia_gamma is None:
-        raise ValueError("risk_premia_gamma must be set for the risk-premia pricer")
-    out = hawkesjd_mc_chain_pricer_conditional_with_risk_premia_gammas(
-        ttms=ttms, forwards=forwards, discfactors=discfactors, strikes_ttms=strikes_ttms, optiontypes_ttms=optiontypes_ttms,
-        risk_premia_gammas=[risk_premia_gamma], nb_path=nb_path, nb_steps_per_year=nb_steps_per_year, seed=seed,
-        recenter_forward=recenter_forward, return_forwards=return_forwards, **kwargs)
-    return tuple(o[0] for o in out)
+    return tuple(o[0] for o in _at_one_gamma(hawkesjd_mc_chain_pricer_conditional_with_risk_premia_gammas, locals()))
 
 
 def hawkesjd_mc_chain_greeks_conditional_with_risk_premia_gammas(ttms: np.ndarray, forwards: np.ndarray, discfactors: np.ndarray,
@@ -1208,9 +1190,7 @@ def hawkesjd_mc_chain_greeks_conditional_with_risk_premia_gammas(ttms: np.ndarra
         raise NotImplementedError(f"{who}: wrt=: parameter sensitivities under the risk-premia kernel are not covered")
     strikes_ttms = [np.asarray(k, dtype=np.float64) for k in strikes_ttms]
     ch = tilted_chain_arrays(forwards, strikes_ttms, codes, risk_premia_gammas, ttms=ttms)
-    block = params_block(lambda_p=lambda_p, lambda_m=lambda_m, mu=mu, sigma=sigma, shift_p=shift_p, mean_p=mean_p,
-                         shift_m=shift_m, mean_m=mean_m, theta_p=theta_p, kappa_p=kappa_p, beta1_p=beta1_p, beta2_p=beta2_p,
-                         theta_m=theta_m, kappa_m=kappa_m, beta1_m=beta1_m, beta2_m=beta2_m)
+    block = params_block_of(locals())
     eng = get_engine(int(nb_path))
     rng_seed, call_id = next_rng_call(seed)
     fields, stats = eng.price_hawkesjd_chain_tilted_cond_greeks(ch, block, int(nb_steps_per_year), rng_seed, call_id, ch["gammas"],
@@ -1229,12 +1209,7 @@ def hawkesjd_mc_chain_greeks_conditional_with_risk_premia(ttms: np.ndarray, forw
                                                           recenter_forward: bool = False, return_stats: bool = False, **kwargs) -> dict:
     """hawkesjd_mc_chain_greeks_conditional_with_risk_premia_gammas at ONE gamma, so the two agree bit for bit: its dict.  kwargs:
     the model parameters (and variable_type=, comm=, devices=, wrt=) of that function."""
-    if risk_premia_gamma is None:
-        raise ValueError("risk_premia_gamma must be set for the risk-premia pricer")
-    return hawkesjd_mc_chain_greeks_conditional_with_risk_premia_gammas(
-        ttms=ttms, forwards=forwards, discfactors=discfactors, strikes_ttms=strikes_ttms, optiontypes_ttms=optiontypes_ttms,
-        risk_premia_gammas=[risk_premia_gamma], nb_path=nb_path, nb_steps_per_year=nb_steps_per_year, seed=seed,
-        recenter_forward=recenter_forward, return_stats=return_stats, **kwargs)[0]
+    return _at_one_gamma(hawkesjd_mc_chain_greeks_conditional_with_risk_premia_gammas, locals())[0]
 
 
 def _model_kwargs(params: HawkesJDParams) -> Dict[str, Any]:
@@ -1344,7 +1319,7 @@ def hawkesjd_mc_chain_pricer_with_risk_premia_gammas_many(params_list: Sequence[
                                                           bool(recenter_forward))
     if not return_forwards:
         return [(prices, stderrs) for prices, stderrs, _ in out]
-    return [(prices, stderrs, [(st[:, 0].copy(), st[:, 2].copy(), st) for st in stats]) for prices, stderrs, stats in out]
+    return [(prices, stderrs, forwards_triples(stats)) for prices, stderrs, stats in out]
 
 
 def _broadcast(v, nb_path: int, fill) -> np.ndarray:
@@ -1379,9 +1354,7 @@ def hawkesjd_terminal_on_engine(ttm: float, x0: np.ndarray, lambda_p0: np.ndarra
     x0 = _broadcast(x0, nb_path, np.zeros)
     lambda_p0 = _broadcast(lambda_p0, nb_path, np.ones)
     lambda_m0 = _broadcast(lambda_m0, nb_path, np.ones)
-    block = params_block(lambda_p=0.0, lambda_m=0.0, mu=mu, sigma=sigma, shift_p=shift_p, mean_p=mean_p, shift_m=shift_m,
-                         mean_m=mean_m, theta_p=theta_p, kappa_p=kappa_p, beta1_p=beta1_p, beta2_p=beta2_p, theta_m=theta_m,
-                         kappa_m=kappa_m, beta1_m=beta1_m, beta2_m=beta2_m)
+    block = params_block_of(dict(locals(), lambda_p=0.0, lambda_m=0.0))
     nb_steps, dt = (time_grid_steps(ttm=ttm, nb_steps_per_year=nb_steps_per_year) if nb_steps is None
                     else (int(nb_steps), float(ttm) / int(nb_steps)))
     rng_seed, call_id = next_rng_call(seed)

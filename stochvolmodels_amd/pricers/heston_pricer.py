@@ -23,7 +23,7 @@ from ..mc_chain import (chain_shaped, check_many_args, many_job_chunks, many_job
 from ..mc_greeks import HESTON_GREEK_PARAMS, check_greeks_request, greeks_bumps, greeks_job_table, greeks_shaped
 from ..utils.calibration import ImpliedVolObjective, chain_calibration_weights, minimize_slsqp
 from ..utils.config import VariableType
-from ..utils.funcs import next_rng_call, set_time_grid, time_grid_steps, timer
+from ..utils.funcs import chain_step_grid, next_rng_call, set_time_grid, time_grid_steps, timer
 from ..analytic import AnalyticGrid, chain_prices_from_sums, chain_sums
 from ..utils import mgf_pricer as mgfp
 from .logsv_pricer import (_broadcast_state, check_conditional_request, check_conditional_sens_expiries, conditional_greeks_shaped,
@@ -544,11 +544,7 @@ def heston_mc_chain_pricer(ttms: np.ndarray, forwards: np.ndarray, discfactors: 
         prices, stderrs = eng.price_heston_chain_fused(ch, v0, theta, kappa, rho, volvol, code, nb_steps_per_year, vt_code,
                                                        rng_seed, call_id)
         return chain_shaped(prices, strikes_ttms), chain_shaped(stderrs, strikes_ttms)
-    grids, t0 = [], 0.0
-    for ttm in ttms:
-        nb, dt = time_grid_steps(ttm=ttm - t0, nb_steps_per_year=nb_steps_per_year)
-        grids.append((nb, dt))
-        t0 = ttm
+    grids = list(zip(*chain_step_grid(ttms, nb_steps_per_year)))
     step0 = np.concatenate([[0], np.cumsum([g[0] for g in grids])])
     start = (0.0, v0, 0.0)     # every path's start state (reference :303-305) goes to the first stepping launch as constants
 

@@ -19,14 +19,14 @@ import pandas as pd
 
 from .. import dist as svdist
 from ..data.option_chain import OptionChain, black_ivols_native
-from ..engine import (CMC_SETS_MAX, DeviceRandoms, cond_density_arrays, cond_density_stats_dicts, get_engine, marshalled_chain,
-                      option_type_codes, payoff_finalize, tilted_type_codes)
+from ..engine import (CMC_SETS_MAX, DeviceRandoms, chain_etas, cond_density_arrays, cond_density_stats_dicts, get_engine,
+                      marshalled_chain, option_type_codes, payoff_finalize, tilted_type_codes)
 from ..mc_chain import (chain_shaped, check_many_args, many_job_chunks, many_job_streams, many_jobs_shaped, price_chain_on_engine,
                         variable_type_code)
 from ..mc_greeks import LOGSV_GREEK_PARAMS, check_greeks_request, greeks_bumps, greeks_job_table, greeks_shaped
 from ..utils.calibration import ImpliedVolObjective, chain_calibration_weights, minimize_slsqp
 from ..utils.config import VariableType
-from ..utils.funcs import histogram_series, next_rng_call, set_time_grid, time_grid_steps, timer
+from ..utils.funcs import chain_step_grid, histogram_series, next_rng_call, set_time_grid, time_grid_steps, timer
 from ..analytic import AnalyticGrid, chain_prices_from_sums, chain_sums, device_histograms, device_kdes, device_kdes_weighted, histogram_edges
 from ..utils import mgf_pricer as mgfp
 from .logsv.affine_expansion import ExpansionOrder, _order_code, get_init_conditions_a, note_integrator_flags
@@ -919,11 +919,7 @@ def logsv_mc_chain_pricer(ttms: np.ndarray, forwards: np.ndarray, discfactors: n
             prices, stderrs = eng.price_logsv_chain_fused(ch, v0, theta, kappa1, kappa2, beta, volvol, vol_backbone_etas,
                                                           is_spot_measure, nb_steps_per_year, vt_code, rng_seed, call_id)
             return chain_shaped(prices, strikes_ttms), chain_shaped(stderrs, strikes_ttms)
-    grids, t0 = [], 0.0
-    for ttm in ttms:
-        nb, dt = time_grid_steps(ttm=ttm - t0, nb_steps_per_year=nb_steps_per_year)
-        grids.append((nb, dt))
-        t0 = ttm
+    grids = list(zip(*chain_step_grid(ttms, nb_steps_per_year)))
     return _logsv_mc_chain_on_grids(grids, rng_seed, call_id, comm, ttms, forwards, discfactors, strikes_ttms, optiontypes_ttms,
                                     v0, theta, kappa1, kappa2, beta, volvol, vol_backbone_etas, is_spot_measure, nb_path,
                                     variable_type)
@@ -938,9 +934,14 @@ def check_conditional_request(who: str, variable_type, comm, devices, optiontype
         raise NotImplementedError(f"{who}: variable_type={variable_type}: the conditional estimator prices the log-return only")
     if not is_spot_measure:
         raise NotImplementedError(f"{who}: is_spot_measure=False: the conditional estimator covers the spot measure")
+    refuse_sharded_paths(who, comm, devices)
+    return codes
+
+
+def refuse_sharded_paths(who: str, comm, devices) -> None:
+    """the conditional routes step every path on one GPU"""
     if devices is not None or (comm or svdist.get_default_comm()).world > 1:
         raise NotImplementedError(f"{who}: sharded paths (comm.world > 1, devices=) are not covered")
-    return codes
 
 
 def logsv_mc_chain_pricer_conditional(ttms: np.ndarray, forwards: np.ndarray, discfactors: np.ndarray,
@@ -1012,9 +1013,7 @@ def logsv_mc_chain_greeks_conditional(ttms: np.ndarray, forwards: np.ndarray, di
     values = dict(sigma0=v0, theta=theta, kappa1=kappa1, kappa2=kappa2, beta=beta, volvol=volvol)
     names, h = greeks_bumps("logsv", values, None if isinstance(wrt, str) and wrt == "all" else wrt, rel_bump, bumps)
     check_conditional_sens_expiries(who, ttms)
-    etas = np.asarray(vol_backbone_etas, dtype=np.float64).ravel()
-    if etas.size != len(ttms):
-        raise ValueError("vol_backbone_etas must have one entry per maturity")
+    etas = chain_etas(vol_backbone_etas, len(ttms))
     rows = greeks_job_table("logsv", np.concatenate([[values[k] for k in LOGSV_GREEK_PARAMS], etas]), names, h)
     rng_seed, call_id = next_rng_call(seed)
     ch = marshalled_chain(ttms, forwards, discfactors, strikes_ttms, codes)
@@ -1201,10 +1200,8 @@ def mixture_log_return_pdf(who: str, step_rows, x_grid: np.ndarray, risk_premia_
 
 def one_expiry_grid(ttm: float, nb_steps_per_year: int) -> Tuple[int, float]:
     """(steps, dt) of one expiry from the origin as the fused chain drivers cut it (svmc_chain.hip expiry_grids)"""
-    if int(nb_steps_per_year) <= 0:
-        raise ValueError("nb_steps_per_year must be positive")
-    nb = int(float(ttm) * float(int(nb_steps_per_year))) + 1
-    return nb, (float(ttm) if nb == 1 else float(ttm) / float(nb))
+    nbs, dts = chain_step_grid([ttm], nb_steps_per_year)
+    return nbs[0], dts[0]
 
 
 def logsv_mc_chain_greeks(params: LogSvParams, ttms: np.ndarray, forwards: np.ndarray, discfactors: np.ndarray,
@@ -1306,13 +1303,11 @@ def get_randoms_for_chain_valuation(ttms: np.ndarray, nb_path: int = 100000, nb_
     """host-side fixed randoms, identical to the reference (:1051-1074): a local RandomState(seed) draws, per
     slice, W0 then W1 of shape [nb_steps_i, nb_path]; the global NumPy RNG is untouched."""
     rng = np.random.RandomState(seed)
-    W0s, W1s, dts, t0 = [], [], [], 0.0
-    for ttm in ttms:
-        nb, dt = time_grid_steps(ttm=ttm - t0, nb_steps_per_year=nb_steps_per_year)
+    W0s, W1s = [], []
+    nbs, dts = chain_step_grid(ttms, nb_steps_per_year)
+    for nb in nbs:
         W0s.append(rng.normal(0, 1, size=(nb, nb_path)))
         W1s.append(rng.normal(0, 1, size=(nb, nb_path)))
-        dts.append(dt)
-        t0 = ttm
     return W0s, W1s, dts
 
 
@@ -1337,11 +1332,7 @@ def draw_fixed_randoms_on_device(ttms: np.ndarray, nb_path: int = 100000, nb_ste
     Either way statistically equivalent to, not bit-identical with, the RandomState(seed) arrays of the reference."""
     comm = comm or svdist.get_default_comm()
     offset, n_local = svdist.shard_range(nb_path, comm.rank, comm.world)
-    grids, t0 = [], 0.0
-    for ttm in ttms:
-        nb, dt = time_grid_steps(ttm=ttm - t0, nb_steps_per_year=nb_steps_per_year)
-        grids.append((nb, dt))
-        t0 = ttm
+    grids = list(zip(*chain_step_grid(ttms, nb_steps_per_year)))
     get_engine(n_local, path_offset=offset)               # the library and the device are up before the first launch
     make = DeviceRandoms.drawn_on_device if in_hbm else DeviceRandoms.frozen
     return make([g[0] for g in grids], [g[1] for g in grids], nb_path, n_local, offset, seed)

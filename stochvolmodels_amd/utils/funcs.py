@@ -38,6 +38,23 @@ def time_grid_steps(ttm: float, nb_steps_per_year: int = 360) -> Tuple[int, floa
     return nb_steps, float(ttm) / nb_steps
 
 
+def chain_step_grid(ttms, nb_steps_per_year: int) -> Tuple[List[int], List[float]]:
+    """(nb_steps, dts) per expiry of a chain stepped from the origin, as the fused C drivers cut them (svmc_chain.hip
+    expiry_grids): expiry i takes time_grid_steps of its gap to the expiry before it, at int(nb_steps_per_year).  The grid decides
+    which random numbers a path sees, so every host route that promises the drivers' bits takes it from here
+    (tests/test_step_grid_host.py holds it to the copies it replaced).  ValueError for a non-positive nb_steps_per_year."""
+    spy = int(nb_steps_per_year)
+    if spy <= 0:
+        raise ValueError("nb_steps_per_year must be positive")
+    nbs, dts, t0 = [], [], 0.0
+    for t in np.asarray(ttms, dtype=np.float64).ravel():
+        nb, dt = time_grid_steps(float(t) - t0, spy)
+        nbs.append(nb)
+        dts.append(dt)
+        t0 = float(t)
+    return nbs, dts
+
+
 # ---------------------------------------------------------------------------------------------------
 # seeding.  The reference seeds Numba's hidden per-thread MT19937 (set_seed) and its high-level wrappers
 # expose no seed.  Here the generators are counter-based (Philox4x32-7 keyed by a 64-bit seed and a
